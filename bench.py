@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: leaf_cnn training images/sec on MI355X (BASELINE.json config C2).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full training step of the reference's `srcs/cli/train.py` path on one
@@ -681,11 +681,42 @@ def predict_end_to_end(dev, n_files=4096):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, arrays) -> None:
+    """Device tensors -> out_dir/<name>.npy, float32.  Should they pass DUMP_MAX_BYTES in all, an array larger than
+    its even share is replaced by a fixed, seeded sample of its flattened elements (the same indices in every run)."""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_MAX_BYTES // len(host)
+    for name, a in host.items():
+        if total > DUMP_MAX_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
+
+
+def _positive_int(text: str) -> int:
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"must be at least 1, got {v}")
+    return v
+
+
+def _nonnegative_int(text: str) -> int:
+    v = int(text)
+    if v < 0:
+        raise argparse.ArgumentTypeError(f"must be at least 0, got {v}")
+    return v
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=_positive_int, default=30, help="timed training steps (at least 1)")
+    ap.add_argument("--warmup", type=_nonnegative_int, default=10)
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (weak scaling)")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="f32 = BASELINE configs[1] (the headline line, with the bf16 step as a second mode "
@@ -695,7 +726,12 @@ def main() -> None:
     ap.add_argument("--no-augment", action="store_true", help="skip the augmentation-pass measurement")
     ap.add_argument("--no-inference", action="store_true", help="skip the forward-only measurement")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end Augmentation.py measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline step returned in its last timed step (probabilities, per-sample "
+                         "loss) and the parameters it left as DIR/<name>.npy, float32, rank 0")
     args = ap.parse_args()
+    if args.dump_outputs is not None:
+        Path(args.dump_outputs).mkdir(parents=True, exist_ok=True)   # a bad path fails before the GPU work
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -755,7 +791,8 @@ def main() -> None:
 
     def timed_train(steps, warmup):
         """`warmup` untimed + exactly `steps` timed training steps between barrier + synchronize
-        pairs; returns (seconds, max over ranks; final mean loss)."""
+        pairs; returns (seconds, max over ranks; final mean loss; the last step's probs and per-sample
+        loss — device tensors the next step overwrites when it replays the HIP graph)."""
         nonlocal step
         for _ in range(warmup):
             model.train_step(x, y, lr_at(step), **step_kw)
@@ -766,7 +803,7 @@ def main() -> None:
         timer.enabled = True
         t0 = time.perf_counter()
         for _ in range(steps):
-            _probs, loss = model.train_step(x, y, lr_at(step), **step_kw)
+            probs, loss = model.train_step(x, y, lr_at(step), **step_kw)
             step += 1
         torch.cuda.synchronize()
         if dist is not None:
@@ -780,7 +817,7 @@ def main() -> None:
         fl = float(loss.mean())
         if not math.isfinite(fl):
             sys.exit(f"bench.py: non-finite loss {fl}")
-        return sec, fl
+        return sec, fl, probs, loss
 
     def bf16_report(sec, steps, fl, ksteps):
         """The mixed-precision step (BASELINE configs[3]'s per-GPU work): whole-step rate, and for
@@ -858,7 +895,10 @@ def main() -> None:
     kern_f32 = None
     if args.dtype == "bf16":
         model.set_training_dtype("bf16")
-    elapsed, final_loss = timed_train(args.steps, args.warmup)
+    elapsed, final_loss, last_probs, last_loss = timed_train(args.steps, args.warmup)
+    if args.dump_outputs is not None and rank == 0:
+        # before anything else runs a step: the graph's output buffers and the parameters are the last timed step's
+        dump_outputs(Path(args.dump_outputs), {"probs": last_probs, "loss": last_loss, "params": model.flat_p})
     timer.records.clear()
     ksteps = kernel_pass()
     if args.dtype == "bf16":
@@ -869,7 +909,7 @@ def main() -> None:
         if not args.no_bf16:
             # second mode: the same step on bf16 storage (its own warm-up: other kernels, other buffers)
             model.set_training_dtype("bf16")
-            sec16, fl16 = timed_train(args.steps, min(args.warmup, 5))
+            sec16, fl16, _probs16, _loss16 = timed_train(args.steps, min(args.warmup, 5))
             timer.records.clear()
             ksteps16 = kernel_pass()
             bf16 = bf16_report(sec16, args.steps, fl16, ksteps16)
