@@ -63,6 +63,17 @@ def _bn_layers(widths: List[int]):
     return out
 
 
+def _weight_names(specs, use_norm: bool) -> List[str]:
+    """get_weights() order: normalization, then every trainable tensor in creation order with
+    each BN layer's moving statistics after its beta (keras' trainable + non-trainable order)."""
+    names = ["input_norm.mean", "input_norm.variance"] if use_norm else []
+    for name, _s, _k in specs:
+        names.append(name)
+        if name.endswith(".beta"):
+            names += [name[:-5] + ".moving_mean", name[:-5] + ".moving_variance"]
+    return names
+
+
 class Normalization:
     """keras.layers.Normalization(axis=-1) stand-in: per-channel mean/variance, adapt()."""
 
@@ -1070,18 +1081,7 @@ class LeafCNN:
 
     # ------------------------------------------------------------- weights
     def weight_names(self) -> List[str]:
-        names = []
-        if self.norm is not None:
-            names += ["input_norm.mean", "input_norm.variance"]
-        bn_done = set()
-        for name, _s, _k in self.specs:
-            names.append(name)
-            if name.endswith(".beta"):
-                base = name[:-5]
-                if base not in bn_done:
-                    bn_done.add(base)
-                    names += [base + ".moving_mean", base + ".moving_variance"]
-        return names
+        return _weight_names(self.specs, self.norm is not None)
 
     def get_weights(self) -> List[np.ndarray]:
         """All weights (trainable + BN moving statistics + normalization) as host arrays in
@@ -1150,12 +1150,19 @@ class LeafCNN:
                 "drop_block": self.drop_block, "drop_top": self.drop_top, "l2_reg": self.l2_reg,
                 "separable": False, "augment": self.augment, "use_se": self.use_se}
 
-    def save(self, path) -> None:
+    def save(self, path, format: str = "npz") -> None:
         """`leaf_cnn.keras`: a zip with config.json / metadata.json (keras-v3 member names) and
-        model.weights.npz (authoritative here; HDF5 needs h5py, which this image lacks)."""
+        model.weights.npz (the default, what `train` writes), or with format="keras" the Keras 3
+        layout (Functional config.json + model.weights.h5, model/keras_format.py)."""
+        if format not in ("npz", "keras"):
+            raise ValueError(f"save: format must be 'npz' or 'keras', got {format!r}")
         path = Path(path)
         path.parent.mkdir(parents=True, exist_ok=True)
         names = self.weight_names()
+        if format == "keras":
+            from . import keras_format
+            keras_format.write_archive(path, self.config(), names, self.get_weights())
+            return
         arrays = {f"{i:03d}:{n}": a for i, (n, a) in enumerate(zip(names, self.get_weights()))}
         import io
         buf = io.BytesIO()
@@ -1171,9 +1178,9 @@ class LeafCNN:
 
 
 def load_model(path) -> LeafCNN:
-    """Counterpart of keras.models.load_model for files written by LeafCNN.save.  A Keras-written
-    `.keras` archive holds model.weights.h5 (HDF5; this image has no h5py) and is refused with a
-    ValueError that says so — as is anything else that is not this package's npz archive."""
+    """Counterpart of keras.models.load_model: reads this package's npz archive (LeafCNN.save) and
+    Keras 3 archives of the reference's leaf_cnn (config.json + model.weights.h5, read by
+    model/keras_format.py).  Anything else is refused with a ValueError."""
     import io
     path = Path(path)
     if not zipfile.is_zipfile(path):
@@ -1182,9 +1189,11 @@ def load_model(path) -> LeafCNN:
         members = set(z.namelist())
         if "model.weights.npz" not in members:
             if "model.weights.h5" in members:
-                raise ValueError(f"{path}: Keras-written .keras archive (model.weights.h5, HDF5): not "
-                                 "readable here — this backend stores model.weights.npz; retrain or "
-                                 "convert with weight_names()/set_weights() (INTEGRATION.md)")
+                from . import keras_format
+                hp, _names, weights = keras_format.read_archive(path)
+                model = LeafCNN(**hp)
+                model.set_weights(weights)
+                return model
             raise ValueError(f"{path}: unsupported .keras archive: expected model.weights.npz or "
                              f"model.weights.h5, found {sorted(members)}")
         for need in ("config.json", "metadata.json"):
