@@ -174,6 +174,34 @@ int lf_inclusive_mask_u8(const uint8_t* rgb, uint8_t* mask, int n, int h, int w,
                          int green_hi, const uint16_t* kq15, void* workspace, size_t ws_bytes,
                          lf_stream_t stream);
 
+/* make_mask (srcs/transform/filters/mask.py:548-582) for the default strategy ("inclusive"): working-image
+ * upscale (cv2.resize INTER_CUBIC, :29-50), the inclusive candidate (lf_inclusive_mask_u8), _postprocess_mask
+ * (pcv.fill, close, open, largest external contour, filled polygon, :53-69), the Otsu fallback of the HSV
+ * channel when no contour of area > 1 exists (:395-411), the brown-region extension (:335-392) and the nearest
+ * resize of the mask back to the input size (:526-545).  GrabCut / shadow refinements are not part of it.
+ * rgb [N,H,W,3] -> mask [N,H,W] 0 / 255; contour [N,cap,2] int32 (x, y) of the largest external contour of the
+ * final mask, in input coordinates (float32(p) / float32(scale), truncated, when rescale); counts [N] = its TRUE
+ * number of points (0: no contour) — when counts[i] > cap only the first cap points were stored and the caller
+ * must run image i again with a larger cap; flags [N]: bit 0 the fallback mask was taken, bit 2 a step bound was
+ * hit (a bug: treat as an error).  wh x ww: the working size (H x W when rescale == 0).  The working image must
+ * fit one workgroup's LDS (four bit planes, 140 KiB; square working images up to 519 x 519): larger sizes are
+ * rejected before any launch.  kq15: HOST pointer to
+ * the 15 Q8.8 taps of GaussianBlur(gray, (15, 15), 0).  Parity unpinned (no cv2 / PlantCV / skimage). */
+typedef struct {
+    int green_lo, green_hi;            /* green_hue_range (config.yaml:10) */
+    int fill_size, morph_kernel;       /* config.yaml:14-15 */
+    int hsv_channel;                   /* hsv_channel_for_mask: 0 h, 1 s, 2 v */
+    int use_lab_brown;                 /* brown predicate: 0 HSV, 1 L*a*b* */
+    int brown_hue_lo, brown_hue_hi, brown_s_min, brown_v_max;
+    int lab_a_min, lab_b_min;
+    int brown_min_area_px, brown_morph_kernel;
+} lf_make_mask_params;
+size_t lf_make_mask_workspace(int n, int h, int w, int wh, int ww);
+int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t* counts, int32_t* flags,
+                    int n, int h, int w, int wh, int ww, int rescale, double scale,
+                    const lf_make_mask_params* params, int cap, const uint16_t* kq15, void* workspace,
+                    size_t ws_bytes, lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* JPEG encode (the file Pillow's Image.save(path, quality=q) writes)          */
 /* ------------------------------------------------------------------------- */

@@ -1292,3 +1292,690 @@ int lf_inclusive_mask_u8(const uint8_t* rgb, uint8_t* mask, int n, int h, int w,
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// make_mask (srcs/transform/filters/mask.py:548-582) for the default strategy (config.yaml:6 "inclusive").
+// PARITY UNPINNED like the rest of this file (no cv2 / PlantCV / skimage here).  Readings, step by step:
+//  * working image (mask.py:29-50): cv2.resize(INTER_CUBIC) on uint8 as resize.cpp's fixed-point path reads:
+//    scale = 1 / (dst / src) in double, fx = (float)((dx + 0.5) * scale - 0.5), sx = floor(fx), fx -= sx, the
+//    A = -0.75 weights of interpolateCubic in float, each rounded (cvRound) to Q11, replicated borders, an int
+//    horizontal pass, vertical (sum + (1 << 21)) >> 22 saturated to uint8.  That is the scalar VResizeCubic; an
+//    OpenCV build whose SIMD vertical pass (VResizeCubicVec_32s8u) converts to float and rounds instead may differ
+//    from it by 1 in a few pixels — unverified either way.
+//  * candidate: lf_inclusive_mask_u8 on the working image, unchanged.
+//  * _postprocess_mask (:53-69): pcv.fill = skimage remove_small_objects (4-connected components of area <
+//    fill_size removed); MORPH_CLOSE then MORPH_OPEN (ellipse morph_kernel); findContours(RETR_EXTERNAL,
+//    CHAIN_APPROX_SIMPLE) + max contourArea; drawContours(filled).  A component is external when the
+//    background pixel left of its first raster pixel is 4-connected to the (zero-padded) frame.  Its outer border
+//    is traced Suzuki-Abe from that pixel exactly as OpenCV's icvFetchContour walks it (one lane per component,
+//    on the bit plane in LDS), the area is the shoelace of the compressed polygon.  Equal areas: OpenCV lists the
+//    external contours in reverse discovery order and max() keeps the first, so the LAST discovered (latest
+//    first pixel in raster order) wins — a reading, not checked against cv2.  The filled polygon of an outer
+//    border is the component plus everything it encloses: computed as the complement of the 4-connected flood
+//    of the frame around that component alone.
+//  * selection (:143-155): no contour or contourArea <= 1 -> fallback (:395-411): Otsu (thresh.cpp
+//    getThreshVal_Otsu_8u, double, first maximum) of PlantCV's HSV channel, `> t`, the same post-processing.
+//  * brown extension (:335-392): dilate(20 x 20 ellipse, anchor (10, 10), iterations=2) search area, the HSV or
+//    L*a*b* brown predicate, open + close (brown_morph_kernel), 8-connected components of area >=
+//    brown_min_area_px ORed in (no re-fill), the largest external contour of the result.
+//  * back to the input size (:526-545): INTER_NEAREST min(floor(d * (1 / (dst / src))), src - 1); the contour
+//    (float32(p) / float32(s)) truncated.  Neither when the scale is 1.
+// Every sequential walk (border following, union-find, flood) has a hard step bound; hitting one sets bit 2 of
+// the image's flag word and the host reports an error.
+// ===========================================================================
+namespace {
+
+constexpr int kMaskT = 256;
+constexpr int kSeMax = 32;
+constexpr int kFlagFallback = 1, kFlagBound = 4;
+
+struct SeRows {   // a structuring element as per-row column ranges relative to its anchor
+    int k, ay;
+    signed char lo[kSeMax], hi[kSeMax];   // lo > hi: empty row
+};
+
+struct MaskArgs {
+    int fill_size, channel;   // channel: 0 H, 1 S, 2 V of PlantCV's rgb2gray_hsv
+    int use_lab, hue_lo, hue_hi, s_min, v_max, a_min, b_min, brown_min_area;
+    SeRows se_morph, se_search, se_brown;
+};
+
+struct Run {
+    unsigned short x0, x1, y, pad;
+};
+
+__device__ __forceinline__ void cubic_q11(float x, int* c) {   // interpolateCubic, then saturate_cast<short>(c * 2048)
+    const float A = -0.75f;
+    const float c0 = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
+    const float c1 = ((A + 2) * x - (A + 3)) * x * x + 1;
+    const float c2 = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
+    const float c3 = 1.f - c0 - c1 - c2;
+    c[0] = (int)rintf(c0 * 2048.f);
+    c[1] = (int)rintf(c1 * 2048.f);
+    c[2] = (int)rintf(c2 * 2048.f);
+    c[3] = (int)rintf(c3 * 2048.f);
+}
+
+__global__ __launch_bounds__(kBlock) void cubic_resize_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                              int n, int h, int w, int oh, int ow, double scale_y,
+                                                              double scale_x) {
+    const long total = (long)n * oh * ow;
+    for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < total; p += (long)gridDim.x * kBlock) {
+        const int dx = (int)(p % ow);
+        const long t = p / ow;
+        const int dy = (int)(t % oh);
+        const size_t img = (size_t)(t / oh);
+        float fx = (float)(__dsub_rn(__dmul_rn(dx + 0.5, scale_x), 0.5));
+        float fy = (float)(__dsub_rn(__dmul_rn(dy + 0.5, scale_y), 0.5));
+        const int sx = (int)floorf(fx), sy = (int)floorf(fy);
+        fx -= (float)sx;
+        fy -= (float)sy;
+        int ax[4], ay[4];
+        cubic_q11(fx, ax);
+        cubic_q11(fy, ay);
+        int xs[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xs[k] = clampi(sx - 1 + k, 0, w - 1);
+        const uint8_t* s = src + img * h * w * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            int acc = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const uint8_t* row = s + (size_t)clampi(sy - 1 + r, 0, h - 1) * w * 3 + c;
+                int hs = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hs += (int)row[xs[k] * 3] * ax[k];
+                acc += hs * ay[r];
+            }
+            dst[(size_t)p * 3 + c] = (uint8_t)clampi((acc + (1 << 21)) >> 22, 0, 255);
+        }
+    }
+}
+
+// one workgroup per image: the planes live in LDS, runs / parents / areas in the image's slice of the workspace
+struct Post {
+    unsigned *A, *B, *C, *D;
+    int* rowstart;
+    Run* rn;
+    int* par;
+    int* area;
+    int h, w, wpr, max_runs;
+    int* nruns;    // LDS
+    int* status;   // LDS
+    int* flag;     // LDS [2]
+    unsigned long long* best;   // LDS
+};
+
+__device__ __forceinline__ unsigned valid_bits(const Post& P, int xw) {
+    const int used = (P.w + 31) >> 5;
+    const unsigned last = (P.w & 31) ? ((1u << (P.w & 31)) - 1u) : 0xffffffffu;
+    return xw < used - 1 ? 0xffffffffu : (xw == used - 1 ? last : 0u);
+}
+
+__device__ __forceinline__ bool bit_at(const Post& P, const unsigned* pl, int x, int y) {
+    if ((unsigned)x >= (unsigned)P.w || (unsigned)y >= (unsigned)P.h) return false;
+    return (pl[y * P.wpr + (x >> 5)] >> (x & 31)) & 1u;
+}
+
+// dst = dilate / erode(src) by the element; pixels outside the image never win
+__device__ void morph_se(const Post& P, const unsigned* src, unsigned* dst, const SeRows& se, bool erode) {
+    const int h = P.h, wpr = P.wpr;
+    for (int i = threadIdx.x; i < h * wpr; i += kMaskT) {
+        const int y = i / wpr, xw = i - y * wpr;
+        unsigned out = 0;
+        for (int r = 0; r < se.k; ++r) {
+            const int yy = y + r - se.ay, lo = se.lo[r], hi = se.hi[r];
+            if (yy < 0 || yy >= h || lo > hi) continue;
+            auto word = [&](int x) -> unsigned {
+                if (x < 0 || x >= wpr) return 0u;
+                const unsigned v = src[yy * wpr + x];
+                return erode ? ~v & valid_bits(P, x) : v;
+            };
+            const unsigned long long cur = word(xw), prev = word(xw - 1), next = word(xw + 1);
+            const unsigned long long hiw = (next << 32) | cur, low = (cur << 32) | prev;
+            for (int j = lo; j <= hi; ++j) out |= (unsigned)(j >= 0 ? hiw >> j : low >> (32 + j));
+        }
+        dst[i] = (erode ? ~out : out) & valid_bits(P, xw);
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ int ld_par(int* p, int x) {
+    return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ int bfind(const Post& P, int x) {
+    for (int i = 0; i <= P.max_runs; ++i) {
+        const int px = ld_par(P.par, x);
+        if (px == x) return x;
+        x = px;
+    }
+    atomicOr(P.status, kFlagBound);
+    return x;
+}
+__device__ void bunion(const Post& P, int a, int b) {
+    for (int i = 0; i <= P.max_runs; ++i) {
+        a = bfind(P, a);
+        b = bfind(P, b);
+        if (a == b) return;
+        if (a > b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = atomicMin(P.par + b, a);   // roots only move to a smaller index: a root is its first run
+        if (old == b) return;
+        b = old;
+    }
+    atomicOr(P.status, kFlagBound);
+}
+
+// runs of `src`, their connected components (par[k] = root = the component's first run in raster order) and areas
+__device__ void label_runs(const Post& P, const unsigned* src, bool conn8) {
+    const int h = P.h, w = P.w, wpr = P.wpr;
+    for (int y = threadIdx.x; y < h; y += kMaskT) {
+        int c = 0, x = 0, s, e;
+        while (next_run(src + y * wpr, w, x, s, e)) {
+            ++c;
+            x = e + 1;
+        }
+        P.rowstart[y + 1] = c;
+    }
+    if (threadIdx.x == 0) P.rowstart[0] = 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int y = 0; y < h; ++y) P.rowstart[y + 1] += P.rowstart[y];
+        *P.nruns = P.rowstart[h];
+    }
+    __syncthreads();
+    for (int y = threadIdx.x; y < h; y += kMaskT) {
+        int k = P.rowstart[y], x = 0, s, e;
+        while (next_run(src + y * wpr, w, x, s, e)) {
+            P.rn[k] = Run{(unsigned short)s, (unsigned short)e, (unsigned short)y, 0};
+            P.par[k] = k;
+            P.area[k] = 0;
+            ++k;
+            x = e + 1;
+        }
+    }
+    __threadfence();
+    __syncthreads();
+    const int g = conn8 ? 1 : 0;
+    for (int y = 1 + threadIdx.x; y < h; y += kMaskT) {
+        int a = P.rowstart[y - 1], b = P.rowstart[y];
+        const int a_end = P.rowstart[y], b_end = P.rowstart[y + 1];
+        while (a < a_end && b < b_end) {
+            const Run ra = P.rn[a], rb = P.rn[b];
+            if ((int)ra.x0 <= (int)rb.x1 + g && (int)ra.x1 + g >= (int)rb.x0) bunion(P, a, b);
+            if (ra.x1 < rb.x1) ++a;
+            else ++b;
+        }
+    }
+    __threadfence();
+    __syncthreads();
+    const int nr = *P.nruns;
+    for (int k = threadIdx.x; k < nr; k += kMaskT) {
+        const int root = bfind(P, k);
+        atomicAdd(P.area + root, (int)P.rn[k].x1 - (int)P.rn[k].x0 + 1);
+    }
+    __threadfence();
+    __syncthreads();
+    for (int k = threadIdx.x; k < nr; k += kMaskT) P.par[k] = bfind(P, k);   // flatten: par[k] is the root
+    __threadfence();
+    __syncthreads();
+}
+
+// dst = the runs whose component passes keep(root); each thread owns whole rows
+template <typename F>
+__device__ void paint_runs(const Post& P, unsigned* dst, bool clear, F keep) {
+    for (int y = threadIdx.x; y < P.h; y += kMaskT) {
+        unsigned* row = dst + y * P.wpr;
+        if (clear)
+            for (int i = 0; i < P.wpr; ++i) row[i] = 0u;
+        for (int k = P.rowstart[y]; k < P.rowstart[y + 1]; ++k) {
+            if (!keep(ld_par(P.par, k))) continue;
+            const Run r = P.rn[k];
+            for (int x = r.x0; x <= (int)r.x1;) {
+                const int b = x & 31, len = min(32 - b, (int)r.x1 - x + 1);
+                row[x >> 5] |= (len == 32 ? 0xffffffffu : ((1u << len) - 1u)) << b;
+                x += len;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// D = the background 4-connected to the zero-padded frame around `bar`
+__device__ void flood_outer(const Post& P, const unsigned* bar, unsigned* D) {
+    const int h = P.h, w = P.w, wpr = P.wpr;
+    for (int i = threadIdx.x; i < h * wpr; i += kMaskT) {
+        const int y = i / wpr, xw = i - y * wpr;
+        unsigned s = 0;
+        if (y == 0 || y == h - 1) s = 0xffffffffu;
+        if (xw == 0) s |= 1u;
+        if (xw == (w - 1) >> 5) s |= 1u << ((w - 1) & 31);
+        D[i] = s & ~bar[i] & valid_bits(P, xw);
+    }
+    if (threadIdx.x == 0) P.flag[0] = P.flag[1] = 0;
+    __syncthreads();
+    for (int it = 0;; ++it) {
+        int local = 0;
+        for (int i = threadIdx.x; i < h * wpr; i += kMaskT) {
+            const int y = i / wpr, xw = i - y * wpr;
+            const unsigned m = ~bar[i] & valid_bits(P, xw), d = D[i];
+            unsigned g = d | (d << 1) | (d >> 1);
+            if (xw > 0) g |= D[i - 1] >> 31;
+            if (xw < wpr - 1) g |= D[i + 1] << 31;
+            if (y > 0) g |= D[i - wpr];
+            if (y < h - 1) g |= D[i + wpr];
+            g &= m;
+            g |= ((m + g) ^ m) & m;   // along the runs of m inside the word, upwards ...
+            const unsigned rm = __builtin_bitreverse32(m), rg = __builtin_bitreverse32(g);
+            g |= __builtin_bitreverse32(((rm + rg) ^ rm) & rm);   // ... and downwards
+            if (g != d) {
+                D[i] = g;   // monotone: a neighbour reading the old or the new word is fine
+                local = 1;
+            }
+        }
+        if (local) P.flag[it & 1] = 1;
+        __syncthreads();
+        const int changed = P.flag[it & 1];
+        if (threadIdx.x == 0) P.flag[(it + 1) & 1] = 0;
+        __syncthreads();
+        if (!changed) break;
+        if (it > h * w) {
+            if (threadIdx.x == 0) atomicOr(P.status, kFlagBound);
+            break;
+        }
+    }
+}
+
+// OpenCV icvFetchContour, CHAIN_APPROX_SIMPLE, outer border from its first raster pixel (x0, y0).  Returns the
+// number of points; area2 = twice contourArea.  out (optional): the first `cap` points, divided by fs if rescale.
+__device__ int trace_outer(const Post& P, const unsigned* pl, int x0, int y0, long long& area2, int* out, int cap,
+                           bool rescale, float fs) {
+    const int DX[8] = {1, 1, 0, -1, -1, -1, 0, 1};
+    const int DY[8] = {0, -1, -1, -1, 0, 1, 1, 1};
+    int npts = 0, fx = 0, fy = 0, px = 0, py = 0;
+    long long a2 = 0;
+    auto emit = [&](int x, int y) {
+        if (out && npts < cap) {
+            out[2 * npts] = rescale ? (int)__fdiv_rn((float)x, fs) : x;
+            out[2 * npts + 1] = rescale ? (int)__fdiv_rn((float)y, fs) : y;
+        }
+        if (npts == 0) {
+            fx = x;
+            fy = y;
+        } else {
+            a2 += (long long)px * y - (long long)py * x;
+        }
+        px = x;
+        py = y;
+        ++npts;
+    };
+    int s = 4;
+    do {
+        s = (s - 1) & 7;
+    } while (!bit_at(P, pl, x0 + DX[s], y0 + DY[s]) && s != 4);
+    if (s == 4) {   // single-pixel component
+        emit(x0, y0);
+        area2 = 0;
+        return 1;
+    }
+    const int x1 = x0 + DX[s], y1 = y0 + DY[s];
+    int x3 = x0, y3 = y0, prev_s = s ^ 4;
+    const long long bound = 4ll * P.h * P.w + 16;
+    for (long long step = 0;; ++step) {
+        int k = s + 1;
+        for (; k < 16; ++k)
+            if (bit_at(P, pl, x3 + DX[k & 7], y3 + DY[k & 7])) break;
+        if (k == 16 || step > bound) {
+            atomicOr(P.status, kFlagBound);
+            break;
+        }
+        s = k & 7;
+        if (s != prev_s) {
+            emit(x3, y3);
+            prev_s = s;
+        }
+        const int x4 = x3 + DX[s], y4 = y3 + DY[s];
+        if (x4 == x0 && y4 == y0 && x3 == x1 && y3 == y1) break;
+        x3 = x4;
+        y3 = y4;
+        s = (s + 4) & 7;
+    }
+    a2 += (long long)px * fy - (long long)py * fx;
+    area2 = a2 < 0 ? -a2 : a2;
+    return npts;
+}
+
+// largest external contour of P.A (labels P.A, leaves D = the outer background).  Returns the winning root or -1
+// and its doubled area.
+__device__ int largest_external(const Post& P, long long& area2) {
+    label_runs(P, P.A, true);
+    flood_outer(P, P.A, P.D);
+    if (threadIdx.x == 0) *P.best = 0ull;
+    __syncthreads();
+    const int nr = *P.nruns;
+    for (int k = threadIdx.x; k < nr; k += kMaskT) {
+        if (P.par[k] != k) continue;
+        const Run r = P.rn[k];
+        if (r.x0 > 0 && !bit_at(P, P.D, r.x0 - 1, r.y)) continue;   // inside a hole of another component
+        long long a2;
+        trace_outer(P, P.A, r.x0, r.y, a2, nullptr, 0, false, 1.f);
+        atomicMax(P.best, ((unsigned long long)a2 << 32) | (unsigned)(k + 1));   // equal areas: the later one
+    }
+    __syncthreads();
+    const unsigned long long b = *P.best;
+    __syncthreads();
+    area2 = (long long)(b >> 32);
+    return b ? (int)(b & 0xffffffffull) - 1 : -1;
+}
+
+// _postprocess_mask on P.A: fill, close, open, largest contour, its filled polygon back in P.A.  Returns whether a
+// contour exists; area2 = twice its area.
+__device__ bool postprocess(const Post& P, const MaskArgs& a, long long& area2) {
+    label_runs(P, P.A, false);   // pcv.fill: 4-connected components below fill_size go
+    paint_runs(P, P.A, true, [&](int root) { return P.area[root] >= a.fill_size; });
+    morph_se(P, P.A, P.B, a.se_morph, false);   // MORPH_CLOSE
+    morph_se(P, P.B, P.A, a.se_morph, true);
+    morph_se(P, P.A, P.B, a.se_morph, true);    // MORPH_OPEN
+    morph_se(P, P.B, P.A, a.se_morph, false);
+    const int best = largest_external(P, area2);
+    if (best < 0) return false;
+    paint_runs(P, P.B, true, [&](int root) { return root == best; });   // drawContours(filled)
+    flood_outer(P, P.B, P.D);
+    for (int i = threadIdx.x; i < P.h * P.wpr; i += kMaskT) P.A[i] = ~P.D[i] & valid_bits(P, i % P.wpr);
+    __syncthreads();
+    return true;
+}
+
+struct PixelTabs {
+    int sdiv[256], hdiv[256];
+    uint16_t gam[256], cbr[kLabCbrtSize];
+};
+
+__device__ __forceinline__ void hsv_px(const PixelTabs& T, int r, int g, int b, int& hh, int& s, int& v) {
+    v = max(r, max(g, b));
+    const int vmin = min(r, min(g, b)), diff = v - vmin;
+    const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
+    s = (__mul24(diff, T.sdiv[v]) + (1 << 11)) >> 12;
+    hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
+    hh = (__mul24(hh, T.hdiv[diff]) + (1 << 11)) >> 12;
+    hh += hh < 0 ? 180 : 0;
+}
+
+// PlantCV's rgb2gray_hsv converts with COLOR_BGR2HSV although it is handed RGB: H is taken from the swapped pixel.
+// S and V do not change under an R / B swap, so the default channel "s" is unaffected by that mix-up.
+__device__ __forceinline__ int channel_px(const PixelTabs& T, const uint8_t* p, int channel) {
+    int hh, s, v;
+    hsv_px(T, p[2], p[1], p[0], hh, s, v);
+    return channel == 0 ? hh : (channel == 1 ? s : v);
+}
+
+__device__ __forceinline__ bool brown_px(const PixelTabs& T, const uint8_t* p, const MaskArgs& a) {
+    const int r = p[0], g = p[1], b = p[2];
+    if (a.use_lab) {
+        const int R = T.gam[r], G = T.gam[g], B = T.gam[b];
+        const int fx = T.cbr[(R * 1777 + G * 1541 + B * 778 + 2048) >> 12];
+        const int fy = T.cbr[(R * 871 + G * 2929 + B * 296 + 2048) >> 12];
+        const int fz = T.cbr[(R * 73 + G * 448 + B * 3575 + 2048) >> 12];
+        const int la = clampi((500 * (fx - fy) + 4194304 + 16384) >> 15, 0, 255);
+        const int lb = clampi((200 * (fy - fz) + 4194304 + 16384) >> 15, 0, 255);
+        return la >= a.a_min && lb >= a.b_min;
+    }
+    int hh, s, v;
+    hsv_px(T, r, g, b, hh, s, v);
+    return hh >= a.hue_lo && hh <= a.hue_hi && s >= a.s_min && v <= a.v_max;
+}
+
+// plane[word] = pred(pixel) for every pixel of the working image (and the search plane, when given)
+template <typename F>
+__device__ void build_plane(const Post& P, unsigned* dst, F pred) {
+    for (int i = threadIdx.x; i < P.h * P.wpr; i += kMaskT) {
+        const int y = i / P.wpr, xw = i - y * P.wpr;
+        unsigned m = 0;
+        const int xe = min(32, P.w - 32 * xw);
+        for (int b = 0; b < xe; ++b)
+            if (pred(y, 32 * xw + b)) m |= 1u << b;
+        dst[i] = m;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kMaskT) void make_mask_post_kernel(
+    const uint8_t* __restrict__ rgbw, const uint8_t* __restrict__ cand, const uint16_t* __restrict__ lab_tabs,
+    Run* __restrict__ runs, int* __restrict__ parent, int* __restrict__ area, int runs_per_image, int h, int w,
+    int wpr, int oh, int ow, int rescale, double ify, double ifx, float fscale, MaskArgs a,
+    uint8_t* __restrict__ out_mask, int* __restrict__ contour, int* __restrict__ counts, int* __restrict__ flags,
+    int cap) {
+    extern __shared__ unsigned lds_planes[];
+    __shared__ PixelTabs T;
+    __shared__ int s_nruns, s_status, s_flag[2], s_hist[256], s_thresh;
+    __shared__ unsigned long long s_best;
+    const size_t n = blockIdx.x;
+    Post P;
+    const int plane = h * wpr;
+    P.A = lds_planes;
+    P.B = P.A + plane;
+    P.C = P.B + plane;
+    P.D = P.C + plane;
+    P.rowstart = reinterpret_cast<int*>(P.D + plane);
+    P.rn = runs + n * runs_per_image;
+    P.par = parent + n * runs_per_image;
+    P.area = area + n * runs_per_image;
+    P.h = h;
+    P.w = w;
+    P.wpr = wpr;
+    P.max_runs = runs_per_image;
+    P.nruns = &s_nruns;
+    P.status = &s_status;
+    P.flag = s_flag;
+    P.best = &s_best;
+    for (int i = threadIdx.x; i < 256; i += kMaskT) {
+        T.sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
+        T.hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
+        T.gam[i] = lab_tabs[i];
+        s_hist[i] = 0;
+    }
+    for (int i = threadIdx.x; i < kLabCbrtSize; i += kMaskT) T.cbr[i] = lab_tabs[256 + i];
+    if (threadIdx.x == 0) s_status = 0;
+    const uint8_t* img = rgbw + n * (size_t)h * w * 3;
+    const uint8_t* cm = cand + n * (size_t)h * w;
+    __syncthreads();
+
+    build_plane(P, P.A, [&](int y, int x) { return cm[y * w + x] > 0; });
+    long long area2 = 0;
+    const bool found = postprocess(P, a, area2);
+    int flag = 0;
+    if (!found || area2 <= 2) {   // _score_mask == -1: no best mask -> _create_fallback_mask
+        flag |= kFlagFallback;
+        for (int p = threadIdx.x; p < h * w; p += kMaskT) atomicAdd(&s_hist[channel_px(T, img + 3 * p, a.channel)], 1);
+        __syncthreads();
+        if (threadIdx.x == 0) {   // getThreshVal_Otsu_8u
+            const double scale = 1.0 / ((double)h * w);
+            double mu = 0.0;
+            for (int i = 0; i < 256; ++i) mu = __dadd_rn(mu, __dmul_rn((double)i, (double)s_hist[i]));
+            mu = __dmul_rn(mu, scale);
+            double mu1 = 0.0, q1 = 0.0, max_sigma = 0.0;
+            int max_val = 0;
+            for (int i = 0; i < 256; ++i) {
+                const double p_i = __dmul_rn((double)s_hist[i], scale);
+                mu1 = __dmul_rn(mu1, q1);
+                q1 = __dadd_rn(q1, p_i);
+                const double q2 = __dsub_rn(1.0, q1);
+                if (fmin(q1, q2) < (double)FLT_EPSILON || fmax(q1, q2) > __dsub_rn(1.0, (double)FLT_EPSILON)) continue;
+                mu1 = __ddiv_rn(__dadd_rn(mu1, __dmul_rn((double)i, p_i)), q1);
+                const double mu2 = __ddiv_rn(__dsub_rn(mu, __dmul_rn(q1, mu1)), q2);
+                const double d = __dsub_rn(mu1, mu2);
+                const double sigma = __dmul_rn(__dmul_rn(__dmul_rn(q1, q2), d), d);
+                if (sigma > max_sigma) {
+                    max_sigma = sigma;
+                    max_val = i;
+                }
+            }
+            s_thresh = max_val;
+        }
+        __syncthreads();
+        const int t = s_thresh;
+        build_plane(P, P.A, [&](int y, int x) { return channel_px(T, img + 3 * (y * w + x), a.channel) > t; });
+        postprocess(P, a, area2);
+    }
+
+    // _extend_mask_with_brown_regions
+    morph_se(P, P.A, P.B, a.se_search, false);
+    morph_se(P, P.B, P.C, a.se_search, false);
+    build_plane(P, P.B, [&](int y, int x) {
+        return ((P.C[y * wpr + (x >> 5)] >> (x & 31)) & 1u) && brown_px(T, img + 3 * (y * w + x), a);
+    });
+    morph_se(P, P.B, P.C, a.se_brown, true);   // MORPH_OPEN
+    morph_se(P, P.C, P.B, a.se_brown, false);
+    morph_se(P, P.B, P.C, a.se_brown, false);  // MORPH_CLOSE
+    morph_se(P, P.C, P.B, a.se_brown, true);
+    label_runs(P, P.B, true);
+    paint_runs(P, P.A, false, [&](int root) { return P.area[root] >= a.brown_min_area; });
+    const int best = largest_external(P, area2);
+    if (threadIdx.x == 0) {
+        int npts = 0;
+        if (best >= 0) {
+            const Run r = P.rn[best];
+            long long a2;
+            npts = trace_outer(P, P.A, r.x0, r.y, a2, contour + n * (size_t)cap * 2, cap, rescale != 0, fscale);
+        }
+        counts[n] = npts;
+    }
+    __syncthreads();
+    uint8_t* o = out_mask + n * (size_t)oh * ow;
+    for (int p = threadIdx.x; p < oh * ow; p += kMaskT) {
+        const int y = p / ow, x = p - y * ow;
+        int sy = y, sx = x;
+        if (rescale) {
+            sy = min((int)floor(__dmul_rn((double)y, ify)), h - 1);
+            sx = min((int)floor(__dmul_rn((double)x, ifx)), w - 1);
+        }
+        o[p] = (P.A[sy * wpr + (sx >> 5)] >> (sx & 31)) & 1u ? 255 : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) flags[n] = flag | s_status;
+}
+
+// getStructuringElement(MORPH_ELLIPSE, (k, k)) with the default anchor (k / 2, k / 2)
+static SeRows ellipse_rows(int k) {
+    SeRows se{};
+    se.k = k;
+    se.ay = k / 2;
+    const int r = k / 2, c = k / 2;
+    const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
+    for (int i = 0; i < k; ++i) {
+        int j1 = 0, j2 = 0;
+        const int dy = i - r;
+        if (std::abs(dy) <= r) {
+            const int dx = (int)nearbyint(c * std::sqrt((r * r - dy * dy) * inv_r2));
+            j1 = std::max(c - dx, 0);
+            j2 = std::min(c + dx + 1, k);
+        }
+        se.lo[i] = (signed char)(j1 - c);
+        se.hi[i] = (signed char)(j2 - 1 - c);
+    }
+    return se;
+}
+
+constexpr size_t kMaskLdsCap = 140 * 1024;
+
+static size_t make_mask_lds(int wh, int ww) {
+    return (size_t)4 * wh * ((ww + 31) / 32) * 4 + (size_t)(wh + 1) * 4;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lf_make_mask_workspace(int n, int h, int w, int wh, int ww) {
+    if (n <= 0 || h <= 0 || w <= 0 || wh <= 0 || ww <= 0) return 0;
+    const size_t wpx = (size_t)n * wh * ww;
+    const size_t runs = (size_t)n * mask_runs_per_image(wh, ww);
+    // working image, candidate mask, the candidate's own workspace, runs / parents / areas, the L*a*b* tables
+    return up(3 * wpx) + up(wpx) + up(lf_inclusive_mask_workspace(n, wh, ww)) + up(runs * sizeof(Run)) +
+           2 * up(runs * 4) + up((256 + kLabCbrtSize) * sizeof(uint16_t));
+}
+
+int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t* counts, int32_t* flags, int n,
+                    int h, int w, int wh, int ww, int rescale, double scale, const lf_make_mask_params* prm, int cap,
+                    const uint16_t* kq15, void* workspace, size_t ws_bytes, lf_stream_t stream) {
+    LF_REQUIRE(rgb && mask && contour && counts && flags && prm && kq15 && workspace, "lf_make_mask: null buffer");
+    LF_REQUIRE(n > 0 && h > 0 && w > 0 && wh > 0 && ww > 0 && cap > 0, "lf_make_mask: bad dims n=%d %dx%d -> %dx%d cap=%d",
+               n, h, w, wh, ww, cap);
+    LF_REQUIRE(n <= 65535, "lf_make_mask: batch too large for the grid");
+    LF_REQUIRE(rescale || (wh == h && ww == w), "lf_make_mask: without rescaling the working size is the input size");
+    LF_REQUIRE(!rescale || scale > 0.0, "lf_make_mask: scale must be positive");
+    LF_REQUIRE(wh <= 65535 && ww <= 65535, "lf_make_mask: working image too large (%d x %d)", wh, ww);
+    const size_t lds = make_mask_lds(wh, ww);
+    LF_REQUIRE(lds <= kMaskLdsCap,
+               "lf_make_mask: a %d x %d working image needs %zu bytes of LDS for its four bit planes (limit %zu, one "
+               "workgroup per image)", wh, ww, lds, kMaskLdsCap);
+    const int ks[3] = {prm->morph_kernel, 20, prm->brown_morph_kernel};
+    for (int k : ks) LF_REQUIRE(k >= 1 && k <= 31, "lf_make_mask: structuring element size %d outside [1, 31]", k);
+    LF_REQUIRE(prm->hsv_channel >= 0 && prm->hsv_channel <= 2, "lf_make_mask: hsv_channel must be 0, 1 or 2");
+    LF_REQUIRE(ws_bytes >= lf_make_mask_workspace(n, h, w, wh, ww), "lf_make_mask: workspace too small (%zu < %zu)",
+               ws_bytes, lf_make_mask_workspace(n, h, w, wh, ww));
+    LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "lf_make_mask: workspace must be 256-byte aligned");
+    static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(make_mask_post_kernel),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)kMaskLdsCap) == hipSuccess;
+    LF_REQUIRE(lds_ok || lds <= 48 * 1024, "lf_make_mask: could not raise the LDS limit of the mask kernel");
+
+    hipStream_t s = lf::as_stream(stream);
+    const size_t wpx = (size_t)n * wh * ww;
+    const size_t runs = (size_t)n * mask_runs_per_image(wh, ww);
+    uint8_t* work = static_cast<uint8_t*>(workspace);
+    uint8_t* cand = work + up(3 * wpx);
+    uint8_t* incl = cand + up(wpx);
+    const size_t incl_bytes = lf_inclusive_mask_workspace(n, wh, ww);
+    Run* rn = reinterpret_cast<Run*>(incl + up(incl_bytes));
+    int* parent = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(rn) + up(runs * sizeof(Run)));
+    int* area = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(parent) + up(runs * 4));
+    uint16_t* tabs = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(area) + up(runs * 4));
+
+    MaskArgs a{};
+    a.fill_size = prm->fill_size;
+    a.channel = prm->hsv_channel;
+    a.use_lab = prm->use_lab_brown;
+    a.hue_lo = prm->brown_hue_lo;
+    a.hue_hi = prm->brown_hue_hi;
+    a.s_min = prm->brown_s_min;
+    a.v_max = prm->brown_v_max;
+    a.a_min = prm->lab_a_min;
+    a.b_min = prm->lab_b_min;
+    a.brown_min_area = prm->brown_min_area_px;
+    a.se_morph = ellipse_rows(prm->morph_kernel);
+    a.se_search = ellipse_rows(20);
+    a.se_brown = ellipse_rows(prm->brown_morph_kernel);
+
+    static const std::vector<uint16_t> host_tabs = []() {
+        std::vector<uint16_t> t(256 + kLabCbrtSize);
+        lab_tables_host(t.data());
+        return t;
+    }();
+    if (hipMemcpyAsync(tabs, host_tabs.data(), host_tabs.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s) !=
+        hipSuccess) {
+        lf::set_error("lf_make_mask: table upload failed");
+        return LF_ERR_LAUNCH;
+    }
+    const uint8_t* src = rgb;
+    if (rescale) {
+        const double sy = 1.0 / ((double)wh / h), sx = 1.0 / ((double)ww / w);
+        cubic_resize_kernel<<<lf::stream_grid(wpx, kBlock), kBlock, 0, s>>>(rgb, work, n, h, w, wh, ww, sy, sx);
+        const int rc = lf::check_launch("lf_make_mask (resize)");
+        if (rc != LF_OK) return rc;
+        src = work;
+    }
+    int rc = lf_inclusive_mask_u8(src, cand, n, wh, ww, prm->green_lo, prm->green_hi, kq15, incl, incl_bytes, stream);
+    if (rc != LF_OK) return rc;
+    const double ify = 1.0 / ((double)h / wh), ifx = 1.0 / ((double)w / ww);
+    make_mask_post_kernel<<<n, kMaskT, lds, s>>>(src, cand, tabs, rn, parent, area, (int)mask_runs_per_image(wh, ww),
+                                                 wh, ww, (ww + 31) / 32, h, w, rescale, ify, ifx, (float)scale, a,
+                                                 mask, contour, counts, flags, cap);
+    return lf::check_launch("lf_make_mask");
+}
+
+}  // extern "C"

@@ -313,6 +313,74 @@ def inclusive_mask_u8(x: torch.Tensor, green_hue_range=(25, 100)) -> torch.Tenso
     return out
 
 
+def mask_working_scale(h: int, w: int, upscale_factor: float = 1.3, upscale_long_side: int = 1500):
+    """_prepare_working_image (mask.py:29-50): (scale, working height, working width, rescale).  The scale is
+    mask_upscale_factor when > 1, else mask_upscale_long_side / max(h, w) when the long side is shorter; the size
+    is Python's round of the double products; a scale within 1e-6 of 1 keeps the input as it is."""
+    s = 1.0
+    if upscale_factor and upscale_factor > 1.0:
+        s = float(upscale_factor)
+    elif upscale_long_side and upscale_long_side > 0:
+        ls = max(h, w)
+        if ls < upscale_long_side:
+            s = float(upscale_long_side) / float(ls)
+    if abs(s - 1.0) < 1e-6:
+        return s, h, w, False
+    return s, int(round(h * s)), int(round(w * s)), True
+
+
+_HSV_CHANNELS = {"h": 0, "s": 1, "v": 2}
+
+
+def make_mask_u8(x: torch.Tensor, green_hue_range=(25, 100), fill_size: int = 1000, morph_kernel: int = 3,
+                 mask_upscale_factor: float = 1.3, mask_upscale_long_side: int = 1500, hsv_channel: str = "s",
+                 use_lab_brown: bool = False, brown_hue_range=(0, 30), brown_s_min: int = 20,
+                 brown_v_max: int = 200, lab_a_min: int = 125, lab_b_min: int = 125, brown_min_area_px: int = 25,
+                 brown_morph_kernel: int = 3, cap: Optional[int] = None):
+    """make_mask (srcs/transform/filters/mask.py:548-582), default strategy, for a same-size batch [N,H,W,3] uint8.
+    Returns (mask [N,H,W] uint8 0 / 255, contour [N,K,2] int32 (x, y), counts [N] int32, fallback [N] bool): the
+    first counts[i] rows of contour[i] are image i's contour (count 0: none).  Defaults: config.yaml.  An image
+    whose contour is longer than `cap` is traced again into a buffer of its exact length: nothing is truncated.
+    A working image must fit one workgroup's LDS (four bit planes, 140 KiB): square working images up to 519 x 519, so square inputs up to 399 x 399 at the default mask_upscale_factor 1.3 (400 x 400 and larger are rejected, as is the long-side rule's 1500 x 1500)."""
+    n, h, w = _hwc(x, "make_mask.x")
+    if hsv_channel not in _HSV_CHANNELS:
+        raise ValueError(f"make_mask: hsv_channel must be one of h, s, v, got {hsv_channel!r}")
+    scale, wh, ww, rescale = mask_working_scale(h, w, mask_upscale_factor, mask_upscale_long_side)
+    prm = np.array([green_hue_range[0], green_hue_range[1], fill_size, morph_kernel, _HSV_CHANNELS[hsv_channel],
+                    1 if use_lab_brown else 0, brown_hue_range[0], brown_hue_range[1], brown_s_min, brown_v_max,
+                    lab_a_min, lab_b_min, brown_min_area_px, brown_morph_kernel], dtype=np.int32)
+    kq15 = np.ascontiguousarray(gaussian_kernel_q8(15, 0.0).astype(np.uint16))  # host constants
+    def run(xb: torch.Tensor, k: int):
+        m = xb.shape[0]
+        ws = torch.empty(int(_lib.load().lf_make_mask_workspace(m, h, w, wh, ww)), dtype=_U8, device=x.device)
+        mask = torch.empty((m, h, w), dtype=_U8, device=x.device)
+        cnt = torch.empty((m, k, 2), dtype=_I32, device=x.device)
+        counts = torch.empty(m, dtype=_I32, device=x.device)
+        flags = torch.empty(m, dtype=_I32, device=x.device)
+        _lib.call("lf_make_mask_u8", xb.data_ptr(), mask.data_ptr(), cnt.data_ptr(), counts.data_ptr(),
+                  flags.data_ptr(), m, h, w, wh, ww, 1 if rescale else 0, float(scale), prm.ctypes.data, k,
+                  kq15.ctypes.data, ws.data_ptr(), ws.numel(), _stream())
+        return mask, cnt, counts, flags
+
+    k = int(cap) if cap else 4 * (wh + ww)
+    mask, cnt, counts, flags = run(x, k)
+    flags_h = flags.cpu()
+    if bool((flags_h & 4).any()):
+        raise _lib.LeafHipError("lf_make_mask_u8: a border-following / union-find / flood step bound was hit")
+    counts_h = counts.cpu()
+    longest = int(counts_h.max())
+    if longest > k:   # re-trace the images whose contour did not fit, into a buffer of the exact length
+        over = torch.nonzero(counts_h > k).flatten()
+        _m2, cnt2, counts2, _f2 = run(x[over.to(x.device)].contiguous(), longest)
+        wide = torch.zeros((n, longest, 2), dtype=_I32, device=x.device)
+        wide[:, :k] = cnt
+        wide[over.to(x.device)] = cnt2
+        if not torch.equal(counts2.cpu(), counts_h[over]):
+            raise _lib.LeafHipError("lf_make_mask_u8: the re-traced contours changed length")
+        cnt = wide
+    return mask, cnt, counts_h.to(x.device), (flags_h & 1).bool().to(x.device)
+
+
 def jpeg_fdct_quant_u8(x: torch.Tensor, quality: int = 95, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The pixel half of Image.save(path, quality=quality) (image_utils.py:49-56) for a batch [N,H,W,3] uint8
     : libjpeg's quantised DCT coefficients, int16 [N, ceil(H/16) * ceil(W/16), 6, 64] — per MCU the

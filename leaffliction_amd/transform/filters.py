@@ -1,15 +1,17 @@
 """Host mirror of the per-pixel filters of srcs/transform/filters (blur.py, hist.py): same call
 shapes (numpy RGB in, numpy out), the arithmetic runs in libleafhip on the GPU.
 
-Of the segmentation that produces the leaf mask (`make_mask`, mask.py:548-582) the first slice is here:
-`create_inclusive_mask`, the default strategy's candidate mask (mask.py:727-831) on the working image.
-The cubic upscale before it (mask.py:29-50) and the GrabCut / brown-extension refinements after it
-(:307-392) are not, so `apply_blur_filter` still receives its mask through `make_mask_func` exactly as
-blur.py does.  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
+`make_mask` (mask.py:548-582) runs the reference's default strategy ("inclusive") on the GPU: working-image
+upscale, the inclusive candidate, post-processing and largest contour, the Otsu fallback, the brown-region
+extension and the resize back (lf_make_mask_u8).  The other strategies are not ported and raise.  GrabCut
+(grabcut_refine, true in config.yaml) and shadow suppression are skipped with one warning per process: the
+reference keeps the candidate whenever a refinement scores lower, so the result is one of the outcomes the
+reference can produce.  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
 reproduced — the numbers it draws are."""
 from __future__ import annotations
 
-from dataclasses import dataclass
+import logging
+from dataclasses import dataclass, fields
 from typing import Callable, Dict, Optional, Tuple
 
 import numpy as np
@@ -26,12 +28,42 @@ HUE_KEYS = ("Vert (35-85°)", "Jaune/Orange (15-35°)", "Rouge (0-15° & 160-180
 @dataclass
 class TransformConfig:
     """The fields of srcs/cli/Transformation.py:62-92 these filters read, with the values of
-    srcs/transform/config.yaml:2,42-44."""
+    srcs/transform/config.yaml."""
     gaussian_sigma: float = 1.5
     brown_hue_range: Tuple[int, int] = (0, 30)
     brown_s_min: int = 20
     brown_v_max: int = 200
     green_hue_range: Tuple[int, int] = (25, 100)      # config.yaml:10
+    # make_mask (config.yaml:6-17, 43-50)
+    mask_strategy: str = "inclusive"
+    bg_bias: str = "light_bg"
+    grabcut_refine: bool = True
+    min_object_area_ratio: float = 0.10
+    max_object_area_ratio: float = 0.98
+    fill_size: int = 1000
+    morph_kernel: int = 3
+    mask_upscale_factor: float = 1.3
+    mask_upscale_long_side: int = 1500
+    shadow_suppression: bool = False
+    hsv_channel_for_mask: str = "s"
+    use_lab_brown: bool = False
+    brown_min_area_px: int = 25
+    brown_morph_kernel: int = 3
+    lab_a_min: int = 125
+    lab_b_min: int = 125
+
+
+def load_config(path) -> TransformConfig:
+    """A TransformConfig from a YAML file with the keys of srcs/transform/config.yaml.  Keys this port does not
+    read are ignored; missing keys keep their defaults; lists become tuples."""
+    import yaml
+    with open(path, "r", encoding="utf-8") as f:
+        data = yaml.safe_load(f) or {}
+    if not isinstance(data, dict):
+        raise ValueError(f"{path}: expected a mapping of configuration keys")
+    known = {f.name for f in fields(TransformConfig)}
+    kw = {k: (tuple(v) if isinstance(v, list) else v) for k, v in data.items() if k in known}
+    return TransformConfig(**kw)
 
 
 def _device() -> torch.device:
@@ -55,10 +87,71 @@ def create_inclusive_mask(rgb_work: np.ndarray, cfg) -> np.ndarray:
     return out[0].cpu().numpy()
 
 
-def apply_blur_filter(rgb: np.ndarray, cfg, make_mask_func: Callable) -> np.ndarray:
+_log = logging.getLogger(__name__)
+_warned = set()
+
+
+def _check_mask_config(cfg) -> None:
+    strategy = getattr(cfg, "mask_strategy", "inclusive")
+    if strategy != "inclusive":
+        raise ValueError(f"make_mask: mask_strategy {strategy!r} is not supported; the GPU port implements the "
+                         "default strategy 'inclusive' only")
+    for key in ("grabcut_refine", "shadow_suppression"):
+        if getattr(cfg, key, False) and key not in _warned:
+            _warned.add(key)
+            _log.warning("make_mask: %s is not implemented on the GPU and is skipped (the reference keeps the "
+                         "candidate mask whenever this refinement scores lower)", key)
+
+
+def make_masks(batch, cfg) -> Tuple[np.ndarray, list, np.ndarray]:
+    """make_mask (mask.py:548-582) for a same-size batch [N,H,W,3] uint8 (numpy or a CUDA tensor).  Returns
+    (masks [N,H,W] uint8 0 / 255, contours: per image int32 [K,1,2] or None, fallback [N] bool)."""
+    _check_mask_config(cfg)
+    if isinstance(batch, torch.Tensor):
+        x = batch.to(_device()).contiguous()
+    else:
+        a = np.ascontiguousarray(batch)
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError(f"expected an NxHxWx3 uint8 RGB batch, got {a.dtype} {a.shape}")
+        x = torch.from_numpy(a).to(_device())
+    mask, cnt, counts, fallback = ops.make_mask_u8(
+        x, green_hue_range=tuple(cfg.green_hue_range), fill_size=int(cfg.fill_size),
+        morph_kernel=int(cfg.morph_kernel), mask_upscale_factor=cfg.mask_upscale_factor,
+        mask_upscale_long_side=cfg.mask_upscale_long_side, hsv_channel=str(cfg.hsv_channel_for_mask),
+        use_lab_brown=bool(cfg.use_lab_brown), brown_hue_range=tuple(cfg.brown_hue_range),
+        brown_s_min=int(cfg.brown_s_min), brown_v_max=int(cfg.brown_v_max), lab_a_min=int(cfg.lab_a_min),
+        lab_b_min=int(cfg.lab_b_min), brown_min_area_px=int(cfg.brown_min_area_px),
+        brown_morph_kernel=int(cfg.brown_morph_kernel))
+    cnt_h, counts_h = cnt.cpu().numpy(), counts.cpu().numpy()
+    contours = [cnt_h[i, :int(c)].reshape(-1, 1, 2).copy() if c > 0 else None for i, c in enumerate(counts_h)]
+    return mask.cpu().numpy(), contours, fallback.cpu().numpy()
+
+
+def make_mask(rgb: np.ndarray, cfg) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """srcs/transform/filters/mask.py:548-582 for one HxWx3 uint8 RGB image: (mask HxW uint8 0 / 255, contour
+    int32 [K,1,2] or None), default strategy on the GPU.  Readings of the OpenCV / PlantCV / skimage steps:
+    include/leafhip.h (lf_make_mask_u8) and the comment above make_mask_post_kernel in lf_filters.hip.
+    Size limit: A working image must fit one workgroup's LDS (four bit planes, 140 KiB): square working images up to 519 x 519, so square inputs up to 399 x 399 at the default mask_upscale_factor 1.3 (400 x 400 and larger are rejected, as is the long-side rule's 1500 x 1500).  Larger images raise LeafHipError before any launch."""
+    masks, contours, _ = make_masks(_rgb_batch(rgb), cfg)
+    return masks[0], contours[0]
+
+
+def apply_mask_filter(rgb: np.ndarray, cfg, make_mask_func: Optional[Callable] = None) -> np.ndarray:
+    """srcs/transform/filters/mask.py:585-604: the image on a black background outside the leaf mask
+    (mask_composite_u8).  make_mask_func defaults to the GPU make_mask with cfg; a None mask returns the input."""
+    mask, _ = make_mask_func(rgb) if make_mask_func is not None else make_mask(rgb, cfg)
+    if mask is None:
+        return rgb
+    x = _rgb_batch(rgb)
+    m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask, dtype=np.uint8))).unsqueeze(0).to(x.device)
+    return ops.mask_composite_u8(x, m, "black")[0].cpu().numpy()
+
+
+def apply_blur_filter(rgb: np.ndarray, cfg, make_mask_func: Optional[Callable] = None) -> np.ndarray:
     """srcs/transform/filters/blur.py:18-79: saliency image under the leaf mask, gray -> RGB.
-    `make_mask_func(rgb)` returns (mask, _); a None mask returns the input unchanged (:22-24)."""
-    mask, _ = make_mask_func(rgb)
+    `make_mask_func(rgb)` returns (mask, _) and defaults to the GPU make_mask with cfg; a None mask returns the
+    input unchanged (:22-24)."""
+    mask, _ = make_mask_func(rgb) if make_mask_func is not None else make_mask(rgb, cfg)
     if mask is None:
         return rgb
     m = np.asarray(mask)
