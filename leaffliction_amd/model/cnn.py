@@ -338,15 +338,21 @@ class LeafCNN:
                                     self.s[name + ".mean"], self.s[name + ".var"], st, BN_EPS)
         return st
 
-    def _conv_bn(self, x, wname: str, ksize: int, bn: str, pro, out: torch.Tensor, training: bool):
+    def _conv_bn(self, x, wname: str, ksize: int, bn: str, pro, out: torch.Tensor, training: bool,
+                 bf16: bool = False):
         """Conv2D -> BatchNormalization: returns (y, stats[4,C]).  In training the batch
-        statistics come out of the convolution's epilogue (no second pass over y)."""
+        statistics come out of the convolution's epilogue (no second pass over y); bf16: the
+        training step on bf16 storage (packed weights from _prep_bf16_weights)."""
         P = self.p
         if training:
             st = self.stats[bn]
-            nn.conv2d_bn_stats(x, P[wname], ksize, P[bn + ".gamma"], P[bn + ".beta"],
-                               self.s[bn + ".mean"], self.s[bn + ".var"], st, pro[0], pro[1], pro[2],
-                               out=out, momentum=BN_MOMENTUM, eps=BN_EPS)
+            bn_args = (P[bn + ".gamma"], P[bn + ".beta"], self.s[bn + ".mean"], self.s[bn + ".var"], st,
+                       pro[0], pro[1], pro[2])
+            if bf16:
+                nn.conv2d_bn_stats_bf16(x, self._wt["f:" + wname], P[wname].shape[2], ksize, *bn_args,
+                                        out=out, momentum=BN_MOMENTUM, eps=BN_EPS)
+            else:
+                nn.conv2d_bn_stats(x, P[wname], ksize, *bn_args, out=out, momentum=BN_MOMENTUM, eps=BN_EPS)
             return out, st
         w = P[wname]
         if self.infer_dtype == "bf16" and x.shape[3] % 4 == 0 and w.shape[2] % 32 == 0:
@@ -443,7 +449,6 @@ class LeafCNN:
                              f"of 4 pixels wide (img_size {self.img_size}, widths {self.widths})")
         self.train_dtype = dtype
 
-    # ------------------------------------------------- mixed-precision step (bf16 storage)
     def _prep_bf16_weights(self) -> None:
         """bf16 copies of the convolution kernels in MFMA operand order, for the forward and the
         input-gradient convolutions: rebuilt from the fp32 masters every step (1.25 M values)."""
@@ -455,151 +460,30 @@ class LeafCNN:
             if name != "stem.w":
                 self._wt["d:" + name] = nn.conv2d_bf16_dgrad_weights(self.p[name], k)
 
-    def _forward_train_bf16(self, x0: torch.Tensor, y_true: torch.Tensor, drops, top_drop):
-        """The training forward pass on bf16 storage; everything backward needs goes to self._saved."""
-        n, _c, h, w = x0.shape
-        self._mut += 1
-        P, bf = self.p, torch.bfloat16
-        B = lambda k, shape, dt=bf: self._buf(n, "t16." + k, shape, dt)  # noqa: E731
-        F32 = torch.float32
-        sv: Dict[str, Any] = {"x0": x0, "n": n}
-        self._prep_bf16_weights()
-
-        def conv_bn(x, wname, k, bn, pro, out):
-            cout = P[wname].shape[2]
-            st = self.stats[bn]
-            nn.conv2d_bn_stats_bf16(x, self._wt["f:" + wname], cout, k, P[bn + ".gamma"], P[bn + ".beta"],
-                                    self.s[bn + ".mean"], self.s[bn + ".var"], st, pro[0], pro[1], pro[2],
-                                    out=out, momentum=BN_MOMENTUM, eps=BN_EPS)
-            return out, st
-
-        y, st = conv_bn(x0, "stem.w", 3, "stem.bn", (None, None, False), B("stem.y", (n, self.widths[0], h, w)))
-        sv["stem.y"] = y
-        xin, xin_st, cin = y, st, self.widths[0]
-        for i, f in enumerate(self.widths):
-            p = f"s{i}."
-            pro = (xin_st[2], xin_st[3], True) if xin_st is not None else (None, None, False)
-            y1, st1 = conv_bn(xin, p + "c1.w", 3, p + "bn1", pro, B(p + "y1", (n, f, h, w)))
-            y2, st2 = conv_bn(y1, p + "c2.w", 3, p + "bn2", (st1[2], st1[3], True), B(p + "y2", (n, f, h, w)))
-            msum = B(p + "msum", (n, f, 2), F32)
-            m = nn.gap_stats_bf16(y2, out=B(p + "m", (n, f), F32), scale=st2[2], shift=st2[3], relu=True,
-                                  mask_sums=msum)
-            z1 = B(p + "z1", (n, f // 8), F32)
-            s = nn.se_fwd(m, P[p + "se.w1"], P[p + "se.b1"], P[p + "se.w2"], P[p + "se.b2"], z1,
-                          B(p + "s", (n, f), F32))
-            sv[p + "msum"], sv[p + "m"], sv[p + "z1"] = msum, m, z1
-            if cin != f:
-                yp, stp = conv_bn(xin, p + "proj.w", 1, p + "bnp", pro, B(p + "yp", (n, f, h, w)))
-                sc, scs, scb, scr = yp, stp[2], stp[3], False
-                sv[p + "yp"] = yp
-            else:
-                sc, scs, scb, scr = xin, pro[0], pro[1], pro[2]
-            drop = drops[i] if drops is not None else None
-            pooled = B(p + "p", (n, f, h // 2, w // 2))
-            route = B(p + "route", pooled.shape, torch.uint8)
-            nn.block_tail_fwd_train_bf16(y2, st2[2], st2[3], s, sc, scs, scb, scr, drop, route, pooled)
-            sv.update({p + "xin": xin, p + "xin_st": xin_st, p + "y1": y1, p + "y2": y2, p + "s": s,
-                       p + "route": route, p + "drop": drop, p + "hw": (h, w)})
-            xin, xin_st, cin, h, w = pooled, None, f, h // 2, w // 2
-        g = nn.gap_stats_bf16(xin, out=B("g", (n, self.widths[-1]), F32))
-        feat = g
-        if top_drop is not None:
-            feat = nn.mul(g, top_drop, B("feat", g.shape, F32))
-        probs = B("probs", (n, self.num_classes), F32)
-        loss = B("loss", (n,), F32)
-        nn.head_fwd(feat, P["dense.w"], P["dense.b"], y_true, probs, loss)
-        sv.update({"feat": feat, "top_drop": top_drop, "probs": probs, "y_true": y_true, "last_hw": (h, w)})
-        self._saved = sv
-        return probs, loss
-
-    def _backward_bf16(self, part: Optional[int] = None) -> None:
-        """Fills flat_g (fp32) from the tensors of the last _forward_train_bf16.  part: see backward()."""
-        sv, P, G = self._saved, self.p, self.g
-        n = sv["n"]
-        bf, F32 = torch.bfloat16, torch.float32
-        B = lambda k, shape, dt=bf: self._buf(n, "t16." + k, shape, dt)  # noqa: E731
-        f_last = self.widths[-1]
-        if part in (None, 0):
-            dlogits = B("dlogits", (n, self.num_classes), F32)
-            dfeat = B("dfeat", (n, f_last), F32)
-            nn.head_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], dlogits, dfeat,
-                        G["dense.w"], G["dense.b"], 1.0 / (self._global_n or n))
-            dg = dfeat
-            if sv["top_drop"] is not None:
-                dg = nn.mul(dfeat, sv["top_drop"], B("dg", dfeat.shape, F32))
-            h, w = sv["last_hw"]
-            dp = nn.bcast_planes_bf16(dg, h, w, 1.0 / (h * w), B("dp_last", (n, f_last, h, w)))
-        else:
-            dp = sv["bwd_dp"]
-        for i in self._backward_stages(part):
-            f = self.widths[i]
-            cin = self.widths[i - 1] if i > 0 else self.widths[0]
-            p = f"s{i}."
-            h, w = sv[p + "hw"]
-            xin, xin_st, y1, y2 = (sv[p + k] for k in ("xin", "xin_st", "y1", "y2"))
-            pro = (xin_st[2], xin_st[3], True) if xin_st is not None else (None, None, False)
-            s, route, drop = sv[p + "s"], sv[p + "route"], sv[p + "drop"]
-            st1, st2 = self.stats[p + "bn1"], self.stats[p + "bn2"]
-            gA, gB, gC = B(p + "gA", y1.shape), B(p + "gB", y1.shape), B(p + "gC", y1.shape)
-            ds = B(p + "ds", (n, f), F32)
-            psum = B(p + "psum", (n, f, 2), F32)
-            yp = sv.get(p + "yp")
-            psum_p = B(p + "psum_p", (n, f, 2), F32) if yp is not None else None
-            # dr (-> gA), the SE gate gradient and BN2's per-plane backward sums in one pass
-            nn.block_tail_bwd_bf16(dp, route, y2, st2[2], st2[3], drop, gA, ds, psum, yp, psum_p)
-            dm = B(p + "dm", (n, f), F32)
-            nn.se_bwd(ds, sv[p + "m"], sv[p + "z1"], s, P[p + "se.w1"], P[p + "se.w2"], dm,
-                      G[p + "se.w1"], G[p + "se.b1"], G[p + "se.w2"], G[p + "se.b2"], dm_scale=1.0 / (h * w))
-            # BN2 backward + conv2 weight gradient; dy2 -> gB
-            nn.bn_bwd_wgrad_bf16(y1, gA, y2, st2, P[p + "bn2.gamma"], G[p + "bn2.gamma"], G[p + "bn2.beta"],
-                                 True, 3, G[p + "c2.w"], gB, st1[2], st1[3], True, alpha_nc=s, add_nc=dm,
-                                 plane_g=psum, plane_m=sv[p + "msum"])
-            # da1 -> gC; the epilogue leaves BN1's backward sums
-            _, tsum = nn.conv2d_bf16_train(gB, self._wt["d:" + p + "c2.w"], f, 3, gC, mask_y=y1,
-                                           mask_scale=st1[2], mask_shift=st1[3], mask_relu=True)
-            # BN1 backward + conv1 weight gradient; dy1 -> gB
-            nn.bn_bwd_wgrad_bf16(xin, gC, y1, st1, P[p + "bn1.gamma"], G[p + "bn1.gamma"], G[p + "bn1.beta"],
-                                 True, 3, G[p + "c1.w"], gB, pro[0], pro[1], pro[2], tile_sums=tsum)
-            if cin != f:
-                stp = self.stats[p + "bnp"]
-                # projection BN backward + 1x1 weight gradient; dyp -> gC
-                nn.bn_bwd_wgrad_bf16(xin, gA, yp, stp, P[p + "bnp.gamma"], G[p + "bnp.gamma"],
-                                     G[p + "bnp.beta"], False, 1, G[p + "proj.w"], gC, pro[0], pro[1], pro[2],
-                                     plane_g=psum_p)
-                dx = B(p + "dx", xin.shape)
-                nn.conv2d_bf16_train(gC, self._wt["d:" + p + "proj.w"], cin, 1, dx)
-            else:
-                dx = gA  # identity shortcut: dx starts as dr
-            stem_sums = None
-            if i == 0:  # dx feeds the stem's BN backward: gather its sums in this epilogue
-                _, stem_sums = nn.conv2d_bf16_train(gB, self._wt["d:" + p + "c1.w"], cin, 3, dx, accumulate=True,
-                                                    mask_y=sv["stem.y"], mask_scale=self.stats["stem.bn"][2],
-                                                    mask_shift=self.stats["stem.bn"][3], mask_relu=True)
-            else:
-                nn.conv2d_bf16_train(gB, self._wt["d:" + p + "c1.w"], cin, 3, dx, accumulate=True)
-            dp = dx
-        if part == 0:
-            sv["bwd_dp"] = dp   # the gradient that enters stage 0: where part 1 picks up
-            return
-        # the stem has no input gradient: its BN backward exists only inside the wgrad kernel
-        nn.bn_bwd_wgrad_bf16(sv["x0"], dp, sv["stem.y"], self.stats["stem.bn"], P["stem.bn.gamma"],
-                             G["stem.bn.gamma"], G["stem.bn.beta"], True, 3, G["stem.w"], None,
-                             tile_sums=stem_sums)
-
     def forward(self, x0: torch.Tensor, training: bool, y_true: Optional[torch.Tensor] = None,
                 drops: Optional[List[torch.Tensor]] = None,
                 top_drop: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """x0: normalised f32 NCHW.  Returns (probs [N,C], per-sample loss or None).
-        In training mode every tensor the backward pass needs is kept in self._saved."""
+        In training mode the step runs in self.train_dtype (see set_training_dtype) and every tensor
+        the backward pass needs is kept in self._saved."""
         n, _c, h, w = x0.shape
+        bf16 = training and self.train_dtype == "bf16"
+        if bf16 and not (self.use_se and self._bf16_storage_ok(h, w)):
+            raise ValueError("bf16 training: unsupported shape (see set_training_dtype)")
         if training:
             self._mut += 1   # the BatchNorm layers update their moving statistics
-        P, B = self.p, lambda k, shape: self._buf(n, k, shape)
-        sv: Dict[str, Any] = {"x0": x0, "n": n}
+        P, F32 = self.p, torch.float32
+        # the bf16 step has buffers of its own: activations and their gradients in bf16, the rest fp32
+        pre, act = ("t16.", torch.bfloat16) if bf16 else ("", F32)
+        B = lambda k, shape, dt=act: self._buf(n, pre + k, shape, dt)  # noqa: E731
+        gap, tail = (nn.gap_stats_bf16, nn.block_tail_fwd_train_bf16) if bf16 else (nn.gap, nn.block_tail_fwd)
+        sv: Dict[str, Any] = {"x0": x0, "n": n, "bf16": bf16}
+        if bf16:
+            self._prep_bf16_weights()
         # Activations a = relu(BN(y)) are never materialised: every consumer (the next conv,
         # wgrad, GAP, the residual tail, BN backward) applies scale/shift(+ReLU) while it reads y.
         y, st = self._conv_bn(x0, "stem.w", 3, "stem.bn", (None, None, False),
-                              B("stem.y", (n, self.widths[0], h, w)), training)
+                              B("stem.y", (n, self.widths[0], h, w)), training, bf16)
         sv["stem.y"] = y
         xin, xin_st = y, st  # block input = relu(xin*xin_st[2]+xin_st[3]) (None = already final)
         cin = self.widths[0]
@@ -607,41 +491,40 @@ class LeafCNN:
             p = f"s{i}."
             pro = (xin_st[2], xin_st[3], True) if xin_st is not None else (None, None, False)
             y1, st1 = self._conv_bn(xin, p + "c1.w", 3, p + "bn1", pro, B(p + "y1", (n, f, h, w)),
-                                    training)
+                                    training, bf16)
             y2, st2 = self._conv_bn(y1, p + "c2.w", 3, p + "bn2", (st1[2], st1[3], True),
-                                    B(p + "y2", y1.shape), training)
+                                    B(p + "y2", y1.shape), training, bf16)
             s = None
             if self.use_se:
                 # the squeeze pass also leaves BN2's ReLU-mask sums for the backward pass
-                msum = B(p + "msum", (n, f, 2)) if training else None
-                m = nn.gap(y2, out=B(p + "m", (n, f)), scale=st2[2], shift=st2[3], relu=True,
-                           mask_sums=msum)
+                msum = B(p + "msum", (n, f, 2), F32) if training else None
+                m = gap(y2, out=B(p + "m", (n, f), F32), scale=st2[2], shift=st2[3], relu=True,
+                        mask_sums=msum)
                 sv[p + "msum"] = msum
-                z1 = B(p + "z1", (n, f // 8))
+                z1 = B(p + "z1", (n, f // 8), F32)
                 s = nn.se_fwd(m, P[p + "se.w1"], P[p + "se.b1"], P[p + "se.w2"], P[p + "se.b2"], z1,
-                              B(p + "s", (n, f)))
+                              B(p + "s", (n, f), F32))
                 sv[p + "m"], sv[p + "z1"] = m, z1
             if cin != f:
                 yp, stp = self._conv_bn(xin, p + "proj.w", 1, p + "bnp", pro, B(p + "yp", y1.shape),
-                                        training)
+                                        training, bf16)
                 sc, scs, scb, scr = yp, stp[2], stp[3], False
                 sv[p + "yp"] = yp
             else:
                 sc, scs, scb, scr = xin, pro[0], pro[1], pro[2]
             drop = drops[i] if (training and drops is not None) else None
             pooled = B(p + "p", (n, f, h // 2, w // 2))
-            route = self._buf(n, p + "route", pooled.shape, torch.uint8)
-            nn.block_tail_fwd(y2, st2[2], st2[3], s, sc, scs, scb, scr, drop, route, pooled)
+            route = B(p + "route", pooled.shape, torch.uint8)
+            tail(y2, st2[2], st2[3], s, sc, scs, scb, scr, drop, route, pooled)
             sv.update({p + "xin": xin, p + "xin_st": xin_st, p + "y1": y1, p + "y2": y2, p + "s": s,
                        p + "route": route, p + "drop": drop, p + "hw": (h, w)})
             xin, xin_st, cin, h, w = pooled, None, f, h // 2, w // 2
-        a = xin
-        g = nn.gap(a, out=B("g", (n, self.widths[-1])))
+        g = gap(xin, out=B("g", (n, self.widths[-1]), F32))
         feat = g
         if training and top_drop is not None:
-            feat = nn.mul(g, top_drop, B("feat", g.shape))
-        probs = B("probs", (n, self.num_classes))
-        loss = B("loss", (n,)) if y_true is not None else None
+            feat = nn.mul(g, top_drop, B("feat", g.shape, F32))
+        probs = B("probs", (n, self.num_classes), F32)
+        loss = B("loss", (n,), F32) if y_true is not None else None
         nn.head_fwd(feat, P["dense.w"], P["dense.b"], y_true, probs, loss)
         sv.update({"feat": feat, "top_drop": top_drop, "probs": probs, "y_true": y_true,
                    "last_hw": (h, w)})
@@ -672,21 +555,28 @@ class LeafCNN:
         return self.n_params
 
     def backward(self, part: Optional[int] = None) -> None:
-        """Fills flat_g with d(mean data loss)/d(param) for the last training forward (part: _backward_stages)."""
+        """Fills flat_g (fp32) with d(mean data loss)/d(param) for the last training forward, in that
+        forward's precision (part: _backward_stages)."""
         sv, P, G = self._saved, self.p, self.g
-        n = sv["n"]
-        B = lambda k, shape: self._buf(n, k, shape)  # noqa: E731
+        n, bf16 = sv["n"], sv["bf16"]
+        F32 = torch.float32
+        pre, act = ("t16.", torch.bfloat16) if bf16 else ("", F32)   # the forward's buffers: see there
+        B = lambda k, shape, dt=act: self._buf(n, pre + k, shape, dt)  # noqa: E731
+        if bf16:
+            bcast, tail_bwd, bn_bwd_wgrad = nn.bcast_planes_bf16, nn.block_tail_bwd_bf16, nn.bn_bwd_wgrad_bf16
+        else:
+            bcast, tail_bwd, bn_bwd_wgrad = nn.bcast_planes, nn.block_tail_bwd, nn.bn_bwd_wgrad
         f_last = self.widths[-1]
         if part in (None, 0):
-            dlogits = B("dlogits", (n, self.num_classes))
-            dfeat = B("dfeat", (n, f_last))
+            dlogits = B("dlogits", (n, self.num_classes), F32)
+            dfeat = B("dfeat", (n, f_last), F32)
             nn.head_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], dlogits, dfeat,
                         G["dense.w"], G["dense.b"], 1.0 / (self._global_n or n))
             dg = dfeat
             if sv["top_drop"] is not None:
-                dg = nn.mul(dfeat, sv["top_drop"], B("dg", dfeat.shape))
+                dg = nn.mul(dfeat, sv["top_drop"], B("dg", dfeat.shape, F32))
             h, w = sv["last_hw"]
-            dp = nn.bcast_planes(dg, h, w, 1.0 / (h * w), out=B("dp_last", (n, f_last, h, w)))
+            dp = bcast(dg, h, w, 1.0 / (h * w), B("dp_last", (n, f_last, h, w)))
         else:
             dp = sv["bwd_dp"]
         for i in self._backward_stages(part):
@@ -701,59 +591,71 @@ class LeafCNN:
             gA = B(p + "gA", y1.shape)
             gB = B(p + "gB", y1.shape)
             gC = B(p + "gC", y1.shape)
-            ds = B(p + "ds", (n, f)) if self.use_se else None
+            ds = B(p + "ds", (n, f), F32) if self.use_se else None
             # dr (into gA), the SE gate gradient, and BN2's per-plane backward sums in one pass
-            psum = B(p + "psum", (n, f, 2))
+            psum = B(p + "psum", (n, f, 2), F32)
             yp = sv.get(p + "yp")  # projection shortcut: its BN's backward sums ride along
-            psum_p = B(p + "psum_p", (n, f, 2)) if yp is not None else None
-            nn.block_tail_bwd(dp, route, y2, st2[2], st2[3], drop, gA, ds, psum, yp, psum_p)
+            psum_p = B(p + "psum_p", (n, f, 2), F32) if yp is not None else None
+            tail_bwd(dp, route, y2, st2[2], st2[3], drop, gA, ds, psum, yp, psum_p)
             add_nc = None
             if self.use_se:
-                dm = B(p + "dm", (n, f))
+                dm = B(p + "dm", (n, f), F32)
                 nn.se_bwd(ds, sv[p + "m"], sv[p + "z1"], s, P[p + "se.w1"], P[p + "se.w2"], dm,
                           G[p + "se.w1"], G[p + "se.b1"], G[p + "se.w2"], G[p + "se.b2"],
                           dm_scale=1.0 / (h * w))
                 add_nc = dm
             # conv2 branch: dz2 = (dr*s + dm/HW) * [a2 > 0];
             # BN2 backward + conv2 weight gradient: dy2 is formed inside the wgrad kernel (-> gB)
-            nn.bn_bwd_wgrad(y1, gA, y2, st2, P[p + "bn2.gamma"], G[p + "bn2.gamma"],
-                            G[p + "bn2.beta"], True, 3, G[p + "c2.w"], gB, st1[2], st1[3], True,
-                            alpha_nc=s, add_nc=add_nc, plane_g=psum,
-                            plane_m=sv[p + "msum"] if self.use_se else None)
+            bn_bwd_wgrad(y1, gA, y2, st2, P[p + "bn2.gamma"], G[p + "bn2.gamma"],
+                         G[p + "bn2.beta"], True, 3, G[p + "c2.w"], gB, st1[2], st1[3], True,
+                         alpha_nc=s, add_nc=add_nc, plane_g=psum,
+                         plane_m=sv[p + "msum"] if self.use_se else None)
             # da1 (-> gC); its epilogue leaves BN1's backward sums
-            _, tsum = nn.conv2d_bnbwd(gB, self._dgrad_w(p + "c2.w", 3), 3, y1, st1, True, gC)
+            tsum = self._dgrad(gB, p + "c2.w", 3, gC, bf16, mask=(y1, st1))
             # BN1 backward + conv1 weight gradient (dy1 -> gB)
-            nn.bn_bwd_wgrad(xin, gC, y1, st1, P[p + "bn1.gamma"], G[p + "bn1.gamma"],
-                            G[p + "bn1.beta"], True, 3, G[p + "c1.w"], gB, pro[0], pro[1], pro[2],
-                            tile_sums=tsum)
+            bn_bwd_wgrad(xin, gC, y1, st1, P[p + "bn1.gamma"], G[p + "bn1.gamma"],
+                         G[p + "bn1.beta"], True, 3, G[p + "c1.w"], gB, pro[0], pro[1], pro[2],
+                         tile_sums=tsum)
             if cin != f:
                 stp = self.stats[p + "bnp"]
                 # projection BN backward + 1x1 weight gradient (dyp -> gC)
-                nn.bn_bwd_wgrad(xin, gA, yp, stp, P[p + "bnp.gamma"], G[p + "bnp.gamma"],
-                                G[p + "bnp.beta"], False, 1, G[p + "proj.w"], gC, pro[0], pro[1], pro[2],
-                                plane_g=psum_p)
+                bn_bwd_wgrad(xin, gA, yp, stp, P[p + "bnp.gamma"], G[p + "bnp.gamma"],
+                             G[p + "bnp.beta"], False, 1, G[p + "proj.w"], gC, pro[0], pro[1], pro[2],
+                             plane_g=psum_p)
                 dx = B(p + "dx", xin.shape)
-                nn.conv2d(gC, self._dgrad_w(p + "proj.w", 1), 1, out=dx)
+                self._dgrad(gC, p + "proj.w", 1, dx, bf16)
             else:
                 dx = gA  # identity shortcut: dx starts as dr
-            stem_sums = None
-            if i == 0:  # dx feeds the stem's BN backward: gather its sums in this epilogue
-                _, stem_sums = nn.conv2d_bnbwd(gB, self._dgrad_w(p + "c1.w", 3), 3, sv["stem.y"],
-                                               self.stats["stem.bn"], True, dx, accumulate=True)
-            else:
-                nn.conv2d(gB, self._dgrad_w(p + "c1.w", 3), 3, out=dx, accumulate=True)
+            # at stage 0 dx feeds the stem's BN backward: gather its sums in this epilogue
+            stem_mask = (sv["stem.y"], self.stats["stem.bn"]) if i == 0 else None
+            stem_sums = self._dgrad(gB, p + "c1.w", 3, dx, bf16, accumulate=True, mask=stem_mask)
             dp = dx
         if part == 0:
             sv["bwd_dp"] = dp   # the gradient that enters stage 0: where part 1 picks up
             return
         # stem: dp is the gradient wrt relu(BN(stem.y))
         # the stem has no input gradient: its BN backward exists only inside the wgrad kernel
-        nn.bn_bwd_wgrad(sv["x0"], dp, sv["stem.y"], self.stats["stem.bn"], P["stem.bn.gamma"],
-                        G["stem.bn.gamma"], G["stem.bn.beta"], True, 3, G["stem.w"], None,
-                        tile_sums=stem_sums)
+        bn_bwd_wgrad(sv["x0"], dp, sv["stem.y"], self.stats["stem.bn"], P["stem.bn.gamma"],
+                     G["stem.bn.gamma"], G["stem.bn.beta"], True, 3, G["stem.w"], None,
+                     tile_sums=stem_sums)
 
-    def _dgrad_w(self, name: str, k: int) -> torch.Tensor:
-        return nn.conv2d_dgrad_weights(self.p[name], k)
+    def _dgrad(self, gy: torch.Tensor, wname: str, k: int, out: torch.Tensor, bf16: bool,
+               accumulate: bool = False, mask=None):
+        """Input-gradient convolution out (+)= conv(gy, flipped w).  mask (y, stats): out feeds the
+        backward of the BatchNorm(+ReLU) with input y; returns the per-tile sums of that backward,
+        which the epilogue gathers (bn_bwd_wgrad's tile_sums)."""
+        if bf16:
+            wt, cin = self._wt["d:" + wname], self.p[wname].shape[0]
+            if mask is None:
+                nn.conv2d_bf16_train(gy, wt, cin, k, out, accumulate=accumulate)
+                return None
+            return nn.conv2d_bf16_train(gy, wt, cin, k, out, accumulate=accumulate, mask_y=mask[0],
+                                        mask_scale=mask[1][2], mask_shift=mask[1][3], mask_relu=True)[1]
+        wt = nn.conv2d_dgrad_weights(self.p[wname], k)
+        if mask is None:
+            nn.conv2d(gy, wt, k, out=out, accumulate=accumulate)
+            return None
+        return nn.conv2d_bnbwd(gy, wt, k, mask[0], mask[1], True, out, accumulate=accumulate)[1]
 
     # ------------------------------------------------------------ training
     def draw_dropout(self, n: int):
@@ -895,19 +797,12 @@ class LeafCNN:
 
     def _forward_backward_body(self, x, y_true, drops, top, aug4, part: Optional[int] = None):
         """part None: forward + the whole backward pass; 0: forward + backward part 0; 1: backward part 1."""
-        bf16 = self.train_dtype == "bf16"
         if part == 1:
-            self._backward_bf16(1) if bf16 else self.backward(1)
+            self.backward(1)
             return None
         x0 = self._input(x, True, aug4)
-        if bf16:
-            if not (self.use_se and self._bf16_storage_ok(x0.shape[2], x0.shape[3])):
-                raise ValueError("bf16 training: unsupported shape (see set_training_dtype)")
-            probs, loss = self._forward_train_bf16(x0, y_true, drops, top)
-            self._backward_bf16(part)
-        else:
-            probs, loss = self.forward(x0, True, y_true, drops, top)
-            self.backward(part)
+        probs, loss = self.forward(x0, True, y_true, drops, top)
+        self.backward(part)
         return probs, loss
 
     def _optimizer_update(self, lr: float, *, weight_decay: float, clipnorm: float,

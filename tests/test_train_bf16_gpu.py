@@ -274,8 +274,8 @@ def test_train_step_bf16_matches_lowp_oracle(cuda, size, n, widths, classes):
     y = R.smooth_labels(onehot, 0.02).to(dev)
     drops, top = m.draw_dropout(n)
     x0 = ops.pack_hwc_u8_to_nchw_f32(x.to(dev))
-    probs, loss = m._forward_train_bf16(x0, y, drops, top)
-    m._backward_bf16()
+    probs, loss = m.forward(x0, True, y, drops, top)
+    m.backward()
     torch.cuda.synchronize()
     args = (x0.cpu(), onehot, widths, [t.cpu() for t in drops], top.cpu())
     _t, dl_lo, p_lo, g_lo = R.train_step(ref_p, R.init_state(widths), *args, grads_include_l2=False, lowp=True)
