@@ -375,10 +375,9 @@ int lf_conv2d_bf16_f32(const float* x, const uint16_t* wprep, float* y, int n, i
 
 /* The reduced-precision forward pass with bf16 ACTIVATION STORAGE as well (what mixed_float16
  * keeps between layers): the same convolution reading and / or writing bf16 NCHW tensors
- * (x_bf16 / y_bf16 flags; the fused prologue and the accumulation stay fp32), and the two plane
- * kernels of the block on bf16 tensors — lf_gap_f32's mean of relu?(x*scale+shift) (no mask
- * sums) and lf_block_tail_fwd_f32's maxpool2x2(relu(shortcut' + relu(BN(y)) * gate)) without the
- * route bytes and dropout a backward pass would need.  hw % 4 == 0 / w % 4 == 0, h even.
+ * (x_bf16 / y_bf16 flags; the fused prologue and the accumulation stay fp32).  The block's plane
+ * kernels on bf16 tensors are those of the training step below: lf_gap_stats_bf16 without mask
+ * sums, and lf_block_tail_fwd_train_bf16 without dropout or route bytes.
  * out_scale / out_shift / out_relu: optional epilogue v*out_scale[co]+out_shift[co] (+ReLU) on the
  * fp32 accumulators — at inference the layer's folded BatchNorm(+ReLU), so that what is stored is
  * the activation itself and the consumer needs no prologue (a bf16 input without prologue is staged
@@ -392,19 +391,13 @@ int lf_conv2d_bf16_act(const void* x, int x_bf16, const uint16_t* wprep, void* y
  * GlobalAveragePooling2D over relu(BN(conv2))): stores the bf16 activation like lf_conv2d_bf16_act and
  * leaves means[n][co] = mean over the plane of the STORED (rounded) values — summed in the
  * convolution's epilogue, per image, so the activation is not read back from memory for the pool
- * (lf_gap_bf16 remains for everything else).  Workspace: lf_conv2d_bf16_act_mean_workspace bytes. */
+ * (lf_gap_stats_bf16 remains for everything else).  Workspace: lf_conv2d_bf16_act_mean_workspace bytes. */
 size_t lf_conv2d_bf16_act_mean_workspace(int n, int cin, int h, int wd, int cout, int ksize, int x_bf16);
 int lf_conv2d_bf16_act_mean(const void* x, int x_bf16, const uint16_t* wprep, uint16_t* y, int n, int cin,
                             int h, int wd, int cout, int ksize, const float* in_scale,
                             const float* in_shift, int in_relu, const float* out_scale,
                             const float* out_shift, int out_relu, float* means, void* workspace,
                             size_t ws_bytes, lf_stream_t stream);
-int lf_gap_bf16(const uint16_t* x, float* out, int n, int c, int hw, const float* scale,
-                const float* shift, int relu, lf_stream_t stream);
-int lf_block_tail_fwd_bf16(const uint16_t* y, const float* a_scale, const float* a_shift,
-                           const float* s, const uint16_t* sc, const float* sc_scale,
-                           const float* sc_shift, int sc_relu, uint16_t* pooled, int n, int c, int h,
-                           int w, lf_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
 /* A2 — the mixed-precision TRAINING step (bf16 storage, fp32 arithmetic)      */
@@ -460,7 +453,8 @@ int lf_conv2d_wgrad_bf16(const void* x, const uint16_t* g, const uint16_t* bn_y,
  * mask_sums), lf_block_tail_fwd_f32 (route bytes, SpatialDropout2D keep-scales),
  * lf_block_tail_bwd_f32 and lf_bcast_planes_f32 (cnn.py:35-49,94-101), fp32 after widening;
  * pooled / dr / out are rounded to bf16 where stored and the per-plane sums are over the rounded
- * gradient.  hw % 4 == 0, w % 4 == 0, h even. */
+ * gradient.  hw % 4 == 0, w % 4 == 0, h even.  lf_block_tail_fwd_train_bf16 takes route = NULL when
+ * no backward pass follows (inference). */
 int lf_gap_stats_bf16(const uint16_t* x, float* out, float* mask_sums, int n, int c, int hw,
                       const float* scale, const float* shift, int relu, lf_stream_t stream);
 int lf_block_tail_fwd_train_bf16(const uint16_t* y, const float* a_scale, const float* a_shift,

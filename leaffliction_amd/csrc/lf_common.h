@@ -162,6 +162,10 @@ __device__ __forceinline__ Block2 xcd_block2() {
     return r;
 }
 
+// bf16 held as uint16_t: widen exactly, and round to nearest even
+__device__ __forceinline__ float bf16_up(unsigned bits16) { return __uint_as_float(bits16 << 16); }
+__device__ __forceinline__ uint16_t bf16_down(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
+
 template <bool NT, typename T>
 __device__ __forceinline__ T ldg(const T* p) {
     return NT ? __builtin_nontemporal_load(p) : *p;

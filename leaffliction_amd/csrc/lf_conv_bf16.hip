@@ -1,12 +1,14 @@
-// libleafhip — forward convolution with bf16 operands and fp32 accumulation (inference only).
+// libleafhip — the K-chunked convolution with bf16 operands and fp32 accumulation.
 //
 // The reference trains and predicts under Keras' `mixed_float16` policy unless told otherwise
 // (train.py:53-117, `--no-mixed-precision`); BASELINE configs[4] asks for reduced-precision
-// inference.  This is that mode for the conv stack: activations and weights stay fp32 in HBM (the
-// BatchNorm / SE / residual-tail kernels are shared with the fp32 path), the convolution rounds its
-// two operands to bf16 while staging them and multiplies on `v_mfma_f32_32x32x16_bf16` with fp32
-// accumulators — 16x the matrix rate of the fp32 path, so the kernel is bound by staging and HBM,
-// not by the MFMA pipe.
+// inference.  This kernel serves that mode at inference and in the mixed-precision training step
+// (forward and input-gradient convolutions the streaming kernel of lf_conv_bf16s.hip does not take).
+// Input and output are fp32 or bf16 NCHW (XBF / YBF); the operands are rounded to bf16 while staged
+// and multiplied on `v_mfma_f32_32x32x16_bf16` with fp32 accumulators — 16x the matrix rate of the
+// fp32 path, so the kernel is bound by staging and HBM, not by the MFMA pipe.  Epilogues: inference
+// applies the layer's folded BatchNorm(+ReLU) before rounding; training (TR) accumulates into the
+// output and leaves per-tile BatchNorm statistics or BatchNorm-backward sums of the stored values.
 //
 // Implicit GEMM D[co][pixel] = sum_k W[co][k] X[k][pixel], K = (input channel, tap).  Workgroup =
 // 32x8 output pixels x 64 output channels (32x16 x 32 when cout is an odd multiple of 32); per 16-channel chunk the input patch sits in LDS as
@@ -80,9 +82,8 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
     return __builtin_bit_cast(unsigned, v);
 }
 
-__device__ __forceinline__ float bf16_up(unsigned bits16) { return __uint_as_float(bits16 << 16); }
-
-__device__ __forceinline__ uint16_t bf16_down(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
+using lf::bf16_down;
+using lf::bf16_up;
 
 // (three or four workgroups per CU would need <= 168 / 128 registers: the spills cost more than the
 // occupancy brings — 40.4 k and 24.5 k img/s against 47.3 k for the whole forward pass)
@@ -514,84 +515,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
 }
 
-// --- the plane kernels of the forward pass on bf16 activations (inference only) ---------------
-// Same arithmetic as gap_kernel / tail_fwd_kernel of lf_nn.hip (fp32 after widening the operands);
-// what differs is the storage type, and that nothing is kept for a backward pass.
-
-// out[n][c] = mean over the plane of relu?(x * scale[c] + shift[c]); one workgroup per plane.
-__global__ __launch_bounds__(kThreads) void gap_bf16_kernel(const uint16_t* __restrict__ x,
-                                                            float* __restrict__ out, int hw, int c,
-                                                            const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, int relu) {
-    __shared__ float red[kThreads / 64];
-    const size_t base = (size_t)blockIdx.x * hw;
-    const bool pro = scale != nullptr;
-    const float sc = pro ? scale[blockIdx.x % c] : 1.f, sh = pro ? shift[blockIdx.x % c] : 0.f;
-    auto one = [&](unsigned bits) {
-        float v = bf16_up(bits);
-        if (pro) v = fmaf(v, sc, sh);
-        return relu ? fmaxf(v, 0.f) : v;
-    };
-    float acc = 0.f;
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    const u32x2* x4 = reinterpret_cast<const u32x2*>(x + base);  // hw % 4 == 0
-    for (int i = threadIdx.x; i < hw / 4; i += kThreads) {
-        const u32x2 v = x4[i];
-        acc += (one(v.x & 0xffffu) + one(v.x >> 16)) + (one(v.y & 0xffffu) + one(v.y >> 16));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)hw;
-}
-
-struct TailBf16Args {
-    const uint16_t* y;       // second conv of the block (raw, before its BatchNorm)
-    const float* a_scale;    // its folded BatchNorm
-    const float* a_shift;
-    const float* s;          // SE gate [n][c] or null
-    const uint16_t* sc;      // shortcut tensor
-    const float* sc_scale;   // its scale / shift (+ReLU) or null when it is final already
-    const float* sc_shift;
-    int sc_relu;
-    int c, h, w;
-};
-
-// pooled = maxpool2x2(relu(shortcut + relu(BN(y)) * gate)), bf16 in, bf16 out; w % 4 == 0.
-__global__ __launch_bounds__(kThreads) void tail_fwd_bf16_kernel(TailBf16Args t, uint16_t* __restrict__ p) {
-    const int plane = blockIdx.x, ch = plane % t.c;
-    const float sv = t.s ? t.s[plane] : 1.f;
-    const float as = t.a_scale ? t.a_scale[ch] : 1.f, ab = t.a_scale ? t.a_shift[ch] : 0.f;
-    const float ks = t.sc_scale ? t.sc_scale[ch] : 1.f, kb = t.sc_scale ? t.sc_shift[ch] : 0.f;
-    const int h = t.h, w = t.w, ph = h / 2, pw = w / 2, pw2 = pw / 2;
-    const size_t base = (size_t)plane * h * w, pbase = (size_t)plane * ph * pw;
-    auto r = [&](unsigned yb, unsigned sb) {
-        const float a = t.a_scale ? fmaxf(fmaf(bf16_up(yb), as, ab), 0.f) : bf16_up(yb);
-        float shv = bf16_up(sb);
-        if (t.sc_scale) {
-            shv = fmaf(shv, ks, kb);
-            if (t.sc_relu) shv = fmaxf(shv, 0.f);
-        }
-        return fmaxf(shv + a * sv, 0.f);
-    };
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    for (int q = blockIdx.y * kThreads + threadIdx.x; q < ph * pw2; q += gridDim.y * kThreads) {
-        const int py = q / pw2, px2 = q - py * pw2;
-        float m0 = 0.f, m1 = 0.f;  // the block's output is >= 0: starting the max at 0 is exact
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy) {
-            const size_t o = base + (size_t)(2 * py + dy) * w + 4 * px2;
-            const u32x2 yv = *reinterpret_cast<const u32x2*>(t.y + o);
-            const u32x2 sv4 = *reinterpret_cast<const u32x2*>(t.sc + o);
-            m0 = fmaxf(m0, fmaxf(r(yv.x & 0xffffu, sv4.x & 0xffffu), r(yv.x >> 16, sv4.x >> 16)));
-            m1 = fmaxf(m1, fmaxf(r(yv.y & 0xffffu, sv4.y & 0xffffu), r(yv.y >> 16, sv4.y >> 16)));
-        }
-        *reinterpret_cast<unsigned*>(p + pbase + (size_t)py * pw + 2 * px2) =
-            (unsigned)bf16_down(m0) | (unsigned)bf16_down(m1) << 16;
-    }
-}
-
 // fp32 [cin][taps][cout] -> bf16 [chunk][tap][cout][16] (channels past cin are zero)
 __global__ void prep_weights_bf16_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int cin,
                                          int taps, int cout, int chunks) {
@@ -847,35 +770,6 @@ int lf_conv2d_bf16_act_mean(const void* x, int x_bf16, const uint16_t* wprep, ui
     if (x_bf16) launch_conv_bf16<true, true, true>(a, ksize, s); else launch_conv_bf16<false, true, true>(a, ksize, s);
     partial_sums_mean_kernel<<<(n * cout + 255) / 256, 256, 0, s>>>(part, means, n, cout, tiles, 1, inv);
     return lf::check_launch("lf_conv2d_bf16_act_mean");
-}
-
-int lf_gap_bf16(const uint16_t* x, float* out, int n, int c, int hw, const float* scale, const float* shift,
-                int relu, lf_stream_t stream) {
-    LF_REQUIRE(x && out, "lf_gap_bf16: null buffer");
-    LF_REQUIRE(n > 0 && c > 0 && hw > 0 && hw % 4 == 0, "lf_gap_bf16: bad dims n=%d c=%d hw=%d (hw %% 4 == 0)", n, c,
-               hw);
-    LF_REQUIRE((scale == nullptr) == (shift == nullptr), "lf_gap_bf16: scale/shift must both be set");
-    LF_REQUIRE((reinterpret_cast<size_t>(x) & 7) == 0, "lf_gap_bf16: x must be 8-byte aligned");
-    gap_bf16_kernel<<<n * c, kThreads, 0, lf::as_stream(stream)>>>(x, out, hw, c, scale, shift, relu);
-    return lf::check_launch("lf_gap_bf16");
-}
-
-int lf_block_tail_fwd_bf16(const uint16_t* y, const float* a_scale, const float* a_shift, const float* s,
-                           const uint16_t* sc, const float* sc_scale, const float* sc_shift, int sc_relu,
-                           uint16_t* pooled, int n, int c, int h, int w, lf_stream_t stream) {
-    LF_REQUIRE(y && sc && pooled, "lf_block_tail_fwd_bf16: null buffer");
-    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_fwd_bf16: a_scale/a_shift must both be set");
-    LF_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && h % 2 == 0 && w % 4 == 0,
-               "lf_block_tail_fwd_bf16: bad dims n=%d c=%d h=%d w=%d (h even, w %% 4 == 0)", n, c, h, w);
-    LF_REQUIRE((sc_scale == nullptr) == (sc_shift == nullptr), "lf_block_tail_fwd_bf16: scale/shift must both be set");
-    LF_REQUIRE(((reinterpret_cast<size_t>(y) | reinterpret_cast<size_t>(sc)) & 7) == 0 &&
-                   (reinterpret_cast<size_t>(pooled) & 3) == 0,
-               "lf_block_tail_fwd_bf16: buffers must be 8-byte (inputs) / 4-byte (output) aligned");
-    TailBf16Args t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, sc_relu, c, h, w};
-    const int per_plane = (h / 2) * (w / 4);
-    dim3 grid(n * c, (per_plane + kThreads - 1) / kThreads > 8 ? 8 : (per_plane + kThreads - 1) / kThreads);
-    tail_fwd_bf16_kernel<<<grid, kThreads, 0, lf::as_stream(stream)>>>(t, pooled);
-    return lf::check_launch("lf_block_tail_fwd_bf16");
 }
 
 int lf_conv2d_bf16_f32(const float* x, const uint16_t* wprep, float* y, int n, int cin, int h, int w,

@@ -47,8 +47,8 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kT = 256;
 
-__device__ __forceinline__ float up(unsigned bits16) { return __uint_as_float(bits16 << 16); }
-__device__ __forceinline__ uint16_t down(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
+using lf::bf16_down;
+using lf::bf16_up;
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {
     typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     bf16x2 v;
@@ -242,8 +242,8 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
                     if (XBF) {
 #pragma unroll
                         for (int e = 0; e < G; e += 2) {
-                            v[e] = up(rx[k][i][e / 2] & 0xffffu);
-                            v[e + 1] = up(rx[k][i][e / 2] >> 16);
+                            v[e] = bf16_up(rx[k][i][e / 2] & 0xffffu);
+                            v[e + 1] = bf16_up(rx[k][i][e / 2] >> 16);
                         }
                     } else {
 #pragma unroll
@@ -278,7 +278,7 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
             if (hmask >> k & 1u) {
                 if (XBF) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = up(rh[k][i]);
+                    for (int i = 0; i < 4; ++i) v[i] = bf16_up(rh[k][i]);
                 } else {
 #pragma unroll
                     for (int i = 0; i < 3; ++i) v[i] = __uint_as_float(rh[k][i]);
@@ -451,8 +451,8 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
                 if (accumulate)
 #pragma unroll
                     for (int e = 0; e < 8; e += 2) {
-                        v[e] += up(rold[cb][j][e / 2] & 0xffffu);
-                        v[e + 1] += up(rold[cb][j][e / 2] >> 16);
+                        v[e] += bf16_up(rold[cb][j][e / 2] & 0xffffu);
+                        v[e + 1] += bf16_up(rold[cb][j][e / 2] >> 16);
                     }
                 if (p.out_scale != nullptr) {
                     const float osc = los[co], osh = los[COUT + co];
@@ -472,7 +472,7 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
                     const float pv = lst[co];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const float d = up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu) - pv;
+                        const float d = bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu) - pv;
                         a += d;
                         b = fmaf(d, d, b);
                     }
@@ -480,9 +480,9 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
                     const float msc = lst[co], msh = lst[COUT + co];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const float rv = up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu);
+                        const float rv = bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu);
                         const unsigned mw = rmask[cb][j][e / 2];
-                        const float yv = up((e & 1) ? mw >> 16 : mw & 0xffffu);
+                        const float yv = bf16_up((e & 1) ? mw >> 16 : mw & 0xffffu);
                         const float d = (!p.mask_relu || fmaf(yv, msc, msh) > 0.f) ? rv : 0.f;
                         a += d;
                         b = fmaf(d, yv, b);

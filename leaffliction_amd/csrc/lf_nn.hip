@@ -1,11 +1,16 @@
-// libleafhip — leaf_cnn non-conv kernels (fp32, NCHW): input stage (pack + in-model
+// libleafhip — leaf_cnn non-conv kernels (NCHW): input stage (pack + in-model
 // augmentation + Normalization), BatchNorm (train statistics / backward), Squeeze-Excite,
 // residual tail (add + ReLU + SpatialDropout + MaxPool) forward/backward, GAP + Dense +
-// softmax cross-entropy head, AdamW with per-tensor clipnorm + EMA.
+// softmax cross-entropy head, AdamW with per-tensor clipnorm + EMA, fp32 <-> bf16 casts.
 //
-// All of these are HBM-bound streaming / reduction kernels: float4 accesses, one
-// (n, c) plane per workgroup row so per-channel / per-sample parameters are uniform, and
-// every cross-workgroup reduction goes through partial sums that are combined in a fixed
+// Activations are fp32.  The plane kernels (GAP, residual tail, GAP backward) also serve the
+// mixed-precision step and bf16 inference on bf16 storage (template parameter T): arithmetic is
+// fp32 after widening, values are rounded to bf16 (nearest even) exactly where they are stored,
+// and every sum a later kernel relies on is taken over the stored values.
+//
+// All of these are HBM-bound streaming / reduction kernels: 16-byte accesses where the shape
+// allows, one (n, c) plane per workgroup row so per-channel / per-sample parameters are uniform,
+// and every cross-workgroup reduction goes through partial sums that are combined in a fixed
 // order (deterministic; no float atomics).  Reference semantics: srcs/model/cnn.py:9-104,
 // srcs/train/utils.py:17-57 (Keras 3 layer / optimizer definitions).
 #include "lf_common.h"
@@ -14,6 +19,25 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kBnSplit = 64;  // partial sums per channel in the BN reductions
+
+// plane-kernel storage: float, or bf16 held as uint16_t
+__device__ __forceinline__ float widen(float v) { return v; }
+__device__ __forceinline__ float widen(uint16_t v) { return lf::bf16_up(v); }
+template <typename T>
+__device__ __forceinline__ T narrow(float v);
+template <>
+__device__ __forceinline__ float narrow<float>(float v) { return v; }
+template <>
+__device__ __forceinline__ uint16_t narrow<uint16_t>(float v) { return lf::bf16_down(v); }
+
+// V consecutive elements moved as one access (a native vector: an array in a struct lets the compiler
+// split the load and sink parts of it into a branch)
+template <typename T, int V>
+using Vec = T __attribute__((ext_vector_type(V)));
+
+// the route bytes of N consecutive pooled values as one integer (byte k = value k)
+template <int N>
+using RouteWord = std::conditional_t<N == 4, unsigned, std::conditional_t<N == 2, uint16_t, uint8_t>>;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -422,8 +446,10 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(BnBwdArgs a,
 // global average pool per plane, and its broadcast backward
 // ---------------------------------------------------------------------------
 // out[plane] = mean_hw act(x*scale[c]+shift[c]) (scale null = plain mean); with mask_sums also
-// {count of x*scale+shift > 0, sum of x over those} per plane (BatchNorm backward needs them)
-__global__ __launch_bounds__(kBlock) void gap_kernel(const float* __restrict__ x,
+// {count of x*scale+shift > 0, sum of x over those} per plane (BatchNorm backward needs them).
+// V = elements per load; each load's values are summed in pairs, left to right.
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void gap_kernel(const T* __restrict__ x,
                                                      float* __restrict__ out, int hw, int c,
                                                      const float* __restrict__ scale,
                                                      const float* __restrict__ shift, int relu,
@@ -433,7 +459,8 @@ __global__ __launch_bounds__(kBlock) void gap_kernel(const float* __restrict__ x
     const bool pro = scale != nullptr;
     const float sc = pro ? scale[blockIdx.x % c] : 1.f, sh = pro ? shift[blockIdx.x % c] : 0.f;
     float acc[3] = {0.f, 0.f, 0.f};
-    auto one = [&](float xv) {
+    auto one = [&](T e) {
+        const float xv = widen(e);
         float v = xv;
         if (pro) {
             v = fmaf(xv, sc, sh);
@@ -445,15 +472,19 @@ __global__ __launch_bounds__(kBlock) void gap_kernel(const float* __restrict__ x
         }
         return v;
     };
-    if ((hw & 3) == 0) {
-        const float4* x4 = reinterpret_cast<const float4*>(x + base);
-        for (int i = threadIdx.x; i < hw / 4; i += kBlock) {
-            const float4 v = x4[i];
-            const float a = one(v.x), b = one(v.y), cc = one(v.z), d = one(v.w);
-            acc[0] += (a + b) + (cc + d);
+    const Vec<T, V>* xv = reinterpret_cast<const Vec<T, V>*>(x + base);
+    for (int i = threadIdx.x; i < hw / V; i += kBlock) {
+        const Vec<T, V> v = xv[i];
+        float s = one(v[0]);
+        if constexpr (V > 1) {
+            s += one(v[1]);
+#pragma unroll
+            for (int e = 2; e < V; e += 2) {
+                const float a = one(v[e]);
+                s += a + one(v[e + 1]);
+            }
         }
-    } else {
-        for (int i = threadIdx.x; i < hw; i += kBlock) acc[0] += one(x[base + i]);
+        acc[0] += s;
     }
     block_sum<3>(acc, red);
     if (threadIdx.x == 0) {
@@ -465,12 +496,16 @@ __global__ __launch_bounds__(kBlock) void gap_kernel(const float* __restrict__ x
     }
 }
 
+// out[plane][:] = v[plane] * scale, V values per store
+template <typename T, int V>
 __global__ __launch_bounds__(kBlock) void bcast_planes_kernel(const float* __restrict__ v,
-                                                              float* __restrict__ out, int hw,
+                                                              T* __restrict__ out, int hw,
                                                               float scale) {
-    const float val = v[blockIdx.x] * scale;
-    const size_t base = (size_t)blockIdx.x * hw;
-    for (int i = blockIdx.y * kBlock + threadIdx.x; i < hw; i += gridDim.y * kBlock) out[base + i] = val;
+    Vec<T, V> o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) o[e] = narrow<T>(v[blockIdx.x] * scale);
+    Vec<T, V>* dst = reinterpret_cast<Vec<T, V>*>(out + (size_t)blockIdx.x * hw);
+    for (int i = blockIdx.y * kBlock + threadIdx.x; i < hw / V; i += gridDim.y * kBlock) dst[i] = o;
 }
 
 // ---------------------------------------------------------------------------
@@ -578,12 +613,13 @@ __global__ __launch_bounds__(kBlock) void outer_sum_kernel(const float* __restri
 // ---------------------------------------------------------------------------
 // a = relu(y*a_scale[c]+a_shift[c]) when a_scale is given (BN2+ReLU fused), else a = y;
 // sc' = act(sc*sc_scale[c] + sc_shift[c]) (projection BN, or the stem's BN+ReLU) or sc.
+template <typename T>
 struct TailArgs {
-    const float* y;
+    const T* y;
     const float* a_scale;
     const float* a_shift;
     const float* s;
-    const float* sc;
+    const T* sc;
     const float* sc_scale;
     const float* sc_shift;
     const float* drop;
@@ -591,7 +627,8 @@ struct TailArgs {
     int c, h, w;
 };
 
-__device__ __forceinline__ float tail_r(const TailArgs& t, float yv, float scv, float as, float ab,
+template <typename T>
+__device__ __forceinline__ float tail_r(const TailArgs<T>& t, float yv, float scv, float as, float ab,
                                         float sv, float ks, float kb) {
     float a = yv;
     if (t.a_scale) a = fmaxf(fmaf(yv, as, ab), 0.f);
@@ -614,84 +651,77 @@ __device__ __forceinline__ unsigned tail_code(float r00, float r01, float r10, f
     return bi | (best > 0.f ? 4u : 0u);
 }
 
-// The residual r is not stored: backward only needs where each pooled value came from.
-__global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs t, uint8_t* __restrict__ route,
-                                                          float* __restrict__ p) {
+// One thread = two rows x V input pixels = V/2 pooled values and their route bytes.  The residual r
+// is not stored: backward only needs where each pooled value came from.  route == null: no backward
+// pass follows (inference).
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs<T> t, uint8_t* __restrict__ route,
+                                                          T* __restrict__ p) {
     const int plane = blockIdx.x, ch = plane % t.c;
     const float sv = t.s ? t.s[plane] : 1.f;
     const float as = t.a_scale ? t.a_scale[ch] : 1.f, ab = t.a_scale ? t.a_shift[ch] : 0.f;
     const float ks = t.sc_scale ? t.sc_scale[ch] : 1.f, kb = t.sc_scale ? t.sc_shift[ch] : 0.f;
     const float dv = t.drop ? t.drop[plane] : 1.f;
-    const int h = t.h, w = t.w, ph = h / 2, pw = w / 2;
+    const int h = t.h, w = t.w, ph = h / 2, pw = w / 2, pwv = w / V;
     const size_t base = (size_t)plane * h * w, pbase = (size_t)plane * ph * pw;
-    if ((w & 3) == 0) {
-        // one thread = 2 pooled outputs: a 2x4 window pair, float4 rows
-        const int pw2 = pw / 2;
-        for (int q = blockIdx.y * kBlock + threadIdx.x; q < ph * pw2; q += gridDim.y * kBlock) {
-            const int py = q / pw2, px2 = q - py * pw2;
-            float4 rv[2];
+    for (int q = blockIdx.y * kBlock + threadIdx.x; q < ph * pwv; q += gridDim.y * kBlock) {
+        const int py = q / pwv, pxv = q - py * pwv;
+        float r[2][V];
 #pragma unroll
-            for (int dy = 0; dy < 2; ++dy) {
-                const size_t o = base + (size_t)(2 * py + dy) * w + 4 * px2;
-                const float4 yv = *reinterpret_cast<const float4*>(t.y + o);
-                const float4 sv4 = *reinterpret_cast<const float4*>(t.sc + o);
-                rv[dy].x = tail_r(t, yv.x, sv4.x, as, ab, sv, ks, kb);
-                rv[dy].y = tail_r(t, yv.y, sv4.y, as, ab, sv, ks, kb);
-                rv[dy].z = tail_r(t, yv.z, sv4.z, as, ab, sv, ks, kb);
-                rv[dy].w = tail_r(t, yv.w, sv4.w, as, ab, sv, ks, kb);
-            }
-            float m0, m1;
-            const unsigned c0 = tail_code(rv[0].x, rv[0].y, rv[1].x, rv[1].y, m0);
-            const unsigned c1 = tail_code(rv[0].z, rv[0].w, rv[1].z, rv[1].w, m1);
-            const size_t po = pbase + (size_t)py * pw + 2 * px2;  // even: pw is even here
-            *reinterpret_cast<uint16_t*>(route + po) = (uint16_t)(c0 | (c1 << 8));
-            *reinterpret_cast<float2*>(p + po) = make_float2(m0 * dv, m1 * dv);
+        for (int dy = 0; dy < 2; ++dy) {
+            const size_t o = base + (size_t)(2 * py + dy) * w + V * pxv;
+            const Vec<T, V> yv = *reinterpret_cast<const Vec<T, V>*>(t.y + o);
+            const Vec<T, V> scv = *reinterpret_cast<const Vec<T, V>*>(t.sc + o);
+#pragma unroll
+            for (int e = 0; e < V; ++e) r[dy][e] = tail_r(t, widen(yv[e]), widen(scv[e]), as, ab, sv, ks, kb);
         }
-    } else {
-        for (int q = blockIdx.y * kBlock + threadIdx.x; q < ph * pw; q += gridDim.y * kBlock) {
-            const int py = q / pw, px = q - py * pw;
-            const size_t o0 = base + (size_t)(2 * py) * w + 2 * px, o1 = o0 + w;
-            const float r00 = tail_r(t, t.y[o0], t.sc[o0], as, ab, sv, ks, kb);
-            const float r01 = tail_r(t, t.y[o0 + 1], t.sc[o0 + 1], as, ab, sv, ks, kb);
-            const float r10 = tail_r(t, t.y[o1], t.sc[o1], as, ab, sv, ks, kb);
-            const float r11 = tail_r(t, t.y[o1 + 1], t.sc[o1 + 1], as, ab, sv, ks, kb);
-            float mx;
-            route[pbase + q] = (uint8_t)tail_code(r00, r01, r10, r11, mx);
-            p[pbase + q] = mx * dv;
+        const size_t po = pbase + (size_t)py * pw + (V / 2) * pxv;
+        unsigned codes = 0;
+        Vec<T, V / 2> pooled;
+#pragma unroll
+        for (int k = 0; k < V / 2; ++k) {
+            float m;
+            codes |= tail_code(r[0][2 * k], r[0][2 * k + 1], r[1][2 * k], r[1][2 * k + 1], m) << (8 * k);
+            pooled[k] = narrow<T>(m * dv);
         }
+        if (route != nullptr) *reinterpret_cast<RouteWord<V / 2>*>(route + po) = (RouteWord<V / 2>)codes;
+        *reinterpret_cast<Vec<T, V / 2>*>(p + po) = pooled;
     }
 }
 
 // dr = dp*drop routed to the recorded position of each 2x2 window when its maximum was > 0.
 // Per plane: ds = sum dr*a with a = relu(y*a_scale+a_shift) (or y), and (a_scale given)
-// plane_sums = {sum dr*[a>0], sum dr*[a>0]*y}: BatchNorm-2's backward sums without a second pass.
-__global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const float* __restrict__ dp,
+// plane_sums = {sum dr*[a>0], sum dr*[a>0]*y}: BatchNorm-2's backward sums without a second pass;
+// sc_sums = {sum dr, sum dr*sc_y} (the projection shortcut's BatchNorm).  The sums are over dr as
+// stored.  One thread = V/2 pooled values -> two rows x V gradient pixels.
+template <typename T, int V>
+__global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ dp,
                                                           const uint8_t* __restrict__ route,
-                                                          const float* __restrict__ y,
+                                                          const T* __restrict__ y,
                                                           const float* __restrict__ a_scale,
                                                           const float* __restrict__ a_shift,
                                                           const float* __restrict__ drop,
-                                                          float* __restrict__ dr,
+                                                          T* __restrict__ dr,
                                                           float* __restrict__ ds,
                                                           float* __restrict__ plane_sums,
-                                                          const float* __restrict__ sc_y,
+                                                          const T* __restrict__ sc_y,
                                                           float* __restrict__ sc_sums, int c,
                                                           int h, int w) {
     __shared__ float red[20];
     const int plane = blockIdx.x, ch = plane % c;
     const float dv = drop ? drop[plane] : 1.f;
     const float as = a_scale ? a_scale[ch] : 1.f, ab = a_scale ? a_shift[ch] : 0.f;
-    const int ph = h / 2, pw = w / 2;
+    const int ph = h / 2, pw = w / 2, pwv = w / V;
     const size_t base = (size_t)plane * h * w, pbase = (size_t)plane * ph * pw;
     const bool sums = ds != nullptr || plane_sums != nullptr;
     float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     auto tally = [&](float gg, size_t pos) {
         if (sc_y != nullptr && gg != 0.f) {  // the shortcut branch's (projection) BN: no mask
             acc[3] += gg;
-            acc[4] += gg * sc_y[pos];
+            acc[4] += gg * widen(sc_y[pos]);
         }
         if (sums && gg != 0.f) {
-            const float yv = y[pos];
+            const float yv = widen(y[pos]);
             float av = yv;
             if (a_scale) {
                 av = fmaf(yv, as, ab);
@@ -705,42 +735,30 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const float* __restric
             acc[0] += gg * av;
         }
     };
-    if ((w & 3) == 0) {
-        const int pw2 = pw / 2;
-        for (int q = threadIdx.x; q < ph * pw2; q += kBlock) {
-            const int py = q / pw2, px2 = q - py * pw2;
-            const size_t po = pbase + (size_t)py * pw + 2 * px2;
-            const unsigned codes = *reinterpret_cast<const uint16_t*>(route + po);
-            const float2 g2 = *reinterpret_cast<const float2*>(dp + po);
-            const unsigned c0 = codes & 0xff, c1 = codes >> 8;
-            const float g0 = (c0 & 4u) ? g2.x * dv : 0.f, g1 = (c1 & 4u) ? g2.y * dv : 0.f;
-            const unsigned b0 = c0 & 3u, b1 = c1 & 3u;
-            const size_t o0 = base + (size_t)(2 * py) * w + 4 * px2, o1 = o0 + w;
-            *reinterpret_cast<float4*>(dr + o0) = make_float4(b0 == 0 ? g0 : 0.f, b0 == 1 ? g0 : 0.f,
-                                                              b1 == 0 ? g1 : 0.f, b1 == 1 ? g1 : 0.f);
-            *reinterpret_cast<float4*>(dr + o1) = make_float4(b0 == 2 ? g0 : 0.f, b0 == 3 ? g0 : 0.f,
-                                                              b1 == 2 ? g1 : 0.f, b1 == 3 ? g1 : 0.f);
-            tally(g0, (b0 < 2 ? o0 : o1) + (b0 & 1u));
-            tally(g1, (b1 < 2 ? o0 : o1) + 2 + (b1 & 1u));
+    for (int q = threadIdx.x; q < ph * pwv; q += kBlock) {
+        const int py = q / pwv, pxv = q - py * pwv;
+        const size_t po = pbase + (size_t)py * pw + (V / 2) * pxv;
+        const unsigned codes = *reinterpret_cast<const RouteWord<V / 2>*>(route + po);
+        const Vec<T, V / 2> g = *reinterpret_cast<const Vec<T, V / 2>*>(dp + po);
+        const size_t o0 = base + (size_t)(2 * py) * w + V * pxv, o1 = o0 + w;
+        Vec<T, V> top, bot;
+#pragma unroll
+        for (int k = 0; k < V / 2; ++k) {   // pooled value k -> input columns 2k, 2k+1
+            const unsigned cd = (codes >> (8 * k)) & 0xffu, b = cd & 3u;
+            const T gk = (cd & 4u) ? narrow<T>(widen(g[k]) * dv) : T(0);
+            top[2 * k] = b == 0 ? gk : T(0);
+            top[2 * k + 1] = b == 1 ? gk : T(0);
+            bot[2 * k] = b == 2 ? gk : T(0);
+            bot[2 * k + 1] = b == 3 ? gk : T(0);
+            tally(widen(gk), (b < 2 ? o0 : o1) + 2 * k + (b & 1u));
         }
-    } else {
-        for (int t = threadIdx.x; t < ph * pw; t += kBlock) {
-            const int py = t / pw, px = t - py * pw;
-            const size_t o0 = base + (size_t)(2 * py) * w + 2 * px, o1 = o0 + w;
-            const unsigned code = route[pbase + t];
-            const float gg = (code & 4u) ? dp[pbase + t] * dv : 0.f;
-            const unsigned bi = code & 3u;
-            dr[o0] = bi == 0 ? gg : 0.f;
-            dr[o0 + 1] = bi == 1 ? gg : 0.f;
-            dr[o1] = bi == 2 ? gg : 0.f;
-            dr[o1 + 1] = bi == 3 ? gg : 0.f;
-            tally(gg, (bi < 2 ? o0 : o1) + (bi & 1u));
-        }
+        *reinterpret_cast<Vec<T, V>*>(dr + o0) = top;
+        *reinterpret_cast<Vec<T, V>*>(dr + o1) = bot;
     }
     if ((h & 1) || (w & 1)) {
         for (int t = threadIdx.x; t < h * w; t += kBlock) {
             const int yy = t / w, x = t - yy * w;
-            if (yy >= 2 * ph || x >= 2 * pw) dr[base + t] = 0.f;
+            if (yy >= 2 * ph || x >= 2 * pw) dr[base + t] = T(0);
         }
     }
     if (sums || sc_y != nullptr) {
@@ -949,7 +967,20 @@ __global__ __launch_bounds__(kBlock) void ema_kernel(float* __restrict__ ema,
         ema[i] = copy ? w[i] : decay * ema[i] + (1.f - decay) * w[i];
 }
 
+__global__ __launch_bounds__(kBlock) void cast_f32_bf16_kernel(const float* __restrict__ in,
+                                                               uint16_t* __restrict__ out, size_t count) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += (size_t)gridDim.x * kBlock)
+        out[i] = lf::bf16_down(in[i]);
+}
+
+__global__ __launch_bounds__(kBlock) void cast_bf16_f32_kernel(const uint16_t* __restrict__ in,
+                                                               float* __restrict__ out, size_t count) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += (size_t)gridDim.x * kBlock)
+        out[i] = lf::bf16_up(in[i]);
+}
+
 inline unsigned plane_grid(int hw_items) { return lf::stream_grid((size_t)hw_items, kBlock, 64); }
+inline bool aligned(const void* p, size_t bytes) { return (reinterpret_cast<size_t>(p) & (bytes - 1)) == 0; }
 
 }  // namespace
 
@@ -1149,18 +1180,41 @@ int lf_gap_f32(const float* x, float* out, int planes, int hw, int c, const floa
     LF_REQUIRE(mask_sums == nullptr || scale != nullptr, "lf_gap: mask_sums needs scale/shift");
     LF_REQUIRE(planes > 0 && hw > 0 && c > 0, "lf_gap: bad dims planes=%d hw=%d c=%d", planes, hw, c);
     LF_REQUIRE((scale == nullptr) == (shift == nullptr), "lf_gap: scale/shift must both be set");
-    gap_kernel<<<planes, kBlock, 0, lf::as_stream(stream)>>>(x, out, hw, c, scale, shift, relu,
-                                                             mask_sums);
+    auto kernel = hw % 4 == 0 ? gap_kernel<float, 4> : gap_kernel<float, 1>;
+    kernel<<<planes, kBlock, 0, lf::as_stream(stream)>>>(x, out, hw, c, scale, shift, relu, mask_sums);
     return lf::check_launch("lf_gap");
+}
+
+int lf_gap_stats_bf16(const uint16_t* x, float* out, float* mask_sums, int n, int c, int hw, const float* scale,
+                      const float* shift, int relu, lf_stream_t stream) {
+    LF_REQUIRE(x && out, "lf_gap_stats_bf16: null buffer");
+    LF_REQUIRE(n > 0 && c > 0 && hw > 0 && hw % 4 == 0, "lf_gap_stats_bf16: bad dims n=%d c=%d hw=%d (hw %% 4 == 0)",
+               n, c, hw);
+    LF_REQUIRE((scale == nullptr) == (shift == nullptr), "lf_gap_stats_bf16: scale/shift must both be set");
+    LF_REQUIRE(mask_sums == nullptr || scale != nullptr, "lf_gap_stats_bf16: mask_sums needs scale/shift");
+    LF_REQUIRE(aligned(x, 8), "lf_gap_stats_bf16: x must be 8-byte aligned");
+    auto kernel = hw % 8 == 0 && aligned(x, 16) ? gap_kernel<uint16_t, 8> : gap_kernel<uint16_t, 4>;
+    kernel<<<n * c, kBlock, 0, lf::as_stream(stream)>>>(x, out, hw, c, scale, shift, relu, mask_sums);
+    return lf::check_launch("lf_gap_stats_bf16");
 }
 
 int lf_bcast_planes_f32(const float* v, float* out, int planes, int hw, float scale,
                         lf_stream_t stream) {
     LF_REQUIRE(v && out, "lf_bcast_planes: null buffer");
     LF_REQUIRE(planes > 0 && hw > 0, "lf_bcast_planes: bad dims planes=%d hw=%d", planes, hw);
-    bcast_planes_kernel<<<dim3(planes, plane_grid(hw)), kBlock, 0, lf::as_stream(stream)>>>(v, out, hw,
-                                                                                           scale);
+    bcast_planes_kernel<float, 1><<<dim3(planes, plane_grid(hw)), kBlock, 0, lf::as_stream(stream)>>>(v, out, hw,
+                                                                                                     scale);
     return lf::check_launch("lf_bcast_planes");
+}
+
+int lf_bcast_planes_bf16(const float* v, uint16_t* out, int planes, int hw, float scale, lf_stream_t stream) {
+    LF_REQUIRE(v && out, "lf_bcast_planes_bf16: null buffer");
+    LF_REQUIRE(planes > 0 && hw > 0 && hw % 4 == 0, "lf_bcast_planes_bf16: bad dims planes=%d hw=%d (hw %% 4 == 0)",
+               planes, hw);
+    LF_REQUIRE(aligned(out, 8), "lf_bcast_planes_bf16: out must be 8-byte aligned");
+    bcast_planes_kernel<uint16_t, 4><<<dim3(planes, plane_grid(hw / 4)), kBlock, 0, lf::as_stream(stream)>>>(
+        v, out, hw, scale);
+    return lf::check_launch("lf_bcast_planes_bf16");
 }
 
 int lf_se_fwd_f32(const float* m, const float* w1, const float* b1, const float* w2,
@@ -1210,10 +1264,29 @@ int lf_block_tail_fwd_f32(const float* y, const float* a_scale, const float* a_s
     LF_REQUIRE((w & 1) == 0, "lf_block_tail_fwd: width must be even");
     LF_REQUIRE((sc_scale == nullptr) == (sc_shift == nullptr), "lf_block_tail_fwd: sc_scale/sc_shift");
     LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_fwd: a_scale/a_shift");
-    TailArgs t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
-    const int items = (w & 3) == 0 ? (h / 2) * (w / 4) : (h / 2) * (w / 2);
-    tail_fwd_kernel<<<dim3(n * c, plane_grid(items)), kBlock, 0, lf::as_stream(stream)>>>(t, route, p);
+    TailArgs<float> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
+    const int v = w % 4 == 0 ? 4 : 2;
+    auto kernel = v == 4 ? tail_fwd_kernel<float, 4> : tail_fwd_kernel<float, 2>;
+    kernel<<<dim3(n * c, plane_grid((h / 2) * (w / v))), kBlock, 0, lf::as_stream(stream)>>>(t, route, p);
     return lf::check_launch("lf_block_tail_fwd");
+}
+
+int lf_block_tail_fwd_train_bf16(const uint16_t* y, const float* a_scale, const float* a_shift, const float* s,
+                                 const uint16_t* sc, const float* sc_scale, const float* sc_shift, int sc_relu,
+                                 const float* drop, uint8_t* route, uint16_t* pooled, int n, int c, int h, int w,
+                                 lf_stream_t stream) {
+    LF_REQUIRE(y && sc && pooled, "lf_block_tail_fwd_train_bf16: null buffer");
+    LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 3 && h % 2 == 0 && w % 4 == 0 && (long long)n * c < (1LL << 31),
+               "lf_block_tail_fwd_train_bf16: bad dims n=%d c=%d h=%d w=%d (h even, w %% 4 == 0)", n, c, h, w);
+    LF_REQUIRE((sc_scale == nullptr) == (sc_shift == nullptr), "lf_block_tail_fwd_train_bf16: sc_scale/sc_shift");
+    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_fwd_train_bf16: a_scale/a_shift");
+    LF_REQUIRE(aligned(y, 8) && aligned(sc, 8) && aligned(pooled, 4) && aligned(route, 2),
+               "lf_block_tail_fwd_train_bf16: misaligned buffer");
+    TailArgs<uint16_t> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
+    const int v = w % 8 == 0 && aligned(y, 16) && aligned(sc, 16) && aligned(pooled, 8) && aligned(route, 4) ? 8 : 4;
+    auto kernel = v == 8 ? tail_fwd_kernel<uint16_t, 8> : tail_fwd_kernel<uint16_t, 4>;
+    kernel<<<dim3(n * c, plane_grid((h / 2) * (w / v))), kBlock, 0, lf::as_stream(stream)>>>(t, route, pooled);
+    return lf::check_launch("lf_block_tail_fwd_train_bf16");
 }
 
 int lf_block_tail_bwd_f32(const float* dp, const uint8_t* route, const float* y,
@@ -1229,9 +1302,30 @@ int lf_block_tail_bwd_f32(const float* dp, const uint8_t* route, const float* y,
     LF_REQUIRE((y == nullptr) == (ds == nullptr && plane_sums == nullptr),
                "lf_block_tail_bwd: y goes with ds / plane_sums");
     LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_bwd: a_scale/a_shift");
-    tail_bwd_kernel<<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr,
-                                                                ds, plane_sums, sc_y, sc_sums, c, h, w);
+    auto kernel = w % 4 == 0 ? tail_bwd_kernel<float, 4> : tail_bwd_kernel<float, 2>;
+    kernel<<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums,
+                                                        sc_y, sc_sums, c, h, w);
     return lf::check_launch("lf_block_tail_bwd");
+}
+
+int lf_block_tail_bwd_bf16(const uint16_t* dp, const uint8_t* route, const uint16_t* y, const float* a_scale,
+                           const float* a_shift, const float* drop, uint16_t* dr, float* ds, float* plane_sums,
+                           const uint16_t* sc_y, float* sc_sums, int n, int c, int h, int w, lf_stream_t stream) {
+    LF_REQUIRE((sc_y == nullptr) == (sc_sums == nullptr), "lf_block_tail_bwd_bf16: sc_y and sc_sums go together");
+    LF_REQUIRE(dp && route && dr, "lf_block_tail_bwd_bf16: null buffer");
+    LF_REQUIRE(plane_sums == nullptr || (y != nullptr && a_scale != nullptr),
+               "lf_block_tail_bwd_bf16: plane_sums needs y and a_scale/a_shift");
+    LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 3 && h % 2 == 0 && w % 4 == 0,
+               "lf_block_tail_bwd_bf16: bad dims n=%d c=%d h=%d w=%d (h even, w %% 4 == 0)", n, c, h, w);
+    LF_REQUIRE((y == nullptr) == (ds == nullptr && plane_sums == nullptr),
+               "lf_block_tail_bwd_bf16: y goes with ds / plane_sums");
+    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_bwd_bf16: a_scale/a_shift");
+    LF_REQUIRE(aligned(dr, 8) && aligned(dp, 4), "lf_block_tail_bwd_bf16: misaligned buffer");
+    auto kernel = w % 8 == 0 && aligned(dr, 16) && aligned(dp, 8) && aligned(route, 4) ? tail_bwd_kernel<uint16_t, 8>
+                                                                                      : tail_bwd_kernel<uint16_t, 4>;
+    kernel<<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums,
+                                                        sc_y, sc_sums, c, h, w);
+    return lf::check_launch("lf_block_tail_bwd_bf16");
 }
 
 int lf_head_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue,
@@ -1306,6 +1400,18 @@ int lf_ema_update_f32(float* ema, const float* w, size_t count, float decay, int
     ema_kernel<<<lf::stream_grid(count, kBlock), kBlock, 0, lf::as_stream(stream)>>>(ema, w, count, decay,
                                                                                  copy);
     return lf::check_launch("lf_ema_update");
+}
+
+int lf_cast_f32_bf16(const float* in, uint16_t* out, size_t count, lf_stream_t stream) {
+    LF_REQUIRE(in && out && count > 0, "lf_cast_f32_bf16: null / empty buffer");
+    cast_f32_bf16_kernel<<<lf::stream_grid(count, kBlock), kBlock, 0, lf::as_stream(stream)>>>(in, out, count);
+    return lf::check_launch("lf_cast_f32_bf16");
+}
+
+int lf_cast_bf16_f32(const uint16_t* in, float* out, size_t count, lf_stream_t stream) {
+    LF_REQUIRE(in && out && count > 0, "lf_cast_bf16_f32: null / empty buffer");
+    cast_bf16_f32_kernel<<<lf::stream_grid(count, kBlock), kBlock, 0, lf::as_stream(stream)>>>(in, out, count);
+    return lf::check_launch("lf_cast_bf16_f32");
 }
 
 }  // extern "C"

@@ -47,7 +47,7 @@ constexpr int kSumT = 256;
 
 using WgBf16Args = lf::WgradBf16Args;
 
-__device__ __forceinline__ float up(unsigned bits16) { return __uint_as_float(bits16 << 16); }
+using lf::bf16_up;
 
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {
     typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -282,8 +282,8 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
                 if (ok) {
 #pragma unroll
                     for (int e = 0; e < G; e += 2) {
-                        gv[e] = up(rg[k][i][e / 2] & 0xffffu);
-                        gv[e + 1] = up(rg[k][i][e / 2] >> 16);
+                        gv[e] = bf16_up(rg[k][i][e / 2] & 0xffffu);
+                        gv[e + 1] = bf16_up(rg[k][i][e / 2] >> 16);
                     }
                     if (bn) {
                         const float c0 = lbn[c], c1 = lbn[32 * COB + c], c2 = lbn[64 * COB + c],
@@ -292,7 +292,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
 #pragma unroll
                         for (int e = 0; e < G; ++e) {
                             const unsigned yw = ry[k][i][e / 2];
-                            const float yv = up((e & 1) ? yw >> 16 : yw & 0xffffu);
+                            const float yv = bf16_up((e & 1) ? yw >> 16 : yw & 0xffffu);
                             float dz = fmaf(gv[e], al, ad);
                             if (p.bn_relu && !(fmaf(yv, c0, c1) > 0.f)) dz = 0.f;
                             gv[e] = fmaf(c2, dz, fmaf(c3, yv, c4));
@@ -350,8 +350,8 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
                     if (ok) {
 #pragma unroll
                         for (int e = 0; e < G; e += 2) {
-                            v[e] = up(rx[k][i][e / 2] & 0xffffu);
-                            v[e + 1] = up(rx[k][i][e / 2] >> 16);
+                            v[e] = bf16_up(rx[k][i][e / 2] & 0xffffu);
+                            v[e + 1] = bf16_up(rx[k][i][e / 2] >> 16);
                         }
                         if (pro) {
                             const float sc = lsc[4 * quad + i], sh = lsc[32 * CIB + 4 * quad + i];
@@ -382,7 +382,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
                 if (hmask >> k & 1u) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        v[i] = RAWH ? up(rh[k][i]) : up(i & 1 ? rh[k][i >> 1] >> 16 : rh[k][i >> 1] & 0xffffu);
+                        v[i] = RAWH ? bf16_up(rh[k][i]) : bf16_up(i & 1 ? rh[k][i >> 1] >> 16 : rh[k][i >> 1] & 0xffffu);
                     if (pro)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {

@@ -418,11 +418,10 @@ class LeafCNN:
                 s = nn.se_fwd(m, P[p + "se.w1"], P[p + "se.b1"], P[p + "se.w2"], P[p + "se.b2"],
                               self._buf(n, p + "z1", (n, f // 8)), self._buf(n, p + "s", (n, f)))
             sc = conv(xin, p + "proj.w", 1, p + "bnp", False) if cin != f else xin
-            xin = nn.block_tail_fwd_bf16(a2, None, None, s, sc, None, None, False,
-                                         out=self._buf(n, "bf16." + p + "p", (n, f, a2.shape[2] // 2,
-                                                                              a2.shape[3] // 2), bf))
+            xin = self._buf(n, "bf16." + p + "p", (n, f, a2.shape[2] // 2, a2.shape[3] // 2), bf)
+            nn.block_tail_fwd(a2, None, None, s, sc, None, None, False, None, None, xin)
             cin = f
-        g = nn.gap_bf16(xin, out=self._buf(n, "g", (n, self.widths[-1])))
+        g = nn.gap(xin, out=self._buf(n, "g", (n, self.widths[-1])))
         probs = self._buf(n, "probs", (n, self.num_classes))
         nn.head_fwd(g, P["dense.w"], P["dense.b"], None, probs, None)
         return probs
@@ -476,7 +475,6 @@ class LeafCNN:
         # the bf16 step has buffers of its own: activations and their gradients in bf16, the rest fp32
         pre, act = ("t16.", torch.bfloat16) if bf16 else ("", F32)
         B = lambda k, shape, dt=act: self._buf(n, pre + k, shape, dt)  # noqa: E731
-        gap, tail = (nn.gap_stats_bf16, nn.block_tail_fwd_train_bf16) if bf16 else (nn.gap, nn.block_tail_fwd)
         sv: Dict[str, Any] = {"x0": x0, "n": n, "bf16": bf16}
         if bf16:
             self._prep_bf16_weights()
@@ -498,8 +496,8 @@ class LeafCNN:
             if self.use_se:
                 # the squeeze pass also leaves BN2's ReLU-mask sums for the backward pass
                 msum = B(p + "msum", (n, f, 2), F32) if training else None
-                m = gap(y2, out=B(p + "m", (n, f), F32), scale=st2[2], shift=st2[3], relu=True,
-                        mask_sums=msum)
+                m = nn.gap(y2, out=B(p + "m", (n, f), F32), scale=st2[2], shift=st2[3], relu=True,
+                           mask_sums=msum)
                 sv[p + "msum"] = msum
                 z1 = B(p + "z1", (n, f // 8), F32)
                 s = nn.se_fwd(m, P[p + "se.w1"], P[p + "se.b1"], P[p + "se.w2"], P[p + "se.b2"], z1,
@@ -515,11 +513,11 @@ class LeafCNN:
             drop = drops[i] if (training and drops is not None) else None
             pooled = B(p + "p", (n, f, h // 2, w // 2))
             route = B(p + "route", pooled.shape, torch.uint8)
-            tail(y2, st2[2], st2[3], s, sc, scs, scb, scr, drop, route, pooled)
+            nn.block_tail_fwd(y2, st2[2], st2[3], s, sc, scs, scb, scr, drop, route, pooled)
             sv.update({p + "xin": xin, p + "xin_st": xin_st, p + "y1": y1, p + "y2": y2, p + "s": s,
                        p + "route": route, p + "drop": drop, p + "hw": (h, w)})
             xin, xin_st, cin, h, w = pooled, None, f, h // 2, w // 2
-        g = gap(xin, out=B("g", (n, self.widths[-1]), F32))
+        g = nn.gap(xin, out=B("g", (n, self.widths[-1]), F32))
         feat = g
         if training and top_drop is not None:
             feat = nn.mul(g, top_drop, B("feat", g.shape, F32))
@@ -562,10 +560,7 @@ class LeafCNN:
         F32 = torch.float32
         pre, act = ("t16.", torch.bfloat16) if bf16 else ("", F32)   # the forward's buffers: see there
         B = lambda k, shape, dt=act: self._buf(n, pre + k, shape, dt)  # noqa: E731
-        if bf16:
-            bcast, tail_bwd, bn_bwd_wgrad = nn.bcast_planes_bf16, nn.block_tail_bwd_bf16, nn.bn_bwd_wgrad_bf16
-        else:
-            bcast, tail_bwd, bn_bwd_wgrad = nn.bcast_planes, nn.block_tail_bwd, nn.bn_bwd_wgrad
+        bn_bwd_wgrad = nn.bn_bwd_wgrad_bf16 if bf16 else nn.bn_bwd_wgrad
         f_last = self.widths[-1]
         if part in (None, 0):
             dlogits = B("dlogits", (n, self.num_classes), F32)
@@ -576,7 +571,7 @@ class LeafCNN:
             if sv["top_drop"] is not None:
                 dg = nn.mul(dfeat, sv["top_drop"], B("dg", dfeat.shape, F32))
             h, w = sv["last_hw"]
-            dp = bcast(dg, h, w, 1.0 / (h * w), B("dp_last", (n, f_last, h, w)))
+            dp = nn.bcast_planes(dg, h, w, 1.0 / (h * w), B("dp_last", (n, f_last, h, w)))
         else:
             dp = sv["bwd_dp"]
         for i in self._backward_stages(part):
@@ -596,7 +591,7 @@ class LeafCNN:
             psum = B(p + "psum", (n, f, 2), F32)
             yp = sv.get(p + "yp")  # projection shortcut: its BN's backward sums ride along
             psum_p = B(p + "psum_p", (n, f, 2), F32) if yp is not None else None
-            tail_bwd(dp, route, y2, st2[2], st2[3], drop, gA, ds, psum, yp, psum_p)
+            nn.block_tail_bwd(dp, route, y2, st2[2], st2[3], drop, gA, ds, psum, yp, psum_p)
             add_nc = None
             if self.use_se:
                 dm = B(p + "dm", (n, f), F32)

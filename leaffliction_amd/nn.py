@@ -148,34 +148,6 @@ def conv2d_bf16_mean(x: torch.Tensor, wprep: torch.Tensor, cout: int, ksize: int
     return out, means
 
 
-def gap_bf16(x: torch.Tensor, scale=None, shift=None, relu: bool = False,
-             out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[N,C] fp32 plane means of relu?(x*scale[c]+shift[c]) for a bf16 NCHW tensor (inference)."""
-    _chk(x, torch.bfloat16, "gap_bf16.x", 4)
-    n, c, h, w = x.shape
-    if out is None:
-        out = torch.empty((n, c), dtype=_F32, device=x.device)
-    _lib.call("lf_gap_bf16", x.data_ptr(), out.data_ptr(), n, c, h * w, _ptr(scale), _ptr(shift),
-              1 if relu else 0, _stream())
-    return out
-
-
-def block_tail_fwd_bf16(y, a_scale, a_shift, s, sc, sc_scale, sc_shift, sc_relu: bool,
-                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """maxpool2x2(relu(shortcut' + relu(y*a_scale+a_shift) * s)) on bf16 NCHW tensors (inference)."""
-    _chk(y, torch.bfloat16, "block_tail_fwd_bf16.y", 4)
-    _chk(sc, torch.bfloat16, "block_tail_fwd_bf16.sc", 4)
-    n, c, h, w = y.shape
-    if tuple(sc.shape) != (n, c, h, w):
-        raise ValueError("block_tail_fwd_bf16.sc: shape mismatch")
-    if out is None:
-        out = torch.empty((n, c, h // 2, w // 2), dtype=torch.bfloat16, device=y.device)
-    _lib.call("lf_block_tail_fwd_bf16", y.data_ptr(), _ptr(a_scale), _ptr(a_shift), _ptr(s),
-              sc.data_ptr(), _ptr(sc_scale), _ptr(sc_shift), 1 if sc_relu else 0, out.data_ptr(), n, c, h, w,
-              _stream())
-    return out
-
-
 # ---------------------------------------------------------------------------
 # mixed-precision training step: bf16 storage, fp32 arithmetic (lf_*_bf16 / *_train_bf16)
 # ---------------------------------------------------------------------------
@@ -246,7 +218,7 @@ def bn_bwd_wgrad_bf16(x: torch.Tensor, g: torch.Tensor, y_bn: torch.Tensor, stat
                       in_scale=None, in_shift=None, in_relu: bool = False, alpha_nc=None, add_nc=None,
                       plane_g=None, plane_m=None, tile_sums=None):
     """bn_bwd_wgrad on bf16 tensors: the BatchNorm-backward sums come from per-plane sums
-    (block_tail_bwd_bf16 / gap_stats_bf16) or per-tile sums (conv2d_bf16_train's epilogue) — never
+    (block_tail_bwd / gap) or per-tile sums (conv2d_bf16_train's epilogue) — never
     from another pass over g and y — and dY = BN'(g) is formed inside the weight-gradient kernel."""
     if x.dtype not in (_F32, _BF16):
         raise TypeError("bn_bwd_wgrad_bf16.x: float32 (stem) or bfloat16")
@@ -300,57 +272,6 @@ def conv2d_wgrad_bf16(x: torch.Tensor, dy: torch.Tensor, ksize: int, in_scale=No
     _lib.call("lf_conv2d_wgrad_bf16", x.data_ptr(), dy.data_ptr(), None, None, None, None, 0, None,
               out.data_ptr(), n, cin, h, w, cout, ksize, _ptr(in_scale), _ptr(in_shift),
               1 if in_relu else 0, ws.data_ptr(), ws.numel(), _stream())
-    return out
-
-
-def gap_stats_bf16(x: torch.Tensor, out=None, scale=None, shift=None, relu: bool = False, mask_sums=None):
-    _chk(x, _BF16, "gap_stats_bf16.x", 4)
-    n, c, h, w = x.shape
-    if out is None:
-        out = torch.empty((n, c), dtype=_F32, device=x.device)
-    if mask_sums is not None and tuple(mask_sums.shape) != (n, c, 2):
-        raise ValueError("gap_stats_bf16.mask_sums: expected [N,C,2]")
-    _lib.call("lf_gap_stats_bf16", x.data_ptr(), out.data_ptr(), _ptr(mask_sums), n, c, h * w, _ptr(scale),
-              _ptr(shift), 1 if relu else 0, _stream())
-    return out
-
-
-def block_tail_fwd_train_bf16(y, a_scale, a_shift, s, sc, sc_scale, sc_shift, sc_relu, drop, route, p):
-    _chk(y, _BF16, "block_tail_fwd_train_bf16.y", 4)
-    _chk(sc, _BF16, "block_tail_fwd_train_bf16.sc", 4)
-    _chk(p, _BF16, "block_tail_fwd_train_bf16.p", 4)
-    _chk(route, torch.uint8, "block_tail_fwd_train_bf16.route", 4)
-    n, c, h, w = y.shape
-    if sc.shape != y.shape or tuple(p.shape) != (n, c, h // 2, w // 2) or route.shape != p.shape:
-        raise ValueError("block_tail_fwd_train_bf16: shape mismatch")
-    _lib.call("lf_block_tail_fwd_train_bf16", y.data_ptr(), _ptr(a_scale), _ptr(a_shift), _ptr(s),
-              sc.data_ptr(), _ptr(sc_scale), _ptr(sc_shift), 1 if sc_relu else 0, _ptr(drop),
-              route.data_ptr(), p.data_ptr(), n, c, h, w, _stream())
-    return route, p
-
-
-def block_tail_bwd_bf16(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums=None, sc_y=None,
-                        sc_sums=None):
-    _chk(dr, _BF16, "block_tail_bwd_bf16.dr", 4)
-    _chk(dp, _BF16, "block_tail_bwd_bf16.dp", 4)
-    _chk(route, torch.uint8, "block_tail_bwd_bf16.route", 4)
-    n, c, h, w = dr.shape
-    if tuple(dp.shape) != (n, c, h // 2, w // 2) or route.shape != dp.shape:
-        raise ValueError("block_tail_bwd_bf16: shape mismatch")
-    for t in (plane_sums, sc_sums):
-        if t is not None and tuple(t.shape) != (n, c, 2):
-            raise ValueError("block_tail_bwd_bf16 plane sums: expected [N,C,2]")
-    _lib.call("lf_block_tail_bwd_bf16", dp.data_ptr(), route.data_ptr(), _ptr(y), _ptr(a_scale),
-              _ptr(a_shift), _ptr(drop), dr.data_ptr(), _ptr(ds), _ptr(plane_sums), _ptr(sc_y),
-              _ptr(sc_sums), n, c, h, w, _stream())
-    return dr, ds
-
-
-def bcast_planes_bf16(v, h, w, scale, out):
-    _chk(v, _F32, "bcast_planes_bf16.v", 2)
-    _chk(out, _BF16, "bcast_planes_bf16.out", 4)
-    n, c = v.shape
-    _lib.call("lf_bcast_planes_bf16", v.data_ptr(), out.data_ptr(), n * c, h * w, float(scale), _stream())
     return out
 
 
@@ -638,10 +559,15 @@ def bn_bwd(g, y, stats, gamma, dgamma, dbeta, relu: bool, alpha_nc=None, add_nc=
     return out
 
 
+def _plane_dtype(t: torch.Tensor, name: str, ndim: int):
+    """Checks a plane-kernel tensor stored as fp32 or bf16 and returns its dtype."""
+    return _chk(t, _BF16 if t.dtype == _BF16 else _F32, name, ndim).dtype
+
+
 def gap(x, out=None, scale=None, shift=None, relu: bool = False, mask_sums=None):
-    """[N,C,H,W] -> [N,C] mean of act(x*scale[c]+shift[c]) (plain mean without scale).
+    """[N,C,H,W] fp32 or bf16 -> [N,C] fp32 mean of act(x*scale[c]+shift[c]) (plain mean without scale).
     mask_sums [N,C,2] (optional) receives {count of x*scale+shift > 0, sum of x over those}."""
-    _chk(x, _F32, "gap.x", 4)
+    bf16 = _plane_dtype(x, "gap.x", 4) == _BF16
     n, c, h, w = x.shape
     if out is None:
         out = torch.empty((n, c), dtype=_F32, device=x.device)
@@ -649,18 +575,23 @@ def gap(x, out=None, scale=None, shift=None, relu: bool = False, mask_sums=None)
         _chk(mask_sums, _F32, "gap.mask_sums", 3)
         if tuple(mask_sums.shape) != (n, c, 2):
             raise ValueError("gap.mask_sums: expected [N,C,2]")
-    _lib.call("lf_gap_f32", x.data_ptr(), out.data_ptr(), n * c, h * w, c, _ptr(scale), _ptr(shift),
-              1 if relu else 0, _ptr(mask_sums), _stream())
+    if bf16:
+        _lib.call("lf_gap_stats_bf16", x.data_ptr(), out.data_ptr(), _ptr(mask_sums), n, c, h * w, _ptr(scale),
+                  _ptr(shift), 1 if relu else 0, _stream())
+    else:
+        _lib.call("lf_gap_f32", x.data_ptr(), out.data_ptr(), n * c, h * w, c, _ptr(scale), _ptr(shift),
+                  1 if relu else 0, _ptr(mask_sums), _stream())
     return out
 
 
 def bcast_planes(v, h, w, scale, out=None):
+    """out[n,c,:,:] = v[n,c] * scale; out is fp32 (allocated when None) or bf16."""
     _chk(v, _F32, "bcast_planes.v", 2)
     n, c = v.shape
     if out is None:
         out = torch.empty((n, c, h, w), dtype=_F32, device=v.device)
-    _lib.call("lf_bcast_planes_f32", v.data_ptr(), out.data_ptr(), n * c, h * w, float(scale),
-              _stream())
+    entry = "lf_bcast_planes_bf16" if _plane_dtype(out, "bcast_planes.out", 4) == _BF16 else "lf_bcast_planes_f32"
+    _lib.call(entry, v.data_ptr(), out.data_ptr(), n * c, h * w, float(scale), _stream())
     return out
 
 
@@ -687,21 +618,26 @@ def se_bwd(ds, m, z1, s, w1, w2, dm, dw1, db1, dw2, db2, dm_scale: float = 1.0):
 
 
 def block_tail_fwd(y, a_scale, a_shift, s, sc, sc_scale, sc_shift, sc_relu, drop, route, p):
-    """Add -> ReLU -> SpatialDropout2D -> MaxPool2D(2); route: uint8 [N,C,H/2,W/2] (written)."""
-    _chk(y, _F32, "block_tail_fwd.y", 4)
-    _chk(route, torch.uint8, "block_tail_fwd.route", 4)
+    """Add -> ReLU -> SpatialDropout2D -> MaxPool2D(2) on fp32 or bf16 tensors; route: uint8 [N,C,H/2,W/2]
+    (written), or None on bf16 tensors when no backward pass follows."""
+    dt = _plane_dtype(y, "block_tail_fwd.y", 4)
+    _chk(sc, dt, "block_tail_fwd.sc", 4)
+    _chk(p, dt, "block_tail_fwd.p", 4)
     n, c, h, w = y.shape
-    if sc.shape != y.shape or tuple(p.shape) != (n, c, h // 2, w // 2) or route.shape != p.shape:
+    if route is not None:
+        _chk(route, torch.uint8, "block_tail_fwd.route", 4)
+    if sc.shape != y.shape or tuple(p.shape) != (n, c, h // 2, w // 2) or (route is not None and route.shape != p.shape):
         raise ValueError("block_tail_fwd: shape mismatch")
-    _lib.call("lf_block_tail_fwd_f32", y.data_ptr(), _ptr(a_scale), _ptr(a_shift), _ptr(s),
-              sc.data_ptr(), _ptr(sc_scale), _ptr(sc_shift), 1 if sc_relu else 0, _ptr(drop),
-              route.data_ptr(), p.data_ptr(), n, c, h, w, _stream())
+    entry = "lf_block_tail_fwd_train_bf16" if dt == _BF16 else "lf_block_tail_fwd_f32"
+    _lib.call(entry, y.data_ptr(), _ptr(a_scale), _ptr(a_shift), _ptr(s), sc.data_ptr(), _ptr(sc_scale),
+              _ptr(sc_shift), 1 if sc_relu else 0, _ptr(drop), _ptr(route), p.data_ptr(), n, c, h, w, _stream())
     return route, p
 
 
 def block_tail_bwd(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums=None, sc_y=None,
                    sc_sums=None):
-    _chk(dr, _F32, "block_tail_bwd.dr", 4)
+    dt = _plane_dtype(dr, "block_tail_bwd.dr", 4)
+    _chk(dp, dt, "block_tail_bwd.dp", 4)
     _chk(route, torch.uint8, "block_tail_bwd.route", 4)
     n, c, h, w = dr.shape
     if tuple(dp.shape) != (n, c, h // 2, w // 2) or route.shape != dp.shape:
@@ -711,9 +647,9 @@ def block_tail_bwd(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums=None
             raise ValueError("block_tail_bwd plane sums: expected [N,C,2]")
     if sc_y is not None and sc_y.shape != dr.shape:
         raise ValueError("block_tail_bwd.sc_y: shape mismatch")
-    _lib.call("lf_block_tail_bwd_f32", dp.data_ptr(), route.data_ptr(), _ptr(y), _ptr(a_scale),
-              _ptr(a_shift), _ptr(drop), dr.data_ptr(), _ptr(ds), _ptr(plane_sums), _ptr(sc_y),
-              _ptr(sc_sums), n, c, h, w, _stream())
+    entry = "lf_block_tail_bwd_bf16" if dt == _BF16 else "lf_block_tail_bwd_f32"
+    _lib.call(entry, dp.data_ptr(), route.data_ptr(), _ptr(y), _ptr(a_scale), _ptr(a_shift), _ptr(drop),
+              dr.data_ptr(), _ptr(ds), _ptr(plane_sums), _ptr(sc_y), _ptr(sc_sums), n, c, h, w, _stream())
     return dr, ds
 
 

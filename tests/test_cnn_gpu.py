@@ -324,7 +324,7 @@ def test_bf16_inference_cache_follows_every_kind_of_parameter_write(cuda):
                                                (2, 3, 32, 64, False)])     # fp32 input (the stem's shape)
 def test_conv2d_bf16_mean_equals_conv_then_gap(cuda, n, cin, cout, hw, xbf):
     """lf_conv2d_bf16_act_mean (inference: a block's second convolution + the squeeze of its SE gate in one pass):
-    the stored activation is BIT-equal to lf_conv2d_bf16_act's, and the means equal lf_gap_bf16's means of that
+    the stored activation is BIT-equal to lf_conv2d_bf16_act's, and the means equal lf_gap_stats_bf16's means of that
     stored tensor up to fp32 summation order (per-segment / per-tile partial sums instead of one plane sum)."""
     from leaffliction_amd import nn
     g = torch.Generator().manual_seed(hw + cin)
@@ -334,7 +334,7 @@ def test_conv2d_bf16_mean_equals_conv_then_gap(cuda, n, cin, cout, hw, xbf):
     osc, osh = (torch.rand(cout, generator=g) + 0.5).to(cuda), (torch.randn(cout, generator=g) * 0.3).to(cuda)
     wp = nn.conv2d_bf16_weights(w, 3)
     ref = nn.conv2d_bf16(x, wp, cout, 3, out_dtype=torch.bfloat16, out_scale=osc, out_shift=osh, out_relu=True)
-    ref_m = nn.gap_bf16(ref)
+    ref_m = nn.gap(ref)
     out = torch.full((n, cout, hw, hw), float("nan"), dtype=torch.bfloat16, device=cuda)
     means = torch.full((n, cout), float("nan"), device=cuda)
     nn.conv2d_bf16_mean(x, wp, cout, 3, out, means, out_scale=osc, out_shift=osh, out_relu=True)

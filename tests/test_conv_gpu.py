@@ -337,28 +337,34 @@ def test_bf16_plane_kernels(cuda):
     """gap / residual-tail on bf16 tensors == the fp32 kernels on the widened tensors (then
     rounded for the bf16 output)."""
     from leaffliction_amd import nn
-    g = torch.Generator().manual_seed(4)
-    n, c, h, w = 3, 64, 28, 28
-    y = torch.randn((n, c, h, w), generator=g).to(cuda).to(torch.bfloat16)
-    sc = torch.randn((n, c, h, w), generator=g).to(cuda).to(torch.bfloat16)
-    a_s, a_b = (torch.rand(c, generator=g) + 0.5).to(cuda), (torch.randn(c, generator=g) * 0.2).to(cuda)
-    k_s, k_b = (torch.rand(c, generator=g) + 0.5).to(cuda), (torch.randn(c, generator=g) * 0.2).to(cuda)
-    gate = torch.rand((n, c), generator=g).to(cuda)
-    m16 = nn.gap_bf16(y, a_s, a_b, True)
-    m32 = nn.gap(y.float(), scale=a_s, shift=a_b, relu=True)
-    assert (m16 - m32).abs().max().item() < 1e-5
-    assert (nn.gap_bf16(y) - y.float().mean((2, 3))).abs().max().item() < 1e-5
-    for sc_scale, sc_shift, sc_relu, s in ((k_s, k_b, True, gate), (k_s, k_b, False, gate), (None, None, False, None)):
-        p16 = nn.block_tail_fwd_bf16(y, a_s, a_b, s, sc, sc_scale, sc_shift, sc_relu)
-        route = torch.empty((n, c, h // 2, w // 2), dtype=torch.uint8, device=cuda)
-        p32 = torch.empty((n, c, h // 2, w // 2), device=cuda)
-        nn.block_tail_fwd(y.float(), a_s, a_b, s, sc.float(), sc_scale, sc_shift, sc_relu, None, route, p32)
-        assert torch.equal(p16, p32.to(torch.bfloat16))
-    # already-activated input (a_scale = None): relu(shortcut + y * gate), pooled
-    ya = torch.relu(y.float()).to(torch.bfloat16)
-    p16 = nn.block_tail_fwd_bf16(ya, None, None, gate, sc, None, None, False)
-    want = torch.nn.functional.max_pool2d(torch.relu(sc.float() + ya.float() * gate[:, :, None, None]), 2)
-    assert torch.equal(p16, want.to(torch.bfloat16))
+    for n, c, h, w in ((3, 64, 28, 28), (3, 64, 56, 56)):   # w % 8 == 0 at 56: the 16-byte path
+        g = torch.Generator().manual_seed(4)
+        y = torch.randn((n, c, h, w), generator=g).to(cuda).to(torch.bfloat16)
+        sc = torch.randn((n, c, h, w), generator=g).to(cuda).to(torch.bfloat16)
+        a_s, a_b = (torch.rand(c, generator=g) + 0.5).to(cuda), (torch.randn(c, generator=g) * 0.2).to(cuda)
+        k_s, k_b = (torch.rand(c, generator=g) + 0.5).to(cuda), (torch.randn(c, generator=g) * 0.2).to(cuda)
+        gate = torch.rand((n, c), generator=g).to(cuda)
+        m16 = nn.gap(y, scale=a_s, shift=a_b, relu=True)
+        m32 = nn.gap(y.float(), scale=a_s, shift=a_b, relu=True)
+        assert (m16 - m32).abs().max().item() < 1e-5
+        assert (nn.gap(y) - y.float().mean((2, 3))).abs().max().item() < 1e-5
+        for sc_scale, sc_shift, sc_relu, s in ((k_s, k_b, True, gate), (k_s, k_b, False, gate),
+                                               (None, None, False, None)):
+            p16 = torch.empty((n, c, h // 2, w // 2), dtype=torch.bfloat16, device=cuda)
+            nn.block_tail_fwd(y, a_s, a_b, s, sc, sc_scale, sc_shift, sc_relu, None, None, p16)
+            route = torch.empty((n, c, h // 2, w // 2), dtype=torch.uint8, device=cuda)
+            p32 = torch.empty((n, c, h // 2, w // 2), device=cuda)
+            nn.block_tail_fwd(y.float(), a_s, a_b, s, sc.float(), sc_scale, sc_shift, sc_relu, None, route, p32)
+            assert torch.equal(p16, p32.to(torch.bfloat16))
+        # already-activated input (a_scale = None): relu(shortcut + y * gate), pooled
+        ya = torch.relu(y.float()).to(torch.bfloat16)
+        p16 = torch.empty((n, c, h // 2, w // 2), dtype=torch.bfloat16, device=cuda)
+        nn.block_tail_fwd(ya, None, None, gate, sc, None, None, False, None, None, p16)
+        # the kernel forms shortcut + y * gate as one fused multiply-add (one rounding to fp32), so the
+        # reference takes it in float64 and rounds to fp32 once
+        r = (sc.double() + ya.double() * gate.double()[:, :, None, None]).float()
+        want = torch.nn.functional.max_pool2d(torch.relu(r), 2)
+        assert torch.equal(p16, want.to(torch.bfloat16))
 
 
 def test_conv2d_bf16_serves_as_input_gradient(cuda):

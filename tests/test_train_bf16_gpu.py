@@ -198,7 +198,7 @@ def test_plane_kernels_bf16(cuda):
     d = lambda t: t.to(dev)  # noqa: E731
     # gap + mask sums
     msum = torch.empty(n, c, 2, device=dev)
-    m = nn.gap_stats_bf16(d(y), scale=d(a_s), shift=d(a_b), relu=True, mask_sums=msum)
+    m = nn.gap(d(y), scale=d(a_s), shift=d(a_b), relu=True, mask_sums=msum)
     v = y.float() * a_s.view(1, -1, 1, 1) + a_b.view(1, -1, 1, 1)
     assert torch.allclose(m.cpu(), torch.relu(v).mean((2, 3)), atol=1e-5)
     assert torch.equal(msum[..., 0].cpu(), (v > 0).float().sum((2, 3)))
@@ -206,7 +206,7 @@ def test_plane_kernels_bf16(cuda):
     # tail forward
     pooled = torch.empty(n, c, h // 2, w // 2, dtype=BF, device=dev)
     route = torch.empty(n, c, h // 2, w // 2, dtype=torch.uint8, device=dev)
-    nn.block_tail_fwd_train_bf16(d(y), d(a_s), d(a_b), d(s), d(sc_t), d(k_s), d(k_b), True, d(drop), route, pooled)
+    nn.block_tail_fwd(d(y), d(a_s), d(a_b), d(s), d(sc_t), d(k_s), d(k_b), True, d(drop), route, pooled)
     a2 = torch.relu(v)
     shc = torch.relu(sc_t.float() * k_s.view(1, -1, 1, 1) + k_b.view(1, -1, 1, 1))
     r = torch.relu(shc + a2 * s.view(n, c, 1, 1))
@@ -219,7 +219,7 @@ def test_plane_kernels_bf16(cuda):
     ds = torch.empty(n, c, device=dev)
     psum = torch.empty(n, c, 2, device=dev)
     ssum = torch.empty(n, c, 2, device=dev)
-    nn.block_tail_bwd_bf16(d(dp), route, d(y), d(a_s), d(a_b), d(drop), dr, ds, psum, d(sc_t), ssum)
+    nn.block_tail_bwd(d(dp), route, d(y), d(a_s), d(a_b), d(drop), dr, ds, psum, d(sc_t), ssum)
     gq = (dp.float() * drop.view(n, c, 1, 1)).to(BF).float() * (mp > 0)
     dr_ref = F.max_unpool2d(gq, idx, 2, output_size=(h, w))
     assert torch.equal(dr.float().cpu(), dr_ref)          # routing + rounding: exact
@@ -232,7 +232,7 @@ def test_plane_kernels_bf16(cuda):
     # broadcast + casts
     vv = torch.randn(n, c, generator=g)
     out = torch.empty(n, c, 4, 4, dtype=BF, device=dev)
-    nn.bcast_planes_bf16(d(vv), 4, 4, 1.0 / 16, out)
+    nn.bcast_planes(d(vv), 4, 4, 1.0 / 16, out)
     assert torch.equal(out.float().cpu(), (vv / 16).to(BF).float().view(n, c, 1, 1).expand(n, c, 4, 4))
     f = torch.randn(1000, generator=g)
     b16 = nn.cast_f32_bf16(d(f), torch.empty(1000, dtype=BF, device=dev))
