@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: leaf_cnn training images/sec on MI355X (BASELINE.json config C2).
 
-    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full training step of the reference's `srcs/cli/train.py` path on one
@@ -11,9 +11,12 @@ cross-entropy, backward, (N>1: one RCCL all-reduce of the flat gradient bucket),
 per-tensor clipnorm + cosine LR, EMA.  fp32 throughout (BASELINE.json configs[1]); weak
 scaling: every rank keeps batch 256.
 
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel,
-algorithmic FLOP / measured launch duration from HIP events recorded inside the timed
-region) and `cpu_baseline` (the torch-CPU oracle's training step on the host cores).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the contract fields: nothing else runs.  With --full the line also
+carries `roofline` (dominant kernel, algorithmic FLOP / launch duration from HIP events in an
+eager pass after the timed region), the bf16 step as a second mode, forward-only and
+augmentation rates, the end-to-end jobs and `cpu_baseline` (the torch-CPU oracle's training
+step on the host cores); the --no-* options leave parts of that out.
 """
 from __future__ import annotations
 
@@ -681,6 +684,39 @@ def predict_end_to_end(dev, n_files=4096):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def f32_roofline(kern, ksteps):
+    """`roofline` and `conv_all` of the fp32 line from the eager pass's per-kernel summary (--full)."""
+    dom_name, dom = max(kern.items(), key=lambda kv: kv[1]["seconds"])
+    achieved = dom["flop"] / dom["seconds"] / 1e12
+    conv_s = sum(v["seconds"] for v in kern.values())
+    conv_f = sum(v["flop"] for v in kern.values())
+    # HBM bytes per launch from rocprofv3 PMC passes are NOT taken in this run (counters need their
+    # own passes): the figure is the committed summary's, with where it came from next to it
+    traffic, traffic_source = None, None
+    pmc = ROOT / "profiles" / "pmc_latest.json"
+    if pmc.exists():
+        try:
+            doc = json.loads(pmc.read_text())
+            traffic = doc.get(dom_name)
+            traffic_source = {"file": "profiles/pmc_latest.json", **doc.get("_source", {"command": "scripts/profile_round.sh (round 1, tag j)"})}
+        except Exception:
+            traffic = None
+    return {"roofline": {"bound": "mfma", "kernel": dom_name,
+                         "achieved": round(achieved, 2), "peak": F32_MFMA_PEAK_TFLOPS,
+                         "unit": "TFLOP/s", "frac": round(achieved / F32_MFMA_PEAK_TFLOPS, 4),
+                         "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)",
+                         "traffic_source": traffic_source,
+                         "algorithmic_bytes_per_launch": round(dom["bytes"] / dom["launches"]),
+                         "launches_per_step": dom["launches"] / ksteps,
+                         "measured": f"HIP events around each launch, {ksteps} eager steps right after the timed "
+                                     "region (which replays the step as one HIP graph)",
+                         "avg_launch_ms": round(dom["seconds"] / dom["launches"] * 1e3, 4),
+                         "algorithmic_gflop_per_launch": round(dom["flop"] / dom["launches"] / 1e9, 3)},
+            "conv_all": {"tflops": round(conv_f / conv_s / 1e12, 2),
+                         "frac_of_mfma_peak": round(conv_f / conv_s / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
+                         "ms_per_step": round(conv_s / ksteps * 1e3, 3)}}
+
+
 DUMP_MAX_BYTES = 64 << 20
 
 
@@ -719,13 +755,16 @@ def main() -> None:
     ap.add_argument("--warmup", type=_nonnegative_int, default=10)
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (weak scaling)")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
-                    help="f32 = BASELINE configs[1] (the headline line, with the bf16 step as a second mode "
+                    help="f32 = BASELINE configs[1] (the headline line; --full adds the bf16 step as a second mode "
                          "inside it); bf16 = the mixed-precision step as the headline (configs[3] per-GPU work)")
-    ap.add_argument("--no-bf16", action="store_true", help="f32 run: skip the second (bf16) training mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-augment", action="store_true", help="skip the augmentation-pass measurement")
-    ap.add_argument("--no-inference", action="store_true", help="skip the forward-only measurement")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end Augmentation.py measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also measure everything else: per-kernel roofline figures, the "
+                         "bf16 step as a second mode, forward-only, augmentation and end-to-end rates, CPU baselines")
+    ap.add_argument("--no-bf16", action="store_true", help="--full f32 run: skip the second (bf16) training mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-augment", action="store_true", help="--full: skip the augmentation-pass measurement")
+    ap.add_argument("--no-inference", action="store_true", help="--full: skip the forward-only measurement")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end Augmentation.py measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the headline step returned in its last timed step (probabilities, per-sample "
                          "loss) and the parameters it left as DIR/<name>.npy, float32, rank 0")
@@ -900,10 +939,11 @@ def main() -> None:
         # before anything else runs a step: the graph's output buffers and the parameters are the last timed step's
         dump_outputs(Path(args.dump_outputs), {"probs": last_probs, "loss": last_loss, "params": model.flat_p})
     timer.records.clear()
-    ksteps = kernel_pass()
-    if args.dtype == "bf16":
+    if args.full and args.dtype == "bf16":
+        ksteps = kernel_pass()
         bf16 = bf16_report(elapsed, args.steps, final_loss, ksteps)
-    else:
+    elif args.full:
+        ksteps = kernel_pass()
         kern_f32 = timer.summary()
         timer.records.clear()
         if not args.no_bf16:
@@ -916,39 +956,28 @@ def main() -> None:
             model.set_training_dtype("f32")
             timer.records.clear()
 
+    images = world * n * args.steps
     if rank == 0 and args.dtype == "bf16":
-        out = {"metric": "224x224 images/sec train", "value": bf16["images_per_sec"], "unit": "images/sec",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": bf16["ms_per_step"],
+        out = {"metric": "224x224 images/sec train", "value": round(images / elapsed, 2), "unit": "images/sec",
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": round(elapsed / args.steps * 1e3, 3),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
                "data": "synthetic",
                "config": {"workload": "leaf_cnn base train step, mixed precision (configs[3] per-GPU work: img 224, "
                                       "batch 256/GPU, bf16, 8 classes, AdamW+clipnorm+EMA, in-model augmentation)",
                           "per_gpu_batch": n, "global_batch": world * n, "img_size": IMG,
                           "parallelism": f"dp{world}", "grad_bucket": dp.bucket_dtype if dp is not None else None,
-                          "grad_overlap": bool(dp is not None and dp.overlap)},
-               "roofline": bf16["roofline"], "conv_all": bf16["conv_all"], "step_tflops": bf16["step_tflops"],
-               "final_loss": bf16["final_loss"], "per_kernel": bf16["per_kernel"]}
-        if not args.no_cpu_baseline and world == 1:
+                          "grad_overlap": bool(dp is not None and dp.overlap)}}
+        if bf16 is not None:
+            out["roofline"], out["conv_all"] = bf16["roofline"], bf16["conv_all"]
+        out["step_tflops"] = round(TRAIN_GFLOP_PER_IMG * n * args.steps / elapsed / 1e3, 2)
+        out["final_loss"] = round(final_loss, 4)
+        if bf16 is not None:
+            out["per_kernel"] = bf16["per_kernel"]
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     elif rank == 0:
-        kern = kern_f32
-        dom_name, dom = max(kern.items(), key=lambda kv: kv[1]["seconds"])
-        achieved = dom["flop"] / dom["seconds"] / 1e12
-        conv_s = sum(v["seconds"] for v in kern.values())
-        conv_f = sum(v["flop"] for v in kern.values())
-        # HBM bytes per launch from rocprofv3 PMC passes are NOT taken in this run (counters need their
-        # own passes): the figure is the committed summary's, with where it came from next to it
-        traffic, traffic_source = None, None
-        pmc = ROOT / "profiles" / "pmc_latest.json"
-        if pmc.exists():
-            try:
-                doc = json.loads(pmc.read_text())
-                traffic = doc.get(dom_name)
-                traffic_source = {"file": "profiles/pmc_latest.json", **doc.get("_source", {"command": "scripts/profile_round.sh (round 1, tag j)"})}
-            except Exception:
-                traffic = None
-        images = world * n * args.steps
         out = {
             "metric": "224x224 images/sec train",
             "value": round(images / elapsed, 2),
@@ -966,31 +995,19 @@ def main() -> None:
                                    "fp32, 8 classes, AdamW+clipnorm+EMA, in-model augmentation)",
                        "per_gpu_batch": n, "global_batch": world * n, "img_size": IMG,
                        "parallelism": f"dp{world}"},
-            "roofline": {"bound": "mfma", "kernel": dom_name,
-                         "achieved": round(achieved, 2), "peak": F32_MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / F32_MFMA_PEAK_TFLOPS, 4),
-                         "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)",
-                         "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": round(dom["bytes"] / dom["launches"]),
-                         "launches_per_step": dom["launches"] / ksteps,
-                         "measured": f"HIP events around each launch, {ksteps} eager steps right after the timed "
-                                     "region (which replays the step as one HIP graph)",
-                         "avg_launch_ms": round(dom["seconds"] / dom["launches"] * 1e3, 4),
-                         "algorithmic_gflop_per_launch": round(dom["flop"] / dom["launches"] / 1e9, 3)},
-            "conv_all": {"tflops": round(conv_f / conv_s / 1e12, 2),
-                         "frac_of_mfma_peak": round(conv_f / conv_s / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
-                         "ms_per_step": round(conv_s / ksteps * 1e3, 3)},
-            "hip_graph": bool(model._graphs_on),
-            "step_tflops": round(TRAIN_GFLOP_PER_IMG * n * args.steps / elapsed / 1e3, 2),
-            "final_loss": round(final_loss, 4),
         }
+        if kern_f32 is not None:
+            out.update(f32_roofline(kern_f32, ksteps))
+        out["hip_graph"] = bool(model._graphs_on)
+        out["step_tflops"] = round(TRAIN_GFLOP_PER_IMG * n * args.steps / elapsed / 1e3, 2)
+        out["final_loss"] = round(final_loss, 4)
         if bf16 is not None:
             out["train_bf16"] = bf16
-        if world == 1 and not args.no_inference:
+        if args.full and world == 1 and not args.no_inference:
             out["inference"] = inference_throughput(model, dev)
             if not args.no_e2e:
                 out["inference"]["predict_end_to_end"] = predict_end_to_end(dev)
-        if not args.no_augment and world == 1:
+        if args.full and not args.no_augment and world == 1:
             del model
             torch.cuda.empty_cache()
             out["augment"] = augment_throughput(dev)
@@ -999,7 +1016,7 @@ def main() -> None:
                 out["augment"]["cpu_baseline"] = cpu_augment_baseline()
             if not args.no_e2e:
                 out["augment"]["end_to_end"] = augment_end_to_end(dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dp is not None:
