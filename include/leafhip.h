@@ -202,6 +202,36 @@ int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t
                     const lf_make_mask_params* params, int cap, const uint16_t* kq15, void* workspace,
                     size_t ws_bytes, lf_stream_t stream);
 
+/* apply_brown_filter (srcs/transform/filters/brown.py) for a same-size batch: leaf = mask > 0; the brown predicate
+ * on the pixel as handed in (8-bit HSV lo <= h <= hi, s >= s_min, v <= v_max, or L*a*b* a >= a_min, b >= b_min
+ * when use_lab_brown) inside the leaf; MORPH_OPEN then MORPH_CLOSE with the (k, k) MORPH_ELLIPSE element
+ * (k = morph_kernel in [1, 31]); 8-connected components of area >= min_area_px kept.
+ * rgb [N,H,W,3], mask [N,H,W] -> out [N,H,W,3] (kept pixels set to (255, 100, 0)), stats [N][3] int32
+ * {count, brown area, leaf area}; flags [N]: bit 2 a step bound was hit (a bug: treat as an error).  An image must
+ * fit one workgroup's LDS (two bit planes, 140 KiB): larger sizes are rejected before any launch.  Parity
+ * unpinned (no cv2). */
+typedef struct {
+    int use_lab_brown;                 /* 0 HSV, 1 L*a*b* */
+    int hue_lo, hue_hi, s_min, v_max;  /* brown_hue_range, brown_s_min, brown_v_max */
+    int lab_a_min, lab_b_min;
+    int min_area_px, morph_kernel;     /* brown_min_area_px, brown_morph_kernel */
+} lf_brown_params;
+size_t lf_brown_spots_workspace(int n, int h, int w);
+int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int32_t* stats, int32_t* flags,
+                      int n, int h, int w, const lf_brown_params* params, void* workspace, size_t ws_bytes,
+                      lf_stream_t stream);
+
+/* apply_roi_filter (srcs/transform/filters/roi.py) for a batch, reading the contour buffer lf_make_mask_u8 made
+ * (contour [N,cap,2] int32 (x, y), counts [N]; counts[i] <= cap, points inside the image): bbox [N][4] int32
+ * (x, y, w, h) = cv2.boundingRect; canvas [N,roi_h,roi_w,3] = the box letterboxed into the canvas (INTER_AREA,
+ * zero border); vis [N,H,W,3] = the input with the box drawn (cv2.rectangle, (255, 0, 0), thickness 2).
+ * flags [N]: bit 0 the image has a contour (else vis is the input, canvas and bbox are zero), bit 2 a count above
+ * cap or a point outside the image (an error).  The cv2 readings: the comment above roi_kernel in
+ * lf_filters.hip.  No workspace.  Parity unpinned (no cv2). */
+int lf_roi_u8(const uint8_t* rgb, const int32_t* contour, const int32_t* counts, int cap, uint8_t* canvas,
+              uint8_t* vis, int32_t* bbox, int32_t* flags, int n, int h, int w, int roi_h, int roi_w,
+              lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* JPEG encode (the file Pillow's Image.save(path, quality=q) writes)          */
 /* ------------------------------------------------------------------------- */

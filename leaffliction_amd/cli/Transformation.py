@@ -1,0 +1,400 @@
+#!/usr/bin/env python3
+"""`Transformation.py <image> | -src DIR -dst OUTDIR [--types ...] [--workers N]` on the GPU.
+
+Same flags, output names and data flow as the reference CLI (srcs/cli/Transformation.py): per image
+`<stem>__T_<Type>.jpg` for the requested types, in `--out-dir` (default artifacts/transformations/<n>) for one
+image, flat in DST for a folder.  Per image, as process_single_image does it: make_mask on the image; `masked` =
+the image on white outside the mask; Mask = the image on black; Blur = apply_blur_filter(masked), which runs
+make_mask a second time, on `masked`; ROI = the box drawn on `masked` (or `masked` without a contour); Brown on
+(masked, mask); Hist on `masked`.
+
+Images are decoded on host threads (Pillow, EXIF transpose, RGB), grouped by size, and every stage runs as one
+batched launch over chunks of bounded size; outputs are encoded on the GPU (quality 95, the balancer's encoder).
+Not ported, each with one warning per run and no file: Analyze and Landmarks (PlantCV shape analysis, CLAHE /
+bilateral filtering, goodFeaturesToTrack) and the mosaic (cv2's Hershey text).  Hist is this project's own
+matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped.
+"""
+from __future__ import annotations
+
+import argparse
+import logging
+import os
+import re
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ..utils.common import setup_logging
+
+IMAGE_EXTS = {".jpg"}
+DEFAULT_TYPES = ("Blur", "Mask", "ROI", "Analyze", "Landmarks", "Hist", "Brown")
+CANONICAL_TYPES: Dict[str, str] = {
+    "blur": "Blur",
+    "mask": "Mask",
+    "roi": "ROI",
+    "analyze": "Analyze",
+    "analyse": "Analyze",
+    "landmarks": "Landmarks",
+    "pseudolandmarks": "Landmarks",
+    "pseudo-landmarks": "Landmarks",
+    "hist": "Hist",
+    "histogram": "Hist",
+    "brown": "Brown",
+    "disease": "Brown",
+    "spots": "Brown",
+}
+NOT_PORTED = ("Analyze", "Landmarks")
+MASK_TYPES = ("Mask", "ROI", "Analyze", "Landmarks", "Brown", "Blur")   # the types that run make_mask first
+JPEG_QUALITY = 95
+CHUNK = 64          # images per batched launch
+WINDOW = 4 * CHUNK  # files decoded ahead
+
+
+def build_types_filter(arg: Optional[str]) -> Tuple[str, ...]:
+    """Comma-separated names, case-insensitive, aliases folded, duplicates dropped; unknown names are warned about
+    and skipped; nothing left means all seven types."""
+    if not arg:
+        return DEFAULT_TYPES
+    result: List[str] = []
+    for s in (s.strip() for s in str(arg).split(",")):
+        if not s:
+            continue
+        name = CANONICAL_TYPES.get(s.lower())
+        if name is None:
+            logging.warning("Unknown transform type skipped: %s", s)
+        elif name not in result:
+            result.append(name)
+    return tuple(result) if result else DEFAULT_TYPES
+
+
+def output_names(stem: str) -> Dict[str, str]:
+    return {t: f"{stem}__T_{t}.jpg" for t in DEFAULT_TYPES}
+
+
+def image_number(stem: str) -> str:
+    """`<n>` of a stem like "image (<n>)", else the stem."""
+    match = re.search(r"image \((\d+)\)", stem)
+    return match.group(1) if match else stem
+
+
+def default_out_dir(image: Path) -> Path:
+    """artifacts/transformations/<n> under the repository root (single-image mode without --out-dir)."""
+    return Path(__file__).resolve().parents[2] / "artifacts" / "transformations" / image_number(image.stem)
+
+
+def is_image(path: Path) -> bool:
+    return path.is_file() and path.suffix.lower() in IMAGE_EXTS
+
+
+def iter_images_in_dir(src: Path) -> Iterable[Path]:
+    """Every .jpg (any letter case) under src, nested directories included, in sorted path order."""
+    for p in sorted(src.rglob("*")):
+        if is_image(p):
+            yield p
+
+
+def should_write(out: Path, skip_existing: bool, overwrite: bool) -> bool:
+    return overwrite or not skip_existing or not out.exists()
+
+
+def pil_read_rgb(path: Path) -> np.ndarray:
+    from PIL import Image, ImageOps
+
+    with Image.open(path) as im:
+        im = ImageOps.exif_transpose(im)
+        im = im.convert("RGB")
+        return np.array(im)
+
+
+def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    p = argparse.ArgumentParser(
+        description=("Image transformation pipeline (GPU).\n"
+                     "- Single image: Transformation.py path/to/image.jpg\n"
+                     "- Folder mode: Transformation.py -src DIR -dst OUTDIR [--workers N]"))
+    p.add_argument("image", nargs="?", help="Path to a single image for preview mode")
+    p.add_argument("--out-dir", default=None, help="Output directory for single image preview")
+    p.add_argument("-src", "--src", default=None, help="Source directory (folder mode)")
+    p.add_argument("-dst", "--dst", default=None, help="Destination directory (folder mode)")
+    p.add_argument("--types", default=",".join(DEFAULT_TYPES), help="Comma-separated transforms to run")
+    p.add_argument("--config", default=None,
+                   help="YAML config path (optional; default: the values of the reference's config.yaml)")
+    p.add_argument("--workers", type=int, default=0, help="Host threads for decode / encode (0=auto)")
+    p.add_argument("--skip-existing", action="store_true", help="Skip images whose outputs already exist")
+    p.add_argument("--overwrite", action="store_true", help="Overwrite existing outputs")
+    p.add_argument("--preview", action="store_true", help="Force saving outputs (no GUI popups)")
+    return p.parse_args(argv)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Hist: the GPU numbers (analyze_color_regions, hue_range_counts, hsv_density_curves) drawn with matplotlib
+# ---------------------------------------------------------------------------------------------------------------
+
+def _have_matplotlib() -> bool:
+    try:
+        import matplotlib  # noqa: F401
+        from matplotlib.backends.backend_agg import FigureCanvasAgg  # noqa: F401
+        from matplotlib.figure import Figure  # noqa: F401
+    except Exception:
+        return False
+    return True
+
+
+def hist_numbers(counts: np.ndarray, hist: np.ndarray):
+    """(region percentages, hue-range counts, density curves) of one image from ops.hsv_region_stats' rows — the
+    same numbers transform.analyze_color_regions / hue_range_counts / hsv_density_curves return."""
+    from ..transform.filters import HUE_KEYS, REGION_KEYS
+    total = int(counts[0])
+    regions = {} if total == 0 else {k: int(counts[1 + i]) / total * 100 for i, k in enumerate(REGION_KEYS)}
+    hues = {k: int(counts[9 + i]) for i, k in enumerate(HUE_KEYS)}
+    values = np.arange(256)
+    curves = {}
+    for name, c in zip(("H", "S", "V"), hist.astype(np.int64)):
+        present = np.nonzero(c)[0]
+        if present.size == 0:
+            continue
+        lo, hi = int(present[0]), int(present[-1])
+        if hi > lo:
+            curves[name] = np.histogram(values, bins=60, range=(lo, hi), weights=c.astype(np.float64), density=True)
+        else:
+            curves[name] = np.histogram(np.full(int(c[lo]), lo), bins=60, density=True)
+    return regions, hues, curves
+
+
+def render_hist(regions, hues, curves) -> np.ndarray:
+    """A 3-panel figure (HSV density curves, colour regions, hue ranges) as an RGB uint8 array."""
+    from matplotlib.backends.backend_agg import FigureCanvasAgg
+    from matplotlib.figure import Figure
+
+    fig = Figure(figsize=(12, 4), dpi=80)
+    FigureCanvasAgg(fig)
+    ax0, ax1, ax2 = fig.subplots(1, 3)
+    for name, color in (("H", "tab:orange"), ("S", "tab:green"), ("V", "tab:blue")):
+        if name in curves:
+            dens, edges = curves[name]
+            ax0.plot(0.5 * (edges[:-1] + edges[1:]), dens, color=color, label=name)
+    ax0.set_title("HSV density (leaf pixels)")
+    ax0.legend(loc="upper right")
+    names = list(regions.keys())
+    ax1.barh(range(len(names)), [regions[k] for k in names], color="tab:olive")
+    ax1.set_yticks(range(len(names)))
+    ax1.set_yticklabels(names, fontsize=8)
+    ax1.set_xlabel("% of leaf pixels")
+    ax1.set_title("Colour regions")
+    hk = list(hues.keys())
+    ax2.bar(range(len(hk)), [hues[k] for k in hk], color="tab:purple")
+    ax2.set_xticks(range(len(hk)))
+    ax2.set_xticklabels([k.split(" ")[0] for k in hk], fontsize=8)
+    ax2.set_title("Hue ranges (pixels)")
+    fig.tight_layout()
+    fig.canvas.draw()
+    return np.ascontiguousarray(np.asarray(fig.canvas.buffer_rgba())[..., :3])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the GPU pipeline
+# ---------------------------------------------------------------------------------------------------------------
+
+def encode_jpeg_batch(x) -> List[bytes]:
+    """The files Image.save(quality=95) writes for a same-size batch [N,H,W,3] uint8 on the device: DCT,
+    quantisation and Huffman coding on the GPU (ops.jpeg_fdct_quant_u8, ops.jpeg_entropy_u8), markers on the host.
+    A scan that does not fit its row is written from the coefficients on the host."""
+    from .. import ops
+    from ..utils import jpeg_host
+    n, h, w = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    coef = ops.jpeg_fdct_quant_u8(x.contiguous(), JPEG_QUALITY)
+    rows = ops.jpeg_entropy_u8(coef, h, w).cpu().numpy()
+    lens = rows[:, :4].copy().view(np.int32)[:, 0]
+    out = []
+    for i in range(n):
+        if lens[i] >= 0:
+            out.append(jpeg_host.wrap_scan(rows[i, 4:4 + int(lens[i])], h, w, JPEG_QUALITY))
+        else:
+            out.append(jpeg_host.write_file(coef[i].cpu().numpy(), h, w, JPEG_QUALITY))
+    return out
+
+
+def transform_batch(x, types: Sequence[str], cfg) -> Dict[str, object]:
+    """process_single_image's data flow for a same-size batch [N,H,W,3] uint8 on the device.  Returns the device
+    outputs of the requested ported types ("Mask", "Blur", "ROI", "Brown": [N,H,W,3] uint8), "brown_stats"
+    (percentages, counts, areas) with Brown, and "hist" (counts, histograms as numpy) with Hist."""
+    import torch
+
+    from .. import ops
+    from ..transform import filters as F
+    res: Dict[str, object] = {}
+    masked = x
+    if any(t in types for t in MASK_TYPES):
+        mask, contour, counts, _fb = F.make_masks_device(x, cfg)
+        masked = ops.mask_composite_u8(x, mask, "white")
+        if "Mask" in types:
+            res["Mask"] = ops.mask_composite_u8(x, mask, "black")
+        if "Blur" in types:   # apply_blur_filter(masked, cfg, make_mask): make_mask again, on `masked`
+            mask2 = F.make_masks_device(masked, cfg)[0]
+            leaf = torch.where(mask2 > 0, 255, 0).to(torch.uint8)
+            res["Blur"] = ops.blur_saliency_u8(
+                masked, leaf, gaussian_sigma=float(cfg.gaussian_sigma), brown_hue_range=tuple(cfg.brown_hue_range),
+                brown_s_min=int(cfg.brown_s_min), brown_v_max=int(cfg.brown_v_max), use_brown=True)
+        if "ROI" in types:
+            _canvas, vis, _bb = F.roi_filter_batch(masked, contour, counts, cfg)
+            res["ROI"] = vis
+        if "Brown" in types:
+            out, stats = ops.brown_spots_u8(
+                masked, mask, brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
+                brown_v_max=int(cfg.brown_v_max), use_lab_brown=bool(cfg.use_lab_brown),
+                lab_a_min=int(cfg.lab_a_min), lab_b_min=int(cfg.lab_b_min),
+                brown_min_area_px=int(cfg.brown_min_area_px), brown_morph_kernel=int(cfg.brown_morph_kernel))
+            st = stats.cpu().numpy().astype(np.int64)
+            res["Brown"] = out
+            res["brown_stats"] = [(int(c), a / max(lf, 1) * 100, int(a)) for c, a, lf in st.tolist()]
+    if "Hist" in types:
+        counts_h, hist_h = ops.hsv_region_stats(masked.contiguous())
+        res["hist"] = (counts_h.cpu().numpy(), hist_h.cpu().numpy())
+    return res
+
+
+class _Runner:
+    def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor):
+        self.types, self.cfg, self.pool = types, cfg, pool
+        self.skip_existing, self.overwrite = skip_existing, overwrite
+        self.hist = "Hist" in types and _have_matplotlib()
+        for t in NOT_PORTED:   # one warning per run
+            if t in types:
+                logging.warning("%s is not ported to the GPU (PlantCV shape analysis / landmarks): no %s output is "
+                                "written", t, t)
+        if "Hist" in types and not self.hist:
+            logging.warning("matplotlib is not available: no Hist output is written")
+        logging.warning("The mosaic is not ported (it needs cv2's Hershey text): no mosaic is written")
+
+    def _write(self, path: Path, data: bytes, saved: List[Path]) -> None:
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_bytes(data)
+        saved.append(path)
+
+    def run_group(self, items: List[Tuple[Path, Path, np.ndarray]]) -> List[Path]:
+        """items: (image path, output directory, RGB array), all of one size."""
+        import torch
+
+        from ..transform.filters import _device
+        saved: List[Path] = []
+        dev = _device()
+        for c0 in range(0, len(items), CHUNK):
+            chunk = items[c0:c0 + CHUNK]
+            x = torch.from_numpy(np.stack([a for _p, _d, a in chunk])).to(dev)
+            res = transform_batch(x, self.types, self.cfg)
+            names = [output_names(p.stem) for p, _d, _a in chunk]
+            for t in ("Mask", "Blur", "ROI", "Brown"):   # process_single_image's order
+                if t not in res:
+                    continue
+                outs = [d / nm[t] for (_p, d, _a), nm in zip(chunk, names)]
+                todo = [i for i, o in enumerate(outs) if should_write(o, self.skip_existing, self.overwrite)]
+                if todo:
+                    y = res[t] if len(todo) == len(chunk) else res[t][torch.tensor(todo, device=dev)]
+                    for i, data in zip(todo, encode_jpeg_batch(y)):
+                        self._write(outs[i], data, saved)
+                if t == "Brown":
+                    for count, pct, area in res["brown_stats"]:
+                        logging.info(f"Brown spots detected: {count} regions, {pct:.1f}% of leaf area ({area} pixels)")
+            if self.hist:
+                counts_h, hist_h = res["hist"]
+                figs = list(self.pool.map(lambda i: render_hist(*hist_numbers(counts_h[i], hist_h[i])),
+                                          range(len(chunk))))
+                outs = [d / nm["Hist"] for (_p, d, _a), nm in zip(chunk, names)]
+                todo = [i for i, o in enumerate(outs) if should_write(o, self.skip_existing, self.overwrite)]
+                if todo:
+                    y = torch.from_numpy(np.stack([figs[i] for i in todo])).to(dev)
+                    for i, data in zip(todo, encode_jpeg_batch(y)):
+                        self._write(outs[i], data, saved)
+        return saved
+
+    def run(self, jobs: List[Tuple[Path, Path]]) -> List[Path]:
+        """jobs: (image path, output directory).  Decodes WINDOW files ahead on the host threads; unreadable files
+        and images over make_mask's size limit are logged and skipped."""
+        from .. import ops
+        saved: List[Path] = []
+        needs_mask = any(t in self.types for t in MASK_TYPES)
+        for w0 in range(0, len(jobs), WINDOW):
+            window = jobs[w0:w0 + WINDOW]
+
+            def load(job):
+                try:
+                    return pil_read_rgb(job[0])
+                except Exception as exc:  # noqa: BLE001 — any unreadable file is skipped
+                    logging.error("Failed to read %s (%s)", job[0], exc)
+                    return None
+
+            groups: Dict[Tuple[int, int], List[Tuple[Path, Path, np.ndarray]]] = {}
+            for (path, out_dir), rgb in zip(window, self.pool.map(load, window)):
+                if rgb is None:
+                    continue
+                h, w = rgb.shape[:2]
+                if needs_mask and not ops.make_mask_fits(h, w, self.cfg.mask_upscale_factor,
+                                                         self.cfg.mask_upscale_long_side):
+                    logging.error("Skipping %s: %d x %d is over make_mask's size limit (square inputs up to "
+                                  "399 x 399 at mask_upscale_factor 1.3)", path, h, w)
+                    continue
+                groups.setdefault((h, w), []).append((path, out_dir, rgb))
+            for items in groups.values():
+                saved.extend(self.run_group(items))
+        return saved
+
+
+def _workers(n: int) -> int:
+    return n if n > 0 else min(8, max(1, (os.cpu_count() or 2) // 2))
+
+
+def main(argv: Optional[Sequence[str]] = None) -> None:
+    args = parse_args(argv)
+    setup_logging()
+    types = build_types_filter(args.types)
+    from ..transform.filters import TransformConfig, load_config
+    if args.config:
+        if not Path(args.config).exists():
+            logging.error("Configuration file not found: %s", args.config)
+            return
+        try:
+            cfg = load_config(Path(args.config))
+        except Exception as exc:  # noqa: BLE001
+            logging.error("Failed to read configuration file (%s)", exc)
+            return
+    else:
+        cfg = TransformConfig()
+
+    if args.image and not args.src and not args.dst:
+        ip = Path(args.image)
+        if not is_image(ip):
+            logging.error("Not a valid image: %s", ip)
+            return
+        out_d = Path(args.out_dir) if args.out_dir else default_out_dir(ip)
+        out_d.mkdir(parents=True, exist_ok=True)
+        with ThreadPoolExecutor(_workers(args.workers)) as pool:
+            saved = _Runner(types, cfg, args.skip_existing, args.overwrite, pool).run([(ip, out_d)])
+        print(f"Saved {len(saved)} outputs to {out_d}")
+        for s in saved:
+            print(f"  - {s}")
+        return
+
+    if args.src and args.dst:
+        src, dst = Path(args.src), Path(args.dst)
+        if not src.exists():
+            logging.error("Source directory does not exist: %s", src)
+            return
+        dst.mkdir(parents=True, exist_ok=True)
+        imgs = list(iter_images_in_dir(src))
+        if not imgs:
+            logging.warning("No images found in %s", src)
+            return
+        logging.info("Found %d images in %s", len(imgs), src)
+        n_threads = _workers(args.workers)
+        logging.info("Using %d host threads", n_threads)
+        with ThreadPoolExecutor(n_threads) as pool:
+            saved = _Runner(types, cfg, args.skip_existing, args.overwrite, pool).run([(p, dst) for p in imgs])
+        logging.info("Processed %d images, saved %d outputs", len(imgs), len(saved))
+        return
+
+    logging.error("Must specify either single image or --src/--dst for folder mode")
+
+
+if __name__ == "__main__":
+    main()

@@ -1979,3 +1979,383 @@ int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// apply_brown_filter (srcs/transform/filters/brown.py) for a same-size batch: one workgroup per image, two bit
+// planes in LDS, the helpers of make_mask_post_kernel above (brown_px, morph_se, label_runs, paint_runs).
+//  * leaf = mask > 0; the predicate on the pixel as handed in (no R / B swap): 8-bit HSV (H in [0, 180))
+//    lo <= h <= hi, s >= s_min, v <= v_max, or L*a*b* a >= a_min, b >= b_min when use_lab; ANDed with leaf.
+//  * MORPH_OPEN then MORPH_CLOSE with getStructuringElement(MORPH_ELLIPSE, (k, k)), default borders: pixels outside
+//    the image never win (morph_se's rule).
+//  * connectedComponentsWithStats(connectivity=8): the components of area >= min_area are kept.
+//  * out = the input with every kept pixel set to (255, 100, 0); stats[n] = {count, brown area, leaf area}.
+// The union-find walks carry make_mask's step bounds: hitting one sets bit 2 of flags[n].
+// ===========================================================================
+namespace {
+
+__global__ __launch_bounds__(kMaskT) void brown_spots_kernel(const uint8_t* __restrict__ rgb,
+                                                             const uint8_t* __restrict__ leaf_mask,
+                                                             const uint16_t* __restrict__ lab_tabs, Run* __restrict__ runs,
+                                                             int* __restrict__ parent, int* __restrict__ area,
+                                                             int runs_per_image, int h, int w, int wpr, MaskArgs a,
+                                                             uint8_t* __restrict__ out, int* __restrict__ stats,
+                                                             int* __restrict__ flags) {
+    extern __shared__ unsigned lds_planes[];
+    __shared__ PixelTabs T;
+    __shared__ int s_nruns, s_status, s_flag[2], s_count, s_brown, s_leaf;
+    __shared__ unsigned long long s_best;
+    const size_t n = blockIdx.x;
+    Post P;
+    const int plane = h * wpr;
+    P.A = lds_planes;
+    P.B = P.A + plane;
+    P.C = P.D = nullptr;
+    P.rowstart = reinterpret_cast<int*>(P.B + plane);
+    P.rn = runs + n * runs_per_image;
+    P.par = parent + n * runs_per_image;
+    P.area = area + n * runs_per_image;
+    P.h = h;
+    P.w = w;
+    P.wpr = wpr;
+    P.max_runs = runs_per_image;
+    P.nruns = &s_nruns;
+    P.status = &s_status;
+    P.flag = s_flag;
+    P.best = &s_best;
+    for (int i = threadIdx.x; i < 256; i += kMaskT) {
+        T.sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
+        T.hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
+        T.gam[i] = lab_tabs[i];
+    }
+    for (int i = threadIdx.x; i < kLabCbrtSize; i += kMaskT) T.cbr[i] = lab_tabs[256 + i];
+    if (threadIdx.x == 0) s_status = s_count = s_brown = s_leaf = 0;
+    const uint8_t* img = rgb + n * (size_t)h * w * 3;
+    const uint8_t* lm = leaf_mask + n * (size_t)h * w;
+    __syncthreads();
+
+    int leaf = 0;
+    for (int p = threadIdx.x; p < h * w; p += kMaskT) leaf += lm[p] > 0;
+    atomicAdd(&s_leaf, leaf);
+    build_plane(P, P.A, [&](int y, int x) { return lm[y * w + x] > 0 && brown_px(T, img + 3 * (y * w + x), a); });
+    morph_se(P, P.A, P.B, a.se_brown, true);   // MORPH_OPEN
+    morph_se(P, P.B, P.A, a.se_brown, false);
+    morph_se(P, P.A, P.B, a.se_brown, false);  // MORPH_CLOSE
+    morph_se(P, P.B, P.A, a.se_brown, true);
+    label_runs(P, P.A, true);
+    const int nr = *P.nruns;
+    int cnt = 0, px = 0;
+    for (int k = threadIdx.x; k < nr; k += kMaskT) {
+        if (P.par[k] != k || P.area[k] < a.brown_min_area) continue;
+        ++cnt;
+        px += P.area[k];
+    }
+    atomicAdd(&s_count, cnt);
+    atomicAdd(&s_brown, px);
+    paint_runs(P, P.B, true, [&](int root) { return P.area[root] >= a.brown_min_area; });
+    uint8_t* o = out + n * (size_t)h * w * 3;
+    for (int p = threadIdx.x; p < h * w; p += kMaskT) {
+        const int y = p / w, x = p - y * w;
+        const bool keep = (P.B[y * wpr + (x >> 5)] >> (x & 31)) & 1u;
+        o[3 * p] = keep ? 255 : img[3 * p];
+        o[3 * p + 1] = keep ? 100 : img[3 * p + 1];
+        o[3 * p + 2] = keep ? 0 : img[3 * p + 2];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stats[3 * n] = s_count;
+        stats[3 * n + 1] = s_brown;
+        stats[3 * n + 2] = s_leaf;
+        flags[n] = s_status;
+    }
+}
+
+static size_t brown_lds(int h, int w) { return (size_t)2 * h * ((w + 31) / 32) * 4 + (size_t)(h + 1) * 4; }
+
+}  // namespace
+
+extern "C" {
+
+size_t lf_brown_spots_workspace(int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    const size_t runs = (size_t)n * mask_runs_per_image(h, w);
+    // runs / parents / areas, the L*a*b* tables
+    return up(runs * sizeof(Run)) + 2 * up(runs * 4) + up((256 + kLabCbrtSize) * sizeof(uint16_t));
+}
+
+int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int32_t* stats, int32_t* flags, int n,
+                      int h, int w, const lf_brown_params* prm, void* workspace, size_t ws_bytes, lf_stream_t stream) {
+    LF_REQUIRE(rgb && mask && out && stats && flags && prm && workspace, "lf_brown_spots: null buffer");
+    LF_REQUIRE(n > 0 && h > 0 && w > 0, "lf_brown_spots: bad dims n=%d %dx%d", n, h, w);
+    LF_REQUIRE(n <= 65535, "lf_brown_spots: batch too large for the grid");
+    LF_REQUIRE(h <= 65535 && w <= 65535, "lf_brown_spots: image too large (%d x %d)", h, w);
+    const size_t lds = brown_lds(h, w);
+    LF_REQUIRE(lds <= kMaskLdsCap,
+               "lf_brown_spots: a %d x %d image needs %zu bytes of LDS for its two bit planes (limit %zu, one "
+               "workgroup per image)", h, w, lds, kMaskLdsCap);
+    LF_REQUIRE(prm->morph_kernel >= 1 && prm->morph_kernel <= 31,
+               "lf_brown_spots: brown_morph_kernel %d outside [1, 31]", prm->morph_kernel);
+    LF_REQUIRE(ws_bytes >= lf_brown_spots_workspace(n, h, w), "lf_brown_spots: workspace too small (%zu < %zu)",
+               ws_bytes, lf_brown_spots_workspace(n, h, w));
+    LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "lf_brown_spots: workspace must be 256-byte aligned");
+    static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(brown_spots_kernel),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)kMaskLdsCap) == hipSuccess;
+    LF_REQUIRE(lds_ok || lds <= 48 * 1024, "lf_brown_spots: could not raise the LDS limit of the brown kernel");
+
+    hipStream_t s = lf::as_stream(stream);
+    const size_t runs = (size_t)n * mask_runs_per_image(h, w);
+    Run* rn = static_cast<Run*>(workspace);
+    int* parent = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(rn) + up(runs * sizeof(Run)));
+    int* area = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(parent) + up(runs * 4));
+    uint16_t* tabs = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(area) + up(runs * 4));
+
+    MaskArgs a{};
+    a.use_lab = prm->use_lab_brown;
+    a.hue_lo = prm->hue_lo;
+    a.hue_hi = prm->hue_hi;
+    a.s_min = prm->s_min;
+    a.v_max = prm->v_max;
+    a.a_min = prm->lab_a_min;
+    a.b_min = prm->lab_b_min;
+    a.brown_min_area = prm->min_area_px;
+    a.se_brown = ellipse_rows(prm->morph_kernel);
+
+    static const std::vector<uint16_t> host_tabs = []() {
+        std::vector<uint16_t> t(256 + kLabCbrtSize);
+        lab_tables_host(t.data());
+        return t;
+    }();
+    if (hipMemcpyAsync(tabs, host_tabs.data(), host_tabs.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s) !=
+        hipSuccess) {
+        lf::set_error("lf_brown_spots: table upload failed");
+        return LF_ERR_LAUNCH;
+    }
+    brown_spots_kernel<<<n, kMaskT, lds, s>>>(rgb, mask, tabs, rn, parent, area, (int)mask_runs_per_image(h, w), h, w,
+                                              (w + 31) / 32, a, out, stats, flags);
+    return lf::check_launch("lf_brown_spots");
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// apply_roi_filter (srcs/transform/filters/roi.py) for a batch, from the contour buffer make_mask_u8 leaves on the
+// device: one workgroup per image.  PARITY UNPINNED (no cv2 here); the readings:
+//  * bbox = cv2.boundingRect of the contour points: x = min, w = max - min + 1, the same for y.  No contour (count
+//    0): vis is the input, no canvas, no bbox (bit 0 of flags clear).  Points outside the image or counts > cap set
+//    bit 2 (an error; nothing but the copy is written).
+//  * letterbox: scale = min(W / max(w, 1), H / max(h, 1)) in double, nw = max(int(w * scale), 1) (truncated), the
+//    same for nh; cv2.resize(crop, (nw, nh), INTER_AREA) pasted on a zero canvas at ((H - nh) // 2, (W - nw) // 2).
+//  * INTER_AREA as OpenCV 4's resize.cpp reads with inv_scale = dst / src and scale = 1 / inv_scale (double):
+//    - equal sizes: a copy;
+//    - both scales >= 1, both within DBL_EPSILON of integers kx, ky: resizeAreaFast, the integer sum of the kx x ky
+//      block times (float)(1 / (kx * ky)), rounded with cvRound (half to even).  READING: this is the scalar loop;
+//      the SIMD 2 x 2 kernel (ResizeAreaFastVec_SIMD_8u) rounds (sum + 2) >> 2, half up, for the pixels it covers,
+//      so a tie may come out one higher there;
+//    - both scales >= 1 otherwise: resizeArea with the computeResizeAreaTab weights (double positions, float
+//      weights), each source row's taps accumulated in float in table order, the rows weighted and summed in
+//      float in table order, cvRound;
+//    - otherwise INTER_LINEAR with area-mode coefficients: sx = floor(dx * scale), fx = (float)((dx + 1) - (sx + 1)
+//      * inv_scale), fx = fx <= 0 ? 0 : fx - floor(fx); sx < 0 -> (0, 0); sx >= src - 1 -> (src - 1, 0); Q11 weights
+//      cvRound((1 - fx) * 2048), cvRound(fx * 2048); rows sy, sy + 1 clamped into the image, no clamp of fy.
+//      READING: the scalar vertical pass (b0 * S0 + b1 * S1 + (1 << 21)) >> 22; the SIMD VResizeLinearVec_32s8u
+//      ((S >> 4) * b >> 16 ... + 2) >> 2 can differ from it by 1.
+//  * vis: cv2.rectangle(vis, (x, y), (x + w, y + h), (255, 0, 0), 2), LINE_8, clipped to the image.  drawing.cpp:
+//    PolyLine closes the four corners into four ThickLine calls; thickness 2 is even, so each segment is
+//    FillConvexPoly of the segment offset by +-1 pixel across it (XY_SHIFT fixed point, exact for whole pixels):
+//    rows y - 1 .. y + 1 over x .. x + w for a horizontal side, columns x - 1 .. x + 1 over y .. y + h for a
+//    vertical one; the round join at each end is Circle(radius 1, filled), a plus sign, already inside the bands.
+//    The four outer corner pixels (x - 1, y - 1) etc. are therefore not drawn.
+// ===========================================================================
+namespace {
+
+constexpr int kRoiT = 256;
+constexpr int kRoiFound = 1, kRoiBad = 4;
+
+// computeResizeAreaTab for destination index d, as a range: [an optional partial tap s1 - 1] full taps s1 .. s2 - 1
+// [an optional partial tap s2], in table order
+struct AreaAxis {
+    int s1, s2, pre, post;
+    float a_pre, a_mid, a_post;
+    __device__ int taps() const { return pre + (s2 - s1) + post; }
+    __device__ void tap(int k, int& s, float& a) const {
+        if (pre && k == 0) {
+            s = s1 - 1;
+            a = a_pre;
+            return;
+        }
+        k -= pre;
+        if (k < s2 - s1) {
+            s = s1 + k;
+            a = a_mid;
+        } else {
+            s = s2;
+            a = a_post;
+        }
+    }
+};
+
+__device__ AreaAxis area_axis(int ssize, double scale, int d) {
+    const double f1 = __dmul_rn((double)d, scale), f2 = __dadd_rn(f1, scale);
+    const double cell = fmin(scale, __dsub_rn((double)ssize, f1));
+    AreaAxis t;
+    t.s2 = min((int)floor(f2), ssize - 1);
+    t.s1 = min((int)ceil(f1), t.s2);
+    t.pre = __dsub_rn((double)t.s1, f1) > 1e-3;
+    t.post = __dsub_rn(f2, (double)t.s2) > 1e-3;
+    t.a_pre = (float)__ddiv_rn(__dsub_rn((double)t.s1, f1), cell);
+    t.a_mid = (float)__ddiv_rn(1.0, cell);
+    t.a_post = (float)__ddiv_rn(fmin(fmin(__dsub_rn(f2, (double)t.s2), 1.0), cell), cell);
+    return t;
+}
+
+// area-mode INTER_LINEAR coordinate: source index, Q11 weights of it and of the next one
+__device__ __forceinline__ void area_linear(int ssize, double scale, double inv, int d, bool clamp_end, int& s, int& w0,
+                                            int& w1) {
+    s = (int)floor(__dmul_rn((double)d, scale));
+    float f = (float)__dsub_rn((double)(d + 1), __dmul_rn((double)(s + 1), inv));
+    f = f <= 0.f ? 0.f : f - floorf(f);
+    if (s < 0) s = 0, f = 0.f;
+    if (clamp_end && s >= ssize - 1) s = ssize - 1, f = 0.f;
+    w0 = (int)rintf((1.f - f) * 2048.f);
+    w1 = (int)rintf(f * 2048.f);
+}
+
+__global__ __launch_bounds__(kRoiT) void roi_kernel(const uint8_t* __restrict__ rgb, const int* __restrict__ contour,
+                                                    const int* __restrict__ counts, int cap, int h, int w, int rh,
+                                                    int rw, uint8_t* __restrict__ canvas, uint8_t* __restrict__ vis,
+                                                    int* __restrict__ bbox, int* __restrict__ flags) {
+    __shared__ int s_lo[2], s_hi[2], s_bad;
+    const size_t n = blockIdx.x;
+    const int cnt = counts[n];
+    if (threadIdx.x == 0) {
+        s_lo[0] = s_lo[1] = INT_MAX;
+        s_hi[0] = s_hi[1] = INT_MIN;
+        s_bad = cnt < 0 || cnt > cap;
+    }
+    __syncthreads();
+    const int m = min(max(cnt, 0), cap);
+    const int* pts = contour + n * (size_t)cap * 2;
+    int lx = INT_MAX, ly = INT_MAX, hx = INT_MIN, hy = INT_MIN, bad = 0;
+    for (int i = threadIdx.x; i < m; i += kRoiT) {
+        const int x = pts[2 * i], y = pts[2 * i + 1];
+        bad |= x < 0 || x >= w || y < 0 || y >= h;
+        lx = min(lx, x);
+        ly = min(ly, y);
+        hx = max(hx, x);
+        hy = max(hy, y);
+    }
+    atomicMin(&s_lo[0], lx);
+    atomicMin(&s_lo[1], ly);
+    atomicMax(&s_hi[0], hx);
+    atomicMax(&s_hi[1], hy);
+    if (bad) atomicOr(&s_bad, 1);
+    __syncthreads();
+    const uint8_t* img = rgb + n * (size_t)h * w * 3;
+    const bool found = m > 0 && !s_bad;
+    const int bx = found ? s_lo[0] : 0, by = found ? s_lo[1] : 0;
+    const int bw = found ? s_hi[0] - s_lo[0] + 1 : 1, bh = found ? s_hi[1] - s_lo[1] + 1 : 1;
+    const int x1 = bx + bw, y1 = by + bh;
+
+    uint8_t* v = vis + n * (size_t)h * w * 3;
+    for (int p = threadIdx.x; p < h * w; p += kRoiT) {
+        const int y = p / w, x = p - y * w;
+        const bool edge = found && ((((y >= by - 1 && y <= by + 1) || (y >= y1 - 1 && y <= y1 + 1)) && x >= bx && x <= x1) ||
+                                    (((x >= bx - 1 && x <= bx + 1) || (x >= x1 - 1 && x <= x1 + 1)) && y >= by && y <= y1));
+        v[3 * p] = edge ? 255 : img[3 * p];
+        v[3 * p + 1] = edge ? 0 : img[3 * p + 1];
+        v[3 * p + 2] = edge ? 0 : img[3 * p + 2];
+    }
+    uint8_t* c = canvas + n * (size_t)rh * rw * 3;
+    if (!found) {
+        for (int p = threadIdx.x; p < rh * rw * 3; p += kRoiT) c[p] = 0;
+        if (threadIdx.x == 0) {
+            bbox[4 * n] = bbox[4 * n + 1] = bbox[4 * n + 2] = bbox[4 * n + 3] = 0;
+            flags[n] = s_bad ? kRoiBad : 0;
+        }
+        return;
+    }
+    const double scale = fmin(__ddiv_rn((double)rw, (double)bw), __ddiv_rn((double)rh, (double)bh));
+    const int nw = min(max((int)__dmul_rn((double)bw, scale), 1), rw), nh = min(max((int)__dmul_rn((double)bh, scale), 1), rh);
+    const int oy = (rh - nh) / 2, ox = (rw - nw) / 2;
+    const double ix = __ddiv_rn((double)nw, (double)bw), iy = __ddiv_rn((double)nh, (double)bh);
+    const double sx = __ddiv_rn(1.0, ix), sy = __ddiv_rn(1.0, iy);
+    const bool copy = nw == bw && nh == bh;
+    const bool area = sx >= 1.0 && sy >= 1.0;
+    const int kx = (int)rint(sx), ky = (int)rint(sy);
+    const bool fast = area && fabs(sx - kx) < DBL_EPSILON && fabs(sy - ky) < DBL_EPSILON;
+    auto src = [&](int yy, int xx, int ch) -> int {   // the crop, indices clamped into it
+        yy = clampi(yy, 0, bh - 1);
+        xx = clampi(xx, 0, bw - 1);
+        return img[((size_t)(by + yy) * w + bx + xx) * 3 + ch];
+    };
+    for (int p = threadIdx.x; p < rh * rw; p += kRoiT) {
+        const int y = p / rw, x = p - y * rw, dy = y - oy, dx = x - ox;
+        uint8_t* o = c + (size_t)p * 3;
+        if (dy < 0 || dy >= nh || dx < 0 || dx >= nw) {
+            o[0] = o[1] = o[2] = 0;
+            continue;
+        }
+        if (copy) {
+            for (int ch = 0; ch < 3; ++ch) o[ch] = (uint8_t)src(dy, dx, ch);
+        } else if (fast) {
+            const float inv_area = __fdiv_rn(1.f, (float)(kx * ky));
+            for (int ch = 0; ch < 3; ++ch) {
+                int sum = 0;
+                for (int r = 0; r < ky; ++r)
+                    for (int q = 0; q < kx; ++q) sum += src(dy * ky + r, dx * kx + q, ch);
+                o[ch] = (uint8_t)clampi((int)rintf(__fmul_rn((float)sum, inv_area)), 0, 255);
+            }
+        } else if (area) {
+            const AreaAxis ax = area_axis(bw, sx, dx), ay = area_axis(bh, sy, dy);
+            const int nx = ax.taps(), ny = ay.taps();
+            for (int ch = 0; ch < 3; ++ch) {
+                float sum = 0.f;
+                for (int j = 0; j < ny; ++j) {
+                    int ys, xs;
+                    float beta, alpha, buf = 0.f;
+                    ay.tap(j, ys, beta);
+                    for (int k = 0; k < nx; ++k) {
+                        ax.tap(k, xs, alpha);
+                        buf = __fadd_rn(buf, __fmul_rn((float)src(ys, xs, ch), alpha));
+                    }
+                    sum = j == 0 ? __fmul_rn(beta, buf) : __fadd_rn(sum, __fmul_rn(beta, buf));
+                }
+                o[ch] = (uint8_t)clampi((int)rintf(sum), 0, 255);
+            }
+        } else {
+            int xs, a0, a1, ys, b0, b1;
+            area_linear(bw, sx, ix, dx, true, xs, a0, a1);
+            area_linear(bh, sy, iy, dy, false, ys, b0, b1);
+            for (int ch = 0; ch < 3; ++ch) {
+                const int r0 = src(ys, xs, ch) * a0 + src(ys, xs + 1, ch) * a1;
+                const int r1 = src(ys + 1, xs, ch) * a0 + src(ys + 1, xs + 1, ch) * a1;
+                o[ch] = (uint8_t)clampi((r0 * b0 + r1 * b1 + (1 << 21)) >> 22, 0, 255);
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        bbox[4 * n] = bx;
+        bbox[4 * n + 1] = by;
+        bbox[4 * n + 2] = bw;
+        bbox[4 * n + 3] = bh;
+        flags[n] = kRoiFound;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int lf_roi_u8(const uint8_t* rgb, const int32_t* contour, const int32_t* counts, int cap, uint8_t* canvas,
+              uint8_t* vis, int32_t* bbox, int32_t* flags, int n, int h, int w, int roi_h, int roi_w,
+              lf_stream_t stream) {
+    LF_REQUIRE(rgb && contour && counts && canvas && vis && bbox && flags, "lf_roi: null buffer");
+    LF_REQUIRE(n > 0 && h > 0 && w > 0 && cap > 0 && roi_h > 0 && roi_w > 0,
+               "lf_roi: bad dims n=%d %dx%d cap=%d roi %dx%d", n, h, w, cap, roi_h, roi_w);
+    LF_REQUIRE(n <= 65535, "lf_roi: batch too large for the grid");
+    roi_kernel<<<n, kRoiT, 0, lf::as_stream(stream)>>>(rgb, contour, counts, cap, h, w, roi_h, roi_w, canvas, vis,
+                                                       bbox, flags);
+    return lf::check_launch("lf_roi");
+}
+
+}  // extern "C"

@@ -329,6 +329,13 @@ def mask_working_scale(h: int, w: int, upscale_factor: float = 1.3, upscale_long
     return s, int(round(h * s)), int(round(w * s)), True
 
 
+def make_mask_fits(h: int, w: int, upscale_factor: float = 1.3, upscale_long_side: int = 1500) -> bool:
+    """Whether make_mask_u8 takes an h x w image: its working image's four bit planes fit one workgroup's LDS
+    (140 KiB, lf_make_mask_u8's limit)."""
+    _s, wh, ww, _r = mask_working_scale(h, w, upscale_factor, upscale_long_side)
+    return wh <= 65535 and ww <= 65535 and 4 * wh * ((ww + 31) // 32) * 4 + (wh + 1) * 4 <= 140 * 1024
+
+
 _HSV_CHANNELS = {"h": 0, "s": 1, "v": 2}
 
 
@@ -379,6 +386,64 @@ def make_mask_u8(x: torch.Tensor, green_hue_range=(25, 100), fill_size: int = 10
             raise _lib.LeafHipError("lf_make_mask_u8: the re-traced contours changed length")
         cnt = wide
     return mask, cnt, counts_h.to(x.device), (flags_h & 1).bool().to(x.device)
+
+
+def brown_spots_u8(x: torch.Tensor, mask: torch.Tensor, brown_hue_range=(0, 30), brown_s_min: int = 20,
+                   brown_v_max: int = 200, use_lab_brown: bool = False, lab_a_min: int = 125, lab_b_min: int = 125,
+                   brown_min_area_px: int = 25, brown_morph_kernel: int = 3):
+    """apply_brown_filter (srcs/transform/filters/brown.py) for a same-size batch [N,H,W,3] uint8 and its leaf masks
+    [N,H,W] uint8 (leaf = mask > 0).  Returns (overlay [N,H,W,3] uint8, stats [N,3] int32 {count, brown area, leaf
+    area}).  Defaults: config.yaml.  An image must fit one workgroup's LDS (two bit planes, 140 KiB); larger ones
+    raise LeafHipError before any launch."""
+    n, h, w = _hwc(x, "brown_spots.x")
+    _chk(mask, _U8, "brown_spots.mask", 3)
+    if tuple(mask.shape) != (n, h, w) or mask.device != x.device:
+        raise ValueError(f"brown_spots.mask: expected {[n, h, w]} on {x.device}, got {list(mask.shape)} on "
+                         f"{mask.device}")
+    if not 1 <= int(brown_morph_kernel) <= 31:
+        raise ValueError(f"brown_spots: brown_morph_kernel {brown_morph_kernel} outside [1, 31]")
+    prm = np.array([1 if use_lab_brown else 0, brown_hue_range[0], brown_hue_range[1], brown_s_min, brown_v_max,
+                    lab_a_min, lab_b_min, brown_min_area_px, brown_morph_kernel], dtype=np.int32)
+    lib = _lib.load()
+    if 2 * h * ((w + 31) // 32) * 4 + (h + 1) * 4 > 140 * 1024:
+        raise _lib.LeafHipError(f"brown_spots: a {h} x {w} image does not fit one workgroup's LDS (two bit planes, "
+                                "140 KiB)")
+    ws = torch.empty(int(lib.lf_brown_spots_workspace(n, h, w)), dtype=_U8, device=x.device)
+    out = torch.empty_like(x)
+    stats = torch.empty((n, 3), dtype=_I32, device=x.device)
+    flags = torch.empty(n, dtype=_I32, device=x.device)
+    _lib.call("lf_brown_spots_u8", x.data_ptr(), mask.data_ptr(), out.data_ptr(), stats.data_ptr(), flags.data_ptr(),
+              n, h, w, prm.ctypes.data, ws.data_ptr(), ws.numel(), _stream())
+    if bool((flags & 4).any()):
+        raise _lib.LeafHipError("lf_brown_spots_u8: a union-find step bound was hit")
+    return out, stats
+
+
+def roi_u8(x: torch.Tensor, contour: torch.Tensor, counts: torch.Tensor, roi_size=(256, 256)):
+    """apply_roi_filter (srcs/transform/filters/roi.py) for a batch [N,H,W,3] uint8 and the contour buffer of
+    make_mask_u8 (contour [N,K,2] int32 (x, y), counts [N] int32; the first counts[i] rows are image i's contour,
+    0: none).  roi_size = (H, W) of the canvas (config.yaml roi_size).  Returns (canvas [N,H',W',3] uint8, vis
+    [N,H,W,3] uint8, bbox [N,4] int32 (x, y, w, h), found [N] bool); an image without a contour has vis = the input
+    and a zero canvas and bbox.  The cv2 readings: include/leafhip.h (lf_roi_u8)."""
+    n, h, w = _hwc(x, "roi.x")
+    _chk(contour, _I32, "roi.contour", 3)
+    _chk(counts, _I32, "roi.counts", 1)
+    if contour.shape[0] != n or contour.shape[2] != 2 or contour.shape[1] < 1 or tuple(counts.shape) != (n,) \
+            or contour.device != x.device or counts.device != x.device:
+        raise ValueError(f"roi: expected contour [{n},K,2] and counts [{n}] on {x.device}, got "
+                         f"{list(contour.shape)} and {list(counts.shape)}")
+    rh, rw = int(roi_size[0]), int(roi_size[1])
+    if rh <= 0 or rw <= 0:
+        raise ValueError(f"roi: roi_size must be positive, got {roi_size}")
+    canvas = torch.empty((n, rh, rw, 3), dtype=_U8, device=x.device)
+    vis = torch.empty_like(x)
+    bbox = torch.empty((n, 4), dtype=_I32, device=x.device)
+    flags = torch.empty(n, dtype=_I32, device=x.device)
+    _lib.call("lf_roi_u8", x.data_ptr(), contour.data_ptr(), counts.data_ptr(), int(contour.shape[1]),
+              canvas.data_ptr(), vis.data_ptr(), bbox.data_ptr(), flags.data_ptr(), n, h, w, rh, rw, _stream())
+    if bool((flags & 4).any()):
+        raise _lib.LeafHipError("lf_roi_u8: a contour count above the buffer or a point outside the image")
+    return canvas, vis, bbox, (flags & 1).bool()
 
 
 def jpeg_fdct_quant_u8(x: torch.Tensor, quality: int = 95, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -6,7 +6,8 @@ upscale, the inclusive candidate, post-processing and largest contour, the Otsu 
 extension and the resize back (lf_make_mask_u8).  The other strategies are not ported and raise.  GrabCut
 (grabcut_refine, true in config.yaml) and shadow suppression are skipped with one warning per process: the
 reference keeps the candidate whenever a refinement scores lower, so the result is one of the outcomes the
-reference can produce.  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
+reference can produce.  `apply_brown_filter` (brown.py) and `apply_roi_filter` (roi.py) run on the GPU too
+(lf_brown_spots_u8, lf_roi_u8), one image at a time or batched on device tensors.  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
 reproduced — the numbers it draws are."""
 from __future__ import annotations
 
@@ -51,6 +52,7 @@ class TransformConfig:
     brown_morph_kernel: int = 3
     lab_a_min: int = 125
     lab_b_min: int = 125
+    roi_size: Tuple[int, int] = (256, 256)            # config.yaml:3, (H, W) of apply_roi_filter's canvas
 
 
 def load_config(path) -> TransformConfig:
@@ -106,6 +108,15 @@ def _check_mask_config(cfg) -> None:
 def make_masks(batch, cfg) -> Tuple[np.ndarray, list, np.ndarray]:
     """make_mask (mask.py:548-582) for a same-size batch [N,H,W,3] uint8 (numpy or a CUDA tensor).  Returns
     (masks [N,H,W] uint8 0 / 255, contours: per image int32 [K,1,2] or None, fallback [N] bool)."""
+    mask, cnt, counts, fallback = make_masks_device(batch, cfg)
+    cnt_h, counts_h = cnt.cpu().numpy(), counts.cpu().numpy()
+    contours = [cnt_h[i, :int(c)].reshape(-1, 1, 2).copy() if c > 0 else None for i, c in enumerate(counts_h)]
+    return mask.cpu().numpy(), contours, fallback.cpu().numpy()
+
+
+def make_masks_device(batch, cfg):
+    """make_masks without leaving the device: (masks [N,H,W] uint8, contour [N,K,2] int32, counts [N] int32,
+    fallback [N] bool), ops.make_mask_u8's outputs — the contour buffer roi_filter_batch reads."""
     _check_mask_config(cfg)
     if isinstance(batch, torch.Tensor):
         x = batch.to(_device()).contiguous()
@@ -114,7 +125,7 @@ def make_masks(batch, cfg) -> Tuple[np.ndarray, list, np.ndarray]:
         if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
             raise ValueError(f"expected an NxHxWx3 uint8 RGB batch, got {a.dtype} {a.shape}")
         x = torch.from_numpy(a).to(_device())
-    mask, cnt, counts, fallback = ops.make_mask_u8(
+    return ops.make_mask_u8(
         x, green_hue_range=tuple(cfg.green_hue_range), fill_size=int(cfg.fill_size),
         morph_kernel=int(cfg.morph_kernel), mask_upscale_factor=cfg.mask_upscale_factor,
         mask_upscale_long_side=cfg.mask_upscale_long_side, hsv_channel=str(cfg.hsv_channel_for_mask),
@@ -122,9 +133,6 @@ def make_masks(batch, cfg) -> Tuple[np.ndarray, list, np.ndarray]:
         brown_s_min=int(cfg.brown_s_min), brown_v_max=int(cfg.brown_v_max), lab_a_min=int(cfg.lab_a_min),
         lab_b_min=int(cfg.lab_b_min), brown_min_area_px=int(cfg.brown_min_area_px),
         brown_morph_kernel=int(cfg.brown_morph_kernel))
-    cnt_h, counts_h = cnt.cpu().numpy(), counts.cpu().numpy()
-    contours = [cnt_h[i, :int(c)].reshape(-1, 1, 2).copy() if c > 0 else None for i, c in enumerate(counts_h)]
-    return mask.cpu().numpy(), contours, fallback.cpu().numpy()
 
 
 def make_mask(rgb: np.ndarray, cfg) -> Tuple[np.ndarray, Optional[np.ndarray]]:
@@ -165,6 +173,89 @@ def apply_blur_filter(rgb: np.ndarray, cfg, make_mask_func: Optional[Callable] =
         brown_s_min=int(cfg.brown_s_min) if brown else 0,
         brown_v_max=int(cfg.brown_v_max) if brown else 0, use_brown=brown)
     return out[0].cpu().numpy()
+
+
+def _device_u8(a, ndim: int, name: str) -> torch.Tensor:
+    if isinstance(a, torch.Tensor):
+        return a.to(_device()).contiguous()
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.uint8 or a.ndim != ndim:
+        raise ValueError(f"{name}: expected a {ndim}-d uint8 array, got {a.dtype} {a.shape}")
+    return torch.from_numpy(a).to(_device())
+
+
+def brown_filter_batch(batch, masks, cfg) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+    """apply_brown_filter for a same-size batch [N,H,W,3] uint8 and its masks [N,H,W] uint8 (CUDA tensors, or numpy
+    moved to the GPU).  Returns (overlay [N,H,W,3] uint8 on the device, percentages float64 [N], counts int64 [N]);
+    the percentage is brown.py's brown_area / max(leaf_area, 1) * 100 in float64.  No log line (apply_brown_filter
+    logs per image)."""
+    x = _device_u8(batch, 4, "brown_filter_batch.batch")
+    m = _device_u8(masks, 3, "brown_filter_batch.masks")
+    out, stats = ops.brown_spots_u8(
+        x, m, brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
+        brown_v_max=int(cfg.brown_v_max), use_lab_brown=bool(cfg.use_lab_brown), lab_a_min=int(cfg.lab_a_min),
+        lab_b_min=int(cfg.lab_b_min), brown_min_area_px=int(cfg.brown_min_area_px),
+        brown_morph_kernel=int(cfg.brown_morph_kernel))
+    st = stats.cpu().numpy().astype(np.int64)
+    pct = np.array([st[i, 1] / max(st[i, 2], 1) * 100 for i in range(st.shape[0])], dtype=np.float64)
+    return out, pct, st[:, 0].copy()
+
+
+def log_brown(count: int, pct: float, area: int) -> None:
+    """brown.py's log line."""
+    logging.info(f"Brown spots detected: {count} regions, {pct:.1f}% of leaf area ({area} pixels)")
+
+
+def apply_brown_filter(rgb: np.ndarray, mask: Optional[np.ndarray], cfg) -> Tuple[np.ndarray, float, int]:
+    """srcs/transform/filters/brown.py: (overlay with the kept brown spots in (255, 100, 0), percentage of the leaf
+    area, number of spots) for one HxWx3 uint8 RGB image; a None mask returns (rgb, 0.0, 0).  A 3-d mask is read
+    through its first channel, as brown.py reads it."""
+    if mask is None:
+        return rgb, 0.0, 0
+    m = np.asarray(mask)
+    leaf = (m > 0) if m.ndim == 2 else (m[..., 0] > 0)
+    x = _rgb_batch(rgb)
+    if leaf.shape != x.shape[1:3]:
+        raise ValueError(f"apply_brown_filter: mask {leaf.shape} does not match the image {tuple(x.shape[1:3])}")
+    md = torch.from_numpy(np.ascontiguousarray(leaf.astype(np.uint8))).unsqueeze(0).to(x.device)
+    out, stats = ops.brown_spots_u8(
+        x, md, brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
+        brown_v_max=int(cfg.brown_v_max), use_lab_brown=bool(cfg.use_lab_brown), lab_a_min=int(cfg.lab_a_min),
+        lab_b_min=int(cfg.lab_b_min), brown_min_area_px=int(cfg.brown_min_area_px),
+        brown_morph_kernel=int(cfg.brown_morph_kernel))
+    count, area, leaf_area = (int(v) for v in stats[0].cpu().tolist())
+    pct = area / max(leaf_area, 1) * 100
+    log_brown(count, pct, area)
+    return out[0].cpu().numpy(), pct, count
+
+
+def roi_filter_batch(batch, contour: torch.Tensor, counts: torch.Tensor, cfg):
+    """apply_roi_filter for a batch [N,H,W,3] uint8 and make_mask_u8's device contour buffer (contour [N,K,2] int32,
+    counts [N] int32) with no host round trip.  Returns (canvas [N,H',W',3], vis [N,H,W,3] on the device, bboxes:
+    per image (x, y, w, h) or None when it has no contour; its canvas is then zero and its vis the input)."""
+    x = _device_u8(batch, 4, "roi_filter_batch.batch")
+    canvas, vis, bbox, found = ops.roi_u8(x, contour, counts, tuple(cfg.roi_size))
+    bb, fd = bbox.cpu().numpy(), found.cpu().numpy()
+    return canvas, vis, [tuple(int(v) for v in bb[i]) if fd[i] else None for i in range(bb.shape[0])]
+
+
+def apply_roi_filter(rgb: np.ndarray, contour: Optional[np.ndarray], cfg):
+    """srcs/transform/filters/roi.py: (canvas cfg.roi_size letterbox of the contour's bounding box, vis = the image
+    with that box drawn, bbox (x, y, w, h)) for one HxWx3 uint8 RGB image; no contour returns (rgb, None, None).
+    The contour ([K,1,2] or [K,2] (x, y)) must lie inside the image (roi.py's numpy slicing would wrap)."""
+    if contour is None:
+        return rgb, None, None
+    pts = np.asarray(contour).reshape(-1, 2)
+    if pts.shape[0] == 0:
+        raise ValueError("apply_roi_filter: empty contour")
+    x = _rgb_batch(rgb)
+    h, w = x.shape[1:3]
+    if (pts[:, 0] < 0).any() or (pts[:, 0] >= w).any() or (pts[:, 1] < 0).any() or (pts[:, 1] >= h).any():
+        raise ValueError("apply_roi_filter: contour points outside the image")
+    c = torch.from_numpy(np.ascontiguousarray(pts.astype(np.int32))).unsqueeze(0).to(x.device)
+    counts = torch.tensor([pts.shape[0]], dtype=torch.int32, device=x.device)
+    canvas, vis, bboxes = roi_filter_batch(x, c, counts, cfg)
+    return canvas[0].cpu().numpy(), vis[0].cpu().numpy(), bboxes[0]
 
 
 def _stats(rgb: np.ndarray):
