@@ -508,6 +508,27 @@ int lf_cast_bf16_f32(const uint16_t* in, float* out, size_t count, lf_stream_t s
 int lf_conv2d_variant(int h, int wd, int cout, int ksize);
 int lf_conv2d_wgrad_variant(int n, int cin, int h, int wd, int cout, int ksize);
 
+/* Plan queries: which kernel and which code path the dispatchers take for a launch, computed by the
+ * same host functions the launchers use.  Host only: they launch nothing and need no device (the
+ * coverage test tests/test_conv_plans.py compares the benchmark's layers with the tested shapes).
+ * lf_conv2d_plan (lf_conv2d_f32 / _stats_f32 / _bnbwd_f32), out[4]:
+ *   {variant, Cin <= 4 stem instantiation, images per strip (stack), vector path by shape}
+ * lf_conv2d_wgrad_plan (lf_conv2d_wgrad_f32 / _bn_f32), out[4]:
+ *   {variant (5 = small-Cin), items per split (1, 2 or 3 = three or more), reduce stages (1 or 2),
+ *    fused BN allowed}
+ * lf_conv2d_bf16_plan (entry 0 = lf_conv2d_bf16_act, 1 = _act_mean, 2 = _train; accumulate and mask
+ * as passed to _train), out[14]:
+ *   {streaming, TAPS, CI, NCO, NB, TW, TH, XBF, YBF, TR, RMW (streaming) or WIDE (K-chunked),
+ *    segments > 1, interleave, units per workgroup > 1}   (fields a kernel has not are 0)
+ * lf_conv2d_wgrad_bf16_plan (lf_conv2d_wgrad_bf16), out[13]:
+ *   {TAPS, TW, TH, CIB, COB, STEM, G, WPRQ, segments > 1, interleave, units per workgroup > 1,
+ *    reduce stages, tiles per unit (1, 2 or 3 = three or more)} */
+int lf_conv2d_plan(int n, int cin, int h, int wd, int cout, int ksize, int* out);
+int lf_conv2d_wgrad_plan(int n, int cin, int h, int wd, int cout, int ksize, int* out);
+int lf_conv2d_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16, int y_bf16, int entry,
+                        int accumulate, int mask, int* out);
+int lf_conv2d_wgrad_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int* out);
+
 /* Conv2D followed by BatchNormalization in training mode (cnn.py:28-33,40-45): the same
  * convolution, and in its epilogue the per-tile sums of (y - pivot[co]) and (y - pivot[co])^2 for
  * every output channel -> tile_part[co][tile][2] (tile < lf_conv2d_stats_tiles(...)).  pivot

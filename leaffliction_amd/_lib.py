@@ -96,6 +96,10 @@ SIGNATURES = {
     "lf_cast_bf16_f32": [P, P, c_size_t, P],
     "lf_conv2d_variant": [c_int, c_int, c_int, c_int],
     "lf_conv2d_wgrad_variant": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "lf_conv2d_plan": [c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "lf_conv2d_wgrad_plan": [c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "lf_conv2d_bf16_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "lf_conv2d_wgrad_bf16_plan": [c_int, c_int, c_int, c_int, c_int, c_int, P],
     "lf_conv2d_stats_tiles": [c_int, c_int, c_int, c_int, c_int, c_int],
     "lf_conv2d_stats_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_size_t, P],
     "lf_conv2d_bnbwd_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P,

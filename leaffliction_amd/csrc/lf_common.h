@@ -120,6 +120,20 @@ struct WgradBf16Args {
 long long conv_bf16s_parts(int n, int cin, int h, int w, int cout, int ksize, int x_bf16);  // 0 = shape not covered
 int conv_bf16s_units_per_image(int n, int cin, int h, int w, int cout, int ksize, int x_bf16);   // segments per image
 int conv_bf16s_launch(ConvBf16TrainArgs a, int ksize, int x_bf16, hipStream_t s);
+// the streaming kernel reads y back (read-modify-write epilogue) when it accumulates or gathers mask sums
+inline bool conv_bf16s_rmw(int accumulate, bool mask) { return accumulate || mask; }
+// the streaming kernel's plan for lf_conv2d_bf16_plan: out = {CI, NCO, TW, TH, XBF, segs > 1, interleave,
+// units per workgroup > 1}; returns 0 when the shape is not covered
+int conv_bf16s_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16, int* out);
+
+// The most units (segments of column strips) one workgroup walks when `wgs` workgroups deal out n images of
+// `units_per_image` units each as conv_bf16s_kernel and wgrad_bf16_kernel do: round-robin over the grid, or with
+// `interleave` image i on XCD i % 8 (workgroups k, k + 8, ...).  Workgroup 0 walks the most.
+inline int max_units_per_workgroup(int n, int units_per_image, int wgs, int interleave) {
+    const long long total = interleave ? (long long)((n + 7) / 8) * units_per_image : (long long)n * units_per_image;
+    const long long step = interleave ? wgs / 8 : wgs;
+    return step > 0 ? (int)((total + step - 1) / step) : 0;
+}
 
 // Tile kernels whose neighbouring tiles share input halos: workgroups are dealt to the eight XCDs
 // round-robin in dispatch order and every XCD has its own L2, so a plain (tile_x, tile_y, image)

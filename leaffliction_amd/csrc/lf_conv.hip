@@ -1430,11 +1430,17 @@ inline long long padded_work(const FwdVariant& v, int h, int w, int cout) {
     return tx * v.tw * ty * v.th * tc * v.ct;
 }
 
+// the stem (Cin = 3) takes its own instantiation of variant 0
+inline bool fwd_small_cin(int taps, int variant, int cin) { return taps == 9 && variant == 0 && cin <= 4; }
+
+// the shape half of ConvArgs::vec_ok (the other half: 16-byte aligned x and w)
+inline bool fwd_vec_shape(int wd, int cout) { return wd % 4 == 0 && cout % 4 == 0; }
+
 // K-chunk of 8 input channels everywhere (16 measured slower: more prefetch registers, fewer resident waves)
 template <int TAPS>
 int launch_fwd(int variant, const ConvArgs& a, dim3 grid, hipStream_t s) {
     constexpr int KS = TAPS == 9 ? LF_KC_SMALL : 8;
-    if (TAPS == 9 && variant == 0 && a.cin <= 4) {
+    if (fwd_small_cin(TAPS, variant, a.cin)) {
         // the stem (Cin = 3): a 4-channel K-chunk instead of 8 halves the MFMAs spent on zeros
         conv_mfma_kernel<9, 32, 8, 1, 1, 4, 2, 4><<<grid, kThreads, 0, s>>>(a);
         return LF_OK;
@@ -1585,6 +1591,30 @@ int lf_conv2d_wgrad_variant(int n, int cin, int h, int wd, int cout, int ksize) 
     return plan_wgrad(n, cin, cout, h, wd, ksize).variant;
 }
 
+int lf_conv2d_plan(int n, int cin, int h, int wd, int cout, int ksize, int* out) {
+    LF_REQUIRE(out, "lf_conv2d_plan: null out");
+    LF_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && wd > 0 && (ksize == 1 || ksize == 3),
+               "lf_conv2d_plan: bad dims");
+    const int best = lf_conv2d_variant(h, wd, cout, ksize);
+    out[0] = best;
+    out[1] = fwd_small_cin(ksize * ksize, best, cin) ? 1 : 0;
+    out[2] = conv_stack(best, n, cin, h, wd, cout);
+    out[3] = fwd_vec_shape(wd, cout) ? 1 : 0;
+    return LF_OK;
+}
+
+int lf_conv2d_wgrad_plan(int n, int cin, int h, int wd, int cout, int ksize, int* out) {
+    LF_REQUIRE(out, "lf_conv2d_wgrad_plan: null out");
+    LF_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && wd > 0 && (ksize == 1 || ksize == 3),
+               "lf_conv2d_wgrad_plan: bad dims");
+    const WgPlan pl = plan_wgrad(n, cin, cout, h, wd, ksize);
+    out[0] = pl.variant;
+    out[1] = pl.items_per_split < 3 ? pl.items_per_split : 3;   // 1, 2, or 3+: the steady-state prefetch
+    out[2] = pl.splits > kReduceGroup ? 2 : 1;
+    out[3] = lf_conv2d_wgrad_bn_supported(n, cin, h, wd, cout, ksize);
+    return LF_OK;
+}
+
 static int conv2d_launch(const char* who, const float* x, const float* w, float* y, int n, int cin,
                          int h, int wd, int cout, int ksize, const float* in_scale,
                          const float* in_shift, int in_relu, int accumulate, float* stat_part,
@@ -1606,7 +1636,7 @@ static int conv2d_launch(const char* who, const float* x, const float* w, float*
     a.n = n; a.cin = cin; a.cout = cout; a.h = h; a.wd = wd;
     a.in_relu = in_relu;
     a.accumulate = accumulate;
-    a.vec_ok = (wd % 4 == 0) && (cout % 4 == 0) && aligned16(x) && aligned16(w);
+    a.vec_ok = fwd_vec_shape(wd, cout) && aligned16(x) && aligned16(w);
     a.stack = conv_stack(best, n, cin, h, wd, cout);
     if (a.stack > 1 && !a.vec_ok) {
         if (stat_part != nullptr) {  // the tile count the caller sized its buffers for assumes it

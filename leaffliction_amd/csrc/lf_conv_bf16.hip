@@ -539,9 +539,22 @@ namespace {
 // the same); cout == 32 (+64k): one block, and a 32x16 tile instead so that a staged patch
 // still feeds 16 accumulator tiles per wave
 inline int bf16_nco(int cout) { return cout % 64 == 0 ? 2 : 1; }
+constexpr int bf16_nb(int nco) { return nco == 2 ? 2 : 4; }   // rows per wave: the tile is 4 * NB rows high
 inline int bf16_tiles(int h, int w, int cout) {
-    const int th = bf16_nco(cout) == 2 ? 8 : 16;
+    const int th = 4 * bf16_nb(bf16_nco(cout));
     return ((w + kTW - 1) / kTW) * ((h + th - 1) / th);
+}
+
+// rows of 16 bytes: the epilogue through LDS
+inline bool bf16_wide(bool ybf, int nco, int w) { return ybf && nco == 2 && w % 8 == 0; }
+
+// The entry points' routing: the streaming kernel (lf_conv_bf16s.hip) or the K-chunked one.  The training
+// convolution streams every shape the streaming kernel covers; the inference ones (kBf16Act, kBf16ActMean) only
+// the 32-channel layers with bf16 output (see lf_conv2d_bf16_act).
+enum { kBf16Act = 0, kBf16ActMean = 1, kBf16Train = 2 };
+inline bool bf16_streams(int entry, int y_bf16, int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
+    if (entry != kBf16Train && !(y_bf16 && cout == 32)) return false;
+    return lf::conv_bf16s_parts(n, cin, h, w, cout, ksize, x_bf16) > 0;
 }
 
 template <bool XBF, bool YBF, bool TR>
@@ -549,20 +562,20 @@ void launch_conv_bf16(const Bf16ConvArgs& a, int ksize, hipStream_t s) {
     const int nco = bf16_nco(a.cout);
     dim3 grid(bf16_tiles(a.h, a.w, a.cout), a.cout / (32 * nco), a.n);
     constexpr bool W = YBF;
-    const bool wide = YBF && nco == 2 && a.w % 8 == 0;  // rows of 16 bytes: the epilogue through LDS
+    const bool wide = bf16_wide(YBF, nco, a.w);
     if (ksize == 3) {
         if (nco == 2) {
-            if (wide) conv_bf16_kernel<9, 2, 2, XBF, YBF, TR, W><<<grid, kThreads, 0, s>>>(a);
-            else conv_bf16_kernel<9, 2, 2, XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
+            if (wide) conv_bf16_kernel<9, 2, bf16_nb(2), XBF, YBF, TR, W><<<grid, kThreads, 0, s>>>(a);
+            else conv_bf16_kernel<9, 2, bf16_nb(2), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
         } else {
-            conv_bf16_kernel<9, 1, 4, XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
+            conv_bf16_kernel<9, 1, bf16_nb(1), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
         }
     } else {
         if (nco == 2) {
-            if (wide) conv_bf16_kernel<1, 2, 2, XBF, YBF, TR, W><<<grid, kThreads, 0, s>>>(a);
-            else conv_bf16_kernel<1, 2, 2, XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
+            if (wide) conv_bf16_kernel<1, 2, bf16_nb(2), XBF, YBF, TR, W><<<grid, kThreads, 0, s>>>(a);
+            else conv_bf16_kernel<1, 2, bf16_nb(2), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
         } else {
-            conv_bf16_kernel<1, 1, 4, XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
+            conv_bf16_kernel<1, 1, bf16_nb(1), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
         }
     }
 }
@@ -624,7 +637,7 @@ int lf_conv2d_bf16_act(const void* x, int x_bf16, const uint16_t* wprep, void* y
     LF_REQUIRE(((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(wprep)) & 15) == 0,
                "lf_conv2d_bf16: x and wprep must be 16-byte aligned");
     hipStream_t s = lf::as_stream(stream);
-    if (y_bf16 && cout == 32 && lf::conv_bf16s_parts(n, cin, h, w, cout, ksize, x_bf16) > 0) {
+    if (bf16_streams(kBf16Act, y_bf16, n, cin, h, w, cout, ksize, x_bf16)) {
         // the 224x224 stage (stem, 32->32): the streaming kernel (resident filter bank, 16-byte accesses).
         // The 64-channel layers of the 112x112 stage stay on the K-chunked kernel: it was well ahead there
         // without a read-modify-write epilogue (1.7 ms against 3.2 ms at 64->64, batch 1,024) and is level with
@@ -688,7 +701,7 @@ int lf_conv2d_bf16_train(const void* x, int x_bf16, const uint16_t* wprep, uint1
         }
     }
     hipStream_t s = lf::as_stream(stream);
-    if (lf::conv_bf16s_parts(n, cin, h, w, cout, ksize, x_bf16) > 0) {
+    if (bf16_streams(kBf16Train, 1, n, cin, h, w, cout, ksize, x_bf16)) {
         lf::ConvBf16TrainArgs t{};
         t.x = x; t.wprep = wprep; t.y = y; t.n = n; t.cin = cin; t.h = h; t.w = w; t.cout = cout;
         t.in_scale = in_scale; t.in_shift = in_shift; t.in_relu = in_relu; t.accumulate = accumulate;
@@ -715,7 +728,8 @@ size_t lf_conv2d_bf16_act_mean_workspace(int n, int cin, int h, int w, int cout,
     if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0) return 0;
     // (the same routing as lf_conv2d_bf16_act: the streaming kernel for the 32-channel layers only, so that the
     // stored activation is bit-equal with and without the means)
-    const int units = cout == 32 ? lf::conv_bf16s_units_per_image(n, cin, h, w, cout, ksize, x_bf16) : 0;
+    const int units = bf16_streams(kBf16ActMean, 1, n, cin, h, w, cout, ksize, x_bf16)
+                          ? lf::conv_bf16s_units_per_image(n, cin, h, w, cout, ksize, x_bf16) : 0;
     if (units > 0) return (size_t)n * units * cout * sizeof(float);
     return (size_t)n * bf16_tiles(h, w, cout) * cout * 2 * sizeof(float);
 }
@@ -747,7 +761,8 @@ int lf_conv2d_bf16_act_mean(const void* x, int x_bf16, const uint16_t* wprep, ui
     hipStream_t s = lf::as_stream(stream);
     float* part = static_cast<float*>(workspace);
     const float inv = 1.0f / (float)((size_t)h * w);
-    const int units = cout == 32 ? lf::conv_bf16s_units_per_image(n, cin, h, w, cout, ksize, x_bf16) : 0;
+    const int units = bf16_streams(kBf16ActMean, 1, n, cin, h, w, cout, ksize, x_bf16)
+                          ? lf::conv_bf16s_units_per_image(n, cin, h, w, cout, ksize, x_bf16) : 0;
     if (units > 0) {
         lf::ConvBf16TrainArgs t{};
         t.x = x; t.wprep = wprep; t.y = y; t.n = n; t.cin = cin; t.h = h; t.w = w; t.cout = cout;
@@ -770,6 +785,42 @@ int lf_conv2d_bf16_act_mean(const void* x, int x_bf16, const uint16_t* wprep, ui
     if (x_bf16) launch_conv_bf16<true, true, true>(a, ksize, s); else launch_conv_bf16<false, true, true>(a, ksize, s);
     partial_sums_mean_kernel<<<(n * cout + 255) / 256, 256, 0, s>>>(part, means, n, cout, tiles, 1, inv);
     return lf::check_launch("lf_conv2d_bf16_act_mean");
+}
+
+int lf_conv2d_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16, int y_bf16, int entry,
+                        int accumulate, int mask, int* out) {
+    LF_REQUIRE(out, "lf_conv2d_bf16_plan: null out");
+    LF_REQUIRE(n > 0 && cin > 0 && h > 0 && w > 0 && cout > 0 && (ksize == 1 || ksize == 3),
+               "lf_conv2d_bf16_plan: bad dims");
+    LF_REQUIRE(entry == kBf16Act || entry == kBf16ActMean || entry == kBf16Train, "lf_conv2d_bf16_plan: bad entry");
+    const int ybf = entry == kBf16Act ? (y_bf16 ? 1 : 0) : 1;
+    for (int i = 0; i < 14; ++i) out[i] = 0;
+    out[1] = ksize * ksize;
+    out[7] = x_bf16 ? 1 : 0;
+    out[8] = ybf;
+    if (bf16_streams(entry, ybf, n, cin, h, w, cout, ksize, x_bf16)) {
+        int sp[8];
+        lf::conv_bf16s_plan(n, cin, h, w, cout, ksize, x_bf16, sp);
+        out[0] = 1;
+        out[2] = sp[0];
+        out[3] = sp[1];
+        out[5] = sp[2];
+        out[6] = sp[3];
+        out[7] = sp[4];
+        out[10] = lf::conv_bf16s_rmw(entry == kBf16Train ? accumulate : 0, entry == kBf16Train && mask) ? 1 : 0;
+        out[11] = sp[5];
+        out[12] = sp[6];
+        out[13] = sp[7];
+        return LF_OK;
+    }
+    const int nco = bf16_nco(cout);
+    out[3] = nco;
+    out[4] = bf16_nb(nco);
+    out[5] = kTW;
+    out[6] = 4 * bf16_nb(nco);
+    out[9] = entry == kBf16Act ? 0 : 1;
+    out[10] = bf16_wide(ybf, nco, w) ? 1 : 0;
+    return LF_OK;
 }
 
 int lf_conv2d_bf16_f32(const float* x, const uint16_t* wprep, float* y, int n, int cin, int h, int w,

@@ -612,7 +612,7 @@ int launch_s2(const lf::ConvBf16TrainArgs& a, int wgs, hipStream_t s) {
 
 template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF>
 int launch_s(const lf::ConvBf16TrainArgs& a, int wgs, hipStream_t s) {
-    return (a.accumulate || a.stat_mask_y != nullptr) ? launch_s2<TAPS, CI, NCO, TW, TH, XBF, true>(a, wgs, s)
+    return lf::conv_bf16s_rmw(a.accumulate, a.stat_mask_y != nullptr) ? launch_s2<TAPS, CI, NCO, TW, TH, XBF, true>(a, wgs, s)
                                                       : launch_s2<TAPS, CI, NCO, TW, TH, XBF, false>(a, wgs, s);
 }
 
@@ -644,6 +644,20 @@ long long conv_bf16s_parts(int n, int cin, int h, int w, int cout, int ksize, in
 int conv_bf16s_units_per_image(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
     const SPlan pl = plan_s(n, cin, h, w, cout, ksize, x_bf16);
     return pl.ok ? pl.tiles_x * pl.segs : 0;
+}
+
+int conv_bf16s_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16, int* out) {
+    const SPlan pl = plan_s(n, cin, h, w, cout, ksize, x_bf16);
+    if (!pl.ok) return 0;
+    out[0] = pl.ci;
+    out[1] = pl.nco;
+    out[2] = pl.tw;
+    out[3] = pl.th;
+    out[4] = pl.ci == 16 ? 0 : 1;   // dispatch_s: the 16-channel slot is the fp32 stem input
+    out[5] = pl.segs > 1 ? 1 : 0;
+    out[6] = pl.interleave;
+    out[7] = max_units_per_workgroup(n, pl.tiles_x * pl.segs, pl.wgs, pl.interleave) > 1 ? 1 : 0;
+    return 1;
 }
 
 int conv_bf16s_launch(ConvBf16TrainArgs a, int ksize, int x_bf16, hipStream_t s) {

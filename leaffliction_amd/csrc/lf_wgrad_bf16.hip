@@ -617,11 +617,31 @@ int launch_wg(const WgBf16Args& a, dim3 grid, hipStream_t s) {
     return LF_OK;
 }
 
+// The instantiation of wgrad_bf16_kernel a plan runs: its template arguments
+struct WgKernel {
+    int taps, tw, th, cib, cob, stem, g, wprq;
+};
+
+WgKernel wg_kernel(const WgBf16Plan& pl, int ksize, int w) {
+    WgKernel k{};
+    k.taps = pl.stem ? 1 : ksize * ksize;   // the stem: im2col rows, one tap
+    k.tw = pl.tw; k.th = pl.th; k.cib = pl.cib; k.cob = pl.cob; k.stem = pl.stem;
+    k.g = w % 8 == 0 ? 8 : 4;                 // rows 16-byte aligned: 8-pixel staging groups
+    // one 32-channel block each way (32->32 at 224x224, the largest tensors): measured on one MI355X
+    // box — 12 waves with 8-byte staging groups 1.35 ms, 6 waves with 16-byte groups 1.52 ms, a
+    // producer/consumer split with two tiles of loads in flight 1.57 ms, 12 waves with 16-byte groups
+    // (register spills) 2.52 ms: this shape wants waves more than it wants wide loads
+    if (!pl.stem && ksize == 3 && pl.cib == 1 && pl.cob == 1 && pl.tw == 56) {
+        k.g = 4;
+        k.wprq = 4;
+    }
+    return k;
+}
+
 template <int TAPS>
-int dispatch_wg(const WgBf16Plan& pl, const WgBf16Args& a, dim3 grid, hipStream_t s) {
-    const bool wide = a.w % 8 == 0;  // rows 16-byte aligned: 8-pixel staging groups
+int dispatch_wg(const WgKernel& k, const WgBf16Args& a, dim3 grid, hipStream_t s) {
 #define LF_WG(TW_, TH_, CIB_, COB_, G_) \
-    if (pl.tw == TW_ && pl.th == TH_ && pl.cib == CIB_ && pl.cob == COB_ && wide == (G_ == 8)) \
+    if (k.tw == TW_ && k.th == TH_ && k.cib == CIB_ && k.cob == COB_ && k.g == G_ && k.wprq == 0) \
         return launch_wg<TAPS, TW_, TH_, CIB_, COB_, false, G_>(a, grid, s)
     LF_WG(32, 8, 1, 1, 8);
     LF_WG(32, 8, 1, 2, 8);
@@ -636,7 +656,7 @@ int dispatch_wg(const WgBf16Plan& pl, const WgBf16Args& a, dim3 grid, hipStream_
     LF_WG(28, 4, 1, 2, 4);
     LF_WG(28, 4, 2, 2, 4);
 #undef LF_WG
-    lf::set_error("lf_conv2d_wgrad_bf16: no kernel for tile %dx%d blocks %dx%d", pl.tw, pl.th, pl.cib, pl.cob);
+    lf::set_error("lf_conv2d_wgrad_bf16: no kernel for tile %dx%d blocks %dx%d", k.tw, k.th, k.cib, k.cob);
     return LF_ERR_INVALID;
 }
 
@@ -650,6 +670,22 @@ size_t lf_conv2d_wgrad_bf16_workspace(int n, int cin, int h, int w, int cout, in
     const size_t count = (size_t)cin * ksize * ksize * cout;
     const size_t groups = (pl.splits + kSumGroup - 1) / kSumGroup;
     return ((size_t)pl.splits + groups) * count * sizeof(float);
+}
+
+int lf_conv2d_wgrad_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int* out) {
+    LF_REQUIRE(out, "lf_conv2d_wgrad_bf16_plan: null out");
+    LF_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && (ksize == 1 || ksize == 3) && cout % 32 == 0,
+               "lf_conv2d_wgrad_bf16_plan: bad dims");
+    const WgBf16Plan pl = plan_wgrad_bf16(n, cin, cout, h, w, ksize);
+    const WgKernel k = wg_kernel(pl, ksize, w);
+    out[0] = k.taps; out[1] = k.tw; out[2] = k.th; out[3] = k.cib; out[4] = k.cob; out[5] = k.stem;
+    out[6] = k.g; out[7] = k.wprq;
+    out[8] = pl.segs > 1 ? 1 : 0;
+    out[9] = pl.interleave;
+    out[10] = lf::max_units_per_workgroup(n, pl.tiles_x * pl.segs, pl.splits, pl.interleave) > 1 ? 1 : 0;
+    out[11] = pl.splits > kSumGroup ? 2 : 1;
+    out[12] = pl.seg_tiles < 3 ? pl.seg_tiles : 3;   // tiles per unit: 1, 2, or 3+ (the in-loop issue of tile i + 2)
+    return LF_OK;
 }
 
 int lf_conv2d_wgrad_bf16(const void* x, const uint16_t* g, const uint16_t* bn_y, const float* alpha_nc,
@@ -689,17 +725,14 @@ int lf_conv2d_wgrad_bf16(const void* x, const uint16_t* g, const uint16_t* bn_y,
     dim3 grid(pl.splits, pl.gy, pl.gz);
     hipStream_t s = lf::as_stream(stream);
     int rc;
-    // one 32-channel block each way (32->32 at 224x224, the largest tensors): measured on one MI355X
-    // box — 12 waves with 8-byte staging groups 1.35 ms, 6 waves with 16-byte groups 1.52 ms, a
-    // producer/consumer split with two tiles of loads in flight 1.57 ms, 12 waves with 16-byte groups
-    // (register spills) 2.52 ms: this shape wants waves more than it wants wide loads
-    if (!pl.stem && ksize == 3 && pl.cib == 1 && pl.cob == 1 && pl.tw == 56)
+    const WgKernel k = wg_kernel(pl, ksize, w);
+    if (k.wprq == 4)
         rc = launch_wg<9, 56, 4, 1, 1, false, 4, 4>(a, grid, s);
-    else if (pl.stem)
-        rc = a.w % 8 == 0 ? launch_wg<1, 32, 8, 1, 1, true, 8>(a, grid, s)
-                          : launch_wg<1, 32, 8, 1, 1, true, 4>(a, grid, s);
+    else if (k.stem)
+        rc = k.g == 8 ? launch_wg<1, 32, 8, 1, 1, true, 8>(a, grid, s)
+                      : launch_wg<1, 32, 8, 1, 1, true, 4>(a, grid, s);
     else
-        rc = ksize == 3 ? dispatch_wg<9>(pl, a, grid, s) : dispatch_wg<1>(pl, a, grid, s);
+        rc = ksize == 3 ? dispatch_wg<9>(k, a, grid, s) : dispatch_wg<1>(k, a, grid, s);
     if (rc != LF_OK) return rc;
     // slabs -> dw, fixed order
     const size_t count = (size_t)cin * ksize * ksize * cout;

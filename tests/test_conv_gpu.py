@@ -136,14 +136,17 @@ def test_conv_bn_stats_epilogue(cuda, n, cin, cout, h, w, k):
     assert torch.allclose(stats, stats2, rtol=1e-4, atol=1e-5 * scale)
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w,with_se,k,relu", [
+BN_WGRAD_SHAPES = [  # n, cin, cout, h, w, with_se, k, relu
     (3, 32, 32, 32, 32, True, 3, True),     # fused, CI_T == Cin
     (2, 64, 64, 32, 32, False, 3, True),    # two ci blocks
     (2, 32, 64, 56, 56, True, 3, True),     # 28-wide tiles
     (2, 3, 32, 64, 64, False, 3, True),     # stem: small-Cin kernel
     (2, 32, 64, 32, 32, False, 1, False),   # 1x1 projection BN (no ReLU)
     (2, 64, 128, 56, 56, False, 1, False),
-    (2, 16, 24, 20, 12, True, 3, True)])    # unsupported -> fallback
+    (2, 16, 24, 20, 12, True, 3, True)]     # unsupported -> fallback
+
+
+@pytest.mark.parametrize("n,cin,cout,h,w,with_se,k,relu", BN_WGRAD_SHAPES)
 def test_bn_backward_inside_wgrad(cuda, n, cin, cout, h, w, with_se, k, relu):
     """BatchNorm backward formed inside the weight-gradient kernel (dy written on the side) vs
     the standalone BN-backward kernel followed by the plain wgrad, and vs torch autograd."""
@@ -198,13 +201,16 @@ def test_bn_backward_inside_wgrad(cuda, n, cin, cout, h, w, with_se, k, relu):
     assert torch.allclose(dg_f, dg_s, rtol=1e-5, atol=1e-5) and torch.allclose(db_f, db_s, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w,k,acc", [(2, 32, 32, 64, 64, 3, False),
-                                                  (2, 64, 32, 32, 32, 3, True),
-                                                  (1, 256, 128, 28, 28, 3, False),   # masked 28-wide tiles
-                                                  (3, 128, 128, 28, 28, 3, True),    # two-image strips, accumulate
-                                                  (4, 64, 256, 28, 28, 3, False),    # strips, two cout tiles
-                                                  (2, 16, 24, 20, 12, 3, True),      # ragged / scalar path
-                                                  (2, 5, 7, 9, 11, 3, False)])
+BNBWD_SHAPES = [(2, 32, 32, 64, 64, 3, False),  # n, cin, cout, h, w, k, acc
+                (2, 64, 32, 32, 32, 3, True),
+                (1, 256, 128, 28, 28, 3, False),   # masked 28-wide tiles
+                (3, 128, 128, 28, 28, 3, True),    # two-image strips, accumulate
+                (4, 64, 256, 28, 28, 3, False),    # strips, two cout tiles
+                (2, 16, 24, 20, 12, 3, True),      # ragged / scalar path
+                (2, 5, 7, 9, 11, 3, False)]
+
+
+@pytest.mark.parametrize("n,cin,cout,h,w,k,acc", BNBWD_SHAPES)
 def test_conv_bn_backward_sums_epilogue(cuda, n, cin, cout, h, w, k, acc):
     """Input-gradient conv whose epilogue gathers the next BN backward's channel sums: same
     output as the plain conv, and dgamma / dbeta / dy equal to the two-pass BN backward."""

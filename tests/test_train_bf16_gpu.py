@@ -43,7 +43,7 @@ def close_bf16(got, ref, max_frac, terms=None):
     assert frac <= max_frac, frac
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w,k,xbf,pro,acc,stat", [
+TRAIN_SHAPES = [  # n, cin, cout, h, w, k, xbf, pro, acc, stat
     (2, 32, 32, 16, 32, 3, True, True, False, "fwd"),
     (2, 3, 32, 16, 32, 3, False, False, False, "fwd"),
     (2, 64, 64, 8, 56, 3, True, False, True, "bwd"),
@@ -61,7 +61,10 @@ def close_bf16(got, ref, max_frac, terms=None):
     (16, 32, 32, 8, 136, 3, True, True, False, "fwd"),    # three strips per image, 48 of them over the XCDs
     (3, 3, 32, 20, 64, 3, False, False, False, "fwd"),    # the stem (fp32 input) on the ring
     (9, 32, 64, 16, 64, 1, True, True, False, "fwd"),     # 1x1: no halo, a ring of TH rows
-])
+]
+
+
+@pytest.mark.parametrize("n,cin,cout,h,w,k,xbf,pro,acc,stat", TRAIN_SHAPES)
 def test_conv2d_bf16_train(cuda, n, cin, cout, h, w, k, xbf, pro, acc, stat):
     from leaffliction_amd import nn
     g = torch.Generator().manual_seed(n * 1000 + cin + h)
