@@ -513,6 +513,9 @@ int lf_conv2d_wgrad_variant(int n, int cin, int h, int wd, int cout, int ksize);
  * coverage test tests/test_conv_plans.py compares the benchmark's layers with the tested shapes).
  * lf_conv2d_plan (lf_conv2d_f32 / _stats_f32 / _bnbwd_f32), out[4]:
  *   {variant, Cin <= 4 stem instantiation, images per strip (stack), vector path by shape}
+ *   Arithmetic: every 3x3 plan but the stem's (out[1] = 1) computes Winograd F(2x2,3x3) on the
+ *   variant's spatial tile (32 output channels per workgroup, 16 for variant 6); the stem and all
+ *   1x1 plans compute the direct implicit GEMM.  The choice depends on ksize and out[0..1] only.
  * lf_conv2d_wgrad_plan (lf_conv2d_wgrad_f32 / _bn_f32), out[4]:
  *   {variant (5 = small-Cin), items per split (1, 2 or 3 = three or more), reduce stages (1 or 2),
  *    fused BN allowed}

@@ -18,6 +18,9 @@
 //   CU so one workgroup's LDS write phase overlaps another's MFMAs.
 //   An optional prologue applies y = relu(x*scale[c]+shift[c]) to the input while staging
 //   (BatchNorm+ReLU of the producer fused into the consumer; zero padding stays zero).
+//   Every 3x3 launch but the stem's computes Winograd F(2x2,3x3) on the same staged patch
+//   (v_mfma_f32_16x16x4_f32, 16 products per 2x2 outputs instead of 36; see the kernel); the
+//   direct GEMM above serves the stem and the 1x1 convolutions.
 //
 // wgrad kernel (wgrad_mfma_kernel): dW[ci][tap][co] = sum_pixels X[ci][p+tap] dY[co][p],
 //   K = pixels, split across workgroups and across the waves of a workgroup (reduced through
@@ -31,11 +34,9 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
-#ifndef LF_KC_SMALL
-#define LF_KC_SMALL 8
-#endif
 
 __device__ __forceinline__ float pro_apply(float v, float sc, float sh, int relu) {
     v = fmaf(v, sc, sh);
@@ -94,33 +95,106 @@ __device__ __forceinline__ float dpp_move(float v) {
     return __builtin_bit_cast(
         float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
 }
-__device__ __forceinline__ float half_sum32(float v) {
+__device__ __forceinline__ float row_sum16(float v) {
     v += dpp_move<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
     v += dpp_move<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
     v += dpp_move<0x141, 0xf>(v);  // row_half_mirror
     v += dpp_move<0x140, 0xf>(v);  // row_mirror: every lane of a 16-lane row holds the row sum
+    return v;
+}
+__device__ __forceinline__ float half_sum32(float v) {
+    v = row_sum16(v);
     v += dpp_move<0x142, 0xa>(v);  // row_bcast15 into rows 1 and 3
     return v;
+}
+
+// Winograd F(2x2,3x3) transforms (Lavin & Gray 2016): Y = A^T [(G g G^T) . (B^T d B)] A with
+//   G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1], B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1],
+//   A^T = [1 1 1 0; 0 1 -1 -1].
+// Every coefficient is 0, +-1 or +-1/2, so small-integer data stays exact.  Index = row * 4 + col.
+__device__ __forceinline__ void wino_filter(const float (&g)[9], float (&u)[16]) {
+    float t[4][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float s = g[c] + g[6 + c];
+        t[0][c] = g[c];
+        t[1][c] = (s + g[3 + c]) * 0.5f;
+        t[2][c] = (s - g[3 + c]) * 0.5f;
+        t[3][c] = g[6 + c];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float s = t[r][0] + t[r][2];
+        u[r * 4 + 0] = t[r][0];
+        u[r * 4 + 1] = (s + t[r][1]) * 0.5f;
+        u[r * 4 + 2] = (s - t[r][1]) * 0.5f;
+        u[r * 4 + 3] = t[r][2];
+    }
+}
+__device__ __forceinline__ void wino_input(const float (&d)[16], float (&v)[16]) {
+    float t[16];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        t[0 + c] = d[0 + c] - d[8 + c];
+        t[4 + c] = d[4 + c] + d[8 + c];
+        t[8 + c] = d[8 + c] - d[4 + c];
+        t[12 + c] = d[4 + c] - d[12 + c];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        v[r * 4 + 0] = t[r * 4 + 0] - t[r * 4 + 2];
+        v[r * 4 + 1] = t[r * 4 + 1] + t[r * 4 + 2];
+        v[r * 4 + 2] = t[r * 4 + 2] - t[r * 4 + 1];
+        v[r * 4 + 3] = t[r * 4 + 1] - t[r * 4 + 3];
+    }
+}
+__device__ __forceinline__ void wino_output(const float (&m)[16], float (&y)[4]) {
+    float b[2][4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        b[0][c] = m[0 + c] + m[4 + c] + m[8 + c];
+        b[1][c] = m[4 + c] - m[8 + c] - m[12 + c];
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        y[r * 2 + 0] = b[r][0] + b[r][1] + b[r][2];
+        y[r * 2 + 1] = b[r][1] - b[r][2] - b[r][3];
+    }
 }
 
 // ---------------------------------------------------------------------------
 // forward / dgrad
 // ---------------------------------------------------------------------------
-// TAPS: 9 (3x3) or 1 (1x1).  Tile TW x TH pixels = NPB blocks of 32 (flat index).
-// Waves: WCO x WPX = 4; each wave computes MB cout-blocks x NB pixel-blocks.
+// TAPS: 9 (3x3) or 1 (1x1).
+// Direct (WINO = false): tile TW x TH pixels = NPB blocks of 32 (flat index); waves WCO x WPX = 4,
+//   each wave computes MB cout-blocks x NB pixel-blocks of 32 with v_mfma_f32_32x32x2_f32.
+// Winograd F(2x2,3x3) (WINO = true, TAPS = 9): the tile is NT = (TW/2)*(TH/2) Winograd tiles
+//   (flat index, 2x2 output pixels each) and the workgroup's CT = 16*WCO*MB output channels.
+//   Per 4-channel K-step, each of the 16 transform positions is a GEMM U[pos] (cout x cin) .
+//   V[pos] (cin x tiles) on v_mfma_f32_16x16x4_f32; a wave owns MB cout-blocks x NB tile-blocks
+//   of 16, all 16 positions, so M[pos] for one (cout, tile) sits in one lane and register and the
+//   inverse transform is register-local.  U = G g G^T is formed while the weights are staged
+//   (one (channel, cout) pair per thread) and kept in LDS; V = B^T d B is formed per lane from
+//   the LDS patch.  The patch staging (prologue, zeros, two-image strip) is the direct kernel's.
 // min waves/SIMD asked of the register allocator: accumulators + VGPRs share one 512-entry
 // file per SIMD lane; with the prefetch registers <=32 accumulators fit 3 waves, more fit 2.
-template <int TAPS, int TW, int TH, int WCO, int MB, int WPX, int NB, int kKC, bool STK = false>
-__global__ __launch_bounds__(kThreads, (MB * NB * 16 <= 32 ? 3 : 2))
+template <int TAPS, int TW, int TH, int WCO, int MB, int WPX, int NB, int kKC, bool STK = false,
+          bool WINO = false>
+__global__ __launch_bounds__(kThreads, (!WINO && MB * NB * 16 <= 32 ? 3 : 2))
 void conv_mfma_kernel(ConvArgs p) {
     constexpr int NPB = TW * TH / 32;
-    static_assert(TW * TH % 32 == 0 && TW % 4 == 0, "tile must be whole 32-pixel blocks, TW % 4 == 0");
-    static_assert(WCO * WPX == 4 && WPX * NB == NPB, "wave decomposition");
-    constexpr int CT = 32 * WCO * MB;
+    constexpr int TXN = TW / 2, NT = TXN * (TH / 2);  // Winograd tiles per row / per workgroup
+    static_assert(TW % 4 == 0, "float4 patch rows");
+    static_assert(WINO || TW * TH % 32 == 0, "tile must be whole 32-pixel blocks");
+    static_assert(!WINO || (TAPS == 9 && TH % 2 == 0 && kKC % 4 == 0), "F(2x2,3x3): even tile, 4-channel K-steps");
+    static_assert(WCO * WPX == 4 && (WINO ? WPX * NB * 16 >= NT : WPX * NB == NPB), "wave decomposition");
+    constexpr int CT = (WINO ? 16 : 32) * WCO * MB;
+    constexpr int kUP = 20;  // LDS pitch of one (channel, cout) U: 16 positions + 4 (conflict-free b128 reads)
     constexpr int HALO = TAPS == 9 ? 1 : 0;
     constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO + (STK ? 2 * HALO : 0), PP = PW * PH;
     constexpr int PATCH = kKC * PP;
-    constexpr int WSZ = kKC * TAPS * CT;
+    constexpr int WSZ = WINO ? kKC * CT * kUP : kKC * TAPS * CT;
+    static_assert(PATCH % 4 == 0, "16-byte aligned weight region");
     // vector staging: per patch row TW/4 float4 interior items + 2 halo scalars, kept in two
     // homogeneous item arrays (mixing both kinds in one array makes the compiler wait for
     // every load right where it is issued)
@@ -182,39 +256,141 @@ void conv_mfma_kernel(ConvArgs p) {
     }
     const int abase = khalf * TAPS * CT + wave_co * MB * 32 + j;
 
-    f32x16 acc[MB][NB];
+    f32x16 acc[WINO ? 1 : MB][WINO ? 1 : NB];
+    if constexpr (!WINO) {
 #pragma unroll
-    for (int m = 0; m < MB; ++m)
+        for (int m = 0; m < MB; ++m)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
+            for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][nb][r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[m][nb][r] = 0.f;
+    }
+
+    // Winograd: lane l reads the 4x4 patch window of tile (l & 15) of each of its tile-blocks for
+    // channel (l >> 4) of the K-step (tiles past NT read the last tile's window; they are never
+    // stored), and U[cout = l & 15][channel = l >> 4] of each of its cout-blocks
+    const int wq = lane >> 4, wl = lane & 15;
+    int vbase[WINO ? NB : 1];
+    const int ubase = (wq * CT + wave_co * MB * 16 + wl) * kUP;
+    f32x4 wacc[WINO ? MB : 1][WINO ? NB : 1][16];
+    if constexpr (WINO) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            const int t = min((wave_px * NB + nb) * 16 + wl, NT - 1);
+            const int r0 = 2 * (t / TXN), prow = (STK && r0 >= ra) ? r0 + 2 : r0;
+            vbase[nb] = wq * PP + prow * PW + 2 * (t % TXN);
+        }
+#pragma unroll
+        for (int m = 0; m < MB; ++m)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) wacc[m][nb][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
     const bool pro = p.in_scale != nullptr;
 
-    // cp loop only partially unrolled: the scheduler otherwise hoists dozens of LDS reads and
-    // the accumulators + prefetch registers no longer fit
-    auto compute_chunk = [&]() {
-#pragma unroll 2
-        for (int cp = 0; cp < kKC / 2; ++cp) {
-            const float* lwc = lw + abase + 2 * cp * TAPS * CT;
-            const float* lpc = lp + 2 * cp * PP;
+    auto compute_chunk_wino = [&]() {
+        if constexpr (WINO) {
 #pragma unroll
-            for (int tap = 0; tap < TAPS; ++tap) {
-                const int dy = TAPS == 9 ? tap / 3 : 0, dx = TAPS == 9 ? tap % 3 : 0;
-                float a[MB], b[NB];
+            for (int s = 0; s < kKC / 4; ++s) {
+                // the cout-blocks' U first, then one tile-block's V at a time
+                float u[MB][16];
 #pragma unroll
-                for (int m = 0; m < MB; ++m) a[m] = lwc[tap * CT + m * 32];
+                for (int m = 0; m < MB; ++m) {
+                    const float4* us = reinterpret_cast<const float4*>(lw + ubase + (4 * s * CT + m * 16) * kUP);
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) b[nb] = lpc[bbase[nb] + dy * PW + dx];
+                    for (int q4 = 0; q4 < 4; ++q4) {
+                        const float4 t = us[q4];
+                        u[m][4 * q4 + 0] = t.x;
+                        u[m][4 * q4 + 1] = t.y;
+                        u[m][4 * q4 + 2] = t.z;
+                        u[m][4 * q4 + 3] = t.w;
+                    }
+                }
 #pragma unroll
-                for (int m = 0; m < MB; ++m)
+                for (int nb = 0; nb < NB; ++nb) {
+                    const float* src = lp + vbase[nb] + 4 * s * PP;
+                    float d[16], v[16];
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[m][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b[nb], acc[m][nb], 0,
-                                                                          0, 0);
+                    for (int r = 0; r < 4; ++r) {
+                        const float2 lo = *reinterpret_cast<const float2*>(src + r * PW);
+                        const float2 hi = *reinterpret_cast<const float2*>(src + r * PW + 2);
+                        d[r * 4 + 0] = lo.x;
+                        d[r * 4 + 1] = lo.y;
+                        d[r * 4 + 2] = hi.x;
+                        d[r * 4 + 3] = hi.y;
+                    }
+                    wino_input(d, v);
+#pragma unroll
+                    for (int m = 0; m < MB; ++m)
+#pragma unroll
+                        for (int q = 0; q < 16; ++q)
+                            wacc[m][nb][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[m][q], v[q], wacc[m][nb][q], 0, 0, 0);
+                }
             }
         }
+    };
+
+    // Winograd weights: thread (kc, co) of the chunk fetches the 9 taps of one filter into
+    // registers (during the previous chunk's MFMAs) and stores U = G g G^T to LDS
+    constexpr int NUW = WINO ? kKC * CT : 1;
+    static_assert(NUW <= kThreads, "one (channel, cout) filter per thread");
+    const int ukc = tid / CT, uco = tid - ukc * CT;
+    const bool u_on = WINO && tid < NUW;
+    const unsigned ugo = (u_on && co0 + uco < p.cout) ? 4u * ((unsigned)ukc * 9u * (unsigned)p.cout + (unsigned)(co0 + uco)) : kBufOob;
+    float wr[WINO ? 9 : 1];
+    auto load_u = [&](int c0) {
+        if constexpr (WINO) {
+            // filters of channels beyond Cin fall outside the chunk's buffer size -> zeros
+            const __amdgpu_buffer_rsrc_t rw =
+                buf_rsrc(p.w + (size_t)c0 * 9 * p.cout, 4u * (unsigned)(min(kKC, p.cin - c0) * 9) * (unsigned)p.cout);
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+                wr[t] = buf_load1(rw, ugo == kBufOob ? kBufOob : ugo + 4u * (unsigned)t * (unsigned)p.cout);
+        }
+    };
+    auto store_u = [&]() {
+        if constexpr (WINO) if (u_on) {
+            float u[16];
+            wino_filter(wr, u);
+            float4* dst = reinterpret_cast<float4*>(lw + (ukc * CT + uco) * kUP);
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) dst[q4] = make_float4(u[4 * q4], u[4 * q4 + 1], u[4 * q4 + 2], u[4 * q4 + 3]);
+        }
+    };
+
+    // cp loop only partially unrolled: the scheduler otherwise hoists dozens of LDS reads and
+    // the accumulators + prefetch registers no longer fit
+    auto compute_chunk_direct = [&]() {
+        if constexpr (!WINO) {
+#pragma unroll 2
+            for (int cp = 0; cp < kKC / 2; ++cp) {
+                const float* lwc = lw + abase + 2 * cp * TAPS * CT;
+                const float* lpc = lp + 2 * cp * PP;
+#pragma unroll
+                for (int tap = 0; tap < TAPS; ++tap) {
+                    const int dy = TAPS == 9 ? tap / 3 : 0, dx = TAPS == 9 ? tap % 3 : 0;
+                    float a[MB], b[NB];
+#pragma unroll
+                    for (int m = 0; m < MB; ++m) a[m] = lwc[tap * CT + m * 32];
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) b[nb] = lpc[bbase[nb] + dy * PW + dx];
+#pragma unroll
+                    for (int m = 0; m < MB; ++m)
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb)
+                            acc[m][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b[nb], acc[m][nb], 0,
+                                                                              0, 0);
+                }
+            }
+        }
+    };
+    auto compute_chunk = [&]() {
+        if constexpr (WINO)
+            compute_chunk_wino();
+        else
+            compute_chunk_direct();
     };
 
     const int nchunks = (p.cin + kKC - 1) / kKC;
@@ -228,7 +404,8 @@ void conv_mfma_kernel(ConvArgs p) {
         unsigned okmask = 0;  // bit i: interior item i in-image; bit 16+i: halo item i in-image
         // variants with > 64 accumulators have no registers left to hold the weight prefetch:
         // they prefetch the patch only and fetch the (L2-resident) weights in the store phase
-        constexpr bool kPrefetchW = MB * NB * 16 <= 64;
+        // (Winograd: 9 registers of filter taps per thread, prefetched unless the wave has two tile-blocks)
+        constexpr bool kPrefetchW = WINO ? NB == 1 : MB * NB * 16 <= 64;
         if (pro) {  // BatchNorm scale/shift of the producer: staged once per workgroup
             for (int c = tid; c < p.cin && c < kMaxProC; c += kThreads) {
                 lsc[c] = p.in_scale[c];
@@ -284,6 +461,10 @@ void conv_mfma_kernel(ConvArgs p) {
             for (int i = 0; i < HPT; ++i) ph[i] = buf_load1(rx, hg[i]);
         };
         auto load_weights = [&](int c0) {
+            if constexpr (WINO) {
+                load_u(c0);
+                return;
+            }
             const __amdgpu_buffer_rsrc_t rw =
                 buf_rsrc(p.w + (size_t)c0 * TAPS * p.cout,
                          4u * (unsigned)(min(kKC, p.cin - c0) * TAPS) * (unsigned)p.cout);
@@ -325,10 +506,14 @@ void conv_mfma_kernel(ConvArgs p) {
                     lp[hl[i] & 0xffffu] = v;
                 }
             }
+            if constexpr (WINO) {
+                store_u();
+            } else {
 #pragma unroll
-            for (int i = 0; i < WPT; ++i) {
-                const int e = tid + i * kThreads;
-                if (e < NWI) reinterpret_cast<float4*>(lw)[e] = wv[i];  // lw[row*CT + col]
+                for (int i = 0; i < WPT; ++i) {
+                    const int e = tid + i * kThreads;
+                    if (e < NWI) reinterpret_cast<float4*>(lw)[e] = wv[i];  // lw[row*CT + col]
+                }
             }
         };
         load_patch(0);
@@ -377,107 +562,214 @@ void conv_mfma_kernel(ConvArgs p) {
                     }
                 }
             }
-            const int wvalid = (p.cin - c0) * TAPS;
+            if constexpr (WINO) {
+                load_u(c0);
+                store_u();
+            } else {
+                const int wvalid = (p.cin - c0) * TAPS;
 #pragma unroll 4
-            for (int row = wrow0; row < WROWS; row += RPP) {
-                float v = 0.f;
-                if (wcol_ok && row < wvalid)
-                    v = p.w[((unsigned)c0 * TAPS + row) * (unsigned)p.cout + (unsigned)(co0 + wcol)];
-                lw[row * CT + wcol] = v;
+                for (int row = wrow0; row < WROWS; row += RPP) {
+                    float v = 0.f;
+                    if (wcol_ok && row < wvalid)
+                        v = p.w[((unsigned)c0 * TAPS + row) * (unsigned)p.cout + (unsigned)(co0 + wcol)];
+                    lw[row * CT + wcol] = v;
+                }
             }
             __syncthreads();
             compute_chunk();
         }
     }
 
-    // epilogue: D[row = co][col = pixel]; row = (r&3) + 8*(r>>2) + 4*(lane>>5).
-    // Processed in groups of RG accumulator rows: the group's read-modify-write operands
-    // (accumulate) and BatchNorm-backward mask values are loaded unconditionally from clamped
-    // addresses first, so RG*NB loads are in flight together, then stored / reduced.
-    constexpr int RG = TAPS == 1 ? (NB <= 2 ? 4 : 1) : (NB <= 2 ? 16 : 4);
     float* yout = p.y + (size_t)n * p.cout * hw;
     const bool stats = p.stat_part != nullptr, masked = p.stat_mask_y != nullptr;
-    bool pix_ok[NB];
-    unsigned pixc[NB];  // pixel offset, 0 when outside the image
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int f = (wave_px * NB + nb) * 32 + j;
-        const int r = f / TW, ox = tx0 + f % TW;
-        const bool in_a = r < ra;
-        const int oy = in_a ? gyA0 + r : r - ra;
-        pix_ok[nb] = (in_a ? imgA_ok : imgB_ok) && oy < p.h && ox < p.wd;
-        pixc[nb] = pix_ok[nb] ? (unsigned)((in_a ? imgA : imgA + 1) * p.cout) * uhw +
-                                    (unsigned)oy * (unsigned)p.wd + (unsigned)ox
-                              : 0u;
-    }
     float* red = lds;  // [WPX][CT][2] statistics scratch
     static_assert(WPX * CT * 2 <= PATCH + WSZ, "stat scratch must fit the staging LDS");
     if (stats) __syncthreads();  // every wave is done with the staging LDS
     const float* my = masked ? p.stat_mask_y + (size_t)n * p.cout * hw : nullptr;
+    // Winograd epilogue: register i of wacc[m][nb][pos] is M[pos] of cout (l >> 4) * 4 + i of
+    // cout-block m and tile l & 15 of tile-block nb; the inverse transform gives its 2x2 pixels
+    // (both rows in one image: the strip seam row ra is even).  Pixel pairs are stored as float2
+    // where y allows it.  Statistics: per lane over its tiles' pixels, then over the 16 lanes of
+    // a row (DPP), then over the WPX waves in LDS.
+    if constexpr (WINO) {
+        const bool y2 = (p.wd & 1) == 0 && (reinterpret_cast<size_t>(p.y) & 7) == 0;
+        bool pok[NB][4];
+        unsigned pofs[NB][4];  // pixel offsets, 0 when outside the image
 #pragma unroll
-    for (int m = 0; m < MB; ++m) {
+        for (int nb = 0; nb < NB; ++nb) {
+            const int t = (wave_px * NB + nb) * 16 + wl;
+            const int r0 = 2 * (t / TXN), ox = tx0 + 2 * (t % TXN);
+            const bool in_a = r0 < ra;
+            const int oy = in_a ? gyA0 + r0 : r0 - ra;
+            const bool img_ok = t < NT && (in_a ? imgA_ok : imgB_ok);
+            const unsigned base = (unsigned)((in_a ? imgA : imgA + 1) * p.cout) * uhw;
 #pragma unroll
-        for (int rg = 0; rg < 16; rg += RG) {
-            float oldv[RG][NB], yv[RG][NB];
-            if (p.accumulate) {
-#pragma unroll
-                for (int rr = 0; rr < RG; ++rr) {
-                    const int r = rg + rr;
-                    const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
-                    const float* src = yout + (size_t)min(co, p.cout - 1) * hw;
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) oldv[rr][nb] = src[pixc[nb]];
-                }
+            for (int q = 0; q < 4; ++q) {
+                const int py = oy + (q >> 1), px = ox + (q & 1);
+                pok[nb][q] = img_ok && py < p.h && px < p.wd;
+                pofs[nb][q] = pok[nb][q] ? base + (unsigned)py * (unsigned)p.wd + (unsigned)px : 0u;
             }
-            if (masked) {
+        }
 #pragma unroll
-                for (int rr = 0; rr < RG; ++rr) {
-                    const int r = rg + rr;
-                    const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
-                    const float* src = my + (size_t)min(co, p.cout - 1) * hw;
+        for (int m = 0; m < MB; ++m) {
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) yv[rr][nb] = src[pixc[nb]];
-                }
-            }
-#pragma unroll
-            for (int rr = 0; rr < RG; ++rr) {
-                const int r = rg + rr;
-                const int cl = (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
+            for (int i = 0; i < 4; ++i) {
+                const int cl = (wave_co * MB + m) * 16 + 4 * wq + i;
                 const int co = co0 + cl;
                 const bool co_ok = co < p.cout;
-                float* dst = yout + (size_t)co * hw;
+                const size_t cofs = (size_t)min(co, p.cout - 1) * hw;
+                float out[NB][4], oldv[NB][4], yv[NB][4];
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
-                    if (p.accumulate) acc[m][nb][r] += oldv[rr][nb];  // the statistics see the sum
-                    if (co_ok && pix_ok[nb])
-                        dst[pixc[nb]] = acc[m][nb][r];
+                    float mm[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) mm[q] = wacc[m][nb][q][i];
+                    wino_output(mm, out[nb]);
+                    if (p.accumulate) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) oldv[nb][q] = yout[cofs + pofs[nb][q]];
+                    }
+                    if (masked) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) yv[nb][q] = my[cofs + pofs[nb][q]];
+                    }
+                }
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) {
+                    if (p.accumulate) {  // the statistics see the sum
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) out[nb][q] += oldv[nb][q];
+                    }
+                    if (co_ok) {
+#pragma unroll
+                        for (int r = 0; r < 2; ++r) {
+                            float* dst = yout + cofs + pofs[nb][2 * r];
+                            if (y2 && pok[nb][2 * r] && pok[nb][2 * r + 1]) {
+                                *reinterpret_cast<float2*>(dst) = make_float2(out[nb][2 * r], out[nb][2 * r + 1]);
+                            } else {
+                                if (pok[nb][2 * r]) dst[0] = out[nb][2 * r];
+                                if (pok[nb][2 * r + 1]) yout[cofs + pofs[nb][2 * r + 1]] = out[nb][2 * r + 1];
+                            }
+                        }
+                    }
                 }
                 if (!stats) continue;
                 float s1 = 0.f, s2 = 0.f;
                 if (!masked) {  // forward statistics about the pivot
                     const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) {
-                        const float d = pix_ok[nb] ? acc[m][nb][r] - pv : 0.f;
-                        s1 += d;
-                        s2 = fmaf(d, d, s2);
-                    }
+                    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const float d = pok[nb][q] ? out[nb][q] - pv : 0.f;
+                            s1 += d;
+                            s2 = fmaf(d, d, s2);
+                        }
                 } else {  // backward sums of the BatchNorm this gradient feeds
                     const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) {
-                        const bool on = co_ok && pix_ok[nb] &&
-                                        (!p.mask_relu || fmaf(yv[rr][nb], msc, msh) > 0.f);
-                        const float d = on ? acc[m][nb][r] : 0.f;
-                        s1 += d;
-                        s2 = fmaf(d, yv[rr][nb], s2);
-                    }
+                    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const bool on = co_ok && pok[nb][q] &&
+                                            (!p.mask_relu || fmaf(yv[nb][q], msc, msh) > 0.f);
+                            const float d = on ? out[nb][q] : 0.f;
+                            s1 += d;
+                            s2 = fmaf(d, yv[nb][q], s2);
+                        }
                 }
-                s1 = half_sum32(s1);
-                s2 = half_sum32(s2);
-                if (j == 31) {
+                s1 = row_sum16(s1);
+                s2 = row_sum16(s2);
+                if (wl == 0) {
                     red[(wave_px * CT + cl) * 2] = s1;
                     red[(wave_px * CT + cl) * 2 + 1] = s2;
+                }
+            }
+        }
+    } else {
+        // epilogue: D[row = co][col = pixel]; row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+        // Processed in groups of RG accumulator rows: the group's read-modify-write operands
+        // (accumulate) and BatchNorm-backward mask values are loaded unconditionally from clamped
+        // addresses first, so RG*NB loads are in flight together, then stored / reduced.
+        constexpr int RG = TAPS == 1 ? (NB <= 2 ? 4 : 1) : (NB <= 2 ? 16 : 4);
+        bool pix_ok[NB];
+        unsigned pixc[NB];  // pixel offset, 0 when outside the image
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            const int f = (wave_px * NB + nb) * 32 + j;
+            const int r = f / TW, ox = tx0 + f % TW;
+            const bool in_a = r < ra;
+            const int oy = in_a ? gyA0 + r : r - ra;
+            pix_ok[nb] = (in_a ? imgA_ok : imgB_ok) && oy < p.h && ox < p.wd;
+            pixc[nb] = pix_ok[nb] ? (unsigned)((in_a ? imgA : imgA + 1) * p.cout) * uhw +
+                                        (unsigned)oy * (unsigned)p.wd + (unsigned)ox
+                                  : 0u;
+        }
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+#pragma unroll
+            for (int rg = 0; rg < 16; rg += RG) {
+                float oldv[RG][NB], yv[RG][NB];
+                if (p.accumulate) {
+#pragma unroll
+                    for (int rr = 0; rr < RG; ++rr) {
+                        const int r = rg + rr;
+                        const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
+                        const float* src = yout + (size_t)min(co, p.cout - 1) * hw;
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb) oldv[rr][nb] = src[pixc[nb]];
+                    }
+                }
+                if (masked) {
+#pragma unroll
+                    for (int rr = 0; rr < RG; ++rr) {
+                        const int r = rg + rr;
+                        const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
+                        const float* src = my + (size_t)min(co, p.cout - 1) * hw;
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb) yv[rr][nb] = src[pixc[nb]];
+                    }
+                }
+#pragma unroll
+                for (int rr = 0; rr < RG; ++rr) {
+                    const int r = rg + rr;
+                    const int cl = (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
+                    const int co = co0 + cl;
+                    const bool co_ok = co < p.cout;
+                    float* dst = yout + (size_t)co * hw;
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) {
+                        if (p.accumulate) acc[m][nb][r] += oldv[rr][nb];  // the statistics see the sum
+                        if (co_ok && pix_ok[nb])
+                            dst[pixc[nb]] = acc[m][nb][r];
+                    }
+                    if (!stats) continue;
+                    float s1 = 0.f, s2 = 0.f;
+                    if (!masked) {  // forward statistics about the pivot
+                        const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb) {
+                            const float d = pix_ok[nb] ? acc[m][nb][r] - pv : 0.f;
+                            s1 += d;
+                            s2 = fmaf(d, d, s2);
+                        }
+                    } else {  // backward sums of the BatchNorm this gradient feeds
+                        const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb) {
+                            const bool on = co_ok && pix_ok[nb] &&
+                                            (!p.mask_relu || fmaf(yv[rr][nb], msc, msh) > 0.f);
+                            const float d = on ? acc[m][nb][r] : 0.f;
+                            s1 += d;
+                            s2 = fmaf(d, yv[rr][nb], s2);
+                        }
+                    }
+                    s1 = half_sum32(s1);
+                    s2 = half_sum32(s2);
+                    if (j == 31) {
+                        red[(wave_px * CT + cl) * 2] = s1;
+                        red[(wave_px * CT + cl) * 2 + 1] = s2;
+                    }
                 }
             }
         }
@@ -1436,26 +1728,48 @@ inline bool fwd_small_cin(int taps, int variant, int cin) { return taps == 9 && 
 // the shape half of ConvArgs::vec_ok (the other half: 16-byte aligned x and w)
 inline bool fwd_vec_shape(int wd, int cout) { return wd % 4 == 0 && cout % 4 == 0; }
 
-// K-chunk of 8 input channels everywhere (16 measured slower: more prefetch registers, fewer resident waves)
+// Output channels per workgroup (grid.y).  The Winograd kernels keep the variant's spatial tile
+// (the statistics partials are laid out per tile) but take 32 couts (16 for the 112-tile 56x8
+// variant): 16 positions x 4 accumulators per (cout, tile) leave room for 128 per wave.
+inline int fwd_ct(int taps, int variant, int cin) {
+    if (taps == 9 && !fwd_small_cin(taps, variant, cin)) return variant == 6 ? 16 : 32;
+    return kFwdVariants[variant].ct;
+}
+
+// K-chunk of 8 input channels everywhere (16 measured slower: more prefetch registers, fewer resident waves).
+// Every 3x3 launch but the stem's runs Winograd F(2x2,3x3); the direct kernel serves the stem and 1x1.
 template <int TAPS>
 int launch_fwd(int variant, const ConvArgs& a, dim3 grid, hipStream_t s) {
-    constexpr int KS = TAPS == 9 ? LF_KC_SMALL : 8;
     if (fwd_small_cin(TAPS, variant, a.cin)) {
         // the stem (Cin = 3): a 4-channel K-chunk instead of 8 halves the MFMAs spent on zeros
         conv_mfma_kernel<9, 32, 8, 1, 1, 4, 2, 4><<<grid, kThreads, 0, s>>>(a);
         return LF_OK;
     }
-    switch (variant) {
-        case 0: conv_mfma_kernel<TAPS, 32, 8, 1, 1, 4, 2, KS><<<grid, kThreads, 0, s>>>(a); break;
-        case 1: conv_mfma_kernel<TAPS, 32, 8, 1, 2, 4, 2, KS><<<grid, kThreads, 0, s>>>(a); break;
-        case 2: conv_mfma_kernel<TAPS, 16, 16, 1, 1, 4, 2, KS><<<grid, kThreads, 0, s>>>(a); break;
-        case 3: conv_mfma_kernel<TAPS, 16, 16, 1, 2, 4, 2, KS><<<grid, kThreads, 0, s>>>(a); break;
-        case 4: conv_mfma_kernel<TAPS, 28, 8, 4, 1, 1, 7, 8, true><<<grid, kThreads, 0, s>>>(a); break;
-        case 5: conv_mfma_kernel<TAPS, 32, 8, 2, 2, 2, 4, 8><<<grid, kThreads, 0, s>>>(a); break;
-        case 6: conv_mfma_kernel<TAPS, 56, 8, 2, 1, 2, 7, 8><<<grid, kThreads, 0, s>>>(a); break;
-        default: return LF_ERR_INVALID;
+    if constexpr (TAPS == 9) {
+        switch (variant) {
+            case 0:
+            case 1:
+            case 5: conv_mfma_kernel<9, 32, 8, 1, 2, 4, 1, 8, false, true><<<grid, kThreads, 0, s>>>(a); break;
+            case 2:
+            case 3: conv_mfma_kernel<9, 16, 16, 1, 2, 4, 1, 8, false, true><<<grid, kThreads, 0, s>>>(a); break;
+            case 4: conv_mfma_kernel<9, 28, 8, 1, 2, 4, 1, 8, true, true><<<grid, kThreads, 0, s>>>(a); break;
+            case 6: conv_mfma_kernel<9, 56, 8, 1, 1, 4, 2, 8, false, true><<<grid, kThreads, 0, s>>>(a); break;
+            default: return LF_ERR_INVALID;
+        }
+        return LF_OK;
+    } else {
+        switch (variant) {
+            case 0: conv_mfma_kernel<TAPS, 32, 8, 1, 1, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
+            case 1: conv_mfma_kernel<TAPS, 32, 8, 1, 2, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
+            case 2: conv_mfma_kernel<TAPS, 16, 16, 1, 1, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
+            case 3: conv_mfma_kernel<TAPS, 16, 16, 1, 2, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
+            case 4: conv_mfma_kernel<TAPS, 28, 8, 4, 1, 1, 7, 8, true><<<grid, kThreads, 0, s>>>(a); break;
+            case 5: conv_mfma_kernel<TAPS, 32, 8, 2, 2, 2, 4, 8><<<grid, kThreads, 0, s>>>(a); break;
+            case 6: conv_mfma_kernel<TAPS, 56, 8, 2, 1, 2, 7, 8><<<grid, kThreads, 0, s>>>(a); break;
+            default: return LF_ERR_INVALID;
+        }
+        return LF_OK;
     }
-    return LF_OK;
 }
 
 struct WgVariant {
@@ -1653,7 +1967,8 @@ static int conv2d_launch(const char* who, const float* x, const float* w, float*
     a.mask_relu = mask_relu;
     const int gz = (n + a.stack - 1) / a.stack;
     a.stat_tiles = (long long)gz * a.tiles_x * a.tiles_y;
-    dim3 grid(a.tiles_x * a.tiles_y, (cout + v.ct - 1) / v.ct, gz);
+    const int ct = fwd_ct(ksize * ksize, best, cin);
+    dim3 grid(a.tiles_x * a.tiles_y, (cout + ct - 1) / ct, gz);
     hipStream_t s = lf::as_stream(stream);
     const int rc = ksize == 3 ? launch_fwd<9>(best, a, grid, s) : launch_fwd<1>(best, a, grid, s);
     if (rc != LF_OK) return rc;
