@@ -25,7 +25,8 @@
 // wgrad kernel (wgrad_mfma_kernel): dW[ci][tap][co] = sum_pixels X[ci][p+tap] dY[co][p],
 //   K = pixels, split across workgroups and across the waves of a workgroup (reduced through
 //   LDS); every workgroup writes one partial slab and a two-stage reduce sums the slabs in a
-//   fixed order (deterministic, no float atomics).  wgrad_smallcin_kernel packs (ci, tap)
+//   fixed order (deterministic, no float atomics).  The 3x3 layers but the stem's use wgrad3_kernel,
+//   which accumulates in the Winograd F(2x2,3x3) domain instead.  wgrad_smallcin_kernel packs (ci, tap)
 //   into the MFMA's M dimension for the stem (Cin*9 <= 32): one MFMA per pixel pair.
 #include <type_traits>
 
@@ -1183,23 +1184,37 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
 }
 
 
-// 3x3 wgrad with the filter rows spread over waves: a workgroup of 3*WCI*WCO*KSPL waves owns a
-// (32*WCI ci) x (32*WCO co) weight block; wave (q, tr, k) accumulates the three taps of filter
-// row tr (48 accumulators) over its K-split share of each tile's rows.  With so few
-// accumulators the next item's tiles are prefetched into registers during the MFMAs.
-// floats of (dynamic) LDS: two staging buffers (X patch + dY tile each), or the K-split scratch
+// 3x3 wgrad in the Winograd domain, F(2x2,3x3) transposed:
+//   dW(3x3) = G^T [ sum_tiles (B^T d B) . (A dY A^T) ] G
+// over the 2x2 output tiles of an item (d = the tile's 4x4 input patch, halo included).  For each of
+// the 16 positions p, M_p[ci][co] = sum_tiles V_p[ci][tile] D_p[co][tile] is a GEMM with K = tiles,
+// 16 MFMAs per tile pair instead of 36 per 8 pixels.  A workgroup of 2*WCI*WCO*KSPL waves owns a
+// (32*WCI ci) x (32*WCO co) weight block; wave (q, g, k) accumulates the 8 positions of rows 2g and
+// 2g+1 of the position grid (128 accumulators, two waves per SIMD) over its K-split share of each
+// item's tiles, forming V and D per lane from the staged patch (4 patch rows x 4 columns, 2 dY
+// rows x 2 columns) with adds only.
+// The K-split partners fold in the Winograd domain; G^T M G is applied once per workgroup.  The
+// next item's X patch (and, where the registers allow, its dY tile) is prefetched into registers
+// during the MFMAs.
+// floats of (dynamic) LDS: two staging buffers (X patch + dY tile each), or the K-split scratch,
+// or the epilogue's exchange of position rows 1 and 2
 template <int TW, int TH, int WCI, int WCO, int KSPL>
 constexpr int wgrad3_lds_floats() {
     const int pp = ((TW + 2) * (TH + 2)) | 1, dp = (TW * TH) | 1;
     const int buf = 32 * WCI * pp + 32 * WCO * dp;
-    const int red = KSPL > 1 ? 3 * 3 * 1024 : 0;
-    return 2 * buf > red ? 2 * buf : red;
+    const int red = KSPL > 1 ? 16 * 1024 : 0;
+    const int xch = WCI * WCO * 2 * 3 * 1024;
+    const int m = 2 * buf > red ? 2 * buf : red;
+    return m > xch ? m : xch;
 }
 
 template <int TW, int TH, int WCI, int WCO, int KSPL>
-__global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(WgradArgs p) {
-    constexpr int NT = 64 * 3 * WCI * WCO * KSPL;
-    static_assert(TH % KSPL == 0 && TW % 4 == 0, "rows split across waves, float4 rows");
+__global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(WgradArgs p) {
+    constexpr int NT = 64 * 2 * WCI * WCO * KSPL;
+    constexpr int TWH = TW / 2, NTILE = TWH * (TH / 2), SH = NTILE / KSPL;  // 2x2 tiles: item, share
+    static_assert(TH % 2 == 0 && TW % 4 == 0 && NTILE % KSPL == 0 && SH % 2 == 0,
+                  "2x2 tiles split across waves in pairs, float4 rows");
+    static_assert(SH % TWH == 0 || TWH % SH == 0, "a K-split share is whole tile rows or part of one");
     constexpr int PW = TW + 2, PH = TH + 2;
     constexpr int PP = (PW * PH) | 1;  // odd plane pitch: 32 lanes on 32 channels hit 32 banks
     constexpr int DP = (TW * TH) | 1;
@@ -1215,25 +1230,35 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int tr = wid % 3, rest = wid / 3;
+    const int pg = wid & 1, rest = wid >> 1;  // rows 2pg, 2pg+1 of the 4x4 position grid
     const int w_ci = rest % WCI, w_co = (rest / WCI) % WCO, w_k = rest / NQ;
     const int ci0 = blockIdx.y * CI_T, co0 = blockIdx.z * CO_T;
     const int khalf = lane >> 5, j = lane & 31;
     const size_t hw = (size_t)p.h * p.wd;
     const unsigned uhw = (unsigned)hw;
 
-    f32x16 acc[3];
+    f32x16 acc[8];
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+    for (int t = 0; t < 8; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-    const int abase = (w_ci * 32 + j) * PP + tr * PW + khalf;
-    const int bbase = (w_co * 32 + j) * DP + khalf;
+    // Row i of B^T d = d[ra] + sa * d[rb] (B^T rows: d0-d2, d1+d2, d2-d1, d1-d3); rows 2pg and 2pg+1
+    // are positions 0-3 and 4-7 of the wave.  Rows of A dY (A rows: dY0, dY0+dY1, dY0-dY1, -dY1):
+    // pg = 0 takes dY0 and dY1 + dY0, pg = 1 takes dY0 - dY1 and +dY1; row 3's sign, and that of
+    // column 3 of A^T (taken as +u1), are undone in the epilogue.  Each lane walks tile 2kk + khalf
+    // of its share.
+    const int ra0 = 2 * pg, rb0 = 2 - pg, ra1 = 1, rb1 = 2 + pg;
+    const float sa0 = -1.f, sa1 = pg ? -1.f : 1.f;
+    const float ea = pg ? -1.f : 0.f, fb = pg ? 0.f : 1.f;
+    const int t0 = w_k * SH;  // first tile of the wave's share
+    const int abase = (w_ci * 32 + j) * PP + (t0 / TWH) * 2 * PW + (t0 % TWH) * 2 + 2 * khalf;
+    const int bbase = (w_co * 32 + j) * DP + (t0 / TWH) * 2 * TW + (t0 % TWH) * 2 + 2 * khalf;
+    const int xa0 = abase + ra0 * PW, xb0 = abase + rb0 * PW, xa1 = abase + ra1 * PW, xb1 = abase + rb1 * PW;
     const bool pro = p.in_scale != nullptr;
 
-    // quarter q (0..3) of an item's pixel pairs from staging buffer `buf`
-    constexpr int ROWS = TH / KSPL, NK = ROWS * (TW / 2);
+    // quarter q (0..3) of the wave's tile pairs from staging buffer `buf`
+    constexpr int NK = SH / 2;
     auto compute_quarter = [&](auto qc, int buf) {
         constexpr int Q = decltype(qc)::value;
         constexpr int K0 = NK * Q / 4, K1 = NK * (Q + 1) / 4;
@@ -1241,12 +1266,28 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
         const float* ld = lx + XSZ;
 #pragma unroll
         for (int kk = K0; kk < K1; ++kk) {
-            const int row = w_k * ROWS + kk / (TW / 2), xx = 2 * (kk % (TW / 2));
-            const float b = ld[bbase + row * TW + xx];
+            // tile pair 2kk, 2kk+1 of the share: same tile row (TWH is even)
+            const int tr = (2 * kk) / TWH, tc = (2 * kk) % TWH;
+            const int xoff = tr * 2 * PW + tc * 2, doff = tr * 2 * TW + tc * 2;
+            float t[2][4], u[2][2];
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const float a = lx[abase + row * PW + xx + dx];
-                acc[dx] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[dx], 0, 0, 0);
+            for (int c = 0; c < 4; ++c) {
+                t[0][c] = fmaf(sa0, lx[xb0 + xoff + c], lx[xa0 + xoff + c]);
+                t[1][c] = fmaf(sa1, lx[xb1 + xoff + c], lx[xa1 + xoff + c]);
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const float y0 = ld[bbase + doff + c], y1 = ld[bbase + TW + doff + c];
+                u[0][c] = fmaf(ea, y1, y0);
+                u[1][c] = fmaf(fb, y0, y1);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float v[4] = {t[h][0] - t[h][2], t[h][1] + t[h][2], t[h][2] - t[h][1], t[h][1] - t[h][3]};
+                const float d[4] = {u[h][0], u[h][0] + u[h][1], u[h][0] - u[h][1], u[h][1]};
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    acc[h * 4 + c] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[c], d[c], acc[h * 4 + c], 0, 0, 0);
             }
         }
     };
@@ -1318,7 +1359,8 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
         }
         const unsigned xbytes = 4u * ((unsigned)min(CI_T, p.cin - ci0) * uhw + (unsigned)p.wd + 1u);
         const unsigned dbytes = 4u * (unsigned)min(CO_T, p.cout - co0) * uhw;
-        auto load_item = [&](int item) {
+        // the X patch (with_x) and / or the dY tile (with_d) of an item
+        auto load_item = [&](int item, bool with_x, bool with_d) {
             const int n = item / tiles, t = item - n * tiles;
             const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
             const size_t torg = (size_t)ty0 * p.wd + tx0;
@@ -1328,6 +1370,7 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
             const __amdgpu_buffer_rsrc_t rx =
                 buf_rsrc(p.x + (nl * p.cin + ci0) * hw + torg - (size_t)p.wd - 1, xbytes);
             const __amdgpu_buffer_rsrc_t rd = buf_rsrc(p.dy + (nl * p.cout + co0) * hw + torg, dbytes);
+            if (with_x) {
             xok = 0;
 #pragma unroll
             for (int i = 0; i < XPT; ++i) {
@@ -1344,6 +1387,8 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
                 xh[i] = buf_load1(rx, ok ? hg[i] : kBufOob);
                 xok |= (ok ? 1u : 0u) << (16 + i);
             }
+            }
+            if (!with_d) return;
             dok = 0;
 #pragma unroll
             for (int i = 0; i < DPT; ++i) {
@@ -1374,9 +1419,10 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
                 }
             }
         };
-        auto store_item = [&](int item, int buf) {
+        auto store_item = [&](int item, int buf, bool with_x, bool with_d) {
             float* lx = lds + buf * BUF;
             float* ld = lx + XSZ;
+            if (with_x) {
 #pragma unroll
             for (int i = 0; i < XPT; ++i) {
                 if (tid + i * NT < NXI) {
@@ -1408,6 +1454,8 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
                     lx[hl[i] & 0xffffu] = v;
                 }
             }
+            }
+            if (!with_d) return;
             const int sn = item / tiles, st = item - sn * tiles;
             const int stx0 = (st % p.tiles_x) * TW, sty0 = (st / p.tiles_x) * TH;
             float* dyo = bn ? p.dy_out + ((size_t)sn * p.cout + co0) * hw + (size_t)sty0 * p.wd + stx0 : nullptr;
@@ -1438,33 +1486,38 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
         };
         // double-buffered staging, one barrier per item: while an item's MFMAs run from one
         // buffer the next item (loaded an iteration earlier) is written into the other, and
-        // the loads of the item after that are issued
+        // the loads of the item after that are issued.  With four float4 of dY per thread
+        // (CO_T = 64 over a 128-pixel tile) the dY prefetch (dv, yv, alpha / add: 40 registers)
+        // does not fit beside the 128 accumulators: those variants load the next item's dY
+        // at its stage point, behind the X stores, and the other wave on the SIMD covers the wait.
+        constexpr bool kLateD = DPT > 2;
         int cur = 0;
         const int count = last - first;
         auto nth = [&](int idx) { return first + idx; };
         if (count > 0) {
-            load_item(nth(0));
+            load_item(nth(0), true, true);
             __syncthreads();  // lsc / lbn are staged
-            store_item(nth(0), 0);
-            if (count > 1) load_item(nth(1));
+            store_item(nth(0), 0, true, true);
+            if (count > 1) load_item(nth(1), true, !kLateD);
         }
         __syncthreads();
-        // The waves sharing a SIMD (wid, wid+4, wid+8) move through their MFMAs in lock step,
-        // so each stages after a different quarter: while one writes LDS the other two keep
-        // the MFMA pipe busy.
-        const int stage_q = (wid >> 2) % 3;
+        // The two waves sharing a SIMD (wid, wid+4) move through their MFMAs in lock step, so
+        // they stage half an item apart (after quarters 0 and 2): while one writes LDS the
+        // other keeps the MFMA pipe busy.
+        const int stage_q = (wid >> 2) & 1;
         for (int idx = 0; idx < count; ++idx) {
             const bool more = idx + 1 < count;
             auto stage = [&]() {
-                store_item(nth(idx + 1), cur ^ 1);
-                if (idx + 2 < count) load_item(nth(idx + 2));
+                if (kLateD) load_item(nth(idx + 1), false, true);
+                store_item(nth(idx + 1), cur ^ 1, true, !kLateD);
+                if (idx + 2 < count) load_item(nth(idx + 2), true, !kLateD);
+                if (kLateD) store_item(nth(idx + 1), cur ^ 1, false, true);
             };
             compute_quarter(Q0{}, cur);
             if (more && stage_q == 0) stage();
             compute_quarter(Q1{}, cur);
-            if (more && stage_q == 1) stage();
             compute_quarter(Q2{}, cur);
-            if (more && stage_q == 2) stage();
+            if (more && stage_q == 1) stage();
             compute_quarter(Q3{}, cur);
             __syncthreads();
             cur ^= 1;
@@ -1507,7 +1560,8 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
         }
     }
 
-    // K-split partner waves fold into k = 0 through LDS, one (ci,co) block per round (fixed order)
+    // K-split partner waves fold into k = 0 through LDS in the Winograd domain, one (ci,co) block per
+    // round (fixed order)
     const int q = w_co * WCI + w_ci;
 #pragma unroll 1
     for (int k = 1; k < KSPL; ++k) {
@@ -1516,29 +1570,58 @@ __global__ __launch_bounds__(64 * 3 * WCI * WCO * KSPL, 3) void wgrad3_kernel(Wg
             __syncthreads();
             if (w_k == k && q == qq) {
 #pragma unroll
-                for (int t = 0; t < 3; ++t)
+                for (int c = 0; c < 8; ++c)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) lds[(tr * 3 + t) * 1024 + r * 64 + lane] = acc[t][r];
+                    for (int r = 0; r < 16; ++r) lds[(pg * 8 + c) * 1024 + r * 64 + lane] = acc[c][r];
             }
             __syncthreads();
             if (w_k == 0 && q == qq) {
 #pragma unroll
-                for (int t = 0; t < 3; ++t)
+                for (int c = 0; c < 8; ++c)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[t][r] += lds[(tr * 3 + t) * 1024 + r * 64 + lane];
+                    for (int r = 0; r < 16; ++r) acc[c][r] += lds[(pg * 8 + c) * 1024 + r * 64 + lane];
             }
         }
     }
+
+    // G^T M G.  Each wave applies G on the right to its two position rows (column 3 enters with the
+    // sign taken in D): P[0] = M0 + (M1+M2)/2, P[1] = (M1-M2)/2, P[2] = (M1+M2)/2 - M3.  P1 and P2 are
+    // exchanged through LDS; wave g = 0 forms filter rows 0 and 1, g = 1 filter row 2:
+    //   dW0 = P0 + (P1+P2)/2,  dW1 = (P1-P2)/2,  dW2 = (P1+P2)/2 - P3  (P3 entered with its sign taken)
+    auto prow = [&](int h, int s, int r) {  // P[s] of the wave's position row h (0 or 1)
+        const float m0 = acc[h * 4][r], m1 = acc[h * 4 + 1][r], m2 = acc[h * 4 + 2][r], m3 = acc[h * 4 + 3][r];
+        const float hs = (m1 + m2) * 0.5f;
+        return s == 0 ? m0 + hs : (s == 1 ? (m1 - m2) * 0.5f : hs - m3);
+    };
+    float* xch = lds + (size_t)q * (2 * 3 * 1024);
+    __syncthreads();  // the staging buffers / K-split scratch are no longer read
+    if (w_k == 0) {  // g = 0 publishes P1 (its second row), g = 1 publishes P2 (its first)
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                xch[(pg * 3 + s) * 1024 + r * 64 + lane] = pg ? prow(0, s, r) : prow(1, s, r);
+    }
+    __syncthreads();
     if (w_k == 0) {
         float* out = p.part + (size_t)blockIdx.x * p.cin * 9 * p.cout;
         const int co = co0 + w_co * 32 + j;
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
+        for (int s = 0; s < 3; ++s)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                const float p1 = xch[s * 1024 + r * 64 + lane], p2 = xch[(3 + s) * 1024 + r * 64 + lane];
+                const float hs = (p1 + p2) * 0.5f;
                 const int ci = ci0 + w_ci * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                if (ci < p.cin && co < p.cout)
-                    out[((size_t)ci * 9 + tr * 3 + t) * p.cout + co] = acc[t][r];
+                if (ci < p.cin && co < p.cout) {
+                    float* o = out + ((size_t)ci * 9 + s) * p.cout + co;
+                    if (pg == 0) {
+                        o[0] = prow(0, s, r) + hs;
+                        o[3 * p.cout] = (p1 - p2) * 0.5f;
+                    } else {
+                        o[6 * p.cout] = hs - prow(1, s, r);
+                    }
+                }
             }
     }
 }
@@ -1792,7 +1875,7 @@ int launch_wgrad3(const WgradArgs& a, dim3 grid, hipStream_t s) {
         }
         raised = true;
     }
-    wgrad3_kernel<TW, TH, WCI, WCO, KSPL><<<grid, 64 * 3 * WCI * WCO * KSPL, bytes, s>>>(a);
+    wgrad3_kernel<TW, TH, WCI, WCO, KSPL><<<grid, 64 * 2 * WCI * WCO * KSPL, bytes, s>>>(a);
     return LF_OK;
 }
 
@@ -1852,7 +1935,7 @@ WgPlan plan_wgrad(int n, int cin, int cout, int h, int w, int ksize) {
     }
     best.items = n * best.tiles_x * best.tiles_y;
     // every split gets the same number of items
-    // resident workgroups per CU: the 12-wave 3x3 kernels 1 (x2 rounds), the others ~3
+    // resident workgroups per CU: the 3x3 kernels 1 (x2 rounds), the others ~3
     int splits = (256 * (ksize == 3 && best.variant != kWgSmallCin ? 2 : 3)) / (best.gy * best.gz);
     if (splits < 1) splits = 1;
     if (splits > best.items) splits = best.items;
