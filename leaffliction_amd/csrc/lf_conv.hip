@@ -5,7 +5,7 @@
 // K-major order, Cout contiguous).  Stride 1, "same" zero padding, no bias
 // (keras Conv2D(filters, 3|1, padding="same", use_bias=False), srcs/model/cnn.py:27-29,44).
 //
-// Forward / dgrad kernel (conv_mfma_kernel):  D[co][pixel] = sum_k W[co][k] X[k][pixel],
+// Forward / dgrad, direct kernel (conv_mfma_kernel: the stem, 1x1):  D[co][pixel] = sum_k W[co][k] X[k][pixel],
 //   k = (ci, tap).  A operand = weights (lane -> co), B operand = pixels (lane -> pixel),
 //   so one accumulator register holds 32 consecutive pixels of one output channel and the
 //   NCHW store is 128-byte contiguous per half-wave.
@@ -18,9 +18,8 @@
 //   CU so one workgroup's LDS write phase overlaps another's MFMAs.
 //   An optional prologue applies y = relu(x*scale[c]+shift[c]) to the input while staging
 //   (BatchNorm+ReLU of the producer fused into the consumer; zero padding stays zero).
-//   Every 3x3 launch but the stem's computes Winograd F(2x2,3x3) on the same staged patch
-//   (v_mfma_f32_16x16x4_f32, 16 products per 2x2 outputs instead of 36; see the kernel); the
-//   direct GEMM above serves the stem and the 1x1 convolutions.
+// Forward / dgrad, Winograd kernel (conv_wino_kernel: every other 3x3): F(2x2,3x3) on the same
+//   staged patch (v_mfma_f32_16x16x4_f32, 16 products per 2x2 outputs instead of 36; see the kernel).
 //
 // wgrad kernel (wgrad_mfma_kernel): dW[ci][tap][co] = sum_pixels X[ci][p+tap] dY[co][p],
 //   K = pixels, split across workgroups and across the waves of a workgroup (reduced through
@@ -164,271 +163,93 @@ __device__ __forceinline__ void wino_output(const float (&m)[16], float (&y)[4])
 }
 
 // ---------------------------------------------------------------------------
-// forward / dgrad
+// forward / dgrad: the pieces both kernels share, the direct kernel, the Winograd kernel
 // ---------------------------------------------------------------------------
-// TAPS: 9 (3x3) or 1 (1x1).
-// Direct (WINO = false): tile TW x TH pixels = NPB blocks of 32 (flat index); waves WCO x WPX = 4,
-//   each wave computes MB cout-blocks x NB pixel-blocks of 32 with v_mfma_f32_32x32x2_f32.
-// Winograd F(2x2,3x3) (WINO = true, TAPS = 9): the tile is NT = (TW/2)*(TH/2) Winograd tiles
-//   (flat index, 2x2 output pixels each) and the workgroup's CT = 16*WCO*MB output channels.
-//   Per 4-channel K-step, each of the 16 transform positions is a GEMM U[pos] (cout x cin) .
-//   V[pos] (cin x tiles) on v_mfma_f32_16x16x4_f32; a wave owns MB cout-blocks x NB tile-blocks
-//   of 16, all 16 positions, so M[pos] for one (cout, tile) sits in one lane and register and the
-//   inverse transform is register-local.  U = G g G^T is formed while the weights are staged
-//   (one (channel, cout) pair per thread) and kept in LDS; V = B^T d B is formed per lane from
-//   the LDS patch.  The patch staging (prologue, zeros, two-image strip) is the direct kernel's.
-// min waves/SIMD asked of the register allocator: accumulators + VGPRs share one 512-entry
-// file per SIMD lane; with the prefetch registers <=32 accumulators fit 3 waves, more fit 2.
-template <int TAPS, int TW, int TH, int WCO, int MB, int WPX, int NB, int kKC, bool STK = false,
-          bool WINO = false>
-__global__ __launch_bounds__(kThreads, (!WINO && MB * NB * 16 <= 32 ? 3 : 2))
-void conv_mfma_kernel(ConvArgs p) {
-    constexpr int NPB = TW * TH / 32;
-    constexpr int TXN = TW / 2, NT = TXN * (TH / 2);  // Winograd tiles per row / per workgroup
-    static_assert(TW % 4 == 0, "float4 patch rows");
-    static_assert(WINO || TW * TH % 32 == 0, "tile must be whole 32-pixel blocks");
-    static_assert(!WINO || (TAPS == 9 && TH % 2 == 0 && kKC % 4 == 0), "F(2x2,3x3): even tile, 4-channel K-steps");
-    static_assert(WCO * WPX == 4 && (WINO ? WPX * NB * 16 >= NT : WPX * NB == NPB), "wave decomposition");
-    constexpr int CT = (WINO ? 16 : 32) * WCO * MB;
-    constexpr int kUP = 20;  // LDS pitch of one (channel, cout) U: 16 positions + 4 (conflict-free b128 reads)
-    constexpr int HALO = TAPS == 9 ? 1 : 0;
-    constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO + (STK ? 2 * HALO : 0), PP = PW * PH;
-    constexpr int PATCH = kKC * PP;
-    constexpr int WSZ = WINO ? kKC * CT * kUP : kKC * TAPS * CT;
-    static_assert(PATCH % 4 == 0, "16-byte aligned weight region");
-    // vector staging: per patch row TW/4 float4 interior items + 2 halo scalars, kept in two
-    // homogeneous item arrays (mixing both kinds in one array makes the compiler wait for
-    // every load right where it is issued)
-    constexpr int TW4 = TW / 4;
-    constexpr int NVI = kKC * PH * TW4, IPT = (NVI + kThreads - 1) / kThreads;
-    constexpr int NHI = kKC * PH * 2 * HALO, HPT = (NHI + kThreads - 1) / kThreads;
-    constexpr int CT4 = CT / 4, NWI = kKC * TAPS * CT4, WPT = (NWI + kThreads - 1) / kThreads;
-    constexpr int kMaxProC = 512;  // prologue scale/shift staged in LDS for up to this many channels
+constexpr int kMaxProC = 512;  // prologue scale/shift staged in LDS for up to this many channels
 
-    __shared__ __attribute__((aligned(16))) float lds[PATCH + WSZ];
-    __shared__ float lsc[2 * kMaxProC];
-    float* lp = lds;
-    float* lw = lds + PATCH;
+// XCD-aware order: workgroups are dealt to the eight XCDs round-robin in dispatch order (x, then y,
+// then z), each XCD with its own L2.  XCD k takes the k-th contiguous share of the (tile, channel
+// group, strip) space, so the tiles that share halo rows meet in one L2.  Strip rows ty0 .. ty0+TH-1:
+// the first `ra` belong to image n + imgA (rows gyA0 ..), the rest (only when the tile straddles a
+// seam, or hangs over the bottom) to the next image.
+template <int TW, int TH, int HALO, bool STK>
+struct ConvTile {
+    int bz, by, tile;  // strip, cout group, tile of the strip
+    int tx0, ty0, n;   // n: first image of the strip
+    int imgA, gyA0, ra;
+    bool imgA_ok, imgB_ok;
 
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wave_co = wid % WCO, wave_px = wid / WCO;
-    // XCD-aware order: workgroups are dealt to the eight XCDs round-robin in dispatch order (x, then
-    // y, then z), each XCD with its own L2.  XCD k takes the k-th contiguous share of the
-    // (tile, channel group, strip) space, so the tiles that share halo rows meet in one L2.
-    const unsigned gxy = gridDim.x * gridDim.y, gtotal = gxy * gridDim.z;
-    const unsigned bflat = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned xk = bflat & 7u, xfloor = gtotal >> 3, xrem = gtotal & 7u;
-    const unsigned wid_flat = xk * xfloor + (xk < xrem ? xk : xrem) + (bflat >> 3);
-    const int bz = (int)(wid_flat / gxy);
-    const int by = (int)((wid_flat - (unsigned)bz * gxy) / gridDim.x);
-    const int tile = (int)(wid_flat - (unsigned)bz * gxy - (unsigned)by * gridDim.x);
-    const int tx0 = (tile % p.tiles_x) * TW, ty0 = (tile / p.tiles_x) * TH;
-    const int co0 = by * CT;
-    const int n = bz * p.stack;  // first image of this workgroup's strip
-    const size_t hw = (size_t)p.h * p.wd;
-    const unsigned uhw = (unsigned)hw;
-    const float* xin = p.x + (size_t)n * p.cin * hw;
-    // strip rows ty0 .. ty0+TH-1: the first `ra` belong to image n + imgA (rows gyA0 ..), the
-    // rest (only when the tile straddles a seam, or hangs over the bottom) to the next image
-    const int imgA = ty0 / p.h, gyA0 = ty0 - imgA * p.h;
-    const int ra = min(TH, p.h - gyA0);
-    const bool imgA_ok = imgA < p.stack && n + imgA < p.n;
-    const bool imgB_ok = STK && imgA + 1 < p.stack && n + imgA + 1 < p.n;
+    __device__ __forceinline__ explicit ConvTile(const ConvArgs& p) {
+        const unsigned gxy = gridDim.x * gridDim.y, gtotal = gxy * gridDim.z;
+        const unsigned bflat = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+        const unsigned xk = bflat & 7u, xfloor = gtotal >> 3, xrem = gtotal & 7u;
+        const unsigned wid_flat = xk * xfloor + (xk < xrem ? xk : xrem) + (bflat >> 3);
+        bz = (int)(wid_flat / gxy);
+        by = (int)((wid_flat - (unsigned)bz * gxy) / gridDim.x);
+        tile = (int)(wid_flat - (unsigned)bz * gxy - (unsigned)by * gridDim.x);
+        tx0 = (tile % p.tiles_x) * TW;
+        ty0 = (tile / p.tiles_x) * TH;
+        n = bz * p.stack;
+        imgA = ty0 / p.h;
+        gyA0 = ty0 - imgA * p.h;
+        ra = min(TH, p.h - gyA0);
+        imgA_ok = imgA < p.stack && n + imgA < p.n;
+        imgB_ok = STK && imgA + 1 < p.stack && n + imgA + 1 < p.n;
+    }
+
     // patch row -> (image, row): [0, ra+2H) image A from gyA0-H; then image B from -H
-    auto patch_row = [&](int py, int& img, int& gy) {
+    __device__ __forceinline__ bool patch_row(int py, int h, int& img, int& gy) const {
         if (py < ra + 2 * HALO) {
             img = imgA;
             gy = gyA0 - HALO + py;
-            return imgA_ok && gy >= 0 && gy < p.h;
+            return imgA_ok && gy >= 0 && gy < h;
         }
         img = imgA + 1;
         gy = py - (ra + 2 * HALO) - HALO;
-        return imgB_ok && ra < TH && gy >= 0 && gy < p.h && gy < TH - ra + HALO;
-    };
-
-    // per-lane LDS read bases
-    const int khalf = lane >> 5, j = lane & 31;
-    int bbase[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int f = (wave_px * NB + nb) * 32 + j;
-        const int r = f / TW, prow = (STK && r >= ra) ? r + 2 * HALO : r;
-        bbase[nb] = khalf * PP + prow * PW + (f % TW);
+        return imgB_ok && ra < TH && gy >= 0 && gy < h && gy < TH - ra + HALO;
     }
-    const int abase = khalf * TAPS * CT + wave_co * MB * 32 + j;
+};
 
-    f32x16 acc[WINO ? 1 : MB][WINO ? 1 : NB];
-    if constexpr (!WINO) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][nb][r] = 0.f;
-    }
+// The input patch (+halo) of one K-chunk of kKC channels in LDS ([kKC][PH][PW]), prologue applied.
+// Vector staging: per patch row TW/4 float4 interior items + 2*HALO halo scalars, kept in two
+// homogeneous item arrays (mixing both kinds in one array makes the compiler wait for every load
+// right where it is issued).  Per-thread invariants (the workgroup has one tile; a chunk only moves
+// the channel base): byte offsets from the chunk's first channel plane with kBufOob for everything
+// that must read as zero (rows and columns outside the image, slots beyond the item count);
+// LDS index | kc << 16.  Channels beyond Cin fall outside the chunk's buffer size -> zeros.
+template <int TW, int TH, int HALO, bool STK, int kKC>
+struct PatchStage {
+    static constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO + (STK ? 2 * HALO : 0), PP = PW * PH;
+    static constexpr int TW4 = TW / 4;
+    static constexpr int NVI = kKC * PH * TW4, IPT = (NVI + kThreads - 1) / kThreads;
+    static constexpr int NHI = kKC * PH * 2 * HALO, HPT = (NHI + kThreads - 1) / kThreads;
+    static_assert(TW % 4 == 0, "float4 patch rows");
 
-    // Winograd: lane l reads the 4x4 patch window of tile (l & 15) of each of its tile-blocks for
-    // channel (l >> 4) of the K-step (tiles past NT read the last tile's window; they are never
-    // stored), and U[cout = l & 15][channel = l >> 4] of each of its cout-blocks
-    const int wq = lane >> 4, wl = lane & 15;
-    int vbase[WINO ? NB : 1];
-    const int ubase = (wq * CT + wave_co * MB * 16 + wl) * kUP;
-    f32x4 wacc[WINO ? MB : 1][WINO ? NB : 1][16];
-    if constexpr (WINO) {
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int t = min((wave_px * NB + nb) * 16 + wl, NT - 1);
-            const int r0 = 2 * (t / TXN), prow = (STK && r0 >= ra) ? r0 + 2 : r0;
-            vbase[nb] = wq * PP + prow * PW + 2 * (t % TXN);
-        }
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) wacc[m][nb][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    size_t hw;  // H*W
+    float4 pv[IPT];
+    float ph[HPT > 0 ? HPT : 1];
+    unsigned pg[IPT], pl[IPT];
+    unsigned hg[HPT > 0 ? HPT : 1], hl[HPT > 0 ? HPT : 1];
+    unsigned okmask = 0;  // bit i: interior item i in-image; bit 16+i: halo item i in-image
 
-    const bool pro = p.in_scale != nullptr;
-
-    auto compute_chunk_wino = [&]() {
-        if constexpr (WINO) {
-#pragma unroll
-            for (int s = 0; s < kKC / 4; ++s) {
-                // the cout-blocks' U first, then one tile-block's V at a time
-                float u[MB][16];
-#pragma unroll
-                for (int m = 0; m < MB; ++m) {
-                    const float4* us = reinterpret_cast<const float4*>(lw + ubase + (4 * s * CT + m * 16) * kUP);
-#pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        const float4 t = us[q4];
-                        u[m][4 * q4 + 0] = t.x;
-                        u[m][4 * q4 + 1] = t.y;
-                        u[m][4 * q4 + 2] = t.z;
-                        u[m][4 * q4 + 3] = t.w;
-                    }
-                }
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    const float* src = lp + vbase[nb] + 4 * s * PP;
-                    float d[16], v[16];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float2 lo = *reinterpret_cast<const float2*>(src + r * PW);
-                        const float2 hi = *reinterpret_cast<const float2*>(src + r * PW + 2);
-                        d[r * 4 + 0] = lo.x;
-                        d[r * 4 + 1] = lo.y;
-                        d[r * 4 + 2] = hi.x;
-                        d[r * 4 + 3] = hi.y;
-                    }
-                    wino_input(d, v);
-#pragma unroll
-                    for (int m = 0; m < MB; ++m)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q)
-                            wacc[m][nb][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[m][q], v[q], wacc[m][nb][q], 0, 0, 0);
-                }
-            }
-        }
-    };
-
-    // Winograd weights: thread (kc, co) of the chunk fetches the 9 taps of one filter into
-    // registers (during the previous chunk's MFMAs) and stores U = G g G^T to LDS
-    constexpr int NUW = WINO ? kKC * CT : 1;
-    static_assert(NUW <= kThreads, "one (channel, cout) filter per thread");
-    const int ukc = tid / CT, uco = tid - ukc * CT;
-    const bool u_on = WINO && tid < NUW;
-    const unsigned ugo = (u_on && co0 + uco < p.cout) ? 4u * ((unsigned)ukc * 9u * (unsigned)p.cout + (unsigned)(co0 + uco)) : kBufOob;
-    float wr[WINO ? 9 : 1];
-    auto load_u = [&](int c0) {
-        if constexpr (WINO) {
-            // filters of channels beyond Cin fall outside the chunk's buffer size -> zeros
-            const __amdgpu_buffer_rsrc_t rw =
-                buf_rsrc(p.w + (size_t)c0 * 9 * p.cout, 4u * (unsigned)(min(kKC, p.cin - c0) * 9) * (unsigned)p.cout);
-#pragma unroll
-            for (int t = 0; t < 9; ++t)
-                wr[t] = buf_load1(rw, ugo == kBufOob ? kBufOob : ugo + 4u * (unsigned)t * (unsigned)p.cout);
-        }
-    };
-    auto store_u = [&]() {
-        if constexpr (WINO) if (u_on) {
-            float u[16];
-            wino_filter(wr, u);
-            float4* dst = reinterpret_cast<float4*>(lw + (ukc * CT + uco) * kUP);
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) dst[q4] = make_float4(u[4 * q4], u[4 * q4 + 1], u[4 * q4 + 2], u[4 * q4 + 3]);
-        }
-    };
-
-    // cp loop only partially unrolled: the scheduler otherwise hoists dozens of LDS reads and
-    // the accumulators + prefetch registers no longer fit
-    auto compute_chunk_direct = [&]() {
-        if constexpr (!WINO) {
-#pragma unroll 2
-            for (int cp = 0; cp < kKC / 2; ++cp) {
-                const float* lwc = lw + abase + 2 * cp * TAPS * CT;
-                const float* lpc = lp + 2 * cp * PP;
-#pragma unroll
-                for (int tap = 0; tap < TAPS; ++tap) {
-                    const int dy = TAPS == 9 ? tap / 3 : 0, dx = TAPS == 9 ? tap % 3 : 0;
-                    float a[MB], b[NB];
-#pragma unroll
-                    for (int m = 0; m < MB; ++m) a[m] = lwc[tap * CT + m * 32];
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) b[nb] = lpc[bbase[nb] + dy * PW + dx];
-#pragma unroll
-                    for (int m = 0; m < MB; ++m)
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb)
-                            acc[m][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b[nb], acc[m][nb], 0,
-                                                                              0, 0);
-                }
-            }
-        }
-    };
-    auto compute_chunk = [&]() {
-        if constexpr (WINO)
-            compute_chunk_wino();
-        else
-            compute_chunk_direct();
-    };
-
-    const int nchunks = (p.cin + kKC - 1) / kKC;
-    const bool vec = p.vec_ok && (tx0 + TW <= p.wd);  // uniform per workgroup
-
-    if (vec) {
-        // ---------------- vector staging with register prefetch ----------------
-        float4 pv[IPT];
-        float ph[HPT > 0 ? HPT : 1];
-        float4 wv[WPT];
-        unsigned okmask = 0;  // bit i: interior item i in-image; bit 16+i: halo item i in-image
-        // variants with > 64 accumulators have no registers left to hold the weight prefetch:
-        // they prefetch the patch only and fetch the (L2-resident) weights in the store phase
-        // (Winograd: 9 registers of filter taps per thread, prefetched unless the wave has two tile-blocks)
-        constexpr bool kPrefetchW = WINO ? NB == 1 : MB * NB * 16 <= 64;
-        if (pro) {  // BatchNorm scale/shift of the producer: staged once per workgroup
+    // also stages the producer's BatchNorm scale/shift in lsc, once per workgroup
+    __device__ __forceinline__ PatchStage(const ConvArgs& p, const ConvTile<TW, TH, HALO, STK>& t, float* lsc, int tid) {
+        if (p.in_scale != nullptr) {
             for (int c = tid; c < p.cin && c < kMaxProC; c += kThreads) {
                 lsc[c] = p.in_scale[c];
                 lsc[kMaxProC + c] = p.in_shift[c];
             }
         }
-        // Per-thread staging invariants (the workgroup has one tile; a chunk only moves the
-        // channel base): byte offsets from the chunk's first channel plane / weight row with
-        // kBufOob for everything that must read as zero (rows and columns outside the image,
-        // slots beyond the item count, cout columns beyond the tensor); LDS index | kc << 16.
-        // Channels / weight rows beyond Cin fall outside the chunk's buffer size -> zeros.
-        unsigned pg[IPT], pl[IPT];
-        unsigned hg[HPT > 0 ? HPT : 1], hl[HPT > 0 ? HPT : 1];
-        unsigned wg[WPT];
+        hw = (size_t)p.h * p.wd;
+        const unsigned uhw = (unsigned)hw;
 #pragma unroll
         for (int i = 0; i < IPT; ++i) {
             const int e = tid + i * kThreads;
             const int kc = e / (PH * TW4), rem = e - kc * (PH * TW4);
             const int py = rem / TW4, slot = rem - py * TW4;
             int img, gy;
-            const bool ok = patch_row(py, img, gy) && e < NVI;
-            pg[i] = ok ? 4u * ((unsigned)(img * p.cin + kc) * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)(tx0 + 4 * slot)) : kBufOob;
+            const bool ok = t.patch_row(py, p.h, img, gy) && e < NVI;
+            pg[i] = ok ? 4u * ((unsigned)(img * p.cin + kc) * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)(t.tx0 + 4 * slot)) : kBufOob;
             pl[i] = (unsigned)(kc * PP + py * PW + HALO + 4 * slot) | ((unsigned)kc << 16);
             okmask |= (ok ? 1u : 0u) << i;
         }
@@ -437,366 +258,628 @@ void conv_mfma_kernel(ConvArgs p) {
             const int e = tid + i * kThreads;
             const int kc = e / (PH * 2), rem = e - kc * (PH * 2);
             const int py = rem >> 1, side = rem & 1;
-            const int gx = side ? tx0 + TW : tx0 - 1;
+            const int gx = side ? t.tx0 + TW : t.tx0 - 1;
             int img, gy;
-            const bool ok = patch_row(py, img, gy) && e < NHI && gx >= 0 && gx < p.wd;
+            const bool ok = t.patch_row(py, p.h, img, gy) && e < NHI && gx >= 0 && gx < p.wd;
             hg[i] = ok ? 4u * ((unsigned)(img * p.cin + kc) * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)gx) : kBufOob;
             hl[i] = (unsigned)(kc * PP + py * PW + (side ? PW - 1 : 0)) | ((unsigned)kc << 16);
             okmask |= (ok ? 1u : 0u) << (16 + i);
         }
+    }
+
+    // chunk c0's loads into registers (with a strip of two images the second image's chunk lies Cin
+    // planes further on; the host only stacks when Cin is a whole number of chunks)
+    __device__ __forceinline__ void load(const ConvArgs& p, const float* xin, int c0) {
+        const __amdgpu_buffer_rsrc_t rx = buf_rsrc(
+            xin + (size_t)c0 * hw,
+            4u * (unsigned)((STK ? (p.stack - 1) * p.cin : 0) + min(kKC, p.cin - c0)) * (unsigned)hw);
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) pv[i] = buf_load4(rx, pg[i]);
+#pragma unroll
+        for (int i = 0; i < HPT; ++i) ph[i] = buf_load1(rx, hg[i]);
+    }
+
+    // the registers loaded for chunk c0 -> LDS
+    __device__ __forceinline__ void store(const ConvArgs& p, float* lp, const float* lsc, int c0, int tid) const {
+        const bool pro = p.in_scale != nullptr;
+        auto pro_sc = [&](int c) { return c < kMaxProC ? lsc[c] : p.in_scale[c]; };
+        auto pro_sh = [&](int c) { return c < kMaxProC ? lsc[kMaxProC + c] : p.in_shift[c]; };
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) {
+            if (tid + i * kThreads < NVI) {
+                const int kc = (int)(pl[i] >> 16);
+                float4 v = pv[i];
+                if (pro && (okmask >> i & 1u)) {
+                    const float sc = pro_sc(c0 + kc), sh = pro_sh(c0 + kc);
+                    v.x = pro_apply(v.x, sc, sh, p.in_relu);
+                    v.y = pro_apply(v.y, sc, sh, p.in_relu);
+                    v.z = pro_apply(v.z, sc, sh, p.in_relu);
+                    v.w = pro_apply(v.w, sc, sh, p.in_relu);
+                }
+                float* dst = lp + (pl[i] & 0xffffu);
+                dst[0] = v.x;
+                dst[1] = v.y;
+                dst[2] = v.z;
+                dst[3] = v.w;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < HPT; ++i) {
+            if (tid + i * kThreads < NHI) {
+                const int kc = (int)(hl[i] >> 16);
+                float v = ph[i];
+                if (pro && (okmask >> (16 + i) & 1u))
+                    v = pro_apply(v, pro_sc(c0 + kc), pro_sh(c0 + kc), p.in_relu);
+                lp[hl[i] & 0xffffu] = v;
+            }
+        }
+    }
+
+    // Scalar staging (ragged shapes / partial tiles), loads straight to LDS: a thread owns one patch
+    // position (two when the patch has more than 256) and walks the chunk's channels: every load is
+    // base + c*H*W
+    static __device__ __forceinline__ void stage_scalar(const ConvArgs& p, float* lp, const float* xin,
+                                                        int tx0, int ty0, int c0, int tid) {
+        constexpr int SLOTS = PP <= 64 ? 64 : (PP <= 128 ? 128 : 256);
+        constexpr int G = kThreads / SLOTS;
+        constexpr int ROUNDS = (PP + SLOTS - 1) / SLOTS;
+        const int slot = tid % SLOTS, grp = tid / SLOTS;
+        const size_t hw = (size_t)p.h * p.wd;
+        const unsigned uhw = (unsigned)hw;
+        const bool pro = p.in_scale != nullptr;
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int pos = slot + r * SLOTS;
+            if (pos < PP) {
+                const int py = pos / PW, px = pos - py * PW;
+                const int gy = ty0 + py - HALO, gx = tx0 + px - HALO;
+                const bool inb = gy >= 0 && gy < p.h && gx >= 0 && gx < p.wd;
+                const unsigned goff = inb ? (unsigned)gy * (unsigned)p.wd + (unsigned)gx : 0u;
+#pragma unroll 4
+                for (int kc = grp; kc < kKC; kc += G) {
+                    const int c = c0 + kc;
+                    float v = 0.f;
+                    if (inb && c < p.cin) {
+                        v = xin[(unsigned)c * uhw + goff];
+                        if (pro) v = pro_apply(v, p.in_scale[c], p.in_shift[c], p.in_relu);
+                    }
+                    lp[kc * PP + pos] = v;
+                }
+            }
+        }
+    }
+};
+
+// BatchNorm statistics: red[WPX][CT][2] (per pixel-wave partials) -> stat_part, in a fixed order
+template <int WPX, int CT>
+__device__ __forceinline__ void write_stat_part(const ConvArgs& p, const float* red, int bz, int tile, int co0,
+                                                int tid) {
+    __syncthreads();
+    const long long tg = (long long)bz * (p.tiles_x * p.tiles_y) + tile;
+    for (int c = tid; c < CT; c += kThreads) {
+        if (co0 + c >= p.cout) continue;
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int wp = 0; wp < WPX; ++wp) {
+            a += red[(wp * CT + c) * 2];
+            b += red[(wp * CT + c) * 2 + 1];
+        }
+        float* dst = p.stat_part + ((size_t)(co0 + c) * (size_t)p.stat_tiles + (size_t)tg) * 2;
+        dst[0] = a;
+        dst[1] = b;
+    }
+}
+
+// Direct GEMM (the stem and the 1x1 convolutions).  TAPS: 9 (3x3) or 1 (1x1).  Tile TW x TH pixels = NPB blocks of 32 (flat index); waves WCO x WPX = 4,
+// each wave computes MB cout-blocks x NB pixel-blocks of 32 with v_mfma_f32_32x32x2_f32.
+// min waves/SIMD asked of the register allocator: accumulators + VGPRs share one 512-entry
+// file per SIMD lane; with the prefetch registers <=32 accumulators fit 3 waves, more fit 2.
+template <int TAPS, int TW, int TH, int WCO, int MB, int WPX, int NB, int kKC, bool STK = false>
+__global__ __launch_bounds__(kThreads, (MB * NB * 16 <= 32 ? 3 : 2))
+void conv_mfma_kernel(ConvArgs p) {
+    constexpr int NPB = TW * TH / 32;
+    static_assert(TW * TH % 32 == 0, "tile must be whole 32-pixel blocks");
+    static_assert(WCO * WPX == 4 && WPX * NB == NPB, "wave decomposition");
+    constexpr int CT = 32 * WCO * MB;
+    constexpr int HALO = TAPS == 9 ? 1 : 0;
+    using Patch = PatchStage<TW, TH, HALO, STK, kKC>;
+    constexpr int PW = Patch::PW, PP = Patch::PP;
+    constexpr int PATCH = kKC * PP;
+    constexpr int WSZ = kKC * TAPS * CT;
+    static_assert(PATCH % 4 == 0, "16-byte aligned weight region");
+    constexpr int CT4 = CT / 4, NWI = kKC * TAPS * CT4, WPT = (NWI + kThreads - 1) / kThreads;
+
+    __shared__ __attribute__((aligned(16))) float lds[PATCH + WSZ];
+    __shared__ float lsc[2 * kMaxProC];
+    float* lp = lds;
+    float* lw = lds + PATCH;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wave_co = wid % WCO, wave_px = wid / WCO;
+    const ConvTile<TW, TH, HALO, STK> t(p);
+    const int co0 = t.by * CT;
+    const size_t hw = (size_t)p.h * p.wd;
+    const unsigned uhw = (unsigned)hw;
+    const float* xin = p.x + (size_t)t.n * p.cin * hw;
+
+    // per-lane LDS read bases
+    const int khalf = lane >> 5, j = lane & 31;
+    int bbase[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        const int f = (wave_px * NB + nb) * 32 + j;
+        const int r = f / TW, prow = (STK && r >= t.ra) ? r + 2 * HALO : r;
+        bbase[nb] = khalf * PP + prow * PW + (f % TW);
+    }
+    const int abase = khalf * TAPS * CT + wave_co * MB * 32 + j;
+
+    f32x16 acc[MB][NB];
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[m][nb][r] = 0.f;
+
+    // cp loop only partially unrolled: the scheduler otherwise hoists dozens of LDS reads and
+    // the accumulators + prefetch registers no longer fit
+    auto compute_chunk = [&]() {
+#pragma unroll 2
+        for (int cp = 0; cp < kKC / 2; ++cp) {
+            const float* lwc = lw + abase + 2 * cp * TAPS * CT;
+            const float* lpc = lp + 2 * cp * PP;
+#pragma unroll
+            for (int tap = 0; tap < TAPS; ++tap) {
+                const int dy = TAPS == 9 ? tap / 3 : 0, dx = TAPS == 9 ? tap % 3 : 0;
+                float a[MB], b[NB];
+#pragma unroll
+                for (int m = 0; m < MB; ++m) a[m] = lwc[tap * CT + m * 32];
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) b[nb] = lpc[bbase[nb] + dy * PW + dx];
+#pragma unroll
+                for (int m = 0; m < MB; ++m)
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb)
+                        acc[m][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b[nb], acc[m][nb], 0, 0, 0);
+            }
+        }
+    };
+
+    const int nchunks = (p.cin + kKC - 1) / kKC;
+    const bool vec = p.vec_ok && (t.tx0 + TW <= p.wd);  // uniform per workgroup
+
+    if (vec) {
+        // ---------------- vector staging with register prefetch ----------------
+        float4 wv[WPT];
+        // with > 64 accumulators there are no registers left to hold the weight prefetch: those
+        // variants prefetch the patch only and fetch the (L2-resident) weights in the store phase
+        constexpr bool kPrefetchW = MB * NB * 16 <= 64;
+        Patch patch(p, t, lsc, tid);
+        // weight rows: byte offsets from the chunk's first row, kBufOob for cout columns beyond the
+        // tensor; rows beyond Cin fall outside the chunk's buffer size -> zeros
+        unsigned wg[WPT];
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
             const int e = tid + i * kThreads;
             const int row = e / CT4, col = (e - row * CT4) * 4;
             wg[i] = (e < NWI && co0 + col < p.cout) ? 4u * ((unsigned)row * (unsigned)p.cout + (unsigned)(co0 + col)) : kBufOob;
         }
-        auto load_patch = [&](int c0) {
-            // (with a strip of two images the second image's chunk lies Cin planes further on;
-            // the host only stacks when Cin is a whole number of chunks)
-            const __amdgpu_buffer_rsrc_t rx = buf_rsrc(
-                xin + (size_t)c0 * hw,
-                4u * (unsigned)((STK ? (p.stack - 1) * p.cin : 0) + min(kKC, p.cin - c0)) * uhw);
-#pragma unroll
-            for (int i = 0; i < IPT; ++i) pv[i] = buf_load4(rx, pg[i]);
-#pragma unroll
-            for (int i = 0; i < HPT; ++i) ph[i] = buf_load1(rx, hg[i]);
-        };
         auto load_weights = [&](int c0) {
-            if constexpr (WINO) {
-                load_u(c0);
-                return;
-            }
             const __amdgpu_buffer_rsrc_t rw =
                 buf_rsrc(p.w + (size_t)c0 * TAPS * p.cout,
                          4u * (unsigned)(min(kKC, p.cin - c0) * TAPS) * (unsigned)p.cout);
 #pragma unroll
             for (int i = 0; i < WPT; ++i) wv[i] = buf_load4(rw, wg[i]);
         };
-        auto pro_sc = [&](int c) { return c < kMaxProC ? lsc[c] : p.in_scale[c]; };
-        auto pro_sh = [&](int c) { return c < kMaxProC ? lsc[kMaxProC + c] : p.in_shift[c]; };
         auto store_chunk = [&](int c0) {
             if (!kPrefetchW) load_weights(c0);
+            patch.store(p, lp, lsc, c0, tid);
 #pragma unroll
-            for (int i = 0; i < IPT; ++i) {
-                if (tid + i * kThreads < NVI) {
-                    const int kc = (int)(pl[i] >> 16);
-                    float4 v = pv[i];
-                    if (pro && (okmask >> i & 1u)) {
-                        const float sc = pro_sc(c0 + kc), sh = pro_sh(c0 + kc);
-                        v.x = pro_apply(v.x, sc, sh, p.in_relu);
-                        v.y = pro_apply(v.y, sc, sh, p.in_relu);
-                        v.z = pro_apply(v.z, sc, sh, p.in_relu);
-                        v.w = pro_apply(v.w, sc, sh, p.in_relu);
-                    }
-                    float* dst = lp + (pl[i] & 0xffffu);
-                    {
-                        dst[0] = v.x;
-                        dst[1] = v.y;
-                        dst[2] = v.z;
-                        dst[3] = v.w;
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < HPT; ++i) {
-                if (tid + i * kThreads < NHI) {
-                    const int kc = (int)(hl[i] >> 16);
-                    float v = ph[i];
-                    if (pro && (okmask >> (16 + i) & 1u))
-                        v = pro_apply(v, pro_sc(c0 + kc), pro_sh(c0 + kc), p.in_relu);
-                    lp[hl[i] & 0xffffu] = v;
-                }
-            }
-            if constexpr (WINO) {
-                store_u();
-            } else {
-#pragma unroll
-                for (int i = 0; i < WPT; ++i) {
-                    const int e = tid + i * kThreads;
-                    if (e < NWI) reinterpret_cast<float4*>(lw)[e] = wv[i];  // lw[row*CT + col]
-                }
+            for (int i = 0; i < WPT; ++i) {
+                const int e = tid + i * kThreads;
+                if (e < NWI) reinterpret_cast<float4*>(lw)[e] = wv[i];  // lw[row*CT + col]
             }
         };
-        load_patch(0);
+        patch.load(p, xin, 0);
         if (kPrefetchW) load_weights(0);
         for (int ch = 0; ch < nchunks; ++ch) {
             __syncthreads();  // previous chunk's LDS reads are done
             store_chunk(ch * kKC);
             __syncthreads();
             if (ch + 1 < nchunks) {  // in flight during the MFMAs
-                load_patch((ch + 1) * kKC);
+                patch.load(p, xin, (ch + 1) * kKC);
                 if (kPrefetchW) load_weights((ch + 1) * kKC);
             }
             compute_chunk();
         }
     } else {
         // ---------------- scalar staging (ragged shapes / partial tiles) ----------------
-        // a thread owns one patch position (two when the patch has more than 256) and walks
-        // the chunk's channels: every load is base + c*H*W
-        constexpr int SLOTS = PP <= 64 ? 64 : (PP <= 128 ? 128 : 256);
-        constexpr int G = kThreads / SLOTS;
-        constexpr int ROUNDS = (PP + SLOTS - 1) / SLOTS;
-        const int slot = tid % SLOTS, grp = tid / SLOTS;
         constexpr int WROWS = kKC * TAPS, RPP = kThreads / CT;
         const int wcol = tid % CT, wrow0 = tid / CT;
         const bool wcol_ok = co0 + wcol < p.cout;
         for (int ch = 0; ch < nchunks; ++ch) {
             const int c0 = ch * kKC;
             __syncthreads();
-#pragma unroll
-            for (int r = 0; r < ROUNDS; ++r) {
-                const int pos = slot + r * SLOTS;
-                if (pos < PP) {
-                    const int py = pos / PW, px = pos - py * PW;
-                    const int gy = ty0 + py - HALO, gx = tx0 + px - HALO;
-                    const bool inb = gy >= 0 && gy < p.h && gx >= 0 && gx < p.wd;
-                    const unsigned goff = inb ? (unsigned)gy * (unsigned)p.wd + (unsigned)gx : 0u;
+            Patch::stage_scalar(p, lp, xin, t.tx0, t.ty0, c0, tid);
+            const int wvalid = (p.cin - c0) * TAPS;
 #pragma unroll 4
-                    for (int kc = grp; kc < kKC; kc += G) {
-                        const int c = c0 + kc;
-                        float v = 0.f;
-                        if (inb && c < p.cin) {
-                            v = xin[(unsigned)c * uhw + goff];
-                            if (pro) v = pro_apply(v, p.in_scale[c], p.in_shift[c], p.in_relu);
-                        }
-                        lp[kc * PP + pos] = v;
-                    }
-                }
-            }
-            if constexpr (WINO) {
-                load_u(c0);
-                store_u();
-            } else {
-                const int wvalid = (p.cin - c0) * TAPS;
-#pragma unroll 4
-                for (int row = wrow0; row < WROWS; row += RPP) {
-                    float v = 0.f;
-                    if (wcol_ok && row < wvalid)
-                        v = p.w[((unsigned)c0 * TAPS + row) * (unsigned)p.cout + (unsigned)(co0 + wcol)];
-                    lw[row * CT + wcol] = v;
-                }
+            for (int row = wrow0; row < WROWS; row += RPP) {
+                float v = 0.f;
+                if (wcol_ok && row < wvalid)
+                    v = p.w[((unsigned)c0 * TAPS + row) * (unsigned)p.cout + (unsigned)(co0 + wcol)];
+                lw[row * CT + wcol] = v;
             }
             __syncthreads();
             compute_chunk();
         }
     }
 
-    float* yout = p.y + (size_t)n * p.cout * hw;
+    float* yout = p.y + (size_t)t.n * p.cout * hw;
     const bool stats = p.stat_part != nullptr, masked = p.stat_mask_y != nullptr;
     float* red = lds;  // [WPX][CT][2] statistics scratch
     static_assert(WPX * CT * 2 <= PATCH + WSZ, "stat scratch must fit the staging LDS");
     if (stats) __syncthreads();  // every wave is done with the staging LDS
-    const float* my = masked ? p.stat_mask_y + (size_t)n * p.cout * hw : nullptr;
-    // Winograd epilogue: register i of wacc[m][nb][pos] is M[pos] of cout (l >> 4) * 4 + i of
-    // cout-block m and tile l & 15 of tile-block nb; the inverse transform gives its 2x2 pixels
-    // (both rows in one image: the strip seam row ra is even).  Pixel pairs are stored as float2
-    // where y allows it.  Statistics: per lane over its tiles' pixels, then over the 16 lanes of
-    // a row (DPP), then over the WPX waves in LDS.
-    if constexpr (WINO) {
-        const bool y2 = (p.wd & 1) == 0 && (reinterpret_cast<size_t>(p.y) & 7) == 0;
-        bool pok[NB][4];
-        unsigned pofs[NB][4];  // pixel offsets, 0 when outside the image
+    const float* my = masked ? p.stat_mask_y + (size_t)t.n * p.cout * hw : nullptr;
+    // epilogue: D[row = co][col = pixel]; row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+    // Processed in groups of RG accumulator rows: the group's read-modify-write operands
+    // (accumulate) and BatchNorm-backward mask values are loaded unconditionally from clamped
+    // addresses first, so RG*NB loads are in flight together, then stored / reduced.
+    constexpr int RG = TAPS == 1 ? (NB <= 2 ? 4 : 1) : (NB <= 2 ? 16 : 4);
+    bool pix_ok[NB];
+    unsigned pixc[NB];  // pixel offset, 0 when outside the image
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int t = (wave_px * NB + nb) * 16 + wl;
-            const int r0 = 2 * (t / TXN), ox = tx0 + 2 * (t % TXN);
-            const bool in_a = r0 < ra;
-            const int oy = in_a ? gyA0 + r0 : r0 - ra;
-            const bool img_ok = t < NT && (in_a ? imgA_ok : imgB_ok);
-            const unsigned base = (unsigned)((in_a ? imgA : imgA + 1) * p.cout) * uhw;
+    for (int nb = 0; nb < NB; ++nb) {
+        const int f = (wave_px * NB + nb) * 32 + j;
+        const int r = f / TW, ox = t.tx0 + f % TW;
+        const bool in_a = r < t.ra;
+        const int oy = in_a ? t.gyA0 + r : r - t.ra;
+        pix_ok[nb] = (in_a ? t.imgA_ok : t.imgB_ok) && oy < p.h && ox < p.wd;
+        pixc[nb] = pix_ok[nb] ? (unsigned)((in_a ? t.imgA : t.imgA + 1) * p.cout) * uhw +
+                                    (unsigned)oy * (unsigned)p.wd + (unsigned)ox
+                              : 0u;
+    }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int py = oy + (q >> 1), px = ox + (q & 1);
-                pok[nb][q] = img_ok && py < p.h && px < p.wd;
-                pofs[nb][q] = pok[nb][q] ? base + (unsigned)py * (unsigned)p.wd + (unsigned)px : 0u;
+    for (int m = 0; m < MB; ++m) {
+#pragma unroll
+        for (int rg = 0; rg < 16; rg += RG) {
+            float oldv[RG][NB], yv[RG][NB];
+            if (p.accumulate) {
+#pragma unroll
+                for (int rr = 0; rr < RG; ++rr) {
+                    const int r = rg + rr;
+                    const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
+                    const float* src = yout + (size_t)min(co, p.cout - 1) * hw;
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) oldv[rr][nb] = src[pixc[nb]];
+                }
             }
-        }
+            if (masked) {
 #pragma unroll
-        for (int m = 0; m < MB; ++m) {
+                for (int rr = 0; rr < RG; ++rr) {
+                    const int r = rg + rr;
+                    const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
+                    const float* src = my + (size_t)min(co, p.cout - 1) * hw;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int cl = (wave_co * MB + m) * 16 + 4 * wq + i;
+                    for (int nb = 0; nb < NB; ++nb) yv[rr][nb] = src[pixc[nb]];
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < RG; ++rr) {
+                const int r = rg + rr;
+                const int cl = (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
                 const int co = co0 + cl;
                 const bool co_ok = co < p.cout;
-                const size_t cofs = (size_t)min(co, p.cout - 1) * hw;
-                float out[NB][4], oldv[NB][4], yv[NB][4];
+                float* dst = yout + (size_t)co * hw;
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
-                    float mm[16];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) mm[q] = wacc[m][nb][q][i];
-                    wino_output(mm, out[nb]);
-                    if (p.accumulate) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) oldv[nb][q] = yout[cofs + pofs[nb][q]];
-                    }
-                    if (masked) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) yv[nb][q] = my[cofs + pofs[nb][q]];
-                    }
-                }
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    if (p.accumulate) {  // the statistics see the sum
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) out[nb][q] += oldv[nb][q];
-                    }
-                    if (co_ok) {
-#pragma unroll
-                        for (int r = 0; r < 2; ++r) {
-                            float* dst = yout + cofs + pofs[nb][2 * r];
-                            if (y2 && pok[nb][2 * r] && pok[nb][2 * r + 1]) {
-                                *reinterpret_cast<float2*>(dst) = make_float2(out[nb][2 * r], out[nb][2 * r + 1]);
-                            } else {
-                                if (pok[nb][2 * r]) dst[0] = out[nb][2 * r];
-                                if (pok[nb][2 * r + 1]) yout[cofs + pofs[nb][2 * r + 1]] = out[nb][2 * r + 1];
-                            }
-                        }
-                    }
+                    if (p.accumulate) acc[m][nb][r] += oldv[rr][nb];  // the statistics see the sum
+                    if (co_ok && pix_ok[nb])
+                        dst[pixc[nb]] = acc[m][nb][r];
                 }
                 if (!stats) continue;
                 float s1 = 0.f, s2 = 0.f;
                 if (!masked) {  // forward statistics about the pivot
                     const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const float d = pok[nb][q] ? out[nb][q] - pv : 0.f;
-                            s1 += d;
-                            s2 = fmaf(d, d, s2);
-                        }
+                    for (int nb = 0; nb < NB; ++nb) {
+                        const float d = pix_ok[nb] ? acc[m][nb][r] - pv : 0.f;
+                        s1 += d;
+                        s2 = fmaf(d, d, s2);
+                    }
                 } else {  // backward sums of the BatchNorm this gradient feeds
                     const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const bool on = co_ok && pok[nb][q] &&
-                                            (!p.mask_relu || fmaf(yv[nb][q], msc, msh) > 0.f);
-                            const float d = on ? out[nb][q] : 0.f;
-                            s1 += d;
-                            s2 = fmaf(d, yv[nb][q], s2);
-                        }
+                    for (int nb = 0; nb < NB; ++nb) {
+                        const bool on = co_ok && pix_ok[nb] &&
+                                        (!p.mask_relu || fmaf(yv[rr][nb], msc, msh) > 0.f);
+                        const float d = on ? acc[m][nb][r] : 0.f;
+                        s1 += d;
+                        s2 = fmaf(d, yv[rr][nb], s2);
+                    }
                 }
-                s1 = row_sum16(s1);
-                s2 = row_sum16(s2);
-                if (wl == 0) {
+                s1 = half_sum32(s1);
+                s2 = half_sum32(s2);
+                if (j == 31) {
                     red[(wave_px * CT + cl) * 2] = s1;
                     red[(wave_px * CT + cl) * 2 + 1] = s2;
                 }
             }
         }
-    } else {
-        // epilogue: D[row = co][col = pixel]; row = (r&3) + 8*(r>>2) + 4*(lane>>5).
-        // Processed in groups of RG accumulator rows: the group's read-modify-write operands
-        // (accumulate) and BatchNorm-backward mask values are loaded unconditionally from clamped
-        // addresses first, so RG*NB loads are in flight together, then stored / reduced.
-        constexpr int RG = TAPS == 1 ? (NB <= 2 ? 4 : 1) : (NB <= 2 ? 16 : 4);
-        bool pix_ok[NB];
-        unsigned pixc[NB];  // pixel offset, 0 when outside the image
+    }
+    if (stats) write_stat_part<WPX, CT>(p, red, t.bz, t.tile, co0, tid);
+}
+
+// Winograd F(2x2,3x3) (every 3x3 convolution but the stem).  The tile TW x TH is NT = (TW/2)*(TH/2) Winograd tiles (flat index, 2x2 output pixels each) and the
+// workgroup's CT = 16*MB output channels; 4 waves, K-chunks of 8 input channels.  Per 4-channel K-step,
+// each of the 16 transform positions is a GEMM U[pos] (cout x cin) . V[pos] (cin x tiles) on
+// v_mfma_f32_16x16x4_f32; a wave owns MB cout-blocks x NB tile-blocks of 16, all 16 positions, so M[pos]
+// for one (cout, tile) sits in one lane and register and the inverse transform is register-local.
+// U = G g G^T is formed while the weights are staged (one (channel, cout) pair per thread) and kept in
+// LDS; V = B^T d B is formed per lane from the LDS patch.  The patch staging (prologue, zeros, two-image
+// strip) is the direct kernel's.  64 accumulators per (cout-block, tile-block): 2 waves per SIMD.
+template <int TW, int TH, int MB, int NB, bool STK>
+__global__ __launch_bounds__(kThreads, 2)
+void conv_wino_kernel(ConvArgs p) {
+    constexpr int kKC = 8, WPX = 4;  // K-chunk; every wave takes all of the workgroup's couts
+    constexpr int TXN = TW / 2, NT = TXN * (TH / 2);  // Winograd tiles per row / per workgroup
+    static_assert(TH % 2 == 0, "F(2x2,3x3): even tile");
+    static_assert(WPX * NB * 16 >= NT, "wave decomposition");
+    constexpr int CT = 16 * MB;
+    constexpr int kUP = 20;  // LDS pitch of one (channel, cout) U: 16 positions + 4 (conflict-free b128 reads)
+    using Patch = PatchStage<TW, TH, 1, STK, kKC>;
+    constexpr int PW = Patch::PW, PP = Patch::PP;
+    constexpr int PATCH = kKC * PP;
+    constexpr int WSZ = kKC * CT * kUP;
+    static_assert(PATCH % 4 == 0, "16-byte aligned U region");
+
+    __shared__ __attribute__((aligned(16))) float lds[PATCH + WSZ];
+    __shared__ float lsc[2 * kMaxProC];
+    float* lp = lds;
+    float* lw = lds + PATCH;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave_px = tid >> 6;
+    const ConvTile<TW, TH, 1, STK> t(p);
+    const int co0 = t.by * CT;
+    const size_t hw = (size_t)p.h * p.wd;
+    const unsigned uhw = (unsigned)hw;
+    const float* xin = p.x + (size_t)t.n * p.cin * hw;
+
+    // lane l reads the 4x4 patch window of tile (l & 15) of each of its tile-blocks for channel
+    // (l >> 4) of the K-step (tiles past NT read the last tile's window; they are never stored), and
+    // U[cout = l & 15][channel = l >> 4] of each of its cout-blocks
+    const int wq = lane >> 4, wl = lane & 15;
+    int vbase[NB];
+    const int ubase = (wq * CT + wl) * kUP;
+    f32x4 wacc[MB][NB][16];
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int f = (wave_px * NB + nb) * 32 + j;
-            const int r = f / TW, ox = tx0 + f % TW;
-            const bool in_a = r < ra;
-            const int oy = in_a ? gyA0 + r : r - ra;
-            pix_ok[nb] = (in_a ? imgA_ok : imgB_ok) && oy < p.h && ox < p.wd;
-            pixc[nb] = pix_ok[nb] ? (unsigned)((in_a ? imgA : imgA + 1) * p.cout) * uhw +
-                                        (unsigned)oy * (unsigned)p.wd + (unsigned)ox
-                                  : 0u;
+    for (int nb = 0; nb < NB; ++nb) {
+        const int tt = min((wave_px * NB + nb) * 16 + wl, NT - 1);
+        const int r0 = 2 * (tt / TXN), prow = (STK && r0 >= t.ra) ? r0 + 2 : r0;
+        vbase[nb] = wq * PP + prow * PW + 2 * (tt % TXN);
+    }
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) wacc[m][nb][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    auto compute_chunk = [&]() {
+#pragma unroll
+        for (int s = 0; s < kKC / 4; ++s) {
+            // the cout-blocks' U first, then one tile-block's V at a time
+            float u[MB][16];
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+                const float4* us = reinterpret_cast<const float4*>(lw + ubase + (4 * s * CT + m * 16) * kUP);
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const float4 v4 = us[q4];
+                    u[m][4 * q4 + 0] = v4.x;
+                    u[m][4 * q4 + 1] = v4.y;
+                    u[m][4 * q4 + 2] = v4.z;
+                    u[m][4 * q4 + 3] = v4.w;
+                }
+            }
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const float* src = lp + vbase[nb] + 4 * s * PP;
+                float d[16], v[16];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float2 lo = *reinterpret_cast<const float2*>(src + r * PW);
+                    const float2 hi = *reinterpret_cast<const float2*>(src + r * PW + 2);
+                    d[r * 4 + 0] = lo.x;
+                    d[r * 4 + 1] = lo.y;
+                    d[r * 4 + 2] = hi.x;
+                    d[r * 4 + 3] = hi.y;
+                }
+                wino_input(d, v);
+#pragma unroll
+                for (int m = 0; m < MB; ++m)
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        wacc[m][nb][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[m][q], v[q], wacc[m][nb][q], 0, 0, 0);
+            }
         }
+    };
+
+    // weights: thread (kc, co) of the chunk fetches the 9 taps of one filter into registers and
+    // stores U = G g G^T to LDS
+    static_assert(kKC * CT <= kThreads, "one (channel, cout) filter per thread");
+    const int ukc = tid / CT, uco = tid - ukc * CT;
+    const bool u_on = tid < kKC * CT;
+    const unsigned ugo = (u_on && co0 + uco < p.cout) ? 4u * ((unsigned)ukc * 9u * (unsigned)p.cout + (unsigned)(co0 + uco)) : kBufOob;
+    float wr[9];
+    auto load_u = [&](int c0) {
+        // filters of channels beyond Cin fall outside the chunk's buffer size -> zeros
+        const __amdgpu_buffer_rsrc_t rw =
+            buf_rsrc(p.w + (size_t)c0 * 9 * p.cout, 4u * (unsigned)(min(kKC, p.cin - c0) * 9) * (unsigned)p.cout);
 #pragma unroll
-        for (int m = 0; m < MB; ++m) {
+        for (int tap = 0; tap < 9; ++tap)
+            wr[tap] = buf_load1(rw, ugo == kBufOob ? kBufOob : ugo + 4u * (unsigned)tap * (unsigned)p.cout);
+    };
+    auto store_u = [&]() {
+        if (u_on) {
+            float u[16];
+            wino_filter(wr, u);
+            float4* dst = reinterpret_cast<float4*>(lw + (ukc * CT + uco) * kUP);
 #pragma unroll
-            for (int rg = 0; rg < 16; rg += RG) {
-                float oldv[RG][NB], yv[RG][NB];
+            for (int q4 = 0; q4 < 4; ++q4) dst[q4] = make_float4(u[4 * q4], u[4 * q4 + 1], u[4 * q4 + 2], u[4 * q4 + 3]);
+        }
+    };
+
+    const int nchunks = (p.cin + kKC - 1) / kKC;
+    const bool vec = p.vec_ok && (t.tx0 + TW <= p.wd);  // uniform per workgroup
+
+    if (vec) {
+        // ---------------- vector staging with register prefetch ----------------
+        // the filter taps (9 registers) are prefetched during the previous chunk's MFMAs unless the
+        // wave has two tile-blocks; then they are fetched (L2-resident) in the store phase
+        constexpr bool kPrefetchW = NB == 1;
+        Patch patch(p, t, lsc, tid);
+        auto store_chunk = [&](int c0) {
+            if (!kPrefetchW) load_u(c0);
+            patch.store(p, lp, lsc, c0, tid);
+            store_u();
+        };
+        patch.load(p, xin, 0);
+        if (kPrefetchW) load_u(0);
+        for (int ch = 0; ch < nchunks; ++ch) {
+            __syncthreads();  // previous chunk's LDS reads are done
+            store_chunk(ch * kKC);
+            __syncthreads();
+            if (ch + 1 < nchunks) {  // in flight during the MFMAs
+                patch.load(p, xin, (ch + 1) * kKC);
+                if (kPrefetchW) load_u((ch + 1) * kKC);
+            }
+            compute_chunk();
+        }
+    } else {
+        // ---------------- scalar staging (ragged shapes / partial tiles) ----------------
+        for (int ch = 0; ch < nchunks; ++ch) {
+            const int c0 = ch * kKC;
+            __syncthreads();
+            Patch::stage_scalar(p, lp, xin, t.tx0, t.ty0, c0, tid);
+            load_u(c0);
+            store_u();
+            __syncthreads();
+            compute_chunk();
+        }
+    }
+
+    float* yout = p.y + (size_t)t.n * p.cout * hw;
+    const bool stats = p.stat_part != nullptr, masked = p.stat_mask_y != nullptr;
+    float* red = lds;  // [WPX][CT][2] statistics scratch
+    static_assert(WPX * CT * 2 <= PATCH + WSZ, "stat scratch must fit the staging LDS");
+    if (stats) __syncthreads();  // every wave is done with the staging LDS
+    const float* my = masked ? p.stat_mask_y + (size_t)t.n * p.cout * hw : nullptr;
+    // epilogue: register i of wacc[m][nb][pos] is M[pos] of cout (l >> 4) * 4 + i of cout-block m
+    // and tile l & 15 of tile-block nb; the inverse transform gives its 2x2 pixels (both rows in one
+    // image: the strip seam row ra is even).  Pixel pairs are stored as float2 where y allows it.
+    // Statistics: per lane over its tiles' pixels, then over the 16 lanes of a row (DPP), then over
+    // the WPX waves in LDS.
+    const bool y2 = (p.wd & 1) == 0 && (reinterpret_cast<size_t>(p.y) & 7) == 0;
+    bool pok[NB][4];
+    unsigned pofs[NB][4];  // pixel offsets, 0 when outside the image
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        const int tt = (wave_px * NB + nb) * 16 + wl;
+        const int r0 = 2 * (tt / TXN), ox = t.tx0 + 2 * (tt % TXN);
+        const bool in_a = r0 < t.ra;
+        const int oy = in_a ? t.gyA0 + r0 : r0 - t.ra;
+        const bool img_ok = tt < NT && (in_a ? t.imgA_ok : t.imgB_ok);
+        const unsigned base = (unsigned)((in_a ? t.imgA : t.imgA + 1) * p.cout) * uhw;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int py = oy + (q >> 1), px = ox + (q & 1);
+            pok[nb][q] = img_ok && py < p.h && px < p.wd;
+            pofs[nb][q] = pok[nb][q] ? base + (unsigned)py * (unsigned)p.wd + (unsigned)px : 0u;
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int cl = m * 16 + 4 * wq + i;
+            const int co = co0 + cl;
+            const bool co_ok = co < p.cout;
+            const size_t cofs = (size_t)min(co, p.cout - 1) * hw;
+            float out[NB][4], oldv[NB][4], yv[NB][4];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                float mm[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) mm[q] = wacc[m][nb][q][i];
+                wino_output(mm, out[nb]);
                 if (p.accumulate) {
 #pragma unroll
-                    for (int rr = 0; rr < RG; ++rr) {
-                        const int r = rg + rr;
-                        const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
-                        const float* src = yout + (size_t)min(co, p.cout - 1) * hw;
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) oldv[rr][nb] = src[pixc[nb]];
-                    }
+                    for (int q = 0; q < 4; ++q) oldv[nb][q] = yout[cofs + pofs[nb][q]];
                 }
                 if (masked) {
 #pragma unroll
-                    for (int rr = 0; rr < RG; ++rr) {
-                        const int r = rg + rr;
-                        const int co = co0 + (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
-                        const float* src = my + (size_t)min(co, p.cout - 1) * hw;
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) yv[rr][nb] = src[pixc[nb]];
-                    }
+                    for (int q = 0; q < 4; ++q) yv[nb][q] = my[cofs + pofs[nb][q]];
                 }
+            }
 #pragma unroll
-                for (int rr = 0; rr < RG; ++rr) {
-                    const int r = rg + rr;
-                    const int cl = (wave_co * MB + m) * 32 + 4 * khalf + (r & 3) + 8 * (r >> 2);
-                    const int co = co0 + cl;
-                    const bool co_ok = co < p.cout;
-                    float* dst = yout + (size_t)co * hw;
+            for (int nb = 0; nb < NB; ++nb) {
+                if (p.accumulate) {  // the statistics see the sum
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) {
-                        if (p.accumulate) acc[m][nb][r] += oldv[rr][nb];  // the statistics see the sum
-                        if (co_ok && pix_ok[nb])
-                            dst[pixc[nb]] = acc[m][nb][r];
-                    }
-                    if (!stats) continue;
-                    float s1 = 0.f, s2 = 0.f;
-                    if (!masked) {  // forward statistics about the pivot
-                        const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
+                    for (int q = 0; q < 4; ++q) out[nb][q] += oldv[nb][q];
+                }
+                if (co_ok) {
 #pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) {
-                            const float d = pix_ok[nb] ? acc[m][nb][r] - pv : 0.f;
-                            s1 += d;
-                            s2 = fmaf(d, d, s2);
+                    for (int r = 0; r < 2; ++r) {
+                        float* dst = yout + cofs + pofs[nb][2 * r];
+                        if (y2 && pok[nb][2 * r] && pok[nb][2 * r + 1]) {
+                            *reinterpret_cast<float2*>(dst) = make_float2(out[nb][2 * r], out[nb][2 * r + 1]);
+                        } else {
+                            if (pok[nb][2 * r]) dst[0] = out[nb][2 * r];
+                            if (pok[nb][2 * r + 1]) yout[cofs + pofs[nb][2 * r + 1]] = out[nb][2 * r + 1];
                         }
-                    } else {  // backward sums of the BatchNorm this gradient feeds
-                        const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) {
-                            const bool on = co_ok && pix_ok[nb] &&
-                                            (!p.mask_relu || fmaf(yv[rr][nb], msc, msh) > 0.f);
-                            const float d = on ? acc[m][nb][r] : 0.f;
-                            s1 += d;
-                            s2 = fmaf(d, yv[rr][nb], s2);
-                        }
-                    }
-                    s1 = half_sum32(s1);
-                    s2 = half_sum32(s2);
-                    if (j == 31) {
-                        red[(wave_px * CT + cl) * 2] = s1;
-                        red[(wave_px * CT + cl) * 2 + 1] = s2;
                     }
                 }
             }
-        }
-    }
-    if (stats) {
-        __syncthreads();
-        const long long tg = (long long)bz * (p.tiles_x * p.tiles_y) + tile;
-        for (int c = tid; c < CT; c += kThreads) {
-            if (co0 + c >= p.cout) continue;
-            float a = 0.f, b = 0.f;
+            if (!stats) continue;
+            float s1 = 0.f, s2 = 0.f;
+            if (!masked) {  // forward statistics about the pivot
+                const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
 #pragma unroll
-            for (int wp = 0; wp < WPX; ++wp) {
-                a += red[(wp * CT + c) * 2];
-                b += red[(wp * CT + c) * 2 + 1];
+                for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float d = pok[nb][q] ? out[nb][q] - pv : 0.f;
+                        s1 += d;
+                        s2 = fmaf(d, d, s2);
+                    }
+            } else {  // backward sums of the BatchNorm this gradient feeds
+                const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const bool on = co_ok && pok[nb][q] &&
+                                        (!p.mask_relu || fmaf(yv[nb][q], msc, msh) > 0.f);
+                        const float d = on ? out[nb][q] : 0.f;
+                        s1 += d;
+                        s2 = fmaf(d, yv[nb][q], s2);
+                    }
             }
-            float* dst = p.stat_part + ((size_t)(co0 + c) * (size_t)p.stat_tiles + (size_t)tg) * 2;
-            dst[0] = a;
-            dst[1] = b;
+            s1 = row_sum16(s1);
+            s2 = row_sum16(s2);
+            if (wl == 0) {
+                red[(wave_px * CT + cl) * 2] = s1;
+                red[(wave_px * CT + cl) * 2 + 1] = s2;
+            }
         }
     }
+    if (stats) write_stat_part<WPX, CT>(p, red, t.bz, t.tile, co0, tid);
 }
 
 // ---------------------------------------------------------------------------
 // wgrad
 // ---------------------------------------------------------------------------
-// D[ci][co] (per tap) += sum over pixel pairs.  A operand = X (lane -> ci, k = pixel),
+// 1x1 (wgrad_mfma_kernel): D[ci][co] += sum over pixel pairs.  A operand = X (lane -> ci, k = pixel),
 // B operand = dY (lane -> co).  A workgroup owns a (32*WCI ci) x (32*WCO co) weight block and
 // a range of (image, tile) work items; its 4 waves are WCI x WCO x KSPL with the KSPL waves
 // splitting the rows of each tile.
@@ -829,23 +912,18 @@ __device__ __forceinline__ float bn_dy1(float g, float y, float al, float ad, fl
     return fmaf(c2, dz, fmaf(c3, y, c4));
 }
 
-template <int TAPS, int TW, int TH, int WCI, int WCO, int KSPL>
-__global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kernel(WgradArgs p) {
+template <int TW, int TH, int WCI, int WCO, int KSPL>
+__global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
     static_assert(WCI * WCO * KSPL == 4, "wave decomposition");
     static_assert(TH % KSPL == 0 && TW % 4 == 0, "rows split across waves, float4 rows");
-    constexpr int HALO = TAPS == 9 ? 1 : 0;
-    constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO;
-    constexpr int PP = (PW * PH) | 1;  // odd plane pitch: 32 lanes on 32 channels hit 32 banks
-    constexpr int DP = (TW * TH) | 1;
+    constexpr int PP = (TW * TH) | 1;  // odd plane pitch (X and dY): 32 lanes on 32 channels hit 32 banks
     constexpr int CI_T = 32 * WCI, CO_T = 32 * WCO;
-    constexpr int XSZ = CI_T * PP, DSZ = CO_T * DP;
-    constexpr int RED = KSPL > 1 ? TAPS * 1024 : 0;  // one wave's accumulators
+    constexpr int XSZ = CI_T * PP, DSZ = CO_T * PP;
+    constexpr int RED = KSPL > 1 ? 1024 : 0;  // one wave's accumulators
     constexpr int LDSF = XSZ + DSZ > RED ? XSZ + DSZ : RED;
     constexpr int TW4 = TW / 4;
-    constexpr int NXI = CI_T * PH * TW4, XPT = (NXI + kThreads - 1) / kThreads;      // interior float4 items
-    constexpr int NHI = CI_T * PH * 2 * HALO, HPT = (NHI + kThreads - 1) / kThreads;  // halo scalars
+    constexpr int NXI = CI_T * TH * TW4, XPT = (NXI + kThreads - 1) / kThreads;
     constexpr int NDI = CO_T * TH * TW4, DPT = (NDI + kThreads - 1) / kThreads;
-    constexpr int kMaxProC = 512;
     __shared__ float lds[LDSF];
     float* lx = lds;
     float* ld = lds + XSZ;
@@ -857,14 +935,12 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
     const size_t hw = (size_t)p.h * p.wd;
     const unsigned uhw = (unsigned)hw;
 
-    f32x16 acc[TAPS];
+    f32x16 acc;
 #pragma unroll
-    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
-    const int abase = (w_ci * 32 + j) * PP + khalf;  // + row*PW + x + tap offset
-    const int bbase = (w_co * 32 + j) * DP + khalf;
+    const int abase = (w_ci * 32 + j) * PP + khalf;  // + row*TW + x
+    const int bbase = (w_co * 32 + j) * PP + khalf;
     const bool pro = p.in_scale != nullptr;
 
     auto compute_item = [&]() {
@@ -872,17 +948,11 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
 #pragma unroll
         for (int rr = 0; rr < ROWS; ++rr) {
             const int row = w_k * ROWS + rr;
-            // 9 MFMAs (576 cycles) per pixel pair: a shallow unroll already hides the LDS
-            // latency and keeps the 144 accumulators + staging registers under 256
 #pragma unroll 2
             for (int xx = 0; xx < TW; xx += 2) {
                 const float b = ld[bbase + row * TW + xx];
-#pragma unroll
-                for (int t = 0; t < TAPS; ++t) {
-                    const int dy = TAPS == 9 ? t / 3 : 0, dx = TAPS == 9 ? t % 3 : 0;
-                    const float a = lx[abase + (row + dy) * PW + xx + dx];
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[t], 0, 0, 0);
-                }
+                const float a = lx[abase + row * TW + xx];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
             }
         }
     };
@@ -893,7 +963,6 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
 
     if (p.vec_ok) {  // every tile is full in x (host guarantees W % TW == 0 for this path)
         float4 xv[XPT], dv[DPT];
-        float xh[HPT > 0 ? HPT : 1];
         unsigned xok = 0;
         // producer BatchNorm scale/shift of this workgroup's CI_T channels, staged once in LDS
         __shared__ float lsc[kMaxProC / 2];
@@ -916,40 +985,25 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
                 lbn[e] = gc < p.cout ? p.bn_coef[(size_t)kk * p.cout + gc] : 0.f;
             }
         }
-        auto load_x = [&](int item, auto i0c, auto i1c) {
-            constexpr int I0 = decltype(i0c)::value, I1 = decltype(i1c)::value;
+        // the next item's loads stay in registers over the MFMAs
+        auto load_x = [&](int item) {
             const int n = item / tiles, t = item - n * tiles;
             const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
             const float* xin = p.x + (size_t)n * p.cin * hw;
-            if (I0 == 0) xok = 0;
+            xok = 0;
 #pragma unroll
-            for (int i = I0; i < I1; ++i) {
+            for (int i = 0; i < XPT; ++i) {
                 const int e = tid + i * kThreads;
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                const int c = e / (PH * TW4), rem = e - c * (PH * TW4);
+                const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
                 const int py = rem / TW4, slot = rem - py * TW4;
-                const int gc = ci0 + c, gy = ty0 + py - HALO;
-                if (e < NXI && gc < p.cin && gy >= 0 && gy < p.h) {
+                const int gc = ci0 + c, gy = ty0 + py;
+                if (e < NXI && gc < p.cin && gy < p.h) {
                     v = *reinterpret_cast<const float4*>(xin + (unsigned)gc * uhw +
                                                          (unsigned)gy * (unsigned)p.wd + tx0 + 4 * slot);
                     xok |= 1u << i;
                 }
                 xv[i] = v;
-            }
-            if (I1 == XPT) {
-#pragma unroll
-                for (int i = 0; i < HPT; ++i) {
-                    const int e = tid + i * kThreads;
-                    float v = 0.f;
-                    const int c = e / (PH * 2), rem = e - c * (PH * 2);
-                    const int py = rem >> 1, side = rem & 1;
-                    const int gc = ci0 + c, gy = ty0 + py - HALO, gx = side ? tx0 + TW : tx0 - 1;
-                    if (e < NHI && gc < p.cin && gy >= 0 && gy < p.h && gx >= 0 && gx < p.wd) {
-                        v = xin[(unsigned)gc * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)gx];
-                        xok |= 1u << (16 + i);
-                    }
-                    xh[i] = v;
-                }
             }
         };
         auto load_d = [&](int item) {
@@ -992,13 +1046,12 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
                 }
             }
         };
-        auto store_x = [&](auto i0c, auto i1c) {
-            constexpr int I0 = decltype(i0c)::value, I1 = decltype(i1c)::value;
+        auto store_x = [&]() {
 #pragma unroll
-            for (int i = I0; i < I1; ++i) {
+            for (int i = 0; i < XPT; ++i) {
                 const int e = tid + i * kThreads;
                 if (e < NXI) {
-                    const int c = e / (PH * TW4), rem = e - c * (PH * TW4);
+                    const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
                     const int py = rem / TW4, slot = rem - py * TW4;
                     float4 v = xv[i];
                     if (pro && (xok >> i & 1u)) {
@@ -1008,25 +1061,11 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
                         v.z = pro_apply(v.z, sc, sh, p.in_relu);
                         v.w = pro_apply(v.w, sc, sh, p.in_relu);
                     }
-                    float* dst = lx + c * PP + py * PW + HALO + 4 * slot;
+                    float* dst = lx + c * PP + py * TW + 4 * slot;
                     dst[0] = v.x;
                     dst[1] = v.y;
                     dst[2] = v.z;
                     dst[3] = v.w;
-                }
-            }
-            if (I1 == XPT) {
-#pragma unroll
-                for (int i = 0; i < HPT; ++i) {
-                    const int e = tid + i * kThreads;
-                    if (e < NHI) {
-                        const int c = e / (PH * 2), rem = e - c * (PH * 2);
-                        const int py = rem >> 1, side = rem & 1;
-                        float v = xh[i];
-                        if (pro && (xok >> (16 + i) & 1u))
-                            v = pro_apply(v, lsc[c], lsc[kMaxProC / 4 + c], p.in_relu);
-                        lx[c * PP + py * PW + (side ? PW - 1 : 0)] = v;
-                    }
                 }
             }
         };
@@ -1052,7 +1091,7 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
                                                        (size_t)(sty0 + py) * p.wd + stx0 + 4 * slot) = v;
                         }
                     }
-                    float* dst = ld + c * DP + rem * 4;
+                    float* dst = ld + c * PP + rem * 4;
                     dst[0] = v.x;
                     dst[1] = v.y;
                     dst[2] = v.z;
@@ -1060,84 +1099,55 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
                 }
             }
         };
-        if (TAPS == 1) {  // few accumulators: next item's loads stay in registers over the MFMAs
-            using Z = std::integral_constant<int, 0>;
-            using E = std::integral_constant<int, XPT>;
-            if (first < last) {
-                load_x(first, Z{}, E{});
-                load_d(first);
+        if (first < last) {
+            load_x(first);
+            load_d(first);
+        }
+        for (int item = first; item < last; ++item) {
+            __syncthreads();
+            store_x();
+            store_d(item);
+            __syncthreads();
+            if (item + 1 < last) {
+                load_x(item + 1);
+                load_d(item + 1);
             }
-            for (int item = first; item < last; ++item) {
-                __syncthreads();
-                store_x(Z{}, E{});
-                store_d(item);
-                __syncthreads();
-                if (item + 1 < last) {
-                    load_x(item + 1, Z{}, E{});
-                    load_d(item + 1);
-                }
-                compute_item();
-            }
-        } else {
-            // 144 accumulators leave ~100 registers: stage X in two halves (XPT/2 float4 in
-            // flight per thread), then dY
-            using Z = std::integral_constant<int, 0>;
-            using H = std::integral_constant<int, (XPT + 1) / 2>;
-            using E = std::integral_constant<int, XPT>;
-            for (int item = first; item < last; ++item) {
-                __syncthreads();
-                load_x(item, Z{}, H{});
-                store_x(Z{}, H{});
-                load_x(item, H{}, E{});
-                store_x(H{}, E{});
-                load_d(item);
-                store_d(item);
-                __syncthreads();
-                compute_item();
-            }
+            compute_item();
         }
     } else {
         // scalar staging: thread -> one tile position, walking channels
-        constexpr int XPOS = PW * PH, DPOS = TW * TH;
-        constexpr int XSLOTS = XPOS <= 64 ? 64 : (XPOS <= 128 ? 128 : 256);
-        constexpr int DSLOTS = DPOS <= 64 ? 64 : (DPOS <= 128 ? 128 : 256);
-        constexpr int XG = kThreads / XSLOTS, DG = kThreads / DSLOTS;
-        static_assert(XPOS <= 256 && DPOS <= 256, "wgrad tiles are at most 256 positions");
-        const int xslot = tid % XSLOTS, xgrp = tid / XSLOTS;
-        const int dslot = tid % DSLOTS, dgrp = tid / DSLOTS;
-        const int xpy = xslot / PW, xpx = xslot - xpy * PW;
-        const int dpy = dslot / TW, dpx = dslot - dpy * TW;
+        constexpr int POS = TW * TH;
+        constexpr int SLOTS = POS <= 64 ? 64 : (POS <= 128 ? 128 : 256);
+        constexpr int G = kThreads / SLOTS;
+        static_assert(POS <= 256, "wgrad tiles are at most 256 positions");
+        const int slot = tid % SLOTS, grp = tid / SLOTS;
+        const int spy = slot / TW, spx = slot - spy * TW;
         for (int item = first; item < last; ++item) {
             const int n = item / tiles, t = item - n * tiles;
             const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
             const float* xin = p.x + (size_t)n * p.cin * hw;
             const float* din = p.dy + (size_t)n * p.cout * hw;
             __syncthreads();
-            if (xslot < XPOS) {
-                const int gy = ty0 + xpy - HALO, gx = tx0 + xpx - HALO;
-                const bool ok = gy >= 0 && gy < p.h && gx >= 0 && gx < p.wd;
+            if (slot < POS) {
+                const int gy = ty0 + spy, gx = tx0 + spx;
+                const bool ok = gy < p.h && gx < p.wd;
                 const unsigned off = ok ? (unsigned)gy * (unsigned)p.wd + (unsigned)gx : 0u;
 #pragma unroll 4
-                for (int c = xgrp; c < CI_T; c += XG) {
+                for (int c = grp; c < CI_T; c += G) {
                     const int gc = ci0 + c;
                     float v = 0.f;
                     if (ok && gc < p.cin) {
                         v = xin[(unsigned)gc * uhw + off];
                         if (pro) v = pro_apply(v, p.in_scale[gc], p.in_shift[gc], p.in_relu);
                     }
-                    lx[c * PP + xslot] = v;
+                    lx[c * PP + slot] = v;
                 }
-            }
-            if (dslot < DPOS) {
-                const int gy = ty0 + dpy, gx = tx0 + dpx;
-                const bool ok = gy < p.h && gx < p.wd;
-                const unsigned off = ok ? (unsigned)gy * (unsigned)p.wd + (unsigned)gx : 0u;
 #pragma unroll 4
-                for (int c = dgrp; c < CO_T; c += DG) {
+                for (int c = grp; c < CO_T; c += G) {
                     const int gc = co0 + c;
                     float v = 0.f;
                     if (ok && gc < p.cout) v = din[(unsigned)gc * uhw + off];
-                    ld[c * DP + dslot] = v;
+                    ld[c * PP + slot] = v;
                 }
             }
             __syncthreads();
@@ -1156,30 +1166,24 @@ __global__ __launch_bounds__(kThreads, (TAPS == 9 ? 2 : 4)) void wgrad_mfma_kern
                 __syncthreads();
                 if (w_k == k && q == qq) {
 #pragma unroll
-                    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) lds[t * 1024 + r * 64 + lane] = acc[t][r];
+                    for (int r = 0; r < 16; ++r) lds[r * 64 + lane] = acc[r];
                 }
                 __syncthreads();
                 if (w_k == 0 && q == qq) {
 #pragma unroll
-                    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[t][r] += lds[t * 1024 + r * 64 + lane];
+                    for (int r = 0; r < 16; ++r) acc[r] += lds[r * 64 + lane];
                 }
             }
         }
     }
     if (w_k == 0) {
-        float* out = p.part + (size_t)blockIdx.x * p.cin * TAPS * p.cout;
+        float* out = p.part + (size_t)blockIdx.x * p.cin * p.cout;
         const int co = co0 + w_co * 32 + j;
 #pragma unroll
-        for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ci = ci0 + w_ci * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                if (ci < p.cin && co < p.cout) out[((size_t)ci * TAPS + t) * p.cout + co] = acc[t][r];
-            }
+        for (int r = 0; r < 16; ++r) {
+            const int ci = ci0 + w_ci * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            if (ci < p.cin && co < p.cout) out[(size_t)ci * p.cout + co] = acc[r];
+        }
     }
 }
 
@@ -1226,7 +1230,6 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
     constexpr int NXI = CI_T * PH * TW4, XPT = (NXI + NT - 1) / NT;      // interior float4 items
     constexpr int NHI = CI_T * PH * 2 * 1, HPT = (NHI + NT - 1) / NT;  // halo scalars
     constexpr int NDI = CO_T * TH * TW4, DPT = (NDI + NT - 1) / NT;
-    constexpr int kMaxProC = 512;
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1792,6 +1795,7 @@ __global__ __launch_bounds__(kThreads) void weight_dgrad_kernel(const float* __r
 // ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
+// ct: the direct kernel's cout tile (launch_fwd gives the Winograd kernels' own)
 struct FwdVariant {
     int tw, th, ct;
 };
@@ -1811,56 +1815,50 @@ inline bool fwd_small_cin(int taps, int variant, int cin) { return taps == 9 && 
 // the shape half of ConvArgs::vec_ok (the other half: 16-byte aligned x and w)
 inline bool fwd_vec_shape(int wd, int cout) { return wd % 4 == 0 && cout % 4 == 0; }
 
-// Output channels per workgroup (grid.y).  The Winograd kernels keep the variant's spatial tile
-// (the statistics partials are laid out per tile) but take 32 couts (16 for the 112-tile 56x8
-// variant): 16 positions x 4 accumulators per (cout, tile) leave room for 128 per wave.
-inline int fwd_ct(int taps, int variant, int cin) {
-    if (taps == 9 && !fwd_small_cin(taps, variant, cin)) return variant == 6 ? 16 : 32;
-    return kFwdVariants[variant].ct;
-}
-
 // K-chunk of 8 input channels everywhere (16 measured slower: more prefetch registers, fewer resident waves).
-// Every 3x3 launch but the stem's runs Winograd F(2x2,3x3); the direct kernel serves the stem and 1x1.
-template <int TAPS>
-int launch_fwd(int variant, const ConvArgs& a, dim3 grid, hipStream_t s) {
-    if (fwd_small_cin(TAPS, variant, a.cin)) {
+// gx x gz: tiles x strips; grid.y = cout / the kernel's cout tile.
+int launch_fwd(int ksize, int variant, const ConvArgs& a, unsigned gx, unsigned gz, hipStream_t s) {
+    const auto grid = [&](int ct) { return dim3(gx, (a.cout + ct - 1) / ct, gz); };
+    const dim3 g = grid(kFwdVariants[variant].ct);  // the direct kernel's cout tile
+    if (ksize == 3 && fwd_small_cin(9, variant, a.cin)) {
         // the stem (Cin = 3): a 4-channel K-chunk instead of 8 halves the MFMAs spent on zeros
-        conv_mfma_kernel<9, 32, 8, 1, 1, 4, 2, 4><<<grid, kThreads, 0, s>>>(a);
+        conv_mfma_kernel<9, 32, 8, 1, 1, 4, 2, 4><<<g, kThreads, 0, s>>>(a);
         return LF_OK;
     }
-    if constexpr (TAPS == 9) {
+    if (ksize == 3) {
+        // Every other 3x3 launch runs Winograd F(2x2,3x3).  The kernel keeps the variant's spatial
+        // tile (the statistics partials are laid out per tile) but takes 32 couts (16 for the
+        // 112-tile 56x8 variant): 16 positions x 4 accumulators per (cout, tile) leave room for 128
+        // per wave.  Variants 1, 3 and 5 have the tile of 0, 2 and 0 with a wider ct, so the 3x3
+        // argmin never picks them.
         switch (variant) {
-            case 0:
-            case 1:
-            case 5: conv_mfma_kernel<9, 32, 8, 1, 2, 4, 1, 8, false, true><<<grid, kThreads, 0, s>>>(a); break;
-            case 2:
-            case 3: conv_mfma_kernel<9, 16, 16, 1, 2, 4, 1, 8, false, true><<<grid, kThreads, 0, s>>>(a); break;
-            case 4: conv_mfma_kernel<9, 28, 8, 1, 2, 4, 1, 8, true, true><<<grid, kThreads, 0, s>>>(a); break;
-            case 6: conv_mfma_kernel<9, 56, 8, 1, 1, 4, 2, 8, false, true><<<grid, kThreads, 0, s>>>(a); break;
-            default: return LF_ERR_INVALID;
-        }
-        return LF_OK;
-    } else {
-        switch (variant) {
-            case 0: conv_mfma_kernel<TAPS, 32, 8, 1, 1, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
-            case 1: conv_mfma_kernel<TAPS, 32, 8, 1, 2, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
-            case 2: conv_mfma_kernel<TAPS, 16, 16, 1, 1, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
-            case 3: conv_mfma_kernel<TAPS, 16, 16, 1, 2, 4, 2, 8><<<grid, kThreads, 0, s>>>(a); break;
-            case 4: conv_mfma_kernel<TAPS, 28, 8, 4, 1, 1, 7, 8, true><<<grid, kThreads, 0, s>>>(a); break;
-            case 5: conv_mfma_kernel<TAPS, 32, 8, 2, 2, 2, 4, 8><<<grid, kThreads, 0, s>>>(a); break;
-            case 6: conv_mfma_kernel<TAPS, 56, 8, 2, 1, 2, 7, 8><<<grid, kThreads, 0, s>>>(a); break;
+            case 0: conv_wino_kernel<32, 8, 2, 1, false><<<grid(32), kThreads, 0, s>>>(a); break;
+            case 2: conv_wino_kernel<16, 16, 2, 1, false><<<grid(32), kThreads, 0, s>>>(a); break;
+            case 4: conv_wino_kernel<28, 8, 2, 1, true><<<grid(32), kThreads, 0, s>>>(a); break;
+            case 6: conv_wino_kernel<56, 8, 1, 2, false><<<grid(16), kThreads, 0, s>>>(a); break;
             default: return LF_ERR_INVALID;
         }
         return LF_OK;
     }
+    switch (variant) {
+        case 0: conv_mfma_kernel<1, 32, 8, 1, 1, 4, 2, 8><<<g, kThreads, 0, s>>>(a); break;
+        case 1: conv_mfma_kernel<1, 32, 8, 1, 2, 4, 2, 8><<<g, kThreads, 0, s>>>(a); break;
+        case 2: conv_mfma_kernel<1, 16, 16, 1, 1, 4, 2, 8><<<g, kThreads, 0, s>>>(a); break;
+        case 3: conv_mfma_kernel<1, 16, 16, 1, 2, 4, 2, 8><<<g, kThreads, 0, s>>>(a); break;
+        case 4: conv_mfma_kernel<1, 28, 8, 4, 1, 1, 7, 8, true><<<g, kThreads, 0, s>>>(a); break;
+        case 5: conv_mfma_kernel<1, 32, 8, 2, 2, 2, 4, 8><<<g, kThreads, 0, s>>>(a); break;
+        case 6: conv_mfma_kernel<1, 56, 8, 2, 1, 2, 7, 8><<<g, kThreads, 0, s>>>(a); break;
+        default: return LF_ERR_INVALID;
+    }
+    return LF_OK;
 }
 
 struct WgVariant {
     int tw, th, ci_t, co_t, kspl;
 };
 constexpr WgVariant kWgVariants[] = {{32, 4, 32, 32, 4}, {16, 8, 32, 64, 2}, {16, 4, 64, 64, 1},
-                                     {28, 2, 64, 64, 1}, {32, 4, 32, 64, 2}};
-constexpr int kWgSmallCin = 5;  // variant id of wgrad_smallcin_kernel<32, 8>
+                                     {28, 2, 64, 64, 1}};
+constexpr int kWgSmallCin = 5;  // variant id of wgrad_smallcin_kernel<32, 8> (4 is not used)
 
 // wgrad3 uses more than the 64 KB of LDS a kernel gets by default: raise the limit once
 template <int TW, int TH, int WCI, int WCO, int KSPL>
@@ -1886,16 +1884,14 @@ int launch_wgrad(int ksize, int variant, const WgradArgs& a, dim3 grid, hipStrea
             case 1: return launch_wgrad3<16, 8, 1, 2, 2>(a, grid, s);
             case 2: return launch_wgrad3<16, 4, 2, 2, 1>(a, grid, s);
             case 3: return launch_wgrad3<28, 2, 2, 2, 1>(a, grid, s);
-            case 4: return launch_wgrad3<32, 4, 1, 2, 2>(a, grid, s);
             default: return LF_ERR_INVALID;
         }
     } else {
         switch (variant) {
-            case 0: wgrad_mfma_kernel<1, 32, 4, 1, 1, 4><<<grid, kThreads, 0, s>>>(a); break;
-            case 1: wgrad_mfma_kernel<1, 16, 8, 1, 2, 2><<<grid, kThreads, 0, s>>>(a); break;
-            case 2: wgrad_mfma_kernel<1, 16, 4, 2, 2, 1><<<grid, kThreads, 0, s>>>(a); break;
-            case 3: wgrad_mfma_kernel<1, 28, 2, 2, 2, 1><<<grid, kThreads, 0, s>>>(a); break;
-            case 4: wgrad_mfma_kernel<1, 32, 4, 1, 2, 2><<<grid, kThreads, 0, s>>>(a); break;
+            case 0: wgrad_mfma_kernel<32, 4, 1, 1, 4><<<grid, kThreads, 0, s>>>(a); break;
+            case 1: wgrad_mfma_kernel<16, 8, 1, 2, 2><<<grid, kThreads, 0, s>>>(a); break;
+            case 2: wgrad_mfma_kernel<16, 4, 2, 2, 1><<<grid, kThreads, 0, s>>>(a); break;
+            case 3: wgrad_mfma_kernel<28, 2, 2, 2, 1><<<grid, kThreads, 0, s>>>(a); break;
             default: return LF_ERR_INVALID;
         }
     }
@@ -2050,10 +2046,7 @@ static int conv2d_launch(const char* who, const float* x, const float* w, float*
     a.mask_relu = mask_relu;
     const int gz = (n + a.stack - 1) / a.stack;
     a.stat_tiles = (long long)gz * a.tiles_x * a.tiles_y;
-    const int ct = fwd_ct(ksize * ksize, best, cin);
-    dim3 grid(a.tiles_x * a.tiles_y, (cout + ct - 1) / ct, gz);
-    hipStream_t s = lf::as_stream(stream);
-    const int rc = ksize == 3 ? launch_fwd<9>(best, a, grid, s) : launch_fwd<1>(best, a, grid, s);
+    const int rc = launch_fwd(ksize, best, a, a.tiles_x * a.tiles_y, gz, lf::as_stream(stream));
     if (rc != LF_OK) return rc;
     return lf::check_launch(who);
 }

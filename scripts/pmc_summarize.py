@@ -2,9 +2,10 @@
 
 usage: pmc_summarize.py OUT.csv [--json pmc_latest.json] DIR [DIR ...]
 Each DIR holds one rocprofv3 pass (`*_counter_collection.csv`).  Kernel names are shortened to
-the form bench.py uses (`conv_mfma_kernel<9,28,8,4,1,1,7>`: the trailing K-chunk template
-argument is dropped).  With --json, writes {kernel: HBM bytes per launch} using the gfx950
-correction of MI355X_MICROARCH.md (HBM section): bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024.
+the form bench.py uses (`conv_mfma_kernel<1,28,8,4,1,1,7>`: the trailing K-chunk and strip template
+arguments are dropped; `conv_wino_kernel<28,8,2,1>`: the strip argument is dropped).  With --json,
+writes {kernel: HBM bytes per launch} using the gfx950 correction of MI355X_MICROARCH.md (HBM
+section): bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024.
 """
 import csv
 import json
@@ -22,9 +23,10 @@ def short(name: str) -> str:
         return re.sub(r"\(anonymous namespace\)::", "", name)[:60]
     base, targs = m.group(1), (m.group(2) or "")
     targs = targs.replace(" ", "")
-    if base == "conv_mfma_kernel" and targs:
+    keep = {"conv_mfma_kernel": 7, "conv_wino_kernel": 4}.get(base)
+    if keep and targs:
         parts = targs[1:-1].split(",")
-        targs = "<" + ",".join(parts[:7]) + ">"
+        targs = "<" + ",".join(parts[:keep]) + ">"
     return base + targs
 
 

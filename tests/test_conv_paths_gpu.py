@@ -116,7 +116,7 @@ BF16_CONV_PATHS = [
 ]
 
 # tile of one fp32 weight-gradient item per variant (lf_conv.hip kWgVariants; 5 = small-Cin 32x8)
-F32_WG_TILE = {0: (32, 4), 1: (16, 8), 2: (16, 4), 3: (28, 2), 4: (32, 4), 5: (32, 8)}
+F32_WG_TILE = {0: (32, 4), 1: (16, 8), 2: (16, 4), 3: (28, 2), 5: (32, 8)}
 
 
 def _plan(fn, size, *args):
