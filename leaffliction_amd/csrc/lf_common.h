@@ -62,36 +62,46 @@ bool blur_mfma_launch(const uint8_t* in, uint8_t* out, int n, int h, int w, int 
                       const BlurTaps& taps, int ksize, hipStream_t s);
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// lf_conv2d_bf16_train is served by two kernels: the streaming one (lf_conv_bf16s.hip: Cin, Cout <= 64,
-// filter bank resident in LDS, one statistics partial per workgroup) and the K-chunked one
-// (lf_conv_bf16.hip: everything else, one partial per tile).
-struct ConvBf16TrainArgs {
-    const void* x;            // fp32 or bf16 NCHW
+// One bf16 convolution, as both of its kernels take it: the streaming one (lf_conv_bf16s.hip: Cin, Cout <= 64,
+// filter bank resident in LDS, one statistics partial per workgroup) and the K-chunked one (lf_conv_bf16.hip:
+// everything else, one partial per tile).  conv_bf16_launch (lf_conv_bf16.hip) fills it and picks the kernel.
+struct ConvBf16Args {
+    const void* x;            // fp32 or bf16 NCHW (template XBF)
     const uint16_t* wprep;    // bf16 [ceil(cin/16)][taps][cout][16]
-    uint16_t* y;              // bf16 NCHW
+    void* y;                  // bf16 NCHW; the K-chunked kernel also stores fp32 (template YBF)
     int n, cin, h, w, cout;
     const float* in_scale;    // optional prologue relu?(x*scale+shift)
     const float* in_shift;
     int in_relu;
-    int accumulate;
-    float* stat_part;         // [cout][stat_tiles][2] or null
-    const float* stat_pivot;
-    long long stat_tiles;
+    // optional epilogue on the fp32 accumulators before rounding: v*out_scale[co]+out_shift[co], then ReLU if
+    // out_relu — inference: the layer's folded BatchNorm(+ReLU), so that what is stored is the activation itself
+    const float* out_scale;
+    const float* out_shift;
+    int out_relu;
+    // ---- training epilogue (the output is bf16 and what is summed is the ROUNDED value, i.e. exactly what later
+    // kernels read back):
+    int accumulate;            // y = bf16(conv + y_old) (input-gradient of a block with two consumers)
+    // per (output channel, partial) sums -> stat_part[(co * stat_tiles + partial) * 2 + {0,1}], a partial being a
+    // workgroup tile (K-chunked kernel) or a workgroup (streaming kernel); the terms are stat_accumulate()'s:
+    //   stat_mask_y == null: BatchNorm FORWARD statistics {sum d, sum d*d}, d = y - stat_pivot[co];
+    //   else BatchNorm-BACKWARD sums of the BN this gradient feeds: d = y * [mask_y*mask_scale[co] +
+    //   mask_shift[co] > 0 or !mask_relu] -> {sum d, sum d*mask_y}
+    float* stat_part;          // or null
+    const float* stat_pivot;   // may be null (pivot 0)
+    long long stat_tiles;      // partials per channel: n * tiles per image, or the streaming grid
     const uint16_t* stat_mask_y;
     const float* mask_scale;
     const float* mask_shift;
     int mask_relu;
-    int tiles_x, tiles_y;     // filled by the streaming launcher
+    // inference, optional, streaming kernel only: per (image, segment) channel sums of the STORED values (what a
+    // global-average pool of the stored activation adds up): unit_sums[(n * segments_per_image + segment) * cout + co]
+    float* unit_sums;
+    // filled by launch_conv_bf16 (K-chunked kernel)
+    int chunks, chunks16;     // staged chunks (32 channels); 16-channel slices of wprep
+    // filled by conv_bf16s_launch (streaming kernel)
+    int tiles_x, tiles_y;
     int seg_tiles, segs;      // a column strip is walked in `segs` segments of `seg_tiles` tiles (see conv_bf16s_kernel)
     int interleave;           // 1: an image's strips on one XCD (see conv_bf16s_kernel)
-    // inference: v*out_scale[co]+out_shift[co] (+ReLU) on the fp32 accumulators before rounding — the
-    // layer's folded BatchNorm(+ReLU), so that what is stored is the activation itself
-    const float* out_scale;
-    const float* out_shift;
-    int out_relu;
-    // inference, optional: per (image, segment) channel sums of the STORED values (what a global-average pool of the
-    // stored activation adds up): unit_sums[(n * segments_per_image + segment) * cout + co]
-    float* unit_sums;
 };
 // arguments of the bf16 weight-gradient kernel (lf_wgrad_bf16.hip)
 struct WgradBf16Args {
@@ -117,14 +127,24 @@ struct WgradBf16Args {
     int bn_relu;
 };
 
-long long conv_bf16s_parts(int n, int cin, int h, int w, int cout, int ksize, int x_bf16);  // 0 = shape not covered
-int conv_bf16s_units_per_image(int n, int cin, int h, int w, int cout, int ksize, int x_bf16);   // segments per image
-int conv_bf16s_launch(ConvBf16TrainArgs a, int ksize, int x_bf16, hipStream_t s);
+// The streaming kernel's plan for a shape: the instantiation <CI, NCO, TW, TH> and how the grid of `wgs` workgroups
+// walks the column strips.  ok = false: the shape is not covered.
+struct ConvBf16sPlan {
+    bool ok;
+    int ci, nco, tw, th, tiles_x, tiles_y, seg_tiles, segs, wgs, interleave;
+};
+ConvBf16sPlan conv_bf16s_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16);
+int conv_bf16s_launch(ConvBf16Args a, const ConvBf16sPlan& pl, int ksize, hipStream_t s);
 // the streaming kernel reads y back (read-modify-write epilogue) when it accumulates or gathers mask sums
 inline bool conv_bf16s_rmw(int accumulate, bool mask) { return accumulate || mask; }
-// the streaming kernel's plan for lf_conv2d_bf16_plan: out = {CI, NCO, TW, TH, XBF, segs > 1, interleave,
-// units per workgroup > 1}; returns 0 when the shape is not covered
-int conv_bf16s_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16, int* out);
+
+// Weight-gradient slabs part[splits][count] -> dst = beta*dst + their sum, in a fixed order (deterministic, no float
+// atomics): more than kSlabGroup slabs are first summed in groups of kSlabGroup into the `slab_groups` slabs that
+// follow them in the workspace.  slab_reduce_kernel lives in lf_conv.hip.
+constexpr int kSlabGroup = 32;
+inline int slab_groups(int splits) { return (splits + kSlabGroup - 1) / kSlabGroup; }
+inline int slab_stages(int splits) { return splits > kSlabGroup ? 2 : 1; }
+void reduce_slabs(float* part, float* dst, size_t count, int splits, float beta, hipStream_t s);
 
 // The most units (segments of column strips) one workgroup walks when `wgs` workgroups deal out n images of
 // `units_per_image` units each as conv_bf16s_kernel and wgrad_bf16_kernel do: round-robin over the grid, or with
@@ -179,6 +199,52 @@ __device__ __forceinline__ Block2 xcd_block2() {
 // bf16 held as uint16_t: widen exactly, and round to nearest even
 __device__ __forceinline__ float bf16_up(unsigned bits16) { return __uint_as_float(bits16 << 16); }
 __device__ __forceinline__ uint16_t bf16_down(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// two floats -> one dword of bf16 (lo in the low half), round to nearest even
+__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    bf16x2 v;
+    v.x = (__bf16)lo;
+    v.y = (__bf16)hi;
+    return __builtin_bit_cast(unsigned, v);
+}
+
+// DPP sums: over each 16-lane row (every lane of the row holds the row sum), and over the 32 lanes of each wave
+// half (the total lands in lanes 16-31 / 48-63)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_move(float v) {
+    return __builtin_bit_cast(
+        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
+}
+__device__ __forceinline__ float row_sum16(float v) {
+    v += dpp_move<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
+    v += dpp_move<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
+    v += dpp_move<0x141, 0xf>(v);  // row_half_mirror
+    v += dpp_move<0x140, 0xf>(v);  // row_mirror: every lane of a 16-lane row holds the row sum
+    return v;
+}
+__device__ __forceinline__ float half_sum32(float v) {
+    v = row_sum16(v);
+    v += dpp_move<0x142, 0xa>(v);  // row_bcast15 into rows 1 and 3
+    return v;
+}
+
+// One term of the statistics a convolution epilogue gathers for the BatchNorm next to it (what
+// lf_bn_train_stats_tiles_f32 / lf_bn_bwd_sums_tiles_f32 read), v being the output value as stored:
+//   forward (masked = false): d = v - pivot                                      -> a += d, b += d*d
+//   backward (masked):        d = v * [!mask_relu or y_mask*msc + msh > 0]       -> a += d, b += d*y_mask
+// A pixel outside the image (in_image = false) adds d = 0.
+__device__ __forceinline__ void stat_accumulate(float v, bool in_image, bool masked, float pivot, float y_mask,
+                                                float msc, float msh, int mask_relu, float& a, float& b) {
+    const bool on = in_image && (!mask_relu || fmaf(y_mask, msc, msh) > 0.f);
+    const float d = masked ? (on ? v : 0.f) : (in_image ? v - pivot : 0.f);
+    a += d;
+    b = fmaf(d, masked ? y_mask : d, b);
+}
 
 template <bool NT, typename T>
 __device__ __forceinline__ T ldg(const T* p) {

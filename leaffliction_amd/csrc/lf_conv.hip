@@ -88,25 +88,8 @@ struct ConvArgs {
     int mask_relu;
 };
 
-// sum over the 32 lanes of each wave half (DPP); the total lands in lanes 16-31 / 48-63
-__device__ __forceinline__ float dpp_add(float v, float moved) { return v + moved; }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
-}
-__device__ __forceinline__ float row_sum16(float v) {
-    v += dpp_move<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v += dpp_move<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v += dpp_move<0x141, 0xf>(v);  // row_half_mirror
-    v += dpp_move<0x140, 0xf>(v);  // row_mirror: every lane of a 16-lane row holds the row sum
-    return v;
-}
-__device__ __forceinline__ float half_sum32(float v) {
-    v = row_sum16(v);
-    v += dpp_move<0x142, 0xa>(v);  // row_bcast15 into rows 1 and 3
-    return v;
-}
+using lf::half_sum32;
+using lf::row_sum16;
 
 // Winograd F(2x2,3x3) transforms (Lavin & Gray 2016): Y = A^T [(G g G^T) . (B^T d B)] A with
 //   G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1], B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1],
@@ -581,21 +564,14 @@ void conv_mfma_kernel(ConvArgs p) {
                 if (!masked) {  // forward statistics about the pivot
                     const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) {
-                        const float d = pix_ok[nb] ? acc[m][nb][r] - pv : 0.f;
-                        s1 += d;
-                        s2 = fmaf(d, d, s2);
-                    }
+                    for (int nb = 0; nb < NB; ++nb)
+                        lf::stat_accumulate(acc[m][nb][r], pix_ok[nb], false, pv, 0.f, 0.f, 0.f, 0, s1, s2);
                 } else {  // backward sums of the BatchNorm this gradient feeds
                     const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) {
-                        const bool on = co_ok && pix_ok[nb] &&
-                                        (!p.mask_relu || fmaf(yv[rr][nb], msc, msh) > 0.f);
-                        const float d = on ? acc[m][nb][r] : 0.f;
-                        s1 += d;
-                        s2 = fmaf(d, yv[rr][nb], s2);
-                    }
+                    for (int nb = 0; nb < NB; ++nb)
+                        lf::stat_accumulate(acc[m][nb][r], co_ok && pix_ok[nb], true, 0.f, yv[rr][nb], msc, msh,
+                                            p.mask_relu, s1, s2);
                 }
                 s1 = half_sum32(s1);
                 s2 = half_sum32(s2);
@@ -847,23 +823,16 @@ void conv_wino_kernel(ConvArgs p) {
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float d = pok[nb][q] ? out[nb][q] - pv : 0.f;
-                        s1 += d;
-                        s2 = fmaf(d, d, s2);
-                    }
+                    for (int q = 0; q < 4; ++q)
+                        lf::stat_accumulate(out[nb][q], pok[nb][q], false, pv, 0.f, 0.f, 0.f, 0, s1, s2);
             } else {  // backward sums of the BatchNorm this gradient feeds
                 const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const bool on = co_ok && pok[nb][q] &&
-                                        (!p.mask_relu || fmaf(yv[nb][q], msc, msh) > 0.f);
-                        const float d = on ? out[nb][q] : 0.f;
-                        s1 += d;
-                        s2 = fmaf(d, yv[nb][q], s2);
-                    }
+                    for (int q = 0; q < 4; ++q)
+                        lf::stat_accumulate(out[nb][q], co_ok && pok[nb][q], true, 0.f, yv[nb][q], msc, msh, p.mask_relu,
+                                            s1, s2);
             }
             s1 = row_sum16(s1);
             s2 = row_sum16(s2);
@@ -1940,8 +1909,6 @@ WgPlan plan_wgrad(int n, int cin, int cout, int h, int w, int ksize) {
     return best;
 }
 
-constexpr int kReduceGroup = 32;  // slabs summed per first-stage workgroup row
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
 // Images per workgroup strip: 2 when the 28x8 tile would leave the last tile of every image
@@ -1957,6 +1924,18 @@ inline int conv_stack(int variant, int n, int cin, int h, int wd, int cout) {
 }
 
 }  // namespace
+
+void lf::reduce_slabs(float* part, float* dst, size_t count, int splits, float beta, hipStream_t s) {
+    const unsigned gx = lf::stream_grid(count, kThreads, 1024);
+    if (slab_stages(splits) == 1) {
+        slab_reduce_kernel<<<dim3(gx, 1), kThreads, 0, s>>>(part, dst, count, splits, splits, beta, 1);
+    } else {
+        const int groups = slab_groups(splits);
+        float* stage = part + (size_t)splits * count;
+        slab_reduce_kernel<<<dim3(gx, groups), kThreads, 0, s>>>(part, stage, count, splits, kSlabGroup, 0.f, 0);
+        slab_reduce_kernel<<<dim3(gx, 1), kThreads, 0, s>>>(stage, dst, count, groups, groups, beta, 1);
+    }
+}
 
 extern "C" {
 
@@ -2003,7 +1982,7 @@ int lf_conv2d_wgrad_plan(int n, int cin, int h, int wd, int cout, int ksize, int
     const WgPlan pl = plan_wgrad(n, cin, cout, h, wd, ksize);
     out[0] = pl.variant;
     out[1] = pl.items_per_split < 3 ? pl.items_per_split : 3;   // 1, 2, or 3+: the steady-state prefetch
-    out[2] = pl.splits > kReduceGroup ? 2 : 1;
+    out[2] = lf::slab_stages(pl.splits);
     out[3] = lf_conv2d_wgrad_bn_supported(n, cin, h, wd, cout, ksize);
     return LF_OK;
 }
@@ -2111,8 +2090,7 @@ size_t lf_conv2d_wgrad_workspace(int n, int cin, int h, int wd, int cout, int ks
     if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || wd <= 0) return 0;
     const WgPlan pl = plan_wgrad(n, cin, cout, h, wd, ksize);
     const size_t count = (size_t)cin * ksize * ksize * cout;
-    const size_t groups = (pl.splits + kReduceGroup - 1) / kReduceGroup;
-    return ((size_t)pl.splits + groups) * count * sizeof(float);
+    return ((size_t)pl.splits + lf::slab_groups(pl.splits)) * count * sizeof(float);
 }
 
 static int wgrad_launch(const char* who, const float* x, const float* dy, int n, int cin, int h,
@@ -2195,18 +2173,7 @@ int lf_conv2d_wgrad_reduce_f32(void* workspace, float* dw, int n, int cin, int h
                "lf_conv2d_wgrad_reduce: bad dims");
     const WgPlan pl = plan_wgrad(n, cin, cout, h, wd, ksize);
     const size_t count = (size_t)cin * ksize * ksize * cout;
-    float* part = static_cast<float*>(workspace);
-    hipStream_t s = lf::as_stream(stream);
-    const unsigned gx = lf::stream_grid(count, kThreads, 1024);
-    if (pl.splits <= kReduceGroup) {
-        slab_reduce_kernel<<<dim3(gx, 1), kThreads, 0, s>>>(part, dw, count, pl.splits, pl.splits, beta, 1);
-    } else {
-        const int groups = (pl.splits + kReduceGroup - 1) / kReduceGroup;
-        float* stage = part + (size_t)pl.splits * count;
-        slab_reduce_kernel<<<dim3(gx, groups), kThreads, 0, s>>>(part, stage, count, pl.splits,
-                                                                 kReduceGroup, 0.f, 0);
-        slab_reduce_kernel<<<dim3(gx, 1), kThreads, 0, s>>>(stage, dw, count, groups, groups, beta, 1);
-    }
+    lf::reduce_slabs(static_cast<float*>(workspace), dw, count, pl.splits, beta, lf::as_stream(stream));
     return lf::check_launch("lf_conv2d_wgrad_reduce");
 }
 

@@ -17,14 +17,13 @@
 // one ds_write_b128 per four pixels of a pair plane; weights are pre-packed once per model to
 // [chunk][tap][cout][16] bf16 so the A operand (one output channel, eight channels) is one 16-byte
 // LDS read.
+//
+// Every bf16 convolution entry (lf_conv2d_bf16_act, _act_mean, _train, _f32) goes through conv_bf16_launch below, which
+// runs this kernel or the streaming one as bf16_route decides.
 #include "lf_common.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 constexpr int kTW = 32;            // output tile width; height = 4 waves x NB rows
@@ -32,63 +31,19 @@ constexpr int kPW = 40;           // patch row pitch in dwords: columns x0-4 .. 
 constexpr int kKC = 2;             // 16-channel k-steps per staged chunk (32 input channels)
 constexpr int kMaxPrologueCin = 512;   // input channels a fused prologue (scale, shift) may have
 
-struct Bf16ConvArgs {
-    const void* x;   // fp32 or bf16 NCHW (template XBF)
-    const uint16_t* wprep;
-    void* y;         // fp32 or bf16 NCHW (template YBF)
-    int n, cin, h, w, cout, chunks, chunks16;   // staged chunks (32 channels); 16-channel slices of wprep
-    const float* in_scale;
-    const float* in_shift;
-    int in_relu;
-    const float* out_scale;  // optional epilogue on the fp32 accumulators: v*out_scale[co]+out_shift[co],
-    const float* out_shift;  // then ReLU if out_relu (inference: the layer's folded BatchNorm + ReLU)
-    int out_relu;
-    // ---- training epilogue (template TR; the output is bf16 and what is summed is the ROUNDED
-    // value, i.e. exactly what later kernels read back):
-    int accumulate;            // y = bf16(conv + y_old) (input-gradient of a block with two consumers)
-    // per (output channel, workgroup tile) sums -> stat_part[(co * stat_tiles + tile) * 2 + {0,1}]:
-    //   stat_mask_y == null: BatchNorm FORWARD statistics {sum d, sum d*d}, d = y - stat_pivot[co];
-    //   else BatchNorm-BACKWARD sums of the BN this gradient feeds: d = y * [mask_y*mask_scale[co] +
-    //   mask_shift[co] > 0 or !mask_relu] -> {sum d, sum d*mask_y}
-    float* stat_part;
-    const float* stat_pivot;   // may be null (pivot 0)
-    long long stat_tiles;      // n * tiles per image
-    const uint16_t* stat_mask_y;
-    const float* mask_scale;
-    const float* mask_shift;
-    int mask_relu;
-};
-
-// sum over the 32 lanes of each wave half (DPP); the total lands in lane 31 / 63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
-}
-__device__ __forceinline__ float half_sum32(float v) {
-    v += dpp_move<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v += dpp_move<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v += dpp_move<0x141, 0xf>(v);  // row_half_mirror
-    v += dpp_move<0x140, 0xf>(v);  // row_mirror: every lane of a 16-lane row holds the row sum
-    v += dpp_move<0x142, 0xa>(v);  // row_bcast15 into rows 1 and 3
-    return v;
-}
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v.x = (__bf16)lo;  // round to nearest even
-    v.y = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
-
+using lf::bf16x8;
+using lf::f32x16;
+using lf::f32x4;
+using lf::u32x2;
+using lf::half_sum32;
+using lf::pack_bf16;
 using lf::bf16_down;
 using lf::bf16_up;
 
 // (three or four workgroups per CU would need <= 168 / 128 registers: the spills cost more than the
 // occupancy brings — 40.4 k and 24.5 k img/s against 47.3 k for the whole forward pass)
 template <int TAPS, int NCO, int NB, bool XBF, bool YBF, bool TR = false, bool WIDE = false>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_bf16_kernel(Bf16ConvArgs p) {
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_bf16_kernel(lf::ConvBf16Args p) {
     static_assert(!WIDE || (YBF && NCO == 2 && NB == 2), "the 16-byte epilogue: bf16 output, 32x8 tile");
     static_assert(!TR || YBF, "the training epilogue stores bf16");
     constexpr int kTH = 4 * NB;
@@ -144,9 +99,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     constexpr int NP = (kPatchItems + kThreads - 1) / kThreads;
     constexpr int kWItems = KC * TAPS * NCO * 64;
     constexpr int NW = (kWItems + kThreads - 1) / kThreads;
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     struct Raw {  // four pixels of one channel as loaded
-        f32x4v f;
+        f32x4 f;
         u32x2 h;
     };
     Raw ra[NP], rb[NP];
@@ -179,7 +133,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
         if (XBF)
             r.h = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(xr, off, 0, 0));
         else
-            r.f = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
+            r.f = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
     };
     const unsigned wchunk_b = (unsigned)(TAPS * p.cout * 32);   // one 16-channel slice of the packed weights
     auto issue = [&](int c) {
@@ -200,8 +154,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
             rw[k] = __builtin_bit_cast(lf::u32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, it < kWItems ? o : kOutside, 0, 0));
         }
     };
-    auto widen = [&](const Raw& r, int ci) -> f32x4v {  // fp32 values with the fused prologue applied
-        f32x4v v;
+    auto widen = [&](const Raw& r, int ci) -> f32x4 {  // fp32 values with the fused prologue applied
+        f32x4 v;
         if (XBF) {
             v[0] = bf16_up(r.h.x & 0xffffu);
             v[1] = bf16_up(r.h.x >> 16);
@@ -238,7 +192,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
                 o.w = (a.y >> 16) | (b.y & 0xffff0000u);
             } else {
                 const bool inside = g_off[k] != kOutside;   // the prologue must not touch the padding
-                f32x4v a = {0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 0.0f, 0.0f};
+                f32x4 a = {0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (inside && ci0 < p.cin) a = widen(ra[k], ci0);
                 if (inside && ci0 + 1 < p.cin) b = widen(rb[k], ci0 + 1);
                 o.x = pack_bf16(a[0], b[0]);
@@ -356,8 +310,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int cl = 8 * j + ec, co = co0 + cb * 32 + cl;
-                const lf::f32x4 a0 = *reinterpret_cast<const lf::f32x4*>(le + cl * 256 + 8 * eg);
-                const lf::f32x4 a1 = *reinterpret_cast<const lf::f32x4*>(le + cl * 256 + 8 * eg + 4);
+                const f32x4 a0 = *reinterpret_cast<const f32x4*>(le + cl * 256 + 8 * eg);
+                const f32x4 a1 = *reinterpret_cast<const f32x4*>(le + cl * 256 + 8 * eg + 4);
                 float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
                 if (TR && p.accumulate)
 #pragma unroll
@@ -379,25 +333,20 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
                 if (eok) *reinterpret_cast<uvec4*>(yout + (size_t)co * hw + epo) = o;
                 if (!TR || !stats) continue;
                 float a = 0.f, b = 0.f;
-                if (eok) {
+                if (eok) {   // (one loop per kind of sum: the kind is uniform, the loops are unrolled)
                     if (!masked) {
                         const float pv = p.stat_pivot != nullptr ? p.stat_pivot[co] : 0.f;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float d = bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu) - pv;
-                            a += d;
-                            b = fmaf(d, d, b);
-                        }
+                        for (int e = 0; e < 8; ++e)
+                            lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, false, pv, 0.f,
+                                                0.f, 0.f, 0, a, b);
                     } else {
                         const float msc = p.mask_scale[co], msh = p.mask_shift[co];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            const float rv = bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu);
                             const unsigned mw = rmask[TR ? cb : 0][j][e / 2];
-                            const float yv = bf16_up((e & 1) ? mw >> 16 : mw & 0xffffu);
-                            const float d = (!p.mask_relu || fmaf(yv, msc, msh) > 0.f) ? rv : 0.f;
-                            a += d;
-                            b = fmaf(d, yv, b);
+                            lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, true, 0.f,
+                                                bf16_up((e & 1) ? mw >> 16 : mw & 0xffffu), msc, msh, p.mask_relu, a, b);
                         }
                     }
                 }
@@ -477,16 +426,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
                 if (ok[nb]) yb[cbase + po[nb]] = vb;
                 if (!stats) continue;
                 const float vr = bf16_up(vb);
-                if (!masked) {
-                    const float d = ok[nb] ? vr - pv : 0.f;
-                    s1 += d;
-                    s2 = fmaf(d, d, s2);
-                } else {
-                    const bool on = ok[nb] && (!p.mask_relu || fmaf(yv[nb], msc, msh) > 0.f);
-                    const float d = on ? vr : 0.f;
-                    s1 += d;
-                    s2 = fmaf(d, yv[nb], s2);
-                }
+                if (!masked) lf::stat_accumulate(vr, ok[nb], false, pv, 0.f, 0.f, 0.f, 0, s1, s2);
+                else lf::stat_accumulate(vr, ok[nb], true, 0.f, yv[nb], msc, msh, p.mask_relu, s1, s2);
             }
             if (stats) {
                 s1 = half_sum32(s1);
@@ -548,36 +489,46 @@ inline int bf16_tiles(int h, int w, int cout) {
 // rows of 16 bytes: the epilogue through LDS
 inline bool bf16_wide(bool ybf, int nco, int w) { return ybf && nco == 2 && w % 8 == 0; }
 
-// The entry points' routing: the streaming kernel (lf_conv_bf16s.hip) or the K-chunked one.  The training
-// convolution streams every shape the streaming kernel covers; the inference ones (kBf16Act, kBf16ActMean) only
-// the 32-channel layers with bf16 output (see lf_conv2d_bf16_act).
+// The entry points' routing, asked once per call: the streaming kernel (lf_conv_bf16s.hip) or the K-chunked one, and
+// the partial sums either leaves.  The training convolution streams every shape the streaming kernel covers; the
+// inference ones (kBf16Act, kBf16ActMean) only the 32-channel layers with bf16 output:
+// the 224x224 stage (stem, 32->32): the streaming kernel (resident filter bank, 16-byte accesses).
+// The 64-channel layers of the 112x112 stage stay on the K-chunked kernel: it was well ahead there
+// without a read-modify-write epilogue (1.7 ms against 3.2 ms at 64->64, batch 1,024) and is level with
+// the streaming kernel since that one got 64x4 tiles and per-XCD tile rows (whole forward pass
+// 52.4 k img/s as routed here, 52.7 k with every covered layer on the streaming kernel).
 enum { kBf16Act = 0, kBf16ActMean = 1, kBf16Train = 2 };
-inline bool bf16_streams(int entry, int y_bf16, int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
-    if (entry != kBf16Train && !(y_bf16 && cout == 32)) return false;
-    return lf::conv_bf16s_parts(n, cin, h, w, cout, ksize, x_bf16) > 0;
+struct Bf16Route {
+    bool streams;
+    lf::ConvBf16sPlan s;   // streams: the streaming kernel's plan
+    int units;             // partial sums per image and channel: segments (streaming) or tiles
+    long long parts;       // statistics partials per channel: the streaming grid, or n * tiles
+};
+Bf16Route bf16_route(int entry, int y_bf16, int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
+    Bf16Route r{};
+    if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0) return r;
+    if (entry == kBf16Train || (y_bf16 && cout == 32)) r.s = lf::conv_bf16s_plan(n, cin, h, w, cout, ksize, x_bf16);
+    r.streams = r.s.ok;
+    r.units = r.streams ? r.s.tiles_x * r.s.segs : bf16_tiles(h, w, cout);
+    r.parts = r.streams ? r.s.wgs : (long long)n * r.units;
+    return r;
 }
 
-template <bool XBF, bool YBF, bool TR>
-void launch_conv_bf16(const Bf16ConvArgs& a, int ksize, hipStream_t s) {
+template <int TAPS, bool XBF, bool YBF, bool TR>
+void launch_conv_bf16_taps(const lf::ConvBf16Args& a, hipStream_t s) {
     const int nco = bf16_nco(a.cout);
     dim3 grid(bf16_tiles(a.h, a.w, a.cout), a.cout / (32 * nco), a.n);
-    constexpr bool W = YBF;
-    const bool wide = bf16_wide(YBF, nco, a.w);
-    if (ksize == 3) {
-        if (nco == 2) {
-            if (wide) conv_bf16_kernel<9, 2, bf16_nb(2), XBF, YBF, TR, W><<<grid, kThreads, 0, s>>>(a);
-            else conv_bf16_kernel<9, 2, bf16_nb(2), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
-        } else {
-            conv_bf16_kernel<9, 1, bf16_nb(1), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
-        }
-    } else {
-        if (nco == 2) {
-            if (wide) conv_bf16_kernel<1, 2, bf16_nb(2), XBF, YBF, TR, W><<<grid, kThreads, 0, s>>>(a);
-            else conv_bf16_kernel<1, 2, bf16_nb(2), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
-        } else {
-            conv_bf16_kernel<1, 1, bf16_nb(1), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
-        }
-    }
+    if (nco == 1) conv_bf16_kernel<TAPS, 1, bf16_nb(1), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
+    else if (bf16_wide(YBF, nco, a.w)) conv_bf16_kernel<TAPS, 2, bf16_nb(2), XBF, YBF, TR, YBF><<<grid, kThreads, 0, s>>>(a);
+    else conv_bf16_kernel<TAPS, 2, bf16_nb(2), XBF, YBF, TR, false><<<grid, kThreads, 0, s>>>(a);
+}
+
+template <bool YBF, bool TR>
+void launch_conv_bf16(lf::ConvBf16Args a, int ksize, int x_bf16, hipStream_t s) {
+    a.chunks16 = (a.cin + 15) / 16;
+    a.chunks = (a.chunks16 + kKC - 1) / kKC;
+    if (ksize == 3) x_bf16 ? launch_conv_bf16_taps<9, true, YBF, TR>(a, s) : launch_conv_bf16_taps<9, false, YBF, TR>(a, s);
+    else x_bf16 ? launch_conv_bf16_taps<1, true, YBF, TR>(a, s) : launch_conv_bf16_taps<1, false, YBF, TR>(a, s);
 }
 
 // means[n][c] = scale * sum over the image's partial sums: `unit` layout part[(n * units + u) * c_total + c] (the
@@ -614,61 +565,63 @@ int lf_conv2d_bf16_prep_weights(const float* w_iko, uint16_t* wprep, int cin, in
     return lf::check_launch("lf_conv2d_bf16_prep_weights");
 }
 
+// The one launch path of the bf16 convolutions: validates, fills the arguments and launches the kernel `r` (the
+// caller's bf16_route for `entry`) names.  `a` arrives with the entry's pointers and flags set.
+static int conv_bf16_launch(const char* who, int entry, const Bf16Route& r, lf::ConvBf16Args a, int x_bf16, int y_bf16,
+                            int ksize, lf_stream_t stream) {
+    LF_REQUIRE(a.x && a.wprep && a.y, "%s: null buffer", who);
+    LF_REQUIRE(a.n > 0 && a.cin > 0 && a.h > 0 && a.w > 0 && a.cout > 0, "%s: bad dims", who);
+    LF_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize must be 1 or 3", who);
+    LF_REQUIRE(a.w % 4 == 0, "%s: width must be a multiple of 4 (got %d)", who, a.w);
+    LF_REQUIRE(a.cout % 32 == 0, "%s: cout must be a multiple of 32 (got %d)", who, a.cout);
+    LF_REQUIRE((a.in_scale == nullptr) == (a.in_shift == nullptr), "%s: scale/shift must both be set", who);
+    LF_REQUIRE(a.in_scale == nullptr || a.cin <= kMaxPrologueCin,
+               "%s: a fused prologue takes at most %d input channels (got %d)", who, kMaxPrologueCin, a.cin);
+    LF_REQUIRE((a.out_scale == nullptr) == (a.out_shift == nullptr), "%s: out_scale/out_shift must both be set", who);
+    // 32-bit buffer offsets: one image's input (plus the two staged chunks past its end that the pipeline asks
+    // for and gets zeros back) and the packed weights must each stay below 2 GiB
+    LF_REQUIRE((size_t)(a.cin + 2 * 16 * kKC) * a.h * a.w * (x_bf16 ? 2 : 4) < ((size_t)1 << 31) &&
+                   lf_conv2d_bf16_weight_elems(a.cin, a.cout, ksize) * 2 < ((size_t)1 << 31),
+               "%s: image or weights too large for 32-bit buffer offsets", who);
+    LF_REQUIRE(a.n <= 65535, "%s: batch too large for grid.z", who);
+    LF_REQUIRE(((reinterpret_cast<size_t>(a.x) | reinterpret_cast<size_t>(a.wprep)) & 15) == 0,
+               "%s: x and wprep must be 16-byte aligned", who);
+    hipStream_t s = lf::as_stream(stream);
+    a.stat_tiles = r.parts;
+    if (r.streams) {
+        const int rc = lf::conv_bf16s_launch(a, r.s, ksize, s);
+        if (rc != LF_OK) return rc;
+    } else if (entry != kBf16Act) {
+        launch_conv_bf16<true, true>(a, ksize, x_bf16, s);
+    } else if (y_bf16) {
+        launch_conv_bf16<true, false>(a, ksize, x_bf16, s);
+    } else {
+        launch_conv_bf16<false, false>(a, ksize, x_bf16, s);
+    }
+    return lf::check_launch(who);
+}
+
+// the arguments every entry has
+static lf::ConvBf16Args bf16_args(const void* x, const uint16_t* wprep, void* y, int n, int cin, int h, int w, int cout,
+                                  const float* in_scale, const float* in_shift, int in_relu) {
+    lf::ConvBf16Args a{};
+    a.x = x; a.wprep = wprep; a.y = y; a.n = n; a.cin = cin; a.h = h; a.w = w; a.cout = cout;
+    a.in_scale = in_scale; a.in_shift = in_shift; a.in_relu = in_relu;
+    return a;
+}
+
 int lf_conv2d_bf16_act(const void* x, int x_bf16, const uint16_t* wprep, void* y, int y_bf16, int n, int cin,
                        int h, int w, int cout, int ksize, const float* in_scale, const float* in_shift,
                        int in_relu, const float* out_scale, const float* out_shift, int out_relu,
                        lf_stream_t stream) {
-    LF_REQUIRE(x && wprep && y, "lf_conv2d_bf16: null buffer");
-    LF_REQUIRE(n > 0 && cin > 0 && h > 0 && w > 0 && cout > 0, "lf_conv2d_bf16: bad dims");
-    LF_REQUIRE(ksize == 1 || ksize == 3, "lf_conv2d_bf16: ksize must be 1 or 3");
-    LF_REQUIRE(w % 4 == 0, "lf_conv2d_bf16: width must be a multiple of 4 (got %d)", w);
-    LF_REQUIRE(cout % 32 == 0, "lf_conv2d_bf16: cout must be a multiple of 32 (got %d)", cout);
-    LF_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "lf_conv2d_bf16: scale/shift must both be set");
-    LF_REQUIRE(in_scale == nullptr || cin <= kMaxPrologueCin,
-               "lf_conv2d_bf16: a fused prologue takes at most %d input channels (got %d)", kMaxPrologueCin, cin);
-    LF_REQUIRE((out_scale == nullptr) == (out_shift == nullptr),
-               "lf_conv2d_bf16: out_scale/out_shift must both be set");
-    // 32-bit buffer offsets: one image's input (plus the two staged chunks past its end that the pipeline asks
-    // for and gets zeros back) and the packed weights must each stay below 2 GiB
-    LF_REQUIRE((size_t)(cin + 2 * 16 * kKC) * h * w * (x_bf16 ? 2 : 4) < ((size_t)1 << 31) &&
-                   lf_conv2d_bf16_weight_elems(cin, cout, ksize) * 2 < ((size_t)1 << 31),
-               "lf_conv2d_bf16: image or weights too large for 32-bit buffer offsets");
-    LF_REQUIRE(n <= 65535, "lf_conv2d_bf16: batch too large for grid.z");
-    LF_REQUIRE(((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(wprep)) & 15) == 0,
-               "lf_conv2d_bf16: x and wprep must be 16-byte aligned");
-    hipStream_t s = lf::as_stream(stream);
-    if (bf16_streams(kBf16Act, y_bf16, n, cin, h, w, cout, ksize, x_bf16)) {
-        // the 224x224 stage (stem, 32->32): the streaming kernel (resident filter bank, 16-byte accesses).
-        // The 64-channel layers of the 112x112 stage stay on the K-chunked kernel: it was well ahead there
-        // without a read-modify-write epilogue (1.7 ms against 3.2 ms at 64->64, batch 1,024) and is level with
-        // the streaming kernel since that one got 64x4 tiles and per-XCD tile rows (whole forward pass
-        // 52.4 k img/s as routed here, 52.7 k with every covered layer on the streaming kernel).
-        lf::ConvBf16TrainArgs t{};
-        t.x = x; t.wprep = wprep; t.y = static_cast<uint16_t*>(y); t.n = n; t.cin = cin; t.h = h; t.w = w; t.cout = cout;
-        t.in_scale = in_scale; t.in_shift = in_shift; t.in_relu = in_relu;
-        t.out_scale = out_scale; t.out_shift = out_shift; t.out_relu = out_relu;
-        const int rc = lf::conv_bf16s_launch(t, ksize, x_bf16, s);
-        if (rc != LF_OK) return rc;
-        return lf::check_launch("lf_conv2d_bf16");
-    }
-    Bf16ConvArgs a{};
-    a.x = x; a.wprep = wprep; a.y = y; a.n = n; a.cin = cin; a.h = h; a.w = w; a.cout = cout;
-    a.chunks16 = (cin + 15) / 16;
-    a.chunks = (a.chunks16 + kKC - 1) / kKC;
-    a.in_scale = in_scale; a.in_shift = in_shift; a.in_relu = in_relu;
+    lf::ConvBf16Args a = bf16_args(x, wprep, y, n, cin, h, w, cout, in_scale, in_shift, in_relu);
     a.out_scale = out_scale; a.out_shift = out_shift; a.out_relu = out_relu;
-    if (x_bf16) {
-        if (y_bf16) launch_conv_bf16<true, true, false>(a, ksize, s); else launch_conv_bf16<true, false, false>(a, ksize, s);
-    } else {
-        if (y_bf16) launch_conv_bf16<false, true, false>(a, ksize, s); else launch_conv_bf16<false, false, false>(a, ksize, s);
-    }
-    return lf::check_launch("lf_conv2d_bf16");
+    return conv_bf16_launch("lf_conv2d_bf16", kBf16Act, bf16_route(kBf16Act, y_bf16, n, cin, h, w, cout, ksize, x_bf16),
+                            a, x_bf16, y_bf16, ksize, stream);
 }
 
 long long lf_conv2d_bf16_stats_tiles(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
-    if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0) return 0;
-    const long long parts = lf::conv_bf16s_parts(n, cin, h, w, cout, ksize, x_bf16);
-    return parts > 0 ? parts : (long long)n * bf16_tiles(h, w, cout);
+    return bf16_route(kBf16Train, 1, n, cin, h, w, cout, ksize, x_bf16).parts;
 }
 
 int lf_conv2d_bf16_train(const void* x, int x_bf16, const uint16_t* wprep, uint16_t* y, int n, int cin, int h,
@@ -676,114 +629,52 @@ int lf_conv2d_bf16_train(const void* x, int x_bf16, const uint16_t* wprep, uint1
                          int accumulate, float* tile_part, size_t tile_part_bytes, const float* pivot,
                          const uint16_t* mask_y, const float* mask_scale, const float* mask_shift,
                          int mask_relu, lf_stream_t stream) {
-    LF_REQUIRE(x && wprep && y, "lf_conv2d_bf16_train: null buffer");
-    LF_REQUIRE(n > 0 && cin > 0 && h > 0 && w > 0 && cout > 0, "lf_conv2d_bf16_train: bad dims");
-    LF_REQUIRE(ksize == 1 || ksize == 3, "lf_conv2d_bf16_train: ksize must be 1 or 3");
-    LF_REQUIRE(w % 4 == 0, "lf_conv2d_bf16_train: width must be a multiple of 4 (got %d)", w);
-    LF_REQUIRE(cout % 32 == 0, "lf_conv2d_bf16_train: cout must be a multiple of 32 (got %d)", cout);
-    LF_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "lf_conv2d_bf16_train: scale/shift must both be set");
-    LF_REQUIRE(in_scale == nullptr || cin <= kMaxPrologueCin,
-               "lf_conv2d_bf16_train: a fused prologue takes at most %d input channels (got %d)", kMaxPrologueCin, cin);
-    LF_REQUIRE((size_t)(cin + 2 * 16 * kKC) * h * w * (x_bf16 ? 2 : 4) < ((size_t)1 << 31) &&
-                   lf_conv2d_bf16_weight_elems(cin, cout, ksize) * 2 < ((size_t)1 << 31),
-               "lf_conv2d_bf16_train: image or weights too large for 32-bit buffer offsets");
-    LF_REQUIRE(n <= 65535, "lf_conv2d_bf16_train: batch too large for grid.z");
-    LF_REQUIRE(((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(wprep)) & 15) == 0,
-               "lf_conv2d_bf16_train: x and wprep must be 16-byte aligned");
     LF_REQUIRE(mask_y == nullptr || (tile_part && mask_scale && mask_shift),
                "lf_conv2d_bf16_train: mask_y needs tile_part and mask_scale / mask_shift");
-    const long long tiles = lf_conv2d_bf16_stats_tiles(n, cin, h, w, cout, ksize, x_bf16);
+    const Bf16Route r = bf16_route(kBf16Train, 1, n, cin, h, w, cout, ksize, x_bf16);
     if (tile_part != nullptr) {
-        const size_t need = (size_t)tiles * (size_t)cout * 2 * sizeof(float);
+        const size_t need = (size_t)r.parts * (size_t)cout * 2 * sizeof(float);
         if (tile_part_bytes < need) {
             lf::set_error("lf_conv2d_bf16_train: tile_part %zu bytes < %zu", tile_part_bytes, need);
             return LF_ERR_WORKSPACE;
         }
     }
-    hipStream_t s = lf::as_stream(stream);
-    if (bf16_streams(kBf16Train, 1, n, cin, h, w, cout, ksize, x_bf16)) {
-        lf::ConvBf16TrainArgs t{};
-        t.x = x; t.wprep = wprep; t.y = y; t.n = n; t.cin = cin; t.h = h; t.w = w; t.cout = cout;
-        t.in_scale = in_scale; t.in_shift = in_shift; t.in_relu = in_relu; t.accumulate = accumulate;
-        t.stat_part = tile_part; t.stat_pivot = pivot; t.stat_mask_y = mask_y;
-        t.mask_scale = mask_scale; t.mask_shift = mask_shift; t.mask_relu = mask_relu;
-        const int rc = lf::conv_bf16s_launch(t, ksize, x_bf16, s);
-        if (rc != LF_OK) return rc;
-        return lf::check_launch("lf_conv2d_bf16_train");
-    }
-    Bf16ConvArgs a{};
-    a.x = x; a.wprep = wprep; a.y = y; a.n = n; a.cin = cin; a.h = h; a.w = w; a.cout = cout;
-    a.chunks16 = (cin + 15) / 16;
-    a.chunks = (a.chunks16 + kKC - 1) / kKC;
-    a.in_scale = in_scale; a.in_shift = in_shift; a.in_relu = in_relu;
+    lf::ConvBf16Args a = bf16_args(x, wprep, y, n, cin, h, w, cout, in_scale, in_shift, in_relu);
     a.accumulate = accumulate;
     a.stat_part = tile_part; a.stat_pivot = pivot;
-    a.stat_tiles = tiles;
     a.stat_mask_y = mask_y; a.mask_scale = mask_scale; a.mask_shift = mask_shift; a.mask_relu = mask_relu;
-    if (x_bf16) launch_conv_bf16<true, true, true>(a, ksize, s); else launch_conv_bf16<false, true, true>(a, ksize, s);
-    return lf::check_launch("lf_conv2d_bf16_train");
+    return conv_bf16_launch("lf_conv2d_bf16_train", kBf16Train, r, a, x_bf16, 1, ksize, stream);
+}
+
+// (the same routing as lf_conv2d_bf16_act: the streaming kernel for the 32-channel layers only, so that the
+// stored activation is bit-equal with and without the means)
+static size_t bf16_mean_workspace(const Bf16Route& r, int n, int cout) {
+    return (size_t)n * r.units * cout * (r.streams ? 1 : 2) * sizeof(float);
 }
 
 size_t lf_conv2d_bf16_act_mean_workspace(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
-    if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0) return 0;
-    // (the same routing as lf_conv2d_bf16_act: the streaming kernel for the 32-channel layers only, so that the
-    // stored activation is bit-equal with and without the means)
-    const int units = bf16_streams(kBf16ActMean, 1, n, cin, h, w, cout, ksize, x_bf16)
-                          ? lf::conv_bf16s_units_per_image(n, cin, h, w, cout, ksize, x_bf16) : 0;
-    if (units > 0) return (size_t)n * units * cout * sizeof(float);
-    return (size_t)n * bf16_tiles(h, w, cout) * cout * 2 * sizeof(float);
+    return bf16_mean_workspace(bf16_route(kBf16ActMean, 1, n, cin, h, w, cout, ksize, x_bf16), n, cout);
 }
 
 int lf_conv2d_bf16_act_mean(const void* x, int x_bf16, const uint16_t* wprep, uint16_t* y, int n, int cin, int h, int w,
                             int cout, int ksize, const float* in_scale, const float* in_shift, int in_relu,
                             const float* out_scale, const float* out_shift, int out_relu, float* means,
                             void* workspace, size_t ws_bytes, lf_stream_t stream) {
-    LF_REQUIRE(x && wprep && y && means && workspace, "lf_conv2d_bf16_act_mean: null buffer");
-    LF_REQUIRE(n > 0 && cin > 0 && h > 0 && w > 0 && cout > 0, "lf_conv2d_bf16_act_mean: bad dims");
-    LF_REQUIRE(ksize == 1 || ksize == 3, "lf_conv2d_bf16_act_mean: ksize must be 1 or 3");
-    LF_REQUIRE(w % 4 == 0, "lf_conv2d_bf16_act_mean: width must be a multiple of 4 (got %d)", w);
-    LF_REQUIRE(cout % 32 == 0, "lf_conv2d_bf16_act_mean: cout must be a multiple of 32 (got %d)", cout);
-    LF_REQUIRE((in_scale == nullptr) == (in_shift == nullptr) && (out_scale == nullptr) == (out_shift == nullptr),
-               "lf_conv2d_bf16_act_mean: scale/shift must both be set");
-    LF_REQUIRE(in_scale == nullptr || cin <= kMaxPrologueCin,
-               "lf_conv2d_bf16_act_mean: a fused prologue takes at most %d input channels (got %d)", kMaxPrologueCin, cin);
-    LF_REQUIRE((size_t)(cin + 2 * 16 * kKC) * h * w * (x_bf16 ? 2 : 4) < ((size_t)1 << 31) &&
-                   lf_conv2d_bf16_weight_elems(cin, cout, ksize) * 2 < ((size_t)1 << 31),
-               "lf_conv2d_bf16_act_mean: image or weights too large for 32-bit buffer offsets");
-    LF_REQUIRE(n <= 65535, "lf_conv2d_bf16_act_mean: batch too large for grid.z");
-    LF_REQUIRE(((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(wprep)) & 15) == 0,
-               "lf_conv2d_bf16_act_mean: x and wprep must be 16-byte aligned");
-    const size_t need = lf_conv2d_bf16_act_mean_workspace(n, cin, h, w, cout, ksize, x_bf16);
+    LF_REQUIRE(means && workspace, "lf_conv2d_bf16_act_mean: null buffer");
+    const Bf16Route r = bf16_route(kBf16ActMean, 1, n, cin, h, w, cout, ksize, x_bf16);
+    const size_t need = bf16_mean_workspace(r, n, cout);
     if (ws_bytes < need) {
         lf::set_error("lf_conv2d_bf16_act_mean: workspace %zu < %zu bytes", ws_bytes, need);
         return LF_ERR_WORKSPACE;
     }
-    hipStream_t s = lf::as_stream(stream);
-    float* part = static_cast<float*>(workspace);
-    const float inv = 1.0f / (float)((size_t)h * w);
-    const int units = bf16_streams(kBf16ActMean, 1, n, cin, h, w, cout, ksize, x_bf16)
-                          ? lf::conv_bf16s_units_per_image(n, cin, h, w, cout, ksize, x_bf16) : 0;
-    if (units > 0) {
-        lf::ConvBf16TrainArgs t{};
-        t.x = x; t.wprep = wprep; t.y = y; t.n = n; t.cin = cin; t.h = h; t.w = w; t.cout = cout;
-        t.in_scale = in_scale; t.in_shift = in_shift; t.in_relu = in_relu;
-        t.out_scale = out_scale; t.out_shift = out_shift; t.out_relu = out_relu;
-        t.unit_sums = part;
-        const int rc = lf::conv_bf16s_launch(t, ksize, x_bf16, s);
-        if (rc != LF_OK) return rc;
-        partial_sums_mean_kernel<<<(n * cout + 255) / 256, 256, 0, s>>>(part, means, n, cout, units, 0, inv);
-        return lf::check_launch("lf_conv2d_bf16_act_mean");
-    }
-    Bf16ConvArgs a{};
-    a.x = x; a.wprep = wprep; a.y = y; a.n = n; a.cin = cin; a.h = h; a.w = w; a.cout = cout;
-    a.chunks16 = (cin + 15) / 16;
-    a.chunks = (a.chunks16 + kKC - 1) / kKC;
-    a.in_scale = in_scale; a.in_shift = in_shift; a.in_relu = in_relu;
+    lf::ConvBf16Args a = bf16_args(x, wprep, y, n, cin, h, w, cout, in_scale, in_shift, in_relu);
     a.out_scale = out_scale; a.out_shift = out_shift; a.out_relu = out_relu;
-    const int tiles = bf16_tiles(h, w, cout);
-    a.stat_part = part; a.stat_pivot = nullptr; a.stat_tiles = (long long)n * tiles;
-    if (x_bf16) launch_conv_bf16<true, true, true>(a, ksize, s); else launch_conv_bf16<false, true, true>(a, ksize, s);
-    partial_sums_mean_kernel<<<(n * cout + 255) / 256, 256, 0, s>>>(part, means, n, cout, tiles, 1, inv);
+    float* part = static_cast<float*>(workspace);   // the streaming kernel's unit sums, or tile statistics (pivot 0)
+    (r.streams ? a.unit_sums : a.stat_part) = part;
+    const int rc = conv_bf16_launch("lf_conv2d_bf16_act_mean", kBf16ActMean, r, a, x_bf16, 1, ksize, stream);
+    if (rc != LF_OK) return rc;
+    partial_sums_mean_kernel<<<(n * cout + 255) / 256, 256, 0, lf::as_stream(stream)>>>(
+        part, means, n, cout, r.units, r.streams ? 0 : 1, 1.0f / (float)((size_t)h * w));
     return lf::check_launch("lf_conv2d_bf16_act_mean");
 }
 
@@ -798,19 +689,18 @@ int lf_conv2d_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int x
     out[1] = ksize * ksize;
     out[7] = x_bf16 ? 1 : 0;
     out[8] = ybf;
-    if (bf16_streams(entry, ybf, n, cin, h, w, cout, ksize, x_bf16)) {
-        int sp[8];
-        lf::conv_bf16s_plan(n, cin, h, w, cout, ksize, x_bf16, sp);
+    const Bf16Route r = bf16_route(entry, ybf, n, cin, h, w, cout, ksize, x_bf16);
+    if (r.streams) {
         out[0] = 1;
-        out[2] = sp[0];
-        out[3] = sp[1];
-        out[5] = sp[2];
-        out[6] = sp[3];
-        out[7] = sp[4];
+        out[2] = r.s.ci;
+        out[3] = r.s.nco;
+        out[5] = r.s.tw;
+        out[6] = r.s.th;
+        out[7] = r.s.ci == 16 ? 0 : 1;   // dispatch_s: the 16-channel slot is the fp32 stem input
         out[10] = lf::conv_bf16s_rmw(entry == kBf16Train ? accumulate : 0, entry == kBf16Train && mask) ? 1 : 0;
-        out[11] = sp[5];
-        out[12] = sp[6];
-        out[13] = sp[7];
+        out[11] = r.s.segs > 1 ? 1 : 0;
+        out[12] = r.s.interleave;
+        out[13] = lf::max_units_per_workgroup(n, r.units, r.s.wgs, r.s.interleave) > 1 ? 1 : 0;
         return LF_OK;
     }
     const int nco = bf16_nco(cout);

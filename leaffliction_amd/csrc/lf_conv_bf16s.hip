@@ -36,41 +36,21 @@
 // requested BEFORE the MFMAs), and the statistics of a channel live in one half-wave.
 // Replaces Conv2D forward and its input-gradient (srcs/model/cnn.py:27-29 under the mixed_float16
 // policy of train.py:179-190).
+//
+// Launched by conv_bf16_launch (lf_conv_bf16.hip) for the shapes bf16_route sends here: lf_conv2d_bf16_train for every
+// shape plan_s covers, the inference entries for the 32-channel layers.
 #include "lf_common.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kT = 256;
 
 using lf::bf16_down;
 using lf::bf16_up;
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v.x = (__bf16)lo;
-    v.y = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
-}
-// sum over the 32 lanes of each wave half; the total lands in lane 31 / 63
-__device__ __forceinline__ float half_sum32(float v) {
-    v += dpp_move<0xB1, 0xf>(v);
-    v += dpp_move<0x4E, 0xf>(v);
-    v += dpp_move<0x141, 0xf>(v);
-    v += dpp_move<0x140, 0xf>(v);
-    v += dpp_move<0x142, 0xa>(v);
-    return v;
-}
+using lf::bf16x8;
+using lf::f32x16;
+using lf::u32x2;
+using lf::pack_bf16;
 
 template <int TAPS, int CI, int NCO, int TW, int TH>
 struct SShape {
@@ -95,7 +75,7 @@ struct SShape {
 template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF, bool RMW>
 __global__ __launch_bounds__(kT, (SShape<TAPS, CI, NCO, TW, TH>::LDS <= 52 * 1024 && !RMW)
                                      ? 3 : (SShape<TAPS, CI, NCO, TW, TH>::LDS <= 80 * 1024 ? 2 : 1))
-void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
+void conv_bf16s_kernel(lf::ConvBf16Args p) {
     using S = SShape<TAPS, CI, NCO, TW, TH>;
     static_assert(TW * TH == 256 && TW % 8 == 0, "tile = 4 waves x 64 pixels, whole 8-pixel groups");
     static_assert(XBF || CI == 16, "fp32 input: the stem only (3 channels padded to one 16-channel group)");
@@ -262,7 +242,7 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
 #pragma unroll
                     for (int e = 0; e < G; ++e)
                         *reinterpret_cast<unsigned*>(lp + poff(pi + e, (unsigned)quad >> 1) + 8 * (quad & 1) +
-                                                     4 * (i >> 1)) = pack2(prev[e], v[e]);
+                                                     4 * (i >> 1)) = pack_bf16(prev[e], v[e]);
                 } else {
 #pragma unroll
                     for (int e = 0; e < G; ++e) prev[e] = v[e];
@@ -292,8 +272,8 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
                 if (!XBF) v[3] = 0.f;
             }
             u32x2 o;
-            o.x = pack2(v[0], v[1]);
-            o.y = pack2(v[2], v[3]);
+            o.x = pack_bf16(v[0], v[1]);
+            o.y = pack_bf16(v[2], v[3]);
             int slot = st_slot + pr;
             slot = slot >= PH ? slot - PH : slot;
             const unsigned pi = (unsigned)(slot * PW + (side ? PW - 1 : 0));
@@ -346,7 +326,7 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
             issue(sn, stx0, stf * TH + HALO, TH);
         }
         // the epilogue's read-modify-write operands: requested now, consumed after the MFMAs
-        uint16_t* yb = p.y + (size_t)n * p.cout * hw;
+        uint16_t* yb = static_cast<uint16_t*>(p.y) + (size_t)n * p.cout * hw;
         const int gy = ty0 + erow, gx = tx0 + ecol;
         const bool ok = gy < p.h && gx < p.w;  // the 8-pixel group is inside or outside as a whole (w % 8 == 0)
         const size_t po = ok ? (size_t)gy * p.w + gx : 0;
@@ -464,28 +444,23 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
                 uvec o;
 #pragma unroll
-                for (int e = 0; e < 8; e += 2) o[e / 2] = pack2(v[e], v[e + 1]);
+                for (int e = 0; e < 8; e += 2) o[e / 2] = pack_bf16(v[e], v[e + 1]);
                 if (ok) *reinterpret_cast<uvec*>(yb + (size_t)co * hw + po) = o;
                 if (!stats || !ok) continue;
                 float a = 0.f, b = 0.f;
-                if (!masked) {
+                if (!masked) {   // (one loop per kind of sum: the kind is uniform, the loops are unrolled)
                     const float pv = lst[co];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float d = bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu) - pv;
-                        a += d;
-                        b = fmaf(d, d, b);
-                    }
+                    for (int e = 0; e < 8; ++e)
+                        lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, false, pv, 0.f, 0.f,
+                                            0.f, 0, a, b);
                 } else {
                     const float msc = lst[co], msh = lst[COUT + co];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const float rv = bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu);
                         const unsigned mw = rmask[cb][j][e / 2];
-                        const float yv = bf16_up((e & 1) ? mw >> 16 : mw & 0xffffu);
-                        const float d = (!p.mask_relu || fmaf(yv, msc, msh) > 0.f) ? rv : 0.f;
-                        a += d;
-                        b = fmaf(d, yv, b);
+                        lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, true, 0.f,
+                                            bf16_up((e & 1) ? mw >> 16 : mw & 0xffffu), msc, msh, p.mask_relu, a, b);
                     }
                 }
                 s1[cb][j] += a;
@@ -549,13 +524,8 @@ void conv_bf16s_kernel(lf::ConvBf16TrainArgs p) {
     }
 }
 
-struct SPlan {
-    bool ok;
-    int ci, nco, tw, th, tiles_x, tiles_y, seg_tiles, segs, wgs, interleave;
-};
-
-SPlan plan_s(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
-    SPlan pl{};
+lf::ConvBf16sPlan plan_s(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
+    lf::ConvBf16sPlan pl{};
     pl.ok = false;
     if (cout != 32 && cout != 64) return pl;
     if (w % 8 != 0) return pl;                              // 16-byte rows
@@ -595,7 +565,7 @@ SPlan plan_s(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
 }
 
 template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF, bool RMW>
-int launch_s2(const lf::ConvBf16TrainArgs& a, int wgs, hipStream_t s) {
+int launch_s2(const lf::ConvBf16Args& a, int wgs, hipStream_t s) {
     using S = SShape<TAPS, CI, NCO, TW, TH>;
     static bool raised = false;
     if (!raised) {
@@ -611,13 +581,13 @@ int launch_s2(const lf::ConvBf16TrainArgs& a, int wgs, hipStream_t s) {
 }
 
 template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF>
-int launch_s(const lf::ConvBf16TrainArgs& a, int wgs, hipStream_t s) {
+int launch_s(const lf::ConvBf16Args& a, int wgs, hipStream_t s) {
     return lf::conv_bf16s_rmw(a.accumulate, a.stat_mask_y != nullptr) ? launch_s2<TAPS, CI, NCO, TW, TH, XBF, true>(a, wgs, s)
                                                       : launch_s2<TAPS, CI, NCO, TW, TH, XBF, false>(a, wgs, s);
 }
 
 template <int TW, int TH>
-int dispatch_s(const SPlan& pl, int ksize, const lf::ConvBf16TrainArgs& a, hipStream_t s) {
+int dispatch_s(const lf::ConvBf16sPlan& pl, int ksize, const lf::ConvBf16Args& a, hipStream_t s) {
     if (pl.ci == 16) return launch_s<9, 16, 1, TW, TH, false>(a, pl.wgs, s);
     if (ksize == 3) {
         if (pl.ci == 32 && pl.nco == 1) return launch_s<9, 32, 1, TW, TH, true>(a, pl.wgs, s);
@@ -636,39 +606,17 @@ int dispatch_s(const SPlan& pl, int ksize, const lf::ConvBf16TrainArgs& a, hipSt
 
 namespace lf {
 
-long long conv_bf16s_parts(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
-    const SPlan pl = plan_s(n, cin, h, w, cout, ksize, x_bf16);
-    return pl.ok ? pl.wgs : 0;
+ConvBf16sPlan conv_bf16s_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
+    return plan_s(n, cin, h, w, cout, ksize, x_bf16);
 }
 
-int conv_bf16s_units_per_image(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
-    const SPlan pl = plan_s(n, cin, h, w, cout, ksize, x_bf16);
-    return pl.ok ? pl.tiles_x * pl.segs : 0;
-}
-
-int conv_bf16s_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16, int* out) {
-    const SPlan pl = plan_s(n, cin, h, w, cout, ksize, x_bf16);
-    if (!pl.ok) return 0;
-    out[0] = pl.ci;
-    out[1] = pl.nco;
-    out[2] = pl.tw;
-    out[3] = pl.th;
-    out[4] = pl.ci == 16 ? 0 : 1;   // dispatch_s: the 16-channel slot is the fp32 stem input
-    out[5] = pl.segs > 1 ? 1 : 0;
-    out[6] = pl.interleave;
-    out[7] = max_units_per_workgroup(n, pl.tiles_x * pl.segs, pl.wgs, pl.interleave) > 1 ? 1 : 0;
-    return 1;
-}
-
-int conv_bf16s_launch(ConvBf16TrainArgs a, int ksize, int x_bf16, hipStream_t s) {
-    const SPlan pl = plan_s(a.n, a.cin, a.h, a.w, a.cout, ksize, x_bf16);
+int conv_bf16s_launch(ConvBf16Args a, const ConvBf16sPlan& pl, int ksize, hipStream_t s) {
     if (!pl.ok) {
         set_error("lf_conv2d_bf16_train: shape not covered by the streaming kernel");
         return LF_ERR_INVALID;
     }
     a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y; a.seg_tiles = pl.seg_tiles; a.segs = pl.segs;
     a.interleave = pl.interleave;
-    a.stat_tiles = pl.wgs;
     if (pl.tw == 64) return dispatch_s<64, 4>(pl, ksize, a, s);
     return pl.tw == 32 ? dispatch_s<32, 8>(pl, ksize, a, s) : dispatch_s<16, 16>(pl, ksize, a, s);
 }

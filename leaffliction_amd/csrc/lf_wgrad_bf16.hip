@@ -31,31 +31,24 @@
 // of raw bf16 per thread with 16-byte accesses).
 //
 // Partial sums: every workgroup owns a (32*CIB x 32*COB) weight block and a range of (image,
-// tile) items and writes one fp32 slab; lf_slab_reduce_f32 adds the slabs in a fixed order
-// (deterministic, no float atomics), exactly like the fp32 path.
+// tile) items and writes one fp32 slab; lf::reduce_slabs adds the slabs in a fixed order
+// (deterministic, no float atomics): the fp32 path's reduction.  lf_conv2d_wgrad_bf16 is the only entry and
+// always runs wgrad_bf16_kernel (the convolutions' bf16_route does not apply to it).
 #include "lf_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kSumT = 256;
 
 using WgBf16Args = lf::WgradBf16Args;
 
 using lf::bf16_up;
 
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v.x = (__bf16)lo;  // round to nearest even
-    v.y = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
+using lf::bf16x8;
+using lf::f32x16;
+using lf::u32x2;
+using lf::pack_bf16;
 
 // byte offset of (pixel, channel quad) inside one [pixel][32 channels] image
 __device__ __forceinline__ unsigned img_off(unsigned pixel, unsigned quad) {
@@ -300,7 +293,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
                         if (p.dy_out != nullptr && blockIdx.y == 0) {
                             uvec o;
 #pragma unroll
-                            for (int e = 0; e < G; e += 2) o[e / 2] = pack2(gv[e], gv[e + 1]);
+                            for (int e = 0; e < G; e += 2) o[e / 2] = pack_bf16(gv[e], gv[e + 1]);
                             *reinterpret_cast<uvec*>(p.dy_out + ((size_t)n * p.cout + co0 + c) * hw +
                                                      (size_t)(ty0 + row) * p.w + tx0 + G * pg) = o;
                         }
@@ -310,7 +303,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
 #pragma unroll
                     for (int e = 0; e < G; ++e)
                         *reinterpret_cast<unsigned*>(img + img_off(pd + e, quad & 7) + 4 * (i >> 1)) =
-                            pack2(prev[e], gv[e]);
+                            pack_bf16(prev[e], gv[e]);
                 } else {
 #pragma unroll
                     for (int e = 0; e < G; ++e) prev[e] = gv[e];
@@ -326,8 +319,8 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = (4 * qd + i < 27) ? rs[(4 * qd + i < 27) ? 4 * qd + i : 0] : 0.f;
                 u32x2 o;
-                o.x = pack2(v[0], v[1]);
-                o.y = pack2(v[2], v[3]);
+                o.x = pack_bf16(v[0], v[1]);
+                o.y = pack_bf16(v[2], v[3]);
                 *reinterpret_cast<u32x2*>(lx + img_off(pd, qd)) = o;
             }
         } else {
@@ -366,7 +359,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
 #pragma unroll
                         for (int e = 0; e < G; ++e)
                             *reinterpret_cast<unsigned*>(img + img_off(pi + e, quad & 7) + 4 * (i >> 1)) =
-                                pack2(prev[e], v[e]);
+                                pack_bf16(prev[e], v[e]);
                     } else {
 #pragma unroll
                         for (int e = 0; e < G; ++e) prev[e] = v[e];
@@ -391,8 +384,8 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
                         }
                 }
                 u32x2 o;
-                o.x = pack2(v[0], v[1]);
-                o.y = pack2(v[2], v[3]);
+                o.x = pack_bf16(v[0], v[1]);
+                o.y = pack_bf16(v[2], v[3]);
                 unsigned char* img = lx + (quad >> 3) * (S::XPIX * 64);
                 int slot = rb + pr;
                 slot = slot >= S::NSLOT ? slot - S::NSLOT : slot;
@@ -541,21 +534,6 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
     }
 }
 
-// dst[g][i] = sum over slabs s in group g of part[s][i]; with one group this is the final
-// dw = beta*dw + sum.  Fixed order -> deterministic.
-__global__ __launch_bounds__(kSumT) void slab_sum_kernel(const float* __restrict__ part, float* __restrict__ dst,
-                                                      size_t count, int nslabs, int per_group, float beta,
-                                                      int final_pass) {
-    const int g = blockIdx.y;
-    const int s0 = g * per_group, s1 = min(s0 + per_group, nslabs);
-    for (size_t i = (size_t)blockIdx.x * kSumT + threadIdx.x; i < count; i += (size_t)gridDim.x * kSumT) {
-        float s = 0.f;
-        for (int k = s0; k < s1; ++k) s += part[(size_t)k * count + i];
-        float* o = dst + (size_t)g * count + i;
-        *o = (final_pass && beta != 0.f) ? fmaf(beta, *o, s) : s;
-    }
-}
-
 struct WgBf16Plan {
     int variant;  // index into the launch table
     int tw, th, cib, cob, stem;
@@ -598,8 +576,6 @@ WgBf16Plan plan_wgrad_bf16(int n, int cin, int cout, int h, int w, int ksize) {
     pl.interleave = (pl.splits % 8 == 0 && n >= 8 && pl.gy * pl.gz == 1) ? 1 : 0;
     return pl;
 }
-
-constexpr int kSumGroup = 32;
 
 template <int TAPS, int TW, int TH, int CIB, int COB, bool STEM, int G, int WPRQ = 0>
 int launch_wg(const WgBf16Args& a, dim3 grid, hipStream_t s) {
@@ -668,8 +644,7 @@ size_t lf_conv2d_wgrad_bf16_workspace(int n, int cin, int h, int w, int cout, in
     if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || cout % 32 != 0) return 0;
     const WgBf16Plan pl = plan_wgrad_bf16(n, cin, cout, h, w, ksize);
     const size_t count = (size_t)cin * ksize * ksize * cout;
-    const size_t groups = (pl.splits + kSumGroup - 1) / kSumGroup;
-    return ((size_t)pl.splits + groups) * count * sizeof(float);
+    return ((size_t)pl.splits + lf::slab_groups(pl.splits)) * count * sizeof(float);
 }
 
 int lf_conv2d_wgrad_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int* out) {
@@ -683,7 +658,7 @@ int lf_conv2d_wgrad_bf16_plan(int n, int cin, int h, int w, int cout, int ksize,
     out[8] = pl.segs > 1 ? 1 : 0;
     out[9] = pl.interleave;
     out[10] = lf::max_units_per_workgroup(n, pl.tiles_x * pl.segs, pl.splits, pl.interleave) > 1 ? 1 : 0;
-    out[11] = pl.splits > kSumGroup ? 2 : 1;
+    out[11] = lf::slab_stages(pl.splits);
     out[12] = pl.seg_tiles < 3 ? pl.seg_tiles : 3;   // tiles per unit: 1, 2, or 3+ (the in-loop issue of tile i + 2)
     return LF_OK;
 }
@@ -734,18 +709,7 @@ int lf_conv2d_wgrad_bf16(const void* x, const uint16_t* g, const uint16_t* bn_y,
     else
         rc = ksize == 3 ? dispatch_wg<9>(k, a, grid, s) : dispatch_wg<1>(k, a, grid, s);
     if (rc != LF_OK) return rc;
-    // slabs -> dw, fixed order
-    const size_t count = (size_t)cin * ksize * ksize * cout;
-    float* part = static_cast<float*>(workspace);
-    const unsigned gx = lf::stream_grid(count, kSumT, 1024);
-    if (pl.splits <= kSumGroup) {
-        slab_sum_kernel<<<dim3(gx, 1), kSumT, 0, s>>>(part, dw, count, pl.splits, pl.splits, 0.f, 1);
-    } else {
-        const int groups = (pl.splits + kSumGroup - 1) / kSumGroup;
-        float* stage = part + (size_t)pl.splits * count;
-        slab_sum_kernel<<<dim3(gx, groups), kSumT, 0, s>>>(part, stage, count, pl.splits, kSumGroup, 0.f, 0);
-        slab_sum_kernel<<<dim3(gx, 1), kSumT, 0, s>>>(stage, dw, count, groups, groups, 0.f, 1);
-    }
+    lf::reduce_slabs(static_cast<float*>(workspace), dw, (size_t)cin * ksize * ksize * cout, pl.splits, 0.f, s);
     return lf::check_launch("lf_conv2d_wgrad_bf16");
 }
 
