@@ -18,10 +18,19 @@
 
 namespace {
 
+// ===========================================================================
+// Shared by the filters below: borders and Sobel, the OpenCV pixel rules (8-bit HSV, 8-bit L*a*b*, the plant
+// predicate), Canny, min / max reductions, bit planes (morphology, runs, connected components), host utilities.
+// ===========================================================================
 constexpr int kBlock = 256;
 constexpr int kPxPerThread = 8;  // passes that end in a per-image min / max: fewer, fatter workgroups
 constexpr int kHystThreads = 1024;
+constexpr int kFuseT = 1024;     // the fused one-workgroup-per-image kernels
+constexpr int kMaskT = 256;      // make_mask_post_kernel, brown_spots_kernel
 constexpr unsigned kInfBits = 0x7f800000u;
+constexpr int kLabCbrtSize = 256 * 3 / 2 * 8;   // LAB_CBRT_TAB_SIZE_B
+constexpr int kSeMax = 32;
+constexpr int kFlagFallback = 1, kFlagBound = 4;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -52,24 +61,103 @@ __device__ __forceinline__ Sob sobel_at(const uint8_t* g, int w, int y0, int y1,
     return s;
 }
 
-// Per-image min / max of non-negative floats through their bit patterns (monotone as uint):
-// wave shuffle, then the four waves through LDS, one atomic pair per workgroup.
+__device__ __forceinline__ unsigned gray_px_f(int r, int g, int b) {   // cv2 RGB2GRAY, 14-bit fixed point (lf_augment.hip)
+    return (unsigned)(r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;
+}
+
+// ---- pixel rules.  The tables live in LDS; the whole workgroup fills them and synchronises afterwards.
+struct HsvTabs {   // the divisor tables of OpenCV's 8-bit RGB2HSV
+    int sdiv[256], hdiv[256];
+    __device__ __forceinline__ void fill(int nthreads) {
+        for (int i = threadIdx.x; i < 256; i += nthreads) {
+            sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
+            hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
+        }
+    }
+};
+
+struct LabTabs {   // sRGBGammaTab_b and LabCbrtTab_b of color_lab.cpp, as lab_tables_host builds them
+    uint16_t gam[256], cbr[kLabCbrtSize];
+    __device__ __forceinline__ void fill(const uint16_t* __restrict__ lab_tabs, int nthreads) {
+        for (int i = threadIdx.x; i < 256; i += nthreads) gam[i] = lab_tabs[i];
+        for (int i = threadIdx.x; i < kLabCbrtSize; i += nthreads) cbr[i] = lab_tabs[256 + i];
+    }
+};
+
+// 8-bit HSV (color_hsv: H in [0, 180))
+__device__ __forceinline__ void hsv_px(const HsvTabs& T, int r, int g, int b, int& hh, int& s, int& v) {
+    v = max(r, max(g, b));
+    const int vmin = min(r, min(g, b)), diff = v - vmin;
+    const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
+    s = (__mul24(diff, T.sdiv[v]) + (1 << 11)) >> 12;
+    hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
+    hh = (__mul24(hh, T.hdiv[diff]) + (1 << 11)) >> 12;
+    hh += hh < 0 ? 180 : 0;
+}
+
+// 8-bit L*a*b* (color_lab RGB2Lab_b)
+__device__ __forceinline__ void lab_px(const LabTabs& T, int r, int g, int b, int& L, int& la, int& lb) {
+    const int R = T.gam[r], G = T.gam[g], B = T.gam[b];
+    const int fx = T.cbr[(R * 1777 + G * 1541 + B * 778 + 2048) >> 12];
+    const int fy = T.cbr[(R * 871 + G * 2929 + B * 296 + 2048) >> 12];
+    const int fz = T.cbr[(R * 73 + G * 448 + B * 3575 + 2048) >> 12];
+    L = clampi((296 * fy - 1336934 + 16384) >> 15, 0, 255);
+    la = clampi((500 * (fx - fy) + 4194304 + 16384) >> 15, 0, 255);
+    lb = clampi((200 * (fy - fz) + 4194304 + 16384) >> 15, 0, 255);
+}
+
+// the HSV brown test of blur.py:47-53, brown.py and mask.py's brown extension
+__device__ __forceinline__ bool brown_hsv(const HsvTabs& T, int r, int g, int b, int hue_lo, int hue_hi, int s_min,
+                                          int v_max) {
+    int hh, s, v;
+    hsv_px(T, r, g, b, hh, s, v);
+    return hh >= hue_lo && hh <= hue_hi && s >= s_min && v <= v_max;
+}
+
+// The per-pixel predicate of _create_inclusive_mask for pixel (y, x) = q of an h x w image: tex = gray - blurred
+// gray, is_edge(q) = whether pixel q is a Canny edge (the 3x3 ellipse dilation of the edges is taken here).
+template <typename IsEdge>
+__device__ __forceinline__ bool plant_px(const HsvTabs& H, const LabTabs& T, int r, int g, int b, int tex, int y,
+                                         int x, int h, int w, int hue_lo, int hue_hi, IsEdge is_edge) {
+    int hh, s, v, L, la, lb;
+    hsv_px(H, r, g, b, hh, s, v);
+    lab_px(T, r, g, b, L, la, lb);
+    const bool strong_green = hh >= hue_lo && hh <= hue_hi && s >= 30 && v >= 30;
+    // uint8 planes: r + 15 wraps (mask.py:759-763)
+    const bool dominant = g > ((r + 15) & 255) || g > ((b + 15) & 255) ||
+                          (g > ((r + 5) & 255) && g > ((b + 5) & 255) && s >= 20);
+    const bool lab_green = la <= 125 && lb >= 120 && L >= 20 && L <= 240;
+    const int q = y * w + x;
+    const bool edge = is_edge(q) || (x > 0 && is_edge(q - 1)) || (x < w - 1 && is_edge(q + 1)) ||
+                      (y > 0 && is_edge(q - w)) || (y < h - 1 && is_edge(q + w));
+    const bool background = (s <= 25 && v >= 50 && v <= 220) ||
+                            (hh >= 120 && hh <= 160 && s >= 20 && r > g && b > g) ||
+                            (s <= 15 && (tex < 0 ? -tex : tex) < 10);
+    return (strong_green || dominant || lab_green || edge) && !background;
+}
+
+// ---- per-image min / max of non-negative floats through their bit patterns (monotone as uint)
 struct MinMax {
     unsigned lo = kInfBits, hi = 0u;
     __device__ __forceinline__ void take(float v) {
         lo = min(lo, __float_as_uint(v));
         hi = max(hi, __float_as_uint(v));
     }
+    __device__ __forceinline__ void reduce_wave() {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            lo = min(lo, (unsigned)__shfl_xor((int)lo, off, 64));
+            hi = max(hi, (unsigned)__shfl_xor((int)hi, off, 64));
+        }
+    }
 };
 
+// kBlock threads, many workgroups per image: wave shuffle, then the four waves through LDS, one atomic pair per
+// workgroup.
 __device__ __forceinline__ void minmax_publish(MinMax r, unsigned* mn, unsigned* mx) {
     __shared__ unsigned wlo[kBlock / 64], whi[kBlock / 64];
+    r.reduce_wave();
     unsigned lo = r.lo, hi = r.hi;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = min(lo, (unsigned)__shfl_xor((int)lo, off, 64));
-        hi = max(hi, (unsigned)__shfl_xor((int)hi, off, 64));
-    }
     if ((threadIdx.x & 63) == 0) {
         wlo[threadIdx.x >> 6] = lo;
         whi[threadIdx.x >> 6] = hi;
@@ -84,6 +172,27 @@ __device__ __forceinline__ void minmax_publish(MinMax r, unsigned* mn, unsigned*
         atomicMin(mn, lo);
         atomicMax(mx, hi);
     }
+}
+
+// kFuseT threads, one workgroup per image: the result in lohi[0..1]
+__device__ __forceinline__ void minmax_block(MinMax r, unsigned* wscratch, unsigned* lohi) {
+    r.reduce_wave();
+    unsigned lo = r.lo, hi = r.hi;
+    __syncthreads();   // wscratch may still be read from the previous reduction
+    if ((threadIdx.x & 63) == 0) {
+        wscratch[2 * (threadIdx.x >> 6)] = lo;
+        wscratch[2 * (threadIdx.x >> 6) + 1] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kFuseT / 64; ++k) {
+            lo = min(lo, wscratch[2 * k]);
+            hi = max(hi, wscratch[2 * k + 1]);
+        }
+        lohi[0] = lo;
+        lohi[1] = hi;
+    }
+    __syncthreads();
 }
 
 // cv2.normalize(.., 0, 255, NORM_MINMAX): scale / shift in double, applied as float32 fma.
@@ -101,42 +210,34 @@ __device__ __forceinline__ uint8_t trunc_u8(float v) {  // numpy float32 -> uint
     return (uint8_t)(i < 0 ? 0 : (i > 255 ? 255 : i));
 }
 
-__global__ void minmax_init_kernel(unsigned* mm, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n * 6) mm[i] = (i & 1) ? 0u : kInfBits;  // (min, max) x {gradient, colour diff, saliency}
-}
-
-// Sobel of the gray plane: dx^2 + dy^2 and (dx, dy) with BORDER_REPLICATE for Canny
-// (canny.cpp), sqrt(dx^2 + dy^2) with BORDER_REFLECT_101 for cv2.Sobel + cv2.magnitude.
-__global__ __launch_bounds__(kBlock) void sal_sobel_kernel(const uint8_t* __restrict__ gray,
-                                                           int32_t* __restrict__ mag2,
-                                                           uint32_t* __restrict__ dxdy,
-                                                           float* __restrict__ gmag,
-                                                           unsigned* __restrict__ mm, int h, int w) {
-    const unsigned n = blockIdx.y;
-    const int hw = h * w;
-    const uint8_t* g = gray + (size_t)n * hw;
-    MinMax mmx;
-    for (int k = 0; k < kPxPerThread; ++k) {
-        const int p = (blockIdx.x * kPxPerThread + k) * kBlock + threadIdx.x;
-        if (p >= hw) break;
-        const int y = p / w, x = p - y * w;
-        const Sob s = sobel_at(g, w, clampi(y - 1, 0, h - 1), y, clampi(y + 1, 0, h - 1),
-                               clampi(x - 1, 0, w - 1), x, clampi(x + 1, 0, w - 1));
-        mag2[(size_t)n * hw + p] = __mul24(s.dx, s.dx) + __mul24(s.dy, s.dy);  // |d| <= 1020
-        dxdy[(size_t)n * hw + p] = ((unsigned)s.dx & 0xffffu) | ((unsigned)s.dy << 16);
-        Sob r = s;
-        if (x == 0 || y == 0 || x == w - 1 || y == h - 1)
-            r = sobel_at(g, w, reflect101i(y - 1, h), y, reflect101i(y + 1, h), reflect101i(x - 1, w), x,
-                         reflect101i(x + 1, w));
-        const float gm = __fsqrt_rn((float)(__mul24(r.dx, r.dx) + __mul24(r.dy, r.dy)));  // < 2^24: exact
-        gmag[(size_t)n * hw + p] = gm;
-        mmx.take(gm);
+// ---- Canny
+// Non-maximum suppression + double threshold for the pixel (y, x) of magnitude m: the map value 1 (no edge),
+// 0 (weak), 2 (strong).  grad() is the pixel's (dx, dy), asked for only above the low threshold; at(y, x) is the
+// magnitude of a neighbour.
+template <typename Grad, typename At>
+__device__ __forceinline__ uint8_t canny_px(int m, int y, int x, int low, int high, Grad grad, At at) {
+    if (m <= low) return 1;
+    const Sob d = grad();
+    const int xs = d.dx, ys = d.dy;
+    const int ax = xs < 0 ? -xs : xs;
+    const int ay = (ys < 0 ? -ys : ys) << 15;
+    const int tg22x = __mul24(ax, 13573);  // tan(22.5 deg) in 15-bit fixed point
+    bool keep;
+    if (ay < tg22x) {
+        keep = m > at(y, x - 1) && m >= at(y, x + 1);
+    } else {
+        const int tg67x = tg22x + (ax << 16);
+        if (ay > tg67x) {
+            keep = m > at(y - 1, x) && m >= at(y + 1, x);
+        } else {
+            const int s = (xs ^ ys) < 0 ? 1 : -1;
+            keep = m > at(y - 1, x - s) && m > at(y + 1, x + s);
+        }
     }
-    minmax_publish(mmx, mm + n * 6 + 0, mm + n * 6 + 1);
+    return keep ? (m > high ? 2 : 0) : 1;
 }
 
-// Non-maximum suppression + double threshold: map = 1 (no edge), 0 (weak), 2 (strong).
+// The multi-launch form, on the stored magnitude and (dx, dy) planes.
 __global__ __launch_bounds__(kBlock) void canny_nms_kernel(const int32_t* __restrict__ mag2,
                                                            const uint32_t* __restrict__ dxdy,
                                                            uint8_t* __restrict__ map, int h, int w,
@@ -147,32 +248,14 @@ __global__ __launch_bounds__(kBlock) void canny_nms_kernel(const int32_t* __rest
     if (p >= hw) return;
     const int32_t* mg = mag2 + (size_t)n * hw;
     const int y = p / w, x = p - y * w;
+    auto grad = [&]() -> Sob {
+        const unsigned pk = dxdy[(size_t)n * hw + p];
+        return Sob{(int)(short)(pk & 0xffffu), (int)(short)(pk >> 16)};
+    };
     auto at = [&](int yy, int xx) -> int {  // the magnitude buffer has a zero frame
         return (yy < 0 || yy >= h || xx < 0 || xx >= w) ? 0 : mg[yy * w + xx];
     };
-    const int m = mg[p];
-    uint8_t out = 1;
-    if (m > low) {
-        const unsigned pk = dxdy[(size_t)n * hw + p];
-        const int xs = (int)(short)(pk & 0xffffu), ys = (int)(short)(pk >> 16);
-        const int ax = xs < 0 ? -xs : xs;
-        const int ay = (ys < 0 ? -ys : ys) << 15;
-        const int tg22x = __mul24(ax, 13573);  // tan(22.5 deg) in 15-bit fixed point
-        bool keep;
-        if (ay < tg22x) {
-            keep = m > at(y, x - 1) && m >= at(y, x + 1);
-        } else {
-            const int tg67x = tg22x + (ax << 16);
-            if (ay > tg67x) {
-                keep = m > at(y - 1, x) && m >= at(y + 1, x);
-            } else {
-                const int s = (xs ^ ys) < 0 ? 1 : -1;
-                keep = m > at(y - 1, x - s) && m > at(y + 1, x + s);
-            }
-        }
-        if (keep) out = m > high ? 2 : 0;
-    }
-    map[(size_t)n * hw + p] = out;
+    map[(size_t)n * hw + p] = canny_px(mg[p], y, x, low, high, grad, at);
 }
 
 // Hysteresis: one workgroup per image sweeps the map until no weak pixel next to a strong one
@@ -215,6 +298,557 @@ __global__ __launch_bounds__(kHystThreads) void canny_hysteresis_kernel(uint8_t*
         __syncthreads();
     } while (changed);
     for (int p = threadIdx.x; p < hw; p += kHystThreads) gm[p] = m[p] == 2 ? 255 : 0;
+}
+
+// ===========================================================================
+// Round 3: the per-image middle of both filters in ONE workgroup per image, planes resident in LDS.
+//
+// Both multi-launch chains spend their time in launches and in round trips of small planes through L2 / HBM (13
+// launches and 20 bytes of intermediates per pixel for the saliency filter).  A 224 x 224 gray plane is 50 KB: the gray
+// plane, the Canny map and the bit planes of the brown regions of one image fit the 160 KB of a CU together, and
+// everything the old kernels kept in 4-byte planes (squared gradient, (dx, dy), gradient magnitude, colour
+// difference, saliency) is cheaper to RECOMPUTE from the gray plane in LDS / the two RGB images in L2 than to store.
+// What stays outside: the two Gaussian blurs (the i8-MFMA kernel of lf_blur_mfma.hip) and the final masking pass.
+// The arithmetic is the old kernels' (the bit-exact tests are unchanged).
+// ===========================================================================
+// Canny's non-maximum suppression + double threshold on a gray plane in LDS: map = 1 (no edge), 0 (weak),
+// 2 (strong).  L1: |dx| + |dy| (cv2.Canny default), else dx^2 + dy^2 against squared thresholds.  The gradient of a
+// neighbour is recomputed from the plane (8 LDS bytes) instead of being read from a 4-byte plane in memory.
+template <bool L1>
+__device__ __forceinline__ void canny_nms_lds(const uint8_t* gray, uint8_t* emap, int h, int w, int low, int high) {
+    const int hw = h * w;
+    auto sob = [&](int y, int x) -> Sob {
+        return sobel_at(gray, w, clampi(y - 1, 0, h - 1), y, clampi(y + 1, 0, h - 1), clampi(x - 1, 0, w - 1), x,
+                        clampi(x + 1, 0, w - 1));
+    };
+    auto mag = [&](const Sob s) -> int {
+        return L1 ? (s.dx < 0 ? -s.dx : s.dx) + (s.dy < 0 ? -s.dy : s.dy) : __mul24(s.dx, s.dx) + __mul24(s.dy, s.dy);
+    };
+    auto at = [&](int yy, int xx) -> int {  // the magnitude buffer has a zero frame
+        return (yy < 0 || yy >= h || xx < 0 || xx >= w) ? 0 : mag(sob(yy, xx));
+    };
+    const float inv_w = 1.0f / (float)w;
+    for (int p = threadIdx.x; p < hw; p += kFuseT) {
+        int y = (int)((float)p * inv_w);
+        int x = p - __mul24(y, w);
+        if (x < 0) { --y; x += w; } else if (x >= w) { ++y; x -= w; }
+        const Sob s = sob(y, x);
+        emap[p] = canny_px(mag(s), y, x, low, high, [&]() -> Sob { return s; }, at);
+    }
+    __syncthreads();
+}
+
+// Hysteresis on the map in LDS (1 = no edge, 0 = weak, 2 = strong; 2 = edge afterwards): a weak pixel with a strong
+// 8-neighbour becomes strong, until nothing changes.  On bit planes — strong bits S, weak bits W, one 32-pixel word
+// per thread and sweep: S |= W & dilate3x3(S) — instead of one pixel per thread with nine byte reads: a sweep over a
+// 224 x 224 map is 1,792 words, and noisy images need dozens of sweeps (the byte sweeps were most of the fused
+// kernels' time: 0.4 ms per image).  Rows are `wpr` words wide (two per 64-pixel segment, as the ballots deliver them).
+__device__ __forceinline__ void canny_hysteresis_lds(uint8_t* m, unsigned* sb, unsigned* wb, int h, int w, int wpr,
+                                                     int* changed) {
+    const int spr = wpr / 2;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int seg = wv; seg < h * spr; seg += kFuseT / 64) {
+        const int y = seg / spr, sx = seg - y * spr, x = sx * 64 + lane;
+        const uint8_t v = x < w ? m[y * w + x] : 1;
+        const unsigned long long s = __ballot(v == 2), wk = __ballot(v == 0);
+        if (lane == 0) {
+            sb[y * wpr + 2 * sx] = (unsigned)s;
+            sb[y * wpr + 2 * sx + 1] = (unsigned)(s >> 32);
+            wb[y * wpr + 2 * sx] = (unsigned)wk;
+            wb[y * wpr + 2 * sx + 1] = (unsigned)(wk >> 32);
+        }
+    }
+    do {
+        __syncthreads();
+        if (threadIdx.x == 0) *changed = 0;
+        __syncthreads();
+        bool any = false;
+        for (int i = threadIdx.x; i < h * wpr; i += kFuseT) {
+            const unsigned weak = wb[i] & ~sb[i];
+            if (weak == 0u) continue;
+            const int y = i / wpr, xw = i - y * wpr;
+            unsigned nb = 0;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+                const int yy = y + dy;
+                if (yy < 0 || yy >= h) continue;
+                const unsigned* row = sb + yy * wpr;
+                const unsigned c = row[xw], pv = xw > 0 ? row[xw - 1] : 0u, nx = xw < wpr - 1 ? row[xw + 1] : 0u;
+                nb |= c | (c << 1) | (pv >> 31) | (c >> 1) | (nx << 31);
+            }
+            const unsigned grow = weak & nb;   // (bits past column w are never weak)
+            if (grow) {
+                sb[i] |= grow;                 // in place: growth is monotone, the fixed point is the same
+                any = true;
+            }
+        }
+        if (any) *changed = 1;
+        __syncthreads();
+    } while (*changed);
+    for (int seg = wv; seg < h * spr; seg += kFuseT / 64) {
+        const int y = seg / spr, sx = seg - y * spr, x = sx * 64 + lane;
+        if (x < w) m[y * w + x] = (sb[y * wpr + (x >> 5)] >> (x & 31) & 1u) ? 2 : 1;
+    }
+    __syncthreads();
+}
+
+// ---- bit planes: one bit per pixel, rows of `wpr` 32-bit words (2 * ceil(w / 64) where ballots deliver them,
+// ceil(w / 32) in make_mask and the brown-spot filter)
+struct BitView {
+    int h, w, wpr;
+};
+
+__device__ __forceinline__ unsigned valid_bits(const BitView& G, int xw) {
+    const int used = (G.w + 31) >> 5;
+    const unsigned last = (G.w & 31) ? ((1u << (G.w & 31)) - 1u) : 0xffffffffu;
+    return xw < used - 1 ? 0xffffffffu : (xw == used - 1 ? last : 0u);
+}
+
+__device__ __forceinline__ bool bit_at(const BitView& G, const unsigned* pl, int x, int y) {
+    if ((unsigned)x >= (unsigned)G.w || (unsigned)y >= (unsigned)G.h) return false;
+    return (pl[y * G.wpr + (x >> 5)] >> (x & 31)) & 1u;
+}
+
+struct SeRows {   // a structuring element as per-row column ranges relative to its anchor
+    int k, ay;
+    signed char lo[kSeMax], hi[kSeMax];   // lo > hi: empty row
+};
+
+// dst = dilate / erode(src) by an element of k rows anchored at row ay, rows(r, lo, hi) giving row r's column range
+// relative to the anchor (lo > hi: empty); pixels outside the image never win, i.e. an erosion is the dilation of
+// the complement taken INSIDE the image.  Bits past column w stay 0.  UNROLL: 1 for an element known at run time; k
+// for one known at compile time, whose loops then unroll into constant funnel shifts.
+template <int UNROLL, typename Rows>
+__device__ __forceinline__ void morph_plane(const BitView& G, const unsigned* src, unsigned* dst, int k, int ay, Rows rows,
+                                            bool erode, int nthreads) {
+    const int h = G.h, wpr = G.wpr;
+    for (int i = threadIdx.x; i < h * wpr; i += nthreads) {
+        const int y = i / wpr, xw = i - y * wpr;
+        unsigned out = 0;
+#pragma unroll UNROLL
+        for (int r = 0; r < k; ++r) {
+            int lo, hi;
+            rows(r, lo, hi);
+            const int yy = y + r - ay;
+            if (yy < 0 || yy >= h || lo > hi) continue;
+            auto word = [&](int x) -> unsigned {
+                if (x < 0 || x >= wpr) return 0u;
+                const unsigned v = src[yy * wpr + x];
+                return erode ? ~v & valid_bits(G, x) : v;
+            };
+            const unsigned cur = word(xw), prev = word(xw - 1), next = word(xw + 1);
+#pragma unroll UNROLL
+            for (int j = lo; j <= hi; ++j)   // the row moved by j columns: a 32-bit funnel over the neighbouring word
+                out |= __funnelshift_r(j >= 0 ? cur : prev, j >= 0 ? next : cur, j & 31);
+        }
+        dst[i] = (erode ? ~out : out) & valid_bits(G, xw);
+    }
+    __syncthreads();
+}
+
+// any element, as the host lays it out (ellipse_rows)
+__device__ void morph_se(const BitView& G, const unsigned* src, unsigned* dst, const SeRows& se, bool erode,
+                         int nthreads) {
+    morph_plane<1>(G, src, dst, se.k, se.ay, [&](int r, int& lo, int& hi) { lo = se.lo[r], hi = se.hi[r]; }, erode,
+                   nthreads);
+}
+
+// cv2.getStructuringElement(MORPH_ELLIPSE, (K, K)) at compile time, for the kernels whose elements never change (the
+// 224 x 224 benchmark path runs them; with run-time rows inclusive_mask measured 10 % slower): the half-width of
+// each row, as ellipse_rows(K) computes it
+template <int K>
+struct EllipseRows;
+template <>
+struct EllipseRows<3> {
+    static constexpr int dx[3] = {0, 1, 0};
+};
+template <>
+struct EllipseRows<5> {
+    static constexpr int dx[5] = {0, 2, 2, 2, 0};
+};
+template <>
+struct EllipseRows<7> {
+    static constexpr int dx[7] = {0, 2, 3, 3, 3, 2, 0};
+};
+template <>
+struct EllipseRows<9> {
+    static constexpr int dx[9] = {0, 3, 3, 4, 4, 4, 3, 3, 0};
+};
+
+template <int K>
+__device__ void morph_ellipse(const BitView& G, const unsigned* src, unsigned* dst, bool erode, int nthreads) {
+    morph_plane<K>(G, src, dst, K, K / 2, [](int r, int& lo, int& hi) { hi = EllipseRows<K>::dx[r], lo = -hi; }, erode,
+                   nthreads);
+}
+
+// next run of ones in row y at or after column x: [start, end] inclusive; false when none
+__device__ bool next_run(const BitView& G, const unsigned* pl, int y, int x, int& start, int& end) {
+    const unsigned* row = pl + y * G.wpr;
+    const int w = G.w;
+    while (x < w) {
+        const unsigned wd = row[x >> 5] >> (x & 31);
+        if (wd == 0u) {
+            x = (x | 31) + 1;
+            continue;
+        }
+        x += __builtin_ctz(wd);
+        break;
+    }
+    if (x >= w) return false;
+    start = x;
+    while (x < w) {
+        const unsigned wd = ~(row[x >> 5] >> (x & 31));   // zeros above the shifted-in part end the run too
+        const int room = 32 - (x & 31);
+        const int ones = wd == 0u ? 32 : __builtin_ctz(wd);
+        if (ones < room) {
+            x += ones;
+            break;
+        }
+        x += room;
+    }
+    end = (x > w ? w : x) - 1;
+    return true;
+}
+
+// plane[word] = pred(y, x) for every pixel
+template <typename F>
+__device__ void build_plane(const BitView& G, unsigned* dst, int nthreads, F pred) {
+    for (int i = threadIdx.x; i < G.h * G.wpr; i += nthreads) {
+        const int y = i / G.wpr, xw = i - y * G.wpr;
+        unsigned m = 0;
+        const int xe = min(32, G.w - 32 * xw);
+        for (int b = 0; b < xe; ++b)
+            if (pred(y, 32 * xw + b)) m |= 1u << b;
+        dst[i] = m;
+    }
+    __syncthreads();
+}
+
+// ---- connected components of a bit plane: run-length union-find
+struct Run {
+    unsigned short x0, x1, y, pad;
+};
+
+// one workgroup of `nt` threads per image: the planes live in LDS, runs / parents / areas in the image's slice of
+// the workspace
+struct Post : BitView {
+    unsigned *A, *B, *C, *D;
+    int* rowstart;   // LDS [h + 1]
+    Run* rn;
+    int* par;
+    int* area;
+    int max_runs, nt;
+    int* nruns;    // LDS
+    int* status;   // LDS
+    int* flag;     // LDS [2]
+    unsigned long long* best;   // LDS
+};
+
+struct PostLds {
+    unsigned long long best;
+    int nruns, status, flag[2];
+};
+
+// the view of workgroup blockIdx.x: `nplanes` (2 or 4) bit planes and the row index carved from `planes`; clears
+// the status word (synchronise before the first walk)
+__device__ __forceinline__ Post post_view(unsigned* planes, int nplanes, PostLds& S, Run* runs, int* parent,
+                                          int* area, int runs_per_image, int h, int w, int wpr, int nt) {
+    Post P;
+    P.h = h;
+    P.w = w;
+    P.wpr = wpr;
+    const int plane = h * wpr;
+    P.A = planes;
+    P.B = P.A + plane;
+    P.C = nplanes > 2 ? P.B + plane : nullptr;
+    P.D = nplanes > 2 ? P.C + plane : nullptr;
+    P.rowstart = reinterpret_cast<int*>(planes + nplanes * plane);
+    const size_t n = blockIdx.x;
+    P.rn = runs + n * runs_per_image;
+    P.par = parent + n * runs_per_image;
+    P.area = area + n * runs_per_image;
+    P.max_runs = runs_per_image;
+    P.nt = nt;
+    P.nruns = &S.nruns;
+    P.status = &S.status;
+    P.flag = S.flag;
+    P.best = &S.best;
+    if (threadIdx.x == 0) S.status = 0;
+    return P;
+}
+
+// Lock-free union-find on the parent array.  Every walk has a hard step bound; hitting one sets kFlagBound in the
+// status word.
+__device__ __forceinline__ int ld_par(int* p, int x) {
+    return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ int bfind(const Post& P, int x) {
+    for (int i = 0; i <= P.max_runs; ++i) {
+        const int px = ld_par(P.par, x);
+        if (px == x) return x;
+        x = px;
+    }
+    atomicOr(P.status, kFlagBound);
+    return x;
+}
+__device__ void bunion(const Post& P, int a, int b) {
+    for (int i = 0; i <= P.max_runs; ++i) {
+        a = bfind(P, a);
+        b = bfind(P, b);
+        if (a == b) return;
+        if (a > b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = atomicMin(P.par + b, a);   // roots only move to a smaller index: a root is its first run
+        if (old == b) return;
+        b = old;
+    }
+    atomicOr(P.status, kFlagBound);
+}
+
+// runs of `src`, their connected components (par[k] = root = the component's first run in raster order) and areas.
+// FLAT = false leaves out the last pass, which writes every run's root into par[k]: for a kernel that asks for each
+// root once, through paint_runs<false> (with it inclusive_mask measured 8 % slower at 224 x 224).
+template <bool FLAT = true>
+__device__ void label_runs(const Post& P, const unsigned* src, bool conn8) {
+    const int h = P.h;
+    for (int y = threadIdx.x; y < h; y += P.nt) {
+        int c = 0, x = 0, s, e;
+        while (next_run(P, src, y, x, s, e)) {
+            ++c;
+            x = e + 1;
+        }
+        P.rowstart[y + 1] = c;
+    }
+    if (threadIdx.x == 0) P.rowstart[0] = 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int y = 0; y < h; ++y) P.rowstart[y + 1] += P.rowstart[y];
+        *P.nruns = P.rowstart[h];
+    }
+    __syncthreads();
+    for (int y = threadIdx.x; y < h; y += P.nt) {
+        int k = P.rowstart[y], x = 0, s, e;
+        while (next_run(P, src, y, x, s, e)) {
+            P.rn[k] = Run{(unsigned short)s, (unsigned short)e, (unsigned short)y, 0};
+            P.par[k] = k;
+            P.area[k] = 0;
+            ++k;
+            x = e + 1;
+        }
+    }
+    __threadfence();
+    __syncthreads();
+    const int g = conn8 ? 1 : 0;
+    for (int y = 1 + threadIdx.x; y < h; y += P.nt) {
+        int a = P.rowstart[y - 1], b = P.rowstart[y];
+        const int a_end = P.rowstart[y], b_end = P.rowstart[y + 1];
+        while (a < a_end && b < b_end) {
+            const Run ra = P.rn[a], rb = P.rn[b];
+            if ((int)ra.x0 <= (int)rb.x1 + g && (int)ra.x1 + g >= (int)rb.x0) bunion(P, a, b);
+            if (ra.x1 < rb.x1) ++a;
+            else ++b;
+        }
+    }
+    __threadfence();
+    __syncthreads();
+    const int nr = *P.nruns;
+    for (int k = threadIdx.x; k < nr; k += P.nt) {
+        const int root = bfind(P, k);
+        atomicAdd(P.area + root, (int)P.rn[k].x1 - (int)P.rn[k].x0 + 1);
+    }
+    __threadfence();
+    __syncthreads();
+    if (!FLAT) return;
+    for (int k = threadIdx.x; k < nr; k += P.nt) P.par[k] = bfind(P, k);   // flatten: par[k] is the root
+    __threadfence();
+    __syncthreads();
+}
+
+// dst = the runs whose component passes keep(root); each thread owns whole rows
+template <bool FLAT = true, typename F>
+__device__ void paint_runs(const Post& P, unsigned* dst, bool clear, F keep) {
+    for (int y = threadIdx.x; y < P.h; y += P.nt) {
+        unsigned* row = dst + y * P.wpr;
+        if (clear)
+            for (int i = 0; i < P.wpr; ++i) row[i] = 0u;
+        for (int k = P.rowstart[y]; k < P.rowstart[y + 1]; ++k) {
+            if (!keep(FLAT ? ld_par(P.par, k) : bfind(P, k))) continue;
+            const Run r = P.rn[k];
+            for (int x = r.x0; x <= (int)r.x1;) {
+                const int b = x & 31, len = min(32 - b, (int)r.x1 - x + 1);
+                row[x >> 5] |= (len == 32 ? 0xffffffffu : ((1u << len) - 1u)) << b;
+                x += len;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// ---- host utilities
+constexpr size_t kAlign = 256;
+inline size_t up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
+
+// A workspace layout is written once, as the take() calls of its constructor: the size query runs them on a null
+// base and reads `off`, the launcher runs them on the caller's buffer.
+struct Carver {
+    void* base;
+    size_t off = 0;
+    template <typename T>
+    T* take(size_t bytes) {
+        T* p = base ? reinterpret_cast<T*>(static_cast<uint8_t*>(base) + off) : nullptr;
+        off += up(bytes);
+        return p;
+    }
+};
+
+// Raises Kernel's dynamic-LDS limit to `want` bytes, once; what a launch may ask for: `want`, or `otherwise` when
+// the runtime refused.
+template <auto Kernel>
+size_t dynamic_lds_cap(size_t want, size_t otherwise) {
+    static const size_t cap = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess
+                                  ? want
+                                  : otherwise;
+    return cap;
+}
+
+// one workgroup sweeps a whole image; the map lives in LDS when it fits
+void launch_canny_hysteresis(uint8_t* map, int n, int h, int w, hipStream_t s) {
+    const int hw = h * w;
+    const int in_lds = (size_t)hw <= dynamic_lds_cap<canny_hysteresis_kernel>(156 * 1024, 60 * 1024);
+    canny_hysteresis_kernel<<<n, kHystThreads, in_lds ? (size_t)((hw + 15) & ~15) : 0, s>>>(map, h, w, in_lds);
+}
+
+// dynamic LDS of the two fused kernels, or 0 when an image does not fit a CU (the multi-launch chains then run)
+constexpr size_t kFusedLdsCap = 140 * 1024;
+size_t fused_lds_bytes(int h, int w, bool with_bits) {
+    if (w % 4 != 0 || h < 1) return 0;
+    const size_t plane = ((size_t)h * w + 15) & ~(size_t)15;
+    const size_t wpr = 2 * (size_t)((w + 63) / 64);
+    const size_t need = 2 * plane + (with_bits ? 3 : 2) * (size_t)h * wpr * 4;   // + strong / weak (/ brown) bit planes
+    return need <= kFusedLdsCap ? need : 0;
+}
+
+// dynamic LDS of a Post: the bit planes and the row index
+size_t post_lds_bytes(int nplanes, int h, int wpr) { return (size_t)nplanes * h * wpr * 4 + (size_t)(h + 1) * 4; }
+
+// getStructuringElement(MORPH_ELLIPSE, (k, k)) with the default anchor (k / 2, k / 2)
+static SeRows ellipse_rows(int k) {
+    SeRows se{};
+    se.k = k;
+    se.ay = k / 2;
+    const int r = k / 2, c = k / 2;
+    const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
+    for (int i = 0; i < k; ++i) {
+        int j1 = 0, j2 = 0;
+        const int dy = i - r;
+        if (std::abs(dy) <= r) {
+            const int dx = (int)nearbyint(c * std::sqrt((r * r - dy * dy) * inv_r2));
+            j1 = std::max(c - dx, 0);
+            j2 = std::min(c + dx + 1, k);
+        }
+        se.lo[i] = (signed char)(j1 - c);
+        se.hi[i] = (signed char)(j2 - 1 - c);
+    }
+    return se;
+}
+
+static void lab_tables_host(uint16_t* out) {   // color_lab.cpp initLabTabs: sRGBGammaTab_b, LabCbrtTab_b
+    for (int i = 0; i < 256; ++i) {
+        const float x = (float)i / 255.0f;
+        const double xd = (double)x;
+        const float lin = (float)(xd <= 0.04045 ? xd / 12.92 : pow((xd + 0.055) / 1.055, 2.4));
+        const long v = lrint((double)(2040.0f * lin));
+        out[i] = (uint16_t)(v < 0 ? 0 : (v > 65535 ? 65535 : v));
+    }
+    const float scale = 1.0f / (255.0f * 8.0f);
+    const float lthresh = 216.0f / 24389.0f, lscale = 841.0f / 108.0f, lbias = 16.0f / 116.0f;
+    for (int i = 0; i < kLabCbrtSize; ++i) {
+        const float y = scale * (float)i;
+        float f;
+        if (y < lthresh) {
+            const float prod = y * lscale;   // two roundings, as numpy's float32 arithmetic in the oracle
+            f = prod + lbias;
+        } else {
+            f = (float)cbrt((double)y);
+        }
+        const long v = lrint((double)(32768.0f * f));
+        out[256 + i] = (uint16_t)(v < 0 ? 0 : (v > 65535 ? 65535 : v));
+    }
+}
+
+// the two L*a*b* tables, built once on the host, to `dst` on the device
+int upload_lab_tables(uint16_t* dst, hipStream_t s, const char* who) {
+    static const std::vector<uint16_t> host_tabs = []() {
+        std::vector<uint16_t> t(256 + kLabCbrtSize);
+        lab_tables_host(t.data());
+        return t;
+    }();
+    if (hipMemcpyAsync(dst, host_tabs.data(), host_tabs.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s) !=
+        hipSuccess) {
+        lf::set_error("%s: table upload failed", who);
+        return LF_ERR_LAUNCH;
+    }
+    return LF_OK;
+}
+
+// what every labelling kernel wants from its workspace: runs, parents, areas (h * (w / 2 + 1) per image, the most
+// a bit plane can hold) and the L*a*b* tables
+size_t mask_runs_per_image(int h, int w) { return (size_t)h * (w / 2 + 1); }
+
+struct LabelBufs {
+    Run* rn;
+    int *parent, *area;
+    uint16_t* tabs;
+    void carve(Carver& c, int n, int h, int w) {
+        const size_t runs = (size_t)n * mask_runs_per_image(h, w);
+        rn = c.take<Run>(runs * sizeof(Run));
+        parent = c.take<int>(runs * 4);
+        area = c.take<int>(runs * 4);
+        tabs = c.take<uint16_t>((256 + kLabCbrtSize) * sizeof(uint16_t));
+    }
+};
+
+// ===========================================================================
+// The saliency filter (the header of this file), multi-launch chain: the only path for images that do not fit a
+// CU's LDS or whose width is not a multiple of four.
+// ===========================================================================
+__global__ void minmax_init_kernel(unsigned* mm, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n * 6) mm[i] = (i & 1) ? 0u : kInfBits;  // (min, max) x {gradient, colour diff, saliency}
+}
+
+// Sobel of the gray plane: dx^2 + dy^2 and (dx, dy) with BORDER_REPLICATE for Canny
+// (canny.cpp), sqrt(dx^2 + dy^2) with BORDER_REFLECT_101 for cv2.Sobel + cv2.magnitude.
+__global__ __launch_bounds__(kBlock) void sal_sobel_kernel(const uint8_t* __restrict__ gray,
+                                                           int32_t* __restrict__ mag2,
+                                                           uint32_t* __restrict__ dxdy,
+                                                           float* __restrict__ gmag,
+                                                           unsigned* __restrict__ mm, int h, int w) {
+    const unsigned n = blockIdx.y;
+    const int hw = h * w;
+    const uint8_t* g = gray + (size_t)n * hw;
+    MinMax mmx;
+    for (int k = 0; k < kPxPerThread; ++k) {
+        const int p = (blockIdx.x * kPxPerThread + k) * kBlock + threadIdx.x;
+        if (p >= hw) break;
+        const int y = p / w, x = p - y * w;
+        const Sob s = sobel_at(g, w, clampi(y - 1, 0, h - 1), y, clampi(y + 1, 0, h - 1),
+                               clampi(x - 1, 0, w - 1), x, clampi(x + 1, 0, w - 1));
+        mag2[(size_t)n * hw + p] = __mul24(s.dx, s.dx) + __mul24(s.dy, s.dy);  // |d| <= 1020
+        dxdy[(size_t)n * hw + p] = ((unsigned)s.dx & 0xffffu) | ((unsigned)s.dy << 16);
+        Sob r = s;
+        if (x == 0 || y == 0 || x == w - 1 || y == h - 1)
+            r = sobel_at(g, w, reflect101i(y - 1, h), y, reflect101i(y + 1, h), reflect101i(x - 1, w), x,
+                         reflect101i(x + 1, w));
+        const float gm = __fsqrt_rn((float)(__mul24(r.dx, r.dx) + __mul24(r.dy, r.dy)));  // < 2^24: exact
+        gmag[(size_t)n * hw + p] = gm;
+        mmx.take(gm);
+    }
+    minmax_publish(mmx, mm + n * 6 + 0, mm + n * 6 + 1);
 }
 
 // dilate / erode with the 3x3 MORPH_ELLIPSE element (a plus); outside pixels never win.
@@ -262,21 +896,12 @@ __global__ __launch_bounds__(kBlock) void brown_mask_kernel(const uint8_t* __res
                                                             const uint8_t* __restrict__ leaf,
                                                             uint8_t* __restrict__ out, size_t npx,
                                                             int hue_lo, int hue_hi, int s_min, int v_max) {
-    __shared__ int sdiv[256], hdiv[256];
-    for (int i = threadIdx.x; i < 256; i += kBlock) {
-        sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
-        hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
-    }
+    __shared__ HsvTabs H;
+    H.fill(kBlock);
     __syncthreads();
     for (size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x; p < npx; p += (size_t)gridDim.x * kBlock) {
-        const int r = rgb[3 * p], g = rgb[3 * p + 1], b = rgb[3 * p + 2];
-        const int v = max(r, max(g, b)), vmin = min(r, min(g, b)), diff = v - vmin;
-        const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
-        const int s = (__mul24(diff, sdiv[v]) + (1 << 11)) >> 12;
-        int hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
-        hh = (__mul24(hh, hdiv[diff]) + (1 << 11)) >> 12;
-        hh += hh < 0 ? 180 : 0;
-        const bool brown = hh >= hue_lo && hh <= hue_hi && s >= s_min && v <= v_max && leaf[p] > 0;
+        const bool brown =
+            brown_hsv(H, rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2], hue_lo, hue_hi, s_min, v_max) && leaf[p] > 0;
         out[p] = brown ? 255 : 0;
     }
 }
@@ -363,451 +988,6 @@ __global__ __launch_bounds__(kBlock) void saliency_out_kernel(const uint8_t* __r
     }
 }
 
-// ===========================================================================
-// _create_inclusive_mask (srcs/transform/filters/mask.py:727-831): the default strategy of make_mask.
-// Per-pixel colour predicates (8-bit HSV and L*a*b*, uint8 channel comparisons that wrap as numpy's
-// do), Canny (L1 gradient, 30 / 100) dilated by the 3x3 ellipse, the texture test against a 15x15
-// Gaussian of the gray plane -> one BIT per pixel; then, one workgroup per image with the bit planes
-// in LDS: open 3x3, close 9x9, close 7x7 (cv2's MORPH_ELLIPSE elements), largest 8-connected
-// component (run-length union-find), close 5x5.
-// ===========================================================================
-__global__ __launch_bounds__(kBlock) void canny_sobel_l1_kernel(const uint8_t* __restrict__ gray,
-                                                                int32_t* __restrict__ mag,
-                                                                uint32_t* __restrict__ dxdy, int h, int w) {
-    const unsigned n = blockIdx.y;
-    const int hw = h * w;
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= hw) return;
-    const int y = p / w, x = p - y * w;
-    const Sob s = sobel_at(gray + (size_t)n * hw, w, clampi(y - 1, 0, h - 1), y, clampi(y + 1, 0, h - 1),
-                           clampi(x - 1, 0, w - 1), x, clampi(x + 1, 0, w - 1));
-    mag[(size_t)n * hw + p] = (s.dx < 0 ? -s.dx : s.dx) + (s.dy < 0 ? -s.dy : s.dy);
-    dxdy[(size_t)n * hw + p] = ((unsigned)s.dx & 0xffffu) | ((unsigned)s.dy << 16);
-}
-
-constexpr int kLabCbrtSize = 256 * 3 / 2 * 8;   // LAB_CBRT_TAB_SIZE_B
-
-// One wave per 64-pixel segment of a row; bit i of the ballot is pixel x0 + i.
-// bits[n][y][2 * seg + {0, 1}]: `wpr` = 2 * ceil(w / 64) words per row.
-__global__ __launch_bounds__(kBlock) void inclusive_pred_kernel(
-    const uint8_t* __restrict__ rgb, const uint8_t* __restrict__ gray, const uint8_t* __restrict__ blur,
-    const uint8_t* __restrict__ edges, const uint16_t* __restrict__ lab_tabs, uint32_t* __restrict__ bits,
-    int n_images, int h, int w, int hue_lo, int hue_hi) {
-    __shared__ int sdiv[256], hdiv[256];
-    __shared__ uint16_t gam[256], cbr[kLabCbrtSize];
-    for (int i = threadIdx.x; i < 256; i += kBlock) {
-        sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
-        hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
-        gam[i] = lab_tabs[i];
-    }
-    for (int i = threadIdx.x; i < kLabCbrtSize; i += kBlock) cbr[i] = lab_tabs[256 + i];
-    __syncthreads();
-    const int spr = (w + 63) / 64, wpr = 2 * spr;
-    const long total = (long)n_images * h * spr;
-    const int lane = threadIdx.x & 63;
-    for (long seg = (long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); seg < total;
-         seg += (long)gridDim.x * (kBlock / 64)) {
-        const int sx = (int)(seg % spr);
-        const long ry = seg / spr;
-        const int y = (int)(ry % h);
-        const size_t n = (size_t)(ry / h);
-        const int x = sx * 64 + lane;
-        bool plant = false;
-        if (x < w) {
-            const size_t p = (n * h + y) * (size_t)w + x;
-            const int r = rgb[3 * p], g = rgb[3 * p + 1], b = rgb[3 * p + 2];
-            // 8-bit HSV (color_hsv: H in [0, 180))
-            const int v = max(r, max(g, b)), vmin = min(r, min(g, b)), diff = v - vmin;
-            const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
-            const int s = (__mul24(diff, sdiv[v]) + (1 << 11)) >> 12;
-            int hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
-            hh = (__mul24(hh, hdiv[diff]) + (1 << 11)) >> 12;
-            hh += hh < 0 ? 180 : 0;
-            // 8-bit L*a*b* (color_lab RGB2Lab_b)
-            const int R = gam[r], G = gam[g], B = gam[b];
-            const int fx = cbr[(R * 1777 + G * 1541 + B * 778 + 2048) >> 12];
-            const int fy = cbr[(R * 871 + G * 2929 + B * 296 + 2048) >> 12];
-            const int fz = cbr[(R * 73 + G * 448 + B * 3575 + 2048) >> 12];
-            const int L = clampi((296 * fy - 1336934 + 16384) >> 15, 0, 255);
-            const int la = clampi((500 * (fx - fy) + 4194304 + 16384) >> 15, 0, 255);
-            const int lb = clampi((200 * (fy - fz) + 4194304 + 16384) >> 15, 0, 255);
-            const bool strong_green = hh >= hue_lo && hh <= hue_hi && s >= 30 && v >= 30;
-            // uint8 planes: r + 15 wraps (mask.py:759-763)
-            const bool dominant = g > ((r + 15) & 255) || g > ((b + 15) & 255) ||
-                                  (g > ((r + 5) & 255) && g > ((b + 5) & 255) && s >= 20);
-            const bool lab_green = la <= 125 && lb >= 120 && L >= 20 && L <= 240;
-            const uint8_t* e = edges + (n * h) * (size_t)w;
-            const int q = y * w + x;
-            const bool edge = e[q] || (x > 0 && e[q - 1]) || (x < w - 1 && e[q + 1]) || (y > 0 && e[q - w]) ||
-                              (y < h - 1 && e[q + w]);
-            const int tex = (int)gray[p] - (int)blur[p];
-            const bool background = (s <= 25 && v >= 50 && v <= 220) ||
-                                    (hh >= 120 && hh <= 160 && s >= 20 && r > g && b > g) ||
-                                    (s <= 15 && (tex < 0 ? -tex : tex) < 10);
-            plant = (strong_green || dominant || lab_green || edge) && !background;
-        }
-        const unsigned long long m = __ballot(plant);
-        if (lane == 0) {
-            uint32_t* o = bits + ((n * h + y) * (size_t)wpr + 2 * sx);
-            o[0] = (unsigned)m;
-            o[1] = (unsigned)(m >> 32);
-        }
-    }
-}
-
-// ---- binary morphology on bit rows in LDS
-template <int K>
-struct EllipseRows;   // half-width of each row of cv2.getStructuringElement(MORPH_ELLIPSE, (K, K))
-template <>
-struct EllipseRows<3> {
-    static constexpr int dx[3] = {0, 1, 0};
-};
-template <>
-struct EllipseRows<5> {
-    static constexpr int dx[5] = {0, 2, 2, 2, 0};
-};
-template <>
-struct EllipseRows<7> {
-    static constexpr int dx[7] = {0, 2, 3, 3, 3, 2, 0};
-};
-template <>
-struct EllipseRows<9> {
-    static constexpr int dx[9] = {0, 3, 3, 4, 4, 4, 3, 3, 0};
-};
-
-// dst = dilate(src) or erode(src) by the K x K ellipse; pixels outside the image never win, i.e. an
-// erosion is the dilation of the complement taken INSIDE the image.  Bits past column w stay 0.
-template <int K, bool ERODE>
-__device__ void morph_bits(const unsigned* __restrict__ src, unsigned* __restrict__ dst, int h, int w, int wpr) {
-    constexpr int R = K / 2;
-    const int used = (w + 31) / 32;
-    const unsigned lastmask = (w & 31) ? ((1u << (w & 31)) - 1u) : 0xffffffffu;
-    auto valid = [&](int xw) -> unsigned { return xw < used - 1 ? 0xffffffffu : (xw == used - 1 ? lastmask : 0u); };
-    auto word = [&](int y, int xw) -> unsigned {
-        if (xw < 0 || xw >= wpr) return 0u;
-        const unsigned v = src[y * wpr + xw];
-        return ERODE ? ~v & valid(xw) : v;
-    };
-    for (int i = threadIdx.x; i < h * wpr; i += blockDim.x) {
-        const int y = i / wpr, xw = i - y * wpr;
-        unsigned out = 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int yy = y + k - R;
-            if (yy < 0 || yy >= h) continue;
-            const unsigned cur = word(yy, xw), prev = word(yy, xw - 1), next = word(yy, xw + 1);
-            out |= cur;
-#pragma unroll
-            for (int s = 1; s <= EllipseRows<K>::dx[k]; ++s)
-                out |= (cur << s) | (prev >> (32 - s)) | (cur >> s) | (next << (32 - s));
-        }
-        dst[i] = (ERODE ? ~out : out) & valid(xw);
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ int uf_load(int* p, int x) {
-    return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // past the L1: atomics update L2 only
-}
-__device__ int uf_find(int* p, int x) {
-    for (;;) {
-        const int px = uf_load(p, x);
-        if (px == x) return x;
-        x = px;
-    }
-}
-__device__ void uf_union(int* p, int a, int b) {
-    for (;;) {
-        a = uf_find(p, a);
-        b = uf_find(p, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(p + b, a);   // roots only ever move to a smaller index
-        if (old == b) return;
-        b = old;
-    }
-}
-
-// next run of ones in a bit row at or after column x: [start, end] inclusive; false when none
-__device__ bool next_run(const unsigned* row, int w, int x, int& start, int& end) {
-    while (x < w) {
-        const unsigned wd = row[x >> 5] >> (x & 31);
-        if (wd == 0u) {
-            x = (x | 31) + 1;
-            continue;
-        }
-        x += __builtin_ctz(wd);
-        break;
-    }
-    if (x >= w) return false;
-    start = x;
-    while (x < w) {
-        const unsigned wd = ~(row[x >> 5] >> (x & 31));   // zeros above the shifted-in part end the run too
-        const int room = 32 - (x & 31);
-        const int ones = wd == 0u ? 32 : __builtin_ctz(wd);
-        if (ones < room) {
-            x += ones;
-            break;
-        }
-        x += room;
-    }
-    end = (x > w ? w : x) - 1;
-    return true;
-}
-
-struct MaskRun {
-    unsigned short start, end;
-};
-
-__global__ __launch_bounds__(kBlock) void inclusive_morph_kernel(const uint32_t* __restrict__ bits,
-                                                                 uint8_t* __restrict__ out, MaskRun* __restrict__ runs,
-                                                                 int* __restrict__ parent, int* __restrict__ area,
-                                                                 int h, int w, int wpr, int runs_per_image) {
-    extern __shared__ unsigned lds_bits[];
-    unsigned* A = lds_bits;
-    unsigned* B = A + h * wpr;
-    int* rowstart = reinterpret_cast<int*>(B + h * wpr);   // [h + 1]
-    __shared__ unsigned long long best;
-    const size_t n = blockIdx.x;
-    for (int i = threadIdx.x; i < h * wpr; i += kBlock) A[i] = bits[n * h * wpr + i];
-    __syncthreads();
-    morph_bits<3, true>(A, B, h, w, wpr);    // MORPH_OPEN 3x3
-    morph_bits<3, false>(B, A, h, w, wpr);
-    morph_bits<9, false>(A, B, h, w, wpr);   // MORPH_CLOSE 9x9
-    morph_bits<9, true>(B, A, h, w, wpr);
-    morph_bits<7, false>(A, B, h, w, wpr);   // MORPH_CLOSE 7x7
-    morph_bits<7, true>(B, A, h, w, wpr);
-
-    // ---- largest 8-connected component of A -> B
-    MaskRun* rn = runs + n * runs_per_image;
-    int* par = parent + n * runs_per_image;
-    int* ar = area + n * runs_per_image;
-    for (int y = threadIdx.x; y < h; y += kBlock) {
-        int c = 0, x = 0, s, e;
-        while (next_run(A + y * wpr, w, x, s, e)) {
-            ++c;
-            x = e + 1;
-        }
-        rowstart[y + 1] = c;
-    }
-    if (threadIdx.x == 0) {
-        rowstart[0] = 0;
-        best = 0ull;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int y = 0; y < h; ++y) rowstart[y + 1] += rowstart[y];
-    __syncthreads();
-    const int nruns = rowstart[h];
-    for (int y = threadIdx.x; y < h; y += kBlock) {
-        int k = rowstart[y], x = 0, s, e;
-        while (next_run(A + y * wpr, w, x, s, e)) {
-            rn[k] = MaskRun{(unsigned short)s, (unsigned short)e};
-            par[k] = k;
-            ar[k] = 0;
-            ++k;
-            x = e + 1;
-        }
-    }
-    __threadfence();
-    __syncthreads();
-    for (int y = 1 + threadIdx.x; y < h; y += kBlock) {   // runs of row y against runs of row y - 1
-        int a = rowstart[y - 1], b = rowstart[y];
-        const int a_end = rowstart[y], b_end = rowstart[y + 1];
-        while (a < a_end && b < b_end) {
-            const MaskRun ra = rn[a], rb = rn[b];
-            if ((int)ra.start <= (int)rb.end + 1 && (int)ra.end >= (int)rb.start - 1) uf_union(par, a, b);
-            if (ra.end < rb.end) ++a;
-            else ++b;
-        }
-    }
-    __threadfence();
-    __syncthreads();
-    for (int k = threadIdx.x; k < nruns; k += kBlock) {
-        const int root = uf_find(par, k);
-        atomicAdd(ar + root, (int)rn[k].end - (int)rn[k].start + 1);
-    }
-    __threadfence();
-    __syncthreads();
-    for (int k = threadIdx.x; k < nruns; k += kBlock) {   // largest area; the earliest component among equals
-        const int a = __hip_atomic_load(ar + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (a > 0) atomicMax(&best, ((unsigned long long)a << 32) | (unsigned)(0x7fffffff - k));
-    }
-    for (int i = threadIdx.x; i < h * wpr; i += kBlock) B[i] = 0u;
-    __syncthreads();
-    if (nruns > 0) {
-        const int keep = 0x7fffffff - (int)(best & 0xffffffffull);
-        for (int y = threadIdx.x; y < h; y += kBlock)
-            for (int k = rowstart[y]; k < rowstart[y + 1]; ++k) {
-                if (uf_find(par, k) != keep) continue;
-                for (int x = rn[k].start; x <= (int)rn[k].end;) {   // this thread owns the row's words
-                    const int bit = x & 31, len = min(32 - bit, (int)rn[k].end - x + 1);
-                    B[y * wpr + (x >> 5)] |= (len == 32 ? 0xffffffffu : ((1u << len) - 1u)) << bit;
-                    x += len;
-                }
-            }
-    }
-    __syncthreads();
-    morph_bits<5, false>(B, A, h, w, wpr);   // MORPH_CLOSE 5x5
-    morph_bits<5, true>(A, B, h, w, wpr);
-    uint8_t* o = out + n * (size_t)h * w;
-    for (int p = threadIdx.x; p < h * w; p += kBlock) {
-        const int y = p / w, x = p - y * w;
-        o[p] = (B[y * wpr + (x >> 5)] >> (x & 31)) & 1u ? 255 : 0;
-    }
-}
-
-constexpr size_t kAlign = 256;
-inline size_t up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
-
-// ===========================================================================
-// Round 3: the per-image middle of both filters in ONE workgroup per image, planes resident in LDS.
-//
-// Both chains above spend their time in launches and in round trips of small planes through L2 / HBM (13 launches
-// and 20 bytes of intermediates per pixel for the saliency filter).  A 224 x 224 gray plane is 50 KB: the gray
-// plane, the Canny map and the bit planes of the brown regions of one image fit the 160 KB of a CU together, and
-// everything the old kernels kept in 4-byte planes (squared gradient, (dx, dy), gradient magnitude, colour
-// difference, saliency) is cheaper to RECOMPUTE from the gray plane in LDS / the two RGB images in L2 than to store.
-// What stays outside: the two Gaussian blurs (the i8-MFMA kernel of lf_blur_mfma.hip) and the final masking pass.
-// The arithmetic is the old kernels', expression for expression (the bit-exact tests are unchanged).
-// ===========================================================================
-constexpr int kFuseT = 1024;
-
-__device__ __forceinline__ unsigned gray_px_f(int r, int g, int b) {   // cv2 RGB2GRAY, 14-bit fixed point (lf_augment.hip)
-    return (unsigned)(r * 4899 + g * 9617 + b * 1868 + 8192) >> 14;
-}
-
-// Canny's non-maximum suppression + double threshold on a gray plane in LDS: map = 1 (no edge), 0 (weak),
-// 2 (strong).  L1: |dx| + |dy| (cv2.Canny default), else dx^2 + dy^2 against squared thresholds.  The gradient of a
-// neighbour is recomputed from the plane (8 LDS bytes) instead of being read from a 4-byte plane in memory.
-template <bool L1>
-__device__ __forceinline__ void canny_nms_lds(const uint8_t* gray, uint8_t* emap, int h, int w, int low, int high) {
-    const int hw = h * w;
-    auto sob = [&](int y, int x) -> Sob {
-        return sobel_at(gray, w, clampi(y - 1, 0, h - 1), y, clampi(y + 1, 0, h - 1), clampi(x - 1, 0, w - 1), x,
-                        clampi(x + 1, 0, w - 1));
-    };
-    auto mag = [&](const Sob s) -> int {
-        return L1 ? (s.dx < 0 ? -s.dx : s.dx) + (s.dy < 0 ? -s.dy : s.dy) : __mul24(s.dx, s.dx) + __mul24(s.dy, s.dy);
-    };
-    auto at = [&](int yy, int xx) -> int {  // the magnitude buffer has a zero frame
-        return (yy < 0 || yy >= h || xx < 0 || xx >= w) ? 0 : mag(sob(yy, xx));
-    };
-    const float inv_w = 1.0f / (float)w;
-    for (int p = threadIdx.x; p < hw; p += kFuseT) {
-        int y = (int)((float)p * inv_w);
-        int x = p - __mul24(y, w);
-        if (x < 0) { --y; x += w; } else if (x >= w) { ++y; x -= w; }
-        const Sob s = sob(y, x);
-        const int m = mag(s);
-        uint8_t out = 1;
-        if (m > low) {
-            const int xs = s.dx, ys = s.dy;
-            const int ax = xs < 0 ? -xs : xs;
-            const int ay = (ys < 0 ? -ys : ys) << 15;
-            const int tg22x = __mul24(ax, 13573);  // tan(22.5 deg) in 15-bit fixed point
-            bool keep;
-            if (ay < tg22x) {
-                keep = m > at(y, x - 1) && m >= at(y, x + 1);
-            } else {
-                const int tg67x = tg22x + (ax << 16);
-                if (ay > tg67x) {
-                    keep = m > at(y - 1, x) && m >= at(y + 1, x);
-                } else {
-                    const int sg = (xs ^ ys) < 0 ? 1 : -1;
-                    keep = m > at(y - 1, x - sg) && m > at(y + 1, x + sg);
-                }
-            }
-            if (keep) out = m > high ? 2 : 0;
-        }
-        emap[p] = out;
-    }
-    __syncthreads();
-}
-
-// Hysteresis on the map in LDS (1 = no edge, 0 = weak, 2 = strong; 2 = edge afterwards): a weak pixel with a strong
-// 8-neighbour becomes strong, until nothing changes.  On bit planes — strong bits S, weak bits W, one 32-pixel word
-// per thread and sweep: S |= W & dilate3x3(S) — instead of one pixel per thread with nine byte reads: a sweep over a
-// 224 x 224 map is 1,792 words, and noisy images need dozens of sweeps (the byte sweeps were most of the fused
-// kernels' time: 0.4 ms per image).  Rows are `wpr` words wide (two per 64-pixel segment, as the ballots deliver them).
-__device__ __forceinline__ void canny_hysteresis_lds(uint8_t* m, unsigned* sb, unsigned* wb, int h, int w, int wpr,
-                                                     int* changed) {
-    const int spr = wpr / 2;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int seg = wv; seg < h * spr; seg += kFuseT / 64) {
-        const int y = seg / spr, sx = seg - y * spr, x = sx * 64 + lane;
-        const uint8_t v = x < w ? m[y * w + x] : 1;
-        const unsigned long long s = __ballot(v == 2), wk = __ballot(v == 0);
-        if (lane == 0) {
-            sb[y * wpr + 2 * sx] = (unsigned)s;
-            sb[y * wpr + 2 * sx + 1] = (unsigned)(s >> 32);
-            wb[y * wpr + 2 * sx] = (unsigned)wk;
-            wb[y * wpr + 2 * sx + 1] = (unsigned)(wk >> 32);
-        }
-    }
-    do {
-        __syncthreads();
-        if (threadIdx.x == 0) *changed = 0;
-        __syncthreads();
-        bool any = false;
-        for (int i = threadIdx.x; i < h * wpr; i += kFuseT) {
-            const unsigned weak = wb[i] & ~sb[i];
-            if (weak == 0u) continue;
-            const int y = i / wpr, xw = i - y * wpr;
-            unsigned nb = 0;
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy) {
-                const int yy = y + dy;
-                if (yy < 0 || yy >= h) continue;
-                const unsigned* row = sb + yy * wpr;
-                const unsigned c = row[xw], pv = xw > 0 ? row[xw - 1] : 0u, nx = xw < wpr - 1 ? row[xw + 1] : 0u;
-                nb |= c | (c << 1) | (pv >> 31) | (c >> 1) | (nx << 31);
-            }
-            const unsigned grow = weak & nb;   // (bits past column w are never weak)
-            if (grow) {
-                sb[i] |= grow;                 // in place: growth is monotone, the fixed point is the same
-                any = true;
-            }
-        }
-        if (any) *changed = 1;
-        __syncthreads();
-    } while (*changed);
-    for (int seg = wv; seg < h * spr; seg += kFuseT / 64) {
-        const int y = seg / spr, sx = seg - y * spr, x = sx * 64 + lane;
-        if (x < w) m[y * w + x] = (sb[y * wpr + (x >> 5)] >> (x & 31) & 1u) ? 2 : 1;
-    }
-    __syncthreads();
-}
-
-// min / max of non-negative floats over the workgroup (bit patterns, as MinMax does), result in lohi[0..1]
-__device__ __forceinline__ void minmax_block(MinMax r, unsigned* wscratch, unsigned* lohi) {
-    unsigned lo = r.lo, hi = r.hi;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = min(lo, (unsigned)__shfl_xor((int)lo, off, 64));
-        hi = max(hi, (unsigned)__shfl_xor((int)hi, off, 64));
-    }
-    __syncthreads();   // wscratch may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) {
-        wscratch[2 * (threadIdx.x >> 6)] = lo;
-        wscratch[2 * (threadIdx.x >> 6) + 1] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kFuseT / 64; ++k) {
-            lo = min(lo, wscratch[2 * k]);
-            hi = max(hi, wscratch[2 * k + 1]);
-        }
-        lohi[0] = lo;
-        lohi[1] = hi;
-    }
-    __syncthreads();
-}
-
 // One workgroup per image: gray plane, Canny (L2 gradient, 50 / 150), brown regions (closed, dilated twice), the
 // three normalisations and the weighted sum of blur.py:30-66 -> the normalised saliency plane (uint8) in `nsal`.
 // rgb / blurred: [n][h][w][3]; leaf: [n][h][w]; w % 4 == 0.
@@ -817,13 +997,14 @@ __global__ __launch_bounds__(kFuseT) void saliency_fused_kernel(const uint8_t* _
                                                                 uint8_t* __restrict__ nsal, int h, int w, int use_brown,
                                                                 int hue_lo, int hue_hi, int s_min, int v_max) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fl[];
-    __shared__ int sdiv[256], hdiv[256];
+    __shared__ HsvTabs H;
     __shared__ unsigned wscratch[2 * (kFuseT / 64)];
     __shared__ unsigned mm[6];
     __shared__ float coef[6];
     __shared__ int changed;
     const int hw = h * w, plane = (hw + 15) & ~15;
     const int spr = (w + 63) / 64, wpr = 2 * spr;      // 64-pixel segments / 32-bit words per bit row
+    const BitView G{h, w, wpr};
     uint8_t* gray = fl;
     uint8_t* emap = fl + plane;
     unsigned* ba = reinterpret_cast<unsigned*>(fl + 2 * plane);
@@ -833,10 +1014,7 @@ __global__ __launch_bounds__(kFuseT) void saliency_fused_kernel(const uint8_t* _
     const uint8_t* src = rgb + n * (size_t)hw * 3;
     const uint8_t* blr = blurred + n * (size_t)hw * 3;
     const uint8_t* lf_ = leaf + n * (size_t)hw;
-    for (int i = threadIdx.x; i < 256; i += kFuseT) {
-        sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
-        hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
-    }
+    H.fill(kFuseT);
     __syncthreads();
     // ---- pass 1: gray plane; brown_regions of blur.py:47-53 as one bit per pixel (a wave = 64 pixels of a row)
     {
@@ -848,15 +1026,7 @@ __global__ __launch_bounds__(kFuseT) void saliency_fused_kernel(const uint8_t* _
                 const int p = y * w + x;
                 const int r = src[3 * p], g = src[3 * p + 1], b = src[3 * p + 2];
                 gray[p] = (uint8_t)gray_px_f(r, g, b);
-                if (use_brown) {
-                    const int v = max(r, max(g, b)), vmin = min(r, min(g, b)), diff = v - vmin;
-                    const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
-                    const int s = (__mul24(diff, sdiv[v]) + (1 << 11)) >> 12;
-                    int hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
-                    hh = (__mul24(hh, hdiv[diff]) + (1 << 11)) >> 12;
-                    hh += hh < 0 ? 180 : 0;
-                    brown = hh >= hue_lo && hh <= hue_hi && s >= s_min && v <= v_max && lf_[p] > 0;
-                }
+                if (use_brown) brown = brown_hsv(H, r, g, b, hue_lo, hue_hi, s_min, v_max) && lf_[p] > 0;
             }
             const unsigned long long m = __ballot(brown);
             if (lane == 0) {
@@ -871,10 +1041,10 @@ __global__ __launch_bounds__(kFuseT) void saliency_fused_kernel(const uint8_t* _
     canny_hysteresis_lds(emap, hs, bb, h, w, wpr, &changed);
     // ---- brown: MORPH_CLOSE with the 3x3 ellipse (a plus), then dilate twice
     if (use_brown) {
-        morph_bits<3, false>(ba, bb, h, w, wpr);
-        morph_bits<3, true>(bb, ba, h, w, wpr);
-        morph_bits<3, false>(ba, bb, h, w, wpr);
-        morph_bits<3, false>(bb, ba, h, w, wpr);
+        morph_ellipse<3>(G, ba, bb, false, kFuseT);
+        morph_ellipse<3>(G, bb, ba, true, kFuseT);
+        morph_ellipse<3>(G, ba, bb, false, kFuseT);
+        morph_ellipse<3>(G, bb, ba, false, kFuseT);
     }
     const float inv_w = 1.0f / (float)w;
     auto rowcol = [&](int p, int& y, int& x) {
@@ -974,87 +1144,28 @@ __global__ __launch_bounds__(kFuseT) void saliency_fused_kernel(const uint8_t* _
     }
 }
 
-// gray plane (from memory) -> Canny (L1 gradient, 30 / 100) in LDS -> the per-pixel predicates of
-// _create_inclusive_mask (inclusive_pred_kernel above, expression for expression) -> one bit per pixel.
-__global__ __launch_bounds__(kFuseT) void inclusive_fused_kernel(
-    const uint8_t* __restrict__ rgb, const uint8_t* __restrict__ gray_g, const uint8_t* __restrict__ blur,
-    const uint16_t* __restrict__ lab_tabs, uint32_t* __restrict__ bits, int h, int w, int hue_lo, int hue_hi) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t fl[];
-    __shared__ int sdiv[256], hdiv[256];
-    __shared__ uint16_t gam[256], cbr[kLabCbrtSize];
-    __shared__ int changed;
-    const int hw = h * w, plane = (hw + 15) & ~15;
-    uint8_t* gray = fl;
-    uint8_t* emap = fl + plane;
-    const size_t n = blockIdx.x;
-    for (int i = threadIdx.x; i < 256; i += kFuseT) {
-        sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
-        hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
-        gam[i] = lab_tabs[i];
+struct SaliencyWs {
+    uint8_t *pa, *pb, *pc, *pd, *blurred;
+    int32_t* mag2;
+    uint32_t* dxdy;
+    float* gmag;
+    unsigned* mm;
+    size_t bytes;
+    SaliencyWs(void* base, int n, int h, int w) {
+        Carver c{base};
+        const size_t px = (size_t)n * h * w;
+        pa = c.take<uint8_t>(px);            // gray -> brown -> closed -> normalised saliency
+        pb = c.take<uint8_t>(px);            // Canny map / edges -> morphology scratch -> blurred saliency
+        pc = c.take<uint8_t>(px);            // dilated edges
+        pd = c.take<uint8_t>(px);            // dilated brown regions
+        blurred = c.take<uint8_t>(3 * px);
+        mag2 = c.take<int32_t>(4 * px);
+        dxdy = c.take<uint32_t>(4 * px);
+        gmag = c.take<float>(4 * px);
+        mm = c.take<unsigned>((size_t)n * 6 * sizeof(unsigned));
+        bytes = c.off;
     }
-    for (int i = threadIdx.x; i < kLabCbrtSize; i += kFuseT) cbr[i] = lab_tabs[256 + i];
-    {
-        const uint32_t* g4 = reinterpret_cast<const uint32_t*>(gray_g + n * (size_t)hw);   // hw % 4 == 0
-        for (int q = threadIdx.x; q < hw / 4; q += kFuseT) reinterpret_cast<uint32_t*>(gray)[q] = g4[q];
-    }
-    __syncthreads();
-    const int spr = (w + 63) / 64, wpr = 2 * spr;
-    canny_nms_lds<true>(gray, emap, h, w, 30, 100);   // cv2.Canny(gray, 30, 100)
-    {
-        unsigned* hs = reinterpret_cast<unsigned*>(fl + 2 * plane);
-        canny_hysteresis_lds(emap, hs, hs + h * wpr, h, w, wpr, &changed);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint8_t* src = rgb + n * (size_t)hw * 3;
-    const uint8_t* bl = blur + n * (size_t)hw;
-    for (int seg = wv; seg < h * spr; seg += kFuseT / 64) {
-        const int y = seg / spr, sx = seg - y * spr, x = sx * 64 + lane;
-        bool plant = false;
-        if (x < w) {
-            const int q = y * w + x;
-            const int r = src[3 * q], g = src[3 * q + 1], b = src[3 * q + 2];
-            const int v = max(r, max(g, b)), vmin = min(r, min(g, b)), diff = v - vmin;
-            const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
-            const int s = (__mul24(diff, sdiv[v]) + (1 << 11)) >> 12;
-            int hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
-            hh = (__mul24(hh, hdiv[diff]) + (1 << 11)) >> 12;
-            hh += hh < 0 ? 180 : 0;
-            const int R = gam[r], G = gam[g], B = gam[b];
-            const int fx = cbr[(R * 1777 + G * 1541 + B * 778 + 2048) >> 12];
-            const int fy = cbr[(R * 871 + G * 2929 + B * 296 + 2048) >> 12];
-            const int fz = cbr[(R * 73 + G * 448 + B * 3575 + 2048) >> 12];
-            const int L = clampi((296 * fy - 1336934 + 16384) >> 15, 0, 255);
-            const int la = clampi((500 * (fx - fy) + 4194304 + 16384) >> 15, 0, 255);
-            const int lb = clampi((200 * (fy - fz) + 4194304 + 16384) >> 15, 0, 255);
-            const bool strong_green = hh >= hue_lo && hh <= hue_hi && s >= 30 && v >= 30;
-            const bool dominant = g > ((r + 15) & 255) || g > ((b + 15) & 255) ||
-                                  (g > ((r + 5) & 255) && g > ((b + 5) & 255) && s >= 20);
-            const bool lab_green = la <= 125 && lb >= 120 && L >= 20 && L <= 240;
-            const bool edge = emap[q] == 2 || (x > 0 && emap[q - 1] == 2) || (x < w - 1 && emap[q + 1] == 2) ||
-                              (y > 0 && emap[q - w] == 2) || (y < h - 1 && emap[q + w] == 2);
-            const int tex = (int)gray[q] - (int)bl[q];
-            const bool background = (s <= 25 && v >= 50 && v <= 220) ||
-                                    (hh >= 120 && hh <= 160 && s >= 20 && r > g && b > g) ||
-                                    (s <= 15 && (tex < 0 ? -tex : tex) < 10);
-            plant = (strong_green || dominant || lab_green || edge) && !background;
-        }
-        const unsigned long long m = __ballot(plant);
-        if (lane == 0) {
-            uint32_t* o = bits + ((n * h + y) * (size_t)wpr + 2 * sx);
-            o[0] = (unsigned)m;
-            o[1] = (unsigned)(m >> 32);
-        }
-    }
-}
-
-// dynamic LDS of the two kernels above, or 0 when an image does not fit a CU (the multi-launch chains then run)
-static size_t fused_lds_bytes(int h, int w, bool with_bits) {
-    if (w % 4 != 0 || h < 1) return 0;
-    const size_t plane = ((size_t)h * w + 15) & ~(size_t)15;
-    const size_t wpr = 2 * (size_t)((w + 63) / 64);
-    const size_t need = 2 * plane + (with_bits ? 3 : 2) * (size_t)h * wpr * 4;   // + strong / weak (/ brown) bit planes
-    return need <= (size_t)140 * 1024 ? need : 0;
-}
+};
 
 }  // namespace
 
@@ -1062,9 +1173,7 @@ extern "C" {
 
 size_t lf_blur_saliency_workspace(int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    const size_t px = (size_t)n * h * w;
-    // 4 byte planes, the blurred RGB copy, 3 four-byte planes, the min/max table
-    return 4 * up(px) + up(3 * px) + 3 * up(4 * px) + up((size_t)n * 6 * sizeof(unsigned));
+    return SaliencyWs(nullptr, n, h, w).bytes;
 }
 
 int lf_blur_saliency_u8(const uint8_t* rgb, const uint8_t* leaf_mask, uint8_t* out, int n, int h, int w,
@@ -1082,16 +1191,12 @@ int lf_blur_saliency_u8(const uint8_t* rgb, const uint8_t* leaf_mask, uint8_t* o
     hipStream_t s = lf::as_stream(stream);
     const int hw = h * w;
     const size_t px = (size_t)n * hw;
-    uint8_t* base = static_cast<uint8_t*>(workspace);
-    uint8_t* pa = base;                      // gray -> brown -> closed -> normalised saliency
-    uint8_t* pb = pa + up(px);               // Canny map / edges -> morphology scratch -> blurred saliency
-    uint8_t* pc = pb + up(px);               // dilated edges
-    uint8_t* pd = pc + up(px);               // dilated brown regions
-    uint8_t* blurred = pd + up(px);
-    int32_t* mag2 = reinterpret_cast<int32_t*>(blurred + up(3 * px));
-    uint32_t* dxdy = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(mag2) + up(4 * px));
-    float* gmag = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(dxdy) + up(4 * px));
-    unsigned* mm = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(gmag) + up(4 * px));
+    const SaliencyWs ws(workspace, n, h, w);
+    uint8_t *pa = ws.pa, *pb = ws.pb, *pc = ws.pc, *pd = ws.pd, *blurred = ws.blurred;
+    int32_t* mag2 = ws.mag2;
+    uint32_t* dxdy = ws.dxdy;
+    float* gmag = ws.gmag;
+    unsigned* mm = ws.mm;
     float* cdiff = reinterpret_cast<float*>(mag2);  // mag2 is dead after the NMS pass
     float* sal = reinterpret_cast<float*>(dxdy);    // so is (dx, dy)
 
@@ -1100,20 +1205,17 @@ int lf_blur_saliency_u8(const uint8_t* rgb, const uint8_t* leaf_mask, uint8_t* o
     int rc;
     // images that fit a CU (two byte planes + the brown bit planes in LDS; 224 x 224 does): the 15 x 15 blur, ONE
     // workgroup per image for everything up to the normalised saliency plane, the 5 x 5 blur, the masking pass
-    if (const size_t fl = fused_lds_bytes(h, w, true)) {
-        static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(saliency_fused_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) == hipSuccess;
-        if (ok) {
-            rc = lf_gauss_blur_u8(rgb, blurred, n, h, w, 3, kq15, 15, stream);
-            if (rc != LF_OK) return rc;
-            saliency_fused_kernel<<<n, kFuseT, fl, s>>>(rgb, blurred, leaf_mask, pa, h, w, use_brown, hue_lo, hue_hi,
-                                                        s_min, v_max);
-            rc = lf_gauss_blur_u8(pa, pb, n, h, w, 1, kq5, 5, stream);
-            if (rc != LF_OK) return rc;
-            saliency_out_kernel<<<lf::stream_grid(px / 4 + 1, kBlock, lf::kFullGrid), kBlock, 0, s>>>(pb, leaf_mask,
-                                                                                                   out, px);
-            return lf::check_launch("lf_blur_saliency");
-        }
+    const size_t fl = fused_lds_bytes(h, w, true);
+    if (fl && dynamic_lds_cap<saliency_fused_kernel>(kFusedLdsCap, 0)) {
+        rc = lf_gauss_blur_u8(rgb, blurred, n, h, w, 3, kq15, 15, stream);
+        if (rc != LF_OK) return rc;
+        saliency_fused_kernel<<<n, kFuseT, fl, s>>>(rgb, blurred, leaf_mask, pa, h, w, use_brown, hue_lo, hue_hi,
+                                                    s_min, v_max);
+        rc = lf_gauss_blur_u8(pa, pb, n, h, w, 1, kq5, 5, stream);
+        if (rc != LF_OK) return rc;
+        saliency_out_kernel<<<lf::stream_grid(px / 4 + 1, kBlock, lf::kFullGrid), kBlock, 0, s>>>(pb, leaf_mask, out,
+                                                                                               px);
+        return lf::check_launch("lf_blur_saliency");
     }
     minmax_init_kernel<<<(n * 6 + 255) / 256, 256, 0, s>>>(mm, n);
     rc = lf_rgb2gray_u8(rgb, pa, px, stream);
@@ -1121,18 +1223,7 @@ int lf_blur_saliency_u8(const uint8_t* rgb, const uint8_t* leaf_mask, uint8_t* o
     sal_sobel_kernel<<<grid_fat, kBlock, 0, s>>>(pa, mag2, dxdy, gmag, mm, h, w);
     // cv2.Canny(gray, 50, 150, L2gradient=True): thresholds are compared squared
     canny_nms_kernel<<<grid_px, kBlock, 0, s>>>(mag2, dxdy, pb, h, w, 50 * 50, 150 * 150);
-    {
-        static const size_t lds_cap = []() {
-            const size_t want = 156 * 1024;
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(canny_hysteresis_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess
-                       ? want
-                       : (size_t)60 * 1024;
-        }();
-        const int in_lds = (size_t)hw <= lds_cap;
-        canny_hysteresis_kernel<<<n, kHystThreads, in_lds ? (size_t)((hw + 15) & ~15) : 0, s>>>(pb, h, w,
-                                                                                                 in_lds);
-    }
+    launch_canny_hysteresis(pb, n, h, w, s);
     // binary planes, 16-byte aligned, so rows of w % 4 == 0 pixels go four at a time
     const bool quad = w % 4 == 0;
     const dim3 grid_q((hw / 4 + kBlock - 1) / kBlock, n);
@@ -1171,40 +1262,184 @@ int lf_blur_saliency_u8(const uint8_t* rgb, const uint8_t* leaf_mask, uint8_t* o
     return lf::check_launch("lf_blur_saliency");
 }
 
-static void lab_tables_host(uint16_t* out) {   // color_lab.cpp initLabTabs: sRGBGammaTab_b, LabCbrtTab_b
-    for (int i = 0; i < 256; ++i) {
-        const float x = (float)i / 255.0f;
-        const double xd = (double)x;
-        const float lin = (float)(xd <= 0.04045 ? xd / 12.92 : pow((xd + 0.055) / 1.055, 2.4));
-        const long v = lrint((double)(2040.0f * lin));
-        out[i] = (uint16_t)(v < 0 ? 0 : (v > 65535 ? 65535 : v));
-    }
-    const float scale = 1.0f / (255.0f * 8.0f);
-    const float lthresh = 216.0f / 24389.0f, lscale = 841.0f / 108.0f, lbias = 16.0f / 116.0f;
-    for (int i = 0; i < kLabCbrtSize; ++i) {
-        const float y = scale * (float)i;
-        float f;
-        if (y < lthresh) {
-            const float prod = y * lscale;   // two roundings, as numpy's float32 arithmetic in the oracle
-            f = prod + lbias;
-        } else {
-            f = (float)cbrt((double)y);
+}  // extern "C"
+
+// ===========================================================================
+// _create_inclusive_mask (srcs/transform/filters/mask.py:727-831): the default strategy of make_mask.
+// Per-pixel colour predicates (8-bit HSV and L*a*b*, uint8 channel comparisons that wrap as numpy's
+// do), Canny (L1 gradient, 30 / 100) dilated by the 3x3 ellipse, the texture test against a 15x15
+// Gaussian of the gray plane -> one BIT per pixel; then, one workgroup per image with the bit planes
+// in LDS: open 3x3, close 9x9, close 7x7 (cv2's MORPH_ELLIPSE elements), largest 8-connected
+// component (run-length union-find), close 5x5.
+// ===========================================================================
+namespace {
+
+__global__ __launch_bounds__(kBlock) void canny_sobel_l1_kernel(const uint8_t* __restrict__ gray,
+                                                                int32_t* __restrict__ mag,
+                                                                uint32_t* __restrict__ dxdy, int h, int w) {
+    const unsigned n = blockIdx.y;
+    const int hw = h * w;
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= hw) return;
+    const int y = p / w, x = p - y * w;
+    const Sob s = sobel_at(gray + (size_t)n * hw, w, clampi(y - 1, 0, h - 1), y, clampi(y + 1, 0, h - 1),
+                           clampi(x - 1, 0, w - 1), x, clampi(x + 1, 0, w - 1));
+    mag[(size_t)n * hw + p] = (s.dx < 0 ? -s.dx : s.dx) + (s.dy < 0 ? -s.dy : s.dy);
+    dxdy[(size_t)n * hw + p] = ((unsigned)s.dx & 0xffffu) | ((unsigned)s.dy << 16);
+}
+
+// One wave per 64-pixel segment of a row; bit i of the ballot is pixel x0 + i.
+// bits[n][y][2 * seg + {0, 1}]: `wpr` = 2 * ceil(w / 64) words per row.
+__global__ __launch_bounds__(kBlock) void inclusive_pred_kernel(
+    const uint8_t* __restrict__ rgb, const uint8_t* __restrict__ gray, const uint8_t* __restrict__ blur,
+    const uint8_t* __restrict__ edges, const uint16_t* __restrict__ lab_tabs, uint32_t* __restrict__ bits,
+    int n_images, int h, int w, int hue_lo, int hue_hi) {
+    __shared__ HsvTabs H;
+    __shared__ LabTabs T;
+    H.fill(kBlock);
+    T.fill(lab_tabs, kBlock);
+    __syncthreads();
+    const int spr = (w + 63) / 64, wpr = 2 * spr;
+    const long total = (long)n_images * h * spr;
+    const int lane = threadIdx.x & 63;
+    for (long seg = (long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); seg < total;
+         seg += (long)gridDim.x * (kBlock / 64)) {
+        const int sx = (int)(seg % spr);
+        const long ry = seg / spr;
+        const int y = (int)(ry % h);
+        const size_t n = (size_t)(ry / h);
+        const int x = sx * 64 + lane;
+        bool plant = false;
+        if (x < w) {
+            const size_t p = (n * h + y) * (size_t)w + x;
+            const uint8_t* e = edges + (n * h) * (size_t)w;
+            plant = plant_px(H, T, rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2], (int)gray[p] - (int)blur[p], y, x, h, w,
+                             hue_lo, hue_hi, [&](int q) { return e[q] != 0; });
         }
-        const long v = lrint((double)(32768.0f * f));
-        out[256 + i] = (uint16_t)(v < 0 ? 0 : (v > 65535 ? 65535 : v));
+        const unsigned long long m = __ballot(plant);
+        if (lane == 0) {
+            uint32_t* o = bits + ((n * h + y) * (size_t)wpr + 2 * sx);
+            o[0] = (unsigned)m;
+            o[1] = (unsigned)(m >> 32);
+        }
     }
 }
 
-static size_t mask_runs_per_image(int h, int w) { return (size_t)h * (w / 2 + 1); }
+// gray plane (from memory) -> Canny (L1 gradient, 30 / 100) in LDS -> the per-pixel predicates of
+// _create_inclusive_mask -> one bit per pixel.
+__global__ __launch_bounds__(kFuseT) void inclusive_fused_kernel(
+    const uint8_t* __restrict__ rgb, const uint8_t* __restrict__ gray_g, const uint8_t* __restrict__ blur,
+    const uint16_t* __restrict__ lab_tabs, uint32_t* __restrict__ bits, int h, int w, int hue_lo, int hue_hi) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t fl[];
+    __shared__ HsvTabs H;
+    __shared__ LabTabs T;
+    __shared__ int changed;
+    const int hw = h * w, plane = (hw + 15) & ~15;
+    uint8_t* gray = fl;
+    uint8_t* emap = fl + plane;
+    const size_t n = blockIdx.x;
+    H.fill(kFuseT);
+    T.fill(lab_tabs, kFuseT);
+    {
+        const uint32_t* g4 = reinterpret_cast<const uint32_t*>(gray_g + n * (size_t)hw);   // hw % 4 == 0
+        for (int q = threadIdx.x; q < hw / 4; q += kFuseT) reinterpret_cast<uint32_t*>(gray)[q] = g4[q];
+    }
+    __syncthreads();
+    const int spr = (w + 63) / 64, wpr = 2 * spr;
+    canny_nms_lds<true>(gray, emap, h, w, 30, 100);   // cv2.Canny(gray, 30, 100)
+    {
+        unsigned* hs = reinterpret_cast<unsigned*>(fl + 2 * plane);
+        canny_hysteresis_lds(emap, hs, hs + h * wpr, h, w, wpr, &changed);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint8_t* src = rgb + n * (size_t)hw * 3;
+    const uint8_t* bl = blur + n * (size_t)hw;
+    for (int seg = wv; seg < h * spr; seg += kFuseT / 64) {
+        const int y = seg / spr, sx = seg - y * spr, x = sx * 64 + lane;
+        bool plant = false;
+        if (x < w) {
+            const int q = y * w + x;
+            plant = plant_px(H, T, src[3 * q], src[3 * q + 1], src[3 * q + 2], (int)gray[q] - (int)bl[q], y, x, h, w,
+                             hue_lo, hue_hi, [&](int p) { return emap[p] == 2; });
+        }
+        const unsigned long long m = __ballot(plant);
+        if (lane == 0) {
+            uint32_t* o = bits + ((n * h + y) * (size_t)wpr + 2 * sx);
+            o[0] = (unsigned)m;
+            o[1] = (unsigned)(m >> 32);
+        }
+    }
+}
+
+// One workgroup per image, the bit planes in LDS: open 3x3, close 9x9, close 7x7, the largest 8-connected
+// component, close 5x5 -> the 0 / 255 mask.
+__global__ __launch_bounds__(kBlock) void inclusive_morph_kernel(const uint32_t* __restrict__ bits,
+                                                                 uint8_t* __restrict__ out, Run* __restrict__ runs,
+                                                                 int* __restrict__ parent, int* __restrict__ area,
+                                                                 int h, int w, int wpr, int runs_per_image) {
+    extern __shared__ unsigned lds_bits[];
+    // S.status collects the step bounds of the union-find walks.  It is not reported: lf_inclusive_mask_u8 has no
+    // flags output, and a correct walk takes at most runs_per_image hops, so the bound cannot be reached.
+    __shared__ PostLds S;
+    const size_t n = blockIdx.x;
+    const Post P = post_view(lds_bits, 2, S, runs, parent, area, runs_per_image, h, w, wpr, kBlock);
+    unsigned *A = P.A, *B = P.B;
+    for (int i = threadIdx.x; i < h * wpr; i += kBlock) A[i] = bits[n * h * wpr + i];
+    if (threadIdx.x == 0) S.best = 0ull;
+    __syncthreads();
+    morph_ellipse<3>(P, A, B, true, kBlock);    // MORPH_OPEN 3x3
+    morph_ellipse<3>(P, B, A, false, kBlock);
+    morph_ellipse<9>(P, A, B, false, kBlock);   // MORPH_CLOSE 9x9
+    morph_ellipse<9>(P, B, A, true, kBlock);
+    morph_ellipse<7>(P, A, B, false, kBlock);   // MORPH_CLOSE 7x7
+    morph_ellipse<7>(P, B, A, true, kBlock);
+
+    // ---- largest 8-connected component of A -> B
+    label_runs<false>(P, A, true);
+    const int nruns = S.nruns;
+    for (int k = threadIdx.x; k < nruns; k += kBlock) {   // largest area; the earliest component among equals
+        const int a = __hip_atomic_load(P.area + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (a > 0) atomicMax(&S.best, ((unsigned long long)a << 32) | (unsigned)(0x7fffffff - k));
+    }
+    __syncthreads();
+    const int keep = 0x7fffffff - (int)(S.best & 0xffffffffull);
+    paint_runs<false>(P, B, true, [&](int root) { return root == keep; });
+    morph_ellipse<5>(P, B, A, false, kBlock);   // MORPH_CLOSE 5x5
+    morph_ellipse<5>(P, A, B, true, kBlock);
+    uint8_t* o = out + n * (size_t)h * w;
+    for (int p = threadIdx.x; p < h * w; p += kBlock) {
+        const int y = p / w, x = p - y * w;
+        o[p] = (B[y * wpr + (x >> 5)] >> (x & 31)) & 1u ? 255 : 0;
+    }
+}
+
+struct InclusiveWs {
+    uint8_t *gray, *blur, *map;
+    int32_t* mag;
+    uint32_t *dxdy, *bits;
+    LabelBufs lb;
+    size_t bytes;
+    InclusiveWs(void* base, int n, int h, int w) {
+        Carver c{base};
+        const size_t px = (size_t)n * h * w;
+        gray = c.take<uint8_t>(px);
+        blur = c.take<uint8_t>(px);       // the 15x15 Gaussian of the gray plane
+        map = c.take<uint8_t>(px);        // Canny map -> edges
+        mag = c.take<int32_t>(4 * px);    // |dx| + |dy|
+        dxdy = c.take<uint32_t>(4 * px);
+        bits = c.take<uint32_t>((size_t)n * h * 2 * ((w + 63) / 64) * 4);
+        lb.carve(c, n, h, w);
+        bytes = c.off;
+    }
+};
+
+}  // namespace
+
+extern "C" {
 
 size_t lf_inclusive_mask_workspace(int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    const size_t px = (size_t)n * h * w;
-    const size_t wpr = 2 * (size_t)((w + 63) / 64);
-    const size_t runs = (size_t)n * mask_runs_per_image(h, w);
-    // gray, blurred gray, Canny map; |dx| + |dy| and (dx, dy); the bit planes; runs, parents, areas; the two tables
-    return 3 * up(px) + 2 * up(4 * px) + up((size_t)n * h * wpr * 4) + up(runs * sizeof(MaskRun)) + 2 * up(runs * 4) +
-           up((256 + kLabCbrtSize) * sizeof(uint16_t));
+    return InclusiveWs(nullptr, n, h, w).bytes;
 }
 
 int lf_inclusive_mask_u8(const uint8_t* rgb, uint8_t* mask, int n, int h, int w, int green_lo, int green_hi,
@@ -1217,76 +1452,37 @@ int lf_inclusive_mask_u8(const uint8_t* rgb, uint8_t* mask, int n, int h, int w,
                ws_bytes, lf_inclusive_mask_workspace(n, h, w));
     LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, "lf_inclusive_mask: workspace must be 16-byte aligned");
     const int wpr = 2 * ((w + 63) / 64);
-    const size_t lds = (size_t)2 * h * wpr * 4 + (size_t)(h + 1) * 4;
-    static const size_t lds_cap = []() {
-        const size_t want = 150 * 1024;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(inclusive_morph_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess
-                   ? want
-                   : (size_t)60 * 1024;
-    }();
+    const size_t lds = post_lds_bytes(2, h, wpr);
+    const size_t lds_cap = dynamic_lds_cap<inclusive_morph_kernel>(150 * 1024, 60 * 1024);
     LF_REQUIRE(lds <= lds_cap, "lf_inclusive_mask: a %d x %d image needs %zu bytes of LDS for its bit planes (limit %zu)",
                h, w, lds, lds_cap);
     hipStream_t s = lf::as_stream(stream);
     const int hw = h * w;
     const size_t px = (size_t)n * hw;
-    const size_t runs = (size_t)n * mask_runs_per_image(h, w);
-    uint8_t* base = static_cast<uint8_t*>(workspace);
-    uint8_t* gray = base;
-    uint8_t* blur = gray + up(px);
-    uint8_t* map = blur + up(px);
-    int32_t* mag = reinterpret_cast<int32_t*>(map + up(px));
-    uint32_t* dxdy = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(mag) + up(4 * px));
-    uint32_t* bits = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(dxdy) + up(4 * px));
-    MaskRun* rn = reinterpret_cast<MaskRun*>(reinterpret_cast<uint8_t*>(bits) + up((size_t)n * h * wpr * 4));
-    int* parent = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(rn) + up(runs * sizeof(MaskRun)));
-    int* area = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(parent) + up(runs * 4));
-    uint16_t* tabs = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(area) + up(runs * 4));
+    const InclusiveWs ws(workspace, n, h, w);
+    const int hue_lo = std::max(0, green_lo - 10), hue_hi = std::min(179, green_hi + 15);
 
-    static const std::vector<uint16_t> host_tabs = []() {
-        std::vector<uint16_t> t(256 + kLabCbrtSize);
-        lab_tables_host(t.data());
-        return t;
-    }();
-    if (hipMemcpyAsync(tabs, host_tabs.data(), host_tabs.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s) != hipSuccess) {
-        lf::set_error("lf_inclusive_mask: table upload failed");
-        return LF_ERR_LAUNCH;
-    }
-    int rc = lf_rgb2gray_u8(rgb, gray, px, stream);
+    int rc = upload_lab_tables(ws.lb.tabs, s, "lf_inclusive_mask");
     if (rc != LF_OK) return rc;
-    rc = lf_gauss_blur_u8(gray, blur, n, h, w, 1, kq15, 15, stream);
+    rc = lf_rgb2gray_u8(rgb, ws.gray, px, stream);
     if (rc != LF_OK) return rc;
-    if (const size_t fl = fused_lds_bytes(h, w, false)) {
+    rc = lf_gauss_blur_u8(ws.gray, ws.blur, n, h, w, 1, kq15, 15, stream);
+    if (rc != LF_OK) return rc;
+    const size_t fl = fused_lds_bytes(h, w, false);
+    if (fl && dynamic_lds_cap<inclusive_fused_kernel>(kFusedLdsCap, 0)) {
         // the image fits a CU: Canny and the predicates in one workgroup per image, gray plane and map in LDS
-        static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(inclusive_fused_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) == hipSuccess;
-        if (ok) {
-            inclusive_fused_kernel<<<n, kFuseT, fl, s>>>(rgb, gray, blur, tabs, bits, h, w, std::max(0, green_lo - 10),
-                                                         std::min(179, green_hi + 15));
-            inclusive_morph_kernel<<<n, kBlock, lds, s>>>(bits, mask, rn, parent, area, h, w, wpr,
-                                                          (int)mask_runs_per_image(h, w));
-            return lf::check_launch("lf_inclusive_mask");
-        }
+        inclusive_fused_kernel<<<n, kFuseT, fl, s>>>(rgb, ws.gray, ws.blur, ws.lb.tabs, ws.bits, h, w, hue_lo, hue_hi);
+    } else {
+        const dim3 grid_px((hw + kBlock - 1) / kBlock, n);
+        canny_sobel_l1_kernel<<<grid_px, kBlock, 0, s>>>(ws.gray, ws.mag, ws.dxdy, h, w);
+        canny_nms_kernel<<<grid_px, kBlock, 0, s>>>(ws.mag, ws.dxdy, ws.map, h, w, 30, 100);   // cv2.Canny(gray, 30, 100)
+        launch_canny_hysteresis(ws.map, n, h, w, s);
+        const long segs = (long)n * h * ((w + 63) / 64);
+        const unsigned pgrid = (unsigned)std::min<long>((segs + 3) / 4, 2048);
+        inclusive_pred_kernel<<<pgrid, kBlock, 0, s>>>(rgb, ws.gray, ws.blur, ws.map, ws.lb.tabs, ws.bits, n, h, w,
+                                                       hue_lo, hue_hi);
     }
-    const dim3 grid_px((hw + kBlock - 1) / kBlock, n);
-    canny_sobel_l1_kernel<<<grid_px, kBlock, 0, s>>>(gray, mag, dxdy, h, w);
-    canny_nms_kernel<<<grid_px, kBlock, 0, s>>>(mag, dxdy, map, h, w, 30, 100);   // cv2.Canny(gray, 30, 100)
-    {
-        static const size_t hyst_cap = []() {
-            const size_t want = 156 * 1024;
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(canny_hysteresis_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess
-                       ? want
-                       : (size_t)60 * 1024;
-        }();
-        const int in_lds = (size_t)hw <= hyst_cap;
-        canny_hysteresis_kernel<<<n, kHystThreads, in_lds ? (size_t)((hw + 15) & ~15) : 0, s>>>(map, h, w, in_lds);
-    }
-    const long segs = (long)n * h * ((w + 63) / 64);
-    const unsigned pgrid = (unsigned)std::min<long>((segs + 3) / 4, 2048);
-    inclusive_pred_kernel<<<pgrid, kBlock, 0, s>>>(rgb, gray, blur, map, tabs, bits, n, h, w,
-                                                   std::max(0, green_lo - 10), std::min(179, green_hi + 15));
-    inclusive_morph_kernel<<<n, kBlock, lds, s>>>(bits, mask, rn, parent, area, h, w, wpr,
+    inclusive_morph_kernel<<<n, kBlock, lds, s>>>(ws.bits, mask, ws.lb.rn, ws.lb.parent, ws.lb.area, h, w, wpr,
                                                   (int)mask_runs_per_image(h, w));
     return lf::check_launch("lf_inclusive_mask");
 }
@@ -1325,23 +1521,10 @@ int lf_inclusive_mask_u8(const uint8_t* rgb, uint8_t* mask, int n, int h, int w,
 // ===========================================================================
 namespace {
 
-constexpr int kMaskT = 256;
-constexpr int kSeMax = 32;
-constexpr int kFlagFallback = 1, kFlagBound = 4;
-
-struct SeRows {   // a structuring element as per-row column ranges relative to its anchor
-    int k, ay;
-    signed char lo[kSeMax], hi[kSeMax];   // lo > hi: empty row
-};
-
 struct MaskArgs {
     int fill_size, channel;   // channel: 0 H, 1 S, 2 V of PlantCV's rgb2gray_hsv
     int use_lab, hue_lo, hue_hi, s_min, v_max, a_min, b_min, brown_min_area;
     SeRows se_morph, se_search, se_brown;
-};
-
-struct Run {
-    unsigned short x0, x1, y, pad;
 };
 
 __device__ __forceinline__ void cubic_q11(float x, int* c) {   // interpolateCubic, then saturate_cast<short>(c * 2048)
@@ -1393,162 +1576,10 @@ __global__ __launch_bounds__(kBlock) void cubic_resize_kernel(const uint8_t* __r
     }
 }
 
-// one workgroup per image: the planes live in LDS, runs / parents / areas in the image's slice of the workspace
-struct Post {
-    unsigned *A, *B, *C, *D;
-    int* rowstart;
-    Run* rn;
-    int* par;
-    int* area;
-    int h, w, wpr, max_runs;
-    int* nruns;    // LDS
-    int* status;   // LDS
-    int* flag;     // LDS [2]
-    unsigned long long* best;   // LDS
-};
-
-__device__ __forceinline__ unsigned valid_bits(const Post& P, int xw) {
-    const int used = (P.w + 31) >> 5;
-    const unsigned last = (P.w & 31) ? ((1u << (P.w & 31)) - 1u) : 0xffffffffu;
-    return xw < used - 1 ? 0xffffffffu : (xw == used - 1 ? last : 0u);
-}
-
-__device__ __forceinline__ bool bit_at(const Post& P, const unsigned* pl, int x, int y) {
-    if ((unsigned)x >= (unsigned)P.w || (unsigned)y >= (unsigned)P.h) return false;
-    return (pl[y * P.wpr + (x >> 5)] >> (x & 31)) & 1u;
-}
-
-// dst = dilate / erode(src) by the element; pixels outside the image never win
-__device__ void morph_se(const Post& P, const unsigned* src, unsigned* dst, const SeRows& se, bool erode) {
-    const int h = P.h, wpr = P.wpr;
-    for (int i = threadIdx.x; i < h * wpr; i += kMaskT) {
-        const int y = i / wpr, xw = i - y * wpr;
-        unsigned out = 0;
-        for (int r = 0; r < se.k; ++r) {
-            const int yy = y + r - se.ay, lo = se.lo[r], hi = se.hi[r];
-            if (yy < 0 || yy >= h || lo > hi) continue;
-            auto word = [&](int x) -> unsigned {
-                if (x < 0 || x >= wpr) return 0u;
-                const unsigned v = src[yy * wpr + x];
-                return erode ? ~v & valid_bits(P, x) : v;
-            };
-            const unsigned long long cur = word(xw), prev = word(xw - 1), next = word(xw + 1);
-            const unsigned long long hiw = (next << 32) | cur, low = (cur << 32) | prev;
-            for (int j = lo; j <= hi; ++j) out |= (unsigned)(j >= 0 ? hiw >> j : low >> (32 + j));
-        }
-        dst[i] = (erode ? ~out : out) & valid_bits(P, xw);
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ int ld_par(int* p, int x) {
-    return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ int bfind(const Post& P, int x) {
-    for (int i = 0; i <= P.max_runs; ++i) {
-        const int px = ld_par(P.par, x);
-        if (px == x) return x;
-        x = px;
-    }
-    atomicOr(P.status, kFlagBound);
-    return x;
-}
-__device__ void bunion(const Post& P, int a, int b) {
-    for (int i = 0; i <= P.max_runs; ++i) {
-        a = bfind(P, a);
-        b = bfind(P, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(P.par + b, a);   // roots only move to a smaller index: a root is its first run
-        if (old == b) return;
-        b = old;
-    }
-    atomicOr(P.status, kFlagBound);
-}
-
-// runs of `src`, their connected components (par[k] = root = the component's first run in raster order) and areas
-__device__ void label_runs(const Post& P, const unsigned* src, bool conn8) {
-    const int h = P.h, w = P.w, wpr = P.wpr;
-    for (int y = threadIdx.x; y < h; y += kMaskT) {
-        int c = 0, x = 0, s, e;
-        while (next_run(src + y * wpr, w, x, s, e)) {
-            ++c;
-            x = e + 1;
-        }
-        P.rowstart[y + 1] = c;
-    }
-    if (threadIdx.x == 0) P.rowstart[0] = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int y = 0; y < h; ++y) P.rowstart[y + 1] += P.rowstart[y];
-        *P.nruns = P.rowstart[h];
-    }
-    __syncthreads();
-    for (int y = threadIdx.x; y < h; y += kMaskT) {
-        int k = P.rowstart[y], x = 0, s, e;
-        while (next_run(src + y * wpr, w, x, s, e)) {
-            P.rn[k] = Run{(unsigned short)s, (unsigned short)e, (unsigned short)y, 0};
-            P.par[k] = k;
-            P.area[k] = 0;
-            ++k;
-            x = e + 1;
-        }
-    }
-    __threadfence();
-    __syncthreads();
-    const int g = conn8 ? 1 : 0;
-    for (int y = 1 + threadIdx.x; y < h; y += kMaskT) {
-        int a = P.rowstart[y - 1], b = P.rowstart[y];
-        const int a_end = P.rowstart[y], b_end = P.rowstart[y + 1];
-        while (a < a_end && b < b_end) {
-            const Run ra = P.rn[a], rb = P.rn[b];
-            if ((int)ra.x0 <= (int)rb.x1 + g && (int)ra.x1 + g >= (int)rb.x0) bunion(P, a, b);
-            if (ra.x1 < rb.x1) ++a;
-            else ++b;
-        }
-    }
-    __threadfence();
-    __syncthreads();
-    const int nr = *P.nruns;
-    for (int k = threadIdx.x; k < nr; k += kMaskT) {
-        const int root = bfind(P, k);
-        atomicAdd(P.area + root, (int)P.rn[k].x1 - (int)P.rn[k].x0 + 1);
-    }
-    __threadfence();
-    __syncthreads();
-    for (int k = threadIdx.x; k < nr; k += kMaskT) P.par[k] = bfind(P, k);   // flatten: par[k] is the root
-    __threadfence();
-    __syncthreads();
-}
-
-// dst = the runs whose component passes keep(root); each thread owns whole rows
-template <typename F>
-__device__ void paint_runs(const Post& P, unsigned* dst, bool clear, F keep) {
-    for (int y = threadIdx.x; y < P.h; y += kMaskT) {
-        unsigned* row = dst + y * P.wpr;
-        if (clear)
-            for (int i = 0; i < P.wpr; ++i) row[i] = 0u;
-        for (int k = P.rowstart[y]; k < P.rowstart[y + 1]; ++k) {
-            if (!keep(ld_par(P.par, k))) continue;
-            const Run r = P.rn[k];
-            for (int x = r.x0; x <= (int)r.x1;) {
-                const int b = x & 31, len = min(32 - b, (int)r.x1 - x + 1);
-                row[x >> 5] |= (len == 32 ? 0xffffffffu : ((1u << len) - 1u)) << b;
-                x += len;
-            }
-        }
-    }
-    __syncthreads();
-}
-
 // D = the background 4-connected to the zero-padded frame around `bar`
 __device__ void flood_outer(const Post& P, const unsigned* bar, unsigned* D) {
     const int h = P.h, w = P.w, wpr = P.wpr;
-    for (int i = threadIdx.x; i < h * wpr; i += kMaskT) {
+    for (int i = threadIdx.x; i < h * wpr; i += P.nt) {
         const int y = i / wpr, xw = i - y * wpr;
         unsigned s = 0;
         if (y == 0 || y == h - 1) s = 0xffffffffu;
@@ -1560,7 +1591,7 @@ __device__ void flood_outer(const Post& P, const unsigned* bar, unsigned* D) {
     __syncthreads();
     for (int it = 0;; ++it) {
         int local = 0;
-        for (int i = threadIdx.x; i < h * wpr; i += kMaskT) {
+        for (int i = threadIdx.x; i < h * wpr; i += P.nt) {
             const int y = i / wpr, xw = i - y * wpr;
             const unsigned m = ~bar[i] & valid_bits(P, xw), d = D[i];
             unsigned g = d | (d << 1) | (d >> 1);
@@ -1657,7 +1688,7 @@ __device__ int largest_external(const Post& P, long long& area2) {
     if (threadIdx.x == 0) *P.best = 0ull;
     __syncthreads();
     const int nr = *P.nruns;
-    for (int k = threadIdx.x; k < nr; k += kMaskT) {
+    for (int k = threadIdx.x; k < nr; k += P.nt) {
         if (P.par[k] != k) continue;
         const Run r = P.rn[k];
         if (r.x0 > 0 && !bit_at(P, P.D, r.x0 - 1, r.y)) continue;   // inside a hole of another component
@@ -1677,70 +1708,35 @@ __device__ int largest_external(const Post& P, long long& area2) {
 __device__ bool postprocess(const Post& P, const MaskArgs& a, long long& area2) {
     label_runs(P, P.A, false);   // pcv.fill: 4-connected components below fill_size go
     paint_runs(P, P.A, true, [&](int root) { return P.area[root] >= a.fill_size; });
-    morph_se(P, P.A, P.B, a.se_morph, false);   // MORPH_CLOSE
-    morph_se(P, P.B, P.A, a.se_morph, true);
-    morph_se(P, P.A, P.B, a.se_morph, true);    // MORPH_OPEN
-    morph_se(P, P.B, P.A, a.se_morph, false);
+    morph_se(P, P.A, P.B, a.se_morph, false, P.nt);   // MORPH_CLOSE
+    morph_se(P, P.B, P.A, a.se_morph, true, P.nt);
+    morph_se(P, P.A, P.B, a.se_morph, true, P.nt);    // MORPH_OPEN
+    morph_se(P, P.B, P.A, a.se_morph, false, P.nt);
     const int best = largest_external(P, area2);
     if (best < 0) return false;
     paint_runs(P, P.B, true, [&](int root) { return root == best; });   // drawContours(filled)
     flood_outer(P, P.B, P.D);
-    for (int i = threadIdx.x; i < P.h * P.wpr; i += kMaskT) P.A[i] = ~P.D[i] & valid_bits(P, i % P.wpr);
+    for (int i = threadIdx.x; i < P.h * P.wpr; i += P.nt) P.A[i] = ~P.D[i] & valid_bits(P, i % P.wpr);
     __syncthreads();
     return true;
 }
 
-struct PixelTabs {
-    int sdiv[256], hdiv[256];
-    uint16_t gam[256], cbr[kLabCbrtSize];
-};
-
-__device__ __forceinline__ void hsv_px(const PixelTabs& T, int r, int g, int b, int& hh, int& s, int& v) {
-    v = max(r, max(g, b));
-    const int vmin = min(r, min(g, b)), diff = v - vmin;
-    const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
-    s = (__mul24(diff, T.sdiv[v]) + (1 << 11)) >> 12;
-    hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
-    hh = (__mul24(hh, T.hdiv[diff]) + (1 << 11)) >> 12;
-    hh += hh < 0 ? 180 : 0;
-}
-
 // PlantCV's rgb2gray_hsv converts with COLOR_BGR2HSV although it is handed RGB: H is taken from the swapped pixel.
 // S and V do not change under an R / B swap, so the default channel "s" is unaffected by that mix-up.
-__device__ __forceinline__ int channel_px(const PixelTabs& T, const uint8_t* p, int channel) {
+__device__ __forceinline__ int channel_px(const HsvTabs& T, const uint8_t* p, int channel) {
     int hh, s, v;
     hsv_px(T, p[2], p[1], p[0], hh, s, v);
     return channel == 0 ? hh : (channel == 1 ? s : v);
 }
 
-__device__ __forceinline__ bool brown_px(const PixelTabs& T, const uint8_t* p, const MaskArgs& a) {
+__device__ __forceinline__ bool brown_px(const HsvTabs& H, const LabTabs& T, const uint8_t* p, const MaskArgs& a) {
     const int r = p[0], g = p[1], b = p[2];
     if (a.use_lab) {
-        const int R = T.gam[r], G = T.gam[g], B = T.gam[b];
-        const int fx = T.cbr[(R * 1777 + G * 1541 + B * 778 + 2048) >> 12];
-        const int fy = T.cbr[(R * 871 + G * 2929 + B * 296 + 2048) >> 12];
-        const int fz = T.cbr[(R * 73 + G * 448 + B * 3575 + 2048) >> 12];
-        const int la = clampi((500 * (fx - fy) + 4194304 + 16384) >> 15, 0, 255);
-        const int lb = clampi((200 * (fy - fz) + 4194304 + 16384) >> 15, 0, 255);
+        int L, la, lb;
+        lab_px(T, r, g, b, L, la, lb);
         return la >= a.a_min && lb >= a.b_min;
     }
-    int hh, s, v;
-    hsv_px(T, r, g, b, hh, s, v);
-    return hh >= a.hue_lo && hh <= a.hue_hi && s >= a.s_min && v <= a.v_max;
-}
-
-// plane[word] = pred(pixel) for every pixel of the working image (and the search plane, when given)
-template <typename F>
-__device__ void build_plane(const Post& P, unsigned* dst, F pred) {
-    for (int i = threadIdx.x; i < P.h * P.wpr; i += kMaskT) {
-        const int y = i / P.wpr, xw = i - y * P.wpr;
-        unsigned m = 0;
-        const int xe = min(32, P.w - 32 * xw);
-        for (int b = 0; b < xe; ++b)
-            if (pred(y, 32 * xw + b)) m |= 1u << b;
-        dst[i] = m;
-    }
-    __syncthreads();
+    return brown_hsv(H, r, g, b, a.hue_lo, a.hue_hi, a.s_min, a.v_max);
 }
 
 __global__ __launch_bounds__(kMaskT) void make_mask_post_kernel(
@@ -1750,47 +1746,26 @@ __global__ __launch_bounds__(kMaskT) void make_mask_post_kernel(
     uint8_t* __restrict__ out_mask, int* __restrict__ contour, int* __restrict__ counts, int* __restrict__ flags,
     int cap) {
     extern __shared__ unsigned lds_planes[];
-    __shared__ PixelTabs T;
-    __shared__ int s_nruns, s_status, s_flag[2], s_hist[256], s_thresh;
-    __shared__ unsigned long long s_best;
+    __shared__ HsvTabs H;
+    __shared__ LabTabs T;
+    __shared__ PostLds S;
+    __shared__ int s_hist[256], s_thresh;
     const size_t n = blockIdx.x;
-    Post P;
-    const int plane = h * wpr;
-    P.A = lds_planes;
-    P.B = P.A + plane;
-    P.C = P.B + plane;
-    P.D = P.C + plane;
-    P.rowstart = reinterpret_cast<int*>(P.D + plane);
-    P.rn = runs + n * runs_per_image;
-    P.par = parent + n * runs_per_image;
-    P.area = area + n * runs_per_image;
-    P.h = h;
-    P.w = w;
-    P.wpr = wpr;
-    P.max_runs = runs_per_image;
-    P.nruns = &s_nruns;
-    P.status = &s_status;
-    P.flag = s_flag;
-    P.best = &s_best;
-    for (int i = threadIdx.x; i < 256; i += kMaskT) {
-        T.sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
-        T.hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
-        T.gam[i] = lab_tabs[i];
-        s_hist[i] = 0;
-    }
-    for (int i = threadIdx.x; i < kLabCbrtSize; i += kMaskT) T.cbr[i] = lab_tabs[256 + i];
-    if (threadIdx.x == 0) s_status = 0;
+    const Post P = post_view(lds_planes, 4, S, runs, parent, area, runs_per_image, h, w, wpr, kMaskT);
+    H.fill(kMaskT);
+    T.fill(lab_tabs, kMaskT);
+    for (int i = threadIdx.x; i < 256; i += kMaskT) s_hist[i] = 0;
     const uint8_t* img = rgbw + n * (size_t)h * w * 3;
     const uint8_t* cm = cand + n * (size_t)h * w;
     __syncthreads();
 
-    build_plane(P, P.A, [&](int y, int x) { return cm[y * w + x] > 0; });
+    build_plane(P, P.A, kMaskT, [&](int y, int x) { return cm[y * w + x] > 0; });
     long long area2 = 0;
     const bool found = postprocess(P, a, area2);
     int flag = 0;
     if (!found || area2 <= 2) {   // _score_mask == -1: no best mask -> _create_fallback_mask
         flag |= kFlagFallback;
-        for (int p = threadIdx.x; p < h * w; p += kMaskT) atomicAdd(&s_hist[channel_px(T, img + 3 * p, a.channel)], 1);
+        for (int p = threadIdx.x; p < h * w; p += kMaskT) atomicAdd(&s_hist[channel_px(H, img + 3 * p, a.channel)], 1);
         __syncthreads();
         if (threadIdx.x == 0) {   // getThreshVal_Otsu_8u
             const double scale = 1.0 / ((double)h * w);
@@ -1818,20 +1793,20 @@ __global__ __launch_bounds__(kMaskT) void make_mask_post_kernel(
         }
         __syncthreads();
         const int t = s_thresh;
-        build_plane(P, P.A, [&](int y, int x) { return channel_px(T, img + 3 * (y * w + x), a.channel) > t; });
+        build_plane(P, P.A, kMaskT, [&](int y, int x) { return channel_px(H, img + 3 * (y * w + x), a.channel) > t; });
         postprocess(P, a, area2);
     }
 
     // _extend_mask_with_brown_regions
-    morph_se(P, P.A, P.B, a.se_search, false);
-    morph_se(P, P.B, P.C, a.se_search, false);
-    build_plane(P, P.B, [&](int y, int x) {
-        return ((P.C[y * wpr + (x >> 5)] >> (x & 31)) & 1u) && brown_px(T, img + 3 * (y * w + x), a);
+    morph_se(P, P.A, P.B, a.se_search, false, kMaskT);
+    morph_se(P, P.B, P.C, a.se_search, false, kMaskT);
+    build_plane(P, P.B, kMaskT, [&](int y, int x) {
+        return ((P.C[y * wpr + (x >> 5)] >> (x & 31)) & 1u) && brown_px(H, T, img + 3 * (y * w + x), a);
     });
-    morph_se(P, P.B, P.C, a.se_brown, true);   // MORPH_OPEN
-    morph_se(P, P.C, P.B, a.se_brown, false);
-    morph_se(P, P.B, P.C, a.se_brown, false);  // MORPH_CLOSE
-    morph_se(P, P.C, P.B, a.se_brown, true);
+    morph_se(P, P.B, P.C, a.se_brown, true, kMaskT);   // MORPH_OPEN
+    morph_se(P, P.C, P.B, a.se_brown, false, kMaskT);
+    morph_se(P, P.B, P.C, a.se_brown, false, kMaskT);  // MORPH_CLOSE
+    morph_se(P, P.C, P.B, a.se_brown, true, kMaskT);
     label_runs(P, P.B, true);
     paint_runs(P, P.A, false, [&](int root) { return P.area[root] >= a.brown_min_area; });
     const int best = largest_external(P, area2);
@@ -1856,35 +1831,27 @@ __global__ __launch_bounds__(kMaskT) void make_mask_post_kernel(
         o[p] = (P.A[sy * wpr + (sx >> 5)] >> (sx & 31)) & 1u ? 255 : 0;
     }
     __syncthreads();
-    if (threadIdx.x == 0) flags[n] = flag | s_status;
-}
-
-// getStructuringElement(MORPH_ELLIPSE, (k, k)) with the default anchor (k / 2, k / 2)
-static SeRows ellipse_rows(int k) {
-    SeRows se{};
-    se.k = k;
-    se.ay = k / 2;
-    const int r = k / 2, c = k / 2;
-    const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
-    for (int i = 0; i < k; ++i) {
-        int j1 = 0, j2 = 0;
-        const int dy = i - r;
-        if (std::abs(dy) <= r) {
-            const int dx = (int)nearbyint(c * std::sqrt((r * r - dy * dy) * inv_r2));
-            j1 = std::max(c - dx, 0);
-            j2 = std::min(c + dx + 1, k);
-        }
-        se.lo[i] = (signed char)(j1 - c);
-        se.hi[i] = (signed char)(j2 - 1 - c);
-    }
-    return se;
+    if (threadIdx.x == 0) flags[n] = flag | S.status;
 }
 
 constexpr size_t kMaskLdsCap = 140 * 1024;
 
-static size_t make_mask_lds(int wh, int ww) {
-    return (size_t)4 * wh * ((ww + 31) / 32) * 4 + (size_t)(wh + 1) * 4;
-}
+struct MakeMaskWs {
+    uint8_t *work, *cand, *incl;
+    size_t incl_bytes;
+    LabelBufs lb;
+    size_t bytes;
+    MakeMaskWs(void* base, int n, int wh, int ww) {
+        Carver c{base};
+        const size_t wpx = (size_t)n * wh * ww;
+        work = c.take<uint8_t>(3 * wpx);   // the working image
+        cand = c.take<uint8_t>(wpx);       // the candidate mask
+        incl_bytes = InclusiveWs(nullptr, n, wh, ww).bytes;
+        incl = c.take<uint8_t>(incl_bytes);   // the candidate's own workspace
+        lb.carve(c, n, wh, ww);
+        bytes = c.off;
+    }
+};
 
 }  // namespace
 
@@ -1892,11 +1859,7 @@ extern "C" {
 
 size_t lf_make_mask_workspace(int n, int h, int w, int wh, int ww) {
     if (n <= 0 || h <= 0 || w <= 0 || wh <= 0 || ww <= 0) return 0;
-    const size_t wpx = (size_t)n * wh * ww;
-    const size_t runs = (size_t)n * mask_runs_per_image(wh, ww);
-    // working image, candidate mask, the candidate's own workspace, runs / parents / areas, the L*a*b* tables
-    return up(3 * wpx) + up(wpx) + up(lf_inclusive_mask_workspace(n, wh, ww)) + up(runs * sizeof(Run)) +
-           2 * up(runs * 4) + up((256 + kLabCbrtSize) * sizeof(uint16_t));
+    return MakeMaskWs(nullptr, n, wh, ww).bytes;
 }
 
 int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t* counts, int32_t* flags, int n,
@@ -1909,7 +1872,7 @@ int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t
     LF_REQUIRE(rescale || (wh == h && ww == w), "lf_make_mask: without rescaling the working size is the input size");
     LF_REQUIRE(!rescale || scale > 0.0, "lf_make_mask: scale must be positive");
     LF_REQUIRE(wh <= 65535 && ww <= 65535, "lf_make_mask: working image too large (%d x %d)", wh, ww);
-    const size_t lds = make_mask_lds(wh, ww);
+    const size_t lds = post_lds_bytes(4, wh, (ww + 31) / 32);
     LF_REQUIRE(lds <= kMaskLdsCap,
                "lf_make_mask: a %d x %d working image needs %zu bytes of LDS for its four bit planes (limit %zu, one "
                "workgroup per image)", wh, ww, lds, kMaskLdsCap);
@@ -1919,22 +1882,12 @@ int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t
     LF_REQUIRE(ws_bytes >= lf_make_mask_workspace(n, h, w, wh, ww), "lf_make_mask: workspace too small (%zu < %zu)",
                ws_bytes, lf_make_mask_workspace(n, h, w, wh, ww));
     LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "lf_make_mask: workspace must be 256-byte aligned");
-    static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(make_mask_post_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)kMaskLdsCap) == hipSuccess;
-    LF_REQUIRE(lds_ok || lds <= 48 * 1024, "lf_make_mask: could not raise the LDS limit of the mask kernel");
+    LF_REQUIRE(lds <= dynamic_lds_cap<make_mask_post_kernel>(kMaskLdsCap, 48 * 1024),
+               "lf_make_mask: could not raise the LDS limit of the mask kernel");
 
     hipStream_t s = lf::as_stream(stream);
     const size_t wpx = (size_t)n * wh * ww;
-    const size_t runs = (size_t)n * mask_runs_per_image(wh, ww);
-    uint8_t* work = static_cast<uint8_t*>(workspace);
-    uint8_t* cand = work + up(3 * wpx);
-    uint8_t* incl = cand + up(wpx);
-    const size_t incl_bytes = lf_inclusive_mask_workspace(n, wh, ww);
-    Run* rn = reinterpret_cast<Run*>(incl + up(incl_bytes));
-    int* parent = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(rn) + up(runs * sizeof(Run)));
-    int* area = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(parent) + up(runs * 4));
-    uint16_t* tabs = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(area) + up(runs * 4));
+    const MakeMaskWs ws(workspace, n, wh, ww);
 
     MaskArgs a{};
     a.fill_size = prm->fill_size;
@@ -1951,30 +1904,23 @@ int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t
     a.se_search = ellipse_rows(20);
     a.se_brown = ellipse_rows(prm->brown_morph_kernel);
 
-    static const std::vector<uint16_t> host_tabs = []() {
-        std::vector<uint16_t> t(256 + kLabCbrtSize);
-        lab_tables_host(t.data());
-        return t;
-    }();
-    if (hipMemcpyAsync(tabs, host_tabs.data(), host_tabs.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s) !=
-        hipSuccess) {
-        lf::set_error("lf_make_mask: table upload failed");
-        return LF_ERR_LAUNCH;
-    }
+    int rc = upload_lab_tables(ws.lb.tabs, s, "lf_make_mask");
+    if (rc != LF_OK) return rc;
     const uint8_t* src = rgb;
     if (rescale) {
         const double sy = 1.0 / ((double)wh / h), sx = 1.0 / ((double)ww / w);
-        cubic_resize_kernel<<<lf::stream_grid(wpx, kBlock), kBlock, 0, s>>>(rgb, work, n, h, w, wh, ww, sy, sx);
-        const int rc = lf::check_launch("lf_make_mask (resize)");
+        cubic_resize_kernel<<<lf::stream_grid(wpx, kBlock), kBlock, 0, s>>>(rgb, ws.work, n, h, w, wh, ww, sy, sx);
+        rc = lf::check_launch("lf_make_mask (resize)");
         if (rc != LF_OK) return rc;
-        src = work;
+        src = ws.work;
     }
-    int rc = lf_inclusive_mask_u8(src, cand, n, wh, ww, prm->green_lo, prm->green_hi, kq15, incl, incl_bytes, stream);
+    rc = lf_inclusive_mask_u8(src, ws.cand, n, wh, ww, prm->green_lo, prm->green_hi, kq15, ws.incl, ws.incl_bytes,
+                              stream);
     if (rc != LF_OK) return rc;
     const double ify = 1.0 / ((double)h / wh), ifx = 1.0 / ((double)w / ww);
-    make_mask_post_kernel<<<n, kMaskT, lds, s>>>(src, cand, tabs, rn, parent, area, (int)mask_runs_per_image(wh, ww),
-                                                 wh, ww, (ww + 31) / 32, h, w, rescale, ify, ifx, (float)scale, a,
-                                                 mask, contour, counts, flags, cap);
+    make_mask_post_kernel<<<n, kMaskT, lds, s>>>(src, ws.cand, ws.lb.tabs, ws.lb.rn, ws.lb.parent, ws.lb.area,
+                                                 (int)mask_runs_per_image(wh, ww), wh, ww, (ww + 31) / 32, h, w,
+                                                 rescale, ify, ifx, (float)scale, a, mask, contour, counts, flags, cap);
     return lf::check_launch("lf_make_mask");
 }
 
@@ -1982,7 +1928,7 @@ int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t
 
 // ===========================================================================
 // apply_brown_filter (srcs/transform/filters/brown.py) for a same-size batch: one workgroup per image, two bit
-// planes in LDS, the helpers of make_mask_post_kernel above (brown_px, morph_se, label_runs, paint_runs).
+// planes in LDS, the shared helpers (brown_px, morph_se, label_runs, paint_runs).
 //  * leaf = mask > 0; the predicate on the pixel as handed in (no R / B swap): 8-bit HSV (H in [0, 180))
 //    lo <= h <= hi, s >= s_min, v <= v_max, or L*a*b* a >= a_min, b >= b_min when use_lab; ANDed with leaf.
 //  * MORPH_OPEN then MORPH_CLOSE with getStructuringElement(MORPH_ELLIPSE, (k, k)), default borders: pixels outside
@@ -2001,34 +1947,15 @@ __global__ __launch_bounds__(kMaskT) void brown_spots_kernel(const uint8_t* __re
                                                              uint8_t* __restrict__ out, int* __restrict__ stats,
                                                              int* __restrict__ flags) {
     extern __shared__ unsigned lds_planes[];
-    __shared__ PixelTabs T;
-    __shared__ int s_nruns, s_status, s_flag[2], s_count, s_brown, s_leaf;
-    __shared__ unsigned long long s_best;
+    __shared__ HsvTabs H;
+    __shared__ LabTabs T;
+    __shared__ PostLds S;
+    __shared__ int s_count, s_brown, s_leaf;
     const size_t n = blockIdx.x;
-    Post P;
-    const int plane = h * wpr;
-    P.A = lds_planes;
-    P.B = P.A + plane;
-    P.C = P.D = nullptr;
-    P.rowstart = reinterpret_cast<int*>(P.B + plane);
-    P.rn = runs + n * runs_per_image;
-    P.par = parent + n * runs_per_image;
-    P.area = area + n * runs_per_image;
-    P.h = h;
-    P.w = w;
-    P.wpr = wpr;
-    P.max_runs = runs_per_image;
-    P.nruns = &s_nruns;
-    P.status = &s_status;
-    P.flag = s_flag;
-    P.best = &s_best;
-    for (int i = threadIdx.x; i < 256; i += kMaskT) {
-        T.sdiv[i] = i ? __double2int_rn(__ddiv_rn(1044480.0, (double)i)) : 0;
-        T.hdiv[i] = i ? __double2int_rn(__ddiv_rn(737280.0, __dmul_rn(6.0, (double)i))) : 0;
-        T.gam[i] = lab_tabs[i];
-    }
-    for (int i = threadIdx.x; i < kLabCbrtSize; i += kMaskT) T.cbr[i] = lab_tabs[256 + i];
-    if (threadIdx.x == 0) s_status = s_count = s_brown = s_leaf = 0;
+    const Post P = post_view(lds_planes, 2, S, runs, parent, area, runs_per_image, h, w, wpr, kMaskT);
+    H.fill(kMaskT);
+    T.fill(lab_tabs, kMaskT);
+    if (threadIdx.x == 0) s_count = s_brown = s_leaf = 0;
     const uint8_t* img = rgb + n * (size_t)h * w * 3;
     const uint8_t* lm = leaf_mask + n * (size_t)h * w;
     __syncthreads();
@@ -2036,11 +1963,12 @@ __global__ __launch_bounds__(kMaskT) void brown_spots_kernel(const uint8_t* __re
     int leaf = 0;
     for (int p = threadIdx.x; p < h * w; p += kMaskT) leaf += lm[p] > 0;
     atomicAdd(&s_leaf, leaf);
-    build_plane(P, P.A, [&](int y, int x) { return lm[y * w + x] > 0 && brown_px(T, img + 3 * (y * w + x), a); });
-    morph_se(P, P.A, P.B, a.se_brown, true);   // MORPH_OPEN
-    morph_se(P, P.B, P.A, a.se_brown, false);
-    morph_se(P, P.A, P.B, a.se_brown, false);  // MORPH_CLOSE
-    morph_se(P, P.B, P.A, a.se_brown, true);
+    build_plane(P, P.A, kMaskT,
+                [&](int y, int x) { return lm[y * w + x] > 0 && brown_px(H, T, img + 3 * (y * w + x), a); });
+    morph_se(P, P.A, P.B, a.se_brown, true, kMaskT);   // MORPH_OPEN
+    morph_se(P, P.B, P.A, a.se_brown, false, kMaskT);
+    morph_se(P, P.A, P.B, a.se_brown, false, kMaskT);  // MORPH_CLOSE
+    morph_se(P, P.B, P.A, a.se_brown, true, kMaskT);
     label_runs(P, P.A, true);
     const int nr = *P.nruns;
     int cnt = 0, px = 0;
@@ -2065,11 +1993,19 @@ __global__ __launch_bounds__(kMaskT) void brown_spots_kernel(const uint8_t* __re
         stats[3 * n] = s_count;
         stats[3 * n + 1] = s_brown;
         stats[3 * n + 2] = s_leaf;
-        flags[n] = s_status;
+        flags[n] = S.status;
     }
 }
 
-static size_t brown_lds(int h, int w) { return (size_t)2 * h * ((w + 31) / 32) * 4 + (size_t)(h + 1) * 4; }
+struct BrownWs {
+    LabelBufs lb;
+    size_t bytes;
+    BrownWs(void* base, int n, int h, int w) {
+        Carver c{base};
+        lb.carve(c, n, h, w);
+        bytes = c.off;
+    }
+};
 
 }  // namespace
 
@@ -2077,9 +2013,7 @@ extern "C" {
 
 size_t lf_brown_spots_workspace(int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    const size_t runs = (size_t)n * mask_runs_per_image(h, w);
-    // runs / parents / areas, the L*a*b* tables
-    return up(runs * sizeof(Run)) + 2 * up(runs * 4) + up((256 + kLabCbrtSize) * sizeof(uint16_t));
+    return BrownWs(nullptr, n, h, w).bytes;
 }
 
 int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int32_t* stats, int32_t* flags, int n,
@@ -2088,7 +2022,7 @@ int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int
     LF_REQUIRE(n > 0 && h > 0 && w > 0, "lf_brown_spots: bad dims n=%d %dx%d", n, h, w);
     LF_REQUIRE(n <= 65535, "lf_brown_spots: batch too large for the grid");
     LF_REQUIRE(h <= 65535 && w <= 65535, "lf_brown_spots: image too large (%d x %d)", h, w);
-    const size_t lds = brown_lds(h, w);
+    const size_t lds = post_lds_bytes(2, h, (w + 31) / 32);
     LF_REQUIRE(lds <= kMaskLdsCap,
                "lf_brown_spots: a %d x %d image needs %zu bytes of LDS for its two bit planes (limit %zu, one "
                "workgroup per image)", h, w, lds, kMaskLdsCap);
@@ -2097,17 +2031,11 @@ int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int
     LF_REQUIRE(ws_bytes >= lf_brown_spots_workspace(n, h, w), "lf_brown_spots: workspace too small (%zu < %zu)",
                ws_bytes, lf_brown_spots_workspace(n, h, w));
     LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "lf_brown_spots: workspace must be 256-byte aligned");
-    static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(brown_spots_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)kMaskLdsCap) == hipSuccess;
-    LF_REQUIRE(lds_ok || lds <= 48 * 1024, "lf_brown_spots: could not raise the LDS limit of the brown kernel");
+    LF_REQUIRE(lds <= dynamic_lds_cap<brown_spots_kernel>(kMaskLdsCap, 48 * 1024),
+               "lf_brown_spots: could not raise the LDS limit of the brown kernel");
 
     hipStream_t s = lf::as_stream(stream);
-    const size_t runs = (size_t)n * mask_runs_per_image(h, w);
-    Run* rn = static_cast<Run*>(workspace);
-    int* parent = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(rn) + up(runs * sizeof(Run)));
-    int* area = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(parent) + up(runs * 4));
-    uint16_t* tabs = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(area) + up(runs * 4));
+    const BrownWs ws(workspace, n, h, w);
 
     MaskArgs a{};
     a.use_lab = prm->use_lab_brown;
@@ -2120,18 +2048,10 @@ int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int
     a.brown_min_area = prm->min_area_px;
     a.se_brown = ellipse_rows(prm->morph_kernel);
 
-    static const std::vector<uint16_t> host_tabs = []() {
-        std::vector<uint16_t> t(256 + kLabCbrtSize);
-        lab_tables_host(t.data());
-        return t;
-    }();
-    if (hipMemcpyAsync(tabs, host_tabs.data(), host_tabs.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s) !=
-        hipSuccess) {
-        lf::set_error("lf_brown_spots: table upload failed");
-        return LF_ERR_LAUNCH;
-    }
-    brown_spots_kernel<<<n, kMaskT, lds, s>>>(rgb, mask, tabs, rn, parent, area, (int)mask_runs_per_image(h, w), h, w,
-                                              (w + 31) / 32, a, out, stats, flags);
+    const int rc = upload_lab_tables(ws.lb.tabs, s, "lf_brown_spots");
+    if (rc != LF_OK) return rc;
+    brown_spots_kernel<<<n, kMaskT, lds, s>>>(rgb, mask, ws.lb.tabs, ws.lb.rn, ws.lb.parent, ws.lb.area,
+                                              (int)mask_runs_per_image(h, w), h, w, (w + 31) / 32, a, out, stats, flags);
     return lf::check_launch("lf_brown_spots");
 }
 
@@ -2359,3 +2279,4 @@ int lf_roi_u8(const uint8_t* rgb, const int32_t* contour, const int32_t* counts,
 }
 
 }  // extern "C"
+
