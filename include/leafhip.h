@@ -696,6 +696,10 @@ int lf_block_tail_bwd_f32(const float* dp, const uint8_t* route, const float* y,
 /* probs = softmax(feat w + b), w [f][c]; loss[n] = -sum_j ytrue[n][j] log(clip(probs)). */
 int lf_head_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue,
                     float* probs, float* loss, int n, int f, int c, lf_stream_t stream);
+/* dlogits = (probs - ytrue) * inv_n (softmax + cross-entropy without the clip); dfeat = dlogits w^T;
+ * dw = feat^T dlogits; db = sum_n dlogits.  Differentiating through the loss's clip to [1e-7, 1 - 1e-7]
+ * instead gives a different dlogits only where a probability is saturated (a clipped class passes no
+ * gradient, and the renormalisation term changes with it); this entry does not follow that rule. */
 int lf_head_bwd_f32(const float* feat, const float* w, const float* probs, const float* ytrue,
                     float* dlogits, float* dfeat, float* dw, float* db, int n, int f, int c,
                     float inv_n, lf_stream_t stream);

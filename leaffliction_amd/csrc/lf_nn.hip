@@ -1320,7 +1320,7 @@ int lf_block_tail_bwd_bf16(const uint16_t* dp, const uint8_t* route, const uint1
     LF_REQUIRE((y == nullptr) == (ds == nullptr && plane_sums == nullptr),
                "lf_block_tail_bwd_bf16: y goes with ds / plane_sums");
     LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_bwd_bf16: a_scale/a_shift");
-    LF_REQUIRE(aligned(dr, 8) && aligned(dp, 4), "lf_block_tail_bwd_bf16: misaligned buffer");
+    LF_REQUIRE(aligned(dr, 8) && aligned(dp, 4) && aligned(route, 2), "lf_block_tail_bwd_bf16: misaligned buffer");
     auto kernel = w % 8 == 0 && aligned(dr, 16) && aligned(dp, 8) && aligned(route, 4) ? tail_bwd_kernel<uint16_t, 8>
                                                                                       : tail_bwd_kernel<uint16_t, 4>;
     kernel<<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums,
