@@ -382,10 +382,15 @@ int lf_resample_tile_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, in
  * Implicit GEMM on v_mfma_f32_32x32x2_f32: result equals an fp32 fmaf chain over
  * k = (ci, tap) in ascending order.  Tolerance vs fp32 torch conv2d: 1e-4 relative.
  * dgrad is the same call on dy with lf_conv2d_dgrad_weights_f32's output; accumulate != 0
- * adds into y (residual gradient joins) instead of overwriting it. */
+ * adds into y (residual gradient joins) instead of overwriting it.
+ * Every 3x3 convolution but the Cin <= 4 stem (lf_conv2d_takes_wino_filters != 0) computes Winograd
+ * F(2x2,3x3) and reads its filters already transformed: wino_u from lf_conv2d_wino_filters_f32 (below) is
+ * required, w is not read and may be null.  Without wino_u such a call returns LF_ERR_INVALID and launches
+ * nothing.  All other calls read w and ignore wino_u.  The same holds for lf_conv2d_stats_f32 and
+ * lf_conv2d_bnbwd_f32. */
 int lf_conv2d_f32(const float* x, const float* w, float* y, int n, int cin, int h, int wd, int cout,
                   int ksize, const float* in_scale, const float* in_shift, int in_relu,
-                  int accumulate, lf_stream_t stream);
+                  int accumulate, lf_stream_t stream, const float* wino_u);
 
 /* The same forward convolution with both operands rounded to bf16 (round to nearest even) while
  * staging and fp32 accumulation on v_mfma_f32_32x32x16_bf16 — the reduced-precision inference mode
@@ -542,7 +547,7 @@ long long lf_conv2d_stats_tiles(int n, int cin, int h, int w, int cout, int ksiz
 int lf_conv2d_stats_f32(const float* x, const float* w, float* y, int n, int cin, int h, int wd,
                         int cout, int ksize, const float* in_scale, const float* in_shift,
                         int in_relu, const float* pivot, float* tile_part, size_t tile_part_bytes,
-                        lf_stream_t stream);
+                        lf_stream_t stream, const float* wino_u);
 
 /* Input-gradient convolution whose output g feeds a BatchNormalization backward (mask_y = that
  * BN's input, same shape as y): besides y (= conv, or y += conv with accumulate) the epilogue
@@ -552,12 +557,25 @@ int lf_conv2d_stats_f32(const float* x, const float* w, float* y, int n, int cin
 int lf_conv2d_bnbwd_f32(const float* x, const float* w, float* y, int n, int cin, int h, int wd,
                         int cout, int ksize, int accumulate, const float* mask_y,
                         const float* mask_scale, const float* mask_shift, int mask_relu,
-                        float* tile_part, size_t tile_part_bytes, lf_stream_t stream);
+                        float* tile_part, size_t tile_part_bytes, lf_stream_t stream, const float* wino_u);
 
 /* w [Cin][k*k][Cout] -> wt [Cout][k*k (flipped)][Cin]: the weights with which
  * lf_conv2d_f32(dy, wt, dx, n, cout, h, w, cin, k, ...) is the input gradient. */
 int lf_conv2d_dgrad_weights_f32(const float* w, float* wt, int cin, int ksize, int cout,
                                 lf_stream_t stream);
+
+/* The 3x3 filters w [cin][9][cout] in the Winograd F(2x2,3x3) domain, U = G g G^T (16 floats per filter,
+ * index row*4+col; additions and halvings only, so the bits do not depend on where it is computed):
+ *   dgrad == 0: u [cin][cout][16], the wino_u of the forward convolution with w;
+ *   dgrad != 0: u [cout][cin][16] from the flipped taps, the wino_u of the input-gradient convolution
+ *               lf_conv2d_f32(dy, ., dx, n, cout, h, w, cin, 3, ...) — equal to dgrad == 0 applied to
+ *               lf_conv2d_dgrad_weights_f32's output.
+ * u: cin*cout*64 bytes, 16-byte aligned, supplied by the caller.  The weights change once per optimizer
+ * step, so one launch per layer and role serves every convolution launch of the step.
+ * lf_conv2d_takes_wino_filters: 1 if lf_conv2d_f32 / _stats_f32 / _bnbwd_f32 need wino_u for this shape
+ * (cin, cout: the convolution's own). */
+int lf_conv2d_takes_wino_filters(int cin, int h, int wd, int cout, int ksize);
+int lf_conv2d_wino_filters_f32(const float* w, float* u, int cin, int cout, int dgrad, lf_stream_t stream);
 
 /* Weight gradient dw[ci][tap][co] = sum_{n,y,x} x'[n][ci][y+ky-1][x+kx-1] * dy[n][co][y][x]
  * (x' = optional prologue as above) in two steps: lf_conv2d_wgrad_f32 writes one partial

@@ -73,7 +73,7 @@ SIGNATURES = {
     "lf_resample_tile_u8": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, c_int, P],
     "lf_resample_u8": [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int,
                        c_int, P],
-    "lf_conv2d_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P],
+    "lf_conv2d_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P],
     "lf_conv2d_bf16_weight_elems": [c_int, c_int, c_int],
     "lf_conv2d_bf16_prep_weights": [P, P, c_int, c_int, c_int, P],
     "lf_conv2d_bf16_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P],
@@ -101,10 +101,12 @@ SIGNATURES = {
     "lf_conv2d_bf16_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "lf_conv2d_wgrad_bf16_plan": [c_int, c_int, c_int, c_int, c_int, c_int, P],
     "lf_conv2d_stats_tiles": [c_int, c_int, c_int, c_int, c_int, c_int],
-    "lf_conv2d_stats_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_size_t, P],
+    "lf_conv2d_stats_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_size_t, P, P],
     "lf_conv2d_bnbwd_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P,
-                            c_size_t, P],
+                            c_size_t, P, P],
     "lf_conv2d_dgrad_weights_f32": [P, P, c_int, c_int, c_int, P],
+    "lf_conv2d_takes_wino_filters": [c_int, c_int, c_int, c_int, c_int],
+    "lf_conv2d_wino_filters_f32": [P, P, c_int, c_int, c_int, P],
     "lf_conv2d_wgrad_workspace": [c_int, c_int, c_int, c_int, c_int, c_int],
     "lf_conv2d_wgrad_f32": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P,
                             c_size_t, P],

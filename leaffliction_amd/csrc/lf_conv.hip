@@ -61,7 +61,8 @@ __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned of
 
 struct ConvArgs {
     const float* x;
-    const float* w;  // [Cin][TAPS][Cout]
+    const float* w;       // [Cin][TAPS][Cout] (the direct kernel)
+    const float* wino_u;  // [Cin][Cout][16], U = G g G^T of every filter (the Winograd kernel)
     float* y;
     const float* in_scale;  // optional prologue (nullptr = none)
     const float* in_shift;
@@ -590,8 +591,9 @@ void conv_mfma_kernel(ConvArgs p) {
 // each of the 16 transform positions is a GEMM U[pos] (cout x cin) . V[pos] (cin x tiles) on
 // v_mfma_f32_16x16x4_f32; a wave owns MB cout-blocks x NB tile-blocks of 16, all 16 positions, so M[pos]
 // for one (cout, tile) sits in one lane and register and the inverse transform is register-local.
-// U = G g G^T is formed while the weights are staged (one (channel, cout) pair per thread) and kept in
-// LDS; V = B^T d B is formed per lane from the LDS patch.  The patch staging (prologue, zeros, two-image
+// U = G g G^T comes prepared from wino_filters_kernel (once per layer, role and step) and a chunk's slice
+// of it is copied to LDS (pitch 20 floats per filter: conflict-free ds_read_b128 of a lane's 16 positions);
+// V = B^T d B is formed per lane from the LDS patch.  The patch staging (prologue, zeros, two-image
 // strip) is the direct kernel's.  64 accumulators per (cout-block, tile-block): 2 waves per SIMD.
 template <int TW, int TH, int MB, int NB, bool STK>
 __global__ __launch_bounds__(kThreads, 2)
@@ -680,29 +682,27 @@ void conv_wino_kernel(ConvArgs p) {
         }
     };
 
-    // weights: thread (kc, co) of the chunk fetches the 9 taps of one filter into registers and
-    // stores U = G g G^T to LDS
-    static_assert(kKC * CT <= kThreads, "one (channel, cout) filter per thread");
-    const int ukc = tid / CT, uco = tid - ukc * CT;
-    const bool u_on = tid < kKC * CT;
-    const unsigned ugo = (u_on && co0 + uco < p.cout) ? 4u * ((unsigned)ukc * 9u * (unsigned)p.cout + (unsigned)(co0 + uco)) : kBufOob;
-    float wr[9];
+    // filters: the chunk's slice of the prepared U (wino_filters_kernel: [Cin][Cout][16]) is kKC runs
+    // of CT * 64 contiguous bytes, copied to LDS as they are.  Thread tid takes quarter tid & 3 of the
+    // filter (channel tid / (4 CT) + i * KSTEP, cout (tid / 4) % CT), i < UPT: a wave's 16-byte loads
+    // cover whole 1 KB runs, and item i lies a fixed stride after item 0 in global memory and in LDS.
+    // Couts beyond Cout start at 2^31, channels beyond Cin fall outside the chunk's buffer size -> zeros.
+    constexpr int KSTEP = kThreads / (4 * CT), UPT = kKC / KSTEP;
+    static_assert(kThreads % (4 * CT) == 0 && kKC % KSTEP == 0, "whole channels per pass");
+    const int ukc = tid / (4 * CT), uco = (tid >> 2) % CT, uq4 = tid & 3;
+    const unsigned ustep = 64u * KSTEP * (unsigned)p.cout;
+    const unsigned ugo = co0 + uco < p.cout ? 4u * (((unsigned)ukc * (unsigned)p.cout + (unsigned)(co0 + uco)) * 16u + 4u * (unsigned)uq4) : 0x80000000u;
+    float* const ulds = lw + (ukc * CT + uco) * kUP + 4 * uq4;
+    float4 uv[UPT];
     auto load_u = [&](int c0) {
-        // filters of channels beyond Cin fall outside the chunk's buffer size -> zeros
-        const __amdgpu_buffer_rsrc_t rw =
-            buf_rsrc(p.w + (size_t)c0 * 9 * p.cout, 4u * (unsigned)(min(kKC, p.cin - c0) * 9) * (unsigned)p.cout);
+        const __amdgpu_buffer_rsrc_t ru =
+            buf_rsrc(p.wino_u + (size_t)c0 * p.cout * 16, 64u * (unsigned)min(kKC, p.cin - c0) * (unsigned)p.cout);
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-            wr[tap] = buf_load1(rw, ugo == kBufOob ? kBufOob : ugo + 4u * (unsigned)tap * (unsigned)p.cout);
+        for (int i = 0; i < UPT; ++i) uv[i] = buf_load4(ru, ugo + (unsigned)i * ustep);
     };
     auto store_u = [&]() {
-        if (u_on) {
-            float u[16];
-            wino_filter(wr, u);
-            float4* dst = reinterpret_cast<float4*>(lw + (ukc * CT + uco) * kUP);
 #pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) dst[q4] = make_float4(u[4 * q4], u[4 * q4 + 1], u[4 * q4 + 2], u[4 * q4 + 3]);
-        }
+        for (int i = 0; i < UPT; ++i) *reinterpret_cast<float4*>(ulds + i * KSTEP * CT * kUP) = uv[i];
     };
 
     const int nchunks = (p.cin + kKC - 1) / kKC;
@@ -710,25 +710,19 @@ void conv_wino_kernel(ConvArgs p) {
 
     if (vec) {
         // ---------------- vector staging with register prefetch ----------------
-        // the filter taps (9 registers) are prefetched during the previous chunk's MFMAs unless the
-        // wave has two tile-blocks; then they are fetched (L2-resident) in the store phase
-        constexpr bool kPrefetchW = NB == 1;
+        // The patch is prefetched into registers during the previous chunk's MFMAs.  U is not: its slice is
+        // L2-resident (every workgroup reads the same few KB), so it is fetched in the store phase, in flight
+        // while the patch goes to LDS.  Prefetching it too (4 * UPT registers held across the MFMAs) measured
+        // 0.8 ms per step slower.
         Patch patch(p, t, lsc, tid);
-        auto store_chunk = [&](int c0) {
-            if (!kPrefetchW) load_u(c0);
-            patch.store(p, lp, lsc, c0, tid);
-            store_u();
-        };
         patch.load(p, xin, 0);
-        if (kPrefetchW) load_u(0);
         for (int ch = 0; ch < nchunks; ++ch) {
             __syncthreads();  // previous chunk's LDS reads are done
-            store_chunk(ch * kKC);
+            load_u(ch * kKC);
+            patch.store(p, lp, lsc, ch * kKC, tid);
+            store_u();
             __syncthreads();
-            if (ch + 1 < nchunks) {  // in flight during the MFMAs
-                patch.load(p, xin, (ch + 1) * kKC);
-                if (kPrefetchW) load_u((ch + 1) * kKC);
-            }
+            if (ch + 1 < nchunks) patch.load(p, xin, (ch + 1) * kKC);  // in flight during the MFMAs
             compute_chunk();
         }
     } else {
@@ -1761,6 +1755,30 @@ __global__ __launch_bounds__(kThreads) void weight_dgrad_kernel(const float* __r
     }
 }
 
+// The 3x3 filters in the Winograd domain, once per layer, role and step: w [Cin][9][Cout] ->
+// U = G g G^T, 16 floats per filter.  Forward role: u[ci][co] from the taps of w[ci][.][co].  Input-gradient
+// role (dgrad != 0): the convolution's channels swap and its taps flip, u[co][ci] from w[ci][8 - tap][co]
+// (what weight_dgrad_kernel followed by the forward role gives, in one launch).
+// Layout [Cin'][Cout'][16] (primed: the convolution's own channels in that role): the slice conv_wino_kernel
+// stages per K-chunk and cout tile is then one run of CT * 64 contiguous bytes per channel, every filter
+// 64-byte aligned whatever Cout is, so the copy takes 16-byte lanes on the ragged shapes too.  (Position-major
+// [16][Cin][Cout] would cut the same slice into 16 * kKC runs of CT * 4 bytes.)
+__global__ __launch_bounds__(kThreads) void wino_filters_kernel(const float* __restrict__ w,
+                                                                float* __restrict__ u, int cin, int cout,
+                                                                int dgrad) {
+    const int total = cin * cout;
+    for (int i = blockIdx.x * kThreads + threadIdx.x; i < total; i += gridDim.x * kThreads) {
+        const int ci = i / cout, co = i - ci * cout;
+        float g[9], t[16];
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) g[tap] = w[((size_t)ci * 9 + (dgrad ? 8 - tap : tap)) * cout + co];
+        wino_filter(g, t);
+        float4* dst = reinterpret_cast<float4*>(u + (dgrad ? (size_t)co * cin + ci : (size_t)i) * 16);
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) dst[q4] = make_float4(t[4 * q4], t[4 * q4 + 1], t[4 * q4 + 2], t[4 * q4 + 3]);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
@@ -1784,7 +1802,8 @@ inline bool fwd_small_cin(int taps, int variant, int cin) { return taps == 9 && 
 // the shape half of ConvArgs::vec_ok (the other half: 16-byte aligned x and w)
 inline bool fwd_vec_shape(int wd, int cout) { return wd % 4 == 0 && cout % 4 == 0; }
 
-// K-chunk of 8 input channels everywhere (16 measured slower: more prefetch registers, fewer resident waves).
+// K-chunk of 8 input channels everywhere (16 measured slower in the direct kernel: more prefetch registers,
+// fewer resident waves).
 // gx x gz: tiles x strips; grid.y = cout / the kernel's cout tile.
 int launch_fwd(int ksize, int variant, const ConvArgs& a, unsigned gx, unsigned gz, hipStream_t s) {
     const auto grid = [&](int ct) { return dim3(gx, (a.cout + ct - 1) / ct, gz); };
@@ -1987,12 +2006,17 @@ int lf_conv2d_wgrad_plan(int n, int cin, int h, int wd, int cout, int ksize, int
     return LF_OK;
 }
 
-static int conv2d_launch(const char* who, const float* x, const float* w, float* y, int n, int cin,
+// every 3x3 launch but the stem's runs conv_wino_kernel, which reads the prepared U instead of w
+static inline bool fwd_takes_wino_filters(int cin, int h, int wd, int cout, int ksize) {
+    return ksize == 3 && !fwd_small_cin(9, lf_conv2d_variant(h, wd, cout, ksize), cin);
+}
+
+static int conv2d_launch(const char* who, const float* x, const float* w, const float* wino_u, float* y, int n, int cin,
                          int h, int wd, int cout, int ksize, const float* in_scale,
                          const float* in_shift, int in_relu, int accumulate, float* stat_part,
                          const float* stat_pivot, const float* stat_mask_y, const float* mask_scale,
                          const float* mask_shift, int mask_relu, lf_stream_t stream) {
-    LF_REQUIRE(x && w && y, "%s: null buffer", who);
+    LF_REQUIRE(x && y, "%s: null buffer", who);
     LF_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && wd > 0,
                "%s: bad dims n=%d cin=%d cout=%d h=%d w=%d", who, n, cin, cout, h, wd);
     LF_REQUIRE(ksize == 3 || ksize == 1, "%s: ksize must be 1 or 3 (got %d)", who, ksize);
@@ -2003,12 +2027,23 @@ static int conv2d_launch(const char* who, const float* x, const float* w, float*
                "%s: per-image tensor too large for 32-bit offsets", who);
     const int best = lf_conv2d_variant(h, wd, cout, ksize);
     const FwdVariant& v = kFwdVariants[best];
+    if (fwd_takes_wino_filters(cin, h, wd, cout, ksize)) {
+        // no in-kernel transform to fall back to: w is not read and may be null
+        LF_REQUIRE(wino_u, "%s: this 3x3 convolution runs in the Winograd domain and needs wino_u "
+                   "(lf_conv2d_wino_filters_f32)", who);
+        LF_REQUIRE(aligned16(wino_u), "%s: wino_u must be 16-byte aligned", who);
+        LF_REQUIRE((size_t)cin * cout * 16 < (1ull << 30) && cout <= (1 << 20), "%s: wino_u too large for 32-bit offsets", who);
+    } else {
+        LF_REQUIRE(w, "%s: null buffer", who);
+    }
     ConvArgs a;
-    a.x = x; a.w = w; a.y = y; a.in_scale = in_scale; a.in_shift = in_shift;
+    a.x = x; a.w = w; a.y = y;
+    a.wino_u = fwd_takes_wino_filters(cin, h, wd, cout, ksize) ? wino_u : nullptr;
+    a.in_scale = in_scale; a.in_shift = in_shift;
     a.n = n; a.cin = cin; a.cout = cout; a.h = h; a.wd = wd;
     a.in_relu = in_relu;
     a.accumulate = accumulate;
-    a.vec_ok = fwd_vec_shape(wd, cout) && aligned16(x) && aligned16(w);
+    a.vec_ok = fwd_vec_shape(wd, cout) && aligned16(x) && aligned16(a.wino_u ? nullptr : w);
     a.stack = conv_stack(best, n, cin, h, wd, cout);
     if (a.stack > 1 && !a.vec_ok) {
         if (stat_part != nullptr) {  // the tile count the caller sized its buffers for assumes it
@@ -2032,8 +2067,8 @@ static int conv2d_launch(const char* who, const float* x, const float* w, float*
 
 int lf_conv2d_f32(const float* x, const float* w, float* y, int n, int cin, int h, int wd, int cout,
                   int ksize, const float* in_scale, const float* in_shift, int in_relu,
-                  int accumulate, lf_stream_t stream) {
-    return conv2d_launch("lf_conv2d", x, w, y, n, cin, h, wd, cout, ksize, in_scale, in_shift, in_relu,
+                  int accumulate, lf_stream_t stream, const float* wino_u) {
+    return conv2d_launch("lf_conv2d", x, w, wino_u, y, n, cin, h, wd, cout, ksize, in_scale, in_shift, in_relu,
                          accumulate, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
 }
 
@@ -2048,7 +2083,7 @@ long long lf_conv2d_stats_tiles(int n, int cin, int h, int wd, int cout, int ksi
 int lf_conv2d_stats_f32(const float* x, const float* w, float* y, int n, int cin, int h, int wd,
                         int cout, int ksize, const float* in_scale, const float* in_shift,
                         int in_relu, const float* pivot, float* tile_part, size_t tile_part_bytes,
-                        lf_stream_t stream) {
+                        lf_stream_t stream, const float* wino_u) {
     LF_REQUIRE(tile_part, "lf_conv2d_stats: null tile_part");
     const long long tiles = lf_conv2d_stats_tiles(n, cin, h, wd, cout, ksize);
     if (tile_part_bytes < (size_t)tiles * (size_t)(cout > 0 ? cout : 0) * 2 * sizeof(float)) {
@@ -2056,14 +2091,14 @@ int lf_conv2d_stats_f32(const float* x, const float* w, float* y, int n, int cin
                       tile_part_bytes, tiles, cout);
         return LF_ERR_WORKSPACE;
     }
-    return conv2d_launch("lf_conv2d_stats", x, w, y, n, cin, h, wd, cout, ksize, in_scale, in_shift,
+    return conv2d_launch("lf_conv2d_stats", x, w, wino_u, y, n, cin, h, wd, cout, ksize, in_scale, in_shift,
                          in_relu, 0, tile_part, pivot, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int lf_conv2d_bnbwd_f32(const float* x, const float* w, float* y, int n, int cin, int h, int wd,
                         int cout, int ksize, int accumulate, const float* mask_y,
                         const float* mask_scale, const float* mask_shift, int mask_relu,
-                        float* tile_part, size_t tile_part_bytes, lf_stream_t stream) {
+                        float* tile_part, size_t tile_part_bytes, lf_stream_t stream, const float* wino_u) {
     LF_REQUIRE(tile_part && mask_y && mask_scale && mask_shift, "lf_conv2d_bnbwd: null buffer");
     const long long tiles = lf_conv2d_stats_tiles(n, cin, h, wd, cout, ksize);
     if (tile_part_bytes < (size_t)tiles * (size_t)(cout > 0 ? cout : 0) * 2 * sizeof(float)) {
@@ -2071,7 +2106,7 @@ int lf_conv2d_bnbwd_f32(const float* x, const float* w, float* y, int n, int cin
                       tile_part_bytes, tiles, cout);
         return LF_ERR_WORKSPACE;
     }
-    return conv2d_launch("lf_conv2d_bnbwd", x, w, y, n, cin, h, wd, cout, ksize, nullptr, nullptr, 0,
+    return conv2d_launch("lf_conv2d_bnbwd", x, w, wino_u, y, n, cin, h, wd, cout, ksize, nullptr, nullptr, 0,
                          accumulate, tile_part, nullptr, mask_y, mask_scale, mask_shift, mask_relu,
                          stream);
 }
@@ -2084,6 +2119,20 @@ int lf_conv2d_dgrad_weights_f32(const float* w, float* wt, int cin, int ksize, i
     weight_dgrad_kernel<<<lf::stream_grid(total, kThreads), kThreads, 0, lf::as_stream(stream)>>>(
         w, wt, cin, ksize * ksize, cout);
     return lf::check_launch("lf_conv2d_dgrad_weights");
+}
+
+int lf_conv2d_takes_wino_filters(int cin, int h, int wd, int cout, int ksize) {
+    if (cin <= 0 || cout <= 0 || h <= 0 || wd <= 0) return 0;
+    return fwd_takes_wino_filters(cin, h, wd, cout, ksize) ? 1 : 0;
+}
+
+int lf_conv2d_wino_filters_f32(const float* w, float* u, int cin, int cout, int dgrad, lf_stream_t stream) {
+    LF_REQUIRE(w && u, "lf_conv2d_wino_filters: null buffer");
+    LF_REQUIRE(cin > 0 && cout > 0 && (size_t)cin * cout * 16 < (1ull << 30), "lf_conv2d_wino_filters: bad dims");
+    LF_REQUIRE(aligned16(u), "lf_conv2d_wino_filters: u must be 16-byte aligned");
+    wino_filters_kernel<<<lf::stream_grid((size_t)cin * cout, kThreads), kThreads, 0, lf::as_stream(stream)>>>(
+        w, u, cin, cout, dgrad ? 1 : 0);
+    return lf::check_launch("lf_conv2d_wino_filters");
 }
 
 size_t lf_conv2d_wgrad_workspace(int n, int cin, int h, int wd, int cout, int ksize) {

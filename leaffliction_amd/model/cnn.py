@@ -338,6 +338,18 @@ class LeafCNN:
                                     self.s[name + ".mean"], self.s[name + ".var"], st, BN_EPS)
         return st
 
+    def _wino_u(self, wname: str, ksize: int, hw, dgrad: bool = False) -> Optional[torch.Tensor]:
+        """The layer's filters in the Winograd domain for the fp32 3x3 convolutions that run there (all but the
+        stem): prepared once per pass and role, where the weights are current, into a buffer of its own (fixed
+        address: the HIP graph of the step bakes pointers in).  None for launches that read the raw weights."""
+        cin, _taps, cout = self.p[wname].shape
+        if dgrad:
+            cin, cout = cout, cin
+        if not nn.conv2d_takes_wino_filters(cin, hw[0], hw[1], cout, ksize):
+            return None
+        u = self._buf("wino", ("d:" if dgrad else "f:") + wname, (cin, cout, 16))
+        return nn.conv2d_wino_filters(self.p[wname], dgrad, out=u)
+
     def _conv_bn(self, x, wname: str, ksize: int, bn: str, pro, out: torch.Tensor, training: bool,
                  bf16: bool = False):
         """Conv2D -> BatchNormalization: returns (y, stats[4,C]).  In training the batch
@@ -352,7 +364,8 @@ class LeafCNN:
                 nn.conv2d_bn_stats_bf16(x, self._wt["f:" + wname], P[wname].shape[2], ksize, *bn_args,
                                         out=out, momentum=BN_MOMENTUM, eps=BN_EPS)
             else:
-                nn.conv2d_bn_stats(x, P[wname], ksize, *bn_args, out=out, momentum=BN_MOMENTUM, eps=BN_EPS)
+                nn.conv2d_bn_stats(x, P[wname], ksize, *bn_args, out=out, momentum=BN_MOMENTUM, eps=BN_EPS,
+                                   wino_u=self._wino_u(wname, ksize, x.shape[2:]))
             return out, st
         w = P[wname]
         if self.infer_dtype == "bf16" and x.shape[3] % 4 == 0 and w.shape[2] % 32 == 0:
@@ -361,7 +374,8 @@ class LeafCNN:
             y = nn.conv2d_bf16(x, nn.conv2d_bf16_weights(w, ksize), w.shape[2], ksize, pro[0], pro[1],
                                pro[2], out=out)
         else:
-            y = nn.conv2d(x, w, ksize, pro[0], pro[1], pro[2], out=out)
+            y = nn.conv2d(x, w, ksize, pro[0], pro[1], pro[2], out=out,
+                          wino_u=self._wino_u(wname, ksize, x.shape[2:]))
         return y, self._bn(bn, y, False)
 
     def _bf16_storage_ok(self, h: int, w: int) -> bool:
@@ -646,11 +660,13 @@ class LeafCNN:
                 return None
             return nn.conv2d_bf16_train(gy, wt, cin, k, out, accumulate=accumulate, mask_y=mask[0],
                                         mask_scale=mask[1][2], mask_shift=mask[1][3], mask_relu=True)[1]
-        wt = nn.conv2d_dgrad_weights(self.p[wname], k)
+        # the flipped, channel-swapped filters: in the Winograd domain straight from w, else as raw weights
+        u = self._wino_u(wname, k, gy.shape[2:], dgrad=True)
+        wt = nn.conv2d_dgrad_weights(self.p[wname], k) if u is None else None
         if mask is None:
-            nn.conv2d(gy, wt, k, out=out, accumulate=accumulate)
+            nn.conv2d(gy, wt, k, out=out, accumulate=accumulate, wino_u=u)
             return None
-        return nn.conv2d_bnbwd(gy, wt, k, mask[0], mask[1], True, out, accumulate=accumulate)[1]
+        return nn.conv2d_bnbwd(gy, wt, k, mask[0], mask[1], True, out, accumulate=accumulate, wino_u=u)[1]
 
     # ------------------------------------------------------------ training
     def draw_dropout(self, n: int):

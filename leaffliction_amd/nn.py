@@ -44,19 +44,74 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def conv2d(x: torch.Tensor, w_iko: torch.Tensor, ksize: int, in_scale=None, in_shift=None,
+def conv2d_takes_wino_filters(cin: int, h: int, w: int, cout: int, ksize: int) -> bool:
+    """Whether conv2d / conv2d_bn_stats / conv2d_bnbwd run this shape in the Winograd domain (every 3x3 but the
+    Cin <= 4 stem) and so read conv2d_wino_filters' output instead of the raw weights."""
+    return bool(_lib.load().lf_conv2d_takes_wino_filters(int(cin), int(h), int(w), int(cout), int(ksize)))
+
+
+def conv2d_wino_filters(w_iko: torch.Tensor, dgrad: bool = False,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3x3 weights [Cin,9,Cout] -> their Winograd F(2x2,3x3) transforms U = G g G^T, the `wino_u` of conv2d /
+    conv2d_bn_stats / conv2d_bnbwd: [Cin,Cout,16] for the forward convolution, or with `dgrad` [Cout,Cin,16] from
+    the flipped taps for the input-gradient convolution (no conv2d_dgrad_weights in between).  The weights change
+    once per optimizer step: prepare once per layer, role and step."""
+    _chk(w_iko, _F32, "conv2d_wino_filters.w", 3)
+    cin, taps, cout = w_iko.shape
+    if taps != 9:
+        raise ValueError("conv2d_wino_filters: 3x3 weights [Cin,9,Cout] expected")
+    shape = (cout, cin, 16) if dgrad else (cin, cout, 16)
+    if out is None:
+        out = torch.empty(shape, dtype=_F32, device=w_iko.device)
+    else:
+        _chk(out, _F32, "conv2d_wino_filters.out", 3)
+        if tuple(out.shape) != shape:
+            raise ValueError(f"conv2d_wino_filters.out: expected {shape}")
+    _lib.call("lf_conv2d_wino_filters_f32", w_iko.data_ptr(), out.data_ptr(), cin, cout, 1 if dgrad else 0,
+              _stream())
+    return out
+
+
+def _conv_weights(who: str, x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int,
+                  wino_u: Optional[torch.Tensor]):
+    """Checks the weights of a convolution launch; returns (cout, w pointer, wino_u pointer).  A launch that runs
+    in the Winograd domain reads U: the caller's prepared `wino_u` (w_iko may then be None), or else U prepared
+    here from w_iko into a workspace slot, one tiny launch.  Every other launch reads w_iko."""
+    n, cin, h, w = x.shape
+    if w_iko is not None:
+        _chk(w_iko, _F32, f"{who}.w", 3)
+        if w_iko.shape[0] != cin or w_iko.shape[1] != ksize * ksize:
+            raise ValueError(f"{who}.w: expected [{cin},{ksize * ksize},Cout], got {tuple(w_iko.shape)}")
+        cout = w_iko.shape[2]
+    elif wino_u is not None:
+        cout = wino_u.shape[1] if wino_u.dim() == 3 else 0
+    else:
+        raise ValueError(f"{who}: no weights")
+    if not conv2d_takes_wino_filters(cin, h, w, cout, ksize):
+        if w_iko is None:
+            raise ValueError(f"{who}: this launch reads the raw weights, not wino_u")
+        return cout, w_iko.data_ptr(), None
+    if wino_u is None:
+        ws = _workspace(cin * cout * 64, x.device, slot=3)
+        wino_u = conv2d_wino_filters(w_iko, out=ws[:cin * cout * 64].view(_F32).view(cin, cout, 16))
+    else:
+        _chk(wino_u, _F32, f"{who}.wino_u", 3)
+        if tuple(wino_u.shape) != (cin, cout, 16):
+            raise ValueError(f"{who}.wino_u: expected [{cin},{cout},16], got {tuple(wino_u.shape)}")
+    return cout, _ptr(w_iko), wino_u.data_ptr()
+
+
+def conv2d(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, in_scale=None, in_shift=None,
            in_relu: bool = False, out: Optional[torch.Tensor] = None,
-           accumulate: bool = False) -> torch.Tensor:
+           accumulate: bool = False, wino_u: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = conv2d_same(x', w); x' = relu?(x*in_scale[c]+in_shift[c]) if a prologue is given.
 
-    x [N,Cin,H,W] f32, w_iko [Cin, k*k, Cout] f32 -> y [N,Cout,H,W].
+    x [N,Cin,H,W] f32, w_iko [Cin, k*k, Cout] f32 -> y [N,Cout,H,W].  wino_u: conv2d_wino_filters' output for a
+    3x3 convolution (see _conv_weights).
     """
     _chk(x, _F32, "conv2d.x", 4)
-    _chk(w_iko, _F32, "conv2d.w", 3)
     n, cin, h, w = x.shape
-    if w_iko.shape[0] != cin or w_iko.shape[1] != ksize * ksize:
-        raise ValueError(f"conv2d.w: expected [{cin},{ksize * ksize},Cout], got {tuple(w_iko.shape)}")
-    cout = w_iko.shape[2]
+    cout, w_ptr, u_ptr = _conv_weights("conv2d", x, w_iko, ksize, wino_u)
     for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift")):
         if t is not None:
             _chk(t, _F32, f"conv2d.{nm}", 1)
@@ -70,9 +125,9 @@ def conv2d(x: torch.Tensor, w_iko: torch.Tensor, ksize: int, in_scale=None, in_s
         _chk(out, _F32, "conv2d.out", 4)
         if tuple(out.shape) != (n, cout, h, w):
             raise ValueError("conv2d.out: shape mismatch")
-    _lib.call("lf_conv2d_f32", x.data_ptr(), w_iko.data_ptr(), out.data_ptr(), n, cin, h, w, cout,
+    _lib.call("lf_conv2d_f32", x.data_ptr(), w_ptr, out.data_ptr(), n, cin, h, w, cout,
               ksize, _ptr(in_scale), _ptr(in_shift), 1 if in_relu else 0, 1 if accumulate else 0,
-              _stream())
+              _stream(), u_ptr)
     return out
 
 
@@ -285,19 +340,16 @@ def cast_bf16_f32(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     return dst
 
 
-def conv2d_bn_stats(x: torch.Tensor, w_iko: torch.Tensor, ksize: int, gamma, beta, mmean, mvar,
+def conv2d_bn_stats(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, gamma, beta, mmean, mvar,
                     stats: torch.Tensor, in_scale=None, in_shift=None, in_relu: bool = False,
                     out: Optional[torch.Tensor] = None, momentum: float = 0.99,
-                    eps: float = 1e-3) -> torch.Tensor:
+                    eps: float = 1e-3, wino_u: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Conv2D + training-mode BatchNormalization statistics: y = conv(x'), and `stats` [4,C]
     (mean, invstd, scale, shift) + the moving statistics are produced from per-tile sums the
     convolution gathers in its epilogue, so y is not read again."""
     _chk(x, _F32, "conv2d_bn_stats.x", 4)
-    _chk(w_iko, _F32, "conv2d_bn_stats.w", 3)
     n, cin, h, w = x.shape
-    if w_iko.shape[0] != cin or w_iko.shape[1] != ksize * ksize:
-        raise ValueError(f"conv2d_bn_stats.w: expected [{cin},{ksize * ksize},Cout]")
-    cout = w_iko.shape[2]
+    cout, w_ptr, u_ptr = _conv_weights("conv2d_bn_stats", x, w_iko, ksize, wino_u)
     for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift")):
         if t is not None:
             _chk(t, _F32, f"conv2d_bn_stats.{nm}", 1)
@@ -319,9 +371,9 @@ def conv2d_bn_stats(x: torch.Tensor, w_iko: torch.Tensor, ksize: int, gamma, bet
     lib = _lib.load()
     tiles = lib.lf_conv2d_stats_tiles(n, cin, h, w, cout, ksize)
     tp = _workspace(tiles * cout * 8, x.device, slot=1)
-    _lib.call("lf_conv2d_stats_f32", x.data_ptr(), w_iko.data_ptr(), out.data_ptr(), n, cin, h, w,
+    _lib.call("lf_conv2d_stats_f32", x.data_ptr(), w_ptr, out.data_ptr(), n, cin, h, w,
               cout, ksize, _ptr(in_scale), _ptr(in_shift), 1 if in_relu else 0, mmean.data_ptr(),
-              tp.data_ptr(), tp.numel(), _stream())
+              tp.data_ptr(), tp.numel(), _stream(), u_ptr)
     ws = _workspace(lib.lf_bn_workspace(cout), x.device)
     _lib.call("lf_bn_train_stats_tiles_f32", tp.data_ptr(), tiles, n, cout, h * w, gamma.data_ptr(),
               beta.data_ptr(), mmean.data_ptr(), mvar.data_ptr(), float(momentum), float(eps),
@@ -330,27 +382,25 @@ def conv2d_bn_stats(x: torch.Tensor, w_iko: torch.Tensor, ksize: int, gamma, bet
     return out
 
 
-def conv2d_bnbwd(x: torch.Tensor, w_iko: torch.Tensor, ksize: int, mask_y: torch.Tensor,
-                 stats: torch.Tensor, relu: bool, out: torch.Tensor, accumulate: bool = False):
+def conv2d_bnbwd(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, mask_y: torch.Tensor,
+                 stats: torch.Tensor, relu: bool, out: torch.Tensor, accumulate: bool = False,
+                 wino_u: Optional[torch.Tensor] = None):
     """Input-gradient convolution out (+)= conv(x, w) whose result feeds the backward of the
     BatchNormalization with input mask_y / statistics `stats`: the epilogue also leaves the
     per-tile sums of that BN backward.  Returns (out, tile_sums) — pass tile_sums to
     bn_bwd_wgrad."""
     _chk(x, _F32, "conv2d_bnbwd.x", 4)
-    _chk(w_iko, _F32, "conv2d_bnbwd.w", 3)
     _chk(mask_y, _F32, "conv2d_bnbwd.mask_y", 4)
     _chk(out, _F32, "conv2d_bnbwd.out", 4)
     n, cin, h, w = x.shape
-    if w_iko.shape[0] != cin or w_iko.shape[1] != ksize * ksize:
-        raise ValueError(f"conv2d_bnbwd.w: expected [{cin},{ksize * ksize},Cout]")
-    cout = w_iko.shape[2]
+    cout, w_ptr, u_ptr = _conv_weights("conv2d_bnbwd", x, w_iko, ksize, wino_u)
     if tuple(out.shape) != (n, cout, h, w) or mask_y.shape != out.shape or tuple(stats.shape) != (4, cout):
         raise ValueError("conv2d_bnbwd: shape mismatch")
     tiles = _lib.load().lf_conv2d_stats_tiles(n, cin, h, w, cout, ksize)
     tp = _workspace(tiles * cout * 8, x.device, slot=1)
-    _lib.call("lf_conv2d_bnbwd_f32", x.data_ptr(), w_iko.data_ptr(), out.data_ptr(), n, cin, h, w,
+    _lib.call("lf_conv2d_bnbwd_f32", x.data_ptr(), w_ptr, out.data_ptr(), n, cin, h, w,
               cout, ksize, 1 if accumulate else 0, mask_y.data_ptr(), stats[2].data_ptr(),
-              stats[3].data_ptr(), 1 if relu else 0, tp.data_ptr(), tp.numel(), _stream())
+              stats[3].data_ptr(), 1 if relu else 0, tp.data_ptr(), tp.numel(), _stream(), u_ptr)
     return out, (tp, tiles)
 
 
