@@ -308,6 +308,41 @@ size_t lf_jpeg_decode_workspace(int n, int h, int w);
 int lf_jpeg_idct_rgb_u8(const void* coef, size_t coef_stride, const void* qtab, size_t qtab_stride,
                         uint8_t* rgb, int n, int h, int w, void* workspace, size_t ws_bytes,
                         lf_stream_t stream);
+/* The same decoding for files of ANY height and any width from 5 up, images of DIFFERENT sizes in one launch per
+ * step (the rotated canvases Augmentation writes: Image.rotate(angle, expand=True) gives every output a size of its
+ * own, dataset_balancer.py:201-207; the loader and the balancer's input step read them back).  The scan of a ragged
+ * size holds ceil(h/16) * ceil(w/16) whole MCUs; libjpeg cuts the planes to h x w (chroma: ceil(h/2) x ceil(w/2))
+ * BEFORE the fancy upsampling, so the image's own last chroma row / column stands in for the missing neighbour.
+ * Narrower files (chroma width 1 or 2: libjpeg-turbo's upsampler does something else there) return 1.
+ * lf_jpeg_read_file_ragged, lf_jpeg_scan_prepare_ragged (HOST, also in libleafcodec.so): the twins of the two
+ *   functions above, same verdicts, same slot layout with the coefficient area sized by the MCUs:
+ *   [256, 256 + 768 * ceil(h/16) * ceil(w/16)), the aux block at lf_jpeg_scan_aux_offset_ragged(h, w) behind it
+ *   (for whole MCUs the very layout of the functions above).
+ * lf_jpeg_dec_item, one per image (the same array on the device for the kernels and on the host for the checks
+ *   before the launch): slot_off = where its slot starts in `slots` (bytes, a multiple of 16), slot_bytes = the
+ *   slot's size, rgb_off = where its pixels go in `rgb` (tightly packed [h][w][3], any byte: neighbours may be packed
+ *   against it, nothing outside its 3hw bytes is written), plane_off = 384 x the MCUs of the images before it (its
+ *   padded Y / Cb / Cr planes in the workspace), group_start = the running sum of lf_jpeg_fdct_groups(h, w).
+ * lf_jpeg_huffman_items_u8 (GPU): lf_jpeg_huffman_u8 with the geometry taken per image; modes and status codes as
+ *   there (the one-lane-per-image kernel shares the tables of the first image among 64 consecutive items).
+ * lf_jpeg_idct_rgb_items_u8 (GPU): dequantisation + IDCT into padded planes (one launch), cut + fancy upsampling +
+ *   YCbCr->RGB (one launch).  lf_jpeg_decode_items_workspace: bytes of workspace for n host descriptors. */
+typedef struct {
+    int64_t slot_off, rgb_off, plane_off, group_start;
+    int32_t h, w;
+    int64_t slot_bytes;
+} lf_jpeg_dec_item;
+int lf_jpeg_read_file_ragged(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtab128,
+                             int* h, int* w);
+size_t lf_jpeg_scan_aux_offset_ragged(int h, int w);
+int lf_jpeg_scan_prepare_ragged(const uint8_t* data, size_t len, uint8_t* slot, size_t cap, int* h, int* w,
+                                uint64_t* hash);
+int lf_jpeg_huffman_items_u8(void* slots, size_t slots_bytes, const lf_jpeg_dec_item* items,
+                             const lf_jpeg_dec_item* host_items, int n, int* status, int mode, lf_stream_t stream);
+size_t lf_jpeg_decode_items_workspace(const lf_jpeg_dec_item* host_items, int n);
+int lf_jpeg_idct_rgb_items_u8(const void* slots, size_t slots_bytes, const lf_jpeg_dec_item* items,
+                              const lf_jpeg_dec_item* host_items, int n, uint8_t* rgb, size_t rgb_bytes,
+                              void* workspace, size_t ws_bytes, lf_stream_t stream);
 
 /* HOST (also in libleafcodec.so): np.random.RandomState(seed).normal(loc, scale, n) — the distortion op's noise
  * plane (srcs/preprocessing/image_augmenter.py:121-123) — from MT19937 and numpy's legacy polar Gaussian with

@@ -57,6 +57,12 @@ SIGNATURES = {
     "lf_jpeg_scan_prepare": [P, c_size_t, P, c_size_t, P, P, P],
     "lf_jpeg_huffman_u8": [P, c_size_t, c_int, c_int, c_int, P, c_int, P],
     "lf_jpeg_idct_rgb_u8": [P, c_size_t, P, c_size_t, P, c_int, c_int, c_int, P, c_size_t, P],
+    "lf_jpeg_read_file_ragged": [P, c_size_t, P, c_size_t, P, P, P],
+    "lf_jpeg_scan_aux_offset_ragged": [c_int, c_int],
+    "lf_jpeg_scan_prepare_ragged": [P, c_size_t, P, c_size_t, P, P, P],
+    "lf_jpeg_huffman_items_u8": [P, c_size_t, P, P, c_int, P, c_int, P],
+    "lf_jpeg_decode_items_workspace": [P, c_int],
+    "lf_jpeg_idct_rgb_items_u8": [P, c_size_t, P, P, c_int, P, c_size_t, P, c_size_t, P],
     "lf_inclusive_mask_workspace": [c_int, c_int, c_int],
     "lf_inclusive_mask_u8": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P],
     "lf_make_mask_workspace": [c_int, c_int, c_int, c_int, c_int],
@@ -148,7 +154,7 @@ _RESTYPES = {"lf_last_error": C.c_char_p, "lf_conv2d_wgrad_workspace": c_size_t,
              "lf_blur_saliency_workspace": c_size_t, "lf_inclusive_mask_workspace": c_size_t, "lf_make_mask_workspace": c_size_t, "lf_brown_spots_workspace": c_size_t, "lf_conv2d_bf16_weight_elems": c_size_t,
              "lf_conv2d_bf16_act_mean_workspace": c_size_t,
              "lf_conv2d_bf16_stats_tiles": C.c_longlong, "lf_conv2d_wgrad_bf16_workspace": c_size_t,
-             "lf_jpeg_file_bound": c_size_t, "lf_jpeg_scan_aux_offset": c_size_t, "lf_jpeg_entropy_workspace": c_size_t, "lf_jpeg_wrap_scan": C.c_long, "lf_jpeg_fdct_groups": C.c_long, "lf_jpeg_decode_workspace": c_size_t, "lf_jpeg_write_file": C.c_long, "lf_jpeg_quant_tables": None}
+             "lf_jpeg_file_bound": c_size_t, "lf_jpeg_scan_aux_offset": c_size_t, "lf_jpeg_scan_aux_offset_ragged": c_size_t, "lf_jpeg_decode_items_workspace": c_size_t, "lf_jpeg_entropy_workspace": c_size_t, "lf_jpeg_wrap_scan": C.c_long, "lf_jpeg_fdct_groups": C.c_long, "lf_jpeg_decode_workspace": c_size_t, "lf_jpeg_write_file": C.c_long, "lf_jpeg_quant_tables": None}
 
 
 class LeafHipError(RuntimeError):

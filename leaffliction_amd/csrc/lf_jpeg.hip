@@ -261,35 +261,71 @@ struct ZigPos {
     uint8_t pos[64];   // row-major index -> zigzag position
 };
 
+// the image a pass (or a wave of the upsampling kernel) belongs to: the last one whose first pass is not behind g
+__device__ __forceinline__ int dec_item_of(const lf_jpeg_dec_item* __restrict__ items, int n, long g) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if (items[m].group_start <= g)
+            lo = m;
+        else
+            hi = m - 1;
+    }
+    return lo;
+}
+
 // coefficients (zigzag, quantised) of four MCUs at a time -> Y plane and the two half-size chroma planes
+// MULTI: images of different sizes in one launch (lf_jpeg_dec_item; `coef` is then the base of the slots).  Each
+// image's planes are those of its whole MCUs, [16 my][16 mx] and twice [8 my][8 mx] back to back at its plane_off of
+// `yp` (the workspace): a ragged size is cut to h x w by the upsampling kernel, as libjpeg cuts it.
+template <bool MULTI>
 __global__ __launch_bounds__(kT) void jpeg_idct_kernel(const uint8_t* __restrict__ coef, size_t coef_stride,
                                                        const uint8_t* __restrict__ qtab, size_t qtab_stride,
                                                        uint8_t* __restrict__ yp, uint8_t* __restrict__ cbp,
-                                                       uint8_t* __restrict__ crp, int h, int w, int n_images, ZigPos zp) {
+                                                       uint8_t* __restrict__ crp, int h, int w, int n_images, ZigPos zp,
+                                                       const lf_jpeg_dec_item* __restrict__ items = nullptr,
+                                                       long total_groups = 0) {
     __shared__ __attribute__((aligned(16))) int16_t cin[6 * kGroup][64];
     __shared__ int mid[6 * kGroup][64];
     __shared__ uint16_t sq[2][64];
     __shared__ uint8_t spos[64];
     const int tid = threadIdx.x;
     if (tid < 64) spos[tid] = zp.pos[tid];
-    const int mcu_w = w / 16, mcu_h = h / 16, gw = (mcu_w + kGroup - 1) / kGroup;
-    const long groups = (long)n_images * mcu_h * gw;
+    int mcu_w = w / 16, mcu_h = h / 16, gw = (mcu_w + kGroup - 1) / kGroup;
+    const long groups = MULTI ? total_groups : (long)n_images * mcu_h * gw;
     long cur_img = -1;
-    for (long g = blockIdx.x; g < groups; g += gridDim.x) {
+    const uint8_t* slot = nullptr;   // MULTI: this image's slot (tables, then coefficients) and its planes
+    uint8_t* py = yp;
+    for (long g0 = blockIdx.x; g0 < groups; g0 += gridDim.x) {
+        long g = g0, n_multi = 0;
+        if (MULTI) {
+            n_multi = dec_item_of(items, n_images, g0);
+            const lf_jpeg_dec_item it = items[n_multi];
+            mcu_w = (it.w + 15) / 16;
+            mcu_h = (it.h + 15) / 16;
+            gw = (mcu_w + kGroup - 1) / kGroup;
+            g = g0 - it.group_start;
+            h = 16 * mcu_h;
+            w = 16 * mcu_w;
+            slot = coef + it.slot_off;
+            py = yp + it.plane_off;
+        }
         const int gx = (int)(g % gw);
         const long t1 = g / gw;
         const int my = (int)(t1 % mcu_h);
-        const long n = t1 / mcu_h;
+        const long n = MULTI ? n_multi : t1 / mcu_h;
         const int mx0 = gx * kGroup, nm = min(kGroup, mcu_w - mx0);
         __syncthreads();
         if (n != cur_img) {   // this image's two tables
-            if (tid < 128) sq[tid >> 6][tid & 63] = reinterpret_cast<const uint16_t*>(qtab + (size_t)n * qtab_stride)[tid];
+            if (tid < 128)
+                sq[tid >> 6][tid & 63] =
+                    reinterpret_cast<const uint16_t*>(MULTI ? slot : qtab + (size_t)n * qtab_stride)[tid];
             cur_img = n;
         }
         const int blk = tid >> 3, k8 = tid & 7, mi = blk / 6, b = blk - 6 * mi;
         const bool work = blk < 6 * nm;
         if (work) {
-            const int16_t* src = reinterpret_cast<const int16_t*>(coef + (size_t)n * coef_stride) +
+            const int16_t* src = reinterpret_cast<const int16_t*>(MULTI ? slot + 256 : coef + (size_t)n * coef_stride) +
                                  ((size_t)my * mcu_w + mx0) * (6 * 64);
             reinterpret_cast<lf::u32x4*>(&cin[0][0])[tid] = reinterpret_cast<const lf::u32x4*>(src)[tid];
         }
@@ -316,10 +352,12 @@ __global__ __launch_bounds__(kT) void jpeg_idct_kernel(const uint8_t* __restrict
                 hi |= (unsigned)min(max(d[k + 4] + 128, 0), 255) << (8 * k);
             }
             uint8_t* dst;
+            const size_t ni = MULTI ? 0 : (size_t)n;
             if (b < 4)
-                dst = yp + ((size_t)n * h + 16 * my + 8 * (b >> 1) + k8) * w + 16 * (mx0 + mi) + 8 * (b & 1);
-            else
-                dst = (b == 4 ? cbp : crp) + ((size_t)n * (h / 2) + 8 * my + k8) * (w / 2) + 8 * (mx0 + mi);
+                dst = py + (ni * h + 16 * my + 8 * (b >> 1) + k8) * w + 16 * (mx0 + mi) + 8 * (b & 1);
+            else   // MULTI: the chroma planes lie behind the image's own luminance plane
+                dst = (MULTI ? py + (size_t)h * w + (b == 4 ? 0 : (size_t)h * w / 4) : (b == 4 ? cbp : crp)) +
+                      (ni * (h / 2) + 8 * my + k8) * (w / 2) + 8 * (mx0 + mi);
             *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
         }
     }
@@ -379,6 +417,98 @@ __global__ __launch_bounds__(kT) void jpeg_upsample_rgb_kernel(const uint8_t* __
 #pragma unroll
             for (int k = 0; k < 6; ++k) dst[k] = o[k];
         }
+    }
+}
+
+// `nbytes` (a multiple of 3, at most 24) bytes of o[] to `dst`, which may start at any byte: single bytes up to
+// the first 4-byte boundary, whole aligned dwords (the data shifted to the boundary's phase) for the interior, single
+// bytes for what is left.  Nothing outside [dst, dst + nbytes) is touched: the neighbours' pixels lie there.
+__device__ __forceinline__ void store_bytes_any(uint8_t* dst, const unsigned (&o)[6], int nbytes) {
+    const int head = min((int)((4u - (unsigned)(reinterpret_cast<size_t>(dst) & 3u)) & 3u), nbytes);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        if (i < head) dst[i] = (uint8_t)(o[0] >> (8 * i));   // head <= 3: all in o[0]
+    unsigned* d4 = reinterpret_cast<unsigned*>(dst + head);
+    const int nd = (nbytes - head) >> 2, sh = 8 * head;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        if (k < nd) d4[k] = sh ? (o[k] >> sh) | ((k < 5 ? o[k + 1] : 0u) << (32 - sh)) : o[k];
+    const int done = head + 4 * nd;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int at = done + i;
+        if (at < nbytes) {
+            unsigned wd = o[0];   // o[at >> 2] with a register index the compiler can resolve
+#pragma unroll
+            for (int k = 1; k < 6; ++k) wd = (at >> 2) == k ? o[k] : wd;
+            dst[at] = (uint8_t)(wd >> (8 * (at & 3)));
+        }
+    }
+}
+
+// The same step for images of different sizes (lf_jpeg_dec_item), from the padded planes jpeg_idct_kernel<true>
+// left.  libjpeg cuts the planes to the image BEFORE it upsamples (jdsample.c works on downsampled_width =
+// ceil(w/2) columns and ceil(h/2) rows): the image's own last chroma column / row stands in for the missing
+// neighbour, not the padding of the block grid.  A wave takes one group of four MCUs, the unit group_start counts:
+// 64 threads = 8 chroma rows x 8 quads of a 64 x 16 pixel strip, so the search for the image is uniform per wave.  An odd width drops the last upsampled column, an odd height the second output row of the last chroma row;
+// rows start at any byte (w * 3 bytes apart, rgb_off any byte), hence store_bytes_any.
+__global__ __launch_bounds__(kT) void jpeg_upsample_rgb_items_kernel(const uint8_t* __restrict__ ws,
+                                                                     uint8_t* __restrict__ rgb,
+                                                                     const lf_jpeg_dec_item* __restrict__ items, int n_images,
+                                                                     long total_groups) {
+    const long g0 = (long)blockIdx.x * (kT / 64) + (threadIdx.x >> 6);
+    if (g0 >= total_groups) return;
+    const lf_jpeg_dec_item it = items[dec_item_of(items, n_images, g0)];
+    const int h = it.h, w = it.w, mcu_w = (w + 15) / 16, mcu_h = (h + 15) / 16, gw = (mcu_w + kGroup - 1) / kGroup;
+    const int pw = 16 * mcu_w, pcw = 8 * mcu_w;   // row lengths of the padded planes
+    const int cw = (w + 1) / 2, ch = (h + 1) / 2;  // libjpeg's downsampled_width / height
+    const long g = g0 - it.group_start;
+    const int gx = (int)(g % gw), my = (int)(g / gw), lane = threadIdx.x & 63;
+    const int i = 8 * my + (lane >> 3), j0 = 32 * gx + 4 * (lane & 7);
+    if (i >= ch || j0 >= cw) return;
+    const uint8_t* yp = ws + it.plane_off;
+    const uint8_t* planes[2] = {yp + (size_t)256 * mcu_h * mcu_w, yp + (size_t)320 * mcu_h * mcu_w};
+    int up[2][2][8];   // [plane][output row v][output column]
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+        const uint8_t* c0 = planes[pl] + (size_t)i * pcw;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            const int inb = v == 0 ? max(i - 1, 0) : min(i + 1, ch - 1);
+            const uint8_t* c1 = planes[pl] + (size_t)inb * pcw;
+            int cs[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const int j = min(max(j0 - 1 + k, 0), cw - 1);
+                cs[k] = 3 * (int)c0[j] + (int)c1[j];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                up[pl][v][2 * k] = (3 * cs[k + 1] + cs[k] + 8) >> 4;
+                up[pl][v][2 * k + 1] = (3 * cs[k + 1] + cs[k + 2] + 7) >> 4;
+            }
+        }
+    }
+    const int x0 = 2 * j0, nv = min(8, w - x0);   // pixels of this thread's eight that lie in the image: 1..8
+    uint8_t* out = rgb + it.rgb_off;
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        const int row = 2 * i + v;
+        if (row >= h) continue;   // (an odd height: the last chroma row yields one output row)
+        const uint2 yy = *reinterpret_cast<const uint2*>(yp + (size_t)row * pw + x0);
+        unsigned o[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int y = (int)(((k < 4 ? yy.x : yy.y) >> (8 * (k & 3))) & 255u);
+            const int xb = up[0][v][k] - 128, xr = up[1][v][k] - 128;
+            const int rr = min(max(y + ((91881 * xr + 32768) >> 16), 0), 255);
+            const int bb = min(max(y + ((116130 * xb + 32768) >> 16), 0), 255);
+            const int gg = min(max(y + ((-22554 * xb + 32768 - 46802 * xr) >> 16), 0), 255);
+            o[(3 * k) >> 2] |= (unsigned)rr << (8 * ((3 * k) & 3));
+            o[(3 * k + 1) >> 2] |= (unsigned)gg << (8 * ((3 * k + 1) & 3));
+            o[(3 * k + 2) >> 2] |= (unsigned)bb << (8 * ((3 * k + 2) & 3));
+        }
+        store_bytes_any(out + ((size_t)row * w + x0) * 3, o, 3 * nv);
     }
 }
 
@@ -664,11 +794,63 @@ int lf_jpeg_idct_rgb_u8(const void* coef, size_t coef_stride, const void* qtab, 
     hipStream_t s = lf::as_stream(stream);
     const long groups = (long)n * (h / 16) * ((w / 16 + kGroup - 1) / kGroup);
     const unsigned grid = (unsigned)(groups < 256 * 16 ? groups : 256 * 16);
-    jpeg_idct_kernel<<<grid, kT, 0, s>>>(static_cast<const uint8_t*>(coef), coef_stride, static_cast<const uint8_t*>(qtab),
-                                         qtab_stride, yp, cbp, crp, h, w, n, zp);
+    jpeg_idct_kernel<false><<<grid, kT, 0, s>>>(static_cast<const uint8_t*>(coef), coef_stride,
+                                                static_cast<const uint8_t*>(qtab), qtab_stride, yp, cbp, crp, h, w, n, zp);
     const size_t total = (size_t)n * (h / 2) * (w / 8);
     jpeg_upsample_rgb_kernel<<<lf::stream_grid(total, kT, 256 * 32), kT, 0, s>>>(yp, cbp, crp, rgb, h, w, total);
     return lf::check_launch("lf_jpeg_idct_rgb");
+}
+
+size_t lf_jpeg_decode_items_workspace(const lf_jpeg_dec_item* host_items, int n) {
+    if (!host_items || n <= 0) return 0;
+    size_t mcus = 0;
+    for (int i = 0; i < n; ++i) {
+        if (host_items[i].h <= 0 || host_items[i].w <= 0) return 0;
+        mcus += (size_t)((host_items[i].h + 15) / 16) * ((host_items[i].w + 15) / 16);
+    }
+    return mcus * 384;   // per MCU 256 luminance and twice 64 chroma samples
+}
+
+int lf_jpeg_idct_rgb_items_u8(const void* slots, size_t slots_bytes, const lf_jpeg_dec_item* items,
+                              const lf_jpeg_dec_item* host_items, int n, uint8_t* rgb, size_t rgb_bytes, void* workspace,
+                              size_t ws_bytes, lf_stream_t stream) {
+    LF_REQUIRE(slots && items && host_items && rgb && workspace, "lf_jpeg_idct_rgb_items: null buffer");
+    LF_REQUIRE(n > 0 && n <= 1 << 20, "lf_jpeg_idct_rgb_items: bad batch size %d", n);
+    LF_REQUIRE((reinterpret_cast<size_t>(slots) & 15) == 0 && (reinterpret_cast<size_t>(workspace) & 15) == 0,
+               "lf_jpeg_idct_rgb_items: slots and workspace must be 16-byte aligned");
+    // the descriptors are checked here, on the host copy: every address the kernels form lies inside the three buffers
+    long groups = 0;
+    size_t mcus = 0;
+    for (int i = 0; i < n; ++i) {
+        const lf_jpeg_dec_item& it = host_items[i];
+        LF_REQUIRE(it.h > 0 && it.w > 0 && it.h < 65536 && it.w < 65536, "lf_jpeg_idct_rgb_items: image %d is %d x %d", i,
+                   it.h, it.w);
+        const size_t m = (size_t)((it.h + 15) / 16) * ((it.w + 15) / 16);
+        LF_REQUIRE(it.slot_off >= 0 && it.slot_off % 16 == 0 && (size_t)it.slot_bytes >= 256 + 768 * m &&
+                       (size_t)it.slot_off + (size_t)it.slot_bytes <= slots_bytes,
+                   "lf_jpeg_idct_rgb_items: slot %d must be 16-byte aligned, hold 256 + 768 bytes per MCU and lie in the buffer",
+                   i);
+        LF_REQUIRE(it.rgb_off >= 0 && (size_t)it.rgb_off + (size_t)3 * it.h * it.w <= rgb_bytes,
+                   "lf_jpeg_idct_rgb_items: the pixels of image %d do not lie in the buffer", i);
+        LF_REQUIRE(it.group_start == groups && it.plane_off == (int64_t)(384 * mcus),
+                   "lf_jpeg_idct_rgb_items: group_start / plane_off of image %d are not the running sums", i);
+        groups += lf_jpeg_fdct_groups(it.h, it.w);
+        mcus += m;
+    }
+    LF_REQUIRE(ws_bytes >= 384 * mcus, "lf_jpeg_idct_rgb_items: workspace too small");
+    static const uint8_t natural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                        41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                        30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    ZigPos zp;
+    for (int i = 0; i < 64; ++i) zp.pos[natural[i]] = (uint8_t)i;
+    hipStream_t s = lf::as_stream(stream);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const unsigned grid = (unsigned)(groups < 256 * 16 ? groups : 256 * 16);
+    jpeg_idct_kernel<true><<<grid, kT, 0, s>>>(static_cast<const uint8_t*>(slots), 0, nullptr, 0, ws, nullptr, nullptr, 0, 0, n,
+                                               zp, items, groups);
+    const long per = kT / 64;
+    jpeg_upsample_rgb_items_kernel<<<(unsigned)((groups + per - 1) / per), kT, 0, s>>>(ws, rgb, items, n, groups);
+    return lf::check_launch("lf_jpeg_idct_rgb_items");
 }
 
 int lf_jpeg_fdct_quant_u8(const uint8_t* rgb, int16_t* coef, int n, int h, int w, int quality,

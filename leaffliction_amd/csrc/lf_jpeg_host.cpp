@@ -18,6 +18,9 @@ long lf_jpeg_write_file(const int16_t* coef, int h, int w, int quality, uint8_t*
 int lf_jpeg_read_file(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtab128, int* h, int* w);
 size_t lf_jpeg_scan_aux_offset(int h, int w);
 int lf_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* slot, size_t cap, int* h, int* w, uint64_t* hash);
+int lf_jpeg_read_file_ragged(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtab128, int* h, int* w);
+size_t lf_jpeg_scan_aux_offset_ragged(int h, int w);
+int lf_jpeg_scan_prepare_ragged(const uint8_t* data, size_t len, uint8_t* slot, size_t cap, int* h, int* w, uint64_t* hash);
 }
 
 namespace {
@@ -294,8 +297,9 @@ static uint8_t* write_headers(uint8_t* p, int h, int w, int quality) {
 // Reading: markers + Huffman decoding of a baseline 4:2:0 file into the same coefficient layout the encoder
 // uses ([MCU][Y00 Y01 Y10 Y11 Cb Cr][64], zigzag order, still quantised) plus the file's two quantisation
 // tables; dequantisation, IDCT, upsampling and colour conversion are lf_jpeg_idct_rgb_u8's (GPU).
-// Everything this does not cover (progressive, other samplings, 12-bit, sizes that are not whole MCUs,
-// arithmetic coding) returns 1 and the caller decodes with libjpeg as before.
+// Everything this does not cover (progressive, other samplings, 12-bit, arithmetic coding; sizes that are not whole
+// MCUs for the plain entry points, widths under 5 for the _ragged ones) returns 1 and the caller decodes with libjpeg
+// as before.
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -477,7 +481,10 @@ struct Parsed {
 };
 
 // 0: `out.scan` is where the scan's bytes start; 1: a kind of file this path does not cover; -1: corrupt.
-int parse_until_scan(const uint8_t* data, size_t len, Parsed& P) {
+// ragged: any height and any width from 5 up instead of whole MCUs only (the scan then holds ceil(h/16) * ceil(w/16)
+// MCUs, libjpeg's dummy blocks included; at chroma widths of 1 and 2 libjpeg-turbo's upsampler does something the GPU
+// back end does not restate, so those stay libjpeg's).
+int parse_until_scan(const uint8_t* data, size_t len, Parsed& P, bool ragged) {
     if (!data || len < 4 || data[0] != 0xFF || data[1] != 0xD8) return -1;
     size_t pos = 2;
     while (pos + 4 <= len) {
@@ -531,7 +538,7 @@ int parse_until_scan(const uint8_t* data, size_t len, Parsed& P) {
                 P.comp_q[c] = q[8 + 3 * c];
                 if (hv != (c == 0 ? 0x22 : 0x11) || P.comp_q[c] > 3) return 1;   // 4:2:0 only
             }
-            if (P.h <= 0 || P.w <= 0 || P.h % 16 || P.w % 16) return 1;
+            if (P.h <= 0 || P.w <= 0 || (ragged ? P.w < 5 : (P.h % 16 || P.w % 16))) return 1;
             P.have_sof = true;
         } else if (m == 0xC2 || (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) {
             return 1;   // progressive, lossless, arithmetic
@@ -561,14 +568,18 @@ int parse_until_scan(const uint8_t* data, size_t len, Parsed& P) {
 
 }  // namespace
 
-extern "C" int lf_jpeg_read_file(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtab128,
-                                 int* h_out, int* w_out) {
+namespace {
+
+inline long mcus_of(int h, int w) { return (long)((h + 15) / 16) * ((w + 15) / 16); }
+
+int read_file(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtab128, int* h_out, int* w_out,
+              bool ragged) {
     if (!data || !coef || !qtab128 || !h_out || !w_out) return -1;
     Parsed P;
-    const int rc = parse_until_scan(data, len, P);
+    const int rc = parse_until_scan(data, len, P, ragged);
     if (rc != 0) return rc;
     const int h = P.h, w = P.w, restart = P.restart;
-    const long mcus = (long)(h / 16) * (w / 16);
+    const long mcus = mcus_of(h, w);
     if ((size_t)mcus * 384 > coef_cap) return -1;
     for (int k = 0; k < 64; ++k) {
         qtab128[k] = P.qt[P.comp_q[0]][k];
@@ -606,6 +617,19 @@ extern "C" int lf_jpeg_read_file(const uint8_t* data, size_t len, int16_t* coef,
     return 0;
 }
 
+}  // namespace
+
+extern "C" int lf_jpeg_read_file(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtab128,
+                                 int* h_out, int* w_out) {
+    return read_file(data, len, coef, coef_cap, qtab128, h_out, w_out, false);
+}
+
+// The same for any height and any width from 5 up: the coefficients of all ceil(h/16) * ceil(w/16) MCUs of the scan.
+extern "C" int lf_jpeg_read_file_ragged(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap,
+                                        uint16_t* qtab128, int* h_out, int* w_out) {
+    return read_file(data, len, coef, coef_cap, qtab128, h_out, w_out, true);
+}
+
 // The same file prepared for the GPU's Huffman decoder (lf_jpeg_huffman_u8, lf_jpeg_huff.hip) instead of being
 // decoded here.  The markers are parsed, the entropy-coded segment is freed of what a one-thread-per-image decoder
 // would stumble over — the 0xFF00 stuffing is undone and the RSTn markers are taken out, their places kept as
@@ -623,18 +647,25 @@ extern "C" int lf_jpeg_read_file(const uint8_t* data, size_t len, int16_t* coef,
 // differ from the Cb tables, a restart-marker count other than the frame calls for, a scan that does not end in
 // EOI, a file that does not fit `cap`: lf_jpeg_read_file or libjpeg then gives the verdict); -1 when the markers
 // are corrupt.
+// The _ragged twins take any height and any width from 5 up; the coefficient area is then sized by the MCUs of the
+// scan, [256, 256 + 768 * ceil(h/16) * ceil(w/16)), and aux = lf_jpeg_scan_aux_offset_ragged(h, w) lies behind that
+// (the same place as lf_jpeg_scan_aux_offset's for whole MCUs); restart intervals count MCUs of the padded grid.
 extern "C" size_t lf_jpeg_scan_aux_offset(int h, int w) { return ((size_t)256 + (size_t)3 * h * w + 15) / 16 * 16; }
 
-extern "C" int lf_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* slot, size_t cap, int* h_out, int* w_out,
-                                    uint64_t* hash_out) {
+extern "C" size_t lf_jpeg_scan_aux_offset_ragged(int h, int w) { return (size_t)256 + (size_t)768 * mcus_of(h, w); }
+
+namespace {
+
+int scan_prepare(const uint8_t* data, size_t len, uint8_t* slot, size_t cap, int* h_out, int* w_out, uint64_t* hash_out,
+                 bool ragged) {
     if (!data || !slot || !h_out || !w_out) return -1;
     Parsed P;
-    const int rc = parse_until_scan(data, len, P);
+    const int rc = parse_until_scan(data, len, P, ragged);
     if (rc != 0) return rc;
     if (P.td[2] != P.td[1] || P.ta[2] != P.ta[1] || P.h > 65535 || P.w > 65535) return 1;
-    const long mcus = (long)(P.h / 16) * (P.w / 16);
+    const long mcus = mcus_of(P.h, P.w);
     const long nint = P.restart ? (mcus + P.restart - 1) / P.restart : 1;
-    const size_t aux = lf_jpeg_scan_aux_offset(P.h, P.w), raw_len = len - P.scan;
+    const size_t aux = lf_jpeg_scan_aux_offset_ragged(P.h, P.w), raw_len = len - P.scan;
     const size_t data_off = 1120 + ((size_t)4 * (nint + 1) + 15) / 16 * 16;
     if (raw_len > 0x7FFFFFF0u || aux + data_off + raw_len + 16 > cap) return 1;
     uint8_t* a = slot + aux;
@@ -698,6 +729,18 @@ extern "C" int lf_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* sl
     *w_out = P.w;
     if (hash_out) *hash_out = hash;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int lf_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* slot, size_t cap, int* h_out, int* w_out,
+                                    uint64_t* hash_out) {
+    return scan_prepare(data, len, slot, cap, h_out, w_out, hash_out, false);
+}
+
+extern "C" int lf_jpeg_scan_prepare_ragged(const uint8_t* data, size_t len, uint8_t* slot, size_t cap, int* h_out,
+                                           int* w_out, uint64_t* hash_out) {
+    return scan_prepare(data, len, slot, cap, h_out, w_out, hash_out, true);
 }
 
 // ---------------------------------------------------------------------------

@@ -95,6 +95,23 @@ __device__ __forceinline__ unsigned lookup(const HuffTab& T, int t, uint64_t buf
     return e;   // 0: no such code
 }
 
+// the MCUs of the scan: ragged sizes are coded as whole MCUs (libjpeg's edge replication and dummy blocks)
+__device__ __forceinline__ uint32_t mcus_of(int h, int w) { return (uint32_t)((h + 15) / 16) * (uint32_t)((w + 15) / 16); }
+
+// One image's geometry: the same for all N of lf_jpeg_huffman_u8 (slots a stride apart), or its own in
+// lf_jpeg_huffman_items_u8 (lf_jpeg_dec_item: where the slot starts, its size, the image's size).
+struct Geom {
+    size_t off, stride, aux;
+    int h, w;
+};
+
+__device__ __forceinline__ Geom geom_of(const lf_jpeg_dec_item* __restrict__ items, int img, size_t stride, int h, int w,
+                                        size_t aux) {
+    if (!items) return Geom{(size_t)img * stride, stride, aux, h, w};
+    const lf_jpeg_dec_item it = items[img];
+    return Geom{(size_t)it.slot_off, (size_t)it.slot_bytes, (size_t)256 + (size_t)768 * mcus_of(it.h, it.w), it.h, it.w};
+}
+
 struct ScanHeader {
     uint32_t restart, nint, data_off, data_len;
     uint64_t hash;
@@ -112,7 +129,7 @@ __device__ __forceinline__ ScanHeader read_header(const uint8_t* a, int h, int w
     __builtin_memcpy(&H.hash, a + 16, 8);
     __builtin_memcpy(&H.data_off, a + 24, 4);
     __builtin_memcpy(&H.data_len, a + 28, 4);
-    const uint32_t mcus = (uint32_t)(h / 16) * (uint32_t)(w / 16);
+    const uint32_t mcus = mcus_of(h, w);
     const uint32_t want_int = H.restart ? (mcus + H.restart - 1) / H.restart : 1u;
     H.ok = magic == kMagic && hw[0] == h && hw[1] == w && H.nint == want_int && H.data_off % 16 == 0 &&
            H.data_off >= 1120 + 4 * (H.nint + 1) && aux + H.data_off + (size_t)H.data_len + 16 <= stride;
@@ -127,6 +144,16 @@ __global__ __launch_bounds__(256) void jpeg_huff_zero_kernel(uint8_t* __restrict
         const size_t img = i / per, o = i - img * per;
         *reinterpret_cast<uint4*>(slots + img * stride + 256 + o * 16) = make_uint4(0, 0, 0, 0);
     }
+}
+
+// images of different sizes: blockIdx.y is the image, the workgroups of a row share its coefficient area
+__global__ __launch_bounds__(256) void jpeg_huff_zero_items_kernel(uint8_t* __restrict__ slots,
+                                                                  const lf_jpeg_dec_item* __restrict__ items) {
+    const lf_jpeg_dec_item it = items[blockIdx.y];
+    const size_t per = (size_t)48 * mcus_of(it.h, it.w);   // 768 bytes per MCU, 16 per store
+    uint4* dst = reinterpret_cast<uint4*>(slots + it.slot_off + 256);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (size_t)gridDim.x * 256)
+        dst[i] = make_uint4(0, 0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -335,8 +362,9 @@ __device__ __forceinline__ void decode_interval(const HuffTab& T, const uint64_t
     if (bad || p > end_bits || end_bits - p >= 8u) *fail = 1;
 }
 
-__global__ __launch_bounds__(kPT) void jpeg_huffman_par_kernel(uint8_t* __restrict__ slots, size_t stride, int h, int w,
-                                                              size_t aux, int* __restrict__ status) {
+__global__ __launch_bounds__(kPT) void jpeg_huffman_par_kernel(uint8_t* __restrict__ slots, size_t stride0, int h0, int w0,
+                                                              size_t aux0, int* __restrict__ status,
+                                                              const lf_jpeg_dec_item* __restrict__ items = nullptr) {
     __shared__ ParLds S;
     const int tid = threadIdx.x, img = blockIdx.x;
 #ifdef LF_HUFF_STATS   // development build: cycle stamps of the phases into the first 64 bytes of the slot (over the tables)
@@ -346,9 +374,12 @@ __global__ __launch_bounds__(kPT) void jpeg_huffman_par_kernel(uint8_t* __restri
 #else
 #define LF_STAMP(i)
 #endif
-    uint8_t* slot = slots + (size_t)img * stride;
+    const Geom G = geom_of(items, img, stride0, h0, w0, aux0);   // the same for every thread
+    const size_t stride = G.stride, aux = G.aux;
+    const int h = G.h, w = G.w;
+    uint8_t* slot = slots + G.off;
     const uint8_t* a = slot + aux;
-    const ScanHeader H = read_header(a, h, w, aux, stride);   // the same for every thread
+    const ScanHeader H = read_header(a, h, w, aux, stride);
     if (!H.ok) {
         if (tid == 0) status[img] = 3;
         return;
@@ -374,7 +405,7 @@ __global__ __launch_bounds__(kPT) void jpeg_huffman_par_kernel(uint8_t* __restri
         for (uint32_t i = tid; i < room; i += kPT)
             reinterpret_cast<uint4*>(S.stream)[i] = i < pieces ? src[i] : make_uint4(0, 0, 0, 0);
     const uint32_t total_bits = H.data_len * 8u;
-    const uint32_t mcus = (uint32_t)(h / 16) * (uint32_t)(w / 16), total = mcus * 6u;
+    const uint32_t mcus = mcus_of(h, w), total = mcus * 6u;
     int16_t* coef = reinterpret_cast<int16_t*>(slot + 256);
     if (H.restart != 0) {
         // restart intervals are where the file itself says a decoder may start: one thread per interval, no guessing
@@ -499,8 +530,9 @@ __device__ __forceinline__ uint64_t load8_be(const uint8_t* p) {
 
 // redo != 0: only the images whose status is 4 (left by the parallel kernel).  The tables are those of the first image
 // of the group of 64 that has work; an image with other tables reports status 2.
-__global__ __launch_bounds__(kHT) void jpeg_huffman_seq_kernel(uint8_t* __restrict__ slots, size_t stride, int n, int h,
-                                                              int w, size_t aux, int* __restrict__ status, int redo) {
+__global__ __launch_bounds__(kHT) void jpeg_huffman_seq_kernel(uint8_t* __restrict__ slots, size_t stride0, int n, int h0,
+                                                              int w0, size_t aux0, int* __restrict__ status, int redo,
+                                                              const lf_jpeg_dec_item* __restrict__ items = nullptr) {
     __shared__ HuffTab T;
     __shared__ int leader;
     const int lane = threadIdx.x;
@@ -512,8 +544,9 @@ __global__ __launch_bounds__(kHT) void jpeg_huffman_seq_kernel(uint8_t* __restri
     __syncthreads();
     if (leader < 0) return;
     const int lead = kHT - 1 - leader;
-    const uint8_t* la = slots + ((size_t)blockIdx.x * kHT + lead) * stride + aux;
-    const ScanHeader LH = read_header(la, h, w, aux, stride);
+    const Geom LG = geom_of(items, blockIdx.x * kHT + lead, stride0, h0, w0, aux0);
+    const uint8_t* la = slots + LG.off + LG.aux;
+    const ScanHeader LH = read_header(la, LG.h, LG.w, LG.aux, LG.stride);
     if (!LH.ok) {   // uniform: nothing to build the tables from
         if (want) status[img] = 3;
         return;
@@ -524,9 +557,10 @@ __global__ __launch_bounds__(kHT) void jpeg_huffman_seq_kernel(uint8_t* __restri
         status[img] = 3;
         return;
     }
-    uint8_t* slot = slots + (size_t)img * stride;
-    const uint8_t* a = slot + aux;
-    const ScanHeader H = read_header(a, h, w, aux, stride);
+    const Geom G = geom_of(items, img, stride0, h0, w0, aux0);
+    uint8_t* slot = slots + G.off;
+    const uint8_t* a = slot + G.aux;
+    const ScanHeader H = read_header(a, G.h, G.w, G.aux, G.stride);
     if (!H.ok) {
         status[img] = 3;
         return;
@@ -548,7 +582,7 @@ __global__ __launch_bounds__(kHT) void jpeg_huffman_seq_kernel(uint8_t* __restri
     uint64_t buf = 0, nxt = load8_be(sp + pos);
     int nb = 0, pad = 0;
     uint32_t iv = 0, until = restart;
-    const uint32_t total = (uint32_t)(h / 16) * (uint32_t)(w / 16) * 6u;
+    const uint32_t total = mcus_of(G.h, G.w) * 6u;
     uint32_t blk = 0;
     int b6 = 0, k = 0;
     int pred0 = 0, pred1 = 0, pred2 = 0;
@@ -663,6 +697,33 @@ int lf_jpeg_huffman_u8(void* slots, size_t stride, int n, int h, int w, int* sta
     jpeg_huffman_seq_kernel<<<(unsigned)((n + kHT - 1) / kHT), kHT, 0, s>>>(static_cast<uint8_t*>(slots), stride, n, h, w,
                                                                            aux, status, mode == 0 ? 1 : 0);
     return lf::check_launch("lf_jpeg_huffman");
+}
+
+size_t lf_jpeg_scan_aux_offset_ragged(int h, int w);   // lf_jpeg_host.cpp
+
+int lf_jpeg_huffman_items_u8(void* slots, size_t slots_bytes, const lf_jpeg_dec_item* items,
+                             const lf_jpeg_dec_item* host_items, int n, int* status, int mode, lf_stream_t stream) {
+    LF_REQUIRE(slots && items && host_items && status, "lf_jpeg_huffman_items: null buffer");
+    LF_REQUIRE(n > 0 && n <= 65535, "lf_jpeg_huffman_items: bad batch size %d", n);
+    LF_REQUIRE(mode == 0 || mode == 1,
+               "lf_jpeg_huffman_items: mode is 0 (parallel kernel first) or 1 (sequential kernel only)");
+    LF_REQUIRE((reinterpret_cast<size_t>(slots) & 15) == 0, "lf_jpeg_huffman_items: slots must be 16-byte aligned");
+    for (int i = 0; i < n; ++i) {
+        const lf_jpeg_dec_item& it = host_items[i];
+        LF_REQUIRE(it.h > 0 && it.w > 0 && it.h < 65536 && it.w < 65536, "lf_jpeg_huffman_items: image %d is %d x %d", i,
+                   it.h, it.w);
+        LF_REQUIRE(it.slot_off >= 0 && it.slot_off % 16 == 0 && it.slot_bytes % 16 == 0 &&
+                       (size_t)it.slot_bytes >= lf_jpeg_scan_aux_offset_ragged(it.h, it.w) + 1120 + 32 &&
+                       (size_t)it.slot_off + (size_t)it.slot_bytes <= slots_bytes,
+                   "lf_jpeg_huffman_items: slot %d must be 16-byte aligned, hold a prepared scan and lie in the buffer", i);
+    }
+    hipStream_t s = lf::as_stream(stream);
+    uint8_t* base = static_cast<uint8_t*>(slots);
+    jpeg_huff_zero_items_kernel<<<dim3(8, (unsigned)n), 256, 0, s>>>(base, items);
+    if (mode == 0) jpeg_huffman_par_kernel<<<(unsigned)n, kPT, 0, s>>>(base, 0, 0, 0, 0, status, items);
+    jpeg_huffman_seq_kernel<<<(unsigned)((n + kHT - 1) / kHT), kHT, 0, s>>>(base, 0, n, 0, 0, 0, status, mode == 0 ? 1 : 0,
+                                                                           items);
+    return lf::check_launch("lf_jpeg_huffman_items");
 }
 
 }  // extern "C"

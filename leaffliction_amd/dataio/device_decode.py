@@ -3,15 +3,18 @@
 The reference decodes one file after the other with Pillow and resizes on the host
 (`ImageLoader.load_as_array` / `resize_array`, srcs/utils/image_utils.py:19-59,109-114, called from
 srcs/dataio/sequence.py:74-125 and srcs/predict/predictor.py).  Here codec worker processes read the
-files and, of baseline 4:2:0 JPEGs of whole MCUs, either the markers only (`chunks`: the un-stuffed scan goes into the
-page-locked slab and the GPU decodes the Huffman stream too, `ops.jpeg_huffman_u8`) or the markers and the Huffman
-stream (the prefetching `submit` / `collect`, which never waits for the GPU and so cannot ask it for a verdict on a
-damaged scan); any other file is decoded whole by Pillow in the worker.  A chunk crosses PCIe as one copy (its used
-parts only when every file is a prepared scan), and the GPU does dequantisation / IDCT / fancy upsampling / colour
-conversion (`ops.jpeg_idct_rgb_u8`) and the Pillow-exact
-LANCZOS resize, chunk after chunk with the next two chunks' files already being read.  The pixels are
-Pillow's bit for bit (tests/test_jpeg_codec.py), so everything downstream sees what the reference's loop
-would have produced.
+files and, of baseline 4:2:0 JPEGs of any height and any width from 5 up, either the markers only (`chunks`: the
+un-stuffed scan goes into the page-locked slab and the GPU decodes the Huffman stream too, `ops.jpeg_huffman_u8`) or the
+markers and the Huffman stream (the prefetching `submit` / `collect`, which never waits for the GPU and so cannot ask it
+for a verdict on a damaged scan); any other file (grey, other samplings, progressive, narrower than 5 pixels) is decoded
+whole by Pillow in the worker.  A chunk crosses PCIe as one copy (its used parts only when every file is a prepared
+scan), and the GPU does dequantisation / IDCT / fancy upsampling / colour conversion and the Pillow-exact LANCZOS
+resize, chunk after chunk with the next two chunks' files already being read.  A chunk of one whole-MCU size goes
+through the one-size calls (`ops.jpeg_idct_rgb_u8`); any other chunk — the augmented tree: every `rotate(expand=True)`
+output has a size of its own, hardly ever whole MCUs — through the `_items_` calls, one Huffman, one IDCT and one
+upsampling launch for all its sizes; only the resize is still one launch per distinct size.  The pixels are Pillow's
+bit for bit (tests/test_jpeg_codec.py, tests/test_jpeg_ragged.py), so everything downstream sees what the reference's
+loop would have produced.  `counts` says how the files were decoded.
 """
 from __future__ import annotations
 
@@ -38,6 +41,10 @@ class DeviceDecoder:
         self._pending: List[dict] = []   # submitted, not yet collected batches (at most two)
         self._uploaded = [None, None, None]   # per slab third: event behind its last (asynchronous) upload
         self._ring = 0                   # next slab third `submit` uses
+        # how the files were decoded so far: Huffman and pixels on the GPU | Huffman in the worker, pixels on the GPU |
+        # whole by Pillow (in the worker, or here for a scan the GPU handed back) | by Pillow, too large for the slot
+        # and so pickled | not at all (an error)
+        self.counts: Dict[str, int] = {"gpu_huffman": 0, "host_huffman": 0, "pillow": 0, "pickled": 0, "failed": 0}
 
     def _ensure(self, slot: int):
         import torch
@@ -53,20 +60,30 @@ class DeviceDecoder:
         return self._codec
 
     @staticmethod
-    def _probe_slot(paths: Sequence[str], fallback: int, scan: bool = False) -> int:
+    def _probe_slot(paths: Sequence[str], fallback: int, scan: bool = False, samples: int = 32) -> int:
+        """Slot size from the largest of `samples` files spread evenly over the list (their headers only), by its
+        padded footprint: the coefficients of a size that is not whole MCUs are those of ceil(h/16) * ceil(w/16) MCUs.
+        Not from the first file: in an augmented tree the first files of a class folder may all be originals while a
+        +-30 degree rotate(expand=True) canvas has up to (cos 30 + sin 30)^2 = 1.87 times their area.  Only the used
+        front of a slot crosses PCIe, so a larger slot costs page-locked memory, not transfer.  A canvas that still
+        does not fit — larger than everything sampled — is decoded whole by Pillow in the worker and travels as a
+        pickled array (counted as "pickled"): ~0.6 ms of a worker and ten times the bytes, but the same pixels."""
         from PIL import Image
-        w0 = h0 = fallback
-        for p in paths[:8]:   # slot size from the first readable file (larger images travel as pickled arrays)
+        px, seen = fallback * fallback, 0
+        last = len(paths) - 1
+        spread = sorted({round(j * last / max(1, samples - 1)) for j in range(samples)}) if last > 0 else [0]
+        for p in (paths[j] for j in spread[:len(paths)]):
             try:
                 with Image.open(p) as probe:
                     w0, h0 = probe.size
-                break
             except Exception:  # noqa: BLE001
                 continue
+            px = max(px if seen else 0, 256 * -(-h0 // 16) * -(-w0 // 16))
+            seen += 1
         # tables + coefficients (or pixels), and behind them room for a prepared scan (header, Huffman tables and the
         # un-stuffed entropy-coded bytes: ~0.16 of the pixel bytes at quality 95; a file that does not fit takes the
         # host's Huffman pass)
-        return (256 + h0 * w0 * 3 + ((1136 + h0 * w0 * 3 // 2) if scan else 0) + 4095) // 4096 * 4096
+        return (256 + px * 3 + ((1136 + px * 3 // 2) if scan else 0) + 4095) // 4096 * 4096
 
     def _submit(self, part: Sequence[str], third: int, scan: bool = False):
         """`scan`: the workers read the markers only and the GPU decodes the Huffman stream as well — for callers that
@@ -103,7 +120,7 @@ class DeviceDecoder:
             # coefficient area are all that has to cross PCIe
             from .. import _lib
             from ..utils import jpeg_host
-            lo = min(jpeg_host.scan_aux_offset(hh, ww) for hh, ww in {(d[1][0], d[1][1]) for d in live})
+            lo = min(jpeg_host.scan_aux_offset_ragged(hh, ww) for hh, ww in {(d[1][0], d[1][1]) for d in live})
             hi = min(_slot, (max(d[1][3] for d in live) + 15) // 16 * 16)
             stream = torch.cuda.current_stream().cuda_stream
             _lib.call("lf_copy_rows", dev_in.data_ptr(), _slot, host.data_ptr(), _slot, 256, n, 0, stream)
@@ -121,21 +138,43 @@ class DeviceDecoder:
         groups: Dict[tuple, List[int]] = {}
         big: Dict[int, np.ndarray] = {}
         errors: List[Tuple[int, str]] = []
+        counts = self.counts
+        # JPEG slots ("scan" / "coef") of one whole-MCU size: the one-size calls, as ever.  Anything else — several
+        # sizes, or a size that is not whole MCUs — is decoded where it lies, all sizes in one launch per step, and only
+        # grouped by size for the resize.
+        jpeg = [k for k, d in enumerate(decoded) if d[0] in ("scan", "coef")]
+        kinds = {(decoded[k][0],) + tuple(decoded[k][1][:2]) for k in jpeg}
+        mixed = len(kinds) > 1 or any(hh % 16 or ww % 16 for _st, hh, ww in kinds)
         for k, (status, payload, _prm) in enumerate(decoded):
             if status == "err":
                 errors.append((pos0 + k, payload))
+                counts["failed"] += 1
             elif status == "big":
                 big[k] = payload
                 groups.setdefault(("big",) + tuple(payload.shape[:2]), []).append(k)
+                counts["pickled"] += 1
             else:
-                groups.setdefault((status,) + tuple(payload[:2]), []).append(k)
+                groups.setdefault(("jpeg" if mixed and status in ("scan", "coef") else status,) + tuple(payload[:2]),
+                                  []).append(k)
+                counts[{"scan": "gpu_huffman", "coef": "host_huffman", "ok": "pillow"}[status]] += 1
         natives: Optional[Dict[int, np.ndarray]] = {} if keep_native else None
         x = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
         huffman: List[tuple] = []   # (positions in the chunk, device status of the GPU's Huffman decoding)
+        views: Dict[int, "torch.Tensor"] = {}
+        if mixed:
+            flat = dev_in.view(-1)
+            scans = [k for k in jpeg if decoded[k][0] == "scan"]
+            if scans:
+                huffman.append((scans, ops.jpeg_huffman_items_u8(
+                    flat, [(k * _slot, _slot) + tuple(decoded[k][1][:2]) for k in scans])))
+            _px, vs = ops.jpeg_idct_rgb_items_u8(flat, [(k * _slot, _slot) + tuple(decoded[k][1][:2]) for k in jpeg])
+            views = dict(zip(jpeg, vs))
         for (status, h, w), ks in groups.items():
             whole = len(ks) == n   # one group holds the whole chunk (the usual case): no gather, no scatter
             idx = None if whole else index(ks)
-            if status == "scan":
+            if status == "jpeg":
+                px = views[ks[0]].unsqueeze(0) if len(ks) == 1 else torch.stack([views[k] for k in ks])
+            elif status == "scan":
                 rows = dev_in if whole else dev_in[idx]
                 huffman.append((ks, ops.jpeg_huffman_u8(rows, h, w)))
                 px = ops.jpeg_idct_rgb_u8(rows, h, w)
@@ -160,6 +199,8 @@ class DeviceDecoder:
             for k in (k for k, v in zip(ks, st) if v):
                 # a scan the GPU handed back (damaged, cut short): Pillow has the reference's verdict
                 # (image_utils.py:19-33) — pixels, with libjpeg's concealment, or an error
+                counts["gpu_huffman"] -= 1
+                counts["pillow"] += 1
                 try:
                     from ..utils.image_utils import ImageLoader
                     arr = ImageLoader.load_as_array(paths[k])
@@ -169,6 +210,8 @@ class DeviceDecoder:
                         natives[pos0 + k] = arr
                 except Exception as e:  # noqa: BLE001
                     errors.append((pos0 + k, f"{paths[k]} - {e}"))
+                    counts["pillow"] -= 1
+                    counts["failed"] += 1
                     kept.remove(k)
                     if natives is not None:
                         natives.pop(pos0 + k, None)
@@ -217,7 +260,7 @@ class DeviceDecoder:
         paths = [str(p) for p in paths]
         if not paths or len(paths) > self.CHUNK or len(self._pending) >= 2:
             return None
-        slot = self._probe_slot(paths, int(img_size))
+        slot = self._probe_slot(paths, int(img_size), samples=4)   # (per batch: four headers, not thirty-two)
         if self._codec is None or self._codec[1] < slot:
             self.drop_pending()
             self._ensure(slot)

@@ -6,7 +6,7 @@ is never launched with operand shapes other than the ones its grid assumes.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -549,6 +549,78 @@ def jpeg_idct_rgb_u8(slots: torch.Tensor, h: int, w: int, out: Optional[torch.Te
     _lib.call("lf_jpeg_idct_rgb_u8", slots.data_ptr() + 256, stride, slots.data_ptr(), stride, out.data_ptr(),
               n, h, w, ws.data_ptr(), nbytes, _stream())
     return out
+
+
+class JpegDecItems:
+    """The lf_jpeg_dec_item array of one chunk of prepared slots of different sizes, on the host (the library checks it
+    before a launch) and on the device (the kernels read it).  `items[i]` = (byte offset of image i's slot in the slot
+    buffer, bytes of the slot, h, w); `rgb_offsets[i]` = where its pixels go in the pixel buffer (default: packed back
+    to back in the order given).  `offsets`, `sizes`, `rgb_bytes` (first byte behind the last image) for the caller."""
+
+    def __init__(self, items: Sequence[Sequence[int]], device, rgb_offsets: Optional[Sequence[int]] = None) -> None:
+        n = len(items)
+        if n == 0:
+            raise ValueError("jpeg_dec_items: no images")
+        lib = _lib.load()
+        desc = np.zeros((n, 6), dtype=np.int64)   # four int64, (h, w) as an int32 pair, one int64
+        hw = desc[:, 4:].view(np.int32)   # [n, 4]: h, w, then the two halves of slot_bytes
+        groups = mcus = packed = end = 0
+        self.offsets: List[int] = []
+        self.sizes: List[Tuple[int, int]] = []
+        for i, (off, room, h, w) in enumerate(items):
+            off, room, h, w = int(off), int(room), int(h), int(w)
+            if h <= 0 or w <= 0 or h > 65535 or w > 65535 or off < 0 or off % 16 or room % 16:
+                raise ValueError(f"jpeg_dec_items: image {i} ({h}x{w}, slot of {room} bytes at {off})")
+            at = packed if rgb_offsets is None else int(rgb_offsets[i])
+            desc[i] = (off, at, 384 * mcus, groups, 0, room)
+            hw[i, :2] = (h, w)
+            self.offsets.append(at)
+            self.sizes.append((h, w))
+            groups += int(lib.lf_jpeg_fdct_groups(h, w))
+            mcus += -(-h // 16) * -(-w // 16)
+            packed += 3 * h * w
+            end = max(end, at + 3 * h * w)
+        self.n, self.host, self.rgb_bytes = n, desc, end
+        self.dev = torch.from_numpy(desc).to(device)
+        self.ws_bytes = int(lib.lf_jpeg_decode_items_workspace(desc.ctypes.data, n))
+
+
+def _dec_items(buf: torch.Tensor, items, what: str) -> JpegDecItems:
+    _chk(buf, _U8, what + ".buf")
+    if not buf.is_contiguous() or buf.data_ptr() % 16:
+        raise ValueError(f"{what}.buf: expected a contiguous, 16-byte aligned uint8 tensor")
+    return items if isinstance(items, JpegDecItems) else JpegDecItems(items, buf.device)
+
+
+def jpeg_huffman_items_u8(buf: torch.Tensor, items, sequential: bool = False) -> torch.Tensor:
+    """jpeg_huffman_u8 for prepared slots of DIFFERENT sizes (utils.jpeg_host.scan_prepare_ragged_into: any height, any
+    width from 5 up) in one launch per step: `buf` is the uint8 device buffer the slots lie in, `items` a JpegDecItems
+    or its (slot offset, slot bytes, h, w) list.  Every slot's coefficient area [256, 256 + 768 * MCUs) is written in
+    place; returns int32 [N] on the device, the status codes of jpeg_huffman_u8."""
+    d = _dec_items(buf, items, "jpeg_huffman_items")
+    status = torch.empty(d.n, dtype=torch.int32, device=buf.device)
+    _lib.call("lf_jpeg_huffman_items_u8", buf.data_ptr(), buf.numel(), d.dev.data_ptr(), d.host.ctypes.data, d.n,
+              status.data_ptr(), 1 if sequential else 0, _stream())
+    return status
+
+
+def jpeg_idct_rgb_items_u8(buf: torch.Tensor, items, out: Optional[torch.Tensor] = None):
+    """The pixel half of Image.open(path).convert("RGB") for slots of DIFFERENT sizes (Huffman-decoded by
+    jpeg_huffman_items_u8 or by utils.jpeg_host.read_file_ragged_into), two launches for all of them: IDCT into padded
+    planes; cut, fancy upsampling and colour conversion.  Returns (flat uint8 pixel buffer, per-image views [h, w, 3]
+    of it): image i tightly packed at the JpegDecItems' offsets[i] (back to back by default) — Pillow's pixels, bit
+    for bit.  `out`: a flat uint8 buffer to write into instead (nothing but each image's 3hw bytes is written)."""
+    d = _dec_items(buf, items, "jpeg_idct_rgb_items")
+    if out is None:
+        out = torch.empty(d.rgb_bytes, dtype=_U8, device=buf.device)
+    else:
+        _chk(out, _U8, "jpeg_idct_rgb_items.out", 1)
+        if not out.is_contiguous() or out.numel() < d.rgb_bytes:
+            raise ValueError("jpeg_idct_rgb_items.out: expected a flat contiguous uint8 buffer that holds every image")
+    ws = torch.empty(d.ws_bytes, dtype=_U8, device=buf.device)
+    _lib.call("lf_jpeg_idct_rgb_items_u8", buf.data_ptr(), buf.numel(), d.dev.data_ptr(), d.host.ctypes.data, d.n,
+              out.data_ptr(), out.numel(), ws.data_ptr(), d.ws_bytes, _stream())
+    return out, [out[o:o + 3 * h * w].view(h, w, 3) for o, (h, w) in zip(d.offsets, d.sizes)]
 
 
 # ---------------------------------------------------------------------------

@@ -86,10 +86,13 @@ def _decode_jobs(names: Dict[str, str], jobs: Sequence[tuple]):
     [, noise on the GPU]]).
     Returns per job ("ok", shape, params) | ("coef", shape, params) | ("scan", shape, params) | ("big", array, params)
     | ("err", message).
-    "coef": the file was a baseline 4:2:0 JPEG of whole MCUs and the slot holds its quantisation tables and
+    "coef": the file was a baseline 4:2:0 JPEG and the slot holds its quantisation tables and
     Huffman-decoded coefficients (libleafcodec.so); the GPU finishes the decoding (ops.jpeg_idct_rgb_u8).
     "scan" (asked for with 2): only the file's markers were read here; the slot holds the tables and the un-stuffed
-    scan, and the Huffman decoding is the GPU's as well (ops.jpeg_huffman_u8); shape = (h, w, 3, bytes of the slot in use)."""
+    scan, and the Huffman decoding is the GPU's as well (ops.jpeg_huffman_u8); shape = (h, w, 3, bytes of the slot in use).
+    A file the whole-MCU functions decline (a rotated canvas, mostly: any height, any width from 5 up) is offered to
+    their ragged twins before Pillow; its slot then holds the coefficients of the padded MCU grid and the GPU calls are
+    the _items_ ones (ops.jpeg_huffman_items_u8 / ops.jpeg_idct_rgb_items_u8); the statuses are the same."""
     from ..utils import jpeg_host
     from ..utils.image_utils import ImageLoader, _checked
     from .image_augmenter import draw_params
@@ -105,10 +108,10 @@ def _decode_jobs(names: Dict[str, str], jobs: Sequence[tuple]):
                     data = f.read()
                 dst = np.frombuffer(buf_in, np.uint8, cap, off)
                 if job[6] == 2:
-                    got = jpeg_host.scan_prepare_into(data, dst)
+                    got = jpeg_host.scan_prepare_into(data, dst) or jpeg_host.scan_prepare_ragged_into(data, dst)
                     scan_hw = (got[0], got[1], got[3]) if got is not None else None
                 if scan_hw is None:
-                    coef_hw = jpeg_host.read_file_into(data, dst)
+                    coef_hw = jpeg_host.read_file_into(data, dst) or jpeg_host.read_file_ragged_into(data, dst)
             if scan_hw is not None:
                 h, w = scan_hw[:2]
             elif coef_hw is None:

@@ -323,6 +323,24 @@ class DatasetBalancer:
             for (op, h, w, status), ks in groups.items():
                 if status in ("coef", "scan"):
                     sizes.setdefault((h, w, status), []).extend(ks)
+            if len(sizes) > 1 or any(h % 16 or w % 16 for h, w, _st in sizes):
+                # several sizes, or sources that are not whole MCUs (a tree that was augmented before: every rotated
+                # canvas has a size of its own): decoded where they lie, all sizes in one launch per step
+                hw = {k: (h, w) for (h, w, _st), ks in sizes.items() for k in ks}
+                jk = sorted(hw)
+                scans = sorted(k for (_h, _w, st), ks in sizes.items() if st == "scan" for k in ks)
+                try:
+                    flat, slot = dev_in.view(-1), pool.slot_bytes
+                    if scans:
+                        huffman.append((scans, ops.jpeg_huffman_items_u8(flat, [(k * slot, slot) + hw[k] for k in scans])))
+                    _px, views = ops.jpeg_idct_rgb_items_u8(flat, [(k * slot, slot) + hw[k] for k in jk])
+                    view_of = dict(zip(jk, views))
+                    for key, ks in sizes.items():
+                        ks.sort()
+                        decoded_px[key] = (torch.stack([view_of[k] for k in ks]), {k: j for j, k in enumerate(ks)})
+                except Exception as e:  # noqa: BLE001
+                    logger.error(f"Failed to decode a batch of {len(jk)} sources of {len(sizes)} sizes: {e}")
+                sizes = {}
             for (h, w, status), ks in sizes.items():
                 ks.sort()
                 try:
@@ -433,7 +451,7 @@ class DatasetBalancer:
         host = pool.tensor("in", base, n)
         live = [d for d in decoded if d[0] != "err"]
         if live and all(d[0] == "scan" for d in live):
-            lo = min(jpeg_host.scan_aux_offset(h, w) for h, w in {(d[1][0], d[1][1]) for d in live})
+            lo = min(jpeg_host.scan_aux_offset_ragged(h, w) for h, w in {(d[1][0], d[1][1]) for d in live})
             hi = (max(d[1][3] for d in live) + 15) // 16 * 16
             if 256 <= lo < hi <= pool.slot_bytes:
                 stream = torch.cuda.current_stream().cuda_stream

@@ -37,6 +37,12 @@ def load() -> C.CDLL:
         lib.lf_jpeg_scan_prepare.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
         lib.lf_jpeg_scan_prepare.restype = C.c_int
+        lib.lf_jpeg_read_file_ragged.argtypes = lib.lf_jpeg_read_file.argtypes
+        lib.lf_jpeg_read_file_ragged.restype = C.c_int
+        lib.lf_jpeg_scan_aux_offset_ragged.argtypes = [C.c_int, C.c_int]
+        lib.lf_jpeg_scan_aux_offset_ragged.restype = C.c_size_t
+        lib.lf_jpeg_scan_prepare_ragged.argtypes = lib.lf_jpeg_scan_prepare.argtypes
+        lib.lf_jpeg_scan_prepare_ragged.restype = C.c_int
         _LIB = lib
     return _LIB
 
@@ -63,19 +69,47 @@ def write_file(coef: np.ndarray, h: int, w: int, quality: int = 95) -> bytes:
 QTAB_BYTES = 256   # two tables of 64 uint16 (luminance, chrominance), row-major
 
 
+def _read_file_code(data: bytes, dst: np.ndarray, ragged: bool):
+    """(the library's verdict: 0 read, 1 not covered, -1 corrupt or no room; h; w)"""
+    lib = load()
+    if dst.dtype != np.uint8 or not dst.flags["C_CONTIGUOUS"] or dst.size < QTAB_BYTES + 768:
+        return -1, 0, 0
+    h, w = C.c_int(0), C.c_int(0)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    base = dst.ctypes.data
+    fn = lib.lf_jpeg_read_file_ragged if ragged else lib.lf_jpeg_read_file
+    rc = fn(buf.ctypes.data, buf.size, base + QTAB_BYTES, (dst.size - QTAB_BYTES) // 2, base, C.byref(h), C.byref(w))
+    return int(rc), h.value, w.value
+
+
 def read_file_into(data: bytes, dst: np.ndarray):
     """Parse + Huffman-decode a baseline 4:2:0 JPEG into `dst` (uint8 view of a slab slot): the two
     quantisation tables (256 bytes) followed by the quantised coefficients [MCUs, 6, 64] int16 in zigzag order.
     Returns (h, w), or None when the file is not of that kind (the caller decodes it with libjpeg) or does not fit."""
+    rc, h, w = _read_file_code(data, dst, False)
+    return (h, w) if rc == 0 else None
+
+
+def read_file_ragged_into(data: bytes, dst: np.ndarray):
+    """read_file_into for any height and any width from 5 up: the coefficients of all ceil(h/16) * ceil(w/16) MCUs
+    of the scan (ops.jpeg_idct_rgb_items_u8 finishes the decoding)."""
+    rc, h, w = _read_file_code(data, dst, True)
+    return (h, w) if rc == 0 else None
+
+
+def _scan_prepare_code(data: bytes, dst: np.ndarray, ragged: bool):
     lib = load()
-    if dst.dtype != np.uint8 or not dst.flags["C_CONTIGUOUS"] or dst.size < QTAB_BYTES + 768:
-        return None
-    h, w = C.c_int(0), C.c_int(0)
+    if dst.dtype != np.uint8 or not dst.flags["C_CONTIGUOUS"]:
+        return -1, None
+    h, w, hh = C.c_int(0), C.c_int(0), C.c_uint64(0)
     buf = np.frombuffer(data, dtype=np.uint8)
-    base = dst.ctypes.data
-    rc = lib.lf_jpeg_read_file(buf.ctypes.data, buf.size, base + QTAB_BYTES, (dst.size - QTAB_BYTES) // 2, base,
-                               C.byref(h), C.byref(w))
-    return (h.value, w.value) if rc == 0 else None
+    fn = lib.lf_jpeg_scan_prepare_ragged if ragged else lib.lf_jpeg_scan_prepare
+    rc = int(fn(buf.ctypes.data, buf.size, dst.ctypes.data, dst.size, C.byref(h), C.byref(w), C.byref(hh)))
+    if rc != 0:
+        return rc, None
+    aux = int((lib.lf_jpeg_scan_aux_offset_ragged if ragged else lib.lf_jpeg_scan_aux_offset)(h.value, w.value))
+    data_off, data_len = (int(v) for v in dst[aux + 24:aux + 32].view(np.uint32))
+    return 0, (h.value, w.value, hh.value, aux + data_off + data_len + 16)
 
 
 def scan_prepare_into(data: bytes, dst: np.ndarray):
@@ -83,34 +117,51 @@ def scan_prepare_into(data: bytes, dst: np.ndarray):
     (uint8 view of a slab slot; layout in csrc/lf_jpeg_host.cpp).  Returns (h, w, hash of the file's Huffman tables,
     first byte of the slot behind what was written), or None when the file is to be decoded on the host
     (read_file_into, then libjpeg) or does not fit."""
-    lib = load()
-    if dst.dtype != np.uint8 or not dst.flags["C_CONTIGUOUS"]:
-        return None
-    h, w, hh = C.c_int(0), C.c_int(0), C.c_uint64(0)
-    buf = np.frombuffer(data, dtype=np.uint8)
-    rc = lib.lf_jpeg_scan_prepare(buf.ctypes.data, buf.size, dst.ctypes.data, dst.size, C.byref(h), C.byref(w), C.byref(hh))
-    if rc != 0:
-        return None
-    aux = int(lib.lf_jpeg_scan_aux_offset(h.value, w.value))
-    data_off, data_len = (int(v) for v in dst[aux + 24:aux + 32].view(np.uint32))
-    return h.value, w.value, hh.value, aux + data_off + data_len + 16
+    return _scan_prepare_code(data, dst, False)[1]
+
+
+def scan_prepare_ragged_into(data: bytes, dst: np.ndarray):
+    """scan_prepare_into for any height and any width from 5 up (ops.jpeg_huffman_items_u8 decodes such slots, of
+    different sizes, in one launch); the aux block lies at scan_aux_offset_ragged(h, w)."""
+    return _scan_prepare_code(data, dst, True)[1]
+
+
+def verdicts(data: bytes, room: int = 1 << 22):
+    """The four return codes (read_file, read_file_ragged, scan_prepare, scan_prepare_ragged) for one file with `room`
+    bytes of slot: 0 taken, 1 not covered / handed back, -1 corrupt — what the tests compare the twins on."""
+    slot = np.zeros(room, dtype=np.uint8)
+    return (_read_file_code(data, slot, False)[0], _read_file_code(data, slot, True)[0],
+            _scan_prepare_code(data, slot, False)[0], _scan_prepare_code(data, slot, True)[0])
 
 
 def scan_aux_offset(h: int, w: int) -> int:
     return int(load().lf_jpeg_scan_aux_offset(int(h), int(w)))
 
 
-def read_file(data: bytes):
-    """(coef int16 [MCUs, 6, 64], qtab uint16 [2, 64], h, w) or None — convenience form of read_file_into."""
+def scan_aux_offset_ragged(h: int, w: int) -> int:
+    return int(load().lf_jpeg_scan_aux_offset_ragged(int(h), int(w)))
+
+
+def _read_file(data: bytes, ragged: bool):
     slot = np.zeros(QTAB_BYTES + 3 * 4096 * 4096 // 16, dtype=np.uint8) if len(data) > (1 << 22) else \
         np.zeros(QTAB_BYTES + 3 * 1024 * 1024, dtype=np.uint8)
-    hw = read_file_into(data, slot)
+    hw = (read_file_ragged_into if ragged else read_file_into)(data, slot)
     if hw is None:
         return None
     h, w = hw
-    n = (h // 16) * (w // 16)
+    n = -(-h // 16) * -(-w // 16)
     coef = slot[QTAB_BYTES:QTAB_BYTES + n * 768].view(np.int16).reshape(n, 6, 64).copy()
     return coef, slot[:QTAB_BYTES].view(np.uint16).reshape(2, 64).copy(), h, w
+
+
+def read_file(data: bytes):
+    """(coef int16 [MCUs, 6, 64], qtab uint16 [2, 64], h, w) or None — convenience form of read_file_into."""
+    return _read_file(data, False)
+
+
+def read_file_ragged(data: bytes):
+    """read_file for any height and any width from 5 up: MCUs = ceil(h/16) * ceil(w/16)."""
+    return _read_file(data, True)
 
 
 def wrap_scan(scan: np.ndarray, h: int, w: int, quality: int = 95) -> bytes:
