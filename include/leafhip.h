@@ -403,6 +403,37 @@ int lf_resample_tile_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, in
                         const int32_t* xbounds, const int32_t* xk, int kx, const int32_t* ybounds,
                         const int32_t* yk, int ky, int per_image_coeffs, lf_stream_t stream);
 
+/* Image.resize((S, S), LANCZOS) for images of DIFFERENT sizes in one launch: what the reference's loader does one
+ * file after the other (`resize_image`, srcs/utils/image_utils.py:109-114, called from srcs/dataio/sequence.py:74-125
+ * and the predictor), for a chunk of an augmented tree whose rotate(expand=True) canvases each have a size of their
+ * own.  The fused kernel of lf_resample_tile_u8 with the geometry taken per image; bit-identical to lf_resample_u8.
+ * lf_resample_item, one per image (the same array on the device for the kernel and on the host for the checks before
+ *   the launch): in_off = where its tightly packed [h][w][3] pixels start in `in` (any byte: what
+ *   lf_jpeg_idct_rgb_items_u8 writes), out_index = the row of `out` [n_out][oh][ow][3] it is written to, tile_start =
+ *   the running sum of ceil(oh/32) * ceil(ow/32) over the items before it, xtab / ytab = where its axis tables start
+ *   in `tables` (int32 elements), kx / ky = their taps per output.
+ * An axis table is [o][2] bounds (start, count) followed by [o][k] coefficients, o = ow (xtab) or oh (ytab), as
+ *   lf_resample_u8 takes them; images of one length share one table.  An identity table (count 1, weight 1 << 22)
+ *   stands for an axis Pillow skips; both axes identity is an exact copy.
+ * Limits: kx, ky <= 16, ow % 4 == 0, out 4-byte aligned, and the windows of any 32 consecutive outputs span at most
+ *   96 inputs with starts that do not decrease; the host checks the last on its tables (ops.ResampleTables).
+ *   Windows are clamped against the image on the device.  No allocation, no synchronisation.
+ * lf_resample_items_fits (HOST): 1 if a h x w image is taken for an oh x ow output — both sides at most 2.5 x the
+ *   output's (conservative: a few longer axes would fit the window rule too), ow % 4 == 0. */
+typedef struct {
+    int64_t in_off;        /* bytes: where the image's [h][w][3] pixels start in `in` (any byte) */
+    int64_t tile_start;    /* running sum of ceil(oh/32)*ceil(ow/32) over the items before it */
+    int32_t h, w;
+    int32_t out_index;     /* row of `out` this image is written to */
+    int32_t xtab, ytab;    /* int32 offsets of the axis tables in `tables` */
+    int32_t kx, ky;        /* taps per output of each table */
+    int32_t reserved;
+} lf_resample_item;
+int lf_resample_items_fits(int h, int w, int oh, int ow);
+int lf_resample_items_u8(const uint8_t* in, size_t in_bytes, uint8_t* out, int n_out, int oh, int ow,
+                         const lf_resample_item* items, const lf_resample_item* host_items, int n,
+                         const int32_t* tables, size_t table_elems, lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* A2 — leaf_cnn conv stack (fp32, NCHW activations)                           */
 /* ------------------------------------------------------------------------- */

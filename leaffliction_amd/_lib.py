@@ -79,6 +79,8 @@ SIGNATURES = {
     "lf_resample_tile_u8": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, c_int, P],
     "lf_resample_u8": [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int,
                        c_int, P],
+    "lf_resample_items_fits": [c_int, c_int, c_int, c_int],
+    "lf_resample_items_u8": [P, c_size_t, P, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P],
     "lf_conv2d_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P],
     "lf_conv2d_bf16_weight_elems": [c_int, c_int, c_int],
     "lf_conv2d_bf16_prep_weights": [P, P, c_int, c_int, c_int, P],
@@ -155,6 +157,13 @@ _RESTYPES = {"lf_last_error": C.c_char_p, "lf_conv2d_wgrad_workspace": c_size_t,
              "lf_conv2d_bf16_act_mean_workspace": c_size_t,
              "lf_conv2d_bf16_stats_tiles": C.c_longlong, "lf_conv2d_wgrad_bf16_workspace": c_size_t,
              "lf_jpeg_file_bound": c_size_t, "lf_jpeg_scan_aux_offset": c_size_t, "lf_jpeg_scan_aux_offset_ragged": c_size_t, "lf_jpeg_decode_items_workspace": c_size_t, "lf_jpeg_entropy_workspace": c_size_t, "lf_jpeg_wrap_scan": C.c_long, "lf_jpeg_fdct_groups": C.c_long, "lf_jpeg_decode_workspace": c_size_t, "lf_jpeg_write_file": C.c_long, "lf_jpeg_quant_tables": None}
+
+
+class ResampleItem(C.Structure):
+    """lf_resample_item (include/leafhip.h)."""
+    _fields_ = [("in_off", C.c_int64), ("tile_start", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("out_index", C.c_int32), ("xtab", C.c_int32), ("ytab", C.c_int32), ("kx", C.c_int32),
+                ("ky", C.c_int32), ("reserved", C.c_int32)]
 
 
 class LeafHipError(RuntimeError):

@@ -703,6 +703,172 @@ __global__ __launch_bounds__(kBlock) void resample_tile_kernel(const uint8_t* __
     }
 }
 
+// resample_tile_kernel for images of DIFFERENT sizes in one launch (lf_resample_items_u8: the rotated canvases of an
+// augmented tree, every one a size of its own): the same 32x32 output tile per workgroup, window and 8-bit
+// intermediate in LDS, but height, width, place in the input buffer, output row and the two axis tables come from the
+// image's lf_resample_item.  A tile finds its image by bisection over the running tile count; ids follow the
+// XCD-aware order, so the tiles of one image are consecutive under one L2.  An image starts at ANY byte of `in`:
+// the buffer resource starts at the image's address aligned down and every window row carries its own shift.
+// Limits: 16 taps and a window of 96 inputs per 32 outputs on either axis (every length up to 2.5 x the output).
+// Tap loop: images with 6 taps and with 15 meet in one launch, so the count is per TILE — the largest count among
+// the tile's columns (rows), rounded up to 4, picks one of four unrolled instantiations of each pass (coefficients
+// in registers, as in resample_tile_kernel).  The choice is uniform over the workgroup; a 7-tap 256 -> 224 axis
+// runs 8 taps, not 16.  One kernel rather than a launch per tap count: the launch stays single for any mix.
+constexpr int kIWin = 96, kITapsMax = 16;
+constexpr int kIPitch = kIWin * 3 + 16;  // bytes per window row in LDS: 19 sixteen-byte pieces (a row starts up to 3 bytes in)
+constexpr int kIPieces = kIPitch / 16;
+
+// horizontal pass, LDS -> LDS: thread = one output column, every 8th window row
+template <int K>
+__device__ __forceinline__ void items_hpass(const uint8_t* wb, uint8_t* tb, const int (*kxs)[kRT], const int* xmn,
+                                            const int* rsh, int xlo, int cols, int wy, int tid) {
+    const int c = tid & (kRT - 1);
+    if (c >= cols) return;
+    int k[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) k[i] = kxs[i][c];
+    const int rel = clampi(xmn[c] - xlo, 0, kIWin - 1) * 3;
+    for (int r = tid / kRT; r < wy; r += kBlock / kRT) {
+        const uint8_t* q = wb + r * kIPitch + rsh[r] + rel;
+        int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {  // taps past the count have k = 0
+            s0 = mac24(s0, q[3 * i], k[i]);
+            s1 = mac24(s1, q[3 * i + 1], k[i]);
+            s2 = mac24(s2, q[3 * i + 2], k[i]);
+        }
+        uint8_t* o = tb + (r * kRT + c) * 3;
+        o[0] = clip8(s0);
+        o[1] = clip8(s1);
+        o[2] = clip8(s2);
+    }
+}
+
+// vertical pass, LDS -> global: thread = four consecutive bytes of one output row of the tile
+template <int K>
+__device__ __forceinline__ void items_vpass(const uint32_t* tmpw, uint8_t* dst, const int (*kys)[kRT], const int* ymn,
+                                            int ylo, int rows, int cols, int ow, int tid) {
+    const int rowd = cols * 3 / 4;  // cols % 4 == 0 (ow % 4 == 0)
+    for (int it = tid; it < rows * (kRT * 3 / 4); it += kBlock) {
+        const int oyl = it / (kRT * 3 / 4), dc = it - oyl * (kRT * 3 / 4);
+        if (dc >= rowd) continue;
+        const int rely = clampi(ymn[oyl] - ylo, 0, kIWin);  // rows past the window meet zero taps only
+        const uint32_t* col = tmpw + __mul24(rely, kRT * 3 / 4) + dc;
+        int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0, a3 = a0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const int kv = kys[i][oyl];
+            const unsigned v = col[i * (kRT * 3 / 4)];
+            a0 = mac24(a0, v & 0xff, kv);
+            a1 = mac24(a1, (v >> 8) & 0xff, kv);
+            a2 = mac24(a2, (v >> 16) & 0xff, kv);
+            a3 = mac24(a3, v >> 24, kv);
+        }
+        *reinterpret_cast<uint32_t*>(dst + (size_t)oyl * ow * 3 + 4 * dc) =
+            (unsigned)clip8(a0) | (unsigned)clip8(a1) << 8 | (unsigned)clip8(a2) << 16 | (unsigned)clip8(a3) << 24;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void resample_items_kernel(const uint8_t* __restrict__ in,
+                                                                uint8_t* __restrict__ out,
+                                                                const lf_resample_item* __restrict__ items,
+                                                                int n_items, unsigned total_tiles, int oh, int ow,
+                                                                const int32_t* __restrict__ tables) {
+    __shared__ __attribute__((aligned(16))) uint32_t win[(kIWin * kIPitch + 48) / 4];
+    __shared__ uint32_t tmpw[(kIWin + kITapsMax) * kRT * 3 / 4];  // + rows that only zero taps reach
+    __shared__ int kxs[kITapsMax][kRT], kys[kITapsMax][kRT];      // [tap][column / row of the tile]
+    __shared__ int xmn[kRT], xct[kRT], ymn[kRT], yct[kRT], rsh[kIWin], ktile[2];
+    // the XCD-aware order of lf::xcd_tile over the running tile count
+    const unsigned per_xcd = (total_tiles + 7) / 8, b = blockIdx.x;
+    const unsigned id = (b & 7u) * per_xcd + (b >> 3);
+    if (id >= total_tiles) return;
+    int lo = 0, hi = n_items - 1;
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if (items[m].tile_start <= (int64_t)id)
+            lo = m;
+        else
+            hi = m - 1;
+    }
+    const lf_resample_item it = items[lo];
+    const int h = it.h, w = it.w;
+    const int tiles_x = (ow + kRT - 1) / kRT;
+    const int t = (int)(id - (unsigned)it.tile_start);
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const int ox0 = tx * kRT, oy0 = ty * kRT;
+    const int cols = min(kRT, ow - ox0), rows = min(kRT, oh - oy0);
+    const int tid = threadIdx.x;
+    if (rows <= 0) return;  // (a tile_start that is not the running sum: the host refuses it)
+    if (tid < 2 * kRT) {  // tables of this tile's columns (lanes 0..31) and rows (32..63): the whole of wave 0
+        const bool isx = tid < kRT;
+        const int l = tid & (kRT - 1);
+        const int cnt_axis = isx ? cols : rows, o = (isx ? ox0 : oy0) + l;
+        const int len = isx ? w : h, ks = isx ? it.kx : it.ky, on = isx ? ow : oh;
+        const int32_t* bnd = tables + (isx ? it.xtab : it.ytab);
+        const int32_t* kk = bnd + 2 * on;
+        int mn = 0, ct = 0;
+        if (l < cnt_axis) {
+            // clamp the host-provided window so a bad table can never read out of bounds
+            mn = clampi(bnd[2 * o], 0, len);
+            ct = max(0, min(min(bnd[2 * o + 1], ks), min(len - mn, kITapsMax)));
+        }
+#pragma unroll
+        for (int i = 0; i < kITapsMax; ++i) {
+            const int v = i < ct ? kk[(size_t)o * ks + i] : 0;
+            if (isx) kxs[i][l] = v; else kys[i][l] = v;
+        }
+        if (isx) { xmn[l] = mn; xct[l] = ct; } else { ymn[l] = mn; yct[l] = ct; }
+        int mx = ct;  // the tile's tap count per axis: the largest of each half of the wave
+#pragma unroll
+        for (int s = 1; s < kRT; s <<= 1) mx = max(mx, __shfl_xor(mx, s));
+        if (l == 0) ktile[isx ? 0 : 1] = mx;
+    }
+    __syncthreads();
+    // windows start at the first column / row's start (the starts grow with the output index)
+    const int xlo = xmn[0], ylo = ymn[0];
+    const int wy = min(kIWin, min(h, ymn[rows - 1] + yct[rows - 1]) - ylo);
+    const int wx = clampi(min(w, xmn[cols - 1] + xct[cols - 1]) - xlo, 0, kIWin);
+    const size_t img_bytes = (size_t)h * w * 3;
+    const uint8_t* img = in + it.in_off;
+    const unsigned mis = (unsigned)(reinterpret_cast<size_t>(img) & 3);
+    // resource over this image, base aligned down: dwords that stick out read as zero
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(img - mis), 0, (int)((img_bytes + mis + 3) & ~(size_t)3), 0x00020000);
+    {   // a window row (<= 3 + 288 bytes from its aligned start) in sixteen-byte pieces, as many as the tile's
+        // window is wide: lane = piece, eight rows per pass
+        const int pieces = min(kIPieces, (3 + wx * 3 + 15) / 16);
+        const int d = tid & 31;
+        if (d < pieces) {
+            for (int r = tid >> 5; r < wy; r += kBlock / 32) {
+                const unsigned off = ((unsigned)(ylo + r) * (unsigned)w + (unsigned)xlo) * 3u + mis;
+                const lf::u32x4 v = __builtin_bit_cast(
+                    lf::u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (off & ~3u) + 16u * d, 0, 0));
+                *reinterpret_cast<lf::u32x4*>(&win[(r * kIPitch) / 4 + 4 * d]) = v;
+                if (d == 0) rsh[r] = (int)(off & 3u);
+            }
+        }
+    }
+    __syncthreads();
+    const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
+    uint8_t* tb = reinterpret_cast<uint8_t*>(tmpw);
+    switch ((ktile[0] + 3) >> 2) {
+        case 0:
+        case 1: items_hpass<4>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
+        case 2: items_hpass<8>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
+        case 3: items_hpass<12>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
+        default: items_hpass<16>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
+    }
+    __syncthreads();
+    uint8_t* dst = out + (((size_t)it.out_index * oh + oy0) * ow + ox0) * 3;
+    switch ((ktile[1] + 3) >> 2) {
+        case 0:
+        case 1: items_vpass<4>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
+        case 2: items_vpass<8>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
+        case 3: items_vpass<12>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
+        default: items_vpass<16>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -772,6 +938,46 @@ int lf_resample_tile_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, in
         resample_tile_kernel<10><<<grid, kBlock, 0, lf::as_stream(stream)>>>(
             in, out, h, w, oh, ow, xbounds, xk, kx, ybounds, yk, ky, per_image_coeffs, n);
     return lf::check_launch("lf_resample_tile");
+}
+
+int lf_resample_items_fits(int h, int w, int oh, int ow) {
+    // every length up to 2.5 x the output stays within 16 taps and 96 inputs per 32 outputs (at most 15 and 93 for
+    // outputs of 48 and 224); a few longer ones would too, but the rule stays this simple
+    if (h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ow % 4) return 0;
+    return 2 * (long long)h <= 5 * (long long)oh && 2 * (long long)w <= 5 * (long long)ow;
+}
+
+int lf_resample_items_u8(const uint8_t* in, size_t in_bytes, uint8_t* out, int n_out, int oh, int ow,
+                         const lf_resample_item* items, const lf_resample_item* host_items, int n,
+                         const int32_t* tables, size_t table_elems, lf_stream_t stream) {
+    LF_REQUIRE(in && out && items && host_items && tables, "lf_resample_items: null buffer");
+    LF_REQUIRE(n > 0 && n_out > 0 && oh > 0 && ow > 0, "lf_resample_items: bad dims n=%d n_out=%d oh=%d ow=%d", n,
+               n_out, oh, ow);
+    LF_REQUIRE(ow % 4 == 0 && (reinterpret_cast<size_t>(out) & 3) == 0,
+               "lf_resample_items: ow must be a multiple of 4 and out 4-byte aligned");
+    LF_REQUIRE(in != out, "lf_resample_items: in-place resample is not supported");
+    const int64_t per_image = (int64_t)((ow + kRT - 1) / kRT) * ((oh + kRT - 1) / kRT);
+    LF_REQUIRE(per_image * n < ((int64_t)1 << 31) - 8, "lf_resample_items: too many tiles");
+    int64_t tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const lf_resample_item& it = host_items[i];
+        LF_REQUIRE(it.h > 0 && it.w > 0 && (size_t)it.h * it.w * 3 + 6 < ((size_t)1 << 31),
+                   "lf_resample_items: size %dx%d of image %d", it.h, it.w, i);
+        LF_REQUIRE(it.in_off >= 0 && (size_t)it.in_off + (size_t)3 * it.h * it.w <= in_bytes,
+                   "lf_resample_items: the pixels of image %d do not lie in the buffer", i);
+        LF_REQUIRE(it.out_index >= 0 && it.out_index < n_out, "lf_resample_items: out_index %d of image %d (0..%d)",
+                   it.out_index, i, n_out - 1);
+        LF_REQUIRE(it.kx > 0 && it.kx <= kITapsMax && it.ky > 0 && it.ky <= kITapsMax,
+                   "lf_resample_items: kx=%d ky=%d of image %d (1..%d)", it.kx, it.ky, i, kITapsMax);
+        LF_REQUIRE(it.xtab >= 0 && (size_t)it.xtab + (size_t)ow * (2 + it.kx) <= table_elems && it.ytab >= 0 &&
+                       (size_t)it.ytab + (size_t)oh * (2 + it.ky) <= table_elems,
+                   "lf_resample_items: the tables of image %d do not lie in the pool", i);
+        LF_REQUIRE(it.tile_start == tiles, "lf_resample_items: tile_start of image %d is not the running sum", i);
+        tiles += per_image;
+    }
+    resample_items_kernel<<<lf::xcd_grid((size_t)tiles), kBlock, 0, lf::as_stream(stream)>>>(
+        in, out, items, n, (unsigned)tiles, oh, ow, tables);
+    return lf::check_launch("lf_resample_items");
 }
 
 int lf_resample_u8(const uint8_t* in, uint8_t* tmp, uint8_t* out, int n, int h, int w, int oh,

@@ -11,8 +11,10 @@ whole by Pillow in the worker.  A chunk crosses PCIe as one copy (its used parts
 scan), and the GPU does dequantisation / IDCT / fancy upsampling / colour conversion and the Pillow-exact LANCZOS
 resize, chunk after chunk with the next two chunks' files already being read.  A chunk of one whole-MCU size goes
 through the one-size calls (`ops.jpeg_idct_rgb_u8`); any other chunk — the augmented tree: every `rotate(expand=True)`
-output has a size of its own, hardly ever whole MCUs — through the `_items_` calls, one Huffman, one IDCT and one
-upsampling launch for all its sizes; only the resize is still one launch per distinct size.  The pixels are Pillow's
+output has a size of its own, hardly ever whole MCUs — through the `_items_` calls, one Huffman, one IDCT, one
+upsampling and one LANCZOS launch for all its sizes (`ops.resize_lanczos_items_u8` reads the pixel buffer where the
+upsampling left it and writes the batch's rows; the Pillow-decoded slots of such a chunk are a second call over the
+staging buffer).  The pixels are Pillow's
 bit for bit (tests/test_jpeg_codec.py, tests/test_jpeg_ragged.py), so everything downstream sees what the reference's
 loop would have produced.  `counts` says how the files were decoded.
 """
@@ -140,11 +142,15 @@ class DeviceDecoder:
         errors: List[Tuple[int, str]] = []
         counts = self.counts
         # JPEG slots ("scan" / "coef") of one whole-MCU size: the one-size calls, as ever.  Anything else — several
-        # sizes, or a size that is not whole MCUs — is decoded where it lies, all sizes in one launch per step, and only
-        # grouped by size for the resize.
+        # sizes, or a size that is not whole MCUs — is decoded where it lies and resized from where it lies, all sizes
+        # in one launch per step; so are the Pillow-decoded slots ("ok") of such a chunk, or of several sizes.
         jpeg = [k for k, d in enumerate(decoded) if d[0] in ("scan", "coef")]
         kinds = {(decoded[k][0],) + tuple(decoded[k][1][:2]) for k in jpeg}
         mixed = len(kinds) > 1 or any(hh % 16 or ww % 16 for _st, hh, ww in kinds)
+        plain = [k for k, d in enumerate(decoded) if d[0] == "ok"]
+        if not mixed and len({tuple(decoded[k][1][:2]) for k in plain}) <= 1:
+            plain = []   # one size: the per-size route below
+        ragged = (jpeg if mixed else []) + plain   # positions the items calls fill
         for k, (status, payload, _prm) in enumerate(decoded):
             if status == "err":
                 errors.append((pos0 + k, payload))
@@ -154,27 +160,37 @@ class DeviceDecoder:
                 groups.setdefault(("big",) + tuple(payload.shape[:2]), []).append(k)
                 counts["pickled"] += 1
             else:
-                groups.setdefault(("jpeg" if mixed and status in ("scan", "coef") else status,) + tuple(payload[:2]),
-                                  []).append(k)
+                if not ((mixed and status in ("scan", "coef")) or (plain and status == "ok")):
+                    groups.setdefault((status,) + tuple(payload[:2]), []).append(k)
                 counts[{"scan": "gpu_huffman", "coef": "host_huffman", "ok": "pillow"}[status]] += 1
         natives: Optional[Dict[int, np.ndarray]] = {} if keep_native else None
         x = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
         huffman: List[tuple] = []   # (positions in the chunk, device status of the GPU's Huffman decoding)
-        views: Dict[int, "torch.Tensor"] = {}
+        flat = dev_in.view(-1)
         if mixed:
-            flat = dev_in.view(-1)
             scans = [k for k in jpeg if decoded[k][0] == "scan"]
             if scans:
                 huffman.append((scans, ops.jpeg_huffman_items_u8(
                     flat, [(k * _slot, _slot) + tuple(decoded[k][1][:2]) for k in scans])))
-            _px, vs = ops.jpeg_idct_rgb_items_u8(flat, [(k * _slot, _slot) + tuple(decoded[k][1][:2]) for k in jpeg])
-            views = dict(zip(jpeg, vs))
+            dec = ops.JpegDecItems([(k * _slot, _slot) + tuple(decoded[k][1][:2]) for k in jpeg], dev)
+            px_buf, _views = ops.jpeg_idct_rgb_items_u8(flat, dec)
+            ops.resize_lanczos_items_u8(px_buf, [(o, hh, ww) for o, (hh, ww) in zip(dec.offsets, dec.sizes)], S,
+                                        out=x, out_index=jpeg)
+            if natives is not None:
+                host_buf = px_buf.cpu().numpy()
+                for k, o, (hh, ww) in zip(jpeg, dec.offsets, dec.sizes):
+                    natives[pos0 + k] = host_buf[o:o + 3 * hh * ww].reshape(hh, ww, 3)
+        if plain:   # Pillow's pixels lie at the front of their slots
+            ops.resize_lanczos_items_u8(flat, [(k * _slot,) + tuple(decoded[k][1][:2]) for k in plain], S,
+                                        out=x, out_index=plain)
+            if natives is not None:
+                for k in plain:
+                    hh, ww = decoded[k][1][:2]
+                    natives[pos0 + k] = host[k, :3 * hh * ww].reshape(hh, ww, 3).numpy().copy()
         for (status, h, w), ks in groups.items():
             whole = len(ks) == n   # one group holds the whole chunk (the usual case): no gather, no scatter
             idx = None if whole else index(ks)
-            if status == "jpeg":
-                px = views[ks[0]].unsqueeze(0) if len(ks) == 1 else torch.stack([views[k] for k in ks])
-            elif status == "scan":
+            if status == "scan":
                 rows = dev_in if whole else dev_in[idx]
                 huffman.append((ks, ops.jpeg_huffman_u8(rows, h, w)))
                 px = ops.jpeg_idct_rgb_u8(rows, h, w)
@@ -193,7 +209,7 @@ class DeviceDecoder:
                 host_px = px.cpu().numpy()
                 for j, k in enumerate(ks):
                     natives[pos0 + k] = host_px[j]
-        kept = sorted(k for ks in groups.values() for k in ks)
+        kept = sorted(ragged + [k for ks in groups.values() for k in ks])
         for ks, st in huffman:
             st = st.cpu().numpy()   # waits for the chunk's device half: only `chunks` asks for prepared scans
             for k in (k for k, v in zip(ks, st) if v):

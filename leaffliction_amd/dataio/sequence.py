@@ -101,6 +101,14 @@ class ManifestSequence:
         groups: Dict[Tuple[int, int], List[int]] = {}
         for k, a in enumerate(arrays):
             groups.setdefault(a.shape[:2], []).append(k)
+        if len([g for g in groups if g != (S, S)]) > 1:   # several sizes: packed, one upload, one launch
+            ks = [k for k, a in enumerate(arrays) if a.shape[:2] != (S, S)]
+            res = ops.resize_lanczos_arrays_u8([arrays[k] for k in ks], S).cpu().numpy()
+            for k, a in enumerate(arrays):
+                out[k] = a
+            for j, k in enumerate(ks):
+                out[k] = res[j]
+            return out  # type: ignore[return-value]
         for (h, w), ks in groups.items():
             if (h, w) == (S, S):
                 for k in ks:

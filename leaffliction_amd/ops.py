@@ -774,3 +774,176 @@ def crop_resize_lanczos_u8(x: torch.Tensor, boxes: Sequence[Sequence[int]]) -> t
         raise ValueError("crop_resize: one box per image")
     t = crop_resize_plan(w, h, boxes, x.device)
     return resample_u8(x, h, w, t[0], t[1], t[2], t[3], per_image=True, tile_ok=t[4])
+
+
+# ---- images of different sizes -> one [N, S, S, 3] batch in one launch (lf_resample_items_u8)
+ITEMS_OUT, ITEMS_WINDOW, ITEMS_TAPS = 32, 96, 16   # lf_resample_items_u8's tile, window and tap limits
+_ITEM_DTYPE = np.dtype(_lib.ResampleItem)
+
+
+def _axis_table(in_len: int, out_len: int):
+    """(bounds, coefficients cut to the largest count) of one axis; the identity table for an axis Pillow skips."""
+    if in_len == out_len:
+        return (np.stack([np.arange(out_len), np.ones(out_len)], 1).astype(np.int32),
+                np.full((out_len, 1), 1 << _geo.PRECISION_BITS, dtype=np.int32))
+    b, k, _ = _geo.lanczos_coeffs(in_len, 0.0, float(in_len), out_len)
+    return b, k[:, :max(1, int(b[:, 1].max()))]   # (ksize is Pillow's allocation, two or so more than any count)
+
+
+def axis_table_fits_items(b: np.ndarray, k: np.ndarray) -> bool:
+    """Host check of lf_resample_items_u8's preconditions on one axis table: at most 16 taps, and every run of 32
+    outputs reads at most 96 inputs from starts that do not decrease (resample_tables_fit_tile's rule, its limits)."""
+    if k.shape[1] > ITEMS_TAPS:
+        return False
+    b = b.astype(np.int64)
+    for o0 in range(0, b.shape[0], ITEMS_OUT):
+        o1 = min(o0 + ITEMS_OUT, b.shape[0])
+        if int((b[o0:o1, 0] + b[o0:o1, 1]).max() - b[o0, 0]) > ITEMS_WINDOW or (np.diff(b[o0:o1, 0]) < 0).any():
+            return False
+    return True
+
+
+class ResampleTables:
+    """The axis tables of lf_resample_items_u8 on one device, one per (input length, output length): made once from
+    the cached geometry.lanczos_coeffs (3-7 ms of Python per new length), laid out [o][2] bounds + [o][k] coefficients
+    in one int32 pool and uploaded when new — the tail of the pool, or all of it when the device buffer had to grow.
+    `uploads` counts those copies, `fallbacks` the images resize_lanczos_items_u8 handed to the per-size kernels."""
+
+    def __init__(self, device=None) -> None:
+        self.device = device
+        self.index: dict = {}           # (in_len, out_len) -> (offset in the pool, taps) or None (does not fit)
+        self.host = np.zeros(1 << 16, dtype=np.int32)
+        self.used = 0                   # elements of `host` in use
+        self.dev: Optional[torch.Tensor] = None
+        self.on_device = 0              # elements of `dev` that are current
+        self.uploads = 0
+        self.fallbacks = 0
+
+    def entry(self, in_len: int, out_len: int):
+        """(offset, taps) of the axis table in the pool, or None when the axis is outside the kernel's limits."""
+        key = (int(in_len), int(out_len))
+        if key not in self.index:
+            b, k = _axis_table(*key)
+            if not axis_table_fits_items(b, k):
+                self.index[key] = None
+            else:
+                flat = np.concatenate([b.ravel(), k.ravel()])
+                if self.used + flat.size > self.host.size:
+                    grown = np.zeros(max(2 * self.host.size, self.used + flat.size), dtype=np.int32)
+                    grown[:self.used] = self.host[:self.used]
+                    self.host = grown
+                self.host[self.used:self.used + flat.size] = flat
+                self.index[key] = (self.used, int(k.shape[1]))
+                self.used += flat.size
+        return self.index[key]
+
+    def sync(self) -> torch.Tensor:
+        """The pool on the device, with every table made so far."""
+        if self.dev is None or self.dev.numel() < self.used:
+            self.dev = torch.empty(self.host.size, dtype=_I32, device=self.device)
+            self.on_device = 0
+        if self.on_device < self.used:
+            self.dev[self.on_device:self.used].copy_(torch.from_numpy(self.host[self.on_device:self.used]))
+            self.on_device = self.used
+            self.uploads += 1
+        return self.dev
+
+
+_RESAMPLE_TABLES: dict = {}
+
+
+def resample_tables(device) -> ResampleTables:
+    """The device's table pool."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device not in _RESAMPLE_TABLES:
+        _RESAMPLE_TABLES[device] = ResampleTables(device)
+    return _RESAMPLE_TABLES[device]
+
+
+def resample_items_fits(h: int, w: int, oh: int, ow: int) -> bool:
+    return bool(_lib.load().lf_resample_items_fits(int(h), int(w), int(oh), int(ow)))
+
+
+def resample_items_plan(items: Sequence[Sequence[int]], size: int, tables: ResampleTables,
+                        out_index: Optional[Sequence[int]] = None):
+    """Host half of resize_lanczos_items_u8: (lf_resample_item array of the images the fused kernel takes,
+    [(position in `items`, output row)] of the others — a side over 2.5 x size, tables outside the kernel's limits,
+    size % 4 != 0)."""
+    S = int(size)
+    per_image = (-(-S // ITEMS_OUT)) ** 2
+    desc = np.zeros(len(items), dtype=_ITEM_DTYPE)
+    rest: List[Tuple[int, int]] = []
+    m = 0
+    for i, (off, h, w) in enumerate(items):
+        off, h, w = int(off), int(h), int(w)
+        row = i if out_index is None else int(out_index[i])
+        if h <= 0 or w <= 0 or off < 0:
+            raise ValueError(f"resize_lanczos_items: image {i} ({h}x{w} at byte {off})")
+        tx = ty = None
+        if resample_items_fits(h, w, S, S):
+            tx, ty = tables.entry(w, S), tables.entry(h, S)
+        if tx is None or ty is None:
+            rest.append((i, row))
+            continue
+        desc[m] = (off, m * per_image, h, w, row, tx[0], ty[0], tx[1], ty[1], 0)
+        m += 1
+    return desc[:m], rest
+
+
+def resize_lanczos_items_u8(buf: torch.Tensor, items: Sequence[Sequence[int]], size: int,
+                            out: Optional[torch.Tensor] = None,
+                            out_index: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Image.resize((size, size), LANCZOS) of images of DIFFERENT sizes in one launch: `buf` is a flat uint8 device
+    buffer, `items` a list of (byte offset, h, w) of tightly packed [h][w][3] images in it (any byte offset: what
+    jpeg_idct_rgb_items_u8 leaves).  Returns uint8 [N, size, size, 3], or fills rows `out_index` (default 0..N-1) of
+    the caller's `out` [*, size, size, 3] and touches no other row.  One descriptor upload and one launch; an image the
+    fused kernel does not take (see resample_items_plan) goes through resize_lanczos_u8 and counts in
+    `resample_tables(device).fallbacks`.  Pillow's pixels either way."""
+    _chk(buf, _U8, "resize_lanczos_items.buf", 1)
+    S, n = int(size), len(items)
+    if not buf.is_contiguous():
+        raise ValueError("resize_lanczos_items.buf: expected a flat contiguous uint8 buffer")
+    if out_index is not None and len(out_index) != n:
+        raise ValueError("resize_lanczos_items: one output row per image")
+    if out is None:
+        n_out = n if out_index is None else (max(int(r) for r in out_index) + 1 if n else 0)
+        out = torch.empty((n_out, S, S, 3), dtype=_U8, device=buf.device)
+    else:
+        _chk(out, _U8, "resize_lanczos_items.out", 4)
+        if tuple(out.shape[1:]) != (S, S, 3) or not out.is_contiguous() or out.device != buf.device:
+            raise ValueError(f"resize_lanczos_items.out: expected a contiguous [*, {S}, {S}, 3] tensor on buf's device")
+    for i, (off, h, w) in enumerate(items):
+        if int(off) + 3 * int(h) * int(w) > buf.numel():
+            raise ValueError(f"resize_lanczos_items: image {i} does not lie in the buffer")
+    if any(not 0 <= int(r) < out.shape[0] for r in (range(n) if out_index is None else out_index)):
+        raise ValueError("resize_lanczos_items: output row outside `out`")
+    tables = resample_tables(buf.device)
+    desc, rest = resample_items_plan(items, S, tables, out_index)
+    if len(desc):
+        pool = tables.sync()
+        dev_desc = torch.from_numpy(desc.view(np.uint8)).to(buf.device)
+        _lib.call("lf_resample_items_u8", buf.data_ptr(), buf.numel(), out.data_ptr(), out.shape[0], S, S,
+                  dev_desc.data_ptr(), desc.ctypes.data, len(desc), pool.data_ptr(), tables.used, _stream())
+    for i, row in rest:
+        off, h, w = (int(v) for v in items[i])
+        out[row] = resize_lanczos_u8(buf[off:off + 3 * h * w].view(1, h, w, 3), S)[0]
+    tables.fallbacks += len(rest)
+    return out
+
+
+def resize_lanczos_arrays_u8(arrays: Sequence[np.ndarray], size: int) -> torch.Tensor:
+    """Host images [h, w, 3] uint8 of any sizes -> uint8 device tensor [N, size, size, 3]: packed back to back,
+    uploaded once and resized in one resize_lanczos_items_u8 call."""
+    items, at = [], 0
+    for a in arrays:
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise ValueError("resize_lanczos_arrays: expected uint8 [h, w, 3] arrays")
+        items.append((at, a.shape[0], a.shape[1]))
+        at += a.size
+    packed = np.empty(at, dtype=np.uint8)
+    for a, (o, _h, _w) in zip(arrays, items):
+        packed[o:o + a.size] = a.reshape(-1)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return resize_lanczos_items_u8(torch.from_numpy(packed).to(dev), items, size)

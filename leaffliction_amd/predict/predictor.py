@@ -1,7 +1,7 @@
 """Predictor with the reference's interface (srcs/predict/predictor.py:16-147).
 
-`predict_batch` decodes every image on the host, resizes groups of equal native size with
-the Pillow-exact LANCZOS kernel on the GPU, and runs ONE batched forward (the reference
+`predict_batch` decodes every image on the host, resizes them with the Pillow-exact LANCZOS
+kernels on the GPU (images of several native sizes in one launch), and runs ONE batched forward (the reference
 stacks all images and calls `model.predict`).  The mask/transform subprocess of the
 reference's ImageProcessor is display-only and not part of the model input path
 (`enable_subprocess=False` at predictor.py:46,99), so it is not reproduced.
@@ -41,6 +41,8 @@ class Predictor:
         groups: Dict[tuple, List[int]] = {}
         for k, a in enumerate(arrays):
             groups.setdefault(a.shape[:2], []).append(k)
+        if len(groups) > 1:   # several sizes: packed, one upload, one launch
+            return ops.resize_lanczos_arrays_u8(arrays, S).cpu().numpy()
         for (h, w), ks in groups.items():
             batch = torch.from_numpy(np.stack([arrays[k] for k in ks])).cuda()
             res = ops.resize_lanczos_u8(batch, S).cpu().numpy()
