@@ -167,10 +167,14 @@ struct TileId {
     int tx, ty, n;
     bool ok;
 };
+// the tile this workgroup of an xcd_grid(total) launch acts as; ids >= total have no tile
+__device__ __forceinline__ unsigned xcd_tile_id(unsigned total) {
+    const unsigned per_xcd = (total + 7) / 8, b = blockIdx.x;
+    return (b & 7u) * per_xcd + (b >> 3);
+}
 __device__ __forceinline__ TileId xcd_tile(int tiles_x, int tiles_y, int n_images) {
     const unsigned per_image = (unsigned)(tiles_x * tiles_y), total = per_image * (unsigned)n_images;
-    const unsigned per_xcd = (total + 7) / 8, b = blockIdx.x;
-    const unsigned id = (b & 7u) * per_xcd + (b >> 3);
+    const unsigned id = xcd_tile_id(total);
     TileId t;
     t.ok = id < total;
     t.n = (int)(id / per_image);
@@ -194,6 +198,21 @@ __device__ __forceinline__ Block2 xcd_block2() {
     r.y = id / gx;
     r.x = id - r.y * gx;
     return r;
+}
+
+// Kernels that take images of different sizes in one launch number their units of work through all images: the
+// last of n items whose first unit, start_of(item), is not past g (the starts ascend from start_of(0) <= g).
+template <typename Start>
+__device__ __forceinline__ int last_item_not_past(int n, long long g, Start start_of) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int m = (lo + hi + 1) >> 1;
+        if ((long long)start_of(m) <= g)
+            lo = m;
+        else
+            hi = m - 1;
+    }
+    return lo;
 }
 
 // bf16 held as uint16_t: widen exactly, and round to nearest even

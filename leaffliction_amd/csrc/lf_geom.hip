@@ -433,6 +433,13 @@ __device__ __forceinline__ uint8_t clip8(int v) {
 // v_mad_i32_i24 / SDWA v_mul_i32_i24 (the byte extraction folds into the operand select).
 __device__ __forceinline__ int mac24(int acc, unsigned px, int k) { return acc + __mul24((int)px, k); }
 
+// four consecutive pixels (one Row12: pixel k channel b = byte 3k+b) x four taps into the three channel sums
+__device__ __forceinline__ void mac_row12(const Row12 q, int c0, int c1, int c2, int c3, int& s0, int& s1, int& s2) {
+    s0 = mac24(mac24(mac24(mac24(s0, q.a & 0xff, c0), q.a >> 24, c1), (q.b >> 16) & 0xff, c2), (q.c >> 8) & 0xff, c3);
+    s1 = mac24(mac24(mac24(mac24(s1, (q.a >> 8) & 0xff, c0), q.b & 0xff, c1), q.b >> 24, c2), (q.c >> 16) & 0xff, c3);
+    s2 = mac24(mac24(mac24(mac24(s2, (q.a >> 16) & 0xff, c0), (q.b >> 8) & 0xff, c1), q.c & 0xff, c2), q.c >> 24, c3);
+}
+
 // horizontal: in [n][h][w][3] -> tmp [n][h][ow][3]; one thread per (y, ox).  The taps are
 // fetched four pixels (12 bytes, one unaligned load) at a time.
 __global__ __launch_bounds__(kBlock) void resample_h_kernel(const uint8_t* __restrict__ in,
@@ -456,14 +463,7 @@ __global__ __launch_bounds__(kBlock) void resample_h_kernel(const uint8_t* __res
         int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
         int i = 0;
         for (; i + 4 <= cnt; i += 4) {
-            const Row12 q = *reinterpret_cast<const Row12*>(p + 3 * i);
-            const int c0 = k[i], c1 = k[i + 1], c2 = k[i + 2], c3 = k[i + 3];
-            s0 = mac24(mac24(mac24(mac24(s0, q.a & 0xff, c0), q.a >> 24, c1), (q.b >> 16) & 0xff, c2),
-                       (q.c >> 8) & 0xff, c3);
-            s1 = mac24(mac24(mac24(mac24(s1, (q.a >> 8) & 0xff, c0), q.b & 0xff, c1), q.b >> 24, c2),
-                       (q.c >> 16) & 0xff, c3);
-            s2 = mac24(mac24(mac24(mac24(s2, (q.a >> 16) & 0xff, c0), (q.b >> 8) & 0xff, c1), q.c & 0xff, c2),
-                       q.c >> 24, c3);
+            mac_row12(*reinterpret_cast<const Row12*>(p + 3 * i), k[i], k[i + 1], k[i + 2], k[i + 3], s0, s1, s2);
         }
         for (; i < cnt; ++i) {
             const int c = k[i];
@@ -513,16 +513,9 @@ __global__ __launch_bounds__(kBlock) void resample_h_strip_kernel(const uint8_t*
             if (vec) {
 #pragma unroll
                 for (int g = 0; g < kHMaxTaps / 4; ++g) {
-                    if (g < groups) {
-                        const Row12 q = *reinterpret_cast<const Row12*>(p + 12 * g);
-                        const int c0 = c[4 * g], c1 = c[4 * g + 1], c2 = c[4 * g + 2], c3 = c[4 * g + 3];
-                        s0 = mac24(mac24(mac24(mac24(s0, q.a & 0xff, c0), q.a >> 24, c1), (q.b >> 16) & 0xff, c2),
-                                   (q.c >> 8) & 0xff, c3);
-                        s1 = mac24(mac24(mac24(mac24(s1, (q.a >> 8) & 0xff, c0), q.b & 0xff, c1), q.b >> 24, c2),
-                                   (q.c >> 16) & 0xff, c3);
-                        s2 = mac24(mac24(mac24(mac24(s2, (q.a >> 16) & 0xff, c0), (q.b >> 8) & 0xff, c1),
-                                         q.c & 0xff, c2), q.c >> 24, c3);
-                    }
+                    if (g < groups)
+                        mac_row12(*reinterpret_cast<const Row12*>(p + 12 * g), c[4 * g], c[4 * g + 1], c[4 * g + 2],
+                                  c[4 * g + 3], s0, s1, s2);
                 }
             } else {
 #pragma unroll
@@ -586,150 +579,122 @@ __global__ __launch_bounds__(kBlock) void resample_v_kernel(const uint8_t* __res
 
 // Both passes in one kernel for resamples whose windows are short (crop -> LANCZOS back to the
 // original size, mild up/down scales): one workgroup = a 32x32 output tile.  The input window of
-// the tile (<= 48 rows x 48 pixels) is copied into LDS with aligned dword loads, the horizontal
-// pass runs LDS -> LDS (8-bit intermediate, as Pillow keeps it), the vertical pass LDS -> global.
+// the tile is copied into LDS with aligned loads, the horizontal pass runs LDS -> LDS (8-bit
+// intermediate, as Pillow keeps it), the vertical pass LDS -> global.
 // Against the two-kernel form this drops the HBM round trip of the intermediate image and the
 // unaligned 12-byte global loads that kept the texture addresser 84 % busy.
-constexpr int kRT = 32, kRWin = 48, kRTapsMax = 10;  // kRTaps: 8 (crop, up-scales) or 10 (256 -> 224)
-constexpr int kRPitch = kRWin * 3 + 8;  // bytes per window row in LDS (a row starts up to 3 bytes in)
+// The four stages below are the body of resample_tile_kernel (one size per batch) and of
+// resample_items_kernel (a size per image); a kernel finds its image and tile, declares the LDS
+// arrays at the sizes of its TileGeom and calls them.
+constexpr int kRT = 32;
 
-template <int kRTaps>
-__global__ __launch_bounds__(kBlock) void resample_tile_kernel(const uint8_t* __restrict__ in,
-                                                               uint8_t* __restrict__ out, int h, int w,
-                                                               int oh, int ow,
-                                                               const int32_t* __restrict__ xbounds,
-                                                               const int32_t* __restrict__ xkk, int kx,
-                                                               const int32_t* __restrict__ ybounds,
-                                                               const int32_t* __restrict__ ykk, int ky,
-                                                               int per_image, int n_images) {
-    __shared__ uint32_t win[(kRWin * kRPitch + 40) / 4];
-    __shared__ uint32_t tmpw[(kRWin + kRTaps) * kRT * 3 / 4];  // + rows that only zero taps reach
-    __shared__ int kxs[kRT][kRTaps], kys[kRT][kRTaps];
-    __shared__ int xmn[kRT], xct[kRT], ymn[kRT], yct[kRT], rsh[kRWin];
-    const lf::TileId tile = lf::xcd_tile((ow + kRT - 1) / kRT, (oh + kRT - 1) / kRT, n_images);
-    if (!tile.ok) return;
-    const unsigned n = (unsigned)tile.n;
-    const int ox0 = tile.tx * kRT, oy0 = tile.ty * kRT;
-    const int cols = min(kRT, ow - ox0), rows = min(kRT, oh - oy0);
-    const int tid = threadIdx.x;
-    if (tid < 2 * kRT) {  // tables of this tile's columns (threads 0..31) and rows (32..63)
-        const bool isx = tid < kRT;
-        const int l = tid & (kRT - 1);
-        const int cnt_axis = isx ? cols : rows, o = (isx ? ox0 : oy0) + l;
-        const int len = isx ? w : h, ks = isx ? kx : ky, on = isx ? ow : oh;
-        const int32_t* bnd = (isx ? xbounds : ybounds) + (per_image ? (size_t)n * on * 2 : 0);
-        const int32_t* kk = (isx ? xkk : ykk) + (per_image ? (size_t)n * on * ks : 0);
-        int mn = 0, ct = 0;
-        if (l < cnt_axis) {
-            mn = clampi(bnd[2 * o], 0, len);
-            ct = max(0, min(min(bnd[2 * o + 1], ks), min(len - mn, kRTaps)));
-        }
-#pragma unroll
-        for (int i = 0; i < kRTaps; ++i) {
-            const int v = i < ct ? kk[(size_t)o * ks + i] : 0;
-            if (isx) kxs[l][i] = v; else kys[l][i] = v;
-        }
-        if (isx) { xmn[l] = mn; xct[l] = ct; } else { ymn[l] = mn; yct[l] = ct; }
+// The limits of a tile kernel.  Compile-time, because they size its LDS and with it its occupancy.
+template <int WIN, int TAPS, int PIECE>
+struct TileGeom {
+    static constexpr int kWin = WIN;      // most inputs the kRT outputs of a tile read on either axis
+    static constexpr int kTaps = TAPS;    // most taps
+    static constexpr int kPiece = PIECE;  // bytes per load of the window copy: 8 or 16
+    static constexpr int kPitch = WIN * 3 + PIECE;  // bytes per window row in LDS (a row starts up to 3 bytes in)
+    static constexpr int kPieces = kPitch / PIECE;
+    static_assert(kPitch % PIECE == 0 && (PIECE == 8 || PIECE == 16), "window rows are whole pieces");
+};
+
+struct AxisTable {  // one axis of one image: [o][2] window (start, count), [o][ks] coefficients, input length
+    const int32_t* bnd;
+    const int32_t* kk;
+    int ks, len;
+};
+struct TileTables {  // a tile's tables in LDS
+    int (*kxs)[kRT], (*kys)[kRT];  // taps [tap][column / row of the tile]
+    int *xmn, *ymn;                // window start of every column / row
+    int* wend;                     // [2]: where the last column's / row's window ends
+    int* rsh;                      // byte shift of every window row
+};
+struct TileWindow {  // first input column and row of the tile's window, its rows
+    int xlo, ylo, wy;
+};
+
+// Stage 1: the tables of this tile's columns (lanes 0..31) and rows (32..63), the whole of wave 0.  Returns, in those
+// lanes, the largest tap count among the tile's columns (rows).
+template <class G>
+__device__ __forceinline__ int stage_tables(const AxisTable& xs, const AxisTable& ys, int ox0, int oy0, int cols,
+                                            int rows, const TileTables& t, int tid) {
+    if (tid >= 2 * kRT) return 0;
+    const bool isx = tid < kRT;
+    const int l = tid & (kRT - 1);
+    const int cnt_axis = isx ? cols : rows, o = (isx ? ox0 : oy0) + l;
+    const int len = isx ? xs.len : ys.len, ks = isx ? xs.ks : ys.ks;
+    const int32_t* bnd = isx ? xs.bnd : ys.bnd;
+    const int32_t* kk = isx ? xs.kk : ys.kk;
+    int mn = 0, ct = 0;
+    if (l < cnt_axis) {
+        // clamp the host-provided window so a bad table can never read out of bounds
+        mn = clampi(bnd[2 * o], 0, len);
+        ct = max(0, min(min(bnd[2 * o + 1], ks), min(len - mn, G::kTaps)));
     }
-    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < G::kTaps; ++i) {
+        const int v = i < ct ? kk[(size_t)o * ks + i] : 0;
+        if (isx) t.kxs[i][l] = v; else t.kys[i][l] = v;
+    }
+    if (isx) t.xmn[l] = mn; else t.ymn[l] = mn;
+    if (l == cnt_axis - 1) t.wend[isx ? 0 : 1] = mn + ct;
+    int mx = ct;  // the largest of each half of the wave
+#pragma unroll
+    for (int s = 1; s < kRT; s <<= 1) mx = max(mx, __shfl_xor(mx, s));
+    return mx;
+}
+
+// Stage 2: the tile's window of the image at `img` (ANY byte address) into LDS, the first `pieces` pieces of every row.
+template <class G>
+__device__ __forceinline__ TileWindow load_window(const uint8_t* img, int h, int w, const TileTables& t, int pieces,
+                                                  uint32_t* win, int tid) {
     // windows start at the first column / row's start (the starts grow with the output index)
-    const int xlo = xmn[0], ylo = ymn[0];
-    const int wy = min(kRWin, min(h, ymn[rows - 1] + yct[rows - 1]) - ylo);
+    TileWindow v;
+    v.xlo = t.xmn[0];
+    v.ylo = t.ymn[0];
+    v.wy = min(G::kWin, min(h, t.wend[1]) - v.ylo);
     const size_t img_bytes = (size_t)h * w * 3;
-    const uint8_t* img = in + (size_t)n * img_bytes;
     const unsigned mis = (unsigned)(reinterpret_cast<size_t>(img) & 3);
     // resource over this image, base aligned down: dwords that stick out read as zero
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint8_t*>(img - mis), 0, (int)((img_bytes + mis + 3) & ~(size_t)3), 0x00020000);
-    // a window row (<= 3 + 144 + 3 bytes from its aligned start) as 19 eight-byte pieces:
-    // three rows per wave
-    constexpr int kPieces = kRPitch / 8;
-    for (int it = tid; it < wy * kPieces; it += kBlock) {
-        const int r = it / kPieces, d = it - r * kPieces;
-        const unsigned off = ((unsigned)(ylo + r) * (unsigned)w + (unsigned)xlo) * 3u + mis;
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        const u32x2 v = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, (off & ~3u) + 8u * d, 0, 0));
-        win[(r * kRPitch) / 4 + 2 * d] = v.x;
-        win[(r * kRPitch) / 4 + 2 * d + 1] = v.y;
-        if (d == 0) rsh[r] = (int)(off & 3u);
-    }
-    __syncthreads();
-    const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
-    uint8_t* tb = reinterpret_cast<uint8_t*>(tmpw);
-    {   // horizontal pass: thread = one output column, every 8th window row
-        const int c = tid & (kRT - 1);
-        if (c < cols) {
-            int k[kRTaps];
-#pragma unroll
-            for (int i = 0; i < kRTaps; ++i) k[i] = kxs[c][i];
-            const int rel = min(xmn[c] - xlo, kRWin - 1) * 3;
-            for (int r = tid / kRT; r < wy; r += kBlock / kRT) {
-                const uint8_t* q = wb + r * kRPitch + rsh[r] + rel;
-                int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
-#pragma unroll
-                for (int i = 0; i < kRTaps; ++i) {  // taps past the count have k = 0
-                    s0 = mac24(s0, q[3 * i], k[i]);
-                    s1 = mac24(s1, q[3 * i + 1], k[i]);
-                    s2 = mac24(s2, q[3 * i + 2], k[i]);
-                }
-                uint8_t* o = tb + (r * kRT + c) * 3;
-                o[0] = clip8(s0);
-                o[1] = clip8(s1);
-                o[2] = clip8(s2);
-            }
+    // a window row (<= 3 + 3 kWin bytes from its aligned start) as kPieces pieces, dealt lane after lane over rows and
+    // pieces: both geometries have 19 pieces a row, so a wave covers 64 / 19 = 3.4 rows.  Lanes whose piece lies
+    // past `pieces` (a window narrower than kWin) sit the step out.
+    for (int it = tid; it < v.wy * G::kPieces; it += kBlock) {
+        const int r = it / G::kPieces, d = it - r * G::kPieces;
+        if (d >= pieces) continue;
+        const unsigned off = ((unsigned)(v.ylo + r) * (unsigned)w + (unsigned)v.xlo) * 3u + mis;
+        const unsigned at = (off & ~3u) + (unsigned)(G::kPiece * d);
+        uint32_t* dst = win + (r * G::kPitch + G::kPiece * d) / 4;
+        if constexpr (G::kPiece == 16) {
+            *reinterpret_cast<lf::u32x4*>(dst) =
+                __builtin_bit_cast(lf::u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, at, 0, 0));
+        } else {
+            const lf::u32x2 q = __builtin_bit_cast(lf::u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, at, 0, 0));
+            dst[0] = q.x;
+            dst[1] = q.y;
         }
+        if (d == 0) t.rsh[r] = (int)(off & 3u);
     }
-    __syncthreads();
-    // vertical pass: thread = four consecutive bytes of one output row of the tile
-    uint8_t* dst = out + (((size_t)n * oh + oy0) * ow + ox0) * 3;
-    const int rowd = cols * 3 / 4;  // cols % 4 == 0 (ow % 4 == 0)
-    for (int it = tid; it < rows * (kRT * 3 / 4); it += kBlock) {
-        const int oyl = it / (kRT * 3 / 4), dc = it - oyl * (kRT * 3 / 4);
-        if (dc >= rowd) continue;
-        const int rely = min(ymn[oyl] - ylo, kRWin);  // rows past the window meet zero taps only
-        const uint32_t* col = tmpw + __mul24(rely, kRT * 3 / 4) + dc;
-        int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0, a3 = a0;
-#pragma unroll
-        for (int i = 0; i < kRTaps; ++i) {
-            const int kv = kys[oyl][i];
-            const unsigned v = col[i * (kRT * 3 / 4)];
-            a0 = mac24(a0, v & 0xff, kv);
-            a1 = mac24(a1, (v >> 8) & 0xff, kv);
-            a2 = mac24(a2, (v >> 16) & 0xff, kv);
-            a3 = mac24(a3, v >> 24, kv);
-        }
-        *reinterpret_cast<uint32_t*>(dst + (size_t)oyl * ow * 3 + 4 * dc) =
-            (unsigned)clip8(a0) | (unsigned)clip8(a1) << 8 | (unsigned)clip8(a2) << 16 | (unsigned)clip8(a3) << 24;
-    }
+    return v;
 }
 
-// resample_tile_kernel for images of DIFFERENT sizes in one launch (lf_resample_items_u8: the rotated canvases of an
-// augmented tree, every one a size of its own): the same 32x32 output tile per workgroup, window and 8-bit
-// intermediate in LDS, but height, width, place in the input buffer, output row and the two axis tables come from the
-// image's lf_resample_item.  A tile finds its image by bisection over the running tile count; ids follow the
-// XCD-aware order, so the tiles of one image are consecutive under one L2.  An image starts at ANY byte of `in`:
-// the buffer resource starts at the image's address aligned down and every window row carries its own shift.
-// Limits: 16 taps and a window of 96 inputs per 32 outputs on either axis (every length up to 2.5 x the output).
-// Tap loop: images with 6 taps and with 15 meet in one launch, so the count is per TILE — the largest count among
-// the tile's columns (rows), rounded up to 4, picks one of four unrolled instantiations of each pass (coefficients
-// in registers, as in resample_tile_kernel).  The choice is uniform over the workgroup; a 7-tap 256 -> 224 axis
-// runs 8 taps, not 16.  One kernel rather than a launch per tap count: the launch stays single for any mix.
-constexpr int kIWin = 96, kITapsMax = 16;
-constexpr int kIPitch = kIWin * 3 + 16;  // bytes per window row in LDS: 19 sixteen-byte pieces (a row starts up to 3 bytes in)
-constexpr int kIPieces = kIPitch / 16;
-
-// horizontal pass, LDS -> LDS: thread = one output column, every 8th window row
-template <int K>
-__device__ __forceinline__ void items_hpass(const uint8_t* wb, uint8_t* tb, const int (*kxs)[kRT], const int* xmn,
-                                            const int* rsh, int xlo, int cols, int wy, int tid) {
+// Stage 3, horizontal pass, LDS -> LDS: thread = one output column, every 8th window row; K taps unrolled
+template <class G, int K>
+__device__ __forceinline__ void tile_hpass(const uint32_t* win, uint32_t* tmpw, const TileTables& t,
+                                           const TileWindow& v, int cols, int tid) {
+    const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
+    uint8_t* tb = reinterpret_cast<uint8_t*>(tmpw);
     const int c = tid & (kRT - 1);
     if (c >= cols) return;
     int k[K];
 #pragma unroll
-    for (int i = 0; i < K; ++i) k[i] = kxs[i][c];
-    const int rel = clampi(xmn[c] - xlo, 0, kIWin - 1) * 3;
-    for (int r = tid / kRT; r < wy; r += kBlock / kRT) {
-        const uint8_t* q = wb + r * kIPitch + rsh[r] + rel;
+    for (int i = 0; i < K; ++i) k[i] = t.kxs[i][c];
+    const int rel = clampi(t.xmn[c] - v.xlo, 0, G::kWin - 1) * 3;
+    for (int r = tid / kRT; r < v.wy; r += kBlock / kRT) {
+        const uint8_t* q = wb + r * G::kPitch + t.rsh[r] + rel;
         int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
 #pragma unroll
         for (int i = 0; i < K; ++i) {  // taps past the count have k = 0
@@ -744,128 +709,125 @@ __device__ __forceinline__ void items_hpass(const uint8_t* wb, uint8_t* tb, cons
     }
 }
 
-// vertical pass, LDS -> global: thread = four consecutive bytes of one output row of the tile
-template <int K>
-__device__ __forceinline__ void items_vpass(const uint32_t* tmpw, uint8_t* dst, const int (*kys)[kRT], const int* ymn,
-                                            int ylo, int rows, int cols, int ow, int tid) {
+// Stage 4, vertical pass, LDS -> global: thread = four consecutive bytes of one output row of the tile
+template <class G, int K>
+__device__ __forceinline__ void tile_vpass(const uint32_t* tmpw, uint8_t* dst, const TileTables& t,
+                                           const TileWindow& v, int rows, int cols, int ow, int tid) {
     const int rowd = cols * 3 / 4;  // cols % 4 == 0 (ow % 4 == 0)
     for (int it = tid; it < rows * (kRT * 3 / 4); it += kBlock) {
         const int oyl = it / (kRT * 3 / 4), dc = it - oyl * (kRT * 3 / 4);
         if (dc >= rowd) continue;
-        const int rely = clampi(ymn[oyl] - ylo, 0, kIWin);  // rows past the window meet zero taps only
+        const int rely = clampi(t.ymn[oyl] - v.ylo, 0, G::kWin);  // rows past the window meet zero taps only
         const uint32_t* col = tmpw + __mul24(rely, kRT * 3 / 4) + dc;
         int a0 = 1 << (kPrec - 1), a1 = a0, a2 = a0, a3 = a0;
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            const int kv = kys[i][oyl];
-            const unsigned v = col[i * (kRT * 3 / 4)];
-            a0 = mac24(a0, v & 0xff, kv);
-            a1 = mac24(a1, (v >> 8) & 0xff, kv);
-            a2 = mac24(a2, (v >> 16) & 0xff, kv);
-            a3 = mac24(a3, v >> 24, kv);
+            const int kv = t.kys[i][oyl];
+            const unsigned px = col[i * (kRT * 3 / 4)];
+            a0 = mac24(a0, px & 0xff, kv);
+            a1 = mac24(a1, (px >> 8) & 0xff, kv);
+            a2 = mac24(a2, (px >> 16) & 0xff, kv);
+            a3 = mac24(a3, px >> 24, kv);
         }
         *reinterpret_cast<uint32_t*>(dst + (size_t)oyl * ow * 3 + 4 * dc) =
             (unsigned)clip8(a0) | (unsigned)clip8(a1) << 8 | (unsigned)clip8(a2) << 16 | (unsigned)clip8(a3) << 24;
     }
 }
 
+// One size per batch: a window of 48 inputs per 32 outputs in 8-byte pieces, kRTaps = 8 (crop, up-scales) or 10
+// (256 -> 224) taps; the tables are the batch's or one set per image.
+constexpr int kRWin = 48, kRTapsMax = 10;
+
+template <int kRTaps>
+__global__ __launch_bounds__(kBlock) void resample_tile_kernel(const uint8_t* __restrict__ in,
+                                                               uint8_t* __restrict__ out, int h, int w,
+                                                               int oh, int ow,
+                                                               const int32_t* __restrict__ xbounds,
+                                                               const int32_t* __restrict__ xkk, int kx,
+                                                               const int32_t* __restrict__ ybounds,
+                                                               const int32_t* __restrict__ ykk, int ky,
+                                                               int per_image, int n_images) {
+    using G = TileGeom<kRWin, kRTaps, 8>;
+    __shared__ uint32_t win[(G::kWin * G::kPitch + 40) / 4];
+    __shared__ uint32_t tmpw[(G::kWin + kRTaps) * kRT * 3 / 4];  // + rows that only zero taps reach
+    __shared__ int kxs[kRTaps][kRT], kys[kRTaps][kRT];
+    __shared__ int xmn[kRT], ymn[kRT], wend[2], rsh[G::kWin];
+    const TileTables t = {kxs, kys, xmn, ymn, wend, rsh};
+    const lf::TileId tile = lf::xcd_tile((ow + kRT - 1) / kRT, (oh + kRT - 1) / kRT, n_images);
+    if (!tile.ok) return;
+    const size_t n = (size_t)tile.n, pn = per_image ? n : 0;
+    const int ox0 = tile.tx * kRT, oy0 = tile.ty * kRT;
+    const int cols = min(kRT, ow - ox0), rows = min(kRT, oh - oy0);
+    const int tid = threadIdx.x;
+    const AxisTable xs = {xbounds + pn * ow * 2, xkk + pn * ow * kx, kx, w};
+    const AxisTable ys = {ybounds + pn * oh * 2, ykk + pn * oh * ky, ky, h};
+    stage_tables<G>(xs, ys, ox0, oy0, cols, rows, t, tid);  // (the tap count it returns is unused: kRTaps is fixed)
+    __syncthreads();
+    const TileWindow v = load_window<G>(in + n * h * w * 3, h, w, t, G::kPieces, win, tid);
+    __syncthreads();
+    tile_hpass<G, kRTaps>(win, tmpw, t, v, cols, tid);
+    __syncthreads();
+    tile_vpass<G, kRTaps>(tmpw, out + ((n * oh + oy0) * ow + ox0) * 3, t, v, rows, cols, ow, tid);
+}
+
+// Images of DIFFERENT sizes in one launch (lf_resample_items_u8: the rotated canvases of an augmented tree, every one
+// a size of its own): height, width, place in the input buffer, output row and the two axis tables come from the
+// image's lf_resample_item.  A tile finds its image by bisection over the running tile count; ids follow the
+// XCD-aware order, so the tiles of one image are consecutive under one L2.
+// Limits: 16 taps and a window of 96 inputs per 32 outputs on either axis (every length up to 2.5 x the output), in
+// 16-byte pieces, as many per row as the tile's window is wide.
+// Tap loop: images with 6 taps and with 15 meet in one launch, so the count is per TILE — the largest count among
+// the tile's columns (rows), rounded up to 4, picks one of four unrolled instantiations of each pass (coefficients
+// in registers, as in resample_tile_kernel).  The choice is uniform over the workgroup; a 7-tap 256 -> 224 axis
+// runs 8 taps, not 16.  One kernel rather than a launch per tap count: the launch stays single for any mix.
+constexpr int kIWin = 96, kITapsMax = 16;
+
 __global__ __launch_bounds__(kBlock) void resample_items_kernel(const uint8_t* __restrict__ in,
                                                                 uint8_t* __restrict__ out,
                                                                 const lf_resample_item* __restrict__ items,
                                                                 int n_items, unsigned total_tiles, int oh, int ow,
                                                                 const int32_t* __restrict__ tables) {
-    __shared__ __attribute__((aligned(16))) uint32_t win[(kIWin * kIPitch + 48) / 4];
-    __shared__ uint32_t tmpw[(kIWin + kITapsMax) * kRT * 3 / 4];  // + rows that only zero taps reach
-    __shared__ int kxs[kITapsMax][kRT], kys[kITapsMax][kRT];      // [tap][column / row of the tile]
-    __shared__ int xmn[kRT], xct[kRT], ymn[kRT], yct[kRT], rsh[kIWin], ktile[2];
-    // the XCD-aware order of lf::xcd_tile over the running tile count
-    const unsigned per_xcd = (total_tiles + 7) / 8, b = blockIdx.x;
-    const unsigned id = (b & 7u) * per_xcd + (b >> 3);
+    using G = TileGeom<kIWin, kITapsMax, 16>;
+    __shared__ __attribute__((aligned(16))) uint32_t win[(G::kWin * G::kPitch + 48) / 4];
+    __shared__ uint32_t tmpw[(G::kWin + G::kTaps) * kRT * 3 / 4];  // + rows that only zero taps reach
+    __shared__ int kxs[G::kTaps][kRT], kys[G::kTaps][kRT];
+    __shared__ int xmn[kRT], ymn[kRT], wend[2], rsh[G::kWin], ktile[2];
+    const TileTables t = {kxs, kys, xmn, ymn, wend, rsh};
+    const unsigned id = lf::xcd_tile_id(total_tiles);
     if (id >= total_tiles) return;
-    int lo = 0, hi = n_items - 1;
-    while (lo < hi) {
-        const int m = (lo + hi + 1) >> 1;
-        if (items[m].tile_start <= (int64_t)id)
-            lo = m;
-        else
-            hi = m - 1;
-    }
-    const lf_resample_item it = items[lo];
+    const lf_resample_item it = items[lf::last_item_not_past(n_items, id, [&](int m) { return items[m].tile_start; })];
     const int h = it.h, w = it.w;
     const int tiles_x = (ow + kRT - 1) / kRT;
-    const int t = (int)(id - (unsigned)it.tile_start);
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const int tl = (int)(id - (unsigned)it.tile_start);
+    const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
     const int ox0 = tx * kRT, oy0 = ty * kRT;
     const int cols = min(kRT, ow - ox0), rows = min(kRT, oh - oy0);
     const int tid = threadIdx.x;
     if (rows <= 0) return;  // (a tile_start that is not the running sum: the host refuses it)
-    if (tid < 2 * kRT) {  // tables of this tile's columns (lanes 0..31) and rows (32..63): the whole of wave 0
-        const bool isx = tid < kRT;
-        const int l = tid & (kRT - 1);
-        const int cnt_axis = isx ? cols : rows, o = (isx ? ox0 : oy0) + l;
-        const int len = isx ? w : h, ks = isx ? it.kx : it.ky, on = isx ? ow : oh;
-        const int32_t* bnd = tables + (isx ? it.xtab : it.ytab);
-        const int32_t* kk = bnd + 2 * on;
-        int mn = 0, ct = 0;
-        if (l < cnt_axis) {
-            // clamp the host-provided window so a bad table can never read out of bounds
-            mn = clampi(bnd[2 * o], 0, len);
-            ct = max(0, min(min(bnd[2 * o + 1], ks), min(len - mn, kITapsMax)));
-        }
-#pragma unroll
-        for (int i = 0; i < kITapsMax; ++i) {
-            const int v = i < ct ? kk[(size_t)o * ks + i] : 0;
-            if (isx) kxs[i][l] = v; else kys[i][l] = v;
-        }
-        if (isx) { xmn[l] = mn; xct[l] = ct; } else { ymn[l] = mn; yct[l] = ct; }
-        int mx = ct;  // the tile's tap count per axis: the largest of each half of the wave
-#pragma unroll
-        for (int s = 1; s < kRT; s <<= 1) mx = max(mx, __shfl_xor(mx, s));
-        if (l == 0) ktile[isx ? 0 : 1] = mx;
-    }
+    const AxisTable xs = {tables + it.xtab, tables + it.xtab + 2 * ow, it.kx, w};
+    const AxisTable ys = {tables + it.ytab, tables + it.ytab + 2 * oh, it.ky, h};
+    const int taps = stage_tables<G>(xs, ys, ox0, oy0, cols, rows, t, tid);
+    if (tid < 2 * kRT && (tid & (kRT - 1)) == 0) ktile[tid / kRT] = taps;  // the tile's tap count per axis
     __syncthreads();
-    // windows start at the first column / row's start (the starts grow with the output index)
-    const int xlo = xmn[0], ylo = ymn[0];
-    const int wy = min(kIWin, min(h, ymn[rows - 1] + yct[rows - 1]) - ylo);
-    const int wx = clampi(min(w, xmn[cols - 1] + xct[cols - 1]) - xlo, 0, kIWin);
-    const size_t img_bytes = (size_t)h * w * 3;
-    const uint8_t* img = in + it.in_off;
-    const unsigned mis = (unsigned)(reinterpret_cast<size_t>(img) & 3);
-    // resource over this image, base aligned down: dwords that stick out read as zero
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(img - mis), 0, (int)((img_bytes + mis + 3) & ~(size_t)3), 0x00020000);
-    {   // a window row (<= 3 + 288 bytes from its aligned start) in sixteen-byte pieces, as many as the tile's
-        // window is wide: lane = piece, eight rows per pass
-        const int pieces = min(kIPieces, (3 + wx * 3 + 15) / 16);
-        const int d = tid & 31;
-        if (d < pieces) {
-            for (int r = tid >> 5; r < wy; r += kBlock / 32) {
-                const unsigned off = ((unsigned)(ylo + r) * (unsigned)w + (unsigned)xlo) * 3u + mis;
-                const lf::u32x4 v = __builtin_bit_cast(
-                    lf::u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (off & ~3u) + 16u * d, 0, 0));
-                *reinterpret_cast<lf::u32x4*>(&win[(r * kIPitch) / 4 + 4 * d]) = v;
-                if (d == 0) rsh[r] = (int)(off & 3u);
-            }
-        }
-    }
+    const int wx = clampi(min(w, wend[0]) - xmn[0], 0, G::kWin);
+    const TileWindow v =
+        load_window<G>(in + it.in_off, h, w, t, min(G::kPieces, (3 + wx * 3 + G::kPiece - 1) / G::kPiece), win, tid);
     __syncthreads();
-    const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
-    uint8_t* tb = reinterpret_cast<uint8_t*>(tmpw);
     switch ((ktile[0] + 3) >> 2) {
         case 0:
-        case 1: items_hpass<4>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
-        case 2: items_hpass<8>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
-        case 3: items_hpass<12>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
-        default: items_hpass<16>(wb, tb, kxs, xmn, rsh, xlo, cols, wy, tid); break;
+        case 1: tile_hpass<G, 4>(win, tmpw, t, v, cols, tid); break;
+        case 2: tile_hpass<G, 8>(win, tmpw, t, v, cols, tid); break;
+        case 3: tile_hpass<G, 12>(win, tmpw, t, v, cols, tid); break;
+        default: tile_hpass<G, 16>(win, tmpw, t, v, cols, tid); break;
     }
     __syncthreads();
     uint8_t* dst = out + (((size_t)it.out_index * oh + oy0) * ow + ox0) * 3;
     switch ((ktile[1] + 3) >> 2) {
         case 0:
-        case 1: items_vpass<4>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
-        case 2: items_vpass<8>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
-        case 3: items_vpass<12>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
-        default: items_vpass<16>(tmpw, dst, kys, ymn, ylo, rows, cols, ow, tid); break;
+        case 1: tile_vpass<G, 4>(tmpw, dst, t, v, rows, cols, ow, tid); break;
+        case 2: tile_vpass<G, 8>(tmpw, dst, t, v, rows, cols, ow, tid); break;
+        case 3: tile_vpass<G, 12>(tmpw, dst, t, v, rows, cols, ow, tid); break;
+        default: tile_vpass<G, 16>(tmpw, dst, t, v, rows, cols, ow, tid); break;
     }
 }
 

@@ -85,15 +85,8 @@ __global__ __launch_bounds__(kT) void jpeg_fdct_quant_kernel(const uint8_t* __re
     for (long g0 = blockIdx.x; g0 < groups; g0 += gridDim.x) {
         long g = g0;
         if (MULTI) {
-            int lo = 0, hi = n_images - 1;
-            while (lo < hi) {
-                const int m = (lo + hi + 1) >> 1;
-                if (items[m].group_start <= g0)
-                    lo = m;
-                else
-                    hi = m - 1;
-            }
-            const lf_jpeg_item it = items[lo];
+            const lf_jpeg_item it =
+                items[lf::last_item_not_past(n_images, g0, [&](int m) { return items[m].group_start; })];
             h = it.h;
             w = it.w;
             rgb = rgb0 + it.rgb_off;
@@ -263,15 +256,7 @@ struct ZigPos {
 
 // the image a pass (or a wave of the upsampling kernel) belongs to: the last one whose first pass is not behind g
 __device__ __forceinline__ int dec_item_of(const lf_jpeg_dec_item* __restrict__ items, int n, long g) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int m = (lo + hi + 1) >> 1;
-        if (items[m].group_start <= g)
-            lo = m;
-        else
-            hi = m - 1;
-    }
-    return lo;
+    return lf::last_item_not_past(n, g, [&](int m) { return items[m].group_start; });
 }
 
 // coefficients (zigzag, quantised) of four MCUs at a time -> Y plane and the two half-size chroma planes
@@ -363,6 +348,51 @@ __global__ __launch_bounds__(kT) void jpeg_idct_kernel(const uint8_t* __restrict
     }
 }
 
+// h2v2_fancy_upsample of chroma row i, columns j0..j0+3, of two cw x ch planes whose rows lie `pitch` bytes apart:
+// up[plane][output row v][output column] for the 2 x 8 output pixels.  Row ch-1 and column cw-1 are the LAST the
+// filter sees: the image's own edge stands in for a missing neighbour, whatever lies behind it in the plane.
+__device__ __forceinline__ void chroma_upsample(const uint8_t* cb, const uint8_t* cr, int pitch, int i, int j0, int cw,
+                                                int ch, int (&up)[2][2][8]) {
+    const uint8_t* planes[2] = {cb, cr};
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+        const uint8_t* c0 = planes[pl] + (size_t)i * pitch;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            const int inb = v == 0 ? max(i - 1, 0) : min(i + 1, ch - 1);
+            const uint8_t* c1 = planes[pl] + (size_t)inb * pitch;
+            int cs[6];   // column sums of columns j0-1 .. j0+4
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const int j = min(max(j0 - 1 + k, 0), cw - 1);
+                cs[k] = 3 * (int)c0[j] + (int)c1[j];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                up[pl][v][2 * k] = (3 * cs[k + 1] + cs[k] + 8) >> 4;
+                up[pl][v][2 * k + 1] = (3 * cs[k + 1] + cs[k + 2] + 7) >> 4;
+            }
+        }
+    }
+}
+
+// ycc_rgb_convert of eight pixels: luminance yy (two dwords), chroma up[plane][v][.] -> 24 bytes of RGB in o[]
+__device__ __forceinline__ void ycc_to_rgb8(uint2 yy, const int (&up)[2][2][8], int v, unsigned (&o)[6]) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int y = (int)(((k < 4 ? yy.x : yy.y) >> (8 * (k & 3))) & 255u);
+        const int xb = up[0][v][k] - 128, xr = up[1][v][k] - 128;
+        const int rr = min(max(y + ((91881 * xr + 32768) >> 16), 0), 255);
+        const int bb = min(max(y + ((116130 * xb + 32768) >> 16), 0), 255);
+        const int gg = min(max(y + ((-22554 * xb + 32768 - 46802 * xr) >> 16), 0), 255);
+        o[(3 * k) >> 2] |= (unsigned)rr << (8 * ((3 * k) & 3));
+        o[(3 * k + 1) >> 2] |= (unsigned)gg << (8 * ((3 * k + 1) & 3));
+        o[(3 * k + 2) >> 2] |= (unsigned)bb << (8 * ((3 * k + 2) & 3));
+    }
+}
+
 // one thread: four chroma samples of a row -> 2 x 8 output pixels (h2v2_fancy_upsample + ycc_rgb_convert)
 __global__ __launch_bounds__(kT) void jpeg_upsample_rgb_kernel(const uint8_t* __restrict__ yp,
                                                                const uint8_t* __restrict__ cbp,
@@ -374,45 +404,13 @@ __global__ __launch_bounds__(kT) void jpeg_upsample_rgb_kernel(const uint8_t* __
         const size_t r = t / qw;
         const int i = (int)(r % ch);
         const size_t n = r / ch;
-        const int j0 = 4 * jq;
-        const uint8_t* planes[2] = {cbp + n * (size_t)ch * cw, crp + n * (size_t)ch * cw};
-        int up[2][2][8];   // [plane][output row v][output column]
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-            const uint8_t* c0 = planes[pl] + (size_t)i * cw;
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                const int inb = v == 0 ? max(i - 1, 0) : min(i + 1, ch - 1);
-                const uint8_t* c1 = planes[pl] + (size_t)inb * cw;
-                int cs[6];   // column sums of columns j0-1 .. j0+4 (the image's own edge stands in outside)
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const int j = min(max(j0 - 1 + k, 0), cw - 1);
-                    cs[k] = 3 * (int)c0[j] + (int)c1[j];
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    up[pl][v][2 * k] = (3 * cs[k + 1] + cs[k] + 8) >> 4;
-                    up[pl][v][2 * k + 1] = (3 * cs[k + 1] + cs[k + 2] + 7) >> 4;
-                }
-            }
-        }
+        int up[2][2][8];
+        chroma_upsample(cbp + n * (size_t)ch * cw, crp + n * (size_t)ch * cw, cw, i, 4 * jq, cw, ch, up);
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
             const size_t row = n * (size_t)h + 2 * i + v;
-            const uint2 yy = *reinterpret_cast<const uint2*>(yp + row * w + 8 * jq);
-            unsigned o[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int y = (int)(((k < 4 ? yy.x : yy.y) >> (8 * (k & 3))) & 255u);
-                const int xb = up[0][v][k] - 128, xr = up[1][v][k] - 128;
-                const int rr = min(max(y + ((91881 * xr + 32768) >> 16), 0), 255);
-                const int bb = min(max(y + ((116130 * xb + 32768) >> 16), 0), 255);
-                const int gg = min(max(y + ((-22554 * xb + 32768 - 46802 * xr) >> 16), 0), 255);
-                o[(3 * k) >> 2] |= (unsigned)rr << (8 * ((3 * k) & 3));
-                o[(3 * k + 1) >> 2] |= (unsigned)gg << (8 * ((3 * k + 1) & 3));
-                o[(3 * k + 2) >> 2] |= (unsigned)bb << (8 * ((3 * k + 2) & 3));
-            }
+            unsigned o[6];
+            ycc_to_rgb8(*reinterpret_cast<const uint2*>(yp + row * w + 8 * jq), up, v, o);
             unsigned* dst = reinterpret_cast<unsigned*>(rgb + (row * w + 8 * jq) * 3);
 #pragma unroll
             for (int k = 0; k < 6; ++k) dst[k] = o[k];
@@ -467,47 +465,16 @@ __global__ __launch_bounds__(kT) void jpeg_upsample_rgb_items_kernel(const uint8
     const int i = 8 * my + (lane >> 3), j0 = 32 * gx + 4 * (lane & 7);
     if (i >= ch || j0 >= cw) return;
     const uint8_t* yp = ws + it.plane_off;
-    const uint8_t* planes[2] = {yp + (size_t)256 * mcu_h * mcu_w, yp + (size_t)320 * mcu_h * mcu_w};
-    int up[2][2][8];   // [plane][output row v][output column]
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-        const uint8_t* c0 = planes[pl] + (size_t)i * pcw;
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const int inb = v == 0 ? max(i - 1, 0) : min(i + 1, ch - 1);
-            const uint8_t* c1 = planes[pl] + (size_t)inb * pcw;
-            int cs[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const int j = min(max(j0 - 1 + k, 0), cw - 1);
-                cs[k] = 3 * (int)c0[j] + (int)c1[j];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                up[pl][v][2 * k] = (3 * cs[k + 1] + cs[k] + 8) >> 4;
-                up[pl][v][2 * k + 1] = (3 * cs[k + 1] + cs[k + 2] + 7) >> 4;
-            }
-        }
-    }
+    int up[2][2][8];
+    chroma_upsample(yp + (size_t)256 * mcu_h * mcu_w, yp + (size_t)320 * mcu_h * mcu_w, pcw, i, j0, cw, ch, up);
     const int x0 = 2 * j0, nv = min(8, w - x0);   // pixels of this thread's eight that lie in the image: 1..8
     uint8_t* out = rgb + it.rgb_off;
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
         const int row = 2 * i + v;
         if (row >= h) continue;   // (an odd height: the last chroma row yields one output row)
-        const uint2 yy = *reinterpret_cast<const uint2*>(yp + (size_t)row * pw + x0);
-        unsigned o[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int y = (int)(((k < 4 ? yy.x : yy.y) >> (8 * (k & 3))) & 255u);
-            const int xb = up[0][v][k] - 128, xr = up[1][v][k] - 128;
-            const int rr = min(max(y + ((91881 * xr + 32768) >> 16), 0), 255);
-            const int bb = min(max(y + ((116130 * xb + 32768) >> 16), 0), 255);
-            const int gg = min(max(y + ((-22554 * xb + 32768 - 46802 * xr) >> 16), 0), 255);
-            o[(3 * k) >> 2] |= (unsigned)rr << (8 * ((3 * k) & 3));
-            o[(3 * k + 1) >> 2] |= (unsigned)gg << (8 * ((3 * k + 1) & 3));
-            o[(3 * k + 2) >> 2] |= (unsigned)bb << (8 * ((3 * k + 2) & 3));
-        }
+        unsigned o[6];
+        ycc_to_rgb8(*reinterpret_cast<const uint2*>(yp + (size_t)row * pw + x0), up, v, o);
         store_bytes_any(out + ((size_t)row * w + x0) * 3, o, 3 * nv);
     }
 }

@@ -698,19 +698,24 @@ def rotate_expand_u8(x: torch.Tensor, angles: Sequence[float], fill: int = 255):
 TILE_OUT, TILE_WINDOW, TILE_TAPS = 32, 48, 10   # lf_resample_tile_u8's tile, window and tap limits
 
 
+def _axis_tables_fit(b: np.ndarray, out: int, window: int) -> bool:
+    """The tile kernels' rule for the windows b [..., outputs, 2] of one axis: every run of `out` outputs reads at
+    most `window` inputs, from starts that do not decrease."""
+    b = b.reshape(-1, b.shape[-2], 2).astype(np.int64)
+    for o0 in range(0, b.shape[1], out):
+        o1 = min(o0 + out, b.shape[1])
+        span = (b[:, o0:o1, 0] + b[:, o0:o1, 1]).max(axis=1) - b[:, o0, 0]
+        if int(span.max()) > window or (np.diff(b[:, o0:o1, 0], axis=1) < 0).any():
+            return False
+    return True
+
+
 def resample_tables_fit_tile(xb: np.ndarray, xk: np.ndarray, yb: np.ndarray, yk: np.ndarray, ow: int) -> bool:
     """Host check of lf_resample_tile_u8's preconditions on the (numpy) tables: at most 10 taps,
     ow % 4 == 0, and every run of 32 outputs reads at most 48 inputs on both axes."""
     if xk.shape[-1] > TILE_TAPS or yk.shape[-1] > TILE_TAPS or ow % 4:
         return False
-    for b in (xb, yb):
-        b = b.reshape(-1, b.shape[-2], 2).astype(np.int64)
-        for o0 in range(0, b.shape[1], TILE_OUT):
-            o1 = min(o0 + TILE_OUT, b.shape[1])
-            span = (b[:, o0:o1, 0] + b[:, o0:o1, 1]).max(axis=1) - b[:, o0, 0]
-            if int(span.max()) > TILE_WINDOW or (np.diff(b[:, o0:o1, 0], axis=1) < 0).any():
-                return False
-    return True
+    return all(_axis_tables_fit(b, TILE_OUT, TILE_WINDOW) for b in (xb, yb))
 
 
 def resample_u8(x: torch.Tensor, oh: int, ow: int, xb: torch.Tensor, xk: torch.Tensor,
@@ -737,22 +742,26 @@ def resample_u8(x: torch.Tensor, oh: int, ow: int, xb: torch.Tensor, xk: torch.T
     return out
 
 
+def _full_axis_table(in_len: int, out_len: int):
+    """(bounds, coefficients) of one axis at Pillow's full coefficient width; for an axis Pillow skips, the identity
+    table, which keeps the kernels generic."""
+    if in_len == out_len:
+        return (np.stack([np.arange(out_len), np.ones(out_len)], 1).astype(np.int32),
+                np.full((out_len, 1), 1 << _geo.PRECISION_BITS, dtype=np.int32))
+    b, k, _ = _geo.lanczos_coeffs(in_len, 0.0, float(in_len), out_len)
+    return b, k
+
+
 def resize_lanczos_u8(x: torch.Tensor, size: int) -> torch.Tensor:
     """ImageTransforms.resize_image(img, (size,size)) (LANCZOS) for a same-sized batch."""
     n, h, w = _hwc(x, "resize_lanczos.x")
     if (h, w) == (size, size):
         return x.clone()  # Image.resize returns a copy when nothing changes
-    xb, xk, _ = _geo.lanczos_coeffs(w, 0.0, float(w), size)
-    yb, yk, _ = _geo.lanczos_coeffs(h, 0.0, float(h), size)
-    dev = x.device
-    if w == size:  # Pillow skips the horizontal pass: identity table keeps the kernel generic
-        xb = np.stack([np.arange(size), np.ones(size)], 1).astype(np.int32)
-        xk = np.full((size, 1), 1 << _geo.PRECISION_BITS, dtype=np.int32)
-    if h == size:
-        yb = np.stack([np.arange(size), np.ones(size)], 1).astype(np.int32)
-        yk = np.full((size, 1), 1 << _geo.PRECISION_BITS, dtype=np.int32)
+    # (the full width: cut to the largest count as in _axis_table, 256 -> 224 would move from the 10-tap to the 8-tap
+    # instantiation of the tile kernel)
+    (xb, xk), (yb, yk) = _full_axis_table(w, size), _full_axis_table(h, size)
     tile_ok = resample_tables_fit_tile(xb, xk, yb, yk, size)
-    t = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (xb, xk, yb, yk)]
+    t = [torch.from_numpy(np.ascontiguousarray(a)).to(x.device) for a in (xb, xk, yb, yk)]
     return resample_u8(x, size, size, t[0], t[1], t[2], t[3], per_image=False, tile_ok=tile_ok)
 
 
@@ -782,25 +791,16 @@ _ITEM_DTYPE = np.dtype(_lib.ResampleItem)
 
 
 def _axis_table(in_len: int, out_len: int):
-    """(bounds, coefficients cut to the largest count) of one axis; the identity table for an axis Pillow skips."""
-    if in_len == out_len:
-        return (np.stack([np.arange(out_len), np.ones(out_len)], 1).astype(np.int32),
-                np.full((out_len, 1), 1 << _geo.PRECISION_BITS, dtype=np.int32))
-    b, k, _ = _geo.lanczos_coeffs(in_len, 0.0, float(in_len), out_len)
-    return b, k[:, :max(1, int(b[:, 1].max()))]   # (ksize is Pillow's allocation, two or so more than any count)
+    """_full_axis_table with the coefficients cut to the largest count (ksize is Pillow's allocation, two or so more
+    than any count)."""
+    b, k = _full_axis_table(in_len, out_len)
+    return b, k[:, :max(1, int(b[:, 1].max()))]
 
 
 def axis_table_fits_items(b: np.ndarray, k: np.ndarray) -> bool:
     """Host check of lf_resample_items_u8's preconditions on one axis table: at most 16 taps, and every run of 32
-    outputs reads at most 96 inputs from starts that do not decrease (resample_tables_fit_tile's rule, its limits)."""
-    if k.shape[1] > ITEMS_TAPS:
-        return False
-    b = b.astype(np.int64)
-    for o0 in range(0, b.shape[0], ITEMS_OUT):
-        o1 = min(o0 + ITEMS_OUT, b.shape[0])
-        if int((b[o0:o1, 0] + b[o0:o1, 1]).max() - b[o0, 0]) > ITEMS_WINDOW or (np.diff(b[o0:o1, 0]) < 0).any():
-            return False
-    return True
+    outputs reads at most 96 inputs from starts that do not decrease."""
+    return k.shape[1] <= ITEMS_TAPS and _axis_tables_fit(b, ITEMS_OUT, ITEMS_WINDOW)
 
 
 class ResampleTables:
