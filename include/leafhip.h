@@ -434,6 +434,23 @@ int lf_resample_items_u8(const uint8_t* in, size_t in_bytes, uint8_t* out, int n
                          const lf_resample_item* items, const lf_resample_item* host_items, int n,
                          const int32_t* tables, size_t table_elems, lf_stream_t stream);
 
+/* cv2.resize(img, (ow, oh), interpolation=cv2.INTER_LANCZOS4) for a same-size batch in [n][h][w][3] ->
+ * out [n][oh][ow][3] (the resize of the reference's training transform, srcs/cli/Transformation.py:799-801 and
+ * :941-946), with its _apply_light_augmentation (:984-1005) fused into the store.  Eight fixed taps per axis,
+ * coefficients short(cvRound(c * 2048)), source index clamp(s - 3 + i, 0, len - 1), a 32-bit horizontal
+ * intermediate, (v + (1 << 21)) >> 22 saturated to 8 bits; the 32-bit sums wrap.  The full reading: the comment
+ * at the top of lf_resize_cv.hip.  cv2 is not available to check against: parity with it is unpinned.
+ * tables (int32, on the device; host_tables = the same values in host memory, read before the launch to size the
+ *   tiles): xofs[ow], xcoef[ow][8], yofs[oh], ycoef[oh][8], ofs = floor of the source coordinate (not clamped;
+ *   it must not decrease along an axis), as ops.lanczos4_axis_table builds them.  Equal sizes give a copy.
+ * aug: null, or [n][4] float64 on the device {use_b, b, use_c, c}: if use_b != 0, p = (uint8)clip(p * b, 0, 255);
+ *   then if use_c != 0, p = (uint8)clip((p - 127.5) * c + 127.5, 0, 255), float64 without FMA contraction.
+ * Any sizes: output tiles of up to 32 x 32 whose source window is at most 56 x 56 (the tile shrinks with the scale,
+ * down to one output).  No allocation, no synchronisation. */
+int lf_resize_lanczos4_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int oh, int ow,
+                          const int32_t* tables, const int32_t* host_tables, const double* aug,
+                          lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* A2 — leaf_cnn conv stack (fp32, NCHW activations)                           */
 /* ------------------------------------------------------------------------- */

@@ -81,6 +81,7 @@ SIGNATURES = {
                        c_int, P],
     "lf_resample_items_fits": [c_int, c_int, c_int, c_int],
     "lf_resample_items_u8": [P, c_size_t, P, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P],
+    "lf_resize_lanczos4_u8": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
     "lf_conv2d_f32": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P],
     "lf_conv2d_bf16_weight_elems": [c_int, c_int, c_int],
     "lf_conv2d_bf16_prep_weights": [P, P, c_int, c_int, c_int, P],

@@ -13,16 +13,21 @@ batched launch over chunks of bounded size; outputs are encoded on the GPU (qual
 Not ported, each with one warning per run and no file: Analyze and Landmarks (PlantCV shape analysis, CLAHE /
 bilateral filtering, goodFeaturesToTrack) and the mosaic (cv2's Hershey text).  Hist is this project's own
 matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped.
+
+`create_transform_function` (at the end of the module) is the reference's training transform, the provider of
+ManifestSequence's `transform=` hook: see TransformFunction.
 """
 from __future__ import annotations
 
 import argparse
 import logging
 import os
+import random
 import re
+import threading
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
-from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -394,6 +399,290 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         return
 
     logging.error("Must specify either single image or --src/--dst for folder mode")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the training transform: ManifestSequence's `transform=` provider
+# ---------------------------------------------------------------------------------------------------------------
+
+TRAIN_MASK_TYPES = ("Mask", "Brown", "ROI", "Analyze", "Landmarks")   # the types whose stages read make_mask's output
+TRAIN_NOT_PRODUCED = ("Analyze", "Landmarks", "Hist")
+
+
+def draw_light_augmentation() -> Tuple[float, float, float, float]:
+    """The draws of the reference's _apply_light_augmentation for one image, from Python's global `random`, in its
+    order: random() < 0.3 -> brightness uniform(0.8, 1.2); random() < 0.2 -> contrast uniform(0.8, 1.2).  Returns
+    ops.resize_lanczos4_u8's parameter row (use_b, b, use_c, c)."""
+    use_b = random.random() < 0.3
+    b = random.uniform(0.8, 1.2) if use_b else 1.0
+    use_c = random.random() < 0.2
+    c = random.uniform(0.8, 1.2) if use_c else 1.0
+    return float(use_b), b, float(use_c), c
+
+
+def _nearest_fallback(path, size: int) -> np.ndarray:
+    """keras load_img(path, target_size=(size, size), color_mode="rgb"): Pillow, no EXIF transpose, NEAREST."""
+    from PIL import Image
+    with Image.open(path) as im:
+        im = im.convert("RGB")
+        if im.size != (size, size):
+            im = im.resize((size, size), Image.NEAREST)
+        return np.array(im)
+
+
+class TransformFunction:
+    """What create_transform_function returns: the reference's training transform (transform_single_image_for_training,
+    srcs/cli/Transformation.py:709-1053) with the filters, the resize and the augmentation on the GPU.
+
+    `fn(img_path, item, img_size, transformations=None, cache=None, logger=None)` is the reference's hook:
+    (orig_uint8 [S,S,3], x_float32 [S,S,3]), orig = the INTER_LANCZOS4 resize of the decoded image, x = uint8 / 255 of
+    the transformed, resized and augmented image.  `fn.batch(paths, img_size, transformations=None)` is the hot path:
+    uint8 [B,S,S,3] on the device, decoded on host threads, grouped by source size, one launch per stage and one
+    resize launch per group; the per-image call is a batch of one through the same code.
+
+    Stages run on the ORIGINAL image in the order Blur, Mask (black background), ROI (the image with the box drawn),
+    Analyze, Landmarks, Hist, Brown; each that produces an image replaces the result, so the last one wins whatever
+    the order of the names.  The mask is made once, on the original.  An image without a contour keeps what it had
+    before ROI.  Analyze, Landmarks and Hist produce no image here and are skipped with one warning per object (the
+    reference would feed their picture when it is the last produced).  The augmentation draws come from Python's
+    global `random`, under a lock, image by image in batch order, so that after random.seed(k) a batch equals
+    sequential calls.  A file the filters reject or any stage error logs the reference's error line and takes its
+    fallback (Pillow NEAREST resize of the file, no augmentation); an unreadable file gives the black pair.  The
+    LEAF_SAVE_TRANSFORMS* preview dumps of the reference are presentation and are not reproduced; apply_brown_filter's
+    per-image log line is not written either."""
+
+    def __init__(self, cfg, transform_types: Optional[Sequence[str]], apply_augmentation: bool, workers: int = 0):
+        self.cfg = cfg
+        self.transform_types = transform_types
+        self.apply_augmentation = bool(apply_augmentation)
+        self.workers = workers
+        self._cache: Dict[Any, Any] = {}
+        self._lock = threading.Lock()        # the draws of one batch are consecutive in `random`'s stream
+        self._warned = False
+
+    # ---------------------------------------------------------------- names
+    def _canonical(self, transformations, log, where) -> Tuple[str, ...]:
+        chosen = transformations if transformations is not None else self.transform_types
+        if chosen is None:
+            chosen = DEFAULT_TYPES
+        result: List[Any] = []
+        for t in chosen:
+            name = CANONICAL_TYPES.get(str(t).strip().lower(), t)
+            if name in result:
+                log.info("Duplicate transform '%s' ignored for %s", name, where)
+            else:
+                result.append(name)
+        skipped = [t for t in TRAIN_NOT_PRODUCED if t in result]
+        if skipped:
+            with self._lock:
+                first, self._warned = not self._warned, True
+            if first:
+                log.warning("%s produce no image in the training transform (Analyze and Landmarks are not ported, "
+                            "Hist is a figure) and are skipped", ", ".join(skipped))
+        return tuple(result)
+
+    # ---------------------------------------------------------------- stages of one same-size group
+    def _masks(self, x):
+        from ..transform import filters as F
+        mask, contour, counts, _fb = F.make_masks_device(x, self.cfg)
+        return mask, contour, counts
+
+    def _stages(self, x, types: Tuple[str, ...], masks=None):
+        """transform_single_image_for_training's stages for a same-size batch [N,H,W,3] uint8 on the device: (the
+        image each row ends with, (mask, contour, counts) or None)."""
+        import torch
+
+        from .. import ops
+        from ..transform import filters as F
+        cfg = self.cfg
+        need_mask = any(t in types for t in TRAIN_MASK_TYPES)
+        if masks is None and (need_mask or "Blur" in types):
+            masks = self._masks(x)
+        res = x
+        if "Blur" in types:    # apply_blur_filter(rgb, cfg, make_mask): the same mask, made there a second time
+            leaf = torch.where(masks[0] > 0, 255, 0).to(torch.uint8)
+            res = ops.blur_saliency_u8(
+                x, leaf, gaussian_sigma=float(cfg.gaussian_sigma), brown_hue_range=tuple(cfg.brown_hue_range),
+                brown_s_min=int(cfg.brown_s_min), brown_v_max=int(cfg.brown_v_max), use_brown=True)
+        if "Mask" in types:
+            res = ops.mask_composite_u8(x, masks[0], "black")
+        if "ROI" in types:
+            mask, contour, counts = masks
+            _canvas, vis, _bb, found = ops.roi_u8(x, contour, counts, tuple(cfg.roi_size))
+            res = torch.where((found != 0).view(-1, 1, 1, 1), vis, res)
+        if "Brown" in types:
+            res, _stats = ops.brown_spots_u8(
+                x, masks[0], brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
+                brown_v_max=int(cfg.brown_v_max), use_lab_brown=bool(cfg.use_lab_brown),
+                lab_a_min=int(cfg.lab_a_min), lab_b_min=int(cfg.lab_b_min),
+                brown_min_area_px=int(cfg.brown_min_area_px), brown_morph_kernel=int(cfg.brown_morph_kernel))
+        return res.contiguous(), (masks if need_mask else None)
+
+    # ---------------------------------------------------------------- the shared path
+    def _run(self, paths: Sequence[Any], size: int, types: Tuple[str, ...], log, cache=None, want_orig: bool = False):
+        """uint8 [B,S,S,3] on the device for `paths` (and, with want_orig, the resized originals as a second tensor;
+        rows that took a fallback hold the fallback image in both).  `cache` (the per-image call's) supplies and
+        receives the reference's "__rgb__", "__mask__" and "__contour__" entries."""
+        import torch
+
+        from .. import ops
+        from ..transform.filters import _device
+        dev = _device()
+        n, S = len(paths), int(size)
+        out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
+        orig = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev) if want_orig else None
+
+        def load(p):
+            key = ("__rgb__", str(p))
+            if cache is not None and key in cache:
+                return cache[key]
+            try:
+                rgb = pil_read_rgb(Path(p))
+            except Exception as exc:  # noqa: BLE001 — any unreadable file takes the fallback
+                return exc
+            if cache is not None:
+                cache[key] = rgb
+            return rgb
+
+        if n > 1:
+            with ThreadPoolExecutor(self.workers if self.workers > 0 else _workers(0)) as pool:
+                decoded = list(pool.map(load, paths))
+        else:
+            decoded = [load(p) for p in paths]
+
+        failed: Dict[int, Exception] = {}
+        groups: Dict[Tuple[int, int], List[int]] = {}
+        for i, rgb in enumerate(decoded):
+            if isinstance(rgb, Exception):
+                failed[i] = rgb
+            else:
+                groups.setdefault(rgb.shape[:2], []).append(i)
+
+        staged = []   # (rows, the group on the device, its transformed images)
+        for rows in groups.values():
+            try:
+                x = torch.from_numpy(np.stack([decoded[i] for i in rows])).to(dev)
+                if want_orig:
+                    self._orig(x, rows, paths, S, cache, orig)
+                masks = self._cached_masks(paths, rows, cache, dev)
+                res, made = self._stages(x, types, masks)
+                if cache is not None and made is not None and masks is None:
+                    self._store_masks(paths, rows, cache, made)
+                staged.append((rows, res))
+            except Exception as exc:  # noqa: BLE001 — the reference's blanket fallback
+                for i in rows:
+                    failed[i] = exc
+
+        if self.apply_augmentation and staged:
+            params = np.zeros((n, 4), dtype=np.float64)
+            with self._lock:
+                for i in sorted(i for rows, _r in staged for i in rows):
+                    params[i] = draw_light_augmentation()
+            aug = torch.from_numpy(params).to(dev)
+        else:
+            aug = None
+        for rows, res in staged:
+            whole = len(rows) == n   # one group, in order: written in place
+            sel = None if whole else torch.tensor(rows, device=dev)
+            a = None if aug is None else (aug if whole else aug[sel].contiguous())
+            try:
+                if whole:
+                    ops.resize_lanczos4_u8(res, S, aug=a, out=out)
+                else:
+                    out[sel] = ops.resize_lanczos4_u8(res, S, aug=a)
+            except Exception as exc:  # noqa: BLE001
+                for i in rows:
+                    failed[i] = exc
+
+        for i in sorted(failed):
+            log.error("Failed to transform %s (%s), falling back to simple resize", paths[i], failed[i])
+            try:
+                fb = torch.from_numpy(_nearest_fallback(paths[i], S)).to(dev)
+            except Exception as exc:  # noqa: BLE001
+                log.error("Complete failure to load %s (%s)", paths[i], exc)
+                fb = torch.zeros((S, S, 3), dtype=torch.uint8, device=dev)
+            out[i] = fb
+            if orig is not None:
+                orig[i] = fb
+        return out, orig, set(failed)
+
+    def _orig(self, x, rows, paths, S, cache, orig) -> None:
+        """The resized originals of a group: from the cache's "__orig__" entries, else one launch (and stored)."""
+        import torch
+
+        from .. import ops
+        keys = [("__orig__", str(paths[i]), S) for i in rows]
+        if cache is not None and all(k in cache for k in keys):
+            for i, k in zip(rows, keys):
+                orig[i] = torch.from_numpy(cache[k]).to(orig.device)
+            return
+        y = ops.resize_lanczos4_u8(x, S)
+        orig[torch.tensor(rows, device=orig.device)] = y
+        if cache is not None:
+            for k, a in zip(keys, y.cpu().numpy()):
+                cache[k] = a
+
+    @staticmethod
+    def _cached_masks(paths, rows, cache, dev):
+        """(mask, contour, counts) of a group from the cache's "__mask__" / "__contour__" entries, or None."""
+        import torch
+        if cache is None:
+            return None
+        keys = [(("__mask__", str(paths[i])), ("__contour__", str(paths[i]))) for i in rows]
+        if not all(m in cache and c in cache for m, c in keys):
+            return None
+        contours = [cache[c] for _m, c in keys]
+        cap = max([1] + [len(c) for c in contours if c is not None])
+        cnt = np.zeros((len(rows), cap, 2), dtype=np.int32)
+        counts = np.zeros(len(rows), dtype=np.int32)
+        for j, c in enumerate(contours):
+            if c is not None:
+                counts[j] = len(c)
+                cnt[j, :len(c)] = np.asarray(c).reshape(-1, 2)
+        mask = torch.from_numpy(np.stack([cache[m] for m, _c in keys])).to(dev)
+        return mask, torch.from_numpy(cnt).to(dev), torch.from_numpy(counts).to(dev)
+
+    @staticmethod
+    def _store_masks(paths, rows, cache, made) -> None:
+        mask, contour, counts = (t.cpu().numpy() for t in made)
+        for j, i in enumerate(rows):
+            k = int(counts[j])
+            cache[("__mask__", str(paths[i]))] = mask[j].copy()
+            cache[("__contour__", str(paths[i]))] = contour[j, :k].reshape(-1, 1, 2).copy() if k > 0 else None
+
+    # ---------------------------------------------------------------- the two entry points
+    def batch(self, paths: Sequence[Any], img_size: int, transformations: Optional[Sequence[str]] = None):
+        """uint8 [B,S,S,3] on the device: the transformed, resized and augmented images of `paths`, in their order.
+        Keeps no cache (that is ManifestSequence's job)."""
+        log = logging.getLogger(__name__)
+        types = self._canonical(transformations, log, f"a batch of {len(paths)}")
+        return self._run(list(paths), int(img_size), types, log)[0]
+
+    def __call__(self, img_path, item, img_size: int, transformations: Optional[Sequence[str]] = None,
+                 cache: Optional[Dict[Any, Any]] = None, logger: Optional[logging.Logger] = None):
+        log = logger or logging.getLogger(__name__)
+        types = self._canonical(transformations, log, img_path)
+        store = cache if cache is not None else self._cache
+        key = (str(img_path), int(img_size), tuple(types))
+        if key in store:
+            hit = store[key]
+            return hit[0], hit[1]
+        out, orig, failed = self._run([img_path], int(img_size), types, log, cache=store, want_orig=True)
+        u8 = out[0].cpu().numpy()
+        pair = (u8 if failed else orig[0].cpu().numpy(), (u8 / 255.0).astype("float32"))
+        store[key] = pair
+        return pair
+
+
+def create_transform_function(config_path: Optional[str] = None, transform_types: Optional[Tuple[str, ...]] = None,
+                              apply_augmentation: bool = True) -> TransformFunction:
+    """The reference's create_transform_function (srcs/cli/Transformation.py:1008-1053): a `transform=` hook for
+    ManifestSequence that feeds leaf-masked, saliency, ROI-boxed or brown-spot images, here a TransformFunction
+    (callable per image, `.batch` for a device batch).  config_path: a YAML file with the reference's keys; None =
+    the values of its config.yaml.  transform_types: names or aliases, None = all seven."""
+    from ..transform.filters import TransformConfig, load_config
+    cfg = load_config(Path(config_path)) if config_path else TransformConfig()
+    return TransformFunction(cfg, transform_types, apply_augmentation)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,12 @@
 Same constructor, same batching rules (ceil(len/batch) batches, short last batch, seeded
 `random.Random(seed)` shuffle at construction and on every `on_epoch_end`), same label
 formats (one-hot float32 [C] or int32 index), same optional `transform` hook
-`(Path, ManifestItem, img_size) -> (uint8 HxWx3, float32 HxWx3)` and RAM cache.
+`(Path, ManifestItem, img_size) -> (uint8 HxWx3, float32 HxWx3)` and RAM cache.  As in the reference
+(sequence.py:80-81,108,141) the model is fed the hook's SECOND element, the transformed image in [0, 1]; batches
+here are uint8, so it is quantised as `np.rint(x * 255)` — exact for every hook that returns `uint8 / 255`, as the
+reference's provider does.  A hook with a `batch(paths, img_size)` method (cli.Transformation's
+create_transform_function) is asked for the whole batch at once instead: one uint8 device tensor, no per-image
+launches.
 
 Differences that matter on MI355X: images are decoded on host threads (Pillow) but resized
 (Pillow-exact LANCZOS kernel) and packed on the GPU; `__getitem__` returns the batch as a
@@ -124,8 +129,11 @@ class ManifestSequence:
         """uint8 [B,S,S,3] for the given item indexes (cache-aware)."""
         missing = [i for i in idxs if i not in self._cache_u8]
         if missing:
-            if self.transform is not None:
-                loaded = [self.transform(Path(self.items[i].src), self.items[i], self.img_size)[0]
+            if self.transform is not None and hasattr(self.transform, "batch"):
+                loaded = list(self._transform_batch(missing).cpu().numpy())
+            elif self.transform is not None:
+                loaded = [np.rint(np.asarray(self.transform(Path(self.items[i].src), self.items[i],
+                                                            self.img_size)[1]) * 255).astype(np.uint8)
                           for i in missing]
             else:
                 if self.workers > 1:
@@ -141,6 +149,13 @@ class ManifestSequence:
             fresh = {}
         return np.stack([self._cache_u8[i] if i in self._cache_u8 else fresh[i] for i in idxs])
 
+    def _transform_batch(self, idxs: List[int]):
+        """uint8 device tensor [B,S,S,3] from the transform hook's `batch`."""
+        x = self.transform.batch([Path(self.items[i].src) for i in idxs], self.img_size)
+        if tuple(x.shape) != (len(idxs), self.img_size, self.img_size, 3) or str(x.dtype) != "torch.uint8":
+            raise ValueError(f"transform.batch returned {x.dtype} {tuple(x.shape)}")
+        return x
+
     POOL_MIN = 64   # below this many files the worker pool costs more than it saves
 
     def _load_dev(self, idxs: List[int]):
@@ -148,6 +163,9 @@ class ManifestSequence:
         when the batch is large enough, else the host path and one upload.  An unreadable file raises,
         as the reference's loader does (image_utils.py:19-33)."""
         import torch
+        if (self.transform is not None and hasattr(self.transform, "batch") and not self.cache
+                and not any(i in self._cache_u8 for i in idxs)):
+            return self._transform_batch(idxs)
         if self.transform is not None or len(idxs) < self.POOL_MIN or any(i in self._cache_u8 for i in idxs):
             return torch.from_numpy(self._load_u8(idxs)).cuda()
         from .device_decode import DeviceDecoder

@@ -6,6 +6,8 @@ is never launched with operand shapes other than the ones its grid assumes.
 """
 from __future__ import annotations
 
+import functools
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -947,3 +949,85 @@ def resize_lanczos_arrays_u8(arrays: Sequence[np.ndarray], size: int) -> torch.T
         packed[o:o + a.size] = a.reshape(-1)
     dev = torch.device("cuda", torch.cuda.current_device())
     return resize_lanczos_items_u8(torch.from_numpy(packed).to(dev), items, size)
+
+
+# ---- cv2.resize(..., INTER_LANCZOS4) with the training provider's light augmentation (lf_resize_lanczos4_u8)
+_FLT_EPSILON = np.float32(1.1920928955078125e-07)
+_R45 = 0.70710678118654752440
+_LANCZOS4_CS = ((1.0, 0.0), (-_R45, -_R45), (0.0, 1.0), (_R45, -_R45), (-1.0, 0.0), (_R45, _R45), (0.0, -1.0),
+                (-_R45, _R45))
+
+
+@functools.lru_cache(maxsize=256)
+def lanczos4_axis_table(src: int, dst: int):
+    """(ofs int32 [dst], coef int32 [dst, 8]) of one axis of OpenCV's 8-bit INTER_LANCZOS4 resize, in the reading
+    stated at the top of lf_resize_cv.hip: float32 where OpenCV computes in float, double where it computes in double
+    (interpolateLanczos4), coefficients short(cvRound(c * 2048)).  ofs is floor of the source coordinate, not
+    clamped; tap i reads clamp(ofs - 3 + i, 0, src - 1).  The arrays are shared between calls: do not write to them.
+    A few extreme up-scales (49 x and beyond) round a fraction to 1.0f, where OpenCV's own taps divide by zero; they
+    raise ValueError."""
+    f32 = np.float32
+    scale = 1.0 / (dst / float(src))
+    ofs = np.empty(dst, dtype=np.int32)
+    coef = np.zeros((dst, 8), dtype=np.int32)
+    for d in range(dst):
+        f = f32((d + 0.5) * scale - 0.5)
+        s = int(math.floor(f))
+        f = f32(f - f32(s))
+        ofs[d] = s
+        if f >= 1.0:
+            raise ValueError(f"lanczos4_axis_table: {src} -> {dst} has no finite taps at output {d} (fraction 1.0f)")
+        if f < _FLT_EPSILON:
+            coef[d, 3] = 2048
+            continue
+        x3 = f32(f + f32(3.0))
+        y0 = -float(x3) * math.pi * 0.25
+        s0, c0 = math.sin(y0), math.cos(y0)
+        c = np.empty(8, dtype=np.float32)
+        total = f32(0.0)
+        for i, (a, b) in enumerate(_LANCZOS4_CS):
+            y = -float(f32(x3 - f32(i))) * math.pi * 0.25
+            c[i] = f32((a * s0 + b * c0) / (y * y))
+            total = f32(total + c[i])
+        inv = f32(f32(1.0) / total)
+        for i in range(8):
+            q = np.rint(f32(f32(c[i] * inv) * f32(2048.0)))
+            coef[d, i] = int(min(max(q, -32768.0), 32767.0))
+    ofs.setflags(write=False)
+    coef.setflags(write=False)
+    return ofs, coef
+
+
+@functools.lru_cache(maxsize=64)
+def _lanczos4_tables(h: int, w: int, oh: int, ow: int, device):
+    """lf_resize_lanczos4_u8's table block xofs[ow], xcoef[ow][8], yofs[oh], ycoef[oh][8]: (host array, its copy on
+    the device), kept per geometry."""
+    (xo, xc), (yo, yc) = lanczos4_axis_table(w, ow), lanczos4_axis_table(h, oh)
+    host = np.ascontiguousarray(np.concatenate([xo, xc.reshape(-1), yo, yc.reshape(-1)]).astype(np.int32))
+    return host, torch.from_numpy(host).to(device)
+
+
+def resize_lanczos4_u8(x: torch.Tensor, size, aug: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cv2.resize(img, (S, S), interpolation=cv2.INTER_LANCZOS4) for a same-size batch [N,H,W,3] uint8 -> [N,S,S,3]
+    (`size` an int, or (OH, OW) for a rectangle); equal sizes give a copy.  aug: None, or [N,4] float64 on the device
+    {use_b, b, use_c, c}, the reference's _apply_light_augmentation fused into the store: brightness
+    uint8(clip(p * b, 0, 255)) if use_b, then contrast uint8(clip((p - 127.5) * c + 127.5, 0, 255)) if use_c.
+    The reading of OpenCV implemented: lf_resize_cv.hip (parity with cv2 is unpinned)."""
+    n, h, w = _hwc(x, "resize_lanczos4.x")
+    oh, ow = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    if oh <= 0 or ow <= 0:
+        raise ValueError(f"resize_lanczos4: bad output size {size}")
+    if aug is not None:
+        _chk(aug, _F64, "resize_lanczos4.aug", 2)
+        if tuple(aug.shape) != (n, 4):
+            raise ValueError(f"resize_lanczos4.aug: expected [{n}, 4], got {tuple(aug.shape)}")
+    if out is None:
+        out = torch.empty((n, oh, ow, 3), dtype=_U8, device=x.device)
+    _chk(out, _U8, "resize_lanczos4.out", 4)
+    if tuple(out.shape) != (n, oh, ow, 3):
+        raise ValueError("resize_lanczos4.out: shape mismatch")
+    host, tables = _lanczos4_tables(h, w, oh, ow, x.device)
+    _lib.call("lf_resize_lanczos4_u8", x.data_ptr(), out.data_ptr(), n, h, w, oh, ow, tables.data_ptr(),
+              host.ctypes.data, aug.data_ptr() if aug is not None else None, _stream())
+    return out
