@@ -2027,7 +2027,8 @@ static int conv2d_launch(const char* who, const float* x, const float* w, const 
                "%s: per-image tensor too large for 32-bit offsets", who);
     const int best = lf_conv2d_variant(h, wd, cout, ksize);
     const FwdVariant& v = kFwdVariants[best];
-    if (fwd_takes_wino_filters(cin, h, wd, cout, ksize)) {
+    const bool wino = fwd_takes_wino_filters(cin, h, wd, cout, ksize);
+    if (wino) {
         // no in-kernel transform to fall back to: w is not read and may be null
         LF_REQUIRE(wino_u, "%s: this 3x3 convolution runs in the Winograd domain and needs wino_u "
                    "(lf_conv2d_wino_filters_f32)", who);
@@ -2038,12 +2039,12 @@ static int conv2d_launch(const char* who, const float* x, const float* w, const 
     }
     ConvArgs a;
     a.x = x; a.w = w; a.y = y;
-    a.wino_u = fwd_takes_wino_filters(cin, h, wd, cout, ksize) ? wino_u : nullptr;
+    a.wino_u = wino ? wino_u : nullptr;
     a.in_scale = in_scale; a.in_shift = in_shift;
     a.n = n; a.cin = cin; a.cout = cout; a.h = h; a.wd = wd;
     a.in_relu = in_relu;
     a.accumulate = accumulate;
-    a.vec_ok = fwd_vec_shape(wd, cout) && aligned16(x) && aligned16(a.wino_u ? nullptr : w);
+    a.vec_ok = fwd_vec_shape(wd, cout) && aligned16(x) && aligned16(wino ? nullptr : w);
     a.stack = conv_stack(best, n, cin, h, wd, cout);
     if (a.stack > 1 && !a.vec_ok) {
         if (stat_part != nullptr) {  // the tile count the caller sized its buffers for assumes it
@@ -2080,17 +2081,20 @@ long long lf_conv2d_stats_tiles(int n, int cin, int h, int wd, int cout, int ksi
     return (long long)((n + stack - 1) / stack) * ((wd + v.tw - 1) / v.tw) * ((stack * h + v.th - 1) / v.th);
 }
 
+// the per-tile sums of a statistics epilogue: [lf_conv2d_stats_tiles][cout][2] floats
+static int check_tile_part(const char* who, size_t tile_part_bytes, int n, int cin, int h, int wd, int cout, int ksize) {
+    const long long tiles = lf_conv2d_stats_tiles(n, cin, h, wd, cout, ksize);
+    if (tile_part_bytes >= (size_t)tiles * (size_t)(cout > 0 ? cout : 0) * 2 * sizeof(float)) return LF_OK;
+    lf::set_error("%s: tile_part %zu bytes < %lld tiles x %d channels x 8", who, tile_part_bytes, tiles, cout);
+    return LF_ERR_WORKSPACE;
+}
+
 int lf_conv2d_stats_f32(const float* x, const float* w, float* y, int n, int cin, int h, int wd,
                         int cout, int ksize, const float* in_scale, const float* in_shift,
                         int in_relu, const float* pivot, float* tile_part, size_t tile_part_bytes,
                         lf_stream_t stream, const float* wino_u) {
     LF_REQUIRE(tile_part, "lf_conv2d_stats: null tile_part");
-    const long long tiles = lf_conv2d_stats_tiles(n, cin, h, wd, cout, ksize);
-    if (tile_part_bytes < (size_t)tiles * (size_t)(cout > 0 ? cout : 0) * 2 * sizeof(float)) {
-        lf::set_error("lf_conv2d_stats: tile_part %zu bytes < %lld tiles x %d channels x 8",
-                      tile_part_bytes, tiles, cout);
-        return LF_ERR_WORKSPACE;
-    }
+    if (const int rc = check_tile_part("lf_conv2d_stats", tile_part_bytes, n, cin, h, wd, cout, ksize)) return rc;
     return conv2d_launch("lf_conv2d_stats", x, w, wino_u, y, n, cin, h, wd, cout, ksize, in_scale, in_shift,
                          in_relu, 0, tile_part, pivot, nullptr, nullptr, nullptr, 0, stream);
 }
@@ -2100,12 +2104,7 @@ int lf_conv2d_bnbwd_f32(const float* x, const float* w, float* y, int n, int cin
                         const float* mask_scale, const float* mask_shift, int mask_relu,
                         float* tile_part, size_t tile_part_bytes, lf_stream_t stream, const float* wino_u) {
     LF_REQUIRE(tile_part && mask_y && mask_scale && mask_shift, "lf_conv2d_bnbwd: null buffer");
-    const long long tiles = lf_conv2d_stats_tiles(n, cin, h, wd, cout, ksize);
-    if (tile_part_bytes < (size_t)tiles * (size_t)(cout > 0 ? cout : 0) * 2 * sizeof(float)) {
-        lf::set_error("lf_conv2d_bnbwd: tile_part %zu bytes < %lld tiles x %d channels x 8",
-                      tile_part_bytes, tiles, cout);
-        return LF_ERR_WORKSPACE;
-    }
+    if (const int rc = check_tile_part("lf_conv2d_bnbwd", tile_part_bytes, n, cin, h, wd, cout, ksize)) return rc;
     return conv2d_launch("lf_conv2d_bnbwd", x, w, wino_u, y, n, cin, h, wd, cout, ksize, nullptr, nullptr, 0,
                          accumulate, tile_part, nullptr, mask_y, mask_scale, mask_shift, mask_relu,
                          stream);

@@ -214,6 +214,12 @@ class LeafCNN:
             d[key] = t
         return t
 
+    def _pass_bufs(self, n: int, bf16: bool):
+        """The buffer getter B(key, shape, dtype = the activation dtype) of a forward / backward pass at batch n.  The
+        bf16 step has buffers of its own: activations and their gradients in bf16, the rest fp32."""
+        pre, act = ("t16.", torch.bfloat16) if bf16 else ("", torch.float32)
+        return lambda k, shape, dt=act: self._buf(n, pre + k, shape, dt)
+
     def _norm_consts(self):
         if self.norm is None:
             return None, None
@@ -486,9 +492,7 @@ class LeafCNN:
         if training:
             self._mut += 1   # the BatchNorm layers update their moving statistics
         P, F32 = self.p, torch.float32
-        # the bf16 step has buffers of its own: activations and their gradients in bf16, the rest fp32
-        pre, act = ("t16.", torch.bfloat16) if bf16 else ("", F32)
-        B = lambda k, shape, dt=act: self._buf(n, pre + k, shape, dt)  # noqa: E731
+        B = self._pass_bufs(n, bf16)
         sv: Dict[str, Any] = {"x0": x0, "n": n, "bf16": bf16}
         if bf16:
             self._prep_bf16_weights()
@@ -572,8 +576,7 @@ class LeafCNN:
         sv, P, G = self._saved, self.p, self.g
         n, bf16 = sv["n"], sv["bf16"]
         F32 = torch.float32
-        pre, act = ("t16.", torch.bfloat16) if bf16 else ("", F32)   # the forward's buffers: see there
-        B = lambda k, shape, dt=act: self._buf(n, pre + k, shape, dt)  # noqa: E731
+        B = self._pass_bufs(n, bf16)   # the forward's buffers
         bn_bwd_wgrad = nn.bn_bwd_wgrad_bf16 if bf16 else nn.bn_bwd_wgrad
         f_last = self.widths[-1]
         if part in (None, 0):

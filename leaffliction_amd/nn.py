@@ -10,6 +10,7 @@ from . import _lib
 from .ops import _chk, _stream
 
 _F32 = torch.float32
+_BF16 = torch.bfloat16
 _ws_cache = {}
 _ws_gen = 0
 # A/B knob for measurements: route BatchNorm backward through the standalone apply kernel
@@ -101,6 +102,83 @@ def _conv_weights(who: str, x: torch.Tensor, w_iko: Optional[torch.Tensor], ksiz
     return cout, _ptr(w_iko), wino_u.data_ptr()
 
 
+# The rules every convolution launcher below shares, each stated once.
+def _prologue(who: str, in_scale, in_shift, cin: int) -> None:
+    """The prologue x' = x*in_scale[c]+in_shift[c] of a launch: f32 vectors [Cin], or None."""
+    for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift")):
+        if t is not None:
+            _chk(t, _F32, f"{who}.{nm}", 1)
+            if t.shape[0] != cin:
+                raise ValueError(f"{who}.{nm}: expected [{cin}]")
+
+
+def _act_in(who: str, x: torch.Tensor) -> bool:
+    """Checks an input stored as fp32 or bf16 (contiguous NCHW); True for bf16."""
+    if x.dtype not in (_F32, _BF16):
+        raise TypeError(f"{who}.x: expected float32 or bfloat16, got {x.dtype}")
+    _chk(x, x.dtype, f"{who}.x", 4)
+    return x.dtype == _BF16
+
+
+def _act_out(who: str, out: Optional[torch.Tensor], shape, dtypes, default, device) -> torch.Tensor:
+    """The output of a launch: `out`, or a new tensor of dtype `default` (None: `out` is required); either way
+    contiguous, of one of `dtypes` and of `shape`."""
+    if out is None and default is not None:
+        out = torch.empty(shape, dtype=default, device=device)
+    dtype = getattr(out, "dtype", None)
+    _chk(out, dtype if dtype in dtypes else dtypes[0], f"{who}.out", len(shape))
+    if tuple(out.shape) != shape:
+        raise ValueError(f"{who}.out: expected {shape}, got {tuple(out.shape)}")
+    return out
+
+
+def _bf16_weight_elems(cin: int, cout: int, ksize: int) -> int:
+    """lf_conv2d_bf16_weight_elems in Python, for the launchers' checks (no library call per launch)."""
+    return ((cin + 15) // 16) * ksize * ksize * cout * 16
+
+
+def _packed_weights(who: str, wprep: torch.Tensor, cin: int, cout: int, ksize: int) -> None:
+    if wprep.dtype != torch.int16 or wprep.numel() != _bf16_weight_elems(cin, cout, ksize):
+        raise ValueError(f"{who}.wprep: not the packed weights of this convolution")
+
+
+def _tile_part(x: torch.Tensor, tiles: int, cout: int) -> torch.Tensor:
+    """Workspace (slot 1) for the per-tile sums [tiles,Cout,2] a convolution's statistics epilogue leaves."""
+    return _workspace(tiles * cout * 8, x.device, slot=1)
+
+
+def _bn_stats_from_tiles(tp, tiles, n, cout, hw, gamma, beta, mmean, mvar, stats, momentum, eps, device) -> None:
+    """BatchNorm training statistics `stats` [4,C] and the moving statistics from a convolution's per-tile sums."""
+    ws = _workspace(_lib.load().lf_bn_workspace(cout), device)
+    _lib.call("lf_bn_train_stats_tiles_f32", tp.data_ptr(), tiles, n, cout, hw, gamma.data_ptr(), beta.data_ptr(),
+              mmean.data_ptr(), mvar.data_ptr(), float(momentum), float(eps), stats[0].data_ptr(),
+              stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+
+
+def _bn_bwd_coef(who: str, stats, gamma, dgamma, dbeta, relu: bool, n: int, c: int, hw: int, device, g=None,
+                 y=None, alpha_nc=None, add_nc=None, plane_g=None, plane_m=None, tile_sums=None):
+    """The reduction half of BatchNorm backward: fills dgamma / dbeta and the per-channel coefficients `coef`
+    (slot 2) from which a kernel forms dy = BN'(g).  Exactly one source of sums: tile_sums (a convolution's
+    epilogue: final, so no alpha/add/plane sums next to them), plane_g (+ plane_m), or a pass over g and y.
+    Returns (coef, the BatchNorm workspace)."""
+    beside = any(t is not None for t in (alpha_nc, add_nc, plane_g))
+    if (beside if tile_sums is not None else (plane_g is None and g is None)):
+        raise ValueError(f"{who}: sums from tile_sums alone (no alpha/add/plane sums), or else from plane_g or g, y")
+    coef = _workspace(5 * c * 4, device, slot=2)
+    ws = _workspace(_lib.load().lf_bn_workspace(c), device)
+    if tile_sums is not None:
+        tp, tiles = tile_sums
+        _lib.call("lf_bn_bwd_sums_tiles_f32", tp.data_ptr(), tiles, stats[0].data_ptr(), stats[1].data_ptr(),
+                  stats[2].data_ptr(), stats[3].data_ptr(), gamma.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                  coef.data_ptr(), n, c, hw, ws.data_ptr(), ws.numel(), _stream())
+    else:
+        _lib.call("lf_bn_bwd_sums_f32", _ptr(g), _ptr(alpha_nc), _ptr(add_nc), _ptr(y), stats[0].data_ptr(),
+                  stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), 1 if relu else 0, gamma.data_ptr(),
+                  dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), _ptr(plane_g), _ptr(plane_m), n, c, hw,
+                  ws.data_ptr(), ws.numel(), _stream())
+    return coef, ws
+
+
 def conv2d(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, in_scale=None, in_shift=None,
            in_relu: bool = False, out: Optional[torch.Tensor] = None,
            accumulate: bool = False, wino_u: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -112,19 +190,10 @@ def conv2d(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, in_scale=
     _chk(x, _F32, "conv2d.x", 4)
     n, cin, h, w = x.shape
     cout, w_ptr, u_ptr = _conv_weights("conv2d", x, w_iko, ksize, wino_u)
-    for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift")):
-        if t is not None:
-            _chk(t, _F32, f"conv2d.{nm}", 1)
-            if t.shape[0] != cin:
-                raise ValueError(f"conv2d.{nm}: expected [{cin}]")
-    if out is None:
-        if accumulate:
-            raise ValueError("conv2d: accumulate needs an output tensor")
-        out = torch.empty((n, cout, h, w), dtype=_F32, device=x.device)
-    else:
-        _chk(out, _F32, "conv2d.out", 4)
-        if tuple(out.shape) != (n, cout, h, w):
-            raise ValueError("conv2d.out: shape mismatch")
+    _prologue("conv2d", in_scale, in_shift, cin)
+    if out is None and accumulate:
+        raise ValueError("conv2d: accumulate needs an output tensor")
+    out = _act_out("conv2d", out, (n, cout, h, w), (_F32,), _F32, x.device)
     _lib.call("lf_conv2d_f32", x.data_ptr(), w_ptr, out.data_ptr(), n, cin, h, w, cout,
               ksize, _ptr(in_scale), _ptr(in_shift), 1 if in_relu else 0, 1 if accumulate else 0,
               _stream(), u_ptr)
@@ -151,29 +220,13 @@ def conv2d_bf16(x: torch.Tensor, wprep: torch.Tensor, cout: int, ksize: int, in_
     """conv2d with bf16 operands / fp32 accumulation (inference).  x: fp32 or bf16 NCHW; the result
     is fp32 or bf16 NCHW (`out_dtype`, or the dtype of `out`); wprep from conv2d_bf16_weights.
     out_scale / out_shift [Cout] (+ out_relu): epilogue on the accumulators (folded BatchNorm)."""
-    if x.dtype not in (_F32, torch.bfloat16):
-        raise TypeError(f"conv2d_bf16.x: expected float32 or bfloat16, got {x.dtype}")
-    _chk(x, x.dtype, "conv2d_bf16.x", 4)
+    xb = _act_in("conv2d_bf16", x)
     n, cin, h, w = x.shape
-    if wprep.dtype != torch.int16 or wprep.numel() != ((cin + 15) // 16) * ksize * ksize * cout * 16:
-        raise ValueError("conv2d_bf16.wprep: not the packed weights of this convolution")
-    for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift")):
-        if t is not None:
-            _chk(t, _F32, f"conv2d_bf16.{nm}", 1)
-            if t.shape[0] != cin:
-                raise ValueError(f"conv2d_bf16.{nm}: expected [{cin}]")
-    if out is None:
-        if out_dtype not in (_F32, torch.bfloat16):
-            raise TypeError("conv2d_bf16.out_dtype: float32 or bfloat16")
-        out = torch.empty((n, cout, h, w), dtype=out_dtype, device=x.device)
-    else:
-        if out.dtype not in (_F32, torch.bfloat16):
-            raise TypeError("conv2d_bf16.out: float32 or bfloat16")
-        _chk(out, out.dtype, "conv2d_bf16.out", 4)
-        if tuple(out.shape) != (n, cout, h, w):
-            raise ValueError("conv2d_bf16.out: shape mismatch")
-    _lib.call("lf_conv2d_bf16_act", x.data_ptr(), 1 if x.dtype == torch.bfloat16 else 0, wprep.data_ptr(),
-              out.data_ptr(), 1 if out.dtype == torch.bfloat16 else 0, n, cin, h, w, cout, ksize,
+    _packed_weights("conv2d_bf16", wprep, cin, cout, ksize)
+    _prologue("conv2d_bf16", in_scale, in_shift, cin)
+    out = _act_out("conv2d_bf16", out, (n, cout, h, w), (_F32, _BF16), out_dtype, x.device)
+    _lib.call("lf_conv2d_bf16_act", x.data_ptr(), 1 if xb else 0, wprep.data_ptr(),
+              out.data_ptr(), 1 if out.dtype == _BF16 else 0, n, cin, h, w, cout, ksize,
               _ptr(in_scale), _ptr(in_shift), 1 if in_relu else 0, _ptr(out_scale), _ptr(out_shift),
               1 if out_relu else 0, _stream())
     return out
@@ -185,17 +238,14 @@ def conv2d_bf16_mean(x: torch.Tensor, wprep: torch.Tensor, cout: int, ksize: int
     """conv2d_bf16 with bf16 output AND the per-image channel means of the stored activation, taken in the
     convolution's epilogue (inference: a block's second convolution + the squeeze of its SE gate in one pass).
     x: fp32 or bf16 NCHW; out: bf16 [N,Cout,H,W]; means: fp32 [N,Cout].  Returns (out, means)."""
-    if x.dtype not in (_F32, torch.bfloat16):
-        raise TypeError(f"conv2d_bf16_mean.x: expected float32 or bfloat16, got {x.dtype}")
-    _chk(x, x.dtype, "conv2d_bf16_mean.x", 4)
+    xb = 1 if _act_in("conv2d_bf16_mean", x) else 0
     n, cin, h, w = x.shape
-    if wprep.dtype != torch.int16 or wprep.numel() != ((cin + 15) // 16) * ksize * ksize * cout * 16:
-        raise ValueError("conv2d_bf16_mean.wprep: not the packed weights of this convolution")
-    _chk(out, torch.bfloat16, "conv2d_bf16_mean.out", 4)
+    _packed_weights("conv2d_bf16_mean", wprep, cin, cout, ksize)
+    _prologue("conv2d_bf16_mean", in_scale, in_shift, cin)
+    _act_out("conv2d_bf16_mean", out, (n, cout, h, w), (_BF16,), None, x.device)
     _chk(means, _F32, "conv2d_bf16_mean.means", 2)
-    if tuple(out.shape) != (n, cout, h, w) or tuple(means.shape) != (n, cout):
-        raise ValueError("conv2d_bf16_mean: out [N,Cout,H,W] / means [N,Cout] shape mismatch")
-    xb = 1 if x.dtype == torch.bfloat16 else 0
+    if tuple(means.shape) != (n, cout):
+        raise ValueError("conv2d_bf16_mean.means: expected [N,Cout]")
     ws = _workspace(int(_lib.load().lf_conv2d_bf16_act_mean_workspace(n, cin, h, w, cout, ksize, xb)), x.device, slot=1)
     _lib.call("lf_conv2d_bf16_act_mean", x.data_ptr(), xb, wprep.data_ptr(), out.data_ptr(), n, cin, h, w, cout, ksize,
               _ptr(in_scale), _ptr(in_shift), 1 if in_relu else 0, _ptr(out_scale), _ptr(out_shift),
@@ -206,9 +256,6 @@ def conv2d_bf16_mean(x: torch.Tensor, wprep: torch.Tensor, cout: int, ksize: int
 # ---------------------------------------------------------------------------
 # mixed-precision training step: bf16 storage, fp32 arithmetic (lf_*_bf16 / *_train_bf16)
 # ---------------------------------------------------------------------------
-_BF16 = torch.bfloat16
-
-
 def conv2d_bf16_dgrad_weights(w_iko: torch.Tensor, ksize: int) -> torch.Tensor:
     """Packed bf16 weights of the input-gradient convolution of a conv with fp32 IKO weights w."""
     return conv2d_bf16_weights(conv2d_dgrad_weights(w_iko, ksize), ksize)
@@ -221,20 +268,11 @@ def conv2d_bf16_train(x: torch.Tensor, wprep: torch.Tensor, cout: int, ksize: in
     """Forward / input-gradient convolution of the bf16 training step: out (bf16 NCHW) = conv(x')
     (+ out when accumulate).  With stats=True returns (out, (tile_part, tiles)) — BatchNorm forward
     statistics about `pivot`, or (mask_y given) the backward sums of the BatchNorm out feeds."""
-    if x.dtype not in (_F32, _BF16):
-        raise TypeError(f"conv2d_bf16_train.x: expected float32 or bfloat16, got {x.dtype}")
-    _chk(x, x.dtype, "conv2d_bf16_train.x", 4)
-    _chk(out, _BF16, "conv2d_bf16_train.out", 4)
+    xb = 1 if _act_in("conv2d_bf16_train", x) else 0
     n, cin, h, w = x.shape
-    if wprep.dtype != torch.int16 or wprep.numel() != ((cin + 15) // 16) * ksize * ksize * cout * 16:
-        raise ValueError("conv2d_bf16_train.wprep: not the packed weights of this convolution")
-    if tuple(out.shape) != (n, cout, h, w):
-        raise ValueError("conv2d_bf16_train.out: shape mismatch")
-    for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift")):
-        if t is not None:
-            _chk(t, _F32, f"conv2d_bf16_train.{nm}", 1)
-            if t.shape[0] != cin:
-                raise ValueError(f"conv2d_bf16_train.{nm}: expected [{cin}]")
+    _packed_weights("conv2d_bf16_train", wprep, cin, cout, ksize)
+    _act_out("conv2d_bf16_train", out, (n, cout, h, w), (_BF16,), None, x.device)
+    _prologue("conv2d_bf16_train", in_scale, in_shift, cin)
     tp, tiles = None, 0
     if mask_y is not None:
         _chk(mask_y, _BF16, "conv2d_bf16_train.mask_y", 4)
@@ -242,9 +280,9 @@ def conv2d_bf16_train(x: torch.Tensor, wprep: torch.Tensor, cout: int, ksize: in
             raise ValueError("conv2d_bf16_train: mask shape mismatch")
         stats = True
     if stats:
-        tiles = int(_lib.load().lf_conv2d_bf16_stats_tiles(n, cin, h, w, cout, ksize, 1 if x.dtype == _BF16 else 0))
-        tp = _workspace(tiles * cout * 8, x.device, slot=1)
-    _lib.call("lf_conv2d_bf16_train", x.data_ptr(), 1 if x.dtype == _BF16 else 0, wprep.data_ptr(),
+        tiles = int(_lib.load().lf_conv2d_bf16_stats_tiles(n, cin, h, w, cout, ksize, xb))
+        tp = _tile_part(x, tiles, cout)
+    _lib.call("lf_conv2d_bf16_train", x.data_ptr(), xb, wprep.data_ptr(),
               out.data_ptr(), n, cin, h, w, cout, ksize, _ptr(in_scale), _ptr(in_shift),
               1 if in_relu else 0, 1 if accumulate else 0, _ptr(tp), tp.numel() if tp is not None else 0,
               _ptr(pivot), _ptr(mask_y), _ptr(mask_scale), _ptr(mask_shift), 1 if mask_relu else 0,
@@ -260,12 +298,33 @@ def conv2d_bn_stats_bf16(x, wprep, cout: int, ksize: int, gamma, beta, mmean, mv
     n, _cin, h, w = x.shape
     out, (tp, tiles) = conv2d_bf16_train(x, wprep, cout, ksize, out, in_scale, in_shift, in_relu,
                                          stats=True, pivot=mmean)
-    ws = _workspace(_lib.load().lf_bn_workspace(cout), x.device)
-    _lib.call("lf_bn_train_stats_tiles_f32", tp.data_ptr(), tiles, n, cout, h * w, gamma.data_ptr(),
-              beta.data_ptr(), mmean.data_ptr(), mvar.data_ptr(), float(momentum), float(eps),
-              stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(),
-              ws.data_ptr(), ws.numel(), _stream())
+    _bn_stats_from_tiles(tp, tiles, n, cout, h * w, gamma, beta, mmean, mvar, stats, momentum, eps, x.device)
     return out
+
+
+def _bn_bwd_wgrad_checks(who: str, act, x, g, y_bn, dy_out, dw_out, ksize, in_scale, in_shift, alpha_nc, add_nc,
+                         plane_g, plane_m):
+    """What bn_bwd_wgrad (act f32) and bn_bwd_wgrad_bf16 (act bf16) check next to x: g, y_bn, dy_out [N,Cout,H,W]
+    of dtype `act`, dw_out f32 [Cin,k*k,Cout], the prologue, plane sums [N,Cout,2], alpha/add [N,Cout].  Returns
+    (n, cin, h, w, cout)."""
+    _chk(g, act, f"{who}.g", 4)
+    _chk(y_bn, act, f"{who}.y", 4)
+    if dy_out is not None:
+        _chk(dy_out, act, f"{who}.dy_out", 4)
+    _chk(dw_out, _F32, f"{who}.dw_out", 3)
+    n, cin, h, w = x.shape
+    cout = g.shape[1]
+    if g.shape != y_bn.shape or (dy_out is not None and dy_out.shape != g.shape) or g.shape[0] != n \
+            or tuple(g.shape[2:]) != (h, w) or tuple(dw_out.shape) != (cin, ksize * ksize, cout):
+        raise ValueError(f"{who}: shape mismatch")
+    _prologue(who, in_scale, in_shift, cin)
+    for t in (plane_g, plane_m):
+        if t is not None and tuple(t.shape) != (n, cout, 2):
+            raise ValueError(f"{who}: plane sums must be [N,C,2]")
+    for t in (alpha_nc, add_nc):
+        if t is not None and tuple(t.shape) != (n, cout):
+            raise ValueError(f"{who}: alpha/add must be [N,C]")
+    return n, cin, h, w, cout
 
 
 def bn_bwd_wgrad_bf16(x: torch.Tensor, g: torch.Tensor, y_bn: torch.Tensor, stats: torch.Tensor, gamma,
@@ -275,39 +334,13 @@ def bn_bwd_wgrad_bf16(x: torch.Tensor, g: torch.Tensor, y_bn: torch.Tensor, stat
     """bn_bwd_wgrad on bf16 tensors: the BatchNorm-backward sums come from per-plane sums
     (block_tail_bwd / gap) or per-tile sums (conv2d_bf16_train's epilogue) — never
     from another pass over g and y — and dY = BN'(g) is formed inside the weight-gradient kernel."""
-    if x.dtype not in (_F32, _BF16):
-        raise TypeError("bn_bwd_wgrad_bf16.x: float32 (stem) or bfloat16")
-    _chk(x, x.dtype, "bn_bwd_wgrad_bf16.x", 4)
-    _chk(g, _BF16, "bn_bwd_wgrad_bf16.g", 4)
-    _chk(y_bn, _BF16, "bn_bwd_wgrad_bf16.y", 4)
-    _chk(dw_out, _F32, "bn_bwd_wgrad_bf16.dw_out", 3)
-    if dy_out is not None:
-        _chk(dy_out, _BF16, "bn_bwd_wgrad_bf16.dy_out", 4)
-    n, cin, h, w = x.shape
-    cout = g.shape[1]
-    if g.shape != y_bn.shape or (dy_out is not None and dy_out.shape != g.shape) or g.shape[0] != n \
-            or tuple(g.shape[2:]) != (h, w) or tuple(dw_out.shape) != (cin, ksize * ksize, cout):
-        raise ValueError("bn_bwd_wgrad_bf16: shape mismatch")
-    if (tile_sums is None) == (plane_g is None):
-        raise ValueError("bn_bwd_wgrad_bf16: exactly one of tile_sums / plane_g must be given")
-    lib = _lib.load()
-    coef = _workspace(5 * cout * 4, x.device, slot=2)
-    ws = _workspace(lib.lf_bn_workspace(cout), x.device)
-    if tile_sums is not None:
-        if alpha_nc is not None or add_nc is not None:
-            raise ValueError("bn_bwd_wgrad_bf16: tile_sums excludes alpha/add")
-        tp, tiles = tile_sums
-        _lib.call("lf_bn_bwd_sums_tiles_f32", tp.data_ptr(), tiles, stats[0].data_ptr(),
-                  stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), gamma.data_ptr(),
-                  dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), n, cout, h * w,
-                  ws.data_ptr(), ws.numel(), _stream())
-    else:
-        _lib.call("lf_bn_bwd_sums_f32", None, _ptr(alpha_nc), _ptr(add_nc), None,
-                  stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(),
-                  1 if relu else 0, gamma.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                  coef.data_ptr(), _ptr(plane_g), _ptr(plane_m), n, cout, h * w, ws.data_ptr(),
-                  ws.numel(), _stream())
-    ws = _workspace(lib.lf_conv2d_wgrad_bf16_workspace(n, cin, h, w, cout, ksize), x.device)
+    who = "bn_bwd_wgrad_bf16"
+    _act_in(who, x)   # float32 for the stem
+    n, cin, h, w, cout = _bn_bwd_wgrad_checks(who, _BF16, x, g, y_bn, dy_out, dw_out, ksize, in_scale, in_shift,
+                                              alpha_nc, add_nc, plane_g, plane_m)
+    coef, _ = _bn_bwd_coef(who, stats, gamma, dgamma, dbeta, relu, n, cout, h * w, x.device, alpha_nc=alpha_nc,
+                           add_nc=add_nc, plane_g=plane_g, plane_m=plane_m, tile_sums=tile_sums)
+    ws = _workspace(_lib.load().lf_conv2d_wgrad_bf16_workspace(n, cin, h, w, cout, ksize), x.device)
     _lib.call("lf_conv2d_wgrad_bf16", x.data_ptr(), g.data_ptr(), y_bn.data_ptr(), _ptr(alpha_nc),
               _ptr(add_nc), coef.data_ptr(), 1 if relu else 0, _ptr(dy_out), dw_out.data_ptr(), n, cin,
               h, w, cout, ksize, _ptr(in_scale), _ptr(in_shift), 1 if in_relu else 0, ws.data_ptr(),
@@ -321,6 +354,7 @@ def conv2d_wgrad_bf16(x: torch.Tensor, dy: torch.Tensor, ksize: int, in_scale=No
     _chk(dy, _BF16, "wgrad_bf16.dy", 4)
     n, cin, h, w = x.shape
     cout = dy.shape[1]
+    _prologue("wgrad_bf16", in_scale, in_shift, cin)
     if out is None:
         out = torch.empty((cin, ksize * ksize, cout), dtype=_F32, device=x.device)
     ws = _workspace(_lib.load().lf_conv2d_wgrad_bf16_workspace(n, cin, h, w, cout, ksize), x.device)
@@ -350,11 +384,7 @@ def conv2d_bn_stats(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, 
     _chk(x, _F32, "conv2d_bn_stats.x", 4)
     n, cin, h, w = x.shape
     cout, w_ptr, u_ptr = _conv_weights("conv2d_bn_stats", x, w_iko, ksize, wino_u)
-    for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift")):
-        if t is not None:
-            _chk(t, _F32, f"conv2d_bn_stats.{nm}", 1)
-            if t.shape[0] != cin:
-                raise ValueError(f"conv2d_bn_stats.{nm}: expected [{cin}]")
+    _prologue("conv2d_bn_stats", in_scale, in_shift, cin)
     for t in (gamma, beta, mmean, mvar):
         _chk(t, _F32, "conv2d_bn_stats.param", 1)
         if t.shape[0] != cout:
@@ -362,23 +392,13 @@ def conv2d_bn_stats(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, 
     _chk(stats, _F32, "conv2d_bn_stats.stats", 2)
     if tuple(stats.shape) != (4, cout):
         raise ValueError("conv2d_bn_stats.stats: expected [4,Cout]")
-    if out is None:
-        out = torch.empty((n, cout, h, w), dtype=_F32, device=x.device)
-    else:
-        _chk(out, _F32, "conv2d_bn_stats.out", 4)
-        if tuple(out.shape) != (n, cout, h, w):
-            raise ValueError("conv2d_bn_stats.out: shape mismatch")
-    lib = _lib.load()
-    tiles = lib.lf_conv2d_stats_tiles(n, cin, h, w, cout, ksize)
-    tp = _workspace(tiles * cout * 8, x.device, slot=1)
+    out = _act_out("conv2d_bn_stats", out, (n, cout, h, w), (_F32,), _F32, x.device)
+    tiles = _lib.load().lf_conv2d_stats_tiles(n, cin, h, w, cout, ksize)
+    tp = _tile_part(x, tiles, cout)
     _lib.call("lf_conv2d_stats_f32", x.data_ptr(), w_ptr, out.data_ptr(), n, cin, h, w,
               cout, ksize, _ptr(in_scale), _ptr(in_shift), 1 if in_relu else 0, mmean.data_ptr(),
               tp.data_ptr(), tp.numel(), _stream(), u_ptr)
-    ws = _workspace(lib.lf_bn_workspace(cout), x.device)
-    _lib.call("lf_bn_train_stats_tiles_f32", tp.data_ptr(), tiles, n, cout, h * w, gamma.data_ptr(),
-              beta.data_ptr(), mmean.data_ptr(), mvar.data_ptr(), float(momentum), float(eps),
-              stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(),
-              ws.data_ptr(), ws.numel(), _stream())
+    _bn_stats_from_tiles(tp, tiles, n, cout, h * w, gamma, beta, mmean, mvar, stats, momentum, eps, x.device)
     return out
 
 
@@ -391,13 +411,13 @@ def conv2d_bnbwd(x: torch.Tensor, w_iko: Optional[torch.Tensor], ksize: int, mas
     bn_bwd_wgrad."""
     _chk(x, _F32, "conv2d_bnbwd.x", 4)
     _chk(mask_y, _F32, "conv2d_bnbwd.mask_y", 4)
-    _chk(out, _F32, "conv2d_bnbwd.out", 4)
     n, cin, h, w = x.shape
     cout, w_ptr, u_ptr = _conv_weights("conv2d_bnbwd", x, w_iko, ksize, wino_u)
-    if tuple(out.shape) != (n, cout, h, w) or mask_y.shape != out.shape or tuple(stats.shape) != (4, cout):
+    _act_out("conv2d_bnbwd", out, (n, cout, h, w), (_F32,), None, x.device)
+    if mask_y.shape != out.shape or tuple(stats.shape) != (4, cout):
         raise ValueError("conv2d_bnbwd: shape mismatch")
     tiles = _lib.load().lf_conv2d_stats_tiles(n, cin, h, w, cout, ksize)
-    tp = _workspace(tiles * cout * 8, x.device, slot=1)
+    tp = _tile_part(x, tiles, cout)
     _lib.call("lf_conv2d_bnbwd_f32", x.data_ptr(), w_ptr, out.data_ptr(), n, cin, h, w,
               cout, ksize, 1 if accumulate else 0, mask_y.data_ptr(), stats[2].data_ptr(),
               stats[3].data_ptr(), 1 if relu else 0, tp.data_ptr(), tp.numel(), _stream(), u_ptr)
@@ -426,13 +446,10 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, in_scale=None, i
     if dy.shape[0] != n or tuple(dy.shape[2:]) != (h, w):
         raise ValueError("wgrad: x and dy must share N,H,W")
     cout = dy.shape[1]
+    _prologue("wgrad", in_scale, in_shift, cin)
     if out is None:
-        out = torch.empty((cin, ksize * ksize, cout), dtype=_F32, device=x.device)
         beta = 0.0
-    else:
-        _chk(out, _F32, "wgrad.out", 3)
-        if tuple(out.shape) != (cin, ksize * ksize, cout):
-            raise ValueError("wgrad.out: shape mismatch")
+    out = _act_out("wgrad", out, (cin, ksize * ksize, cout), (_F32,), _F32, x.device)
     nbytes = _lib.load().lf_conv2d_wgrad_workspace(n, cin, h, w, cout, ksize)
     ws = _workspace(nbytes, x.device)
     _lib.call("lf_conv2d_wgrad_f32", x.data_ptr(), dy.data_ptr(), n, cin, h, w, cout, ksize,
@@ -452,47 +469,18 @@ def bn_bwd_wgrad(x: torch.Tensor, g: torch.Tensor, y_bn: torch.Tensor, stats: to
     g and y_bn (and written to dy_out, when given, for the input-gradient convolution); dgamma / dbeta /
     dw_out are filled.  Falls back to the two-kernel route for shapes the fused kernel does not
     take (same results up to rounding)."""
-    _chk(x, _F32, "bn_bwd_wgrad.x", 4)
-    _chk(g, _F32, "bn_bwd_wgrad.g", 4)
-    _chk(y_bn, _F32, "bn_bwd_wgrad.y", 4)
-    if dy_out is not None:
-        _chk(dy_out, _F32, "bn_bwd_wgrad.dy_out", 4)
-    _chk(dw_out, _F32, "bn_bwd_wgrad.dw_out", 3)
-    n, cin, h, w = x.shape
-    cout = g.shape[1]
-    if g.shape != y_bn.shape or (dy_out is not None and dy_out.shape != g.shape) or g.shape[0] != n \
-            or tuple(g.shape[2:]) != (h, w):
-        raise ValueError("bn_bwd_wgrad: shape mismatch")
-    if tuple(dw_out.shape) != (cin, ksize * ksize, cout):
-        raise ValueError("bn_bwd_wgrad.dw_out: shape mismatch")
+    who = "bn_bwd_wgrad"
+    _chk(x, _F32, f"{who}.x", 4)
+    n, cin, h, w, cout = _bn_bwd_wgrad_checks(who, _F32, x, g, y_bn, dy_out, dw_out, ksize, in_scale, in_shift,
+                                              alpha_nc, add_nc, plane_g, plane_m)
     lib = _lib.load()
     if _NO_FUSED_BN_WGRAD or not lib.lf_conv2d_wgrad_bn_supported(n, cin, h, w, cout, ksize):
         dy = bn_bwd(g, y_bn, stats, gamma, dgamma, dbeta, relu, alpha_nc=alpha_nc, add_nc=add_nc,
                     out=dy_out, plane_g=plane_g, plane_m=plane_m, tile_sums=tile_sums)
         conv2d_wgrad(x, dy, ksize, in_scale, in_shift, in_relu, out=dw_out)
         return dy_out
-    for t in (plane_g, plane_m):
-        if t is not None and tuple(t.shape) != (n, cout, 2):
-            raise ValueError("bn_bwd_wgrad: plane sums must be [N,C,2]")
-    for t in (alpha_nc, add_nc):
-        if t is not None and tuple(t.shape) != (n, cout):
-            raise ValueError("bn_bwd_wgrad: alpha/add must be [N,C]")
-    coef = _workspace(5 * cout * 4, x.device, slot=2)
-    ws = _workspace(lib.lf_bn_workspace(cout), x.device)
-    if tile_sums is not None:
-        if alpha_nc is not None or add_nc is not None or plane_g is not None:
-            raise ValueError("bn_bwd_wgrad: tile_sums excludes alpha/add/plane sums")
-        tp, tiles = tile_sums
-        _lib.call("lf_bn_bwd_sums_tiles_f32", tp.data_ptr(), tiles, stats[0].data_ptr(),
-                  stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), gamma.data_ptr(),
-                  dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), n, cout, h * w,
-                  ws.data_ptr(), ws.numel(), _stream())
-    else:
-        _lib.call("lf_bn_bwd_sums_f32", g.data_ptr(), _ptr(alpha_nc), _ptr(add_nc), y_bn.data_ptr(),
-                  stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(),
-                  1 if relu else 0, gamma.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                  coef.data_ptr(), _ptr(plane_g), _ptr(plane_m), n, cout, h * w, ws.data_ptr(),
-                  ws.numel(), _stream())
+    coef, _ = _bn_bwd_coef(who, stats, gamma, dgamma, dbeta, relu, n, cout, h * w, x.device, g, y_bn, alpha_nc,
+                           add_nc, plane_g, plane_m, tile_sums)
     ws = _workspace(lib.lf_conv2d_wgrad_workspace(n, cin, h, w, cout, ksize), x.device)
     _lib.call("lf_conv2d_wgrad_bn_f32", x.data_ptr(), g.data_ptr(), y_bn.data_ptr(), _ptr(alpha_nc),
               _ptr(add_nc), coef.data_ptr(), 1 if relu else 0, _ptr(dy_out), n, cin, h, w, cout,
@@ -589,18 +577,12 @@ def bn_bwd(g, y, stats, gamma, dgamma, dbeta, relu: bool, alpha_nc=None, add_nc=
                 raise ValueError("bn_bwd: alpha/add must be [N,C]")
     if out is None:
         out = torch.empty_like(y)
-    ws = _workspace(_lib.load().lf_bn_workspace(c), y.device)
-    have = 0
-    if tile_sums is not None:
-        if alpha_nc is not None or add_nc is not None or plane_g is not None:
-            raise ValueError("bn_bwd: tile_sums excludes alpha/add/plane sums")
-        tp, tiles = tile_sums
-        coef = _workspace(5 * c * 4, y.device, slot=2)
-        _lib.call("lf_bn_bwd_sums_tiles_f32", tp.data_ptr(), tiles, stats[0].data_ptr(),
-                  stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), gamma.data_ptr(),
-                  dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), n, c, h * w, ws.data_ptr(),
-                  ws.numel(), _stream())
-        have = 1
+    have = 1 if tile_sums is not None else 0
+    if have:   # dgamma / dbeta come from the tiles; only the apply pass runs below
+        ws = _bn_bwd_coef("bn_bwd", stats, gamma, dgamma, dbeta, relu, n, c, h * w, y.device, alpha_nc=alpha_nc,
+                          add_nc=add_nc, plane_g=plane_g, tile_sums=tile_sums)[1]
+    else:
+        ws = _workspace(_lib.load().lf_bn_workspace(c), y.device)
     _lib.call("lf_bn_bwd_f32", g.data_ptr(), _ptr(alpha_nc), _ptr(add_nc), y.data_ptr(),
               stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(),
               1 if relu else 0, gamma.data_ptr(), out.data_ptr(), dgamma.data_ptr(),

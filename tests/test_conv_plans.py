@@ -170,6 +170,14 @@ def test_plan_queries_match_the_launch_tables():
     assert lib.lf_conv2d_plan(0, 1, 1, 1, 1, 3, None) < 0
 
 
+@pytest.mark.parametrize("cin,cout,k", [(3, 32, 3), (16, 32, 1), (17, 64, 3), (32, 32, 3), (256, 256, 3)])
+def test_packed_weight_size_matches_the_library(cin, cout, k):
+    """The launchers check packed bf16 weights against nn._bf16_weight_elems (no library call per launch): it is
+    lf_conv2d_bf16_weight_elems, where rounding Cin up to 16 bites and where it does not."""
+    from leaffliction_amd import nn
+    assert nn._bf16_weight_elems(cin, cout, k) == _lib.load().lf_conv2d_bf16_weight_elems(cin, cout, k)
+
+
 def test_benchmark_conv_paths_are_tested():
     have = {key(s) for s in signatures_under_test()}
     missing = {}
