@@ -18,8 +18,81 @@ constexpr int kBlock = 256;
 __device__ __forceinline__ unsigned byte_of(unsigned w, int i) { return (w >> (8 * i)) & 0xffu; }
 
 // ---------------------------------------------------------------------------
+// interleaved RGB bytes, walked in 16-byte chunks
+// ---------------------------------------------------------------------------
+// Channel of byte 0 of chunk q of an image that starts on a chunk: 16 q % 3 = q % 3.  With the chunks starting
+// `head` bytes into the image (hc = head % 3): (head + 16 q) % 3 = (hc + q) % 3.
+__device__ __forceinline__ unsigned chunk_channel(size_t q) { return (unsigned)(q % 3); }
+__device__ __forceinline__ unsigned chunk_channel(unsigned hc, size_t q) { return (hc + chunk_channel(q)) % 3; }
+
+// f(channel, byte, j) for the 16 bytes of a chunk whose byte 0 belongs to channel c0.
+template <typename F>
+__device__ __forceinline__ void each_byte16(const lf::u32x4 v, unsigned c0, F f) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        unsigned c = c0 + (j % 3);
+        c = c >= 3 ? c - 3 : c;
+        f(c, byte_of(w[j >> 2], j & 3), j);
+    }
+}
+
+// An image's bytes as a scalar head up to 16-byte alignment, nchunks aligned chunks at mid, and a scalar tail.
+struct AlignedSpan {
+    const uint8_t* base;
+    const lf::u32x4* mid;
+    size_t nbytes, head, nchunks;
+    unsigned hc;  // head % 3: the channel of mid's first byte
+};
+__device__ __forceinline__ AlignedSpan aligned_span(const uint8_t* base, size_t nbytes) {
+    AlignedSpan sp;
+    sp.base = base;
+    sp.nbytes = nbytes;
+    sp.head = (16 - (reinterpret_cast<size_t>(base) & 15)) & 15;
+    if (sp.head > nbytes) sp.head = nbytes;
+    sp.nchunks = (nbytes - sp.head) / 16;
+    sp.mid = reinterpret_cast<const lf::u32x4*>(base + sp.head);
+    sp.hc = (unsigned)(sp.head % 3);
+    return sp;
+}
+
+// sink(channel, byte) for every byte of the chunks first, first + stride, ... of the image at `base` and, with `ends`,
+// of its head and tail (dealt over the workgroup's threads).  Four 16-byte loads in flight per thread: one load per
+// trip leaves the kernel latency-bound (32 KB in flight per CU ~ 4.2 TB/s).  The span is taken here, from the kernel's
+// own pointer expression: handed in as a struct, its pointers lose their address space and the loads become flat ones.
+template <bool NT, typename Sink>
+__device__ __forceinline__ void walk_span(const uint8_t* base, size_t nbytes, size_t first, size_t stride, bool ends,
+                                          Sink sink) {
+    const AlignedSpan sp = aligned_span(base, nbytes);
+    auto chunk = [hc = sp.hc, &sink](const lf::u32x4 v, size_t q) {
+        each_byte16(v, chunk_channel(hc, q), [&](unsigned c, unsigned byte, int) { sink(c, byte); });
+    };
+    size_t q = first;
+    for (; q + 3 * stride < sp.nchunks; q += 4 * stride) {
+        const lf::u32x4 v0 = lf::ldg<NT>(sp.mid + q), v1 = lf::ldg<NT>(sp.mid + q + stride),
+                        v2 = lf::ldg<NT>(sp.mid + q + 2 * stride), v3 = lf::ldg<NT>(sp.mid + q + 3 * stride);
+        chunk(v0, q);
+        chunk(v1, q + stride);
+        chunk(v2, q + 2 * stride);
+        chunk(v3, q + 3 * stride);
+    }
+    for (; q < sp.nchunks; q += stride) chunk(lf::ldg<NT>(sp.mid + q), q); if (ends) {
+        const size_t tail0 = sp.head + sp.nchunks * 16;
+        for (size_t i = threadIdx.x; i < sp.head; i += kBlock) sink((unsigned)(i % 3), sp.base[i]);
+        for (size_t i = tail0 + threadIdx.x; i < sp.nbytes; i += kBlock) sink((unsigned)(i % 3), sp.base[i]);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // pack: u8 HWC -> f32 NCHW, x/255 (+ optional per-channel normalisation)
 // ---------------------------------------------------------------------------
+// The value of one byte; every division and the subtraction round on their own.
+template <bool NORM>
+__device__ __forceinline__ float pack_value(float byte, float mean, float denom) {
+    const float v = __fdiv_rn(byte, 255.0f);
+    return NORM ? __fdiv_rn(__fsub_rn(v, mean), denom) : v;
+}
+
 // One thread = 4 pixels = 12 input bytes (3 dwords) -> one float4 per plane.
 template <bool NORM, bool NT>
 __global__ __launch_bounds__(kBlock) void pack_kernel(const uint8_t* __restrict__ in,
@@ -45,16 +118,9 @@ __global__ __launch_bounds__(kBlock) void pack_kernel(const uint8_t* __restrict_
         float* pb = reinterpret_cast<float*>(&o2);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            float vr = __fdiv_rn(r[i], 255.0f), vg = __fdiv_rn(gch[i], 255.0f),
-                  vb = __fdiv_rn(b[i], 255.0f);
-            if (NORM) {
-                vr = __fdiv_rn(__fsub_rn(vr, m0), d0);
-                vg = __fdiv_rn(__fsub_rn(vg, m1), d1);
-                vb = __fdiv_rn(__fsub_rn(vb, m2), d2);
-            }
-            pr[i] = vr;
-            pg[i] = vg;
-            pb[i] = vb;
+            pr[i] = pack_value<NORM>(r[i], m0, d0);
+            pg[i] = pack_value<NORM>(gch[i], m1, d1);
+            pb[i] = pack_value<NORM>(b[i], m2, d2);
         }
         lf::stg<NT>(reinterpret_cast<lf::f32x4*>(dst) + g, o0);
         lf::stg<NT>(reinterpret_cast<lf::f32x4*>(dst + hw) + g, o1);
@@ -75,11 +141,7 @@ __global__ __launch_bounds__(kBlock) void pack_scalar_kernel(const uint8_t* __re
     for (size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x; p < hw;
          p += (size_t)gridDim.x * kBlock) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v = __fdiv_rn((float)src[3 * p + c], 255.0f);
-            if (NORM) v = __fdiv_rn(__fsub_rn(v, m[c]), d[c]);
-            dst[(size_t)c * hw + p] = v;
-        }
+        for (int c = 0; c < 3; ++c) dst[(size_t)c * hw + p] = pack_value<NORM>((float)src[3 * p + c], m[c], d[c]);
     }
 }
 
@@ -88,7 +150,8 @@ __global__ __launch_bounds__(kBlock) void pack_scalar_kernel(const uint8_t* __re
 // ---------------------------------------------------------------------------
 // grid = (splits, n).  Each wave owns a private 3x256 LDS histogram so that the
 // 64 lanes of one ds_add only collide with each other; the four copies are summed
-// and flushed with one global atomic per bin per workgroup.
+// and flushed with one global atomic per bin per workgroup.  The image's chunks are dealt over
+// its workgroups; block 0 also counts the head and the tail.
 constexpr int kHistCopies = kBlock / 64;
 
 template <bool NT>
@@ -99,45 +162,9 @@ __global__ __launch_bounds__(kBlock) void hist_kernel(const uint8_t* __restrict_
     for (int i = threadIdx.x; i < kHistCopies * 768; i += kBlock) (&lh[0][0])[i] = 0;
     __syncthreads();
     unsigned* my = lh[threadIdx.x >> 6];
-    const uint8_t* base = in + (size_t)n * nbytes;
-    // 16-byte aligned middle part [a0, a1) of this image's bytes; head/tail are scalar.
-    const size_t addr = reinterpret_cast<size_t>(base);
-    size_t head = (16 - (addr & 15)) & 15;
-    if (head > nbytes) head = nbytes;
-    const size_t nchunks = (nbytes - head) / 16;
-    const lf::u32x4* mid = reinterpret_cast<const lf::u32x4*>(base + head);
-    const unsigned hc = (unsigned)(head % 3);
-    auto tally = [&](const lf::u32x4 v, size_t q) {
-        // channel of byte 0 of this chunk: (head + 16 q) % 3 = (hc + q) % 3
-        const unsigned r = (hc + (unsigned)(q % 3)) % 3;
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            unsigned c = r + (j % 3);
-            c = c >= 3 ? c - 3 : c;
-            atomicAdd(&my[c * 256 + byte_of(w[j >> 2], j & 3)], 1u);
-        }
-    };
-    // four 16-byte loads in flight per thread: one load per trip leaves the kernel
-    // latency-bound (32 KB in flight per CU ~ 4.2 TB/s)
-    const size_t stride = (size_t)gridDim.x * kBlock;
-    size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    for (; q + 3 * stride < nchunks; q += 4 * stride) {
-        const lf::u32x4 v0 = lf::ldg<NT>(mid + q), v1 = lf::ldg<NT>(mid + q + stride),
-                        v2 = lf::ldg<NT>(mid + q + 2 * stride), v3 = lf::ldg<NT>(mid + q + 3 * stride);
-        tally(v0, q);
-        tally(v1, q + stride);
-        tally(v2, q + 2 * stride);
-        tally(v3, q + 3 * stride);
-    }
-    for (; q < nchunks; q += stride) tally(lf::ldg<NT>(mid + q), q);
-    if (blockIdx.x == 0) {
-        const size_t tail0 = head + nchunks * 16;
-        for (size_t i = threadIdx.x; i < head; i += kBlock)
-            atomicAdd(&my[(i % 3) * 256 + base[i]], 1u);
-        for (size_t i = tail0 + threadIdx.x; i < nbytes; i += kBlock)
-            atomicAdd(&my[(i % 3) * 256 + base[i]], 1u);
-    }
+    walk_span<NT>(in + (size_t)n * nbytes, nbytes, (size_t)blockIdx.x * kBlock + threadIdx.x,
+                  (size_t)gridDim.x * kBlock, blockIdx.x == 0,
+                  [&](unsigned c, unsigned byte) { atomicAdd(&my[c * 256 + byte], 1u); });
     __syncthreads();
     int32_t* gh = hist + (size_t)n * 768;
     for (int i = threadIdx.x; i < 768; i += kBlock) {
@@ -148,57 +175,30 @@ __global__ __launch_bounds__(kBlock) void hist_kernel(const uint8_t* __restrict_
     }
 }
 
-// One workgroup per image, ONE table per workgroup with 16 lane slots per bin: tab[bin][lane % 16].
+// ONE table per workgroup with 16 lane slots per bin: tab[bin][lane % 16].
 // The word a lane touches sits in bank 16*(bin & 1) + lane % 16, so the 64 lanes of a ds_add spread
 // over all 32 banks whatever the bytes are (two lanes per bank on average; equal bytes in
 // neighbouring lanes — flat leaf regions — land in different slots instead of serialising on one
 // word), where the per-wave 768-word histogram above takes ~3-4 LDS cycles per bank on uniform bytes
-// and more on flat images.  The image's 768 sums go out with plain stores (no global atomics).
+// and more on flat images.  A workgroup counts one image at a time between clear() and flush(), which
+// hold the barriers; the image's 768 sums go out with plain stores (no global atomics).
 constexpr int kHistSlots = 16;
+constexpr int kSlotTableWords = 768 * kHistSlots;
 
-template <bool NT>
-__global__ __launch_bounds__(kBlock) void hist_slot_kernel(const uint8_t* __restrict__ in,
-                                                           int32_t* __restrict__ hist, size_t nbytes, int n) {
-    __shared__ __attribute__((aligned(16))) unsigned tab[768 * kHistSlots];
-    const unsigned slot = threadIdx.x & (kHistSlots - 1);
-    for (int img = blockIdx.x; img < n; img += gridDim.x) {
-        for (int i = threadIdx.x; i < 768 * kHistSlots / 4; i += kBlock)
+struct SlotTable {
+    unsigned* tab;  // kSlotTableWords of LDS, 16-byte aligned
+    unsigned slot;
+    __device__ __forceinline__ explicit SlotTable(unsigned* lds) : tab(lds), slot(threadIdx.x & (kHistSlots - 1)) {}
+    __device__ __forceinline__ void clear() const {
+        for (int i = threadIdx.x; i < kSlotTableWords / 4; i += kBlock)
             reinterpret_cast<lf::u32x4*>(tab)[i] = lf::u32x4{0u, 0u, 0u, 0u};
         __syncthreads();
-        const uint8_t* base = in + (size_t)img * nbytes;
-        const size_t addr = reinterpret_cast<size_t>(base);
-        size_t head = (16 - (addr & 15)) & 15;
-        if (head > nbytes) head = nbytes;
-        const size_t nchunks = (nbytes - head) / 16;
-        const lf::u32x4* mid = reinterpret_cast<const lf::u32x4*>(base + head);
-        const unsigned hc = (unsigned)(head % 3);
-        auto tally = [&](const lf::u32x4 v, size_t q) {
-            const unsigned r = (hc + (unsigned)(q % 3)) % 3;   // channel of byte 0 of this chunk
-            const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                unsigned c = r + (j % 3);
-                c = c >= 3 ? c - 3 : c;
-                atomicAdd(&tab[(c * 256 + byte_of(w[j >> 2], j & 3)) * kHistSlots + slot], 1u);
-            }
-        };
-        size_t q = threadIdx.x;
-        for (; q + 3 * kBlock < nchunks; q += 4 * kBlock) {
-            const lf::u32x4 v0 = lf::ldg<NT>(mid + q), v1 = lf::ldg<NT>(mid + q + kBlock),
-                            v2 = lf::ldg<NT>(mid + q + 2 * kBlock), v3 = lf::ldg<NT>(mid + q + 3 * kBlock);
-            tally(v0, q);
-            tally(v1, q + kBlock);
-            tally(v2, q + 2 * kBlock);
-            tally(v3, q + 3 * kBlock);
-        }
-        for (; q < nchunks; q += kBlock) tally(lf::ldg<NT>(mid + q), q);
-        const size_t tail0 = head + nchunks * 16;
-        for (size_t i = threadIdx.x; i < head; i += kBlock)
-            atomicAdd(&tab[((i % 3) * 256 + base[i]) * kHistSlots + slot], 1u);
-        for (size_t i = tail0 + threadIdx.x; i < nbytes; i += kBlock)
-            atomicAdd(&tab[((i % 3) * 256 + base[i]) * kHistSlots + slot], 1u);
+    }
+    __device__ __forceinline__ void add(unsigned c, unsigned byte) const {
+        atomicAdd(&tab[(c * 256 + byte) * kHistSlots + slot], 1u);
+    }
+    __device__ __forceinline__ void flush(int32_t* gh) const {
         __syncthreads();
-        int32_t* gh = hist + (size_t)img * 768;
         for (int b = threadIdx.x; b < 768; b += kBlock) {
             unsigned sum = 0;
 #pragma unroll
@@ -209,6 +209,20 @@ __global__ __launch_bounds__(kBlock) void hist_slot_kernel(const uint8_t* __rest
             gh[b] = (int32_t)sum;
         }
         __syncthreads();
+    }
+};
+
+// One workgroup per image (grid-stride over the images).
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void hist_slot_kernel(const uint8_t* __restrict__ in,
+                                                           int32_t* __restrict__ hist, size_t nbytes, int n) {
+    __shared__ __attribute__((aligned(16))) unsigned lds[kSlotTableWords];
+    const SlotTable tab(lds);
+    for (int img = blockIdx.x; img < n; img += gridDim.x) {
+        tab.clear();
+        walk_span<NT>(in + (size_t)img * nbytes, nbytes, threadIdx.x, kBlock, true,
+                      [&](unsigned c, unsigned byte) { tab.add(c, byte); });
+        tab.flush(hist + (size_t)img * 768);
     }
 }
 
@@ -296,6 +310,13 @@ __global__ void autocontrast_lut_kernel(const int32_t* __restrict__ hist,
 // ---------------------------------------------------------------------------
 // LUT apply (Image.point)
 // ---------------------------------------------------------------------------
+// Image n's 3 x 256 table into LDS; a byte's new value is sl[channel][byte].
+__device__ __forceinline__ void stage_lut(uint8_t* sl, const uint8_t* __restrict__ lut, unsigned n) {
+    for (int i = threadIdx.x; i < 768; i += kBlock) sl[i] = lut[(size_t)n * 768 + i];
+    __syncthreads();
+}
+__device__ __forceinline__ unsigned lut_byte(const uint8_t* sl, unsigned c, unsigned byte) { return sl[c * 256 + byte]; }
+
 template <bool NT>
 __global__ __launch_bounds__(kBlock) void lut_apply_kernel(const uint8_t* __restrict__ in,
                                                            const uint8_t* __restrict__ lut,
@@ -303,8 +324,7 @@ __global__ __launch_bounds__(kBlock) void lut_apply_kernel(const uint8_t* __rest
                                                            size_t nbytes) {
     __shared__ uint8_t sl[768];
     const unsigned n = blockIdx.y;
-    for (int i = threadIdx.x; i < 768; i += kBlock) sl[i] = lut[(size_t)n * 768 + i];
-    __syncthreads();
+    stage_lut(sl, lut, n);
     const uint8_t* src = in + (size_t)n * nbytes;
     uint8_t* dst = out + (size_t)n * nbytes;
     const size_t nchunks = nbytes / 16;  // caller guarantees 16-byte aligned images
@@ -312,45 +332,43 @@ __global__ __launch_bounds__(kBlock) void lut_apply_kernel(const uint8_t* __rest
     lf::u32x4* d4 = reinterpret_cast<lf::u32x4*>(dst);
     for (size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x; q < nchunks;
          q += (size_t)gridDim.x * kBlock) {
-        const lf::u32x4 v = lf::ldg<NT>(s4 + q);
-        const unsigned r = (unsigned)(q % 3);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
         unsigned o[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            unsigned c = r + (j % 3);
-            c = c >= 3 ? c - 3 : c;
-            o[j >> 2] |= (unsigned)sl[c * 256 + byte_of(w[j >> 2], j & 3)] << (8 * (j & 3));
-        }
-        lf::u32x4 ov;
-        ov.x = o[0]; ov.y = o[1]; ov.z = o[2]; ov.w = o[3];
-        lf::stg<NT>(d4 + q, ov);
+        each_byte16(lf::ldg<NT>(s4 + q), chunk_channel(q),
+                    [&](unsigned c, unsigned byte, int j) { o[j >> 2] |= lut_byte(sl, c, byte) << (8 * (j & 3)); });
+        lf::stg<NT>(d4 + q, lf::u32x4{o[0], o[1], o[2], o[3]});
     }
     if (blockIdx.x == 0) {
         for (size_t i = nchunks * 16 + threadIdx.x; i < nbytes; i += kBlock)
-            dst[i] = sl[(i % 3) * 256 + src[i]];
+            dst[i] = (uint8_t)lut_byte(sl, (unsigned)(i % 3), src[i]);
     }
 }
 
+// Images or buffers that are not 16-byte aligned: one byte per thread and trip.
 __global__ __launch_bounds__(kBlock) void lut_apply_scalar_kernel(const uint8_t* __restrict__ in,
                                                                   const uint8_t* __restrict__ lut,
                                                                   uint8_t* __restrict__ out,
                                                                   size_t nbytes) {
     __shared__ uint8_t sl[768];
     const unsigned n = blockIdx.y;
-    for (int i = threadIdx.x; i < 768; i += kBlock) sl[i] = lut[(size_t)n * 768 + i];
-    __syncthreads();
+    stage_lut(sl, lut, n);
     const uint8_t* src = in + (size_t)n * nbytes;
     uint8_t* dst = out + (size_t)n * nbytes;
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < nbytes;
          i += (size_t)gridDim.x * kBlock)
-        dst[i] = sl[(i % 3) * 256 + src[i]];
+        dst[i] = (uint8_t)lut_byte(sl, (unsigned)(i % 3), src[i]);
 }
 
 // ---------------------------------------------------------------------------
 // flip
 // ---------------------------------------------------------------------------
-// One thread = 4 pixels (12 bytes).  w % 4 == 0.
+// The source cell of destination cell (y, x) of an h x w image: mode 0 (FLIP_LEFT_RIGHT) mirrors the columns,
+// mode 1 (FLIP_TOP_BOTTOM) the rows.
+template <typename I>
+__device__ __forceinline__ I flip_source(int mode, I y, I x, I h, I w) {
+    return mode == 0 ? y * w + (w - 1 - x) : (h - 1 - y) * w + x;
+}
+
+// One thread = one cell of 4 pixels (12 bytes).  w % 4 == 0.
 __global__ __launch_bounds__(kBlock) void flip_kernel(const uint8_t* __restrict__ in,
                                                       uint8_t* __restrict__ out,
                                                       const int32_t* __restrict__ mode, int h,
@@ -363,8 +381,7 @@ __global__ __launch_bounds__(kBlock) void flip_kernel(const uint8_t* __restrict_
     const unsigned total = (unsigned)h * w4;
     for (unsigned t = blockIdx.x * kBlock + threadIdx.x; t < total; t += gridDim.x * kBlock) {
         const unsigned y = t / w4, g = t - y * w4;
-        const uint32_t* s = src + (m == 0 ? ((size_t)y * w4 + (w4 - 1 - g)) * 3
-                                          : ((size_t)(h - 1 - y) * w4 + g) * 3);
+        const uint32_t* s = src + (size_t)flip_source<unsigned>(m, y, g, h, w4) * 3;
         uint32_t* d = dst + (size_t)t * 3;
         const unsigned w0 = s[0], w1 = s[1], w2 = s[2];
         unsigned o0 = w0, o1 = w1, o2 = w2;
@@ -379,6 +396,7 @@ __global__ __launch_bounds__(kBlock) void flip_kernel(const uint8_t* __restrict_
     }
 }
 
+// Any width or alignment: one thread = one pixel.
 __global__ __launch_bounds__(kBlock) void flip_scalar_kernel(const uint8_t* __restrict__ in,
                                                              uint8_t* __restrict__ out,
                                                              const int32_t* __restrict__ mode,
@@ -392,7 +410,7 @@ __global__ __launch_bounds__(kBlock) void flip_scalar_kernel(const uint8_t* __re
     for (size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x; t < total;
          t += (size_t)gridDim.x * kBlock) {
         const size_t y = t / w, x = t - y * w;
-        const size_t s = m == 0 ? (y * w + (w - 1 - x)) : ((h - 1 - y) * w + x);
+        const size_t s = flip_source<size_t>(m, y, x, h, w);
         dst[3 * t] = src[3 * s];
         dst[3 * t + 1] = src[3 * s + 1];
         dst[3 * t + 2] = src[3 * s + 2];
@@ -413,16 +431,18 @@ __global__ __launch_bounds__(kBlock) void noise_add_kernel(const uint8_t* __rest
     }
 }
 
+// x + y (mod 256) in each of a dword's four bytes, without carries across bytes
+__device__ __forceinline__ uint32_t add_wrap_word(uint32_t x, uint32_t y) {
+    return ((x & 0x7f7f7f7fu) + (y & 0x7f7f7f7fu)) ^ ((x ^ y) & 0x80808080u);
+}
+
 // out = in + add (mod 256) on whole dwords: the same wrap-around add when the noise has already been
 // cast to uint8 on the host (numpy's own astype, image_augmenter.py:121-123)
 __global__ __launch_bounds__(kBlock) void add_wrap_u8_kernel(const uint32_t* __restrict__ a,
                                                              const uint32_t* __restrict__ b,
                                                              uint32_t* __restrict__ out, size_t nwords) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < nwords; i += (size_t)gridDim.x * kBlock) {
-        const uint32_t x = a[i], y = b[i];
-        // per-byte add without carries across bytes
-        out[i] = ((x & 0x7f7f7f7fu) + (y & 0x7f7f7f7fu)) ^ ((x ^ y) & 0x80808080u);
-    }
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < nwords; i += (size_t)gridDim.x * kBlock)
+        out[i] = add_wrap_word(a[i], b[i]);
 }
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
@@ -442,7 +462,29 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
 }
 
-// One thread = 4 bytes: one Philox block -> two Box-Muller pairs.
+// Dword `word` of a buffer, bytes x, with the device-drawn noise added (mod 256): one Philox4x32-10 block keyed by
+// (seed, word) -> two Box-Muller pairs scaled by sigma -> four values truncated toward zero, one per byte.
+__device__ __forceinline__ uint32_t philox_noise_word(uint32_t x, size_t word, uint64_t seed, float sigma) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)word, (uint32_t)(word >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    float z[4];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float u1 = ((float)(r[2 * k] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float u2 = ((float)(r[2 * k + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float rad = sigma * __fsqrt_rn(-2.0f * __logf(u1));
+        float s, c;
+        __sincosf(6.283185307179586f * u2, &s, &c);
+        z[2 * k] = rad * c;
+        z[2 * k + 1] = rad * s;
+    }
+    uint32_t o = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o |= ((byte_of(x, j) + (unsigned)(int)z[j]) & 0xffu) << (8 * j);
+    return o;
+}
+
+// One thread = 4 bytes; a last word of fewer than 4 is made as a whole word and its first bytes stored.
 template <bool NT>
 __global__ __launch_bounds__(kBlock) void noise_philox_kernel(const uint8_t* __restrict__ in,
                                                               uint8_t* __restrict__ out,
@@ -450,115 +492,69 @@ __global__ __launch_bounds__(kBlock) void noise_philox_kernel(const uint8_t* __r
                                                               uint64_t seed, float sigma) {
     for (size_t q = (size_t)blockIdx.x * kBlock + threadIdx.x; q < nwords;
          q += (size_t)gridDim.x * kBlock) {
-        uint32_t r[4];
-        philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u, (uint32_t)seed,
-                      (uint32_t)(seed >> 32), r);
-        float z[4];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const float u1 = ((float)(r[2 * k] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float u2 = ((float)(r[2 * k + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float rad = sigma * __fsqrt_rn(-2.0f * __logf(u1));
-            float s, c;
-            __sincosf(6.283185307179586f * u2, &s, &c);
-            z[2 * k] = rad * c;
-            z[2 * k + 1] = rad * s;
-        }
         const size_t b = q * 4;
-        if (b + 4 <= nbytes) {
-            const unsigned v = lf::ldg<NT>(reinterpret_cast<const uint32_t*>(in) + q);
-            unsigned o = 0;
+        const bool whole = b + 4 <= nbytes;
+        uint32_t x = 0;
+        if (whole) x = lf::ldg<NT>(reinterpret_cast<const uint32_t*>(in) + q);
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o |= ((byte_of(v, j) + (unsigned)(int)z[j]) & 0xffu) << (8 * j);
-            lf::stg<NT>(reinterpret_cast<uint32_t*>(out) + q, o);
-        } else {
-            for (size_t i = b; i < nbytes; ++i) out[i] = (uint8_t)(in[i] + (uint8_t)(int)z[i - b]);
-        }
+        for (int j = 0; j < 3; ++j)
+            if (!whole && b + j < nbytes) x |= (uint32_t)in[b + j] << (8 * j);
+        const uint32_t o = philox_noise_word(x, q, seed, sigma);
+        if (whole) lf::stg<NT>(reinterpret_cast<uint32_t*>(out) + q, o);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (!whole && b + j < nbytes) out[b + j] = (uint8_t)byte_of(o, j);
     }
 }
 
-// The distortion's first two passes in one (round 3): out = in + noise (mod 256) AND the per-image, per-channel
+// The distortion's first two passes in one: out = in + noise (mod 256) AND the per-image, per-channel
 // histogram of `out`, which autocontrast needs next — one workgroup per image with the slotted table of
 // hist_slot_kernel, so the noisy image is not read back from memory just to be counted (5 image passes -> 4).
 // ADD: the noise is a uint8 plane (cast on the host by numpy, lf_add_wrap_u8); otherwise Philox4x32-10 + Box-Muller
-// keyed by (seed, dword index in the BATCH), the very values lf_noise_philox_add_u8 draws.  nbytes % 16 == 0.
+// keyed by (seed, dword index in the BATCH), the very values lf_noise_philox_add_u8 draws.  nbytes % 16 == 0 and the
+// buffers are 16-byte aligned, so an image is whole chunks and starts on a pixel.
 template <bool ADD>
 __global__ __launch_bounds__(kBlock) void noise_hist_kernel(const uint8_t* __restrict__ in,
                                                             const uint8_t* __restrict__ add,
                                                             uint8_t* __restrict__ out, int32_t* __restrict__ hist,
                                                             size_t nbytes, int n, uint64_t seed, float sigma) {
-    __shared__ __attribute__((aligned(16))) unsigned tab[768 * kHistSlots];
-    const unsigned slot = threadIdx.x & (kHistSlots - 1);
+    __shared__ __attribute__((aligned(16))) unsigned lds[kSlotTableWords];
+    const SlotTable tab(lds);
     const size_t nchunks = nbytes / 16;
     for (int img = blockIdx.x; img < n; img += gridDim.x) {
-        for (int i = threadIdx.x; i < 768 * kHistSlots / 4; i += kBlock)
-            reinterpret_cast<lf::u32x4*>(tab)[i] = lf::u32x4{0u, 0u, 0u, 0u};
-        __syncthreads();
+        tab.clear();
         const lf::u32x4* src = reinterpret_cast<const lf::u32x4*>(in + (size_t)img * nbytes);
         const lf::u32x4* nz = ADD ? reinterpret_cast<const lf::u32x4*>(add + (size_t)img * nbytes) : nullptr;
         lf::u32x4* dst = reinterpret_cast<lf::u32x4*>(out + (size_t)img * nbytes);
         const size_t word0 = (size_t)img * (nbytes / 4);
         for (size_t q = threadIdx.x; q < nchunks; q += kBlock) {
             const lf::u32x4 v = src[q];
-            const unsigned x[4] = {v.x, v.y, v.z, v.w};
-            unsigned y[4];
+            lf::u32x4 y;
             if (ADD) {
                 const lf::u32x4 a = nz[q];
-                const unsigned b[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
-                for (int k = 0; k < 4; ++k)   // per-byte add without carries across bytes
-                    y[k] = ((x[k] & 0x7f7f7f7fu) + (b[k] & 0x7f7f7f7fu)) ^ ((x[k] ^ b[k]) & 0x80808080u);
+                for (int k = 0; k < 4; ++k) y[k] = add_wrap_word(v[k], a[k]);
             } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const size_t wq = word0 + 4 * q + k;
-                    uint32_t r[4];
-                    philox4x32_10((uint32_t)wq, (uint32_t)(wq >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-                    float z[4];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const float u1 = ((float)(r[2 * j] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-                        const float u2 = ((float)(r[2 * j + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-                        const float rad = sigma * __fsqrt_rn(-2.0f * __logf(u1));
-                        float sn, cs;
-                        __sincosf(6.283185307179586f * u2, &sn, &cs);
-                        z[2 * j] = rad * cs;
-                        z[2 * j + 1] = rad * sn;
-                    }
-                    unsigned o = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o |= ((byte_of(x[k], j) + (unsigned)(int)z[j]) & 0xffu) << (8 * j);
-                    y[k] = o;
-                }
+                for (int k = 0; k < 4; ++k) y[k] = philox_noise_word(v[k], word0 + 4 * q + k, seed, sigma);
             }
-            dst[q] = lf::u32x4{y[0], y[1], y[2], y[3]};
-            const unsigned r0 = (unsigned)((q * 16) % 3);   // channel of byte 0 of this chunk (images start on a pixel)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                unsigned c = r0 + (j % 3);
-                c = c >= 3 ? c - 3 : c;
-                atomicAdd(&tab[(c * 256 + byte_of(y[j >> 2], j & 3)) * kHistSlots + slot], 1u);
-            }
+            dst[q] = y;
+            each_byte16(y, chunk_channel(q), [&](unsigned c, unsigned byte, int) { tab.add(c, byte); });
         }
-        __syncthreads();
-        int32_t* gh = hist + (size_t)img * 768;
-        for (int b = threadIdx.x; b < 768; b += kBlock) {
-            unsigned sum = 0;
-#pragma unroll
-            for (int k = 0; k < kHistSlots / 4; ++k) {
-                const lf::u32x4 v = reinterpret_cast<const lf::u32x4*>(tab)[b * (kHistSlots / 4) + k];
-                sum += (v.x + v.y) + (v.z + v.w);
-            }
-            gh[b] = (int32_t)sum;
-        }
-        __syncthreads();
+        tab.flush(hist + (size_t)img * 768);
     }
 }
 
 // ---------------------------------------------------------------------------
 // mask-and-composite
 // ---------------------------------------------------------------------------
+// apply_mask's rule: a pixel whose mask byte is above 127 keeps its bytes, any other takes the fill;
+// composite_bits picks image or fill bit by bit, `keep` having ones on the kept pixels' bits.
+__device__ __forceinline__ bool keeps_pixel(unsigned mask_byte) { return mask_byte > 127; }
+__device__ __forceinline__ unsigned composite_bits(unsigned px, unsigned keep, unsigned fill) {
+    return (px & keep) | (fill & ~keep);
+}
+
 // One thread = 4 pixels: 12 image bytes + 4 mask bytes.
 template <bool NT>
 __global__ __launch_bounds__(kBlock) void composite_kernel(const uint8_t* __restrict__ img,
@@ -575,17 +571,18 @@ __global__ __launch_bounds__(kBlock) void composite_kernel(const uint8_t* __rest
         const unsigned w0 = lf::ldg<NT>(s + 3 * g), w1 = lf::ldg<NT>(s + 3 * g + 1),
                        w2 = lf::ldg<NT>(s + 3 * g + 2);
         // per-pixel keep masks expanded to the byte lanes each pixel occupies
-        const unsigned k0 = byte_of(mk, 0) > 127, k1 = byte_of(mk, 1) > 127,
-                       k2 = byte_of(mk, 2) > 127, k3 = byte_of(mk, 3) > 127;
+        const bool k0 = keeps_pixel(byte_of(mk, 0)), k1 = keeps_pixel(byte_of(mk, 1)),
+                   k2 = keeps_pixel(byte_of(mk, 2)), k3 = keeps_pixel(byte_of(mk, 3));
         const unsigned m0 = (k0 ? 0x00ffffffu : 0u) | (k1 ? 0xff000000u : 0u);
         const unsigned m1 = (k1 ? 0x0000ffffu : 0u) | (k2 ? 0xffff0000u : 0u);
         const unsigned m2 = (k2 ? 0x000000ffu : 0u) | (k3 ? 0xffffff00u : 0u);
-        lf::stg<NT>(d + 3 * g, (w0 & m0) | (f4 & ~m0));
-        lf::stg<NT>(d + 3 * g + 1, (w1 & m1) | (f4 & ~m1));
-        lf::stg<NT>(d + 3 * g + 2, (w2 & m2) | (f4 & ~m2));
+        lf::stg<NT>(d + 3 * g, composite_bits(w0, m0, f4));
+        lf::stg<NT>(d + 3 * g + 1, composite_bits(w1, m1, f4));
+        lf::stg<NT>(d + 3 * g + 2, composite_bits(w2, m2, f4));
     }
 }
 
+// The pixels from `start` on (unaligned buffers, and the last npx % 4 pixels): one thread = one pixel.
 __global__ __launch_bounds__(kBlock) void composite_scalar_kernel(const uint8_t* __restrict__ img,
                                                                   const uint8_t* __restrict__ mask,
                                                                   uint8_t* __restrict__ out,
@@ -593,9 +590,9 @@ __global__ __launch_bounds__(kBlock) void composite_scalar_kernel(const uint8_t*
                                                                   unsigned fill) {
     for (size_t p = start + (size_t)blockIdx.x * kBlock + threadIdx.x; p < npx;
          p += (size_t)gridDim.x * kBlock) {
-        const bool keep = mask[p] > 127;
+        const unsigned keep = keeps_pixel(mask[p]) ? 0xffu : 0u;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) out[3 * p + c] = keep ? img[3 * p + c] : (uint8_t)fill;
+        for (int c = 0; c < 3; ++c) out[3 * p + c] = (uint8_t)composite_bits(img[3 * p + c], keep, fill);
     }
 }
 
@@ -1036,6 +1033,19 @@ bool launch_blur_fast(const uint8_t* in, uint8_t* out, int n, int h, int w, cons
     }
 }
 
+// The nontemporal instantiation of a kernel once the launch touches more than the Infinity Cache would keep
+// (lf::streaming), else the plain one.
+template <typename K>
+K by_streaming(size_t bytes_touched, K nontemporal, K plain) {
+    return lf::streaming(bytes_touched) ? nontemporal : plain;
+}
+
+// Workgroups per image for a (splits, n) grid: enough that a small batch still fills the chip, at most `maxs`.
+unsigned image_splits(int n, unsigned maxs) {
+    const unsigned splits = n >= 2048 ? 1 : (unsigned)((2048 + n - 1) / n);
+    return splits > maxs ? maxs : splits;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1061,18 +1071,14 @@ int lf_pack_hwc_u8_to_nchw_f32(const uint8_t* in, float* out, int n, int h, int 
     hipStream_t s = lf::as_stream(stream);
     if (hw % 4 == 0) {
         dim3 grid(lf::stream_grid(hw / 4, kBlock, 1024), n);
-        const bool nt = lf::streaming((size_t)n * hw * 15);
-        auto kern = norm ? (nt ? pack_kernel<true, true> : pack_kernel<true, false>)
-                         : (nt ? pack_kernel<false, true> : pack_kernel<false, false>);
+        const size_t touched = (size_t)n * hw * 15;
+        auto kern = norm ? by_streaming(touched, pack_kernel<true, true>, pack_kernel<true, false>)
+                         : by_streaming(touched, pack_kernel<false, true>, pack_kernel<false, false>);
         kern<<<grid, kBlock, 0, s>>>(in, out, (unsigned)(hw / 4), m[0], m[1], m[2], d[0], d[1], d[2]);
     } else {
         dim3 grid(lf::stream_grid(hw, kBlock, 64), n);
-        if (norm)
-            pack_scalar_kernel<true><<<grid, kBlock, 0, s>>>(in, out, hw, m[0], m[1], m[2], d[0],
-                                                             d[1], d[2]);
-        else
-            pack_scalar_kernel<false><<<grid, kBlock, 0, s>>>(in, out, hw, m[0], m[1], m[2], d[0],
-                                                              d[1], d[2]);
+        auto kern = norm ? pack_scalar_kernel<true> : pack_scalar_kernel<false>;
+        kern<<<grid, kBlock, 0, s>>>(in, out, hw, m[0], m[1], m[2], d[0], d[1], d[2]);
     }
     return lf::check_launch("lf_pack");
 }
@@ -1086,25 +1092,16 @@ int lf_hist_u8(const uint8_t* in, int32_t* hist, int n, int h, int w, lf_stream_
         // enough images to fill the chip with one workgroup per image: the slotted table, no memset, no
         // global atomics
         const unsigned grid = (unsigned)(n < 256 * 12 ? n : 256 * 12);
-        if (lf::streaming((size_t)n * nbytes))
-            hist_slot_kernel<true><<<grid, kBlock, 0, s>>>(in, hist, nbytes, n);
-        else
-            hist_slot_kernel<false><<<grid, kBlock, 0, s>>>(in, hist, nbytes, n);
+        by_streaming((size_t)n * nbytes, hist_slot_kernel<true>, hist_slot_kernel<false>)<<<grid, kBlock, 0, s>>>(
+            in, hist, nbytes, n);
         return lf::check_launch("lf_hist");
     }
     if (hipMemsetAsync(hist, 0, (size_t)n * 768 * sizeof(int32_t), s) != hipSuccess) {
         lf::set_error("lf_hist: memset failed");
         return LF_ERR_LAUNCH;
     }
-    // enough workgroups per image that small batches still fill the chip
-    unsigned splits = n >= 2048 ? 1 : (unsigned)((2048 + n - 1) / n);
-    const unsigned maxs = lf::stream_grid(nbytes / 16 + 1, kBlock, 64);
-    if (splits > maxs) splits = maxs;
-    dim3 grid(splits, n);
-    if (lf::streaming((size_t)n * nbytes))
-        hist_kernel<true><<<grid, kBlock, 0, s>>>(in, hist, nbytes);
-    else
-        hist_kernel<false><<<grid, kBlock, 0, s>>>(in, hist, nbytes);
+    dim3 grid(image_splits(n, lf::stream_grid(nbytes / 16 + 1, kBlock, 64)), n);
+    by_streaming((size_t)n * nbytes, hist_kernel<true>, hist_kernel<false>)<<<grid, kBlock, 0, s>>>(in, hist, nbytes);
     return lf::check_launch("lf_hist");
 }
 
@@ -1124,21 +1121,16 @@ int lf_lut_apply_u8(const uint8_t* in, const uint8_t* lut, uint8_t* out, int n, 
     LF_REQUIRE(n > 0 && h > 0 && w > 0, "lf_lut_apply: bad dims n=%d h=%d w=%d", n, h, w);
     const size_t nbytes = (size_t)h * w * 3;
     hipStream_t s = lf::as_stream(stream);
-    unsigned splits = n >= 2048 ? 1 : (unsigned)((2048 + n - 1) / n);
     const bool aligned = nbytes % 16 == 0 && ((reinterpret_cast<size_t>(in) |
                                                reinterpret_cast<size_t>(out)) & 15) == 0;
     if (aligned) {
         const unsigned maxs = lf::stream_grid(nbytes / 16, kBlock, 64);
-        const unsigned few = (maxs + 3) / 4;  // about four 16-byte chunks per thread
-        if (splits < few) splits = few;
-        if (splits > maxs) splits = maxs;
-        if (lf::streaming((size_t)n * nbytes * 2))
-            lut_apply_kernel<true><<<dim3(splits, n), kBlock, 0, s>>>(in, lut, out, nbytes);
-        else
-            lut_apply_kernel<false><<<dim3(splits, n), kBlock, 0, s>>>(in, lut, out, nbytes);
+        const unsigned few = (maxs + 3) / 4;  // at most about four 16-byte chunks per thread (few <= maxs)
+        const unsigned splits = std::max(image_splits(n, maxs), few);
+        by_streaming((size_t)n * nbytes * 2, lut_apply_kernel<true>, lut_apply_kernel<false>)<<<
+            dim3(splits, n), kBlock, 0, s>>>(in, lut, out, nbytes);
     } else {
-        const unsigned maxs = lf::stream_grid(nbytes, kBlock, 64);
-        if (splits > maxs) splits = maxs;
+        const unsigned splits = image_splits(n, lf::stream_grid(nbytes, kBlock, 64));
         lut_apply_scalar_kernel<<<dim3(splits, n), kBlock, 0, s>>>(in, lut, out, nbytes);
     }
     return lf::check_launch("lf_lut_apply");
@@ -1204,12 +1196,8 @@ int lf_noise_philox_add_u8(const uint8_t* in, uint8_t* out, size_t nbytes, uint6
                "lf_noise_philox_add: buffers must be 4-byte aligned");
     const size_t nwords = (nbytes + 3) / 4;
     const unsigned grid = lf::stream_grid(nwords, kBlock, lf::kFullGrid);
-    if (lf::streaming(nbytes * 2))
-        noise_philox_kernel<true><<<grid, kBlock, 0, lf::as_stream(stream)>>>(in, out, nwords, nbytes,
-                                                                             seed, sigma);
-    else
-        noise_philox_kernel<false><<<grid, kBlock, 0, lf::as_stream(stream)>>>(in, out, nwords,
-                                                                              nbytes, seed, sigma);
+    by_streaming(nbytes * 2, noise_philox_kernel<true>, noise_philox_kernel<false>)<<<
+        grid, kBlock, 0, lf::as_stream(stream)>>>(in, out, nwords, nbytes, seed, sigma);
     return lf::check_launch("lf_noise_philox_add");
 }
 
@@ -1222,10 +1210,8 @@ int lf_noise_hist_u8(const uint8_t* in, const uint8_t* add, uint8_t* out, int32_
     LF_REQUIRE(((reinterpret_cast<size_t>(in) | reinterpret_cast<size_t>(add) | reinterpret_cast<size_t>(out)) & 15) == 0,
                "lf_noise_hist_u8: buffers must be 16-byte aligned");
     const unsigned grid = (unsigned)std::min<size_t>((size_t)n, (size_t)256 * 8);
-    if (add != nullptr)
-        noise_hist_kernel<true><<<grid, kBlock, 0, lf::as_stream(stream)>>>(in, add, out, hist, nbytes, n, seed, sigma);
-    else
-        noise_hist_kernel<false><<<grid, kBlock, 0, lf::as_stream(stream)>>>(in, add, out, hist, nbytes, n, seed, sigma);
+    auto kern = add != nullptr ? noise_hist_kernel<true> : noise_hist_kernel<false>;
+    kern<<<grid, kBlock, 0, lf::as_stream(stream)>>>(in, add, out, hist, nbytes, n, seed, sigma);
     return lf::check_launch("lf_noise_hist_u8");
 }
 
@@ -1241,10 +1227,8 @@ int lf_mask_composite_u8(const uint8_t* img, const uint8_t* mask, uint8_t* out, 
     const size_t npx4 = aligned ? npx / 4 : 0;
     if (npx4) {
         const unsigned grid = lf::stream_grid(npx4, kBlock, lf::kFullGrid);
-        if (lf::streaming(npx * 7))
-            composite_kernel<true><<<grid, kBlock, 0, s>>>(img, mask, out, npx4, (unsigned)color);
-        else
-            composite_kernel<false><<<grid, kBlock, 0, s>>>(img, mask, out, npx4, (unsigned)color);
+        by_streaming(npx * 7, composite_kernel<true>, composite_kernel<false>)<<<grid, kBlock, 0, s>>>(
+            img, mask, out, npx4, (unsigned)color);
     }
     if (npx4 * 4 < npx)
         composite_scalar_kernel<<<lf::stream_grid(npx - npx4 * 4, kBlock), kBlock, 0, s>>>(
@@ -1259,10 +1243,8 @@ int lf_rgb2hsv_u8(const uint8_t* rgb, uint8_t* hsv, size_t npixels, lf_stream_t 
                "lf_rgb2hsv: buffers must be 4-byte aligned");
     // four 4-pixel groups per thread: the per-workgroup divide tables stay a small share
     const unsigned grid = lf::stream_grid(npixels / 16 + 1, kBlock, lf::kFullGrid);
-    if (lf::streaming(npixels * 6))
-        rgb2hsv_kernel<true><<<grid, kBlock, 0, lf::as_stream(stream)>>>(rgb, hsv, npixels);
-    else
-        rgb2hsv_kernel<false><<<grid, kBlock, 0, lf::as_stream(stream)>>>(rgb, hsv, npixels);
+    by_streaming(npixels * 6, rgb2hsv_kernel<true>, rgb2hsv_kernel<false>)<<<grid, kBlock, 0, lf::as_stream(stream)>>>(
+        rgb, hsv, npixels);
     return lf::check_launch("lf_rgb2hsv");
 }
 
@@ -1272,10 +1254,8 @@ int lf_rgb2gray_u8(const uint8_t* rgb, uint8_t* gray, size_t npixels, lf_stream_
     LF_REQUIRE(((reinterpret_cast<size_t>(rgb) | reinterpret_cast<size_t>(gray)) & 3) == 0,
                "lf_rgb2gray: buffers must be 4-byte aligned");
     const unsigned grid = lf::stream_grid(npixels / 4 + 1, kBlock, lf::kFullGrid);
-    if (lf::streaming(npixels * 4))
-        rgb2gray_kernel<true><<<grid, kBlock, 0, lf::as_stream(stream)>>>(rgb, gray, npixels);
-    else
-        rgb2gray_kernel<false><<<grid, kBlock, 0, lf::as_stream(stream)>>>(rgb, gray, npixels);
+    by_streaming(npixels * 4, rgb2gray_kernel<true>, rgb2gray_kernel<false>)<<<grid, kBlock, 0, lf::as_stream(stream)>>>(
+        rgb, gray, npixels);
     return lf::check_launch("lf_rgb2gray");
 }
 
@@ -1290,9 +1270,7 @@ int lf_hsv_region_stats(const uint8_t* rgb, int32_t* counts, int32_t* hsv_hist, 
         return LF_ERR_LAUNCH;
     }
     const size_t npx = (size_t)h * w;
-    unsigned splits = n >= 2048 ? 1 : (unsigned)((2048 + n - 1) / n);
-    const unsigned maxs = lf::stream_grid(npx, kBlock, 64);
-    if (splits > maxs) splits = maxs;
+    const unsigned splits = image_splits(n, lf::stream_grid(npx, kBlock, 64));
     hsv_stats_kernel<<<dim3(splits, n), kBlock, 0, s>>>(rgb, counts, hsv_hist, npx);
     return lf::check_launch("lf_hsv_region_stats");
 }
@@ -1328,9 +1306,7 @@ int lf_gauss_blur_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int c
     return lf::check_launch("lf_gauss_blur");
 }
 
-}  // extern "C"
-
-extern "C" int lf_copy_rows(void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t width, size_t rows,
+int lf_copy_rows(void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t width, size_t rows,
                             int to_host, lf_stream_t stream) {
     LF_REQUIRE(dst && src, "lf_copy_rows: null buffer");
     LF_REQUIRE(width > 0 && rows > 0 && width <= dst_pitch && width <= src_pitch, "lf_copy_rows: bad extent");
@@ -1342,3 +1318,5 @@ extern "C" int lf_copy_rows(void* dst, size_t dst_pitch, const void* src, size_t
     }
     return LF_OK;
 }
+
+}  // extern "C"

@@ -420,3 +420,80 @@ def test_legacy_normal_planes_are_numpys(cuda, count):
             assert np.array_equal(p2[i].cpu().numpy(), np.random.RandomState(sd).normal(100.0, 20.0, 5000).astype(np.uint8))
     with pytest.raises(ValueError):
         ops.legacy_normal_u8([2 ** 32], 0.0, 5.0, 10, cuda)
+
+
+def hist_np(x):
+    """np.bincount per image and channel of a [N,H,W,3] uint8 batch: [N,3,256]."""
+    n = x.shape[0]
+    key = (np.arange(n)[:, None, None] * 3 + np.arange(3)) * 256 + x.reshape(n, -1, 3)
+    return np.bincount(key.ravel(), minlength=n * 768).reshape(n, 3, 256)
+
+
+def small_batch(n, h, w, seed):
+    """Random bytes, every 8th image flat (equal bytes in neighbouring lanes)."""
+    x = np.random.RandomState(seed).randint(0, 256, (n, h, w, 3)).astype(np.uint8)
+    x[::8] = (np.arange(0, n, 8) % 256).astype(np.uint8)[:, None, None, None]
+    return x
+
+
+@pytest.mark.parametrize("h,w", [(5, 7), (16, 16), (33, 17)])
+def test_hist_slotted_table_small_images(cuda, h, w):
+    """512 images take the slotted-table kernel (one workgroup per image).  5 x 7 is 105 bytes: image i starts
+    9 i mod 16 bytes past a 16-byte boundary, so every head length occurs and an image holds 5 or 6 aligned chunks
+    next to its scalar head and tail; 16 x 16 is aligned with no head; 33 x 17 has all three parts and more chunks
+    than one trip of the four-in-flight loop leaves to the remainder loop."""
+    from leaffliction_amd import ops
+    x = small_batch(512, h, w, 50 + h)
+    got = ops.hist_u8(dev(x, cuda)).cpu().numpy()
+    assert np.array_equal(got, hist_np(x))
+
+
+def test_hist_slotted_table_walks_two_images_per_workgroup(cuda):
+    """3,073 images are one more than the slotted kernel's grid (256 * 12): workgroup 0 counts image 0, flushes,
+    clears its table and counts image 3,072."""
+    from leaffliction_amd import ops
+    x = small_batch(3073, 5, 7, 61)
+    got = ops.hist_u8(dev(x, cuda)).cpu().numpy()
+    want = hist_np(x)
+    for i in (0, 3071, 3072):
+        assert np.array_equal(got[i], want[i]), i
+    assert np.array_equal(got.sum(0), want.sum(0))
+
+
+def test_noise_hist_walks_two_images_per_workgroup(cuda):
+    """2,049 images of 16 x 16 are one more than the fused noise + histogram kernel's grid (256 * 8): workgroup 0
+    takes images 0 and 2,048.  Both noise sources: the uint8 plane, and Philox keyed by the dword's index in the
+    batch (the bytes of noise_philox_add_u8 with the same seed)."""
+    from leaffliction_amd import ops
+    x = small_batch(2049, 16, 16, 62)
+    xd = dev(x, cuda)
+    n8 = np.random.RandomState(3).normal(0, 5, x.shape).astype(np.uint8)
+    y, hist = ops.noise_hist_u8(xd, dev(n8, cuda))
+    want = (x + n8).astype(np.uint8)
+    assert np.array_equal(y.cpu().numpy(), want)
+    assert np.array_equal(hist.cpu().numpy(), hist_np(want))
+    yp, hp = ops.noise_hist_u8(xd, None, seed=42, sigma=5.0)
+    ref = ops.noise_philox_add_u8(xd, 42, 5.0).cpu().numpy()
+    assert np.array_equal(yp.cpu().numpy(), ref)
+    assert np.array_equal(hp.cpu().numpy(), hist_np(ref))
+
+
+def test_philox_add_ragged_last_word(cuda):
+    """315 bytes end in a word of 3: its bytes are the first 3 of the whole word the same call makes of those
+    bytes padded to 316 (the generator is keyed by dword index, not by the buffer's length)."""
+    from leaffliction_amd import ops
+    x = np.random.RandomState(63).randint(0, 256, (3, 5, 7, 3)).astype(np.uint8)
+    padded = np.concatenate([x.ravel(), np.array([200], np.uint8)]).reshape(1, 79, 4, 1)
+    got = ops.noise_philox_add_u8(dev(x, cuda), 7).cpu().numpy()
+    full = ops.noise_philox_add_u8(dev(padded, cuda), 7).cpu().numpy()
+    assert np.array_equal(got.ravel(), full.ravel()[:315])
+    assert not np.array_equal(got, x)
+
+
+def test_hist_one_image_split_over_workgroups(cuda):
+    """One 64 x 48 image: the 2,048 workgroups a single image would get are clamped to the 3 its 576 chunks fill;
+    only the first of them counts the (empty) head and tail."""
+    from leaffliction_amd import ops
+    x = small_batch(1, 64, 48, 64)
+    x[0] = np.random.RandomState(64).randint(0, 256, (64, 48, 3))
+    assert np.array_equal(ops.hist_u8(dev(x, cuda)).cpu().numpy(), hist_np(x))
