@@ -146,13 +146,36 @@ inline int slab_groups(int splits) { return (splits + kSlabGroup - 1) / kSlabGro
 inline int slab_stages(int splits) { return splits > kSlabGroup ? 2 : 1; }
 void reduce_slabs(float* part, float* dst, size_t count, int splits, float beta, hipStream_t s);
 
-// The most units (segments of column strips) one workgroup walks when `wgs` workgroups deal out n images of
-// `units_per_image` units each as conv_bf16s_kernel and wgrad_bf16_kernel do: round-robin over the grid, or with
-// `interleave` image i on XCD i % 8 (workgroups k, k + 8, ...).  Workgroup 0 walks the most.
+// How conv_bf16s_kernel and wgrad_bf16_kernel deal out units of work (segments of column strips, `units_per_image`
+// to each of n images) to `wgs` workgroups: round-robin over the grid, or with `interleave` image i on XCD i % 8
+// (workgroups k, k + 8, ... run on XCD k and take that XCD's units in order).  Workgroup wg walks units
+// first, first + step, ... < total of its sequence (the grid's, or its XCD's); lf::StripWalk decodes them.
+struct StripShare {
+    int total, first, step, units;
+};
+__host__ __device__ inline StripShare strip_share(int n, int units_per_image, int wgs, int interleave, int wg) {
+    const int xk = wg & 7;
+    StripShare s;
+    s.total = interleave ? (n > xk ? (n - xk + 7) / 8 : 0) * units_per_image : n * units_per_image;
+    s.first = interleave ? wg >> 3 : wg;
+    s.step = interleave ? wgs >> 3 : wgs;
+    s.units = (s.step > 0 && s.total > s.first) ? (s.total - s.first + s.step - 1) / s.step : 0;
+    return s;
+}
+// The most units one workgroup walks: workgroup 0 walks the most.
 inline int max_units_per_workgroup(int n, int units_per_image, int wgs, int interleave) {
-    const long long total = interleave ? (long long)((n + 7) / 8) * units_per_image : (long long)n * units_per_image;
-    const long long step = interleave ? wgs / 8 : wgs;
-    return step > 0 ? (int)((total + step - 1) / step) : 0;
+    return strip_share(n, units_per_image, wgs, interleave, 0).units;
+}
+
+// Column strips are cut into segments (which re-stage the two rows above them) only when `strips` of them are fewer
+// than the `want` units that fill the chip, and never into segments of fewer than four tiles.
+inline void strip_segments(int strips, int want, int tiles_y, int* seg_tiles, int* segs) {
+    int s = (want + strips - 1) / strips;
+    const int max_segs = (tiles_y + 3) / 4;        // at least four tiles to a segment
+    if (s > max_segs) s = max_segs;
+    if (s < 1) s = 1;
+    *seg_tiles = (tiles_y + s - 1) / s;
+    *segs = (tiles_y + *seg_tiles - 1) / *seg_tiles;
 }
 
 // Tile kernels whose neighbouring tiles share input halos: workgroups are dealt to the eight XCDs
@@ -189,16 +212,66 @@ __device__ __forceinline__ TileId xcd_tile(int tiles_x, int tiles_y, int n_image
 struct Block2 {
     unsigned x, y;
 };
-__device__ __forceinline__ Block2 xcd_block2() {
-    const unsigned gx = gridDim.x, total = gx * gridDim.y;
-    const unsigned b = blockIdx.x + gx * blockIdx.y;
+// the core: workgroup b (flat, in dispatch order) of `total` acts as block xcd_flat(b, total), which gives XCD k
+// the k-th contiguous share of the blocks whatever total % 8 is
+__device__ __forceinline__ unsigned xcd_flat(unsigned b, unsigned total) {
     const unsigned k = b & 7u, fl = total >> 3, rm = total & 7u;
-    const unsigned id = k * fl + (k < rm ? k : rm) + (b >> 3);
+    return k * fl + (k < rm ? k : rm) + (b >> 3);
+}
+__device__ __forceinline__ Block2 xcd_block2() {
+    const unsigned gx = gridDim.x;
+    const unsigned id = xcd_flat(blockIdx.x + gx * blockIdx.y, gx * gridDim.y);
     Block2 r;
     r.y = id / gx;
     r.x = id - r.y * gx;
     return r;
 }
+// and on a 3-D grid (the tile kernels of the convolutions: tile, channel group, image)
+struct Block3 {
+    int x, y, z;
+};
+__device__ __forceinline__ Block3 xcd_block3() {
+    const unsigned gx = gridDim.x, gxy = gx * gridDim.y;
+    const unsigned id = xcd_flat(blockIdx.x + gx * (blockIdx.y + gridDim.y * blockIdx.z), gxy * gridDim.z);
+    Block3 r;
+    r.z = (int)(id / gxy);
+    r.y = (int)((id - (unsigned)r.z * gxy) / gx);
+    r.x = (int)(id - (unsigned)r.z * gxy - (unsigned)r.y * gx);
+    return r;
+}
+
+// One workgroup's walk over segments of column strips (a strip = a tile's width of columns of one image, a segment
+// = seg_tiles consecutive tiles of it, top to bottom; `segs` segments to a strip), dealt out as strip_share() says.
+struct StripUnit {
+    int n, strip, t_first, t_count;  // image, strip of the image, first tile of the segment, its tiles
+    int rem;                         // the segment's index inside its image: segment * tiles_x + strip
+};
+struct StripWalk {
+    int units;  // what this workgroup walks: unit(0) .. unit(units - 1)
+    __device__ __forceinline__ StripWalk(int n, int tiles_x, int tiles_y, int seg_tiles, int segs, int interleave)
+        : tiles_x_(tiles_x), tiles_y_(tiles_y), seg_tiles_(seg_tiles), per_image_(tiles_x * segs),
+          interleave_(interleave != 0) {
+        const StripShare s = strip_share(n, per_image_, (int)gridDim.x, interleave_, (int)blockIdx.x);
+        units = s.units;
+        first_ = s.first;
+        step_ = s.step;
+    }
+    __device__ __forceinline__ StripUnit unit(int ui) const {
+        const int q = first_ + ui * step_;
+        const int im = q / per_image_, seg = (q - im * per_image_) / tiles_x_;
+        StripUnit u;
+        u.rem = q - im * per_image_;
+        u.n = interleave_ ? im * 8 + (int)(blockIdx.x & 7) : im;
+        u.strip = u.rem - seg * tiles_x_;
+        u.t_first = seg * seg_tiles_;
+        u.t_count = min(seg_tiles_, tiles_y_ - u.t_first);
+        return u;
+    }
+
+private:
+    int tiles_x_, tiles_y_, seg_tiles_, per_image_, first_, step_;
+    bool interleave_;
+};
 
 // Kernels that take images of different sizes in one launch number their units of work through all images: the
 // last of n items whose first unit, start_of(item), is not past g (the starts ascend from start_of(0) <= g).
@@ -263,6 +336,147 @@ __device__ __forceinline__ void stat_accumulate(float v, bool in_image, bool mas
     const float d = masked ? (on ? v : 0.f) : (in_image ? v - pivot : 0.f);
     a += d;
     b = fmaf(d, masked ? y_mask : d, b);
+}
+
+// ---- pieces of the bf16 convolution kernels (lf_conv_bf16.hip, lf_conv_bf16s.hip, lf_wgrad_bf16.hip).  None holds a
+// barrier or a wait of its own, and all take the kernel's own pointers and arrays: where the waves meet stays in
+// the kernels.
+
+// element e of a vector of dwords that each hold two bf16 (the lower-indexed one in the low half), widened
+template <typename W>
+__device__ __forceinline__ float bf16_at(const W& w, int e) {
+    return bf16_up((e & 1) ? w[e / 2] >> 16 : w[e / 2] & 0xffffu);
+}
+// and all G of them (v: float[G] or a float vector)
+template <int G, typename W, typename V>
+__device__ __forceinline__ void unpack_bf16(const W& w, V& v) {
+#pragma unroll
+    for (int e = 0; e < G; e += 2) {
+        v[e] = bf16_up(w[e / 2] & 0xffffu);
+        v[e + 1] = bf16_up(w[e / 2] >> 16);
+    }
+}
+
+// the fused prologue of a convolution input: the producer's BatchNorm (+ReLU) on one value
+__device__ __forceinline__ float pro_apply(float v, float sc, float sh, int relu) {
+    v = fmaf(v, sc, sh);
+    return relu ? fmaxf(v, 0.f) : v;
+}
+
+// Staging four channels x G pixels as [pixel][channel] bf16: raw[i] = channel i's G pixels as loaded; ok = false:
+// outside the image, which stays exactly zero.  transform(i, v) works on channel i's G fp32 values; every second
+// channel the pair (i - 1, i) leaves as store(e, pair, dword), one dword per pixel e — channel by channel, so that
+// few values are live at a time.
+template <int G, typename W, typename Transform, typename Store>
+__device__ __forceinline__ void stage_quad(const W (&raw)[4], bool ok, Transform transform, Store store) {
+    float prev[G];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float v[G];
+#pragma unroll
+        for (int e = 0; e < G; ++e) v[e] = 0.f;
+        if (ok) {
+            unpack_bf16<G>(raw[i], v);
+            transform(i, v);
+        }
+        if (i & 1) {
+#pragma unroll
+            for (int e = 0; e < G; ++e) store(e, i >> 1, pack_bf16(prev[e], v[e]));
+        } else {
+#pragma unroll
+            for (int e = 0; e < G; ++e) prev[e] = v[e];
+        }
+    }
+}
+// Its twin for the halo columns: four channels of ONE pixel -> the pixel's two dwords.  widen(i) = channel i's value,
+// transform(i, v) as above with v a float[1].
+template <typename Widen, typename Transform>
+__device__ __forceinline__ u32x2 stage_halo_quad(bool ok, Widen widen, Transform transform) {
+    float v[4][1] = {{0.f}, {0.f}, {0.f}, {0.f}};
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i][0] = widen(i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) transform(i, v[i]);
+    }
+    u32x2 o;
+    o.x = pack_bf16(v[0][0], v[1][0]);
+    o.y = pack_bf16(v[2][0], v[3][0]);
+    return o;
+}
+
+// The epilogue of a thread that finishes EIGHT consecutive pixels of one output channel (16 bytes of bf16), the
+// accumulators having gone through a transpose buffer in LDS.
+// row8_request: the read-modify-write operand rows of the thread's channels co0 + 32 * cb + 8 * j + ec, eight
+// pixels at offset po of each channel plane of `image` — asked for before the MFMAs, used after them.
+template <int NCB>
+__device__ __forceinline__ void row8_request(u32x4 (&r)[NCB][4], const uint16_t* image, int co0, int ec, size_t hw,
+                                             size_t po) {
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            r[cb][j] = *reinterpret_cast<const u32x4*>(image + (size_t)(co0 + cb * 32 + 8 * j + ec) * hw + po);
+}
+// row8_finish: acc8 = the eight fp32 accumulators (16-byte aligned LDS) -> (+ old) -> (* *osc + *osh, read only
+// when scaled) -> ReLU -> bf16
+__device__ __forceinline__ u32x4 row8_finish(const float* acc8, bool accumulate, const u32x4& old, bool scaled,
+                                             const float* osc, const float* osh, int relu) {
+    const f32x4 a0 = *reinterpret_cast<const f32x4*>(acc8);
+    const f32x4 a1 = *reinterpret_cast<const f32x4*>(acc8 + 4);
+    float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+    if (accumulate)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += bf16_at(old, e);
+    if (scaled) {
+        const float sc = *osc, sh = *osh;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = fmaf(v[e], sc, sh);
+    }
+    if (relu)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) o[e / 2] = pack_bf16(v[e], v[e + 1]);
+    return o;
+}
+// row8_sums: the eight stat_accumulate terms of the ROUNDED values o, all inside the image: forward terms about
+// *pivot (null: 0), or (masked) backward terms under the mask rows `mask_words` with mask scale *msc and shift *msh.
+// Only the kind's own constants are read.  (One loop per kind of sum: the kind is uniform, the loops are unrolled.)
+__device__ __forceinline__ void row8_sums(const u32x4& o, bool masked, const float* pivot, const float* msc,
+                                          const float* msh, const u32x4& mask_words, int mask_relu, float& a,
+                                          float& b) {
+    if (!masked) {
+        const float pv = pivot != nullptr ? *pivot : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) stat_accumulate(bf16_at(o, e), true, false, pv, 0.f, 0.f, 0.f, 0, a, b);
+    } else {
+        const float sc = *msc, sh = *msh;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            stat_accumulate(bf16_at(o, e), true, true, 0.f, bf16_at(mask_words, e), sc, sh, mask_relu, a, b);
+    }
+}
+
+// Statistics partials of a workgroup: red[WAVES][CT][2] (one partial per wave and channel of the workgroup's CT
+// channels from co0 on) -> stat_part[(co * stat_tiles + partial) * 2 + {0,1}], the waves added in order from the
+// left (deterministic).  The caller's barrier stands between the writes of `red` and this.
+template <int WAVES, int CT>
+__device__ __forceinline__ void write_stat_part(float* stat_part, long long stat_tiles, int cout, long long partial,
+                                                int co0, const float* red, int tid, int threads) {
+    for (int c = tid; c < CT; c += threads) {
+        if (co0 + c >= cout) continue;
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int wp = 0; wp < WAVES; ++wp) {
+            a += red[(wp * CT + c) * 2];
+            b += red[(wp * CT + c) * 2 + 1];
+        }
+        float* dst = stat_part + ((size_t)(co0 + c) * (size_t)stat_tiles + (size_t)partial) * 2;
+        dst[0] = a;
+        dst[1] = b;
+    }
 }
 
 template <bool NT, typename T>

@@ -38,11 +38,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ float pro_apply(float v, float sc, float sh, int relu) {
-    v = fmaf(v, sc, sh);
-    return relu ? fmaxf(v, 0.f) : v;
-}
-
 // Raw buffer loads: SGPR resource (base, byte size) + a 32-bit byte offset per lane; an offset
 // at or beyond the size returns 0, which is how zero padding is fetched (no branches, no
 // 64-bit address arithmetic per lane).
@@ -90,6 +85,7 @@ struct ConvArgs {
 };
 
 using lf::half_sum32;
+using lf::pro_apply;
 using lf::row_sum16;
 
 // Winograd F(2x2,3x3) transforms (Lavin & Gray 2016): Y = A^T [(G g G^T) . (B^T d B)] A with
@@ -164,13 +160,10 @@ struct ConvTile {
     bool imgA_ok, imgB_ok;
 
     __device__ __forceinline__ explicit ConvTile(const ConvArgs& p) {
-        const unsigned gxy = gridDim.x * gridDim.y, gtotal = gxy * gridDim.z;
-        const unsigned bflat = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned xk = bflat & 7u, xfloor = gtotal >> 3, xrem = gtotal & 7u;
-        const unsigned wid_flat = xk * xfloor + (xk < xrem ? xk : xrem) + (bflat >> 3);
-        bz = (int)(wid_flat / gxy);
-        by = (int)((wid_flat - (unsigned)bz * gxy) / gridDim.x);
-        tile = (int)(wid_flat - (unsigned)bz * gxy - (unsigned)by * gridDim.x);
+        const lf::Block3 b = lf::xcd_block3();
+        bz = b.z;
+        by = b.y;
+        tile = b.x;
         tx0 = (tile % p.tiles_x) * TW;
         ty0 = (tile / p.tiles_x) * TH;
         n = bz * p.stack;
@@ -339,19 +332,8 @@ template <int WPX, int CT>
 __device__ __forceinline__ void write_stat_part(const ConvArgs& p, const float* red, int bz, int tile, int co0,
                                                 int tid) {
     __syncthreads();
-    const long long tg = (long long)bz * (p.tiles_x * p.tiles_y) + tile;
-    for (int c = tid; c < CT; c += kThreads) {
-        if (co0 + c >= p.cout) continue;
-        float a = 0.f, b = 0.f;
-#pragma unroll
-        for (int wp = 0; wp < WPX; ++wp) {
-            a += red[(wp * CT + c) * 2];
-            b += red[(wp * CT + c) * 2 + 1];
-        }
-        float* dst = p.stat_part + ((size_t)(co0 + c) * (size_t)p.stat_tiles + (size_t)tg) * 2;
-        dst[0] = a;
-        dst[1] = b;
-    }
+    lf::write_stat_part<WPX, CT>(p.stat_part, p.stat_tiles, p.cout, (long long)bz * (p.tiles_x * p.tiles_y) + tile,
+                                 co0, red, tid, kThreads);
 }
 
 // Direct GEMM (the stem and the 1x1 convolutions).  TAPS: 9 (3x3) or 1 (1x1).  Tile TW x TH pixels = NPB blocks of 32 (flat index); waves WCO x WPX = 4,

@@ -64,13 +64,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     __shared__ float lsc[2][kMaxPrologueCin];
     // XCD-aware order (see lf_conv.hip): XCD k walks the k-th contiguous share of the
     // (tile, channel group, image) space, so tiles that share halo rows meet in one L2
-    const unsigned gxy = gridDim.x * gridDim.y, gtotal = gxy * gridDim.z;
-    const unsigned bflat = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned xk = bflat & 7u, xfloor = gtotal >> 3, xrem = gtotal & 7u;
-    const unsigned wflat = xk * xfloor + (xk < xrem ? xk : xrem) + (bflat >> 3);
-    const int n = (int)(wflat / gxy);
-    const int cog = (int)((wflat - (unsigned)n * gxy) / gridDim.x);
-    const int tile = (int)(wflat - (unsigned)n * gxy - (unsigned)cog * gridDim.x);
+    const lf::Block3 blk = lf::xcd_block3();
+    const int n = blk.z, cog = blk.y, tile = blk.x;
     const int tiles_x = (p.w + kTW - 1) / kTW;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int x0 = tx * kTW, y0 = ty * kTH;
@@ -156,14 +151,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     };
     auto widen = [&](const Raw& r, int ci) -> f32x4 {  // fp32 values with the fused prologue applied
         f32x4 v;
-        if (XBF) {
-            v[0] = bf16_up(r.h.x & 0xffffu);
-            v[1] = bf16_up(r.h.x >> 16);
-            v[2] = bf16_up(r.h.y & 0xffffu);
-            v[3] = bf16_up(r.h.y >> 16);
-        } else {
+        if (XBF)
+            lf::unpack_bf16<4>(r.h, v);
+        else
             v = r.f;
-        }
+        // (this kernel alone also takes a ReLU without a scale — its entries do not forbid it —, so the two are
+        // applied apart and not through lf::pro_apply)
         if (p.in_scale) {
             const float sc = lsc[0][ci], sh = lsc[1][ci];
 #pragma unroll
@@ -221,32 +214,17 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
     // training, 32x8 tile, 16-byte rows: the epilogue works on (8 consecutive pixels, one channel)
     // per thread — its read-modify-write operands are requested now and arrive during the MFMAs
-    typedef unsigned uvec4 __attribute__((ext_vector_type(4)));
     const bool wide = kWide;
     const int eg = tid & 31, ec = tid >> 5;
     const int egy = y0 + (eg >> 2), egx = x0 + 8 * (eg & 3);
     const bool eok = egy < p.h && egx < p.w;
     const size_t epo = eok ? (size_t)egy * p.w + egx : 0;
-    uvec4 rold[(kWide && TR) ? NCO : 1][4], rmask[(kWide && TR) ? NCO : 1][4];
-    auto request_rmw = [&]() {
-        if (!TR) return;  // inference: nothing is read back
-        const uint16_t* yold = static_cast<const uint16_t*>(p.y) + (size_t)n * p.cout * hw;
+    lf::u32x4 rold[(kWide && TR) ? NCO : 1][4], rmask[(kWide && TR) ? NCO : 1][4];
+    if (wide && TR) {  // (inference: nothing is read back)
         if (p.accumulate)
-#pragma unroll
-            for (int cb = 0; cb < ((kWide && TR) ? NCO : 1); ++cb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    rold[cb][j] = *reinterpret_cast<const uvec4*>(yold + (size_t)(co0 + cb * 32 + 8 * j + ec) * hw + epo);
-        if (p.stat_mask_y != nullptr) {
-            const uint16_t* ym = p.stat_mask_y + (size_t)n * p.cout * hw;
-#pragma unroll
-            for (int cb = 0; cb < ((kWide && TR) ? NCO : 1); ++cb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    rmask[cb][j] = *reinterpret_cast<const uvec4*>(ym + (size_t)(co0 + cb * 32 + 8 * j + ec) * hw + epo);
-        }
-    };
-    if (wide) request_rmw();
+            lf::row8_request(rold, static_cast<const uint16_t*>(p.y) + (size_t)n * p.cout * hw, co0, ec, hw, epo);
+        if (p.stat_mask_y != nullptr) lf::row8_request(rmask, p.stat_mask_y + (size_t)n * p.cout * hw, co0, ec, hw, epo);
+    }
     issue(0);
     for (int c = 0; c < p.chunks; ++c) {
         __syncthreads();  // the previous chunk's LDS reads are done
@@ -310,46 +288,15 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int cl = 8 * j + ec, co = co0 + cb * 32 + cl;
-                const f32x4 a0 = *reinterpret_cast<const f32x4*>(le + cl * 256 + 8 * eg);
-                const f32x4 a1 = *reinterpret_cast<const f32x4*>(le + cl * 256 + 8 * eg + 4);
-                float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                if (TR && p.accumulate)
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        v[e] += bf16_up(rold[TR ? cb : 0][j][e / 2] & 0xffffu);
-                        v[e + 1] += bf16_up(rold[TR ? cb : 0][j][e / 2] >> 16);
-                    }
-                if (p.out_scale) {
-                    const float osc = eps[0][cb * 32 + cl], osh = eps[1][cb * 32 + cl];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaf(v[e], osc, osh);
-                }
-                if (p.out_relu)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.0f);
-                uvec4 o;
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) o[e / 2] = pack_bf16(v[e], v[e + 1]);
-                if (eok) *reinterpret_cast<uvec4*>(yout + (size_t)co * hw + epo) = o;
+                const lf::u32x4 o = lf::row8_finish(le + cl * 256 + 8 * eg, TR && p.accumulate, rold[TR ? cb : 0][j],
+                                                    p.out_scale != nullptr, &eps[0][cb * 32 + cl], &eps[1][cb * 32 + cl],
+                                                    p.out_relu);
+                if (eok) *reinterpret_cast<lf::u32x4*>(yout + (size_t)co * hw + epo) = o;
                 if (!TR || !stats) continue;
                 float a = 0.f, b = 0.f;
-                if (eok) {   // (one loop per kind of sum: the kind is uniform, the loops are unrolled)
-                    if (!masked) {
-                        const float pv = p.stat_pivot != nullptr ? p.stat_pivot[co] : 0.f;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, false, pv, 0.f,
-                                                0.f, 0.f, 0, a, b);
-                    } else {
-                        const float msc = p.mask_scale[co], msh = p.mask_shift[co];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const unsigned mw = rmask[TR ? cb : 0][j][e / 2];
-                            lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, true, 0.f,
-                                                bf16_up((e & 1) ? mw >> 16 : mw & 0xffffu), msc, msh, p.mask_relu, a, b);
-                        }
-                    }
-                }
+                if (eok)
+                    lf::row8_sums(o, masked, p.stat_pivot != nullptr ? p.stat_pivot + co : nullptr, p.mask_scale + co,
+                                  p.mask_shift + co, rmask[TR ? cb : 0][j], p.mask_relu, a, b);
                 a = half_sum32(a);
                 b = half_sum32(b);
                 if (eg == 31) {
@@ -441,18 +388,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
     if (stats) {
         __syncthreads();
-        const long long tg = (long long)n * gridDim.x + tile;
-        if (tid < NCO * 32) {
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int w4 = 0; w4 < 4; ++w4) {
-                a += red[(w4 * (NCO * 32) + tid) * 2];
-                b += red[(w4 * (NCO * 32) + tid) * 2 + 1];
-            }
-            float* dst = p.stat_part + ((size_t)(co0 + tid) * (size_t)p.stat_tiles + (size_t)tg) * 2;
-            dst[0] = a;
-            dst[1] = b;
-        }
+        lf::write_stat_part<4, NCO * 32>(p.stat_part, p.stat_tiles, p.cout, (long long)n * gridDim.x + tile, co0, red,
+                                         tid, kThreads);
     }
 }
 

@@ -102,21 +102,7 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
     // XCD's segments in order — the strips of one image by NEIGHBOURING workgroups, started together —, so what two
     // strips share (halo columns, 128-byte lines that straddle a strip boundary) crosses the fabric once.
     // interleave = 0 (small launches): segments dealt round-robin over the grid.
-    const int SG = p.tiles_x, UI = SG * p.segs;   // strips, segments per image
-    int unit_rem = 0;                             // the current segment's index inside its image
-    const int xk = blockIdx.x & 7, xj = blockIdx.x >> 3, xw = gridDim.x >> 3;
-    const int my_total = (p.interleave & 1) ? (p.n > xk ? (p.n - xk + 7) / 8 : 0) * UI : p.n * UI;
-    const int my_first = (p.interleave & 1) ? xj : (int)blockIdx.x, my_step = (p.interleave & 1) ? xw : (int)gridDim.x;
-    const int my_units = my_total > my_first ? (my_total - my_first + my_step - 1) / my_step : 0;
-    auto unit_of = [&](int ui, int& n, int& tx0, int& t_first, int& t_count) {
-        const int q = my_first + ui * my_step;
-        const int im = q / UI, rem = q - im * UI, seg = rem / SG;
-        unit_rem = rem;
-        n = (p.interleave & 1) ? im * 8 + xk : im;
-        tx0 = (rem - seg * SG) * TW;
-        t_first = seg * p.seg_tiles;
-        t_count = min(p.seg_tiles, p.tiles_y - t_first);
-    };
+    const lf::StripWalk walk(p.n, p.tiles_x, p.tiles_y, p.seg_tiles, p.segs, p.interleave);
 
     // ---- one-time: filter bank -> LDS as [chunk][tap][k half][cout][8 channels] (16 B per entry)
     {
@@ -201,6 +187,13 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
         }
     };
 
+    // the producer's BatchNorm (+ReLU) on the values v of channel c, in fp32
+    auto prologue = [&](int c, auto& v) {
+        if (!pro) return;
+        const float sc = lsc[c], sh = lsc[CI + c];
+#pragma unroll
+        for (int e = 0; e < (int)(sizeof(v) / sizeof(float)); ++e) v[e] = lf::pro_apply(v[e], sc, sh, p.in_relu);
+    };
     auto commit = [&]() {
 #pragma unroll
         for (int k = 0; k < XPT; ++k) {
@@ -211,41 +204,28 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
             int slot = st_slot + pr;
             slot = slot >= PH ? slot - PH : slot;
             const unsigned pi = (unsigned)(slot * PW + HALO + G * pg);
-            float prev[G];
-            // channel by channel; every second channel the pair goes to LDS, one dword per pixel
+            auto store = [&](int e, int pair, unsigned dword) {
+                *reinterpret_cast<unsigned*>(lp + poff(pi + e, (unsigned)quad >> 1) + 8 * (quad & 1) + 4 * pair) = dword;
+            };
+            if constexpr (XBF) {
+                lf::stage_quad<G>(rx[k], ok, [&](int i, float (&v)[G]) { prologue(4 * quad + i, v); }, store);
+            } else {
+                // the stem: three fp32 channels and a zero one
+                float v[4][G];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float v[G];
+                for (int i = 0; i < 4; ++i) {
 #pragma unroll
-                for (int e = 0; e < G; ++e) v[e] = 0.f;  // zero padding stays exactly zero
-                if (ok && (XBF || (i < 3 && i < p.cin))) {
-                    if (XBF) {
+                    for (int e = 0; e < G; ++e) v[i][e] = 0.f;  // zero padding stays exactly zero
+                    if (ok && i < 3 && i < p.cin) {
 #pragma unroll
-                        for (int e = 0; e < G; e += 2) {
-                            v[e] = bf16_up(rx[k][i][e / 2] & 0xffffu);
-                            v[e + 1] = bf16_up(rx[k][i][e / 2] >> 16);
-                        }
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < G; ++e) v[e] = __uint_as_float(rx[k][i < 3 ? i : 0][e]);
-                    }
-                    if (pro) {
-                        const float sc = lsc[4 * quad + i], sh = lsc[CI + 4 * quad + i];
-#pragma unroll
-                        for (int e = 0; e < G; ++e) {
-                            v[e] = fmaf(v[e], sc, sh);
-                            if (p.in_relu) v[e] = fmaxf(v[e], 0.f);
-                        }
+                        for (int e = 0; e < G; ++e) v[i][e] = __uint_as_float(rx[k][i < 3 ? i : 0][e]);
+                        prologue(i, v[i]);
                     }
                 }
-                if (i & 1) {
 #pragma unroll
-                    for (int e = 0; e < G; ++e)
-                        *reinterpret_cast<unsigned*>(lp + poff(pi + e, (unsigned)quad >> 1) + 8 * (quad & 1) +
-                                                     4 * (i >> 1)) = pack_bf16(prev[e], v[e]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < G; ++e) prev[e] = v[e];
+                for (int e = 0; e < G; ++e) {
+                    store(e, 0, pack_bf16(v[0][e], v[1][e]));
+                    store(e, 1, pack_bf16(v[2][e], v[3][e]));
                 }
             }
         }
@@ -254,26 +234,11 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
             const int u = tid + k * kT;
             const int side = u & 1, t1 = u >> 1, quad = t1 % QD, pr = t1 / QD;
             if (pr >= st_rows) continue;
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-            if (hmask >> k & 1u) {
-                if (XBF) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = bf16_up(rh[k][i]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) v[i] = __uint_as_float(rh[k][i]);
-                }
-                if (pro)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        v[i] = fmaf(v[i], lsc[4 * quad + i], lsc[CI + 4 * quad + i]);
-                        if (p.in_relu) v[i] = fmaxf(v[i], 0.f);
-                    }
-                if (!XBF) v[3] = 0.f;
-            }
-            u32x2 o;
-            o.x = pack_bf16(v[0], v[1]);
-            o.y = pack_bf16(v[2], v[3]);
+            // (the stem: three fp32 channels, the fourth stays zero)
+            const u32x2 o = lf::stage_halo_quad(
+                hmask >> k & 1u,
+                [&](int i) { return XBF ? bf16_up(rh[k][i]) : (i < 3 ? __uint_as_float(rh[k][i]) : 0.f); },
+                [&](int i, float (&v)[1]) { if (XBF || i < 3) prologue(4 * quad + i, v); });
             int slot = st_slot + pr;
             slot = slot >= PH ? slot - PH : slot;
             const unsigned pi = (unsigned)(slot * PW + (side ? PW - 1 : 0));
@@ -300,16 +265,16 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
     uvec rold[NCO][4], rmask[NCO][4];  // eight pixels of one channel each, as stored
 
     // A tile's new rows are gy = ty * TH + HALO .. + TH - 1; a segment's first tile also needs the 2 * HALO rows above
-    // them (the "prime" pass: staged when the segment starts, its latency exposed once per segment).
-    int sn = 0, stx0 = 0, stf = 0, stc = 0;
-    if (my_units > 0) {
-        unit_of(0, sn, stx0, stf, stc);
-        issue(sn, stx0, stf * TH + HALO, TH);
+    // them (the "prime" pass: staged when the segment starts, its latency exposed once per segment).  (The first
+    // rows of a unit are issued in two places, written out: behind a lambda of their own the 1x1 variants, which
+    // sit at 168 registers, spilled two.)
+    if (walk.units > 0) {
+        const lf::StripUnit u = walk.unit(0);
+        issue(u.n, u.strip * TW, u.t_first * TH + HALO, TH);
     }
-    for (int ui = 0; ui < my_units; ++ui) {
-    int n, tx0, t_first, t_count;
-    unit_of(ui, n, tx0, t_first, t_count);
-    const int cur_rem = unit_rem;   // (unit_of is called again for the next segment's prefetch)
+    for (int ui = 0; ui < walk.units; ++ui) {
+    const lf::StripUnit un = walk.unit(ui);
+    const int n = un.n, tx0 = un.strip * TW, t_first = un.t_first, t_count = un.t_count;
     for (int tt = 0; tt < t_count; ++tt) {
         __syncthreads();  // the previous tile's operand reads are done (first pass: weights / lsc / lst staged)
         const int ty0 = (t_first + tt) * TH;
@@ -321,30 +286,17 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
         // the next tile's new rows: in flight during the MFMAs and the epilogue
         if (tt + 1 < t_count) {
             issue(n, tx0, ty0 + TH + HALO, TH);
-        } else if (ui + 1 < my_units) {
-            unit_of(ui + 1, sn, stx0, stf, stc);
-            issue(sn, stx0, stf * TH + HALO, TH);
+        } else if (ui + 1 < walk.units) {
+            const lf::StripUnit u = walk.unit(ui + 1);
+            issue(u.n, u.strip * TW, u.t_first * TH + HALO, TH);
         }
         // the epilogue's read-modify-write operands: requested now, consumed after the MFMAs
         uint16_t* yb = static_cast<uint16_t*>(p.y) + (size_t)n * p.cout * hw;
         const int gy = ty0 + erow, gx = tx0 + ecol;
         const bool ok = gy < p.h && gx < p.w;  // the 8-pixel group is inside or outside as a whole (w % 8 == 0)
         const size_t po = ok ? (size_t)gy * p.w + gx : 0;
-        if (accumulate) {
-#pragma unroll
-            for (int cb = 0; cb < NCO; ++cb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    rold[cb][j] = *reinterpret_cast<const uvec*>(yb + (size_t)(cb * 32 + 8 * j + ec) * hw + po);
-        }
-        if (masked) {
-            const uint16_t* my = p.stat_mask_y + (size_t)n * p.cout * hw;
-#pragma unroll
-            for (int cb = 0; cb < NCO; ++cb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    rmask[cb][j] = *reinterpret_cast<const uvec*>(my + (size_t)(cb * 32 + 8 * j + ec) * hw + po);
-        }
+        if (accumulate) lf::row8_request(rold, yb, 0, ec, hw, po);
+        if (masked) lf::row8_request(rmask, p.stat_mask_y + (size_t)n * p.cout * hw, 0, ec, hw, po);
         __syncthreads();
         // patch row r of this tile (image row ty0 - HALO + r) sits in ring slot (ty0 + r) mod PH
         unsigned rowpp[TAPS == 9 ? 3 : 1];
@@ -425,44 +377,12 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
 #pragma unroll
             for (int j = 2 * hf; j < 2 * hf + 2; ++j) {
                 const int cl = 8 * j + ec, co = cb * 32 + cl;
-                const lf::f32x4 a0 = *reinterpret_cast<const lf::f32x4*>(le + (cl & 15) * 256 + 8 * eg);
-                const lf::f32x4 a1 = *reinterpret_cast<const lf::f32x4*>(le + (cl & 15) * 256 + 8 * eg + 4);
-                float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                if (accumulate)
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        v[e] += bf16_up(rold[cb][j][e / 2] & 0xffffu);
-                        v[e + 1] += bf16_up(rold[cb][j][e / 2] >> 16);
-                    }
-                if (p.out_scale != nullptr) {
-                    const float osc = los[co], osh = los[COUT + co];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaf(v[e], osc, osh);
-                }
-                if (p.out_relu)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                uvec o;
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) o[e / 2] = pack_bf16(v[e], v[e + 1]);
+                const uvec o = lf::row8_finish(le + (cl & 15) * 256 + 8 * eg, accumulate, rold[cb][j],
+                                               p.out_scale != nullptr, &los[co], &los[COUT + co], p.out_relu);
                 if (ok) *reinterpret_cast<uvec*>(yb + (size_t)co * hw + po) = o;
                 if (!stats || !ok) continue;
                 float a = 0.f, b = 0.f;
-                if (!masked) {   // (one loop per kind of sum: the kind is uniform, the loops are unrolled)
-                    const float pv = lst[co];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, false, pv, 0.f, 0.f,
-                                            0.f, 0, a, b);
-                } else {
-                    const float msc = lst[co], msh = lst[COUT + co];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const unsigned mw = rmask[cb][j][e / 2];
-                        lf::stat_accumulate(bf16_up((e & 1) ? o[e / 2] >> 16 : o[e / 2] & 0xffffu), true, true, 0.f,
-                                            bf16_up((e & 1) ? mw >> 16 : mw & 0xffffu), msc, msh, p.mask_relu, a, b);
-                    }
-                }
+                lf::row8_sums(o, masked, &lst[co], &lst[co], &lst[COUT + co], rmask[cb][j], p.mask_relu, a, b);
                 s1[cb][j] += a;
                 s2[cb][j] += b;
             }
@@ -486,7 +406,7 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
             }
         __syncthreads();
         for (int c = tid; c < COUT; c += kT)
-            p.unit_sums[((size_t)n * UI + cur_rem) * p.cout + c] =
+            p.unit_sums[((size_t)n * (p.tiles_x * p.segs) + un.rem) * p.cout + c] =
                 (red[c] + red[COUT + c]) + (red[2 * COUT + c] + red[3 * COUT + c]);
     }
     }
@@ -510,17 +430,7 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
                 }
             }
         __syncthreads();
-        for (int c = tid; c < COUT; c += kT) {
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {   // fixed order: deterministic
-                a += red[(v * COUT + c) * 2];
-                b += red[(v * COUT + c) * 2 + 1];
-            }
-            float* dst = p.stat_part + ((size_t)c * (size_t)p.stat_tiles + blockIdx.x) * 2;
-            dst[0] = a;
-            dst[1] = b;
-        }
+        lf::write_stat_part<4, COUT>(p.stat_part, p.stat_tiles, p.cout, blockIdx.x, 0, red, tid, kT);
     }
 }
 
@@ -551,12 +461,7 @@ lf::ConvBf16sPlan plan_s(int n, int cin, int h, int w, int cout, int ksize, int 
     // batches): a segment re-stages the two rows above it, so whole strips are what the full-size step gets
     // (batch 256 @224: 1,024 strips of 56 tiles; @112: 512 strips in two segments of 14 tiles).
     const int strips = n * pl.tiles_x;
-    int segs = (4 * 256 + strips - 1) / strips;
-    const int max_segs = (pl.tiles_y + 3) / 4;        // at least four tiles to a segment
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    pl.seg_tiles = (pl.tiles_y + segs - 1) / segs;
-    pl.segs = (pl.tiles_y + pl.seg_tiles - 1) / pl.seg_tiles;
+    lf::strip_segments(strips, 4 * 256, pl.tiles_y, &pl.seg_tiles, &pl.segs);
     const int units = strips * pl.segs;
     pl.wgs = units < 256 * 2 ? units : 256 * 2;
     pl.interleave = (pl.wgs % 8 == 0 && n >= 8) ? 1 : 0;

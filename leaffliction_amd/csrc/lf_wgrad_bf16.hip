@@ -142,11 +142,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
 
     // What a workgroup walks: segments of column strips (a strip = TW columns of one image, a segment = seg_tiles
     // consecutive tiles of it from top to bottom); see plan_wgrad_bf16 for how they are dealt out.
-    const int SG = p.tiles_x, UI = SG * p.segs;
-    const int xk = blockIdx.x & 7, xj = blockIdx.x >> 3, xw = gridDim.x >> 3;
-    const int my_total = p.interleave ? (p.n > xk ? (p.n - xk + 7) / 8 : 0) * UI : p.n * UI;
-    const int my_first = p.interleave ? xj : (int)blockIdx.x, my_step = p.interleave ? xw : (int)gridDim.x;
-    const int my_units = my_total > my_first ? (my_total - my_first + my_step - 1) / my_step : 0;
+    const lf::StripWalk walk(p.n, p.tiles_x, p.tiles_y, p.seg_tiles, p.segs, p.interleave);
 
     // a position in the workgroup's sequence of tiles: unit ui, tile tt of it
     struct Cursor {
@@ -155,18 +151,17 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
     auto seek = [&](Cursor& c, int ui) {
         c.ui = ui;
         c.tt = 0;
-        if (ui >= my_units) return;
-        const int q = my_first + ui * my_step;
-        const int im = q / UI, rem = q - im * UI, seg = rem / SG;
-        c.n = p.interleave ? im * 8 + xk : im;
-        c.tx0 = (rem - seg * SG) * TW;
-        c.t_first = seg * p.seg_tiles;
-        c.t_count = min(p.seg_tiles, p.tiles_y - c.t_first);
+        if (ui >= walk.units) return;
+        const lf::StripUnit u = walk.unit(ui);
+        c.n = u.n;
+        c.tx0 = u.strip * TW;
+        c.t_first = u.t_first;
+        c.t_count = u.t_count;
     };
     auto advance = [&](Cursor& c) {
         if (++c.tt >= c.t_count) seek(c, c.ui + 1);
     };
-    auto valid = [&](const Cursor& c) { return c.ui < my_units; };
+    auto valid = [&](const Cursor& c) { return c.ui < walk.units; };
 
     // A tile's A patch is rows ty0 - HALO .. ty0 + TH + HALO - 1 of the strip.  The first tile of a segment stages
     // all PH of them, every other tile only the TH new ones (patch rows 2 * HALO .. PH - 1): the rest is in the ring.
@@ -237,6 +232,13 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
         }
     };
 
+    // the producer's BatchNorm (+ReLU) on the values v of A's channel c (inside the workgroup's block), in fp32
+    auto prologue = [&](int c, auto& v) {
+        if (!pro) return;
+        const float sc = lsc[c], sh = lsc[32 * CIB + c];
+#pragma unroll
+        for (int e = 0; e < (int)(sizeof(v) / sizeof(float)); ++e) v[e] = lf::pro_apply(v[e], sc, sh, p.in_relu);
+    };
     // rb = ring slot of the tile's patch row 0; buf = which dY buffer
     auto commit = [&](const Cursor& c, int rb, int buf) {
         unsigned char* lx = lds;
@@ -265,50 +267,32 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
             // stands; every second channel the pair (c-1, c) goes to LDS, one dword per pixel
             unsigned char* img = ld + (quad >> 3) * (S::DPIX * 64);
             const unsigned pd = (unsigned)(row * TW + G * pg);
-            float prev[G];
+            lf::stage_quad<G>(
+                rg[k], ok,
+                [&](int i, float (&gv)[G]) {
+                    if (!bn) return;
+                    const int c = 4 * quad + i;  // channel inside the workgroup's block
+                    const float c0 = lbn[c], c1 = lbn[32 * COB + c], c2 = lbn[64 * COB + c], c3 = lbn[96 * COB + c],
+                                c4 = lbn[128 * COB + c];
+                    const float al = gated ? lal[c] : 1.f, ad = gated ? lal[32 * COB + c] : 0.f;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = 4 * quad + i;  // channel inside the workgroup's block
-                float gv[G];
-#pragma unroll
-                for (int e = 0; e < G; ++e) gv[e] = 0.f;
-                if (ok) {
-#pragma unroll
-                    for (int e = 0; e < G; e += 2) {
-                        gv[e] = bf16_up(rg[k][i][e / 2] & 0xffffu);
-                        gv[e + 1] = bf16_up(rg[k][i][e / 2] >> 16);
+                    for (int e = 0; e < G; ++e) {
+                        const float yv = lf::bf16_at(ry[k][i], e);
+                        float dz = fmaf(gv[e], al, ad);
+                        if (p.bn_relu && !(fmaf(yv, c0, c1) > 0.f)) dz = 0.f;
+                        gv[e] = fmaf(c2, dz, fmaf(c3, yv, c4));
                     }
-                    if (bn) {
-                        const float c0 = lbn[c], c1 = lbn[32 * COB + c], c2 = lbn[64 * COB + c],
-                                    c3 = lbn[96 * COB + c], c4 = lbn[128 * COB + c];
-                        const float al = gated ? lal[c] : 1.f, ad = gated ? lal[32 * COB + c] : 0.f;
+                    if (p.dy_out != nullptr && blockIdx.y == 0) {
+                        uvec o;
 #pragma unroll
-                        for (int e = 0; e < G; ++e) {
-                            const unsigned yw = ry[k][i][e / 2];
-                            const float yv = bf16_up((e & 1) ? yw >> 16 : yw & 0xffffu);
-                            float dz = fmaf(gv[e], al, ad);
-                            if (p.bn_relu && !(fmaf(yv, c0, c1) > 0.f)) dz = 0.f;
-                            gv[e] = fmaf(c2, dz, fmaf(c3, yv, c4));
-                        }
-                        if (p.dy_out != nullptr && blockIdx.y == 0) {
-                            uvec o;
-#pragma unroll
-                            for (int e = 0; e < G; e += 2) o[e / 2] = pack_bf16(gv[e], gv[e + 1]);
-                            *reinterpret_cast<uvec*>(p.dy_out + ((size_t)n * p.cout + co0 + c) * hw +
-                                                     (size_t)(ty0 + row) * p.w + tx0 + G * pg) = o;
-                        }
+                        for (int e = 0; e < G; e += 2) o[e / 2] = pack_bf16(gv[e], gv[e + 1]);
+                        *reinterpret_cast<uvec*>(p.dy_out + ((size_t)n * p.cout + co0 + c) * hw +
+                                                 (size_t)(ty0 + row) * p.w + tx0 + G * pg) = o;
                     }
-                }
-                if (i & 1) {
-#pragma unroll
-                    for (int e = 0; e < G; ++e)
-                        *reinterpret_cast<unsigned*>(img + img_off(pd + e, quad & 7) + 4 * (i >> 1)) =
-                            pack_bf16(prev[e], gv[e]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < G; ++e) prev[e] = gv[e];
-                }
-            }
+                },
+                [&](int e, int pair, unsigned dword) {
+                    *reinterpret_cast<unsigned*>(img + img_off(pd + e, quad & 7) + 4 * pair) = dword;
+                });
         }
         if (STEM) {
             // im2col row of this thread's pixel: "channel" = ci*9 + tap (27 used, 5 zero)
@@ -334,58 +318,20 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
                 int slot = rb + pr;
                 slot = slot >= S::NSLOT ? slot - S::NSLOT : slot;
                 const unsigned pi = (unsigned)(slot * PW + HALO + G * pg);
-                float prev[G];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v[G];
-#pragma unroll
-                    for (int e = 0; e < G; ++e) v[e] = 0.f;  // zero padding stays zero
-                    if (ok) {
-#pragma unroll
-                        for (int e = 0; e < G; e += 2) {
-                            v[e] = bf16_up(rx[k][i][e / 2] & 0xffffu);
-                            v[e + 1] = bf16_up(rx[k][i][e / 2] >> 16);
-                        }
-                        if (pro) {
-                            const float sc = lsc[4 * quad + i], sh = lsc[32 * CIB + 4 * quad + i];
-#pragma unroll
-                            for (int e = 0; e < G; ++e) {
-                                v[e] = fmaf(v[e], sc, sh);
-                                if (p.in_relu) v[e] = fmaxf(v[e], 0.f);
-                            }
-                        }
-                    }
-                    if (i & 1) {
-#pragma unroll
-                        for (int e = 0; e < G; ++e)
-                            *reinterpret_cast<unsigned*>(img + img_off(pi + e, quad & 7) + 4 * (i >> 1)) =
-                                pack_bf16(prev[e], v[e]);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < G; ++e) prev[e] = v[e];
-                    }
-                }
+                lf::stage_quad<G>(
+                    rx[k], ok, [&](int i, float (&v)[G]) { prologue(4 * quad + i, v); },
+                    [&](int e, int pair, unsigned dword) {
+                        *reinterpret_cast<unsigned*>(img + img_off(pi + e, quad & 7) + 4 * pair) = dword;
+                    });
             }
 #pragma unroll
             for (int k = 0; k < HPT; ++k) {
                 const int u = tid + k * kT;
                 const int side = u & 1, t1 = u >> 1, quad = t1 % (8 * CIB), pr = pr0 + t1 / (8 * CIB);
                 if (pr >= PH) continue;
-                float v[4] = {0.f, 0.f, 0.f, 0.f};
-                if (hmask >> k & 1u) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        v[i] = RAWH ? bf16_up(rh[k][i]) : bf16_up(i & 1 ? rh[k][i >> 1] >> 16 : rh[k][i >> 1] & 0xffffu);
-                    if (pro)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            v[i] = fmaf(v[i], lsc[4 * quad + i], lsc[32 * CIB + 4 * quad + i]);
-                            if (p.in_relu) v[i] = fmaxf(v[i], 0.f);
-                        }
-                }
-                u32x2 o;
-                o.x = pack_bf16(v[0], v[1]);
-                o.y = pack_bf16(v[2], v[3]);
+                const u32x2 o = lf::stage_halo_quad(
+                    hmask >> k & 1u, [&](int i) { return RAWH ? bf16_up(rh[k][RAWH ? i : 0]) : lf::bf16_at(rh[k], i); },
+                    [&](int i, float (&v)[1]) { prologue(4 * quad + i, v); });
                 unsigned char* img = lx + (quad >> 3) * (S::XPIX * 64);
                 int slot = rb + pr;
                 slot = slot >= S::NSLOT ? slot - S::NSLOT : slot;
@@ -564,12 +510,7 @@ WgBf16Plan plan_wgrad_bf16(int n, int cin, int cout, int h, int w, int ksize) {
     int want = (256 * 2) / (pl.gy * pl.gz);
     if (want < 1) want = 1;
     const int strips = n * pl.tiles_x;
-    int segs = (want + strips - 1) / strips;
-    const int max_segs = (pl.tiles_y + 3) / 4;        // at least four tiles to a segment
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    pl.seg_tiles = (pl.tiles_y + segs - 1) / segs;
-    pl.segs = (pl.tiles_y + pl.seg_tiles - 1) / pl.seg_tiles;
+    lf::strip_segments(strips, want, pl.tiles_y, &pl.seg_tiles, &pl.segs);
     const int units = strips * pl.segs;
     pl.splits = want < units ? want : units;
     // an image's strips side by side on one XCD (see the kernel) when the grid's x extent divides over the XCDs

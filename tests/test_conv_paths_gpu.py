@@ -67,6 +67,10 @@ BF16_WGRAD_PATHS = [
     (8, 64, 128, 12, 56, 1, False, True, False, True, False),
     (10, 32, 32, 12, 224, 3, True, False, False, False, False),
     (33, 64, 128, 12, 56, 1, False, False, False, False, False),
+    # the per-XCD interleave together with several segments per strip (what a small training batch runs): 9 tiles
+    # per strip in 3 segments of 3; two strips per image with 5 tiles per strip in segments of 3 and 2
+    (8, 32, 32, 36, 56, 3, True, True, True, True, True),
+    (8, 32, 32, 40, 64, 3, True, True, True, True, True),
 ]
 # fp32 convolution (forward / input gradient): n, cin, cout, h, w, k, prologue, statistics, mask sums, accumulate
 F32_CONV_PATHS = [
