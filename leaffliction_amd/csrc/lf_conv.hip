@@ -147,6 +147,29 @@ __device__ __forceinline__ void wino_output(const float (&m)[16], float (&y)[4])
 // ---------------------------------------------------------------------------
 constexpr int kMaxProC = 512;  // prologue scale/shift staged in LDS for up to this many channels
 
+// The per-channel constants a workgroup reads, staged in LDS once: the producer's BatchNorm scale/shift of the
+// first kMaxProC input channels (lsc[2][kMaxProC]) and the epilogue's statistics constants of the workgroup's CT
+// couts from co0 on (lep[3][CT]: pivot, 0 where there is none; mask scale; mask shift).  A kernel calls this
+// right after it has issued chunk 0's patch loads, so the wait for these few L2-resident floats lies under the
+// patch's own.  The barriers of the K-loop stand between the writes and every reader.
+template <int CT>
+__device__ __forceinline__ void stage_channel_consts(const ConvArgs& p, float* lsc, float* lep, int co0, int tid) {
+    static_assert(CT <= kThreads, "at most one cout per thread");
+    if (p.in_scale != nullptr) {
+        for (int c = tid; c < p.cin && c < kMaxProC; c += kThreads) {
+            lsc[c] = p.in_scale[c];
+            lsc[kMaxProC + c] = p.in_shift[c];
+        }
+    }
+    if (p.stat_part != nullptr && tid < CT) {
+        const int co = co0 + tid, coc = min(co, p.cout - 1);
+        const bool masked = p.stat_mask_y != nullptr;
+        lep[tid] = (!masked && p.stat_pivot != nullptr && co < p.cout) ? p.stat_pivot[co] : 0.f;
+        lep[CT + tid] = masked ? p.mask_scale[coc] : 0.f;
+        lep[2 * CT + tid] = masked ? p.mask_shift[coc] : 0.f;
+    }
+}
+
 // XCD-aware order: workgroups are dealt to the eight XCDs round-robin in dispatch order (x, then y,
 // then z), each XCD with its own L2.  XCD k takes the k-th contiguous share of the (tile, channel
 // group, strip) space, so the tiles that share halo rows meet in one L2.  Strip rows ty0 .. ty0+TH-1:
@@ -209,14 +232,7 @@ struct PatchStage {
     unsigned hg[HPT > 0 ? HPT : 1], hl[HPT > 0 ? HPT : 1];
     unsigned okmask = 0;  // bit i: interior item i in-image; bit 16+i: halo item i in-image
 
-    // also stages the producer's BatchNorm scale/shift in lsc, once per workgroup
-    __device__ __forceinline__ PatchStage(const ConvArgs& p, const ConvTile<TW, TH, HALO, STK>& t, float* lsc, int tid) {
-        if (p.in_scale != nullptr) {
-            for (int c = tid; c < p.cin && c < kMaxProC; c += kThreads) {
-                lsc[c] = p.in_scale[c];
-                lsc[kMaxProC + c] = p.in_shift[c];
-            }
-        }
+    __device__ __forceinline__ PatchStage(const ConvArgs& p, const ConvTile<TW, TH, HALO, STK>& t, int tid) {
         hw = (size_t)p.h * p.wd;
         const unsigned uhw = (unsigned)hw;
 #pragma unroll
@@ -357,6 +373,7 @@ void conv_mfma_kernel(ConvArgs p) {
 
     __shared__ __attribute__((aligned(16))) float lds[PATCH + WSZ];
     __shared__ float lsc[2 * kMaxProC];
+    __shared__ float lep[3 * CT];
     float* lp = lds;
     float* lw = lds + PATCH;
 
@@ -420,7 +437,7 @@ void conv_mfma_kernel(ConvArgs p) {
         // with > 64 accumulators there are no registers left to hold the weight prefetch: those
         // variants prefetch the patch only and fetch the (L2-resident) weights in the store phase
         constexpr bool kPrefetchW = MB * NB * 16 <= 64;
-        Patch patch(p, t, lsc, tid);
+        Patch patch(p, t, tid);
         // weight rows: byte offsets from the chunk's first row, kBufOob for cout columns beyond the
         // tensor; rows beyond Cin fall outside the chunk's buffer size -> zeros
         unsigned wg[WPT];
@@ -448,6 +465,7 @@ void conv_mfma_kernel(ConvArgs p) {
         };
         patch.load(p, xin, 0);
         if (kPrefetchW) load_weights(0);
+        stage_channel_consts<CT>(p, lsc, lep, co0, tid);
         for (int ch = 0; ch < nchunks; ++ch) {
             __syncthreads();  // previous chunk's LDS reads are done
             store_chunk(ch * kKC);
@@ -463,6 +481,7 @@ void conv_mfma_kernel(ConvArgs p) {
         constexpr int WROWS = kKC * TAPS, RPP = kThreads / CT;
         const int wcol = tid % CT, wrow0 = tid / CT;
         const bool wcol_ok = co0 + wcol < p.cout;
+        stage_channel_consts<CT>(p, lsc, lep, co0, tid);
         for (int ch = 0; ch < nchunks; ++ch) {
             const int c0 = ch * kKC;
             __syncthreads();
@@ -508,6 +527,9 @@ void conv_mfma_kernel(ConvArgs p) {
     for (int m = 0; m < MB; ++m) {
 #pragma unroll
         for (int rg = 0; rg < 16; rg += RG) {
+            // keeps the later groups' LDS reads of the statistics constants from being hoisted to the top of the
+            // epilogue, where they cost the 112- and 128-accumulator variants their third wave per SIMD
+            asm volatile("" ::: "memory");
             float oldv[RG][NB], yv[RG][NB];
             if (p.accumulate) {
 #pragma unroll
@@ -545,12 +567,12 @@ void conv_mfma_kernel(ConvArgs p) {
                 if (!stats) continue;
                 float s1 = 0.f, s2 = 0.f;
                 if (!masked) {  // forward statistics about the pivot
-                    const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
+                    const float pv = lep[cl];
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb)
                         lf::stat_accumulate(acc[m][nb][r], pix_ok[nb], false, pv, 0.f, 0.f, 0.f, 0, s1, s2);
                 } else {  // backward sums of the BatchNorm this gradient feeds
-                    const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
+                    const float msc = lep[CT + cl], msh = lep[2 * CT + cl];
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb)
                         lf::stat_accumulate(acc[m][nb][r], co_ok && pix_ok[nb], true, 0.f, yv[rr][nb], msc, msh,
@@ -594,6 +616,7 @@ void conv_wino_kernel(ConvArgs p) {
 
     __shared__ __attribute__((aligned(16))) float lds[PATCH + WSZ];
     __shared__ float lsc[2 * kMaxProC];
+    __shared__ float lep[3 * CT];
     float* lp = lds;
     float* lw = lds + PATCH;
 
@@ -695,12 +718,15 @@ void conv_wino_kernel(ConvArgs p) {
         // The patch is prefetched into registers during the previous chunk's MFMAs.  U is not: its slice is
         // L2-resident (every workgroup reads the same few KB), so it is fetched in the store phase, in flight
         // while the patch goes to LDS.  Prefetching it too (4 * UPT registers held across the MFMAs) measured
-        // 0.8 ms per step slower.
-        Patch patch(p, t, lsc, tid);
+        // 0.8 ms per step slower.  Chunk 0's U and the per-channel constants are asked for right behind chunk
+        // 0's patch, so the workgroup's first wait covers all three.
+        Patch patch(p, t, tid);
         patch.load(p, xin, 0);
+        load_u(0);
+        stage_channel_consts<CT>(p, lsc, lep, co0, tid);
         for (int ch = 0; ch < nchunks; ++ch) {
             __syncthreads();  // previous chunk's LDS reads are done
-            load_u(ch * kKC);
+            if (ch > 0) load_u(ch * kKC);
             patch.store(p, lp, lsc, ch * kKC, tid);
             store_u();
             __syncthreads();
@@ -709,6 +735,7 @@ void conv_wino_kernel(ConvArgs p) {
         }
     } else {
         // ---------------- scalar staging (ragged shapes / partial tiles) ----------------
+        stage_channel_consts<CT>(p, lsc, lep, co0, tid);
         for (int ch = 0; ch < nchunks; ++ch) {
             const int c0 = ch * kKC;
             __syncthreads();
@@ -728,12 +755,21 @@ void conv_wino_kernel(ConvArgs p) {
     const float* my = masked ? p.stat_mask_y + (size_t)t.n * p.cout * hw : nullptr;
     // epilogue: register i of wacc[m][nb][pos] is M[pos] of cout (l >> 4) * 4 + i of cout-block m
     // and tile l & 15 of tile-block nb; the inverse transform gives its 2x2 pixels (both rows in one
-    // image: the strip seam row ra is even).  Pixel pairs are stored as float2 where y allows it.
+    // image: the strip seam row ra is even).  Pixel pairs are loaded and stored as float2 where y (and
+    // the mask tensor) allow it: W even makes every offset here even and both pixels of a pair in-image
+    // together.
+    // The 4 * MB (cout-block, register) steps go in groups of G.  A group first issues every read it
+    // needs (the old outputs when accumulating, the mask tensor for the BatchNorm-backward sums),
+    // unconditionally and from clamped offsets, so one memory latency is exposed per group instead of
+    // one per step; only then does it transform, add and store, step by step in the old order.  A wave
+    // whose tiles and couts all lie inside the tensor (FULL) stores without a branch.
     // Statistics: per lane over its tiles' pixels, then over the 16 lanes of a row (DPP), then over
     // the WPX waves in LDS.
-    const bool y2 = (p.wd & 1) == 0 && (reinterpret_cast<size_t>(p.y) & 7) == 0;
+    const bool y2 = (p.wd & 1) == 0 && (reinterpret_cast<size_t>(p.y) & 7) == 0 &&
+                    (reinterpret_cast<size_t>(p.stat_mask_y) & 7) == 0;
     bool pok[NB][4];
     unsigned pofs[NB][4];  // pixel offsets, 0 when outside the image
+    bool lane_full = true;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
         const int tt = (wave_px * NB + nb) * 16 + wl;
@@ -747,77 +783,117 @@ void conv_wino_kernel(ConvArgs p) {
             const int py = oy + (q >> 1), px = ox + (q & 1);
             pok[nb][q] = img_ok && py < p.h && px < p.wd;
             pofs[nb][q] = pok[nb][q] ? base + (unsigned)py * (unsigned)p.wd + (unsigned)px : 0u;
+            lane_full = lane_full && (pok[nb][q] || tt >= NT);
         }
     }
+    constexpr int STEPS = 4 * MB, G = (STEPS * NB <= 8 ? STEPS : 8 / NB);  // 32 pixels per lane and tensor in flight
+    static_assert(STEPS % G == 0, "whole groups");
+    auto epilogue = [&](auto full_c) {
+        // FULL: every tile slot below NT has all four pixels in the image, y2 holds and no cout is absent
+        constexpr bool FULL = decltype(full_c)::value;
 #pragma unroll
-    for (int m = 0; m < MB; ++m) {
+        for (int g0 = 0; g0 < STEPS; g0 += G) {
+            float oldv[G][NB][4], yv[G][NB][4];
+            // one tensor after the other, each behind a single uniform branch: with a branch per step between
+            // the loads the compiler falls back to full waits
+            auto batch = [&](const float* src, float (&dst)[G][NB][4]) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int cl = m * 16 + 4 * wq + i;
-            const int co = co0 + cl;
-            const bool co_ok = co < p.cout;
-            const size_t cofs = (size_t)min(co, p.cout - 1) * hw;
-            float out[NB][4], oldv[NB][4], yv[NB][4];
+                for (int gs = 0; gs < G; ++gs) {
+                    const int m = (g0 + gs) / 4, i = (g0 + gs) % 4;
+                    const float* sp = src + (size_t)min(co0 + m * 16 + 4 * wq + i, p.cout - 1) * hw;
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                float mm[16];
+                    for (int nb = 0; nb < NB; ++nb) {
+                        if (FULL || y2) {
 #pragma unroll
-                for (int q = 0; q < 16; ++q) mm[q] = wacc[m][nb][q][i];
-                wino_output(mm, out[nb]);
-                if (p.accumulate) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) oldv[nb][q] = yout[cofs + pofs[nb][q]];
-                }
-                if (masked) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) yv[nb][q] = my[cofs + pofs[nb][q]];
-                }
-            }
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                if (p.accumulate) {  // the statistics see the sum
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) out[nb][q] += oldv[nb][q];
-                }
-                if (co_ok) {
-#pragma unroll
-                    for (int r = 0; r < 2; ++r) {
-                        float* dst = yout + cofs + pofs[nb][2 * r];
-                        if (y2 && pok[nb][2 * r] && pok[nb][2 * r + 1]) {
-                            *reinterpret_cast<float2*>(dst) = make_float2(out[nb][2 * r], out[nb][2 * r + 1]);
+                            for (int r = 0; r < 2; ++r) {
+                                const float2 v2 = *reinterpret_cast<const float2*>(sp + pofs[nb][2 * r]);
+                                dst[gs][nb][2 * r] = v2.x;
+                                dst[gs][nb][2 * r + 1] = v2.y;
+                            }
                         } else {
-                            if (pok[nb][2 * r]) dst[0] = out[nb][2 * r];
-                            if (pok[nb][2 * r + 1]) yout[cofs + pofs[nb][2 * r + 1]] = out[nb][2 * r + 1];
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) dst[gs][nb][q] = sp[pofs[nb][q]];
                         }
                     }
                 }
-            }
-            if (!stats) continue;
-            float s1 = 0.f, s2 = 0.f;
-            if (!masked) {  // forward statistics about the pivot
-                const float pv = (p.stat_pivot != nullptr && co_ok) ? p.stat_pivot[co] : 0.f;
+            };
+            if (p.accumulate) batch(yout, oldv);
+            if (masked) batch(my, yv);
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb)
+            for (int gs = 0; gs < G; ++gs) {
+                const int m = (g0 + gs) / 4, i = (g0 + gs) % 4;
+                const int cl = m * 16 + 4 * wq + i;
+                const int co = co0 + cl;
+                const bool co_ok = FULL || co < p.cout;
+                const size_t cofs = (size_t)min(co, p.cout - 1) * hw;
+                float out[NB][4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        lf::stat_accumulate(out[nb][q], pok[nb][q], false, pv, 0.f, 0.f, 0.f, 0, s1, s2);
-            } else {  // backward sums of the BatchNorm this gradient feeds
-                const float msc = p.mask_scale[min(co, p.cout - 1)], msh = p.mask_shift[min(co, p.cout - 1)];
+                for (int nb = 0; nb < NB; ++nb) {
+                    float mm[16];
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb)
+                    for (int q = 0; q < 16; ++q) mm[q] = wacc[m][nb][q][i];
+                    wino_output(mm, out[nb]);
+                }
 #pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        lf::stat_accumulate(out[nb][q], co_ok && pok[nb][q], true, 0.f, yv[nb][q], msc, msh, p.mask_relu,
-                                            s1, s2);
-            }
-            s1 = row_sum16(s1);
-            s2 = row_sum16(s2);
-            if (wl == 0) {
-                red[(wave_px * CT + cl) * 2] = s1;
-                red[(wave_px * CT + cl) * 2 + 1] = s2;
+                for (int nb = 0; nb < NB; ++nb) {
+                    if (p.accumulate) {  // the statistics see the sum
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) out[nb][q] += oldv[gs][nb][q];
+                    }
+                    if (FULL) {
+                        // slots beyond NT (only where the tiles do not fill the waves) are the one thing left to mask
+                        if (NT == WPX * NB * 16 || pok[nb][0]) {
+#pragma unroll
+                            for (int r = 0; r < 2; ++r)
+                                *reinterpret_cast<float2*>(yout + cofs + pofs[nb][2 * r]) =
+                                    make_float2(out[nb][2 * r], out[nb][2 * r + 1]);
+                        }
+                    } else if (co_ok) {
+#pragma unroll
+                        for (int r = 0; r < 2; ++r) {
+                            float* dst = yout + cofs + pofs[nb][2 * r];
+                            if (y2 && pok[nb][2 * r] && pok[nb][2 * r + 1]) {
+                                *reinterpret_cast<float2*>(dst) = make_float2(out[nb][2 * r], out[nb][2 * r + 1]);
+                            } else {
+                                if (pok[nb][2 * r]) dst[0] = out[nb][2 * r];
+                                if (pok[nb][2 * r + 1]) yout[cofs + pofs[nb][2 * r + 1]] = out[nb][2 * r + 1];
+                            }
+                        }
+                    }
+                }
+                if (!stats) continue;
+                float s1 = 0.f, s2 = 0.f;
+                if (!masked) {  // forward statistics about the pivot
+                    const float pv = lep[cl];
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            lf::stat_accumulate(out[nb][q], pok[nb][q], false, pv, 0.f, 0.f, 0.f, 0, s1, s2);
+                } else {  // backward sums of the BatchNorm this gradient feeds
+                    const float msc = lep[CT + cl], msh = lep[2 * CT + cl];
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            lf::stat_accumulate(out[nb][q], co_ok && pok[nb][q], true, 0.f, yv[gs][nb][q], msc, msh,
+                                                p.mask_relu, s1, s2);
+                }
+                s1 = row_sum16(s1);
+                s2 = row_sum16(s2);
+                if (wl == 0) {
+                    red[(wave_px * CT + cl) * 2] = s1;
+                    red[(wave_px * CT + cl) * 2 + 1] = s2;
+                }
             }
         }
-    }
+    };
+    // wave-uniform: voted over the lanes' own store predicates, so the branch-free path cannot store where the
+    // general one would not
+    if (__all(y2 && lane_full && co0 + CT <= p.cout))
+        epilogue(std::true_type{});
+    else
+        epilogue(std::false_type{});
     if (stats) write_stat_part<WPX, CT>(p, red, t.bz, t.tile, co0, tid);
 }
 
