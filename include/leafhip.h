@@ -482,7 +482,8 @@ int lf_conv2d_f32(const float* x, const float* w, float* y, int n, int cin, int 
  * shared with the fp32 path.  Weights are packed once per model with
  * lf_conv2d_bf16_prep_weights: fp32 IKO [cin][k*k][cout] -> bf16 [ceil(cin/16)][k*k][cout][16]
  * (lf_conv2d_bf16_weight_elems uint16 elements, channels past cin zero).  Requires w % 4 == 0,
- * cout % 32 == 0, ksize 1 or 3.  Tolerance vs lf_conv2d_f32: bf16 operand rounding, 2^-8
+ * cout % 32 == 0 (lf_conv2d_bf16_act with bf16 output also takes cout == 16 with w % 8 == 0 and cin <= 3 in fp32
+ * or cin 16 / 32 in bf16; 1x1: cin 32), ksize 1 or 3.  Tolerance vs lf_conv2d_f32: bf16 operand rounding, 2^-8
  * relative per product (tests bound the error by 2e-2 of the output's scale). */
 size_t lf_conv2d_bf16_weight_elems(int cin, int cout, int ksize);
 int lf_conv2d_bf16_prep_weights(const float* w_iko, uint16_t* wprep, int cin, int cout, int ksize,
@@ -542,7 +543,9 @@ int lf_conv2d_bf16_act_mean(const void* x, int x_bf16, const uint16_t* wprep, ui
  *     (feed lf_bn_train_stats_tiles_f32; pivot = the moving mean, may be null);
  *   mask_y != null: the backward sums of the BatchNorm this gradient feeds, {sum d, sum d*mask_y}
  *     with d = y*[mask_y*mask_scale+mask_shift > 0 or !mask_relu] (feed lf_bn_bwd_sums_tiles_f32).
- * Requires w % 4 == 0, cout % 32 == 0, ksize 1 or 3, 16-byte aligned x / wprep. */
+ * Requires w % 4 == 0, ksize 1 or 3, 16-byte aligned x / wprep, and cout % 32 == 0 or else cout == 16 with
+ * w % 8 == 0 and an input of cin <= 3 in fp32 (3x3) or cin 16 (3x3) / 32 (3x3, 1x1) in bf16 — the layers of a
+ * 16-wide stage and the input gradients that flow into it, which only the streaming path serves. */
 long long lf_conv2d_bf16_stats_tiles(int n, int cin, int h, int w, int cout, int ksize, int x_bf16);
 int lf_conv2d_bf16_train(const void* x, int x_bf16, const uint16_t* wprep, uint16_t* y, int n, int cin,
                          int h, int w, int cout, int ksize, const float* in_scale,
@@ -558,8 +561,8 @@ int lf_conv2d_bf16_train(const void* x, int x_bf16, const uint16_t* wprep, uint1
  * BatchNormalization(+ReLU) that follows the conv, in which case the BatchNorm backward is formed
  * while staging exactly as lf_conv2d_wgrad_bn_f32 does (alpha_nc / add_nc [n][cout] optional,
  * coef [5][cout] from lf_bn_bwd_sums*_f32) and dY is also written to dy_out (bf16, may be null)
- * for the input-gradient convolution.  Requires w % 4 == 0, cout % 32 == 0, cin % 4 == 0 (or the
- * stem), 8-byte aligned tensors.  workspace >= lf_conv2d_wgrad_bf16_workspace(...) bytes. */
+ * for the input-gradient convolution.  Requires w % 4 == 0, cout == 16 or cout % 32 == 0, cin % 4 == 0
+ * (or the stem), 16-byte aligned tensors.  workspace >= lf_conv2d_wgrad_bf16_workspace(...) bytes. */
 size_t lf_conv2d_wgrad_bf16_workspace(int n, int cin, int h, int w, int cout, int ksize);
 int lf_conv2d_wgrad_bf16(const void* x, const uint16_t* g, const uint16_t* bn_y, const float* alpha_nc,
                          const float* add_nc, const float* coef, int bn_relu, uint16_t* dy_out,
@@ -609,7 +612,7 @@ int lf_conv2d_wgrad_variant(int n, int cin, int h, int wd, int cout, int ksize);
  *    fused BN allowed}
  * lf_conv2d_bf16_plan (entry 0 = lf_conv2d_bf16_act, 1 = _act_mean, 2 = _train; accumulate and mask
  * as passed to _train), out[14]:
- *   {streaming, TAPS, CI, NCO, NB, TW, TH, XBF, YBF, TR, RMW (streaming) or WIDE (K-chunked),
+ *   {streaming, TAPS, CI, NCO (0: one 16-channel block), NB, TW, TH, XBF, YBF, TR, RMW (streaming) or WIDE (K-chunked),
  *    segments > 1, interleave, units per workgroup > 1}   (fields a kernel has not are 0)
  * lf_conv2d_wgrad_bf16_plan (lf_conv2d_wgrad_bf16), out[13]:
  *   {TAPS, TW, TH, CIB, COB, STEM, G, WPRQ, segments > 1, interleave, units per workgroup > 1,

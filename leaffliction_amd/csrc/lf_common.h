@@ -127,10 +127,12 @@ struct WgradBf16Args {
     int bn_relu;
 };
 
-// The streaming kernel's plan for a shape: the instantiation <CI, NCO, TW, TH> and how the grid of `wgs` workgroups
-// walks the column strips.  ok = false: the shape is not covered.
+// The streaming kernel's plan for a shape: the instantiation <CI, NCO, TW, TH> (xbf: bf16 input, c16: one
+// 16-channel output block instead of nco 32-channel ones) and how the grid of `wgs` workgroups walks the column
+// strips.  ok = false: the shape is not covered.
 struct ConvBf16sPlan {
     bool ok;
+    int xbf, c16;
     int ci, nco, tw, th, tiles_x, tiles_y, seg_tiles, segs, wgs, interleave;
 };
 ConvBf16sPlan conv_bf16s_plan(int n, int cin, int h, int w, int cout, int ksize, int x_bf16);
@@ -407,15 +409,16 @@ __device__ __forceinline__ u32x2 stage_halo_quad(bool ok, Widen widen, Transform
 
 // The epilogue of a thread that finishes EIGHT consecutive pixels of one output channel (16 bytes of bf16), the
 // accumulators having gone through a transpose buffer in LDS.
-// row8_request: the read-modify-write operand rows of the thread's channels co0 + 32 * cb + 8 * j + ec, eight
-// pixels at offset po of each channel plane of `image` — asked for before the MFMAs, used after them.
-template <int NCB>
-__device__ __forceinline__ void row8_request(u32x4 (&r)[NCB][4], const uint16_t* image, int co0, int ec, size_t hw,
+// row8_request: the read-modify-write operand rows of the thread's channels co0 + 32 * cb + 8 * j + ec (j < NJ:
+// four rows of 8 channels to a 32-channel block, two to a 16-channel one), eight pixels at offset po of each
+// channel plane of `image` — asked for before the MFMAs, used after them.
+template <int NCB, int NJ>
+__device__ __forceinline__ void row8_request(u32x4 (&r)[NCB][NJ], const uint16_t* image, int co0, int ec, size_t hw,
                                              size_t po) {
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < NJ; ++j)
             r[cb][j] = *reinterpret_cast<const u32x4*>(image + (size_t)(co0 + cb * 32 + 8 * j + ec) * hw + po);
 }
 // row8_finish: acc8 = the eight fp32 accumulators (16-byte aligned LDS) -> (+ old) -> (* *osc + *osh, read only

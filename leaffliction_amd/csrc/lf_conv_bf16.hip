@@ -428,7 +428,8 @@ inline bool bf16_wide(bool ybf, int nco, int w) { return ybf && nco == 2 && w % 
 
 // The entry points' routing, asked once per call: the streaming kernel (lf_conv_bf16s.hip) or the K-chunked one, and
 // the partial sums either leaves.  The training convolution streams every shape the streaming kernel covers; the
-// inference ones (kBf16Act, kBf16ActMean) only the 32-channel layers with bf16 output:
+// inference ones (kBf16Act, kBf16ActMean) only the 16- and 32-channel layers with bf16 output (16 output channels
+// have no other kernel: the K-chunked one works in 32-channel blocks):
 // the 224x224 stage (stem, 32->32): the streaming kernel (resident filter bank, 16-byte accesses).
 // The 64-channel layers of the 112x112 stage stay on the K-chunked kernel: it was well ahead there
 // without a read-modify-write epilogue (1.7 ms against 3.2 ms at 64->64, batch 1,024) and is level with
@@ -444,7 +445,7 @@ struct Bf16Route {
 Bf16Route bf16_route(int entry, int y_bf16, int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
     Bf16Route r{};
     if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0) return r;
-    if (entry == kBf16Train || (y_bf16 && cout == 32)) r.s = lf::conv_bf16s_plan(n, cin, h, w, cout, ksize, x_bf16);
+    if (entry == kBf16Train || (y_bf16 && (cout == 32 || cout == 16))) r.s = lf::conv_bf16s_plan(n, cin, h, w, cout, ksize, x_bf16);
     r.streams = r.s.ok;
     r.units = r.streams ? r.s.tiles_x * r.s.segs : bf16_tiles(h, w, cout);
     r.parts = r.streams ? r.s.wgs : (long long)n * r.units;
@@ -510,7 +511,9 @@ static int conv_bf16_launch(const char* who, int entry, const Bf16Route& r, lf::
     LF_REQUIRE(a.n > 0 && a.cin > 0 && a.h > 0 && a.w > 0 && a.cout > 0, "%s: bad dims", who);
     LF_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize must be 1 or 3", who);
     LF_REQUIRE(a.w % 4 == 0, "%s: width must be a multiple of 4 (got %d)", who, a.w);
-    LF_REQUIRE(a.cout % 32 == 0, "%s: cout must be a multiple of 32 (got %d)", who, a.cout);
+    LF_REQUIRE(r.streams || a.cout % 32 == 0,
+               "%s: cout must be a multiple of 32, or a 16-channel shape of the streaming kernel (got cin %d cout %d)",
+               who, a.cin, a.cout);
     LF_REQUIRE((a.in_scale == nullptr) == (a.in_shift == nullptr), "%s: scale/shift must both be set", who);
     LF_REQUIRE(a.in_scale == nullptr || a.cin <= kMaxPrologueCin,
                "%s: a fused prologue takes at most %d input channels (got %d)", who, kMaxPrologueCin, a.cin);
@@ -583,7 +586,7 @@ int lf_conv2d_bf16_train(const void* x, int x_bf16, const uint16_t* wprep, uint1
     return conv_bf16_launch("lf_conv2d_bf16_train", kBf16Train, r, a, x_bf16, 1, ksize, stream);
 }
 
-// (the same routing as lf_conv2d_bf16_act: the streaming kernel for the 32-channel layers only, so that the
+// (the same routing as lf_conv2d_bf16_act: the streaming kernel for the 16- and 32-channel layers only, so that the
 // stored activation is bit-equal with and without the means)
 static size_t bf16_mean_workspace(const Bf16Route& r, int n, int cout) {
     return (size_t)n * r.units * cout * (r.streams ? 1 : 2) * sizeof(float);
@@ -627,13 +630,14 @@ int lf_conv2d_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int x
     out[7] = x_bf16 ? 1 : 0;
     out[8] = ybf;
     const Bf16Route r = bf16_route(entry, ybf, n, cin, h, w, cout, ksize, x_bf16);
+    LF_REQUIRE(r.streams || cout % 32 == 0, "lf_conv2d_bf16_plan: no kernel covers cin %d cout %d", cin, cout);
     if (r.streams) {
         out[0] = 1;
         out[2] = r.s.ci;
-        out[3] = r.s.nco;
+        out[3] = r.s.c16 ? 0 : r.s.nco;
         out[5] = r.s.tw;
         out[6] = r.s.th;
-        out[7] = r.s.ci == 16 ? 0 : 1;   // dispatch_s: the 16-channel slot is the fp32 stem input
+        out[7] = r.s.xbf;                // dispatch_s: fp32 input is the stem (one padded 16-channel group)
         out[10] = lf::conv_bf16s_rmw(entry == kBf16Train ? accumulate : 0, entry == kBf16Train && mask) ? 1 : 0;
         out[11] = r.s.segs > 1 ? 1 : 0;
         out[12] = r.s.interleave;

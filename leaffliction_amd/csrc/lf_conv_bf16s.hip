@@ -38,7 +38,13 @@
 // policy of train.py:179-190).
 //
 // Launched by conv_bf16_launch (lf_conv_bf16.hip) for the shapes bf16_route sends here: lf_conv2d_bf16_train for every
-// shape plan_s covers, the inference entries for the 32-channel layers.
+// shape plan_s covers, the inference entries for the 16- and 32-channel layers.
+//
+// A 16-channel output block (C16: the 16-wide stage of the tiny preset, and the input gradients that flow back
+// into it) runs the same 32x32x16 MFMA: rows 16-31 of the A operand repeat rows 0-15, the rows of D they produce
+// (accumulator registers 8-15) are never looked at, and the epilogue is the first of a 32-channel block's two
+// passes.  Nothing of a channel >= 16 is stored, loaded or summed.  These layers wait for memory, not for the
+// MFMA pipe, which a 32->32 layer already keeps only about a fifth busy.
 #include "lf_common.h"
 
 namespace {
@@ -52,13 +58,14 @@ using lf::f32x16;
 using lf::u32x2;
 using lf::pack_bf16;
 
-template <int TAPS, int CI, int NCO, int TW, int TH>
+template <int TAPS, int CI, int NCO, int TW, int TH, bool C16 = false>
 struct SShape {
     static constexpr int HALO = TAPS == 9 ? 1 : 0;
     static constexpr int PW = TW + 2 * HALO, PH = TH + 2 * HALO, PPIX = PW * PH;
     static constexpr int ROWB = CI * 2;                     // bytes per pixel row of the patch image
     static constexpr int R = 256 / ROWB, C = ROWB / 16;    // rows per 256-byte bank window, 16-byte groups per row
-    static constexpr int COUT = 32 * NCO, CH = CI / 16;
+    static constexpr int COUT = C16 ? 16 : 32 * NCO, CH = CI / 16;
+    static constexpr int NJ = C16 ? 2 : 4;                  // rows of 8 channels to an output block
     static constexpr int WBYTES = CH * TAPS * 2 * COUT * 16;
     static constexpr int PBYTES = (PPIX * ROWB + 15) / 16 * 16;
     // The epilogue's transpose buffer: fp32 accumulators of HALF a 32-channel block (16 channels x 256 pixels), a
@@ -72,14 +79,15 @@ struct SShape {
 // RMW = false: a launch with no read-modify-write operand (no accumulate, no BatchNorm-backward mask): the
 // 32 registers those operands wait in are free, which is what lets three workgroups share a CU (12 waves at
 // <= 168 registers) where the filter bank and the patch are small enough.
-template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF, bool RMW>
-__global__ __launch_bounds__(kT, (SShape<TAPS, CI, NCO, TW, TH>::LDS <= 52 * 1024 && !RMW)
-                                     ? 3 : (SShape<TAPS, CI, NCO, TW, TH>::LDS <= 80 * 1024 ? 2 : 1))
+template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF, bool RMW, bool C16 = false>
+__global__ __launch_bounds__(kT, (SShape<TAPS, CI, NCO, TW, TH, C16>::LDS <= 52 * 1024 && !RMW)
+                                     ? 3 : (SShape<TAPS, CI, NCO, TW, TH, C16>::LDS <= 80 * 1024 ? 2 : 1))
 void conv_bf16s_kernel(lf::ConvBf16Args p) {
-    using S = SShape<TAPS, CI, NCO, TW, TH>;
+    using S = SShape<TAPS, CI, NCO, TW, TH, C16>;
+    static_assert(!C16 || NCO == 1, "a 16-channel output block is half of ONE 32-row MFMA block");
     static_assert(TW * TH == 256 && TW % 8 == 0, "tile = 4 waves x 64 pixels, whole 8-pixel groups");
     static_assert(XBF || CI == 16, "fp32 input: the stem only (3 channels padded to one 16-channel group)");
-    constexpr int HALO = S::HALO, PW = S::PW, PH = S::PH, ROWB = S::ROWB, COUT = S::COUT, CH = S::CH;
+    constexpr int HALO = S::HALO, PW = S::PW, PH = S::PH, ROWB = S::ROWB, COUT = S::COUT, CH = S::CH, NJ = S::NJ;
     constexpr int G = XBF ? 8 : 4;           // pixels per staging unit: 16 bytes of bf16 / of fp32
     constexpr int PGS = TW / G, NB = 2;
     typedef unsigned uvec __attribute__((ext_vector_type(4)));
@@ -257,12 +265,12 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
     const int erow = (8 * eg) / TW, ecol = (8 * eg) - erow * TW;
 
     f32x16 acc[NB][NCO];
-    float s1[NCO][4], s2[NCO][4];  // running sums of this thread's channels over all its pixels and tiles
+    float s1[NCO][NJ], s2[NCO][NJ];  // running sums of this thread's channels over all its pixels and tiles
 #pragma unroll
     for (int cb = 0; cb < NCO; ++cb)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) s1[cb][j] = s2[cb][j] = 0.f;
-    uvec rold[NCO][4], rmask[NCO][4];  // eight pixels of one channel each, as stored
+        for (int j = 0; j < NJ; ++j) s1[cb][j] = s2[cb][j] = 0.f;
+    uvec rold[NCO][NJ], rmask[NCO][NJ];  // eight pixels of one channel each, as stored
 
     // A tile's new rows are gy = ty * TH + HALO .. + TH - 1; a segment's first tile also needs the 2 * HALO rows above
     // them (the "prime" pass: staged when the segment starts, its latency exposed once per segment).  (The first
@@ -326,7 +334,9 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
         // With one output block per workgroup the registers allow TWO groups' operands: group g + 1 is requested,
         // whole, before group g's MFMAs are issued (scheduling barriers keep the compiler from sinking the reads back
         // to their uses).  Two output blocks (NCO = 2) are at their register budget and keep the compiler's order.
-        constexpr bool DEEP = NCO == 1 && CI >= 32;   // (the stem variant runs three workgroups per CU at 168 registers)
+        // (the stem variant runs three workgroups per CU at 168 registers; so does 32 -> 16, which spilled 24 with two
+        // groups in flight)
+        constexpr bool DEEP = NCO == 1 && CI >= 32 && !C16;
         bf16x8 A[DEEP ? 2 : 1][TPR][NCO], B[DEEP ? 2 : 1][NBP];
         auto fetch = [&](int g, int buf) {
             const int ch = g / ROWS, dy = g - ch * ROWS;
@@ -339,7 +349,7 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
 #pragma unroll
                 for (int cb = 0; cb < NCO; ++cb)
                     A[buf][dx][cb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const lf::u32x4*>(
-                        lw + ((((ch * TAPS + dy * TPR + dx) * 2 + kh) * COUT) + cb * 32 + px) * 16));
+                        lw + ((((ch * TAPS + dy * TPR + dx) * 2 + kh) * COUT) + cb * 32 + (C16 ? px & 15 : px)) * 16));
         };
         if (DEEP) fetch(0, 0);
 #pragma unroll
@@ -366,7 +376,7 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
 #pragma unroll
         for (int cb = 0; cb < NCO; ++cb)
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
+        for (int hf = 0; hf < NJ / 2; ++hf) {
 #pragma unroll
             for (int r = 8 * hf; r < 8 * hf + 8; ++r) {
                 const int cl = 8 * ((r >> 2) & 1) + 4 * kh + (r & 3);   // channel within the half block
@@ -397,7 +407,7 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
 #pragma unroll
         for (int cb = 0; cb < NCO; ++cb)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < NJ; ++j) {
                 float a = s1[cb][j];
 #pragma unroll
                 for (int m = 1; m < 8; m <<= 1) a += __shfl_xor(a, m, 64);
@@ -417,7 +427,7 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
 #pragma unroll
         for (int cb = 0; cb < NCO; ++cb)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < NJ; ++j) {
                 float a = s1[cb][j], b = s2[cb][j];
 #pragma unroll
                 for (int m = 1; m < 8; m <<= 1) {
@@ -437,17 +447,24 @@ void conv_bf16s_kernel(lf::ConvBf16Args p) {
 lf::ConvBf16sPlan plan_s(int n, int cin, int h, int w, int cout, int ksize, int x_bf16) {
     lf::ConvBf16sPlan pl{};
     pl.ok = false;
-    if (cout != 32 && cout != 64) return pl;
+    if (cout != 16 && cout != 32 && cout != 64) return pl;
     if (w % 8 != 0) return pl;                              // 16-byte rows
+    pl.xbf = x_bf16 ? 1 : 0;
+    pl.c16 = cout == 16 ? 1 : 0;
     if (!x_bf16) {
-        if (cin > 3 || ksize != 3 || cout != 32) return pl;
+        if (cin > 3 || ksize != 3 || cout > 32) return pl;
         pl.ci = 16;
     } else {
-        if (cin != 32 && cin != 64) return pl;
+        if (cin != 16 && cin != 32 && cin != 64) return pl;
         pl.ci = cin;
     }
-    pl.nco = cout / 32;
-    if (ksize == 1 && !(pl.ci == 32 && pl.nco == 2) && !(pl.ci == 64 && pl.nco == 1)) return pl;
+    pl.nco = pl.c16 ? 1 : cout / 32;
+    // The 16-channel blocks that exist are those a 16-wide stage and its neighbours launch, forward and backward:
+    // 16 <-> 16 and 16 <-> 32 (1x1: the projection 16 -> 32 and its input gradient 32 -> 16).
+    if ((pl.c16 || pl.ci == 16) && x_bf16 && (pl.ci > 32 || cout > 32)) return pl;
+    if (ksize == 1 && !(pl.ci == 32 && pl.nco == 2) && !(pl.ci == 64 && pl.nco == 1) &&
+        !(pl.ci == 16 && cout == 32) && !(pl.ci == 32 && pl.c16))
+        return pl;
     // Rows of a tile are the unit of every global access (64 px = 128 bytes of bf16 per channel row): measured
     // on 32->32 @224, 64x4 tiles against 32x8: forward 687 -> 659 us, input gradient with accumulate + mask +
     // sums 1167 -> 913 us; 64->64 @112 against 16x16: 724 -> 513 and 1043 -> 699 us — although an eighth of
@@ -469,41 +486,50 @@ lf::ConvBf16sPlan plan_s(int n, int cin, int h, int w, int cout, int ksize, int 
     return pl;
 }
 
-template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF, bool RMW>
+template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF, bool RMW, bool C16>
 int launch_s2(const lf::ConvBf16Args& a, int wgs, hipStream_t s) {
-    using S = SShape<TAPS, CI, NCO, TW, TH>;
+    using S = SShape<TAPS, CI, NCO, TW, TH, C16>;
     static bool raised = false;
     if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16s_kernel<TAPS, CI, NCO, TW, TH, XBF, RMW>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16s_kernel<TAPS, CI, NCO, TW, TH, XBF, RMW, C16>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS) != hipSuccess) {
             lf::set_error("lf_conv2d_bf16_train: cannot reserve %d bytes of LDS", S::LDS);
             return LF_ERR_LAUNCH;
         }
         raised = true;
     }
-    conv_bf16s_kernel<TAPS, CI, NCO, TW, TH, XBF, RMW><<<wgs, kT, S::LDS, s>>>(a);
+    conv_bf16s_kernel<TAPS, CI, NCO, TW, TH, XBF, RMW, C16><<<wgs, kT, S::LDS, s>>>(a);
     return LF_OK;
 }
 
-template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF>
+template <int TAPS, int CI, int NCO, int TW, int TH, bool XBF, bool C16 = false>
 int launch_s(const lf::ConvBf16Args& a, int wgs, hipStream_t s) {
-    return lf::conv_bf16s_rmw(a.accumulate, a.stat_mask_y != nullptr) ? launch_s2<TAPS, CI, NCO, TW, TH, XBF, true>(a, wgs, s)
-                                                      : launch_s2<TAPS, CI, NCO, TW, TH, XBF, false>(a, wgs, s);
+    return lf::conv_bf16s_rmw(a.accumulate, a.stat_mask_y != nullptr)
+               ? launch_s2<TAPS, CI, NCO, TW, TH, XBF, true, C16>(a, wgs, s)
+               : launch_s2<TAPS, CI, NCO, TW, TH, XBF, false, C16>(a, wgs, s);
 }
 
 template <int TW, int TH>
 int dispatch_s(const lf::ConvBf16sPlan& pl, int ksize, const lf::ConvBf16Args& a, hipStream_t s) {
-    if (pl.ci == 16) return launch_s<9, 16, 1, TW, TH, false>(a, pl.wgs, s);
+    if (!pl.xbf)   // the stem: fp32 input, three channels in one 16-channel group
+        return pl.c16 ? launch_s<9, 16, 1, TW, TH, false, true>(a, pl.wgs, s)
+                      : launch_s<9, 16, 1, TW, TH, false>(a, pl.wgs, s);
     if (ksize == 3) {
+        if (pl.ci == 16 && pl.c16) return launch_s<9, 16, 1, TW, TH, true, true>(a, pl.wgs, s);
+        if (pl.ci == 16 && pl.nco == 1) return launch_s<9, 16, 1, TW, TH, true>(a, pl.wgs, s);
+        if (pl.ci == 32 && pl.c16) return launch_s<9, 32, 1, TW, TH, true, true>(a, pl.wgs, s);
         if (pl.ci == 32 && pl.nco == 1) return launch_s<9, 32, 1, TW, TH, true>(a, pl.wgs, s);
         if (pl.ci == 32 && pl.nco == 2) return launch_s<9, 32, 2, TW, TH, true>(a, pl.wgs, s);
         if (pl.ci == 64 && pl.nco == 1) return launch_s<9, 64, 1, TW, TH, true>(a, pl.wgs, s);
         if (pl.ci == 64 && pl.nco == 2) return launch_s<9, 64, 2, TW, TH, true>(a, pl.wgs, s);
     } else {
+        if (pl.ci == 16 && pl.nco == 1 && !pl.c16) return launch_s<1, 16, 1, TW, TH, true>(a, pl.wgs, s);
+        if (pl.ci == 32 && pl.c16) return launch_s<1, 32, 1, TW, TH, true, true>(a, pl.wgs, s);
         if (pl.ci == 32 && pl.nco == 2) return launch_s<1, 32, 2, TW, TH, true>(a, pl.wgs, s);
         if (pl.ci == 64 && pl.nco == 1) return launch_s<1, 64, 1, TW, TH, true>(a, pl.wgs, s);
     }
-    lf::set_error("lf_conv2d_bf16_train: no streaming kernel for cin %d nco %d ksize %d", pl.ci, pl.nco, ksize);
+    lf::set_error("lf_conv2d_bf16_train: no streaming kernel for cin %d nco %d c16 %d ksize %d", pl.ci, pl.nco, pl.c16,
+                  ksize);
     return LF_ERR_INVALID;
 }
 

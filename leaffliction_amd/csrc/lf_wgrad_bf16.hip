@@ -34,6 +34,12 @@
 // tile) items and writes one fp32 slab; lf::reduce_slabs adds the slabs in a fixed order
 // (deterministic, no float atomics): the fp32 path's reduction.  lf_conv2d_wgrad_bf16 is the only entry and
 // always runs wgrad_bf16_kernel (the convolutions' bf16_route does not apply to it).
+//
+// Blocks are 32 channels each way whatever cin and cout are.  Channels past cin (A) are never touched: their
+// staging units are masked like the pixels outside the image and leave exact zeros in LDS.  CO16 (cout = 16, the
+// tiny preset's first stage: half a block) does the same for the channels past cout of g, bn_y, dy_out and the
+// BatchNorm coefficients — at the last image those planes lie past the end of the tensors —; the store keeps
+// ci < cin, co < cout.  (An instantiation of its own: the extra compare cost the others up to four registers.)
 #include "lf_common.h"
 
 namespace {
@@ -74,9 +80,10 @@ struct WgShape {
 // G = pixels per staging unit: 8 (16-byte global accesses: the vector memory pipe moves ~5.3 TB/s
 // with 16-byte lanes, ~3 TB/s with 8-byte lanes, ~1.5 TB/s with 4-byte lanes —
 // scripts/microbench/seg_bw.hip) when rows are 16-byte aligned (w % 8 == 0), else 4.
-template <int TAPS, int TW, int TH, int CIB, int COB, bool STEM, int G, int WPRQ = 0>
+template <int TAPS, int TW, int TH, int CIB, int COB, bool STEM, int G, int WPRQ = 0, bool CO16 = false>
 __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 1) void wgrad_bf16_kernel(WgBf16Args p) {
     using S = WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>;
+    static_assert(!CO16 || COB == 1, "cout = 16 is half of ONE 32-channel block");
     static_assert((G == 4 || G == 8) && TW % G == 0, "staging groups of 4 or 8 pixels");
     typedef unsigned uvec __attribute__((ext_vector_type(G / 2)));   // G bf16
     constexpr int kT = S::NT, ROWS = S::ROWS, TPW = TAPS / ROWS;  // taps per wave
@@ -109,7 +116,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
     if (bn)
         for (int e = tid; e < 5 * 32 * COB; e += kT) {
             const int kk = e / (32 * COB), c = e - kk * (32 * COB);
-            lbn[e] = p.bn_coef[(size_t)kk * p.cout + co0 + c];
+            lbn[e] = (!CO16 || c < 16) ? p.bn_coef[(size_t)kk * p.cout + co0 + c] : 0.f;
         }
     if (pro && !STEM)
         for (int c = tid; c < 32 * CIB; c += kT) {
@@ -176,7 +183,7 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
             const int u = tid + k * kT;
             const int pg = u % PGS, t1 = u / PGS, quad = t1 % (8 * COB), row = t1 / (8 * COB);
             const int gy = ty0 + row, gx = tx0 + G * pg;
-            const bool ok = u < NDU && gy < p.h && gx < p.w;
+            const bool ok = u < NDU && gy < p.h && gx < p.w && (!CO16 || quad < 4);
             dmask |= (ok ? 1u : 0u) << k;
             if (!ok) continue;
             const size_t o = (size_t)(co0 + 4 * quad) * hw + (size_t)gy * p.w + gx;
@@ -480,6 +487,9 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
     }
 }
 
+// whole 32-channel blocks of output channels, or the half block of a 16-wide stage
+inline bool wgrad_cout_ok(int cout) { return cout == 16 || cout % 32 == 0; }
+
 struct WgBf16Plan {
     int variant;  // index into the launch table
     int tw, th, cib, cob, stem;
@@ -503,7 +513,7 @@ WgBf16Plan plan_wgrad_bf16(int n, int cin, int cout, int h, int w, int ksize) {
     pl.tiles_x = (w + pl.tw - 1) / pl.tw;
     pl.tiles_y = (h + pl.th - 1) / pl.th;
     pl.gy = pl.stem ? 1 : (cin + 32 * pl.cib - 1) / (32 * pl.cib);
-    pl.gz = cout / (32 * pl.cob);
+    pl.gz = (cout + 32 * pl.cob - 1) / (32 * pl.cob);   // cout = 16: half a block
     // one resident 12-wave workgroup per CU (3x3), a few 4-wave ones (1x1): two rounds' worth of workgroups, each
     // with a slab of partial sums of its own.  They walk column strips; strips are cut into segments (which re-stage
     // the two rows above them) only when there are too few to go round — small batches.
@@ -518,19 +528,19 @@ WgBf16Plan plan_wgrad_bf16(int n, int cin, int cout, int h, int w, int ksize) {
     return pl;
 }
 
-template <int TAPS, int TW, int TH, int CIB, int COB, bool STEM, int G, int WPRQ = 0>
+template <int TAPS, int TW, int TH, int CIB, int COB, bool STEM, int G, int WPRQ = 0, bool CO16 = false>
 int launch_wg(const WgBf16Args& a, dim3 grid, hipStream_t s) {
     using S = WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>;
     static bool raised = false;
     if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<TAPS, TW, TH, CIB, COB, STEM, G, WPRQ>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<TAPS, TW, TH, CIB, COB, STEM, G, WPRQ, CO16>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS) != hipSuccess) {
             lf::set_error("lf_conv2d_wgrad_bf16: cannot reserve %d bytes of LDS", S::LDS);
             return LF_ERR_LAUNCH;
         }
         raised = true;
     }
-    wgrad_bf16_kernel<TAPS, TW, TH, CIB, COB, STEM, G, WPRQ><<<grid, S::NT, S::LDS, s>>>(a);
+    wgrad_bf16_kernel<TAPS, TW, TH, CIB, COB, STEM, G, WPRQ, CO16><<<grid, S::NT, S::LDS, s>>>(a);
     return LF_OK;
 }
 
@@ -560,6 +570,14 @@ int dispatch_wg(const WgKernel& k, const WgBf16Args& a, dim3 grid, hipStream_t s
 #define LF_WG(TW_, TH_, CIB_, COB_, G_) \
     if (k.tw == TW_ && k.th == TH_ && k.cib == CIB_ && k.cob == COB_ && k.g == G_ && k.wprq == 0) \
         return launch_wg<TAPS, TW_, TH_, CIB_, COB_, false, G_>(a, grid, s)
+#define LF_WG16(TW_, TH_, G_) \
+    if (a.cout == 16 && k.tw == TW_ && k.th == TH_ && k.cib == 1 && k.cob == 1 && k.g == G_ && k.wprq == 0) \
+        return launch_wg<TAPS, TW_, TH_, 1, 1, false, G_, 0, true>(a, grid, s)
+    LF_WG16(32, 8, 8);   // cout = 16: before their 32-channel twins
+    LF_WG16(32, 8, 4);
+    LF_WG16(56, 4, 8);
+    LF_WG16(28, 4, 4);
+#undef LF_WG16
     LF_WG(32, 8, 1, 1, 8);
     LF_WG(32, 8, 1, 2, 8);
     LF_WG(32, 8, 2, 2, 8);
@@ -582,7 +600,7 @@ int dispatch_wg(const WgKernel& k, const WgBf16Args& a, dim3 grid, hipStream_t s
 extern "C" {
 
 size_t lf_conv2d_wgrad_bf16_workspace(int n, int cin, int h, int w, int cout, int ksize) {
-    if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || cout % 32 != 0) return 0;
+    if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || !wgrad_cout_ok(cout)) return 0;
     const WgBf16Plan pl = plan_wgrad_bf16(n, cin, cout, h, w, ksize);
     const size_t count = (size_t)cin * ksize * ksize * cout;
     return ((size_t)pl.splits + lf::slab_groups(pl.splits)) * count * sizeof(float);
@@ -590,7 +608,7 @@ size_t lf_conv2d_wgrad_bf16_workspace(int n, int cin, int h, int w, int cout, in
 
 int lf_conv2d_wgrad_bf16_plan(int n, int cin, int h, int w, int cout, int ksize, int* out) {
     LF_REQUIRE(out, "lf_conv2d_wgrad_bf16_plan: null out");
-    LF_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && (ksize == 1 || ksize == 3) && cout % 32 == 0,
+    LF_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0 && (ksize == 1 || ksize == 3) && wgrad_cout_ok(cout),
                "lf_conv2d_wgrad_bf16_plan: bad dims");
     const WgBf16Plan pl = plan_wgrad_bf16(n, cin, cout, h, w, ksize);
     const WgKernel k = wg_kernel(pl, ksize, w);
@@ -613,7 +631,7 @@ int lf_conv2d_wgrad_bf16(const void* x, const uint16_t* g, const uint16_t* bn_y,
     LF_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0, "lf_conv2d_wgrad_bf16: bad dims");
     LF_REQUIRE(ksize == 3 || ksize == 1, "lf_conv2d_wgrad_bf16: ksize must be 1 or 3 (got %d)", ksize);
     LF_REQUIRE(w % 4 == 0, "lf_conv2d_wgrad_bf16: width must be a multiple of 4 (got %d)", w);
-    LF_REQUIRE(cout % 32 == 0, "lf_conv2d_wgrad_bf16: cout must be a multiple of 32 (got %d)", cout);
+    LF_REQUIRE(wgrad_cout_ok(cout), "lf_conv2d_wgrad_bf16: cout must be 16 or a multiple of 32 (got %d)", cout);
     LF_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "lf_conv2d_wgrad_bf16: scale/shift must both be set");
     LF_REQUIRE(bn_y != nullptr || (alpha_nc == nullptr && add_nc == nullptr && dy_out == nullptr),
                "lf_conv2d_wgrad_bf16: alpha / add / dy_out need bn_y");
@@ -643,7 +661,11 @@ int lf_conv2d_wgrad_bf16(const void* x, const uint16_t* g, const uint16_t* bn_y,
     int rc;
     const WgKernel k = wg_kernel(pl, ksize, w);
     if (k.wprq == 4)
-        rc = launch_wg<9, 56, 4, 1, 1, false, 4, 4>(a, grid, s);
+        rc = cout == 16 ? launch_wg<9, 56, 4, 1, 1, false, 4, 4, true>(a, grid, s)
+                        : launch_wg<9, 56, 4, 1, 1, false, 4, 4>(a, grid, s);
+    else if (k.stem && cout == 16)
+        rc = k.g == 8 ? launch_wg<1, 32, 8, 1, 1, true, 8, 0, true>(a, grid, s)
+                      : launch_wg<1, 32, 8, 1, 1, true, 4, 0, true>(a, grid, s);
     else if (k.stem)
         rc = k.g == 8 ? launch_wg<1, 32, 8, 1, 1, true, 8>(a, grid, s)
                       : launch_wg<1, 32, 8, 1, 1, true, 4>(a, grid, s);

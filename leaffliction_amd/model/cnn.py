@@ -385,12 +385,18 @@ class LeafCNN:
         return y, self._bn(bn, y, False)
 
     def _bf16_storage_ok(self, h: int, w: int) -> bool:
-        """The bf16-activation forward needs 4-pixel groups at every stage (conv staging, the
-        2x2-pool tail, the final mean) and 32-channel output blocks."""
+        """The rule of bf16 storage, for the training step and the inference forward alike: 4-pixel groups
+        at every stage (conv staging, the 2x2-pool tail, the final mean) and stage widths of 16 or a
+        multiple of 32 channels.  Convolutions with 16 channels on either side exist only in the streaming
+        kernel, which works in 16-byte rows and pairs 16 channels with 16 or 32: a stage that is 16 wide or
+        follows a 16-wide one is a multiple of 8 pixels wide, and its neighbours are 16 or 32 wide."""
+        cin = self.widths[0]
         for f in self.widths:
-            if f % 32 or w % 4 or h % 2:
+            if (f != 16 and f % 32) or w % 4 or h % 2:
                 return False
-            h, w = h // 2, w // 2
+            if 16 in (cin, f) and (w % 8 or max(cin, f) > 32):
+                return False
+            cin, h, w = f, h // 2, w // 2
         return (h * w) % 4 == 0
 
     def _forward_infer_bf16(self, x0: torch.Tensor) -> torch.Tensor:
@@ -459,13 +465,15 @@ class LeafCNN:
         policy is mixed_float16, train.py:179-190; `--no-mixed-precision` selects f32).  bf16:
         activations and gradients are STORED as bf16 and every convolution operand is bf16
         (fp32 accumulation); master weights, Adam state, BatchNorm statistics, SE, softmax and the
-        loss stay fp32.  Needs widths that are multiples of 32 and an image size that keeps every
-        stage a multiple of four pixels wide (224, 64, 32 do)."""
+        loss stay fp32.  Needs the SE blocks, widths of 16 or multiples of 32 and an image size that keeps
+        every stage a multiple of four pixels wide, eight where 16 channels are involved (224, 64, 32 do):
+        _bf16_storage_ok states the rule."""
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"training dtype must be 'f32' or 'bf16', got {dtype!r}")
         if dtype == "bf16" and not (self.use_se and self._bf16_storage_ok(self.img_size, self.img_size)):
-            raise ValueError("bf16 training needs use_se, widths % 32 == 0 and every stage a multiple "
-                             f"of 4 pixels wide (img_size {self.img_size}, widths {self.widths})")
+            raise ValueError("bf16 training needs use_se, widths of 16 or a multiple of 32 (16 next to 16 or 32 "
+                             "only) and every stage a multiple of 4 pixels wide, 8 at 16 channels "
+                             f"(img_size {self.img_size}, widths {self.widths})")
         self.train_dtype = dtype
 
     def _prep_bf16_weights(self) -> None:
