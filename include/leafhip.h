@@ -519,6 +519,41 @@ int lf_conv2d_bf16_act_mean(const void* x, int x_bf16, const uint16_t* wprep, ui
                             size_t ws_bytes, lf_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* A2 — class activation maps: where on the leaf a prediction comes from      */
+/* ------------------------------------------------------------------------- */
+/* The reference explains nothing: its ImageProcessor pastes a display-only Mask picture beside the prediction
+ * (srcs/predict/predictor.py:46,99).  leaf_cnn ends in MaxPool -> GlobalAveragePooling2D -> Dense
+ * (srcs/model/cnn.py:96-101), so the class activation map of Zhou et al. (CVPR 2016) is an identity here:
+ *     logit_c = b_c + mean_{y,x} cam_c(y,x),    cam_c(y,x) = sum_k W[k][c] * F[k][y][x]
+ * with F the last stage's pooled output and W the dense kernel.
+ *
+ * lf_cam_maps: up to 8 class slots per image in one pass over the features.
+ *   feat     [N][K][h][w] NCHW, fp32 or bf16 (feat_bf16 != 0), read once whatever m is;
+ *   w        [K][C] fp32 (the layout of dense.w);
+ *   classes  [N][m] int32 on the device, 1 <= m <= 8, values in [0, C), repeats allowed;
+ *   classes_host  optional HOST copy of classes: when non-null every value is checked against [0, C) and a value
+ *            outside returns LF_ERR_INVALID before anything is launched.  The kernel itself clamps a class into
+ *            [0, C), so w is never read outside whatever the device buffer holds;
+ *   cam      [N][m][h][w] fp32 = sum_k w[k][classes[n][j]] * feat[n][k]  (no bias);
+ *   peak     [N][m] fp32 = max(0, max_{y,x} cam[n][j]).
+ * The sum over k is four ascending fmaf chains over consecutive quarters of the channels, added left to right:
+ * |cam - exact| <= (K + 2) 2^-24 sum_k |w f|; no atomics, two launches give the same bits.  K <= 512.
+ *
+ * lf_cam_overlay_u8: slot `slot` of such maps blended into img [N][H][W][3] uint8 -> out (same shape), per pixel
+ * in fp32:  sx = (x + 0.5)(w/W) - 0.5 clamped to [0, w-1], x0 = floor(sx), x1 = min(x0+1, w-1), fx = sx - x0, the
+ * same in y, v = the bilinear value of cam;  t = peak > 0 ? max(v, 0)/peak : 0  (as max(v, 0) * (1/peak));
+ *   r = clamp(1.5 - |4t - 3|, 0, 1),  g = clamp(1.5 - |4t - 2|, 0, 1),  b = clamp(1.5 - |4t - 1|, 0, 1);
+ *   a = alpha t;  out = floor(a 255 colour + (1 - a) img + 0.5).
+ * A pixel without positive evidence keeps its byte exactly; a map that is nowhere positive returns img.
+ * Any H, W, h, w >= 1; 0 <= alpha <= 1; img and out must not overlap.  Against the formulas in float64 a byte may
+ * differ by one where the value before the floor lies within 1e-3 of an integer. */
+int lf_cam_maps(const void* feat, int feat_bf16, const float* w, const int32_t* classes,
+                const int32_t* classes_host, float* cam, float* peak, int n, int k, int h, int wd, int c, int m,
+                lf_stream_t stream);
+int lf_cam_overlay_u8(const uint8_t* img, const float* cam, const float* peak, uint8_t* out, int n, int hh, int ww,
+                      int h, int wd, int m, int slot, float alpha, lf_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* A2 — the mixed-precision TRAINING step (bf16 storage, fp32 arithmetic)      */
 /* ------------------------------------------------------------------------- */
 /* The reference trains under keras.mixed_precision.set_global_policy("mixed_float16") unless

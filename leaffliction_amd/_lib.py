@@ -91,6 +91,8 @@ SIGNATURES = {
     "lf_conv2d_bf16_act_mean_workspace": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "lf_conv2d_bf16_act_mean": [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, P, P,
                                 c_size_t, P],
+    "lf_cam_maps": [P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "lf_cam_overlay_u8": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P],
     "lf_conv2d_bf16_stats_tiles": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "lf_conv2d_bf16_train": [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P,
                              c_size_t, P, P, P, P, c_int, P],

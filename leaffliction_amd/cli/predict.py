@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--evaluate ...]`.
+"""`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--evaluate ...]`.
 
 Flags, JSON schema (`batch_results` + `summary`), the sampled accuracy gate and the exit
 codes (1 on error, 2 when the gate is never reached) follow srcs/cli/predict.py:17-87,
 305-436,492-563.  Montage / dashboard rendering is presentation and not reproduced.
+`--cam` (not in the reference) also writes, per image, the model input with the predicted class's activation map
+laid over it: `<out>/<stem>__CAM.jpg`, in batch mode `<out>/cam/<the path below image_or_dir>__CAM.jpg`.
 """
 from __future__ import annotations
 
@@ -37,11 +39,18 @@ def parse_args(argv=None):
     p.add_argument("--sample-size", type=int, default=100)
     p.add_argument("--target-acc", type=float, default=0.90)
     p.add_argument("--max-attempts", type=int, default=5)
+    p.add_argument("--cam", action="store_true",
+                   help="write a class-activation heat map over each model input (<stem>__CAM.jpg)")
+    p.add_argument("--cam-alpha", type=float, default=0.6, help="weight of the heat map at its peak (0..1)")
     return p.parse_args(argv)
 
 
 def validate_inputs(args):
     image_path, learnings_dir = Path(args.image_path), Path(args.learnings_dir)
+    if args.cam and args.evaluate:
+        raise ValueError("--cam cannot be combined with --evaluate")
+    if args.cam and not 0.0 <= args.cam_alpha <= 1.0:
+        raise ValueError(f"--cam-alpha must lie in [0, 1], got {args.cam_alpha}")
     if not image_path.exists():
         raise FileNotFoundError(f"Path not found: {image_path}")
     if args.batch_mode and not image_path.is_dir():
@@ -86,6 +95,32 @@ def save_batch_results_json(results, processing_time, output_path):
     with open(output_path, "w") as f:
         json.dump(data, f, indent=2)
     return output_path
+
+
+CAM_SUFFIX = "__CAM.jpg"
+CAM_ENCODE_CHUNK = 256   # overlays per JPEG encode launch
+
+
+def write_cam_overlays(results, targets) -> None:
+    """results[i]["cam_overlay"] -> the file targets[i], the bytes Image.save(quality=95) would write (encoded on
+    the GPU: Transformation.encode_jpeg_batch, one launch per CAM_ENCODE_CHUNK overlays -- they all have one size)."""
+    import numpy as np
+    import torch
+
+    from .Transformation import encode_jpeg_batch
+    for b in range(0, len(results), CAM_ENCODE_CHUNK):
+        part = results[b:b + CAM_ENCODE_CHUNK]
+        x = torch.from_numpy(np.stack([r["cam_overlay"] for r in part])).cuda()
+        for target, data in zip(targets[b:b + CAM_ENCODE_CHUNK], encode_jpeg_batch(x)):
+            target.parent.mkdir(parents=True, exist_ok=True)
+            target.write_bytes(data)
+
+
+def cam_target(path: Path, image_dir: Path, output_dir: Path) -> Path:
+    """Where batch mode writes the overlay of image_dir/sub/leaf.jpg: output_dir/cam/sub/leaf__CAM.jpg (stems repeat
+    across class folders, so the tree is mirrored)."""
+    rel = Path(path).relative_to(image_dir)
+    return Path(output_dir) / "cam" / rel.parent / (rel.stem + CAM_SUFFIX)
 
 
 def _item_path(item, image_dir: Path, manifest_path: Optional[Path]) -> Optional[Path]:
@@ -180,20 +215,37 @@ def main(argv=None) -> None:
                 logger.warning(f"No image files found in {image_path}")
                 return
             t0 = time.time()
-            results = predictor.predict_batch_sharded(files, rk)
+            if args.cam:
+                results = predictor.explain_batch_sharded(
+                    files, rk, alpha=args.cam_alpha, each=lambda mine: write_cam_overlays(
+                        mine, [cam_target(r["image_path"], image_path, Path(args.output_dir)) for r in mine]))
+            else:
+                results = predictor.predict_batch_sharded(files, rk)
             proc = time.time() - t0
             if rk.rank != 0:
                 return
+            if args.cam:
+                logger.info("Heat maps saved under: %s", Path(args.output_dir) / "cam")
             out = save_batch_results_json(results, proc, args.json_output)
             logger.info("Results saved to: %s", out)
             for k, v in create_batch_summary(results, proc).items():
                 logger.info("  %s: %s", k, v)
         else:
-            r = predictor.predict_single(image_path)
+            if args.cam:
+                found = predictor.explain_batch([image_path], alpha=args.cam_alpha)
+                if not found:
+                    raise ValueError(f"Could not read image: {image_path}")
+                r = found[0]
+            else:
+                r = predictor.predict_single(image_path)
             logger.info(f"Image: {r['image_path']}")
             logger.info(f"Prediction: {r['top_prediction']} ({r['confidence']:.2%})")
             for name, prob in sorted(r["all_probabilities"].items(), key=lambda x: -x[1])[:3]:
                 logger.info(f"    {name}: {prob:.2%}")
+            if args.cam:
+                target = Path(args.output_dir) / (image_path.stem + CAM_SUFFIX)
+                write_cam_overlays([r], [target])
+                logger.info(f"Heat map: {target}")
     except SystemExit:
         raise
     except (FileNotFoundError, ValueError) as e:

@@ -447,6 +447,7 @@ class LeafCNN:
             xin = self._buf(n, "bf16." + p + "p", (n, f, a2.shape[2] // 2, a2.shape[3] // 2), bf)
             nn.block_tail_fwd(a2, None, None, s, sc, None, None, False, None, None, xin)
             cin = f
+        self._last_pooled = xin   # class_activation_maps reads it
         g = nn.gap(xin, out=self._buf(n, "g", (n, self.widths[-1])))
         probs = self._buf(n, "probs", (n, self.num_classes))
         nn.head_fwd(g, P["dense.w"], P["dense.b"], None, probs, None)
@@ -543,6 +544,7 @@ class LeafCNN:
             sv.update({p + "xin": xin, p + "xin_st": xin_st, p + "y1": y1, p + "y2": y2, p + "s": s,
                        p + "route": route, p + "drop": drop, p + "hw": (h, w)})
             xin, xin_st, cin, h, w = pooled, None, f, h // 2, w // 2
+        self._last_pooled = xin   # class_activation_maps reads it
         g = nn.gap(xin, out=B("g", (n, self.widths[-1]), F32))
         feat = g
         if training and top_drop is not None:
@@ -971,6 +973,31 @@ class LeafCNN:
             return self._forward_infer_bf16(x0)
         probs, _ = self.forward(x0, False)
         return probs
+
+    @torch.no_grad()
+    def class_activation_maps(self, x, classes=None, top: int = 1):
+        """Where on the picture each class's logit comes from.  The network ends in GlobalAveragePooling2D -> Dense,
+        so with F the last stage's pooled output and W, b the dense layer
+            logit_c = b_c + mean_{y,x} cam_c(y,x),    cam_c(y,x) = sum_k W[k][c] * F[k][y][x]
+        exactly: the maps sum to the prediction.  Runs predict_device(x), so F is what the pass that produced the
+        probabilities left behind (fp32, or the stored bf16 values of the bf16 inference pass).
+        classes: None = the `top` most probable classes of every image (slot 0 is the prediction), or an int
+        tensor / array [N] or [N,M], M <= 8.  Returns (probs [N,C], classes [N,M] int32, cam [N,M,h,w], peak [N,M] =
+        max(0, max cam)): device tensors of their own, which the next forward pass does not overwrite."""
+        probs = self.predict_device(x).clone()
+        n = probs.shape[0]
+        if classes is None:
+            if not 1 <= int(top) <= min(8, self.num_classes):
+                raise ValueError(f"class_activation_maps: top={top} (1..{min(8, self.num_classes)})")
+            cls = probs.topk(int(top), dim=1).indices
+        else:
+            cls = torch.as_tensor(np.asarray(classes) if not isinstance(classes, torch.Tensor) else classes)
+            cls = cls.to(self.device).reshape(n, -1)
+            if cls.dtype.is_floating_point or cls.dtype == torch.bool:
+                raise TypeError(f"class_activation_maps: classes must be integers, got {cls.dtype}")
+        cls = cls.to(torch.int32).contiguous()
+        cam, peak = nn.cam_maps(self._last_pooled, self.p["dense.w"], cls)
+        return probs, cls, cam, peak
 
     def evaluate(self, data, verbose: Any = 0, dp=None) -> List[float]:
         """[loss, accuracy] over a sequence of (X, y) batches (one-hot or sparse labels); the

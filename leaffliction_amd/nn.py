@@ -627,6 +627,33 @@ def bcast_planes(v, h, w, scale, out=None):
     return out
 
 
+def cam_maps(feat, w, classes, out=None, peak=None):
+    """Class activation maps of the dense head: feat [N,K,h,w] fp32 or bf16 (the last stage's pooled output),
+    w [K,C] fp32 (dense.w), classes [N,M] int32 with 1 <= M <= 8 and values in [0, C) ->
+    (cam [N,M,h,w] fp32 = sum_k w[k, classes[n,j]] * feat[n,k], peak [N,M] fp32 = max(0, max cam)).
+    A class outside [0, C) raises LeafHipError before anything is launched (checked on a host copy)."""
+    bf16 = _plane_dtype(feat, "cam_maps.feat", 4) == _BF16
+    _chk(w, _F32, "cam_maps.w", 2)
+    _chk(classes, torch.int32, "cam_maps.classes", 2)
+    n, k, h, wd = feat.shape
+    c, m = w.shape[1], classes.shape[1]
+    if w.shape[0] != k or classes.shape[0] != n:
+        raise ValueError(f"cam_maps: w {tuple(w.shape)} / classes {tuple(classes.shape)} do not fit feat "
+                         f"{tuple(feat.shape)}")
+    if out is None:
+        out = torch.empty((n, m, h, wd), dtype=_F32, device=feat.device)
+    if peak is None:
+        peak = torch.empty((n, m), dtype=_F32, device=feat.device)
+    _chk(out, _F32, "cam_maps.out", 4)
+    _chk(peak, _F32, "cam_maps.peak", 2)
+    if tuple(out.shape) != (n, m, h, wd) or tuple(peak.shape) != (n, m):
+        raise ValueError("cam_maps: out must be [N,M,h,w] and peak [N,M]")
+    host = classes.cpu()
+    _lib.call("lf_cam_maps", feat.data_ptr(), 1 if bf16 else 0, w.data_ptr(), classes.data_ptr(), host.data_ptr(),
+              out.data_ptr(), peak.data_ptr(), n, k, h, wd, c, m, _stream())
+    return out, peak
+
+
 def se_fwd(m, w1, b1, w2, b2, z1, s):
     n, c = m.shape
     cr = w1.shape[1]

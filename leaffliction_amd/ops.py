@@ -1031,3 +1031,25 @@ def resize_lanczos4_u8(x: torch.Tensor, size, aug: Optional[torch.Tensor] = None
     _lib.call("lf_resize_lanczos4_u8", x.data_ptr(), out.data_ptr(), n, h, w, oh, ow, tables.data_ptr(),
               host.ctypes.data, aug.data_ptr() if aug is not None else None, _stream())
     return out
+
+
+def cam_overlay_u8(img: torch.Tensor, cam: torch.Tensor, peak: torch.Tensor, slot: int = 0,
+                   alpha: float = 0.6) -> torch.Tensor:
+    """Heat-map overlay of class activation maps (nn.cam_maps): img [N,H,W,3] uint8, cam [N,M,h,w] fp32, peak [N,M]
+    fp32 -> [N,H,W,3] uint8.  Slot `slot`'s map is upsampled bilinearly to H x W, t = max(v, 0) / peak, and a
+    blue-to-red ramp of t is blended in with weight alpha * t: a pixel without positive evidence keeps its byte,
+    an image whose map is nowhere positive comes back unchanged."""
+    n, hh, ww = _hwc(img, "cam_overlay.img")
+    _chk(cam, _F32, "cam_overlay.cam", 4)
+    _chk(peak, _F32, "cam_overlay.peak", 2)
+    m, h, w = cam.shape[1:]
+    if cam.shape[0] != n or tuple(peak.shape) != (n, m):
+        raise ValueError(f"cam_overlay: cam {tuple(cam.shape)} / peak {tuple(peak.shape)} do not fit {n} images")
+    if not 0 <= int(slot) < m:
+        raise ValueError(f"cam_overlay: slot {slot} of {m}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"cam_overlay: alpha {alpha} outside [0, 1]")
+    out = torch.empty_like(img)
+    _lib.call("lf_cam_overlay_u8", img.data_ptr(), cam.data_ptr(), peak.data_ptr(), out.data_ptr(), n, hh, ww, h, w,
+              m, int(slot), float(alpha), _stream())
+    return out

@@ -123,6 +123,81 @@ class Predictor:
         probs = self.model_loader.model.predict(self._prepare([a for _p, a in loaded]))
         return [self._result(p, a, probs[i]) for i, (p, a) in enumerate(loaded)]
 
+    def _explain_chunk(self, x, step: int, top: int, alpha: float):
+        """Probabilities and heat-map overlays of one chunk of model inputs x [n,S,S,3] uint8 on the device, the
+        forward pass run in slices of `step` images as the prediction path does: the class activation maps of each
+        image's `top` classes (LeafCNN.class_activation_maps), slot 0 -- the prediction -- laid over the picture the
+        network saw (ops.cam_overlay_u8).  Host arrays."""
+        import torch
+
+        from .. import ops
+        model = self.model_loader.model
+        probs, overlays = [], []
+        for b in range(0, x.shape[0], step):
+            xb = x[b:b + step].contiguous()
+            p, _classes, cam, peak = model.class_activation_maps(xb, top=top)
+            probs.append(p)
+            overlays.append(ops.cam_overlay_u8(xb, cam, peak, 0, alpha))
+        return torch.cat(probs).cpu().numpy(), torch.cat(overlays).cpu().numpy()
+
+    def explain_batch(self, image_paths, top: int = 1, alpha: float = 0.6) -> List[Dict[str, Any]]:
+        """`predict_batch` with the reason for each prediction: the same result dicts (same decoding and resize
+        route: the pooled path from POOL_MIN files on, the host loop below; unreadable files skipped and logged
+        alike) plus `cam_overlay`, a uint8 [S,S,3] host array: the model input with the predicted class's
+        activation map blended in (weight `alpha` at the map's peak)."""
+        if not self._initialized:
+            raise RuntimeError("Predictor not initialized. Call load() first.")
+        import torch
+        if getattr(self.model_loader.model, "class_activation_maps", None) is None:
+            raise ValueError("class activation maps need a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
+        paths = [Path(p) for p in image_paths]
+        results: List[Dict[str, Any]] = []
+        if len(paths) >= self.POOL_MIN:
+            from ..dataio.device_decode import DeviceDecoder
+            if self._codec is None:
+                self._codec = DeviceDecoder()
+            for _first, kept, x, natives, errors in self._codec.chunks(paths, self.model_loader.img_size,
+                                                                       keep_native=True):
+                for _k, message in errors:
+                    logger.error(f"Error processing image {message}")
+                if not kept:
+                    continue
+                probs, overlays = self._explain_chunk(x, 1024, top, alpha)
+                for j, k in enumerate(kept):
+                    results.append(dict(self._result(paths[k], natives[k], probs[j]), cam_overlay=overlays[j]))
+        else:
+            loaded = []
+            for p in paths:
+                try:
+                    loaded.append((p, ImageLoader.load_as_array(p)))
+                except Exception as e:  # noqa: BLE001 — skipped like the reference
+                    logger.error(f"Error processing image {p}: {e}")
+            if loaded:
+                x = torch.from_numpy(self._prepare([a for _p, a in loaded])).cuda()
+                probs, overlays = self._explain_chunk(x, 256, top, alpha)
+                results = [dict(self._result(p, a, probs[i]), cam_overlay=overlays[i])
+                           for i, (p, a) in enumerate(loaded)]
+        if not results:
+            logger.warning("No valid images to predict.")
+        return results
+
+    def explain_batch_sharded(self, image_paths, ranks=None, top: int = 1, alpha: float = 0.6,
+                              each=None) -> List[Dict[str, Any]]:
+        """`explain_batch` cut into one contiguous share per GPU replica like `predict_batch_sharded`.  `each` is
+        called with this replica's own results (which carry the overlays) before the gather; what every rank
+        returns is the full list in input order, results from other ranks without pixel arrays or overlays."""
+        from ..utils import ranks as R
+        rk = ranks or R.current()
+        paths = [Path(p) for p in image_paths]
+        b, e = R.contiguous_share(len(paths), rk.rank, rk.world) if rk.active else (0, len(paths))
+        mine = self.explain_batch(paths[b:e], top=top, alpha=alpha) if e > b else []
+        if each is not None:
+            each(mine)
+        if not rk.active:
+            return mine
+        slim = [{k: (None if k.endswith("_array") or k == "cam_overlay" else v) for k, v in r.items()} for r in mine]
+        return rk.gather_in_order(slim)
+
     def predict_batch_sharded(self, image_paths, ranks=None) -> List[Dict[str, Any]]:
         """`predict_batch` with the file list cut into one contiguous share per GPU replica
         (SURVEY §8e "inference: replicas only"; reference call site predict.py:492).  Every
