@@ -232,6 +232,52 @@ int lf_roi_u8(const uint8_t* rgb, const int32_t* contour, const int32_t* counts,
               uint8_t* vis, int32_t* bbox, int32_t* flags, int n, int h, int w, int roi_h, int roi_w,
               lf_stream_t stream);
 
+/* Leaf measurements from the contour buffer lf_make_mask_u8 made (contour [N,cap,2] int32 (x, y), counts [N]): the
+ * geometry srcs/transform/filters/analyze.py draws (centroid, extreme points, convex hull, PCA axes) and the shape
+ * numbers pcv.analyze_object computes there, as data.  One workgroup per image; no image is read; two launches give
+ * the same bits.  Limits, checked before the launch: h, w <= 4096 and cap <= 65536, which keep every integer sum
+ * below 2^57, inside int64.  The points may repeat and the contour may touch itself.
+ * flags [N] as lf_roi_u8: bit 0 the image has a contour (else its records and hull are zero), bit 2 a count below 0
+ * or above cap or a point outside the image (an error; nothing outside [0, min(count, cap)) is read), or a hull
+ * past its capacity, which no point set can cause (a bug: treat as an error).
+ * With P_0 .. P_{m-1} the points, P_m = P_0 and c_i = x_i * y_{i+1} - x_{i+1} * y_i:
+ * ints [N][32] int64, exact:
+ *    0 npts = m;  1 area2s = sum c_i (signed);  2 s10 = sum (x_i + x_{i+1}) c_i;  3 s01 = sum (y_i + y_{i+1}) c_i;
+ *    4..7 bbox x, y, w, h (cv2.boundingRect, lf_roi_u8's);
+ *    8..15 left, right, top, bottom as (x, y): the first point in contour order with the least x, the greatest x,
+ *      the least y, the greatest y (numpy argmin / argmax);
+ *    16 in_frame: 1 when the bbox touches no image border (x > 0, y > 0, x + w < W, y + h < H);
+ *    17..21 sx, sy, sxx, sxy, syy: sums of x, y, x^2, x y, y^2 over the points;
+ *    22 hull_n, 23 hull_area2 = |sum c| over the hull, 24 feret2 = the greatest squared distance between two hull
+ *      vertices;
+ *    25..28 i0min, i0max, i1min, i1max: indices of the points with the least and the greatest projection on the
+ *      major axis (vx, vy) and on its normal (-vy, vx);  29..31 zero.
+ * hull [N][2 * min(h, w)][2] int32: the strict convex hull of the points (no three vertices collinear), starting at
+ *   the lexicographically smallest (x, y), every consecutive triple with a positive cross product; rows from hull_n
+ *   on are zero.  One point gives 1 vertex; two or more points on one line give its 2 end points.  A strict hull of
+ *   lattice points has at most two vertices per row and per column, so the capacity always suffices.
+ * vals [N][16] float64:
+ *    0 area = |area2s| / 2;  1 perimeter = sum |P_{i+1} - P_i|;
+ *    2, 3 cx, cy = s10 / (3 area2s), s01 / (3 area2s) (cv2.moments' m10 / m00, m01 / m00), the mean of the points
+ *      when area2s == 0;
+ *    4 hull_area = hull_area2 / 2;  5 solidity = area / hull_area, 0 when hull_area is 0;
+ *    6 circularity = 4 pi area / perimeter^2, 0 when the perimeter is 0;  7 feret = sqrt(feret2);
+ *    8, 9 l1 >= l2: eigenvalues of the population covariance (1 / m) of the points;
+ *    10, 11 vx, vy: the unit eigenvector of l1 with vx > 0, or vx == 0 and vy > 0; (1, 0) when l1 == l2;
+ *    12, 13 axis_major, axis_minor: greatest minus least projection on (vx, vy) and on (-vy, vx);
+ *    14 axis_angle_deg = atan2(vy, vx) in degrees;  15 zero. */
+int lf_shape_stats(const int32_t* contour, const int32_t* counts, int cap, int64_t* ints, double* vals,
+                   int32_t* hull, int32_t* flags, int n, int h, int w, lf_stream_t stream);
+
+/* cv2.Canny(gray, low, high, L2gradient=l2gradient), aperture 3, for gray [N,H,W] uint8 of any size -> edges
+ * [N,H,W] uint8 (0 / 255): Sobel with replicated borders, the magnitude |dx| + |dy| against floor(threshold) or,
+ * with l2gradient, dx^2 + dy^2 against floor(min(32767, threshold)^2); low > high are swapped; 22.5 / 67.5 degree
+ * sectors in 15-bit fixed point, the asymmetric > / >= neighbour tests, 8-connected hysteresis (in LDS when the
+ * plane fits 156 KiB, in memory otherwise).  Parity unpinned (no cv2): oracle/cv_ops.canny is the same reading. */
+size_t lf_canny_workspace(int n, int h, int w);
+int lf_canny_u8(const uint8_t* gray, uint8_t* edges, int n, int h, int w, double low, double high, int l2gradient,
+                void* workspace, size_t ws_bytes, lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* JPEG encode (the file Pillow's Image.save(path, quality=q) writes)          */
 /* ------------------------------------------------------------------------- */

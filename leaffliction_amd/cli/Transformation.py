@@ -14,6 +14,11 @@ Not ported, each with one warning per run and no file: Analyze and Landmarks (Pl
 bilateral filtering, goodFeaturesToTrack) and the mosaic (cv2's Hershey text).  Hist is this project's own
 matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped.
 
+`--measure [FILE]` writes Analyze's numbers (not its picture) as one CSV table, a row per processed image in path
+order: shape, hull and axes from make_mask's contour (ops.shape_stats), the brown share and the Canny edge count
+inside the mask (transform.measure_leaves).  FILE defaults to measurements.csv in the output directory; in
+single-image mode put the flag after the image path, or write --measure=FILE.
+
 `create_transform_function` (at the end of the module) is the reference's training transform, the provider of
 ManifestSequence's `transform=` hook: see TransformFunction.
 """
@@ -129,6 +134,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--skip-existing", action="store_true", help="Skip images whose outputs already exist")
     p.add_argument("--overwrite", action="store_true", help="Overwrite existing outputs")
     p.add_argument("--preview", action="store_true", help="Force saving outputs (no GUI popups)")
+    p.add_argument("--measure", nargs="?", const="", default=None, metavar="FILE",
+                   help="Write leaf measurements (shape, hull, axes, brown share, edge count) of every processed "
+                        "image as CSV (default FILE: measurements.csv in the output directory)")
     return p.parse_args(argv)
 
 
@@ -220,19 +228,25 @@ def encode_jpeg_batch(x) -> List[bytes]:
     return out
 
 
-def transform_batch(x, types: Sequence[str], cfg) -> Dict[str, object]:
+def transform_batch(x, types: Sequence[str], cfg, measure: bool = False) -> Dict[str, object]:
     """process_single_image's data flow for a same-size batch [N,H,W,3] uint8 on the device.  Returns the device
     outputs of the requested ported types ("Mask", "Blur", "ROI", "Brown": [N,H,W,3] uint8), "brown_stats"
-    (percentages, counts, areas) with Brown, and "hist" (counts, histograms as numpy) with Hist."""
+    (percentages, counts, areas) with Brown, and "hist" (counts, histograms as numpy) with Hist.  measure: also
+    "measure", transform.measure_leaves' columns, from the one make_mask result, its white composite and Brown's stats
+    when Brown ran; no other output changes."""
     import torch
 
     from .. import ops
     from ..transform import filters as F
     res: Dict[str, object] = {}
     masked = x
-    if any(t in types for t in MASK_TYPES):
+    stats = None
+    wants_mask = any(t in types for t in MASK_TYPES)
+    if measure or wants_mask:
         mask, contour, counts, _fb = F.make_masks_device(x, cfg)
-        masked = ops.mask_composite_u8(x, mask, "white")
+        white = ops.mask_composite_u8(x, mask, "white")
+        if wants_mask:   # a mask made for the table alone leaves Hist on the image, as without --measure
+            masked = white
         if "Mask" in types:
             res["Mask"] = ops.mask_composite_u8(x, mask, "black")
         if "Blur" in types:   # apply_blur_filter(masked, cfg, make_mask): make_mask again, on `masked`
@@ -253,6 +267,9 @@ def transform_batch(x, types: Sequence[str], cfg) -> Dict[str, object]:
             st = stats.cpu().numpy().astype(np.int64)
             res["Brown"] = out
             res["brown_stats"] = [(int(c), a / max(lf, 1) * 100, int(a)) for c, a, lf in st.tolist()]
+        if measure:
+            res["measure"] = F.measure_leaves(x, cfg, masks=(mask, contour, counts, _fb), brown_stats=stats,
+                                              masked=white)[0]
     if "Hist" in types:
         counts_h, hist_h = ops.hsv_region_stats(masked.contiguous())
         res["hist"] = (counts_h.cpu().numpy(), hist_h.cpu().numpy())
@@ -260,8 +277,11 @@ def transform_batch(x, types: Sequence[str], cfg) -> Dict[str, object]:
 
 
 class _Runner:
-    def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor):
+    def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor,
+                 measure: bool = False):
         self.types, self.cfg, self.pool = types, cfg, pool
+        self.measure = measure
+        self.rows: Dict[Path, List[str]] = {}   # --measure: image path -> CSV cells after `file`
         self.skip_existing, self.overwrite = skip_existing, overwrite
         self.hist = "Hist" in types and _have_matplotlib()
         for t in NOT_PORTED:   # one warning per run
@@ -281,13 +301,21 @@ class _Runner:
         """items: (image path, output directory, RGB array), all of one size."""
         import torch
 
+        from .. import ops
         from ..transform.filters import _device
         saved: List[Path] = []
         dev = _device()
+        h, w = items[0][2].shape[:2]
+        measure = self.measure and ops.make_mask_fits(h, w, self.cfg.mask_upscale_factor,
+                                                      self.cfg.mask_upscale_long_side)
         for c0 in range(0, len(items), CHUNK):
             chunk = items[c0:c0 + CHUNK]
             x = torch.from_numpy(np.stack([a for _p, _d, a in chunk])).to(dev)
-            res = transform_batch(x, self.types, self.cfg)
+            res = transform_batch(x, self.types, self.cfg, measure)
+            if measure:
+                from ..transform.filters import measure_row
+                for i, (p, _d, _a) in enumerate(chunk):
+                    self.rows[p] = measure_row(res["measure"], i)
             names = [output_names(p.stem) for p, _d, _a in chunk]
             for t in ("Mask", "Blur", "ROI", "Brown"):   # process_single_image's order
                 if t not in res:
@@ -315,7 +343,8 @@ class _Runner:
 
     def run(self, jobs: List[Tuple[Path, Path]]) -> List[Path]:
         """jobs: (image path, output directory).  Decodes WINDOW files ahead on the host threads; unreadable files
-        and images over make_mask's size limit are logged and skipped."""
+        and images over make_mask's size limit are logged and skipped; where only --measure needs the mask, such an
+        image keeps its outputs and gets no row."""
         from .. import ops
         saved: List[Path] = []
         needs_mask = any(t in self.types for t in MASK_TYPES)
@@ -339,10 +368,29 @@ class _Runner:
                     logging.error("Skipping %s: %d x %d is over make_mask's size limit (square inputs up to "
                                   "399 x 399 at mask_upscale_factor 1.3)", path, h, w)
                     continue
+                if self.measure and not needs_mask and not ops.make_mask_fits(
+                        h, w, self.cfg.mask_upscale_factor, self.cfg.mask_upscale_long_side):
+                    logging.error("No measurements for %s: %d x %d is over make_mask's size limit", path, h, w)
                 groups.setdefault((h, w), []).append((path, out_dir, rgb))
             for items in groups.values():
                 saved.extend(self.run_group(items))
         return saved
+
+
+def write_measurements(path: Path, jobs: Sequence[Tuple[Path, Path]], rows: Dict[Path, List[str]],
+                       root: Optional[Path] = None) -> None:
+    """The --measure table: the header, then one row per processed image in the order of `jobs`; `file` is the path
+    relative to `root` (folder mode) or the file name."""
+    import csv
+
+    from ..transform.filters import MEASURE_COLUMNS
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        out = csv.writer(f)
+        out.writerow(("file",) + MEASURE_COLUMNS)
+        for p, _d in jobs:
+            if p in rows:
+                out.writerow([p.relative_to(root).as_posix() if root else p.name] + rows[p])
 
 
 def _workers(n: int) -> int:
@@ -374,7 +422,11 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         out_d = Path(args.out_dir) if args.out_dir else default_out_dir(ip)
         out_d.mkdir(parents=True, exist_ok=True)
         with ThreadPoolExecutor(_workers(args.workers)) as pool:
-            saved = _Runner(types, cfg, args.skip_existing, args.overwrite, pool).run([(ip, out_d)])
+            runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None)
+            saved = runner.run([(ip, out_d)])
+        if runner.measure:
+            write_measurements(Path(args.measure) if args.measure else out_d / "measurements.csv", [(ip, out_d)],
+                               runner.rows)
         print(f"Saved {len(saved)} outputs to {out_d}")
         for s in saved:
             print(f"  - {s}")
@@ -393,8 +445,13 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         logging.info("Found %d images in %s", len(imgs), src)
         n_threads = _workers(args.workers)
         logging.info("Using %d host threads", n_threads)
+        jobs = [(p, dst) for p in imgs]
         with ThreadPoolExecutor(n_threads) as pool:
-            saved = _Runner(types, cfg, args.skip_existing, args.overwrite, pool).run([(p, dst) for p in imgs])
+            runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None)
+            saved = runner.run(jobs)
+        if runner.measure:
+            write_measurements(Path(args.measure) if args.measure else dst / "measurements.csv", jobs, runner.rows,
+                               root=src)
         logging.info("Processed %d images, saved %d outputs", len(imgs), len(saved))
         return
 

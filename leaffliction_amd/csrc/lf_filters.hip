@@ -34,6 +34,46 @@ constexpr int kFlagFallback = 1, kFlagBound = 4;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// ---- contours (make_mask's trace, lf_roi_u8, lf_shape_stats)
+// One shoelace term c = x0 * y1 - x1 * y0; twice the signed area of a polygon is the sum over its edges.
+__device__ __forceinline__ long long shoelace_term(int x0, int y0, int x1, int y1) {
+    return (long long)x0 * y1 - (long long)x1 * y0;
+}
+
+// cv2.boundingRect of the first min(max(cnt, 0), cap) points of `pts` (x, y), by the whole workgroup of T threads:
+// lo / hi = the least / greatest x and y; bad = cnt outside [0, cap] or a point outside the h x w image.  Returns
+// the number of points read; nothing outside them is.  B lives in LDS and is valid after the call.
+struct ContourBox {
+    int lo[2], hi[2], bad;
+};
+
+template <int T>
+__device__ int contour_bbox(ContourBox& B, const int* __restrict__ pts, int cnt, int cap, int h, int w) {
+    if (threadIdx.x == 0) {
+        B.lo[0] = B.lo[1] = INT_MAX;
+        B.hi[0] = B.hi[1] = INT_MIN;
+        B.bad = cnt < 0 || cnt > cap;
+    }
+    __syncthreads();
+    const int m = min(max(cnt, 0), cap);
+    int lx = INT_MAX, ly = INT_MAX, hx = INT_MIN, hy = INT_MIN, bad = 0;
+    for (int i = threadIdx.x; i < m; i += T) {
+        const int x = pts[2 * i], y = pts[2 * i + 1];
+        bad |= x < 0 || x >= w || y < 0 || y >= h;
+        lx = min(lx, x);
+        ly = min(ly, y);
+        hx = max(hx, x);
+        hy = max(hy, y);
+    }
+    atomicMin(&B.lo[0], lx);
+    atomicMin(&B.lo[1], ly);
+    atomicMax(&B.hi[0], hx);
+    atomicMax(&B.hi[1], hy);
+    if (bad) atomicOr(&B.bad, 1);
+    __syncthreads();
+    return m;
+}
+
 // BORDER_REFLECT_101 for p in [-1, len]
 __device__ __forceinline__ int reflect101i(int p, int len) {
     if (len == 1) return 0;
@@ -1274,9 +1314,12 @@ int lf_blur_saliency_u8(const uint8_t* rgb, const uint8_t* leaf_mask, uint8_t* o
 // ===========================================================================
 namespace {
 
-__global__ __launch_bounds__(kBlock) void canny_sobel_l1_kernel(const uint8_t* __restrict__ gray,
-                                                                int32_t* __restrict__ mag,
-                                                                uint32_t* __restrict__ dxdy, int h, int w) {
+// Canny's Sobel pass (BORDER_REPLICATE) on its own: the magnitude, |dx| + |dy| (L1, cv2.Canny's default) or
+// dx^2 + dy^2, and the packed (dx, dy) that canny_nms_kernel reads.
+template <bool L1>
+__global__ __launch_bounds__(kBlock) void canny_sobel_kernel(const uint8_t* __restrict__ gray,
+                                                             int32_t* __restrict__ mag,
+                                                             uint32_t* __restrict__ dxdy, int h, int w) {
     const unsigned n = blockIdx.y;
     const int hw = h * w;
     const int p = blockIdx.x * kBlock + threadIdx.x;
@@ -1284,7 +1327,8 @@ __global__ __launch_bounds__(kBlock) void canny_sobel_l1_kernel(const uint8_t* _
     const int y = p / w, x = p - y * w;
     const Sob s = sobel_at(gray + (size_t)n * hw, w, clampi(y - 1, 0, h - 1), y, clampi(y + 1, 0, h - 1),
                            clampi(x - 1, 0, w - 1), x, clampi(x + 1, 0, w - 1));
-    mag[(size_t)n * hw + p] = (s.dx < 0 ? -s.dx : s.dx) + (s.dy < 0 ? -s.dy : s.dy);
+    mag[(size_t)n * hw + p] = L1 ? (s.dx < 0 ? -s.dx : s.dx) + (s.dy < 0 ? -s.dy : s.dy)
+                                 : __mul24(s.dx, s.dx) + __mul24(s.dy, s.dy);   // |d| <= 1020
     dxdy[(size_t)n * hw + p] = ((unsigned)s.dx & 0xffffu) | ((unsigned)s.dy << 16);
 }
 
@@ -1474,7 +1518,7 @@ int lf_inclusive_mask_u8(const uint8_t* rgb, uint8_t* mask, int n, int h, int w,
         inclusive_fused_kernel<<<n, kFuseT, fl, s>>>(rgb, ws.gray, ws.blur, ws.lb.tabs, ws.bits, h, w, hue_lo, hue_hi);
     } else {
         const dim3 grid_px((hw + kBlock - 1) / kBlock, n);
-        canny_sobel_l1_kernel<<<grid_px, kBlock, 0, s>>>(ws.gray, ws.mag, ws.dxdy, h, w);
+        canny_sobel_kernel<true><<<grid_px, kBlock, 0, s>>>(ws.gray, ws.mag, ws.dxdy, h, w);
         canny_nms_kernel<<<grid_px, kBlock, 0, s>>>(ws.mag, ws.dxdy, ws.map, h, w, 30, 100);   // cv2.Canny(gray, 30, 100)
         launch_canny_hysteresis(ws.map, n, h, w, s);
         const long segs = (long)n * h * ((w + 63) / 64);
@@ -1485,6 +1529,67 @@ int lf_inclusive_mask_u8(const uint8_t* rgb, uint8_t* mask, int n, int h, int w,
     inclusive_morph_kernel<<<n, kBlock, lds, s>>>(ws.bits, mask, ws.lb.rn, ws.lb.parent, ws.lb.area, h, w, wpr,
                                                   (int)mask_runs_per_image(h, w));
     return lf::check_launch("lf_inclusive_mask");
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// cv2.Canny(gray, low, high, L2gradient) on its own, for planes of any size: the multi-launch chain above (Sobel,
+// non-maximum suppression with the double threshold, hysteresis) with the thresholds as arguments.
+// ===========================================================================
+namespace {
+
+struct CannyWs {
+    int32_t* mag;
+    uint32_t* dxdy;
+    size_t bytes;
+    CannyWs(void* base, int n, int h, int w) {
+        Carver c{base};
+        const size_t px = (size_t)n * h * w;
+        mag = c.take<int32_t>(4 * px);
+        dxdy = c.take<uint32_t>(4 * px);
+        bytes = c.off;
+    }
+};
+
+// canny.cpp's integer threshold: floor(t) on |dx| + |dy|; with L2gradient floor(min(32767, t)^2) for t > 0
+int canny_threshold(double t, int l2) {
+    if (l2 && t > 0.0) t = std::min(32767.0, t) * std::min(32767.0, t);
+    return (int)std::floor(std::max(-1.0, std::min(t, 2147483647.0)));
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lf_canny_workspace(int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return CannyWs(nullptr, n, h, w).bytes;
+}
+
+int lf_canny_u8(const uint8_t* gray, uint8_t* edges, int n, int h, int w, double low, double high, int l2gradient,
+                void* workspace, size_t ws_bytes, lf_stream_t stream) {
+    LF_REQUIRE(gray && edges && workspace, "lf_canny: null buffer");
+    LF_REQUIRE(n > 0 && h > 0 && w > 0, "lf_canny: bad dims n=%d h=%d w=%d", n, h, w);
+    LF_REQUIRE(n <= 65535, "lf_canny: batch too large for grid.y");
+    LF_REQUIRE((size_t)h * w < ((size_t)1 << 30), "lf_canny: image too large");
+    LF_REQUIRE(low == low && high == high, "lf_canny: a threshold is NaN");
+    LF_REQUIRE(ws_bytes >= lf_canny_workspace(n, h, w), "lf_canny: workspace too small (%zu < %zu)", ws_bytes,
+               lf_canny_workspace(n, h, w));
+    LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, "lf_canny: workspace must be 16-byte aligned");
+    if (low > high) std::swap(low, high);   // as cv2.Canny does
+    const int lo = canny_threshold(low, l2gradient), hi = canny_threshold(high, l2gradient);
+    hipStream_t s = lf::as_stream(stream);
+    const int hw = h * w;
+    const CannyWs ws(workspace, n, h, w);
+    const dim3 grid_px((hw + kBlock - 1) / kBlock, n);
+    if (l2gradient)
+        canny_sobel_kernel<false><<<grid_px, kBlock, 0, s>>>(gray, ws.mag, ws.dxdy, h, w);
+    else
+        canny_sobel_kernel<true><<<grid_px, kBlock, 0, s>>>(gray, ws.mag, ws.dxdy, h, w);
+    canny_nms_kernel<<<grid_px, kBlock, 0, s>>>(ws.mag, ws.dxdy, edges, h, w, lo, hi);
+    launch_canny_hysteresis(edges, n, h, w, s);
+    return lf::check_launch("lf_canny");
 }
 
 }  // extern "C"
@@ -1638,7 +1743,7 @@ __device__ int trace_outer(const Post& P, const unsigned* pl, int x0, int y0, lo
             fx = x;
             fy = y;
         } else {
-            a2 += (long long)px * y - (long long)py * x;
+            a2 += shoelace_term(px, py, x, y);
         }
         px = x;
         py = y;
@@ -1675,7 +1780,7 @@ __device__ int trace_outer(const Post& P, const unsigned* pl, int x0, int y0, lo
         y3 = y4;
         s = (s + 4) & 7;
     }
-    a2 += (long long)px * fy - (long long)py * fx;
+    a2 += shoelace_term(px, py, fx, fy);
     area2 = a2 < 0 ? -a2 : a2;
     return npts;
 }
@@ -2144,32 +2249,10 @@ __global__ __launch_bounds__(kRoiT) void roi_kernel(const uint8_t* __restrict__ 
                                                     const int* __restrict__ counts, int cap, int h, int w, int rh,
                                                     int rw, uint8_t* __restrict__ canvas, uint8_t* __restrict__ vis,
                                                     int* __restrict__ bbox, int* __restrict__ flags) {
-    __shared__ int s_lo[2], s_hi[2], s_bad;
+    __shared__ ContourBox B;
     const size_t n = blockIdx.x;
-    const int cnt = counts[n];
-    if (threadIdx.x == 0) {
-        s_lo[0] = s_lo[1] = INT_MAX;
-        s_hi[0] = s_hi[1] = INT_MIN;
-        s_bad = cnt < 0 || cnt > cap;
-    }
-    __syncthreads();
-    const int m = min(max(cnt, 0), cap);
-    const int* pts = contour + n * (size_t)cap * 2;
-    int lx = INT_MAX, ly = INT_MAX, hx = INT_MIN, hy = INT_MIN, bad = 0;
-    for (int i = threadIdx.x; i < m; i += kRoiT) {
-        const int x = pts[2 * i], y = pts[2 * i + 1];
-        bad |= x < 0 || x >= w || y < 0 || y >= h;
-        lx = min(lx, x);
-        ly = min(ly, y);
-        hx = max(hx, x);
-        hy = max(hy, y);
-    }
-    atomicMin(&s_lo[0], lx);
-    atomicMin(&s_lo[1], ly);
-    atomicMax(&s_hi[0], hx);
-    atomicMax(&s_hi[1], hy);
-    if (bad) atomicOr(&s_bad, 1);
-    __syncthreads();
+    const int m = contour_bbox<kRoiT>(B, contour + n * (size_t)cap * 2, counts[n], cap, h, w);
+    const int *s_lo = B.lo, *s_hi = B.hi, s_bad = B.bad;
     const uint8_t* img = rgb + n * (size_t)h * w * 3;
     const bool found = m > 0 && !s_bad;
     const int bx = found ? s_lo[0] : 0, by = found ? s_lo[1] : 0;
@@ -2276,6 +2359,315 @@ int lf_roi_u8(const uint8_t* rgb, const int32_t* contour, const int32_t* counts,
     roi_kernel<<<n, kRoiT, 0, lf::as_stream(stream)>>>(rgb, contour, counts, cap, h, w, roi_h, roi_w, canvas, vis,
                                                        bbox, flags);
     return lf::check_launch("lf_roi");
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// lf_shape_stats: the numbers behind srcs/transform/filters/analyze.py (centroid, extreme points, convex hull, PCA
+// axes) and the ones pcv.analyze_object computes there and drops (area, hull area, solidity, perimeter), from the
+// contour buffer alone: one workgroup per image, no pixel is read.  The definitions are in include/leafhip.h.
+//  * Bounds: h, w <= 4096 and cap <= 65536, so |c_i| < 2^25, |(x_i + x_{i+1}) c_i| < 2^38 and every sum over the
+//    points is below 2^54: int64 holds them all, and m * sxx - sx^2 (< 2^57) as well.
+//  * Determinism: the integer sums may be added in any order; the one float64 sum (the perimeter) and the
+//    projection extremes go thread-strided, then down a fixed shuffle tree, then over the waves in order.
+//  * Hull: only the lowest and the highest point of a column can be a vertex of the strict hull, and the columns
+//    come sorted by x.  Andrew's chain over (x, min y) left to right and over (x, max y) right to left, popping
+//    while the cross product is <= 0, is Andrew's chain over the sorted point set: the other point of a column
+//    would be pushed and popped again by the next column without touching what lies below it.  Each chain is one
+//    lane's walk over LDS; its stack overwrites the column entries it has already read (a stack never holds more
+//    than the columns consumed).  Repeated and touching points are nothing special: the column table is a set.
+//  * Cost: the two chains are serial walks of one lane each over the bounding box's columns while the rest of the
+//    workgroup waits, and the Feret pass is hull_n^2 / 512 distance tests per thread.  Measured only at 256 x 256
+//    leaf scenes (boxes about 200 columns wide, 41 hull vertices: 0.1 ms per 1,024 images).  A box near 4,096
+//    columns has not been measured; its walks are 20 times longer and would want the chains split over lanes.
+// ===========================================================================
+namespace {
+
+constexpr int kShapeT = 256;
+constexpr int kShapeMaxDim = 4096, kShapeMaxCap = 65536;
+constexpr int kShapeInts = 32, kShapeVals = 16;
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+    for (int off = 32; off; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
+// (value, index) of the least (MAX: greatest) value over the wave, the lower index on a tie
+template <bool MAX>
+__device__ __forceinline__ void wave_arg(double& v, int& i) {
+    for (int off = 32; off; off >>= 1) {
+        const double ov = __shfl_down(v, off);
+        const int oi = __shfl_down(i, off);
+        if ((MAX ? ov > v : ov < v) || (ov == v && oi < i)) {
+            v = ov;
+            i = oi;
+        }
+    }
+}
+
+__device__ __forceinline__ int hull_pack(int x, int y) { return (x << 16) | y; }
+__device__ __forceinline__ int hull_cross(int a, int b, int x, int y) {   // (b - a) x (p - a), |.| < 2^25
+    const int ax = a >> 16, ay = a & 0xffff;
+    return ((b >> 16) - ax) * (y - ay) - ((b & 0xffff) - ay) * (x - ax);
+}
+
+__global__ __launch_bounds__(kShapeT) void shape_stats_kernel(const int* __restrict__ contour,
+                                                              const int* __restrict__ counts, int cap, int h, int w,
+                                                              long long* __restrict__ ints, double* __restrict__ vals,
+                                                              int* __restrict__ hull, int* __restrict__ flags) {
+    __shared__ ContourBox B;
+    __shared__ int s_col[2][kShapeMaxDim];          // per column: min y | max y, then the two chain stacks
+    __shared__ unsigned long long s_sum[8];
+    __shared__ unsigned s_ext[4];
+    __shared__ double s_wv[kShapeT / 64][4];
+    __shared__ int s_wi[kShapeT / 64][4];
+    __shared__ double s_per[kShapeT / 64], s_axis[2];
+    __shared__ int s_hn[4], s_over;                  // lower count, upper start, upper count, hull count
+    __shared__ unsigned long long s_feret;
+    __shared__ long long s_ha2;
+    const size_t n = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int* pts = contour + n * (size_t)cap * 2;
+    const int hcap = 2 * min(h, w);
+    long long* oi = ints + n * kShapeInts;
+    double* ov = vals + n * kShapeVals;
+    int* oh = hull + n * (size_t)hcap * 2;
+    const int m = contour_bbox<kShapeT>(B, pts, counts[n], cap, h, w);
+    if (m == 0 || B.bad) {
+        for (int i = tid; i < kShapeInts; i += kShapeT) oi[i] = 0;
+        for (int i = tid; i < kShapeVals; i += kShapeT) ov[i] = 0.0;
+        for (int i = tid; i < 2 * hcap; i += kShapeT) oh[i] = 0;
+        if (tid == 0) flags[n] = B.bad ? kRoiBad : 0;
+        return;
+    }
+    const int bx = B.lo[0], by = B.lo[1], bw = B.hi[0] - bx + 1, bh = B.hi[1] - by + 1;
+    for (int i = tid; i < bw; i += kShapeT) {
+        s_col[0][i] = INT_MAX;
+        s_col[1][i] = -1;
+    }
+    if (tid < 8) s_sum[tid] = 0ull;
+    if (tid < 4) s_ext[tid] = (tid & 1) ? 0u : 0xffffffffu;
+    if (tid == 0) s_feret = 0ull;
+    __syncthreads();
+
+    // ---- the sums over the points, the first extreme points, the column table
+    long long a2 = 0, s10 = 0, s01 = 0, sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0;
+    double per = 0.0;
+    unsigned e_l = 0xffffffffu, e_r = 0u, e_t = 0xffffffffu, e_b = 0u;
+    for (int i = tid; i < m; i += kShapeT) {
+        const int j = i + 1 < m ? i + 1 : 0;
+        const int x = pts[2 * i], y = pts[2 * i + 1], xn = pts[2 * j], yn = pts[2 * j + 1];
+        const long long c = shoelace_term(x, y, xn, yn);
+        a2 += c;
+        s10 += (x + xn) * c;
+        s01 += (y + yn) * c;
+        sx += x;
+        sy += y;
+        sxx += x * x;
+        sxy += x * y;
+        syy += y * y;
+        const int dx = xn - x, dy = yn - y;
+        per = __dadd_rn(per, __dsqrt_rn((double)(dx * dx + dy * dy)));
+        const unsigned fwd = (unsigned)i, rev = (unsigned)(kShapeMaxCap - 1 - i);   // the first index wins
+        e_l = min(e_l, ((unsigned)x << 16) | fwd);
+        e_r = max(e_r, ((unsigned)x << 16) | rev);
+        e_t = min(e_t, ((unsigned)y << 16) | fwd);
+        e_b = max(e_b, ((unsigned)y << 16) | rev);
+        atomicMin(&s_col[0][x - bx], y);
+        atomicMax(&s_col[1][x - bx], y);
+    }
+    atomicMin(&s_ext[0], e_l);
+    atomicMax(&s_ext[1], e_r);
+    atomicMin(&s_ext[2], e_t);
+    atomicMax(&s_ext[3], e_b);
+    const long long part[8] = {a2, s10, s01, sx, sy, sxx, sxy, syy};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const long long t = wave_sum(part[k]);
+        if (lane == 0) atomicAdd(&s_sum[k], (unsigned long long)t);
+    }
+    for (int off = 32; off; off >>= 1) per = __dadd_rn(per, __shfl_down(per, off));
+    if (lane == 0) s_per[wv] = per;
+    __syncthreads();
+
+    // ---- the axes: eigenvectors of [[A, Bc], [Bc, C]] / m^2, A = m sxx - sx^2 and so on, exact in int64
+    if (tid == 0) {
+        const long long SX = (long long)s_sum[3], SY = (long long)s_sum[4];
+        const long long A = m * (long long)s_sum[5] - SX * SX, Bc = m * (long long)s_sum[6] - SX * SY,
+                        C = m * (long long)s_sum[7] - SY * SY;
+        double vx = 1.0, vy = 0.0;
+        if (A != C || Bc != 0) {
+            const double d = __dmul_rn(0.5, (double)(A - C)), b = (double)Bc;
+            const double r = __dsqrt_rn(__dadd_rn(__dmul_rn(d, d), __dmul_rn(b, b)));
+            // (r + d, b) and (b, r - d) are both eigenvectors of the greater eigenvalue: the one without cancellation
+            vx = d >= 0.0 ? __dadd_rn(r, d) : b;
+            vy = d >= 0.0 ? b : __dsub_rn(r, d);
+            const double len = __dsqrt_rn(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)));
+            vx = __ddiv_rn(vx, len);
+            vy = __ddiv_rn(vy, len);
+            if (vx < 0.0 || (vx == 0.0 && vy < 0.0)) {
+                vx = -vx;
+                vy = -vy;
+            }
+        }
+        s_axis[0] = vx;
+        s_axis[1] = vy;
+    }
+    // ---- the hull chains, one lane each, while the other waves wait at the barrier
+    if (tid == 0) {   // (x, min y), left to right; the stack grows from s_col[0][0]
+        int* S = s_col[0];
+        int sp = 0;
+        for (int k = 0; k < bw; ++k) {
+            const int y = S[k];
+            if (y == INT_MAX) continue;
+            while (sp >= 2 && hull_cross(S[sp - 2], S[sp - 1], bx + k, y) <= 0) --sp;
+            S[sp++] = hull_pack(bx + k, y);
+        }
+        s_hn[0] = sp;
+    }
+    if (tid == 64) {   // (x, max y), right to left; the stack grows down from s_col[1][bw - 1]
+        int* S = s_col[1];
+        int sp = 0;
+        for (int k = bw - 1; k >= 0; --k) {
+            const int y = S[k];
+            if (y < 0) continue;
+            while (sp >= 2 && hull_cross(S[bw - sp + 1], S[bw - sp], bx + k, y) <= 0) --sp;
+            S[bw - 1 - sp++] = hull_pack(bx + k, y);
+        }
+        s_hn[2] = sp;
+    }
+    __syncthreads();
+    if (tid == 0) {   // join: a chain's last point may be the other's first
+        const int nl = s_hn[0], nu = s_hn[2];
+        int us = 0, un = nu;
+        if (s_col[0][nl - 1] == s_col[1][bw - 1]) us = 1, --un;
+        if (un > 0 && s_col[1][bw - nu] == s_col[0][0]) --un;
+        s_hn[1] = us;
+        s_hn[2] = un;
+        // nl + un <= hcap for any point set (two vertices per row and per column at most).  Defence only, against a
+        // store past the hull buffer should the chains ever be wrong: the count is cut and the image flagged bad.
+        s_hn[3] = min(nl + un, hcap);
+        s_over = nl + un > hcap;
+        s_ha2 = 0;
+    }
+    __syncthreads();
+    const int nl = s_hn[0], us = s_hn[1], hn = s_hn[3];
+    auto hull_at = [&](int k) -> int { return k < nl ? s_col[0][k] : s_col[1][bw - 1 - (k - nl + us)]; };
+
+    // ---- projection extremes, hull area, Feret diameter, the hull itself
+    const double vx = s_axis[0], vy = s_axis[1];
+    double p0lo = INFINITY, p0hi = -INFINITY, p1lo = INFINITY, p1hi = -INFINITY;
+    int i0lo = INT_MAX, i0hi = INT_MAX, i1lo = INT_MAX, i1hi = INT_MAX;
+    for (int i = tid; i < m; i += kShapeT) {
+        const double x = (double)pts[2 * i], y = (double)pts[2 * i + 1];
+        const double p0 = __dadd_rn(__dmul_rn(x, vx), __dmul_rn(y, vy));
+        const double p1 = __dsub_rn(__dmul_rn(y, vx), __dmul_rn(x, vy));
+        if (p0 < p0lo) p0lo = p0, i0lo = i;
+        if (p0 > p0hi) p0hi = p0, i0hi = i;
+        if (p1 < p1lo) p1lo = p1, i1lo = i;
+        if (p1 > p1hi) p1hi = p1, i1hi = i;
+    }
+    wave_arg<false>(p0lo, i0lo);
+    wave_arg<true>(p0hi, i0hi);
+    wave_arg<false>(p1lo, i1lo);
+    wave_arg<true>(p1hi, i1hi);
+    if (lane == 0) {
+        s_wv[wv][0] = p0lo, s_wv[wv][1] = p0hi, s_wv[wv][2] = p1lo, s_wv[wv][3] = p1hi;
+        s_wi[wv][0] = i0lo, s_wi[wv][1] = i0hi, s_wi[wv][2] = i1lo, s_wi[wv][3] = i1hi;
+    }
+    long long ha2 = 0;
+    unsigned long long far = 0ull;
+    for (int k = tid; k < hn; k += kShapeT) {
+        const int a = hull_at(k), b = hull_at(k + 1 < hn ? k + 1 : 0);
+        const int ax = a >> 16, ay = a & 0xffff;
+        ha2 += shoelace_term(ax, ay, b >> 16, b & 0xffff);
+        for (int q = k + 1; q < hn; ++q) {
+            const int c = hull_at(q);
+            const long long dx = (c >> 16) - ax, dy = (c & 0xffff) - ay;
+            far = max(far, (unsigned long long)(dx * dx + dy * dy));
+        }
+        oh[2 * k] = ax;
+        oh[2 * k + 1] = ay;
+    }
+    for (int i = 2 * hn + tid; i < 2 * hcap; i += kShapeT) oh[i] = 0;
+    ha2 = wave_sum(ha2);
+    if (lane == 0) atomicAdd((unsigned long long*)&s_ha2, (unsigned long long)ha2);
+    atomicMax(&s_feret, far);
+    __syncthreads();
+
+    if (tid == 0) {
+        for (int q = 0; q < 4; ++q) {   // over the waves in order; the lower index on a tie
+            double v = s_wv[0][q];
+            int ix = s_wi[0][q];
+            for (int k = 1; k < kShapeT / 64; ++k) {
+                const double o = s_wv[k][q];
+                if (((q & 1) ? o > v : o < v) || (o == v && s_wi[k][q] < ix)) v = o, ix = s_wi[k][q];
+            }
+            s_wv[0][q] = v;
+            s_wi[0][q] = ix;
+        }
+        double perim = s_per[0];
+        for (int k = 1; k < kShapeT / 64; ++k) perim = __dadd_rn(perim, s_per[k]);
+        const long long A2 = (long long)s_sum[0], S10 = (long long)s_sum[1], S01 = (long long)s_sum[2];
+        const long long SX = (long long)s_sum[3], SY = (long long)s_sum[4], SXX = (long long)s_sum[5],
+                        SXY = (long long)s_sum[6], SYY = (long long)s_sum[7];
+        const long long HA2 = s_ha2 < 0 ? -s_ha2 : s_ha2, F2 = (long long)s_feret;
+        const int il = s_ext[0] & 0xffff, ir = kShapeMaxCap - 1 - (s_ext[1] & 0xffff), it = s_ext[2] & 0xffff,
+                  ib = kShapeMaxCap - 1 - (s_ext[3] & 0xffff);
+        const long long rec[29] = {m, A2, S10, S01, bx, by, bw, bh,
+                                   pts[2 * il], pts[2 * il + 1], pts[2 * ir], pts[2 * ir + 1],
+                                   pts[2 * it], pts[2 * it + 1], pts[2 * ib], pts[2 * ib + 1],
+                                   bx > 0 && by > 0 && bx + bw < w && by + bh < h,
+                                   SX, SY, SXX, SXY, SYY, hn, HA2, F2,
+                                   s_wi[0][0], s_wi[0][1], s_wi[0][2], s_wi[0][3]};
+#pragma unroll
+        for (int k = 0; k < kShapeInts; ++k) oi[k] = k < 29 ? rec[k] : 0;
+
+        const double area = __dmul_rn(0.5, (double)(A2 < 0 ? -A2 : A2)), harea = __dmul_rn(0.5, (double)HA2);
+        const double md = (double)m;
+        const double cx = A2 ? __ddiv_rn((double)S10, (double)(3 * A2)) : __ddiv_rn((double)SX, md);
+        const double cy = A2 ? __ddiv_rn((double)S01, (double)(3 * A2)) : __ddiv_rn((double)SY, md);
+        const long long A = m * SXX - SX * SX, Bc = m * SXY - SX * SY, C = m * SYY - SY * SY;
+        const double mean = __dmul_rn(0.5, (double)(A + C)), d = __dmul_rn(0.5, (double)(A - C)), b = (double)Bc;
+        const double r = __dsqrt_rn(__dadd_rn(__dmul_rn(d, d), __dmul_rn(b, b))), m2 = __dmul_rn(md, md);
+        const double pi = 3.141592653589793;
+        ov[0] = area;
+        ov[1] = perim;
+        ov[2] = cx;
+        ov[3] = cy;
+        ov[4] = harea;
+        ov[5] = HA2 ? __ddiv_rn(area, harea) : 0.0;
+        ov[6] = perim > 0.0 ? __ddiv_rn(__dmul_rn(__dmul_rn(4.0, pi), area), __dmul_rn(perim, perim)) : 0.0;
+        ov[7] = __dsqrt_rn((double)F2);
+        ov[8] = __ddiv_rn(__dadd_rn(mean, r), m2);
+        ov[9] = fmax(__ddiv_rn(__dsub_rn(mean, r), m2), 0.0);
+        ov[10] = vx;
+        ov[11] = vy;
+        ov[12] = __dsub_rn(s_wv[0][1], s_wv[0][0]);
+        ov[13] = __dsub_rn(s_wv[0][3], s_wv[0][2]);
+        ov[14] = __ddiv_rn(__dmul_rn(atan2(vy, vx), 180.0), pi);
+        ov[15] = 0.0;
+        flags[n] = kRoiFound | (s_over ? kRoiBad : 0);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int lf_shape_stats(const int32_t* contour, const int32_t* counts, int cap, int64_t* ints, double* vals,
+                   int32_t* hull, int32_t* flags, int n, int h, int w, lf_stream_t stream) {
+    LF_REQUIRE(contour && counts && ints && vals && hull && flags, "lf_shape_stats: null buffer");
+    LF_REQUIRE(n > 0 && h > 0 && w > 0 && cap > 0, "lf_shape_stats: bad dims n=%d %dx%d cap=%d", n, h, w, cap);
+    LF_REQUIRE(n <= 65535, "lf_shape_stats: batch too large for the grid");
+    LF_REQUIRE(h <= kShapeMaxDim && w <= kShapeMaxDim && cap <= kShapeMaxCap,
+               "lf_shape_stats: %d x %d with cap %d is over the limits (h, w <= %d, cap <= %d) that keep every sum "
+               "inside int64", h, w, cap, kShapeMaxDim, kShapeMaxCap);
+    static_assert(sizeof(long long) == sizeof(int64_t), "the integer record is int64");
+    shape_stats_kernel<<<n, kShapeT, 0, lf::as_stream(stream)>>>(contour, counts, cap, h, w,
+                                                                 reinterpret_cast<long long*>(ints), vals, hull, flags);
+    return lf::check_launch("lf_shape_stats");
 }
 
 }  // extern "C"

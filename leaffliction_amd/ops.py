@@ -448,6 +448,55 @@ def roi_u8(x: torch.Tensor, contour: torch.Tensor, counts: torch.Tensor, roi_siz
     return canvas, vis, bbox, (flags & 1).bool()
 
 
+SHAPE_INT_FIELDS = ("npts", "area2s", "s10", "s01", "bbox_x", "bbox_y", "bbox_w", "bbox_h", "left_x", "left_y",
+                    "right_x", "right_y", "top_x", "top_y", "bottom_x", "bottom_y", "in_frame", "sx", "sy", "sxx",
+                    "sxy", "syy", "hull_n", "hull_area2", "feret2", "i0min", "i0max", "i1min", "i1max")
+SHAPE_VAL_FIELDS = ("area", "perimeter", "cx", "cy", "hull_area", "solidity", "circularity", "feret", "l1", "l2",
+                    "vx", "vy", "axis_major", "axis_minor", "axis_angle_deg")
+
+
+def shape_stats(contour: torch.Tensor, counts: torch.Tensor, h: int, w: int):
+    """Leaf measurements from make_mask_u8's contour buffer (contour [N,K,2] int32 (x, y), counts [N] int32) for
+    h x w images: (ints [N,32] int64, vals [N,16] float64, hull [N, 2 * min(h, w), 2] int32, found [N] bool).  The
+    leading columns of ints / vals are SHAPE_INT_FIELDS / SHAPE_VAL_FIELDS, the rest zero; the first ints[i, 22]
+    rows of hull[i] are the strict convex hull.  An image without a contour has found False and zero records.  The
+    definitions: include/leafhip.h (lf_shape_stats).  h, w <= 4096 and K <= 65536."""
+    _chk(contour, _I32, "shape_stats.contour", 3)
+    _chk(counts, _I32, "shape_stats.counts", 1)
+    n = contour.shape[0]
+    if contour.shape[2] != 2 or contour.shape[1] < 1 or n < 1 or tuple(counts.shape) != (n,) \
+            or counts.device != contour.device:
+        raise ValueError(f"shape_stats: expected contour [N,K,2] and counts [N] on one device, got "
+                         f"{list(contour.shape)} and {list(counts.shape)}")
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"shape_stats: bad image size {h} x {w}")
+    dev = contour.device
+    ints = torch.empty((n, 32), dtype=torch.int64, device=dev)
+    vals = torch.empty((n, 16), dtype=torch.float64, device=dev)
+    hull = torch.empty((n, 2 * min(h, w), 2), dtype=_I32, device=dev)
+    flags = torch.empty(n, dtype=_I32, device=dev)
+    _lib.call("lf_shape_stats", contour.data_ptr(), counts.data_ptr(), int(contour.shape[1]), ints.data_ptr(),
+              vals.data_ptr(), hull.data_ptr(), flags.data_ptr(), n, h, w, _stream())
+    if bool((flags & 4).any()):
+        raise _lib.LeafHipError("lf_shape_stats: a contour count outside the buffer or a point outside the image (or a "
+                                "hull past its capacity: a bug)")
+    return ints, vals, hull, (flags & 1).bool()
+
+
+def canny_u8(gray: torch.Tensor, low: float, high: float, l2gradient: bool = True) -> torch.Tensor:
+    """cv2.Canny(gray, low, high, L2gradient=l2gradient) for gray [N,H,W] uint8 of any size: edges [N,H,W] uint8
+    (0 / 255).  The reading: include/leafhip.h (lf_canny_u8), the same as oracle/cv_ops.canny."""
+    _chk(gray, _U8, "canny.gray", 3)
+    n, h, w = (int(v) for v in gray.shape)
+    nbytes = int(_lib.load().lf_canny_workspace(n, h, w))
+    ws = torch.empty(nbytes, dtype=_U8, device=gray.device)
+    out = torch.empty_like(gray)
+    _lib.call("lf_canny_u8", gray.data_ptr(), out.data_ptr(), n, h, w, float(low), float(high),
+              1 if l2gradient else 0, ws.data_ptr(), nbytes, _stream())
+    return out
+
+
 def jpeg_fdct_quant_u8(x: torch.Tensor, quality: int = 95, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The pixel half of Image.save(path, quality=quality) (image_utils.py:49-56) for a batch [N,H,W,3] uint8
     : libjpeg's quantised DCT coefficients, int16 [N, ceil(H/16) * ceil(W/16), 6, 64] — per MCU the

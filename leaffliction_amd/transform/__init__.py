@@ -2,4 +2,4 @@
 from .filters import (TransformConfig, analyze_color_regions, apply_blur_filter, apply_brown_filter,  # noqa: F401
                       apply_mask_filter, apply_roi_filter, brown_filter_batch, create_inclusive_mask,
                       hsv_density_curves, hue_range_counts, leaf_hsv_histograms, load_config, make_mask, make_masks,
-                      roi_filter_batch)
+                      measure_leaves, roi_filter_batch)

@@ -258,6 +258,81 @@ def apply_roi_filter(rgb: np.ndarray, contour: Optional[np.ndarray], cfg):
     return canvas[0].cpu().numpy(), vis[0].cpu().numpy(), bboxes[0]
 
 
+# One row of leaf measurements: the CSV columns of `Transformation --measure` after `file`.  Integer columns hold
+# int64, the others float64; SHAPE_COLUMNS are empty (NaN / 0 here, empty cells in the CSV) without a contour.
+MEASURE_COLUMNS = ("width", "height", "found", "fallback", "contour_points", "area", "perimeter", "centroid_x",
+                   "centroid_y", "bbox_x", "bbox_y", "bbox_w", "bbox_h", "in_frame", "left_x", "left_y", "right_x",
+                   "right_y", "top_x", "top_y", "bottom_x", "bottom_y", "hull_points", "hull_area", "solidity",
+                   "circularity", "feret", "axis_major", "axis_minor", "axis_angle_deg", "pca_l1", "pca_l2", "mask_px",
+                   "brown_regions", "brown_px", "brown_pct", "edge_px")
+_MEASURE_FROM_SHAPE = {"contour_points": "npts", "centroid_x": "cx", "centroid_y": "cy", "hull_points": "hull_n",
+                       "pca_l1": "l1", "pca_l2": "l2"}
+SHAPE_COLUMNS = MEASURE_COLUMNS[4:32]
+
+
+def measure_leaves(batch, cfg, masks=None, brown_stats=None, masked=None):
+    """The numbers behind srcs/transform/filters/analyze.py for a same-size batch [N,H,W,3] uint8 (numpy or a CUDA
+    tensor), as data: (columns: {name: numpy [N]} for MEASURE_COLUMNS, hulls: per image int32 [k,2] (x, y),
+    edges [N,H,W] uint8 0 / 255 on the device).  masks: make_masks_device's (mask, contour, counts[, fallback]) when
+    the caller has them; masked: the white composite of (batch, mask), and brown_stats: ops.brown_spots_u8's stats of
+    (masked, mask), likewise.  Shape, hull and axes
+    come from ops.shape_stats on the contour; mask_px = count(mask > 0); the brown numbers are apply_brown_filter's
+    on the white composite; edges = Canny(gray(masked), 80, 160, L2) inside the mask (analyze.py:115-121), edge_px
+    their count.  An image without a contour has found 0, NaN in its float shape columns and 0 in the integer ones."""
+    x = _device_u8(batch, 4, "measure_leaves.batch")
+    n, h, w = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    if masks is None:
+        masks = make_masks_device(x, cfg)
+    mask, contour, counts = masks[0], masks[1], masks[2]
+    fallback = masks[3] if len(masks) > 3 else torch.zeros(n, dtype=torch.bool, device=x.device)
+    ints, vals, hull, found = ops.shape_stats(contour, counts, h, w)
+    leaf = mask > 0
+    mask_px = leaf.sum(dim=(1, 2))
+    if masked is None:
+        masked = ops.mask_composite_u8(x, mask, "white")
+    if brown_stats is None:
+        brown_stats = ops.brown_spots_u8(
+            masked, mask, brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
+            brown_v_max=int(cfg.brown_v_max), use_lab_brown=bool(cfg.use_lab_brown), lab_a_min=int(cfg.lab_a_min),
+            lab_b_min=int(cfg.lab_b_min), brown_min_area_px=int(cfg.brown_min_area_px),
+            brown_morph_kernel=int(cfg.brown_morph_kernel))[1]
+    edges = ops.canny_u8(ops.rgb2gray_u8(masked), 80, 160, True) * leaf
+    edge_px = (edges > 0).sum(dim=(1, 2))
+
+    ih, vh, fh = ints.cpu().numpy(), vals.cpu().numpy(), found.cpu().numpy()
+    st = (brown_stats.cpu().numpy() if isinstance(brown_stats, torch.Tensor) else np.asarray(brown_stats)).astype(np.int64)
+    cols: Dict[str, np.ndarray] = {"width": np.full(n, w, np.int64), "height": np.full(n, h, np.int64),
+                                   "found": fh.astype(np.int64), "fallback": fallback.cpu().numpy().astype(np.int64)}
+    for name in SHAPE_COLUMNS:
+        key = _MEASURE_FROM_SHAPE.get(name, name)
+        if key in ops.SHAPE_INT_FIELDS:
+            cols[name] = ih[:, ops.SHAPE_INT_FIELDS.index(key)].copy()
+        else:
+            cols[name] = np.where(fh, vh[:, ops.SHAPE_VAL_FIELDS.index(key)], np.nan)
+    cols["mask_px"] = mask_px.cpu().numpy().astype(np.int64)
+    cols["brown_regions"], cols["brown_px"] = st[:, 0].copy(), st[:, 1].copy()
+    cols["brown_pct"] = np.array([st[i, 1] / max(st[i, 2], 1) * 100 for i in range(n)], dtype=np.float64)
+    cols["edge_px"] = edge_px.cpu().numpy().astype(np.int64)
+    hh = hull.cpu().numpy()
+    hulls = [hh[i, :int(ih[i, ops.SHAPE_INT_FIELDS.index("hull_n")])].copy() for i in range(n)]
+    return cols, hulls, edges
+
+
+def measure_row(cols: Dict[str, np.ndarray], i: int) -> list:
+    """Row i of measure_leaves' columns as CSV cells (without `file`): integers as they are, floats with repr, the
+    shape columns empty when the image has no contour."""
+    cells = []
+    for name in MEASURE_COLUMNS:
+        v = cols[name][i]
+        if name in SHAPE_COLUMNS and not cols["found"][i]:
+            cells.append("")
+        elif np.issubdtype(cols[name].dtype, np.integer):
+            cells.append(str(int(v)))
+        else:
+            cells.append(repr(float(v)))
+    return cells
+
+
 def _stats(rgb: np.ndarray):
     counts, hist = ops.hsv_region_stats(_rgb_batch(rgb))
     return counts[0].cpu().numpy().astype(np.int64), hist[0].cpu().numpy().astype(np.int64)
