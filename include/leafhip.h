@@ -269,6 +269,49 @@ int lf_roi_u8(const uint8_t* rgb, const int32_t* contour, const int32_t* counts,
 int lf_shape_stats(const int32_t* contour, const int32_t* counts, int cap, int64_t* ints, double* vals,
                    int32_t* hull, int32_t* flags, int n, int h, int w, lf_stream_t stream);
 
+/* apply_analyze_filter's picture (srcs/transform/filters/analyze.py) for a same-size batch, drawn from the contour
+ * buffer lf_make_mask_u8 made, lf_shape_stats' records for the same contours and Canny edges:
+ * rgb [N,H,W,3], mask [N,H,W], edges [N,H,W], contour [N,cap,2], counts [N], ints [N][32], vals [N][16],
+ * hull [N][2 * min(h, w)][2] -> out [N,H,W,3] (must not overlap rgb), flags [N] with lf_roi_u8's bits: bit 0 the
+ * image has a contour (else out is the input; the reference's "Analyze: no object" caption needs cv2's font and is
+ * not drawn), bit 2 a count outside [0, cap] or a point outside the image (an error; out is the input).  Limits as
+ * lf_shape_stats (h, w <= 4096, cap <= 65536), checked before any launch.  No workspace; two launches give the same
+ * bits.  The records are not trusted: the hull count is cut to its capacity, indices into [0, m), coordinates as
+ * below, and no pixel outside the image is touched.
+ *
+ * Drawing rules.  cv2 is not available to pin LineAA or FillConvexPoly, so these are the project's own rules, in
+ * integers throughout, restated in numpy by tests/draw_ref.py; they reproduce the cv2 readings the ROI box relies
+ * on (an axis-aligned thickness-2 line is the rows y - 1 .. y + 1 with a plus-sign cap; the radius-3 disc has rows
+ * 3, 5, 7, 7, 7, 5, 3 wide).  Parity unpinned (no cv2).
+ *   Points are integer (x, y).  For a segment A -> B and a pixel p: d = B - A, L2 = |d|^2, u = (p - A) . d,
+ *   c = (p - A) x d, all in int64.
+ *   Thick segment (thickness 2, colour k): p = k when its distance to the segment is <= 1: |p - A|^2 <= 1 if u <= 0,
+ *     |p - B|^2 <= 1 if u >= L2, c^2 <= L2 otherwise.  A = B gives the plus sign at A.  An overwrite: no order.
+ *   Disc (radius 3, centre q, colour k): p = k when |p - q|^2 <= 12.
+ *   Anti-aliased segment (thickness 1, colour k): the pixels with 0 <= u <= L2 and c^2 < L2 (A = B: the pixel A
+ *     alone) are blended once each, per channel out = (a k + (256 - a) out + 128) >> 8 with
+ *     a = 256 - floor(sqrt(floor(65536 c^2 / L2))) (A = B: a = 256).  Segments are drawn one after another in the
+ *     stated order; a pixel two segments touch is blended twice, in that order.
+ *   Clipping: a pixel outside the image is skipped; nothing else clips.
+ *   Record coordinates (the centroid, the extreme points, the hull's vertices) are clamped to [-16384, 16383] before
+ *     drawing.  Only the centroid of a self-touching contour with a small signed area can be that far out; the clamp
+ *     keeps c^2 below 2^62.
+ * Paint order for an image with a contour P_0 .. P_{m-1}, on a copy of the input (analyze.py's order):
+ *   1 the contour: thick segments P_i -> P_{(i+1) mod m} in (255, 0, 0);
+ *   2 the centroid marker: (cx, cy) = vals[2], vals[3] truncated toward zero; thick segments
+ *     (cx - 7, cy) -> (cx + 7, cy) and (cx, cy - 7) -> (cx, cy + 7) in (255, 255, 0);
+ *   3 for left, right, top, bottom (ints[8..15]) in that order: the disc at the point, then the anti-aliased
+ *     segment centroid -> point, both in (255, 255, 0);
+ *   4 the hull: anti-aliased segments H_i -> H_{(i+1) mod hull_n}, i = 0 .. hull_n - 1, in (0, 255, 0) (one vertex:
+ *     one degenerate segment; two: the segment there and back);
+ *   5 the axes: thick segments P[i0min] -> P[i0max] in (255, 255, 0), then P[i1min] -> P[i1max] in (255, 0, 255)
+ *     (ints[25..28]);
+ *   6 every pixel with edges > 0 and mask > 0 becomes (0, 255, 255). */
+int lf_analyze_overlay_u8(const uint8_t* rgb, const uint8_t* mask, const uint8_t* edges, const int32_t* contour,
+                          const int32_t* counts, int cap, const int64_t* ints, const double* vals,
+                          const int32_t* hull, uint8_t* out, int32_t* flags, int n, int h, int w,
+                          lf_stream_t stream);
+
 /* cv2.Canny(gray, low, high, L2gradient=l2gradient), aperture 3, for gray [N,H,W] uint8 of any size -> edges
  * [N,H,W] uint8 (0 / 255): Sobel with replicated borders, the magnitude |dx| + |dy| against floor(threshold) or,
  * with l2gradient, dx^2 + dy^2 against floor(min(32767, threshold)^2); low > high are swapped; 22.5 / 67.5 degree

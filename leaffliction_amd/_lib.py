@@ -72,6 +72,7 @@ SIGNATURES = {
     "lf_brown_spots_u8": [P, P, P, P, P, c_int, c_int, c_int, P, P, c_size_t, P],
     "lf_roi_u8": [P, P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "lf_shape_stats": [P, P, c_int, P, P, P, P, c_int, c_int, c_int, P],
+    "lf_analyze_overlay_u8": [P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, P],
     "lf_canny_workspace": [c_int, c_int, c_int],
     "lf_canny_u8": [P, P, c_int, c_int, c_int, c_double, c_double, c_int, P, c_size_t, P],
     "lf_blur_saliency_workspace": [c_int, c_int, c_int],

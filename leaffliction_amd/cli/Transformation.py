@@ -14,6 +14,13 @@ Not ported, each with one warning per run and no file: Analyze and Landmarks (Pl
 bilateral filtering, goodFeaturesToTrack) and the mosaic (cv2's Hershey text).  Hist is this project's own
 matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped.
 
+`--overlays` (a flag of this project) draws Analyze's picture: with Analyze among the types, `<stem>__T_Analyze.jpg` is
+apply_analyze_filter(masked, mask, contour) as process_single_image calls it: the contour, the centroid marker, the
+extreme points and their rays, the convex hull, the PCA axes and the Canny edges inside the mask, on the white
+composite (transform.analyze_filter_batch).  The lines follow the project's own integer drawing rules
+(include/leafhip.h), not cv2's pixels, and an image without a contour is written without the reference's
+"Analyze: no object" caption.  The Analyze warning is then not given; without the flag nothing changes.
+
 `--measure [FILE]` writes Analyze's numbers (not its picture) as one CSV table, a row per processed image in path
 order: shape, hull and axes from make_mask's contour (ops.shape_stats), the brown share and the Canny edge count
 inside the mask (transform.measure_leaves).  FILE defaults to measurements.csv in the output directory; in
@@ -134,6 +141,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--skip-existing", action="store_true", help="Skip images whose outputs already exist")
     p.add_argument("--overwrite", action="store_true", help="Overwrite existing outputs")
     p.add_argument("--preview", action="store_true", help="Force saving outputs (no GUI popups)")
+    p.add_argument("--overlays", action="store_true",
+                   help="Draw Analyze's picture (<stem>__T_Analyze.jpg) by this project's own drawing rules")
     p.add_argument("--measure", nargs="?", const="", default=None, metavar="FILE",
                    help="Write leaf measurements (shape, hull, axes, brown share, edge count) of every processed "
                         "image as CSV (default FILE: measurements.csv in the output directory)")
@@ -228,12 +237,14 @@ def encode_jpeg_batch(x) -> List[bytes]:
     return out
 
 
-def transform_batch(x, types: Sequence[str], cfg, measure: bool = False) -> Dict[str, object]:
+def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlays: bool = False) -> Dict[str, object]:
     """process_single_image's data flow for a same-size batch [N,H,W,3] uint8 on the device.  Returns the device
     outputs of the requested ported types ("Mask", "Blur", "ROI", "Brown": [N,H,W,3] uint8), "brown_stats"
     (percentages, counts, areas) with Brown, and "hist" (counts, histograms as numpy) with Hist.  measure: also
     "measure", transform.measure_leaves' columns, from the one make_mask result, its white composite and Brown's stats
-    when Brown ran; no other output changes."""
+    when Brown ran; no other output changes.  overlays: with Analyze among the types also "Analyze" [N,H,W,3] uint8,
+    analyze_filter_batch on `masked` with the mask made from the original; ops.shape_stats runs once for the picture and
+    the table."""
     import torch
 
     from .. import ops
@@ -258,6 +269,10 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False) -> Dict
         if "ROI" in types:
             _canvas, vis, _bb = F.roi_filter_batch(masked, contour, counts, cfg)
             res["ROI"] = vis
+        analyze = overlays and "Analyze" in types
+        shape = ops.shape_stats(contour, counts, int(x.shape[1]), int(x.shape[2])) if measure or analyze else None
+        if analyze:
+            res["Analyze"] = F.analyze_filter_batch(masked, (mask, contour, counts), cfg, shape=shape)
         if "Brown" in types:
             out, stats = ops.brown_spots_u8(
                 masked, mask, brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
@@ -269,7 +284,7 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False) -> Dict
             res["brown_stats"] = [(int(c), a / max(lf, 1) * 100, int(a)) for c, a, lf in st.tolist()]
         if measure:
             res["measure"] = F.measure_leaves(x, cfg, masks=(mask, contour, counts, _fb), brown_stats=stats,
-                                              masked=white)[0]
+                                              masked=white, shape=shape)[0]
     if "Hist" in types:
         counts_h, hist_h = ops.hsv_region_stats(masked.contiguous())
         res["hist"] = (counts_h.cpu().numpy(), hist_h.cpu().numpy())
@@ -278,14 +293,14 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False) -> Dict
 
 class _Runner:
     def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor,
-                 measure: bool = False):
+                 measure: bool = False, overlays: bool = False):
         self.types, self.cfg, self.pool = types, cfg, pool
-        self.measure = measure
+        self.measure, self.overlays = measure, overlays
         self.rows: Dict[Path, List[str]] = {}   # --measure: image path -> CSV cells after `file`
         self.skip_existing, self.overwrite = skip_existing, overwrite
         self.hist = "Hist" in types and _have_matplotlib()
         for t in NOT_PORTED:   # one warning per run
-            if t in types:
+            if t in types and not (overlays and t == "Analyze"):
                 logging.warning("%s is not ported to the GPU (PlantCV shape analysis / landmarks): no %s output is "
                                 "written", t, t)
         if "Hist" in types and not self.hist:
@@ -311,13 +326,13 @@ class _Runner:
         for c0 in range(0, len(items), CHUNK):
             chunk = items[c0:c0 + CHUNK]
             x = torch.from_numpy(np.stack([a for _p, _d, a in chunk])).to(dev)
-            res = transform_batch(x, self.types, self.cfg, measure)
+            res = transform_batch(x, self.types, self.cfg, measure, self.overlays)
             if measure:
                 from ..transform.filters import measure_row
                 for i, (p, _d, _a) in enumerate(chunk):
                     self.rows[p] = measure_row(res["measure"], i)
             names = [output_names(p.stem) for p, _d, _a in chunk]
-            for t in ("Mask", "Blur", "ROI", "Brown"):   # process_single_image's order
+            for t in ("Mask", "Blur", "ROI", "Analyze", "Brown"):   # process_single_image's order
                 if t not in res:
                     continue
                 outs = [d / nm[t] for (_p, d, _a), nm in zip(chunk, names)]
@@ -422,7 +437,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         out_d = Path(args.out_dir) if args.out_dir else default_out_dir(ip)
         out_d.mkdir(parents=True, exist_ok=True)
         with ThreadPoolExecutor(_workers(args.workers)) as pool:
-            runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None)
+            runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
+                             args.overlays)
             saved = runner.run([(ip, out_d)])
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else out_d / "measurements.csv", [(ip, out_d)],
@@ -447,7 +463,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         logging.info("Using %d host threads", n_threads)
         jobs = [(p, dst) for p in imgs]
         with ThreadPoolExecutor(n_threads) as pool:
-            runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None)
+            runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
+                             args.overlays)
             saved = runner.run(jobs)
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else dst / "measurements.csv", jobs, runner.rows,
@@ -501,15 +518,19 @@ class TransformFunction:
     Analyze, Landmarks, Hist, Brown; each that produces an image replaces the result, so the last one wins whatever
     the order of the names.  The mask is made once, on the original.  An image without a contour keeps what it had
     before ROI.  Analyze, Landmarks and Hist produce no image here and are skipped with one warning per object (the
-    reference would feed their picture when it is the last produced).  The augmentation draws come from Python's
-    global `random`, under a lock, image by image in batch order, so that after random.seed(k) a batch equals
+    reference would feed their picture when it is the last produced).  With overlays=True Analyze does produce its
+    picture (transform.analyze_filter_batch on the original image and its mask, at its place after ROI and before
+    Brown); an image without a contour then gets the original image, the reference's picture without its caption.
+    The augmentation draws come from Python's global `random`, under a lock, image by image in batch order, so that after random.seed(k) a batch equals
     sequential calls.  A file the filters reject or any stage error logs the reference's error line and takes its
     fallback (Pillow NEAREST resize of the file, no augmentation); an unreadable file gives the black pair.  The
     LEAF_SAVE_TRANSFORMS* preview dumps of the reference are presentation and are not reproduced; apply_brown_filter's
     per-image log line is not written either."""
 
-    def __init__(self, cfg, transform_types: Optional[Sequence[str]], apply_augmentation: bool, workers: int = 0):
+    def __init__(self, cfg, transform_types: Optional[Sequence[str]], apply_augmentation: bool, workers: int = 0,
+                 overlays: bool = False):
         self.cfg = cfg
+        self.overlays = bool(overlays)
         self.transform_types = transform_types
         self.apply_augmentation = bool(apply_augmentation)
         self.workers = workers
@@ -529,13 +550,14 @@ class TransformFunction:
                 log.info("Duplicate transform '%s' ignored for %s", name, where)
             else:
                 result.append(name)
-        skipped = [t for t in TRAIN_NOT_PRODUCED if t in result]
+        skipped = [t for t in TRAIN_NOT_PRODUCED if t in result and not (self.overlays and t == "Analyze")]
         if skipped:
             with self._lock:
                 first, self._warned = not self._warned, True
             if first:
-                log.warning("%s produce no image in the training transform (Analyze and Landmarks are not ported, "
-                            "Hist is a figure) and are skipped", ", ".join(skipped))
+                log.warning("%s produce no image in the training transform (%s not ported, Hist is a figure) and are "
+                            "skipped", ", ".join(skipped),
+                            "Landmarks is" if self.overlays else "Analyze and Landmarks are")
         return tuple(result)
 
     # ---------------------------------------------------------------- stages of one same-size group
@@ -567,6 +589,8 @@ class TransformFunction:
             mask, contour, counts = masks
             _canvas, vis, _bb, found = ops.roi_u8(x, contour, counts, tuple(cfg.roi_size))
             res = torch.where((found != 0).view(-1, 1, 1, 1), vis, res)
+        if self.overlays and "Analyze" in types:   # an image without a contour gets the original, without the caption
+            res = F.analyze_filter_batch(x, masks, cfg)
         if "Brown" in types:
             res, _stats = ops.brown_spots_u8(
                 x, masks[0], brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
@@ -732,14 +756,15 @@ class TransformFunction:
 
 
 def create_transform_function(config_path: Optional[str] = None, transform_types: Optional[Tuple[str, ...]] = None,
-                              apply_augmentation: bool = True) -> TransformFunction:
+                              apply_augmentation: bool = True, overlays: bool = False) -> TransformFunction:
     """The reference's create_transform_function (srcs/cli/Transformation.py:1008-1053): a `transform=` hook for
     ManifestSequence that feeds leaf-masked, saliency, ROI-boxed or brown-spot images, here a TransformFunction
     (callable per image, `.batch` for a device batch).  config_path: a YAML file with the reference's keys; None =
-    the values of its config.yaml.  transform_types: names or aliases, None = all seven."""
+    the values of its config.yaml.  transform_types: names or aliases, None = all seven.  overlays (a switch of this
+    project): Analyze feeds its picture instead of being skipped."""
     from ..transform.filters import TransformConfig, load_config
     cfg = load_config(Path(config_path)) if config_path else TransformConfig()
-    return TransformFunction(cfg, transform_types, apply_augmentation)
+    return TransformFunction(cfg, transform_types, apply_augmentation, overlays=overlays)
 
 
 if __name__ == "__main__":

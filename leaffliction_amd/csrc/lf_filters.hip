@@ -2672,3 +2672,204 @@ int lf_shape_stats(const int32_t* contour, const int32_t* counts, int cap, int64
 
 }  // extern "C"
 
+
+// ===========================================================================
+// lf_analyze_overlay_u8: the picture srcs/transform/filters/analyze.py returns, drawn from make_mask's contour,
+// lf_shape_stats' records and the Canny edges by the project's own integer drawing rules (include/leafhip.h,
+// "Drawing rules"; tests/draw_ref.py is the same reading in numpy).  Three launches on one stream: a copy of the
+// input, one workgroup per image for the primitives, a pass over the pixels for the cyan edges.
+//  * A segment's pixels: the walk goes along the major axis over [min - 1, max + 1] (the caps of a thick segment
+//    reach one pixel past its ends), and at each step tests the five pixels centre - 2 .. centre + 2 across it,
+//    centre = floor of the line there.  A pixel within distance 1 of a line whose slope is at most 1 lies within
+//    sqrt(2) of it across the minor axis, so within floor - 1 .. floor + 2; the exact integer tests of the rules
+//    decide.  A (step, pixel) pair belongs to one thread, so a segment blends each pixel it touches exactly once.
+//  * Order: overwrites of one colour may race (every writer stores the same bytes); everything else is separated
+//    by a barrier: the contour | the marker | disc, ray, four times | the hull's segments one after another | the
+//    two axes one after the other.  __syncthreads orders the workgroup's stores to `out` before its later loads.
+//  * Safety: the contour is validated as lf_roi_u8 validates it (a bad one leaves the copy untouched); the records
+//    are not trusted: coordinates are clamped to +-16384 (which also keeps c^2 below 2^62), the hull count to its
+//    capacity, the axis indices into [0, m); a pixel is stored only after the test against the image's bounds.
+//  * Cost: the hull's anti-aliased segments (about 40 of about 20 pixels on a 256 x 256 leaf) run one after another
+//    with 256 threads on each, most of them idle.
+// ===========================================================================
+namespace {
+
+constexpr int kDrawT = 256;
+constexpr int kDrawClamp = 16384;
+constexpr unsigned kRed = 0x0000ffu, kYellow = 0x00ffffu, kGreen = 0x00ff00u, kMagenta = 0xff00ffu;   // r | g << 8 | b << 16
+
+__device__ __forceinline__ int draw_coord(long long v) {
+    return (int)(v < -kDrawClamp ? -kDrawClamp : (v > kDrawClamp - 1 ? kDrawClamp - 1 : v));
+}
+__device__ __forceinline__ int draw_coord(double v) {   // truncated; NaN goes to the lower bound
+    return v >= (double)-kDrawClamp ? (v <= (double)(kDrawClamp - 1) ? (int)v : kDrawClamp - 1) : -kDrawClamp;
+}
+
+__device__ __forceinline__ long long floor_div(long long a, long long b) {
+    const long long q = a / b;
+    return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
+}
+
+// Calls px(x, y, u, c, L2) for every pixel of the h x w image that can lie within distance 1 of the segment
+// A -> B (see above), major steps t0, t0 + stride, ...: u = (p - A) . d, c = (p - A) x d, L2 = |d|^2.
+template <class F>
+__device__ __forceinline__ void seg_walk(int ax, int ay, int bx, int by, int h, int w, int t0, int stride, F&& px) {
+    const long long dx = bx - ax, dy = by - ay, L2 = dx * dx + dy * dy;
+    const bool xm = (dx < 0 ? -dx : dx) >= (dy < 0 ? -dy : dy);
+    const int a0 = xm ? ax : ay, b0 = xm ? bx : by, a1 = xm ? ay : ax;
+    const long long d0 = xm ? dx : dy, d1 = xm ? dy : dx;
+    const int n0 = xm ? w : h, n1 = xm ? h : w;
+    const int lo = max(min(a0, b0) - 1, 0), hi = min(max(a0, b0) + 1, n0 - 1);
+    for (int s = lo + t0; s <= hi; s += stride) {
+        const int mid = a1 + (d0 ? (int)floor_div((s - a0) * d1, d0) : 0);
+        for (int q = max(mid - 2, 0); q <= min(mid + 2, n1 - 1); ++q) {
+            const int x = xm ? s : q, y = xm ? q : s;
+            const long long rx = x - ax, ry = y - ay;
+            px(x, y, rx * dx + ry * dy, rx * dy - ry * dx, L2);
+        }
+    }
+}
+
+__device__ __forceinline__ void put_px(uint8_t* img, int w, int x, int y, unsigned k) {
+    uint8_t* o = img + ((size_t)y * w + x) * 3;
+    o[0] = (uint8_t)k;
+    o[1] = (uint8_t)(k >> 8);
+    o[2] = (uint8_t)(k >> 16);
+}
+
+// thickness 2: every pixel within distance 1 of the segment
+__device__ __forceinline__ void draw_thick(uint8_t* img, int h, int w, int ax, int ay, int bx, int by, unsigned k,
+                                           int t0, int stride) {
+    seg_walk(ax, ay, bx, by, h, w, t0, stride, [&](int x, int y, long long u, long long c, long long L2) {
+        const long long ex = u <= 0 ? x - ax : x - bx, ey = u <= 0 ? y - ay : y - by;
+        if ((u <= 0 || u >= L2) ? ex * ex + ey * ey <= 1 : c * c <= L2) put_px(img, w, x, y, k);
+    });
+}
+
+// thickness 1, anti-aliased: 0 <= u <= L2 and c^2 < L2, blended with a = 256 - isqrt(65536 c^2 / L2)
+__device__ __forceinline__ void draw_aa(uint8_t* img, int h, int w, int ax, int ay, int bx, int by, unsigned k,
+                                        int t0, int stride) {
+    seg_walk(ax, ay, bx, by, h, w, t0, stride, [&](int x, int y, long long u, long long c, long long L2) {
+        const long long c2 = c * c;
+        if (L2 == 0 ? (x != ax || y != ay) : (u < 0 || u > L2 || c2 >= L2)) return;
+        int s = 0;
+        if (L2) {
+            const int v = (int)((65536 * c2) / L2);   // below 65536
+            s = (int)sqrtf((float)v);
+            while (s * s > v) --s;
+            while ((s + 1) * (s + 1) <= v) ++s;
+        }
+        const int a = 256 - s;
+        uint8_t* o = img + ((size_t)y * w + x) * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            o[ch] = (uint8_t)((a * (int)((k >> (8 * ch)) & 255u) + (256 - a) * (int)o[ch] + 128) >> 8);
+    });
+}
+
+__global__ __launch_bounds__(kDrawT) void analyze_draw_kernel(const int* __restrict__ contour,
+                                                              const int* __restrict__ counts, int cap,
+                                                              const long long* __restrict__ ints,
+                                                              const double* __restrict__ vals,
+                                                              const int* __restrict__ hull, int h, int w,
+                                                              uint8_t* out, int* __restrict__ flags) {
+    __shared__ ContourBox B;
+    const size_t n = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int* pts = contour + n * (size_t)cap * 2;
+    const int m = contour_bbox<kDrawT>(B, pts, counts[n], cap, h, w);
+    const bool found = m > 0 && !B.bad;
+    if (tid == 0) flags[n] = found ? kRoiFound : (B.bad ? kRoiBad : 0);
+    if (!found) return;
+    uint8_t* img = out + n * (size_t)h * w * 3;
+    const long long* rec = ints + n * kShapeInts;
+    const int hcap = 2 * min(h, w);
+    const int* hv = hull + n * (size_t)hcap * 2;
+
+    // 1: the contour, a closed polyline of thick segments, a segment per thread
+    for (int i = tid; i < m; i += kDrawT) {
+        const int j = i + 1 < m ? i + 1 : 0;
+        draw_thick(img, h, w, pts[2 * i], pts[2 * i + 1], pts[2 * j], pts[2 * j + 1], kRed, 0, 1);
+    }
+    __syncthreads();
+    // 2: the centroid marker
+    const int cx = draw_coord(vals[n * kShapeVals + 2]), cy = draw_coord(vals[n * kShapeVals + 3]);
+    draw_thick(img, h, w, cx - 7, cy, cx + 7, cy, kYellow, tid, kDrawT);
+    draw_thick(img, h, w, cx, cy - 7, cx, cy + 7, kYellow, tid, kDrawT);
+    __syncthreads();
+    // 3: left, right, top, bottom: the disc, then the ray from the centroid
+    for (int e = 0; e < 4; ++e) {
+        const int qx = draw_coord(rec[8 + 2 * e]), qy = draw_coord(rec[9 + 2 * e]);
+        if (tid < 49) {
+            const int ox = tid % 7 - 3, oy = tid / 7 - 3, x = qx + ox, y = qy + oy;
+            if (ox * ox + oy * oy <= 12 && x >= 0 && x < w && y >= 0 && y < h) put_px(img, w, x, y, kYellow);
+        }
+        __syncthreads();
+        draw_aa(img, h, w, cx, cy, qx, qy, kYellow, tid, kDrawT);
+        __syncthreads();
+    }
+    // 4: the hull, a closed anti-aliased polyline, one segment after another
+    const int hn = (int)min(max(rec[22], 0ll), (long long)hcap);
+    for (int i = 0; i < hn; ++i) {
+        const int j = i + 1 < hn ? i + 1 : 0;
+        draw_aa(img, h, w, draw_coord((long long)hv[2 * i]), draw_coord((long long)hv[2 * i + 1]),
+                draw_coord((long long)hv[2 * j]), draw_coord((long long)hv[2 * j + 1]), kGreen, tid, kDrawT);
+        __syncthreads();
+    }
+    // 5: the axes
+    for (int e = 0; e < 2; ++e) {
+        const int i = (int)min(max(rec[25 + 2 * e], 0ll), (long long)m - 1);
+        const int j = (int)min(max(rec[26 + 2 * e], 0ll), (long long)m - 1);
+        draw_thick(img, h, w, pts[2 * i], pts[2 * i + 1], pts[2 * j], pts[2 * j + 1], e ? kMagenta : kYellow, tid, kDrawT);
+        __syncthreads();
+    }
+}
+
+// 6: the Canny edges inside the mask, in cyan, on the images that have a contour
+__global__ __launch_bounds__(kBlock) void analyze_edges_kernel(const uint8_t* __restrict__ mask,
+                                                               const uint8_t* __restrict__ edges,
+                                                               const int* __restrict__ flags, int hw,
+                                                               uint8_t* __restrict__ out) {
+    const size_t n = blockIdx.y;
+    if (!(flags[n] & kRoiFound)) return;
+    const uint8_t *mk = mask + n * (size_t)hw, *ed = edges + n * (size_t)hw;
+    uint8_t* o = out + n * (size_t)hw * 3;
+    for (int p = blockIdx.x * kBlock + threadIdx.x; p < hw; p += gridDim.x * kBlock)
+        if (ed[p] && mk[p]) {
+            o[3 * (size_t)p] = 0;
+            o[3 * (size_t)p + 1] = 255;
+            o[3 * (size_t)p + 2] = 255;
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+int lf_analyze_overlay_u8(const uint8_t* rgb, const uint8_t* mask, const uint8_t* edges, const int32_t* contour,
+                          const int32_t* counts, int cap, const int64_t* ints, const double* vals,
+                          const int32_t* hull, uint8_t* out, int32_t* flags, int n, int h, int w,
+                          lf_stream_t stream) {
+    LF_REQUIRE(rgb && mask && edges && contour && counts && ints && vals && hull && out && flags,
+               "lf_analyze_overlay: null buffer");
+    LF_REQUIRE(n > 0 && h > 0 && w > 0 && cap > 0, "lf_analyze_overlay: bad dims n=%d %dx%d cap=%d", n, h, w, cap);
+    LF_REQUIRE(n <= 65535, "lf_analyze_overlay: batch too large for the grid");
+    LF_REQUIRE(h <= kShapeMaxDim && w <= kShapeMaxDim && cap <= kShapeMaxCap,
+               "lf_analyze_overlay: %d x %d with cap %d is over lf_shape_stats' limits (h, w <= %d, cap <= %d)", h, w,
+               cap, kShapeMaxDim, kShapeMaxCap);
+    const size_t bytes = (size_t)n * h * w * 3;
+    LF_REQUIRE(rgb + bytes <= out || out + bytes <= rgb, "lf_analyze_overlay: rgb and out overlap");
+    hipStream_t s = lf::as_stream(stream);
+    if (hipMemcpyAsync(out, rgb, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        lf::set_error("lf_analyze_overlay: the copy of the input failed");
+        return LF_ERR_LAUNCH;
+    }
+    analyze_draw_kernel<<<n, kDrawT, 0, s>>>(contour, counts, cap, reinterpret_cast<const long long*>(ints), vals,
+                                             hull, h, w, out, flags);
+    const int hw = h * w;
+    analyze_edges_kernel<<<dim3(std::min((hw + kBlock - 1) / kBlock, 64), n), kBlock, 0, s>>>(mask, edges, flags, hw,
+                                                                                              out);
+    return lf::check_launch("lf_analyze_overlay");
+}
+
+}  // extern "C"

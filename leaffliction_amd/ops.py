@@ -484,6 +484,46 @@ def shape_stats(contour: torch.Tensor, counts: torch.Tensor, h: int, w: int):
     return ints, vals, hull, (flags & 1).bool()
 
 
+def analyze_overlay_u8(x: torch.Tensor, mask: torch.Tensor, edges: torch.Tensor, contour: torch.Tensor,
+                       counts: torch.Tensor, ints: torch.Tensor, vals: torch.Tensor, hull: torch.Tensor,
+                       strict: bool = True, out: Optional[torch.Tensor] = None):
+    """apply_analyze_filter's picture (srcs/transform/filters/analyze.py) for a batch [N,H,W,3] uint8: the contour in
+    red, the centroid marker, the extreme points with their rays and the PCA major axis in yellow, the convex hull in
+    green, the minor axis in magenta, and the pixels with edges > 0 and mask > 0 in cyan.  mask, edges [N,H,W] uint8;
+    contour [N,K,2] / counts [N]: make_mask_u8's buffer; ints, vals, hull: shape_stats' for the same contours.
+    Returns (out [N,H,W,3] uint8, flags [N] int32: bit 0 the image has a contour, else its row of out is the input;
+    bit 2 a bad contour record, which raises unless strict is False).  out: a contiguous uint8 tensor of x's shape
+    that does not overlap x.  The drawing rules: include/leafhip.h (lf_analyze_overlay_u8)."""
+    n, h, w = _hwc(x, "analyze_overlay.x")
+    _chk(mask, _U8, "analyze_overlay.mask", 3)
+    _chk(edges, _U8, "analyze_overlay.edges", 3)
+    _chk(contour, _I32, "analyze_overlay.contour", 3)
+    _chk(counts, _I32, "analyze_overlay.counts", 1)
+    _chk(ints, torch.int64, "analyze_overlay.ints", 2)
+    _chk(vals, torch.float64, "analyze_overlay.vals", 2)
+    _chk(hull, _I32, "analyze_overlay.hull", 3)
+    want = {"mask": (mask, (n, h, w)), "edges": (edges, (n, h, w)), "counts": (counts, (n,)),
+            "ints": (ints, (n, 32)), "vals": (vals, (n, 16)), "hull": (hull, (n, 2 * min(h, w), 2))}
+    for name, (t, shape) in want.items():
+        if tuple(t.shape) != shape or t.device != x.device:
+            raise ValueError(f"analyze_overlay.{name}: expected {list(shape)} on {x.device}, got {list(t.shape)} on "
+                             f"{t.device}")
+    if contour.shape[0] != n or contour.shape[2] != 2 or contour.shape[1] < 1 or contour.device != x.device:
+        raise ValueError(f"analyze_overlay.contour: expected [{n},K,2] on {x.device}, got {list(contour.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif _chk(out, _U8, "analyze_overlay.out", 4).shape != x.shape or out.device != x.device:
+        raise ValueError(f"analyze_overlay.out: expected {list(x.shape)} on {x.device}, got {list(out.shape)}")
+    flags = torch.empty(n, dtype=_I32, device=x.device)
+    _lib.call("lf_analyze_overlay_u8", x.data_ptr(), mask.data_ptr(), edges.data_ptr(), contour.data_ptr(),
+              counts.data_ptr(), int(contour.shape[1]), ints.data_ptr(), vals.data_ptr(), hull.data_ptr(),
+              out.data_ptr(), flags.data_ptr(), n, h, w, _stream())
+    if strict and bool((flags & 4).any()):
+        raise _lib.LeafHipError("lf_analyze_overlay_u8: a contour count outside the buffer or a point outside the "
+                                "image")
+    return out, flags
+
+
 def canny_u8(gray: torch.Tensor, low: float, high: float, l2gradient: bool = True) -> torch.Tensor:
     """cv2.Canny(gray, low, high, L2gradient=l2gradient) for gray [N,H,W] uint8 of any size: edges [N,H,W] uint8
     (0 / 255).  The reading: include/leafhip.h (lf_canny_u8), the same as oracle/cv_ops.canny."""

@@ -7,7 +7,8 @@ extension and the resize back (lf_make_mask_u8).  The other strategies are not p
 (grabcut_refine, true in config.yaml) and shadow suppression are skipped with one warning per process: the
 reference keeps the candidate whenever a refinement scores lower, so the result is one of the outcomes the
 reference can produce.  `apply_brown_filter` (brown.py) and `apply_roi_filter` (roi.py) run on the GPU too
-(lf_brown_spots_u8, lf_roi_u8), one image at a time or batched on device tensors.  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
+(lf_brown_spots_u8, lf_roi_u8), one image at a time or batched on device tensors, and so does `apply_analyze_filter`
+(analyze.py), whose picture is drawn by the project's own integer rules (lf_analyze_overlay_u8).  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
 reproduced — the numbers it draws are."""
 from __future__ import annotations
 
@@ -258,6 +259,45 @@ def apply_roi_filter(rgb: np.ndarray, contour: Optional[np.ndarray], cfg):
     return canvas[0].cpu().numpy(), vis[0].cpu().numpy(), bboxes[0]
 
 
+def analyze_filter_batch(batch, masks, cfg, shape=None) -> torch.Tensor:
+    """apply_analyze_filter for a same-size batch [N,H,W,3] uint8 on the device.  masks: make_masks_device's tuple
+    (mask, contour, counts[, fallback]) for the images the contours belong to; shape: ops.shape_stats' result for these
+    contours when the caller has it.  The edges are Canny(gray(batch), 80, 160, L2) (analyze.py:115-121).  Returns the
+    pictures [N,H,W,3] uint8 on the device; an image without a contour keeps its input (the reference's
+    "Analyze: no object" caption is not drawn).  cfg is not read (analyze.py does not read it either)."""
+    x = _device_u8(batch, 4, "analyze_filter_batch.batch")
+    mask, contour, counts = masks[0], masks[1], masks[2]
+    if shape is None:
+        shape = ops.shape_stats(contour, counts, int(x.shape[1]), int(x.shape[2]))
+    edges = ops.canny_u8(ops.rgb2gray_u8(x), 80, 160, True)
+    return ops.analyze_overlay_u8(x, mask, edges, contour, counts, shape[0], shape[1], shape[2])[0]
+
+
+def apply_analyze_filter(rgb: np.ndarray, mask: Optional[np.ndarray], contour: Optional[np.ndarray], cfg) -> np.ndarray:
+    """srcs/transform/filters/analyze.py for one HxWx3 uint8 RGB image: the contour, the centroid marker, the extreme
+    points and their rays, the convex hull, the PCA axes and the Canny edges inside the mask, drawn on a copy of the
+    image.  A None mask or contour returns a copy of the image (the reference writes "Analyze: no object" on it with
+    cv2's font).  A 3-d mask is read through its first channel; the contour ([K,1,2] or [K,2] (x, y)) must lie inside
+    the image.  Parity unpinned (no cv2): the drawing rules are the project's own, include/leafhip.h."""
+    if mask is None or contour is None:
+        return np.array(rgb, copy=True)
+    pts = np.asarray(contour).reshape(-1, 2)
+    if pts.shape[0] == 0:
+        raise ValueError("apply_analyze_filter: empty contour")
+    m = np.asarray(mask)
+    leaf = (m > 0) if m.ndim == 2 else (m[..., 0] > 0)
+    x = _rgb_batch(rgb)
+    h, w = x.shape[1:3]
+    if leaf.shape != (h, w):
+        raise ValueError(f"apply_analyze_filter: mask {leaf.shape} does not match the image {(h, w)}")
+    if (pts[:, 0] < 0).any() or (pts[:, 0] >= w).any() or (pts[:, 1] < 0).any() or (pts[:, 1] >= h).any():
+        raise ValueError("apply_analyze_filter: contour points outside the image")
+    md = torch.from_numpy(np.ascontiguousarray(leaf.astype(np.uint8) * 255)).unsqueeze(0).to(x.device)
+    c = torch.from_numpy(np.ascontiguousarray(pts.astype(np.int32))).unsqueeze(0).to(x.device)
+    counts = torch.tensor([pts.shape[0]], dtype=torch.int32, device=x.device)
+    return analyze_filter_batch(x, (md, c, counts), cfg)[0].cpu().numpy()
+
+
 # One row of leaf measurements: the CSV columns of `Transformation --measure` after `file`.  Integer columns hold
 # int64, the others float64; SHAPE_COLUMNS are empty (NaN / 0 here, empty cells in the CSV) without a contour.
 MEASURE_COLUMNS = ("width", "height", "found", "fallback", "contour_points", "area", "perimeter", "centroid_x",
@@ -270,12 +310,12 @@ _MEASURE_FROM_SHAPE = {"contour_points": "npts", "centroid_x": "cx", "centroid_y
 SHAPE_COLUMNS = MEASURE_COLUMNS[4:32]
 
 
-def measure_leaves(batch, cfg, masks=None, brown_stats=None, masked=None):
+def measure_leaves(batch, cfg, masks=None, brown_stats=None, masked=None, shape=None):
     """The numbers behind srcs/transform/filters/analyze.py for a same-size batch [N,H,W,3] uint8 (numpy or a CUDA
     tensor), as data: (columns: {name: numpy [N]} for MEASURE_COLUMNS, hulls: per image int32 [k,2] (x, y),
     edges [N,H,W] uint8 0 / 255 on the device).  masks: make_masks_device's (mask, contour, counts[, fallback]) when
     the caller has them; masked: the white composite of (batch, mask), and brown_stats: ops.brown_spots_u8's stats of
-    (masked, mask), likewise.  Shape, hull and axes
+    (masked, mask), likewise; shape: ops.shape_stats' result for the contours, likewise.  Shape, hull and axes
     come from ops.shape_stats on the contour; mask_px = count(mask > 0); the brown numbers are apply_brown_filter's
     on the white composite; edges = Canny(gray(masked), 80, 160, L2) inside the mask (analyze.py:115-121), edge_px
     their count.  An image without a contour has found 0, NaN in its float shape columns and 0 in the integer ones."""
@@ -285,7 +325,7 @@ def measure_leaves(batch, cfg, masks=None, brown_stats=None, masked=None):
         masks = make_masks_device(x, cfg)
     mask, contour, counts = masks[0], masks[1], masks[2]
     fallback = masks[3] if len(masks) > 3 else torch.zeros(n, dtype=torch.bool, device=x.device)
-    ints, vals, hull, found = ops.shape_stats(contour, counts, h, w)
+    ints, vals, hull, found = shape if shape is not None else ops.shape_stats(contour, counts, h, w)
     leaf = mask > 0
     mask_px = leaf.sum(dim=(1, 2))
     if masked is None:
