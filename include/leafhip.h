@@ -321,6 +321,102 @@ size_t lf_canny_workspace(int n, int h, int w);
 int lf_canny_u8(const uint8_t* gray, uint8_t* edges, int n, int h, int w, double low, double high, int l2gradient,
                 void* workspace, size_t ws_bytes, lf_stream_t stream);
 
+/* The pixel stages of the pseudo-landmarks filter (srcs/transform/filters/landmarks.py: CLAHE, bilateralFilter,
+ * goodFeaturesToTrack) for a same-size batch of planes [N,H,W], h, w >= 8 (smaller images are rejected before the
+ * launch).  Parity unpinned (no cv2): these are the project's own rules, in integers throughout, restated in numpy by
+ * tests/landmarks_ref.py; `//` is the floor division of non-negative integers.
+ *
+ * lf_clahe_u8: createCLAHE(clipLimit 2.0, tileGridSize (8, 8)).apply(gray) -> out (uint8).
+ *   Wp, Hp = W, H rounded up to multiples of 8; the added columns / rows are the image reflected (reflect-101).
+ *   A tile is tw x th = Wp/8 x Hp/8 with area a; clip = max(1, (2 a) // 256).  Per tile, from its 256-bin histogram:
+ *   excess = sum max(h_i - clip, 0) and the bins are cut to clip; every bin gets excess // 256; with
+ *   r = excess % 256 > 0 and step = max(256 // r, 1) the bins 0, step, 2 step, ... get 1 more each while the index
+ *   is < 256 and units of r remain; lut[i] = min(255, (2 * 255 * cum_i + a) // (2 a)), cum the inclusive prefix sum.
+ *   Per pixel (x, y): fx = 2x + 1 - tw, tx = floor(fx / (2 tw)), ax = fx - 2 tw tx; the tiles tx and tx + 1, each
+ *   clamped to [0, 7], weigh 2 tw - ax and ax; the same in y;
+ *   out = (sum lut * wx * wy + 2 tw th) // (4 tw th) over the four tiles.  Hp * Wp <= 2^27.
+ *   Two launches: one workgroup per (image, tile), then a pixel pass.  workspace: the 64 LUTs of every image.
+ *
+ * lf_bilateral_u8: bilateralFilter(gray, d = 5, sigmaColor, sigmaSpace) with the weights as Q16 tables on the
+ *   DEVICE: wc [256] int32 by |v - centre|, ws [5] int32 by dx^2 + dy^2, each in [0, 65536].  The taps are the 21
+ *   offsets with dx^2 + dy^2 <= 4, reflect-101 borders; a tap weighs w = (ws[dx^2 + dy^2] * wc[|v - centre|] + 2^15)
+ *   >> 16; out = (2 sum w v + sum w) // (2 sum w), the centre value when sum w is 0.  The caller makes the tables
+ *   (ops.bilateral_tables: rint(65536 exp(-k^2 / (2 sigma^2))) in float64), so no device exp enters the result.
+ *   gray and out must differ.
+ *
+ * lf_corner_score_u8: cornerMinEigenVal(blockSize 3, ksize 3) in integers -> score int32.  dx, dy = the 3 x 3 Sobel
+ *   with reflect-101 borders; A = sum dx^2, B = sum dx dy, C = sum dy^2 over the 3 x 3 block, the dx / dy planes
+ *   continued by reflect-101 again; S = A + C - isqrt((A - C)^2 + 4 B^2), isqrt the exact floor of the root (the
+ *   radicand is below 2^49).  0 <= S < 2^25.
+ *
+ * lf_good_features: goodFeaturesToTrack's selection on a score plane (int32, values in [0, 2^31)) under a mask
+ *   (uint8, > 0 = inside) -> points [N,max_points,2] int32 (x, y), rows past the count zero, counts [N].
+ *   Smax = the largest score where mask > 0; Smax = 0 gives no points.  A pixel is live when q_den S > q_num Smax.
+ *   A candidate is a live pixel with mask > 0, not on the outermost rows or columns, whose S is >= every live
+ *   8-neighbour's S.  Candidates are ordered by S descending, then (y, x) ascending; going down that order one is
+ *   taken unless a taken one lies within dx^2 + dy^2 < min_dist^2; selection stops at max_points.  One workgroup per
+ *   image: the candidates are compacted to a key list, then at most max_points rounds of arg-max with suppression.
+ *   q_num >= 0, q_den > 0, 0 <= min_dist <= 16384, 1 <= max_points <= 2^20.  Two launches give the same bits. */
+size_t lf_clahe_workspace(int n, int h, int w);
+int lf_clahe_u8(const uint8_t* gray, uint8_t* out, int n, int h, int w, void* workspace, size_t ws_bytes,
+                lf_stream_t stream);
+int lf_bilateral_u8(const uint8_t* gray, const int32_t* wc, const int32_t* ws, uint8_t* out, int n, int h, int w,
+                    lf_stream_t stream);
+int lf_corner_score_u8(const uint8_t* gray, int32_t* score, int n, int h, int w, lf_stream_t stream);
+size_t lf_good_features_workspace(int n, int h, int w);
+int lf_good_features(const int32_t* score, const uint8_t* mask, int32_t* points, int32_t* counts, int n, int h, int w,
+                     int q_num, int q_den, int min_dist, int max_points, void* workspace, size_t ws_bytes,
+                     lf_stream_t stream);
+
+/* apply_landmarks_filter (srcs/transform/filters/landmarks.py) for a same-size batch: rgb [N,H,W,3], the mask
+ * [N,H,W], contour [N,cap,2] and counts [N] that lf_make_mask_u8 gave for these images, the brown numbers of the
+ * config (lf_brown_params: predicate, brown_morph_kernel, brown_min_area_px), landmarks_count and the two Q16 tables
+ * of lf_bilateral_u8 (device) -> out [N,H,W,3] (must not overlap rgb); points [N,pcap,3] int32 (kind, x, y), kind
+ * 0 border, 1 vein, 2 disease, in placement order, rows past the counts zero; pcounts [N,3] per kind; flags [N] as
+ * lf_roi_u8: bit 0 the image has a contour (else out is the input and there are no points; the reference's
+ * "Landmarks: no object" caption needs cv2's font and is not drawn), bit 2 a count outside [0, cap], a point outside
+ * the image, a step bound that was hit or an enhanced contour of more than 8 (H + W) points (an error: out is the
+ * input, the counts are zero).
+ * Quotas: total = max(1, landmarks_count), bq = vq = max(1, total // 3), dq = max(1, total - bq - vq),
+ * pcap = bq + vq + 5 dq = lf_landmarks_points_cap(landmarks_count).
+ * A sequence of launches on one stream: gray, lf_clahe_u8, the saliency filter's Sobel pass, two lf_canny_u8, lf_bilateral_u8,
+ * two lf_corner_score_u8 on workspace planes, then one workgroup per image with four bit planes in LDS (make_mask's
+ * limit, 140 KiB: larger images are rejected before any launch).  h, w >= 8.  Two launches give the same bits.
+ *
+ * Landmark rules, for an image with a contour C and leaf M = mask > 0.  Parity unpinned (no cv2): the project's own
+ * rules, restated in numpy by tests/landmarks_ref.py.
+ *   1 Enhanced mask: E = close5((M) | close5(brown_px & M)), the 5 x 5 MORPH_ELLIPSE element, pixels outside the
+ *     image never win.  C' = the largest external contour of E (make_mask's reading: Suzuki-Abe, CHAIN_APPROX_SIMPLE,
+ *     equal areas: the last discovered); E empty: C' = C.
+ *   2 Border: bq points resample the closed polygon C' as the reference's resample_contour reads, in float64:
+ *     segment lengths sqrt((double)(dx^2 + dy^2)), the closing segment included; cumulative lengths summed in index
+ *     order; targets t_i = i * (total / bq); the segment pointer j advances while cum[j + 1] < t;
+ *     a = (t - cum[j]) / (cum[j + 1] - cum[j]), 0 for a zero-length segment; the point is
+ *     (1 - a) P_j + a P_{j+1}, truncated.  total = 0 gives the single point P_0.
+ *   3 Vein: q = CLAHE(gray(rgb)); e1 = Canny(q, 30, 90, L2); e2 = Canny(bilateral(q), 50, 130, L2); e3 = the Sobel
+ *     magnitude of q (float32, reflect-101) min-max normalised to 0 .. 255, truncated to uint8, > 40 (the saliency
+ *     filter's reading); edges = (e1 | e2 | e3) & erode3(E); D = dilate3(edges) (the 3 x 3 ellipse is the cross).
+ *     Points: lf_good_features(lf_corner_score(q), D, 2 / 1000, min_dist 2, max_points vq).  Fewer than vq: with cnt
+ *     the set pixels of D in raster order and need = vq - placed, the pixels of rank (i (cnt - 1)) // (need - 1),
+ *     i = 0 .. need - 1 (rank 0 when need = 1) follow; none when cnt = 0.
+ *   4 Disease: brown_px & E, opened then closed with the brown_morph_kernel ellipse; its 8-connected components of
+ *     area >= brown_min_area_px, by area descending, ties in raster order of their first pixel;
+ *     quota = min(max(ncomp, total_area // 50), 5 dq).  Walking the components while placed < quota:
+ *     k = max(1, min(area // 40, quota - placed)); its points are lf_good_features(lf_corner_score(gray(rgb)), the
+ *     component, 5 / 1000, min_dist 3, max_points k), taken one by one, each counting, until placed >= dq; a
+ *     component that yields none gets its centroid (sum x // area, sum y // area).
+ *   5 Picture, on a copy of rgb, in this order: the border points as discs of radius 2 in (255, 0, 0); C' closed as
+ *     anti-aliased segments in (0, 255, 0), in contour order; the vein points as discs of radius 2 in (0, 0, 255);
+ *     the disease points as discs of radius 4 in (139, 69, 19).  A disc of radius r is |p - q|^2 <= r^2 + r, an
+ *     overwrite (the radius-3 disc of the drawing rules above is the same rule); the anti-aliased segment is that of
+ *     the drawing rules above.  Only the image border clips. */
+int lf_landmarks_points_cap(int landmarks_count);
+size_t lf_landmarks_workspace(int n, int h, int w, int landmarks_count);
+int lf_landmarks_u8(const uint8_t* rgb, const uint8_t* mask, const int32_t* contour, const int32_t* counts, int cap,
+                    const lf_brown_params* params, int landmarks_count, const int32_t* wc, const int32_t* ws,
+                    uint8_t* out, int32_t* points, int32_t* pcounts, int32_t* flags, int n, int h, int w,
+                    void* workspace, size_t ws_bytes, lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* JPEG encode (the file Pillow's Image.save(path, quality=q) writes)          */
 /* ------------------------------------------------------------------------- */

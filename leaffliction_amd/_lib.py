@@ -75,6 +75,15 @@ SIGNATURES = {
     "lf_analyze_overlay_u8": [P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, P],
     "lf_canny_workspace": [c_int, c_int, c_int],
     "lf_canny_u8": [P, P, c_int, c_int, c_int, c_double, c_double, c_int, P, c_size_t, P],
+    "lf_clahe_workspace": [c_int, c_int, c_int],
+    "lf_clahe_u8": [P, P, c_int, c_int, c_int, P, c_size_t, P],
+    "lf_bilateral_u8": [P, P, P, P, c_int, c_int, c_int, P],
+    "lf_corner_score_u8": [P, P, c_int, c_int, c_int, P],
+    "lf_good_features_workspace": [c_int, c_int, c_int],
+    "lf_good_features": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P],
+    "lf_landmarks_points_cap": [c_int],
+    "lf_landmarks_workspace": [c_int, c_int, c_int, c_int],
+    "lf_landmarks_u8": [P, P, P, P, c_int, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, P, c_size_t, P],
     "lf_blur_saliency_workspace": [c_int, c_int, c_int],
     "lf_blur_saliency_u8": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P,
                             c_size_t, P],
@@ -160,7 +169,9 @@ SIGNATURES = {
 _RESTYPES = {"lf_last_error": C.c_char_p, "lf_conv2d_wgrad_workspace": c_size_t,
              "lf_bn_workspace": c_size_t, "lf_se_bwd_workspace": c_size_t,
              "lf_adamw_workspace": c_size_t, "lf_conv2d_stats_tiles": C.c_longlong,
-             "lf_blur_saliency_workspace": c_size_t, "lf_inclusive_mask_workspace": c_size_t, "lf_make_mask_workspace": c_size_t, "lf_brown_spots_workspace": c_size_t, "lf_canny_workspace": c_size_t, "lf_conv2d_bf16_weight_elems": c_size_t,
+             "lf_blur_saliency_workspace": c_size_t, "lf_inclusive_mask_workspace": c_size_t, "lf_make_mask_workspace": c_size_t, "lf_brown_spots_workspace": c_size_t, "lf_canny_workspace": c_size_t, "lf_clahe_workspace": c_size_t,
+             "lf_good_features_workspace": c_size_t, "lf_landmarks_workspace": c_size_t,
+             "lf_conv2d_bf16_weight_elems": c_size_t,
              "lf_conv2d_bf16_act_mean_workspace": c_size_t,
              "lf_conv2d_bf16_stats_tiles": C.c_longlong, "lf_conv2d_wgrad_bf16_workspace": c_size_t,
              "lf_jpeg_file_bound": c_size_t, "lf_jpeg_scan_aux_offset": c_size_t, "lf_jpeg_scan_aux_offset_ragged": c_size_t, "lf_jpeg_decode_items_workspace": c_size_t, "lf_jpeg_entropy_workspace": c_size_t, "lf_jpeg_wrap_scan": C.c_long, "lf_jpeg_fdct_groups": C.c_long, "lf_jpeg_decode_workspace": c_size_t, "lf_jpeg_write_file": C.c_long, "lf_jpeg_quant_tables": None}

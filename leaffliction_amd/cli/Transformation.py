@@ -10,8 +10,8 @@ make_mask a second time, on `masked`; ROI = the box drawn on `masked` (or `maske
 
 Images are decoded on host threads (Pillow, EXIF transpose, RGB), grouped by size, and every stage runs as one
 batched launch over chunks of bounded size; outputs are encoded on the GPU (quality 95, the balancer's encoder).
-Not ported, each with one warning per run and no file: Analyze and Landmarks (PlantCV shape analysis, CLAHE /
-bilateral filtering, goodFeaturesToTrack) and the mosaic (cv2's Hershey text).  Hist is this project's own
+Without their switches (below), each with one warning per run and no file: Analyze and Landmarks (PlantCV shape
+analysis, CLAHE / bilateral filtering, goodFeaturesToTrack); not ported: the mosaic (cv2's Hershey text).  Hist is this project's own
 matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped.
 
 `--overlays` (a flag of this project) draws Analyze's picture: with Analyze among the types, `<stem>__T_Analyze.jpg` is
@@ -20,6 +20,14 @@ extreme points and their rays, the convex hull, the PCA axes and the Canny edges
 composite (transform.analyze_filter_batch).  The lines follow the project's own integer drawing rules
 (include/leafhip.h), not cv2's pixels, and an image without a contour is written without the reference's
 "Analyze: no object" caption.  The Analyze warning is then not given; without the flag nothing changes.
+
+`--landmarks` (a flag of this project) runs the pseudo-landmarks filter: with Landmarks among the types,
+`<stem>__T_Landmarks.jpg` is apply_landmarks_filter(masked, contour, cfg, make_mask) as process_single_image calls it:
+border, vein and disease points and the enhanced contour on the white composite, with a mask made from that composite
+(transform.landmarks_filter_batch), and the reference's "Landmarks summary" line per image.  CLAHE, the bilateral
+filter, the corner score and the point selection follow the project's own integer rules (include/leafhip.h), not
+cv2's pixels, and an image without a contour is written without the "Landmarks: no object" caption.  The Landmarks
+warning is then not given; without the flag nothing changes.
 
 `--measure [FILE]` writes Analyze's numbers (not its picture) as one CSV table, a row per processed image in path
 order: shape, hull and axes from make_mask's contour (ops.shape_stats), the brown share and the Canny edge count
@@ -143,6 +151,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--preview", action="store_true", help="Force saving outputs (no GUI popups)")
     p.add_argument("--overlays", action="store_true",
                    help="Draw Analyze's picture (<stem>__T_Analyze.jpg) by this project's own drawing rules")
+    p.add_argument("--landmarks", action="store_true",
+                   help="Run the pseudo-landmarks filter (<stem>__T_Landmarks.jpg) by this project's own integer rules")
     p.add_argument("--measure", nargs="?", const="", default=None, metavar="FILE",
                    help="Write leaf measurements (shape, hull, axes, brown share, edge count) of every processed "
                         "image as CSV (default FILE: measurements.csv in the output directory)")
@@ -237,14 +247,17 @@ def encode_jpeg_batch(x) -> List[bytes]:
     return out
 
 
-def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlays: bool = False) -> Dict[str, object]:
+def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlays: bool = False,
+                    landmarks: bool = False) -> Dict[str, object]:
     """process_single_image's data flow for a same-size batch [N,H,W,3] uint8 on the device.  Returns the device
     outputs of the requested ported types ("Mask", "Blur", "ROI", "Brown": [N,H,W,3] uint8), "brown_stats"
     (percentages, counts, areas) with Brown, and "hist" (counts, histograms as numpy) with Hist.  measure: also
     "measure", transform.measure_leaves' columns, from the one make_mask result, its white composite and Brown's stats
     when Brown ran; no other output changes.  overlays: with Analyze among the types also "Analyze" [N,H,W,3] uint8,
     analyze_filter_batch on `masked` with the mask made from the original; ops.shape_stats runs once for the picture and
-    the table."""
+    the table.  landmarks: with Landmarks among the types also "Landmarks" [N,H,W,3] uint8, landmarks_filter_batch on
+    `masked` with the original's contour and the mask made from `masked` (the one Blur makes, made once), and
+    "landmark_counts", per image (border, vein, disease)."""
     import torch
 
     from .. import ops
@@ -260,8 +273,10 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
             masked = white
         if "Mask" in types:
             res["Mask"] = ops.mask_composite_u8(x, mask, "black")
-        if "Blur" in types:   # apply_blur_filter(masked, cfg, make_mask): make_mask again, on `masked`
+        marks = landmarks and "Landmarks" in types
+        if "Blur" in types or marks:   # apply_blur_filter / apply_landmarks_filter(masked, ...): make_mask again, on `masked`
             mask2 = F.make_masks_device(masked, cfg)[0]
+        if "Blur" in types:
             leaf = torch.where(mask2 > 0, 255, 0).to(torch.uint8)
             res["Blur"] = ops.blur_saliency_u8(
                 masked, leaf, gaussian_sigma=float(cfg.gaussian_sigma), brown_hue_range=tuple(cfg.brown_hue_range),
@@ -273,6 +288,10 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
         shape = ops.shape_stats(contour, counts, int(x.shape[1]), int(x.shape[2])) if measure or analyze else None
         if analyze:
             res["Analyze"] = F.analyze_filter_batch(masked, (mask, contour, counts), cfg, shape=shape)
+        if marks:
+            pics, _pts, pc = F.landmarks_filter_batch(masked, (mask2, contour, counts), cfg)
+            res["Landmarks"] = pics
+            res["landmark_counts"] = [tuple(int(v) for v in row) for row in pc.cpu().tolist()]
         if "Brown" in types:
             out, stats = ops.brown_spots_u8(
                 masked, mask, brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
@@ -293,14 +312,14 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
 
 class _Runner:
     def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor,
-                 measure: bool = False, overlays: bool = False):
+                 measure: bool = False, overlays: bool = False, landmarks: bool = False):
         self.types, self.cfg, self.pool = types, cfg, pool
-        self.measure, self.overlays = measure, overlays
+        self.measure, self.overlays, self.landmarks = measure, overlays, landmarks
         self.rows: Dict[Path, List[str]] = {}   # --measure: image path -> CSV cells after `file`
         self.skip_existing, self.overwrite = skip_existing, overwrite
         self.hist = "Hist" in types and _have_matplotlib()
         for t in NOT_PORTED:   # one warning per run
-            if t in types and not (overlays and t == "Analyze"):
+            if t in types and not (overlays and t == "Analyze") and not (landmarks and t == "Landmarks"):
                 logging.warning("%s is not ported to the GPU (PlantCV shape analysis / landmarks): no %s output is "
                                 "written", t, t)
         if "Hist" in types and not self.hist:
@@ -326,13 +345,13 @@ class _Runner:
         for c0 in range(0, len(items), CHUNK):
             chunk = items[c0:c0 + CHUNK]
             x = torch.from_numpy(np.stack([a for _p, _d, a in chunk])).to(dev)
-            res = transform_batch(x, self.types, self.cfg, measure, self.overlays)
+            res = transform_batch(x, self.types, self.cfg, measure, self.overlays, self.landmarks)
             if measure:
                 from ..transform.filters import measure_row
                 for i, (p, _d, _a) in enumerate(chunk):
                     self.rows[p] = measure_row(res["measure"], i)
             names = [output_names(p.stem) for p, _d, _a in chunk]
-            for t in ("Mask", "Blur", "ROI", "Analyze", "Brown"):   # process_single_image's order
+            for t in ("Mask", "Blur", "ROI", "Analyze", "Landmarks", "Brown"):   # process_single_image's order
                 if t not in res:
                     continue
                 outs = [d / nm[t] for (_p, d, _a), nm in zip(chunk, names)]
@@ -341,6 +360,10 @@ class _Runner:
                     y = res[t] if len(todo) == len(chunk) else res[t][torch.tensor(todo, device=dev)]
                     for i, data in zip(todo, encode_jpeg_batch(y)):
                         self._write(outs[i], data, saved)
+                if t == "Landmarks":
+                    from ..transform.filters import log_landmarks
+                    for b, v, d in res["landmark_counts"]:
+                        log_landmarks(b, v, d)
                 if t == "Brown":
                     for count, pct, area in res["brown_stats"]:
                         logging.info(f"Brown spots detected: {count} regions, {pct:.1f}% of leaf area ({area} pixels)")
@@ -438,7 +461,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         out_d.mkdir(parents=True, exist_ok=True)
         with ThreadPoolExecutor(_workers(args.workers)) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays)
+                             args.overlays, args.landmarks)
             saved = runner.run([(ip, out_d)])
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else out_d / "measurements.csv", [(ip, out_d)],
@@ -464,7 +487,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         jobs = [(p, dst) for p in imgs]
         with ThreadPoolExecutor(n_threads) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays)
+                             args.overlays, args.landmarks)
             saved = runner.run(jobs)
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else dst / "measurements.csv", jobs, runner.rows,
@@ -521,6 +544,8 @@ class TransformFunction:
     reference would feed their picture when it is the last produced).  With overlays=True Analyze does produce its
     picture (transform.analyze_filter_batch on the original image and its mask, at its place after ROI and before
     Brown); an image without a contour then gets the original image, the reference's picture without its caption.
+    With landmarks=True Landmarks produces its picture too (transform.landmarks_filter_batch on the original image
+    with the mask made from it, after Analyze and before Hist and Brown); an image without a contour keeps what it had.
     The augmentation draws come from Python's global `random`, under a lock, image by image in batch order, so that after random.seed(k) a batch equals
     sequential calls.  A file the filters reject or any stage error logs the reference's error line and takes its
     fallback (Pillow NEAREST resize of the file, no augmentation); an unreadable file gives the black pair.  The
@@ -528,9 +553,10 @@ class TransformFunction:
     per-image log line is not written either."""
 
     def __init__(self, cfg, transform_types: Optional[Sequence[str]], apply_augmentation: bool, workers: int = 0,
-                 overlays: bool = False):
+                 overlays: bool = False, landmarks: bool = False):
         self.cfg = cfg
         self.overlays = bool(overlays)
+        self.landmarks = bool(landmarks)
         self.transform_types = transform_types
         self.apply_augmentation = bool(apply_augmentation)
         self.workers = workers
@@ -550,14 +576,16 @@ class TransformFunction:
                 log.info("Duplicate transform '%s' ignored for %s", name, where)
             else:
                 result.append(name)
-        skipped = [t for t in TRAIN_NOT_PRODUCED if t in result and not (self.overlays and t == "Analyze")]
+        on = {"Analyze": self.overlays, "Landmarks": self.landmarks}
+        skipped = [t for t in TRAIN_NOT_PRODUCED if t in result and not on.get(t, False)]
         if skipped:
             with self._lock:
                 first, self._warned = not self._warned, True
             if first:
-                log.warning("%s produce no image in the training transform (%s not ported, Hist is a figure) and are "
-                            "skipped", ", ".join(skipped),
-                            "Landmarks is" if self.overlays else "Analyze and Landmarks are")
+                off = [t for t in ("Analyze", "Landmarks") if not on[t]]
+                why = (" and ".join(off) + (" are" if len(off) > 1 else " is") + " not ported, ") if off else ""
+                log.warning("%s produce no image in the training transform (%sHist is a figure) and are "
+                            "skipped", ", ".join(skipped), why)
         return tuple(result)
 
     # ---------------------------------------------------------------- stages of one same-size group
@@ -591,6 +619,9 @@ class TransformFunction:
             res = torch.where((found != 0).view(-1, 1, 1, 1), vis, res)
         if self.overlays and "Analyze" in types:   # an image without a contour gets the original, without the caption
             res = F.analyze_filter_batch(x, masks, cfg)
+        if self.landmarks and "Landmarks" in types:   # an image without a contour keeps what it had
+            pics = F.landmarks_filter_batch(x, masks, cfg)[0]
+            res = torch.where((masks[2] > 0).view(-1, 1, 1, 1), pics, res)
         if "Brown" in types:
             res, _stats = ops.brown_spots_u8(
                 x, masks[0], brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
@@ -756,15 +787,16 @@ class TransformFunction:
 
 
 def create_transform_function(config_path: Optional[str] = None, transform_types: Optional[Tuple[str, ...]] = None,
-                              apply_augmentation: bool = True, overlays: bool = False) -> TransformFunction:
+                              apply_augmentation: bool = True, overlays: bool = False,
+                              landmarks: bool = False) -> TransformFunction:
     """The reference's create_transform_function (srcs/cli/Transformation.py:1008-1053): a `transform=` hook for
     ManifestSequence that feeds leaf-masked, saliency, ROI-boxed or brown-spot images, here a TransformFunction
     (callable per image, `.batch` for a device batch).  config_path: a YAML file with the reference's keys; None =
     the values of its config.yaml.  transform_types: names or aliases, None = all seven.  overlays (a switch of this
-    project): Analyze feeds its picture instead of being skipped."""
+    project): Analyze feeds its picture instead of being skipped.  landmarks (another one): so does Landmarks."""
     from ..transform.filters import TransformConfig, load_config
     cfg = load_config(Path(config_path)) if config_path else TransformConfig()
-    return TransformFunction(cfg, transform_types, apply_augmentation, overlays=overlays)
+    return TransformFunction(cfg, transform_types, apply_augmentation, overlays=overlays, landmarks=landmarks)
 
 
 if __name__ == "__main__":

@@ -2873,3 +2873,803 @@ int lf_analyze_overlay_u8(const uint8_t* rgb, const uint8_t* mask, const uint8_t
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// The pixel stages of the pseudo-landmarks filter (srcs/transform/filters/landmarks.py): CLAHE, the d = 5 bilateral
+// filter, the Shi-Tomasi corner score and the greedy point selection of goodFeaturesToTrack.  PARITY UNPINNED (no
+// cv2): the rules are the project's own, all in integers, stated in include/leafhip.h and restated in numpy by
+// tests/landmarks_ref.py; the kernels are held to them bit for bit.
+// ===========================================================================
+namespace {
+
+constexpr int kClaheTiles = 8;       // per axis
+constexpr int kGfT = 256;            // good_features_kernel
+constexpr size_t kClaheMaxArea = (size_t)1 << 27;   // keeps 1022 * tw * th below 2^31
+
+// p in [0, 2 * len - 2]: the image continued past its last sample by reflect-101
+__device__ __forceinline__ int reflect_pad(int p, int len) { return p >= len ? 2 * len - 2 - p : p; }
+
+// One workgroup of 256 threads per (tile, image): the tile's histogram in LDS, clipped and redistributed, its
+// inclusive prefix sum, and the LUT -> luts[n][tile][256].
+__global__ __launch_bounds__(kBlock) void clahe_lut_kernel(const uint8_t* __restrict__ gray,
+                                                           uint8_t* __restrict__ luts, int h, int w, int tw, int th) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned cum[2][256];
+    __shared__ unsigned excess;
+    const int t = threadIdx.x, tile = blockIdx.x;
+    const size_t n = blockIdx.y;
+    const uint8_t* g = gray + n * (size_t)h * w;
+    const int x0 = (tile % kClaheTiles) * tw, y0 = (tile / kClaheTiles) * th;
+    hist[t] = 0;
+    if (t == 0) excess = 0;
+    __syncthreads();
+    const int a = tw * th;
+    for (int p = t; p < a; p += kBlock) {
+        const int yy = p / tw, xx = p - yy * tw;
+        atomicAdd(&hist[g[(size_t)reflect_pad(y0 + yy, h) * w + reflect_pad(x0 + xx, w)]], 1u);
+    }
+    __syncthreads();
+    const unsigned clip = (unsigned)max(1, (2 * a) / 256);
+    unsigned v = hist[t];
+    if (v > clip) {
+        atomicAdd(&excess, v - clip);
+        v = clip;
+    }
+    __syncthreads();
+    const unsigned ex = excess, r = ex % 256u;
+    v += ex / 256u;
+    if (r > 0) {
+        const unsigned step = max(256u / r, 1u);
+        if (t % step == 0 && t / step < r) v += 1;
+    }
+    cum[0][t] = v;
+    __syncthreads();
+    int cur = 0;
+    for (int d = 1; d < 256; d <<= 1) {   // Hillis-Steele inclusive scan
+        cum[cur ^ 1][t] = cum[cur][t] + (t >= d ? cum[cur][t - d] : 0u);
+        cur ^= 1;
+        __syncthreads();
+    }
+    const long long l = (2LL * 255 * cum[cur][t] + a) / (2LL * a);
+    luts[(n * (kClaheTiles * kClaheTiles) + tile) * 256 + t] = (uint8_t)(l > 255 ? 255 : l);
+}
+
+// fx = 2 p + 1 - t (twice the distance from the first tile's centre): the lower tile, clamped with its neighbour into
+// [0, 7], and the neighbour's weight a in [0, 2 t) (the lower tile's is 2 t - a).
+__device__ __forceinline__ void clahe_axis(int p, int t, int& lo, int& hi, unsigned& a) {
+    const int f = 2 * p + 1 - t;
+    const int i = f < 0 ? -1 : f / (2 * t);
+    a = (unsigned)(f - 2 * t * i);
+    lo = clampi(i, 0, kClaheTiles - 1);
+    hi = clampi(i + 1, 0, kClaheTiles - 1);
+}
+
+__global__ __launch_bounds__(kBlock) void clahe_apply_kernel(const uint8_t* __restrict__ gray,
+                                                             const uint8_t* __restrict__ luts,
+                                                             uint8_t* __restrict__ out, int h, int w, int tw, int th) {
+    const size_t n = blockIdx.y;
+    const int hw = h * w;
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= hw) return;
+    const int y = p / w, x = p - y * w;
+    int tx0, tx1, ty0, ty1;
+    unsigned ax, ay;
+    clahe_axis(x, tw, tx0, tx1, ax);
+    clahe_axis(y, th, ty0, ty1, ay);
+    const unsigned v = gray[n * hw + p];
+    const uint8_t* L = luts + n * (kClaheTiles * kClaheTiles) * 256 + v;
+    const unsigned bx = 2u * tw - ax, by = 2u * th - ay;
+    const unsigned l00 = L[(ty0 * kClaheTiles + tx0) * 256], l01 = L[(ty0 * kClaheTiles + tx1) * 256];
+    const unsigned l10 = L[(ty1 * kClaheTiles + tx0) * 256], l11 = L[(ty1 * kClaheTiles + tx1) * 256];
+    const unsigned sum = (l00 * bx + l01 * ax) * by + (l10 * bx + l11 * ax) * ay;   // <= 255 * 4 tw th < 2^31
+    out[n * hw + p] = (uint8_t)((sum + 2u * tw * th) / (4u * tw * th));
+}
+
+// d = 5: the 21 taps with dx^2 + dy^2 <= 4; wc / ws are Q16 tables (range by |difference|, space by squared distance)
+__global__ __launch_bounds__(kBlock) void bilateral_kernel(const uint8_t* __restrict__ gray,
+                                                           const int32_t* __restrict__ wc,
+                                                           const int32_t* __restrict__ ws, uint8_t* __restrict__ out,
+                                                           int h, int w) {
+    __shared__ unsigned swc[256];
+    __shared__ unsigned sws[5];
+    swc[threadIdx.x] = (unsigned)wc[threadIdx.x];
+    if (threadIdx.x < 5) sws[threadIdx.x] = (unsigned)ws[threadIdx.x];
+    __syncthreads();
+    const size_t n = blockIdx.y;
+    const int hw = h * w;
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= hw) return;
+    const uint8_t* g = gray + n * hw;
+    const int y = p / w, x = p - y * w;
+    const int c = g[p];
+    unsigned sw = 0, swv = 0;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int yy = dy < 0 ? (y + dy < 0 ? -(y + dy) : y + dy) : reflect_pad(y + dy, h);
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            if (dx * dx + dy * dy > 4) continue;
+            const int xx = dx < 0 ? (x + dx < 0 ? -(x + dx) : x + dx) : reflect_pad(x + dx, w);
+            const int v = g[(size_t)yy * w + xx];
+            const int d = v > c ? v - c : c - v;
+            const unsigned wt =
+                (unsigned)(((unsigned long long)sws[dx * dx + dy * dy] * swc[d] + 32768u) >> 16);   // <= 65536
+            sw += wt;
+            swv += wt * (unsigned)v;   // <= 21 * 65536 * 255 < 2^29
+        }
+    }
+    out[n * hw + p] = sw ? (uint8_t)((2u * swv + sw) / (2u * sw)) : (uint8_t)c;
+}
+
+// floor(sqrt(v)) for 0 <= v < 2^52: the double root, then the integer fix-up
+__device__ __forceinline__ long long isqrt_ll(long long v) {
+    long long r = (long long)sqrt((double)v);
+    if (r * r > v) --r;
+    if ((r + 1) * (r + 1) <= v) ++r;
+    return r;
+}
+
+// Shi-Tomasi, block size 3: S = A + C - isqrt((A - C)^2 + 4 B^2) over the 3 x 3 sums of the Sobel products
+__global__ __launch_bounds__(kBlock) void corner_score_kernel(const uint8_t* __restrict__ gray,
+                                                              int32_t* __restrict__ score, int h, int w) {
+    const size_t n = blockIdx.y;
+    const int hw = h * w;
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= hw) return;
+    const uint8_t* g = gray + n * hw;
+    const int y = p / w, x = p - y * w;
+    int A = 0, B = 0, C = 0;   // A, C <= 9 * 1020^2 < 2^24
+    for (int j = -1; j <= 1; ++j) {
+        const int yy = reflect101i(y + j, h);
+        const int y0 = reflect101i(yy - 1, h), y2 = reflect101i(yy + 1, h);
+        for (int i = -1; i <= 1; ++i) {
+            const int xx = reflect101i(x + i, w);
+            const Sob s = sobel_at(g, w, y0, yy, y2, reflect101i(xx - 1, w), xx, reflect101i(xx + 1, w));
+            A += s.dx * s.dx;
+            B += s.dx * s.dy;
+            C += s.dy * s.dy;
+        }
+    }
+    const long long d = (long long)A - C;
+    score[n * hw + p] = (int32_t)((long long)A + C - isqrt_ll(d * d + 4LL * B * B));
+}
+
+// ---- point selection.  A candidate's key orders by score descending, then raster position ascending; 0 = dead.
+__device__ __forceinline__ unsigned long long gf_key(int s, int pos) {
+    return ((unsigned long long)(unsigned)s << 32) | (0xffffffffu - (unsigned)pos);
+}
+__device__ __forceinline__ int gf_key_pos(unsigned long long k) { return (int)(0xffffffffu - (unsigned)k); }
+
+struct GfLds {
+    int smax;
+    unsigned count;
+    unsigned long long best;
+};
+
+// The whole workgroup of T threads selects up to max_points points of one score plane where mask(p) holds, into
+// pts (x, y); returns their number (uniform).  keys: (h - 2) * (w - 2) words of scratch.  Bounded: at most
+// max_points rounds of one pass over the candidates.
+template <int T, typename M>
+__device__ int good_features_block(GfLds& L, const int32_t* __restrict__ sc, int h, int w, long long q_num,
+                                   long long q_den, int min_dist, int max_points,
+                                   unsigned long long* __restrict__ keys, int32_t* __restrict__ pts, M mask) {
+    const int t = threadIdx.x, hw = h * w;
+    __syncthreads();
+    if (t == 0) {
+        L.smax = 0;
+        L.count = 0;
+    }
+    __syncthreads();
+    int m = 0;
+    for (int p = t; p < hw; p += T)
+        if (mask(p)) m = max(m, sc[p]);
+    if (m > 0) atomicMax(&L.smax, m);
+    __syncthreads();
+    const int smax = L.smax;
+    if (smax <= 0 || max_points <= 0) return 0;
+    const long long thr = q_num * smax;
+    const int iw = w - 2, inner = (h - 2) * iw;
+    for (int q = t; q < inner; q += T) {
+        const int y = q / iw + 1, x = q - (y - 1) * iw + 1, p = y * w + x;
+        const int s = sc[p];
+        if (q_den * s <= thr || !mask(p)) continue;
+        // a neighbour that is not live scores below every live pixel, so >= all eight is >= the live ones
+        const int32_t *r0 = sc + p - w, *r2 = sc + p + w;
+        const int nb = max(max(max(r0[-1], r0[0]), max(r0[1], sc[p - 1])),
+                           max(max(sc[p + 1], r2[-1]), max(r2[0], r2[1])));
+        if (s >= nb) keys[atomicAdd(&L.count, 1u)] = gf_key(s, p);
+    }
+    __syncthreads();
+    const int cnt = (int)L.count;
+    const int md2 = min_dist * min_dist;
+    int taken = 0;
+    for (; taken < max_points; ++taken) {
+        if (t == 0) L.best = 0;
+        __syncthreads();
+        unsigned long long b = 0;
+        for (int i = t; i < cnt; i += T) b = max(b, keys[i]);
+        for (int o = 32; o; o >>= 1) b = max(b, __shfl_xor(b, o));
+        if ((t & 63) == 0 && b) atomicMax(&L.best, b);
+        __syncthreads();
+        const unsigned long long best = L.best;
+        if (!best) break;   // uniform
+        const int bp = gf_key_pos(best), by = bp / w, bx = bp - by * w;
+        if (t == 0) {
+            pts[2 * taken] = bx;
+            pts[2 * taken + 1] = by;
+        }
+        for (int i = t; i < cnt; i += T) {
+            const unsigned long long k = keys[i];
+            if (!k) continue;
+            const int kp = gf_key_pos(k), ky = kp / w, kx = kp - ky * w;
+            if (k == best || (kx - bx) * (kx - bx) + (ky - by) * (ky - by) < md2) keys[i] = 0;
+        }
+        __syncthreads();
+    }
+    return taken;
+}
+
+__global__ __launch_bounds__(kGfT) void good_features_kernel(const int32_t* __restrict__ score,
+                                                             const uint8_t* __restrict__ mask, int h, int w,
+                                                             int q_num, int q_den, int min_dist, int max_points,
+                                                             unsigned long long* __restrict__ keys,
+                                                             int32_t* __restrict__ points,
+                                                             int32_t* __restrict__ counts) {
+    __shared__ GfLds L;
+    const size_t n = blockIdx.x;
+    const uint8_t* mk = mask + n * (size_t)h * w;
+    int32_t* pts = points + n * (size_t)max_points * 2;
+    const int got = good_features_block<kGfT>(L, score + n * (size_t)h * w, h, w, q_num, q_den, min_dist, max_points,
+                                              keys + n * (size_t)(h - 2) * (w - 2), pts,
+                                              [mk](int p) { return mk[p] != 0; });
+    for (int i = 2 * got + threadIdx.x; i < 2 * max_points; i += kGfT) pts[i] = 0;   // rows past the count
+    if (threadIdx.x == 0) counts[n] = got;
+}
+
+size_t clahe_lut_bytes(int n) { return up((size_t)n * kClaheTiles * kClaheTiles * 256); }
+size_t good_features_key_bytes(int n, int h, int w) { return up((size_t)n * (h - 2) * (w - 2) * 8); }
+
+}  // namespace
+
+extern "C" {
+
+#define LF_PLANE_CHECKS(name, n, h, w)                                                                           \
+    LF_REQUIRE(n > 0 && n <= 65535, name ": bad batch n=%d", n);                                                  \
+    LF_REQUIRE(h >= 8 && w >= 8, name ": a %d x %d image is below the 8 x 8 minimum", h, w);                      \
+    LF_REQUIRE((size_t)h * w < ((size_t)1 << 30), name ": image too large")
+
+size_t lf_clahe_workspace(int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return clahe_lut_bytes(n);
+}
+
+int lf_clahe_u8(const uint8_t* gray, uint8_t* out, int n, int h, int w, void* workspace, size_t ws_bytes,
+                lf_stream_t stream) {
+    LF_REQUIRE(gray && out && workspace, "lf_clahe: null buffer");
+    LF_PLANE_CHECKS("lf_clahe", n, h, w);
+    const int wp = (w + 7) & ~7, hp = (h + 7) & ~7;
+    LF_REQUIRE((size_t)wp * hp <= kClaheMaxArea, "lf_clahe: a %d x %d image is over the 2^27-pixel limit", h, w);
+    LF_REQUIRE(ws_bytes >= lf_clahe_workspace(n, h, w), "lf_clahe: workspace too small (%zu < %zu)", ws_bytes,
+               lf_clahe_workspace(n, h, w));
+    hipStream_t s = lf::as_stream(stream);
+    uint8_t* luts = static_cast<uint8_t*>(workspace);
+    const int tw = wp / kClaheTiles, th = hp / kClaheTiles;
+    clahe_lut_kernel<<<dim3(kClaheTiles * kClaheTiles, n), kBlock, 0, s>>>(gray, luts, h, w, tw, th);
+    clahe_apply_kernel<<<dim3((h * w + kBlock - 1) / kBlock, n), kBlock, 0, s>>>(gray, luts, out, h, w, tw, th);
+    return lf::check_launch("lf_clahe");
+}
+
+int lf_bilateral_u8(const uint8_t* gray, const int32_t* wc, const int32_t* ws, uint8_t* out, int n, int h, int w,
+                    lf_stream_t stream) {
+    LF_REQUIRE(gray && wc && ws && out, "lf_bilateral: null buffer");
+    LF_PLANE_CHECKS("lf_bilateral", n, h, w);
+    LF_REQUIRE(gray != out, "lf_bilateral: in place is not supported");
+    bilateral_kernel<<<dim3((h * w + kBlock - 1) / kBlock, n), kBlock, 0, lf::as_stream(stream)>>>(gray, wc, ws, out,
+                                                                                                   h, w);
+    return lf::check_launch("lf_bilateral");
+}
+
+int lf_corner_score_u8(const uint8_t* gray, int32_t* score, int n, int h, int w, lf_stream_t stream) {
+    LF_REQUIRE(gray && score, "lf_corner_score: null buffer");
+    LF_PLANE_CHECKS("lf_corner_score", n, h, w);
+    corner_score_kernel<<<dim3((h * w + kBlock - 1) / kBlock, n), kBlock, 0, lf::as_stream(stream)>>>(gray, score, h,
+                                                                                                      w);
+    return lf::check_launch("lf_corner_score");
+}
+
+size_t lf_good_features_workspace(int n, int h, int w) {
+    if (n <= 0 || h < 3 || w < 3) return 0;
+    return good_features_key_bytes(n, h, w);
+}
+
+int lf_good_features(const int32_t* score, const uint8_t* mask, int32_t* points, int32_t* counts, int n, int h, int w,
+                     int q_num, int q_den, int min_dist, int max_points, void* workspace, size_t ws_bytes,
+                     lf_stream_t stream) {
+    LF_REQUIRE(score && mask && points && counts && workspace, "lf_good_features: null buffer");
+    LF_PLANE_CHECKS("lf_good_features", n, h, w);
+    LF_REQUIRE(q_num >= 0 && q_den > 0, "lf_good_features: bad quality %d / %d", q_num, q_den);
+    LF_REQUIRE(min_dist >= 0 && min_dist <= 16384, "lf_good_features: bad min_dist %d", min_dist);
+    LF_REQUIRE(max_points >= 1 && max_points <= (1 << 20), "lf_good_features: bad max_points %d", max_points);
+    LF_REQUIRE(ws_bytes >= lf_good_features_workspace(n, h, w), "lf_good_features: workspace too small (%zu < %zu)",
+               ws_bytes, lf_good_features_workspace(n, h, w));
+    LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, "lf_good_features: workspace must be 16-byte aligned");
+    good_features_kernel<<<n, kGfT, 0, lf::as_stream(stream)>>>(score, mask, h, w, q_num, q_den, min_dist, max_points,
+                                                               static_cast<unsigned long long*>(workspace), points,
+                                                               counts);
+    return lf::check_launch("lf_good_features");
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// apply_landmarks_filter (srcs/transform/filters/landmarks.py) for a same-size batch.  The pixel stages above and the
+// gray / Canny / Sobel kernels run on workspace planes; then one workgroup per image, beside brown_spots_kernel and
+// with its helpers, does everything that needs bit planes, labels, the contour and drawing.  The rules: "Landmark
+// rules" in include/leafhip.h, restated by tests/landmarks_ref.py.  Every walk is bounded: the union-find, flood and
+// border walks by their own step bounds, point selection by max_points, the component loop by the component count.
+// ===========================================================================
+namespace {
+
+constexpr unsigned kLmRed = 0x0000ffu, kLmGreen = 0x00ff00u, kLmBlue = 0xff0000u,
+                   kLmBrown = 139u | (69u << 8) | (19u << 16);   // r | g << 8 | b << 16
+
+struct LmArgs {
+    MaskArgs a;   // the brown predicate, se_brown, brown_min_area
+    int bq, vq, dq, pcap, ccap, gfcap;
+};
+
+struct LmLds {
+    GfLds gf;
+    ContourBox box;
+    int m, nb, ncomp, tarea;
+    unsigned long long sel, sx, sy;
+};
+
+// edges = e1 | e2 | (uint8(minmax-normalised Sobel magnitude) > 40), as 0 / 255
+__global__ __launch_bounds__(kBlock) void lm_edges_kernel(const uint8_t* __restrict__ e1,
+                                                          const uint8_t* __restrict__ e2,
+                                                          const float* __restrict__ gmag,
+                                                          const unsigned* __restrict__ mm, uint8_t* __restrict__ out,
+                                                          int hw) {
+    const unsigned n = blockIdx.y;
+    __shared__ float coef[2];
+    if (threadIdx.x == 0) norm_coeffs(mm[n * 6 + 0], mm[n * 6 + 1], coef[0], coef[1]);
+    __syncthreads();
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= hw) return;
+    const size_t i = (size_t)n * hw + p;
+    out[i] = (e1[i] | e2[i] || trunc_u8(__fmaf_rn(gmag[i], coef[0], coef[1])) > 40) ? 255 : 0;
+}
+
+// discs of radius r (|p - q|^2 <= r^2 + r, an overwrite) at `count` points (kind, x, y), by the whole workgroup
+__device__ void lm_discs(uint8_t* img, int h, int w, const int* pts3, int count, int r, unsigned k) {
+    const int side = 2 * r + 1, cells = side * side;
+    for (int i = threadIdx.x; i < count * cells; i += kMaskT) {
+        const int pi = i / cells, o = i - pi * cells;
+        const int ox = o % side - r, oy = o / side - r;
+        const int x = pts3[3 * pi + 1] + ox, y = pts3[3 * pi + 2] + oy;
+        if (ox * ox + oy * oy <= r * r + r && x >= 0 && x < w && y >= 0 && y < h) put_px(img, w, x, y, k);
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double lm_seg_len(const int* cp, int m, int k) {
+    const int j = k + 1 < m ? k + 1 : 0;
+    const long long dx = cp[2 * j] - cp[2 * k], dy = cp[2 * j + 1] - cp[2 * k + 1];
+    return __dsqrt_rn((double)(dx * dx + dy * dy));
+}
+
+// resample_contour: bq points along the closed polygon cp[0 .. m), one lane, float64 in numpy's order.  Returns the
+// number of points written to pts3 as (0, x, y).
+__device__ int lm_resample(const int* cp, int m, int bq, int* pts3) {
+    double total = 0.0;
+    for (int k = 0; k < m; ++k) total = __dadd_rn(total, lm_seg_len(cp, m, k));
+    if (total == 0.0) {
+        pts3[0] = 0;
+        pts3[1] = cp[0];
+        pts3[2] = cp[1];
+        return 1;
+    }
+    const double step = __ddiv_rn(total, (double)bq);
+    int j = 0;
+    double cj = 0.0, cj1 = lm_seg_len(cp, m, 0);   // cum[j], cum[j + 1]
+    for (int i = 0; i < bq; ++i) {
+        const double t = __dmul_rn((double)i, step);
+        while (j < m && cj1 < t) {   // at most m advances over the whole loop
+            ++j;
+            cj = cj1;
+            if (j < m) cj1 = __dadd_rn(cj, lm_seg_len(cp, m, j));
+        }
+        int x = cp[0], y = cp[1];
+        if (j < m) {
+            const int j1 = j + 1 < m ? j + 1 : 0;
+            const double dt = __dsub_rn(cj1, cj);
+            const double a = dt == 0.0 ? 0.0 : __ddiv_rn(__dsub_rn(t, cj), dt), b = __dsub_rn(1.0, a);
+            x = (int)__dadd_rn(__dmul_rn(b, (double)cp[2 * j]), __dmul_rn(a, (double)cp[2 * j1]));
+            y = (int)__dadd_rn(__dmul_rn(b, (double)cp[2 * j + 1]), __dmul_rn(a, (double)cp[2 * j1 + 1]));
+        }
+        pts3[3 * i] = 0;
+        pts3[3 * i + 1] = x;
+        pts3[3 * i + 2] = y;
+    }
+    return bq;
+}
+
+__global__ __launch_bounds__(kMaskT) void landmarks_kernel(
+    const uint8_t* __restrict__ rgb, const uint8_t* __restrict__ leaf_mask, const int* __restrict__ contour,
+    const int* __restrict__ counts, int cap, const uint8_t* __restrict__ edges, const int32_t* __restrict__ score_q,
+    const int32_t* __restrict__ score_g, const uint16_t* __restrict__ lab_tabs, Run* __restrict__ runs,
+    int* __restrict__ parent, int* __restrict__ area, int runs_per_image, int h, int w, int wpr, LmArgs g,
+    unsigned long long* __restrict__ keys, int* cbuf, int* gfbuf, uint8_t* out, int* points,
+    int* __restrict__ pcounts, int* __restrict__ flags) {
+    extern __shared__ unsigned lds_planes[];
+    __shared__ HsvTabs H;
+    __shared__ LabTabs T;
+    __shared__ PostLds S;
+    __shared__ LmLds L;
+    const size_t n = blockIdx.x;
+    const int tid = threadIdx.x, hw = h * w;
+    const Post P = post_view(lds_planes, 4, S, runs, parent, area, runs_per_image, h, w, wpr, kMaskT);
+    H.fill(kMaskT);
+    T.fill(lab_tabs, kMaskT);
+    const uint8_t* img = rgb + n * (size_t)hw * 3;
+    const uint8_t* lm = leaf_mask + n * (size_t)hw;
+    const uint8_t* ed = edges + n * (size_t)hw;
+    const int32_t *sq = score_q + n * (size_t)hw, *sg = score_g + n * (size_t)hw;
+    const int* cin = contour + n * (size_t)cap * 2;
+    unsigned long long* kb = keys + n * (size_t)(h - 2) * (w - 2);
+    int* cb = cbuf + n * (size_t)g.ccap * 2;
+    int* gp = gfbuf + n * (size_t)g.gfcap * 2;
+    int* pts = points + n * (size_t)g.pcap * 3;
+    uint8_t* o = out + n * (size_t)hw * 3;
+
+    const int m0 = contour_bbox<kMaskT>(L.box, cin, counts[n], cap, h, w);
+    if (m0 <= 0 || L.box.bad) {   // no contour: the copy, no points; a bad record: the error bit
+        if (tid == 0) {
+            flags[n] = L.box.bad ? kRoiBad : 0;
+            pcounts[3 * n] = pcounts[3 * n + 1] = pcounts[3 * n + 2] = 0;
+        }
+        return;
+    }
+    auto bit = [&](const unsigned* pl, int p) {
+        const int y = p / w, x = p - y * w;
+        return ((pl[y * wpr + (x >> 5)] >> (x & 31)) & 1u) != 0;
+    };
+
+    // 1: the enhanced mask E = close5(M | close5(brown & M)) in P.A, its largest external contour C'
+    build_plane(P, P.A, kMaskT, [&](int y, int x) { return lm[y * w + x] > 0; });
+    build_plane(P, P.B, kMaskT,
+                [&](int y, int x) { return lm[y * w + x] > 0 && brown_px(H, T, img + 3 * (y * w + x), g.a); });
+    morph_ellipse<5>(P, P.B, P.C, false, kMaskT);
+    morph_ellipse<5>(P, P.C, P.B, true, kMaskT);
+    for (int i = tid; i < h * wpr; i += kMaskT) P.A[i] |= P.B[i];
+    __syncthreads();
+    morph_ellipse<5>(P, P.A, P.C, false, kMaskT);
+    morph_ellipse<5>(P, P.C, P.A, true, kMaskT);
+    long long area2 = 0;
+    const int best = largest_external(P, area2);
+    if (tid == 0) {
+        int m = -1;   // E is empty: C' = C
+        if (best >= 0) {
+            const Run r = P.rn[best];
+            long long a2;
+            m = trace_outer(P, P.A, r.x0, r.y, a2, cb, g.ccap, false, 1.f);
+            if (m > g.ccap) {   // the contour buffer of the workspace is full
+                atomicOr(P.status, kFlagBound);
+                m = g.ccap;
+            }
+        }
+        L.m = m;
+    }
+    __syncthreads();
+    const int* cp = L.m < 0 ? cin : cb;
+    const int m = L.m < 0 ? m0 : L.m;
+
+    // 2: the border points
+    if (tid == 0) L.nb = lm_resample(cp, m, g.bq, pts);
+    __syncthreads();
+    const int nb = L.nb;
+
+    // 3: the vein points: corners of the equalised plane on the dilated edges inside erode3(E), then the fill
+    morph_ellipse<3>(P, P.A, P.B, true, kMaskT);
+    build_plane(P, P.C, kMaskT, [&](int y, int x) {
+        return ed[y * w + x] != 0 && ((P.B[y * wpr + (x >> 5)] >> (x & 31)) & 1u);
+    });
+    morph_ellipse<3>(P, P.C, P.D, false, kMaskT);
+    const int vgot = good_features_block<kMaskT>(L.gf, sq, h, w, 2, 1000, 2, g.vq, kb, gp,
+                                                 [&](int p) { return bit(P.D, p); });
+    __syncthreads();
+    for (int i = tid; i < vgot; i += kMaskT) {
+        pts[3 * (nb + i)] = 1;
+        pts[3 * (nb + i) + 1] = gp[2 * i];
+        pts[3 * (nb + i) + 2] = gp[2 * i + 1];
+    }
+    int nv = vgot;
+    if (vgot < g.vq) {   // evenly spaced set pixels of D in raster order
+        for (int y = tid; y < h; y += kMaskT) {
+            int c = 0;
+            for (int i = 0; i < wpr; ++i) c += __popc(P.D[y * wpr + i]);
+            P.rowstart[y + 1] = c;
+        }
+        if (tid == 0) P.rowstart[0] = 0;
+        __syncthreads();
+        if (tid == 0)
+            for (int y = 0; y < h; ++y) P.rowstart[y + 1] += P.rowstart[y];
+        __syncthreads();
+        const int cnt = P.rowstart[h], need = g.vq - vgot;
+        if (cnt > 0) {
+            for (int i = tid; i < need; i += kMaskT) {
+                int r = need == 1 ? 0 : (int)(((long long)i * (cnt - 1)) / (need - 1));
+                int lo = 0, hi = h - 1;   // the last row whose start is <= r
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (P.rowstart[mid] <= r) lo = mid;
+                    else hi = mid - 1;
+                }
+                r -= P.rowstart[lo];
+                int x = 0;
+                for (int xw = 0; xw < wpr; ++xw) {
+                    unsigned wd = P.D[lo * wpr + xw];
+                    const int pc = __popc(wd);
+                    if (r >= pc) {
+                        r -= pc;
+                        continue;
+                    }
+                    for (; r > 0; --r) wd &= wd - 1;
+                    x = 32 * xw + __builtin_ctz(wd);
+                    break;
+                }
+                pts[3 * (nb + vgot + i)] = 1;
+                pts[3 * (nb + vgot + i) + 1] = x;
+                pts[3 * (nb + vgot + i) + 2] = lo;
+            }
+            nv = g.vq;
+        }
+        __syncthreads();
+    }
+
+    // 4: the disease points: components of open-close(brown & E), largest first
+    build_plane(P, P.B, kMaskT, [&](int y, int x) {
+        return ((P.A[y * wpr + (x >> 5)] >> (x & 31)) & 1u) && brown_px(H, T, img + 3 * (y * w + x), g.a);
+    });
+    morph_se(P, P.B, P.C, g.a.se_brown, true, kMaskT);   // MORPH_OPEN
+    morph_se(P, P.C, P.B, g.a.se_brown, false, kMaskT);
+    morph_se(P, P.B, P.C, g.a.se_brown, false, kMaskT);  // MORPH_CLOSE
+    morph_se(P, P.C, P.B, g.a.se_brown, true, kMaskT);
+    label_runs(P, P.B, true);
+    const int nr = *P.nruns;
+    if (tid == 0) L.ncomp = L.tarea = 0;
+    __syncthreads();
+    {
+        int c = 0, px = 0;
+        for (int k = tid; k < nr; k += kMaskT) {
+            if (P.par[k] != k || P.area[k] < g.a.brown_min_area) continue;
+            ++c;
+            px += P.area[k];
+        }
+        if (c) {
+            atomicAdd(&L.ncomp, c);
+            atomicAdd(&L.tarea, px);
+        }
+    }
+    __syncthreads();
+    const int ncomp = L.ncomp;
+    const int quota = min(max(ncomp, L.tarea / 50), 5 * g.dq);
+    int placed = 0;
+    unsigned long long prev = ~0ull;
+    int* dp = pts + 3 * (nb + nv);
+    for (int it = 0; it < ncomp && placed < quota; ++it) {
+        if (tid == 0) L.sel = L.sx = L.sy = 0;
+        __syncthreads();
+        unsigned long long b = 0;   // the next component: area descending, then first run ascending
+        for (int k = tid; k < nr; k += kMaskT) {
+            if (P.par[k] != k || P.area[k] < g.a.brown_min_area) continue;
+            const unsigned long long key = ((unsigned long long)(unsigned)P.area[k] << 32) | (0xffffffffu - (unsigned)k);
+            if (key < prev) b = max(b, key);
+        }
+        for (int off = 32; off; off >>= 1) b = max(b, __shfl_xor(b, off));
+        if ((tid & 63) == 0 && b) atomicMax(&L.sel, b);
+        __syncthreads();
+        const unsigned long long sel = L.sel;
+        if (!sel) break;
+        prev = sel;
+        const int comp = (int)(0xffffffffu - (unsigned)sel), carea = (int)(sel >> 32);
+        const int k = max(1, min(carea / 40, quota - placed));
+        paint_runs(P, P.C, true, [&](int root) { return root == comp; });
+        const int got = good_features_block<kMaskT>(L.gf, sg, h, w, 5, 1000, 3, k, kb, gp,
+                                                    [&](int p) { return bit(P.C, p); });
+        __syncthreads();
+        if (got > 0) {
+            const int take = min(got, max(1, g.dq - placed));
+            for (int i = tid; i < take; i += kMaskT) {
+                dp[3 * (placed + i)] = 2;
+                dp[3 * (placed + i) + 1] = gp[2 * i];
+                dp[3 * (placed + i) + 2] = gp[2 * i + 1];
+            }
+            placed += take;
+        } else {   // the centroid
+            unsigned long long sx = 0, sy = 0;
+            for (int r = tid; r < nr; r += kMaskT) {
+                if (P.par[r] != comp) continue;
+                const Run rr = P.rn[r];
+                const unsigned long long len = (unsigned)rr.x1 - rr.x0 + 1;
+                sx += ((unsigned long long)rr.x0 + rr.x1) * len / 2;
+                sy += (unsigned long long)rr.y * len;
+            }
+            if (sx | sy) {
+                atomicAdd(&L.sx, sx);
+                atomicAdd(&L.sy, sy);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                dp[3 * placed] = 2;
+                dp[3 * placed + 1] = (int)(L.sx / (unsigned)carea);
+                dp[3 * placed + 2] = (int)(L.sy / (unsigned)carea);
+            }
+            placed += 1;
+        }
+        __syncthreads();
+    }
+    const int nd = placed;
+
+    // 5: the picture, unless a bound was hit
+    __syncthreads();
+    const int status = S.status;
+    if (tid == 0) {
+        flags[n] = kRoiFound | status;
+        pcounts[3 * n] = status ? 0 : nb;
+        pcounts[3 * n + 1] = status ? 0 : nv;
+        pcounts[3 * n + 2] = status ? 0 : nd;
+    }
+    if (status) return;
+    lm_discs(o, h, w, pts, nb, 2, kLmRed);
+    for (int i = 0; i < m; ++i) {
+        const int j = i + 1 < m ? i + 1 : 0;
+        draw_aa(o, h, w, cp[2 * i], cp[2 * i + 1], cp[2 * j], cp[2 * j + 1], kLmGreen, tid, kMaskT);
+        __syncthreads();
+    }
+    lm_discs(o, h, w, pts + 3 * nb, nv, 2, kLmBlue);
+    lm_discs(o, h, w, dp, nd, 4, kLmBrown);
+}
+
+int lm_quota(int landmarks_count, int* bq, int* vq, int* dq) {
+    const int total = std::max(1, landmarks_count);
+    *bq = *vq = std::max(1, total / 3);
+    *dq = std::max(1, total - *bq - *vq);
+    return *bq + *vq + 5 * *dq;
+}
+
+struct LandmarksWs {
+    uint8_t *gray, *q, *bil, *e1, *e2, *luts, *canny;
+    int32_t *sq, *sg, *mag2;
+    uint32_t* dxdy;
+    float* gmag;
+    unsigned* mm;
+    unsigned long long* keys;
+    int *cbuf, *gfbuf;
+    size_t canny_bytes, lut_bytes;
+    int ccap, gfcap;
+    LabelBufs lb;
+    size_t bytes;
+    LandmarksWs(void* base, int n, int h, int w, int landmarks_count) {
+        Carver c{base};
+        const size_t px = (size_t)n * h * w;
+        int bq, vq, dq;
+        lm_quota(landmarks_count, &bq, &vq, &dq);
+        ccap = 8 * (h + w);
+        gfcap = std::max(vq, 5 * dq);
+        gray = c.take<uint8_t>(px);
+        q = c.take<uint8_t>(px);     // CLAHE(gray)
+        bil = c.take<uint8_t>(px);   // bilateral(q)
+        e1 = c.take<uint8_t>(px);    // Canny(q) -> the union of the three edge maps
+        e2 = c.take<uint8_t>(px);    // Canny(bil)
+        sq = c.take<int32_t>(4 * px);
+        sg = c.take<int32_t>(4 * px);
+        gmag = c.take<float>(4 * px);
+        mm = c.take<unsigned>((size_t)n * 6 * sizeof(unsigned));
+        const CannyWs cw(nullptr, n, h, w);
+        canny_bytes = cw.bytes;
+        canny = c.take<uint8_t>(canny_bytes);   // Canny's magnitude / (dx, dy), also what sal_sobel_kernel leaves there
+        const CannyWs cv(canny, n, h, w);
+        mag2 = cv.mag;
+        dxdy = cv.dxdy;
+        lut_bytes = clahe_lut_bytes(n);
+        luts = c.take<uint8_t>(lut_bytes);
+        keys = c.take<unsigned long long>(good_features_key_bytes(n, h, w));
+        cbuf = c.take<int>((size_t)n * ccap * 2 * 4);
+        gfbuf = c.take<int>((size_t)n * gfcap * 2 * 4);
+        lb.carve(c, n, h, w);
+        bytes = c.off;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int lf_landmarks_points_cap(int landmarks_count) {
+    int bq, vq, dq;
+    return lm_quota(landmarks_count, &bq, &vq, &dq);
+}
+
+size_t lf_landmarks_workspace(int n, int h, int w, int landmarks_count) {
+    if (n <= 0 || h < 8 || w < 8) return 0;
+    return LandmarksWs(nullptr, n, h, w, landmarks_count).bytes;
+}
+
+int lf_landmarks_u8(const uint8_t* rgb, const uint8_t* mask, const int32_t* contour, const int32_t* counts, int cap,
+                    const lf_brown_params* prm, int landmarks_count, const int32_t* wc, const int32_t* ws_tab,
+                    uint8_t* out, int32_t* points, int32_t* pcounts, int32_t* flags, int n, int h, int w,
+                    void* workspace, size_t ws_bytes, lf_stream_t stream) {
+    LF_REQUIRE(rgb && mask && contour && counts && prm && wc && ws_tab && out && points && pcounts && flags && workspace,
+               "lf_landmarks: null buffer");
+    LF_PLANE_CHECKS("lf_landmarks", n, h, w);
+    LF_REQUIRE(cap > 0, "lf_landmarks: bad contour capacity %d", cap);
+    LF_REQUIRE(h <= 65535 && w <= 65535, "lf_landmarks: image too large (%d x %d)", h, w);
+    LF_REQUIRE(landmarks_count <= (1 << 16), "lf_landmarks: landmarks_count %d is over 65536", landmarks_count);
+    const size_t lds = post_lds_bytes(4, h, (w + 31) / 32);
+    LF_REQUIRE(lds <= kMaskLdsCap,
+               "lf_landmarks: a %d x %d image needs %zu bytes of LDS for its four bit planes (limit %zu, one "
+               "workgroup per image)", h, w, lds, kMaskLdsCap);
+    LF_REQUIRE(prm->morph_kernel >= 1 && prm->morph_kernel <= 31,
+               "lf_landmarks: brown_morph_kernel %d outside [1, 31]", prm->morph_kernel);
+    LF_REQUIRE(ws_bytes >= lf_landmarks_workspace(n, h, w, landmarks_count),
+               "lf_landmarks: workspace too small (%zu < %zu)", ws_bytes,
+               lf_landmarks_workspace(n, h, w, landmarks_count));
+    LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "lf_landmarks: workspace must be 256-byte aligned");
+    const size_t bytes = (size_t)n * h * w * 3;
+    LF_REQUIRE(rgb + bytes <= out || out + bytes <= rgb, "lf_landmarks: rgb and out overlap");
+    LF_REQUIRE(lds <= dynamic_lds_cap<landmarks_kernel>(kMaskLdsCap, 48 * 1024),
+               "lf_landmarks: could not raise the LDS limit of the landmarks kernel");
+
+    hipStream_t s = lf::as_stream(stream);
+    const int hw = h * w;
+    const size_t px = (size_t)n * hw;
+    const LandmarksWs ws(workspace, n, h, w, landmarks_count);
+    LmArgs g{};
+    g.a.use_lab = prm->use_lab_brown;
+    g.a.hue_lo = prm->hue_lo;
+    g.a.hue_hi = prm->hue_hi;
+    g.a.s_min = prm->s_min;
+    g.a.v_max = prm->v_max;
+    g.a.a_min = prm->lab_a_min;
+    g.a.b_min = prm->lab_b_min;
+    g.a.brown_min_area = prm->min_area_px;
+    g.a.se_brown = ellipse_rows(prm->morph_kernel);
+    g.pcap = lm_quota(landmarks_count, &g.bq, &g.vq, &g.dq);
+    g.ccap = ws.ccap;
+    g.gfcap = ws.gfcap;
+
+    if (hipMemcpyAsync(out, rgb, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemsetAsync(points, 0, (size_t)n * g.pcap * 3 * sizeof(int32_t), s) != hipSuccess) {
+        lf::set_error("lf_landmarks: the copy of the input failed");
+        return LF_ERR_LAUNCH;
+    }
+    int rc = upload_lab_tables(ws.lb.tabs, s, "lf_landmarks");
+    if (rc != LF_OK) return rc;
+    rc = lf_rgb2gray_u8(rgb, ws.gray, px, stream);
+    if (rc != LF_OK) return rc;
+    rc = lf_clahe_u8(ws.gray, ws.q, n, h, w, ws.luts, ws.lut_bytes, stream);
+    if (rc != LF_OK) return rc;
+    const dim3 grid_px((hw + kBlock - 1) / kBlock, n);
+    const dim3 grid_fat((hw + kBlock * kPxPerThread - 1) / (kBlock * kPxPerThread), n);
+    minmax_init_kernel<<<(n * 6 + 255) / 256, 256, 0, s>>>(ws.mm, n);
+    sal_sobel_kernel<<<grid_fat, kBlock, 0, s>>>(ws.q, ws.mag2, ws.dxdy, ws.gmag, ws.mm, h, w);
+    rc = lf_canny_u8(ws.q, ws.e1, n, h, w, 30.0, 90.0, 1, ws.canny, ws.canny_bytes, stream);
+    if (rc != LF_OK) return rc;
+    rc = lf_bilateral_u8(ws.q, wc, ws_tab, ws.bil, n, h, w, stream);
+    if (rc != LF_OK) return rc;
+    rc = lf_canny_u8(ws.bil, ws.e2, n, h, w, 50.0, 130.0, 1, ws.canny, ws.canny_bytes, stream);
+    if (rc != LF_OK) return rc;
+    lm_edges_kernel<<<grid_px, kBlock, 0, s>>>(ws.e1, ws.e2, ws.gmag, ws.mm, ws.bil, hw);
+    rc = lf_corner_score_u8(ws.q, ws.sq, n, h, w, stream);
+    if (rc != LF_OK) return rc;
+    rc = lf_corner_score_u8(ws.gray, ws.sg, n, h, w, stream);
+    if (rc != LF_OK) return rc;
+    landmarks_kernel<<<n, kMaskT, lds, s>>>(rgb, mask, contour, counts, cap, ws.bil, ws.sq, ws.sg, ws.lb.tabs, ws.lb.rn,
+                                            ws.lb.parent, ws.lb.area, (int)mask_runs_per_image(h, w), h, w,
+                                            (w + 31) / 32, g, ws.keys, ws.cbuf, ws.gfbuf, out, points, pcounts, flags);
+    return lf::check_launch("lf_landmarks");
+}
+
+}  // extern "C"

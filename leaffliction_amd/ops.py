@@ -537,6 +537,144 @@ def canny_u8(gray: torch.Tensor, low: float, high: float, l2gradient: bool = Tru
     return out
 
 
+def _plane(t: torch.Tensor, dtype, name: str):
+    """A same-size batch of planes [N,H,W] for the landmark stages: h, w >= 8."""
+    _chk(t, dtype, name, 3)
+    n, h, w = (int(v) for v in t.shape)
+    if n == 0 or h < 8 or w < 8:
+        raise ValueError(f"{name}: expected [N,H,W] with N > 0 and H, W >= 8, got {tuple(t.shape)}")
+    return n, h, w
+
+
+def clahe_u8(gray: torch.Tensor) -> torch.Tensor:
+    """createCLAHE(clipLimit=2.0, tileGridSize=(8, 8)).apply for gray [N,H,W] uint8, H, W >= 8 -> [N,H,W] uint8.
+    The rule, in integers: include/leafhip.h (lf_clahe_u8)."""
+    n, h, w = _plane(gray, _U8, "clahe.gray")
+    nbytes = int(_lib.load().lf_clahe_workspace(n, h, w))
+    ws = torch.empty(nbytes, dtype=_U8, device=gray.device)
+    out = torch.empty_like(gray)
+    _lib.call("lf_clahe_u8", gray.data_ptr(), out.data_ptr(), n, h, w, ws.data_ptr(), nbytes, _stream())
+    return out
+
+
+def bilateral_tables(sigma_color: float = 50.0, sigma_space: float = 50.0):
+    """The Q16 weight tables of lf_bilateral_u8 as int32 numpy arrays: wc [256] by |difference|, ws [5] by squared
+    distance, rint(65536 exp(-k^2 / (2 sigma^2))) in float64."""
+    k = np.arange(256, dtype=np.float64)
+    wc = np.rint(65536.0 * np.exp(-(k * k) / (2.0 * float(sigma_color) ** 2))).astype(np.int32)
+    d2 = np.arange(5, dtype=np.float64)
+    ws = np.rint(65536.0 * np.exp(-d2 / (2.0 * float(sigma_space) ** 2))).astype(np.int32)
+    return wc, ws
+
+
+def bilateral_u8(gray: torch.Tensor, wc=None, ws=None) -> torch.Tensor:
+    """bilateralFilter(gray, 5, 50, 50) for gray [N,H,W] uint8, H, W >= 8 -> [N,H,W] uint8.  wc [256] / ws [5]: the
+    Q16 tables (int32, numpy or tensors; default bilateral_tables()).  The rule: include/leafhip.h (lf_bilateral_u8)."""
+    n, h, w = _plane(gray, _U8, "bilateral.gray")
+    dwc, dws = bilateral_tables()
+    tabs = []
+    for name, t, dflt, size in (("wc", wc, dwc, 256), ("ws", ws, dws, 5)):
+        t = torch.as_tensor(dflt if t is None else t)
+        if t.dtype != _I32 or tuple(t.shape) != (size,):
+            raise ValueError(f"bilateral.{name}: expected int32 [{size}], got {t.dtype} {list(t.shape)}")
+        if int(t.min()) < 0 or int(t.max()) > 65536:
+            raise ValueError(f"bilateral.{name}: a Q16 weight outside [0, 65536]")
+        tabs.append(t.to(gray.device).contiguous())
+    out = torch.empty_like(gray)
+    _lib.call("lf_bilateral_u8", gray.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr(), out.data_ptr(), n, h, w,
+              _stream())
+    return out
+
+
+def corner_score_u8(gray: torch.Tensor) -> torch.Tensor:
+    """The Shi-Tomasi score (cornerMinEigenVal, block size 3, Sobel 3) of gray [N,H,W] uint8, H, W >= 8, in integers
+    -> int32 [N,H,W], 0 <= S < 2^25.  The rule: include/leafhip.h (lf_corner_score_u8)."""
+    n, h, w = _plane(gray, _U8, "corner_score.gray")
+    out = torch.empty((n, h, w), dtype=_I32, device=gray.device)
+    _lib.call("lf_corner_score_u8", gray.data_ptr(), out.data_ptr(), n, h, w, _stream())
+    return out
+
+
+def good_features(score: torch.Tensor, mask: torch.Tensor, q_num: int, q_den: int, min_dist: int, max_points: int):
+    """goodFeaturesToTrack's selection on score planes [N,H,W] int32 (values >= 0) under mask [N,H,W] uint8: quality
+    level q_num / q_den of the largest masked score, local maxima, then greedy by score with the minimum distance.
+    Returns (points [N,max_points,2] int32 (x, y), rows past the count zero; counts [N] int32).  The rule:
+    include/leafhip.h (lf_good_features)."""
+    n, h, w = _plane(score, _I32, "good_features.score")
+    _chk(mask, _U8, "good_features.mask", 3)
+    if tuple(mask.shape) != (n, h, w) or mask.device != score.device:
+        raise ValueError(f"good_features.mask: expected {[n, h, w]} on {score.device}, got {list(mask.shape)} on "
+                         f"{mask.device}")
+    q_num, q_den, min_dist, max_points = int(q_num), int(q_den), int(min_dist), int(max_points)
+    if q_num < 0 or q_den <= 0 or min_dist < 0 or max_points < 1:
+        raise ValueError(f"good_features: bad parameters q = {q_num} / {q_den}, min_dist {min_dist}, max_points "
+                         f"{max_points}")
+    nbytes = int(_lib.load().lf_good_features_workspace(n, h, w))
+    ws = torch.empty(nbytes, dtype=_U8, device=score.device)
+    points = torch.empty((n, max_points, 2), dtype=_I32, device=score.device)
+    counts = torch.empty(n, dtype=_I32, device=score.device)
+    _lib.call("lf_good_features", score.data_ptr(), mask.data_ptr(), points.data_ptr(), counts.data_ptr(), n, h, w,
+              q_num, q_den, min_dist, max_points, ws.data_ptr(), nbytes, _stream())
+    return points, counts
+
+
+def landmarks_quotas(landmarks_count: int):
+    """(border, vein, disease quota, rows of the points buffer) for cfg.landmarks_count, as landmarks.py splits it."""
+    total = max(1, int(landmarks_count))
+    bq = vq = max(1, total // 3)
+    dq = max(1, total - bq - vq)
+    return bq, vq, dq, bq + vq + 5 * dq
+
+
+def landmarks_u8(x: torch.Tensor, mask: torch.Tensor, contour: torch.Tensor, counts: torch.Tensor,
+                 landmarks_count: int = 32, brown_hue_range=(0, 30), brown_s_min: int = 20, brown_v_max: int = 200,
+                 use_lab_brown: bool = False, lab_a_min: int = 125, lab_b_min: int = 125, brown_min_area_px: int = 25,
+                 brown_morph_kernel: int = 3, strict: bool = True):
+    """apply_landmarks_filter (srcs/transform/filters/landmarks.py) for a same-size batch [N,H,W,3] uint8 with the
+    mask [N,H,W], contour [N,K,2] and counts [N] make_mask_u8 gave for it.  Returns (picture [N,H,W,3] uint8, points
+    [N,cap,3] int32 (kind, x, y) with kind 0 border, 1 vein, 2 disease in placement order, counts [N,3] int32, flags
+    [N] int32: bit 0 the image has a contour, else its picture is the input and it has no points; bit 2 an error (a
+    bad contour record or a step bound), which raises unless strict is False).  H, W >= 8; an image must fit one
+    workgroup's LDS (four bit planes, 140 KiB).  The rules: include/leafhip.h (lf_landmarks_u8)."""
+    n, h, w = _hwc(x, "landmarks.x")
+    _chk(mask, _U8, "landmarks.mask", 3)
+    _chk(contour, _I32, "landmarks.contour", 3)
+    _chk(counts, _I32, "landmarks.counts", 1)
+    if tuple(mask.shape) != (n, h, w) or mask.device != x.device:
+        raise ValueError(f"landmarks.mask: expected {[n, h, w]} on {x.device}, got {list(mask.shape)} on {mask.device}")
+    if contour.shape[0] != n or contour.shape[2] != 2 or contour.shape[1] < 1 or tuple(counts.shape) != (n,) \
+            or contour.device != x.device or counts.device != x.device:
+        raise ValueError(f"landmarks: expected contour [{n},K,2] and counts [{n}] on {x.device}, got "
+                         f"{list(contour.shape)} and {list(counts.shape)}")
+    if h < 8 or w < 8:
+        raise ValueError(f"landmarks: a {h} x {w} image is below the 8 x 8 minimum")
+    if not 1 <= int(brown_morph_kernel) <= 31:
+        raise ValueError(f"landmarks: brown_morph_kernel {brown_morph_kernel} outside [1, 31]")
+    landmarks_count = int(landmarks_count)
+    if landmarks_count > 65536:
+        raise ValueError(f"landmarks: landmarks_count {landmarks_count} is over 65536")
+    if 4 * h * ((w + 31) // 32) * 4 + (h + 1) * 4 > 140 * 1024:
+        raise _lib.LeafHipError(f"landmarks: a {h} x {w} image does not fit one workgroup's LDS (four bit planes, "
+                                "140 KiB)")
+    prm = np.array([1 if use_lab_brown else 0, brown_hue_range[0], brown_hue_range[1], brown_s_min, brown_v_max,
+                    lab_a_min, lab_b_min, brown_min_area_px, brown_morph_kernel], dtype=np.int32)
+    wc, wsp = (torch.from_numpy(t).to(x.device) for t in bilateral_tables())
+    lib = _lib.load()
+    cap = int(lib.lf_landmarks_points_cap(landmarks_count))
+    ws = torch.empty(int(lib.lf_landmarks_workspace(n, h, w, landmarks_count)), dtype=_U8, device=x.device)
+    out = torch.empty_like(x)
+    points = torch.empty((n, cap, 3), dtype=_I32, device=x.device)
+    pcounts = torch.empty((n, 3), dtype=_I32, device=x.device)
+    flags = torch.empty(n, dtype=_I32, device=x.device)
+    _lib.call("lf_landmarks_u8", x.data_ptr(), mask.data_ptr(), contour.data_ptr(), counts.data_ptr(),
+              int(contour.shape[1]), prm.ctypes.data, landmarks_count, wc.data_ptr(), wsp.data_ptr(), out.data_ptr(),
+              points.data_ptr(), pcounts.data_ptr(), flags.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(), _stream())
+    if strict and bool((flags & 4).any()):
+        raise _lib.LeafHipError("lf_landmarks_u8: a contour count above the buffer, a point outside the image or a step "
+                                "bound that was hit")
+    return out, points, pcounts, flags
+
+
 def jpeg_fdct_quant_u8(x: torch.Tensor, quality: int = 95, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The pixel half of Image.save(path, quality=quality) (image_utils.py:49-56) for a batch [N,H,W,3] uint8
     : libjpeg's quantised DCT coefficients, int16 [N, ceil(H/16) * ceil(W/16), 6, 64] — per MCU the

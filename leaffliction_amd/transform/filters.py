@@ -8,7 +8,9 @@ extension and the resize back (lf_make_mask_u8).  The other strategies are not p
 reference keeps the candidate whenever a refinement scores lower, so the result is one of the outcomes the
 reference can produce.  `apply_brown_filter` (brown.py) and `apply_roi_filter` (roi.py) run on the GPU too
 (lf_brown_spots_u8, lf_roi_u8), one image at a time or batched on device tensors, and so does `apply_analyze_filter`
-(analyze.py), whose picture is drawn by the project's own integer rules (lf_analyze_overlay_u8).  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
+(analyze.py), whose picture is drawn by the project's own integer rules (lf_analyze_overlay_u8), and
+`apply_landmarks_filter` (landmarks.py: CLAHE, bilateral filter, Canny, Shi-Tomasi corners, greedy point selection),
+whose arithmetic follows the project's own integer rules as well (lf_landmarks_u8).  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
 reproduced — the numbers it draws are."""
 from __future__ import annotations
 
@@ -54,6 +56,7 @@ class TransformConfig:
     lab_a_min: int = 125
     lab_b_min: int = 125
     roi_size: Tuple[int, int] = (256, 256)            # config.yaml:3, (H, W) of apply_roi_filter's canvas
+    landmarks_count: int = 80                         # config.yaml:4
 
 
 def load_config(path) -> TransformConfig:
@@ -296,6 +299,74 @@ def apply_analyze_filter(rgb: np.ndarray, mask: Optional[np.ndarray], contour: O
     c = torch.from_numpy(np.ascontiguousarray(pts.astype(np.int32))).unsqueeze(0).to(x.device)
     counts = torch.tensor([pts.shape[0]], dtype=torch.int32, device=x.device)
     return analyze_filter_batch(x, (md, c, counts), cfg)[0].cpu().numpy()
+
+
+def _landmarks_kwargs(cfg) -> dict:
+    return dict(landmarks_count=int(getattr(cfg, "landmarks_count", 80)), brown_hue_range=tuple(cfg.brown_hue_range),
+                brown_s_min=int(cfg.brown_s_min), brown_v_max=int(cfg.brown_v_max),
+                use_lab_brown=bool(cfg.use_lab_brown), lab_a_min=int(cfg.lab_a_min), lab_b_min=int(cfg.lab_b_min),
+                brown_min_area_px=int(cfg.brown_min_area_px), brown_morph_kernel=int(cfg.brown_morph_kernel))
+
+
+def landmarks_filter_batch(batch, masks, cfg):
+    """apply_landmarks_filter for a same-size batch [N,H,W,3] uint8 on the device.  masks: make_masks_device's tuple
+    (mask, contour, counts[, fallback]) for these images.  Returns (pictures [N,H,W,3] uint8, points [N,cap,3] int32
+    (kind, x, y) with kind 0 border, 1 vein, 2 disease in placement order, counts [N,3] int32), all on the device; an
+    image without a contour keeps its input and has no points (the reference's "Landmarks: no object" caption is not
+    drawn).  The rules: include/leafhip.h (lf_landmarks_u8)."""
+    x = _device_u8(batch, 4, "landmarks_filter_batch.batch")
+    out, points, counts, _flags = ops.landmarks_u8(x, masks[0], masks[1], masks[2], **_landmarks_kwargs(cfg))
+    return out, points, counts
+
+
+def leaf_landmarks(batch, cfg, masks=None):
+    """The pseudo-landmarks of a same-size batch [N,H,W,3] uint8 as data: per image an int32 array [k,3] of (kind, x, y)
+    rows, kind 0 border, 1 vein, 2 disease, in placement order (k = 0 without a contour).  masks: make_masks_device's
+    tuple when the caller has it."""
+    x = _device_u8(batch, 4, "leaf_landmarks.batch")
+    if masks is None:
+        masks = make_masks_device(x, cfg)
+    _out, points, counts = landmarks_filter_batch(x, masks, cfg)
+    pts, k = points.cpu().numpy(), counts.cpu().numpy().sum(axis=1)
+    return [pts[i, :int(k[i])].copy() for i in range(pts.shape[0])]
+
+
+def log_landmarks(b: int, v: int, d: int) -> None:
+    """landmarks.py's summary line."""
+    logging.info(f"Landmarks summary: {b} border + {v} veins + {d} disease points = {b + v + d} total landmarks")
+
+
+def apply_landmarks_filter(rgb: np.ndarray, contour: Optional[np.ndarray], cfg,
+                           make_mask_func: Optional[Callable] = None) -> np.ndarray:
+    """srcs/transform/filters/landmarks.py for one HxWx3 uint8 RGB image: border, vein and disease pseudo-landmarks and
+    the enhanced contour drawn on a copy of the image.  `make_mask_func(rgb)` returns (mask, _), as the reference
+    calls it, and defaults to the GPU make_mask with cfg.  A None contour returns a copy of the image (the reference
+    writes "Landmarks: no object" on it with cv2's font).  A 3-d mask is read through its first channel; a None mask
+    counts as an empty one; the contour ([K,1,2] or [K,2] (x, y)) must lie inside the image.  Parity unpinned (no
+    cv2): the rules are the project's own, include/leafhip.h."""
+    if contour is None:
+        return np.array(rgb, copy=True)
+    pts = np.asarray(contour).reshape(-1, 2)
+    if pts.shape[0] == 0:
+        raise ValueError("apply_landmarks_filter: empty contour")
+    x = _rgb_batch(rgb)
+    h, w = x.shape[1:3]
+    if (pts[:, 0] < 0).any() or (pts[:, 0] >= w).any() or (pts[:, 1] < 0).any() or (pts[:, 1] >= h).any():
+        raise ValueError("apply_landmarks_filter: contour points outside the image")
+    mask, _ = make_mask_func(rgb) if make_mask_func is not None else make_mask(rgb, cfg)
+    if mask is None:
+        leaf = np.zeros((h, w), bool)
+    else:
+        m = np.asarray(mask)
+        leaf = (m > 0) if m.ndim == 2 else (m[..., 0] > 0)
+    if leaf.shape != (h, w):
+        raise ValueError(f"apply_landmarks_filter: mask {leaf.shape} does not match the image {(h, w)}")
+    md = torch.from_numpy(np.ascontiguousarray(leaf.astype(np.uint8) * 255)).unsqueeze(0).to(x.device)
+    c = torch.from_numpy(np.ascontiguousarray(pts.astype(np.int32))).unsqueeze(0).to(x.device)
+    counts = torch.tensor([pts.shape[0]], dtype=torch.int32, device=x.device)
+    out, _points, pc = landmarks_filter_batch(x, (md, c, counts), cfg)
+    log_landmarks(*(int(v) for v in pc[0].cpu().tolist()))
+    return out[0].cpu().numpy()
 
 
 # One row of leaf measurements: the CSV columns of `Transformation --measure` after `file`.  Integer columns hold
