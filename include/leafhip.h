@@ -907,6 +907,30 @@ int lf_conv2d_wgrad_bn_f32(const float* x, const float* g, const float* bn_y,
                            int ksize, const float* in_scale, const float* in_shift, int in_relu,
                            void* workspace, size_t ws_bytes, lf_stream_t stream);
 
+/* Depthwise 3x3 convolution, padding "same", depth multiplier 1, no bias: the first half of the separable
+ * conv block (srcs/model/cnn.py:22-25, SeparableConv2D); the pointwise half is lf_conv2d_* with ksize == 1.
+ *   y[n][c][i][j] = sum_t w[c][t] * a[n][c][i+ky-1][j+kx-1],  t = ky*3+kx,  w [C][9],
+ * a = relu?(x*in_scale[c]+in_shift[c]) being the producer's BatchNorm(+ReLU) applied while loading (in_scale /
+ * in_shift both null or both set); a tap outside the image adds 0, not relu(in_shift).  x, y [n][c][h][w]; any
+ * h, w >= 1 (16-byte rows where w % 4 == 0 and x, y are 16-byte aligned, single columns otherwise).
+ * Constraints: n <= 65535, h*w < 2^30, n*c*w < 2^31.  y must not overlap x.
+ * The reference hands the block's kernel_regularizer to this layer, for which Keras has no such argument: this
+ * project reads it as L2 on BOTH kernels of a separable conv block, depthwise and pointwise, and on nothing else. */
+int lf_dwconv3x3_f32(const float* x, const float* w, float* y, int n, int c, int h, int wd,
+                     const float* in_scale, const float* in_shift, int in_relu, lf_stream_t stream);
+/* Both gradients of lf_dwconv3x3_f32 (cnn.py:22-25) in one pass over dy and x:
+ *   dw[c][t]       = sum_{n,i,j} dy[n][c][i][j] * a[n][c][i+ky-1][j+kx-1]        (overwritten)
+ *   dx[n][c][i][j] (+)= sum_t w[c][t] * dy[n][c][i-ky+1][j-kx+1]
+ * dx is the gradient with respect to a, not x (the producer's BatchNorm backward applies the ReLU mask), as with
+ * the dense input-gradient convolution; accumulate != 0 adds into dx; dx may be null (the stem), and then nothing
+ * but dw and the workspace is written.  dw is deterministic: every lane leaves its nine partial sums in the
+ * workspace (lf_dwconv3x3_bwd_workspace(...) bytes, 4-byte aligned) and a second kernel adds them in a fixed
+ * order; no float atomics.  Constraints as for the forward; dx must not overlap x or dy. */
+size_t lf_dwconv3x3_bwd_workspace(int n, int c, int h, int wd);
+int lf_dwconv3x3_bwd_f32(const float* x, const float* w, const float* dy, float* dx, int accumulate, float* dw,
+                         int n, int c, int h, int wd, const float* in_scale, const float* in_shift, int in_relu,
+                         void* workspace, size_t ws_bytes, lf_stream_t stream);
+
 /* ---- input stage ----------------------------------------------------------- */
 /* u8 HWC -> f32 NCHW with the model's train-time augmentation fused (cnn.py:74-86):
  * keras RandomFlip("horizontal") -> RandomRotation (bilinear, fill_mode="reflect") ->

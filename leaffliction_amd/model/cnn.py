@@ -10,6 +10,9 @@ Data layout in HBM: activations NCHW f32; every trainable tensor lives in ONE fl
 buffer (`flat_p`, with matching `flat_g`, Adam `flat_m`/`flat_v` and `flat_ema`), so the
 optimizer is two launches and data-parallel training all-reduces one bucket.  Conv kernels
 are stored "IKO" [Cin, k*k, Cout]; `get_weights()` converts to keras HWIO.
+
+`separable=True` (cnn.py:22-25) replaces every conv of a conv block by a depthwise 3x3 (weights [Cin, 9]) and a
+pointwise 1x1 ([Cin, 1, Cout]); that model runs in fp32.
 """
 from __future__ import annotations
 
@@ -30,17 +33,26 @@ BN_EPS = 1e-3
 NORM_EPS = 1e-7
 
 
-def _specs(num_classes: int, widths: List[int], use_se: bool):
+L2_KINDS = ("w3", "dw", "pw")   # the kernels of a conv block: they carry its kernel_regularizer
+
+
+def _specs(num_classes: int, widths: List[int], use_se: bool, separable: bool = False):
     """Trainable tensors in creation order: (name, shape, kind).  kind 'w3' = 3x3 kernel
-    (carries the L2 kernel_regularizer, cnn.py:21-29), 'w1' = 1x1 kernel, 'vec', 'dense'."""
-    out = [("stem.w", (3, 9, widths[0]), "w3"), ("stem.bn.gamma", (widths[0],), "vec"),
-           ("stem.bn.beta", (widths[0],), "vec")]
+    (carries the L2 kernel_regularizer, cnn.py:21-29), 'w1' = 1x1 kernel, 'vec', 'dense'.  separable: the 3x3
+    kernel X.w of every conv block is X.dw [Cin,9] (kind 'dw') then X.pw [Cin,1,Cout] (kind 'pw'), Keras'
+    depthwise_kernel and pointwise_kernel; the block's regularizer is read as applying to both."""
+    def conv3(name, cin, cout):
+        if separable:
+            return [(name + ".dw", (cin, 9), "dw"), (name + ".pw", (cin, 1, cout), "pw")]
+        return [(name + ".w", (cin, 9, cout), "w3")]
+
+    out = conv3("stem", 3, widths[0]) + [("stem.bn.gamma", (widths[0],), "vec"),
+                                         ("stem.bn.beta", (widths[0],), "vec")]
     cin = widths[0]
     for i, f in enumerate(widths):
         p = f"s{i}."
-        out += [(p + "c1.w", (cin, 9, f), "w3"), (p + "bn1.gamma", (f,), "vec"),
-                (p + "bn1.beta", (f,), "vec"), (p + "c2.w", (f, 9, f), "w3"),
-                (p + "bn2.gamma", (f,), "vec"), (p + "bn2.beta", (f,), "vec")]
+        out += conv3(p + "c1", cin, f) + [(p + "bn1.gamma", (f,), "vec"), (p + "bn1.beta", (f,), "vec")]
+        out += conv3(p + "c2", f, f) + [(p + "bn2.gamma", (f,), "vec"), (p + "bn2.beta", (f,), "vec")]
         if use_se:
             out += [(p + "se.w1", (f, f // 8), "w1"), (p + "se.b1", (f // 8,), "vec"),
                     (p + "se.w2", (f // 8, f), "w1"), (p + "se.b2", (f,), "vec")]
@@ -104,13 +116,6 @@ class LeafCNN:
                  drop_top: float = 0.40, l2_reg: float = 0.0, separable: bool = False,
                  augment: bool = True, use_se: bool = True, seed: int = 0,
                  device: Optional[torch.device] = None) -> None:
-        if separable:
-            # cnn.py:22-25 passes `kernel_regularizer=` to keras.layers.SeparableConv2D, which
-            # Keras 3 (requirements: keras>=3) rejects as an unrecognised keyword with a
-            # ValueError — `train --separable` therefore logs the error and returns in the
-            # reference too (train.py:471-473).  Same outcome here, no depthwise kernels.
-            raise ValueError("--separable: SeparableConv2D is not available (the reference's "
-                             "own call is rejected by Keras 3; no depthwise path is provided)")
         if not torch.cuda.is_available():
             raise RuntimeError("LeafCNN needs a HIP device: there is no CPU fallback")
         self.num_classes = int(num_classes)
@@ -121,12 +126,20 @@ class LeafCNN:
         self.l2_reg = float(l2_reg or 0.0)
         self.augment = bool(augment)
         self.use_se = bool(use_se)
+        # cnn.py:22-25: SeparableConv2D in every conv block (the reference's own call passes kernel_regularizer=,
+        # which Keras 3 rejects; here the model exists, and l2_reg is read as applying to both of its kernels)
+        self.separable = bool(separable)
         self.infer_dtype = os.environ.get("LEAFFLICTION_INFER_DTYPE", "f32")  # see set_inference_dtype
         if self.infer_dtype not in ("f32", "bf16"):
             raise ValueError("LEAFFLICTION_INFER_DTYPE must be f32 or bf16")
         self.train_dtype = os.environ.get("LEAFFLICTION_TRAIN_DTYPE", "f32")  # see set_training_dtype
         if self.train_dtype not in ("f32", "bf16"):
             raise ValueError("LEAFFLICTION_TRAIN_DTYPE must be f32 or bf16")
+        if self.separable and "bf16" in (self.infer_dtype, self.train_dtype):
+            import logging
+            logging.getLogger(__name__).warning(
+                "separable leaf_cnn runs in fp32: LEAFFLICTION_TRAIN_DTYPE / LEAFFLICTION_INFER_DTYPE=bf16 ignored")
+            self.infer_dtype = self.train_dtype = "f32"
         # (the data-parallel gradient bucket's dtype is train.parallel.DataParallel.bucket_dtype)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.norm = Normalization() if use_norm else None
@@ -139,10 +152,14 @@ class LeafCNN:
         cap_torch_threads()   # the per-step host draws are small CPU tensor ops: see there
 
         # ---- flat parameter / state storage
-        self.specs = _specs(self.num_classes, self.widths, self.use_se)
+        self.specs = _specs(self.num_classes, self.widths, self.use_se, self.separable)
+        # The separable model starts every tensor on a 16-byte boundary (its [3,9] stem kernel would otherwise leave
+        # every 1x1 kernel after it unaligned, off the convolutions' 16-byte paths): the few padding floats count to
+        # the tensor before them for the optimizer and stay zero in every flat buffer.  Dense: tightly packed.
+        pad = 4 if self.separable else 1
         offs, off = [0], 0
         for _n, shape, _k in self.specs:
-            off += int(np.prod(shape))
+            off += -(-int(np.prod(shape)) // pad) * pad
             offs.append(off)
         self.n_params = off
         dev = self.device
@@ -152,13 +169,14 @@ class LeafCNN:
         self.flat_v = torch.zeros_like(self.flat_p)
         self.flat_ema = torch.zeros_like(self.flat_p)
         self.offsets = torch.tensor(offs, dtype=torch.int64, device=dev)
-        self.l2_vec = torch.tensor([self.l2_reg if k == "w3" else 0.0 for _n, _s, k in self.specs],
+        self.l2_vec = torch.tensor([self.l2_reg if k in L2_KINDS else 0.0 for _n, _s, k in self.specs],
                                    dtype=torch.float32, device=dev)
-        self.max_count = max(int(np.prod(s)) for _n, s, _k in self.specs)
+        self.max_count = max(e - b for b, e in zip(offs[:-1], offs[1:]))
         self.norms_ws = torch.empty(len(self.specs), dtype=torch.float32, device=dev)
         self.p: Dict[str, torch.Tensor] = {}
         self.g: Dict[str, torch.Tensor] = {}
-        for (name, shape, _k), b, e in zip(self.specs, offs[:-1], offs[1:]):
+        for (name, shape, _k), b in zip(self.specs, offs[:-1]):
+            e = b + int(np.prod(shape))
             self.p[name] = self.flat_p[b:e].view(shape)
             self.g[name] = self.flat_g[b:e].view(shape)
         self.bn_layers = _bn_layers(self.widths)
@@ -194,7 +212,9 @@ class LeafCNN:
             if kind == "vec":
                 self.p[name].fill_(1.0 if name.endswith("gamma") else 0.0)
                 continue
-            if len(shape) == 3:
+            if kind == "dw":     # keras' fans of a depthwise kernel (3,3,cin,1): receptive field x (cin, 1)
+                fan_in, fan_out = 9 * shape[0], 9
+            elif len(shape) == 3:
                 fan_in, fan_out = shape[0] * shape[1], shape[2] * shape[1]
             else:
                 fan_in, fan_out = shape
@@ -357,11 +377,20 @@ class LeafCNN:
         return nn.conv2d_wino_filters(self.p[wname], dgrad, out=u)
 
     def _conv_bn(self, x, wname: str, ksize: int, bn: str, pro, out: torch.Tensor, training: bool,
-                 bf16: bool = False):
+                 bf16: bool = False, sv: Optional[Dict[str, Any]] = None):
         """Conv2D -> BatchNormalization: returns (y, stats[4,C]).  In training the batch
         statistics come out of the convolution's epilogue (no second pass over y); bf16: the
-        training step on bf16 storage (packed weights from _prep_bf16_weights)."""
+        training step on bf16 storage (packed weights from _prep_bf16_weights).
+        A separable model's 3x3 convs are depthwise 3x3 (which applies the prologue) into a pass buffer t, then
+        the pointwise 1x1 through the same launchers; t stays in sv[X.t] for the pointwise weight gradient."""
         P = self.p
+        if self.separable and ksize == 3:
+            base = wname[:-2]
+            t = nn.dwconv3x3(x, P[base + ".dw"], pro[0], pro[1], pro[2],
+                             out=self._buf(x.shape[0], base + ".t", tuple(x.shape)))
+            if sv is not None:
+                sv[base + ".t"] = t
+            x, wname, ksize, pro = t, base + ".pw", 1, (None, None, False)
         if training:
             st = self.stats[bn]
             bn_args = (P[bn + ".gamma"], P[bn + ".beta"], self.s[bn + ".mean"], self.s[bn + ".var"], st,
@@ -459,6 +488,8 @@ class LeafCNN:
         (train.py:53-117).  The training step's precision is set_training_dtype's."""
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"inference dtype must be 'f32' or 'bf16', got {dtype!r}")
+        if dtype == "bf16" and self.separable:
+            raise ValueError("bf16 inference: the separable model runs in fp32 (no bf16 depthwise kernels)")
         self.infer_dtype = dtype
 
     def set_training_dtype(self, dtype: str) -> None:
@@ -471,6 +502,8 @@ class LeafCNN:
         _bf16_storage_ok states the rule."""
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"training dtype must be 'f32' or 'bf16', got {dtype!r}")
+        if dtype == "bf16" and self.separable:
+            raise ValueError("bf16 training: the separable model runs in fp32 (no bf16 depthwise kernels)")
         if dtype == "bf16" and not (self.use_se and self._bf16_storage_ok(self.img_size, self.img_size)):
             raise ValueError("bf16 training needs use_se, widths of 16 or a multiple of 32 (16 next to 16 or 32 "
                              "only) and every stage a multiple of 4 pixels wide, 8 at 16 channels "
@@ -508,7 +541,7 @@ class LeafCNN:
         # Activations a = relu(BN(y)) are never materialised: every consumer (the next conv,
         # wgrad, GAP, the residual tail, BN backward) applies scale/shift(+ReLU) while it reads y.
         y, st = self._conv_bn(x0, "stem.w", 3, "stem.bn", (None, None, False),
-                              B("stem.y", (n, self.widths[0], h, w)), training, bf16)
+                              B("stem.y", (n, self.widths[0], h, w)), training, bf16, sv)
         sv["stem.y"] = y
         xin, xin_st = y, st  # block input = relu(xin*xin_st[2]+xin_st[3]) (None = already final)
         cin = self.widths[0]
@@ -516,9 +549,9 @@ class LeafCNN:
             p = f"s{i}."
             pro = (xin_st[2], xin_st[3], True) if xin_st is not None else (None, None, False)
             y1, st1 = self._conv_bn(xin, p + "c1.w", 3, p + "bn1", pro, B(p + "y1", (n, f, h, w)),
-                                    training, bf16)
+                                    training, bf16, sv)
             y2, st2 = self._conv_bn(y1, p + "c2.w", 3, p + "bn2", (st1[2], st1[3], True),
-                                    B(p + "y2", y1.shape), training, bf16)
+                                    B(p + "y2", y1.shape), training, bf16, sv)
             s = None
             if self.use_se:
                 # the squeeze pass also leaves BN2's ReLU-mask sums for the backward pass
@@ -626,6 +659,9 @@ class LeafCNN:
                           G[p + "se.w1"], G[p + "se.b1"], G[p + "se.w2"], G[p + "se.b2"],
                           dm_scale=1.0 / (h * w))
                 add_nc = dm
+            if self.separable:
+                dp = self._backward_block_separable(sv, i, B, gA, gB, gC, s, add_nc, psum, psum_p)
+                continue
             # conv2 branch: dz2 = (dr*s + dm/HW) * [a2 > 0];
             # BN2 backward + conv2 weight gradient: dy2 is formed inside the wgrad kernel (-> gB)
             bn_bwd_wgrad(y1, gA, y2, st2, P[p + "bn2.gamma"], G[p + "bn2.gamma"],
@@ -656,10 +692,57 @@ class LeafCNN:
             sv["bwd_dp"] = dp   # the gradient that enters stage 0: where part 1 picks up
             return
         # stem: dp is the gradient wrt relu(BN(stem.y))
+        if self.separable:
+            dys = B("stem.dy", sv["stem.y"].shape)
+            self._sep_conv_bwd("stem", sv["x0"], (None, None, False), sv["stem.t"], dp, sv["stem.y"], "stem.bn", dys,
+                               B("stem.dt", sv["x0"].shape), None, False)
+            return
         # the stem has no input gradient: its BN backward exists only inside the wgrad kernel
         bn_bwd_wgrad(sv["x0"], dp, sv["stem.y"], self.stats["stem.bn"], P["stem.bn.gamma"],
                      G["stem.bn.gamma"], G["stem.bn.beta"], True, 3, G["stem.w"], None,
                      tile_sums=stem_sums)
+
+    def _sep_conv_bwd(self, base: str, x, pro, t, g, y, bn: str, dy_buf, dt_buf, dx, accumulate: bool,
+                      **sums) -> None:
+        """Backward of one separable conv + BatchNorm(+ReLU) of the fp32 step: g = the gradient wrt relu(BN(y)),
+        y = pointwise(t), t = depthwise(x') with x' = the prologue `pro` on x.  BN backward + the pointwise weight
+        gradient (dy -> dy_buf; the BN sums from `sums`: plane_g / plane_m / alpha_nc / add_nc, or else from g and
+        y), the pointwise input gradient (-> dt_buf), then both depthwise gradients: G[X.dw], and dx (+)= the
+        gradient wrt x' (dx None: the stem).  The BN-sums epilogues of the dense input-gradient kernels have no
+        counterpart in the depthwise kernel: the next BatchNorm backward takes its sums in a pass of its own."""
+        P, G = self.p, self.g
+        nn.bn_bwd_wgrad(t, g, y, self.stats[bn], P[bn + ".gamma"], G[bn + ".gamma"], G[bn + ".beta"], True, 1,
+                        G[base + ".pw"], dy_buf, **sums)
+        self._dgrad(dy_buf, base + ".pw", 1, dt_buf, False)
+        nn.dwconv3x3_bwd(x, P[base + ".dw"], dt_buf, G[base + ".dw"], dx, accumulate, pro[0], pro[1], pro[2])
+
+    def _backward_block_separable(self, sv, i: int, B, gA, gB, gC, s, add_nc, psum, psum_p):
+        """backward()'s stage i from the block tail's outputs on, for the separable model (gA = dr, psum / psum_p
+        = the plane sums of BN2 / the projection's BN).  Returns the gradient wrt the block's input."""
+        P, G = self.p, self.g
+        f = self.widths[i]
+        cin = self.widths[i - 1] if i > 0 else self.widths[0]
+        p = f"s{i}."
+        xin, xin_st, y1, y2 = (sv[p + k] for k in ("xin", "xin_st", "y1", "y2"))
+        pro = (xin_st[2], xin_st[3], True) if xin_st is not None else (None, None, False)
+        st1 = self.stats[p + "bn1"]
+        # conv2: dz2 = (dr*s + dm/HW) * [a2 > 0]; da1 -> gC
+        self._sep_conv_bwd(p + "c2", y1, (st1[2], st1[3], True), sv[p + "c2.t"], gA, y2, p + "bn2", gB,
+                           B(p + "dt2", y1.shape), gC, False, alpha_nc=s, add_nc=add_nc, plane_g=psum,
+                           plane_m=sv[p + "msum"] if self.use_se else None)
+        if cin != f:
+            yp, stp = sv[p + "yp"], self.stats[p + "bnp"]
+            dyp = B(p + "dyp", y1.shape)
+            nn.bn_bwd_wgrad(xin, gA, yp, stp, P[p + "bnp.gamma"], G[p + "bnp.gamma"], G[p + "bnp.beta"], False, 1,
+                            G[p + "proj.w"], dyp, pro[0], pro[1], pro[2], plane_g=psum_p)
+            dx = B(p + "dx", xin.shape)
+            self._dgrad(dyp, p + "proj.w", 1, dx, False)
+        else:
+            dx = gA  # identity shortcut: dx starts as dr
+        # conv1: dx += the gradient through the main path
+        self._sep_conv_bwd(p + "c1", xin, pro, sv[p + "c1.t"], gC, y1, p + "bn1", gB, B(p + "dt1", xin.shape), dx,
+                           True)
+        return dx
 
     def _dgrad(self, gy: torch.Tensor, wname: str, k: int, out: torch.Tensor, bf16: bool,
                accumulate: bool = False, mask=None):
@@ -852,7 +935,7 @@ class LeafCNN:
         tot = torch.zeros((), dtype=torch.float32, device=self.device)
         if self.l2_reg > 0:
             for name, _s, kind in self.specs:
-                if kind == "w3":
+                if kind in L2_KINDS:
                     tot = tot + self.l2_reg * (self.p[name] ** 2).sum()
         return tot
 
@@ -1046,7 +1129,9 @@ class LeafCNN:
             return self.s[name[:-16] + ".var"].cpu().numpy()
         t = self.p[name].detach().cpu()
         kind = next(k for n_, _s, k in self.specs if n_ == name)
-        if kind == "w3" or (kind == "w1" and t.dim() == 3):
+        if kind == "dw":   # keras depthwise_kernel [3,3,Cin,1]
+            return t.view(t.shape[0], 3, 3, 1).permute(1, 2, 0, 3).contiguous().numpy()
+        if kind in ("w3", "pw") or (kind == "w1" and t.dim() == 3):
             cin, taps, cout = t.shape
             k = int(round(math.sqrt(taps)))
             return t.view(cin, k, k, cout).permute(1, 2, 0, 3).contiguous().numpy()
@@ -1071,7 +1156,9 @@ class LeafCNN:
             else:
                 t = torch.from_numpy(arr)
                 dst = self.p[name]
-                if t.dim() == 4 and dst.dim() == 3:      # HWIO -> IKO
+                if t.dim() == 4 and dst.dim() == 2 and dst.shape[1] == 9 and tuple(t.shape[:2]) == (3, 3):
+                    t = t.permute(2, 0, 1, 3).reshape(t.shape[2], 9)   # depthwise [3,3,Cin,1] -> [Cin,9]
+                elif t.dim() == 4 and dst.dim() == 3:      # HWIO -> IKO
                     k = t.shape[0]
                     t = t.permute(2, 0, 1, 3).reshape(t.shape[2], k * k, t.shape[3])
                 elif t.dim() == 4 and dst.dim() == 2:    # [1,1,in,out] -> [in,out]
@@ -1092,7 +1179,7 @@ class LeafCNN:
         return {"name": self.name, "num_classes": self.num_classes, "img_size": self.img_size,
                 "use_norm": self.norm is not None, "widths": self.widths,
                 "drop_block": self.drop_block, "drop_top": self.drop_top, "l2_reg": self.l2_reg,
-                "separable": False, "augment": self.augment, "use_se": self.use_se}
+                "separable": self.separable, "augment": self.augment, "use_se": self.use_se}
 
     def save(self, path, format: str = "npz") -> None:
         """`leaf_cnn.keras`: a zip with config.json / metadata.json (keras-v3 member names) and
@@ -1104,6 +1191,9 @@ class LeafCNN:
         path.parent.mkdir(parents=True, exist_ok=True)
         names = self.weight_names()
         if format == "keras":
+            if self.separable:
+                raise ValueError("save(format='keras'): the Keras-layout writer holds the dense leaf_cnn only, not "
+                                 "the separable model (use the default npz archive)")
             from . import keras_format
             keras_format.write_archive(path, self.config(), names, self.get_weights())
             return
@@ -1152,7 +1242,7 @@ def load_model(path) -> LeafCNN:
     model = LeafCNN(num_classes=cfg["num_classes"], img_size=cfg["img_size"],
                     use_norm=cfg["use_norm"], widths=cfg["widths"], drop_block=cfg["drop_block"],
                     drop_top=cfg["drop_top"], l2_reg=cfg["l2_reg"], augment=cfg["augment"],
-                    use_se=cfg["use_se"])
+                    use_se=cfg["use_se"], separable=bool(cfg.get("separable", False)))
     keys = sorted(data.files)
     if [k.split(":", 1)[1] for k in keys] != meta["weight_names"]:
         raise ValueError(f"{path}: model.weights.npz does not hold the tensors metadata.json lists")

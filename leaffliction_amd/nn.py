@@ -491,6 +491,52 @@ def bn_bwd_wgrad(x: torch.Tensor, g: torch.Tensor, y_bn: torch.Tensor, stats: to
     return dy_out
 
 
+def _dw_weights(who: str, w_c9: torch.Tensor, c: int) -> None:
+    _chk(w_c9, _F32, f"{who}.w", 2)
+    if tuple(w_c9.shape) != (c, 9):
+        raise ValueError(f"{who}.w: expected [{c},9], got {tuple(w_c9.shape)}")
+
+
+def dwconv3x3(x: torch.Tensor, w_c9: torch.Tensor, in_scale=None, in_shift=None, in_relu: bool = False,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depthwise 3x3 convolution, padding "same": y[n,c] = conv(x'[n,c], w[c]); x' = relu?(x*in_scale[c]+in_shift[c])
+    if a prologue is given.  x [N,C,H,W] f32, w_c9 [C,9] (tap = ky*3+kx) -> y [N,C,H,W]."""
+    _chk(x, _F32, "dwconv3x3.x", 4)
+    n, c, h, w = x.shape
+    _dw_weights("dwconv3x3", w_c9, c)
+    _prologue("dwconv3x3", in_scale, in_shift, c)
+    out = _act_out("dwconv3x3", out, (n, c, h, w), (_F32,), _F32, x.device)
+    _lib.call("lf_dwconv3x3_f32", x.data_ptr(), w_c9.data_ptr(), out.data_ptr(), n, c, h, w, _ptr(in_scale),
+              _ptr(in_shift), 1 if in_relu else 0, _stream())
+    return out
+
+
+def dwconv3x3_bwd(x: torch.Tensor, w_c9: torch.Tensor, dy: torch.Tensor, dw_out: torch.Tensor,
+                  dx_out: Optional[torch.Tensor] = None, accumulate: bool = False, in_scale=None, in_shift=None,
+                  in_relu: bool = False):
+    """Both gradients of dwconv3x3 in one pass: dw_out [C,9] = sum dy * x' (overwritten, deterministic), and, when
+    dx_out is given, dx_out (+)= conv(dy, flipped w), the gradient wrt x' (accumulate: added into dx_out).
+    Returns (dw_out, dx_out)."""
+    who = "dwconv3x3_bwd"
+    _chk(x, _F32, f"{who}.x", 4)
+    _chk(dy, _F32, f"{who}.dy", 4)
+    n, c, h, w = x.shape
+    if dy.shape != x.shape:
+        raise ValueError(f"{who}: x and dy must share their shape")
+    _dw_weights(who, w_c9, c)
+    _dw_weights(f"{who}.dw_out", dw_out, c)
+    _prologue(who, in_scale, in_shift, c)
+    if dx_out is None and accumulate:
+        raise ValueError(f"{who}: accumulate needs dx_out")
+    if dx_out is not None:
+        _act_out(who, dx_out, (n, c, h, w), (_F32,), None, x.device)
+    ws = _workspace(_lib.load().lf_dwconv3x3_bwd_workspace(n, c, h, w), x.device)
+    _lib.call("lf_dwconv3x3_bwd_f32", x.data_ptr(), w_c9.data_ptr(), dy.data_ptr(), _ptr(dx_out),
+              1 if accumulate else 0, dw_out.data_ptr(), n, c, h, w, _ptr(in_scale), _ptr(in_shift),
+              1 if in_relu else 0, ws.data_ptr(), ws.numel(), _stream())
+    return dw_out, dx_out
+
+
 # ---------------------------------------------------------------------------
 # non-conv layers
 # ---------------------------------------------------------------------------

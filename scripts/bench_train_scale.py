@@ -2,8 +2,9 @@
 mixed precision (MI355X only): what `train --SCALE` runs per step once the loader keeps up.  A uniform uint8 batch at
 224 x 224 goes through `LeafCNN.train_step` with the HIP graph on (steps one and two run eagerly, the third records);
 prints one JSON line with ms per step and img/s.
-usage: python scripts/bench_train_scale.py --scale tiny|small|base --dtype f32|bf16 [--batch 256] [--steps 20]
-       [--warmup 5]"""
+usage: python scripts/bench_train_scale.py --scale tiny|small|base --dtype f32|bf16 [--separable] [--batch 256]
+       [--steps 20] [--warmup 5]
+--separable: the depthwise-separable network of `train --separable` (fp32 only)."""
 import argparse
 import json
 import sys
@@ -23,6 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", choices=("tiny", "small", "base"), default="tiny")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="bf16")
+    ap.add_argument("--separable", action="store_true")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -30,7 +32,7 @@ def main():
     dev = torch.device("cuda:0")
     widths, drop_block, drop_top = get_model_parameters(a.scale)
     model = LeafCNN(num_classes=CLASSES, img_size=IMG, widths=widths, drop_block=drop_block, drop_top=drop_top,
-                    l2_reg=1e-4, augment=True, use_se=True, seed=42, device=dev)
+                    l2_reg=1e-4, augment=True, use_se=True, seed=42, device=dev, separable=a.separable)
     model.norm.mean[:] = 0.5       # statistics of the synthetic uniform data
     model.norm.variance[:] = 1.0 / 12.0
     model.set_training_dtype(a.dtype)   # raises where the preset has no mixed-precision step
@@ -45,7 +47,8 @@ def main():
         _p, loss = model.train_step(x, y, 1e-3)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    print(json.dumps({"bench": "train_scale", "scale": a.scale, "widths": widths, "dtype": model.train_dtype,
+    print(json.dumps({"bench": "train_scale", "scale": a.scale, "widths": widths, "separable": a.separable,
+                      "dtype": model.train_dtype,
                       "batch": a.batch, "steps": a.steps, "graph": any(st["graph"] is not None
                                                                           for st in model._graphs.values()),
                       "ms_per_step": round(dt * 1e3, 3), "img_per_s": round(a.batch / dt, 1),
