@@ -738,6 +738,57 @@ int lf_cam_maps(const void* feat, int feat_bf16, const float* w, const int32_t* 
 int lf_cam_overlay_u8(const uint8_t* img, const float* cam, const float* peak, uint8_t* out, int n, int hh, int ww,
                       int h, int wd, int m, int slot, float alpha, lf_stream_t stream);
 
+/* ---- Text and canvas: the pictures that carry titles (Transformation's mosaic, create_mosaic in
+ * srcs/cli/Transformation.py; predict's montage, PredictionVisualizer.create_montage).  The reference writes its text
+ * with cv2.putText (Hershey) and PIL's ImageDraw; neither is available, so the rules below are this project's own
+ * integer rules and claim no pixel parity with either.  tests/text_ref.py and tests/canvas_ref.py restate them in
+ * numpy; the kernels match them bit for bit.
+ *
+ * Text.  The font is the project's 5x7 bitmap font (csrc/lf_font5x7.h): 95 glyphs, ASCII 0x20..0x7E, 7 bytes per
+ * glyph, one per row, top row first, bit 4 the leftmost of 5 columns; a character is drawn into a cell 6 columns wide
+ * (one blank column of advance) and 7 rows high; a byte outside 0x20..0x7E draws as '?'.
+ * lf_font5x7 (HOST): copies the 95*7 bytes of the table to `out`.
+ *
+ * lf_draw_text_u8: n_items strings drawn in place into img [N][H][W][3] uint8, one launch for all of them.
+ *   items   [n_items][8] int32 on the device: {image, x, y, first, length, colour, scale, first_group};
+ *           the string is chars[first .. first + length), colour = r | g << 8 | b << 16, 1 <= scale <= 8,
+ *           0 <= length <= 4096; the table is ordered by image (ascending); first_group is the running sum of
+ *           ceil(6*scale*length * 7*scale / 256) over the strings before it (the workgroup the string's box starts at);
+ *   items_host  HOST copy of items: every field is checked against the above, the image index against [0, N) and
+ *           the characters against chars_bytes, before anything is launched (LF_ERR_INVALID otherwise);
+ *   chars   the bytes of all strings on the device.
+ * Pixel rule for a string s of length L at origin (x, y) with scale k: with u = px - x and v = py - y, pixel
+ * (px, py) is painted iff 0 <= v < 7k, 0 <= u < 6kL, (u mod 6k)/k < 5 and the bit of row v/k, column (u mod 6k)/k of
+ * glyph s[u/(6k)] is set.  A painted pixel takes the colour (opaque); nothing else is written.  Pixels outside the
+ * image are dropped; negative origins are legal.  Where strings of one image overlap, the string later in the table
+ * wins whatever order the hardware runs them in: a lane writes only if no later string of its image paints the pixel.
+ * A table of empty strings launches nothing.
+ *
+ * Canvas.  lf_canvas_tiles_u8: out [N][OH][OW][3] uint8 composed from T source batches in one launch.
+ *   plan    int32 block on the device, plan_ints long: T tile descriptors of 12 ints, then the shade rectangles of
+ *           6 ints, then the axis tables;  plan_host is its HOST copy, checked in full before the launch.
+ *   tile    {dst_x, dst_y, dst_w, dst_h, src_h, src_w, channels, xtab, ytab, ptr_lo, ptr_hi, flags}: source t is
+ *           [N][src_h][src_w][channels] uint8 at the device address ptr_hi:ptr_lo, channels 3 or 1 (gray, replicated);
+ *           tiles lie inside the canvas and do not overlap; at most 64.  xtab / ytab are the positions in the plan of
+ *           the tile's axis tables, dst_w and dst_h entries of {i, k}.  flags bit 0: the tile has its source's size,
+ *           three channels and rows of whole dwords, and may be copied with aligned dword loads.
+ *   table   for destination index d of D over a source length S: pos = (d + 0.5) * S / D - 0.5 in float64,
+ *           i = floor(pos), f = pos - i; i < 0 -> i = 0, f = 0; i >= S - 1 -> i = S - 1, f = 0; k = rint(f * 2048).
+ *           The second tap is min(i + 1, S - 1).
+ *   pixel   (ky0 * (kx0 * a + kx1 * b) + ky1 * (kx0 * c + kx1 * d) + 2^21) >> 22 with k0 = 2048 - k1, a b the two
+ *           taps of row i_y, c d those of the second row, in 32-bit integers.  A tile of its source's own size is an
+ *           exact copy.  A pixel in no tile gets fill = r | g << 8 | b << 16.
+ *   shade   {x, y, w, h, num, den}, 0 <= num <= den <= 65536, at most 64, applied in table order after the tiles to
+ *           every channel of the pixels inside: v' = (v * num + den / 2) / den  (den / 2 and the division truncate).
+ * The kernel finishes runs of four pixels (12 bytes, aligned dword stores) when OW, every dst_x and every dst_w are
+ * multiples of four and out is 4-byte aligned, single pixels otherwise; the bytes are the same.  Integer arithmetic
+ * only, no atomics; two launches give the same bits.  out must not overlap a source. */
+int lf_font5x7(uint8_t* out);
+int lf_draw_text_u8(uint8_t* img, int n, int h, int w, const int32_t* items, const int32_t* items_host, int n_items,
+                    const uint8_t* chars, size_t chars_bytes, lf_stream_t stream);
+int lf_canvas_tiles_u8(uint8_t* out, int n, int oh, int ow, const int32_t* plan, const int32_t* plan_host,
+                       size_t plan_ints, int n_tiles, int n_shades, int fill, lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* A2 — the mixed-precision TRAINING step (bf16 storage, fp32 arithmetic)      */
 /* ------------------------------------------------------------------------- */

@@ -11,7 +11,7 @@ make_mask a second time, on `masked`; ROI = the box drawn on `masked` (or `maske
 Images are decoded on host threads (Pillow, EXIF transpose, RGB), grouped by size, and every stage runs as one
 batched launch over chunks of bounded size; outputs are encoded on the GPU (quality 95, the balancer's encoder).
 Without their switches (below), each with one warning per run and no file: Analyze and Landmarks (PlantCV shape
-analysis, CLAHE / bilateral filtering, goodFeaturesToTrack); not ported: the mosaic (cv2's Hershey text).  Hist is this project's own
+analysis, CLAHE / bilateral filtering, goodFeaturesToTrack) and the mosaic (its titles are cv2's Hershey text).  Hist is this project's own
 matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped.
 
 `--overlays` (a flag of this project) draws Analyze's picture: with Analyze among the types, `<stem>__T_Analyze.jpg` is
@@ -28,6 +28,15 @@ border, vein and disease points and the enhanced contour on the white composite,
 filter, the corner score and the point selection follow the project's own integer rules (include/leafhip.h), not
 cv2's pixels, and an image without a contour is written without the "Landmarks: no object" caption.  The Landmarks
 warning is then not given; without the flag nothing changes.
+
+`--mosaic` (a flag of this project) writes create_mosaic's titled overview, `image<n>_mosaic.jpg` per image (<n> as
+in the default output directory, else the stem), flat in the output directory: "Original" and every picture the run
+produced, in the reference's order Mask, Blur, ROI, Analyze, Landmarks, Hist, Brown, in 300 x 300 cells, three to a
+row, each under a shaded title bar (transform.mosaic_batch: one canvas launch and one text launch per chunk).  The
+cells are resampled and the titles written by the project's own integer rules and 5x7 font (include/leafhip.h), not
+cv2's pixels.  As in the reference the file has no --skip-existing test of its own, and in folder mode two images
+of one name or number in different folders write the same file.  The mosaic warning is then not given; without the
+flag nothing changes.
 
 `--measure [FILE]` writes Analyze's numbers (not its picture) as one CSV table, a row per processed image in path
 order: shape, hull and axes from make_mask's contour (ops.shape_stats), the brown share and the Canny edge count
@@ -153,6 +162,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                    help="Draw Analyze's picture (<stem>__T_Analyze.jpg) by this project's own drawing rules")
     p.add_argument("--landmarks", action="store_true",
                    help="Run the pseudo-landmarks filter (<stem>__T_Landmarks.jpg) by this project's own integer rules")
+    p.add_argument("--mosaic", action="store_true",
+                   help="Write the titled overview image<n>_mosaic.jpg of every image (this project's own resampling "
+                        "and 5x7 font).  The name is flat, as the reference's: in folder mode images of one name or "
+                        "number in different folders write the same file")
     p.add_argument("--measure", nargs="?", const="", default=None, metavar="FILE",
                    help="Write leaf measurements (shape, hull, axes, brown share, edge count) of every processed "
                         "image as CSV (default FILE: measurements.csv in the output directory)")
@@ -312,9 +325,9 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
 
 class _Runner:
     def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor,
-                 measure: bool = False, overlays: bool = False, landmarks: bool = False):
+                 measure: bool = False, overlays: bool = False, landmarks: bool = False, mosaic: bool = False):
         self.types, self.cfg, self.pool = types, cfg, pool
-        self.measure, self.overlays, self.landmarks = measure, overlays, landmarks
+        self.measure, self.overlays, self.landmarks, self.mosaic = measure, overlays, landmarks, mosaic
         self.rows: Dict[Path, List[str]] = {}   # --measure: image path -> CSV cells after `file`
         self.skip_existing, self.overwrite = skip_existing, overwrite
         self.hist = "Hist" in types and _have_matplotlib()
@@ -324,7 +337,8 @@ class _Runner:
                                 "written", t, t)
         if "Hist" in types and not self.hist:
             logging.warning("matplotlib is not available: no Hist output is written")
-        logging.warning("The mosaic is not ported (it needs cv2's Hershey text): no mosaic is written")
+        if not mosaic:
+            logging.warning("The mosaic is not ported (it needs cv2's Hershey text): no mosaic is written")
 
     def _write(self, path: Path, data: bytes, saved: List[Path]) -> None:
         path.parent.mkdir(parents=True, exist_ok=True)
@@ -367,17 +381,41 @@ class _Runner:
                 if t == "Brown":
                     for count, pct, area in res["brown_stats"]:
                         logging.info(f"Brown spots detected: {count} regions, {pct:.1f}% of leaf area ({area} pixels)")
+            hist_dev = None
             if self.hist:
                 counts_h, hist_h = res["hist"]
                 figs = list(self.pool.map(lambda i: render_hist(*hist_numbers(counts_h[i], hist_h[i])),
                                           range(len(chunk))))
                 outs = [d / nm["Hist"] for (_p, d, _a), nm in zip(chunk, names)]
                 todo = [i for i, o in enumerate(outs) if should_write(o, self.skip_existing, self.overwrite)]
+                if self.mosaic:   # the mosaic shows every figure of the chunk: one upload for both uses
+                    hist_dev = torch.from_numpy(np.stack(figs)).to(dev)
                 if todo:
-                    y = torch.from_numpy(np.stack([figs[i] for i in todo])).to(dev)
+                    if hist_dev is None:
+                        y = torch.from_numpy(np.stack([figs[i] for i in todo])).to(dev)
+                    else:
+                        y = hist_dev if len(todo) == len(chunk) else hist_dev[torch.tensor(todo, device=dev)]
                     for i, data in zip(todo, encode_jpeg_batch(y)):
                         self._write(outs[i], data, saved)
+            if self.mosaic:
+                self._mosaics(chunk, x, res, hist_dev, saved)
         return saved
+
+    def _mosaics(self, chunk, x, res, hist_dev, saved: List[Path]) -> None:
+        """create_mosaic for a chunk from the tensors the run already holds, in the reference's insertion order; an
+        image gets a mosaic whenever at least one type produced a picture."""
+        from ..transform.filters import mosaic_batch
+        pictures = {t: res[t] for t in ("Mask", "Blur", "ROI", "Analyze", "Landmarks") if t in res}
+        if hist_dev is not None:
+            pictures["Hist"] = hist_dev
+        if "Brown" in res:
+            pictures["Brown"] = res["Brown"]
+        if not pictures:
+            return
+        for (p, d, _a), data in zip(chunk, encode_jpeg_batch(mosaic_batch(x, pictures))):
+            out = d / f"image{image_number(p.stem)}_mosaic.jpg"
+            self._write(out, data, saved)
+            logging.info("Mosaic saved: %s", out)
 
     def run(self, jobs: List[Tuple[Path, Path]]) -> List[Path]:
         """jobs: (image path, output directory).  Decodes WINDOW files ahead on the host threads; unreadable files
@@ -461,7 +499,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         out_d.mkdir(parents=True, exist_ok=True)
         with ThreadPoolExecutor(_workers(args.workers)) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays, args.landmarks)
+                             args.overlays, args.landmarks, args.mosaic)
             saved = runner.run([(ip, out_d)])
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else out_d / "measurements.csv", [(ip, out_d)],
@@ -487,7 +525,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         jobs = [(p, dst) for p in imgs]
         with ThreadPoolExecutor(n_threads) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays, args.landmarks)
+                             args.overlays, args.landmarks, args.mosaic)
             saved = runner.run(jobs)
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else dst / "measurements.csv", jobs, runner.rows,

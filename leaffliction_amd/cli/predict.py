@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--evaluate ...]`.
+"""`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--montage] [--evaluate ...]`.
 
 Flags, JSON schema (`batch_results` + `summary`), the sampled accuracy gate and the exit
 codes (1 on error, 2 when the gate is never reached) follow srcs/cli/predict.py:17-87,
-305-436,492-563.  Montage / dashboard rendering is presentation and not reproduced.
+305-436,492-563.  The matplotlib batch dashboard is presentation and not reproduced.
+`--montage` (opt-in here; what the reference's single-image mode shows) writes the original beside the masked leaf
+with the prediction under them, composed on the GPU (predict/montage.py; the letters are the project's 5x7 font):
+`<out>/<stem>_prediction.png`, in batch mode `<out>/montage/<the path below image_or_dir>_prediction.jpg`.  It cannot
+be combined with --evaluate or --cam.
 `--cam` (not in the reference) also writes, per image, the model input with the predicted class's activation map
 laid over it: `<out>/<stem>__CAM.jpg`, in batch mode `<out>/cam/<the path below image_or_dir>__CAM.jpg`.
 """
@@ -42,6 +46,9 @@ def parse_args(argv=None):
     p.add_argument("--cam", action="store_true",
                    help="write a class-activation heat map over each model input (<stem>__CAM.jpg)")
     p.add_argument("--cam-alpha", type=float, default=0.6, help="weight of the heat map at its peak (0..1)")
+    p.add_argument("--montage", action="store_true",
+                   help="write the original beside the masked leaf with the prediction under them "
+                        "(<stem>_prediction.png; in batch mode montage/<path>_prediction.jpg)")
     return p.parse_args(argv)
 
 
@@ -49,6 +56,10 @@ def validate_inputs(args):
     image_path, learnings_dir = Path(args.image_path), Path(args.learnings_dir)
     if args.cam and args.evaluate:
         raise ValueError("--cam cannot be combined with --evaluate")
+    if args.montage and args.evaluate:
+        raise ValueError("--montage cannot be combined with --evaluate")
+    if args.montage and args.cam:
+        raise ValueError("--montage cannot be combined with --cam")
     if args.cam and not 0.0 <= args.cam_alpha <= 1.0:
         raise ValueError(f"--cam-alpha must lie in [0, 1], got {args.cam_alpha}")
     if not image_path.exists():
@@ -121,6 +132,37 @@ def cam_target(path: Path, image_dir: Path, output_dir: Path) -> Path:
     across class folders, so the tree is mirrored)."""
     rel = Path(path).relative_to(image_dir)
     return Path(output_dir) / "cam" / rel.parent / (rel.stem + CAM_SUFFIX)
+
+
+MONTAGE_SUFFIX = "_prediction"
+MONTAGE_CHUNK = 64   # montages per canvas, text and JPEG encode launch
+
+
+def montage_target(path: Path, image_dir: Path, output_dir: Path) -> Path:
+    """Where batch mode writes the montage of image_dir/sub/leaf.jpg: output_dir/montage/sub/leaf_prediction.jpg (the
+    tree is mirrored, as cam_target does)."""
+    rel = Path(path).relative_to(image_dir)
+    return Path(output_dir) / "montage" / rel.parent / (rel.stem + MONTAGE_SUFFIX + ".jpg")
+
+
+def montages(predictor, results):
+    """uint8 [n,284,468,3] on the device for results that carry their `original_array`: the masked leaves of the
+    whole list first (grouped by size), then one montage_batch call."""
+    from ..predict.montage import caption_text, montage_batch
+    originals = [r["original_array"] for r in results]
+    processed = predictor.masked_arrays(originals, [r["image_path"] for r in results])
+    return montage_batch(originals, processed, [caption_text(r["top_prediction"], r["confidence"]) for r in results])
+
+
+def write_montages(predictor, results, targets) -> None:
+    """The montage of results[i] -> the JPEG file targets[i] (Transformation.encode_jpeg_batch, quality 95),
+    MONTAGE_CHUNK at a time."""
+    from .Transformation import encode_jpeg_batch
+    for b in range(0, len(results), MONTAGE_CHUNK):
+        part = results[b:b + MONTAGE_CHUNK]
+        for target, data in zip(targets[b:b + MONTAGE_CHUNK], encode_jpeg_batch(montages(predictor, part))):
+            target.parent.mkdir(parents=True, exist_ok=True)
+            target.write_bytes(data)
 
 
 def _item_path(item, image_dir: Path, manifest_path: Optional[Path]) -> Optional[Path]:
@@ -219,6 +261,11 @@ def main(argv=None) -> None:
                 results = predictor.explain_batch_sharded(
                     files, rk, alpha=args.cam_alpha, each=lambda mine: write_cam_overlays(
                         mine, [cam_target(r["image_path"], image_path, Path(args.output_dir)) for r in mine]))
+            elif args.montage:
+                results = predictor.predict_batch_sharded(
+                    files, rk, each=lambda mine: write_montages(
+                        predictor, mine,
+                        [montage_target(r["image_path"], image_path, Path(args.output_dir)) for r in mine]))
             else:
                 results = predictor.predict_batch_sharded(files, rk)
             proc = time.time() - t0
@@ -226,6 +273,8 @@ def main(argv=None) -> None:
                 return
             if args.cam:
                 logger.info("Heat maps saved under: %s", Path(args.output_dir) / "cam")
+            if args.montage:
+                logger.info("Montages saved under: %s", Path(args.output_dir) / "montage")
             out = save_batch_results_json(results, proc, args.json_output)
             logger.info("Results saved to: %s", out)
             for k, v in create_batch_summary(results, proc).items():
@@ -237,7 +286,7 @@ def main(argv=None) -> None:
                     raise ValueError(f"Could not read image: {image_path}")
                 r = found[0]
             else:
-                r = predictor.predict_single(image_path)
+                r = predictor.predict_single(image_path, use_transform=args.montage)
             logger.info(f"Image: {r['image_path']}")
             logger.info(f"Prediction: {r['top_prediction']} ({r['confidence']:.2%})")
             for name, prob in sorted(r["all_probabilities"].items(), key=lambda x: -x[1])[:3]:
@@ -246,6 +295,16 @@ def main(argv=None) -> None:
                 target = Path(args.output_dir) / (image_path.stem + CAM_SUFFIX)
                 write_cam_overlays([r], [target])
                 logger.info(f"Heat map: {target}")
+            if args.montage:
+                from PIL import Image
+
+                from ..predict.montage import caption_text, montage_batch
+                target = Path(args.output_dir) / (image_path.stem + MONTAGE_SUFFIX + ".png")
+                picture = montage_batch([r["original_array"]], [r["processed_array"]],
+                                        [caption_text(r["top_prediction"], r["confidence"])])[0].cpu().numpy()
+                target.parent.mkdir(parents=True, exist_ok=True)
+                Image.fromarray(picture).save(target)   # the container is written on the host
+                logger.info(f"Montage saved: {target}")
     except SystemExit:
         raise
     except (FileNotFoundError, ValueError) as e:

@@ -1280,3 +1280,138 @@ def cam_overlay_u8(img: torch.Tensor, cam: torch.Tensor, peak: torch.Tensor, slo
     _lib.call("lf_cam_overlay_u8", img.data_ptr(), cam.data_ptr(), peak.data_ptr(), out.data_ptr(), n, hh, ww, h, w,
               m, int(slot), float(alpha), _stream())
     return out
+
+
+# ---- text and canvas: the pictures that carry titles (lf_draw_text_u8, lf_canvas_tiles_u8; rules: include/leafhip.h)
+TEXT_CELL_W, TEXT_CELL_H, TEXT_MAX_SCALE, TEXT_MAX_LENGTH = 6, 7, 8, 4096
+_TEXT_BLOCK = 256
+
+
+def font5x7() -> np.ndarray:
+    """The project's 5x7 bitmap font as the library holds it: uint8 [95, 7], glyphs of ASCII 0x20..0x7E, one byte per
+    row, top row first, bit 4 the leftmost column (lf_font5x7; needs no GPU)."""
+    table = np.zeros(95 * 7, dtype=np.uint8)
+    _lib.call("lf_font5x7", table.ctypes.data)
+    return table.reshape(95, 7)
+
+
+def text_table(texts):
+    """Host half of draw_text_u8: (int32 [K, 8] item table {image, x, y, first, length, colour, scale, first_group},
+    uint8 characters) of texts = [(image, x, y, string, (r, g, b), scale), ...], ordered by image and, inside an
+    image, as given.  One byte per character; what does not fit a byte becomes '?'."""
+    rows = []
+    for k, item in enumerate(texts):
+        image, x, y, s, colour, scale = item
+        r, g, b = (int(v) for v in colour)
+        if min(r, g, b) < 0 or max(r, g, b) > 255:
+            raise ValueError(f"draw_text: colour {colour} of string {k}")
+        rows.append((int(image), k, int(x), int(y), str(s), r | g << 8 | b << 16, int(scale)))
+    rows.sort(key=lambda t: (t[0], t[1]))
+    table = np.zeros((len(rows), 8), dtype=np.int32)
+    chars = bytearray()
+    group = 0
+    for j, (image, _k, x, y, s, colour, scale) in enumerate(rows):
+        table[j] = (image, x, y, len(chars), len(s), colour, scale, group)
+        chars += bytes(ord(c) if ord(c) < 256 else 0x3F for c in s)
+        if 1 <= scale <= TEXT_MAX_SCALE and len(s) <= TEXT_MAX_LENGTH:   # (the launcher names what is out of range)
+            group += -(-(TEXT_CELL_W * scale * len(s) * TEXT_CELL_H * scale) // _TEXT_BLOCK)
+    return table, np.frombuffer(bytes(chars), dtype=np.uint8)
+
+
+def draw_text_u8(img: torch.Tensor, texts) -> torch.Tensor:
+    """Strings of the project's 5x7 font drawn in place into img [N,H,W,3] uint8, all strings of all images in one
+    launch.  texts: a sequence of (image, x, y, string, (r, g, b), scale), integer scale 1..8; where strings of one
+    image overlap, the one later in `texts` wins.  A character outside ASCII 0x20..0x7E draws as '?'; pixels outside
+    the image are dropped, negative origins are legal.  Returns img."""
+    n, h, w = _hwc(img, "draw_text.img")
+    table, chars = text_table(texts)
+    if not len(table):
+        return img
+    d_table = torch.from_numpy(table).to(img.device)
+    d_chars = torch.from_numpy(chars.copy() if chars.size else np.zeros(1, dtype=np.uint8)).to(img.device)
+    _lib.call("lf_draw_text_u8", img.data_ptr(), n, h, w, d_table.data_ptr(), table.ctypes.data, len(table),
+              d_chars.data_ptr(), int(chars.size), _stream())
+    return img
+
+
+@functools.lru_cache(maxsize=256)
+def canvas_axis_table(src: int, dst: int) -> np.ndarray:
+    """lf_canvas_tiles_u8's table of one axis, int32 [dst, 2] = {first tap i, weight k of the second tap (of 2048)}:
+    pos = (d + 0.5) * src / dst - 0.5 in float64, i = floor(pos), f = pos - i, clamped to the source with f = 0 at
+    both ends, k = rint(f * 2048).  Shared between calls: do not write to it."""
+    d = np.arange(dst, dtype=np.float64)
+    pos = (d + 0.5) * float(src) / float(dst) - 0.5
+    i = np.floor(pos)
+    f = pos - i
+    low, high = i < 0, i >= src - 1
+    i = np.where(low, 0, np.where(high, src - 1, i))
+    f = np.where(low | high, 0.0, f)
+    table = np.stack([i.astype(np.int32), np.rint(f * 2048.0).astype(np.int32)], 1)
+    table.setflags(write=False)
+    return table
+
+
+def canvas_tiles_plan(sources, tiles, out_hw, fill, shades=()):
+    """Host half of canvas_tiles_u8: the checks, and lf_canvas_tiles_u8's plan (int32: tile descriptors with the
+    sources' device addresses, shade rectangles, axis tables).  Returns (plan, n, oh, ow, tiles, shades, fill as
+    r | g << 8 | b << 16, device)."""
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    sources, tiles = list(sources), [tuple(int(v) for v in t) for t in tiles]
+    if len(sources) != len(tiles) or not sources:
+        raise ValueError(f"canvas_tiles: {len(sources)} sources for {len(tiles)} tiles (at least one)")
+    if oh <= 0 or ow <= 0:
+        raise ValueError(f"canvas_tiles: bad canvas size {out_hw}")
+    n, dev = int(sources[0].shape[0]), sources[0].device
+    for t, s in enumerate(sources):
+        _chk(s, _U8, f"canvas_tiles.sources[{t}]")
+        if s.dim() not in (3, 4) or (s.dim() == 4 and s.shape[3] != 3) or s.shape[0] != n or s.device != dev \
+                or n == 0 or s.shape[1] == 0 or s.shape[2] == 0:
+            raise ValueError(f"canvas_tiles.sources[{t}]: expected [{n},h,w,3] or [{n},h,w] on {dev}, got "
+                             f"{tuple(s.shape)} on {s.device}")
+    for t, (x, y, w, h) in enumerate(tiles):
+        if w <= 0 or h <= 0 or x < 0 or y < 0 or x + w > ow or y + h > oh:
+            raise ValueError(f"canvas_tiles: tile {t} {tiles[t]} does not lie in the {ow} x {oh} canvas")
+        for u, (x2, y2, w2, h2) in enumerate(tiles[:t]):
+            if not (x >= x2 + w2 or x2 >= x + w or y >= y2 + h2 or y2 >= y + h):
+                raise ValueError(f"canvas_tiles: tiles {u} and {t} overlap")
+    fill_rgb = [int(v) for v in fill]
+    if len(fill_rgb) != 3 or min(fill_rgb) < 0 or max(fill_rgb) > 255:
+        raise ValueError(f"canvas_tiles: fill {fill}")
+    shades = [tuple(int(v) for v in s) for s in shades]
+    for s in shades:
+        if len(s) != 6 or s[2] < 0 or s[3] < 0 or not 0 <= s[4] <= s[5] <= 65536 or s[5] == 0:
+            raise ValueError(f"canvas_tiles: shade {s}")
+    head = 12 * len(tiles) + 6 * len(shades)
+    at, where, parts = head, {}, []
+    for (_x, _y, w, h), s in zip(tiles, sources):   # one table per (source length, tile length)
+        for key in ((int(s.shape[2]), w), (int(s.shape[1]), h)):
+            if key not in where:
+                where[key] = at
+                parts.append(canvas_axis_table(*key).reshape(-1))
+                at += 2 * key[1]
+    plan = np.zeros(at, dtype=np.int32)
+    for t, ((x, y, w, h), s) in enumerate(zip(tiles, sources)):
+        sh, sw, ch = int(s.shape[1]), int(s.shape[2]), 3 if s.dim() == 4 else 1
+        ptr = s.data_ptr()
+        copy = (sh, sw) == (h, w) and ch == 3 and sw % 4 == 0 and ptr % 4 == 0
+        lo, hi = ptr & 0xFFFFFFFF, ptr >> 32
+        plan[12 * t:12 * t + 12] = (x, y, w, h, sh, sw, ch, where[(sw, w)], where[(sh, h)],
+                                    lo - (1 << 32) if lo >= 1 << 31 else lo, hi, 1 if copy else 0)
+    for k, s in enumerate(shades):
+        plan[12 * len(tiles) + 6 * k:12 * len(tiles) + 6 * k + 6] = s
+    plan[head:] = np.concatenate(parts)
+    return plan, n, oh, ow, len(tiles), len(shades), fill_rgb[0] | fill_rgb[1] << 8 | fill_rgb[2] << 16, dev
+
+
+def canvas_tiles_u8(sources, tiles, out_hw, fill, shades=()) -> torch.Tensor:
+    """One canvas [N,OH,OW,3] uint8 composed from T source batches in one launch.  sources[t] is [N,h,w,3] or
+    [N,h,w] uint8 on the device (gray is replicated), all of one N and device; tiles[t] = (dst_x, dst_y, dst_w, dst_h),
+    inside the canvas and not overlapping (ValueError otherwise); the source is resampled bilinearly into its tile by
+    canvas_axis_table's integer tables (a tile of the source's own size is an exact copy); a pixel in no tile gets
+    fill = (r, g, b).  shades: rectangles (x, y, w, h, num, den) applied after the tiles, v' = (v*num + den//2)//den."""
+    plan, n, oh, ow, n_tiles, n_shades, fill_word, dev = canvas_tiles_plan(sources, tiles, out_hw, fill, shades)
+    out = torch.empty((n, oh, ow, 3), dtype=_U8, device=dev)
+    d_plan = torch.from_numpy(plan).to(dev)   # descriptors, pointers and tables: one upload per launch
+    _lib.call("lf_canvas_tiles_u8", out.data_ptr(), n, oh, ow, d_plan.data_ptr(), plan.ctypes.data, plan.size,
+              n_tiles, n_shades, fill_word, _stream())
+    return out

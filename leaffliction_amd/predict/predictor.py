@@ -4,7 +4,9 @@
 kernels on the GPU (images of several native sizes in one launch), and runs ONE batched forward (the reference
 stacks all images and calls `model.predict`).  The mask/transform subprocess of the
 reference's ImageProcessor is display-only and not part of the model input path
-(`enable_subprocess=False` at predictor.py:46,99), so it is not reproduced.
+(`enable_subprocess=False` at predictor.py:46,99): the model always sees the original.  What that subprocess shows,
+the leaf on black outside make_mask's mask, is `processed_array` of `predict_single(path, use_transform=True)` and
+what `masked_arrays` returns for a batch (make_mask and the composite on the GPU); predict --montage draws it.
 """
 from __future__ import annotations
 
@@ -58,12 +60,55 @@ class Predictor:
                 "original_array": original, "processed_array": original}
 
     def predict_single(self, image_path, use_transform: bool = False) -> Dict[str, Any]:
+        """use_transform: `processed_array` is the image on black outside make_mask's mask (masked_arrays) instead
+        of the original; the prediction is the same either way."""
         if not self._initialized:
             raise RuntimeError("Predictor not initialized. Call load() first.")
         image_path = Path(image_path)
         original = ImageLoader.load_as_array(image_path)
         probs = self.model_loader.model.predict(self._prepare([original]))[0]
-        return self._result(image_path, original, probs)
+        result = self._result(image_path, original, probs)
+        if use_transform:
+            result["processed_array"] = self.masked_arrays([original], [image_path])[0]
+        return result
+
+    MASK_CHUNK = 64   # images per make_mask launch
+
+    def masked_arrays(self, arrays: List[np.ndarray], names=None) -> List[np.ndarray]:
+        """Per image [h,w,3] uint8 the picture the reference's transform subprocess shows: the image on black outside
+        make_mask's mask, with the default TransformConfig (transform.make_masks_device, ops.mask_composite_u8
+        "black"), images grouped by size and masked MASK_CHUNK at a time.  An image over make_mask's size limit, or
+        one whose mask is empty, keeps the original, with one warning naming it."""
+        import torch
+
+        from .. import ops
+        from ..transform import filters as F
+        if names is not None and len(names) != len(arrays):
+            raise ValueError(f"masked_arrays: {len(names)} names for {len(arrays)} images")
+        cfg = F.TransformConfig()
+        out: List[Any] = list(arrays)
+        groups: Dict[tuple, List[int]] = {}
+        for k, a in enumerate(arrays):
+            groups.setdefault(tuple(a.shape[:2]), []).append(k)
+        for (h, w), ks in groups.items():
+            if not ops.make_mask_fits(h, w, cfg.mask_upscale_factor, cfg.mask_upscale_long_side):
+                for k in ks:
+                    logger.warning("%s: %d x %d is over make_mask's size limit; the montage shows the original",
+                                   names[k] if names else f"image {k}", h, w)
+                continue
+            for b in range(0, len(ks), self.MASK_CHUNK):
+                part = ks[b:b + self.MASK_CHUNK]
+                x = torch.from_numpy(np.stack([arrays[k] for k in part])).to(F._device())
+                mask, _contour, counts, _fb = F.make_masks_device(x, cfg)
+                black = ops.mask_composite_u8(x, mask, "black").cpu().numpy()
+                found = ((counts > 0) & (mask.flatten(1).max(dim=1).values > 0)).cpu().numpy()
+                for j, k in enumerate(part):
+                    if found[j]:
+                        out[k] = black[j]
+                    else:
+                        logger.warning("%s: make_mask found no leaf; the montage shows the original",
+                                       names[k] if names else f"image {k}")
+        return out
 
     POOL_MIN = 64   # below this many files the worker pool costs more than it saves
 
@@ -198,17 +243,23 @@ class Predictor:
         slim = [{k: (None if k.endswith("_array") or k == "cam_overlay" else v) for k, v in r.items()} for r in mine]
         return rk.gather_in_order(slim)
 
-    def predict_batch_sharded(self, image_paths, ranks=None) -> List[Dict[str, Any]]:
+    def predict_batch_sharded(self, image_paths, ranks=None, each=None) -> List[Dict[str, Any]]:
         """`predict_batch` with the file list cut into one contiguous share per GPU replica
         (SURVEY §8e "inference: replicas only"; reference call site predict.py:492).  Every
         rank returns the full result list in input order; results that came from another rank
-        carry no pixel arrays (`original_array` / `processed_array` are None)."""
+        carry no pixel arrays (`original_array` / `processed_array` are None).  `each`, if given, is called with
+        this replica's own results (which carry the arrays) before the gather."""
         from ..utils import ranks as R
         rk = ranks or R.current()
         paths = [Path(p) for p in image_paths]
         if not rk.active:
-            return self.predict_batch(paths)
+            mine = self.predict_batch(paths)
+            if each is not None:
+                each(mine)
+            return mine
         b, e = R.contiguous_share(len(paths), rk.rank, rk.world)
         mine = self.predict_batch(paths[b:e]) if e > b else []
+        if each is not None:
+            each(mine)
         slim = [{k: (None if k.endswith("_array") else v) for k, v in r.items()} for r in mine]
         return rk.gather_in_order(slim)

@@ -10,7 +10,8 @@ reference can produce.  `apply_brown_filter` (brown.py) and `apply_roi_filter` (
 (lf_brown_spots_u8, lf_roi_u8), one image at a time or batched on device tensors, and so does `apply_analyze_filter`
 (analyze.py), whose picture is drawn by the project's own integer rules (lf_analyze_overlay_u8), and
 `apply_landmarks_filter` (landmarks.py: CLAHE, bilateral filter, Canny, Shi-Tomasi corners, greedy point selection),
-whose arithmetic follows the project's own integer rules as well (lf_landmarks_u8).  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
+whose arithmetic follows the project's own integer rules as well (lf_landmarks_u8).  `mosaic_batch` is create_mosaic's
+titled overview, laid out by lf_canvas_tiles_u8 and lettered by lf_draw_text_u8 in the project's 5x7 font.  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
 reproduced — the numbers it draws are."""
 from __future__ import annotations
 
@@ -491,3 +492,41 @@ def hsv_density_curves(rgb: np.ndarray, bins: int = 60):
             if hi > lo else np.histogram(np.full(int(counts[lo]), lo), bins=bins, density=True)
         out[name] = (dens, edges)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the mosaic: create_mosaic's titled overview (srcs/cli/Transformation.py), by the project's own canvas and text rules
+# ---------------------------------------------------------------------------------------------------------------
+
+MOSAIC_CELL, MOSAIC_COLS, MOSAIC_BAR = 300, 3, 25
+MOSAIC_SHADE = (7, 10)                         # the title bar keeps 7/10 of the picture under it
+MOSAIC_TITLE_AT, MOSAIC_TITLE_SCALE = (10, 5), 2
+
+
+def mosaic_layout(names):
+    """(rows, tiles, shades, titles) of a mosaic of the pictures `names`: cell i at column i % 3, row i // 3 of
+    300 x 300 cells; per cell the tile, the shade rectangle of its title bar and the title's origin."""
+    rows = -(-len(names) // MOSAIC_COLS)
+    tiles, shades, titles = [], [], []
+    for i, name in enumerate(names):
+        x0, y0 = (i % MOSAIC_COLS) * MOSAIC_CELL, (i // MOSAIC_COLS) * MOSAIC_CELL
+        tiles.append((x0, y0, MOSAIC_CELL, MOSAIC_CELL))
+        shades.append((x0, y0, MOSAIC_CELL, MOSAIC_BAR) + MOSAIC_SHADE)
+        titles.append((x0 + MOSAIC_TITLE_AT[0], y0 + MOSAIC_TITLE_AT[1], str(name)))
+    return rows, tiles, shades, titles
+
+
+def mosaic_batch(x, results) -> torch.Tensor:
+    """create_mosaic for a batch: x [N,H,W,3] uint8 (the originals) and `results`, an ordered mapping name ->
+    [N,h,w,3] or [N,h,w] uint8 on the device, become [N, 300*rows, 900, 3]: "Original" first, then the results in
+    their order, three 300 x 300 cells to a row, unused cells black; each cell is the integer bilinear resample of
+    ops.canvas_tiles_u8, its top 25 rows shaded to 7/10 under the white title at (x0 + 10, y0 + 5), scale 2, in the
+    project's 5x7 font (ops.draw_text_u8).  One canvas launch and one text launch for the batch."""
+    x = _device_u8(x, 4, "mosaic_batch.x")
+    names = ["Original"] + [str(k) for k in results]
+    sources = [x] + [results[k].contiguous() for k in results]
+    rows, tiles, shades, titles = mosaic_layout(names)
+    out = ops.canvas_tiles_u8(sources, tiles, (MOSAIC_CELL * rows, MOSAIC_CELL * MOSAIC_COLS), (0, 0, 0), shades)
+    white = (255, 255, 255)
+    return ops.draw_text_u8(out, [(i, tx, ty, name, white, MOSAIC_TITLE_SCALE)
+                                  for i in range(int(x.shape[0])) for tx, ty, name in titles])
