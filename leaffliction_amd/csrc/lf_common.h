@@ -241,6 +241,24 @@ __device__ __forceinline__ Block3 xcd_block3() {
     r.x = (int)(id - (unsigned)r.z * gxy - (unsigned)r.y * gx);
     return r;
 }
+// and on a (splits, gy, gz) grid of split-K kernels (the fp32 weight gradients), whose gy * gz channel blocks
+// of one split stage the same items: x is the split, and the channel block is the fastest part of the logical
+// id, so the blocks of a split are neighbours in one XCD's dispatch sequence and run there side by side
+__device__ __forceinline__ Block3 xcd_split_block3() {
+    const unsigned gx = gridDim.x, gy = gridDim.y, per = gy * gridDim.z;
+    Block3 r;
+    if (per == 1) {  // one channel block: nothing to share, the splits keep their blockIdx order
+        r.x = (int)blockIdx.x;
+        r.y = r.z = 0;
+        return r;
+    }
+    const unsigned id = xcd_flat(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * per);
+    r.x = (int)(id / per);
+    const unsigned c = id - (unsigned)r.x * per;
+    r.z = (int)(c / gy);
+    r.y = (int)(c - (unsigned)r.z * gy);
+    return r;
+}
 
 // One workgroup's walk over segments of column strips (a strip = a tile's width of columns of one image, a segment
 // = seg_tiles consecutive tiles of it, top to bottom; `segs` segments to a strip), dealt out as strip_share() says.

@@ -951,7 +951,9 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int w_ci = wid % WCI, w_co = (wid / WCI) % WCO, w_k = wid / (WCI * WCO);
-    const int ci0 = blockIdx.y * CI_T, co0 = blockIdx.z * CO_T;
+    // split and channel blocks from the dispatch index: the blocks of a split share an XCD (lf::xcd_split_block3)
+    const lf::Block3 blk = lf::xcd_split_block3();
+    const int ci0 = blk.y * CI_T, co0 = blk.z * CO_T;
     const int khalf = lane >> 5, j = lane & 31;
     const size_t hw = (size_t)p.h * p.wd;
     const unsigned uhw = (unsigned)hw;
@@ -978,7 +980,7 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
         }
     };
 
-    const int first = blockIdx.x * p.items_per_split;
+    const int first = blk.x * p.items_per_split;
     const int last = min(first + p.items_per_split, p.items);
     const int tiles = p.tiles_x * p.tiles_y;
 
@@ -1106,7 +1108,7 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
                         v.y = bn_dy1(v.y, yv[i].y, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
                         v.z = bn_dy1(v.z, yv[i].z, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
                         v.w = bn_dy1(v.w, yv[i].w, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
-                        if (blockIdx.y == 0 && p.dy_out != nullptr) {
+                        if (blk.y == 0 && p.dy_out != nullptr) {
                             const int py = rem / TW4, slot = rem - py * TW4;
                             *reinterpret_cast<float4*>(p.dy_out + ((size_t)sn * p.cout + co0 + c) * hw +
                                                        (size_t)(sty0 + py) * p.wd + stx0 + 4 * slot) = v;
@@ -1198,7 +1200,7 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
         }
     }
     if (w_k == 0) {
-        float* out = p.part + (size_t)blockIdx.x * p.cin * p.cout;
+        float* out = p.part + (size_t)blk.x * p.cin * p.cout;
         const int co = co0 + w_co * 32 + j;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1219,8 +1221,14 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
 // item's tiles, forming V and D per lane from the staged patch (4 patch rows x 4 columns, 2 dY
 // rows x 2 columns) with adds only.
 // The K-split partners fold in the Winograd domain; G^T M G is applied once per workgroup.  The
-// next item's X patch (and, where the registers allow, its dY tile) is prefetched into registers
-// during the MFMAs.
+// next item's X patch and dY tile are prefetched into registers during the MFMAs: the dY tile whole
+// where the registers allow, in two halves at two stage points per item where they do not (the
+// schedule is described at the item loop).
+// Grid (splits, ci-blocks, co-blocks).  A workgroup takes its split and channel blocks from its
+// dispatch index (lf::xcd_split_block3), not from blockIdx: the channel blocks of a split stage the
+// same X patches and dY tiles, so they run side by side on one XCD and find each other's lines in
+// its L2.  The placement is for speed only; which items a split walks and the slab it writes
+// (part[split]) do not depend on it.
 // floats of (dynamic) LDS: two staging buffers (X patch + dY tile each), or the K-split scratch,
 // or the epilogue's exchange of position rows 1 and 2
 template <int TW, int TH, int WCI, int WCO, int KSPL>
@@ -1256,7 +1264,9 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int pg = wid & 1, rest = wid >> 1;  // rows 2pg, 2pg+1 of the 4x4 position grid
     const int w_ci = rest % WCI, w_co = (rest / WCI) % WCO, w_k = rest / NQ;
-    const int ci0 = blockIdx.y * CI_T, co0 = blockIdx.z * CO_T;
+    // split and channel blocks from the dispatch index: the blocks of a split share an XCD (lf::xcd_split_block3)
+    const lf::Block3 blk = lf::xcd_split_block3();
+    const int ci0 = blk.y * CI_T, co0 = blk.z * CO_T;
     const int khalf = lane >> 5, j = lane & 31;
     const size_t hw = (size_t)p.h * p.wd;
     const unsigned uhw = (unsigned)hw;
@@ -1320,13 +1330,19 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
     using Q2 = std::integral_constant<int, 2>;
     using Q3 = std::integral_constant<int, 3>;
 
-    const int first = blockIdx.x * p.items_per_split;
+    const int first = blk.x * p.items_per_split;
     const int last = min(first + p.items_per_split, p.items);
     const int tiles = p.tiles_x * p.tiles_y;
 
     if (p.vec_ok) {  // every tile is full in x (host guarantees W % TW == 0 for this path)
-        float4 xv[XPT], dv[DPT], yv[DPT];
-        float xh[HPT], dal[DPT], dad[DPT];
+        // With four float4 of dY per thread (CO_T = 64 over a 128-pixel tile) a whole prefetched dY tile (dv, yv,
+        // alpha / add: 40 registers) does not fit beside the 128 accumulators.  Those variants hold half of the
+        // thread's slots at a time: slots [0, DH) are the tile's first CO_T / 2 channels, [DH, DPT) the others.
+        constexpr bool kSplitD = DPT > 2;
+        static_assert(!kSplitD || DPT == 4, "the dY tile is prefetched whole or in two halves");
+        constexpr int DH = kSplitD ? DPT / 2 : DPT;  // dY slots a thread holds in registers
+        float4 xv[XPT], dv[DH], yv[DH];
+        float xh[HPT], dal[DH], dad[DH];
         unsigned xok = 0, dok = 0;
         const bool bn = p.bn_y != nullptr;
         // producer BatchNorm scale/shift of this workgroup's CI_T channels, staged once in LDS
@@ -1383,8 +1399,10 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
         }
         const unsigned xbytes = 4u * ((unsigned)min(CI_T, p.cin - ci0) * uhw + (unsigned)p.wd + 1u);
         const unsigned dbytes = 4u * (unsigned)min(CO_T, p.cout - co0) * uhw;
-        // the X patch (with_x) and / or the dY tile (with_d) of an item
-        auto load_item = [&](int item, bool with_x, bool with_d) {
+        // Issue the loads of an item's X patch (with_x) and / or of half `dhalf` of its dY tile (-1: no dY; a
+        // variant that holds the whole tile has only half 0).  Nothing here is conditional: where `live` is false
+        // (there is no such item) every load takes the out-of-range offset, which fetches zeros and no memory.
+        auto load_item = [&](int item, bool with_x, int dhalf, bool live) {
             const int n = item / tiles, t = item - n * tiles;
             const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
             const size_t torg = (size_t)ty0 * p.wd + tx0;
@@ -1399,7 +1417,7 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
 #pragma unroll
             for (int i = 0; i < XPT; ++i) {
                 const unsigned gy = (unsigned)(ty0 + (int)((xl[i] >> 16) & 0xffu) - 1);
-                const bool ok = xg[i] != kBufOob && gy < (unsigned)p.h;
+                const bool ok = live && xg[i] != kBufOob && gy < (unsigned)p.h;
                 xv[i] = buf_load4(rx, ok ? xg[i] : kBufOob);
                 xok |= (ok ? 1u : 0u) << i;
             }
@@ -1407,43 +1425,45 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
             for (int i = 0; i < HPT; ++i) {
                 const unsigned gy = (unsigned)(ty0 + (int)((hl[i] >> 16) & 0xffu) - 1);
                 const bool side = (hl[i] >> 30) & 1u;
-                const bool ok = hg[i] != kBufOob && gy < (unsigned)p.h && (side ? tx0 + TW < p.wd : tx0 > 0);
+                const bool ok = live && hg[i] != kBufOob && gy < (unsigned)p.h && (side ? tx0 + TW < p.wd : tx0 > 0);
                 xh[i] = buf_load1(rx, ok ? hg[i] : kBufOob);
                 xok |= (ok ? 1u : 0u) << (16 + i);
             }
             }
-            if (!with_d) return;
+            if (dhalf < 0) return;
+            const int s0 = dhalf * DH;  // the half's first slot
             dok = 0;
 #pragma unroll
-            for (int i = 0; i < DPT; ++i) {
-                const unsigned gy = (unsigned)(ty0 + (int)((dl[i] >> 16) & 0xffu));
-                const bool ok = dg[i] != kBufOob && gy < (unsigned)p.h;
-                dv[i] = buf_load4(rd, ok ? dg[i] : kBufOob);
+            for (int i = 0; i < DH; ++i) {
+                const unsigned gy = (unsigned)(ty0 + (int)((dl[s0 + i] >> 16) & 0xffu));
+                const bool ok = live && dg[s0 + i] != kBufOob && gy < (unsigned)p.h;
+                dv[i] = buf_load4(rd, ok ? dg[s0 + i] : kBufOob);
                 dok |= (ok ? 1u : 0u) << i;
             }
             if (bn) {
                 const __amdgpu_buffer_rsrc_t ry =
                     buf_rsrc(p.bn_y + ((size_t)n * p.cout + co0) * hw + torg, dbytes);
 #pragma unroll
-                for (int i = 0; i < DPT; ++i) yv[i] = buf_load4(ry, (dok >> i & 1u) ? dg[i] : kBufOob);
+                for (int i = 0; i < DH; ++i) yv[i] = buf_load4(ry, (dok >> i & 1u) ? dg[s0 + i] : kBufOob);
                 if (p.bn_alpha != nullptr) {
 #pragma unroll
-                    for (int i = 0; i < DPT; ++i) {
-                        const int e = tid + i * NT;
+                    for (int i = 0; i < DH; ++i) {
+                        const int e = tid + (s0 + i) * NT;
                         const int gc = min(co0 + e / (TH * TW4), p.cout - 1);
                         dal[i] = p.bn_alpha[(size_t)n * p.cout + gc];
                         dad[i] = p.bn_add != nullptr ? p.bn_add[(size_t)n * p.cout + gc] : 0.f;
                     }
                 } else {
 #pragma unroll
-                    for (int i = 0; i < DPT; ++i) {
+                    for (int i = 0; i < DH; ++i) {
                         dal[i] = 1.f;
                         dad[i] = 0.f;
                     }
                 }
             }
         };
-        auto store_item = [&](int item, int buf, bool with_x, bool with_d) {
+        // write what load_item(item, with_x, dhalf) fetched into staging buffer `buf`
+        auto store_item = [&](int item, int buf, bool with_x, int dhalf) {
             float* lx = lds + buf * BUF;
             float* ld = lx + XSZ;
             if (with_x) {
@@ -1479,14 +1499,15 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
                 }
             }
             }
-            if (!with_d) return;
+            if (dhalf < 0) return;
+            const int s0 = dhalf * DH;
             const int sn = item / tiles, st = item - sn * tiles;
             const int stx0 = (st % p.tiles_x) * TW, sty0 = (st / p.tiles_x) * TH;
             float* dyo = bn ? p.dy_out + ((size_t)sn * p.cout + co0) * hw + (size_t)sty0 * p.wd + stx0 : nullptr;
 #pragma unroll
-            for (int i = 0; i < DPT; ++i) {
-                if (tid + i * NT < NDI) {
-                    const int c = (tid + i * NT) / (TH * TW4);
+            for (int i = 0; i < DH; ++i) {
+                if (tid + (s0 + i) * NT < NDI) {
+                    const int c = (tid + (s0 + i) * NT) / (TH * TW4);
                     float4 v = dv[i];
                     if (bn && (dok >> i & 1u)) {
                         const float c0 = lbn[c], c1 = lbn[CO_T + c], c2 = lbn[2 * CO_T + c],
@@ -1495,10 +1516,10 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
                         v.y = bn_dy1(v.y, yv[i].y, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
                         v.z = bn_dy1(v.z, yv[i].z, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
                         v.w = bn_dy1(v.w, yv[i].w, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
-                        if (blockIdx.y == 0 && p.dy_out != nullptr)
-                            *reinterpret_cast<float4*>(dyo + (dg[i] >> 2)) = v;
+                        if (blk.y == 0 && p.dy_out != nullptr)
+                            *reinterpret_cast<float4*>(dyo + (dg[s0 + i] >> 2)) = v;
                     }
-                    float* dst = ld + (dl[i] & 0xffffu);
+                    float* dst = ld + (dl[s0 + i] & 0xffffu);
                     {
                         dst[0] = v.x;
                         dst[1] = v.y;
@@ -1508,41 +1529,62 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
                 }
             }
         };
-        // double-buffered staging, one barrier per item: while an item's MFMAs run from one
-        // buffer the next item (loaded an iteration earlier) is written into the other, and
-        // the loads of the item after that are issued.  With four float4 of dY per thread
-        // (CO_T = 64 over a 128-pixel tile) the dY prefetch (dv, yv, alpha / add: 40 registers)
-        // does not fit beside the 128 accumulators: those variants load the next item's dY
-        // at its stage point, behind the X stores, and the other wave on the SIMD covers the wait.
-        constexpr bool kLateD = DPT > 2;
+        // Double-buffered staging, one barrier per item: while an item's MFMAs run from one buffer the next
+        // item is written into the other from registers loaded well before, and the loads after those are
+        // issued.  No load is stored at the stage point that issued it.
+        // The two waves sharing a SIMD (wid, wid+4) move through their MFMAs in lock step, so they stage at
+        // different quarters: while one writes LDS the other keeps the MFMA pipe busy.
+        //   whole dY tile in registers: one stage point per item (after quarter 0 or 2), which stores item
+        //     idx+1 (X patch and dY tile, loaded a full item earlier) and loads item idx+2;
+        //   dY tile in halves (kSplitD): two stage points per item, half an item apart (after quarters 0 and
+        //     2, or 1 and 3).  The first stores X and dY half 0 of item idx+1 and loads dY half 1 of idx+1,
+        //     then X of idx+2; the second stores that half 1 and loads dY half 0 of idx+2.  A half is in
+        //     flight over two quarters of MFMAs, the X patch over a whole item.
+        // The variants that hold the whole tile keep the branch around their loads (idx + 2 < count): with a
+        // `live` flag in its place they compiled to slower loops (profiles/r07_a_wgrad_schedule.md).
         int cur = 0;
         const int count = last - first;
-        auto nth = [&](int idx) { return first + idx; };
+        // clamped where loads are issued for items that do not exist: a dead load's item is the split's last
+        auto nth = [&](int idx) { return first + (kSplitD ? min(idx, count - 1) : idx); };
         if (count > 0) {
-            load_item(nth(0), true, true);
+            load_item(nth(0), true, 0, true);
             __syncthreads();  // lsc / lbn are staged
-            store_item(nth(0), 0, true, true);
-            if (count > 1) load_item(nth(1), true, !kLateD);
+            store_item(nth(0), 0, true, 0);
+            if (kSplitD) {
+                load_item(nth(0), false, 1, true);
+                store_item(nth(0), 0, false, 1);
+            }
+            if (kSplitD)
+                load_item(nth(1), true, 0, count > 1);
+            else if (count > 1)
+                load_item(nth(1), true, 0, true);
         }
         __syncthreads();
-        // The two waves sharing a SIMD (wid, wid+4) move through their MFMAs in lock step, so
-        // they stage half an item apart (after quarters 0 and 2): while one writes LDS the
-        // other keeps the MFMA pipe busy.
         const int stage_q = (wid >> 2) & 1;
         for (int idx = 0; idx < count; ++idx) {
             const bool more = idx + 1 < count;
-            auto stage = [&]() {
-                if (kLateD) load_item(nth(idx + 1), false, true);
-                store_item(nth(idx + 1), cur ^ 1, true, !kLateD);
-                if (idx + 2 < count) load_item(nth(idx + 2), true, !kLateD);
-                if (kLateD) store_item(nth(idx + 1), cur ^ 1, false, true);
+            auto stage_a = [&]() {
+                store_item(nth(idx + 1), cur ^ 1, true, 0);
+                if (kSplitD) {
+                    load_item(nth(idx + 1), false, 1, true);
+                    load_item(nth(idx + 2), true, -1, idx + 2 < count);
+                } else if (idx + 2 < count) {
+                    load_item(nth(idx + 2), true, 0, true);
+                }
+            };
+            auto stage_b = [&]() {
+                store_item(nth(idx + 1), cur ^ 1, false, 1);
+                load_item(nth(idx + 2), false, 0, idx + 2 < count);
             };
             compute_quarter(Q0{}, cur);
-            if (more && stage_q == 0) stage();
+            if (more && stage_q == 0) stage_a();
             compute_quarter(Q1{}, cur);
+            if (kSplitD && more && stage_q == 1) stage_a();
             compute_quarter(Q2{}, cur);
-            if (more && stage_q == 1) stage();
+            if (kSplitD && more && stage_q == 0) stage_b();
+            if (!kSplitD && more && stage_q == 1) stage_a();
             compute_quarter(Q3{}, cur);
+            if (kSplitD && more && stage_q == 1) stage_b();
             __syncthreads();
             cur ^= 1;
         }
@@ -1628,7 +1670,7 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
     }
     __syncthreads();
     if (w_k == 0) {
-        float* out = p.part + (size_t)blockIdx.x * p.cin * 9 * p.cout;
+        float* out = p.part + (size_t)blk.x * p.cin * 9 * p.cout;
         const int co = co0 + w_co * 32 + j;
 #pragma unroll
         for (int s = 0; s < 3; ++s)
