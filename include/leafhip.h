@@ -789,6 +789,65 @@ int lf_draw_text_u8(uint8_t* img, int n, int h, int w, const int32_t* items, con
 int lf_canvas_tiles_u8(uint8_t* out, int n, int oh, int ow, const int32_t* plan, const int32_t* plan_host,
                        size_t plan_ints, int n_tiles, int n_shades, int fill, lf_stream_t stream);
 
+/* ---- Charts: Transformation's Hist figure (apply_histogram_filter, srcs/transform/filters/hist.py:181-297) drawn
+ * from lf_hsv_region_stats' numbers.  The reference draws it with matplotlib; the rules below are this project's own
+ * integer rules and claim no pixel parity with it.  tests/chart_ref.py restates them in numpy; the kernel matches it
+ * bit for bit.
+ *
+ * lf_hist_figure_u8: counts [N][14] int32 and hsv_hist [N][3][256] int32 (lf_hsv_region_stats' outputs, on the
+ * device) -> out [N][LF_HIST_FIG_H][LF_HIST_FIG_W][3] uint8, the geometry of the figure: every pixel of out is
+ * written, none outside it.  The lettering is a second launch (lf_draw_text_u8) the host formats from the 14 counts
+ * (transform.hist_figure_texts).  Null pointers and n <= 0 are refused before any launch.
+ *
+ * The figure is 960 x 640 on white (255, 255, 255), four panels of 480 x 320: (column 0, row 0) the colour regions,
+ * (1, 0) the HSV histograms, (0, 1) the summary (text only: the kernel leaves it white), (1, 1) the hue ranges.  Each
+ * chart panel has a plot rectangle {x0, y0, PW, PH} in figure coordinates (the LF_CHART_*_RECT constants); below,
+ * (lx, ly) = (x - x0, y - y0), and every division truncates.
+ *   Frame   the pixels with lx = -1, lx = PW, ly = -1 or ly = PH and -1 <= lx <= PW, -1 <= ly <= PH are black: the
+ *           frame lies around the plot rectangle, so nothing drawn inside touches it.
+ *   Grid    inside the rectangle, the columns lx = k PW / 4 and the rows ly = k PH / 4, k = 1, 2, 3, are LF_CHART_GRID.
+ *   Regions eight horizontal bars, bar i (counts[1 + i], REGION_KEYS order) in the rows LF_CHART_REGION_SLOT * i +
+ *           [LF_CHART_REGION_BAR_LO, LF_CHART_REGION_BAR_HI) and the columns lx < len, in LF_CHART_REGION_COLOURS[i]:
+ *           with total = counts[0], len = (min(max(c, 0), total) * PW + total / 2) / total in int64, 0 when total <= 0.
+ *           No minimum length.
+ *   Hues    five vertical bars, bar i (counts[9 + i], HUE_KEYS order) in the columns LF_CHART_HUE_SLOT * i +
+ *           [LF_CHART_HUE_BAR_LO, LF_CHART_HUE_BAR_HI) and the rows ly >= PH - hgt, in LF_CHART_HUE_COLOURS[i]: with
+ *           m = max(1, the largest of the five max(c, 0)), hgt = (max(c, 0) * PH + m / 2) / m in int64.
+ *   HSV     each of the H, S, V histograms (entries below zero count as zero) is summed into 64 bins of four values,
+ *           in int64; ymax = max(1, the largest of the 192 bins).  Bin j has its point at lx = LF_CHART_HSV_PITCH * j +
+ *           LF_CHART_HSV_PITCH / 2, ly = PH - 2 - hp with hp = (min(b, ymax) * (PH - 3) + ymax / 2) / ymax: the span
+ *           PH - 3 keeps a thick segment (one pixel around its points) inside the rectangle.  A curve is the 63 thick
+ *           segments ("Drawing rules" above: distance <= 1, int64 terms) between neighbouring points, in tab:orange
+ *           (255, 127, 14) for H, tab:green (44, 160, 44) for S, tab:blue (31, 119, 180) for V; a channel whose 64
+ *           bins are all zero has no curve.  Markers: the columns lx = (LF_CHART_HSV_PITCH * v + 3) / 4 for hue
+ *           v = 15, 35, 85 are LF_CHART_MARKER in the rows with ly mod 8 < 4 (dashed).
+ *   Order   background, grid, markers, frames, region and hue bars, curves H, S, V: the later wins.  A pixel's colour
+ *           is a function of the image's 14 + 768 numbers and its own coordinates alone: the kernel evaluates the
+ *           elements in this order for each pixel (for a curve, the segments whose columns reach it), with no order
+ *           between threads and no atomics; two launches give the same bits.
+ * The numbers are not trusted: negative counts are zero, a count over its total is the total, and by the formulas a
+ * bar or a curve stays inside its plot rectangle whatever they are.  Colours are r | g << 8 | b << 16. */
+#define LF_HIST_FIG_H 640
+#define LF_HIST_FIG_W 960
+#define LF_CHART_PANEL_W 480
+#define LF_CHART_PANEL_H 320
+#define LF_CHART_REGIONS_RECT {110, 40, 300, 240}
+#define LF_CHART_HSV_RECT {528, 40, 384, 240}
+#define LF_CHART_HUES_RECT {520, 370, 400, 220}
+#define LF_CHART_REGION_SLOT 30
+#define LF_CHART_REGION_BAR_LO 5
+#define LF_CHART_REGION_BAR_HI 25
+#define LF_CHART_HUE_SLOT 80
+#define LF_CHART_HUE_BAR_LO 16
+#define LF_CHART_HUE_BAR_HI 64
+#define LF_CHART_HSV_PITCH 6
+#define LF_CHART_GRID 0xe0e0e0
+#define LF_CHART_MARKER 0x808080
+#define LF_CHART_CURVE_COLOURS {0x0e7fff, 0x2ca02c, 0xb4771f}
+#define LF_CHART_REGION_COLOURS {0x327d2e, 0x32cd9a, 0x00d7ff, 0x3f85cd, 0x3c14dc, 0x4f4f2f, 0xdec4b0, 0xd30094}
+#define LF_CHART_HUE_COLOURS {0x3ca03c, 0x00a5ff, 0x2827d6, 0xbd6794, 0x7f7f7f}
+int lf_hist_figure_u8(const int32_t* counts, const int32_t* hsv_hist, uint8_t* out, int n, lf_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* A2 — the mixed-precision TRAINING step (bf16 storage, fp32 arithmetic)      */
 /* ------------------------------------------------------------------------- */

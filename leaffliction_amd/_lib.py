@@ -109,6 +109,7 @@ SIGNATURES = {
     "lf_font5x7": [P],
     "lf_draw_text_u8": [P, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P],
     "lf_canvas_tiles_u8": [P, c_int, c_int, c_int, P, P, c_size_t, c_int, c_int, c_int, P],
+    "lf_hist_figure_u8": [P, P, P, c_int, P],
     "lf_conv2d_bf16_stats_tiles": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "lf_conv2d_bf16_train": [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P,
                              c_size_t, P, P, P, P, c_int, P],

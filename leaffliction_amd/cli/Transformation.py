@@ -12,7 +12,8 @@ Images are decoded on host threads (Pillow, EXIF transpose, RGB), grouped by siz
 batched launch over chunks of bounded size; outputs are encoded on the GPU (quality 95, the balancer's encoder).
 Without their switches (below), each with one warning per run and no file: Analyze and Landmarks (PlantCV shape
 analysis, CLAHE / bilateral filtering, goodFeaturesToTrack) and the mosaic (its titles are cv2's Hershey text).  Hist is this project's own
-matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped.
+matplotlib figure of the GPU numbers; without matplotlib it is warned about and skipped (`--figures`, below, draws it
+on the GPU instead).
 
 `--overlays` (a flag of this project) draws Analyze's picture: with Analyze among the types, `<stem>__T_Analyze.jpg` is
 apply_analyze_filter(masked, mask, contour) as process_single_image calls it: the contour, the centroid marker, the
@@ -37,6 +38,15 @@ cells are resampled and the titles written by the project's own integer rules an
 cv2's pixels.  As in the reference the file has no --skip-existing test of its own, and in folder mode two images
 of one name or number in different folders write the same file.  The mosaic warning is then not given; without the
 flag nothing changes.
+
+`--figures` (a flag of this project) draws Hist's figure on the GPU: with Hist among the types, `<stem>__T_Hist.jpg`
+is apply_histogram_filter(masked) as process_single_image calls it, a 960 x 640 report of four panels: the colour
+regions as bars, the H, S and V histograms of the leaf pixels as curves, the reference's summary with its health
+status, and the hue ranges as bars where the reference has a pie (transform.hist_figure_batch: one kernel launch and
+one text launch per chunk).  The bars, curves and letters follow the project's own integer rules and 5x7 font
+(include/leafhip.h, "Charts"), not matplotlib's pixels, and the names are written without accents.  matplotlib is
+then not needed, not imported and not warned about, and the mosaic's Hist cell is that picture; without the flag
+nothing changes.
 
 `--measure [FILE]` writes Analyze's numbers (not its picture) as one CSV table, a row per processed image in path
 order: shape, hull and axes from make_mask's contour (ops.shape_stats), the brown share and the Canny edge count
@@ -162,6 +172,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                    help="Draw Analyze's picture (<stem>__T_Analyze.jpg) by this project's own drawing rules")
     p.add_argument("--landmarks", action="store_true",
                    help="Run the pseudo-landmarks filter (<stem>__T_Landmarks.jpg) by this project's own integer rules")
+    p.add_argument("--figures", action="store_true",
+                   help="Draw Hist's figure (<stem>__T_Hist.jpg) on the GPU by this project's own chart rules and 5x7 "
+                        "font, without matplotlib")
     p.add_argument("--mosaic", action="store_true",
                    help="Write the titled overview image<n>_mosaic.jpg of every image (this project's own resampling "
                         "and 5x7 font).  The name is flat, as the reference's: in folder mode images of one name or "
@@ -261,7 +274,7 @@ def encode_jpeg_batch(x) -> List[bytes]:
 
 
 def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlays: bool = False,
-                    landmarks: bool = False) -> Dict[str, object]:
+                    landmarks: bool = False, figures: bool = False) -> Dict[str, object]:
     """process_single_image's data flow for a same-size batch [N,H,W,3] uint8 on the device.  Returns the device
     outputs of the requested ported types ("Mask", "Blur", "ROI", "Brown": [N,H,W,3] uint8), "brown_stats"
     (percentages, counts, areas) with Brown, and "hist" (counts, histograms as numpy) with Hist.  measure: also
@@ -270,7 +283,8 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
     analyze_filter_batch on `masked` with the mask made from the original; ops.shape_stats runs once for the picture and
     the table.  landmarks: with Landmarks among the types also "Landmarks" [N,H,W,3] uint8, landmarks_filter_batch on
     `masked` with the original's contour and the mask made from `masked` (the one Blur makes, made once), and
-    "landmark_counts", per image (border, vein, disease)."""
+    "landmark_counts", per image (border, vein, disease).  figures: with Hist among the types also "Hist"
+    [N,640,960,3] uint8, hist_figure_batch's picture of the same numbers; "hist" stays as it is."""
     import torch
 
     from .. import ops
@@ -318,24 +332,29 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
             res["measure"] = F.measure_leaves(x, cfg, masks=(mask, contour, counts, _fb), brown_stats=stats,
                                               masked=white, shape=shape)[0]
     if "Hist" in types:
-        counts_h, hist_h = ops.hsv_region_stats(masked.contiguous())
-        res["hist"] = (counts_h.cpu().numpy(), hist_h.cpu().numpy())
+        stats_h = ops.hsv_region_stats(masked.contiguous())
+        if figures:
+            res["Hist"], res["hist"] = F.hist_figure_batch(None, stats_h)
+        else:
+            res["hist"] = (stats_h[0].cpu().numpy(), stats_h[1].cpu().numpy())
     return res
 
 
 class _Runner:
     def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor,
-                 measure: bool = False, overlays: bool = False, landmarks: bool = False, mosaic: bool = False):
+                 measure: bool = False, overlays: bool = False, landmarks: bool = False, mosaic: bool = False,
+                 figures: bool = False):
         self.types, self.cfg, self.pool = types, cfg, pool
         self.measure, self.overlays, self.landmarks, self.mosaic = measure, overlays, landmarks, mosaic
+        self.figures = figures
         self.rows: Dict[Path, List[str]] = {}   # --measure: image path -> CSV cells after `file`
         self.skip_existing, self.overwrite = skip_existing, overwrite
-        self.hist = "Hist" in types and _have_matplotlib()
+        self.hist = "Hist" in types and not figures and _have_matplotlib()   # the matplotlib figure
         for t in NOT_PORTED:   # one warning per run
             if t in types and not (overlays and t == "Analyze") and not (landmarks and t == "Landmarks"):
                 logging.warning("%s is not ported to the GPU (PlantCV shape analysis / landmarks): no %s output is "
                                 "written", t, t)
-        if "Hist" in types and not self.hist:
+        if "Hist" in types and not figures and not self.hist:
             logging.warning("matplotlib is not available: no Hist output is written")
         if not mosaic:
             logging.warning("The mosaic is not ported (it needs cv2's Hershey text): no mosaic is written")
@@ -359,13 +378,14 @@ class _Runner:
         for c0 in range(0, len(items), CHUNK):
             chunk = items[c0:c0 + CHUNK]
             x = torch.from_numpy(np.stack([a for _p, _d, a in chunk])).to(dev)
-            res = transform_batch(x, self.types, self.cfg, measure, self.overlays, self.landmarks)
+            res = transform_batch(x, self.types, self.cfg, measure, self.overlays, self.landmarks, self.figures)
             if measure:
                 from ..transform.filters import measure_row
                 for i, (p, _d, _a) in enumerate(chunk):
                     self.rows[p] = measure_row(res["measure"], i)
             names = [output_names(p.stem) for p, _d, _a in chunk]
-            for t in ("Mask", "Blur", "ROI", "Analyze", "Landmarks", "Brown"):   # process_single_image's order
+            # process_single_image's order; Hist last, where the matplotlib figure is written too
+            for t in ("Mask", "Blur", "ROI", "Analyze", "Landmarks", "Brown", "Hist"):
                 if t not in res:
                     continue
                 outs = [d / nm[t] for (_p, d, _a), nm in zip(chunk, names)]
@@ -381,8 +401,8 @@ class _Runner:
                 if t == "Brown":
                     for count, pct, area in res["brown_stats"]:
                         logging.info(f"Brown spots detected: {count} regions, {pct:.1f}% of leaf area ({area} pixels)")
-            hist_dev = None
-            if self.hist:
+            hist_dev = res.get("Hist")   # --figures: drawn on the device, and written by the loop above
+            if hist_dev is None and self.hist:
                 counts_h, hist_h = res["hist"]
                 figs = list(self.pool.map(lambda i: render_hist(*hist_numbers(counts_h[i], hist_h[i])),
                                           range(len(chunk))))
@@ -499,7 +519,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         out_d.mkdir(parents=True, exist_ok=True)
         with ThreadPoolExecutor(_workers(args.workers)) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays, args.landmarks, args.mosaic)
+                             args.overlays, args.landmarks, args.mosaic, args.figures)
             saved = runner.run([(ip, out_d)])
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else out_d / "measurements.csv", [(ip, out_d)],
@@ -525,7 +545,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         jobs = [(p, dst) for p in imgs]
         with ThreadPoolExecutor(n_threads) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays, args.landmarks, args.mosaic)
+                             args.overlays, args.landmarks, args.mosaic, args.figures)
             saved = runner.run(jobs)
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else dst / "measurements.csv", jobs, runner.rows,
@@ -584,6 +604,8 @@ class TransformFunction:
     Brown); an image without a contour then gets the original image, the reference's picture without its caption.
     With landmarks=True Landmarks produces its picture too (transform.landmarks_filter_batch on the original image
     with the mask made from it, after Analyze and before Hist and Brown); an image without a contour keeps what it had.
+    With figures=True Hist produces its picture as well (transform.hist_figure_batch on the original image, after
+    Landmarks and before Brown): the 960 x 640 report, resized like any other stage's picture.
     The augmentation draws come from Python's global `random`, under a lock, image by image in batch order, so that after random.seed(k) a batch equals
     sequential calls.  A file the filters reject or any stage error logs the reference's error line and takes its
     fallback (Pillow NEAREST resize of the file, no augmentation); an unreadable file gives the black pair.  The
@@ -591,8 +613,9 @@ class TransformFunction:
     per-image log line is not written either."""
 
     def __init__(self, cfg, transform_types: Optional[Sequence[str]], apply_augmentation: bool, workers: int = 0,
-                 overlays: bool = False, landmarks: bool = False):
+                 overlays: bool = False, landmarks: bool = False, figures: bool = False):
         self.cfg = cfg
+        self.figures = bool(figures)
         self.overlays = bool(overlays)
         self.landmarks = bool(landmarks)
         self.transform_types = transform_types
@@ -614,7 +637,7 @@ class TransformFunction:
                 log.info("Duplicate transform '%s' ignored for %s", name, where)
             else:
                 result.append(name)
-        on = {"Analyze": self.overlays, "Landmarks": self.landmarks}
+        on = {"Analyze": self.overlays, "Landmarks": self.landmarks, "Hist": self.figures}
         skipped = [t for t in TRAIN_NOT_PRODUCED if t in result and not on.get(t, False)]
         if skipped:
             with self._lock:
@@ -622,8 +645,12 @@ class TransformFunction:
             if first:
                 off = [t for t in ("Analyze", "Landmarks") if not on[t]]
                 why = (" and ".join(off) + (" are" if len(off) > 1 else " is") + " not ported, ") if off else ""
-                log.warning("%s produce no image in the training transform (%sHist is a figure) and are "
-                            "skipped", ", ".join(skipped), why)
+                if self.figures:   # Hist feeds its picture: only types that are not ported are left to skip
+                    log.warning("%s produce no image in the training transform (%s) and are skipped",
+                                ", ".join(skipped), why[:-2])
+                else:
+                    log.warning("%s produce no image in the training transform (%sHist is a figure) and are "
+                                "skipped", ", ".join(skipped), why)
         return tuple(result)
 
     # ---------------------------------------------------------------- stages of one same-size group
@@ -660,6 +687,8 @@ class TransformFunction:
         if self.landmarks and "Landmarks" in types:   # an image without a contour keeps what it had
             pics = F.landmarks_filter_batch(x, masks, cfg)[0]
             res = torch.where((masks[2] > 0).view(-1, 1, 1, 1), pics, res)
+        if self.figures and "Hist" in types:   # apply_histogram_filter(rgb): the report, whatever the image's size
+            res = F.hist_figure_batch(x)[0]
         if "Brown" in types:
             res, _stats = ops.brown_spots_u8(
                 x, masks[0], brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
@@ -826,15 +855,17 @@ class TransformFunction:
 
 def create_transform_function(config_path: Optional[str] = None, transform_types: Optional[Tuple[str, ...]] = None,
                               apply_augmentation: bool = True, overlays: bool = False,
-                              landmarks: bool = False) -> TransformFunction:
+                              landmarks: bool = False, figures: bool = False) -> TransformFunction:
     """The reference's create_transform_function (srcs/cli/Transformation.py:1008-1053): a `transform=` hook for
     ManifestSequence that feeds leaf-masked, saliency, ROI-boxed or brown-spot images, here a TransformFunction
     (callable per image, `.batch` for a device batch).  config_path: a YAML file with the reference's keys; None =
     the values of its config.yaml.  transform_types: names or aliases, None = all seven.  overlays (a switch of this
-    project): Analyze feeds its picture instead of being skipped.  landmarks (another one): so does Landmarks."""
+    project): Analyze feeds its picture instead of being skipped.  landmarks (another one): so does Landmarks.  figures (a third): so
+    does Hist, the 960 x 640 report of transform.hist_figure_batch."""
     from ..transform.filters import TransformConfig, load_config
     cfg = load_config(Path(config_path)) if config_path else TransformConfig()
-    return TransformFunction(cfg, transform_types, apply_augmentation, overlays=overlays, landmarks=landmarks)
+    return TransformFunction(cfg, transform_types, apply_augmentation, overlays=overlays, landmarks=landmarks,
+                             figures=figures)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "lf_common.h"
+#include "lf_draw.h"
 
 namespace {
 
@@ -2705,46 +2706,12 @@ __device__ __forceinline__ int draw_coord(double v) {   // truncated; NaN goes t
     return v >= (double)-kDrawClamp ? (v <= (double)(kDrawClamp - 1) ? (int)v : kDrawClamp - 1) : -kDrawClamp;
 }
 
-__device__ __forceinline__ long long floor_div(long long a, long long b) {
-    const long long q = a / b;
-    return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
-}
-
-// Calls px(x, y, u, c, L2) for every pixel of the h x w image that can lie within distance 1 of the segment
-// A -> B (see above), major steps t0, t0 + stride, ...: u = (p - A) . d, c = (p - A) x d, L2 = |d|^2.
-template <class F>
-__device__ __forceinline__ void seg_walk(int ax, int ay, int bx, int by, int h, int w, int t0, int stride, F&& px) {
-    const long long dx = bx - ax, dy = by - ay, L2 = dx * dx + dy * dy;
-    const bool xm = (dx < 0 ? -dx : dx) >= (dy < 0 ? -dy : dy);
-    const int a0 = xm ? ax : ay, b0 = xm ? bx : by, a1 = xm ? ay : ax;
-    const long long d0 = xm ? dx : dy, d1 = xm ? dy : dx;
-    const int n0 = xm ? w : h, n1 = xm ? h : w;
-    const int lo = max(min(a0, b0) - 1, 0), hi = min(max(a0, b0) + 1, n0 - 1);
-    for (int s = lo + t0; s <= hi; s += stride) {
-        const int mid = a1 + (d0 ? (int)floor_div((s - a0) * d1, d0) : 0);
-        for (int q = max(mid - 2, 0); q <= min(mid + 2, n1 - 1); ++q) {
-            const int x = xm ? s : q, y = xm ? q : s;
-            const long long rx = x - ax, ry = y - ay;
-            px(x, y, rx * dx + ry * dy, rx * dy - ry * dx, L2);
-        }
-    }
-}
-
-__device__ __forceinline__ void put_px(uint8_t* img, int w, int x, int y, unsigned k) {
-    uint8_t* o = img + ((size_t)y * w + x) * 3;
-    o[0] = (uint8_t)k;
-    o[1] = (uint8_t)(k >> 8);
-    o[2] = (uint8_t)(k >> 16);
-}
-
-// thickness 2: every pixel within distance 1 of the segment
-__device__ __forceinline__ void draw_thick(uint8_t* img, int h, int w, int ax, int ay, int bx, int by, unsigned k,
-                                           int t0, int stride) {
-    seg_walk(ax, ay, bx, by, h, w, t0, stride, [&](int x, int y, long long u, long long c, long long L2) {
-        const long long ex = u <= 0 ? x - ax : x - bx, ey = u <= 0 ? y - ay : y - by;
-        if ((u <= 0 || u >= L2) ? ex * ex + ey * ey <= 1 : c * c <= L2) put_px(img, w, x, y, k);
-    });
-}
+// floor_div, seg_walk, put_px and draw_thick (the thick segment: every pixel within distance 1) are stated in lf_draw.h,
+// which lf_hist_figure_u8 shares
+using lf::draw_thick;
+using lf::floor_div;
+using lf::put_px;
+using lf::seg_walk;
 
 // thickness 1, anti-aliased: 0 <= u <= L2 and c^2 < L2, blended with a = 256 - isqrt(65536 c^2 / L2)
 __device__ __forceinline__ void draw_aa(uint8_t* img, int h, int w, int ax, int ay, int bx, int by, unsigned k,

@@ -1415,3 +1415,31 @@ def canvas_tiles_u8(sources, tiles, out_hw, fill, shades=()) -> torch.Tensor:
     _lib.call("lf_canvas_tiles_u8", out.data_ptr(), n, oh, ow, d_plan.data_ptr(), plan.ctypes.data, plan.size,
               n_tiles, n_shades, fill_word, _stream())
     return out
+
+
+# ---- charts: Transformation's Hist figure (lf_hist_figure_u8; rules: include/leafhip.h, "Charts")
+HIST_FIG_H, HIST_FIG_W = 640, 960
+
+
+def hist_figure_u8(counts: torch.Tensor, hist: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The geometry of the Hist figure, [N,640,960,3] uint8, from hsv_region_stats' outputs on the device: counts
+    int32 [N,14] and hist int32 [N,3,256], contiguous.  Frames, grid, markers, the region and hue bars and the three
+    curves; no text (transform.hist_figure_batch adds it).  The numbers are not trusted: negative counts are zero and
+    nothing leaves its plot rectangle.  out: a contiguous [N,640,960,3] uint8 tensor to write into."""
+    _chk(counts, _I32, "hist_figure.counts", 2)
+    _chk(hist, _I32, "hist_figure.hist", 3)
+    n = int(counts.shape[0])
+    if n == 0 or tuple(counts.shape) != (n, 14) or tuple(hist.shape) != (n, 3, 256):
+        raise ValueError(f"hist_figure: expected counts [N,14] and hist [N,3,256] with N>0, got "
+                         f"{tuple(counts.shape)} and {tuple(hist.shape)}")
+    if hist.device != counts.device:
+        raise ValueError("hist_figure: counts and hist are on different devices")
+    if out is None:
+        out = torch.empty((n, HIST_FIG_H, HIST_FIG_W, 3), dtype=_U8, device=counts.device)
+    else:
+        _chk(out, _U8, "hist_figure.out", 4)
+        if tuple(out.shape) != (n, HIST_FIG_H, HIST_FIG_W, 3) or out.device != counts.device:
+            raise ValueError(f"hist_figure.out: expected [{n},{HIST_FIG_H},{HIST_FIG_W},3] on {counts.device}, got "
+                             f"{tuple(out.shape)} on {out.device}")
+    _lib.call("lf_hist_figure_u8", counts.data_ptr(), hist.data_ptr(), out.data_ptr(), n, _stream())
+    return out

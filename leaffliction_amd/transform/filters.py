@@ -12,7 +12,8 @@ reference can produce.  `apply_brown_filter` (brown.py) and `apply_roi_filter` (
 `apply_landmarks_filter` (landmarks.py: CLAHE, bilateral filter, Canny, Shi-Tomasi corners, greedy point selection),
 whose arithmetic follows the project's own integer rules as well (lf_landmarks_u8).  `mosaic_batch` is create_mosaic's
 titled overview, laid out by lf_canvas_tiles_u8 and lettered by lf_draw_text_u8 in the project's 5x7 font.  matplotlib rendering of the histogram report (hist.py:191-297) is presentation and is not
-reproduced — the numbers it draws are."""
+reproduced — the numbers it draws are, and `apply_histogram_filter` / `hist_figure_batch` draw a report of the same
+content from them on the GPU, by the project's own chart rules (lf_hist_figure_u8) and the same font."""
 from __future__ import annotations
 
 import logging
@@ -530,3 +531,146 @@ def mosaic_batch(x, results) -> torch.Tensor:
     white = (255, 255, 255)
     return ops.draw_text_u8(out, [(i, tx, ty, name, white, MOSAIC_TITLE_SCALE)
                                   for i in range(int(x.shape[0])) for tx, ty, name in titles])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the Hist figure: apply_histogram_filter's report (hist.py:181-297), by the project's own chart and text rules
+# ---------------------------------------------------------------------------------------------------------------
+
+HIST_FIG_H, HIST_FIG_W = ops.HIST_FIG_H, ops.HIST_FIG_W
+CHART_PANEL_W, CHART_PANEL_H = 480, 320
+CHART_REGIONS_RECT = (110, 40, 300, 240)       # plot rectangles (x0, y0, PW, PH): include/leafhip.h, "Charts"
+CHART_HSV_RECT = (528, 40, 384, 240)
+CHART_HUES_RECT = (520, 370, 400, 220)
+CHART_REGION_SLOT, CHART_HUE_SLOT, CHART_HSV_PITCH = 30, 80, 6
+CHART_CURVE_COLOURS = ((255, 127, 14), (44, 160, 44), (31, 119, 180))   # tab:orange, tab:green, tab:blue
+CHART_TITLES = ("Colour regions", "HSV histograms (leaf pixels)", "Hue ranges (pixels)")
+CHART_TITLE_AT, CHART_TITLE_SCALE = (16, 8), 2            # a title's origin inside its panel
+CHART_LABEL_GAP = 6                                       # between a plot rectangle and the labels beside or under it
+CHART_SUMMARY_AT, CHART_SUMMARY_PITCH, CHART_SUMMARY_SCALE = (16, 16), 20, 2
+HIST_STATUSES = ("Feuillage majoritairement sain", "Signes significatifs de maladie", "Possible jaunissement/stress",
+                 "Etat mixte ou indetermine")
+_BLACK = (0, 0, 0)
+
+
+def _ascii(s: str) -> str:
+    """The ASCII fold of a name (the 5x7 font has ASCII only): accents dropped, anything else non-ASCII too."""
+    import unicodedata
+    return unicodedata.normalize("NFKD", s).encode("ascii", "ignore").decode("ascii")
+
+
+REGION_NAMES = tuple(_ascii(k) for k in REGION_KEYS)
+HUE_NAMES = tuple(_ascii(k.split(" ")[0]) for k in HUE_KEYS)
+
+
+def _hist_counts(counts):
+    """(total, the 8 region counts, the 5 hue counts) of one row of hsv_region_stats' counts as Python ints, read as
+    the figure kernel reads them: negative numbers are zero, a region over the total is the total."""
+    row = [int(v) for v in np.asarray(counts).reshape(-1)]
+    if len(row) != 14:
+        raise ValueError(f"expected the 14 counts of one image, got {len(row)}")
+    total = max(row[0], 0)
+    return total, [min(max(c, 0), total) for c in row[1:9]], [max(c, 0) for c in row[9:14]]
+
+
+def _tenths(c: int, total: int) -> str:
+    """c of total as a percentage with one decimal, rounded half up in integers."""
+    p10 = (c * 1000 + total // 2) // total
+    return f"{p10 // 10}.{p10 % 10}%"
+
+
+def hist_summary(counts):
+    """The summary panel of apply_histogram_filter (hist.py:202-232) for one image's 14 counts, as data: (lines,
+    status).  lines: "ANALYSE DES COULEURS:", "", "Pixels analyses: 12,345", "", up to six "- Name: 12.3%" for the
+    regions with at least 0.5 % (c * 200 >= total), by count descending with ties in REGION_KEYS order, "",
+    "ETAT: <status>".  status, by integer comparisons in the reference's order: 2 (Vert Sain + Vert Jaunatre) > total,
+    else 10 (Brun/Orange + Rouge + Jaune) > 3 total, else 5 Jaune > total, else (and without leaf pixels) the last of
+    HIST_STATUSES.  The wording is the reference's without accents."""
+    total, reg, _hues = _hist_counts(counts)
+    lines = ["ANALYSE DES COULEURS:", "", f"Pixels analyses: {total:,}", ""]
+    if total > 0:
+        order = sorted(range(8), key=lambda i: -reg[i])[:6]   # sorted is stable: ties keep REGION_KEYS order
+        lines += [f"- {REGION_NAMES[i]}: {_tenths(reg[i], total)}" for i in order if reg[i] * 200 >= total]
+    c = dict(zip(REGION_NAMES, reg))
+    if total > 0 and 2 * (c["Vert Sain"] + c["Vert Jaunatre"]) > total:
+        status = HIST_STATUSES[0]
+    elif total > 0 and 10 * (c["Brun/Orange"] + c["Rouge"] + c["Jaune"]) > 3 * total:
+        status = HIST_STATUSES[1]
+    elif total > 0 and 5 * c["Jaune"] > total:
+        status = HIST_STATUSES[2]
+    else:
+        status = HIST_STATUSES[3]
+    lines += ["", f"ETAT: {status}"]
+    return lines, status
+
+
+def hist_figure_texts(counts):
+    """The lettering of the Hist figures of a batch, as ops.draw_text_u8's items (image, x, y, string, (r, g, b),
+    scale), from the host array counts [N,14] (or [14]): per image the three panel titles; under the regions panel
+    the ticks 0 25 50 75 100, left of it the region names, at the end of each bar its percentage; in the HSV panel
+    the legend H S V in the curve colours and the ticks 0 64 128 192 under it; above each hue bar its count, under
+    it the first word of its name; the summary (hist_summary) in the lower left panel.  Bar ends are computed by
+    the kernel's integer formulas, so a label sits where its bar ends."""
+    rows = np.asarray(counts)
+    rows = rows.reshape(1, -1) if rows.ndim == 1 else rows
+    items = []
+    for n, row in enumerate(rows):
+        total, reg, hues = _hist_counts(row)
+
+        def put(x, y, s, colour=_BLACK, scale=1):
+            items.append((n, int(x), int(y), s, colour, scale))
+
+        for (px, py), title in zip(((0, 0), (CHART_PANEL_W, 0), (CHART_PANEL_W, CHART_PANEL_H)), CHART_TITLES):
+            put(px + CHART_TITLE_AT[0], py + CHART_TITLE_AT[1], title, scale=CHART_TITLE_SCALE)
+        # colour regions
+        x0, y0, pw, ph = CHART_REGIONS_RECT
+        for k in range(5):
+            s = str(25 * k)
+            put(x0 + k * pw // 4 - 3 * len(s), y0 + ph + CHART_LABEL_GAP, s)
+        for i, name in enumerate(REGION_NAMES):
+            y = y0 + CHART_REGION_SLOT * i + (CHART_REGION_SLOT - 7) // 2
+            put(x0 - CHART_LABEL_GAP - 6 * len(name), y, name)
+            if total > 0:
+                put(x0 + (reg[i] * pw + total // 2) // total + 4, y, _tenths(reg[i], total))
+        # HSV histograms
+        x0, y0, pw, ph = CHART_HSV_RECT
+        for k, (name, colour) in enumerate(zip("HSV", CHART_CURVE_COLOURS)):
+            put(x0 + pw - 56 + 16 * k, y0 + 6, name, colour, 2)
+        for v in (0, 64, 128, 192):
+            s = str(v)
+            put(x0 + (CHART_HSV_PITCH * v + 3) // 4 - 3 * len(s), y0 + ph + CHART_LABEL_GAP, s)
+        # hue ranges
+        x0, y0, pw, ph = CHART_HUES_RECT
+        m = max([1] + hues)
+        for i, name in enumerate(HUE_NAMES):
+            mid = x0 + CHART_HUE_SLOT * i + CHART_HUE_SLOT // 2
+            s = str(hues[i])
+            put(mid - 3 * len(s), y0 + ph - (hues[i] * ph + m // 2) // m - 10, s)
+            put(mid - 3 * len(name), y0 + ph + CHART_LABEL_GAP, name)
+        # the summary
+        for k, line in enumerate(hist_summary(row)[0]):
+            if line:
+                put(CHART_SUMMARY_AT[0], CHART_PANEL_H + CHART_SUMMARY_AT[1] + CHART_SUMMARY_PITCH * k, line,
+                    scale=CHART_SUMMARY_SCALE)
+    return items
+
+
+def hist_figure_batch(batch, stats=None):
+    """apply_histogram_filter for a same-size batch [N,H,W,3] uint8 on the device: ops.hsv_region_stats (or its
+    result (counts, hist) on the device, handed in as `stats`; the batch is then not read), the figure kernel and the
+    lettering, one launch each.  Returns (pictures [N,640,960,3] uint8 on the device, (counts [N,14], hist [N,3,256])
+    as numpy on the host)."""
+    if stats is None:
+        stats = ops.hsv_region_stats(_device_u8(batch, 4, "hist_figure_batch.batch"))
+    counts, hist = stats
+    host = (counts.cpu().numpy(), hist.cpu().numpy())
+    pictures = ops.hist_figure_u8(counts, hist)
+    return ops.draw_text_u8(pictures, hist_figure_texts(host[0])), host
+
+
+def apply_histogram_filter(rgb: np.ndarray, cfg=None) -> np.ndarray:
+    """srcs/transform/filters/hist.py:181-297 for one HxWx3 uint8 RGB image: the 960 x 640 report as an RGB array:
+    the colour regions as bars, the H, S and V histograms of the leaf pixels as curves, the summary with the health
+    status, and the hue ranges as bars (where the reference has a pie).  Drawn by the project's own chart and text
+    rules (include/leafhip.h), no parity with matplotlib's pixels.  cfg is not read (hist.py does not read it)."""
+    return hist_figure_batch(_rgb_batch(rgb))[0][0].cpu().numpy()
