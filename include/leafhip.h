@@ -221,6 +221,33 @@ int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int
                       int n, int h, int w, const lf_brown_params* params, void* workspace, size_t ws_bytes,
                       lf_stream_t stream);
 
+/* Lesions: the components lf_brown_spots_u8 keeps for the same (rgb, mask, params), as a table of integers.  The
+ * pipeline is that function's, stated once in the library: leaf = mask > 0; the brown predicate on the pixel as
+ * handed in, inside the leaf; MORPH_OPEN then MORPH_CLOSE with the (k, k) MORPH_ELLIPSE element; the 8-connected
+ * components of area >= min_area_px are the lesions.
+ * rgb [N,H,W,3], mask [N,H,W] -> table [N][cap][LF_LESION_FIELDS] int64, counts [N] int32, flags [N] int32.
+ * counts[n] is the true number of lesions of image n, also when it exceeds cap.  One row per lesion, in raster order
+ * of the lesion's first pixel (topmost row first, then leftmost column); rows at and after min(counts[n], cap) are
+ * zero.  The fields:
+ *    0 area: pixels;  1..4 x0, y0, bw, bh: the tight bounding box;
+ *    5, 6 sum_x, sum_y: sums of the pixel coordinates (the centroid is sum / area, formed by the caller);
+ *    7..9 sum_r, sum_g, sum_b: sums of the input image's channels over the lesion's pixels;
+ *    10 border_px: lesion pixels with at least one 4-neighbour that is not in the lesion (outside the image counts as
+ *       not in it);
+ *    11 margin_px: lesion pixels with at least one 4-neighbour that is not leaf (mask == 0, or outside the image).
+ * flags [N]: bit 0 the image has at least one lesion; bit 1 counts[n] > cap, the table holds the first cap; bit 2 a
+ * union-find step bound was hit (a bug: treat as an error).
+ * Integer arithmetic throughout; the only atomics are integer adds, minima and maxima, whose result does not depend
+ * on their order, so two launches on the same inputs give the same bits.  One workgroup per image, the planes in LDS:
+ * an image must fit as for lf_brown_spots_u8 (two bit planes, 140 KiB).  Checked before any launch, with nothing
+ * written: that limit, n <= 65535, 1 <= morph_kernel <= 31, cap >= 1, the workspace's size
+ * (lf_lesion_table_workspace) and its 256-byte alignment.  Parity unpinned (no cv2). */
+#define LF_LESION_FIELDS 12
+size_t lf_lesion_table_workspace(int n, int h, int w);
+int lf_lesion_table(const uint8_t* rgb, const uint8_t* mask, int64_t* table, int32_t* counts, int32_t* flags,
+                    int n, int h, int w, int cap, const lf_brown_params* params, void* workspace, size_t ws_bytes,
+                    lf_stream_t stream);
+
 /* apply_roi_filter (srcs/transform/filters/roi.py) for a batch, reading the contour buffer lf_make_mask_u8 made
  * (contour [N,cap,2] int32 (x, y), counts [N]; counts[i] <= cap, points inside the image): bbox [N][4] int32
  * (x, y, w, h) = cv2.boundingRect; canvas [N,roi_h,roi_w,3] = the box letterboxed into the canvas (INTER_AREA,

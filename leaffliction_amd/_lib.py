@@ -70,6 +70,8 @@ SIGNATURES = {
                         c_size_t, P],
     "lf_brown_spots_workspace": [c_int, c_int, c_int],
     "lf_brown_spots_u8": [P, P, P, P, P, c_int, c_int, c_int, P, P, c_size_t, P],
+    "lf_lesion_table_workspace": [c_int, c_int, c_int],
+    "lf_lesion_table": [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P],
     "lf_roi_u8": [P, P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P],
     "lf_shape_stats": [P, P, c_int, P, P, P, P, c_int, c_int, c_int, P],
     "lf_analyze_overlay_u8": [P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, P],
@@ -177,7 +179,7 @@ _RESTYPES = {"lf_last_error": C.c_char_p, "lf_conv2d_wgrad_workspace": c_size_t,
              "lf_dwconv3x3_bwd_workspace": c_size_t,
              "lf_bn_workspace": c_size_t, "lf_se_bwd_workspace": c_size_t,
              "lf_adamw_workspace": c_size_t, "lf_conv2d_stats_tiles": C.c_longlong,
-             "lf_blur_saliency_workspace": c_size_t, "lf_inclusive_mask_workspace": c_size_t, "lf_make_mask_workspace": c_size_t, "lf_brown_spots_workspace": c_size_t, "lf_canny_workspace": c_size_t, "lf_clahe_workspace": c_size_t,
+             "lf_blur_saliency_workspace": c_size_t, "lf_inclusive_mask_workspace": c_size_t, "lf_make_mask_workspace": c_size_t, "lf_brown_spots_workspace": c_size_t, "lf_lesion_table_workspace": c_size_t, "lf_canny_workspace": c_size_t, "lf_clahe_workspace": c_size_t,
              "lf_good_features_workspace": c_size_t, "lf_landmarks_workspace": c_size_t,
              "lf_conv2d_bf16_weight_elems": c_size_t,
              "lf_conv2d_bf16_act_mean_workspace": c_size_t,

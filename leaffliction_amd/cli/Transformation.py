@@ -53,6 +53,14 @@ order: shape, hull and axes from make_mask's contour (ops.shape_stats), the brow
 inside the mask (transform.measure_leaves).  FILE defaults to measurements.csv in the output directory; in
 single-image mode put the flag after the image path, or write --measure=FILE.
 
+`--lesions [FILE]` writes the numeric counterpart of the Brown picture as one CSV table, a row per brown spot: its
+area and share of the leaf, bounding box, centroid, mean colour, equivalent diameter, and how many of its pixels lie
+on its own border and on the leaf's margin (transform.measure_lesions, from the mask and white composite `--measure`
+and Brown use, made once).  Files in job order, lesions in raster order of their first pixels; a processed leaf
+without lesions gets one row with lesion 0 and empty cells; a leaf with more than filters.LESION_CAP lesions keeps
+the first ones and is warned about.  FILE defaults to lesions.csv in the output directory and is parsed like
+--measure's.
+
 `create_transform_function` (at the end of the module) is the reference's training transform, the provider of
 ManifestSequence's `transform=` hook: see TransformFunction.
 """
@@ -182,6 +190,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--measure", nargs="?", const="", default=None, metavar="FILE",
                    help="Write leaf measurements (shape, hull, axes, brown share, edge count) of every processed "
                         "image as CSV (default FILE: measurements.csv in the output directory)")
+    p.add_argument("--lesions", nargs="?", const="", default=None, metavar="FILE",
+                   help="Write one CSV row per brown spot of every processed image: area, box, centroid, mean colour, "
+                        "border and leaf-margin pixels (default FILE: lesions.csv in the output directory)")
     return p.parse_args(argv)
 
 
@@ -274,7 +285,7 @@ def encode_jpeg_batch(x) -> List[bytes]:
 
 
 def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlays: bool = False,
-                    landmarks: bool = False, figures: bool = False) -> Dict[str, object]:
+                    landmarks: bool = False, figures: bool = False, lesions: bool = False) -> Dict[str, object]:
     """process_single_image's data flow for a same-size batch [N,H,W,3] uint8 on the device.  Returns the device
     outputs of the requested ported types ("Mask", "Blur", "ROI", "Brown": [N,H,W,3] uint8), "brown_stats"
     (percentages, counts, areas) with Brown, and "hist" (counts, histograms as numpy) with Hist.  measure: also
@@ -284,7 +295,9 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
     the table.  landmarks: with Landmarks among the types also "Landmarks" [N,H,W,3] uint8, landmarks_filter_batch on
     `masked` with the original's contour and the mask made from `masked` (the one Blur makes, made once), and
     "landmark_counts", per image (border, vein, disease).  figures: with Hist among the types also "Hist"
-    [N,640,960,3] uint8, hist_figure_batch's picture of the same numbers; "hist" stays as it is."""
+    [N,640,960,3] uint8, hist_figure_batch's picture of the same numbers; "hist" stays as it is.  lesions: also
+    "lesions", transform.measure_lesions' result, from the same make_mask result and white composite; no other output
+    changes."""
     import torch
 
     from .. import ops
@@ -293,7 +306,7 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
     masked = x
     stats = None
     wants_mask = any(t in types for t in MASK_TYPES)
-    if measure or wants_mask:
+    if measure or lesions or wants_mask:
         mask, contour, counts, _fb = F.make_masks_device(x, cfg)
         white = ops.mask_composite_u8(x, mask, "white")
         if wants_mask:   # a mask made for the table alone leaves Hist on the image, as without --measure
@@ -331,6 +344,8 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
         if measure:
             res["measure"] = F.measure_leaves(x, cfg, masks=(mask, contour, counts, _fb), brown_stats=stats,
                                               masked=white, shape=shape)[0]
+        if lesions:
+            res["lesions"] = F.measure_lesions(x, cfg, masks=(mask, contour, counts, _fb), masked=white)
     if "Hist" in types:
         stats_h = ops.hsv_region_stats(masked.contiguous())
         if figures:
@@ -343,8 +358,10 @@ def transform_batch(x, types: Sequence[str], cfg, measure: bool = False, overlay
 class _Runner:
     def __init__(self, types: Tuple[str, ...], cfg, skip_existing: bool, overwrite: bool, pool: ThreadPoolExecutor,
                  measure: bool = False, overlays: bool = False, landmarks: bool = False, mosaic: bool = False,
-                 figures: bool = False):
+                 figures: bool = False, lesions: bool = False):
         self.types, self.cfg, self.pool = types, cfg, pool
+        self.lesions = lesions
+        self.lesion_rows: Dict[Path, List[List[str]]] = {}   # --lesions: image path -> CSV rows after `file`
         self.measure, self.overlays, self.landmarks, self.mosaic = measure, overlays, landmarks, mosaic
         self.figures = figures
         self.rows: Dict[Path, List[str]] = {}   # --measure: image path -> CSV cells after `file`
@@ -373,16 +390,25 @@ class _Runner:
         saved: List[Path] = []
         dev = _device()
         h, w = items[0][2].shape[:2]
-        measure = self.measure and ops.make_mask_fits(h, w, self.cfg.mask_upscale_factor,
-                                                      self.cfg.mask_upscale_long_side)
+        fits = ops.make_mask_fits(h, w, self.cfg.mask_upscale_factor, self.cfg.mask_upscale_long_side)
+        measure, lesions = self.measure and fits, self.lesions and fits
         for c0 in range(0, len(items), CHUNK):
             chunk = items[c0:c0 + CHUNK]
             x = torch.from_numpy(np.stack([a for _p, _d, a in chunk])).to(dev)
-            res = transform_batch(x, self.types, self.cfg, measure, self.overlays, self.landmarks, self.figures)
+            res = transform_batch(x, self.types, self.cfg, measure, self.overlays, self.landmarks, self.figures,
+                                  lesions)
             if measure:
                 from ..transform.filters import measure_row
                 for i, (p, _d, _a) in enumerate(chunk):
                     self.rows[p] = measure_row(res["measure"], i)
+            if lesions:
+                from ..transform.filters import LESION_CAP, lesion_rows
+                cols, found, truncated = res["lesions"]
+                for i, (p, _d, _a) in enumerate(chunk):
+                    self.lesion_rows[p] = lesion_rows(cols[i])
+                    if truncated[i]:
+                        logging.warning("%s has %d lesions: the table holds the first %d", p, int(found[i]),
+                                        LESION_CAP)
             names = [output_names(p.stem) for p, _d, _a in chunk]
             # process_single_image's order; Hist last, where the matplotlib figure is written too
             for t in ("Mask", "Blur", "ROI", "Analyze", "Landmarks", "Brown", "Hist"):
@@ -439,8 +465,8 @@ class _Runner:
 
     def run(self, jobs: List[Tuple[Path, Path]]) -> List[Path]:
         """jobs: (image path, output directory).  Decodes WINDOW files ahead on the host threads; unreadable files
-        and images over make_mask's size limit are logged and skipped; where only --measure needs the mask, such an
-        image keeps its outputs and gets no row."""
+        and images over make_mask's size limit are logged and skipped; where only --measure or --lesions needs the
+        mask, such an image keeps its outputs and gets no row."""
         from .. import ops
         saved: List[Path] = []
         needs_mask = any(t in self.types for t in MASK_TYPES)
@@ -467,6 +493,9 @@ class _Runner:
                 if self.measure and not needs_mask and not ops.make_mask_fits(
                         h, w, self.cfg.mask_upscale_factor, self.cfg.mask_upscale_long_side):
                     logging.error("No measurements for %s: %d x %d is over make_mask's size limit", path, h, w)
+                if self.lesions and not needs_mask and not ops.make_mask_fits(
+                        h, w, self.cfg.mask_upscale_factor, self.cfg.mask_upscale_long_side):
+                    logging.error("No lesion rows for %s: %d x %d is over make_mask's size limit", path, h, w)
                 groups.setdefault((h, w), []).append((path, out_dir, rgb))
             for items in groups.values():
                 saved.extend(self.run_group(items))
@@ -487,6 +516,23 @@ def write_measurements(path: Path, jobs: Sequence[Tuple[Path, Path]], rows: Dict
         for p, _d in jobs:
             if p in rows:
                 out.writerow([p.relative_to(root).as_posix() if root else p.name] + rows[p])
+
+
+def write_lesions(path: Path, jobs: Sequence[Tuple[Path, Path]], rows: Dict[Path, List[List[str]]],
+                  root: Optional[Path] = None) -> None:
+    """The --lesions table: the header, then the rows of every processed image in the order of `jobs`, lesions in
+    table order; `file` as write_measurements writes it."""
+    import csv
+
+    from ..transform.filters import LESION_COLUMNS
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        out = csv.writer(f)
+        out.writerow(("file",) + LESION_COLUMNS)
+        for p, _d in jobs:
+            name = p.relative_to(root).as_posix() if root else p.name
+            for cells in rows.get(p, ()):
+                out.writerow([name] + cells)
 
 
 def _workers(n: int) -> int:
@@ -519,11 +565,14 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         out_d.mkdir(parents=True, exist_ok=True)
         with ThreadPoolExecutor(_workers(args.workers)) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays, args.landmarks, args.mosaic, args.figures)
+                             args.overlays, args.landmarks, args.mosaic, args.figures, args.lesions is not None)
             saved = runner.run([(ip, out_d)])
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else out_d / "measurements.csv", [(ip, out_d)],
                                runner.rows)
+        if runner.lesions:
+            write_lesions(Path(args.lesions) if args.lesions else out_d / "lesions.csv", [(ip, out_d)],
+                          runner.lesion_rows)
         print(f"Saved {len(saved)} outputs to {out_d}")
         for s in saved:
             print(f"  - {s}")
@@ -545,11 +594,14 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         jobs = [(p, dst) for p in imgs]
         with ThreadPoolExecutor(n_threads) as pool:
             runner = _Runner(types, cfg, args.skip_existing, args.overwrite, pool, args.measure is not None,
-                             args.overlays, args.landmarks, args.mosaic, args.figures)
+                             args.overlays, args.landmarks, args.mosaic, args.figures, args.lesions is not None)
             saved = runner.run(jobs)
         if runner.measure:
             write_measurements(Path(args.measure) if args.measure else dst / "measurements.csv", jobs, runner.rows,
                                root=src)
+        if runner.lesions:
+            write_lesions(Path(args.lesions) if args.lesions else dst / "lesions.csv", jobs, runner.lesion_rows,
+                          root=src)
         logging.info("Processed %d images, saved %d outputs", len(imgs), len(saved))
         return
 

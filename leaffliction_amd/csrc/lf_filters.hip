@@ -2045,6 +2045,20 @@ int lf_make_mask_u8(const uint8_t* rgb, uint8_t* mask, int32_t* contour, int32_t
 // ===========================================================================
 namespace {
 
+// The pipeline above up to its labelling, for brown_spots_kernel and lesion_table_kernel: P.A = the predicate
+// inside the leaf, opened and closed; its runs, their roots (flattened) and the components' areas.  P.B is scratch.
+__device__ void brown_label(const Post& P, const HsvTabs& H, const LabTabs& T, const uint8_t* img, const uint8_t* lm,
+                            const MaskArgs& a) {
+    const int w = P.w;
+    build_plane(P, P.A, kMaskT,
+                [&](int y, int x) { return lm[y * w + x] > 0 && brown_px(H, T, img + 3 * (y * w + x), a); });
+    morph_se(P, P.A, P.B, a.se_brown, true, kMaskT);   // MORPH_OPEN
+    morph_se(P, P.B, P.A, a.se_brown, false, kMaskT);
+    morph_se(P, P.A, P.B, a.se_brown, false, kMaskT);  // MORPH_CLOSE
+    morph_se(P, P.B, P.A, a.se_brown, true, kMaskT);
+    label_runs(P, P.A, true);
+}
+
 __global__ __launch_bounds__(kMaskT) void brown_spots_kernel(const uint8_t* __restrict__ rgb,
                                                              const uint8_t* __restrict__ leaf_mask,
                                                              const uint16_t* __restrict__ lab_tabs, Run* __restrict__ runs,
@@ -2069,13 +2083,7 @@ __global__ __launch_bounds__(kMaskT) void brown_spots_kernel(const uint8_t* __re
     int leaf = 0;
     for (int p = threadIdx.x; p < h * w; p += kMaskT) leaf += lm[p] > 0;
     atomicAdd(&s_leaf, leaf);
-    build_plane(P, P.A, kMaskT,
-                [&](int y, int x) { return lm[y * w + x] > 0 && brown_px(H, T, img + 3 * (y * w + x), a); });
-    morph_se(P, P.A, P.B, a.se_brown, true, kMaskT);   // MORPH_OPEN
-    morph_se(P, P.B, P.A, a.se_brown, false, kMaskT);
-    morph_se(P, P.A, P.B, a.se_brown, false, kMaskT);  // MORPH_CLOSE
-    morph_se(P, P.B, P.A, a.se_brown, true, kMaskT);
-    label_runs(P, P.A, true);
+    brown_label(P, H, T, img, lm, a);
     const int nr = *P.nruns;
     int cnt = 0, px = 0;
     for (int k = threadIdx.x; k < nr; k += kMaskT) {
@@ -2113,6 +2121,21 @@ struct BrownWs {
     }
 };
 
+// the kernel's view of lf_brown_params (morph_kernel checked by the caller)
+MaskArgs brown_args(const lf_brown_params* prm) {
+    MaskArgs a{};
+    a.use_lab = prm->use_lab_brown;
+    a.hue_lo = prm->hue_lo;
+    a.hue_hi = prm->hue_hi;
+    a.s_min = prm->s_min;
+    a.v_max = prm->v_max;
+    a.a_min = prm->lab_a_min;
+    a.b_min = prm->lab_b_min;
+    a.brown_min_area = prm->min_area_px;
+    a.se_brown = ellipse_rows(prm->morph_kernel);
+    return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2143,22 +2166,178 @@ int lf_brown_spots_u8(const uint8_t* rgb, const uint8_t* mask, uint8_t* out, int
     hipStream_t s = lf::as_stream(stream);
     const BrownWs ws(workspace, n, h, w);
 
-    MaskArgs a{};
-    a.use_lab = prm->use_lab_brown;
-    a.hue_lo = prm->hue_lo;
-    a.hue_hi = prm->hue_hi;
-    a.s_min = prm->s_min;
-    a.v_max = prm->v_max;
-    a.a_min = prm->lab_a_min;
-    a.b_min = prm->lab_b_min;
-    a.brown_min_area = prm->min_area_px;
-    a.se_brown = ellipse_rows(prm->morph_kernel);
-
+    const MaskArgs a = brown_args(prm);
     const int rc = upload_lab_tables(ws.lb.tabs, s, "lf_brown_spots");
     if (rc != LF_OK) return rc;
     brown_spots_kernel<<<n, kMaskT, lds, s>>>(rgb, mask, ws.lb.tabs, ws.lb.rn, ws.lb.parent, ws.lb.area,
                                               (int)mask_runs_per_image(h, w), h, w, (w + 31) / 32, a, out, stats, flags);
     return lf::check_launch("lf_brown_spots");
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// The lesion table: one row of integers per component lf_brown_spots_u8 keeps (brown_label and the area test, the
+// pipeline above), in raster order of the components' first pixels, which is the order of label_runs' roots.  One
+// workgroup per image, the same two bit planes in LDS.
+//  * a prefix count over the runs gives every kept root its row; its owner writes the area and seeds the bounding box
+//    with the root run (the component's topmost row);
+//  * a lane per run adds the run's closed forms (sum x, sum y, the box) and what its pixels give (the colour sums and
+//    the two neighbour tests) to the row with 64-bit integer adds, minima and maxima: no order to depend on.
+// A 4-neighbour that is set in P.A belongs to the pixel's own component, so "not in the lesion" is "not set in P.A".
+// ===========================================================================
+namespace {
+
+__device__ __forceinline__ long long ld_i64(const long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void add_i64(long long* p, long long v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(kMaskT) void lesion_table_kernel(const uint8_t* __restrict__ rgb,
+                                                              const uint8_t* __restrict__ leaf_mask,
+                                                              const uint16_t* __restrict__ lab_tabs, Run* __restrict__ runs,
+                                                              int* __restrict__ parent, int* __restrict__ area,
+                                                              int runs_per_image, int h, int w, int wpr, MaskArgs a,
+                                                              long long* __restrict__ table, int* __restrict__ counts,
+                                                              int* __restrict__ flags, int cap) {
+    extern __shared__ unsigned lds_planes[];
+    __shared__ HsvTabs H;
+    __shared__ LabTabs T;
+    __shared__ PostLds S;
+    __shared__ int s_roots[kMaskT];
+    __shared__ int s_total;
+    constexpr int F = LF_LESION_FIELDS;
+    const size_t n = blockIdx.x;
+    const Post P = post_view(lds_planes, 2, S, runs, parent, area, runs_per_image, h, w, wpr, kMaskT);
+    H.fill(kMaskT);
+    T.fill(lab_tabs, kMaskT);
+    const uint8_t* img = rgb + n * (size_t)h * w * 3;
+    const uint8_t* lm = leaf_mask + n * (size_t)h * w;
+    long long* tab = table + n * (size_t)cap * F;
+    for (size_t i = threadIdx.x; i < (size_t)cap * F; i += kMaskT) tab[i] = 0;
+    __syncthreads();
+
+    brown_label(P, H, T, img, lm, a);
+
+    // rows: thread t owns the runs [k0, k1); the kept roots before k0 are the rows before its first
+    const int nr = *P.nruns;
+    const int chunk = (nr + kMaskT - 1) / kMaskT;
+    const int k0 = min(nr, (int)threadIdx.x * chunk), k1 = min(nr, k0 + chunk);
+    int mine = 0;
+    for (int k = k0; k < k1; ++k) mine += P.par[k] == k && P.area[k] >= a.brown_min_area;
+    s_roots[threadIdx.x] = mine;
+    __syncthreads();
+    int row = 0;
+    for (int t = 0; t < (int)threadIdx.x; ++t) row += s_roots[t];
+    if (threadIdx.x == kMaskT - 1) s_total = row + mine;
+    for (int k = k0; k < k1; ++k) {
+        if (P.par[k] != k) continue;
+        const int ar = P.area[k];
+        int slot = -1;
+        if (ar >= a.brown_min_area) {
+            if (row < cap) slot = row;
+            ++row;
+        }
+        P.area[k] = slot;   // from here on area[root] is the component's row; -1: not in the table
+        if (slot < 0) continue;
+        const Run r = P.rn[k];
+        long long* o = tab + (size_t)slot * F;
+        o[0] = ar;
+        o[1] = r.x0;   // least x so far
+        o[2] = r.y;    // the root run lies in the component's topmost row
+        o[3] = r.x1;   // greatest x so far
+        o[4] = r.y;    // greatest y so far
+    }
+    __threadfence();
+    __syncthreads();
+
+    for (int k = threadIdx.x; k < nr; k += kMaskT) {
+        const int slot = ld_par(P.area, P.par[k]);
+        if (slot < 0) continue;
+        const Run r = P.rn[k];
+        const int y = r.y, x0 = r.x0, x1 = r.x1;
+        int sr = 0, sg = 0, sb = 0, border = 0, margin = 0;
+        for (int x = x0; x <= x1; ++x) {
+            const size_t p = (size_t)y * w + x;
+            sr += img[3 * p];
+            sg += img[3 * p + 1];
+            sb += img[3 * p + 2];
+            const bool inside = x > x0 && x < x1 && bit_at(P, P.A, x, y - 1) && bit_at(P, P.A, x, y + 1);
+            border += !inside;
+            const bool in_leaf = y > 0 && lm[p - w] > 0 && y < h - 1 && lm[p + w] > 0 && x > 0 && lm[p - 1] > 0 &&
+                                 x < w - 1 && lm[p + 1] > 0;
+            margin += !in_leaf;
+        }
+        const long long len = x1 - x0 + 1;
+        long long* o = tab + (size_t)slot * F;
+        __hip_atomic_fetch_min(o + 1, (long long)x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(o + 3, (long long)x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(o + 4, (long long)y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        add_i64(o + 5, len * (x0 + x1) / 2);
+        add_i64(o + 6, len * y);
+        add_i64(o + 7, sr);
+        add_i64(o + 8, sg);
+        add_i64(o + 9, sb);
+        add_i64(o + 10, border);
+        add_i64(o + 11, margin);
+    }
+    __threadfence();
+    __syncthreads();
+
+    const int total = s_total;
+    for (int i = threadIdx.x; i < min(total, cap); i += kMaskT) {   // greatest x, y -> width, height
+        long long* o = tab + (size_t)i * F;
+        const long long bx = ld_i64(o + 1), by = ld_i64(o + 2), mx = ld_i64(o + 3), my = ld_i64(o + 4);
+        o[3] = mx - bx + 1;
+        o[4] = my - by + 1;
+    }
+    if (threadIdx.x == 0) {
+        counts[n] = total;
+        flags[n] = (total > 0 ? 1 : 0) | (total > cap ? 2 : 0) | (S.status & kFlagBound);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lf_lesion_table_workspace(int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return BrownWs(nullptr, n, h, w).bytes;
+}
+
+int lf_lesion_table(const uint8_t* rgb, const uint8_t* mask, int64_t* table, int32_t* counts, int32_t* flags, int n,
+                    int h, int w, int cap, const lf_brown_params* prm, void* workspace, size_t ws_bytes,
+                    lf_stream_t stream) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "the table is written as long long");
+    LF_REQUIRE(rgb && mask && table && counts && flags && prm && workspace, "lf_lesion_table: null buffer");
+    LF_REQUIRE(n > 0 && h > 0 && w > 0, "lf_lesion_table: bad dims n=%d %dx%d", n, h, w);
+    LF_REQUIRE(n <= 65535, "lf_lesion_table: batch too large for the grid");
+    LF_REQUIRE(h <= 65535 && w <= 65535, "lf_lesion_table: image too large (%d x %d)", h, w);
+    LF_REQUIRE(cap >= 1, "lf_lesion_table: cap %d below 1", cap);
+    const size_t lds = post_lds_bytes(2, h, (w + 31) / 32);
+    LF_REQUIRE(lds <= kMaskLdsCap,
+               "lf_lesion_table: a %d x %d image needs %zu bytes of LDS for its two bit planes (limit %zu, one "
+               "workgroup per image)", h, w, lds, kMaskLdsCap);
+    LF_REQUIRE(prm->morph_kernel >= 1 && prm->morph_kernel <= 31,
+               "lf_lesion_table: brown_morph_kernel %d outside [1, 31]", prm->morph_kernel);
+    LF_REQUIRE(ws_bytes >= lf_lesion_table_workspace(n, h, w), "lf_lesion_table: workspace too small (%zu < %zu)",
+               ws_bytes, lf_lesion_table_workspace(n, h, w));
+    LF_REQUIRE((reinterpret_cast<size_t>(workspace) & 255) == 0, "lf_lesion_table: workspace must be 256-byte aligned");
+    LF_REQUIRE(lds <= dynamic_lds_cap<lesion_table_kernel>(kMaskLdsCap, 48 * 1024),
+               "lf_lesion_table: could not raise the LDS limit of the lesion kernel");
+
+    hipStream_t s = lf::as_stream(stream);
+    const BrownWs ws(workspace, n, h, w);
+    const MaskArgs a = brown_args(prm);
+    const int rc = upload_lab_tables(ws.lb.tabs, s, "lf_lesion_table");
+    if (rc != LF_OK) return rc;
+    lesion_table_kernel<<<n, kMaskT, lds, s>>>(rgb, mask, ws.lb.tabs, ws.lb.rn, ws.lb.parent, ws.lb.area,
+                                               (int)mask_runs_per_image(h, w), h, w, (w + 31) / 32, a,
+                                               reinterpret_cast<long long*>(table), counts, flags, cap);
+    return lf::check_launch("lf_lesion_table");
 }
 
 }  // extern "C"

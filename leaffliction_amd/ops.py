@@ -390,6 +390,25 @@ def make_mask_u8(x: torch.Tensor, green_hue_range=(25, 100), fill_size: int = 10
     return mask, cnt, counts_h.to(x.device), (flags_h & 1).bool().to(x.device)
 
 
+def _brown_inputs(who: str, x, mask, brown_hue_range, brown_s_min, brown_v_max, use_lab_brown, lab_a_min, lab_b_min,
+                  brown_min_area_px, brown_morph_kernel):
+    """The argument checks of the kernels that take (image batch, leaf masks, lf_brown_params): (n, h, w, the
+    parameter block as int32)."""
+    n, h, w = _hwc(x, f"{who}.x")
+    _chk(mask, _U8, f"{who}.mask", 3)
+    if tuple(mask.shape) != (n, h, w) or mask.device != x.device:
+        raise ValueError(f"{who}.mask: expected {[n, h, w]} on {x.device}, got {list(mask.shape)} on "
+                         f"{mask.device}")
+    if not 1 <= int(brown_morph_kernel) <= 31:
+        raise ValueError(f"{who}: brown_morph_kernel {brown_morph_kernel} outside [1, 31]")
+    prm = np.array([1 if use_lab_brown else 0, brown_hue_range[0], brown_hue_range[1], brown_s_min, brown_v_max,
+                    lab_a_min, lab_b_min, brown_min_area_px, brown_morph_kernel], dtype=np.int32)
+    if 2 * h * ((w + 31) // 32) * 4 + (h + 1) * 4 > 140 * 1024:
+        raise _lib.LeafHipError(f"{who}: a {h} x {w} image does not fit one workgroup's LDS (two bit planes, "
+                                "140 KiB)")
+    return n, h, w, prm
+
+
 def brown_spots_u8(x: torch.Tensor, mask: torch.Tensor, brown_hue_range=(0, 30), brown_s_min: int = 20,
                    brown_v_max: int = 200, use_lab_brown: bool = False, lab_a_min: int = 125, lab_b_min: int = 125,
                    brown_min_area_px: int = 25, brown_morph_kernel: int = 3):
@@ -397,19 +416,9 @@ def brown_spots_u8(x: torch.Tensor, mask: torch.Tensor, brown_hue_range=(0, 30),
     [N,H,W] uint8 (leaf = mask > 0).  Returns (overlay [N,H,W,3] uint8, stats [N,3] int32 {count, brown area, leaf
     area}).  Defaults: config.yaml.  An image must fit one workgroup's LDS (two bit planes, 140 KiB); larger ones
     raise LeafHipError before any launch."""
-    n, h, w = _hwc(x, "brown_spots.x")
-    _chk(mask, _U8, "brown_spots.mask", 3)
-    if tuple(mask.shape) != (n, h, w) or mask.device != x.device:
-        raise ValueError(f"brown_spots.mask: expected {[n, h, w]} on {x.device}, got {list(mask.shape)} on "
-                         f"{mask.device}")
-    if not 1 <= int(brown_morph_kernel) <= 31:
-        raise ValueError(f"brown_spots: brown_morph_kernel {brown_morph_kernel} outside [1, 31]")
-    prm = np.array([1 if use_lab_brown else 0, brown_hue_range[0], brown_hue_range[1], brown_s_min, brown_v_max,
-                    lab_a_min, lab_b_min, brown_min_area_px, brown_morph_kernel], dtype=np.int32)
+    n, h, w, prm = _brown_inputs("brown_spots", x, mask, brown_hue_range, brown_s_min, brown_v_max, use_lab_brown,
+                                 lab_a_min, lab_b_min, brown_min_area_px, brown_morph_kernel)
     lib = _lib.load()
-    if 2 * h * ((w + 31) // 32) * 4 + (h + 1) * 4 > 140 * 1024:
-        raise _lib.LeafHipError(f"brown_spots: a {h} x {w} image does not fit one workgroup's LDS (two bit planes, "
-                                "140 KiB)")
     ws = torch.empty(int(lib.lf_brown_spots_workspace(n, h, w)), dtype=_U8, device=x.device)
     out = torch.empty_like(x)
     stats = torch.empty((n, 3), dtype=_I32, device=x.device)
@@ -419,6 +428,36 @@ def brown_spots_u8(x: torch.Tensor, mask: torch.Tensor, brown_hue_range=(0, 30),
     if bool((flags & 4).any()):
         raise _lib.LeafHipError("lf_brown_spots_u8: a union-find step bound was hit")
     return out, stats
+
+
+LESION_FIELDS = ("area", "x0", "y0", "bw", "bh", "sum_x", "sum_y", "sum_r", "sum_g", "sum_b", "border_px",
+                 "margin_px")
+
+
+def lesion_table(x: torch.Tensor, mask: torch.Tensor, *, brown_hue_range=(0, 30), brown_s_min: int = 20,
+                 brown_v_max: int = 200, use_lab_brown: bool = False, lab_a_min: int = 125, lab_b_min: int = 125,
+                 brown_min_area_px: int = 25, brown_morph_kernel: int = 3, cap: int = 256):
+    """The lesions of a same-size batch [N,H,W,3] uint8 with its leaf masks [N,H,W] uint8: the components
+    brown_spots_u8 keeps for the same arguments, one row of integers each.  Returns (table [N,cap,12] int64 with the
+    columns LESION_FIELDS, counts [N] int32, flags [N] int32).  counts[i] is the true number of lesions; the table
+    holds the first min(counts[i], cap) in raster order of their first pixels and zeros after them; flags bit 0: the
+    image has a lesion, bit 1: counts[i] > cap.  The definitions: include/leafhip.h (lf_lesion_table).  Same limits
+    and errors as brown_spots_u8."""
+    n, h, w, prm = _brown_inputs("lesion_table", x, mask, brown_hue_range, brown_s_min, brown_v_max, use_lab_brown,
+                                 lab_a_min, lab_b_min, brown_min_area_px, brown_morph_kernel)
+    cap = int(cap)
+    if cap < 1:
+        raise ValueError(f"lesion_table: cap must be at least 1, got {cap}")
+    lib = _lib.load()
+    ws = torch.empty(int(lib.lf_lesion_table_workspace(n, h, w)), dtype=_U8, device=x.device)
+    table = torch.empty((n, cap, len(LESION_FIELDS)), dtype=torch.int64, device=x.device)
+    counts = torch.empty(n, dtype=_I32, device=x.device)
+    flags = torch.empty(n, dtype=_I32, device=x.device)
+    _lib.call("lf_lesion_table", x.data_ptr(), mask.data_ptr(), table.data_ptr(), counts.data_ptr(), flags.data_ptr(),
+              n, h, w, cap, prm.ctypes.data, ws.data_ptr(), ws.numel(), _stream())
+    if bool((flags & 4).any()):
+        raise _lib.LeafHipError("lf_lesion_table: a union-find step bound was hit")
+    return table, counts, flags
 
 
 def roi_u8(x: torch.Tensor, contour: torch.Tensor, counts: torch.Tensor, roi_size=(256, 256)):

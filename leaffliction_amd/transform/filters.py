@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import logging
 from dataclasses import dataclass, fields
-from typing import Callable, Dict, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -444,6 +444,68 @@ def measure_row(cols: Dict[str, np.ndarray], i: int) -> list:
         else:
             cells.append(repr(float(v)))
     return cells
+
+
+# One row per lesion: the CSV columns of `Transformation --lesions` after `file`.  `lesion` is 1-based; the integer
+# columns hold int64, the others float64.
+LESION_COLUMNS = ("lesion", "area", "leaf_pct", "bbox_x", "bbox_y", "bbox_w", "bbox_h", "centroid_x", "centroid_y",
+                  "mean_r", "mean_g", "mean_b", "equiv_diameter", "border_px", "margin_px")
+_LESION_FROM_TABLE = {"bbox_x": "x0", "bbox_y": "y0", "bbox_w": "bw", "bbox_h": "bh"}
+LESION_CAP = 256   # rows per image in the table; a leaf with more keeps its first LESION_CAP
+
+
+def measure_lesions(batch, cfg, masks=None, masked=None, cap: Optional[int] = None):
+    """Every brown spot of a same-size batch [N,H,W,3] uint8 (numpy or a CUDA tensor) as numbers: (rows: per image
+    {name: numpy [k]} for LESION_COLUMNS, k = min(count, cap) lesions in raster order of their first pixels,
+    counts int64 [N]: the true numbers of lesions, truncated bool [N]: counts > cap).  The lesions are the regions
+    apply_brown_filter keeps on the pair `--measure` reads its brown numbers from: the white composite of
+    (batch, mask), and the mask (ops.lesion_table).  masks: make_masks_device's (mask, ...) and masked: that
+    composite, when the caller has them.  leaf_pct = area / max(count(mask > 0), 1) * 100; centroid and mean colour
+    = the table's sums / area; equiv_diameter = sqrt(4 area / pi).  cap: the rows per image, LESION_CAP when None."""
+    x = _device_u8(batch, 4, "measure_lesions.batch")
+    n = int(x.shape[0])
+    cap = LESION_CAP if cap is None else int(cap)
+    if masks is None:
+        masks = make_masks_device(x, cfg)
+    mask = masks[0]
+    if masked is None:
+        masked = ops.mask_composite_u8(x, mask, "white")
+    table, counts, flags = ops.lesion_table(
+        masked, mask, brown_hue_range=tuple(cfg.brown_hue_range), brown_s_min=int(cfg.brown_s_min),
+        brown_v_max=int(cfg.brown_v_max), use_lab_brown=bool(cfg.use_lab_brown), lab_a_min=int(cfg.lab_a_min),
+        lab_b_min=int(cfg.lab_b_min), brown_min_area_px=int(cfg.brown_min_area_px),
+        brown_morph_kernel=int(cfg.brown_morph_kernel), cap=cap)
+    leaf_px = (mask > 0).sum(dim=(1, 2)).cpu().numpy().astype(np.int64)
+    ch, fh = counts.cpu().numpy().astype(np.int64), flags.cpu().numpy()
+    th = table[:, :min(int(ch.max()), cap)].cpu().numpy()   # the rows in use: the rest of the table is zeros
+    rows = []
+    for i in range(n):
+        k = min(int(ch[i]), int(cap))
+        f = {name: th[i, :k, j].copy() for j, name in enumerate(ops.LESION_FIELDS)}
+        area = f["area"].astype(np.float64)
+        cols: Dict[str, np.ndarray] = {"lesion": np.arange(1, k + 1, dtype=np.int64)}
+        for name in LESION_COLUMNS[1:]:
+            if name == "leaf_pct":
+                cols[name] = area / max(int(leaf_px[i]), 1) * 100
+            elif name.startswith("centroid_") or name.startswith("mean_"):
+                cols[name] = f["sum_" + name.split("_")[1]] / area
+            elif name == "equiv_diameter":
+                cols[name] = np.sqrt(4 * area / np.pi)
+            else:
+                cols[name] = f[_LESION_FROM_TABLE.get(name, name)]
+        rows.append(cols)
+    return rows, ch, (fh & 2) != 0
+
+
+def lesion_rows(cols: Dict[str, np.ndarray]) -> List[list]:
+    """One image's measure_lesions columns as CSV rows (without `file`), a row per lesion: integers as they are,
+    floats with repr, as measure_row writes them.  An image without lesions gets one row: lesion 0, the other cells
+    empty."""
+    k = len(cols["lesion"])
+    if k == 0:
+        return [["0"] + [""] * (len(LESION_COLUMNS) - 1)]
+    return [[str(int(cols[name][j])) if np.issubdtype(cols[name].dtype, np.integer) else repr(float(cols[name][j]))
+             for name in LESION_COLUMNS] for j in range(k)]
 
 
 def _stats(rgb: np.ndarray):
