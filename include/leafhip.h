@@ -1068,6 +1068,31 @@ int lf_dwconv3x3_bwd_f32(const float* x, const float* w, const float* dy, float*
                          int n, int c, int h, int wd, const float* in_scale, const float* in_shift, int in_relu,
                          void* workspace, size_t ws_bytes, lf_stream_t stream);
 
+/* Knowledge distillation: the head (lf_head_fwd_f32 / lf_head_bwd_f32 below) with a soft-target term from a
+ * teacher's probabilities tprobs [n][c].  Per sample, with z = feat w + b, y = ytrue, T = temperature > 0 (finite),
+ * 0 <= alpha <= 1:
+ *   p    = softmax(z)                      p_T = softmax(z / T)
+ *   lt_j = log(max(tprobs_j, FLT_MIN))     q_T = softmax(lt / T)        FLT_MIN = 1.17549435e-38
+ *   hard = -sum_j y_j log(clip(p_j, 1e-7, 1 - 1e-7))                    (lf_head_fwd_f32's loss)
+ *   kd   = T^2 sum_j q_T,j (log q_T,j - log p_T,j)                      (both logs as log-softmax)
+ *   loss = (1 - alpha) hard + alpha kd
+ * Outputs: probs = p, soft [n][c] = p_T - q_T (what the backward entry needs), loss [n], kd [n] (the kd term alone;
+ * may be null).  The teacher's probabilities suffice, its logits are not needed: softmax(lt / T) does not depend on
+ * the constant that log tprobs drops.  The clamp bounds a class whose teacher probability underflowed to 0: it
+ * enters with lt = log FLT_MIN = -87.3, i.e. relative weight exp(-87.3 / T) (3e-10 at T = 4), not with weight zero.
+ * The maxima, sums and loss terms are reduced across the 64 lanes of a wave, so probs agrees with lf_head_fwd_f32
+ * within rounding, not bit for bit.  c <= 4096. */
+int lf_head_distill_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue,
+                            const float* tprobs, float temperature, float alpha, float* probs, float* soft,
+                            float* loss, float* kd, int n, int f, int c, lf_stream_t stream);
+/* dlogits = [(1 - alpha)(probs - ytrue) + alpha T soft] * inv_n: the gradient of the mean of `loss` over 1 / inv_n
+ * samples, with the unclipped rule of lf_head_bwd_f32 for the hard term.  dfeat = dlogits w^T, dw = feat^T dlogits,
+ * db = sum_n dlogits, computed as lf_head_bwd_f32 computes them.  T = 1 makes it lf_head_bwd_f32 on the mixed target
+ * (1 - alpha) ytrue + alpha tprobs; alpha = 0 makes it lf_head_bwd_f32. */
+int lf_head_distill_bwd_f32(const float* feat, const float* w, const float* probs, const float* ytrue,
+                            const float* soft, float temperature, float alpha, float* dlogits, float* dfeat,
+                            float* dw, float* db, int n, int f, int c, float inv_n, lf_stream_t stream);
+
 /* ---- input stage ----------------------------------------------------------- */
 /* u8 HWC -> f32 NCHW with the model's train-time augmentation fused (cnn.py:74-86):
  * keras RandomFlip("horizontal") -> RandomRotation (bilinear, fill_mode="reflect") ->

@@ -8,6 +8,11 @@ gradient bucket); a plain `python -m ...` run is single-GPU.  Like the reference
 mixed-precision unless `--no-mixed-precision` is given: bf16 storage and MFMA operands, fp32
 accumulation / variables / statistics (fp32 throughout when the shape cannot take the bf16 path).
 Logs and returns 0 on FileNotFoundError/ValueError like the reference (train.py:471-473).
+
+Beyond the reference: `--out-dir DIR` (default artifacts/models) says where the artifacts go, and
+`--teacher DIR [--distill-alpha 0.5] [--distill-temperature 4.0]` trains by knowledge distillation from the
+model in the learnings directory DIR: loss = (1 - alpha) * cross-entropy + alpha * T^2 * KL(teacher_T || student_T),
+the teacher running its inference path on every batch (bf16 unless --no-mixed-precision or it cannot).
 """
 from __future__ import annotations
 
@@ -55,6 +60,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     mx.add_argument("--base", action="store_true")
     p.add_argument("--separable", action="store_true")
     p.add_argument("--target-val-acc", type=float, default=None)
+    p.add_argument("--teacher", type=Path, default=None,
+                   help="learnings directory of a trained model to distil from (meta.json + its model file)")
+    p.add_argument("--distill-alpha", type=float, default=0.5,
+                   help="weight of the soft-target term: loss = (1 - alpha) * CE + alpha * T^2 * KL")
+    p.add_argument("--distill-temperature", type=float, default=4.0)
+    p.add_argument("--out-dir", type=Path, default=Path("artifacts/models"),
+                   help="where the model and its JSON artifacts are written")
     args = p.parse_args(argv)
     for s in ("tiny", "small", "base"):
         if getattr(args, s, False):
@@ -99,6 +111,53 @@ def get_model_parameters(scale: str) -> Tuple[List[int], float, float]:
     if scale == "small":
         return [32, 64, 128], 0.15, 0.35
     return [32, 64, 128, 256], 0.15, 0.40
+
+
+def load_teacher(args, label2idx: Dict[str, int]):
+    """The model `--teacher DIR` names, ready for inference, and the "distillation" entry of meta.json.  The model
+    file is the basename of DIR/meta.json's model_file inside DIR (a moved directory still loads).  Refused with
+    ValueError: alpha / temperature out of range, labels in another order than this run's, another image size, and
+    an --out-dir that is the teacher's directory (the run would overwrite the model it learns from)."""
+    import json
+    import math
+
+    from ..model.cnn import load_model
+    alpha, temperature = float(args.distill_alpha), float(args.distill_temperature)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"--distill-alpha must lie in [0, 1], got {alpha}")
+    if not (temperature > 0.0 and math.isfinite(temperature)):
+        raise ValueError(f"--distill-temperature must be positive and finite, got {temperature}")
+    tdir = Path(args.teacher).resolve()
+    if Path(args.out_dir).resolve() == tdir:
+        raise ValueError(f"--out-dir is the teacher's directory ({tdir}): the run would overwrite its teacher")
+    meta_path = tdir / "meta.json"
+    if not meta_path.exists():
+        raise FileNotFoundError(f"Teacher meta file not found: {meta_path}")
+    meta = json.loads(meta_path.read_text(encoding="utf-8"))
+    if not meta.get("model_file"):
+        raise ValueError(f"{meta_path}: no model_file")
+    labels = sorted(label2idx, key=lambda k: label2idx[k])
+    if list(meta.get("labels", [])) != labels:
+        raise ValueError(f"teacher labels {meta.get('labels')} differ from this run's {labels}")
+    t_size = int(meta.get("data", {}).get("img_size", 224))
+    if t_size != args.img_size:
+        raise ValueError(f"teacher was trained at img_size {t_size}, this run uses {args.img_size}")
+    model_path = tdir / Path(meta["model_file"]).name
+    if not model_path.exists():
+        raise FileNotFoundError(f"Teacher model file not found: {model_path}")
+    teacher = load_model(model_path)
+    dtype = "f32"
+    if not args.no_mixed_precision:
+        try:
+            teacher.set_inference_dtype("bf16")
+            if teacher._bf16_storage_ok(args.img_size, args.img_size):
+                dtype = "bf16"
+            else:
+                teacher.set_inference_dtype("f32")
+        except ValueError as e:
+            LOGGER.info("Teacher runs fp32 inference (%s)", e)
+    LOGGER.info("Teacher: %s (%s inference), alpha %.3g, temperature %.3g", model_path, dtype, alpha, temperature)
+    return teacher, {"teacher": str(tdir), "alpha": alpha, "temperature": temperature, "teacher_dtype": dtype}
 
 
 def create_data_sequences(train_items, val_items, label2idx, args, cfg, num_classes, dp):
@@ -182,17 +241,24 @@ def main(argv=None) -> None:
         train_items, val_items, label2idx = prepare_data(manifest_path)
         num_classes = len(label2idx)
         cfg = get_training_config(args.fast)
+        teacher = distillation = None
+        if args.teacher is not None:
+            teacher, distillation = load_teacher(args, label2idx)
+            cfg["distill"] = {"alpha": distillation["alpha"], "temperature": distillation["temperature"]}
         train_seq, val_seq = create_data_sequences(train_items, val_items, label2idx, args, cfg,
                                                    num_classes, dp)
         model = build_and_compile_model(args, cfg, num_classes, train_seq, dp)
         meta = create_training_metadata(args, cfg, num_classes, train_items, val_items, dp)
         meta["training"]["mixed_precision"] = model.train_dtype == "bf16"
+        if distillation is not None:
+            meta["training"]["distillation"] = distillation
         callbacks, ema_cb = build_callbacks(cfg)
         if getattr(args, "target_val_acc", None):
             callbacks.append(StopOnValAcc(args.target_val_acc))
+        fit_extra = {"teacher": teacher} if teacher is not None else {}
         history = model.fit(train_seq, validation_data=val_seq, epochs=args.epochs, callbacks=callbacks,
-                            dp=dp)
-        save_best_variant(model, val_seq, ema_cb, out_dir=Path("artifacts/models"),
+                            dp=dp, **fit_extra)
+        save_best_variant(model, val_seq, ema_cb, out_dir=args.out_dir,
                           label2idx=label2idx, history=history, meta=meta, dp=dp)
     except (FileNotFoundError, ValueError) as e:
         LOGGER.error("Training failed: %s", e)

@@ -13,6 +13,8 @@
 // and every cross-workgroup reduction goes through partial sums that are combined in a fixed
 // order (deterministic; no float atomics).  Reference semantics: srcs/model/cnn.py:9-104,
 // srcs/train/utils.py:17-57 (Keras 3 layer / optimizer definitions).
+#include <float.h>
+
 #include "lf_common.h"
 
 namespace {
@@ -857,14 +859,93 @@ __global__ void head_fwd_kernel(const float* __restrict__ feat, const float* __r
     }
 }
 
-// dlogits = (probs - ytrue) * inv_n; dfeat = dlogits W^T; (dW, db) by outer_sum_kernel
+// The same value in every lane of the 64-lane wave (xor butterfly: both partners of a step add / compare the same
+// pair, so the lanes agree bit for bit).
+__device__ __forceinline__ float wave_sum_all(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max_all(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// Distillation head: the head above plus the soft-target term at temperature T.
+//   p = softmax(z), p_T = softmax(z/T), q_T = softmax(lt/T), lt = log(max(tprobs, FLT_MIN))
+//   hard = -sum y log(clip(p)),  kd = T^2 sum q_T (log q_T - log p_T),  loss = (1-alpha) hard + alpha kd
+// One workgroup = one wave per sample.  Lane l owns the classes l, l+64, ...: it writes their logits and teacher
+// logs to LDS and is the only lane that reads them back, and the three maxima, three sums and the two loss terms
+// cross the lanes by butterfly, so no class is walked serially.  Both logs of kd are log-softmax values
+// (exponent minus log-sum-exp).
+__global__ __launch_bounds__(64) void head_distill_fwd_kernel(
+    const float* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ b,
+    const float* __restrict__ ytrue, const float* __restrict__ tprobs, float inv_t, float t2, float alpha,
+    float* __restrict__ probs, float* __restrict__ soft, float* __restrict__ loss, float* __restrict__ kd, int f,
+    int c) {
+    extern __shared__ float sm[];  // [c] logits, [c] teacher logs
+    float* lt = sm + c;
+    const int n = blockIdx.x;
+    const size_t row = (size_t)n * c;
+    float mz = -INFINITY, ml = -INFINITY;
+    for (int j = threadIdx.x; j < c; j += 64) {
+        float acc = b[j];
+        for (int i = 0; i < f; ++i) acc = fmaf(feat[(size_t)n * f + i], w[(size_t)i * c + j], acc);
+        const float l = logf(fmaxf(tprobs[row + j], FLT_MIN));
+        sm[j] = acc;
+        lt[j] = l;
+        mz = fmaxf(mz, acc);
+        ml = fmaxf(ml, l);
+    }
+    mz = wave_max_all(mz);
+    ml = wave_max_all(ml);
+    float den = 0.f, den_t = 0.f, den_q = 0.f;
+    for (int j = threadIdx.x; j < c; j += 64) {
+        const float dz = sm[j] - mz;
+        den += expf(dz);
+        den_t += expf(dz * inv_t);
+        den_q += expf((lt[j] - ml) * inv_t);
+    }
+    den = wave_sum_all(den);
+    den_t = wave_sum_all(den_t);
+    den_q = wave_sum_all(den_q);
+    const float lse_t = logf(den_t), lse_q = logf(den_q);
+    float hard = 0.f, kl = 0.f;
+    for (int j = threadIdx.x; j < c; j += 64) {
+        const float dz = sm[j] - mz;
+        const float pr = expf(dz) / den;
+        probs[row + j] = pr;
+        // keras categorical_crossentropy: clip to [1e-7, 1-1e-7] then -sum y log p
+        const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
+        hard -= ytrue[row + j] * logf(pc);
+        const float et = dz * inv_t, eq = (lt[j] - ml) * inv_t;
+        const float qt = expf(eq) / den_q;
+        soft[row + j] = expf(et) / den_t - qt;
+        kl += qt * ((eq - lse_q) - (et - lse_t));
+    }
+    hard = wave_sum_all(hard);
+    kl = wave_sum_all(kl) * t2;
+    if (threadIdx.x == 0) {
+        loss[n] = (1.f - alpha) * hard + alpha * kl;
+        if (kd != nullptr) kd[n] = kl;
+    }
+}
+
+// dlogits = (probs - ytrue) * inv_n, or with kDistill
+//   [(1-alpha)(probs - ytrue) + alpha T soft] * inv_n   (hard_w = 1-alpha, soft_w = alpha T);
+// dfeat = dlogits W^T; (dW, db) by outer_sum_kernel
+template <bool kDistill>
 __global__ void head_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ ytrue,
+                                const float* __restrict__ soft, float hard_w, float soft_w,
                                 const float* __restrict__ w, float* __restrict__ dlogits,
                                 float* __restrict__ dfeat, int f, int c, float inv_n) {
     extern __shared__ float sm[];  // [c]
     const int n = blockIdx.x;
     for (int j = threadIdx.x; j < c; j += blockDim.x) {
-        const float d = (probs[(size_t)n * c + j] - ytrue[(size_t)n * c + j]) * inv_n;
+        float d = probs[(size_t)n * c + j] - ytrue[(size_t)n * c + j];
+        if (kDistill) d = hard_w * d + soft_w * soft[(size_t)n * c + j];
+        d *= inv_n;
         sm[j] = d;
         dlogits[(size_t)n * c + j] = d;
     }
@@ -981,6 +1062,25 @@ __global__ __launch_bounds__(kBlock) void cast_bf16_f32_kernel(const uint16_t* _
 
 inline unsigned plane_grid(int hw_items) { return lf::stream_grid((size_t)hw_items, kBlock, 64); }
 inline bool aligned(const void* p, size_t bytes) { return (reinterpret_cast<size_t>(p) & (bytes - 1)) == 0; }
+
+// temperature > 0 and finite, 0 <= alpha <= 1 (NaN fails every comparison)
+inline bool distill_args_ok(float temperature, float alpha) {
+    return temperature > 0.f && temperature <= FLT_MAX && alpha >= 0.f && alpha <= 1.f;
+}
+
+// The backward pass of both heads: dlogits and dfeat per sample, then (dW, db) over the batch.
+template <bool kDistill>
+int head_bwd_launch(const char* what, const float* feat, const float* w, const float* probs, const float* ytrue,
+                    const float* soft, float hard_w, float soft_w, float* dlogits, float* dfeat, float* dw,
+                    float* db, int n, int f, int c, float inv_n, lf_stream_t stream) {
+    hipStream_t st = lf::as_stream(stream);
+    head_bwd_kernel<kDistill><<<n, 64, (size_t)c * sizeof(float), st>>>(probs, ytrue, soft, hard_w, soft_w, w,
+                                                                       dlogits, dfeat, f, c, inv_n);
+    // dW[f][c] = sum_n feat[n][f] dlogits[n][c]; db[c] = sum_n dlogits[n][c]
+    outer_sum_kernel<<<(unsigned)(((size_t)(f + 1) * c + 63) / 64), kBlock, 0, st>>>(feat, dlogits, dw, db,
+                                                                                   n, f, c);
+    return lf::check_launch(what);
+}
 
 }  // namespace
 
@@ -1343,12 +1443,32 @@ int lf_head_bwd_f32(const float* feat, const float* w, const float* probs, const
                     float inv_n, lf_stream_t stream) {
     LF_REQUIRE(feat && w && probs && ytrue && dlogits && dfeat && dw && db, "lf_head_bwd: null buffer");
     LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= 4096, "lf_head_bwd: bad dims n=%d f=%d c=%d", n, f, c);
-    hipStream_t st = lf::as_stream(stream);
-    head_bwd_kernel<<<n, 64, (size_t)c * sizeof(float), st>>>(probs, ytrue, w, dlogits, dfeat, f, c, inv_n);
-    // dW[f][c] = sum_n feat[n][f] dlogits[n][c]; db[c] = sum_n dlogits[n][c]
-    outer_sum_kernel<<<(unsigned)(((size_t)(f + 1) * c + 63) / 64), kBlock, 0, st>>>(feat, dlogits, dw, db,
-                                                                                   n, f, c);
-    return lf::check_launch("lf_head_bwd");
+    return head_bwd_launch<false>("lf_head_bwd", feat, w, probs, ytrue, nullptr, 0.f, 0.f, dlogits, dfeat, dw, db, n,
+                                  f, c, inv_n, stream);
+}
+
+int lf_head_distill_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue,
+                            const float* tprobs, float temperature, float alpha, float* probs, float* soft,
+                            float* loss, float* kd, int n, int f, int c, lf_stream_t stream) {
+    LF_REQUIRE(feat && w && b && ytrue && tprobs && probs && soft && loss, "lf_head_distill_fwd: null buffer");
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= 4096, "lf_head_distill_fwd: bad dims n=%d f=%d c=%d", n, f, c);
+    LF_REQUIRE(distill_args_ok(temperature, alpha), "lf_head_distill_fwd: bad temperature=%g (> 0, finite) or "
+               "alpha=%g (0..1)", (double)temperature, (double)alpha);
+    head_distill_fwd_kernel<<<n, 64, 2 * (size_t)c * sizeof(float), lf::as_stream(stream)>>>(
+        feat, w, b, ytrue, tprobs, 1.f / temperature, temperature * temperature, alpha, probs, soft, loss, kd, f, c);
+    return lf::check_launch("lf_head_distill_fwd");
+}
+
+int lf_head_distill_bwd_f32(const float* feat, const float* w, const float* probs, const float* ytrue,
+                            const float* soft, float temperature, float alpha, float* dlogits, float* dfeat,
+                            float* dw, float* db, int n, int f, int c, float inv_n, lf_stream_t stream) {
+    LF_REQUIRE(feat && w && probs && ytrue && soft && dlogits && dfeat && dw && db,
+               "lf_head_distill_bwd: null buffer");
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= 4096, "lf_head_distill_bwd: bad dims n=%d f=%d c=%d", n, f, c);
+    LF_REQUIRE(distill_args_ok(temperature, alpha), "lf_head_distill_bwd: bad temperature=%g (> 0, finite) or "
+               "alpha=%g (0..1)", (double)temperature, (double)alpha);
+    return head_bwd_launch<true>("lf_head_distill_bwd", feat, w, probs, ytrue, soft, 1.f - alpha,
+                                 alpha * temperature, dlogits, dfeat, dw, db, n, f, c, inv_n, stream);
 }
 
 int lf_mul_f32(const float* a, const float* b, float* out, size_t count, lf_stream_t stream) {

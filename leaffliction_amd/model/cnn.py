@@ -109,6 +109,7 @@ class Normalization:
 class LeafCNN:
     name = "leaf_cnn"
     _mut = 0                            # see __init__ (class-level defaults: subclasses that skip it still step)
+    last_kd: Optional[torch.Tensor] = None   # train_step with a teacher: the per-sample kd term
     _infer_cache: Dict[str, Any] = {}
 
     def __init__(self, *, num_classes: int, img_size: int = 224, use_norm: bool = True,
@@ -523,10 +524,13 @@ class LeafCNN:
 
     def forward(self, x0: torch.Tensor, training: bool, y_true: Optional[torch.Tensor] = None,
                 drops: Optional[List[torch.Tensor]] = None,
-                top_drop: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                top_drop: Optional[torch.Tensor] = None,
+                teacher_probs: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """x0: normalised f32 NCHW.  Returns (probs [N,C], per-sample loss or None).
         In training mode the step runs in self.train_dtype (see set_training_dtype) and every tensor
-        the backward pass needs is kept in self._saved."""
+        the backward pass needs is kept in self._saved.  teacher_probs (f32 [N,C], with y_true): the head is the
+        distillation head at the compiled alpha / temperature, the loss the combined one, and the kd term alone
+        is left in _kd_buf(N)."""
         n, _c, h, w = x0.shape
         bf16 = training and self.train_dtype == "bf16"
         if bf16 and not (self.use_se and self._bf16_storage_ok(h, w)):
@@ -584,7 +588,14 @@ class LeafCNN:
             feat = nn.mul(g, top_drop, B("feat", g.shape, F32))
         probs = B("probs", (n, self.num_classes), F32)
         loss = B("loss", (n,), F32) if y_true is not None else None
-        nn.head_fwd(feat, P["dense.w"], P["dense.b"], y_true, probs, loss)
+        if teacher_probs is not None:
+            alpha, temperature = self._distill_setting(required=True)
+            soft = B("soft", (n, self.num_classes), F32)
+            nn.head_distill_fwd(feat, P["dense.w"], P["dense.b"], y_true, teacher_probs, temperature, alpha, probs,
+                                soft, loss, self._kd_buf(n))
+            sv.update({"soft": soft, "distill": (alpha, temperature)})
+        else:
+            nn.head_fwd(feat, P["dense.w"], P["dense.b"], y_true, probs, loss)
         sv.update({"feat": feat, "top_drop": top_drop, "probs": probs, "y_true": y_true,
                    "last_hw": (h, w)})
         if training:
@@ -625,8 +636,14 @@ class LeafCNN:
         if part in (None, 0):
             dlogits = B("dlogits", (n, self.num_classes), F32)
             dfeat = B("dfeat", (n, f_last), F32)
-            nn.head_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], dlogits, dfeat,
-                        G["dense.w"], G["dense.b"], 1.0 / (self._global_n or n))
+            inv_n = 1.0 / (self._global_n or n)
+            if sv.get("soft") is not None:
+                alpha, temperature = sv["distill"]
+                nn.head_distill_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], sv["soft"], temperature,
+                                    alpha, dlogits, dfeat, G["dense.w"], G["dense.b"], inv_n)
+            else:
+                nn.head_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], dlogits, dfeat,
+                            G["dense.w"], G["dense.b"], inv_n)
             dg = dfeat
             if sv["top_drop"] is not None:
                 dg = nn.mul(dfeat, sv["top_drop"], B("dg", dfeat.shape, F32))
@@ -779,8 +796,12 @@ class LeafCNN:
 
     def train_step(self, x, y_true: Optional[torch.Tensor], lr: float, *, weight_decay: float = 1e-4,
                    clipnorm: float = 0.5, ema_decay: float = 0.999, adamw: bool = True,
-                   grad_sync=None, global_n: Optional[int] = None, grad_overlap=None):
+                   grad_sync=None, global_n: Optional[int] = None, grad_overlap=None,
+                   teacher_probs: Optional[torch.Tensor] = None):
         """One optimisation step on a batch.  y_true: f32 [N,C] (already label-smoothed).
+        teacher_probs (f32 [N,C] on the device; needs compile(loss={..., "distill": {...}})): the step minimises
+        (1 - alpha) * cross-entropy + alpha * T^2 KL(teacher_T || student_T) (lf_head_distill_*_f32), the returned
+        loss is that sum and `last_kd` holds the per-sample kd term; without it the step is the plain one.
         grad_sync(flat_g) is called between backward and the optimizer (data-parallel
         all-reduce); with global_n the local gradient is scaled by 1/global_n so that a SUM
         all-reduce yields the global-batch mean.  Returns (probs, per-sample loss) device
@@ -800,6 +821,12 @@ class LeafCNN:
         self._mut += 1   # parameters and moving statistics change (also when the step is a graph replay)
         n = int(x.shape[0])
         self._global_n = global_n
+        # the extra argument goes to _forward_backward only when distilling (an empty local batch has no teacher)
+        extra = {}
+        if teacher_probs is not None and n > 0:
+            self._distill_setting(required=True)
+            extra = {"teacher_probs": teacher_probs}
+        self.last_kd = self._kd_buf(n) if extra else None
         if grad_overlap is not None:
             # two exchanges, the same two on every rank (a rank with an empty batch sends zeros in both)
             split = min(self.n_params, -(-self.grad_split() // 64) * 64)   # whole 256-byte lines per piece
@@ -810,7 +837,7 @@ class LeafCNN:
                 handles.append(grad_overlap.allreduce_begin(self.flat_g, split, self.n_params))
             else:
                 probs, loss = self._forward_backward(x, y_true, between=lambda: handles.append(
-                    grad_overlap.allreduce_begin(self.flat_g, split, self.n_params)))
+                    grad_overlap.allreduce_begin(self.flat_g, split, self.n_params)), **extra)
             handles.append(grad_overlap.allreduce_begin(self.flat_g, 0, split))
             grad_overlap.allreduce_finish(self.flat_g, handles)
             grad_sync = None
@@ -818,7 +845,7 @@ class LeafCNN:
             self.flat_g.zero_()
             probs = loss = None
         else:
-            probs, loss = self._forward_backward(x, y_true)
+            probs, loss = self._forward_backward(x, y_true, **extra)
         if grad_sync is not None:
             grad_sync(self.flat_g)
         self.opt_step += 1
@@ -826,7 +853,7 @@ class LeafCNN:
                                ema_decay=ema_decay)
         return probs, loss
 
-    def _forward_backward(self, x, y_true: torch.Tensor, between=None):
+    def _forward_backward(self, x, y_true: torch.Tensor, between=None, teacher_probs=None):
         """Forward + backward of one local batch: fills flat_g, returns (probs, loss).  `between`, when given, is
         called on the host between the two parts of the backward pass (backward()'s `part`): everything of part 0
         has been issued to the stream by then, nothing of part 1.
@@ -837,15 +864,18 @@ class LeafCNN:
         captured.  Inputs and labels are copied into fixed buffers, the per-step random draws go up
         through their fixed staging buffer before the replay; the optimizer (its learning rate
         changes every step) and the gradient all-reduce stay outside.  LEAFFLICTION_GRAPH=0 turns
-        this off."""
+        this off.  teacher_probs (train_step) has a fixed buffer of its own, st["t"], and the distillation setting
+        is part of the graph's key: the step with a teacher and the step without are two graphs."""
         if self._graphs_on and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8:
-            return self._forward_backward_graph(x, y_true, between)
-        return self._forward_backward_eager(x, y_true, between)
+            return self._forward_backward_graph(x, y_true, between, teacher_probs)
+        return self._forward_backward_eager(x, y_true, between, teacher_probs)
 
-    def _forward_backward_graph(self, x: torch.Tensor, y_true: torch.Tensor, between=None):
+    def _forward_backward_graph(self, x: torch.Tensor, y_true: torch.Tensor, between=None, teacher_probs=None):
         n = int(x.shape[0])
         key = (tuple(x.shape), self.train_dtype, self.augment, self._global_n, tuple(y_true.shape),
                between is not None)
+        if teacher_probs is not None:
+            key += (self._distill_setting(required=True),)
         st = self._graphs.get(key)
         if st is None:
             st = self._graphs[key] = {"calls": 0, "graph": None}
@@ -856,13 +886,17 @@ class LeafCNN:
             # Drop it and record the step again (this call runs eagerly on the current buffers).
             st["graph"], st["calls"] = None, 2
         if st["graph"] is None and st["calls"] <= 2:
-            return self._forward_backward_eager(x, y_true, between)
+            return self._forward_backward_eager(x, y_true, between, teacher_probs)
         drops, top, aug4 = self.draw_step_randoms(n, self.augment)  # fixed device views, fresh values
         if st["graph"] is None:
             st["x"] = torch.empty_like(x)
             st["y"] = torch.empty_like(y_true)
             st["x"].copy_(x)
             st["y"].copy_(y_true)
+            st["t"] = None
+            if teacher_probs is not None:
+                st["t"] = torch.empty_like(teacher_probs)
+                st["t"].copy_(teacher_probs)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             g2 = torch.cuda.CUDAGraph() if between is not None else None
@@ -870,45 +904,51 @@ class LeafCNN:
                 # with `between`: two graphs out of one memory pool, cut where the host may start the first exchange
                 with torch.cuda.graph(g):
                     st["out"] = self._forward_backward_body(st["x"], st["y"], drops, top, aug4,
-                                                            part=None if between is None else 0)
+                                                            part=None if between is None else 0,
+                                                            teacher_probs=st["t"])
                 if g2 is not None:
                     with torch.cuda.graph(g2, pool=g.pool()):
                         self._forward_backward_body(st["x"], st["y"], drops, top, aug4, part=1)
             except Exception:
                 self._graphs_on = False   # capture is an optimisation: fall back to eager launches
                 torch.cuda.synchronize()
-                return self._forward_backward_split(x, y_true, drops, top, aug4, between)
+                return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs)
             st["graph"], st["graph2"] = g, g2
             st["ws_gen"] = nn.workspace_generation()
         else:
             st["x"].copy_(x)
             st["y"].copy_(y_true)
+            if teacher_probs is not None:
+                st["t"].copy_(teacher_probs)
         st["graph"].replay()
         if between is not None:
             between()
             st["graph2"].replay()
         return st["out"]
 
-    def _forward_backward_eager(self, x, y_true: torch.Tensor, between=None):
+    def _forward_backward_eager(self, x, y_true: torch.Tensor, between=None, teacher_probs=None):
         n = int(x.shape[0])
         drops, top, aug4 = self.draw_step_randoms(n, self.augment)
-        return self._forward_backward_split(x, y_true, drops, top, aug4, between)
+        return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs)
 
-    def _forward_backward_split(self, x, y_true, drops, top, aug4, between):
+    def _forward_backward_split(self, x, y_true, drops, top, aug4, between, teacher_probs=None):
         if between is None:
-            return self._forward_backward_body(x, y_true, drops, top, aug4)
-        out = self._forward_backward_body(x, y_true, drops, top, aug4, part=0)
+            return self._forward_backward_body(x, y_true, drops, top, aug4, teacher_probs=teacher_probs)
+        out = self._forward_backward_body(x, y_true, drops, top, aug4, part=0, teacher_probs=teacher_probs)
         between()
         self._forward_backward_body(x, y_true, drops, top, aug4, part=1)
         return out
 
-    def _forward_backward_body(self, x, y_true, drops, top, aug4, part: Optional[int] = None):
+    def _forward_backward_body(self, x, y_true, drops, top, aug4, part: Optional[int] = None, teacher_probs=None):
         """part None: forward + the whole backward pass; 0: forward + backward part 0; 1: backward part 1."""
         if part == 1:
             self.backward(1)
             return None
         x0 = self._input(x, True, aug4)
-        probs, loss = self.forward(x0, True, y_true, drops, top)
+        if teacher_probs is None:
+            probs, loss = self.forward(x0, True, y_true, drops, top)
+        else:
+            probs, loss = self.forward(x0, True, y_true, drops, top, teacher_probs)
         self.backward(part)
         return probs, loss
 
@@ -941,8 +981,29 @@ class LeafCNN:
 
     # --------------------------------------------------------- keras-like API
     def compile(self, optimizer=None, loss=None, metrics=None) -> None:
-        """optimizer: dict from train.utils.build_optimizer; loss: dict from build_loss."""
+        """optimizer: dict from train.utils.build_optimizer; loss: dict from build_loss, optionally with
+        "distill": {"alpha": a, "temperature": t} (0 <= a <= 1, t > 0 and finite): the setting of the steps that
+        are given a teacher's probabilities."""
         self._compiled = {"optimizer": optimizer or {}, "loss": loss or {}, "metrics": metrics or []}
+        self._distill_setting()
+
+    def _distill_setting(self, required: bool = False) -> Optional[Tuple[float, float]]:
+        """(alpha, temperature) of the compiled loss, None when it has no "distill"."""
+        d = self._compiled.get("loss", {}).get("distill")
+        if d is None:
+            if required:
+                raise ValueError('a teacher needs compile(loss={..., "distill": {"alpha": a, "temperature": t}})')
+            return None
+        alpha, temperature = float(d.get("alpha", 0.5)), float(d.get("temperature", 4.0))
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"distill alpha must lie in [0, 1], got {alpha}")
+        if not (temperature > 0.0 and math.isfinite(temperature)):
+            raise ValueError(f"distill temperature must be positive and finite, got {temperature}")
+        return alpha, temperature
+
+    def _kd_buf(self, n: int) -> torch.Tensor:
+        """The per-sample kd term of the last distillation step at batch n (fp32, whatever the step's precision)."""
+        return self._buf(n, "kd", (n,))
 
     def _targets(self, by) -> Tuple[torch.Tensor, torch.Tensor]:
         """labels (one-hot [B,C] or sparse [B]) -> (smoothed one-hot f32 on device, indices)."""
@@ -964,14 +1025,25 @@ class LeafCNN:
         return yt.contiguous(), idx
 
     def fit(self, train_seq, validation_data=None, epochs: int = 1, callbacks=None, dp=None,
-            verbose: int = 1):
+            verbose: int = 1, teacher=None):
         """Keras `Model.fit` for a ManifestSequence: per epoch the batch order is shuffled
         (keras shuffles Sequence batches), every batch is one `train_step`, then validation,
-        callbacks and `train_seq.on_epoch_end()`.  `dp` is a train.parallel.DataParallel."""
+        callbacks and `train_seq.on_epoch_end()`.  `dp` is a train.parallel.DataParallel.
+
+        teacher (a LeafCNN with the same classes; needs the compiled "distill" setting): knowledge distillation.
+        Every non-empty local batch first goes through `teacher.predict_device` — its inference path: no in-model
+        augmentation, its own normalisation and inference dtype — and the step takes those probabilities
+        (train_step's teacher_probs) while this model sees its own augmented view of the batch.  `history` gains
+        "kd_loss", the mean kd term, and "loss" is the combined loss; validation stays plain cross-entropy."""
         import logging
         import random as _random
         log = logging.getLogger(__name__)
         opt = self._compiled.get("optimizer", {})
+        if teacher is not None:
+            self._distill_setting(required=True)
+            if teacher.num_classes != self.num_classes:
+                raise ValueError(f"fit: the teacher has {teacher.num_classes} classes, this model "
+                                 f"{self.num_classes}")
         callbacks = callbacks or []
         hist: Dict[str, List[float]] = {}
         steps_per_epoch = len(train_seq)
@@ -985,6 +1057,7 @@ class LeafCNN:
             order_rng.shuffle(order)
             acc_loss = torch.zeros((), device=self.device)
             acc_correct = torch.zeros((), device=self.device)
+            acc_kd = torch.zeros((), device=self.device)
             seen = 0
             prefetch = getattr(train_seq, "prefetch", None)
             for step_no, bi in enumerate(order):
@@ -1000,13 +1073,19 @@ class LeafCNN:
                 yt, idx = self._targets(by) if n_local else (None, None)
                 lr = opt["schedule"](self.opt_step) if "schedule" in opt else opt.get("lr", 1e-3)
                 gn = train_seq.global_batch_size(bi) if dp_on else None
+                extra = {}
+                if teacher is not None and n_local:
+                    # a copy: the teacher's next forward pass overwrites the buffer predict_device returns
+                    extra = {"teacher_probs": teacher.predict_device(bx).clone()}
                 probs, loss = self.train_step(
                     bx, yt, lr, weight_decay=opt.get("weight_decay", 0.0),
                     clipnorm=opt.get("clipnorm", 0.0), ema_decay=opt.get("ema_decay", 0.0),
                     adamw=opt.get("name", "adamw") == "adamw",
                     grad_sync=dp.allreduce_grads if dp_on else None, global_n=gn,
-                    grad_overlap=dp if dp_on and getattr(dp, "overlap", False) else None)
+                    grad_overlap=dp if dp_on and getattr(dp, "overlap", False) else None, **extra)
                 if n_local:
+                    if extra:
+                        acc_kd += self.last_kd.sum()
                     acc_loss += loss.sum()
                     acc_correct += (probs.argmax(-1) == idx).sum()
                     seen += n_local
@@ -1016,6 +1095,11 @@ class LeafCNN:
             if dp is not None and dp.active:
                 tl, tc, tn = dp.allreduce_scalars([tl, tc, tn])
             logs = {"loss": tl / max(tn, 1.0) + float(self.l2_penalty()), "accuracy": tc / max(tn, 1.0)}
+            if teacher is not None:
+                tk = float(acc_kd)
+                if dp is not None and dp.active:
+                    tk = dp.allreduce_scalars([tk])[0]
+                logs["kd_loss"] = tk / max(tn, 1.0)
             if validation_data is not None:
                 vl, va = self.evaluate(validation_data, dp=dp)
                 logs["val_loss"], logs["val_accuracy"] = vl, va

@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -772,6 +772,43 @@ def head_bwd(feat, w, probs, ytrue, dlogits, dfeat, dw, db, inv_n):
     _lib.call("lf_head_bwd_f32", feat.data_ptr(), w.data_ptr(), probs.data_ptr(), ytrue.data_ptr(),
               dlogits.data_ptr(), dfeat.data_ptr(), dw.data_ptr(), db.data_ptr(), n, f, c,
               float(inv_n), _stream())
+
+
+def _head_distill_checks(who: str, feat, w, shaped) -> Tuple[int, int, int]:
+    """(n, f, c) of a distillation head launch; `shaped`: name -> (tensor, expected shape), fp32 contiguous all."""
+    if feat.dim() != 2 or w.dim() != 2 or w.shape[0] != feat.shape[1]:
+        raise ValueError(f"{who}: feat [N,F] and w [F,C] expected, got {tuple(feat.shape)} and {tuple(w.shape)}")
+    n, f = feat.shape
+    c = w.shape[1]
+    dims = {"n": (n,), "nc": (n, c), "nf": (n, f), "fc": (f, c), "c": (c,)}
+    for name, (t, shape) in dict(shaped, feat=(feat, "nf"), w=(w, "fc")).items():
+        if t is None:
+            continue
+        if t.dtype != _F32 or not t.is_contiguous() or t.device != feat.device:
+            raise ValueError(f"{who}.{name}: a contiguous float32 tensor on {feat.device} expected")
+        if tuple(t.shape) != dims[shape]:
+            raise ValueError(f"{who}.{name}: expected {dims[shape]}, got {tuple(t.shape)}")
+    return n, f, c
+
+
+def head_distill_fwd(feat, w, b, ytrue, tprobs, temperature: float, alpha: float, probs, soft, loss, kd=None):
+    """The head with a teacher (lf_head_distill_fwd_f32): writes probs, soft = p_T - q_T, loss and (optionally) kd."""
+    n, f, c = _head_distill_checks("head_distill_fwd", feat, w, {
+        "b": (b, "c"), "ytrue": (ytrue, "nc"), "tprobs": (tprobs, "nc"), "probs": (probs, "nc"),
+        "soft": (soft, "nc"), "loss": (loss, "n"), "kd": (kd, "n")})
+    _lib.call("lf_head_distill_fwd_f32", feat.data_ptr(), w.data_ptr(), b.data_ptr(), ytrue.data_ptr(),
+              tprobs.data_ptr(), float(temperature), float(alpha), probs.data_ptr(), soft.data_ptr(),
+              loss.data_ptr(), _ptr(kd), n, f, c, _stream())
+    return probs
+
+
+def head_distill_bwd(feat, w, probs, ytrue, soft, temperature: float, alpha: float, dlogits, dfeat, dw, db, inv_n):
+    n, f, c = _head_distill_checks("head_distill_bwd", feat, w, {
+        "probs": (probs, "nc"), "ytrue": (ytrue, "nc"), "soft": (soft, "nc"), "dlogits": (dlogits, "nc"),
+        "dfeat": (dfeat, "nf"), "dw": (dw, "fc"), "db": (db, "c")})
+    _lib.call("lf_head_distill_bwd_f32", feat.data_ptr(), w.data_ptr(), probs.data_ptr(), ytrue.data_ptr(),
+              soft.data_ptr(), float(temperature), float(alpha), dlogits.data_ptr(), dfeat.data_ptr(),
+              dw.data_ptr(), db.data_ptr(), n, f, c, float(inv_n), _stream())
 
 
 def mul(a, b, out):

@@ -47,10 +47,15 @@ def build_optimizer(cfg: Dict, base_lr) -> Dict[str, Any]:
 
 
 def build_loss(cfg: Dict) -> Dict[str, Any]:
-    """CategoricalCrossentropy(label_smoothing) or sparse CCE (utils.py:30-35)."""
+    """CategoricalCrossentropy(label_smoothing) or sparse CCE (utils.py:30-35); a cfg that carries
+    "distill": {"alpha", "temperature"} (train --teacher) hands it on to LeafCNN.compile."""
     ls = float(cfg.get("label_smoothing", 0.0) or 0.0)
-    return {"name": "categorical_crossentropy" if ls > 0 else "sparse_categorical_crossentropy",
-            "label_smoothing": ls}
+    loss: Dict[str, Any] = {"name": "categorical_crossentropy" if ls > 0 else "sparse_categorical_crossentropy",
+                            "label_smoothing": ls}
+    if cfg.get("distill") is not None:
+        loss["distill"] = {"alpha": float(cfg["distill"]["alpha"]),
+                           "temperature": float(cfg["distill"]["temperature"])}
+    return loss
 
 
 class Callback:
