@@ -1044,6 +1044,30 @@ int lf_conv2d_wgrad_bn_f32(const float* x, const float* g, const float* bn_y,
                            int ksize, const float* in_scale, const float* in_shift, int in_relu,
                            void* workspace, size_t ws_bytes, lf_stream_t stream);
 
+/* Backward of a projection shortcut (1x1 conv + BatchNormalization) in one pass over x, g and bn_y:
+ *   dyp = coef2*dz + coef3*bn_y + coef4, dz = g*[bn_y*coef0+coef1 > 0 or !bn_relu]   (the dy_out of
+ *         lf_conv2d_wgrad_bn_f32 without alpha_nc / add_nc, bit for bit; kept on chip, never written)
+ *   dw[ci][co] = sum_{n,px} x[n][ci][px] * dyp[n][co][px]       (overwritten)
+ *   dx[n][ci][px] = sum_co w[ci][co] * dyp[n][co][px]           (overwritten; accumulate onto it afterwards)
+ * x [n][cin][h*w] is the conv's input as it stands (no prologue), g / bn_y [n][cout][h*w], coef [5][cout] from
+ * lf_bn_bwd_sums*_f32, w [cin][1][cout].  Both products run on the fp32 MFMA; the weight gradient is summed
+ * from one slab per workgroup in a fixed order (no float atomics: the same inputs give the same bits).
+ * It replaces lf_conv2d_wgrad_bn_f32 (ksize 1, dy_out) + lf_conv2d_wgrad_reduce_f32 + lf_conv2d_dgrad_weights_f32
+ * + lf_conv2d_f32, which stay the route for every shape it does not take.
+ * lf_conv2d_proj_bwd_supported != 0 requires: cin 32 or 64 and cout == 2*cin (the filter bank is held in
+ * registers; so cin, cout % 32 == 0 and cin*cout <= 8192), h*w % P == 0 with P = 64 pixels per work item,
+ * cout*h*w < 2^30, and x, g, bn_y, w, dx non-null and 16-byte aligned (only their addresses are looked at).
+ * The caller keeps the four-call route for everything else; lf_conv2d_proj_bwd_f32 rejects it.
+ * lf_conv2d_proj_bwd_plan (host only, supported shapes): out[3] = {P, items per workgroup (1, 2, 3 = three
+ * or more), slab reduce stages (1 or 2)}.  workspace >= lf_conv2d_proj_bwd_workspace(...) bytes (0: unsupported). */
+int lf_conv2d_proj_bwd_supported(const float* x, const float* g, const float* bn_y, const float* w,
+                                 const float* dx, int n, int cin, int h, int wd, int cout);
+int lf_conv2d_proj_bwd_plan(int n, int cin, int h, int wd, int cout, int* out);
+size_t lf_conv2d_proj_bwd_workspace(int n, int cin, int h, int wd, int cout);
+int lf_conv2d_proj_bwd_f32(const float* x, const float* g, const float* bn_y, const float* coef, int bn_relu,
+                           const float* w, float* dx, float* dw, int n, int cin, int h, int wd, int cout,
+                           void* workspace, size_t ws_bytes, lf_stream_t stream);
+
 /* Depthwise 3x3 convolution, padding "same", depth multiplier 1, no bias: the first half of the separable
  * conv block (srcs/model/cnn.py:22-25, SeparableConv2D); the pointwise half is lf_conv2d_* with ksize == 1.
  *   y[n][c][i][j] = sum_t w[c][t] * a[n][c][i+ky-1][j+kx-1],  t = ky*3+kx,  w [C][9],

@@ -143,6 +143,10 @@ SIGNATURES = {
     "lf_conv2d_wgrad_bn_supported": [c_int, c_int, c_int, c_int, c_int, c_int],
     "lf_conv2d_wgrad_bn_f32": [P, P, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P,
                                c_int, P, c_size_t, P],
+    "lf_conv2d_proj_bwd_supported": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int],
+    "lf_conv2d_proj_bwd_plan": [c_int, c_int, c_int, c_int, c_int, P],
+    "lf_conv2d_proj_bwd_workspace": [c_int, c_int, c_int, c_int, c_int],
+    "lf_conv2d_proj_bwd_f32": [P, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P],
     "lf_dwconv3x3_f32": [P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, P],
     "lf_dwconv3x3_bwd_workspace": [c_int, c_int, c_int, c_int],
     "lf_dwconv3x3_bwd_f32": [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P],
@@ -178,6 +182,7 @@ SIGNATURES = {
     "lf_ema_update_f32": [P, P, c_size_t, c_float, c_int, P],
 }
 _RESTYPES = {"lf_last_error": C.c_char_p, "lf_conv2d_wgrad_workspace": c_size_t,
+             "lf_conv2d_proj_bwd_workspace": c_size_t,
              "lf_dwconv3x3_bwd_workspace": c_size_t,
              "lf_bn_workspace": c_size_t, "lf_se_bwd_workspace": c_size_t,
              "lf_adamw_workspace": c_size_t, "lf_conv2d_stats_tiles": C.c_longlong,

@@ -27,6 +27,9 @@
 //   fixed order (deterministic, no float atomics).  The 3x3 layers but the stem's use wgrad3_kernel,
 //   which accumulates in the Winograd F(2x2,3x3) domain instead.  wgrad_smallcin_kernel packs (ci, tap)
 //   into the MFMA's M dimension for the stem (Cin*9 <= 32): one MFMA per pixel pair.
+//
+// proj_bwd_kernel: the backward of a projection shortcut (1x1 conv + BatchNorm) in one pass — BatchNorm backward,
+//   the 1x1 weight gradient and the 1x1 input gradient share the staged dY, which never leaves the chip.
 #include <type_traits>
 
 #include "lf_common.h"
@@ -933,8 +936,10 @@ __device__ __forceinline__ float bn_dy1(float g, float y, float al, float ad, fl
     return fmaf(c2, dz, fmaf(c3, y, c4));
 }
 
+// Three waves per SIMD for the instantiations that spilled to scratch at four (128 registers): plan_wgrad sizes
+// the grid for three resident workgroups per CU anyway.  <16,8,1,2,2> needs more than either and runs at two.
 template <int TW, int TH, int WCI, int WCO, int KSPL>
-__global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
+__global__ __launch_bounds__(kThreads, KSPL == 2 ? 4 : 3) void wgrad_mfma_kernel(WgradArgs p) {
     static_assert(WCI * WCO * KSPL == 4, "wave decomposition");
     static_assert(TH % KSPL == 0 && TW % 4 == 0, "rows split across waves, float4 rows");
     constexpr int PP = (TW * TH) | 1;  // odd plane pitch (X and dY): 32 lanes on 32 channels hit 32 banks
@@ -1208,6 +1213,164 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_mfma_kernel(WgradArgs p) {
             if (ci < p.cin && co < p.cout) out[(size_t)ci * p.cout + co] = acc[r];
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// projection shortcut backward: BatchNorm backward + 1x1 weight gradient + 1x1 input gradient
+// ---------------------------------------------------------------------------
+// One pass over x, g and bn_y: dyp = BN'(g) (bn_dy1 with alpha 1, add 0: the bits wgrad_mfma_kernel writes to
+// dy_out) lives only in LDS and feeds both products,
+//   dW[ci][co] = sum_px x[ci][px] dyp[co][px]      (A = x, lane -> ci; B = dyp, lane -> co; K = pixels)
+//   dx[ci][px] = sum_co w[ci][co] dyp[co][px]      (A = w, lane -> ci; B = dyp, lane -> pixel; K = co)
+// A 1x1 has no halo: a plane is hw flat pixels and an item is kProjP consecutive pixels of one image.  A workgroup
+// owns every channel of its items (Cin = 32 CIB, Cout = 64 CIB, one wave per 32 output channels), so each tensor is
+// read once.  Wave w accumulates dW[all ci][co block w] over the workgroup's items and computes, per item, the dx
+// block (ci block w % CIB, pixel half w / CIB); its rows of w stay in registers for the whole launch (lane half h
+// holds co = h Cout/2 + s at k-step s, one contiguous run per lane), so the filter bank takes no LDS.  The next
+// item's loads are issued into registers ahead of the MFMAs; the dx block is stored (128-byte runs per channel)
+// before the weight-gradient MFMAs, which cover the stores' latency.  Grid = splits, one slab [Cin][Cout] each,
+// summed by lf::reduce_slabs in a fixed order: no atomics.
+struct ProjBwdArgs {
+    const float* x;     // [N][Cin][HW]
+    const float* g;     // [N][Cout][HW]
+    const float* bn_y;  // [N][Cout][HW]
+    const float* coef;  // [5][Cout]
+    const float* w;     // [Cin][Cout]
+    float* dx;          // [N][Cin][HW]
+    float* part;        // [splits][Cin][Cout]
+    int hw, items_per_image, items, items_per_split;
+    int bn_relu;
+};
+
+constexpr int kProjP = 64;
+
+__device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, 0);
+}
+
+template <int CIB>
+__global__ __launch_bounds__(128 * CIB, 2) void proj_bwd_kernel(ProjBwdArgs p) {
+    constexpr int CIN = 32 * CIB, COUT = 64 * CIB, NT = 128 * CIB;
+    constexpr int P = kProjP, PP = P | 1, P4 = P / 4;  // odd channel pitch: 32 lanes on 32 channels hit 32 banks
+    constexpr int CSTEP = NT / P4;                     // channels between a thread's staging slots
+    constexpr int XPT = CIN / CSTEP, DPT = COUT / CSTEP;
+    constexpr int HC = COUT / 2;
+    static_assert(CIN % CSTEP == 0 && COUT % CSTEP == 0 && HC % 4 == 0, "whole float4 slots per thread");
+    __shared__ float lds[(CIN + COUT) * PP + 5 * COUT];
+    float* lx = lds;
+    float* ld = lds + CIN * PP;
+    float* lbn = ld + COUT * PP;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int khalf = lane >> 5, j = lane & 31;
+    const int cib = wid % CIB, pxb = wid / CIB;
+    const unsigned uhw = (unsigned)p.hw;
+
+    for (int e = tid; e < 5 * COUT; e += NT) lbn[e] = p.coef[e];
+    // this wave's rows of w, for the whole launch
+    float wr[HC];
+    {
+        const float4* wp = reinterpret_cast<const float4*>(p.w + (size_t)(cib * 32 + j) * COUT + khalf * HC);
+#pragma unroll
+        for (int q = 0; q < HC / 4; ++q) {
+            const float4 v = wp[q];
+            wr[4 * q] = v.x;
+            wr[4 * q + 1] = v.y;
+            wr[4 * q + 2] = v.z;
+            wr[4 * q + 3] = v.w;
+        }
+    }
+    f32x16 accw[CIB];
+#pragma unroll
+    for (int a = 0; a < CIB; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accw[a][r] = 0.f;
+
+    // Staging invariants, decoded once: slot i of a thread is channel c0 + i * CSTEP, pixels 4 * slot .. + 3 of the
+    // item; an item only moves the buffer base.
+    const int c0 = tid / P4, slot = tid % P4;
+    const unsigned goff = 4u * ((unsigned)c0 * uhw + 4u * (unsigned)slot), gstep = 4u * CSTEP * uhw;
+    const int loff = c0 * PP + 4 * slot;
+    const unsigned xbytes = 4u * ((CIN - 1) * uhw + P), dbytes = 4u * ((COUT - 1) * uhw + P);
+    const unsigned soff = 4u * ((unsigned)(cib * 32 + 4 * khalf) * uhw + (unsigned)(pxb * 32 + j));
+
+    float4 xv[XPT], gv[DPT], yv[DPT];
+    auto load_item = [&](int item) {
+        const int n = item / p.items_per_image;
+        const size_t px0 = (size_t)(item - n * p.items_per_image) * P;
+        const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.x + (size_t)n * CIN * p.hw + px0, xbytes);
+        const __amdgpu_buffer_rsrc_t rg = buf_rsrc(p.g + (size_t)n * COUT * p.hw + px0, dbytes);
+        const __amdgpu_buffer_rsrc_t ry = buf_rsrc(p.bn_y + (size_t)n * COUT * p.hw + px0, dbytes);
+#pragma unroll
+        for (int i = 0; i < XPT; ++i) xv[i] = buf_load4(rx, goff + (unsigned)i * gstep);
+#pragma unroll
+        for (int i = 0; i < DPT; ++i) gv[i] = buf_load4(rg, goff + (unsigned)i * gstep);
+#pragma unroll
+        for (int i = 0; i < DPT; ++i) yv[i] = buf_load4(ry, goff + (unsigned)i * gstep);
+    };
+    auto store_item = [&]() {
+#pragma unroll
+        for (int i = 0; i < XPT; ++i) {
+            float* dst = lx + loff + i * CSTEP * PP;
+            dst[0] = xv[i].x;
+            dst[1] = xv[i].y;
+            dst[2] = xv[i].z;
+            dst[3] = xv[i].w;
+        }
+#pragma unroll
+        for (int i = 0; i < DPT; ++i) {
+            const int c = c0 + i * CSTEP;
+            const float k0 = lbn[c], k1 = lbn[COUT + c], k2 = lbn[2 * COUT + c], k3 = lbn[3 * COUT + c],
+                        k4 = lbn[4 * COUT + c];
+            float* dst = ld + loff + i * CSTEP * PP;
+            dst[0] = bn_dy1(gv[i].x, yv[i].x, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
+            dst[1] = bn_dy1(gv[i].y, yv[i].y, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
+            dst[2] = bn_dy1(gv[i].z, yv[i].z, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
+            dst[3] = bn_dy1(gv[i].w, yv[i].w, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
+        }
+    };
+    auto compute_item = [&](int item) {
+        // input gradient of the item: K = co, this lane half's run of HC channels
+        f32x16 accx;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accx[r] = 0.f;
+        const float* bx = ld + khalf * HC * PP + pxb * 32 + j;
+#pragma unroll
+        for (int s = 0; s < HC; ++s) accx = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[s], bx[s * PP], accx, 0, 0, 0);
+        const int n = item / p.items_per_image;
+        const size_t px0 = (size_t)(item - n * p.items_per_image) * P;
+        const __amdgpu_buffer_rsrc_t rdx = buf_rsrc(p.dx + (size_t)n * CIN * p.hw + px0, xbytes);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) buf_store1(rdx, soff + 4u * (unsigned)((r & 3) + 8 * (r >> 2)) * uhw, accx[r]);
+        // weight gradient: K = the item's pixels
+        const float* bw = ld + (wid * 32 + j) * PP + khalf;
+        const float* aw = lx + j * PP + khalf;
+#pragma unroll 8
+        for (int s = 0; s < P; s += 2) {
+            const float b = bw[s];
+#pragma unroll
+            for (int a = 0; a < CIB; ++a)
+                accw[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[a * 32 * PP + s], b, accw[a], 0, 0, 0);
+        }
+    };
+
+    const int first = blockIdx.x * p.items_per_split;
+    const int last = min(first + p.items_per_split, p.items);
+    if (first < last) load_item(first);
+    for (int item = first; item < last; ++item) {
+        __syncthreads();  // lbn is staged / the previous item's MFMAs have read the tiles
+        store_item();
+        __syncthreads();
+        if (item + 1 < last) load_item(item + 1);
+        compute_item(item);
+    }
+
+    float* out = p.part + (size_t)blockIdx.x * CIN * COUT;
+#pragma unroll
+    for (int a = 0; a < CIB; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            out[(a * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf) * COUT + wid * 32 + j] = accw[a][r];
 }
 
 
@@ -2030,6 +2193,31 @@ WgPlan plan_wgrad(int n, int cin, int cout, int h, int w, int ksize) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
+// proj_bwd_kernel: Cin 32 or 64 with Cout = 2 Cin (its instantiations), whole items, 32-bit byte offsets within
+// an image, a 32-bit item count
+struct ProjPlan {
+    int cib, items_per_image, items, splits, items_per_split;
+};
+inline bool proj_bwd_shape(int n, int cin, int h, int wd, int cout) {
+    if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || wd <= 0) return false;
+    if (cin % 32 != 0 || cout % 32 != 0 || (long long)cin * cout > 8192) return false;
+    if ((cin != 32 && cin != 64) || cout != 2 * cin) return false;
+    const long long hw = (long long)h * wd;
+    return hw % kProjP == 0 && cout * hw < (1ll << 30) && n * (hw / kProjP) < (1ll << 31);
+}
+inline ProjPlan plan_proj_bwd(int n, int cin, int h, int wd) {
+    ProjPlan pl;
+    pl.cib = cin / 32;
+    pl.items_per_image = h * wd / kProjP;
+    pl.items = n * pl.items_per_image;
+    // two waves per SIMD are resident (the kernel's register budget): 8 waves per CU
+    const int resident = 256 * 8 / (2 * pl.cib);
+    const int splits = resident < pl.items ? resident : pl.items;
+    pl.items_per_split = (pl.items + splits - 1) / splits;
+    pl.splits = (pl.items + pl.items_per_split - 1) / pl.items_per_split;
+    return pl;
+}
+
 // Images per workgroup strip: 2 when the 28x8 tile would leave the last tile of every image
 // half empty (H = 28: 3.5 tiles) and the shape meets what the strip path needs (full-width
 // vector tiles, Cin a whole number of K-chunks, two images within 32-bit byte offsets).
@@ -2323,6 +2511,58 @@ int lf_conv2d_wgrad_reduce_f32(void* workspace, float* dw, int n, int cin, int h
     const size_t count = (size_t)cin * ksize * ksize * cout;
     lf::reduce_slabs(static_cast<float*>(workspace), dw, count, pl.splits, beta, lf::as_stream(stream));
     return lf::check_launch("lf_conv2d_wgrad_reduce");
+}
+
+int lf_conv2d_proj_bwd_supported(const float* x, const float* g, const float* bn_y, const float* w,
+                                 const float* dx, int n, int cin, int h, int wd, int cout) {
+    if (!x || !g || !bn_y || !w || !dx) return 0;
+    if (!aligned16(x) || !aligned16(g) || !aligned16(bn_y) || !aligned16(w) || !aligned16(dx)) return 0;
+    return proj_bwd_shape(n, cin, h, wd, cout) ? 1 : 0;
+}
+
+int lf_conv2d_proj_bwd_plan(int n, int cin, int h, int wd, int cout, int* out) {
+    LF_REQUIRE(out, "lf_conv2d_proj_bwd_plan: null out");
+    LF_REQUIRE(proj_bwd_shape(n, cin, h, wd, cout), "lf_conv2d_proj_bwd_plan: unsupported shape");
+    const ProjPlan pl = plan_proj_bwd(n, cin, h, wd);
+    out[0] = kProjP;
+    out[1] = pl.items_per_split < 3 ? pl.items_per_split : 3;  // 1, 2, or 3+: how far the prefetch runs
+    out[2] = lf::slab_stages(pl.splits);
+    return LF_OK;
+}
+
+size_t lf_conv2d_proj_bwd_workspace(int n, int cin, int h, int wd, int cout) {
+    if (!proj_bwd_shape(n, cin, h, wd, cout)) return 0;
+    const ProjPlan pl = plan_proj_bwd(n, cin, h, wd);
+    return ((size_t)pl.splits + lf::slab_groups(pl.splits)) * cin * cout * sizeof(float);
+}
+
+int lf_conv2d_proj_bwd_f32(const float* x, const float* g, const float* bn_y, const float* coef, int bn_relu,
+                           const float* w, float* dx, float* dw, int n, int cin, int h, int wd, int cout,
+                           void* workspace, size_t ws_bytes, lf_stream_t stream) {
+    const char* who = "lf_conv2d_proj_bwd";
+    LF_REQUIRE(x && g && bn_y && coef && w && dx && dw && workspace, "%s: null buffer", who);
+    LF_REQUIRE(lf_conv2d_proj_bwd_supported(x, g, bn_y, w, dx, n, cin, h, wd, cout),
+               "%s: shape/alignment not supported (ask lf_conv2d_proj_bwd_supported first)", who);
+    if (ws_bytes < lf_conv2d_proj_bwd_workspace(n, cin, h, wd, cout)) {
+        lf::set_error("%s: workspace %zu < %zu bytes", who, ws_bytes,
+                      lf_conv2d_proj_bwd_workspace(n, cin, h, wd, cout));
+        return LF_ERR_WORKSPACE;
+    }
+    const ProjPlan pl = plan_proj_bwd(n, cin, h, wd);
+    ProjBwdArgs a;
+    a.x = x; a.g = g; a.bn_y = bn_y; a.coef = coef; a.w = w; a.dx = dx;
+    a.part = static_cast<float*>(workspace);
+    a.hw = h * wd; a.items_per_image = pl.items_per_image; a.items = pl.items;
+    a.items_per_split = pl.items_per_split;
+    a.bn_relu = bn_relu;
+    hipStream_t s = lf::as_stream(stream);
+    if (pl.cib == 1)
+        proj_bwd_kernel<1><<<pl.splits, 128, 0, s>>>(a);
+    else
+        proj_bwd_kernel<2><<<pl.splits, 256, 0, s>>>(a);
+    if (const int rc = lf::check_launch(who)) return rc;
+    lf::reduce_slabs(a.part, dw, (size_t)cin * cout, pl.splits, 0.f, s);
+    return lf::check_launch(who);
 }
 
 }  // extern "C"

@@ -693,12 +693,18 @@ class LeafCNN:
                          tile_sums=tsum)
             if cin != f:
                 stp = self.stats[p + "bnp"]
-                # projection BN backward + 1x1 weight gradient (dyp -> gC)
-                bn_bwd_wgrad(xin, gA, yp, stp, P[p + "bnp.gamma"], G[p + "bnp.gamma"],
-                             G[p + "bnp.beta"], False, 1, G[p + "proj.w"], gC, pro[0], pro[1], pro[2],
-                             plane_g=psum_p)
                 dx = B(p + "dx", xin.shape)
-                self._dgrad(gC, p + "proj.w", 1, dx, bf16)
+                if bf16:
+                    # projection BN backward + 1x1 weight gradient (dyp -> gC)
+                    bn_bwd_wgrad(xin, gA, yp, stp, P[p + "bnp.gamma"], G[p + "bnp.gamma"],
+                                 G[p + "bnp.beta"], False, 1, G[p + "proj.w"], gC, pro[0], pro[1], pro[2],
+                                 plane_g=psum_p)
+                    self._dgrad(gC, p + "proj.w", 1, dx, bf16)
+                else:
+                    # projection BN backward, 1x1 weight gradient and dx in one kernel where the shape allows
+                    # (dyp stays on chip; gC holds it on the fallback route)
+                    nn.proj_bwd(xin, gA, yp, stp, P[p + "bnp.gamma"], G[p + "bnp.gamma"], G[p + "bnp.beta"],
+                                P[p + "proj.w"], G[p + "proj.w"], dx, gC, pro[0], pro[1], pro[2], plane_g=psum_p)
             else:
                 dx = gA  # identity shortcut: dx starts as dr
             # at stage 0 dx feeds the stem's BN backward: gather its sums in this epilogue

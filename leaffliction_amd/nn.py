@@ -15,6 +15,8 @@ _ws_cache = {}
 _ws_gen = 0
 # A/B knob for measurements: route BatchNorm backward through the standalone apply kernel
 _NO_FUSED_BN_WGRAD = os.environ.get("LEAFFLICTION_NO_FUSED_BN_WGRAD", "0") == "1"
+# A/B knob for measurements: the projection shortcut's backward as bn_bwd_wgrad + the 1x1 input-gradient convolution
+_NO_FUSED_PROJ_BWD = os.environ.get("LEAFFLICTION_NO_FUSED_PROJ_BWD", "0") == "1"
 
 
 def _workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
@@ -489,6 +491,39 @@ def bn_bwd_wgrad(x: torch.Tensor, g: torch.Tensor, y_bn: torch.Tensor, stats: to
     _lib.call("lf_conv2d_wgrad_reduce_f32", ws.data_ptr(), dw_out.data_ptr(), n, cin, h, w, cout,
               ksize, 0.0, _stream())
     return dy_out
+
+
+def proj_bwd(x: torch.Tensor, g: torch.Tensor, y_bn: torch.Tensor, stats: torch.Tensor, gamma, dgamma, dbeta,
+             w: torch.Tensor, dw_out: torch.Tensor, dx_out: torch.Tensor, dy_scratch: Optional[torch.Tensor] = None,
+             in_scale=None, in_shift=None, in_relu: bool = False, plane_g=None) -> torch.Tensor:
+    """Backward of a projection shortcut y_bn = conv1x1(x, w) followed by BatchNormalization without ReLU, g being
+    the gradient wrt the BatchNorm's output: fills dgamma / dbeta, dw_out [Cin,1,Cout] and dx_out (overwritten: the
+    main path's input gradient accumulates onto it afterwards).  One kernel reads x, g and y_bn once and keeps
+    dy = BN'(g) on chip (lf_conv2d_proj_bwd_f32); shapes it does not take, and a prologue on x, go through
+    bn_bwd_wgrad + conv2d_dgrad_weights + conv2d with dy in dy_scratch (same results up to rounding)."""
+    who = "proj_bwd"
+    _chk(x, _F32, f"{who}.x", 4)
+    n, cin, h, wd, cout = _bn_bwd_wgrad_checks(who, _F32, x, g, y_bn, dy_scratch, dw_out, 1, in_scale, in_shift,
+                                               None, None, plane_g, None)
+    _chk(w, _F32, f"{who}.w", 3)
+    _chk(dx_out, _F32, f"{who}.dx_out", 4)
+    if tuple(w.shape) != (cin, 1, cout) or dx_out.shape != x.shape:
+        raise ValueError(f"{who}: shape mismatch")
+    lib = _lib.load()
+    if _NO_FUSED_PROJ_BWD or in_scale is not None or not lib.lf_conv2d_proj_bwd_supported(
+            x.data_ptr(), g.data_ptr(), y_bn.data_ptr(), w.data_ptr(), dx_out.data_ptr(), n, cin, h, wd, cout):
+        if dy_scratch is None:
+            dy_scratch = torch.empty_like(g)
+        bn_bwd_wgrad(x, g, y_bn, stats, gamma, dgamma, dbeta, False, 1, dw_out, dy_scratch, in_scale, in_shift,
+                     in_relu, plane_g=plane_g)
+        return conv2d(dy_scratch, conv2d_dgrad_weights(w, 1), 1, out=dx_out)
+    coef, _ = _bn_bwd_coef(who, stats, gamma, dgamma, dbeta, False, n, cout, h * wd, x.device, g, y_bn,
+                           plane_g=plane_g)
+    ws = _workspace(lib.lf_conv2d_proj_bwd_workspace(n, cin, h, wd, cout), x.device)
+    _lib.call("lf_conv2d_proj_bwd_f32", x.data_ptr(), g.data_ptr(), y_bn.data_ptr(), coef.data_ptr(), 0,
+              w.data_ptr(), dx_out.data_ptr(), dw_out.data_ptr(), n, cin, h, wd, cout, ws.data_ptr(), ws.numel(),
+              _stream())
+    return dx_out
 
 
 def _dw_weights(who: str, w_c9: torch.Tensor, c: int) -> None:
