@@ -1117,6 +1117,26 @@ int lf_head_distill_bwd_f32(const float* feat, const float* w, const float* prob
                             const float* soft, float temperature, float alpha, float* dlogits, float* dfeat,
                             float* dw, float* db, int n, int f, int c, float inv_n, lf_stream_t stream);
 
+/* Mixup and CutMix: lf_input_stage_f32 (below) writing a blend of two model views per image, and the same blend of
+ * the targets.  For a batch of n images of h x w, mix8[i] = {partner, w_out, w_in, y0, y1, x0, x1, t} (device, f32):
+ *   A_i  = image i after its own aug4[i] (flip, rotation, contrast about its own mean, clamp) on the [0,1] image:
+ *          what lf_input_stage_f32 normalises; A_p the same for image p = partner with aug4[p] and p's means.
+ *   out[i](y, x) = (v - mean) / denom,  v = w A_i(y, x) + (1 - w) A_p(y, x),
+ *          w = w_in where y0 <= y < y1 and x0 <= x < x1 (output coordinates), w = w_out elsewhere.
+ *   w == 1: A_p is not sampled and v = A_i(y, x); w == 0: A_i is not sampled and v = A_p(y, x).  Such a pixel equals
+ *          lf_input_stage_f32's of that view bit for bit.
+ *   targets (lf_mix_targets_f32): out[i] = y[p] + t (y[i] - y[p]); t == 1 stores y[i] and t == 0 stores y[p] exactly.
+ * Mixup with factor l is w_out = w_in = t = l and an empty box; CutMix is w_out = 1, w_in = 0,
+ * t = 1 - (y1 - y0)(x1 - x0) / (h w); an unmixed row is w_out = w_in = t = 1.  partner may equal i.
+ * The rows are device data, so the entries cannot refuse a bad one without a sync: both clamp partner into
+ * [0, n - 1] and w_out, w_in, t into [0, 1], and read a NaN as 0 there; a NaN box edge puts every pixel outside.
+ * Other arguments, scratch and constraints as for lf_input_stage_f32 (means_ws: n*24 floats, all n images' means
+ * are taken).  lf_mix_targets_f32: y, out [n][c], n <= 65535, c <= 4096, out must not overlap y. */
+int lf_input_stage_mix_f32(const uint8_t* in, float* out, int n, int h, int w, const float* aug4,
+                           const float* mix8, const float* mean3, const float* denom3, float* means_ws,
+                           lf_stream_t stream);
+int lf_mix_targets_f32(const float* y, const float* mix8, float* out, int n, int c, lf_stream_t stream);
+
 /* ---- input stage ----------------------------------------------------------- */
 /* u8 HWC -> f32 NCHW with the model's train-time augmentation fused (cnn.py:74-86):
  * keras RandomFlip("horizontal") -> RandomRotation (bilinear, fill_mode="reflect") ->

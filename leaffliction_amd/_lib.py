@@ -152,6 +152,8 @@ SIGNATURES = {
     "lf_dwconv3x3_bwd_f32": [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P],
     "lf_conv2d_wgrad_reduce_f32": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P],
     "lf_input_stage_f32": [P, P, c_int, c_int, c_int, P, P, P, P, P],
+    "lf_input_stage_mix_f32": [P, P, c_int, c_int, c_int, P, P, P, P, P, P],
+    "lf_mix_targets_f32": [P, P, P, c_int, c_int, P],
     "lf_scale_shift_act_f32": [P, P, c_int, c_int, c_int, P, P, c_int, P],
     "lf_bn_workspace": [c_int],
     "lf_bn_train_stats_f32": [P, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P, P, P, P,

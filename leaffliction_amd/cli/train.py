@@ -13,6 +13,10 @@ Beyond the reference: `--out-dir DIR` (default artifacts/models) says where the 
 `--teacher DIR [--distill-alpha 0.5] [--distill-temperature 4.0]` trains by knowledge distillation from the
 model in the learnings directory DIR: loss = (1 - alpha) * cross-entropy + alpha * T^2 * KL(teacher_T || student_T),
 the teacher running its inference path on every batch (bf16 unless --no-mixed-precision or it cannot).
+`--mixup ALPHA` / `--cutmix ALPHA` [`--mix-prob P`] (defaults 0, 0, 1.0: off) turn on the batch-mixing regularisers:
+with probability P an image is blended with a partner from its batch, by Mixup (lambda ~ Beta(ALPHA, ALPHA)) or
+CutMix (a pasted box of area 1 - lambda), a fair coin deciding where both are on, and the step trains on the labels
+blended in the same ratio.  Not together with --teacher.
 """
 from __future__ import annotations
 
@@ -65,6 +69,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--distill-alpha", type=float, default=0.5,
                    help="weight of the soft-target term: loss = (1 - alpha) * CE + alpha * T^2 * KL")
     p.add_argument("--distill-temperature", type=float, default=4.0)
+    p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
+                   help="Mixup with lambda ~ Beta(ALPHA, ALPHA); 0 = off")
+    p.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
+                   help="CutMix with a box of area 1 - lambda, lambda ~ Beta(ALPHA, ALPHA); 0 = off")
+    p.add_argument("--mix-prob", type=float, default=1.0, metavar="P",
+                   help="probability that an image is mixed at all (with --mixup / --cutmix)")
     p.add_argument("--out-dir", type=Path, default=Path("artifacts/models"),
                    help="where the model and its JSON artifacts are written")
     args = p.parse_args(argv)
@@ -160,6 +170,25 @@ def load_teacher(args, label2idx: Dict[str, int]):
     return teacher, {"teacher": str(tdir), "alpha": alpha, "temperature": temperature, "teacher_dtype": dtype}
 
 
+def mix_setting(args):
+    """The "mix" entry of the training configuration and of meta.json from --mixup / --cutmix / --mix-prob, None
+    when both alphas are 0.  Refused with ValueError: a negative or non-finite alpha, a probability outside [0, 1],
+    and mixing together with --teacher (the teacher would have to see the mixed image, which exists only inside the
+    student's input stage)."""
+    import math
+    mixup, cutmix, prob = float(args.mixup), float(args.cutmix), float(args.mix_prob)
+    for flag, a in (("--mixup", mixup), ("--cutmix", cutmix)):
+        if not (a >= 0.0 and math.isfinite(a)):
+            raise ValueError(f"{flag} must be >= 0 and finite, got {a}")
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"--mix-prob must lie in [0, 1], got {prob}")
+    if mixup == 0.0 and cutmix == 0.0:
+        return None
+    if args.teacher is not None:
+        raise ValueError("--mixup / --cutmix cannot be combined with --teacher")
+    return {"mixup": mixup, "cutmix": cutmix, "prob": prob}
+
+
 def create_data_sequences(train_items, val_items, label2idx, args, cfg, num_classes, dp):
     seq_workers = get_optimal_worker_count()
     common = dict(num_classes=num_classes, one_hot=cfg["label_smoothing"] > 0.0, workers=seq_workers,
@@ -241,6 +270,11 @@ def main(argv=None) -> None:
         train_items, val_items, label2idx = prepare_data(manifest_path)
         num_classes = len(label2idx)
         cfg = get_training_config(args.fast)
+        mix = mix_setting(args)
+        if mix is not None:
+            cfg["mix"] = mix
+            LOGGER.info("Mixing: mixup alpha %.3g, cutmix alpha %.3g, probability %.3g", mix["mixup"], mix["cutmix"],
+                        mix["prob"])
         teacher = distillation = None
         if args.teacher is not None:
             teacher, distillation = load_teacher(args, label2idx)
@@ -252,6 +286,8 @@ def main(argv=None) -> None:
         meta["training"]["mixed_precision"] = model.train_dtype == "bf16"
         if distillation is not None:
             meta["training"]["distillation"] = distillation
+        if mix is not None:
+            meta["training"]["mix"] = mix
         callbacks, ema_cb = build_callbacks(cfg)
         if getattr(args, "target_val_acc", None):
             callbacks.append(StopOnValAcc(args.target_val_acc))

@@ -106,10 +106,48 @@ class Normalization:
         return np.maximum(np.sqrt(self.variance), NORM_EPS).astype(np.float32)
 
 
+MIX_UNMIXED = (0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0)   # a mix8 row that leaves image and label alone (partner set per row)
+
+
+def draw_mix_rows(rng: np.random.RandomState, n: int, h: int, w: int, mixup: float, cutmix: float,
+                  prob: float) -> np.ndarray:
+    """The Mixup / CutMix rows of one step, f32 [n, 8] = {partner, w_out, w_in, y0, y1, x0, x1, t} (the rule is stated
+    at lf_input_stage_mix_f32 in include/leafhip.h).  Partners are one permutation of range(n).  Per image: unmixed
+    with probability 1 - prob; else Mixup or CutMix (a fair coin when both alphas are positive, else the positive
+    one) with lambda ~ Beta(alpha, alpha).  Mixup: w_out = w_in = t = lambda, empty box.  CutMix: the box of
+    timm / the CutMix paper, r = sqrt(1 - lambda), bh = int(h r), bw = int(w r), centre (int(U h), int(U w)), clipped to
+    the image; w_out = 1, w_in = 0 and t = 1 - area / (h w) from the clipped box.
+    Taken from `rng`, in this order: the permutation; n uniforms for "mixed at all" (u < prob) and n for the coin
+    (u < 1/2: Mixup); n Beta(mixup, mixup) if mixup > 0; n Beta(cutmix, cutmix) if cutmix > 0; n uniforms for the
+    box centre's row and n for its column.  So the count depends on n and on which alphas are positive only, never
+    on what was drawn."""
+    rows = np.empty((n, 8), np.float32)
+    rows[:] = MIX_UNMIXED
+    rows[:, 0] = rng.permutation(n)
+    mixed = rng.uniform(size=n) < prob
+    coin = rng.uniform(size=n) < 0.5
+    lam_m = rng.beta(mixup, mixup, size=n) if mixup > 0 else None
+    lam_c = rng.beta(cutmix, cutmix, size=n) if cutmix > 0 else None
+    uy, ux = rng.uniform(size=n), rng.uniform(size=n)
+    for i in np.nonzero(mixed)[0]:
+        if lam_m is not None and (lam_c is None or coin[i]):
+            rows[i, 1:3] = rows[i, 7] = min(max(lam_m[i], 0.0), 1.0)
+            continue
+        r = math.sqrt(1.0 - min(max(lam_c[i], 0.0), 1.0))
+        bh, bw = int(h * r), int(w * r)
+        cy, cx = int(uy[i] * h), int(ux[i] * w)
+        y0, y1 = min(max(cy - bh // 2, 0), h), min(max(cy + bh // 2, 0), h)
+        x0, x1 = min(max(cx - bw // 2, 0), w), min(max(cx + bw // 2, 0), w)
+        rows[i, 1:7] = (1.0, 0.0, y0, y1, x0, x1)
+        rows[i, 7] = 1.0 - (y1 - y0) * (x1 - x0) / float(h * w)
+    return rows
+
+
 class LeafCNN:
     name = "leaf_cnn"
     _mut = 0                            # see __init__ (class-level defaults: subclasses that skip it still step)
     last_kd: Optional[torch.Tensor] = None   # train_step with a teacher: the per-sample kd term
+    last_targets: Optional[torch.Tensor] = None   # train_step with mixing on: the mixed targets the step trained on
     _infer_cache: Dict[str, Any] = {}
 
     def __init__(self, *, num_classes: int, img_size: int = 224, use_norm: bool = True,
@@ -149,6 +187,7 @@ class LeafCNN:
         self._infer_cache: Dict[str, Any] = {}
         self.gen = torch.Generator(device="cpu").manual_seed(int(seed))
         self.np_rng = np.random.RandomState(int(seed) & 0x7FFFFFFF)
+        self.mix_rng = np.random.RandomState(self._mix_seed(seed))
         from ..utils.system_info import cap_torch_threads
         cap_torch_threads()   # the per-step host draws are small CPU tensor ops: see there
 
@@ -271,67 +310,102 @@ class LeafCNN:
             keep = (torch.rand((n, self.widths[-1]), generator=self.gen) >= self.drop_top).float()
             torch.div(keep, 1.0 - self.drop_top, out=out[k])
 
-    def draw_step_randoms(self, n: int, augment: bool):
-        """All per-step host draws (SpatialDropout2D / Dropout keep-scales, in-model
-        augmentation parameters) through ONE pinned staging buffer and one asynchronous copy:
-        pageable uploads would block the host until the stream drains, once per tensor.
-        Returns (drops, top_drop, aug4) as views of a persistent device buffer."""
-        sizes = []
+    def _host_mix(self, n: int, h: int, w: int) -> np.ndarray:
+        """This step's mix8 rows (draw_mix_rows at the compiled setting) from the mix generator."""
+        mixup, cutmix, prob = self._mix_setting()
+        return draw_mix_rows(self.mix_rng, n, h, w, mixup, cutmix, prob)
+
+    def _step_random_views(self, n: int, augment: bool, mix: bool) -> Dict[str, Tuple[int, int]]:
+        """name -> shape of the per-step random tensors, in their order in the staging buffer: "drop<i>" per stage,
+        "top", "aug", "mix" — each only when the model (or the step) has it."""
+        shapes: Dict[str, Tuple[int, int]] = {}
         if self.drop_block > 0:
-            sizes += [(n, f) for f in self.widths]
+            shapes.update({f"drop{i}": (n, f) for i, f in enumerate(self.widths)})
         if self.drop_top > 0:
-            sizes.append((n, self.widths[-1]))
+            shapes["top"] = (n, self.widths[-1])
         if augment:
-            sizes.append((n, 4))
-        if not sizes:
-            return None, None, None
-        st = self._stage.get((n, augment))
+            shapes["aug"] = (n, 4)
+        if mix:
+            shapes["mix"] = (n, 8)
+        return shapes
+
+    @staticmethod
+    def _named_views(flat: torch.Tensor, shapes: Dict[str, Tuple[int, int]]) -> Dict[str, torch.Tensor]:
+        out, off = {}, 0
+        for name, (a, b) in shapes.items():
+            out[name] = flat[off:off + a * b].view(a, b)
+            off += a * b
+        return out
+
+    def _fill_step_randoms(self, hv: Dict[str, torch.Tensor], n: int, mix_hw: Optional[Tuple[int, int]]) -> None:
+        """This step's draws into the host views `hv` (_named_views of _step_random_views): dropout from `gen`,
+        augmentation from `np_rng`, the mix rows from `mix_rng`.  Needs no device."""
+        self._host_dropout(n, [v for k, v in hv.items() if k.startswith("drop") or k == "top"])
+        if "aug" in hv:
+            hv["aug"].copy_(torch.from_numpy(self._host_augmentation(n)))
+        if "mix" in hv:
+            hv["mix"].copy_(torch.from_numpy(self._host_mix(n, *mix_hw)))
+
+    def draw_step_randoms(self, n: int, augment: bool, mix_hw: Optional[Tuple[int, int]] = None):
+        """All per-step host draws (SpatialDropout2D / Dropout keep-scales, in-model
+        augmentation parameters, with mix_hw = (H, W) of the batch the Mixup / CutMix rows) through ONE pinned
+        staging buffer and one asynchronous copy:
+        pageable uploads would block the host until the stream drains, once per tensor.
+        Returns (drops, top_drop, aug4, mix8) as views of a persistent device buffer."""
+        shapes = self._step_random_views(n, augment, mix_hw is not None)
+        if not shapes:
+            return None, None, None, None
+        skey = (n, augment) if mix_hw is None else (n, augment, "mix")
+        st = self._stage.get(skey)
         if st is None:
-            total = sum(a * b for a, b in sizes)
+            total = sum(a * b for a, b in shapes.values())
             st = {"dev": torch.empty(total, dtype=torch.float32, device=self.device),
                   "ring": [(torch.empty(total, dtype=torch.float32).pin_memory(),
                             torch.cuda.Event()) for _ in range(3)], "i": 0, "used": 0}
-            self._stage[(n, augment)] = st
-
-        def views(flat):
-            out, off = [], 0
-            for a, b in sizes:
-                out.append(flat[off:off + a * b].view(a, b))
-                off += a * b
-            return out
-
+            self._stage[skey] = st
         host, ev = st["ring"][st["i"]]
         if st["used"] >= len(st["ring"]):
             ev.synchronize()  # the copy that last read this pinned slot has executed
         st["i"] = (st["i"] + 1) % len(st["ring"])
         st["used"] += 1
-        hv = views(host)
-        self._host_dropout(n, hv)
-        if augment:
-            hv[-1].copy_(torch.from_numpy(self._host_augmentation(n)))
+        self._fill_step_randoms(self._named_views(host, shapes), n, mix_hw)
         st["dev"].copy_(host, non_blocking=True)
         ev.record()
-        dv = views(st["dev"])
-        k = 0
-        drops = top = aug4 = None
-        if self.drop_block > 0:
-            drops = dv[:len(self.widths)]
-            k = len(self.widths)
-        if self.drop_top > 0:
-            top = dv[k]
-        if augment:
-            aug4 = dv[-1]
-        return drops, top, aug4
+        dv = self._named_views(st["dev"], shapes)
+        drops = [dv[f"drop{i}"] for i in range(len(self.widths))] if self.drop_block > 0 else None
+        return drops, dv.get("top"), dv.get("aug"), dv.get("mix")
 
-    def _input(self, x, training: bool, aug4: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _identity_aug(self, n: int) -> torch.Tensor:
+        """aug4 rows that leave an image alone (no flip, angle 0, contrast 1), in a buffer that stays (the step's HIP
+        graph bakes its address in; the eager steps before the capture create it)."""
+        t = self._bufs.setdefault(n, {}).get("aug_id")
+        if t is None:
+            t = self._bufs[n]["aug_id"] = torch.tensor([[0.0, 1.0, 0.0, 1.0]] * n, dtype=torch.float32,
+                                                       device=self.device)
+        return t
+
+    def _input(self, x, training: bool, aug4: Optional[torch.Tensor] = None,
+               mix8: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Accepts uint8 [N,H,W,3] (host or device) or float32 [N,H,W,3] in [0,1] (the
-        reference loader's format); returns normalised f32 NCHW on the device."""
+        reference loader's format); returns normalised f32 NCHW on the device.  mix8 (f32 [N,8] on the device, with
+        training): the Mixup / CutMix input stage, nn.input_stage_mix; a model without in-model augmentation mixes
+        the plain images (identity aug4 rows)."""
         if isinstance(x, np.ndarray):
             x = torch.from_numpy(np.ascontiguousarray(x))
         x = x.to(self.device, non_blocking=True)
         n = x.shape[0]
         mean, denom = self._norm_consts()
         out = self._buf(n, "x0", (n, 3, x.shape[1], x.shape[2]))
+        if training and mix8 is not None:
+            if x.dtype == torch.float32:
+                x = (x * 255.0).round().clamp_(0, 255).to(torch.uint8)
+            elif x.dtype != torch.uint8:
+                raise TypeError("model input must be uint8 or float32 [N,H,W,3]")
+            if not self.augment:
+                aug4 = self._identity_aug(n)
+            elif aug4 is None:
+                aug4 = self.draw_augmentation(n)
+            return nn.input_stage_mix(x.contiguous(), aug4, mix8, mean, denom, out=out)
         if x.dtype == torch.uint8:
             x = x.contiguous()
             if training and self.augment:
@@ -808,6 +882,9 @@ class LeafCNN:
         teacher_probs (f32 [N,C] on the device; needs compile(loss={..., "distill": {...}})): the step minimises
         (1 - alpha) * cross-entropy + alpha * T^2 KL(teacher_T || student_T) (lf_head_distill_*_f32), the returned
         loss is that sum and `last_kd` holds the per-sample kd term; without it the step is the plain one.
+        With a compiled "mix" setting the step draws its Mixup / CutMix rows, mixes within the local batch in the input
+        stage and trains on the mixed targets, which `last_targets` holds afterwards (None otherwise); a teacher
+        and mixing together are refused.
         grad_sync(flat_g) is called between backward and the optimizer (data-parallel
         all-reduce); with global_n the local gradient is scaled by 1/global_n so that a SUM
         all-reduce yields the global-batch mean.  Returns (probs, per-sample loss) device
@@ -833,6 +910,11 @@ class LeafCNN:
             self._distill_setting(required=True)
             extra = {"teacher_probs": teacher_probs}
         self.last_kd = self._kd_buf(n) if extra else None
+        mixing = self._mix_setting() is not None and n > 0
+        if mixing and extra:
+            raise ValueError("train_step: Mixup / CutMix with a teacher is not supported (the teacher would have to "
+                             "see the mixed image, which exists only inside this model's input stage)")
+        self.last_targets = self._mixed_targets_buf(n, self.num_classes) if mixing else None
         if grad_overlap is not None:
             # two exchanges, the same two on every rank (a rank with an empty batch sends zeros in both)
             split = min(self.n_params, -(-self.grad_split() // 64) * 64)   # whole 256-byte lines per piece
@@ -871,7 +953,9 @@ class LeafCNN:
         through their fixed staging buffer before the replay; the optimizer (its learning rate
         changes every step) and the gradient all-reduce stay outside.  LEAFFLICTION_GRAPH=0 turns
         this off.  teacher_probs (train_step) has a fixed buffer of its own, st["t"], and the distillation setting
-        is part of the graph's key: the step with a teacher and the step without are two graphs."""
+        is part of the graph's key: the step with a teacher and the step without are two graphs.  The Mixup /
+        CutMix rows are one more view of the staging buffer and the mix setting one more part of the key: a model
+        compiled without mixing replays the graph it always did."""
         if self._graphs_on and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8:
             return self._forward_backward_graph(x, y_true, between, teacher_probs)
         return self._forward_backward_eager(x, y_true, between, teacher_probs)
@@ -882,6 +966,10 @@ class LeafCNN:
                between is not None)
         if teacher_probs is not None:
             key += (self._distill_setting(required=True),)
+        mix_hw = None
+        if self._mix_setting() is not None:
+            key += (("mix",) + self._mix_setting(),)
+            mix_hw = (int(x.shape[1]), int(x.shape[2]))
         st = self._graphs.get(key)
         if st is None:
             st = self._graphs[key] = {"calls": 0, "graph": None}
@@ -893,7 +981,7 @@ class LeafCNN:
             st["graph"], st["calls"] = None, 2
         if st["graph"] is None and st["calls"] <= 2:
             return self._forward_backward_eager(x, y_true, between, teacher_probs)
-        drops, top, aug4 = self.draw_step_randoms(n, self.augment)  # fixed device views, fresh values
+        drops, top, aug4, mix8 = self.draw_step_randoms(n, self.augment, mix_hw)  # fixed device views, fresh values
         if st["graph"] is None:
             st["x"] = torch.empty_like(x)
             st["y"] = torch.empty_like(y_true)
@@ -911,14 +999,14 @@ class LeafCNN:
                 with torch.cuda.graph(g):
                     st["out"] = self._forward_backward_body(st["x"], st["y"], drops, top, aug4,
                                                             part=None if between is None else 0,
-                                                            teacher_probs=st["t"])
+                                                            teacher_probs=st["t"], mix8=mix8)
                 if g2 is not None:
                     with torch.cuda.graph(g2, pool=g.pool()):
                         self._forward_backward_body(st["x"], st["y"], drops, top, aug4, part=1)
             except Exception:
                 self._graphs_on = False   # capture is an optimisation: fall back to eager launches
                 torch.cuda.synchronize()
-                return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs)
+                return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs, mix8)
             st["graph"], st["graph2"] = g, g2
             st["ws_gen"] = nn.workspace_generation()
         else:
@@ -934,23 +1022,30 @@ class LeafCNN:
 
     def _forward_backward_eager(self, x, y_true: torch.Tensor, between=None, teacher_probs=None):
         n = int(x.shape[0])
-        drops, top, aug4 = self.draw_step_randoms(n, self.augment)
-        return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs)
+        mix_hw = (int(x.shape[1]), int(x.shape[2])) if self._mix_setting() is not None else None
+        drops, top, aug4, mix8 = self.draw_step_randoms(n, self.augment, mix_hw)
+        return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs, mix8)
 
-    def _forward_backward_split(self, x, y_true, drops, top, aug4, between, teacher_probs=None):
+    def _forward_backward_split(self, x, y_true, drops, top, aug4, between, teacher_probs=None, mix8=None):
         if between is None:
-            return self._forward_backward_body(x, y_true, drops, top, aug4, teacher_probs=teacher_probs)
-        out = self._forward_backward_body(x, y_true, drops, top, aug4, part=0, teacher_probs=teacher_probs)
+            return self._forward_backward_body(x, y_true, drops, top, aug4, teacher_probs=teacher_probs, mix8=mix8)
+        out = self._forward_backward_body(x, y_true, drops, top, aug4, part=0, teacher_probs=teacher_probs,
+                                          mix8=mix8)
         between()
         self._forward_backward_body(x, y_true, drops, top, aug4, part=1)
         return out
 
-    def _forward_backward_body(self, x, y_true, drops, top, aug4, part: Optional[int] = None, teacher_probs=None):
-        """part None: forward + the whole backward pass; 0: forward + backward part 0; 1: backward part 1."""
+    def _forward_backward_body(self, x, y_true, drops, top, aug4, part: Optional[int] = None, teacher_probs=None,
+                               mix8=None):
+        """part None: forward + the whole backward pass; 0: forward + backward part 0; 1: backward part 1.
+        mix8: the step's Mixup / CutMix rows; the input stage blends the images and the head sees the targets blended
+        the same way (the buffer `last_targets` names)."""
         if part == 1:
             self.backward(1)
             return None
-        x0 = self._input(x, True, aug4)
+        x0 = self._input(x, True, aug4, mix8)
+        if mix8 is not None:
+            y_true = nn.mix_targets(y_true, mix8, out=self._mixed_targets_buf(*y_true.shape))
         if teacher_probs is None:
             probs, loss = self.forward(x0, True, y_true, drops, top)
         else:
@@ -976,6 +1071,14 @@ class LeafCNN:
         across the shards of a global batch."""
         self.gen = torch.Generator(device="cpu").manual_seed(int(seed))
         self.np_rng = np.random.RandomState(int(seed) & 0x7FFFFFFF)
+        self.mix_rng = np.random.RandomState(self._mix_seed(seed))
+
+    @staticmethod
+    def _mix_seed(seed: int) -> int:
+        """The Mixup / CutMix draws have a generator of their own, so that the dropout and augmentation streams are
+        the same with mixing on and off; its seed is the model's with a constant folded in, so that it does not repeat
+        np_rng's stream."""
+        return (int(seed) ^ 0x4D495838) & 0x7FFFFFFF
 
     def l2_penalty(self) -> torch.Tensor:
         tot = torch.zeros((), dtype=torch.float32, device=self.device)
@@ -989,9 +1092,13 @@ class LeafCNN:
     def compile(self, optimizer=None, loss=None, metrics=None) -> None:
         """optimizer: dict from train.utils.build_optimizer; loss: dict from build_loss, optionally with
         "distill": {"alpha": a, "temperature": t} (0 <= a <= 1, t > 0 and finite): the setting of the steps that
-        are given a teacher's probabilities."""
+        are given a teacher's probabilities; and with "mix": {"mixup": a, "cutmix": b, "prob": p} (alphas >= 0 and
+        finite, 0 <= p <= 1, default 1): every training step blends each image of its batch with a partner, by Mixup
+        (lambda ~ Beta(a, a)) or CutMix (a box of area 1 - lambda, lambda ~ Beta(b, b)) with probability p, and
+        trains on the targets blended the same way (draw_mix_rows).  Mixing is off unless an alpha is positive."""
         self._compiled = {"optimizer": optimizer or {}, "loss": loss or {}, "metrics": metrics or []}
         self._distill_setting()
+        self._mix_setting()
 
     def _distill_setting(self, required: bool = False) -> Optional[Tuple[float, float]]:
         """(alpha, temperature) of the compiled loss, None when it has no "distill"."""
@@ -1006,6 +1113,24 @@ class LeafCNN:
         if not (temperature > 0.0 and math.isfinite(temperature)):
             raise ValueError(f"distill temperature must be positive and finite, got {temperature}")
         return alpha, temperature
+
+    def _mix_setting(self) -> Optional[Tuple[float, float, float]]:
+        """(mixup alpha, cutmix alpha, prob) of the compiled loss; None when it has no "mix" or both alphas are 0."""
+        d = self._compiled.get("loss", {}).get("mix")
+        if d is None:
+            return None
+        mixup, cutmix = float(d.get("mixup", 0.0)), float(d.get("cutmix", 0.0))
+        prob = float(d.get("prob", 1.0))
+        for name, a in (("mixup", mixup), ("cutmix", cutmix)):
+            if not (a >= 0.0 and math.isfinite(a)):
+                raise ValueError(f"mix: the {name} alpha must be >= 0 and finite, got {a}")
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError(f"mix: prob must lie in [0, 1], got {prob}")
+        return (mixup, cutmix, prob) if (mixup > 0 or cutmix > 0) else None
+
+    def _mixed_targets_buf(self, n: int, c: int) -> torch.Tensor:
+        """The mixed targets of the last mixing step at batch n."""
+        return self._buf(n, "y_mix", (n, c))
 
     def _kd_buf(self, n: int) -> torch.Tensor:
         """The per-sample kd term of the last distillation step at batch n (fp32, whatever the step's precision)."""
@@ -1040,12 +1165,19 @@ class LeafCNN:
         Every non-empty local batch first goes through `teacher.predict_device` — its inference path: no in-model
         augmentation, its own normalisation and inference dtype — and the step takes those probabilities
         (train_step's teacher_probs) while this model sees its own augmented view of the batch.  `history` gains
-        "kd_loss", the mean kd term, and "loss" is the combined loss; validation stays plain cross-entropy."""
+        "kd_loss", the mean kd term, and "loss" is the combined loss; validation stays plain cross-entropy.
+
+        With a compiled "mix" setting (Mixup / CutMix) the training loss is the one against the mixed targets and the
+        training accuracy counts a prediction as right when it is the argmax of the mixed target, the class with the
+        larger share of the image; validation is untouched.  A teacher together with mixing is refused."""
         import logging
         import random as _random
         log = logging.getLogger(__name__)
         opt = self._compiled.get("optimizer", {})
         if teacher is not None:
+            if self._mix_setting() is not None:
+                raise ValueError("fit: Mixup / CutMix with a teacher is not supported (the teacher would have to see "
+                                 "the mixed image, which exists only inside this model's input stage)")
             self._distill_setting(required=True)
             if teacher.num_classes != self.num_classes:
                 raise ValueError(f"fit: the teacher has {teacher.num_classes} classes, this model "
@@ -1092,6 +1224,8 @@ class LeafCNN:
                 if n_local:
                     if extra:
                         acc_kd += self.last_kd.sum()
+                    if self.last_targets is not None:
+                        idx = self.last_targets.argmax(-1)
                     acc_loss += loss.sum()
                     acc_correct += (probs.argmax(-1) == idx).sum()
                     seen += n_local

@@ -595,6 +595,52 @@ def input_stage(x_u8: torch.Tensor, aug4: torch.Tensor, mean=None, denom=None,
     return out
 
 
+def _mix_checks(who: str, lead: torch.Tensor, shaped) -> None:
+    """`shaped`: name -> (tensor, expected shape); every one a contiguous float32 tensor on lead's device."""
+    for name, (t, shape) in shaped.items():
+        if t.dtype != _F32 or not t.is_contiguous() or t.device != lead.device:
+            raise ValueError(f"{who}.{name}: a contiguous float32 tensor on {lead.device} expected")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}.{name}: expected {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def input_stage_mix(x_u8: torch.Tensor, aug4: torch.Tensor, mix8: torch.Tensor, mean=None, denom=None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """input_stage with Mixup / CutMix fused (lf_input_stage_mix_f32): every image is blended with the model view of
+    its partner, mix8 [N,8] = {partner, w_out, w_in, y0, y1, x0, x1, t} per image (the rule: include/leafhip.h)."""
+    if x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3 or not x_u8.is_contiguous() \
+            or not x_u8.is_cuda:
+        raise ValueError("input_stage_mix.x: a contiguous uint8 [N,H,W,3] tensor on the GPU expected")
+    n, h, w, _c = x_u8.shape
+    if (mean is None) != (denom is None):
+        raise ValueError("input_stage_mix: mean and denom go together")
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=_F32, device=x_u8.device)
+    _mix_checks("input_stage_mix", x_u8, {"aug": (aug4, (n, 4)), "mix": (mix8, (n, 8)), "out": (out, (n, 3, h, w))})
+    ws = torch.empty((n, 24), dtype=_F32, device=x_u8.device)
+    m = d = None
+    if mean is not None:
+        m = (_lib.c_float * 3)(*[float(v) for v in mean])
+        d = (_lib.c_float * 3)(*[float(v) for v in denom])
+    _lib.call("lf_input_stage_mix_f32", x_u8.data_ptr(), out.data_ptr(), n, h, w, aug4.data_ptr(), mix8.data_ptr(),
+              m, d, ws.data_ptr(), _stream())
+    return out
+
+
+def mix_targets(y: torch.Tensor, mix8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mixed targets out[i] = y[p] + t (y[i] - y[p]) with p, t from mix8 [N,8] (lf_mix_targets_f32), out of place."""
+    if y.dim() != 2 or not y.is_cuda:
+        raise ValueError(f"mix_targets.y: [N,C] on the GPU expected, got {tuple(y.shape)} on {y.device}")
+    n, c = y.shape
+    if out is None:
+        out = torch.empty_like(y)
+    _mix_checks("mix_targets", y, {"y": (y, (n, c)), "mix": (mix8, (n, 8)), "out": (out, (n, c))})
+    if abs(out.data_ptr() - y.data_ptr()) < 4 * n * c:
+        raise ValueError("mix_targets: out must not overlap y (a row is also read as its partner's partner)")
+    _lib.call("lf_mix_targets_f32", y.data_ptr(), mix8.data_ptr(), out.data_ptr(), n, c, _stream())
+    return out
+
+
 def scale_shift_act(x, scale, shift, relu: bool, out=None):
     _chk(x, _F32, "scale_shift_act.x", 4)
     n, c, h, w = x.shape

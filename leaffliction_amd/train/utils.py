@@ -48,13 +48,17 @@ def build_optimizer(cfg: Dict, base_lr) -> Dict[str, Any]:
 
 def build_loss(cfg: Dict) -> Dict[str, Any]:
     """CategoricalCrossentropy(label_smoothing) or sparse CCE (utils.py:30-35); a cfg that carries
-    "distill": {"alpha", "temperature"} (train --teacher) hands it on to LeafCNN.compile."""
+    "distill": {"alpha", "temperature"} (train --teacher) hands it on to LeafCNN.compile, and so does one that
+    carries "mix": {"mixup", "cutmix", "prob"} (train --mixup / --cutmix)."""
     ls = float(cfg.get("label_smoothing", 0.0) or 0.0)
     loss: Dict[str, Any] = {"name": "categorical_crossentropy" if ls > 0 else "sparse_categorical_crossentropy",
                             "label_smoothing": ls}
     if cfg.get("distill") is not None:
         loss["distill"] = {"alpha": float(cfg["distill"]["alpha"]),
                            "temperature": float(cfg["distill"]["temperature"])}
+    if cfg.get("mix") is not None:
+        loss["mix"] = {"mixup": float(cfg["mix"]["mixup"]), "cutmix": float(cfg["mix"]["cutmix"]),
+                       "prob": float(cfg["mix"]["prob"])}
     return loss
 
 
