@@ -148,22 +148,35 @@ __device__ __forceinline__ void wino_output(const float (&m)[16], float (&y)[4])
 // ---------------------------------------------------------------------------
 // forward / dgrad: the pieces both kernels share, the direct kernel, the Winograd kernel
 // ---------------------------------------------------------------------------
-constexpr int kMaxProC = 512;  // prologue scale/shift staged in LDS for up to this many channels
+constexpr int kMaxProC = 512;  // prologue scale/shift staged in LDS for this many channels at a time
 
-// The per-channel constants a workgroup reads, staged in LDS once: the producer's BatchNorm scale/shift of the
-// first kMaxProC input channels (lsc[2][kMaxProC]) and the epilogue's statistics constants of the workgroup's CT
-// couts from co0 on (lep[3][CT]: pivot, 0 where there is none; mask scale; mask shift).  A kernel calls this
-// right after it has issued chunk 0's patch loads, so the wait for these few L2-resident floats lies under the
-// patch's own.  The barriers of the K-loop stand between the writes and every reader.
+// The producer's BatchNorm scale/shift of the kMaxProC input channels from cbase on (a multiple of kMaxProC) ->
+// lsc[2][kMaxProC].  The channels that fill up a ragged last K-chunk (of at most 8) get 0, 0: they stage as zeros.
+__device__ __forceinline__ void stage_pro_consts(const ConvArgs& p, float* lsc, int cbase, int tid) {
+    const int nc = min(((p.cin + 7) & ~7) - cbase, kMaxProC);
+    for (int c = tid; c < nc; c += kThreads) {
+        const bool in = cbase + c < p.cin;
+        lsc[c] = in ? p.in_scale[cbase + c] : 0.f;
+        lsc[kMaxProC + c] = in ? p.in_shift[cbase + c] : 0.f;
+    }
+}
+// A launch with more input channels than that moves the window when the K-loop reaches its end: called (by every
+// thread) at the top of chunk c0, in front of the chunk's first barrier.  The last readers of the old window, the
+// store phase of the chunk before, finished before that chunk's second barrier; the first barrier of this one
+// stands between these writes and the chunk's own store phase.
+__device__ __forceinline__ void advance_pro_consts(const ConvArgs& p, float* lsc, int c0, int tid) {
+    if (p.in_scale != nullptr && c0 > 0 && (c0 & (kMaxProC - 1)) == 0) stage_pro_consts(p, lsc, c0, tid);
+}
+
+// The per-channel constants a workgroup reads, staged in LDS: the prologue's first window and the epilogue's
+// statistics constants of the workgroup's CT couts from co0 on (lep[3][CT]: pivot, 0 where there is none; mask
+// scale; mask shift).  A kernel calls this right after it has issued chunk 0's patch loads, so the wait for these
+// few L2-resident floats lies under the patch's own.  The barriers of the K-loop stand between the writes and
+// every reader.
 template <int CT>
 __device__ __forceinline__ void stage_channel_consts(const ConvArgs& p, float* lsc, float* lep, int co0, int tid) {
     static_assert(CT <= kThreads, "at most one cout per thread");
-    if (p.in_scale != nullptr) {
-        for (int c = tid; c < p.cin && c < kMaxProC; c += kThreads) {
-            lsc[c] = p.in_scale[c];
-            lsc[kMaxProC + c] = p.in_shift[c];
-        }
-    }
+    if (p.in_scale != nullptr) stage_pro_consts(p, lsc, 0, tid);
     if (p.stat_part != nullptr && tid < CT) {
         const int co = co0 + tid, coc = min(co, p.cout - 1);
         const bool masked = p.stat_mask_y != nullptr;
@@ -264,33 +277,58 @@ struct PatchStage {
     }
 
     // chunk c0's loads into registers (with a strip of two images the second image's chunk lies Cin
-    // planes further on; the host only stacks when Cin is a whole number of chunks)
+    // planes further on; the host only stacks when Cin is a whole number of chunks).  A chunk past the last one
+    // would have an empty buffer: its loads fetch nothing and return zeros.
     __device__ __forceinline__ void load(const ConvArgs& p, const float* xin, int c0) {
+        const int nc = min(kKC, p.cin - c0);
         const __amdgpu_buffer_rsrc_t rx = buf_rsrc(
             xin + (size_t)c0 * hw,
-            4u * (unsigned)((STK ? (p.stack - 1) * p.cin : 0) + min(kKC, p.cin - c0)) * (unsigned)hw);
+            nc > 0 ? 4u * (unsigned)((STK ? (p.stack - 1) * p.cin : 0) + nc) * (unsigned)hw : 0u);
 #pragma unroll
         for (int i = 0; i < IPT; ++i) pv[i] = buf_load4(rx, pg[i]);
 #pragma unroll
         for (int i = 0; i < HPT; ++i) ph[i] = buf_load1(rx, hg[i]);
     }
 
-    // the registers loaded for chunk c0 -> LDS
+    // The registers loaded for chunk c0 -> LDS.  PRO: the launch has a prologue (the K-loop exists once for either
+    // case, so the store phase has no branch on it); lsc then holds the window that contains the chunk
+    // (advance_pro_consts).
+    template <bool PRO, bool AHEAD = true>
     __device__ __forceinline__ void store(const ConvArgs& p, float* lp, const float* lsc, int c0, int tid) const {
-        const bool pro = p.in_scale != nullptr;
-        auto pro_sc = [&](int c) { return c < kMaxProC ? lsc[c] : p.in_scale[c]; };
-        auto pro_sh = [&](int c) { return c < kMaxProC ? lsc[kMaxProC + c] : p.in_shift[c]; };
+        // Every item's scale and shift are read from the LDS window first: they do not depend on the patch loads,
+        // so their latency lies under the counted waits for those.  An item outside the image takes 0, 0 and stays
+        // zero without a branch of its own; slots beyond the item count read a clamped channel and store nothing.
+        // (!AHEAD: each item's constants are read where the item is stored, for a kernel that has no registers
+        // to hold them all.)
+        float isc[IPT], ish[IPT], hsc[HPT > 0 ? HPT : 1], hsh[HPT > 0 ? HPT : 1];
+        const int cw = c0 & (kMaxProC - 1);
+        auto consts = [&](unsigned l, bool ok, float& sc, float& sh) {
+            const int c = min(cw + (int)(l >> 16), kMaxProC - 1);
+            const float s = lsc[c], t = lsc[kMaxProC + c];
+            sc = ok ? s : 0.f;
+            sh = ok ? t : 0.f;
+        };
+        if (PRO && AHEAD) {
+#pragma unroll
+            for (int i = 0; i < IPT; ++i) consts(pl[i], okmask >> i & 1u, isc[i], ish[i]);
+#pragma unroll
+            for (int i = 0; i < HPT; ++i) consts(hl[i], okmask >> (16 + i) & 1u, hsc[i], hsh[i]);
+            // an opaque use, so that no read is moved down into the branch of a partial item, behind a wait
+#pragma unroll
+            for (int i = 0; i < IPT; ++i) asm volatile("" : "+v"(isc[i]), "+v"(ish[i]));
+#pragma unroll
+            for (int i = 0; i < HPT; ++i) asm volatile("" : "+v"(hsc[i]), "+v"(hsh[i]));
+        }
 #pragma unroll
         for (int i = 0; i < IPT; ++i) {
-            if (tid + i * kThreads < NVI) {
-                const int kc = (int)(pl[i] >> 16);
+            if ((i + 1) * kThreads <= NVI || tid + i * kThreads < NVI) {  // only the last item can be partial
                 float4 v = pv[i];
-                if (pro && (okmask >> i & 1u)) {
-                    const float sc = pro_sc(c0 + kc), sh = pro_sh(c0 + kc);
-                    v.x = pro_apply(v.x, sc, sh, p.in_relu);
-                    v.y = pro_apply(v.y, sc, sh, p.in_relu);
-                    v.z = pro_apply(v.z, sc, sh, p.in_relu);
-                    v.w = pro_apply(v.w, sc, sh, p.in_relu);
+                if (PRO) {
+                    if (!AHEAD) consts(pl[i], okmask >> i & 1u, isc[i], ish[i]);
+                    v.x = pro_apply(v.x, isc[i], ish[i], p.in_relu);
+                    v.y = pro_apply(v.y, isc[i], ish[i], p.in_relu);
+                    v.z = pro_apply(v.z, isc[i], ish[i], p.in_relu);
+                    v.w = pro_apply(v.w, isc[i], ish[i], p.in_relu);
                 }
                 float* dst = lp + (pl[i] & 0xffffu);
                 dst[0] = v.x;
@@ -301,11 +339,10 @@ struct PatchStage {
         }
 #pragma unroll
         for (int i = 0; i < HPT; ++i) {
-            if (tid + i * kThreads < NHI) {
-                const int kc = (int)(hl[i] >> 16);
+            if ((i + 1) * kThreads <= NHI || tid + i * kThreads < NHI) {
                 float v = ph[i];
-                if (pro && (okmask >> (16 + i) & 1u))
-                    v = pro_apply(v, pro_sc(c0 + kc), pro_sh(c0 + kc), p.in_relu);
+                if (PRO && !AHEAD) consts(hl[i], okmask >> (16 + i) & 1u, hsc[i], hsh[i]);
+                if (PRO) v = pro_apply(v, hsc[i], hsh[i], p.in_relu);
                 lp[hl[i] & 0xffffu] = v;
             }
         }
@@ -459,7 +496,12 @@ void conv_mfma_kernel(ConvArgs p) {
         };
         auto store_chunk = [&](int c0) {
             if (!kPrefetchW) load_weights(c0);
-            patch.store(p, lp, lsc, c0, tid);
+            // the constants of more than three items at once would cost <1,56,8,2,1,2,7> its third wave per SIMD
+            constexpr bool kAhead = Patch::IPT + Patch::HPT <= 3;
+            if (p.in_scale != nullptr)  // workgroup-uniform, around the whole patch store
+                patch.template store<true, kAhead>(p, lp, lsc, c0, tid);
+            else
+                patch.template store<false>(p, lp, lsc, c0, tid);
 #pragma unroll
             for (int i = 0; i < WPT; ++i) {
                 const int e = tid + i * kThreads;
@@ -470,6 +512,7 @@ void conv_mfma_kernel(ConvArgs p) {
         if (kPrefetchW) load_weights(0);
         stage_channel_consts<CT>(p, lsc, lep, co0, tid);
         for (int ch = 0; ch < nchunks; ++ch) {
+            advance_pro_consts(p, lsc, ch * kKC, tid);
             __syncthreads();  // previous chunk's LDS reads are done
             store_chunk(ch * kKC);
             __syncthreads();
@@ -650,7 +693,9 @@ void conv_wino_kernel(ConvArgs p) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) wacc[m][nb][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    auto compute_chunk = [&]() {
+    // late(0), late(1) (unless late is nullptr): called before the last quarter and the last eighth of the chunk's
+    // MFMAs; the scheduler moves nothing across them
+    auto compute_chunk = [&](auto late) {
 #pragma unroll
         for (int s = 0; s < kKC / 4; ++s) {
             // the cout-blocks' U first, then one tile-block's V at a time
@@ -684,8 +729,17 @@ void conv_wino_kernel(ConvArgs p) {
 #pragma unroll
                 for (int m = 0; m < MB; ++m)
 #pragma unroll
-                    for (int q = 0; q < 16; ++q)
+                    for (int q = 0; q < 16; ++q) {
+                        if constexpr (!std::is_same_v<decltype(late), std::nullptr_t>) {
+                            const int at = (nb * MB + m) * 16 + q;
+                            if (s == kKC / 4 - 1 && (at == NB * MB * 8 || at == NB * MB * 12)) {
+                                __builtin_amdgcn_sched_barrier(0);
+                                late(at == NB * MB * 8 ? 0 : 1);
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
                         wacc[m][nb][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[m][q], v[q], wacc[m][nb][q], 0, 0, 0);
+                    }
             }
         }
     };
@@ -702,11 +756,22 @@ void conv_wino_kernel(ConvArgs p) {
     const unsigned ugo = co0 + uco < p.cout ? 4u * (((unsigned)ukc * (unsigned)p.cout + (unsigned)(co0 + uco)) * 16u + 4u * (unsigned)uq4) : 0x80000000u;
     float* const ulds = lw + (ukc * CT + uco) * kUP + 4 * uq4;
     float4 uv[UPT];
-    auto load_u = [&](int c0) {
+    static_assert(UPT % 2 == 0, "U is asked for in two halves");
+    auto load_u_half = [&](int c0, int half) {
+        // (the size as in PatchStage::load; written as a select, which stays in scalar registers where
+        // max(min(), 0) becomes a vector instruction and the loads a loop over lanes)
+        const int nc = min(kKC, p.cin - c0);
         const __amdgpu_buffer_rsrc_t ru =
-            buf_rsrc(p.wino_u + (size_t)c0 * p.cout * 16, 64u * (unsigned)min(kKC, p.cin - c0) * (unsigned)p.cout);
+            buf_rsrc(p.wino_u + (size_t)c0 * p.cout * 16, nc > 0 ? 64u * (unsigned)nc * (unsigned)p.cout : 0u);
 #pragma unroll
-        for (int i = 0; i < UPT; ++i) uv[i] = buf_load4(ru, ugo + (unsigned)i * ustep);
+        for (int i = 0; i < UPT / 2; ++i) {
+            const int e = half * (UPT / 2) + i;
+            uv[e] = buf_load4(ru, ugo + (unsigned)e * ustep);
+        }
+    };
+    auto load_u = [&](int c0) {
+        load_u_half(c0, 0);
+        load_u_half(c0, 1);
     };
     auto store_u = [&]() {
 #pragma unroll
@@ -718,24 +783,47 @@ void conv_wino_kernel(ConvArgs p) {
 
     if (vec) {
         // ---------------- vector staging with register prefetch ----------------
-        // The patch is prefetched into registers during the previous chunk's MFMAs.  U is not: its slice is
-        // L2-resident (every workgroup reads the same few KB), so it is fetched in the store phase, in flight
-        // while the patch goes to LDS.  Prefetching it too (4 * UPT registers held across the MFMAs) measured
-        // 0.8 ms per step slower.  Chunk 0's U and the per-channel constants are asked for right behind chunk
-        // 0's patch, so the workgroup's first wait covers all three.
+        // The patch is prefetched into registers during the previous chunk's MFMAs.  The next chunk's U is asked
+        // for inside the last quarter of those MFMAs, one half at its start and one in its middle, where the
+        // operand registers of the MFMAs already issued are free (held across all of a chunk's MFMAs its 4 * UPT
+        // registers measured 0.8 ms per step slower); so the store phase waits for no load issued after the
+        // chunk's first barrier.  With two tile-blocks per wave (21 patch registers) there is no room for that
+        // without scratch: that instantiation fetches U in the store phase, in flight while the patch goes to LDS.
+        // Chunk 0's U and the per-channel constants are asked for right behind chunk 0's patch, so the
+        // workgroup's first wait covers all three.
+        constexpr bool kUAhead = NB == 1;
         Patch patch(p, t, tid);
         patch.load(p, xin, 0);
-        load_u(0);
+        if (kUAhead) load_u(0);
         stage_channel_consts<CT>(p, lsc, lep, co0, tid);
-        for (int ch = 0; ch < nchunks; ++ch) {
-            __syncthreads();  // previous chunk's LDS reads are done
-            if (ch > 0) load_u(ch * kKC);
-            patch.store(p, lp, lsc, ch * kKC, tid);
-            store_u();
-            __syncthreads();
-            if (ch + 1 < nchunks) patch.load(p, xin, (ch + 1) * kKC);  // in flight during the MFMAs
-            compute_chunk();
-        }
+        // The loop exists once with and once without a prologue (workgroup-uniform), and the last chunk, which
+        // asks for nothing more, stands behind it: no body has a branch around a load, so every wait of a store
+        // phase counts exactly the loads issued after the one it needs.
+        auto k_loop = [&](auto pro_c) {
+            constexpr bool PRO = decltype(pro_c)::value;
+            auto chunk = [&](int ch, auto last_c) {
+                constexpr bool LAST = decltype(last_c)::value;
+                // kept in a scalar register, so that the buffer descriptors built from it are
+                const int c0 = __builtin_amdgcn_readfirstlane(ch * kKC);
+                if (PRO) advance_pro_consts(p, lsc, c0, tid);
+                __syncthreads();  // previous chunk's LDS reads are done
+                if (!kUAhead) load_u(c0);
+                patch.template store<PRO>(p, lp, lsc, c0, tid);
+                store_u();
+                __syncthreads();
+                if (!LAST) patch.load(p, xin, c0 + kKC);  // in flight during the MFMAs
+                if constexpr (kUAhead && !LAST)
+                    compute_chunk([&](int half) { load_u_half(c0 + kKC, half); });
+                else
+                    compute_chunk(nullptr);
+            };
+            for (int ch = 0; ch + 1 < nchunks; ++ch) chunk(ch, std::false_type{});
+            chunk(nchunks - 1, std::true_type{});
+        };
+        if (p.in_scale != nullptr)
+            k_loop(std::true_type{});
+        else
+            k_loop(std::false_type{});
     } else {
         // ---------------- scalar staging (ragged shapes / partial tiles) ----------------
         stage_channel_consts<CT>(p, lsc, lep, co0, tid);
@@ -746,7 +834,7 @@ void conv_wino_kernel(ConvArgs p) {
             load_u(c0);
             store_u();
             __syncthreads();
-            compute_chunk();
+            compute_chunk(nullptr);
         }
     }
 

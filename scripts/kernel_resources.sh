@@ -3,7 +3,7 @@
 #   scripts/kernel_resources.sh leaffliction_amd/csrc/lf_wgrad_bf16.hip [filter]
 F=$1; FILT=${2:-.}
 EXTRA=""
-case "$F" in *lf_augment*|*lf_geom*|*lf_resize_cv*|*lf_filters*) EXTRA="-ffp-contract=off";; esac
+case "$F" in *lf_augment*|*lf_geom*|*lf_resize_cv*|*lf_filters*) EXTRA="-ffp-contract=off";; *lf_conv.hip) EXTRA="-fno-slp-vectorize";; esac
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude $EXTRA -c "$F" -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 \
  | grep -E "Function Name|VGPRs:|AGPRs:|Spill|Occupancy|LDS Size" \
  | sed -E 's/^.*remark: +//; s/ \[-Rpass.*//; s/^ +//' \
