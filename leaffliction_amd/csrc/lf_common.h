@@ -142,7 +142,7 @@ inline bool conv_bf16s_rmw(int accumulate, bool mask) { return accumulate || mas
 
 // Weight-gradient slabs part[splits][count] -> dst = beta*dst + their sum, in a fixed order (deterministic, no float
 // atomics): more than kSlabGroup slabs are first summed in groups of kSlabGroup into the `slab_groups` slabs that
-// follow them in the workspace.  slab_reduce_kernel lives in lf_conv.hip.
+// follow them in the workspace.  slab_reduce_kernel lives in lf_wgrad.hip.
 constexpr int kSlabGroup = 32;
 inline int slab_groups(int splits) { return (splits + kSlabGroup - 1) / kSlabGroup; }
 inline int slab_stages(int splits) { return splits > kSlabGroup ? 2 : 1; }

@@ -447,25 +447,21 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int c,
     dgamma[ch] = (float)q;
 }
 
-// dbeta = sum d, dgamma = invstd * (sum d*y - mean * sum d) from the kBnSplit partial pairs
-// {sum d, sum d*y} (convolution-epilogue tile sums, lf_conv2d_bnbwd_f32)
-__global__ void bn_bwd_tiles_finalize_kernel(const float* __restrict__ part, int c,
-                                             const float* __restrict__ mean,
-                                             const float* __restrict__ invstd,
-                                             float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= c) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < kBnSplit; ++k) {
-        s += part[((size_t)ch * kBnSplit + k) * 2];
-        q += part[((size_t)ch * kBnSplit + k) * 2 + 1];
-    }
-    dbeta[ch] = (float)s;
-    dgamma[ch] = (float)((q - (double)mean[ch] * s) * (double)invstd[ch]);
+// dy = coef2*dz + coef3*y + coef4 with dz masked by y*coef0+coef1 > 0: the apply step as five
+// per-channel coefficients, for consumers that form dy while they read g and y.  One channel's five, from the
+// dgamma / dbeta just formed (the floats stored, so a producer that calls this gives bn_bwd_coef_kernel's bits).
+__device__ __forceinline__ void bn_bwd_coef1(int ch, int c, float mean, float invstd, float scale, float shift,
+                                             float gamma, float dgamma, float dbeta, float inv_count,
+                                             float* __restrict__ coef) {
+    const float k = gamma * invstd;
+    const float mdz = dbeta * inv_count, mdzx = dgamma * inv_count;
+    coef[ch] = scale;
+    coef[c + ch] = shift;
+    coef[2 * c + ch] = k;
+    coef[3 * c + ch] = -k * invstd * mdzx;
+    coef[4 * c + ch] = k * (mean * invstd * mdzx - mdz);
 }
 
-// dy = coef2*dz + coef3*y + coef4 with dz masked by y*coef0+coef1 > 0: the apply step as five
-// per-channel coefficients, for consumers that form dy while they read g and y
 __global__ void bn_bwd_coef_kernel(const float* __restrict__ mean, const float* __restrict__ invstd,
                                    const float* __restrict__ scale, const float* __restrict__ shift,
                                    const float* __restrict__ gamma, const float* __restrict__ dgamma,
@@ -473,13 +469,31 @@ __global__ void bn_bwd_coef_kernel(const float* __restrict__ mean, const float* 
                                    float* __restrict__ coef) {
     const int ch = blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= c) return;
-    const float k = gamma[ch] * invstd[ch];
-    const float mdz = dbeta[ch] * inv_count, mdzx = dgamma[ch] * inv_count;
-    coef[ch] = scale[ch];
-    coef[c + ch] = shift[ch];
-    coef[2 * c + ch] = k;
-    coef[3 * c + ch] = -k * invstd[ch] * mdzx;
-    coef[4 * c + ch] = k * (mean[ch] * invstd[ch] * mdzx - mdz);
+    bn_bwd_coef1(ch, c, mean[ch], invstd[ch], scale[ch], shift[ch], gamma[ch], dgamma[ch], dbeta[ch], inv_count, coef);
+}
+
+// dbeta = sum d, dgamma = invstd * (sum d*y - mean * sum d) from the kBnSplit partial pairs
+// {sum d, sum d*y} (convolution-epilogue tile sums, lf_conv2d_bnbwd_f32), and the channel's five coefficients
+__global__ void bn_bwd_tiles_finalize_kernel(const float* __restrict__ part, int c,
+                                             const float* __restrict__ mean,
+                                             const float* __restrict__ invstd,
+                                             const float* __restrict__ scale,
+                                             const float* __restrict__ shift,
+                                             const float* __restrict__ gamma, float inv_count,
+                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                             float* __restrict__ coef) {
+    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= c) return;
+    double s = 0.0, q = 0.0;
+    for (int k = 0; k < kBnSplit; ++k) {
+        s += part[((size_t)ch * kBnSplit + k) * 2];
+        q += part[((size_t)ch * kBnSplit + k) * 2 + 1];
+    }
+    const float db = (float)s;
+    const float dg = (float)((q - (double)mean[ch] * s) * (double)invstd[ch]);
+    dbeta[ch] = db;
+    dgamma[ch] = dg;
+    bn_bwd_coef1(ch, c, mean[ch], invstd[ch], scale[ch], shift[ch], gamma[ch], dg, db, inv_count, coef);
 }
 
 __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(BnBwdArgs a,
@@ -856,7 +870,8 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ 
 // dz = (g*alpha + add) * [y*scale+shift > 0],
 //   sum dz       = sum_n alpha*G0 + add*M0          G = tail_bwd plane sums {sum g*mask, sum g*mask*y}
 //   sum dz*xhat  = invstd * sum_n alpha*(G1 - mean*G0) + add*(M1 - mean*M0)   M = gap mask sums
-// one workgroup per channel, fixed-order double accumulation.
+// one workgroup per channel, fixed-order double accumulation.  With `coef` the channel's five coefficients follow
+// (bn_bwd_coef1); scale, shift and gamma are read only then.
 __global__ __launch_bounds__(kBlock) void bn_bwd_planes_kernel(const float* __restrict__ plane_g,
                                                                const float* __restrict__ plane_m,
                                                                const float* __restrict__ alpha,
@@ -864,7 +879,11 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_planes_kernel(const float* __re
                                                                const float* __restrict__ mean,
                                                                const float* __restrict__ invstd, int n,
                                                                int c, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta) {
+                                                               float* __restrict__ dbeta,
+                                                               const float* __restrict__ scale,
+                                                               const float* __restrict__ shift,
+                                                               const float* __restrict__ gamma, float inv_count,
+                                                               float* __restrict__ coef) {
     __shared__ double red[2][kBlock / 64];
     const int ch = blockIdx.x;
     const double mu = mean[ch];
@@ -893,8 +912,12 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_planes_kernel(const float* __re
             a += red[0][k];
             b += red[1][k];
         }
-        dbeta[ch] = (float)a;
-        dgamma[ch] = (float)(b * (double)invstd[ch]);
+        const float db = (float)a;
+        const float dg = (float)(b * (double)invstd[ch]);
+        dbeta[ch] = db;
+        dgamma[ch] = dg;
+        if (coef != nullptr)
+            bn_bwd_coef1(ch, c, mean[ch], invstd[ch], scale[ch], shift[ch], gamma[ch], dg, db, inv_count, coef);
     }
 }
 
@@ -1310,7 +1333,7 @@ int lf_bn_bwd_f32(const float* g, const float* alpha_nc, const float* add_nc, co
         // dgamma / dbeta already hold the two channel sums (lf_bn_bwd_sums*_f32)
     } else if (plane_g != nullptr) {
         bn_bwd_planes_kernel<<<c, kBlock, 0, s>>>(plane_g, plane_m, alpha_nc, add_nc, mean, invstd, n, c,
-                                                  dgamma, dbeta);
+                                                  dgamma, dbeta, nullptr, nullptr, nullptr, 0.f, nullptr);
     } else {
         bn_bwd_reduce_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(a, part);
         bn_bwd_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, dgamma, dbeta);
@@ -1340,17 +1363,18 @@ int lf_bn_bwd_sums_f32(const float* g, const float* alpha_nc, const float* add_n
         return LF_ERR_WORKSPACE;
     }
     hipStream_t s = lf::as_stream(stream);
-    if (plane_g != nullptr) {
+    const float inv_count = 1.0f / ((float)n * (float)hw);
+    if (plane_g != nullptr) {  // the plane route forms the coefficients where it forms the sums
         bn_bwd_planes_kernel<<<c, kBlock, 0, s>>>(plane_g, plane_m, alpha_nc, add_nc, mean, invstd, n, c,
-                                                  dgamma, dbeta);
+                                                  dgamma, dbeta, scale, shift, gamma, inv_count, coef);
     } else {
         BnBwdArgs a{g, alpha_nc, add_nc, y, mean, invstd, scale, shift, relu, n, c, hw};
         float* part = static_cast<float*>(workspace);
         bn_bwd_reduce_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(a, part);
         bn_bwd_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, dgamma, dbeta);
+        bn_bwd_coef_kernel<<<(c + 63) / 64, 64, 0, s>>>(mean, invstd, scale, shift, gamma, dgamma, dbeta, inv_count,
+                                                       c, coef);
     }
-    bn_bwd_coef_kernel<<<(c + 63) / 64, 64, 0, s>>>(mean, invstd, scale, shift, gamma, dgamma, dbeta,
-                                                   1.0f / ((float)n * (float)hw), c, coef);
     return lf::check_launch("lf_bn_bwd_sums");
 }
 
@@ -1370,9 +1394,8 @@ int lf_bn_bwd_sums_tiles_f32(const float* tile_part, long long tiles, const floa
     hipStream_t s = lf::as_stream(stream);
     float* part = static_cast<float*>(workspace);
     bn_tile_reduce_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(tile_part, tiles, part);
-    bn_bwd_tiles_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, mean, invstd, dgamma, dbeta);
-    bn_bwd_coef_kernel<<<(c + 63) / 64, 64, 0, s>>>(mean, invstd, scale, shift, gamma, dgamma, dbeta,
-                                                   1.0f / ((float)n * (float)hw), c, coef);
+    bn_bwd_tiles_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, mean, invstd, scale, shift, gamma,
+                                                             1.0f / ((float)n * (float)hw), dgamma, dbeta, coef);
     return lf::check_launch("lf_bn_bwd_sums_tiles");
 }
 
