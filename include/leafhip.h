@@ -1137,6 +1137,34 @@ int lf_input_stage_mix_f32(const uint8_t* in, float* out, int n, int h, int w, c
                            lf_stream_t stream);
 int lf_mix_targets_f32(const float* y, const float* mix8, float* out, int n, int c, lf_stream_t stream);
 
+/* Test-time augmentation: v views of every image of a batch in one launch, and the v probability rows of every
+ * image folded back into one.
+ * lf_tta_views_f32: in u8 HWC [n,h,w,3] -> out f32 NCHW [n*v,3,h,w], image-major: row i*v + k is view k of image i.
+ * view6 is a HOST pointer to v rows {flip, cos, sin, zoom, dy, dx}, 1 <= v <= 16 (copied into the kernel's
+ * arguments: no upload, no scratch); mean3 / denom3 as for lf_pack_hwc_u8_to_nchw_f32.  Output pixel (oy, ox) of a
+ * view, with cx = (w-1)/2, cy = (h-1)/2, u = ox - cx, t = oy - cy, in fp32 in this order and without contraction:
+ *   fx = zoom*(cos*u - sin*t) + cx + dx        fy = zoom*(sin*u + cos*t) + cy + dy
+ *   x0 = floor(fx), ax = fx - x0; y0 = floor(fy), ay = fy - y0; the taps x0, x0 + 1, y0, y0 + 1 are reflected
+ *   (d c b a | a b c d | d c b a, any number of periods, negative indices too), and flip != 0 then mirrors the two x
+ *   taps (x -> w-1-x): the flip precedes the rotation, as in lf_input_stage_f32.  zoom < 1 magnifies the centre.
+ *   b = top + (bot - top)*ay, top = v00 + (v01 - v00)*ax, bot = v10 + (v11 - v10)*ax on the bytes as floats;
+ *   out = b/255, then (. - mean)/denom with mean3 set: each division and the subtraction rounded on its own, the
+ *   arithmetic of lf_pack_hwc_u8_to_nchw_f32.  There is no contrast term.
+ * A row with cos = 1, sin = 0, zoom = 1 and integer dy, dx therefore equals lf_pack_hwc_u8_to_nchw_f32 of the moved
+ * (and mirrored) image bit for bit; row {0,1,0,1,0,0} is the plain model input.
+ * Refused before any launch: null buffers, n <= 0, h < 2, w < 2, v outside 1..16, n*v > 65535, a value of view6 that
+ * is not finite, zoom == 0, mean3 / denom3 not both set or both null.
+ * lf_tta_combine_f32: probs [n*v, c] image-major; weight a HOST pointer to v floats, each >= 0 and finite with a
+ * positive sum S (added in ascending order in fp32), or null for all ones.
+ *   out[i][j] = (sum_k weight[k] * probs[i*v + k][j]) / S, the sum in ascending k in fp32;
+ *   top[i]    = argmax_j out[i][j], the lowest index on ties (np.argmax);
+ *   agree[i]  = the number of views k with weight[k] > 0 whose own argmax (same tie rule) equals top[i].
+ * One wave per image; c <= 4096, 1 <= v <= 16, n > 0. */
+int lf_tta_views_f32(const uint8_t* in, float* out, int n, int h, int w, const float* view6, int v,
+                     const float* mean3, const float* denom3, lf_stream_t stream);
+int lf_tta_combine_f32(const float* probs, const float* weight, int v, float* out, int32_t* top, int32_t* agree,
+                       int n, int c, lf_stream_t stream);
+
 /* ---- input stage ----------------------------------------------------------- */
 /* u8 HWC -> f32 NCHW with the model's train-time augmentation fused (cnn.py:74-86):
  * keras RandomFlip("horizontal") -> RandomRotation (bilinear, fill_mode="reflect") ->

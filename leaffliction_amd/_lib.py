@@ -154,6 +154,8 @@ SIGNATURES = {
     "lf_input_stage_f32": [P, P, c_int, c_int, c_int, P, P, P, P, P],
     "lf_input_stage_mix_f32": [P, P, c_int, c_int, c_int, P, P, P, P, P, P],
     "lf_mix_targets_f32": [P, P, P, c_int, c_int, P],
+    "lf_tta_views_f32": [P, P, c_int, c_int, c_int, P, c_int, P, P, P],
+    "lf_tta_combine_f32": [P, P, c_int, P, P, P, c_int, c_int, P],
     "lf_scale_shift_act_f32": [P, P, c_int, c_int, c_int, P, P, c_int, P],
     "lf_bn_workspace": [c_int],
     "lf_bn_train_stats_f32": [P, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P, P, P, P,

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--montage] [--evaluate ...]`.
+"""`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--montage] [--tta PRESET]
+[--evaluate ...]`.
 
 Flags, JSON schema (`batch_results` + `summary`), the sampled accuracy gate and the exit
 codes (1 on error, 2 when the gate is never reached) follow srcs/cli/predict.py:17-87,
@@ -10,6 +11,9 @@ with the prediction under them, composed on the GPU (predict/montage.py; the let
 be combined with --evaluate or --cam.
 `--cam` (not in the reference) also writes, per image, the model input with the predicted class's activation map
 laid over it: `<out>/<stem>__CAM.jpg`, in batch mode `<out>/cam/<the path below image_or_dir>__CAM.jpg`.
+`--tta {flip,rot,crop,full}` (not in the reference) predicts from the mean over several views of every image
+(predict/tta.py) in every mode but --cam, the sampled gate of --evaluate included; the JSON's `batch_results` keep
+their keys and `summary` gains `tta` and `mean_view_agreement`.
 """
 from __future__ import annotations
 
@@ -23,6 +27,7 @@ from typing import Optional
 
 from ..predict.evaluation import PredictionEvaluator
 from ..predict.predictor import Predictor
+from ..predict.tta import PRESETS as TTA_PRESETS
 from ..utils.common import get_logger, setup_logging
 from ..utils.image_utils import ImageLoader
 from ..utils.ranks import init_from_env
@@ -49,6 +54,8 @@ def parse_args(argv=None):
     p.add_argument("--montage", action="store_true",
                    help="write the original beside the masked leaf with the prediction under them "
                         "(<stem>_prediction.png; in batch mode montage/<path>_prediction.jpg)")
+    p.add_argument("--tta", choices=TTA_PRESETS, default=None,
+                   help="test-time augmentation: average the prediction over this preset's views of every image")
     return p.parse_args(argv)
 
 
@@ -60,6 +67,8 @@ def validate_inputs(args):
         raise ValueError("--montage cannot be combined with --evaluate")
     if args.montage and args.cam:
         raise ValueError("--montage cannot be combined with --cam")
+    if args.tta and args.cam:
+        raise ValueError("--tta cannot be combined with --cam (a heat map belongs to one view)")
     if args.cam and not 0.0 <= args.cam_alpha <= 1.0:
         raise ValueError(f"--cam-alpha must lie in [0, 1], got {args.cam_alpha}")
     if not image_path.exists():
@@ -93,7 +102,9 @@ def create_batch_summary(results, processing_time):
             "average_confidence": f"{avg:.2%}", "prediction_distribution": counts}
 
 
-def save_batch_results_json(results, processing_time, output_path):
+def save_batch_results_json(results, processing_time, output_path, tta=None):
+    """tta (the preset, when the predictions are test-time-augmented ones): `summary` also says so and gives the mean
+    of the results' view agreement."""
     output_path = Path(output_path)
     if not output_path.is_absolute() and not str(output_path).startswith("artifacts/"):
         output_path = Path("artifacts/prediction_output") / output_path.name
@@ -102,6 +113,10 @@ def save_batch_results_json(results, processing_time, output_path):
                                "confidence": r["confidence"],
                                "all_probabilities": r["all_probabilities"]} for r in results],
             "summary": create_batch_summary(results, processing_time)}
+    if tta is not None:
+        seen = [r["view_agreement"] for r in results if r.get("view_agreement") is not None]
+        data["summary"]["tta"] = tta
+        data["summary"]["mean_view_agreement"] = sum(seen) / len(seen) if seen else None
     output_path.parent.mkdir(parents=True, exist_ok=True)
     with open(output_path, "w") as f:
         json.dump(data, f, indent=2)
@@ -222,7 +237,8 @@ def run_sampling_enforced_batch(predictor, image_dir: Path, manifest_path: Path,
             if rk.rank != 0:
                 return True
             if json_output:
-                logger.info("Results saved to: %s", save_batch_results_json(results, proc, json_output))
+                logger.info("Results saved to: %s", save_batch_results_json(results, proc, json_output,
+                                                                            tta=getattr(predictor, "tta", None)))
             try:
                 PredictionEvaluator(predictor).evaluate_predictions(
                     paths, labels, output_dir=Path("artifacts/prediction_output/evaluation"))
@@ -242,7 +258,7 @@ def main(argv=None) -> None:
         args = parse_args(argv)
         image_path, learnings_dir = validate_inputs(args)
         rk = init_from_env()   # replicas under torch.distributed.run; one process otherwise
-        predictor = Predictor(learnings_dir)
+        predictor = Predictor(learnings_dir, tta=args.tta)
         predictor.load()
         if args.batch_mode:
             if args.evaluate:
@@ -275,7 +291,7 @@ def main(argv=None) -> None:
                 logger.info("Heat maps saved under: %s", Path(args.output_dir) / "cam")
             if args.montage:
                 logger.info("Montages saved under: %s", Path(args.output_dir) / "montage")
-            out = save_batch_results_json(results, proc, args.json_output)
+            out = save_batch_results_json(results, proc, args.json_output, tta=args.tta)
             logger.info("Results saved to: %s", out)
             for k, v in create_batch_summary(results, proc).items():
                 logger.info("  %s: %s", k, v)
@@ -289,6 +305,8 @@ def main(argv=None) -> None:
                 r = predictor.predict_single(image_path, use_transform=args.montage)
             logger.info(f"Image: {r['image_path']}")
             logger.info(f"Prediction: {r['top_prediction']} ({r['confidence']:.2%})")
+            if args.tta:
+                logger.info(f"Views agreeing ({args.tta}): {r['view_agreement']:.0%}")
             for name, prob in sorted(r["all_probabilities"].items(), key=lambda x: -x[1])[:3]:
                 logger.info(f"    {name}: {prob:.2%}")
             if args.cam:

@@ -1281,6 +1281,58 @@ class LeafCNN:
         probs, _ = self.forward(x0, False)
         return probs
 
+    TTA_PASS_ROWS = 1024   # the most rows (images x views) one forward pass of predict_tta_device sees
+
+    @torch.no_grad()
+    def predict_tta_device(self, x, rows, weights=None):
+        """Test-time augmentation: every image is shown to the network in the v views of `rows` ([v,6] host floats
+        {flip, cos, sin, zoom, dy, dx}: predict/tta.py has presets, the rule is lf_tta_views_f32's in leafhip.h) and
+        the v probability rows are averaged with `weights` (v host floats, None: all 1).  x: uint8 [N,H,W,3] on host
+        or device, or float32 in [0,1] (brought to bytes as the Mixup input stage does).  The views of a slice of
+        whole images are made in one launch (nn.tta_views), go through the forward pass predict_device runs (no
+        pass sees more than TTA_PASS_ROWS rows) and are folded by nn.tta_combine.  Returns (probs [N,C], top [N]
+        int32 = argmax of probs, agree [N] int32 = how many counted views agree with top): device tensors of their
+        own, which the next forward pass does not overwrite."""
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        x = x.to(self.device, non_blocking=True)
+        if x.dtype == torch.float32:
+            x = (x * 255.0).round().clamp_(0, 255).to(torch.uint8)
+        elif x.dtype != torch.uint8:
+            raise TypeError("model input must be uint8 or float32 [N,H,W,3]")
+        if x.dim() != 4 or x.shape[0] == 0:
+            raise ValueError(f"predict_tta_device: [N,H,W,3] with N > 0 expected, got {tuple(x.shape)}")
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float32))
+        if rows.ndim != 2 or rows.shape[1] != 6 or not 1 <= rows.shape[0] <= nn.TTA_MAX_VIEWS:
+            raise ValueError(f"predict_tta_device: rows must be [v,6] with 1 <= v <= {nn.TTA_MAX_VIEWS}, "
+                             f"got {rows.shape}")
+        v = rows.shape[0]
+        n, h, w, _c = x.shape
+        mean, denom = self._norm_consts()
+        step = max(1, self.TTA_PASS_ROWS // v)
+        parts = []
+        for b in range(0, n, step):
+            xb = x[b:b + step].contiguous()
+            m = xb.shape[0]
+            x0 = nn.tta_views(xb, rows, mean, denom, out=self._buf(m * v, "x0", (m * v, 3, h, w)))
+            if self.infer_dtype == "bf16" and self._bf16_storage_ok(h, w):
+                p = self._forward_infer_bf16(x0)
+            else:
+                p, _ = self.forward(x0, False)
+            parts.append(nn.tta_combine(p, v, weights))
+        if len(parts) == 1:
+            return parts[0]
+        return tuple(torch.cat([part[k] for part in parts]) for k in range(3))
+
+    def predict_tta(self, x, rows, weights=None, batch_size: int = 256) -> np.ndarray:
+        """predict with test-time augmentation: probabilities [N,C] as a host array, `batch_size` images uploaded at
+        a time (predict_tta_device)."""
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        outs = [self.predict_tta_device(x[b:b + batch_size], rows, weights)[0]
+                for b in range(0, x.shape[0], batch_size)]
+        return torch.cat(outs).cpu().numpy()
+
     @torch.no_grad()
     def class_activation_maps(self, x, classes=None, top: int = 1):
         """Where on the picture each class's logit comes from.  The network ends in GlobalAveragePooling2D -> Dense,

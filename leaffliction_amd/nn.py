@@ -641,6 +641,69 @@ def mix_targets(y: torch.Tensor, mix8: torch.Tensor, out: Optional[torch.Tensor]
     return out
 
 
+TTA_MAX_VIEWS = 16
+
+
+def _host_f32(who: str, values, shape) -> "np.ndarray":
+    """A host array of float32 in C order with the given shape (-1: any), from an array, a list or a CPU tensor."""
+    import numpy as np
+    if isinstance(values, torch.Tensor):
+        if values.is_cuda:
+            raise ValueError(f"{who}: host values expected (they travel as kernel arguments), got a tensor on "
+                             f"{values.device}")
+        values = values.numpy()
+    a = np.ascontiguousarray(np.asarray(values), dtype=np.float32)
+    if a.ndim != len(shape) or any(s not in (-1, d) for s, d in zip(shape, a.shape)):
+        raise ValueError(f"{who}: expected shape {tuple(shape)}, got {a.shape}")
+    return a
+
+
+def tta_views(x_u8: torch.Tensor, rows, mean=None, denom=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """v views of every image in one launch (lf_tta_views_f32; the rule: include/leafhip.h): x_u8 uint8 [N,H,W,3] on
+    the GPU, rows [v,6] = {flip, cos, sin, zoom, dy, dx} per view on the HOST -> f32 [N*v,3,H,W], row i*v + k the
+    view k of image i, normalised with mean / denom as pack_hwc_u8_to_nchw_f32 does it."""
+    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3 \
+            or not x_u8.is_contiguous() or not x_u8.is_cuda:
+        raise ValueError("tta_views.x: a contiguous uint8 [N,H,W,3] tensor on the GPU expected")
+    n, h, w, _c = x_u8.shape
+    r = _host_f32("tta_views.rows", rows, (-1, 6))
+    v = r.shape[0]
+    if not 1 <= v <= TTA_MAX_VIEWS:
+        raise ValueError(f"tta_views: {v} views (1..{TTA_MAX_VIEWS})")
+    if (mean is None) != (denom is None):
+        raise ValueError("tta_views: mean and denom go together")
+    if out is None:
+        out = torch.empty((n * v, 3, h, w), dtype=_F32, device=x_u8.device)
+    _mix_checks("tta_views", x_u8, {"out": (out, (n * v, 3, h, w))})
+    m = d = None
+    if mean is not None:
+        m = (_lib.c_float * 3)(*[float(t) for t in mean])
+        d = (_lib.c_float * 3)(*[float(t) for t in denom])
+    _lib.call("lf_tta_views_f32", x_u8.data_ptr(), out.data_ptr(), n, h, w, r.ctypes.data, v, m, d, _stream())
+    return out
+
+
+def tta_combine(probs: torch.Tensor, v: int, weights=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The v probability rows of every image folded into one (lf_tta_combine_f32): probs f32 [N*v,C] image-major,
+    weights v host floats (None: all 1) -> (out [N,C] the weighted mean, top [N] int32 its argmax, agree [N] int32
+    the number of counted views whose own argmax is top)."""
+    _chk(probs, _F32, "tta_combine.probs", 2)
+    rows, c = probs.shape
+    v = int(v)
+    if not 1 <= v <= TTA_MAX_VIEWS:
+        raise ValueError(f"tta_combine: {v} views (1..{TTA_MAX_VIEWS})")
+    if rows == 0 or rows % v:
+        raise ValueError(f"tta_combine.probs: {rows} rows are not a positive multiple of v={v}")
+    wt = None if weights is None else _host_f32("tta_combine.weights", weights, (v,))
+    n = rows // v
+    out = torch.empty((n, c), dtype=_F32, device=probs.device)
+    top = torch.empty((n,), dtype=torch.int32, device=probs.device)
+    agree = torch.empty((n,), dtype=torch.int32, device=probs.device)
+    _lib.call("lf_tta_combine_f32", probs.data_ptr(), None if wt is None else wt.ctypes.data, v, out.data_ptr(),
+              top.data_ptr(), agree.data_ptr(), n, c, _stream())
+    return out, top, agree
+
+
 def scale_shift_act(x, scale, shift, relu: bool, out=None):
     _chk(x, _F32, "scale_shift_act.x", 4)
     n, c, h, w = x.shape

@@ -7,6 +7,10 @@ reference's ImageProcessor is display-only and not part of the model input path
 (`enable_subprocess=False` at predictor.py:46,99): the model always sees the original.  What that subprocess shows,
 the leaf on black outside make_mask's mask, is `processed_array` of `predict_single(path, use_transform=True)` and
 what `masked_arrays` returns for a batch (make_mask and the composite on the GPU); predict --montage draws it.
+
+`Predictor(dir, tta=preset)` (not in the reference) predicts from several views of every image instead of one
+(predict/tta.py, LeafCNN.predict_tta_device): the probabilities are the views' mean, and every result also carries
+`view_agreement`, the share of the views whose own prediction is the result's.
 """
 from __future__ import annotations
 
@@ -23,8 +27,12 @@ logger = get_logger(__name__)
 
 
 class Predictor:
-    def __init__(self, learnings_dir):
+    def __init__(self, learnings_dir, tta=None):
+        from .tta import PRESETS
+        if tta is not None and tta not in PRESETS:
+            raise ValueError(f"unknown TTA preset {tta!r}: one of {', '.join(PRESETS)}")
         self.learnings_dir = Path(learnings_dir)
+        self.tta = tta
         self.model_loader = None
         self._initialized = False
         self._codec = None   # DeviceDecoder of the pooled batch path
@@ -52,12 +60,36 @@ class Predictor:
                 out[k] = res[j]
         return out
 
-    def _result(self, path, original, probs) -> Dict[str, Any]:
+    def _result(self, path, original, probs, agreement=None) -> Dict[str, Any]:
         labels = self.model_loader.labels
         top = int(np.argmax(probs))
-        return {"image_path": path, "top_prediction": labels[top], "confidence": float(probs[top]),
-                "all_probabilities": {labels[j]: float(probs[j]) for j in range(len(labels))},
-                "original_array": original, "processed_array": original}
+        result = {"image_path": path, "top_prediction": labels[top], "confidence": float(probs[top]),
+                  "all_probabilities": {labels[j]: float(probs[j]) for j in range(len(labels))},
+                  "original_array": original, "processed_array": original}
+        if agreement is not None:
+            result["view_agreement"] = float(agreement)
+        return result
+
+    def _predict_inputs(self, x, step: int):
+        """Probabilities [n,C] of model inputs x [n,S,S,3] uint8 (host array or device tensor) as a host array, `step`
+        images at a time, and the view agreement [n] (agree / v) with a TTA preset set, None without one."""
+        import torch
+        model = self.model_loader.model
+        if self.tta is None:
+            if isinstance(x, np.ndarray):
+                return model.predict(x, batch_size=step), None
+            return torch.cat([model.predict_device(x[b:b + step]).clone()
+                              for b in range(0, x.shape[0], step)]).cpu().numpy(), None
+        from .tta import view_rows
+        rows, weights = view_rows(self.tta, int(x.shape[1]), int(x.shape[2]))
+        if getattr(model, "predict_tta_device", None) is None:
+            raise ValueError("test-time augmentation needs a leaf_cnn model")
+        probs, agree = [], []
+        for b in range(0, x.shape[0], step):   # predict_tta_device keeps images x views of a pass within 1,024
+            p, _top, a = model.predict_tta_device(x[b:b + step], rows, weights)
+            probs.append(p)
+            agree.append(a)
+        return torch.cat(probs).cpu().numpy(), torch.cat(agree).cpu().numpy() / float(len(rows))
 
     def predict_single(self, image_path, use_transform: bool = False) -> Dict[str, Any]:
         """use_transform: `processed_array` is the image on black outside make_mask's mask (masked_arrays) instead
@@ -66,8 +98,8 @@ class Predictor:
             raise RuntimeError("Predictor not initialized. Call load() first.")
         image_path = Path(image_path)
         original = ImageLoader.load_as_array(image_path)
-        probs = self.model_loader.model.predict(self._prepare([original]))[0]
-        result = self._result(image_path, original, probs)
+        probs, agreement = self._predict_inputs(self._prepare([original]), 256)
+        result = self._result(image_path, original, probs[0], None if agreement is None else agreement[0])
         if use_transform:
             result["processed_array"] = self.masked_arrays([original], [image_path])[0]
         return result
@@ -117,10 +149,7 @@ class Predictor:
         Huffman-decode the files, the GPU finishes the JPEG decoding and resizes) and the forward pass run chunk
         after chunk.  Same results, same order, same skipping of unreadable files as the sequential loop
         (the pixels are Pillow's, bit for bit: tests/test_jpeg_codec.py)."""
-        import torch
-
         from ..dataio.device_decode import DeviceDecoder
-        model = self.model_loader.model
         if self._codec is None:
             self._codec = DeviceDecoder()
         results: List[Dict[str, Any]] = []
@@ -129,9 +158,9 @@ class Predictor:
                 logger.error(f"Error processing image {message}")
             if not kept:
                 continue
-            probs = torch.cat([model.predict_device(x[b:b + 1024]).clone()
-                               for b in range(0, len(kept), 1024)]).cpu().numpy()
-            results += [self._result(paths[k], natives[k], probs[j]) for j, k in enumerate(kept)]
+            probs, agreement = self._predict_inputs(x, 1024)
+            results += [self._result(paths[k], natives[k], probs[j], None if agreement is None else agreement[j])
+                        for j, k in enumerate(kept)]
         if not results:
             logger.warning("No valid images to predict.")
         return results
@@ -165,8 +194,9 @@ class Predictor:
         if not loaded:
             logger.warning("No valid images to predict.")
             return []
-        probs = self.model_loader.model.predict(self._prepare([a for _p, a in loaded]))
-        return [self._result(p, a, probs[i]) for i, (p, a) in enumerate(loaded)]
+        probs, agreement = self._predict_inputs(self._prepare([a for _p, a in loaded]), 256)
+        return [self._result(p, a, probs[i], None if agreement is None else agreement[i])
+                for i, (p, a) in enumerate(loaded)]
 
     def _explain_chunk(self, x, step: int, top: int, alpha: float):
         """Probabilities and heat-map overlays of one chunk of model inputs x [n,S,S,3] uint8 on the device, the
