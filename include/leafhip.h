@@ -1165,6 +1165,46 @@ int lf_tta_views_f32(const uint8_t* in, float* out, int n, int h, int w, const f
 int lf_tta_combine_f32(const float* probs, const float* weight, int v, float* out, int32_t* top, int32_t* agree,
                        int n, int c, lf_stream_t stream);
 
+/* ---- Calibration: temperature scaling of probability rows ------------------- */
+/* A model here hands out probabilities p [n][c] (f32), not logits, and that is enough.  With
+ *   z_j = ln(max(p_j, FLT_MIN))          FLT_MIN = 1.17549435e-38, in float64
+ *   q   = softmax(beta z)                beta = 1 / T > 0 the inverse temperature
+ * q is the temperature-scaled softmax of the logits: ln p differs from them by a constant per row, which the softmax
+ * drops.  A probability that underflowed to 0 is read as FLT_MIN (z = -87.3), not as weight zero; so is a NaN.
+ * All per-row arithmetic is float64, every operation rounded on its own (no contraction).
+ *
+ * lf_calib_stats: labels int32 [n]; betas a HOST pointer to k doubles, 1 <= k <= 8, each finite and > 0; 1 <= bins
+ * <= 64.  A row whose label lies outside [0, c) is skipped (counted, and left out of everything but pred).  Per beta,
+ * summed over the other rows, with y the label, m = beta ln(max_j p_j), s = sum_j exp(beta z_j - m), q_j =
+ * exp(beta z_j - m) / s, mu = sum_j q_j z_j:
+ *   nll   = m + ln s - beta z_y
+ *   g     = mu - z_y                          d nll / d beta
+ *   h     = sum_j q_j (z_j - mu)^2            d2 nll / d beta2: a second pass about mu, never negative
+ *   brier = sum_j (q_j - [j == y])^2
+ *   conf  = max_j q_j = 1 / s
+ *   bin b = min(bins - 1, (int)(conf * bins)): the rows in it, the sum of their conf, and those with pred == y
+ * Independent of beta: pred[i] = the lowest index attaining the maximum of the INPUT row (np.argmax; so no
+ * prediction moves with beta; written for skipped rows too), the number of rows with pred == y, the number skipped,
+ * and cm[y][pred] += 1.
+ * Outputs (device): sums f64 [k][5 + bins] = {nll, g, h, brier, conf, the bins' conf sums}; counts i32
+ * [k][2][bins] = {rows per bin, correct rows per bin}, followed by {correct, skipped}; pred i32 [n] or null; cm i32
+ * [c][c] or null, cleared by the call.  ws: lf_calib_stats_workspace(n, k, bins) bytes, 8-byte aligned (0: bad
+ * arguments).
+ * Order of summation: a wave adds its rows i, i + waves, ... in ascending order (one lane per beta, in registers;
+ * the bins in a table of the wave's own), a workgroup its waves in order, a second one-workgroup kernel the
+ * workgroups in order; the number of workgroups depends on n alone.  No float goes through an atomic: the same
+ * input gives the same bits.  (cm is counted with integer atomics.)
+ *
+ * lf_calib_apply_f32: out[i][j] = (float) q_ij for one beta, conf[i] = (float)(1 / s_i) = max_j out[i][j], top[i] =
+ * pred as above.  out == probs (in place) is allowed; any other overlap of out and probs is refused.
+ * Both: n > 0, 1 <= c <= 4096. */
+size_t lf_calib_stats_workspace(int n, int k, int bins);
+int lf_calib_stats(const float* probs, const int32_t* labels, int n, int c, const double* betas, int k, int bins,
+                   double* sums, int32_t* counts, int32_t* pred, int32_t* cm, void* ws, size_t ws_bytes,
+                   lf_stream_t stream);
+int lf_calib_apply_f32(const float* probs, double beta, float* out, float* conf, int32_t* top, int n, int c,
+                       lf_stream_t stream);
+
 /* ---- input stage ----------------------------------------------------------- */
 /* u8 HWC -> f32 NCHW with the model's train-time augmentation fused (cnn.py:74-86):
  * keras RandomFlip("horizontal") -> RandomRotation (bilinear, fill_mode="reflect") ->

@@ -156,6 +156,9 @@ SIGNATURES = {
     "lf_mix_targets_f32": [P, P, P, c_int, c_int, P],
     "lf_tta_views_f32": [P, P, c_int, c_int, c_int, P, c_int, P, P, P],
     "lf_tta_combine_f32": [P, P, c_int, P, P, P, c_int, c_int, P],
+    "lf_calib_stats_workspace": [c_int, c_int, c_int],
+    "lf_calib_stats": [P, P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_size_t, P],
+    "lf_calib_apply_f32": [P, c_double, P, P, P, c_int, c_int, P],
     "lf_scale_shift_act_f32": [P, P, c_int, c_int, c_int, P, P, c_int, P],
     "lf_bn_workspace": [c_int],
     "lf_bn_train_stats_f32": [P, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P, P, P, P,
@@ -189,7 +192,7 @@ _RESTYPES = {"lf_last_error": C.c_char_p, "lf_conv2d_wgrad_workspace": c_size_t,
              "lf_conv2d_proj_bwd_workspace": c_size_t,
              "lf_dwconv3x3_bwd_workspace": c_size_t,
              "lf_bn_workspace": c_size_t, "lf_se_bwd_workspace": c_size_t,
-             "lf_adamw_workspace": c_size_t, "lf_conv2d_stats_tiles": C.c_longlong,
+             "lf_adamw_workspace": c_size_t, "lf_calib_stats_workspace": c_size_t, "lf_conv2d_stats_tiles": C.c_longlong,
              "lf_blur_saliency_workspace": c_size_t, "lf_inclusive_mask_workspace": c_size_t, "lf_make_mask_workspace": c_size_t, "lf_brown_spots_workspace": c_size_t, "lf_lesion_table_workspace": c_size_t, "lf_canny_workspace": c_size_t, "lf_clahe_workspace": c_size_t,
              "lf_good_features_workspace": c_size_t, "lf_landmarks_workspace": c_size_t,
              "lf_conv2d_bf16_weight_elems": c_size_t,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--montage] [--tta PRESET]
-[--evaluate ...]`.
+[--calibrated] [--evaluate ...]`.
 
 Flags, JSON schema (`batch_results` + `summary`), the sampled accuracy gate and the exit
 codes (1 on error, 2 when the gate is never reached) follow srcs/cli/predict.py:17-87,
@@ -14,6 +14,10 @@ laid over it: `<out>/<stem>__CAM.jpg`, in batch mode `<out>/cam/<the path below 
 `--tta {flip,rot,crop,full}` (not in the reference) predicts from the mean over several views of every image
 (predict/tta.py) in every mode but --cam, the sampled gate of --evaluate included; the JSON's `batch_results` keep
 their keys and `summary` gains `tta` and `mean_view_agreement`.
+`--calibrated` (not in the reference), in every mode: `confidence` and `all_probabilities` are the probabilities at
+the temperature `<learnings>/calibration.json` holds (fitted by cli.calibrate or train --calibrate; exit status 1
+without the file), after the views' mean with --tta.  No prediction, view agreement or heat map changes; `summary`
+gains `calibration`.
 """
 from __future__ import annotations
 
@@ -56,6 +60,8 @@ def parse_args(argv=None):
                         "(<stem>_prediction.png; in batch mode montage/<path>_prediction.jpg)")
     p.add_argument("--tta", choices=TTA_PRESETS, default=None,
                    help="test-time augmentation: average the prediction over this preset's views of every image")
+    p.add_argument("--calibrated", action="store_true",
+                   help="report confidences at the temperature of <learnings>/calibration.json")
     return p.parse_args(argv)
 
 
@@ -81,6 +87,9 @@ def validate_inputs(args):
         raise FileNotFoundError(f"Learnings directory not found: {learnings_dir}")
     if not (learnings_dir / "meta.json").exists():
         raise FileNotFoundError(f"Meta file not found: {learnings_dir / 'meta.json'}")
+    if args.calibrated and not (learnings_dir / "calibration.json").exists():
+        raise FileNotFoundError(f"Calibration file not found: {learnings_dir / 'calibration.json'} "
+                                "(fit one with cli.calibrate or train --calibrate)")
     if args.evaluate:
         if not args.batch_mode:
             raise ValueError("--evaluate requires --batch-mode")
@@ -102,9 +111,18 @@ def create_batch_summary(results, processing_time):
             "average_confidence": f"{avg:.2%}", "prediction_distribution": counts}
 
 
-def save_batch_results_json(results, processing_time, output_path, tta=None):
+def calibration_summary(predictor):
+    """`summary.calibration` of a predictor that reports calibrated confidences, None of any other."""
+    data = getattr(predictor, "calibration", None)
+    if data is None:
+        return None
+    return {"temperature": float(data["temperature"]), "fitted_with_tta": data.get("fitted_on", {}).get("tta")}
+
+
+def save_batch_results_json(results, processing_time, output_path, tta=None, calibration=None):
     """tta (the preset, when the predictions are test-time-augmented ones): `summary` also says so and gives the mean
-    of the results' view agreement."""
+    of the results' view agreement.  calibration (calibration_summary, when the confidences are calibrated ones):
+    `summary.calibration`."""
     output_path = Path(output_path)
     if not output_path.is_absolute() and not str(output_path).startswith("artifacts/"):
         output_path = Path("artifacts/prediction_output") / output_path.name
@@ -117,6 +135,8 @@ def save_batch_results_json(results, processing_time, output_path, tta=None):
         seen = [r["view_agreement"] for r in results if r.get("view_agreement") is not None]
         data["summary"]["tta"] = tta
         data["summary"]["mean_view_agreement"] = sum(seen) / len(seen) if seen else None
+    if calibration is not None:
+        data["summary"]["calibration"] = calibration
     output_path.parent.mkdir(parents=True, exist_ok=True)
     with open(output_path, "w") as f:
         json.dump(data, f, indent=2)
@@ -237,8 +257,9 @@ def run_sampling_enforced_batch(predictor, image_dir: Path, manifest_path: Path,
             if rk.rank != 0:
                 return True
             if json_output:
-                logger.info("Results saved to: %s", save_batch_results_json(results, proc, json_output,
-                                                                            tta=getattr(predictor, "tta", None)))
+                saved = save_batch_results_json(results, proc, json_output, tta=getattr(predictor, "tta", None),
+                                                calibration=calibration_summary(predictor))
+                logger.info("Results saved to: %s", saved)
             try:
                 PredictionEvaluator(predictor).evaluate_predictions(
                     paths, labels, output_dir=Path("artifacts/prediction_output/evaluation"))
@@ -258,7 +279,7 @@ def main(argv=None) -> None:
         args = parse_args(argv)
         image_path, learnings_dir = validate_inputs(args)
         rk = init_from_env()   # replicas under torch.distributed.run; one process otherwise
-        predictor = Predictor(learnings_dir, tta=args.tta)
+        predictor = Predictor(learnings_dir, tta=args.tta, calibrated=args.calibrated)
         predictor.load()
         if args.batch_mode:
             if args.evaluate:
@@ -291,7 +312,8 @@ def main(argv=None) -> None:
                 logger.info("Heat maps saved under: %s", Path(args.output_dir) / "cam")
             if args.montage:
                 logger.info("Montages saved under: %s", Path(args.output_dir) / "montage")
-            out = save_batch_results_json(results, proc, args.json_output, tta=args.tta)
+            out = save_batch_results_json(results, proc, args.json_output, tta=args.tta,
+                                          calibration=calibration_summary(predictor))
             logger.info("Results saved to: %s", out)
             for k, v in create_batch_summary(results, proc).items():
                 logger.info("  %s: %s", k, v)
@@ -305,6 +327,8 @@ def main(argv=None) -> None:
                 r = predictor.predict_single(image_path, use_transform=args.montage)
             logger.info(f"Image: {r['image_path']}")
             logger.info(f"Prediction: {r['top_prediction']} ({r['confidence']:.2%})")
+            if args.calibrated:
+                logger.info(f"Calibrated at temperature {predictor.calibration['temperature']:.4f}")
             if args.tta:
                 logger.info(f"Views agreeing ({args.tta}): {r['view_agreement']:.0%}")
             for name, prob in sorted(r["all_probabilities"].items(), key=lambda x: -x[1])[:3]:

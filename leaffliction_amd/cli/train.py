@@ -17,6 +17,10 @@ the teacher running its inference path on every batch (bf16 unless --no-mixed-pr
 with probability P an image is blended with a partner from its batch, by Mixup (lambda ~ Beta(ALPHA, ALPHA)) or
 CutMix (a pasted box of area 1 - lambda), a fair coin deciding where both are on, and the step trains on the labels
 blended in the same ratio.  Not together with --teacher.
+`--calibrate` fits the temperature behind `predict --calibrated` once the model is saved: the saved variant's
+probabilities on the validation sequence (its inference path, batch by batch) go through predict/calibration.py and
+the result is written to calibration.json in --out-dir.  The training step and meta.json are untouched; with more than
+one rank the fit is skipped and logged.
 """
 from __future__ import annotations
 
@@ -75,6 +79,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="CutMix with a box of area 1 - lambda, lambda ~ Beta(ALPHA, ALPHA); 0 = off")
     p.add_argument("--mix-prob", type=float, default=1.0, metavar="P",
                    help="probability that an image is mixed at all (with --mixup / --cutmix)")
+    p.add_argument("--calibrate", action="store_true",
+                   help="after saving, fit the temperature on the validation split and write calibration.json")
     p.add_argument("--out-dir", type=Path, default=Path("artifacts/models"),
                    help="where the model and its JSON artifacts are written")
     args = p.parse_args(argv)
@@ -252,6 +258,29 @@ def create_training_metadata(args, cfg, num_classes, train_items, val_items, dp)
     }
 
 
+def calibrate_saved_model(model, val_seq, label2idx, args, manifest_path, dp) -> None:
+    """--calibrate: the temperature of the model as saved, fitted on the validation sequence."""
+    if dp.world > 1:
+        LOGGER.info("--calibrate is skipped with %d ranks: fit afterwards with cli.calibrate", dp.world)
+        return
+    import torch
+
+    from ..predict import calibration
+    probs, labels = [], []
+    for i in range(len(val_seq)):
+        bx, by = val_seq[i]
+        if bx.shape[0] == 0:
+            continue
+        probs.append(model.predict_device(bx).clone())
+        labels.append(model._targets(by)[1].to(torch.int32))
+    names = sorted(label2idx, key=lambda k: label2idx[k])
+    data = calibration.fit_and_save(args.out_dir, torch.cat(probs).contiguous(), torch.cat(labels).contiguous(),
+                                    names, manifest=manifest_path, split="val", tta=None)
+    LOGGER.info("Calibration: temperature %.4f, NLL %.4f -> %.4f, ECE %.4f -> %.4f (%s)", data["temperature"],
+                data["before"]["nll"], data["after"]["nll"], data["before"]["ece"], data["after"]["ece"],
+                Path(args.out_dir) / calibration.FILE_NAME)
+
+
 def main(argv=None) -> None:
     args = parse_args(argv)
     setup_logging()
@@ -296,6 +325,8 @@ def main(argv=None) -> None:
                             dp=dp, **fit_extra)
         save_best_variant(model, val_seq, ema_cb, out_dir=args.out_dir,
                           label2idx=label2idx, history=history, meta=meta, dp=dp)
+        if args.calibrate:
+            calibrate_saved_model(model, val_seq, label2idx, args, manifest_path, dp)
     except (FileNotFoundError, ValueError) as e:
         LOGGER.error("Training failed: %s", e)
     finally:

@@ -704,6 +704,89 @@ def tta_combine(probs: torch.Tensor, v: int, weights=None) -> Tuple[torch.Tensor
     return out, top, agree
 
 
+CALIB_MAX_BETAS = 8
+CALIB_MAX_BINS = 64
+CALIB_MAX_CLASSES = 4096
+CALIB_SUMS = ("nll", "g", "h", "brier", "conf")
+CALIB_STATS_WAVES = 1024   # the most waves a calib_stats launch runs: beyond that many rows a wave takes several
+
+
+def _calib_probs(who: str, probs: torch.Tensor) -> Tuple[int, int]:
+    _chk(probs, _F32, f"{who}.probs", 2)
+    n, c = probs.shape
+    if n == 0 or not 1 <= c <= CALIB_MAX_CLASSES:
+        raise ValueError(f"{who}.probs: [N,C] with N > 0 and 1 <= C <= {CALIB_MAX_CLASSES} expected, got "
+                         f"{tuple(probs.shape)}")
+    return n, c
+
+
+def _calib_beta(who: str, beta) -> float:
+    import math
+    b = float(beta)
+    if not (math.isfinite(b) and b > 0.0):
+        raise ValueError(f"{who}: an inverse temperature must be finite and positive, got {beta!r}")
+    return b
+
+
+def calib_stats(probs: torch.Tensor, labels: torch.Tensor, betas, bins: int = 15, confusion: bool = True) -> dict:
+    """What probability rows and their labels say about each inverse temperature of `betas` (lf_calib_stats; the
+    rule: include/leafhip.h): probs f32 [N,C] and labels int32 [N] on the GPU, betas 1..8 host floats.  Returns host
+    numpy arrays: betas [K]; nll, g, h, brier, conf f64 [K] (sums over the rows with a label in [0, C)); bin_conf f64
+    [K,bins], bin_count and bin_correct int64 [K,bins]; pred int32 [N]; confusion int64 [C,C] ([true][pred]) or
+    None; and the ints n (rows counted), correct, skipped and bins.  One device-to-host sync."""
+    import numpy as np
+    n, c = _calib_probs("calib_stats", probs)
+    _chk(labels, torch.int32, "calib_stats.labels", 1)
+    if labels.shape[0] != n or labels.device != probs.device:
+        raise ValueError(f"calib_stats.labels: expected [{n}] on {probs.device}, got {tuple(labels.shape)} on "
+                         f"{labels.device}")
+    bt = np.ascontiguousarray(np.atleast_1d(np.asarray(betas, dtype=np.float64)))
+    if bt.ndim != 1 or not 1 <= bt.shape[0] <= CALIB_MAX_BETAS:
+        raise ValueError(f"calib_stats.betas: 1..{CALIB_MAX_BETAS} values expected, got shape {bt.shape}")
+    for b in bt:
+        _calib_beta("calib_stats.betas", b)
+    k, bins = int(bt.shape[0]), int(bins)
+    if not 1 <= bins <= CALIB_MAX_BINS:
+        raise ValueError(f"calib_stats: bins={bins} (1..{CALIB_MAX_BINS})")
+    per = len(CALIB_SUMS) + bins
+    sums = torch.empty((k, per), dtype=torch.float64, device=probs.device)
+    counts = torch.empty((k * 2 * bins + 2,), dtype=torch.int32, device=probs.device)
+    pred = torch.empty((n,), dtype=torch.int32, device=probs.device)
+    cm = torch.empty((c, c), dtype=torch.int32, device=probs.device) if confusion else None
+    ws = _workspace(_lib.load().lf_calib_stats_workspace(n, k, bins), probs.device)
+    _lib.call("lf_calib_stats", probs.data_ptr(), labels.data_ptr(), n, c, bt.ctypes.data, k, bins, sums.data_ptr(),
+              counts.data_ptr(), pred.data_ptr(), _ptr(cm), ws.data_ptr(), ws.numel(), _stream())
+    sums_h, counts_h = sums.cpu().numpy(), counts.cpu().numpy().astype(np.int64)
+    per_bin = counts_h[:k * 2 * bins].reshape(k, 2, bins)
+    out = {name: sums_h[:, j].copy() for j, name in enumerate(CALIB_SUMS)}
+    skipped = int(counts_h[-1])
+    out.update(betas=bt.copy(), bin_conf=sums_h[:, len(CALIB_SUMS):].copy(), bin_count=per_bin[:, 0].copy(),
+               bin_correct=per_bin[:, 1].copy(), pred=pred.cpu().numpy(),
+               confusion=None if cm is None else cm.cpu().numpy().astype(np.int64),
+               n=n - skipped, correct=int(counts_h[-2]), skipped=skipped, bins=bins)
+    return out
+
+
+def calib_apply(probs: torch.Tensor, beta, out: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The rows at inverse temperature beta (lf_calib_apply_f32): probs f32 [N,C] on the GPU -> (out f32 [N,C] =
+    softmax(beta ln max(probs, FLT_MIN)), conf f32 [N] its row maximum, top int32 [N] the argmax of the INPUT row,
+    lowest index on ties).  `out` may be probs itself (in place); any other overlap is refused."""
+    n, c = _calib_probs("calib_apply", probs)
+    b = _calib_beta("calib_apply.beta", beta)
+    if out is None:
+        out = torch.empty_like(probs)
+    _mix_checks("calib_apply", probs, {"out": (out, (n, c))})
+    lo, hi = out.data_ptr(), probs.data_ptr()
+    if lo != hi and abs(lo - hi) < 4 * n * c:
+        raise ValueError("calib_apply: out overlaps probs without being probs (in place means out is probs)")
+    conf = torch.empty((n,), dtype=_F32, device=probs.device)
+    top = torch.empty((n,), dtype=torch.int32, device=probs.device)
+    _lib.call("lf_calib_apply_f32", probs.data_ptr(), _lib.c_double(b), out.data_ptr(), conf.data_ptr(),
+              top.data_ptr(), n, c, _stream())
+    return out, conf, top
+
+
 def scale_shift_act(x, scale, shift, relu: bool, out=None):
     _chk(x, _F32, "scale_shift_act.x", 4)
     n, c, h, w = x.shape

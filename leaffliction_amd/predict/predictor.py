@@ -11,6 +11,11 @@ what `masked_arrays` returns for a batch (make_mask and the composite on the GPU
 `Predictor(dir, tta=preset)` (not in the reference) predicts from several views of every image instead of one
 (predict/tta.py, LeafCNN.predict_tta_device): the probabilities are the views' mean, and every result also carries
 `view_agreement`, the share of the views whose own prediction is the result's.
+
+`Predictor(dir, calibrated=True)` (not in the reference) reports calibrated confidences: the probability rows go
+through `nn.calib_apply` at the inverse temperature DIR/calibration.json holds (predict/calibration.py), after the
+views' mean with a TTA preset.  `confidence` and `all_probabilities` are then the calibrated values; the prediction is
+the argmax of the uncalibrated row and so never moves.
 """
 from __future__ import annotations
 
@@ -27,17 +32,27 @@ logger = get_logger(__name__)
 
 
 class Predictor:
-    def __init__(self, learnings_dir, tta=None):
+    def __init__(self, learnings_dir, tta=None, calibrated: bool = False):
         from .tta import PRESETS
         if tta is not None and tta not in PRESETS:
             raise ValueError(f"unknown TTA preset {tta!r}: one of {', '.join(PRESETS)}")
         self.learnings_dir = Path(learnings_dir)
         self.tta = tta
+        self.calibrated = bool(calibrated)
+        self.calibration = None   # what calibration.json holds, with calibrated=True and after load()
         self.model_loader = None
         self._initialized = False
         self._codec = None   # DeviceDecoder of the pooled batch path
 
     def load(self):
+        if self.calibrated:   # before the model: a missing file fails at once
+            from . import calibration
+            self.calibration = calibration.load(self.learnings_dir)
+            fitted = self.calibration.get("fitted_on", {}).get("tta")
+            if fitted != self.tta:
+                logger.warning("calibration.json was fitted %s, these predictions are made %s: the temperature may "
+                               "not suit them", f"with --tta {fitted}" if fitted else "without TTA",
+                               f"with --tta {self.tta}" if self.tta else "without TTA")
         self.model_loader = ModelLoader(self.learnings_dir)
         self.model_loader.load()
         self._initialized = True
@@ -60,9 +75,11 @@ class Predictor:
                 out[k] = res[j]
         return out
 
-    def _result(self, path, original, probs, agreement=None) -> Dict[str, Any]:
+    def _result(self, path, original, probs, agreement=None, top=None) -> Dict[str, Any]:
+        """top: the predicted class where it is not to be taken from `probs` (calibrated rows: two probabilities that
+        differ may round to one float at a high temperature, and the prediction is the uncalibrated row's)."""
         labels = self.model_loader.labels
-        top = int(np.argmax(probs))
+        top = int(np.argmax(probs)) if top is None else int(top)
         result = {"image_path": path, "top_prediction": labels[top], "confidence": float(probs[top]),
                   "all_probabilities": {labels[j]: float(probs[j]) for j in range(len(labels))},
                   "original_array": original, "processed_array": original}
@@ -70,26 +87,45 @@ class Predictor:
             result["view_agreement"] = float(agreement)
         return result
 
+    def _calibrate(self, probs):
+        """Device rows [n,C] -> (the rows at the stored inverse temperature, their predictions [n]) as host arrays."""
+        from .. import nn
+        out, _conf, top = nn.calib_apply(probs.contiguous(), float(self.calibration["beta"]))
+        return out.cpu().numpy(), top.cpu().numpy()
+
     def _predict_inputs(self, x, step: int):
         """Probabilities [n,C] of model inputs x [n,S,S,3] uint8 (host array or device tensor) as a host array, `step`
-        images at a time, and the view agreement [n] (agree / v) with a TTA preset set, None without one."""
+        images at a time; the view agreement [n] (agree / v) with a TTA preset set, None without one; and with
+        calibrated=True the predictions [n] (the rows are then the calibrated ones), None without."""
         import torch
         model = self.model_loader.model
+        agreement = None
         if self.tta is None:
+            if isinstance(x, np.ndarray) and self.calibration is None:
+                return model.predict(x, batch_size=step), None, None
             if isinstance(x, np.ndarray):
-                return model.predict(x, batch_size=step), None
-            return torch.cat([model.predict_device(x[b:b + step]).clone()
-                              for b in range(0, x.shape[0], step)]).cpu().numpy(), None
-        from .tta import view_rows
-        rows, weights = view_rows(self.tta, int(x.shape[1]), int(x.shape[2]))
-        if getattr(model, "predict_tta_device", None) is None:
-            raise ValueError("test-time augmentation needs a leaf_cnn model")
-        probs, agree = [], []
-        for b in range(0, x.shape[0], step):   # predict_tta_device keeps images x views of a pass within 1,024
-            p, _top, a = model.predict_tta_device(x[b:b + step], rows, weights)
-            probs.append(p)
-            agree.append(a)
-        return torch.cat(probs).cpu().numpy(), torch.cat(agree).cpu().numpy() / float(len(rows))
+                x = torch.from_numpy(np.ascontiguousarray(x))
+            probs = torch.cat([model.predict_device(x[b:b + step]).clone() for b in range(0, x.shape[0], step)])
+        else:
+            from .tta import view_rows
+            rows, weights = view_rows(self.tta, int(x.shape[1]), int(x.shape[2]))
+            if getattr(model, "predict_tta_device", None) is None:
+                raise ValueError("test-time augmentation needs a leaf_cnn model")
+            parts, agree = [], []
+            for b in range(0, x.shape[0], step):   # predict_tta_device keeps images x views of a pass within 1,024
+                p, _top, a = model.predict_tta_device(x[b:b + step], rows, weights)
+                parts.append(p)
+                agree.append(a)
+            probs, agreement = torch.cat(parts), torch.cat(agree).cpu().numpy() / float(len(rows))
+        if self.calibration is not None:
+            out, top = self._calibrate(probs)
+            return out, agreement, top
+        return probs.cpu().numpy(), agreement, None
+
+    def _results(self, paths, kept, natives, probs, agreement, top) -> List[Dict[str, Any]]:
+        """One result per kept file: row j of probs (agreement, top: [n] or None) belongs to paths[kept[j]]."""
+        return [self._result(paths[k], natives[k], probs[j], None if agreement is None else agreement[j],
+                             None if top is None else top[j]) for j, k in enumerate(kept)]
 
     def predict_single(self, image_path, use_transform: bool = False) -> Dict[str, Any]:
         """use_transform: `processed_array` is the image on black outside make_mask's mask (masked_arrays) instead
@@ -98,8 +134,8 @@ class Predictor:
             raise RuntimeError("Predictor not initialized. Call load() first.")
         image_path = Path(image_path)
         original = ImageLoader.load_as_array(image_path)
-        probs, agreement = self._predict_inputs(self._prepare([original]), 256)
-        result = self._result(image_path, original, probs[0], None if agreement is None else agreement[0])
+        probs, agreement, top = self._predict_inputs(self._prepare([original]), 256)
+        result = self._results([image_path], [0], [original], probs, agreement, top)[0]
         if use_transform:
             result["processed_array"] = self.masked_arrays([original], [image_path])[0]
         return result
@@ -144,26 +180,36 @@ class Predictor:
 
     POOL_MIN = 64   # below this many files the worker pool costs more than it saves
 
-    def _predict_batch_pooled(self, paths: List[Path]) -> List[Dict[str, Any]]:
-        """The batch path with the decoding spread out (dataio/device_decode.py: codec worker processes
-        Huffman-decode the files, the GPU finishes the JPEG decoding and resizes) and the forward pass run chunk
-        after chunk.  Same results, same order, same skipping of unreadable files as the sequential loop
-        (the pixels are Pillow's, bit for bit: tests/test_jpeg_codec.py)."""
-        from ..dataio.device_decode import DeviceDecoder
-        if self._codec is None:
-            self._codec = DeviceDecoder()
-        results: List[Dict[str, Any]] = []
-        for _first, kept, x, natives, errors in self._codec.chunks(paths, self.model_loader.img_size, keep_native=True):
-            for _k, message in errors:
-                logger.error(f"Error processing image {message}")
-            if not kept:
-                continue
-            probs, agreement = self._predict_inputs(x, 1024)
-            results += [self._result(paths[k], natives[k], probs[j], None if agreement is None else agreement[j])
-                        for j, k in enumerate(kept)]
-        if not results:
-            logger.warning("No valid images to predict.")
-        return results
+    def _model_inputs(self, paths: List[Path], keep_native: bool = True):
+        """The files as model inputs, the way every batch entry reads them: yields (kept, x, natives, step) with kept
+        the indices into `paths` of the files that could be read (the others are logged and skipped, like the
+        reference), x their uint8 [len(kept),S,S,3] inputs, natives[k] the decoded picture of file k (with
+        keep_native) and `step` the images to a forward pass.  From POOL_MIN files on the decoding is spread out
+        (dataio/device_decode.py: codec worker processes Huffman-decode the files, the GPU finishes the JPEG decoding
+        and resizes), x is a device tensor and a chunk is yielded at a time; below that the host loop decodes and x
+        is one host array.  Same pixels either way (Pillow's, bit for bit: tests/test_jpeg_codec.py)."""
+        import torch
+        if len(paths) >= self.POOL_MIN and getattr(self.model_loader.model, "predict_device", None) is not None \
+                and torch.cuda.is_available():
+            from ..dataio.device_decode import DeviceDecoder
+            if self._codec is None:
+                self._codec = DeviceDecoder()
+            for _first, kept, x, natives, errors in self._codec.chunks(paths, self.model_loader.img_size,
+                                                                       keep_native=keep_native):
+                for _k, message in errors:
+                    logger.error(f"Error processing image {message}")
+                if kept:
+                    yield kept, x, natives, 1024
+            return
+        kept, natives = [], {}
+        for k, p in enumerate(paths):
+            try:
+                natives[k] = ImageLoader.load_as_array(p)
+                kept.append(k)
+            except Exception as e:  # noqa: BLE001 — skipped like the reference
+                logger.error(f"Error processing image {p}: {e}")
+        if kept:
+            yield kept, self._prepare([natives[k] for k in kept]), natives, 256
 
     def close(self) -> None:
         """Stop the codec workers of the pooled batch path and release their slabs (idempotent)."""
@@ -181,28 +227,33 @@ class Predictor:
         if not self._initialized:
             raise RuntimeError("Predictor not initialized. Call load() first.")
         paths = [Path(p) for p in image_paths]
-        if len(paths) >= self.POOL_MIN and getattr(self.model_loader.model, "predict_device", None) is not None:
-            import torch
-            if torch.cuda.is_available():
-                return self._predict_batch_pooled(paths)
-        loaded = []
-        for p in paths:
-            try:
-                loaded.append((p, ImageLoader.load_as_array(p)))
-            except Exception as e:  # noqa: BLE001 — skipped like the reference
-                logger.error(f"Error processing image {p}: {e}")
-        if not loaded:
+        results: List[Dict[str, Any]] = []
+        for kept, x, natives, step in self._model_inputs(paths):
+            results += self._results(paths, kept, natives, *self._predict_inputs(x, step))
+        if not results:
             logger.warning("No valid images to predict.")
-            return []
-        probs, agreement = self._predict_inputs(self._prepare([a for _p, a in loaded]), 256)
-        return [self._result(p, a, probs[i], None if agreement is None else agreement[i])
-                for i, (p, a) in enumerate(loaded)]
+        return results
+
+    def predict_probabilities(self, image_paths):
+        """The probability rows of predict_batch without the result dicts: (float32 [m,C] host array, the indices into
+        image_paths of the m files that could be read, in order).  Same decoding route, TTA preset and calibration
+        as predict_batch."""
+        if not self._initialized:
+            raise RuntimeError("Predictor not initialized. Call load() first.")
+        paths = [Path(p) for p in image_paths]
+        rows, indices = [], []
+        for kept, x, _natives, step in self._model_inputs(paths, keep_native=False):
+            rows.append(self._predict_inputs(x, step)[0])
+            indices += kept
+        if not rows:
+            return np.zeros((0, self.model_loader.num_classes), np.float32), []
+        return np.concatenate(rows).astype(np.float32, copy=False), indices
 
     def _explain_chunk(self, x, step: int, top: int, alpha: float):
-        """Probabilities and heat-map overlays of one chunk of model inputs x [n,S,S,3] uint8 on the device, the
-        forward pass run in slices of `step` images as the prediction path does: the class activation maps of each
-        image's `top` classes (LeafCNN.class_activation_maps), slot 0 -- the prediction -- laid over the picture the
-        network saw (ops.cam_overlay_u8).  Host arrays."""
+        """Probabilities, heat-map overlays and (calibrated=True; else None) predictions of one chunk of model inputs
+        x [n,S,S,3] uint8 on the device, the forward pass run in slices of `step` images as the prediction path
+        does: the class activation maps of each image's `top` classes (LeafCNN.class_activation_maps), slot 0 -- the
+        prediction -- laid over the picture the network saw (ops.cam_overlay_u8).  Host arrays."""
         import torch
 
         from .. import ops
@@ -213,7 +264,11 @@ class Predictor:
             p, _classes, cam, peak = model.class_activation_maps(xb, top=top)
             probs.append(p)
             overlays.append(ops.cam_overlay_u8(xb, cam, peak, 0, alpha))
-        return torch.cat(probs).cpu().numpy(), torch.cat(overlays).cpu().numpy()
+        overlays = torch.cat(overlays).cpu().numpy()
+        if self.calibration is not None:   # the maps and the overlay belong to the prediction, which does not move
+            out, tops = self._calibrate(torch.cat(probs))
+            return out, overlays, tops
+        return torch.cat(probs).cpu().numpy(), overlays, None
 
     def explain_batch(self, image_paths, top: int = 1, alpha: float = 0.6) -> List[Dict[str, Any]]:
         """`predict_batch` with the reason for each prediction: the same result dicts (same decoding and resize
@@ -227,31 +282,12 @@ class Predictor:
             raise ValueError("class activation maps need a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
         paths = [Path(p) for p in image_paths]
         results: List[Dict[str, Any]] = []
-        if len(paths) >= self.POOL_MIN:
-            from ..dataio.device_decode import DeviceDecoder
-            if self._codec is None:
-                self._codec = DeviceDecoder()
-            for _first, kept, x, natives, errors in self._codec.chunks(paths, self.model_loader.img_size,
-                                                                       keep_native=True):
-                for _k, message in errors:
-                    logger.error(f"Error processing image {message}")
-                if not kept:
-                    continue
-                probs, overlays = self._explain_chunk(x, 1024, top, alpha)
-                for j, k in enumerate(kept):
-                    results.append(dict(self._result(paths[k], natives[k], probs[j]), cam_overlay=overlays[j]))
-        else:
-            loaded = []
-            for p in paths:
-                try:
-                    loaded.append((p, ImageLoader.load_as_array(p)))
-                except Exception as e:  # noqa: BLE001 — skipped like the reference
-                    logger.error(f"Error processing image {p}: {e}")
-            if loaded:
-                x = torch.from_numpy(self._prepare([a for _p, a in loaded])).cuda()
-                probs, overlays = self._explain_chunk(x, 256, top, alpha)
-                results = [dict(self._result(p, a, probs[i]), cam_overlay=overlays[i])
-                           for i, (p, a) in enumerate(loaded)]
+        for kept, x, natives, step in self._model_inputs(paths):
+            if isinstance(x, np.ndarray):
+                x = torch.from_numpy(x).cuda()
+            probs, overlays, tops = self._explain_chunk(x, step, top, alpha)
+            results += [dict(r, cam_overlay=overlays[j])
+                        for j, r in enumerate(self._results(paths, kept, natives, probs, None, tops))]
         if not results:
             logger.warning("No valid images to predict.")
         return results
