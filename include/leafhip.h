@@ -1205,6 +1205,51 @@ int lf_calib_stats(const float* probs, const int32_t* labels, int n, int c, cons
 int lf_calib_apply_f32(const float* probs, double beta, float* out, float* conf, int32_t* top, int n, int c,
                        lf_stream_t stream);
 
+/* ---- Near-duplicate search: 128-bit difference hashes and their all-pairs Hamming search ---- */
+/* Integer and exact throughout; no float appears.
+ *
+ * lf_dhash128_u8: in u8 HWC [n,h,w,3], 9 <= h, w <= 4096 -> sig i32 [n][V][4], V = variants in {1, 2, 4, 8}.
+ *   Pixel value: y = 77 R + 150 G + 29 B (no shift).
+ *   Cells: a 9 x 9 grid.  Cell row r covers image rows [(r*h + 4) / 9, ((r+1)*h + 4) / 9) in C integer division,
+ *   cell column c the columns [(c*w + 4) / 9, ((c+1)*w + 4) / 9).  The bounds are mirror-symmetric, b(9-c) = w - b(c),
+ *   and every cell holds at least floor(w/9) >= 1 columns: the grid of a mirrored image is exactly the mirrored grid.
+ *   Per cell: sum (64 bits) of y over its pixels and cnt, the number of its pixels.
+ *   darker(a, b) = sum_a * cnt_b < sum_b * cnt_a in 64-bit arithmetic: strict, a tie gives 0.  At 4096 x 4096 a cell
+ *   has at most 456 * 456 pixels of at most 65,280 each: a product stays below 2.83e15 < 2^63.
+ *   Variant s, with h = s & 1, v = (s >> 1) & 1, t = (s >> 2) & 1 (applied to sums and counts alike):
+ *     G_s[r][c] = G[r1][c1],  (r0, c0) = t ? (c, r) : (r, c),  r1 = v ? 8 - r0 : r0,  c1 = h ? 8 - c0 : c0.
+ *   Variants 0 .. V-1 are written.  Variant 1 is exactly the signature of the left-right mirrored image; with h == w
+ *   the eight variants are the signatures of the eight flips and quarter turns.
+ *   Signature: 128 bits; bit 8r + c (r, c in 0..7) = darker(G_s[r][c], G_s[r][c+1]), bit 64 + 8r + c =
+ *   darker(G_s[r][c], G_s[r+1][c]); bit k lives in word k / 32 at position k % 32.
+ *   One workgroup per image, which is read once; no global atomics.
+ *   Refused before any launch: null buffers, n <= 0, h or w outside 9..4096, V not in {1, 2, 4, 8}.
+ *
+ * lf_hamming_pairs_count / lf_hamming_pairs_fill: a = na signatures of 4 int32, row i at a + i * a_stride (a_stride
+ * >= 4, in int32: variant 0 of an [na][Va][4] array has a_stride = 4 * Va); b i32 [nb][V][4] on a 16-byte boundary.
+ *   distance(i, j) = min over s < V of popcount(a_i xor b_{j,s}); s = the lowest variant reaching the minimum.
+ *   A pair is reported when distance <= threshold (0..128); with self != 0 (a is variant 0 of b, na == nb) only
+ *   pairs with i < j.
+ *   The columns j are cut into chunks = lf_hamming_pairs_chunks(na, nb) runs (0: bad arguments), which depends on
+ *   (na, nb) alone.  count writes counts i32 [na][chunks], the matches of row i in chunk k.  fill takes offsets i64
+ *   [na][chunks], the EXCLUSIVE running sum of counts in that order (i major, chunk minor), and writes out i32
+ *   [total][4] on a 16-byte boundary: rows {i, j, distance, s} in ascending (i, j) order.  Nothing is appended
+ *   through an atomic: the same input gives the same rows in the same places.
+ *   Refused before any launch: null buffers, na or nb <= 0, V not in {1, 2, 4, 8}, threshold outside 0..128,
+ *   a_stride < 4, a misaligned buffer, self with na != nb, a chunks argument other than lf_hamming_pairs_chunks.
+ *   The launch geometry, for callers and tests that want to reason about it: a workgroup holds lf_hamming_pairs_rows()
+ *   rows of a and stages lf_hamming_pairs_tile() columns of b at a time; a chunk is ceil(ceil(nb / tile) / chunks)
+ *   whole tiles of columns. */
+int lf_dhash128_u8(const uint8_t* in, int32_t* sig, int n, int h, int w, int variants, lf_stream_t stream);
+int lf_hamming_pairs_tile(void);
+int lf_hamming_pairs_rows(void);
+int lf_hamming_pairs_chunks(int na, int nb);
+int lf_hamming_pairs_count(const int32_t* a, long long a_stride, int na, const int32_t* b, int nb, int variants,
+                           int threshold, int self, int32_t* counts, int chunks, lf_stream_t stream);
+int lf_hamming_pairs_fill(const int32_t* a, long long a_stride, int na, const int32_t* b, int nb, int variants,
+                          int threshold, int self, const long long* offsets, int chunks, int32_t* out,
+                          lf_stream_t stream);
+
 /* ---- input stage ----------------------------------------------------------- */
 /* u8 HWC -> f32 NCHW with the model's train-time augmentation fused (cnn.py:74-86):
  * keras RandomFlip("horizontal") -> RandomRotation (bilinear, fill_mode="reflect") ->

@@ -159,6 +159,12 @@ SIGNATURES = {
     "lf_calib_stats_workspace": [c_int, c_int, c_int],
     "lf_calib_stats": [P, P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_size_t, P],
     "lf_calib_apply_f32": [P, c_double, P, P, P, c_int, c_int, P],
+    "lf_dhash128_u8": [P, P, c_int, c_int, c_int, c_int, P],
+    "lf_hamming_pairs_tile": [],
+    "lf_hamming_pairs_rows": [],
+    "lf_hamming_pairs_chunks": [c_int, c_int],
+    "lf_hamming_pairs_count": [P, C.c_longlong, c_int, P, c_int, c_int, c_int, c_int, P, c_int, P],
+    "lf_hamming_pairs_fill": [P, C.c_longlong, c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P],
     "lf_scale_shift_act_f32": [P, P, c_int, c_int, c_int, P, P, c_int, P],
     "lf_bn_workspace": [c_int],
     "lf_bn_train_stats_f32": [P, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P, P, P, P,

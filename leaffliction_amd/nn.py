@@ -787,6 +787,84 @@ def calib_apply(probs: torch.Tensor, beta, out: Optional[torch.Tensor] = None
     return out, conf, top
 
 
+DHASH_VARIANTS = (1, 2, 4, 8)
+DHASH_MIN_SIDE, DHASH_MAX_SIDE = 9, 4096
+
+
+def dhash128(x_u8: torch.Tensor, variants: int = 2) -> torch.Tensor:
+    """128-bit difference hashes of a batch (lf_dhash128_u8; the rule: include/leafhip.h): x_u8 uint8 [N,H,W,3] on the
+    GPU with 9 <= H, W <= 4096 -> int32 [N,V,4], variant s < V the signature of the flipped / turned cell grid (1: the
+    mirrored image)."""
+    if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3 \
+            or not x_u8.is_contiguous() or not x_u8.is_cuda:
+        raise ValueError("dhash128.x: a contiguous uint8 [N,H,W,3] tensor on the GPU expected")
+    n, h, w, _c = x_u8.shape
+    if not (DHASH_MIN_SIDE <= h <= DHASH_MAX_SIDE and DHASH_MIN_SIDE <= w <= DHASH_MAX_SIDE):
+        raise ValueError(f"dhash128.x: H={h}, W={w} (each {DHASH_MIN_SIDE}..{DHASH_MAX_SIDE})")
+    if variants not in DHASH_VARIANTS:
+        raise ValueError(f"dhash128: variants={variants!r} (one of {DHASH_VARIANTS})")
+    sig = torch.empty((n, int(variants), 4), dtype=torch.int32, device=x_u8.device)
+    if n:
+        _lib.call("lf_dhash128_u8", x_u8.data_ptr(), sig.data_ptr(), n, h, w, int(variants), _stream())
+    return sig
+
+
+def hamming_pairs_geometry(na: int, nb: int) -> Tuple[int, int, int, int]:
+    """How lf_hamming_pairs_* walk na rows against nb columns, from the library: (rows of `a` per workgroup, columns of
+    `b` staged at a time, chunks the columns are cut into, columns per chunk — whole tiles)."""
+    lib = _lib.load()
+    rows, tile, chunks = lib.lf_hamming_pairs_rows(), lib.lf_hamming_pairs_tile(), lib.lf_hamming_pairs_chunks(na, nb)
+    tiles = -(-nb // tile)
+    return rows, tile, chunks, -(-tiles // chunks) * tile
+
+
+def _signatures(who: str, sig: torch.Tensor) -> Tuple[int, int]:
+    _chk(sig, torch.int32, who, 3)
+    n, v, words = sig.shape
+    if words != 4 or v not in DHASH_VARIANTS:
+        raise ValueError(f"{who}: int32 [n,V,4] with V one of {DHASH_VARIANTS} expected, got {tuple(sig.shape)}")
+    return n, v
+
+
+def hamming_pairs(sig: torch.Tensor, threshold: int, other: Optional[torch.Tensor] = None,
+                  max_pairs: int = 1 << 24) -> torch.Tensor:
+    """All pairs of signatures within `threshold` bits (lf_hamming_pairs_count -> scan -> lf_hamming_pairs_fill; the
+    rule: include/leafhip.h): sig int32 [n,V,4] on the GPU -> int32 [m,4] rows {i, j, distance, s} in ascending (i, j)
+    order, the distance the minimum over the V variants of column j and s the lowest variant reaching it.  other=None:
+    rows are variant 0 of `sig` itself and only i < j is reported; else the rows are variant 0 of `other` [na,Va,4].
+    Raises ValueError naming the total when more than `max_pairs` pairs match, before anything of that size is
+    allocated.  One device-to-host sync (the total)."""
+    nb, v = _signatures("hamming_pairs.sig", sig)
+    threshold = int(threshold)
+    if not 0 <= threshold <= 128:
+        raise ValueError(f"hamming_pairs: threshold={threshold} (0..128)")
+    rows = sig if other is None else other
+    if other is not None:
+        _signatures("hamming_pairs.other", other)
+        if other.device != sig.device:
+            raise ValueError(f"hamming_pairs.other: expected a tensor on {sig.device}, got {other.device}")
+    na, va = rows.shape[0], rows.shape[1]
+    out = torch.empty((0, 4), dtype=torch.int32, device=sig.device)
+    if na == 0 or nb == 0:
+        return out
+    lib = _lib.load()
+    chunks = lib.lf_hamming_pairs_chunks(na, nb)
+    counts = torch.empty((na, chunks), dtype=torch.int32, device=sig.device)
+    args = (rows.data_ptr(), 4 * va, na, sig.data_ptr(), nb, v, threshold, 1 if other is None else 0)
+    _lib.call("lf_hamming_pairs_count", *args, counts.data_ptr(), chunks, _stream())
+    ends = torch.cumsum(counts.view(-1), 0, dtype=torch.int64)
+    total = int(ends[-1].item())
+    if total > int(max_pairs):
+        raise ValueError(f"hamming_pairs: {total} pairs within {threshold} bits, more than max_pairs={int(max_pairs)}"
+                         f" (lower the threshold, or raise max_pairs)")
+    if total == 0:
+        return out
+    offsets = (ends - counts.view(-1)).contiguous()
+    out = torch.empty((total, 4), dtype=torch.int32, device=sig.device)
+    _lib.call("lf_hamming_pairs_fill", *args, offsets.data_ptr(), chunks, out.data_ptr(), _stream())
+    return out
+
+
 def scale_shift_act(x, scale, shift, relu: bool, out=None):
     _chk(x, _F32, "scale_shift_act.x", 4)
     n, c, h, w = x.shape
