@@ -10,6 +10,7 @@
 // arithmetic below restates Python / Pillow expressions whose mul and add round
 // separately.
 #include "lf_common.h"
+#include "lf_wave.h"
 
 namespace {
 
@@ -736,9 +737,7 @@ __global__ __launch_bounds__(kBlock) void hsv_stats_kernel(const uint8_t* __rest
     }
 #pragma unroll
     for (int i = 0; i < LF_HSV_NCOUNTS; ++i) {
-        unsigned v = cnt[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        const unsigned v = lf::wave_sum(cnt[i]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&lc[i], v);
     }
     __syncthreads();

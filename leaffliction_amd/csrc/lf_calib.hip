@@ -14,14 +14,18 @@
 #include <math.h>
 
 #include "lf_common.h"
+#include "lf_wave.h"
 
 namespace {
+
+using lf::kHeadMaxClasses;
+using lf::take_larger;
+using lf::wave_sum_all;
 
 constexpr int kWaves = 4;
 constexpr int kBlock = 64 * kWaves;
 constexpr int kMaxBetas = 8;
 constexpr int kMaxBins = 64;
-constexpr int kMaxClasses = 4096;   // the head's limit
 constexpr int kMaxGroups = 256;     // workgroups of a stats launch: one per CU
 constexpr int kSums = 5;            // nll, g, h, brier, conf
 
@@ -33,33 +37,13 @@ struct Betas {
 // fmaxf returns the other operand for a NaN: a NaN is read as FLT_MIN too
 __device__ __forceinline__ double zlog(float p) { return log((double)fmaxf(p, FLT_MIN)); }
 
-// the same sum in every lane of the 64-lane wave: both partners of a butterfly step add the same two values
-__device__ __forceinline__ double wave_sum_all(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// the larger of two (value, index) pairs; the lower index on equal values (np.argmax)
-__device__ __forceinline__ void take_larger(float& bv, int& bi, float ov, int oi) {
-    if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-    }
-}
-
 // The maximum of the input row and the lowest index that attains it, the same in every lane.  A row of NaNs alone
 // has no maximum: index 0, so that what is returned always indexes a class.
 __device__ __forceinline__ int row_argmax(const float* row, int c, int lane, float* best) {
     float bv = -INFINITY;
     int bi = INT_MAX;
     for (int j = lane; j < c; j += 64) take_larger(bv, bi, row[j], j);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        take_larger(bv, bi, ov, oi);
-    }
+    bi = lf::wave_argmax_all(bv, bi);
     *best = bv;
     return (unsigned)bi < (unsigned)c ? bi : 0;
 }
@@ -219,7 +203,7 @@ int stats_groups(int n) {
     return g < kMaxGroups ? g : kMaxGroups;
 }
 
-bool calib_dims_ok(int n, int c) { return n > 0 && c >= 1 && c <= kMaxClasses; }
+bool calib_dims_ok(int n, int c) { return n > 0 && c >= 1 && c <= kHeadMaxClasses; }
 
 }  // namespace
 
@@ -235,7 +219,7 @@ int lf_calib_stats(const float* probs, const int32_t* labels, int n, int c, cons
                    double* sums, int32_t* counts, int32_t* pred, int32_t* cm, void* ws, size_t ws_bytes,
                    lf_stream_t stream) {
     LF_REQUIRE(probs && labels && betas && sums && counts && ws, "lf_calib_stats: null buffer");
-    LF_REQUIRE(calib_dims_ok(n, c), "lf_calib_stats: bad dims n=%d c=%d (c in 1..%d)", n, c, kMaxClasses);
+    LF_REQUIRE(calib_dims_ok(n, c), "lf_calib_stats: bad dims n=%d c=%d (c in 1..%d)", n, c, kHeadMaxClasses);
     LF_REQUIRE(k >= 1 && k <= kMaxBetas, "lf_calib_stats: k=%d inverse temperatures (1..%d)", k, kMaxBetas);
     LF_REQUIRE(bins >= 1 && bins <= kMaxBins, "lf_calib_stats: bins=%d (1..%d)", bins, kMaxBins);
     Betas bt = {};
@@ -263,7 +247,7 @@ int lf_calib_stats(const float* probs, const int32_t* labels, int n, int c, cons
 int lf_calib_apply_f32(const float* probs, double beta, float* out, float* conf, int32_t* top, int n, int c,
                        lf_stream_t stream) {
     LF_REQUIRE(probs && out && conf && top, "lf_calib_apply: null buffer");
-    LF_REQUIRE(calib_dims_ok(n, c), "lf_calib_apply: bad dims n=%d c=%d (c in 1..%d)", n, c, kMaxClasses);
+    LF_REQUIRE(calib_dims_ok(n, c), "lf_calib_apply: bad dims n=%d c=%d (c in 1..%d)", n, c, kHeadMaxClasses);
     LF_REQUIRE(isfinite(beta) && beta > 0.0, "lf_calib_apply: beta is not finite and positive");
     const uintptr_t a = (uintptr_t)probs, b = (uintptr_t)out, bytes = (uintptr_t)n * c * sizeof(float);
     LF_REQUIRE(a == b || a + bytes <= b || b + bytes <= a,

@@ -10,8 +10,12 @@
 // once with the few KB of map in LDS.  No atomics anywhere: the sums over k are folded in a fixed order and a
 // maximum does not depend on its order, so two launches give the same bits.
 #include "lf_common.h"
+#include "lf_wave.h"
 
 namespace {
+
+using lf::Vec;
+using lf::widen;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
@@ -19,18 +23,6 @@ constexpr int kMaxSlots = 8;
 constexpr int kMaxK = 512;          // the M weight columns [K][8] take at most 16 KB of LDS
 constexpr int kOverlayIters = 4;    // pixel groups per thread: the map is staged once per 256 * 4 groups
 constexpr int kOverlayLdsMap = 8192;  // maps of up to this many values (32 KB) are staged in LDS
-
-__device__ __forceinline__ float widen(float v) { return v; }
-__device__ __forceinline__ float widen(uint16_t v) { return lf::bf16_up(v); }
-
-template <typename T, int V>
-using Vec = T __attribute__((ext_vector_type(V)));
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // One workgroup per image.  A lane owns V consecutive pixels (one 16-byte load of fp32, one 8-byte load of bf16;
 // V = 1: any h*w), the 64 lanes of a wave a tile of 64*V pixels, and the four waves split the channels into four
@@ -119,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void cam_maps_kernel(const T* __restrict__ 
     // peak: thread tid folded slot (tid + kBlock * r) / TP in round r, the same slot in every lane of a wave
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const float v = wave_max(pm[r]);
+        const float v = lf::wave_max_all(pm[r]);
         if (lane == 0) part[r * kWaves + wv] = v;
     }
     __syncthreads();

@@ -16,52 +16,24 @@
 #include <float.h>
 
 #include "lf_common.h"
+#include "lf_wave.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using lf::block_sum;
+using lf::kHeadMaxClasses;
+using lf::narrow;
+using lf::Vec;
+using lf::wave_max_all;
+using lf::wave_sum_all;
+using lf::widen;
+
+constexpr int kBlock = 256;   // block_sum's workgroup
 constexpr int kBnSplit = 64;  // partial sums per channel in the BN reductions
-
-// plane-kernel storage: float, or bf16 held as uint16_t
-__device__ __forceinline__ float widen(float v) { return v; }
-__device__ __forceinline__ float widen(uint16_t v) { return lf::bf16_up(v); }
-template <typename T>
-__device__ __forceinline__ T narrow(float v);
-template <>
-__device__ __forceinline__ float narrow<float>(float v) { return v; }
-template <>
-__device__ __forceinline__ uint16_t narrow<uint16_t>(float v) { return lf::bf16_down(v); }
-
-// V consecutive elements moved as one access (a native vector: an array in a struct lets the compiler
-// split the load and sink parts of it into a branch)
-template <typename T, int V>
-using Vec = T __attribute__((ext_vector_type(V)));
 
 // the route bytes of N consecutive pooled values as one integer (byte k = value k)
 template <int N>
 using RouteWord = std::conditional_t<N == 4, unsigned, std::conditional_t<N == 2, uint16_t, uint8_t>>;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// block-wide sum of up to 3 values; result valid in thread 0
-template <int K>
-__device__ __forceinline__ void block_sum(float (&v)[K], float* red /* [K][4] */) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = wave_sum(v[k]);
-        if (lane == 0) red[k * 4 + wid] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = red[k * 4] + red[k * 4 + 1] + red[k * 4 + 2] + red[k * 4 + 3];
-    }
-}
 
 // ---------------------------------------------------------------------------
 // input stage: u8 HWC -> [flip, rotate(bilinear, reflect), contrast] -> normalise -> f32 NCHW
@@ -270,8 +242,37 @@ __global__ __launch_bounds__(kBlock) void scale_shift_act_kernel(const float* __
 // ---------------------------------------------------------------------------
 // BatchNorm statistics (training): per-channel sum / sum of squares over N*H*W
 // ---------------------------------------------------------------------------
+// The BN reductions go through kBnSplit partial pairs per channel, part[C][kBnSplit][2]: a reduce kernel's thread 0
+// stores the pair of its slice, a finalizer adds a channel's pairs in double, in slice order.
+__device__ __forceinline__ void store_pair(float* __restrict__ part, int ch, int s, const float (&acc)[2]) {
+    part[((size_t)ch * kBnSplit + s) * 2] = acc[0];
+    part[((size_t)ch * kBnSplit + s) * 2 + 1] = acc[1];
+}
+__device__ __forceinline__ void sum_pairs(const float* __restrict__ part, int ch, double* s, double* q) {
+    double a = 0.0, b = 0.0;
+    for (int k = 0; k < kBnSplit; ++k) {
+        a += part[((size_t)ch * kBnSplit + k) * 2];
+        b += part[((size_t)ch * kBnSplit + k) * 2 + 1];
+    }
+    *s = a;
+    *q = b;
+}
+
+// The V terms of one load as one addend: V = 4 is (t0 + t1) + (t2 + t3), and a term that is a product contracts
+// with its own pair's sum, so the roundings do not depend on how the body around it is written.
+template <int V, class F>
+__device__ __forceinline__ float pair_fold(F&& term) {
+    static_assert(V == 1 || V == 4, "pair_fold: one element or two pairs");
+    if constexpr (V == 1)
+        return term(0);
+    else
+        return (term(0) + term(1)) + (term(2) + term(3));
+}
+
 // grid = (kBnSplit, C): workgroup (s, c) reduces the planes n = s, s+kBnSplit, ... of channel c
 // around a per-channel pivot (the first element) to keep sum-of-squares well conditioned.
+// V = elements per load (4 needs hw % 4 == 0).
+template <int V>
 __global__ __launch_bounds__(kBlock) void bn_stats_kernel(const float* __restrict__ y, int n, int c,
                                                           int hw, float* __restrict__ part) {
     __shared__ float red[8];
@@ -279,32 +280,20 @@ __global__ __launch_bounds__(kBlock) void bn_stats_kernel(const float* __restric
     const float pivot = y[(size_t)ch * hw];
     float acc[2] = {0.f, 0.f};
     for (int img = s; img < n; img += kBnSplit) {
-        const float* p = y + ((size_t)img * c + ch) * hw;
-        if ((hw & 3) == 0) {
-            const float4* p4 = reinterpret_cast<const float4*>(p);
-            for (int i = threadIdx.x; i < hw / 4; i += kBlock) {
-                const float4 v = p4[i];
-                const float a = v.x - pivot, b = v.y - pivot, cc = v.z - pivot, d = v.w - pivot;
-                acc[0] += (a + b) + (cc + d);
-                acc[1] += (a * a + b * b) + (cc * cc + d * d);
-            }
-        } else {
-            for (int i = threadIdx.x; i < hw; i += kBlock) {
-                const float a = p[i] - pivot;
-                acc[0] += a;
-                acc[1] += a * a;
-            }
+        const Vec<float, V>* p = reinterpret_cast<const Vec<float, V>*>(y + ((size_t)img * c + ch) * hw);
+        for (int i = threadIdx.x; i < hw / V; i += kBlock) {
+            const Vec<float, V> v = p[i];
+            float d[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) d[e] = v[e] - pivot;
+            acc[0] += pair_fold<V>([&](int e) { return d[e]; });
+            acc[1] += pair_fold<V>([&](int e) { return d[e] * d[e]; });
         }
     }
     block_sum<2>(acc, red);
-    if (threadIdx.x == 0) {
-        part[((size_t)ch * kBnSplit + s) * 2] = acc[0];
-        part[((size_t)ch * kBnSplit + s) * 2 + 1] = acc[1];
-    }
+    if (threadIdx.x == 0) store_pair(part, ch, s, acc);
 }
 
-// One thread per channel: combine partials in double, produce mean / invstd / scale / shift and
-// update the moving statistics (keras BatchNormalization: biased variance, momentum 0.99).
 // grid = (kBnSplit, C): workgroup (s, c) adds slice s of channel c's per-tile partial sums
 // (written by the convolution epilogue, lf_conv2d_stats_f32) in a fixed order.
 __global__ __launch_bounds__(kBlock) void bn_tile_reduce_kernel(const float* __restrict__ tile_part,
@@ -322,12 +311,11 @@ __global__ __launch_bounds__(kBlock) void bn_tile_reduce_kernel(const float* __r
         acc[1] += v.y;
     }
     block_sum<2>(acc, red);
-    if (threadIdx.x == 0) {
-        part[((size_t)ch * kBnSplit + s) * 2] = acc[0];
-        part[((size_t)ch * kBnSplit + s) * 2 + 1] = acc[1];
-    }
+    if (threadIdx.x == 0) store_pair(part, ch, s, acc);
 }
 
+// One thread per channel: combine partials in double, produce mean / invstd / scale / shift and
+// update the moving statistics (keras BatchNormalization: biased variance, momentum 0.99).
 // `pivot_src[ch * pivot_stride]` is the value the partial sums were taken about (null = 0).
 __global__ void bn_finalize_kernel(const float* __restrict__ pivot_src, int pivot_stride,
                                    const float* __restrict__ part, int c, double count, const float* __restrict__ gamma,
@@ -337,11 +325,8 @@ __global__ void bn_finalize_kernel(const float* __restrict__ pivot_src, int pivo
                                    float* __restrict__ scale_o, float* __restrict__ shift_o) {
     const int ch = blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= c) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < kBnSplit; ++k) {
-        s += part[((size_t)ch * kBnSplit + k) * 2];
-        q += part[((size_t)ch * kBnSplit + k) * 2 + 1];
-    }
+    double s, q;
+    sum_pairs(part, ch, &s, &q);
     const double pivot = pivot_src != nullptr ? (double)pivot_src[(size_t)ch * pivot_stride] : 0.0;
     const double dm = s / count;
     double var = q / count - dm * dm;
@@ -396,6 +381,7 @@ __device__ __forceinline__ float bn_dz1(float g, float y, float al, float ad, fl
     return dz;
 }
 
+template <int V>
 __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(BnBwdArgs a, float* __restrict__ part) {
     __shared__ float red[8];
     const int ch = blockIdx.y, s = blockIdx.x;
@@ -405,51 +391,24 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(BnBwdArgs a, floa
         const size_t base = ((size_t)img * a.c + ch) * a.hw;
         const float al = a.alpha ? a.alpha[img * a.c + ch] : 1.f;
         const float ad = a.addnc ? a.addnc[img * a.c + ch] : 0.f;
-        if ((a.hw & 3) == 0) {
-            const float4* g4 = reinterpret_cast<const float4*>(a.g + base);
-            const float4* y4 = reinterpret_cast<const float4*>(a.y + base);
-            for (int i = threadIdx.x; i < a.hw / 4; i += kBlock) {
-                const float4 g = g4[i], y = y4[i];
-                const float d0 = bn_dz1(g.x, y.x, al, ad, sc, sh, a.relu);
-                const float d1 = bn_dz1(g.y, y.y, al, ad, sc, sh, a.relu);
-                const float d2 = bn_dz1(g.z, y.z, al, ad, sc, sh, a.relu);
-                const float d3 = bn_dz1(g.w, y.w, al, ad, sc, sh, a.relu);
-                acc[0] += (d0 + d1) + (d2 + d3);
-                acc[1] += (d0 * ((y.x - mean) * invstd) + d1 * ((y.y - mean) * invstd)) +
-                          (d2 * ((y.z - mean) * invstd) + d3 * ((y.w - mean) * invstd));
-            }
-        } else {
-            for (int i = threadIdx.x; i < a.hw; i += kBlock) {
-                const float y = a.y[base + i];
-                const float dz = bn_dz1(a.g[base + i], y, al, ad, sc, sh, a.relu);
-                acc[0] += dz;
-                acc[1] += dz * ((y - mean) * invstd);
-            }
+        const Vec<float, V>* gv = reinterpret_cast<const Vec<float, V>*>(a.g + base);
+        const Vec<float, V>* yv = reinterpret_cast<const Vec<float, V>*>(a.y + base);
+        for (int i = threadIdx.x; i < a.hw / V; i += kBlock) {
+            const Vec<float, V> g = gv[i], y = yv[i];
+            float dz[V];
+#pragma unroll
+            for (int e = 0; e < V; ++e) dz[e] = bn_dz1(g[e], y[e], al, ad, sc, sh, a.relu);
+            acc[0] += pair_fold<V>([&](int e) { return dz[e]; });
+            acc[1] += pair_fold<V>([&](int e) { return dz[e] * ((y[e] - mean) * invstd); });
         }
     }
     block_sum<2>(acc, red);
-    if (threadIdx.x == 0) {
-        part[((size_t)ch * kBnSplit + s) * 2] = acc[0];
-        part[((size_t)ch * kBnSplit + s) * 2 + 1] = acc[1];
-    }
-}
-
-__global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int c,
-                                       float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= c) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < kBnSplit; ++k) {
-        s += part[((size_t)ch * kBnSplit + k) * 2];
-        q += part[((size_t)ch * kBnSplit + k) * 2 + 1];
-    }
-    dbeta[ch] = (float)s;
-    dgamma[ch] = (float)q;
+    if (threadIdx.x == 0) store_pair(part, ch, s, acc);
 }
 
 // dy = coef2*dz + coef3*y + coef4 with dz masked by y*coef0+coef1 > 0: the apply step as five
 // per-channel coefficients, for consumers that form dy while they read g and y.  One channel's five, from the
-// dgamma / dbeta just formed (the floats stored, so a producer that calls this gives bn_bwd_coef_kernel's bits).
+// dgamma / dbeta just formed (the floats stored).
 __device__ __forceinline__ void bn_bwd_coef1(int ch, int c, float mean, float invstd, float scale, float shift,
                                              float gamma, float dgamma, float dbeta, float inv_count,
                                              float* __restrict__ coef) {
@@ -462,40 +421,41 @@ __device__ __forceinline__ void bn_bwd_coef1(int ch, int c, float mean, float in
     coef[4 * c + ch] = k * (mean * invstd * mdzx - mdz);
 }
 
-__global__ void bn_bwd_coef_kernel(const float* __restrict__ mean, const float* __restrict__ invstd,
-                                   const float* __restrict__ scale, const float* __restrict__ shift,
-                                   const float* __restrict__ gamma, const float* __restrict__ dgamma,
-                                   const float* __restrict__ dbeta, float inv_count, int c,
-                                   float* __restrict__ coef) {
-    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= c) return;
-    bn_bwd_coef1(ch, c, mean[ch], invstd[ch], scale[ch], shift[ch], gamma[ch], dgamma[ch], dbeta[ch], inv_count, coef);
+// what every route to a channel's backward sums needs to end: scale, shift, gamma and inv_count are read only with coef
+struct BnBwdOut {
+    const float* mean;
+    const float* invstd;
+    const float* scale;
+    const float* shift;
+    const float* gamma;
+    float inv_count;
+    float* dgamma;
+    float* dbeta;
+    float* coef;   // [5][C] or null
+};
+
+// a channel's two sums stored, and with `coef` its five coefficients from the floats just stored
+__device__ __forceinline__ void bn_bwd_store(const BnBwdOut& o, int ch, int c, float db, float dg) {
+    o.dbeta[ch] = db;
+    o.dgamma[ch] = dg;
+    if (o.coef != nullptr)
+        bn_bwd_coef1(ch, c, o.mean[ch], o.invstd[ch], o.scale[ch], o.shift[ch], o.gamma[ch], dg, db, o.inv_count,
+                     o.coef);
 }
 
-// dbeta = sum d, dgamma = invstd * (sum d*y - mean * sum d) from the kBnSplit partial pairs
-// {sum d, sum d*y} (convolution-epilogue tile sums, lf_conv2d_bnbwd_f32), and the channel's five coefficients
-__global__ void bn_bwd_tiles_finalize_kernel(const float* __restrict__ part, int c,
-                                             const float* __restrict__ mean,
-                                             const float* __restrict__ invstd,
-                                             const float* __restrict__ scale,
-                                             const float* __restrict__ shift,
-                                             const float* __restrict__ gamma, float inv_count,
-                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                             float* __restrict__ coef) {
+// One thread per channel: dbeta = s and dgamma = q from the kBnSplit partial pairs {s, q} of bn_bwd_reduce_kernel
+// ({sum dz, sum dz*xhat}), or with about_mean from pairs {sum d, sum d*y} (convolution-epilogue tile sums,
+// lf_conv2d_bnbwd_f32), which become dgamma = invstd * (q - mean * s).
+__global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int c, int about_mean, BnBwdOut o) {
     const int ch = blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= c) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < kBnSplit; ++k) {
-        s += part[((size_t)ch * kBnSplit + k) * 2];
-        q += part[((size_t)ch * kBnSplit + k) * 2 + 1];
-    }
-    const float db = (float)s;
-    const float dg = (float)((q - (double)mean[ch] * s) * (double)invstd[ch]);
-    dbeta[ch] = db;
-    dgamma[ch] = dg;
-    bn_bwd_coef1(ch, c, mean[ch], invstd[ch], scale[ch], shift[ch], gamma[ch], dg, db, inv_count, coef);
+    double s, q;
+    sum_pairs(part, ch, &s, &q);
+    const double dg = about_mean ? (q - (double)o.mean[ch] * s) * (double)o.invstd[ch] : q;
+    bn_bwd_store(o, ch, c, (float)s, (float)dg);
 }
 
+template <int V>
 __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(BnBwdArgs a,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ dgamma,
@@ -509,25 +469,16 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(BnBwdArgs a,
     const float al = a.alpha ? a.alpha[plane] : 1.f;
     const float ad = a.addnc ? a.addnc[plane] : 0.f;
     const size_t base = (size_t)plane * a.hw;
-    if ((a.hw & 3) == 0) {
-        const float4* g4 = reinterpret_cast<const float4*>(a.g + base);
-        const float4* y4 = reinterpret_cast<const float4*>(a.y + base);
-        float4* o4 = reinterpret_cast<float4*>(dy + base);
-        for (int i = blockIdx.y * kBlock + threadIdx.x; i < a.hw / 4; i += gridDim.y * kBlock) {
-            const float4 g = g4[i], y = y4[i];
-            float4 o;
-            o.x = k * (bn_dz1(g.x, y.x, al, ad, sc, sh, a.relu) - mdz - ((y.x - mean) * invstd) * mdzx);
-            o.y = k * (bn_dz1(g.y, y.y, al, ad, sc, sh, a.relu) - mdz - ((y.y - mean) * invstd) * mdzx);
-            o.z = k * (bn_dz1(g.z, y.z, al, ad, sc, sh, a.relu) - mdz - ((y.z - mean) * invstd) * mdzx);
-            o.w = k * (bn_dz1(g.w, y.w, al, ad, sc, sh, a.relu) - mdz - ((y.w - mean) * invstd) * mdzx);
-            o4[i] = o;
-        }
-    } else {
-        for (int i = blockIdx.y * kBlock + threadIdx.x; i < a.hw; i += gridDim.y * kBlock) {
-            const float y = a.y[base + i];
-            const float dz = bn_dz1(a.g[base + i], y, al, ad, sc, sh, a.relu);
-            dy[base + i] = k * (dz - mdz - ((y - mean) * invstd) * mdzx);
-        }
+    const Vec<float, V>* gv = reinterpret_cast<const Vec<float, V>*>(a.g + base);
+    const Vec<float, V>* yv = reinterpret_cast<const Vec<float, V>*>(a.y + base);
+    Vec<float, V>* ov = reinterpret_cast<Vec<float, V>*>(dy + base);
+    for (int i = blockIdx.y * kBlock + threadIdx.x; i < a.hw / V; i += gridDim.y * kBlock) {
+        const Vec<float, V> g = gv[i], y = yv[i];
+        Vec<float, V> o;
+#pragma unroll
+        for (int e = 0; e < V; ++e)
+            o[e] = k * (bn_dz1(g[e], y[e], al, ad, sc, sh, a.relu) - mdz - ((y[e] - mean) * invstd) * mdzx);
+        ov[i] = o;
     }
 }
 
@@ -870,55 +821,26 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ 
 // dz = (g*alpha + add) * [y*scale+shift > 0],
 //   sum dz       = sum_n alpha*G0 + add*M0          G = tail_bwd plane sums {sum g*mask, sum g*mask*y}
 //   sum dz*xhat  = invstd * sum_n alpha*(G1 - mean*G0) + add*(M1 - mean*M0)   M = gap mask sums
-// one workgroup per channel, fixed-order double accumulation.  With `coef` the channel's five coefficients follow
-// (bn_bwd_coef1); scale, shift and gamma are read only then.
+// one workgroup per channel, fixed-order double accumulation, then bn_bwd_store.
 __global__ __launch_bounds__(kBlock) void bn_bwd_planes_kernel(const float* __restrict__ plane_g,
                                                                const float* __restrict__ plane_m,
                                                                const float* __restrict__ alpha,
-                                                               const float* __restrict__ addnc,
-                                                               const float* __restrict__ mean,
-                                                               const float* __restrict__ invstd, int n,
-                                                               int c, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta,
-                                                               const float* __restrict__ scale,
-                                                               const float* __restrict__ shift,
-                                                               const float* __restrict__ gamma, float inv_count,
-                                                               float* __restrict__ coef) {
-    __shared__ double red[2][kBlock / 64];
+                                                               const float* __restrict__ addnc, int n, int c,
+                                                               BnBwdOut o) {
+    __shared__ double red[8];
     const int ch = blockIdx.x;
-    const double mu = mean[ch];
-    double s0 = 0.0, s1 = 0.0;
+    const double mu = o.mean[ch];
+    double acc[2] = {0.0, 0.0};
     for (int img = threadIdx.x; img < n; img += kBlock) {
         const size_t pl = (size_t)img * c + ch;
         const double al = alpha ? alpha[pl] : 1.0, ad = addnc ? addnc[pl] : 0.0;
         const double g0 = plane_g[2 * pl], g1 = plane_g[2 * pl + 1];
         const double m0 = plane_m ? plane_m[2 * pl] : 0.0, m1 = plane_m ? plane_m[2 * pl + 1] : 0.0;
-        s0 += al * g0 + ad * m0;
-        s1 += al * (g1 - mu * g0) + ad * (m1 - mu * m0);
+        acc[0] += al * g0 + ad * m0;
+        acc[1] += al * (g1 - mu * g0) + ad * (m1 - mu * m0);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s0 += __shfl_down(s0, off, 64);
-        s1 += __shfl_down(s1, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = s0;
-        red[1][threadIdx.x >> 6] = s1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) {
-            a += red[0][k];
-            b += red[1][k];
-        }
-        const float db = (float)a;
-        const float dg = (float)(b * (double)invstd[ch]);
-        dbeta[ch] = db;
-        dgamma[ch] = dg;
-        if (coef != nullptr)
-            bn_bwd_coef1(ch, c, mean[ch], invstd[ch], scale[ch], shift[ch], gamma[ch], dg, db, inv_count, coef);
-    }
+    block_sum<2>(acc, red);
+    if (threadIdx.x == 0) bn_bwd_store(o, ch, c, (float)acc[0], (float)(acc[1] * (double)o.invstd[ch]));
 }
 
 // ---------------------------------------------------------------------------
@@ -953,19 +875,6 @@ __global__ void head_fwd_kernel(const float* __restrict__ feat, const float* __r
         }
         if (loss != nullptr) loss[n] = l;
     }
-}
-
-// The same value in every lane of the 64-lane wave (xor butterfly: both partners of a step add / compare the same
-// pair, so the lanes agree bit for bit).
-__device__ __forceinline__ float wave_sum_all(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max_all(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
 }
 
 // Distillation head: the head above plus the soft-target term at temperature T.
@@ -1073,27 +982,20 @@ __global__ __launch_bounds__(kBlock) void adam_norm_kernel(const float* __restri
                                                            const long long* __restrict__ offs,
                                                            const float* __restrict__ l2,
                                                            double* __restrict__ partial) {
-    __shared__ double red[kBlock / 64];
+    __shared__ double red[4];
     const int t = blockIdx.y;
     const long long b = offs[t], e = offs[t + 1];
     const long long per = (e - b + kNormSplit - 1) / kNormSplit;
     const long long s0 = b + per * blockIdx.x, s1 = s0 + per < e ? s0 + per : e;
     const float l2c = 2.f * l2[t];
-    double acc = 0.0;
+    double acc[1] = {0.0};
 #pragma unroll 4
     for (long long i = s0 + threadIdx.x; i < s1; i += kBlock) {
         const float gv = fmaf(l2c, p[i], g[i]);
-        acc += (double)gv * gv;
+        acc[0] += (double)gv * gv;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) s += red[k];
-        partial[(size_t)t * kNormSplit + blockIdx.x] = s;
-    }
+    block_sum<1>(acc, red);
+    if (threadIdx.x == 0) partial[(size_t)t * kNormSplit + blockIdx.x] = acc[0];
 }
 
 struct AdamArgs {
@@ -1178,6 +1080,78 @@ int head_bwd_launch(const char* what, const float* feat, const float* w, const f
     return lf::check_launch(what);
 }
 
+// lf_input_stage_f32 (mix8 == nullptr) and lf_input_stage_mix_f32: the contrast means, then the stage's kernel
+int input_stage_launch(const char* who, const uint8_t* in, float* out, int n, int h, int w, const float* aug4,
+                       const float* mix8, const float* mean3, const float* denom3, float* means_ws,
+                       lf_stream_t stream) {
+    LF_REQUIRE(in && out && aug4 && means_ws, "%s: null buffer", who);
+    LF_REQUIRE(n > 0 && h > 1 && w > 1, "%s: bad dims n=%d h=%d w=%d", who, n, h, w);
+    LF_REQUIRE((mean3 == nullptr) == (denom3 == nullptr), "%s: mean/denom must both be set", who);
+    LF_REQUIRE(n <= 65535, "%s: batch too large", who);
+    float m[3], d[3];
+    lf::norm_consts(mean3, denom3, m, d);
+    hipStream_t s = lf::as_stream(stream);
+    const dim3 grid(plane_grid(h * w), n);
+    aug_means_kernel<<<dim3(kMeanSplit, n), kBlock, 0, s>>>(in, aug4, means_ws, h, w);
+    if (mix8 == nullptr)
+        input_aug_kernel<<<grid, kBlock, 0, s>>>(in, out, aug4, means_ws, h, w, m[0], m[1], m[2], d[0], d[1], d[2]);
+    else
+        input_mix_kernel<<<grid, kBlock, 0, s>>>(in, out, aug4, mix8, means_ws, n, h, w, m[0], m[1], m[2], d[0], d[1],
+                                                 d[2]);
+    return lf::check_launch(who);
+}
+
+// LF_OK when a BN entry's workspace holds the kBnSplit partial pairs of its c channels
+int bn_workspace_ok(const char* who, size_t ws_bytes, int c) {
+    if (ws_bytes >= lf_bn_workspace(c)) return LF_OK;
+    lf::set_error("%s: workspace %zu < %zu", who, ws_bytes, lf_bn_workspace(c));
+    return LF_ERR_WORKSPACE;
+}
+
+// what the plane-sum route of BatchNorm's backward (plane_g, plane_m) asks of its arguments
+int bn_plane_rules(const char* who, const float* plane_g, const float* plane_m, const float* alpha_nc,
+                   const float* add_nc, int relu) {
+    LF_REQUIRE(plane_g != nullptr || plane_m == nullptr, "%s: plane_m needs plane_g", who);
+    LF_REQUIRE(plane_g == nullptr || relu != 0 || (alpha_nc == nullptr && add_nc == nullptr),
+               "%s: plane sums without a mask take no alpha / add", who);
+    LF_REQUIRE(plane_g == nullptr || add_nc == nullptr || plane_m != nullptr,
+               "%s: add_nc with plane sums needs plane_m", who);
+    return LF_OK;
+}
+
+// the g / y route to BatchNorm's backward sums: kBnSplit slices per channel, then the finalizer
+void bn_bwd_sums_launch(const BnBwdArgs& a, float* part, const BnBwdOut& o, hipStream_t s) {
+    auto reduce = a.hw % 4 == 0 ? bn_bwd_reduce_kernel<4> : bn_bwd_reduce_kernel<1>;
+    reduce<<<dim3(kBnSplit, a.c), kBlock, 0, s>>>(a, part);
+    bn_bwd_finalize_kernel<<<(a.c + 63) / 64, 64, 0, s>>>(part, a.c, 0, o);
+}
+
+// The rules both storage types of the residual tail share; the bf16 entries add their shape and alignment rules.
+template <typename T, int V>
+int tail_fwd_launch(const char* who, const TailArgs<T>& t, uint8_t* route, T* p, int n, lf_stream_t stream) {
+    LF_REQUIRE(t.y && t.sc && p, "%s: null buffer", who);
+    LF_REQUIRE((t.sc_scale == nullptr) == (t.sc_shift == nullptr), "%s: sc_scale/sc_shift", who);
+    LF_REQUIRE((t.a_scale == nullptr) == (t.a_shift == nullptr), "%s: a_scale/a_shift", who);
+    tail_fwd_kernel<T, V><<<dim3(n * t.c, plane_grid((t.h / 2) * (t.w / V))), kBlock, 0, lf::as_stream(stream)>>>(
+        t, route, p);
+    return lf::check_launch(who);
+}
+
+template <typename T, int V>
+int tail_bwd_launch(const char* who, const T* dp, const uint8_t* route, const T* y, const float* a_scale,
+                    const float* a_shift, const float* drop, T* dr, float* ds, float* plane_sums, const T* sc_y,
+                    float* sc_sums, int n, int c, int h, int w, lf_stream_t stream) {
+    LF_REQUIRE((sc_y == nullptr) == (sc_sums == nullptr), "%s: sc_y and sc_sums go together", who);
+    LF_REQUIRE(dp && route && dr, "%s: null buffer", who);
+    LF_REQUIRE(plane_sums == nullptr || (y != nullptr && a_scale != nullptr),
+               "%s: plane_sums needs y and a_scale/a_shift", who);
+    LF_REQUIRE((y == nullptr) == (ds == nullptr && plane_sums == nullptr), "%s: y goes with ds / plane_sums", who);
+    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "%s: a_scale/a_shift", who);
+    tail_bwd_kernel<T, V><<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr, ds,
+                                                                       plane_sums, sc_y, sc_sums, c, h, w);
+    return lf::check_launch(who);
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1188,46 +1162,19 @@ extern "C" {
 int lf_input_stage_f32(const uint8_t* in, float* out, int n, int h, int w, const float* aug4,
                        const float* mean3, const float* denom3, float* means_ws,
                        lf_stream_t stream) {
-    LF_REQUIRE(in && out && aug4 && means_ws, "lf_input_stage: null buffer");
-    LF_REQUIRE(n > 0 && h > 1 && w > 1, "lf_input_stage: bad dims n=%d h=%d w=%d", n, h, w);
-    LF_REQUIRE((mean3 == nullptr) == (denom3 == nullptr), "lf_input_stage: mean/denom must both be set");
-    LF_REQUIRE(n <= 65535, "lf_input_stage: batch too large");
-    float m[3] = {0, 0, 0}, d[3] = {1, 1, 1};
-    if (mean3)
-        for (int c = 0; c < 3; ++c) {
-            m[c] = mean3[c];
-            d[c] = denom3[c];
-        }
-    hipStream_t s = lf::as_stream(stream);
-    aug_means_kernel<<<dim3(kMeanSplit, n), kBlock, 0, s>>>(in, aug4, means_ws, h, w);
-    input_aug_kernel<<<dim3(plane_grid(h * w), n), kBlock, 0, s>>>(in, out, aug4, means_ws, h, w,
-                                                                   m[0], m[1], m[2], d[0], d[1], d[2]);
-    return lf::check_launch("lf_input_stage");
+    return input_stage_launch("lf_input_stage", in, out, n, h, w, aug4, nullptr, mean3, denom3, means_ws, stream);
 }
 
 int lf_input_stage_mix_f32(const uint8_t* in, float* out, int n, int h, int w, const float* aug4,
                            const float* mix8, const float* mean3, const float* denom3, float* means_ws,
                            lf_stream_t stream) {
-    LF_REQUIRE(in && out && aug4 && mix8 && means_ws, "lf_input_stage_mix: null buffer");
-    LF_REQUIRE(n > 0 && h > 1 && w > 1, "lf_input_stage_mix: bad dims n=%d h=%d w=%d", n, h, w);
-    LF_REQUIRE((mean3 == nullptr) == (denom3 == nullptr), "lf_input_stage_mix: mean/denom must both be set");
-    LF_REQUIRE(n <= 65535, "lf_input_stage_mix: batch too large");
-    float m[3] = {0, 0, 0}, d[3] = {1, 1, 1};
-    if (mean3)
-        for (int c = 0; c < 3; ++c) {
-            m[c] = mean3[c];
-            d[c] = denom3[c];
-        }
-    hipStream_t s = lf::as_stream(stream);
-    aug_means_kernel<<<dim3(kMeanSplit, n), kBlock, 0, s>>>(in, aug4, means_ws, h, w);
-    input_mix_kernel<<<dim3(plane_grid(h * w), n), kBlock, 0, s>>>(in, out, aug4, mix8, means_ws, n, h, w,
-                                                                   m[0], m[1], m[2], d[0], d[1], d[2]);
-    return lf::check_launch("lf_input_stage_mix");
+    LF_REQUIRE(mix8, "lf_input_stage_mix: null buffer");
+    return input_stage_launch("lf_input_stage_mix", in, out, n, h, w, aug4, mix8, mean3, denom3, means_ws, stream);
 }
 
 int lf_mix_targets_f32(const float* y, const float* mix8, float* out, int n, int c, lf_stream_t stream) {
     LF_REQUIRE(y && mix8 && out, "lf_mix_targets: null buffer");
-    LF_REQUIRE(n > 0 && n <= 65535 && c > 0 && c <= 4096, "lf_mix_targets: bad dims n=%d c=%d", n, c);
+    LF_REQUIRE(n > 0 && n <= 65535 && c > 0 && c <= kHeadMaxClasses, "lf_mix_targets: bad dims n=%d c=%d", n, c);
     LF_REQUIRE(out + (size_t)n * c <= y || y + (size_t)n * c <= out, "lf_mix_targets: out overlaps y");
     mix_targets_kernel<<<(unsigned)(((size_t)n * c + kBlock - 1) / kBlock), kBlock, 0, lf::as_stream(stream)>>>(
         y, mix8, out, n, c);
@@ -1260,13 +1207,11 @@ int lf_bn_train_stats_f32(const float* y, int n, int c, int hw, const float* gam
                    workspace,
                "lf_bn_train_stats: null buffer");
     LF_REQUIRE(n > 0 && c > 0 && hw > 0 && c <= 65535, "lf_bn_train_stats: bad dims n=%d c=%d hw=%d", n, c, hw);
-    if (ws_bytes < lf_bn_workspace(c)) {
-        lf::set_error("lf_bn_train_stats: workspace %zu < %zu", ws_bytes, lf_bn_workspace(c));
-        return LF_ERR_WORKSPACE;
-    }
+    if (int err = bn_workspace_ok("lf_bn_train_stats", ws_bytes, c)) return err;
     hipStream_t s = lf::as_stream(stream);
     float* part = static_cast<float*>(workspace);
-    bn_stats_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(y, n, c, hw, part);
+    auto stats = hw % 4 == 0 ? bn_stats_kernel<4> : bn_stats_kernel<1>;
+    stats<<<dim3(kBnSplit, c), kBlock, 0, s>>>(y, n, c, hw, part);
     bn_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(y, hw, part, c, (double)n * hw, gamma, beta,
                                                    moving_mean, moving_var, momentum, eps, mean,
                                                    invstd, scale, shift);
@@ -1283,10 +1228,7 @@ int lf_bn_train_stats_tiles_f32(const float* tile_part, long long tiles, int n, 
                "lf_bn_train_stats_tiles: null buffer");
     LF_REQUIRE(n > 0 && c > 0 && hw > 0 && c <= 65535 && tiles > 0,
                "lf_bn_train_stats_tiles: bad dims n=%d c=%d hw=%d tiles=%lld", n, c, hw, tiles);
-    if (ws_bytes < lf_bn_workspace(c)) {
-        lf::set_error("lf_bn_train_stats_tiles: workspace %zu < %zu", ws_bytes, lf_bn_workspace(c));
-        return LF_ERR_WORKSPACE;
-    }
+    if (int err = bn_workspace_ok("lf_bn_train_stats_tiles", ws_bytes, c)) return err;
     hipStream_t s = lf::as_stream(stream);
     float* part = static_cast<float*>(workspace);
     bn_tile_reduce_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(tile_part, tiles, part);
@@ -1315,31 +1257,24 @@ int lf_bn_bwd_f32(const float* g, const float* alpha_nc, const float* add_nc, co
     LF_REQUIRE(g && y && mean && invstd && scale && shift && gamma && dy && dgamma && dbeta && workspace,
                "lf_bn_bwd: null buffer");
     LF_REQUIRE(!have_sums || plane_g == nullptr, "lf_bn_bwd: have_sums excludes plane sums");
-    LF_REQUIRE(plane_g != nullptr || plane_m == nullptr, "lf_bn_bwd: plane_m needs plane_g");
-    LF_REQUIRE(plane_g == nullptr || relu != 0 || (alpha_nc == nullptr && add_nc == nullptr),
-               "lf_bn_bwd: plane sums without a mask take no alpha / add");
-    LF_REQUIRE(plane_g == nullptr || add_nc == nullptr || plane_m != nullptr,
-               "lf_bn_bwd: add_nc with plane sums needs plane_m");
+    if (int err = bn_plane_rules("lf_bn_bwd", plane_g, plane_m, alpha_nc, add_nc, relu)) return err;
     LF_REQUIRE(n > 0 && c > 0 && hw > 0 && c <= 65535 && (long long)n * c < (1LL << 31),
                "lf_bn_bwd: bad dims n=%d c=%d hw=%d", n, c, hw);
-    if (ws_bytes < lf_bn_workspace(c)) {
-        lf::set_error("lf_bn_bwd: workspace %zu < %zu", ws_bytes, lf_bn_workspace(c));
-        return LF_ERR_WORKSPACE;
-    }
-    BnBwdArgs a{g, alpha_nc, add_nc, y, mean, invstd, scale, shift, relu, n, c, hw};
+    if (int err = bn_workspace_ok("lf_bn_bwd", ws_bytes, c)) return err;
+    const BnBwdArgs a{g, alpha_nc, add_nc, y, mean, invstd, scale, shift, relu, n, c, hw};
+    const BnBwdOut o{mean, invstd, scale, shift, gamma, 0.f, dgamma, dbeta, nullptr};
     hipStream_t s = lf::as_stream(stream);
-    float* part = static_cast<float*>(workspace);
+    const int v = hw % 4 == 0 ? 4 : 1;
     if (have_sums) {
         // dgamma / dbeta already hold the two channel sums (lf_bn_bwd_sums*_f32)
     } else if (plane_g != nullptr) {
-        bn_bwd_planes_kernel<<<c, kBlock, 0, s>>>(plane_g, plane_m, alpha_nc, add_nc, mean, invstd, n, c,
-                                                  dgamma, dbeta, nullptr, nullptr, nullptr, 0.f, nullptr);
+        bn_bwd_planes_kernel<<<c, kBlock, 0, s>>>(plane_g, plane_m, alpha_nc, add_nc, n, c, o);
     } else {
-        bn_bwd_reduce_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(a, part);
-        bn_bwd_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, dgamma, dbeta);
+        bn_bwd_sums_launch(a, static_cast<float*>(workspace), o, s);
     }
-    bn_bwd_apply_kernel<<<dim3(n * c, plane_grid((hw & 3) ? hw : hw / 4)), kBlock, 0, s>>>(
-        a, gamma, dgamma, dbeta, 1.0f / ((float)n * (float)hw), dy);
+    auto apply = v == 4 ? bn_bwd_apply_kernel<4> : bn_bwd_apply_kernel<1>;
+    apply<<<dim3(n * c, plane_grid(hw / v)), kBlock, 0, s>>>(a, gamma, dgamma, dbeta, 1.0f / ((float)n * (float)hw),
+                                                            dy);
     return lf::check_launch("lf_bn_bwd");
 }
 
@@ -1353,27 +1288,16 @@ int lf_bn_bwd_sums_f32(const float* g, const float* alpha_nc, const float* add_n
     LF_REQUIRE(plane_g != nullptr || (g != nullptr && y != nullptr), "lf_bn_bwd_sums: g / y missing");
     LF_REQUIRE(n > 0 && c > 0 && hw > 0 && c <= 65535 && (long long)n * c < (1LL << 31),
                "lf_bn_bwd_sums: bad dims n=%d c=%d hw=%d", n, c, hw);
-    LF_REQUIRE(plane_g != nullptr || plane_m == nullptr, "lf_bn_bwd_sums: plane_m needs plane_g");
-    LF_REQUIRE(plane_g == nullptr || relu != 0 || (alpha_nc == nullptr && add_nc == nullptr),
-               "lf_bn_bwd_sums: plane sums without a mask take no alpha / add");
-    LF_REQUIRE(plane_g == nullptr || add_nc == nullptr || plane_m != nullptr,
-               "lf_bn_bwd_sums: add_nc with plane sums needs plane_m");
-    if (ws_bytes < lf_bn_workspace(c)) {
-        lf::set_error("lf_bn_bwd_sums: workspace %zu < %zu", ws_bytes, lf_bn_workspace(c));
-        return LF_ERR_WORKSPACE;
-    }
+    if (int err = bn_plane_rules("lf_bn_bwd_sums", plane_g, plane_m, alpha_nc, add_nc, relu)) return err;
+    if (int err = bn_workspace_ok("lf_bn_bwd_sums", ws_bytes, c)) return err;
     hipStream_t s = lf::as_stream(stream);
-    const float inv_count = 1.0f / ((float)n * (float)hw);
-    if (plane_g != nullptr) {  // the plane route forms the coefficients where it forms the sums
-        bn_bwd_planes_kernel<<<c, kBlock, 0, s>>>(plane_g, plane_m, alpha_nc, add_nc, mean, invstd, n, c,
-                                                  dgamma, dbeta, scale, shift, gamma, inv_count, coef);
+    // every route forms the coefficients where it forms the sums
+    const BnBwdOut o{mean, invstd, scale, shift, gamma, 1.0f / ((float)n * (float)hw), dgamma, dbeta, coef};
+    if (plane_g != nullptr) {
+        bn_bwd_planes_kernel<<<c, kBlock, 0, s>>>(plane_g, plane_m, alpha_nc, add_nc, n, c, o);
     } else {
-        BnBwdArgs a{g, alpha_nc, add_nc, y, mean, invstd, scale, shift, relu, n, c, hw};
-        float* part = static_cast<float*>(workspace);
-        bn_bwd_reduce_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(a, part);
-        bn_bwd_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, dgamma, dbeta);
-        bn_bwd_coef_kernel<<<(c + 63) / 64, 64, 0, s>>>(mean, invstd, scale, shift, gamma, dgamma, dbeta, inv_count,
-                                                       c, coef);
+        const BnBwdArgs a{g, alpha_nc, add_nc, y, mean, invstd, scale, shift, relu, n, c, hw};
+        bn_bwd_sums_launch(a, static_cast<float*>(workspace), o, s);
     }
     return lf::check_launch("lf_bn_bwd_sums");
 }
@@ -1387,15 +1311,12 @@ int lf_bn_bwd_sums_tiles_f32(const float* tile_part, long long tiles, const floa
                "lf_bn_bwd_sums_tiles: null buffer");
     LF_REQUIRE(n > 0 && c > 0 && hw > 0 && c <= 65535 && tiles > 0,
                "lf_bn_bwd_sums_tiles: bad dims n=%d c=%d hw=%d tiles=%lld", n, c, hw, tiles);
-    if (ws_bytes < lf_bn_workspace(c)) {
-        lf::set_error("lf_bn_bwd_sums_tiles: workspace %zu < %zu", ws_bytes, lf_bn_workspace(c));
-        return LF_ERR_WORKSPACE;
-    }
+    if (int err = bn_workspace_ok("lf_bn_bwd_sums_tiles", ws_bytes, c)) return err;
     hipStream_t s = lf::as_stream(stream);
     float* part = static_cast<float*>(workspace);
+    const BnBwdOut o{mean, invstd, scale, shift, gamma, 1.0f / ((float)n * (float)hw), dgamma, dbeta, coef};
     bn_tile_reduce_kernel<<<dim3(kBnSplit, c), kBlock, 0, s>>>(tile_part, tiles, part);
-    bn_bwd_tiles_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, mean, invstd, scale, shift, gamma,
-                                                             1.0f / ((float)n * (float)hw), dgamma, dbeta, coef);
+    bn_bwd_finalize_kernel<<<(c + 63) / 64, 64, 0, s>>>(part, c, 1, o);
     return lf::check_launch("lf_bn_bwd_sums_tiles");
 }
 
@@ -1483,80 +1404,56 @@ int lf_block_tail_fwd_f32(const float* y, const float* a_scale, const float* a_s
                           const float* s, const float* sc, const float* sc_scale,
                           const float* sc_shift, int sc_relu, const float* drop, uint8_t* route,
                           float* p, int n, int c, int h, int w, lf_stream_t stream) {
-    LF_REQUIRE(y && sc && route && p, "lf_block_tail_fwd: null buffer");
+    LF_REQUIRE(route, "lf_block_tail_fwd: null buffer");
     LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 1 && (long long)n * c < (1LL << 31),
                "lf_block_tail_fwd: bad dims n=%d c=%d h=%d w=%d", n, c, h, w);
     LF_REQUIRE((w & 1) == 0, "lf_block_tail_fwd: width must be even");
-    LF_REQUIRE((sc_scale == nullptr) == (sc_shift == nullptr), "lf_block_tail_fwd: sc_scale/sc_shift");
-    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_fwd: a_scale/a_shift");
-    TailArgs<float> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
-    const int v = w % 4 == 0 ? 4 : 2;
-    auto kernel = v == 4 ? tail_fwd_kernel<float, 4> : tail_fwd_kernel<float, 2>;
-    kernel<<<dim3(n * c, plane_grid((h / 2) * (w / v))), kBlock, 0, lf::as_stream(stream)>>>(t, route, p);
-    return lf::check_launch("lf_block_tail_fwd");
+    const TailArgs<float> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
+    auto launch = w % 4 == 0 ? tail_fwd_launch<float, 4> : tail_fwd_launch<float, 2>;
+    return launch("lf_block_tail_fwd", t, route, p, n, stream);
 }
 
 int lf_block_tail_fwd_train_bf16(const uint16_t* y, const float* a_scale, const float* a_shift, const float* s,
                                  const uint16_t* sc, const float* sc_scale, const float* sc_shift, int sc_relu,
                                  const float* drop, uint8_t* route, uint16_t* pooled, int n, int c, int h, int w,
                                  lf_stream_t stream) {
-    LF_REQUIRE(y && sc && pooled, "lf_block_tail_fwd_train_bf16: null buffer");
     LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 3 && h % 2 == 0 && w % 4 == 0 && (long long)n * c < (1LL << 31),
                "lf_block_tail_fwd_train_bf16: bad dims n=%d c=%d h=%d w=%d (h even, w %% 4 == 0)", n, c, h, w);
-    LF_REQUIRE((sc_scale == nullptr) == (sc_shift == nullptr), "lf_block_tail_fwd_train_bf16: sc_scale/sc_shift");
-    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_fwd_train_bf16: a_scale/a_shift");
     LF_REQUIRE(aligned(y, 8) && aligned(sc, 8) && aligned(pooled, 4) && aligned(route, 2),
                "lf_block_tail_fwd_train_bf16: misaligned buffer");
-    TailArgs<uint16_t> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
-    const int v = w % 8 == 0 && aligned(y, 16) && aligned(sc, 16) && aligned(pooled, 8) && aligned(route, 4) ? 8 : 4;
-    auto kernel = v == 8 ? tail_fwd_kernel<uint16_t, 8> : tail_fwd_kernel<uint16_t, 4>;
-    kernel<<<dim3(n * c, plane_grid((h / 2) * (w / v))), kBlock, 0, lf::as_stream(stream)>>>(t, route, pooled);
-    return lf::check_launch("lf_block_tail_fwd_train_bf16");
+    const TailArgs<uint16_t> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
+    const bool v8 = w % 8 == 0 && aligned(y, 16) && aligned(sc, 16) && aligned(pooled, 8) && aligned(route, 4);
+    auto launch = v8 ? tail_fwd_launch<uint16_t, 8> : tail_fwd_launch<uint16_t, 4>;
+    return launch("lf_block_tail_fwd_train_bf16", t, route, pooled, n, stream);
 }
 
 int lf_block_tail_bwd_f32(const float* dp, const uint8_t* route, const float* y,
                           const float* a_scale, const float* a_shift, const float* drop, float* dr,
                           float* ds, float* plane_sums, const float* sc_y, float* sc_sums, int n,
                           int c, int h, int w, lf_stream_t stream) {
-    LF_REQUIRE((sc_y == nullptr) == (sc_sums == nullptr), "lf_block_tail_bwd: sc_y and sc_sums go together");
-    LF_REQUIRE(dp && route && dr, "lf_block_tail_bwd: null buffer");
-    LF_REQUIRE(plane_sums == nullptr || (y != nullptr && a_scale != nullptr),
-               "lf_block_tail_bwd: plane_sums needs y and a_scale/a_shift");
     LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 1, "lf_block_tail_bwd: bad dims n=%d c=%d h=%d w=%d", n, c, h, w);
     LF_REQUIRE((w & 1) == 0, "lf_block_tail_bwd: width must be even (float2 rows)");
-    LF_REQUIRE((y == nullptr) == (ds == nullptr && plane_sums == nullptr),
-               "lf_block_tail_bwd: y goes with ds / plane_sums");
-    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_bwd: a_scale/a_shift");
-    auto kernel = w % 4 == 0 ? tail_bwd_kernel<float, 4> : tail_bwd_kernel<float, 2>;
-    kernel<<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums,
-                                                        sc_y, sc_sums, c, h, w);
-    return lf::check_launch("lf_block_tail_bwd");
+    auto launch = w % 4 == 0 ? tail_bwd_launch<float, 4> : tail_bwd_launch<float, 2>;
+    return launch("lf_block_tail_bwd", dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums, sc_y, sc_sums, n, c, h,
+                  w, stream);
 }
 
 int lf_block_tail_bwd_bf16(const uint16_t* dp, const uint8_t* route, const uint16_t* y, const float* a_scale,
                            const float* a_shift, const float* drop, uint16_t* dr, float* ds, float* plane_sums,
                            const uint16_t* sc_y, float* sc_sums, int n, int c, int h, int w, lf_stream_t stream) {
-    LF_REQUIRE((sc_y == nullptr) == (sc_sums == nullptr), "lf_block_tail_bwd_bf16: sc_y and sc_sums go together");
-    LF_REQUIRE(dp && route && dr, "lf_block_tail_bwd_bf16: null buffer");
-    LF_REQUIRE(plane_sums == nullptr || (y != nullptr && a_scale != nullptr),
-               "lf_block_tail_bwd_bf16: plane_sums needs y and a_scale/a_shift");
     LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 3 && h % 2 == 0 && w % 4 == 0,
                "lf_block_tail_bwd_bf16: bad dims n=%d c=%d h=%d w=%d (h even, w %% 4 == 0)", n, c, h, w);
-    LF_REQUIRE((y == nullptr) == (ds == nullptr && plane_sums == nullptr),
-               "lf_block_tail_bwd_bf16: y goes with ds / plane_sums");
-    LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "lf_block_tail_bwd_bf16: a_scale/a_shift");
     LF_REQUIRE(aligned(dr, 8) && aligned(dp, 4) && aligned(route, 2), "lf_block_tail_bwd_bf16: misaligned buffer");
-    auto kernel = w % 8 == 0 && aligned(dr, 16) && aligned(dp, 8) && aligned(route, 4) ? tail_bwd_kernel<uint16_t, 8>
-                                                                                      : tail_bwd_kernel<uint16_t, 4>;
-    kernel<<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums,
-                                                        sc_y, sc_sums, c, h, w);
-    return lf::check_launch("lf_block_tail_bwd_bf16");
+    auto launch = w % 8 == 0 && aligned(dr, 16) && aligned(dp, 8) && aligned(route, 4) ? tail_bwd_launch<uint16_t, 8>
+                                                                                      : tail_bwd_launch<uint16_t, 4>;
+    return launch("lf_block_tail_bwd_bf16", dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums, sc_y, sc_sums, n,
+                  c, h, w, stream);
 }
 
 int lf_head_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue,
                     float* probs, float* loss, int n, int f, int c, lf_stream_t stream) {
     LF_REQUIRE(feat && w && b && probs, "lf_head_fwd: null buffer");
-    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= 4096, "lf_head_fwd: bad dims n=%d f=%d c=%d", n, f, c);
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= kHeadMaxClasses, "lf_head_fwd: bad dims n=%d f=%d c=%d", n, f, c);
     LF_REQUIRE((ytrue == nullptr) == (loss == nullptr), "lf_head_fwd: ytrue and loss go together");
     head_fwd_kernel<<<n, 64, (size_t)c * sizeof(float), lf::as_stream(stream)>>>(feat, w, b, ytrue, probs,
                                                                                loss, f, c);
@@ -1567,7 +1464,7 @@ int lf_head_bwd_f32(const float* feat, const float* w, const float* probs, const
                     float* dlogits, float* dfeat, float* dw, float* db, int n, int f, int c,
                     float inv_n, lf_stream_t stream) {
     LF_REQUIRE(feat && w && probs && ytrue && dlogits && dfeat && dw && db, "lf_head_bwd: null buffer");
-    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= 4096, "lf_head_bwd: bad dims n=%d f=%d c=%d", n, f, c);
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= kHeadMaxClasses, "lf_head_bwd: bad dims n=%d f=%d c=%d", n, f, c);
     return head_bwd_launch<false>("lf_head_bwd", feat, w, probs, ytrue, nullptr, 0.f, 0.f, dlogits, dfeat, dw, db, n,
                                   f, c, inv_n, stream);
 }
@@ -1576,7 +1473,8 @@ int lf_head_distill_fwd_f32(const float* feat, const float* w, const float* b, c
                             const float* tprobs, float temperature, float alpha, float* probs, float* soft,
                             float* loss, float* kd, int n, int f, int c, lf_stream_t stream) {
     LF_REQUIRE(feat && w && b && ytrue && tprobs && probs && soft && loss, "lf_head_distill_fwd: null buffer");
-    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= 4096, "lf_head_distill_fwd: bad dims n=%d f=%d c=%d", n, f, c);
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= kHeadMaxClasses, "lf_head_distill_fwd: bad dims n=%d f=%d c=%d", n, f,
+               c);
     LF_REQUIRE(distill_args_ok(temperature, alpha), "lf_head_distill_fwd: bad temperature=%g (> 0, finite) or "
                "alpha=%g (0..1)", (double)temperature, (double)alpha);
     head_distill_fwd_kernel<<<n, 64, 2 * (size_t)c * sizeof(float), lf::as_stream(stream)>>>(
@@ -1589,7 +1487,8 @@ int lf_head_distill_bwd_f32(const float* feat, const float* w, const float* prob
                             float* dw, float* db, int n, int f, int c, float inv_n, lf_stream_t stream) {
     LF_REQUIRE(feat && w && probs && ytrue && soft && dlogits && dfeat && dw && db,
                "lf_head_distill_bwd: null buffer");
-    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= 4096, "lf_head_distill_bwd: bad dims n=%d f=%d c=%d", n, f, c);
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= kHeadMaxClasses, "lf_head_distill_bwd: bad dims n=%d f=%d c=%d", n, f,
+               c);
     LF_REQUIRE(distill_args_ok(temperature, alpha), "lf_head_distill_bwd: bad temperature=%g (> 0, finite) or "
                "alpha=%g (0..1)", (double)temperature, (double)alpha);
     return head_bwd_launch<true>("lf_head_distill_bwd", feat, w, probs, ytrue, soft, 1.f - alpha,

@@ -10,12 +10,16 @@
 #include <math.h>
 
 #include "lf_common.h"
+#include "lf_wave.h"
 
 namespace {
 
+using lf::kHeadMaxClasses;
+using lf::take_larger;
+using lf::wave_argmax_all;
+
 constexpr int kBlock = 256;
 constexpr int kMaxViews = 16;
-constexpr int kMaxClasses = 4096;   // the head's limit
 
 // the view rows as a kernel argument: uniform over the launch, read through scalar registers
 struct ViewRows {
@@ -103,25 +107,6 @@ __global__ __launch_bounds__(kBlock) void tta_views_kernel(const uint8_t* __rest
     }
 }
 
-// the larger of two (value, index) pairs; the lower index on equal values (np.argmax)
-__device__ __forceinline__ void take_larger(float& bv, int& bi, float ov, int oi) {
-    if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-    }
-}
-// the same answer in every lane of the 64-lane wave (xor butterfly, as wave_max_all of lf_nn.hip: both partners of
-// a step compare the same two pairs)
-__device__ __forceinline__ int wave_argmax_all(float bv, int bi) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        take_larger(bv, bi, ov, oi);
-    }
-    return bi;
-}
-
 // One workgroup = one wave per image.  Lane l owns the classes l, l + 64, ...: it averages them over the views in
 // ascending order and keeps its best, the best of the wave is found by butterfly; then every counted view's own
 // argmax the same way.
@@ -177,14 +162,9 @@ int lf_tta_views_f32(const uint8_t* in, float* out, int n, int h, int w, const f
         }
         LF_REQUIRE(rows.r[k][3] != 0.f, "lf_tta_views: view %d has zoom 0", k);
     }
-    float m[3] = {0, 0, 0}, d[3] = {1, 1, 1};
+    float m[3], d[3];
+    lf::norm_consts(mean3, denom3, m, d);
     const bool norm = mean3 != nullptr;
-    if (norm) {   // HOST pointers (3 floats each): model constants
-        for (int c = 0; c < 3; ++c) {
-            m[c] = mean3[c];
-            d[c] = denom3[c];
-        }
-    }
     hipStream_t s = lf::as_stream(stream);
     const size_t hw = (size_t)h * w;
     const bool nt = lf::streaming((size_t)n * hw * 3 * (1 + 4 * (size_t)v));
@@ -199,7 +179,7 @@ int lf_tta_views_f32(const uint8_t* in, float* out, int n, int h, int w, const f
 int lf_tta_combine_f32(const float* probs, const float* weight, int v, float* out, int32_t* top, int32_t* agree,
                        int n, int c, lf_stream_t stream) {
     LF_REQUIRE(probs && out && top && agree, "lf_tta_combine: null buffer");
-    LF_REQUIRE(n > 0 && c > 0 && c <= kMaxClasses, "lf_tta_combine: bad dims n=%d c=%d", n, c);
+    LF_REQUIRE(n > 0 && c > 0 && c <= kHeadMaxClasses, "lf_tta_combine: bad dims n=%d c=%d", n, c);
     LF_REQUIRE(v >= 1 && v <= kMaxViews, "lf_tta_combine: v=%d views (1..%d)", v, kMaxViews);
     ViewWeights wt = {};
     float wsum = 0.f;

@@ -53,9 +53,11 @@ ENTRY_TESTS = {
     "lf_bn_train_stats_f32": ["test_bn_train_stats"],
     "lf_bn_train_stats_tiles_f32": ["test_bn_tile_entries"],
     "lf_bn_infer_scale_shift_f32": ["test_bn_infer_scale_shift"],
-    "lf_bn_bwd_f32": ["test_bn_bwd", "test_bn_bwd_plane_sums", "test_bn_bwd_tile_sums", "test_bn_argument_rules"],
-    "lf_bn_bwd_sums_f32": ["test_bn_bwd", "test_bn_bwd_plane_sums", "test_bn_argument_rules"],
-    "lf_bn_bwd_sums_tiles_f32": ["test_bn_tile_entries", "test_bn_bwd_tile_sums"],
+    "lf_bn_bwd_f32": ["test_bn_bwd", "test_bn_bwd_plane_sums", "test_bn_bwd_tile_sums", "test_bn_argument_rules",
+                      "test_bn_bwd_routes_same_bits"],
+    "lf_bn_bwd_sums_f32": ["test_bn_bwd", "test_bn_bwd_plane_sums", "test_bn_argument_rules",
+                           "test_bn_bwd_routes_same_bits"],
+    "lf_bn_bwd_sums_tiles_f32": ["test_bn_tile_entries", "test_bn_bwd_tile_sums", "test_bn_bwd_routes_same_bits"],
     "lf_gap_f32": ["test_gap_exact"],
     "lf_gap_stats_bf16": ["test_gap_exact", "test_bf16_plane_kernels_reject_odd_shapes"],
     "lf_bcast_planes_f32": ["test_bcast_planes_exact"],
@@ -724,6 +726,66 @@ def test_bn_bwd_tile_sums(cuda, n, c, hw):
     l0, l1 = part.to(D)[:, t0:t1, 0].sum(1), part.to(D)[:, t0:t1, 1].sum(1)
     res = run_bn_bwd(cuda, t, n, c, hw, True, tile_sums=(part.to(cuda), n), sums_entry=False)
     check_bn_bwd("bn_bwd tile sums", t, n * hw, res, e_db, e_dg, l0, (l1 - mean * l0) * inv)
+
+
+@pytest.mark.parametrize("n,c,hw", [(3, 7, 12), (5, 7, 9), (70, 65, 4)])
+def test_bn_bwd_routes_same_bits(cuda, n, c, hw):
+    """The three routes to BatchNorm's backward sums give the same bits: lf_bn_bwd_sums_f32 from g / y, the same entry
+    from plane sums, and lf_bn_bwd_sums_tiles_f32 from one tile pair per plane; lf_bn_bwd_f32's own g / y route
+    (finalizer without coefficients) too.  Every value is an integer or a half-integer (g in [-3, 3], y in
+    [-2.5, 2.5], mean 0.5, invstd 2), so every partial and every total is exact in fp32 and in float64 whatever the
+    order of the additions: dbeta and dgamma must equal the host's sums, and the five coefficients, the same fp32
+    expression of the same floats, must agree between the routes.  (3, 7, 12): the 4-element body, fewer images than
+    slices; (5, 7, 9): the 1-element body; (70, 65, 4): two images in some slices, and channel 64 in the finalizer's
+    second workgroup."""
+    from leaffliction_amd import _lib, nn
+    rg = gen(n * 19 + c + hw)
+    g = torch.randint(-3, 4, (n, c, hw), generator=rg).to(D)
+    y = torch.randint(-5, 6, (n, c, hw), generator=rg).to(D) * 0.5
+    gamma = cycle(c, [0.5, 1.0, 2.0])
+    beta = torch.randint(-8, 9, (c,), generator=rg).to(D) * 0.25
+    mean, inv = torch.full((c,), 0.5, dtype=D), torch.full((c,), 2.0, dtype=D)
+    scale = gamma * inv
+    shift = beta - mean * scale
+    v = lambda x: x.view(1, c, 1)  # noqa: E731
+    on = (y * v(scale) + v(shift) > 0).to(D)           # exact: multiples of 0.25 below 2^5
+    dz = g * on
+    xhat = (y - v(mean)) * v(inv)
+    # the largest intermediate any route can form: the sums of the absolute values, and q - mean*s of the tile route
+    worst = max(float((dz.abs() * xhat.abs()).sum((0, 2)).max()),
+                float(((dz.abs() * y.abs()).sum((0, 2)) + 0.5 * dz.abs().sum((0, 2))).max()))
+    assert worst < 2.0 ** 23            # at most n * hw * 3 * 6 = 5040: half-integers that small are exact in fp32
+    dbeta, dgamma = dz.sum((0, 2)).float(), (dz * xhat).sum((0, 2)).float()
+    plane = torch.stack([dz.sum(2), (dz * y).sum(2)], -1).float()      # [n][c][2]: the plane sums and the tile pairs
+    tiles = plane.permute(1, 0, 2).contiguous()                        # [c][tiles = n][2]
+
+    d = lambda x: x.float().to(cuda)  # noqa: E731
+    gd, yd, gam, pl, tl = d(g), d(y), d(gamma), plane.to(cuda), tiles.to(cuda)
+    st = torch.stack([mean, inv, scale, shift]).float().to(cuda)
+    stp = [st[k].data_ptr() for k in range(4)]
+    ws = nn._workspace(_lib.load().lf_bn_workspace(c), cuda)
+    out = lambda: (torch.full((c,), 3.0, device=cuda), torch.full((c,), 3.0, device=cuda),  # noqa: E731
+                   torch.full((5, c), math.nan, device=cuda))           # an unwritten coefficient equals nothing
+    res = []
+    for g_ptr, y_ptr, pg in ((gd.data_ptr(), yd.data_ptr(), None), (None, None, pl)):
+        dg, db, coef = out()
+        _lib.call("lf_bn_bwd_sums_f32", g_ptr, None, None, y_ptr, *stp, 1, gam.data_ptr(), dg.data_ptr(),
+                  db.data_ptr(), coef.data_ptr(), ptr(pg), None, n, c, hw, ws.data_ptr(), ws.numel(), None)
+        res.append((dg, db, coef))
+    dg, db, coef = out()
+    _lib.call("lf_bn_bwd_sums_tiles_f32", tl.data_ptr(), n, *stp, gam.data_ptr(), dg.data_ptr(), db.data_ptr(),
+              coef.data_ptr(), n, c, hw, ws.data_ptr(), ws.numel(), None)
+    res.append((dg, db, coef))
+    dg, db, _ = out()
+    dy = torch.empty_like(gd)
+    _lib.call("lf_bn_bwd_f32", gd.data_ptr(), None, None, yd.data_ptr(), *stp, 1, gam.data_ptr(), dy.data_ptr(),
+              dg.data_ptr(), db.data_ptr(), None, None, 0, n, c, hw, ws.data_ptr(), ws.numel(), None)
+    res.append((dg, db, res[0][2]))
+    torch.cuda.synchronize()
+    for route, (dg, db, coef) in zip(("g / y", "plane sums", "tile pairs", "lf_bn_bwd_f32"), res):
+        assert torch.equal(db.cpu(), dbeta), f"dbeta, route {route}"
+        assert torch.equal(dg.cpu(), dgamma), f"dgamma, route {route}"
+        assert torch.equal(coef, res[0][2]), f"coef, route {route}"
 
 
 def test_bn_argument_rules(cuda):
