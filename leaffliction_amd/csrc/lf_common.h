@@ -383,6 +383,21 @@ __device__ __forceinline__ float pro_apply(float v, float sc, float sh, int relu
     return relu ? fmaxf(v, 0.f) : v;
 }
 
+// BatchNorm backward on one element (lf_nn.hip's kernels, and the weight gradients that form dY while staging):
+//   dz = (g*al + ad) * [y*sc + sh > 0 or !relu]
+// the ReLU mask is recomputed from y with the forward's own fmaf, so the activation tensor is never materialised:
+// fmaf(y, sc, sh) > 0 here and fmaf(y, c0, c1) > 0 below are that fmaf, (c0, c1) being the BN's (scale, shift).
+__device__ __forceinline__ float bn_dz1(float g, float y, float al, float ad, float sc, float sh, int relu) {
+    float dz = fmaf(g, al, ad);
+    if (relu && !(fmaf(y, sc, sh) > 0.f)) dz = 0.f;
+    return dz;
+}
+//   dY = c2*dz + c3*y + c4, c0..c4 being the channel's column of the [5][C] coefficient block
+__device__ __forceinline__ float bn_dy1(float g, float y, float al, float ad, float c0, float c1, float c2, float c3,
+                                        float c4, int relu) {
+    return fmaf(c2, bn_dz1(g, y, al, ad, c0, c1, relu), fmaf(c3, y, c4));
+}
+
 // Staging four channels x G pixels as [pixel][channel] bf16: raw[i] = channel i's G pixels as loaded; ok = false:
 // outside the image, which stays exactly zero.  transform(i, v) works on channel i's G fp32 values; every second
 // channel the pair (i - 1, i) leaves as store(e, pair, dword), one dword per pixel e — channel by channel, so that

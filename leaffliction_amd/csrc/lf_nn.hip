@@ -21,6 +21,7 @@
 namespace {
 
 using lf::block_sum;
+using lf::bn_dz1;
 using lf::kHeadMaxClasses;
 using lf::narrow;
 using lf::Vec;
@@ -371,15 +372,6 @@ struct BnBwdArgs {
     int relu;            // 1: the BN was followed by ReLU -> gradient passes where y*scale+shift > 0
     int n, c, hw;
 };
-
-// dz for one element: the ReLU mask is recomputed from y with the forward's own fmaf, so the
-// activation tensor is never materialised
-__device__ __forceinline__ float bn_dz1(float g, float y, float al, float ad, float sc, float sh,
-                                        int relu) {
-    float dz = fmaf(g, al, ad);
-    if (relu && !(fmaf(y, sc, sh) > 0.f)) dz = 0.f;
-    return dz;
-}
 
 template <int V>
 __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(BnBwdArgs a, float* __restrict__ part) {

@@ -21,6 +21,7 @@
 namespace {
 
 using namespace lf::conv_f32;
+using lf::bn_dy1;
 using lf::pro_apply;
 
 // ---------------------------------------------------------------------------
@@ -52,11 +53,151 @@ struct WgradArgs {
     int bn_relu;
 };
 
-__device__ __forceinline__ float bn_dy1(float g, float y, float al, float ad, float c0, float c1,
-                                        float c2, float c3, float c4, int relu) {
-    float dz = fmaf(g, al, ad);
-    if (relu && !(fmaf(y, c0, c1) > 0.f)) dz = 0.f;
-    return fmaf(c2, dz, fmaf(c3, y, c4));
+// ---- staging rules the kernels below share.  None holds a barrier or a wait of its own except fold_ksplit, whose
+// rounds are barriers; all take the kernel's own pointers, so where a kernel loads and stores stays in the kernel.
+
+// Work item -> image n, tile t of the image, and the tile's origin, for TW x TH tiles
+struct TileItem {
+    int n, t, tx0, ty0;
+};
+template <int TW, int TH>
+__device__ __forceinline__ TileItem tile_item(int item, int tiles, int tiles_x) {
+    TileItem it;
+    it.n = item / tiles;
+    it.t = item - it.n * tiles;
+    it.tx0 = (it.t % tiles_x) * TW;
+    it.ty0 = (it.t / tiles_x) * TH;
+    return it;
+}
+
+// Flat staging index e -> the float4 it stands for in a block of channels x ROWS rows x TW4 float4s: channel c, row
+// py, float4 `slot` of the row; rem = the float4's index inside the channel plane
+struct Slot4 {
+    int c, py, slot, rem;
+};
+template <int ROWS, int TW4>
+__device__ __forceinline__ Slot4 slot4(int e) {
+    Slot4 s;
+    s.c = e / (ROWS * TW4);
+    s.rem = e - s.c * (ROWS * TW4);
+    s.py = s.rem / TW4;
+    s.slot = s.rem - s.py * TW4;
+    return s;
+}
+
+// The producer BatchNorm's scale / shift of channels ci0 .. ci0 + ci_t - 1 -> lsc[c] / lsc[kMaxProC / 4 + c], neutral
+// (1, 0) beyond cin
+__device__ __forceinline__ void stage_pro_consts(float* lsc, const float* scale, const float* shift, int ci0, int ci_t,
+                                                 int cin, int tid, int threads) {
+    for (int c = tid; c < ci_t; c += threads) {
+        const int gc = ci0 + c;
+        lsc[c] = gc < cin ? scale[gc] : 1.f;
+        lsc[kMaxProC / 4 + c] = gc < cin ? shift[gc] : 0.f;
+    }
+}
+__device__ __forceinline__ float4 pro_apply4(float4 v, const float* lsc, int c, int relu) {
+    const float sc = lsc[c], sh = lsc[kMaxProC / 4 + c];
+    return make_float4(pro_apply(v.x, sc, sh, relu), pro_apply(v.y, sc, sh, relu), pro_apply(v.z, sc, sh, relu),
+                       pro_apply(v.w, sc, sh, relu));
+}
+
+// The BatchNorm-backward coefficients coef[5][cout] of channels co0 .. co0 + CO_T - 1 -> lbn[5][CO_T], zero beyond
+// cout.  WHOLE: the block is the tensor (co0 = 0, cout = CO_T), copied without bounds.
+template <int CO_T, bool WHOLE = false>
+__device__ __forceinline__ void stage_bn_coef(float* lbn, const float* coef, int co0, int cout, int tid, int threads) {
+    for (int e = tid; e < 5 * CO_T; e += threads) {
+        if (WHOLE) {
+            lbn[e] = coef[e];
+        } else {
+            const int kk = e / CO_T, gc = co0 + (e - kk * CO_T);
+            lbn[e] = gc < cout ? coef[(size_t)kk * cout + gc] : 0.f;
+        }
+    }
+}
+// bn_dy1 on the four lanes of a float4 of channel c of the staged block
+template <int CO_T>
+__device__ __forceinline__ float4 bn_dy4(float4 g, float4 y, float al, float ad, const float* lbn, int c, int relu) {
+    const float c0 = lbn[c], c1 = lbn[CO_T + c], c2 = lbn[2 * CO_T + c], c3 = lbn[3 * CO_T + c], c4 = lbn[4 * CO_T + c];
+    return make_float4(bn_dy1(g.x, y.x, al, ad, c0, c1, c2, c3, c4, relu), bn_dy1(g.y, y.y, al, ad, c0, c1, c2, c3, c4, relu),
+                       bn_dy1(g.z, y.z, al, ad, c0, c1, c2, c3, c4, relu), bn_dy1(g.w, y.w, al, ad, c0, c1, c2, c3, c4, relu));
+}
+// dy_out is written by the workgroups of ci-block 0 alone: each element exactly once
+__device__ __forceinline__ bool writes_dy_out(const float* dy_out, int ci_block) {
+    return ci_block == 0 && dy_out != nullptr;
+}
+
+// A float4 into LDS planes of odd pitch: no 16-byte alignment, four scalar stores
+__device__ __forceinline__ void lds_put4(float* dst, float4 v) {
+    dst[0] = v.x;
+    dst[1] = v.y;
+    dst[2] = v.z;
+    dst[3] = v.w;
+}
+
+// Scalar (ragged-shape) staging by all `threads` threads, any W and alignment.
+// The haloed X patch of a TW x TH tile at (tx0, ty0): `nch` planes of (TW + 2) x (TH + 2) at pitch `pitch`, zero
+// outside the image and for channels ci0 + c >= cin, through the producer's prologue (scale null: none).
+template <int TW, int TH>
+__device__ __forceinline__ void stage_x_patch_scalar(float* lx, int pitch, int nch, const float* xin, int ci0, int cin,
+                                                     int tx0, int ty0, int h, int wd, unsigned uhw, const float* scale,
+                                                     const float* shift, int relu, int tid, int threads) {
+    constexpr int PW = TW + 2, PH = TH + 2;
+    for (int e = tid; e < nch * PW * PH; e += threads) {
+        const int c = e / (PW * PH), rem = e - c * (PW * PH);
+        const int py = rem / PW, px = rem - py * PW;
+        const int gc = ci0 + c, gy = ty0 + py - 1, gx = tx0 + px - 1;
+        float v = 0.f;
+        if (gc < cin && gy >= 0 && gy < h && gx >= 0 && gx < wd) {
+            v = xin[(unsigned)gc * uhw + (unsigned)gy * (unsigned)wd + (unsigned)gx];
+            if (scale != nullptr) v = pro_apply(v, scale[gc], shift[gc], relu);
+        }
+        lx[c * pitch + rem] = v;
+    }
+}
+// The dY tile: `nch` planes of TW x TH at pitch `pitch`, zero outside the image and for channels co0 + c >= cout.
+template <int TW, int TH>
+__device__ __forceinline__ void stage_dy_tile_scalar(float* ld, int pitch, int nch, const float* din, int co0, int cout,
+                                                     int tx0, int ty0, int h, int wd, unsigned uhw, int tid,
+                                                     int threads) {
+    for (int e = tid; e < nch * TW * TH; e += threads) {
+        const int c = e / (TW * TH), rem = e - c * (TW * TH);
+        const int py = rem / TW, px = rem - py * TW;
+        const int gc = co0 + c, gy = ty0 + py, gx = tx0 + px;
+        float v = 0.f;
+        if (gc < cout && gy < h && gx < wd) v = din[(unsigned)gc * uhw + (unsigned)gy * (unsigned)wd + (unsigned)gx];
+        ld[c * pitch + rem] = v;
+    }
+}
+
+// Row of the 32x32 result that accumulator register r of a v_mfma_f32_32x32x2_f32 holds in lane half khalf (its
+// column is lane & 31)
+__device__ __forceinline__ constexpr int mfma32_row(int r, int khalf) { return (r & 3) + 8 * (r >> 2) + 4 * khalf; }
+
+// K-split fold: the waves w_k = 1 .. KSPL - 1 add their A accumulators into wave w_k = 0 of the same (ci, co) block q
+// (of NQ) through LDS, one writer and one reader per round, in a fixed order (deterministic); accumulator a, register
+// r goes through slab[a * 1024 + r * 64 + lane].  Every wave of the workgroup calls it: the rounds are barriers.
+template <int A, int KSPL, int NQ>
+__device__ __forceinline__ void fold_ksplit(f32x16* acc, float* slab, int w_k, int q, int lane) {
+#pragma unroll 1
+    for (int k = 1; k < KSPL; ++k) {
+#pragma unroll 1
+        for (int qq = 0; qq < NQ; ++qq) {
+            __syncthreads();
+            if (w_k == k && q == qq) {
+#pragma unroll
+                for (int a = 0; a < A; ++a)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) slab[a * 1024 + r * 64 + lane] = acc[a][r];
+            }
+            __syncthreads();
+            if (w_k == 0 && q == qq) {
+#pragma unroll
+                for (int a = 0; a < A; ++a)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[a][r] += slab[a * 1024 + r * 64 + lane];
+            }
+        }
+    }
 }
 
 // Three waves per SIMD for the instantiations that spilled to scratch at four (128 registers): plan_wgrad sizes
@@ -117,61 +258,47 @@ __global__ __launch_bounds__(kThreads, KSPL == 2 ? 4 : 3) void wgrad_mfma_kernel
         unsigned xok = 0;
         // producer BatchNorm scale/shift of this workgroup's CI_T channels, staged once in LDS
         __shared__ float lsc[kMaxProC / 2];
-        if (pro) {
-            for (int c = tid; c < CI_T; c += kThreads) {
-                const int gc = ci0 + c;
-                lsc[c] = gc < p.cin ? p.in_scale[gc] : 1.f;
-                lsc[kMaxProC / 4 + c] = gc < p.cin ? p.in_shift[gc] : 0.f;
-            }
-        }
+        if (pro) stage_pro_consts(lsc, p.in_scale, p.in_shift, ci0, CI_T, p.cin, tid, kThreads);
         // optional: dY = BatchNorm backward of p.dy, formed while staging (see WgradArgs)
         const bool bn = p.bn_y != nullptr;
         float4 yv[DPT];
         float dal[DPT], dad[DPT];
         unsigned dok = 0;
         __shared__ float lbn[5 * CO_T];
-        if (bn) {
-            for (int e = tid; e < 5 * CO_T; e += kThreads) {
-                const int kk = e / CO_T, gc = co0 + (e - kk * CO_T);
-                lbn[e] = gc < p.cout ? p.bn_coef[(size_t)kk * p.cout + gc] : 0.f;
-            }
-        }
+        if (bn) stage_bn_coef<CO_T>(lbn, p.bn_coef, co0, p.cout, tid, kThreads);
         // the next item's loads stay in registers over the MFMAs
         auto load_x = [&](int item) {
-            const int n = item / tiles, t = item - n * tiles;
-            const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
-            const float* xin = p.x + (size_t)n * p.cin * hw;
+            const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
+            const float* xin = p.x + (size_t)it.n * p.cin * hw;
             xok = 0;
 #pragma unroll
             for (int i = 0; i < XPT; ++i) {
                 const int e = tid + i * kThreads;
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
-                const int py = rem / TW4, slot = rem - py * TW4;
-                const int gc = ci0 + c, gy = ty0 + py;
+                const Slot4 s = slot4<TH, TW4>(e);
+                const int gc = ci0 + s.c, gy = it.ty0 + s.py;
                 if (e < NXI && gc < p.cin && gy < p.h) {
                     v = *reinterpret_cast<const float4*>(xin + (unsigned)gc * uhw +
-                                                         (unsigned)gy * (unsigned)p.wd + tx0 + 4 * slot);
+                                                         (unsigned)gy * (unsigned)p.wd + it.tx0 + 4 * s.slot);
                     xok |= 1u << i;
                 }
                 xv[i] = v;
             }
         };
         auto load_d = [&](int item) {
-            const int n = item / tiles, t = item - n * tiles;
-            const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
+            const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
+            const int n = it.n;
             const float* din = p.dy + (size_t)n * p.cout * hw;
             dok = 0;
 #pragma unroll
             for (int i = 0; i < DPT; ++i) {
                 const int e = tid + i * kThreads;
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
-                const int py = rem / TW4, slot = rem - py * TW4;
-                const int gc = co0 + c, gy = ty0 + py;
+                const Slot4 s = slot4<TH, TW4>(e);
+                const int gc = co0 + s.c, gy = it.ty0 + s.py;
                 if (e < NDI && gc < p.cout && gy < p.h) {
                     v = *reinterpret_cast<const float4*>(din + (unsigned)gc * uhw +
-                                                         (unsigned)gy * (unsigned)p.wd + tx0 + 4 * slot);
+                                                         (unsigned)gy * (unsigned)p.wd + it.tx0 + 4 * s.slot);
                     dok |= 1u << i;
                 }
                 dv[i] = v;
@@ -180,18 +307,17 @@ __global__ __launch_bounds__(kThreads, KSPL == 2 ? 4 : 3) void wgrad_mfma_kernel
                 const float* yin = p.bn_y + (size_t)n * p.cout * hw;
 #pragma unroll
                 for (int i = 0; i < DPT; ++i) {
-                    const int e = tid + i * kThreads;
+                    const Slot4 s = slot4<TH, TW4>(tid + i * kThreads);
                     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
-                    const int py = rem / TW4, slot = rem - py * TW4;
                     if (dok >> i & 1u)
-                        v = *reinterpret_cast<const float4*>(yin + (unsigned)(co0 + c) * uhw +
-                                                             (unsigned)(ty0 + py) * (unsigned)p.wd + tx0 + 4 * slot);
+                        v = *reinterpret_cast<const float4*>(yin + (unsigned)(co0 + s.c) * uhw +
+                                                             (unsigned)(it.ty0 + s.py) * (unsigned)p.wd + it.tx0 +
+                                                             4 * s.slot);
                     yv[i] = v;
                 }
 #pragma unroll
                 for (int i = 0; i < DPT; ++i) {
-                    const int gc = min(co0 + (tid + i * kThreads) / (TH * TW4), p.cout - 1);
+                    const int gc = min(co0 + slot4<TH, TW4>(tid + i * kThreads).c, p.cout - 1);
                     dal[i] = p.bn_alpha != nullptr ? p.bn_alpha[(size_t)n * p.cout + gc] : 1.f;
                     dad[i] = p.bn_add != nullptr ? p.bn_add[(size_t)n * p.cout + gc] : 0.f;
                 }
@@ -202,51 +328,28 @@ __global__ __launch_bounds__(kThreads, KSPL == 2 ? 4 : 3) void wgrad_mfma_kernel
             for (int i = 0; i < XPT; ++i) {
                 const int e = tid + i * kThreads;
                 if (e < NXI) {
-                    const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
-                    const int py = rem / TW4, slot = rem - py * TW4;
+                    const Slot4 s = slot4<TH, TW4>(e);
                     float4 v = xv[i];
-                    if (pro && (xok >> i & 1u)) {
-                        const float sc = lsc[c], sh = lsc[kMaxProC / 4 + c];
-                        v.x = pro_apply(v.x, sc, sh, p.in_relu);
-                        v.y = pro_apply(v.y, sc, sh, p.in_relu);
-                        v.z = pro_apply(v.z, sc, sh, p.in_relu);
-                        v.w = pro_apply(v.w, sc, sh, p.in_relu);
-                    }
-                    float* dst = lx + c * PP + py * TW + 4 * slot;
-                    dst[0] = v.x;
-                    dst[1] = v.y;
-                    dst[2] = v.z;
-                    dst[3] = v.w;
+                    if (pro && (xok >> i & 1u)) v = pro_apply4(v, lsc, s.c, p.in_relu);
+                    lds_put4(lx + s.c * PP + s.py * TW + 4 * s.slot, v);
                 }
             }
         };
         auto store_d = [&](int item) {
-            const int sn = item / tiles, st = item - sn * tiles;
-            const int stx0 = (st % p.tiles_x) * TW, sty0 = (st / p.tiles_x) * TH;
+            const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
 #pragma unroll
             for (int i = 0; i < DPT; ++i) {
                 const int e = tid + i * kThreads;
                 if (e < NDI) {
-                    const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
+                    const Slot4 s = slot4<TH, TW4>(e);
                     float4 v = dv[i];
                     if (bn && (dok >> i & 1u)) {
-                        const float c0 = lbn[c], c1 = lbn[CO_T + c], c2 = lbn[2 * CO_T + c],
-                                    c3 = lbn[3 * CO_T + c], c4 = lbn[4 * CO_T + c];
-                        v.x = bn_dy1(v.x, yv[i].x, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
-                        v.y = bn_dy1(v.y, yv[i].y, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
-                        v.z = bn_dy1(v.z, yv[i].z, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
-                        v.w = bn_dy1(v.w, yv[i].w, dal[i], dad[i], c0, c1, c2, c3, c4, p.bn_relu);
-                        if (blk.y == 0 && p.dy_out != nullptr) {
-                            const int py = rem / TW4, slot = rem - py * TW4;
-                            *reinterpret_cast<float4*>(p.dy_out + ((size_t)sn * p.cout + co0 + c) * hw +
-                                                       (size_t)(sty0 + py) * p.wd + stx0 + 4 * slot) = v;
-                        }
+                        v = bn_dy4<CO_T>(v, yv[i], dal[i], dad[i], lbn, s.c, p.bn_relu);
+                        if (writes_dy_out(p.dy_out, blk.y))
+                            *reinterpret_cast<float4*>(p.dy_out + ((size_t)it.n * p.cout + co0 + s.c) * hw +
+                                                       (size_t)(it.ty0 + s.py) * p.wd + it.tx0 + 4 * s.slot) = v;
                     }
-                    float* dst = ld + c * PP + rem * 4;
-                    dst[0] = v.x;
-                    dst[1] = v.y;
-                    dst[2] = v.z;
-                    dst[3] = v.w;
+                    lds_put4(ld + s.c * PP + s.rem * 4, v);
                 }
             }
         };
@@ -274,13 +377,12 @@ __global__ __launch_bounds__(kThreads, KSPL == 2 ? 4 : 3) void wgrad_mfma_kernel
         const int slot = tid % SLOTS, grp = tid / SLOTS;
         const int spy = slot / TW, spx = slot - spy * TW;
         for (int item = first; item < last; ++item) {
-            const int n = item / tiles, t = item - n * tiles;
-            const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
-            const float* xin = p.x + (size_t)n * p.cin * hw;
-            const float* din = p.dy + (size_t)n * p.cout * hw;
+            const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
+            const float* xin = p.x + (size_t)it.n * p.cin * hw;
+            const float* din = p.dy + (size_t)it.n * p.cout * hw;
             __syncthreads();
             if (slot < POS) {
-                const int gy = ty0 + spy, gx = tx0 + spx;
+                const int gy = it.ty0 + spy, gx = it.tx0 + spx;
                 const bool ok = gy < p.h && gx < p.wd;
                 const unsigned off = ok ? (unsigned)gy * (unsigned)p.wd + (unsigned)gx : 0u;
 #pragma unroll 4
@@ -308,31 +410,13 @@ __global__ __launch_bounds__(kThreads, KSPL == 2 ? 4 : 3) void wgrad_mfma_kernel
 
     // K-split waves fold their accumulators into wave k = 0 through LDS, one (ci,co) block
     // at a time, in a fixed order
-    if (KSPL > 1) {
-        const int q = w_co * WCI + w_ci;
-#pragma unroll 1
-        for (int k = 1; k < KSPL; ++k) {
-#pragma unroll 1
-            for (int qq = 0; qq < WCI * WCO; ++qq) {
-                __syncthreads();
-                if (w_k == k && q == qq) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) lds[r * 64 + lane] = acc[r];
-                }
-                __syncthreads();
-                if (w_k == 0 && q == qq) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] += lds[r * 64 + lane];
-                }
-            }
-        }
-    }
+    fold_ksplit<1, KSPL, WCI * WCO>(&acc, lds, w_k, w_co * WCI + w_ci, lane);
     if (w_k == 0) {
         float* out = p.part + (size_t)blk.x * p.cin * p.cout;
         const int co = co0 + w_co * 32 + j;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + w_ci * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            const int ci = ci0 + w_ci * 32 + mfma32_row(r, khalf);
             if (ci < p.cin && co < p.cout) out[(size_t)ci * p.cout + co] = acc[r];
         }
     }
@@ -367,6 +451,18 @@ struct ProjBwdArgs {
 
 constexpr int kProjP = 64;
 
+// Work item -> image n and the item's first pixel px0 of the flat plane
+struct ProjItem {
+    int n;
+    size_t px0;
+};
+__device__ __forceinline__ ProjItem proj_item(int item, int items_per_image) {
+    ProjItem it;
+    it.n = item / items_per_image;
+    it.px0 = (size_t)(item - it.n * items_per_image) * kProjP;
+    return it;
+}
+
 __device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, 0);
 }
@@ -389,7 +485,7 @@ __global__ __launch_bounds__(128 * CIB, 2) void proj_bwd_kernel(ProjBwdArgs p) {
     const int cib = wid % CIB, pxb = wid / CIB;
     const unsigned uhw = (unsigned)p.hw;
 
-    for (int e = tid; e < 5 * COUT; e += NT) lbn[e] = p.coef[e];
+    stage_bn_coef<COUT, true>(lbn, p.coef, 0, COUT, tid, NT);
     // this wave's rows of w, for the whole launch
     float wr[HC];
     {
@@ -419,11 +515,10 @@ __global__ __launch_bounds__(128 * CIB, 2) void proj_bwd_kernel(ProjBwdArgs p) {
 
     float4 xv[XPT], gv[DPT], yv[DPT];
     auto load_item = [&](int item) {
-        const int n = item / p.items_per_image;
-        const size_t px0 = (size_t)(item - n * p.items_per_image) * P;
-        const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.x + (size_t)n * CIN * p.hw + px0, xbytes);
-        const __amdgpu_buffer_rsrc_t rg = buf_rsrc(p.g + (size_t)n * COUT * p.hw + px0, dbytes);
-        const __amdgpu_buffer_rsrc_t ry = buf_rsrc(p.bn_y + (size_t)n * COUT * p.hw + px0, dbytes);
+        const ProjItem it = proj_item(item, p.items_per_image);
+        const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.x + (size_t)it.n * CIN * p.hw + it.px0, xbytes);
+        const __amdgpu_buffer_rsrc_t rg = buf_rsrc(p.g + (size_t)it.n * COUT * p.hw + it.px0, dbytes);
+        const __amdgpu_buffer_rsrc_t ry = buf_rsrc(p.bn_y + (size_t)it.n * COUT * p.hw + it.px0, dbytes);
 #pragma unroll
         for (int i = 0; i < XPT; ++i) xv[i] = buf_load4(rx, goff + (unsigned)i * gstep);
 #pragma unroll
@@ -433,24 +528,11 @@ __global__ __launch_bounds__(128 * CIB, 2) void proj_bwd_kernel(ProjBwdArgs p) {
     };
     auto store_item = [&]() {
 #pragma unroll
-        for (int i = 0; i < XPT; ++i) {
-            float* dst = lx + loff + i * CSTEP * PP;
-            dst[0] = xv[i].x;
-            dst[1] = xv[i].y;
-            dst[2] = xv[i].z;
-            dst[3] = xv[i].w;
-        }
+        for (int i = 0; i < XPT; ++i) lds_put4(lx + loff + i * CSTEP * PP, xv[i]);
 #pragma unroll
-        for (int i = 0; i < DPT; ++i) {
-            const int c = c0 + i * CSTEP;
-            const float k0 = lbn[c], k1 = lbn[COUT + c], k2 = lbn[2 * COUT + c], k3 = lbn[3 * COUT + c],
-                        k4 = lbn[4 * COUT + c];
-            float* dst = ld + loff + i * CSTEP * PP;
-            dst[0] = bn_dy1(gv[i].x, yv[i].x, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
-            dst[1] = bn_dy1(gv[i].y, yv[i].y, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
-            dst[2] = bn_dy1(gv[i].z, yv[i].z, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
-            dst[3] = bn_dy1(gv[i].w, yv[i].w, 1.f, 0.f, k0, k1, k2, k3, k4, p.bn_relu);
-        }
+        for (int i = 0; i < DPT; ++i)
+            lds_put4(ld + loff + i * CSTEP * PP,
+                     bn_dy4<COUT>(gv[i], yv[i], 1.f, 0.f, lbn, c0 + i * CSTEP, p.bn_relu));
     };
     auto compute_item = [&](int item) {
         // input gradient of the item: K = co, this lane half's run of HC channels
@@ -460,11 +542,11 @@ __global__ __launch_bounds__(128 * CIB, 2) void proj_bwd_kernel(ProjBwdArgs p) {
         const float* bx = ld + khalf * HC * PP + pxb * 32 + j;
 #pragma unroll
         for (int s = 0; s < HC; ++s) accx = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[s], bx[s * PP], accx, 0, 0, 0);
-        const int n = item / p.items_per_image;
-        const size_t px0 = (size_t)(item - n * p.items_per_image) * P;
-        const __amdgpu_buffer_rsrc_t rdx = buf_rsrc(p.dx + (size_t)n * CIN * p.hw + px0, xbytes);
+        const ProjItem it = proj_item(item, p.items_per_image);
+        const __amdgpu_buffer_rsrc_t rdx = buf_rsrc(p.dx + (size_t)it.n * CIN * p.hw + it.px0, xbytes);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) buf_store1(rdx, soff + 4u * (unsigned)((r & 3) + 8 * (r >> 2)) * uhw, accx[r]);
+        for (int r = 0; r < 16; ++r)  // the lane half's four rows are in soff
+            buf_store1(rdx, soff + 4u * (unsigned)mfma32_row(r, 0) * uhw, accx[r]);
         // weight gradient: K = the item's pixels
         const float* bw = ld + (wid * 32 + j) * PP + khalf;
         const float* aw = lx + j * PP + khalf;
@@ -493,7 +575,7 @@ __global__ __launch_bounds__(128 * CIB, 2) void proj_bwd_kernel(ProjBwdArgs p) {
     for (int a = 0; a < CIB; ++a)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            out[(a * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf) * COUT + wid * 32 + j] = accw[a][r];
+            out[(a * 32 + mfma32_row(r, khalf)) * COUT + wid * 32 + j] = accw[a][r];
 }
 
 
@@ -637,6 +719,7 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
         const bool bn = p.bn_y != nullptr;
         // producer BatchNorm scale/shift of this workgroup's CI_T channels, staged once in LDS
         __shared__ float lsc[kMaxProC / 2];
+        // (stage_pro_consts and stage_bn_coef written out: through the helpers <16,8,1,2,2> spilled 7 and 10 more SGPRs)
         if (pro) {
             for (int c = tid; c < CI_T; c += NT) {
                 const int gc = ci0 + c;
@@ -675,11 +758,11 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
 #pragma unroll
         for (int i = 0; i < XPT; ++i) {
             const int e = tid + i * NT;
-            const int c = e / (PH * TW4), rem = e - c * (PH * TW4);
-            const int py = rem / TW4, slot = rem - py * TW4;
-            const bool ok = e < NXI && ci0 + c < p.cin;
-            xg[i] = ok ? 4u * ((unsigned)c * uhw + (unsigned)py * (unsigned)p.wd + 1u + 4u * (unsigned)slot) : kBufOob;
-            xl[i] = (unsigned)(c * PP + py * PW + 1 + 4 * slot) | ((unsigned)py << 16);
+            const Slot4 s = slot4<PH, TW4>(e);
+            const bool ok = e < NXI && ci0 + s.c < p.cin;
+            xg[i] = ok ? 4u * ((unsigned)s.c * uhw + (unsigned)s.py * (unsigned)p.wd + 1u + 4u * (unsigned)s.slot)
+                       : kBufOob;
+            xl[i] = (unsigned)(s.c * PP + s.py * PW + 1 + 4 * s.slot) | ((unsigned)s.py << 16);
         }
 #pragma unroll
         for (int i = 0; i < HPT; ++i) {
@@ -694,11 +777,10 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
 #pragma unroll
         for (int i = 0; i < DPT; ++i) {
             const int e = tid + i * NT;
-            const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
-            const int py = rem / TW4, slot = rem - py * TW4;
-            const bool ok = e < NDI && co0 + c < p.cout;
-            dg[i] = ok ? 4u * ((unsigned)c * uhw + (unsigned)py * (unsigned)p.wd + 4u * (unsigned)slot) : kBufOob;
-            dl[i] = (unsigned)(c * DP + rem * 4) | ((unsigned)py << 16);
+            const Slot4 s = slot4<TH, TW4>(e);
+            const bool ok = e < NDI && co0 + s.c < p.cout;
+            dg[i] = ok ? 4u * ((unsigned)s.c * uhw + (unsigned)s.py * (unsigned)p.wd + 4u * (unsigned)s.slot) : kBufOob;
+            dl[i] = (unsigned)(s.c * DP + s.rem * 4) | ((unsigned)s.py << 16);
         }
         const unsigned xbytes = 4u * ((unsigned)min(CI_T, p.cin - ci0) * uhw + (unsigned)p.wd + 1u);
         const unsigned dbytes = 4u * (unsigned)min(CO_T, p.cout - co0) * uhw;
@@ -706,8 +788,8 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
         // variant that holds the whole tile has only half 0).  Nothing here is conditional: where `live` is false
         // (there is no such item) every load takes the out-of-range offset, which fetches zeros and no memory.
         auto load_item = [&](int item, bool with_x, int dhalf, bool live) {
-            const int n = item / tiles, t = item - n * tiles;
-            const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
+            const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
+            const int n = it.n, t = it.t, tx0 = it.tx0, ty0 = it.ty0;
             const size_t torg = (size_t)ty0 * p.wd + tx0;
             const size_t nl = (size_t)n;
             // patch origin = one row up, one column left of the tile (never dereferenced there:
@@ -766,22 +848,9 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
 #pragma unroll
             for (int i = 0; i < XPT; ++i) {
                 if (tid + i * NT < NXI) {
-                    const int c = (tid + i * NT) / (PH * TW4);
                     float4 v = xv[i];  // padding was fetched as zeros
-                    if (pro && (xok >> i & 1u)) {
-                        const float sc = lsc[c], sh = lsc[kMaxProC / 4 + c];
-                        v.x = pro_apply(v.x, sc, sh, p.in_relu);
-                        v.y = pro_apply(v.y, sc, sh, p.in_relu);
-                        v.z = pro_apply(v.z, sc, sh, p.in_relu);
-                        v.w = pro_apply(v.w, sc, sh, p.in_relu);
-                    }
-                    float* dst = lx + (xl[i] & 0xffffu);
-                    {
-                        dst[0] = v.x;
-                        dst[1] = v.y;
-                        dst[2] = v.z;
-                        dst[3] = v.w;
-                    }
+                    if (pro && (xok >> i & 1u)) v = pro_apply4(v, lsc, slot4<PH, TW4>(tid + i * NT).c, p.in_relu);
+                    lds_put4(lx + (xl[i] & 0xffffu), v);
                 }
             }
 #pragma unroll
@@ -797,37 +866,25 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
             }
             if (dhalf < 0) return;
             const int s0 = dhalf * DH;
-            const int sn = item / tiles, st = item - sn * tiles;
-            const int stx0 = (st % p.tiles_x) * TW, sty0 = (st / p.tiles_x) * TH;
-            float* dyo = bn ? p.dy_out + ((size_t)sn * p.cout + co0) * hw + (size_t)sty0 * p.wd + stx0 : nullptr;
+            const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
+            const int sn = it.n;
+            float* dyo = bn ? p.dy_out + ((size_t)sn * p.cout + co0) * hw + (size_t)it.ty0 * p.wd + it.tx0 : nullptr;
             const float* tb = lal[sn & 1];
 #pragma unroll
             for (int i = 0; i < DH; ++i) {
                 if (tid + (s0 + i) * NT < NDI) {
-                    const int c = (tid + (s0 + i) * NT) / (TH * TW4);
+                    const int c = slot4<TH, TW4>(tid + (s0 + i) * NT).c;
                     float4 v = dv[i];
                     if (bn && (dok >> i & 1u)) {
-                        const float c0 = lbn[c], c1 = lbn[CO_T + c], c2 = lbn[2 * CO_T + c],
-                                    c3 = lbn[3 * CO_T + c], c4 = lbn[4 * CO_T + c];
                         const float al = tabbed ? tb[c] : 1.f, ad = tabbed ? tb[CO_T + c] : 0.f;
-                        v.x = bn_dy1(v.x, yv[i].x, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        v.y = bn_dy1(v.y, yv[i].y, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        v.z = bn_dy1(v.z, yv[i].z, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        v.w = bn_dy1(v.w, yv[i].w, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        if (blk.y == 0 && p.dy_out != nullptr)
-                            *reinterpret_cast<float4*>(dyo + (dg[s0 + i] >> 2)) = v;
+                        v = bn_dy4<CO_T>(v, yv[i], al, ad, lbn, c, p.bn_relu);
+                        if (writes_dy_out(p.dy_out, blk.y)) *reinterpret_cast<float4*>(dyo + (dg[s0 + i] >> 2)) = v;
                     }
-                    float* dst = ld + (dl[s0 + i] & 0xffffu);
-                    {
-                        dst[0] = v.x;
-                        dst[1] = v.y;
-                        dst[2] = v.z;
-                        dst[3] = v.w;
-                    }
+                    lds_put4(ld + (dl[s0 + i] & 0xffffu), v);
                 }
             }
             // the next item's image, asked for by load_item(item): the newest of its loads, so this wait is the last
-            if (tabbed && dhalf == 0 && st + 1 == tiles && item + 1 < last && tid < CO_T) {
+            if (tabbed && dhalf == 0 && it.t + 1 == tiles && item + 1 < last && tid < CO_T) {
                 lal[(sn + 1) & 1][tid] = tal;
                 lal[(sn + 1) & 1][CO_T + tid] = tad;
             }
@@ -902,31 +959,12 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
         float* ld = lds + XSZ;
         // scalar staging for ragged shapes
         for (int item = first; item < last; ++item) {
-            const int n = item / tiles, t = item - n * tiles;
-            const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
-            const float* xin = p.x + (size_t)n * p.cin * hw;
-            const float* din = p.dy + (size_t)n * p.cout * hw;
+            const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
             __syncthreads();
-            for (int e = tid; e < CI_T * PW * PH; e += NT) {
-                const int c = e / (PW * PH), rem = e - c * (PW * PH);
-                const int py = rem / PW, px = rem - py * PW;
-                const int gc = ci0 + c, gy = ty0 + py - 1, gx = tx0 + px - 1;
-                float v = 0.f;
-                if (gc < p.cin && gy >= 0 && gy < p.h && gx >= 0 && gx < p.wd) {
-                    v = xin[(unsigned)gc * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)gx];
-                    if (pro) v = pro_apply(v, p.in_scale[gc], p.in_shift[gc], p.in_relu);
-                }
-                lx[c * PP + rem] = v;
-            }
-            for (int e = tid; e < CO_T * TW * TH; e += NT) {
-                const int c = e / (TW * TH), rem = e - c * (TW * TH);
-                const int py = rem / TW, px = rem - py * TW;
-                const int gc = co0 + c, gy = ty0 + py, gx = tx0 + px;
-                float v = 0.f;
-                if (gc < p.cout && gy < p.h && gx < p.wd)
-                    v = din[(unsigned)gc * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)gx];
-                ld[c * DP + rem] = v;
-            }
+            stage_x_patch_scalar<TW, TH>(lx, PP, CI_T, p.x + (size_t)it.n * p.cin * hw, ci0, p.cin, it.tx0, it.ty0, p.h,
+                                         p.wd, uhw, p.in_scale, p.in_shift, p.in_relu, tid, NT);
+            stage_dy_tile_scalar<TW, TH>(ld, DP, CO_T, p.dy + (size_t)it.n * p.cout * hw, co0, p.cout, it.tx0, it.ty0,
+                                         p.h, p.wd, uhw, tid, NT);
             __syncthreads();
             compute_quarter(Q0{}, 0);
             compute_quarter(Q1{}, 0);
@@ -938,26 +976,7 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
     // K-split partner waves fold into k = 0 through LDS in the Winograd domain, one (ci,co) block per
     // round (fixed order)
     const int q = w_co * WCI + w_ci;
-#pragma unroll 1
-    for (int k = 1; k < KSPL; ++k) {
-#pragma unroll 1
-        for (int qq = 0; qq < NQ; ++qq) {
-            __syncthreads();
-            if (w_k == k && q == qq) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) lds[(pg * 8 + c) * 1024 + r * 64 + lane] = acc[c][r];
-            }
-            __syncthreads();
-            if (w_k == 0 && q == qq) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[c][r] += lds[(pg * 8 + c) * 1024 + r * 64 + lane];
-            }
-        }
-    }
+    fold_ksplit<8, KSPL, NQ>(acc, lds + pg * 8 * 1024, w_k, q, lane);
 
     // G^T M G.  Each wave applies G on the right to its two position rows (column 3 enters with the
     // sign taken in D): P[0] = M0 + (M1+M2)/2, P[1] = (M1-M2)/2, P[2] = (M1+M2)/2 - M3.  P1 and P2 are
@@ -987,7 +1006,7 @@ __global__ __launch_bounds__(64 * 2 * WCI * WCO * KSPL, 2) void wgrad3_kernel(Wg
             for (int r = 0; r < 16; ++r) {
                 const float p1 = xch[s * 1024 + r * 64 + lane], p2 = xch[(3 + s) * 1024 + r * 64 + lane];
                 const float hs = (p1 + p2) * 0.5f;
-                const int ci = ci0 + w_ci * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+                const int ci = ci0 + w_ci * 32 + mfma32_row(r, khalf);
                 if (ci < p.cin && co < p.cout) {
                     float* o = out + ((size_t)ci * 9 + s) * p.cout + co;
                     if (pg == 0) {
@@ -1031,75 +1050,40 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_smallcin_kernel(WgradArgs p
     const int first = blockIdx.x * p.items_per_split;
     const int last = min(first + p.items_per_split, p.items);
     const int tiles = p.tiles_x * p.tiles_y;
-    const bool pro = p.in_scale != nullptr;
     const bool bn = p.bn_y != nullptr;  // dY = BatchNorm backward of p.dy, formed while staging
     __shared__ float lbn[5 * 32];
-    if (bn) {
-        for (int e = tid; e < 5 * 32; e += kThreads) {
-            const int kk = e / 32, gc = co0 + (e - kk * 32);
-            lbn[e] = gc < p.cout ? p.bn_coef[(size_t)kk * p.cout + gc] : 0.f;
-        }
-    }
+    if (bn) stage_bn_coef<32>(lbn, p.bn_coef, co0, p.cout, tid, kThreads);
     constexpr int ROWS = TH / 4;
     for (int item = first; item < last; ++item) {
-        const int n = item / tiles, t = item - n * tiles;
-        const int tx0 = (t % p.tiles_x) * TW, ty0 = (t / p.tiles_x) * TH;
-        const float* xin = p.x + (size_t)n * p.cin * hw;
+        const TileItem it = tile_item<TW, TH>(item, tiles, p.tiles_x);
+        const int n = it.n;
         const float* din = p.dy + (size_t)n * p.cout * hw;
         __syncthreads();
-        for (int e = tid; e < p.cin * PP; e += kThreads) {
-            const int c = e / PP, rem = e - c * PP;
-            const int py = rem / PW, px = rem - py * PW;
-            const int gy = ty0 + py - 1, gx = tx0 + px - 1;
-            float v = 0.f;
-            if (gy >= 0 && gy < p.h && gx >= 0 && gx < p.wd) {
-                v = xin[(unsigned)c * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)gx];
-                if (pro) v = pro_apply(v, p.in_scale[c], p.in_shift[c], p.in_relu);
-            }
-            lx[e] = v;
-        }
+        stage_x_patch_scalar<TW, TH>(lx, PP, p.cin, p.x + (size_t)n * p.cin * hw, 0, p.cin, it.tx0, it.ty0, p.h, p.wd,
+                                     uhw, p.in_scale, p.in_shift, p.in_relu, tid, kThreads);
         if (p.vec_ok) {
 #pragma unroll
             for (int i = 0; i < 32 * TH * TW4 / kThreads; ++i) {
-                const int e = tid + i * kThreads;
-                const int c = e / (TH * TW4), rem = e - c * (TH * TW4);
-                const int py = rem / TW4, slot = rem - py * TW4;
-                const int gc = co0 + c, gy = ty0 + py;
+                const Slot4 s = slot4<TH, TW4>(tid + i * kThreads);
+                const int gc = co0 + s.c, gy = it.ty0 + s.py;
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (gc < p.cout && gy < p.h) {
-                    const size_t off = (size_t)gc * uhw + (size_t)gy * p.wd + tx0 + 4 * slot;
+                    const size_t off = (size_t)gc * uhw + (size_t)gy * p.wd + it.tx0 + 4 * s.slot;
                     v = *reinterpret_cast<const float4*>(din + off);
                     if (bn) {
                         const float4 yv = *reinterpret_cast<const float4*>(
                             p.bn_y + (size_t)n * p.cout * hw + off);
                         const float al = p.bn_alpha ? p.bn_alpha[(size_t)n * p.cout + gc] : 1.f;
                         const float ad = p.bn_add ? p.bn_add[(size_t)n * p.cout + gc] : 0.f;
-                        const float c0 = lbn[c], c1 = lbn[32 + c], c2 = lbn[64 + c], c3 = lbn[96 + c],
-                                    c4 = lbn[128 + c];
-                        v.x = bn_dy1(v.x, yv.x, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        v.y = bn_dy1(v.y, yv.y, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        v.z = bn_dy1(v.z, yv.z, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        v.w = bn_dy1(v.w, yv.w, al, ad, c0, c1, c2, c3, c4, p.bn_relu);
-                        if (blockIdx.y == 0 && p.dy_out != nullptr)
+                        v = bn_dy4<32>(v, yv, al, ad, lbn, s.c, p.bn_relu);
+                        if (writes_dy_out(p.dy_out, blockIdx.y))
                             *reinterpret_cast<float4*>(p.dy_out + (size_t)n * p.cout * hw + off) = v;
                     }
                 }
-                float* dst = ld + c * DP + rem * 4;
-                dst[0] = v.x;
-                dst[1] = v.y;
-                dst[2] = v.z;
-                dst[3] = v.w;
+                lds_put4(ld + s.c * DP + s.rem * 4, v);
             }
         } else {
-            for (int e = tid; e < 32 * TW * TH; e += kThreads) {
-                const int c = e / (TW * TH), rem = e - c * (TW * TH);
-                const int py = rem / TW, px = rem - py * TW;
-                const int gc = co0 + c, gy = ty0 + py, gx = tx0 + px;
-                float v = 0.f;
-                if (gc < p.cout && gy < p.h && gx < p.wd)
-                    v = din[(unsigned)gc * uhw + (unsigned)gy * (unsigned)p.wd + (unsigned)gx];
-                ld[c * DP + rem] = v;
-            }
+            stage_dy_tile_scalar<TW, TH>(ld, DP, 32, din, co0, p.cout, it.tx0, it.ty0, p.h, p.wd, uhw, tid, kThreads);
         }
         __syncthreads();
 #pragma unroll
@@ -1113,24 +1097,14 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad_smallcin_kernel(WgradArgs p
             }
         }
     }
-    // fold the 4 row-split waves through LDS
-#pragma unroll 1
-    for (int k = 1; k < 4; ++k) {
-        __syncthreads();
-        if (wid == k)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) lds[r * 64 + lane] = acc[r];
-        __syncthreads();
-        if (wid == 0)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] += lds[r * 64 + lane];
-    }
+    // the 4 row-split waves fold as a K-split of one (ci, co) block
+    fold_ksplit<1, 4, 1>(&acc, lds, wid, 0, lane);
     if (wid == 0) {
         float* out = p.part + (size_t)blockIdx.x * p.cin * 9 * p.cout;
         const int co = co0 + j;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kidx = (r & 3) + 8 * (r >> 2) + 4 * khalf;  // = ci*9 + tap
+            const int kidx = mfma32_row(r, khalf);  // = ci*9 + tap
             if (kidx < ktot && co < p.cout) out[(size_t)kidx * p.cout + co] = acc[r];
         }
     }
@@ -1153,12 +1127,19 @@ __global__ __launch_bounds__(kThreads) void slab_reduce_kernel(const float* __re
     }
 }
 
+// The tile variants, stated once: plan_wgrad's cost loop and both dispatches (launch_wgrad) walk this table.  A
+// variant's id is its index (bench.py labels kernels by it): it runs wgrad3_kernel (3x3) or wgrad_mfma_kernel (1x1) as
+// <tw, th, ci_t / 32, co_t / 32, kspl>.
 struct WgVariant {
     int tw, th, ci_t, co_t, kspl;
 };
 constexpr WgVariant kWgVariants[] = {{32, 4, 32, 32, 4}, {16, 8, 32, 64, 2}, {16, 4, 64, 64, 1},
                                      {28, 2, 64, 64, 1}};
-constexpr int kWgSmallCin = 5;  // variant id of wgrad_smallcin_kernel<32, 8> (4 is not used)
+constexpr int kNumWgVariants = (int)(sizeof(kWgVariants) / sizeof(kWgVariants[0]));
+// wgrad_smallcin_kernel: its tile (4 waves split the rows; the (ci, tap) pairs are the one 32-row ci block) and its
+// variant id (4 is not used)
+constexpr WgVariant kWgSmallCinTile = {32, 8, 32, 32, 4};
+constexpr int kWgSmallCin = 5;
 
 // wgrad3 uses more than the 64 KB of LDS a kernel gets by default: raise the limit once
 // TAB: the launch passes per-image alpha / add (the kernel's LDS table)
@@ -1184,55 +1165,50 @@ int launch_wgrad3(const WgradArgs& a, dim3 grid, hipStream_t s) {
     return launch_wgrad3_tab<TW, TH, WCI, WCO, KSPL, false>(a, grid, s);
 }
 
-int launch_wgrad(int ksize, int variant, const WgradArgs& a, dim3 grid, hipStream_t s) {
-    if (ksize == 3) {
-        switch (variant) {
-            case 0: return launch_wgrad3<32, 4, 1, 1, 4>(a, grid, s);
-            case 1: return launch_wgrad3<16, 8, 1, 2, 2>(a, grid, s);
-            case 2: return launch_wgrad3<16, 4, 2, 2, 1>(a, grid, s);
-            case 3: return launch_wgrad3<28, 2, 2, 2, 1>(a, grid, s);
-            default: return LF_ERR_INVALID;
-        }
+// Variant `variant` of the KS x KS kernel: a compile-time walk over kWgVariants, one instantiation per entry
+template <int KS, int V = 0>
+int launch_wgrad(int variant, const WgradArgs& a, dim3 grid, hipStream_t s) {
+    if constexpr (V == kNumWgVariants) {
+        return LF_ERR_INVALID;
     } else {
-        switch (variant) {
-            case 0: wgrad_mfma_kernel<32, 4, 1, 1, 4><<<grid, kThreads, 0, s>>>(a); break;
-            case 1: wgrad_mfma_kernel<16, 8, 1, 2, 2><<<grid, kThreads, 0, s>>>(a); break;
-            case 2: wgrad_mfma_kernel<16, 4, 2, 2, 1><<<grid, kThreads, 0, s>>>(a); break;
-            case 3: wgrad_mfma_kernel<28, 2, 2, 2, 1><<<grid, kThreads, 0, s>>>(a); break;
-            default: return LF_ERR_INVALID;
+        if (variant != V) return launch_wgrad<KS, V + 1>(variant, a, grid, s);
+        constexpr WgVariant k = kWgVariants[V];
+        if constexpr (KS == 3) {
+            return launch_wgrad3<k.tw, k.th, k.ci_t / 32, k.co_t / 32, k.kspl>(a, grid, s);
+        } else {
+            wgrad_mfma_kernel<k.tw, k.th, k.ci_t / 32, k.co_t / 32, k.kspl><<<grid, kThreads, 0, s>>>(a);
+            return LF_OK;
         }
     }
-    return LF_OK;
 }
 
 struct WgPlan {
     int variant, tw, tiles_x, tiles_y, items, splits, items_per_split, gy, gz;
 };
 
+// Variant v (tile k) on a shape: its tiles and channel blocks, and what plan_wgrad minimises, the work padded to them
+long long tile_shape(WgPlan& pl, int v, const WgVariant& k, int cin, int cout, int h, int w) {
+    pl.variant = v;
+    pl.tw = k.tw;
+    pl.tiles_x = (w + k.tw - 1) / k.tw;
+    pl.tiles_y = (h + k.th - 1) / k.th;
+    pl.gy = (cin + k.ci_t - 1) / k.ci_t;
+    pl.gz = (cout + k.co_t - 1) / k.co_t;
+    return (long long)pl.tiles_x * k.tw * pl.tiles_y * k.th * pl.gy * k.ci_t * pl.gz * k.co_t;
+}
+
 WgPlan plan_wgrad(int n, int cin, int cout, int h, int w, int ksize) {
     WgPlan best{};
     if (ksize == 3 && cin * 9 <= 32) {
-        best.variant = kWgSmallCin;
-        best.tw = 32;
-        best.tiles_x = (w + 31) / 32;
-        best.tiles_y = (h + 7) / 8;
-        best.gy = 1;
-        best.gz = (cout + 31) / 32;
+        tile_shape(best, kWgSmallCin, kWgSmallCinTile, cin, cout, h, w);
     } else {
         long long best_cost = -1;
-        for (int v = 0; v < (int)(sizeof(kWgVariants) / sizeof(kWgVariants[0])); ++v) {
-            const WgVariant& k = kWgVariants[v];
-            const long long tx = (w + k.tw - 1) / k.tw, ty = (h + k.th - 1) / k.th;
-            const long long gy = (cin + k.ci_t - 1) / k.ci_t, gz = (cout + k.co_t - 1) / k.co_t;
-            const long long cost = tx * k.tw * ty * k.th * gy * k.ci_t * gz * k.co_t;
+        for (int v = 0; v < kNumWgVariants; ++v) {
+            WgPlan cand{};
+            const long long cost = tile_shape(cand, v, kWgVariants[v], cin, cout, h, w);
             if (best_cost < 0 || cost < best_cost) {
                 best_cost = cost;
-                best.variant = v;
-                best.tw = k.tw;
-                best.tiles_x = (int)tx;
-                best.tiles_y = (int)ty;
-                best.gy = (int)gy;
-                best.gz = (int)gz;
+                best = cand;
             }
         }
     }
@@ -1245,6 +1221,13 @@ WgPlan plan_wgrad(int n, int cin, int cout, int h, int w, int ksize) {
     best.items_per_split = (best.items + splits - 1) / splits;
     best.splits = (best.items + best.items_per_split - 1) / best.items_per_split;
     return best;
+}
+
+// the "workspace too small" answer of the entries that take one
+int require_workspace(const char* who, size_t have, size_t need) {
+    if (have >= need) return LF_OK;
+    lf::set_error("%s: workspace %zu < %zu bytes", who, have, need);
+    return LF_ERR_WORKSPACE;
 }
 
 // proj_bwd_kernel: Cin 32 or 64 with Cout = 2 Cin (its instantiations), whole items, 32-bit byte offsets within
@@ -1326,11 +1309,8 @@ static int wgrad_launch(const char* who, const float* x, const float* dy, int n,
     LF_REQUIRE((size_t)cin * h * wd < (1ull << 30) && (size_t)cout * h * wd < (1ull << 30),
                "%s: per-image tensor too large for 32-bit offsets", who);
     const WgPlan pl = plan_wgrad(n, cin, cout, h, wd, ksize);
-    if (ws_bytes < lf_conv2d_wgrad_workspace(n, cin, h, wd, cout, ksize)) {
-        lf::set_error("%s: workspace %zu < %zu bytes", who, ws_bytes,
-                      lf_conv2d_wgrad_workspace(n, cin, h, wd, cout, ksize));
-        return LF_ERR_WORKSPACE;
-    }
+    if (const int rc = require_workspace(who, ws_bytes, lf_conv2d_wgrad_workspace(n, cin, h, wd, cout, ksize)))
+        return rc;
     WgradArgs a;
     a.x = x; a.dy = dy; a.part = static_cast<float*>(workspace);
     a.in_scale = in_scale; a.in_shift = in_shift;
@@ -1353,9 +1333,9 @@ static int wgrad_launch(const char* who, const float* x, const float* dy, int n,
     hipStream_t s = lf::as_stream(stream);
     int rc = LF_OK;
     if (pl.variant == kWgSmallCin)
-        wgrad_smallcin_kernel<32, 8><<<grid, kThreads, 0, s>>>(a);
+        wgrad_smallcin_kernel<kWgSmallCinTile.tw, kWgSmallCinTile.th><<<grid, kThreads, 0, s>>>(a);
     else
-        rc = launch_wgrad(ksize, pl.variant, a, grid, s);
+        rc = ksize == 3 ? launch_wgrad<3>(pl.variant, a, grid, s) : launch_wgrad<1>(pl.variant, a, grid, s);
     if (rc != LF_OK) return rc;
     return lf::check_launch(who);
 }
@@ -1426,11 +1406,7 @@ int lf_conv2d_proj_bwd_f32(const float* x, const float* g, const float* bn_y, co
     LF_REQUIRE(x && g && bn_y && coef && w && dx && dw && workspace, "%s: null buffer", who);
     LF_REQUIRE(lf_conv2d_proj_bwd_supported(x, g, bn_y, w, dx, n, cin, h, wd, cout),
                "%s: shape/alignment not supported (ask lf_conv2d_proj_bwd_supported first)", who);
-    if (ws_bytes < lf_conv2d_proj_bwd_workspace(n, cin, h, wd, cout)) {
-        lf::set_error("%s: workspace %zu < %zu bytes", who, ws_bytes,
-                      lf_conv2d_proj_bwd_workspace(n, cin, h, wd, cout));
-        return LF_ERR_WORKSPACE;
-    }
+    if (const int rc = require_workspace(who, ws_bytes, lf_conv2d_proj_bwd_workspace(n, cin, h, wd, cout))) return rc;
     const ProjPlan pl = plan_proj_bwd(n, cin, h, wd);
     ProjBwdArgs a;
     a.x = x; a.g = g; a.bn_y = bn_y; a.coef = coef; a.w = w; a.dx = dx;

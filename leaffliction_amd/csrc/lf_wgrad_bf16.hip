@@ -283,12 +283,8 @@ __global__ __launch_bounds__((WgShape<TAPS, TW, TH, CIB, COB, STEM, WPRQ>::NT), 
                                 c4 = lbn[128 * COB + c];
                     const float al = gated ? lal[c] : 1.f, ad = gated ? lal[32 * COB + c] : 0.f;
 #pragma unroll
-                    for (int e = 0; e < G; ++e) {
-                        const float yv = lf::bf16_at(ry[k][i], e);
-                        float dz = fmaf(gv[e], al, ad);
-                        if (p.bn_relu && !(fmaf(yv, c0, c1) > 0.f)) dz = 0.f;
-                        gv[e] = fmaf(c2, dz, fmaf(c3, yv, c4));
-                    }
+                    for (int e = 0; e < G; ++e)
+                        gv[e] = lf::bn_dy1(gv[e], lf::bf16_at(ry[k][i], e), al, ad, c0, c1, c2, c3, c4, p.bn_relu);
                     if (p.dy_out != nullptr && blockIdx.y == 0) {
                         uvec o;
 #pragma unroll

@@ -35,6 +35,10 @@ SHAPES = [  # n, cin, cout, h, w, k
     (2, 32, 64, 32, 32, 1),    # 1x1 projection
     (1, 128, 256, 28, 28, 1),
     (3, 8, 40, 17, 5, 1),
+    (2, 3, 8, 9, 11, 3),       # small-Cin kernel, scalar dY staging (W % 32 != 0): partial tiles, Cout < 32
+    (1, 2, 40, 10, 36, 3),     # the same with a partial second Cout block and a second tile column
+    (2, 24, 40, 6, 32, 3),     # vector staging, variant 0 (32 x 4): Cin < a block, partial Cout block and tile row
+    (2, 24, 40, 6, 32, 1),     # the same through the 1x1 kernel (variant 0)
 ]
 
 
@@ -143,7 +147,9 @@ BN_WGRAD_SHAPES = [  # n, cin, cout, h, w, with_se, k, relu
     (2, 3, 32, 64, 64, False, 3, True),     # stem: small-Cin kernel
     (2, 32, 64, 32, 32, False, 1, False),   # 1x1 projection BN (no ReLU)
     (2, 64, 128, 56, 56, False, 1, False),
-    (2, 16, 24, 20, 12, True, 3, True)]     # unsupported -> fallback
+    (2, 16, 24, 20, 12, True, 3, True),     # unsupported -> fallback
+    (2, 24, 40, 6, 32, True, 3, True),      # variant 0: alpha/add table of a partial Cout block, partial tile row
+    (2, 24, 40, 6, 32, False, 1, False)]    # the same masks in the 1x1 kernel
 
 
 @pytest.mark.parametrize("n,cin,cout,h,w,with_se,k,relu", BN_WGRAD_SHAPES)
