@@ -210,7 +210,9 @@ __global__ __launch_bounds__(kBlock) void warp_bicubic_tile_kernel(const uint8_t
         __syncthreads();
     }
     const int rlo = axis ? srange[0] : 0, rhi = axis ? srange[1] : -1;
-    const int nrows = rhi - rlo + 1;
+    // a tile without a valid output row (srange = {INT_MAX, -1}) stages nothing: rhi - rlo + 1 is then about
+    // -2^31, and times kTX it wrapped to +32, which sent phase 1 to source row INT_MAX
+    const int nrows = rhi >= rlo ? rhi - rlo + 1 : 0;
     if (!axis || nrows > kTileRows) {
         // general map inside a hinted batch, or a strong down-scale: per-pixel path
         for (int i = tid; i < kTX * kTY; i += kBlock) {

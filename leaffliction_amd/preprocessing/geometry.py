@@ -22,6 +22,13 @@ LANCZOS_SUPPORT = 3.0
 def rotate_expand_matrix(w: int, h: int, angle_deg: float) -> Tuple[List[float], int, int]:
     """Inverse affine matrix and expanded canvas of `Image.rotate(angle, expand=True)`."""
     angle = angle_deg % 360.0
+    if angle in (90.0, 270.0):
+        # Image.rotate transposes here (ROTATE_90 / ROTATE_270) instead of resampling.  When w - h is even the
+        # formulas below land on this very matrix; when it is odd the centre of rotation sits half a pixel off
+        # the grid and they give a canvas one pixel larger, with a border of fill that Pillow never draws.
+        if angle == 90.0:
+            return [0.0, -1.0, float(w), 1.0, 0.0, 0.0], h, w
+        return [0.0, 1.0, 0.0, -1.0, 0.0, float(h)], h, w
     cx, cy = w / 2, h / 2
     a = -math.radians(angle)
     m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0,
