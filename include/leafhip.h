@@ -1205,6 +1205,36 @@ int lf_calib_stats(const float* probs, const int32_t* labels, int n, int c, cons
 int lf_calib_apply_f32(const float* probs, double beta, float* out, float* conf, int32_t* top, int n, int c,
                        lf_stream_t stream);
 
+/* ---- Novelty score: Mahalanobis distance of the pooled features to the nearest class ---- */
+/* feat f32 [n][d] are rows of the network's pooled feature vector (GlobalAveragePooling's output).  Both calls: n > 0,
+ * d a multiple of 16 with 16 <= d <= 256, 1 <= c <= 4096; anything else returns -1 with a message before any launch.
+ *
+ * lf_feat_moments: the sums a per-class Gaussian fit with one shared covariance needs, in float64.  labels i32 [n].
+ * The call ADDS INTO four device accumulators (8-byte aligned; a fit is many calls, one per forward pass):
+ *   count   i64 [c]     rows of class k
+ *   skipped i64 [1]     rows whose label lies outside [0, c): they are counted here and nowhere else
+ *   sum     f64 [c][d]  sum of the rows of class k
+ *   gram    f64 [d][d]  sum_r f_r f_r^T over the counted rows, the full symmetric matrix
+ * A product of two f32 values is exact in f64, so only the additions round.  Every output element has one owner,
+ * which adds the rows in ascending order from 0 and then adds that partial to the accumulator: the same calls give
+ * the same bits.  No float goes through an atomic (skipped is counted with an integer one).  The Gram matrix is
+ * computed on the f64 matrix cores (v_mfma_f64_16x16x4_f64) in upper 16 x 16 tiles, four rows to an instruction;
+ * the tiles below the diagonal receive the transposed partial of their mirror tile.
+ *
+ * lf_maha_score_f32: mu0 f32 [d] (the pooled mean), w f32 [d][d] row-major (the whitening matrix; 16-byte aligned),
+ * m f32 [c][d] (the whitened, centred class means).  In f32:
+ *   t_j     = feat[i][j] - mu0[j]
+ *   z_k     = sum_j w[k][j] t_j       an fmaf chain from 0 (v_mfma_f32_32x32x2_f32) in the order j = 0, d/2, 1,
+ *                                     d/2 + 1, ..., d/2 - 1, d - 1
+ *   d2[i][k] = sum_j (z_j - m[k][j])^2   an fmaf chain from 0 in the order j = 0 .. d - 1; a non-finite value
+ *                                     (NaN or inf) is stored and read as +inf
+ *   score[i] = min_k d2[i][k], nearest[i] = the lowest k attaining it; a row with no finite d2 gets (+inf, 0).
+ * d2 f32 [n][c] may be null; score f32 [n]; nearest i32 [n]. */
+int lf_feat_moments(const float* feat, const int32_t* labels, int n, int d, int c, long long* count,
+                    long long* skipped, double* sum, double* gram, lf_stream_t stream);
+int lf_maha_score_f32(const float* feat, const float* mu0, const float* w, const float* m, int n, int d, int c,
+                      float* d2, float* score, int32_t* nearest, lf_stream_t stream);
+
 /* ---- Near-duplicate search: 128-bit difference hashes and their all-pairs Hamming search ---- */
 /* Integer and exact throughout; no float appears.
  *

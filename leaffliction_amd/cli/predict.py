@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--montage] [--tta PRESET]
-[--calibrated] [--evaluate ...]`.
+[--calibrated] [--novelty] [--evaluate ...]`.
 
 Flags, JSON schema (`batch_results` + `summary`), the sampled accuracy gate and the exit
 codes (1 on error, 2 when the gate is never reached) follow srcs/cli/predict.py:17-87,
@@ -18,6 +18,10 @@ their keys and `summary` gains `tta` and `mean_view_agreement`.
 the temperature `<learnings>/calibration.json` holds (fitted by cli.calibrate or train --calibrate; exit status 1
 without the file), after the views' mean with --tta.  No prediction, view agreement or heat map changes; `summary`
 gains `calibration`.
+`--novelty` (not in the reference), in every mode but --cam and --tta, also together with --calibrated: every result
+gains `novelty_score` (squared Mahalanobis distance of the pooled features to the nearest class mean),
+`novelty_threshold`, `known` (score <= threshold) and `nearest_class`, from `<learnings>/novelty.json` and `novelty.npz`
+(fitted by cli.novelty; exit status 1 without them); `summary` gains `novelty`.  No prediction or probability changes.
 """
 from __future__ import annotations
 
@@ -62,6 +66,9 @@ def parse_args(argv=None):
                    help="test-time augmentation: average the prediction over this preset's views of every image")
     p.add_argument("--calibrated", action="store_true",
                    help="report confidences at the temperature of <learnings>/calibration.json")
+    p.add_argument("--novelty", action="store_true",
+                   help="also say whether each picture is one of the model's classes at all "
+                        "(<learnings>/novelty.json, fitted by cli.novelty)")
     return p.parse_args(argv)
 
 
@@ -75,6 +82,10 @@ def validate_inputs(args):
         raise ValueError("--montage cannot be combined with --cam")
     if args.tta and args.cam:
         raise ValueError("--tta cannot be combined with --cam (a heat map belongs to one view)")
+    if args.novelty and args.tta:
+        raise ValueError("--novelty cannot be combined with --tta (a score over several views is not defined)")
+    if args.novelty and args.cam:
+        raise ValueError("--novelty cannot be combined with --cam")
     if args.cam and not 0.0 <= args.cam_alpha <= 1.0:
         raise ValueError(f"--cam-alpha must lie in [0, 1], got {args.cam_alpha}")
     if not image_path.exists():
@@ -90,6 +101,10 @@ def validate_inputs(args):
     if args.calibrated and not (learnings_dir / "calibration.json").exists():
         raise FileNotFoundError(f"Calibration file not found: {learnings_dir / 'calibration.json'} "
                                 "(fit one with cli.calibrate or train --calibrate)")
+    if args.novelty:
+        for name in ("novelty.json", "novelty.npz"):
+            if not (learnings_dir / name).exists():
+                raise FileNotFoundError(f"Novelty file not found: {learnings_dir / name} (fit one with cli.novelty)")
     if args.evaluate:
         if not args.batch_mode:
             raise ValueError("--evaluate requires --batch-mode")
@@ -119,17 +134,31 @@ def calibration_summary(predictor):
     return {"temperature": float(data["temperature"]), "fitted_with_tta": data.get("fitted_on", {}).get("tta")}
 
 
-def save_batch_results_json(results, processing_time, output_path, tta=None, calibration=None):
+NOVELTY_KEYS = ("novelty_score", "novelty_threshold", "known", "nearest_class")
+
+
+def novelty_summary(predictor, results):
+    """`summary.novelty` of a predictor that scores novelty, None of any other."""
+    data = getattr(predictor, "novelty_data", None)
+    if data is None:
+        return None
+    return {"threshold": float(data["threshold"]), "quantile": float(data["quantile"]),
+            "unknown_count": sum(1 for r in results if r.get("known") is False)}
+
+
+def save_batch_results_json(results, processing_time, output_path, tta=None, calibration=None, novelty=None):
     """tta (the preset, when the predictions are test-time-augmented ones): `summary` also says so and gives the mean
     of the results' view agreement.  calibration (calibration_summary, when the confidences are calibrated ones):
-    `summary.calibration`."""
+    `summary.calibration`.  novelty (novelty_summary, when the results carry a novelty score): `summary.novelty`, and
+    every entry of `batch_results` keeps its NOVELTY_KEYS."""
     output_path = Path(output_path)
     if not output_path.is_absolute() and not str(output_path).startswith("artifacts/"):
         output_path = Path("artifacts/prediction_output") / output_path.name
     data = {"batch_results": [{"image_path": str(r["image_path"]),
                                "top_prediction": r["top_prediction"],
                                "confidence": r["confidence"],
-                               "all_probabilities": r["all_probabilities"]} for r in results],
+                               "all_probabilities": r["all_probabilities"],
+                               **({k: r[k] for k in NOVELTY_KEYS} if novelty is not None else {})} for r in results],
             "summary": create_batch_summary(results, processing_time)}
     if tta is not None:
         seen = [r["view_agreement"] for r in results if r.get("view_agreement") is not None]
@@ -137,6 +166,8 @@ def save_batch_results_json(results, processing_time, output_path, tta=None, cal
         data["summary"]["mean_view_agreement"] = sum(seen) / len(seen) if seen else None
     if calibration is not None:
         data["summary"]["calibration"] = calibration
+    if novelty is not None:
+        data["summary"]["novelty"] = novelty
     output_path.parent.mkdir(parents=True, exist_ok=True)
     with open(output_path, "w") as f:
         json.dump(data, f, indent=2)
@@ -258,7 +289,8 @@ def run_sampling_enforced_batch(predictor, image_dir: Path, manifest_path: Path,
                 return True
             if json_output:
                 saved = save_batch_results_json(results, proc, json_output, tta=getattr(predictor, "tta", None),
-                                                calibration=calibration_summary(predictor))
+                                                calibration=calibration_summary(predictor),
+                                                novelty=novelty_summary(predictor, results))
                 logger.info("Results saved to: %s", saved)
             try:
                 PredictionEvaluator(predictor).evaluate_predictions(
@@ -279,7 +311,7 @@ def main(argv=None) -> None:
         args = parse_args(argv)
         image_path, learnings_dir = validate_inputs(args)
         rk = init_from_env()   # replicas under torch.distributed.run; one process otherwise
-        predictor = Predictor(learnings_dir, tta=args.tta, calibrated=args.calibrated)
+        predictor = Predictor(learnings_dir, tta=args.tta, calibrated=args.calibrated, novelty=args.novelty)
         predictor.load()
         if args.batch_mode:
             if args.evaluate:
@@ -313,7 +345,8 @@ def main(argv=None) -> None:
             if args.montage:
                 logger.info("Montages saved under: %s", Path(args.output_dir) / "montage")
             out = save_batch_results_json(results, proc, args.json_output, tta=args.tta,
-                                          calibration=calibration_summary(predictor))
+                                          calibration=calibration_summary(predictor),
+                                          novelty=novelty_summary(predictor, results))
             logger.info("Results saved to: %s", out)
             for k, v in create_batch_summary(results, proc).items():
                 logger.info("  %s: %s", k, v)
@@ -329,6 +362,10 @@ def main(argv=None) -> None:
             logger.info(f"Prediction: {r['top_prediction']} ({r['confidence']:.2%})")
             if args.calibrated:
                 logger.info(f"Calibrated at temperature {predictor.calibration['temperature']:.4f}")
+            if args.novelty:
+                logger.info(f"Novelty score: {r['novelty_score']:.4g} (threshold {r['novelty_threshold']:.4g}): "
+                            f"{'known' if r['known'] else 'UNKNOWN: not one of the trained classes'}; nearest class "
+                            f"{r['nearest_class']}")
             if args.tta:
                 logger.info(f"Views agreeing ({args.tta}): {r['view_agreement']:.0%}")
             for name, prob in sorted(r["all_probabilities"].items(), key=lambda x: -x[1])[:3]:

@@ -1,5 +1,6 @@
 // Wave and workgroup reductions, the plane kernels' storage helpers and the head's class limit, stated once for the
-// units that reduce over a 64-lane wave: lf_nn.hip, lf_tta.hip, lf_calib.hip, lf_cam.hip and lf_augment.hip.  The
+// units that reduce over a 64-lane wave: lf_nn.hip, lf_tta.hip, lf_calib.hip, lf_cam.hip, lf_novelty.hip and
+// lf_augment.hip.  The
 // tests derive their error bounds from these exact shuffle patterns and orders.  An inline helper is compiled with
 // the flags of the unit that includes it (lf_tta, lf_calib and lf_augment are built without FMA contraction); none of
 // them contains a product-sum, so the bits are the same everywhere.
@@ -51,6 +52,13 @@ __device__ __forceinline__ float wave_max_all(float v) {
 // the larger of two (value, index) pairs; the lower index on equal values (np.argmax)
 __device__ __forceinline__ void take_larger(float& bv, int& bi, float ov, int oi) {
     if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+    }
+}
+// its twin: the smaller of two (value, index) pairs; the lower index on equal values (np.argmin)
+__device__ __forceinline__ void take_smaller(float& bv, int& bi, float ov, int oi) {
+    if (ov < bv || (ov == bv && oi < bi)) {
         bv = ov;
         bi = oi;
     }

@@ -1281,6 +1281,16 @@ class LeafCNN:
         probs, _ = self.forward(x0, False)
         return probs
 
+    @torch.no_grad()
+    def features_device(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
+        """predict_device(x) with the vector the dense head saw: (probs [N,C], g [N,widths[-1]]), the probability rows
+        and GlobalAveragePooling's output of that same pass (f32, bf16 and separable models alike: both inference
+        paths leave g in the buffer "g" of batch N).  Device tensors of their own, which the next forward pass does
+        not overwrite."""
+        probs = self.predict_device(x)
+        n = probs.shape[0]
+        return probs.clone(), self._buf(n, "g", (n, self.widths[-1])).clone()
+
     TTA_PASS_ROWS = 1024   # the most rows (images x views) one forward pass of predict_tta_device sees
 
     @torch.no_grad()

@@ -787,6 +787,81 @@ def calib_apply(probs: torch.Tensor, beta, out: Optional[torch.Tensor] = None
     return out, conf, top
 
 
+NOVELTY_MAX_DIM = 256
+NOVELTY_DIM_STEP = 16
+NOVELTY_MAX_CLASSES = 4096
+NOVELTY_STATE = (("count", torch.int64), ("skipped", torch.int64), ("sum", torch.float64), ("gram", torch.float64))
+
+
+def novelty_dim_ok(d: int) -> bool:
+    """Whether the novelty kernels take feature rows of d floats."""
+    return NOVELTY_DIM_STEP <= d <= NOVELTY_MAX_DIM and d % NOVELTY_DIM_STEP == 0
+
+
+def _novelty_feat(who: str, feat: torch.Tensor) -> Tuple[int, int]:
+    _chk(feat, _F32, f"{who}.feat", 2)
+    n, d = feat.shape
+    if n == 0 or not novelty_dim_ok(d):
+        raise ValueError(f"{who}.feat: [N,D] with N > 0 and D a multiple of {NOVELTY_DIM_STEP} in "
+                         f"{NOVELTY_DIM_STEP}..{NOVELTY_MAX_DIM} expected, got {tuple(feat.shape)}")
+    return n, d
+
+
+def _novelty_classes(who: str, c) -> int:
+    c = int(c)
+    if not 1 <= c <= NOVELTY_MAX_CLASSES:
+        raise ValueError(f"{who}: {c} classes (1..{NOVELTY_MAX_CLASSES})")
+    return c
+
+
+def feat_moments(feat: torch.Tensor, labels: torch.Tensor, num_classes: int, state: Optional[dict] = None) -> dict:
+    """The float64 sums of a Mahalanobis fit, added into `state` (lf_feat_moments; the rule: include/leafhip.h): feat
+    f32 [N,D] and labels int32 [N] on the GPU.  state: {"count" int64 [C], "skipped" int64 [1], "sum" f64 [C,D],
+    "gram" f64 [D,D]} on feat's device, created zeroed when None; returned.  A row whose label lies outside [0, C)
+    counts in `skipped` alone.  No sync."""
+    n, d = _novelty_feat("feat_moments", feat)
+    c = _novelty_classes("feat_moments.num_classes", num_classes)
+    _chk(labels, torch.int32, "feat_moments.labels", 1)
+    if labels.shape[0] != n or labels.device != feat.device:
+        raise ValueError(f"feat_moments.labels: expected [{n}] on {feat.device}, got {tuple(labels.shape)} on "
+                         f"{labels.device}")
+    shapes = {"count": (c,), "skipped": (1,), "sum": (c, d), "gram": (d, d)}
+    if state is None:
+        state = {k: torch.zeros(shapes[k], dtype=dt, device=feat.device) for k, dt in NOVELTY_STATE}
+    if not isinstance(state, dict):
+        raise TypeError(f"feat_moments.state: a dict of {', '.join(k for k, _dt in NOVELTY_STATE)} expected")
+    for k, dt in NOVELTY_STATE:
+        t = state.get(k)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"feat_moments.state: no tensor {k!r}")
+        if t.dtype != dt:
+            raise TypeError(f"feat_moments.state.{k}: expected {dt}, got {t.dtype}")
+        if tuple(t.shape) != shapes[k] or not t.is_contiguous() or t.device != feat.device:
+            raise ValueError(f"feat_moments.state.{k}: a contiguous {shapes[k]} tensor on {feat.device} expected, got "
+                             f"{tuple(t.shape)} on {t.device}")
+    _lib.call("lf_feat_moments", feat.data_ptr(), labels.data_ptr(), n, d, c, state["count"].data_ptr(),
+              state["skipped"].data_ptr(), state["sum"].data_ptr(), state["gram"].data_ptr(), _stream())
+    return state
+
+
+def maha_score(feat: torch.Tensor, mu0: torch.Tensor, W: torch.Tensor, M: torch.Tensor, want_d2: bool = False
+               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Squared distance to the nearest whitened class mean (lf_maha_score_f32; the rule: include/leafhip.h): feat f32
+    [N,D], mu0 f32 [D], W f32 [D,D] row-major and M f32 [C,D] on the GPU -> (score f32 [N] = min_c |W (f - mu0) -
+    M_c|^2, nearest int32 [N] the lowest class attaining it, d2 f32 [N,C] with want_d2 else None).  A non-finite
+    distance reads as +inf; a row with no finite one gets (+inf, 0)."""
+    n, d = _novelty_feat("maha_score", feat)
+    _chk(M, _F32, "maha_score.M", 2)
+    c = _novelty_classes("maha_score.M", M.shape[0])
+    _mix_checks("maha_score", feat, {"mu0": (mu0, (d,)), "W": (W, (d, d)), "M": (M, (c, d))})
+    score = torch.empty((n,), dtype=_F32, device=feat.device)
+    nearest = torch.empty((n,), dtype=torch.int32, device=feat.device)
+    d2 = torch.empty((n, c), dtype=_F32, device=feat.device) if want_d2 else None
+    _lib.call("lf_maha_score_f32", feat.data_ptr(), mu0.data_ptr(), W.data_ptr(), M.data_ptr(), n, d, c, _ptr(d2),
+              score.data_ptr(), nearest.data_ptr(), _stream())
+    return score, nearest, d2
+
+
 DHASH_VARIANTS = (1, 2, 4, 8)
 DHASH_MIN_SIDE, DHASH_MAX_SIDE = 9, 4096
 

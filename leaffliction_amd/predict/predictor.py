@@ -16,6 +16,12 @@ what `masked_arrays` returns for a batch (make_mask and the composite on the GPU
 through `nn.calib_apply` at the inverse temperature DIR/calibration.json holds (predict/calibration.py), after the
 views' mean with a TTA preset.  `confidence` and `all_probabilities` are then the calibrated values; the prediction is
 the argmax of the uncalibrated row and so never moves.
+
+`Predictor(dir, novelty=True)` (not in the reference) also says whether a picture is one of the model's classes at all
+(predict/novelty.py): the pooled feature vector of the pass that made the probabilities (LeafCNN.features_device) goes
+through `nn.maha_score` with what DIR/novelty.npz holds, and every result gains `novelty_score`, `novelty_threshold`,
+`known` (score <= threshold) and `nearest_class`.  No prediction or probability changes.  It cannot be combined with a
+TTA preset or with the heat maps of explain_batch.
 """
 from __future__ import annotations
 
@@ -32,14 +38,20 @@ logger = get_logger(__name__)
 
 
 class Predictor:
-    def __init__(self, learnings_dir, tta=None, calibrated: bool = False):
+    def __init__(self, learnings_dir, tta=None, calibrated: bool = False, novelty: bool = False):
         from .tta import PRESETS
         if tta is not None and tta not in PRESETS:
             raise ValueError(f"unknown TTA preset {tta!r}: one of {', '.join(PRESETS)}")
+        if novelty and tta is not None:
+            raise ValueError("the novelty score cannot be combined with a TTA preset (a score over several views "
+                             "is not defined)")
         self.learnings_dir = Path(learnings_dir)
         self.tta = tta
         self.calibrated = bool(calibrated)
         self.calibration = None   # what calibration.json holds, with calibrated=True and after load()
+        self.novelty = bool(novelty)
+        self.novelty_data = None  # what novelty.json and novelty.npz hold, with novelty=True and after load()
+        self._novelty_dev = None  # (mu0, W, M) on the model's device
         self.model_loader = None
         self._initialized = False
         self._codec = None   # DeviceDecoder of the pooled batch path
@@ -53,9 +65,34 @@ class Predictor:
                 logger.warning("calibration.json was fitted %s, these predictions are made %s: the temperature may "
                                "not suit them", f"with --tta {fitted}" if fitted else "without TTA",
                                f"with --tta {self.tta}" if self.tta else "without TTA")
+        if self.novelty:   # before the model: a missing file fails at once
+            from . import novelty
+            novelty.load(self.learnings_dir)
         self.model_loader = ModelLoader(self.learnings_dir)
         self.model_loader.load()
+        if self.novelty:
+            self._load_novelty()
         self._initialized = True
+
+    def _load_novelty(self) -> None:
+        import torch
+
+        from .. import nn
+        from . import novelty
+        model = self.model_loader.model
+        widths = getattr(model, "widths", None)
+        if getattr(model, "features_device", None) is None or not widths:
+            raise ValueError("the novelty score needs a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
+        if not nn.novelty_dim_ok(int(widths[-1])):
+            raise ValueError(f"the novelty score needs a last width that is a multiple of {nn.NOVELTY_DIM_STEP} in "
+                             f"{nn.NOVELTY_DIM_STEP}..{nn.NOVELTY_MAX_DIM}; this model's is {widths[-1]}")
+        data = novelty.load(self.learnings_dir, dim=int(widths[-1]), labels=self.model_loader.labels)
+        dtype = getattr(model, "infer_dtype", None)
+        if data["infer_dtype"] != dtype:
+            logger.warning("novelty.json was fitted on %s features, these predictions are made in %s: the threshold "
+                           "may not suit them", data["infer_dtype"], dtype)
+        self.novelty_data = data
+        self._novelty_dev = tuple(torch.from_numpy(data[k]).to(model.device) for k in ("mu0", "W", "M"))
 
     def _prepare(self, arrays: List[np.ndarray]) -> np.ndarray:
         import torch
@@ -75,9 +112,10 @@ class Predictor:
                 out[k] = res[j]
         return out
 
-    def _result(self, path, original, probs, agreement=None, top=None) -> Dict[str, Any]:
+    def _result(self, path, original, probs, agreement=None, top=None, nov=None) -> Dict[str, Any]:
         """top: the predicted class where it is not to be taken from `probs` (calibrated rows: two probabilities that
-        differ may round to one float at a high temperature, and the prediction is the uncalibrated row's)."""
+        differ may round to one float at a high temperature, and the prediction is the uncalibrated row's).  nov:
+        (novelty score, row of M nearest) of this picture."""
         labels = self.model_loader.labels
         top = int(np.argmax(probs)) if top is None else int(top)
         result = {"image_path": path, "top_prediction": labels[top], "confidence": float(probs[top]),
@@ -85,6 +123,10 @@ class Predictor:
                   "original_array": original, "processed_array": original}
         if agreement is not None:
             result["view_agreement"] = float(agreement)
+        if nov is not None:
+            thr = float(self.novelty_data["threshold"])
+            result.update(novelty_score=float(nov[0]), novelty_threshold=thr, known=bool(float(nov[0]) <= thr),
+                          nearest_class=labels[self.novelty_data["present"][int(nov[1])]])
         return result
 
     def _calibrate(self, probs):
@@ -96,16 +138,25 @@ class Predictor:
     def _predict_inputs(self, x, step: int):
         """Probabilities [n,C] of model inputs x [n,S,S,3] uint8 (host array or device tensor) as a host array, `step`
         images at a time; the view agreement [n] (agree / v) with a TTA preset set, None without one; and with
-        calibrated=True the predictions [n] (the rows are then the calibrated ones), None without."""
+        calibrated=True the predictions [n] (the rows are then the calibrated ones), None without; and with
+        novelty=True the pairs [n,2] (novelty score, nearest row of M) from the features of the same passes, None
+        without."""
         import torch
         model = self.model_loader.model
-        agreement = None
+        agreement = nov = None
         if self.tta is None:
-            if isinstance(x, np.ndarray) and self.calibration is None:
-                return model.predict(x, batch_size=step), None, None
+            if isinstance(x, np.ndarray) and self.calibration is None and not self.novelty:
+                return model.predict(x, batch_size=step), None, None, None
             if isinstance(x, np.ndarray):
                 x = torch.from_numpy(np.ascontiguousarray(x))
-            probs = torch.cat([model.predict_device(x[b:b + step]).clone() for b in range(0, x.shape[0], step)])
+            if self.novelty:
+                from .. import nn
+                passes = [model.features_device(x[b:b + step]) for b in range(0, x.shape[0], step)]
+                probs = torch.cat([p for p, _g in passes])
+                score, nearest, _d2 = nn.maha_score(torch.cat([g for _p, g in passes]), *self._novelty_dev)
+                nov = np.stack([score.cpu().numpy().astype(np.float64), nearest.cpu().numpy().astype(np.float64)], 1)
+            else:
+                probs = torch.cat([model.predict_device(x[b:b + step]).clone() for b in range(0, x.shape[0], step)])
         else:
             from .tta import view_rows
             rows, weights = view_rows(self.tta, int(x.shape[1]), int(x.shape[2]))
@@ -119,13 +170,14 @@ class Predictor:
             probs, agreement = torch.cat(parts), torch.cat(agree).cpu().numpy() / float(len(rows))
         if self.calibration is not None:
             out, top = self._calibrate(probs)
-            return out, agreement, top
-        return probs.cpu().numpy(), agreement, None
+            return out, agreement, top, nov
+        return probs.cpu().numpy(), agreement, None, nov
 
-    def _results(self, paths, kept, natives, probs, agreement, top) -> List[Dict[str, Any]]:
-        """One result per kept file: row j of probs (agreement, top: [n] or None) belongs to paths[kept[j]]."""
+    def _results(self, paths, kept, natives, probs, agreement, top, nov=None) -> List[Dict[str, Any]]:
+        """One result per kept file: row j of probs (agreement, top, nov: [n] or None) belongs to paths[kept[j]]."""
         return [self._result(paths[k], natives[k], probs[j], None if agreement is None else agreement[j],
-                             None if top is None else top[j]) for j, k in enumerate(kept)]
+                             None if top is None else top[j], None if nov is None else nov[j])
+                for j, k in enumerate(kept)]
 
     def predict_single(self, image_path, use_transform: bool = False) -> Dict[str, Any]:
         """use_transform: `processed_array` is the image on black outside make_mask's mask (masked_arrays) instead
@@ -134,8 +186,7 @@ class Predictor:
             raise RuntimeError("Predictor not initialized. Call load() first.")
         image_path = Path(image_path)
         original = ImageLoader.load_as_array(image_path)
-        probs, agreement, top = self._predict_inputs(self._prepare([original]), 256)
-        result = self._results([image_path], [0], [original], probs, agreement, top)[0]
+        result = self._results([image_path], [0], [original], *self._predict_inputs(self._prepare([original]), 256))[0]
         if use_transform:
             result["processed_array"] = self.masked_arrays([original], [image_path])[0]
         return result
@@ -249,6 +300,26 @@ class Predictor:
             return np.zeros((0, self.model_loader.num_classes), np.float32), []
         return np.concatenate(rows).astype(np.float32, copy=False), indices
 
+    def feature_chunks(self, image_paths):
+        """The pooled feature rows behind predict_batch's probabilities, one forward pass at a time: yields (the
+        indices into image_paths of the pass's files, probs [m,C], g [m,widths[-1]]) as device tensors of their own
+        (LeafCNN.features_device).  Same decoding route as predict_batch; unreadable files are logged and left out.
+        Nothing holds all features.  No TTA preset, no calibration: these are the rows the novelty score is fitted
+        and taken on."""
+        if not self._initialized:
+            raise RuntimeError("Predictor not initialized. Call load() first.")
+        import torch
+        model = self.model_loader.model
+        if getattr(model, "features_device", None) is None:
+            raise ValueError("pooled features need a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
+        paths = [Path(p) for p in image_paths]
+        for kept, x, _natives, step in self._model_inputs(paths, keep_native=False):
+            if isinstance(x, np.ndarray):
+                x = torch.from_numpy(np.ascontiguousarray(x))
+            for b in range(0, x.shape[0], step):
+                probs, g = model.features_device(x[b:b + step])
+                yield kept[b:b + step], probs, g
+
     def _explain_chunk(self, x, step: int, top: int, alpha: float):
         """Probabilities, heat-map overlays and (calibrated=True; else None) predictions of one chunk of model inputs
         x [n,S,S,3] uint8 on the device, the forward pass run in slices of `step` images as the prediction path
@@ -278,6 +349,8 @@ class Predictor:
         if not self._initialized:
             raise RuntimeError("Predictor not initialized. Call load() first.")
         import torch
+        if self.novelty:
+            raise ValueError("the novelty score cannot be combined with class activation maps")
         if getattr(self.model_loader.model, "class_activation_maps", None) is None:
             raise ValueError("class activation maps need a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
         paths = [Path(p) for p in image_paths]
