@@ -1280,6 +1280,24 @@ int lf_hamming_pairs_fill(const int32_t* a, long long a_stride, int na, const in
                           int threshold, int self, const long long* offsets, int chunks, int32_t* out,
                           lf_stream_t stream);
 
+/* ---- residual tail, fp32 training step: the values at the recorded positions kept at pooled size ---- */
+/* lf_block_tail_fwd_f32 (below) that also writes, at pooled size [n][c][h/2][w/2], the raw y and the raw sc at the
+ * window position the route byte records (the first maximum in scan order): y_at and sc_at, either may be null (not
+ * written).  p and route are those of lf_block_tail_fwd_f32, bit for bit.
+ * lf_block_tail_bwd_kept_f32 is lf_block_tail_bwd_f32 (below) reading them: where y_at (sc_at) is given, the sums
+ * take y_at[pooled index] (sc_at[...]) in place of y[recorded position] (sc_y[...]) and y (sc_y) may be null, so the
+ * backward pass reads pooled-size tensors instead of touching every cache line of the full-size planes to use one
+ * pixel in four.  The same values enter the same sums in the same order: dr, ds, plane_sums and sc_sums are those
+ * of lf_block_tail_bwd_f32 on the same inputs, bit for bit. */
+int lf_block_tail_fwd_keep_f32(const float* y, const float* a_scale, const float* a_shift, const float* s,
+                               const float* sc, const float* sc_scale, const float* sc_shift, int sc_relu,
+                               const float* drop, uint8_t* route, float* p, float* y_at, float* sc_at, int n, int c,
+                               int h, int w, lf_stream_t stream);
+int lf_block_tail_bwd_kept_f32(const float* dp, const uint8_t* route, const float* y, const float* y_at,
+                               const float* a_scale, const float* a_shift, const float* drop, float* dr, float* ds,
+                               float* plane_sums, const float* sc_y, const float* sc_at, float* sc_sums, int n, int c,
+                               int h, int w, lf_stream_t stream);
+
 /* ---- input stage ----------------------------------------------------------- */
 /* u8 HWC -> f32 NCHW with the model's train-time augmentation fused (cnn.py:74-86):
  * keras RandomFlip("horizontal") -> RandomRotation (bilinear, fill_mode="reflect") ->

@@ -685,10 +685,13 @@ __device__ __forceinline__ unsigned tail_code(float r00, float r01, float r10, f
 
 // One thread = two rows x V input pixels = V/2 pooled values and their route bytes.  The residual r
 // is not stored: backward only needs where each pooled value came from.  route == null: no backward
-// pass follows (inference).
-template <typename T, int V>
+// pass follows (inference).  Keep: the raw y and sc at the recorded position of each window also go out, at
+// pooled size (y_at, sc_at; either may be null), so that the backward pass reads them there instead of
+// gathering one pixel in four from the full-size planes.
+template <typename T, int V, bool Keep = false>
 __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs<T> t, uint8_t* __restrict__ route,
-                                                          T* __restrict__ p) {
+                                                          T* __restrict__ p, T* __restrict__ y_at = nullptr,
+                                                          T* __restrict__ sc_at = nullptr) {
     const int plane = blockIdx.x, ch = plane % t.c;
     const float sv = t.s ? t.s[plane] : 1.f;
     const float as = t.a_scale ? t.a_scale[ch] : 1.f, ab = t.a_scale ? t.a_shift[ch] : 0.f;
@@ -699,34 +702,56 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs<T> t, uint8_t
     for (int q = blockIdx.y * kBlock + threadIdx.x; q < ph * pwv; q += gridDim.y * kBlock) {
         const int py = q / pwv, pxv = q - py * pwv;
         float r[2][V];
+        Vec<T, V> yv[2], scv[2];
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy) {
             const size_t o = base + (size_t)(2 * py + dy) * w + V * pxv;
-            const Vec<T, V> yv = *reinterpret_cast<const Vec<T, V>*>(t.y + o);
-            const Vec<T, V> scv = *reinterpret_cast<const Vec<T, V>*>(t.sc + o);
+            yv[dy] = *reinterpret_cast<const Vec<T, V>*>(t.y + o);
+            scv[dy] = *reinterpret_cast<const Vec<T, V>*>(t.sc + o);
 #pragma unroll
-            for (int e = 0; e < V; ++e) r[dy][e] = tail_r(t, widen(yv[e]), widen(scv[e]), as, ab, sv, ks, kb);
+            for (int e = 0; e < V; ++e)
+                r[dy][e] = tail_r(t, widen(yv[dy][e]), widen(scv[dy][e]), as, ab, sv, ks, kb);
         }
         const size_t po = pbase + (size_t)py * pw + (V / 2) * pxv;
         unsigned codes = 0;
-        Vec<T, V / 2> pooled;
+        Vec<T, V / 2> pooled, ya, sa;
 #pragma unroll
         for (int k = 0; k < V / 2; ++k) {
             float m;
-            codes |= tail_code(r[0][2 * k], r[0][2 * k + 1], r[1][2 * k], r[1][2 * k + 1], m) << (8 * k);
+            const unsigned cd = tail_code(r[0][2 * k], r[0][2 * k + 1], r[1][2 * k], r[1][2 * k + 1], m);
+            codes |= cd << (8 * k);
             pooled[k] = narrow<T>(m * dv);
+            if (Keep) {
+                const bool low = (cd & 2u) != 0, right = (cd & 1u) != 0;
+                const T y0 = right ? yv[0][2 * k + 1] : yv[0][2 * k], y1 = right ? yv[1][2 * k + 1] : yv[1][2 * k];
+                const T s0 = right ? scv[0][2 * k + 1] : scv[0][2 * k], s1 = right ? scv[1][2 * k + 1] : scv[1][2 * k];
+                ya[k] = low ? y1 : y0;
+                sa[k] = low ? s1 : s0;
+            }
         }
         if (route != nullptr) *reinterpret_cast<RouteWord<V / 2>*>(route + po) = (RouteWord<V / 2>)codes;
         *reinterpret_cast<Vec<T, V / 2>*>(p + po) = pooled;
+        if (Keep && y_at != nullptr) *reinterpret_cast<Vec<T, V / 2>*>(y_at + po) = ya;
+        if (Keep && sc_at != nullptr) *reinterpret_cast<Vec<T, V / 2>*>(sc_at + po) = sa;
     }
+}
+
+// a * b rounded on its own, whatever the compiler would contract it with
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
 }
 
 // dr = dp*drop routed to the recorded position of each 2x2 window when its maximum was > 0.
 // Per plane: ds = sum dr*a with a = relu(y*a_scale+a_shift) (or y), and (a_scale given)
 // plane_sums = {sum dr*[a>0], sum dr*[a>0]*y}: BatchNorm-2's backward sums without a second pass;
 // sc_sums = {sum dr, sum dr*sc_y} (the projection shortcut's BatchNorm).  The sums are over dr as
-// stored.  One thread = V/2 pooled values -> two rows x V gradient pixels.
-template <typename T, int V>
+// stored.  One thread = V/2 pooled values -> two rows x V gradient pixels.  Kept: where y_at / sc_at
+// (tail_fwd_kernel's pooled-size copies of y / sc_y at the recorded positions) are given, the sums read
+// them in place of y[pos] / sc_y[pos]: the same values, without touching the full-size planes.
+// The sums' roundings are stated (products rounded on their own in the two second moments, one fma in ds), so
+// that every instantiation adds the same floats: left to the compiler, the contraction differed between them.
+template <typename T, int V, bool Kept = false>
 __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ dp,
                                                           const uint8_t* __restrict__ route,
                                                           const T* __restrict__ y,
@@ -738,7 +763,8 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ 
                                                           float* __restrict__ plane_sums,
                                                           const T* __restrict__ sc_y,
                                                           float* __restrict__ sc_sums, int c,
-                                                          int h, int w) {
+                                                          int h, int w, const T* __restrict__ y_at = nullptr,
+                                                          const T* __restrict__ sc_at = nullptr) {
     __shared__ float red[20];
     const int plane = blockIdx.x, ch = plane % c;
     const float dv = drop ? drop[plane] : 1.f;
@@ -746,25 +772,28 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ 
     const int ph = h / 2, pw = w / 2, pwv = w / V;
     const size_t base = (size_t)plane * h * w, pbase = (size_t)plane * ph * pw;
     const bool sums = ds != nullptr || plane_sums != nullptr;
+    const bool sc_on = sc_y != nullptr || (Kept && sc_at != nullptr);
+    const bool y_kept = Kept && y_at != nullptr, sc_kept = Kept && sc_at != nullptr;
     float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    auto tally = [&](float gg, size_t pos) {
-        if (sc_y != nullptr && gg != 0.f) {  // the shortcut branch's (projection) BN: no mask
+    Vec<T, V / 2> ya, sa;   // Kept: y_at / sc_at of this thread's pooled values
+    auto tally = [&](float gg, size_t pos, int k) {
+        if (sc_on && gg != 0.f) {  // the shortcut branch's (projection) BN: no mask
             acc[3] += gg;
-            acc[4] += gg * widen(sc_y[pos]);
+            acc[4] += mul_rounded(gg, widen(sc_kept ? sa[k] : sc_y[pos]));
         }
         if (sums && gg != 0.f) {
-            const float yv = widen(y[pos]);
+            const float yv = widen(y_kept ? ya[k] : y[pos]);
             float av = yv;
             if (a_scale) {
                 av = fmaf(yv, as, ab);
                 if (av > 0.f) {
                     acc[1] += gg;
-                    acc[2] += gg * yv;
+                    acc[2] += mul_rounded(gg, yv);
                 } else {
                     av = 0.f;
                 }
             }
-            acc[0] += gg * av;
+            acc[0] = fmaf(gg, av, acc[0]);
         }
     };
     for (int q = threadIdx.x; q < ph * pwv; q += kBlock) {
@@ -773,6 +802,8 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ 
         const unsigned codes = *reinterpret_cast<const RouteWord<V / 2>*>(route + po);
         const Vec<T, V / 2> g = *reinterpret_cast<const Vec<T, V / 2>*>(dp + po);
         const size_t o0 = base + (size_t)(2 * py) * w + V * pxv, o1 = o0 + w;
+        if (y_kept && sums) ya = *reinterpret_cast<const Vec<T, V / 2>*>(y_at + po);
+        if (sc_kept) sa = *reinterpret_cast<const Vec<T, V / 2>*>(sc_at + po);
         Vec<T, V> top, bot;
 #pragma unroll
         for (int k = 0; k < V / 2; ++k) {   // pooled value k -> input columns 2k, 2k+1
@@ -782,7 +813,7 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ 
             top[2 * k + 1] = b == 1 ? gk : T(0);
             bot[2 * k] = b == 2 ? gk : T(0);
             bot[2 * k + 1] = b == 3 ? gk : T(0);
-            tally(widen(gk), (b < 2 ? o0 : o1) + 2 * k + (b & 1u));
+            tally(widen(gk), (b < 2 ? o0 : o1) + 2 * k + (b & 1u), k);
         }
         *reinterpret_cast<Vec<T, V>*>(dr + o0) = top;
         *reinterpret_cast<Vec<T, V>*>(dr + o1) = bot;
@@ -793,7 +824,7 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(const T* __restrict__ 
             if (yy >= 2 * ph || x >= 2 * pw) dr[base + t] = T(0);
         }
     }
-    if (sums || sc_y != nullptr) {
+    if (sums || sc_on) {
         block_sum<5>(acc, red);
         if (threadIdx.x == 0) {
             if (ds != nullptr) ds[plane] = acc[0];
@@ -1119,28 +1150,32 @@ void bn_bwd_sums_launch(const BnBwdArgs& a, float* part, const BnBwdOut& o, hipS
 }
 
 // The rules both storage types of the residual tail share; the bf16 entries add their shape and alignment rules.
-template <typename T, int V>
-int tail_fwd_launch(const char* who, const TailArgs<T>& t, uint8_t* route, T* p, int n, lf_stream_t stream) {
+template <typename T, int V, bool Keep = false>
+int tail_fwd_launch(const char* who, const TailArgs<T>& t, uint8_t* route, T* p, int n, lf_stream_t stream,
+                    T* y_at, T* sc_at) {
     LF_REQUIRE(t.y && t.sc && p, "%s: null buffer", who);
     LF_REQUIRE((t.sc_scale == nullptr) == (t.sc_shift == nullptr), "%s: sc_scale/sc_shift", who);
     LF_REQUIRE((t.a_scale == nullptr) == (t.a_shift == nullptr), "%s: a_scale/a_shift", who);
-    tail_fwd_kernel<T, V><<<dim3(n * t.c, plane_grid((t.h / 2) * (t.w / V))), kBlock, 0, lf::as_stream(stream)>>>(
-        t, route, p);
+    tail_fwd_kernel<T, V, Keep><<<dim3(n * t.c, plane_grid((t.h / 2) * (t.w / V))), kBlock, 0,
+                                  lf::as_stream(stream)>>>(t, route, p, y_at, sc_at);
     return lf::check_launch(who);
 }
 
-template <typename T, int V>
+// Kept: y_at / sc_at stand in for y / sc_y (tail_bwd_kernel), so either of a pair satisfies the rules.
+template <typename T, int V, bool Kept = false>
 int tail_bwd_launch(const char* who, const T* dp, const uint8_t* route, const T* y, const float* a_scale,
                     const float* a_shift, const float* drop, T* dr, float* ds, float* plane_sums, const T* sc_y,
-                    float* sc_sums, int n, int c, int h, int w, lf_stream_t stream) {
-    LF_REQUIRE((sc_y == nullptr) == (sc_sums == nullptr), "%s: sc_y and sc_sums go together", who);
+                    float* sc_sums, int n, int c, int h, int w, lf_stream_t stream, const T* y_at,
+                    const T* sc_at) {
+    const bool has_y = y != nullptr || y_at != nullptr, has_sc = sc_y != nullptr || sc_at != nullptr;
+    LF_REQUIRE(has_sc == (sc_sums != nullptr), "%s: sc_y and sc_sums go together", who);
     LF_REQUIRE(dp && route && dr, "%s: null buffer", who);
-    LF_REQUIRE(plane_sums == nullptr || (y != nullptr && a_scale != nullptr),
+    LF_REQUIRE(plane_sums == nullptr || (has_y && a_scale != nullptr),
                "%s: plane_sums needs y and a_scale/a_shift", who);
-    LF_REQUIRE((y == nullptr) == (ds == nullptr && plane_sums == nullptr), "%s: y goes with ds / plane_sums", who);
+    LF_REQUIRE(has_y == (ds != nullptr || plane_sums != nullptr), "%s: y goes with ds / plane_sums", who);
     LF_REQUIRE((a_scale == nullptr) == (a_shift == nullptr), "%s: a_scale/a_shift", who);
-    tail_bwd_kernel<T, V><<<n * c, kBlock, 0, lf::as_stream(stream)>>>(dp, route, y, a_scale, a_shift, drop, dr, ds,
-                                                                       plane_sums, sc_y, sc_sums, c, h, w);
+    tail_bwd_kernel<T, V, Kept><<<n * c, kBlock, 0, lf::as_stream(stream)>>>(
+        dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums, sc_y, sc_sums, c, h, w, y_at, sc_at);
     return lf::check_launch(who);
 }
 
@@ -1402,7 +1437,20 @@ int lf_block_tail_fwd_f32(const float* y, const float* a_scale, const float* a_s
     LF_REQUIRE((w & 1) == 0, "lf_block_tail_fwd: width must be even");
     const TailArgs<float> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
     auto launch = w % 4 == 0 ? tail_fwd_launch<float, 4> : tail_fwd_launch<float, 2>;
-    return launch("lf_block_tail_fwd", t, route, p, n, stream);
+    return launch("lf_block_tail_fwd", t, route, p, n, stream, nullptr, nullptr);
+}
+
+int lf_block_tail_fwd_keep_f32(const float* y, const float* a_scale, const float* a_shift, const float* s,
+                               const float* sc, const float* sc_scale, const float* sc_shift, int sc_relu,
+                               const float* drop, uint8_t* route, float* p, float* y_at, float* sc_at, int n, int c,
+                               int h, int w, lf_stream_t stream) {
+    LF_REQUIRE(route, "lf_block_tail_fwd_keep: null buffer");
+    LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 1 && (long long)n * c < (1LL << 31),
+               "lf_block_tail_fwd_keep: bad dims n=%d c=%d h=%d w=%d", n, c, h, w);
+    LF_REQUIRE((w & 1) == 0, "lf_block_tail_fwd_keep: width must be even");
+    const TailArgs<float> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
+    auto launch = w % 4 == 0 ? tail_fwd_launch<float, 4, true> : tail_fwd_launch<float, 2, true>;
+    return launch("lf_block_tail_fwd_keep", t, route, p, n, stream, y_at, sc_at);
 }
 
 int lf_block_tail_fwd_train_bf16(const uint16_t* y, const float* a_scale, const float* a_shift, const float* s,
@@ -1416,7 +1464,7 @@ int lf_block_tail_fwd_train_bf16(const uint16_t* y, const float* a_scale, const 
     const TailArgs<uint16_t> t{y, a_scale, a_shift, s, sc, sc_scale, sc_shift, drop, sc_relu, c, h, w};
     const bool v8 = w % 8 == 0 && aligned(y, 16) && aligned(sc, 16) && aligned(pooled, 8) && aligned(route, 4);
     auto launch = v8 ? tail_fwd_launch<uint16_t, 8> : tail_fwd_launch<uint16_t, 4>;
-    return launch("lf_block_tail_fwd_train_bf16", t, route, pooled, n, stream);
+    return launch("lf_block_tail_fwd_train_bf16", t, route, pooled, n, stream, nullptr, nullptr);
 }
 
 int lf_block_tail_bwd_f32(const float* dp, const uint8_t* route, const float* y,
@@ -1427,7 +1475,18 @@ int lf_block_tail_bwd_f32(const float* dp, const uint8_t* route, const float* y,
     LF_REQUIRE((w & 1) == 0, "lf_block_tail_bwd: width must be even (float2 rows)");
     auto launch = w % 4 == 0 ? tail_bwd_launch<float, 4> : tail_bwd_launch<float, 2>;
     return launch("lf_block_tail_bwd", dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums, sc_y, sc_sums, n, c, h,
-                  w, stream);
+                  w, stream, nullptr, nullptr);
+}
+
+int lf_block_tail_bwd_kept_f32(const float* dp, const uint8_t* route, const float* y, const float* y_at,
+                               const float* a_scale, const float* a_shift, const float* drop, float* dr, float* ds,
+                               float* plane_sums, const float* sc_y, const float* sc_at, float* sc_sums, int n, int c,
+                               int h, int w, lf_stream_t stream) {
+    LF_REQUIRE(n > 0 && c > 0 && h > 1 && w > 1, "lf_block_tail_bwd_kept: bad dims n=%d c=%d h=%d w=%d", n, c, h, w);
+    LF_REQUIRE((w & 1) == 0, "lf_block_tail_bwd_kept: width must be even (float2 rows)");
+    auto launch = w % 4 == 0 ? tail_bwd_launch<float, 4, true> : tail_bwd_launch<float, 2, true>;
+    return launch("lf_block_tail_bwd_kept", dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums, sc_y, sc_sums, n,
+                  c, h, w, stream, y_at, sc_at);
 }
 
 int lf_block_tail_bwd_bf16(const uint16_t* dp, const uint8_t* route, const uint16_t* y, const float* a_scale,
@@ -1439,7 +1498,7 @@ int lf_block_tail_bwd_bf16(const uint16_t* dp, const uint8_t* route, const uint1
     auto launch = w % 8 == 0 && aligned(dr, 16) && aligned(dp, 8) && aligned(route, 4) ? tail_bwd_launch<uint16_t, 8>
                                                                                       : tail_bwd_launch<uint16_t, 4>;
     return launch("lf_block_tail_bwd_bf16", dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums, sc_y, sc_sums, n,
-                  c, h, w, stream);
+                  c, h, w, stream, nullptr, nullptr);
 }
 
 int lf_head_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue,

@@ -651,9 +651,13 @@ class LeafCNN:
             drop = drops[i] if (training and drops is not None) else None
             pooled = B(p + "p", (n, f, h // 2, w // 2))
             route = B(p + "route", pooled.shape, torch.uint8)
-            nn.block_tail_fwd(y2, st2[2], st2[3], s, sc, scs, scb, scr, drop, route, pooled)
+            # fp32 training: y2 (and yp) at the recorded positions stay, at pooled size, for the tail's backward
+            keep = training and not bf16 and nn.tail_keeps()
+            yat = B(p + "yat", pooled.shape) if keep else None
+            scat = B(p + "scat", pooled.shape) if keep and cin != f else None
+            nn.block_tail_fwd(y2, st2[2], st2[3], s, sc, scs, scb, scr, drop, route, pooled, yat, scat)
             sv.update({p + "xin": xin, p + "xin_st": xin_st, p + "y1": y1, p + "y2": y2, p + "s": s,
-                       p + "route": route, p + "drop": drop, p + "hw": (h, w)})
+                       p + "route": route, p + "drop": drop, p + "hw": (h, w), p + "yat": yat, p + "scat": scat})
             xin, xin_st, cin, h, w = pooled, None, f, h // 2, w // 2
         self._last_pooled = xin   # class_activation_maps reads it
         g = nn.gap(xin, out=B("g", (n, self.widths[-1]), F32))
@@ -742,7 +746,8 @@ class LeafCNN:
             psum = B(p + "psum", (n, f, 2), F32)
             yp = sv.get(p + "yp")  # projection shortcut: its BN's backward sums ride along
             psum_p = B(p + "psum_p", (n, f, 2), F32) if yp is not None else None
-            nn.block_tail_bwd(dp, route, y2, st2[2], st2[3], drop, gA, ds, psum, yp, psum_p)
+            nn.block_tail_bwd(dp, route, y2, st2[2], st2[3], drop, gA, ds, psum, yp, psum_p,
+                              y_at=sv[p + "yat"], sc_at=sv[p + "scat"])
             add_nc = None
             if self.use_se:
                 dm = B(p + "dm", (n, f), F32)

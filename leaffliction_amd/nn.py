@@ -17,6 +17,8 @@ _ws_gen = 0
 _NO_FUSED_BN_WGRAD = os.environ.get("LEAFFLICTION_NO_FUSED_BN_WGRAD", "0") == "1"
 # A/B knob for measurements: the projection shortcut's backward as bn_bwd_wgrad + the 1x1 input-gradient convolution
 _NO_FUSED_PROJ_BWD = os.environ.get("LEAFFLICTION_NO_FUSED_PROJ_BWD", "0") == "1"
+# A/B knob for measurements: the fp32 tail backward gathers y / sc_y from the full-size planes (no y_at / sc_at)
+_NO_TAIL_KEEP = os.environ.get("LEAFFLICTION_NO_TAIL_KEEP", "0") == "1"
 
 
 def _workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
@@ -1102,9 +1104,16 @@ def se_bwd(ds, m, z1, s, w1, w2, dm, dw1, db1, dw2, db2, dm_scale: float = 1.0):
     return dm
 
 
-def block_tail_fwd(y, a_scale, a_shift, s, sc, sc_scale, sc_shift, sc_relu, drop, route, p):
+def tail_keeps() -> bool:
+    """Whether the fp32 training step keeps y / sc at the tail's recorded positions (block_tail_fwd's y_at / sc_at)
+    for block_tail_bwd to read."""
+    return not _NO_TAIL_KEEP
+
+
+def block_tail_fwd(y, a_scale, a_shift, s, sc, sc_scale, sc_shift, sc_relu, drop, route, p, y_at=None, sc_at=None):
     """Add -> ReLU -> SpatialDropout2D -> MaxPool2D(2) on fp32 or bf16 tensors; route: uint8 [N,C,H/2,W/2]
-    (written), or None on bf16 tensors when no backward pass follows."""
+    (written), or None on bf16 tensors when no backward pass follows.  y_at / sc_at (fp32, shaped like p; written):
+    the raw y / sc at the position each route byte records, for block_tail_bwd."""
     dt = _plane_dtype(y, "block_tail_fwd.y", 4)
     _chk(sc, dt, "block_tail_fwd.sc", 4)
     _chk(p, dt, "block_tail_fwd.p", 4)
@@ -1113,14 +1122,33 @@ def block_tail_fwd(y, a_scale, a_shift, s, sc, sc_scale, sc_shift, sc_relu, drop
         _chk(route, torch.uint8, "block_tail_fwd.route", 4)
     if sc.shape != y.shape or tuple(p.shape) != (n, c, h // 2, w // 2) or (route is not None and route.shape != p.shape):
         raise ValueError("block_tail_fwd: shape mismatch")
+    if y_at is not None or sc_at is not None:
+        _tail_kept("block_tail_fwd", dt, route, p, y_at, sc_at)
+        _lib.call("lf_block_tail_fwd_keep_f32", y.data_ptr(), _ptr(a_scale), _ptr(a_shift), _ptr(s), sc.data_ptr(),
+                  _ptr(sc_scale), _ptr(sc_shift), 1 if sc_relu else 0, _ptr(drop), _ptr(route), p.data_ptr(),
+                  _ptr(y_at), _ptr(sc_at), n, c, h, w, _stream())
+        return route, p
     entry = "lf_block_tail_fwd_train_bf16" if dt == _BF16 else "lf_block_tail_fwd_f32"
     _lib.call(entry, y.data_ptr(), _ptr(a_scale), _ptr(a_shift), _ptr(s), sc.data_ptr(), _ptr(sc_scale),
               _ptr(sc_shift), 1 if sc_relu else 0, _ptr(drop), _ptr(route), p.data_ptr(), n, c, h, w, _stream())
     return route, p
 
 
+def _tail_kept(who: str, dt, route, pooled, y_at, sc_at) -> None:
+    """The rules of the tail's kept values: fp32 only, with route bytes, shaped like the pooled tensor."""
+    if dt != _F32 or route is None:
+        raise ValueError(f"{who}: y_at / sc_at go with fp32 tensors and route bytes")
+    for t, nm in ((y_at, "y_at"), (sc_at, "sc_at")):
+        if t is not None:
+            _chk(t, _F32, f"{who}.{nm}", 4)
+            if t.shape != pooled.shape:
+                raise ValueError(f"{who}.{nm}: shape mismatch")
+
+
 def block_tail_bwd(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums=None, sc_y=None,
-                   sc_sums=None):
+                   sc_sums=None, y_at=None, sc_at=None):
+    """y_at / sc_at (block_tail_fwd's): read in place of y / sc_y at the recorded positions; y / sc_y may then be
+    None."""
     dt = _plane_dtype(dr, "block_tail_bwd.dr", 4)
     _chk(dp, dt, "block_tail_bwd.dp", 4)
     _chk(route, torch.uint8, "block_tail_bwd.route", 4)
@@ -1132,6 +1160,12 @@ def block_tail_bwd(dp, route, y, a_scale, a_shift, drop, dr, ds, plane_sums=None
             raise ValueError("block_tail_bwd plane sums: expected [N,C,2]")
     if sc_y is not None and sc_y.shape != dr.shape:
         raise ValueError("block_tail_bwd.sc_y: shape mismatch")
+    if y_at is not None or sc_at is not None:
+        _tail_kept("block_tail_bwd", dt, route, dp, y_at, sc_at)
+        _lib.call("lf_block_tail_bwd_kept_f32", dp.data_ptr(), route.data_ptr(), _ptr(y), _ptr(y_at), _ptr(a_scale),
+                  _ptr(a_shift), _ptr(drop), dr.data_ptr(), _ptr(ds), _ptr(plane_sums), _ptr(sc_y), _ptr(sc_at),
+                  _ptr(sc_sums), n, c, h, w, _stream())
+        return dr, ds
     entry = "lf_block_tail_bwd_bf16" if dt == _BF16 else "lf_block_tail_bwd_f32"
     _lib.call(entry, dp.data_ptr(), route.data_ptr(), _ptr(y), _ptr(a_scale), _ptr(a_shift), _ptr(drop),
               dr.data_ptr(), _ptr(ds), _ptr(plane_sums), _ptr(sc_y), _ptr(sc_sums), n, c, h, w, _stream())
