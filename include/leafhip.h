@@ -1235,6 +1235,34 @@ int lf_feat_moments(const float* feat, const int32_t* labels, int n, int d, int 
 int lf_maha_score_f32(const float* feat, const float* mu0, const float* w, const float* m, int n, int d, int c,
                       float* d2, float* score, int32_t* nearest, lf_stream_t stream);
 
+/* ---- Nearest neighbours: the k gallery rows closest to each query row, exactly ---- */
+/* lf_knn_topk_f32: q f32 [nq][d] (queries), g f32 [ng][d] (the gallery; 16-byte aligned), exclude i32 [nq] or null:
+ * the gallery row query i must not return, -1 for none (a leave-one-out search passes 0 .. nq - 1).
+ * Out: d2 f32 [nq][k] and idx i32 [nq][k].  The rule, in f32:
+ *   qn_i   = sum_c q[i][c]^2          an fmaf chain from 0 in the order c = 0 .. d - 1; gn_j likewise over g[j]
+ *   dot_ij = sum_c q[i][c] g[j][c]    an fmaf chain from 0 (v_mfma_f32_32x32x2_f32) in the order c = 0, 4, 1, 5, 2,
+ *                                     6, 3, 7, then 8, 12, 9, 13, ...: each run of 8 features in that order, the
+ *                                     runs ascending
+ *   d2_ij  = max(0, fmaf(-2, dot_ij, qn_i + gn_j)); a non-finite value (NaN or an infinity) is +inf; a zero is +0
+ *   Row i of the output holds the k smallest pairs (d2_ij, j) over all j != exclude[i], ascending in the TOTAL order
+ *   "smaller d2 first, the lower j on equal d2".  With fewer than k eligible rows the remaining slots hold (+inf, -1),
+ *   after every eligible row, those at distance +inf included.
+ * The order is total, so the output does not depend on tiling, on `segments` or on the order in which candidates are
+ * met; no atomic is used; the same call gives the same bits.  The distance matrix is never written: a workgroup
+ * holds lf_knn_query_tile() queries in LDS, walks one of `segments` equal runs of ceil(ng / segments) gallery rows and
+ * keeps k pairs per query; with segments > 1 the runs' lists go to the workspace and a second kernel merges them.
+ * lf_knn_segments(nq, ng) is the number of runs that fills the device at that size (1 when the query tiles alone do;
+ * 0: bad arguments).  ws: 16-byte aligned, lf_knn_topk_workspace(nq, ng, k, segments) bytes (0: bad arguments): gn,
+ * then the runs' lists.
+ * Refused before any launch (-1 with a message): a null buffer, nq < 1, ng < 1, d not a multiple of 16 in 16..256,
+ * k outside 1..lf_knn_max_k() = 32, segments outside 1..64, a misaligned g or ws, a workspace that is too small. */
+int lf_knn_query_tile(void);
+int lf_knn_max_k(void);
+int lf_knn_segments(int nq, int ng);
+size_t lf_knn_topk_workspace(int nq, int ng, int k, int segments);
+int lf_knn_topk_f32(const float* q, const float* g, int nq, int ng, int d, int k, const int32_t* exclude,
+                    int segments, float* d2, int32_t* idx, void* ws, size_t ws_bytes, lf_stream_t stream);
+
 /* ---- Near-duplicate search: 128-bit difference hashes and their all-pairs Hamming search ---- */
 /* Integer and exact throughout; no float appears.
  *

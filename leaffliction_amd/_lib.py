@@ -161,6 +161,11 @@ SIGNATURES = {
     "lf_calib_apply_f32": [P, c_double, P, P, P, c_int, c_int, P],
     "lf_feat_moments": [P, P, c_int, c_int, c_int, P, P, P, P, P],
     "lf_maha_score_f32": [P, P, P, P, c_int, c_int, c_int, P, P, P, P],
+    "lf_knn_query_tile": [],
+    "lf_knn_max_k": [],
+    "lf_knn_segments": [c_int, c_int],
+    "lf_knn_topk_workspace": [c_int, c_int, c_int, c_int],
+    "lf_knn_topk_f32": [P, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P],
     "lf_dhash128_u8": [P, P, c_int, c_int, c_int, c_int, P],
     "lf_hamming_pairs_tile": [],
     "lf_hamming_pairs_rows": [],
@@ -202,7 +207,7 @@ _RESTYPES = {"lf_last_error": C.c_char_p, "lf_conv2d_wgrad_workspace": c_size_t,
              "lf_conv2d_proj_bwd_workspace": c_size_t,
              "lf_dwconv3x3_bwd_workspace": c_size_t,
              "lf_bn_workspace": c_size_t, "lf_se_bwd_workspace": c_size_t,
-             "lf_adamw_workspace": c_size_t, "lf_calib_stats_workspace": c_size_t, "lf_conv2d_stats_tiles": C.c_longlong,
+             "lf_adamw_workspace": c_size_t, "lf_calib_stats_workspace": c_size_t, "lf_knn_topk_workspace": c_size_t, "lf_conv2d_stats_tiles": C.c_longlong,
              "lf_blur_saliency_workspace": c_size_t, "lf_inclusive_mask_workspace": c_size_t, "lf_make_mask_workspace": c_size_t, "lf_brown_spots_workspace": c_size_t, "lf_lesion_table_workspace": c_size_t, "lf_canny_workspace": c_size_t, "lf_clahe_workspace": c_size_t,
              "lf_good_features_workspace": c_size_t, "lf_landmarks_workspace": c_size_t,
              "lf_conv2d_bf16_weight_elems": c_size_t,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--montage] [--tta PRESET]
-[--calibrated] [--novelty] [--evaluate ...]`.
+[--calibrated] [--novelty] [--neighbours K] [--evaluate ...]`.
 
 Flags, JSON schema (`batch_results` + `summary`), the sampled accuracy gate and the exit
 codes (1 on error, 2 when the gate is never reached) follow srcs/cli/predict.py:17-87,
@@ -22,6 +22,10 @@ gains `calibration`.
 gains `novelty_score` (squared Mahalanobis distance of the pooled features to the nearest class mean),
 `novelty_threshold`, `known` (score <= threshold) and `nearest_class`, from `<learnings>/novelty.json` and `novelty.npz`
 (fitted by cli.novelty; exit status 1 without them); `summary` gains `novelty`.  No prediction or probability changes.
+`--neighbours K` (not in the reference; 1..32), in the same modes as --novelty and also together with it: every result
+gains `neighbours` (the K pictures of `<learnings>/neighbours.npz` nearest in the model's feature space, as {file,
+label, sq_distance}, nearest first), `knn_label` (their vote), `knn_agreement` and `kth_sq_distance`; the index is
+built by cli.neighbours (exit status 1 without it); `summary` gains `neighbours`.  No prediction or probability changes.
 """
 from __future__ import annotations
 
@@ -69,6 +73,9 @@ def parse_args(argv=None):
     p.add_argument("--novelty", action="store_true",
                    help="also say whether each picture is one of the model's classes at all "
                         "(<learnings>/novelty.json, fitted by cli.novelty)")
+    p.add_argument("--neighbours", type=int, default=None, metavar="K",
+                   help="also name the K index pictures each picture most resembles "
+                        "(<learnings>/neighbours.npz, built by cli.neighbours)")
     return p.parse_args(argv)
 
 
@@ -86,6 +93,15 @@ def validate_inputs(args):
         raise ValueError("--novelty cannot be combined with --tta (a score over several views is not defined)")
     if args.novelty and args.cam:
         raise ValueError("--novelty cannot be combined with --cam")
+    if args.neighbours is not None:
+        from ..nn import KNN_MAX_K
+        if not 1 <= args.neighbours <= KNN_MAX_K:
+            raise ValueError(f"--neighbours must lie in 1..{KNN_MAX_K}, got {args.neighbours}")
+        if args.tta:
+            raise ValueError("--neighbours cannot be combined with --tta (the features of several views are not one "
+                             "point)")
+        if args.cam:
+            raise ValueError("--neighbours cannot be combined with --cam")
     if args.cam and not 0.0 <= args.cam_alpha <= 1.0:
         raise ValueError(f"--cam-alpha must lie in [0, 1], got {args.cam_alpha}")
     if not image_path.exists():
@@ -105,6 +121,9 @@ def validate_inputs(args):
         for name in ("novelty.json", "novelty.npz"):
             if not (learnings_dir / name).exists():
                 raise FileNotFoundError(f"Novelty file not found: {learnings_dir / name} (fit one with cli.novelty)")
+    if args.neighbours is not None:
+        from ..predict.neighbours import require_files
+        require_files(learnings_dir)
     if args.evaluate:
         if not args.batch_mode:
             raise ValueError("--evaluate requires --batch-mode")
@@ -146,11 +165,26 @@ def novelty_summary(predictor, results):
             "unknown_count": sum(1 for r in results if r.get("known") is False)}
 
 
-def save_batch_results_json(results, processing_time, output_path, tta=None, calibration=None, novelty=None):
+NEIGHBOUR_KEYS = ("neighbours", "knn_label", "knn_agreement", "kth_sq_distance")
+
+
+def neighbours_summary(predictor, results):
+    """`summary.neighbours` of a predictor that names nearest neighbours, None of any other."""
+    data = getattr(predictor, "neighbours_data", None)
+    if data is None:
+        return None
+    agree = sum(1 for r in results if r.get("knn_label") == r["top_prediction"])
+    return {"k": int(predictor.neighbours), "index_size": int(data["n"]),
+            "agrees_with_prediction": agree / len(results) if results else None}
+
+
+def save_batch_results_json(results, processing_time, output_path, tta=None, calibration=None, novelty=None,
+                            neighbours=None):
     """tta (the preset, when the predictions are test-time-augmented ones): `summary` also says so and gives the mean
     of the results' view agreement.  calibration (calibration_summary, when the confidences are calibrated ones):
     `summary.calibration`.  novelty (novelty_summary, when the results carry a novelty score): `summary.novelty`, and
-    every entry of `batch_results` keeps its NOVELTY_KEYS."""
+    every entry of `batch_results` keeps its NOVELTY_KEYS.  neighbours (neighbours_summary): `summary.neighbours`, and
+    every entry keeps its NEIGHBOUR_KEYS."""
     output_path = Path(output_path)
     if not output_path.is_absolute() and not str(output_path).startswith("artifacts/"):
         output_path = Path("artifacts/prediction_output") / output_path.name
@@ -158,7 +192,9 @@ def save_batch_results_json(results, processing_time, output_path, tta=None, cal
                                "top_prediction": r["top_prediction"],
                                "confidence": r["confidence"],
                                "all_probabilities": r["all_probabilities"],
-                               **({k: r[k] for k in NOVELTY_KEYS} if novelty is not None else {})} for r in results],
+                               **({k: r[k] for k in NOVELTY_KEYS} if novelty is not None else {}),
+                               **({k: r[k] for k in NEIGHBOUR_KEYS} if neighbours is not None else {})}
+                              for r in results],
             "summary": create_batch_summary(results, processing_time)}
     if tta is not None:
         seen = [r["view_agreement"] for r in results if r.get("view_agreement") is not None]
@@ -168,6 +204,8 @@ def save_batch_results_json(results, processing_time, output_path, tta=None, cal
         data["summary"]["calibration"] = calibration
     if novelty is not None:
         data["summary"]["novelty"] = novelty
+    if neighbours is not None:
+        data["summary"]["neighbours"] = neighbours
     output_path.parent.mkdir(parents=True, exist_ok=True)
     with open(output_path, "w") as f:
         json.dump(data, f, indent=2)
@@ -290,7 +328,8 @@ def run_sampling_enforced_batch(predictor, image_dir: Path, manifest_path: Path,
             if json_output:
                 saved = save_batch_results_json(results, proc, json_output, tta=getattr(predictor, "tta", None),
                                                 calibration=calibration_summary(predictor),
-                                                novelty=novelty_summary(predictor, results))
+                                                novelty=novelty_summary(predictor, results),
+                                                neighbours=neighbours_summary(predictor, results))
                 logger.info("Results saved to: %s", saved)
             try:
                 PredictionEvaluator(predictor).evaluate_predictions(
@@ -311,7 +350,8 @@ def main(argv=None) -> None:
         args = parse_args(argv)
         image_path, learnings_dir = validate_inputs(args)
         rk = init_from_env()   # replicas under torch.distributed.run; one process otherwise
-        predictor = Predictor(learnings_dir, tta=args.tta, calibrated=args.calibrated, novelty=args.novelty)
+        predictor = Predictor(learnings_dir, tta=args.tta, calibrated=args.calibrated, novelty=args.novelty,
+                              neighbours=args.neighbours)
         predictor.load()
         if args.batch_mode:
             if args.evaluate:
@@ -346,7 +386,8 @@ def main(argv=None) -> None:
                 logger.info("Montages saved under: %s", Path(args.output_dir) / "montage")
             out = save_batch_results_json(results, proc, args.json_output, tta=args.tta,
                                           calibration=calibration_summary(predictor),
-                                          novelty=novelty_summary(predictor, results))
+                                          novelty=novelty_summary(predictor, results),
+                                          neighbours=neighbours_summary(predictor, results))
             logger.info("Results saved to: %s", out)
             for k, v in create_batch_summary(results, proc).items():
                 logger.info("  %s: %s", k, v)
@@ -366,6 +407,11 @@ def main(argv=None) -> None:
                 logger.info(f"Novelty score: {r['novelty_score']:.4g} (threshold {r['novelty_threshold']:.4g}): "
                             f"{'known' if r['known'] else 'UNKNOWN: not one of the trained classes'}; nearest class "
                             f"{r['nearest_class']}")
+            if args.neighbours is not None:
+                logger.info(f"Nearest neighbours vote {r['knn_label']} ({r['knn_agreement']} of "
+                            f"{len(r['neighbours'])}; k-th squared distance {r['kth_sq_distance']:.4g})")
+                for nb in r["neighbours"]:
+                    logger.info(f"    {nb['sq_distance']:.4g}  {nb['label']}  {nb['file']}")
             if args.tta:
                 logger.info(f"Views agreeing ({args.tta}): {r['view_agreement']:.0%}")
             for name, prob in sorted(r["all_probabilities"].items(), key=lambda x: -x[1])[:3]:

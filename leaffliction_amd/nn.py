@@ -864,6 +864,68 @@ def maha_score(feat: torch.Tensor, mu0: torch.Tensor, W: torch.Tensor, M: torch.
     return score, nearest, d2
 
 
+KNN_MAX_K = 32
+KNN_MAX_SEGMENTS = 64
+
+
+def knn_geometry(nq: int, ng: int) -> Tuple[int, int, int]:
+    """How lf_knn_topk_f32 walks nq queries against ng gallery rows when `segments` is left to it, from the library:
+    (queries per workgroup, segments the gallery is cut into, gallery rows per segment)."""
+    lib = _lib.load()
+    nq, ng = int(nq), int(ng)
+    segments = lib.lf_knn_segments(nq, ng)
+    if segments < 1:
+        raise ValueError(f"knn_geometry: nq={nq}, ng={ng} (each >= 1 and below 2^31)")
+    return lib.lf_knn_query_tile(), segments, -(-ng // segments)
+
+
+def _knn_rows(who: str, t: torch.Tensor) -> Tuple[int, int]:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.LeafHipError(f"{who}: expected a CUDA(HIP) tensor — there is no CPU path")
+    if t.dtype != _F32 or t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{who}: a contiguous float32 [N,D] tensor expected, got {t.dtype} {tuple(t.shape)}"
+                         f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    n, d = t.shape
+    if n == 0 or n >= 1 << 31 or not novelty_dim_ok(d):
+        raise ValueError(f"{who}: [N,D] with 1 <= N < 2^31 and D a multiple of {NOVELTY_DIM_STEP} in "
+                         f"{NOVELTY_DIM_STEP}..{NOVELTY_MAX_DIM} expected, got {tuple(t.shape)}")
+    return n, d
+
+
+def knn_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None,
+             segments: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k gallery rows nearest to each query (lf_knn_topk_f32; the rule: include/leafhip.h): queries f32 [nq,D] and
+    gallery f32 [ng,D] on the GPU -> (d2 f32 [nq,k], idx int32 [nq,k]), each row ascending by (d2, index), padded with
+    (+inf, -1) when fewer than k rows are eligible.  exclude int32 [nq]: the gallery row query i must not return, -1
+    for none.  segments: into how many runs the gallery is cut (None: knn_geometry's choice); the result does not
+    depend on it.  The distance matrix is never written.  No sync."""
+    nq, d = _knn_rows("knn_topk.queries", queries)
+    ng, dg = _knn_rows("knn_topk.gallery", gallery)
+    if dg != d or gallery.device != queries.device:
+        raise ValueError(f"knn_topk.gallery: [ng,{d}] on {queries.device} expected, got {tuple(gallery.shape)} on "
+                         f"{gallery.device}")
+    if gallery.data_ptr() % 16:
+        raise ValueError("knn_topk.gallery: must start on a 16-byte boundary")
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"knn_topk: k={k} (1..{KNN_MAX_K})")
+    if exclude is not None:
+        if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.dim() != 1 \
+                or exclude.shape[0] != nq or not exclude.is_contiguous() or exclude.device != queries.device:
+            raise ValueError(f"knn_topk.exclude: a contiguous int32 [{nq}] tensor on {queries.device} expected")
+    lib = _lib.load()
+    segments = lib.lf_knn_segments(nq, ng) if segments is None else int(segments)
+    if not 1 <= segments <= KNN_MAX_SEGMENTS:
+        raise ValueError(f"knn_topk: segments={segments} (1..{KNN_MAX_SEGMENTS})")
+    nbytes = int(lib.lf_knn_topk_workspace(nq, ng, k, segments))
+    ws = _workspace(nbytes, queries.device, slot=4)
+    d2 = torch.empty((nq, k), dtype=_F32, device=queries.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=queries.device)
+    _lib.call("lf_knn_topk_f32", queries.data_ptr(), gallery.data_ptr(), nq, ng, d, k, _ptr(exclude), segments,
+              d2.data_ptr(), idx.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return d2, idx
+
+
 DHASH_VARIANTS = (1, 2, 4, 8)
 DHASH_MIN_SIDE, DHASH_MAX_SIDE = 9, 4096
 

@@ -22,6 +22,12 @@ the argmax of the uncalibrated row and so never moves.
 through `nn.maha_score` with what DIR/novelty.npz holds, and every result gains `novelty_score`, `novelty_threshold`,
 `known` (score <= threshold) and `nearest_class`.  No prediction or probability changes.  It cannot be combined with a
 TTA preset or with the heat maps of explain_batch.
+
+`Predictor(dir, neighbours=K)` (not in the reference) also names the K index pictures each picture most resembles
+(predict/neighbours.py): the same pooled feature vector, divided by its length, goes through `nn.knn_topk` against the
+index DIR/neighbours.npz holds (on the device from load() on), and every result gains `neighbours` (K dicts {file,
+label, sq_distance}, nearest first), `knn_label`, `knn_agreement` and `kth_sq_distance`.  No prediction or probability
+changes.  The same combinations are refused as for novelty.
 """
 from __future__ import annotations
 
@@ -38,13 +44,20 @@ logger = get_logger(__name__)
 
 
 class Predictor:
-    def __init__(self, learnings_dir, tta=None, calibrated: bool = False, novelty: bool = False):
+    def __init__(self, learnings_dir, tta=None, calibrated: bool = False, novelty: bool = False, neighbours=None):
         from .tta import PRESETS
         if tta is not None and tta not in PRESETS:
             raise ValueError(f"unknown TTA preset {tta!r}: one of {', '.join(PRESETS)}")
         if novelty and tta is not None:
             raise ValueError("the novelty score cannot be combined with a TTA preset (a score over several views "
                              "is not defined)")
+        if neighbours is not None:
+            from ..nn import KNN_MAX_K
+            if isinstance(neighbours, bool) or int(neighbours) != neighbours or not 1 <= int(neighbours) <= KNN_MAX_K:
+                raise ValueError(f"neighbours must be a whole number in 1..{KNN_MAX_K}, got {neighbours!r}")
+            if tta is not None:
+                raise ValueError("nearest neighbours cannot be combined with a TTA preset (the features of several "
+                                 "views are not one point)")
         self.learnings_dir = Path(learnings_dir)
         self.tta = tta
         self.calibrated = bool(calibrated)
@@ -52,6 +65,9 @@ class Predictor:
         self.novelty = bool(novelty)
         self.novelty_data = None  # what novelty.json and novelty.npz hold, with novelty=True and after load()
         self._novelty_dev = None  # (mu0, W, M) on the model's device
+        self.neighbours = None if neighbours is None else int(neighbours)   # K, or None
+        self.neighbours_data = None   # what neighbours.json and neighbours.npz hold, with neighbours=K after load()
+        self._neighbours_dev = None   # the index's prepared features on the model's device
         self.model_loader = None
         self._initialized = False
         self._codec = None   # DeviceDecoder of the pooled batch path
@@ -68,10 +84,15 @@ class Predictor:
         if self.novelty:   # before the model: a missing file fails at once
             from . import novelty
             novelty.load(self.learnings_dir)
+        if self.neighbours is not None:   # before the model: a missing file fails at once
+            from . import neighbours
+            neighbours.require_files(self.learnings_dir)
         self.model_loader = ModelLoader(self.learnings_dir)
         self.model_loader.load()
         if self.novelty:
             self._load_novelty()
+        if self.neighbours is not None:
+            self._load_neighbours()
         self._initialized = True
 
     def _load_novelty(self) -> None:
@@ -94,6 +115,41 @@ class Predictor:
         self.novelty_data = data
         self._novelty_dev = tuple(torch.from_numpy(data[k]).to(model.device) for k in ("mu0", "W", "M"))
 
+    def _load_neighbours(self) -> None:
+        import torch
+
+        from .. import nn
+        from . import neighbours
+        model = self.model_loader.model
+        widths = getattr(model, "widths", None)
+        if getattr(model, "features_device", None) is None or not widths:
+            raise ValueError("nearest neighbours need a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
+        if not nn.novelty_dim_ok(int(widths[-1])):
+            raise ValueError(f"nearest neighbours need a last width that is a multiple of {nn.NOVELTY_DIM_STEP} in "
+                             f"{nn.NOVELTY_DIM_STEP}..{nn.NOVELTY_MAX_DIM}; this model's is {widths[-1]}")
+        data = neighbours.load(self.learnings_dir, dim=int(widths[-1]), labels=self.model_loader.labels)
+        if data["n"] < 1:
+            raise ValueError(f"{self.learnings_dir / neighbours.JSON_NAME}: the index is empty")
+        dtype = getattr(model, "infer_dtype", None)
+        if data["infer_dtype"] != dtype:
+            logger.warning("neighbours.json was built on %s features, these predictions are made in %s: the distances "
+                           "may not suit them", data["infer_dtype"], dtype)
+        self.neighbours_data = data
+        self._neighbours_dev = torch.from_numpy(data["features"]).to(model.device)
+
+    def _neighbour_rows(self, g) -> List[Dict[str, Any]]:
+        """The four neighbour keys of every row of the pooled features g [n,D] (device)."""
+        from .. import nn
+        from . import neighbours
+        data, labels = self.neighbours_data, self.model_loader.labels
+        d2, idx = nn.knn_topk(neighbours.prepare(g), self._neighbours_dev, self.neighbours)
+        d2, idx = d2.cpu().numpy(), idx.cpu().numpy()
+        v = neighbours.vote(idx, d2, data["gallery_labels"], len(labels))
+        return [{"neighbours": [{"file": data["files"][j], "label": labels[data["gallery_labels"][j]],
+                                 "sq_distance": float(s)} for j, s in zip(idx[i], d2[i]) if j >= 0],
+                 "knn_label": labels[v["knn_label"][i]], "knn_agreement": int(v["agreement"][i]),
+                 "kth_sq_distance": float(v["kth_sq_distance"][i])} for i in range(idx.shape[0])]
+
     def _prepare(self, arrays: List[np.ndarray]) -> np.ndarray:
         import torch
 
@@ -112,10 +168,10 @@ class Predictor:
                 out[k] = res[j]
         return out
 
-    def _result(self, path, original, probs, agreement=None, top=None, nov=None) -> Dict[str, Any]:
+    def _result(self, path, original, probs, agreement=None, top=None, nov=None, nb=None) -> Dict[str, Any]:
         """top: the predicted class where it is not to be taken from `probs` (calibrated rows: two probabilities that
         differ may round to one float at a high temperature, and the prediction is the uncalibrated row's).  nov:
-        (novelty score, row of M nearest) of this picture."""
+        (novelty score, row of M nearest) of this picture.  nb: its four neighbour keys."""
         labels = self.model_loader.labels
         top = int(np.argmax(probs)) if top is None else int(top)
         result = {"image_path": path, "top_prediction": labels[top], "confidence": float(probs[top]),
@@ -127,6 +183,8 @@ class Predictor:
             thr = float(self.novelty_data["threshold"])
             result.update(novelty_score=float(nov[0]), novelty_threshold=thr, known=bool(float(nov[0]) <= thr),
                           nearest_class=labels[self.novelty_data["present"][int(nov[1])]])
+        if nb is not None:
+            result.update(nb)
         return result
 
     def _calibrate(self, probs):
@@ -140,21 +198,26 @@ class Predictor:
         images at a time; the view agreement [n] (agree / v) with a TTA preset set, None without one; and with
         calibrated=True the predictions [n] (the rows are then the calibrated ones), None without; and with
         novelty=True the pairs [n,2] (novelty score, nearest row of M) from the features of the same passes, None
-        without."""
+        without; and with neighbours=K the rows' neighbour keys (_neighbour_rows) from those features, None without."""
         import torch
         model = self.model_loader.model
-        agreement = nov = None
+        agreement = nov = nb = None
         if self.tta is None:
-            if isinstance(x, np.ndarray) and self.calibration is None and not self.novelty:
-                return model.predict(x, batch_size=step), None, None, None
+            if isinstance(x, np.ndarray) and self.calibration is None and not self.novelty and self.neighbours is None:
+                return model.predict(x, batch_size=step), None, None, None, None
             if isinstance(x, np.ndarray):
                 x = torch.from_numpy(np.ascontiguousarray(x))
-            if self.novelty:
+            if self.novelty or self.neighbours is not None:
                 from .. import nn
                 passes = [model.features_device(x[b:b + step]) for b in range(0, x.shape[0], step)]
                 probs = torch.cat([p for p, _g in passes])
-                score, nearest, _d2 = nn.maha_score(torch.cat([g for _p, g in passes]), *self._novelty_dev)
-                nov = np.stack([score.cpu().numpy().astype(np.float64), nearest.cpu().numpy().astype(np.float64)], 1)
+                g = torch.cat([g for _p, g in passes])
+                if self.novelty:
+                    score, nearest, _d2 = nn.maha_score(g, *self._novelty_dev)
+                    nov = np.stack([score.cpu().numpy().astype(np.float64), nearest.cpu().numpy().astype(np.float64)],
+                                   1)
+                if self.neighbours is not None:
+                    nb = self._neighbour_rows(g)
             else:
                 probs = torch.cat([model.predict_device(x[b:b + step]).clone() for b in range(0, x.shape[0], step)])
         else:
@@ -170,13 +233,15 @@ class Predictor:
             probs, agreement = torch.cat(parts), torch.cat(agree).cpu().numpy() / float(len(rows))
         if self.calibration is not None:
             out, top = self._calibrate(probs)
-            return out, agreement, top, nov
-        return probs.cpu().numpy(), agreement, None, nov
+            return out, agreement, top, nov, nb
+        return probs.cpu().numpy(), agreement, None, nov, nb
 
-    def _results(self, paths, kept, natives, probs, agreement, top, nov=None) -> List[Dict[str, Any]]:
-        """One result per kept file: row j of probs (agreement, top, nov: [n] or None) belongs to paths[kept[j]]."""
+    def _results(self, paths, kept, natives, probs, agreement, top, nov=None, nb=None) -> List[Dict[str, Any]]:
+        """One result per kept file: row j of probs (agreement, top, nov, nb: [n] or None) belongs to
+        paths[kept[j]]."""
         return [self._result(paths[k], natives[k], probs[j], None if agreement is None else agreement[j],
-                             None if top is None else top[j], None if nov is None else nov[j])
+                             None if top is None else top[j], None if nov is None else nov[j],
+                             None if nb is None else nb[j])
                 for j, k in enumerate(kept)]
 
     def predict_single(self, image_path, use_transform: bool = False) -> Dict[str, Any]:
@@ -351,6 +416,8 @@ class Predictor:
         import torch
         if self.novelty:
             raise ValueError("the novelty score cannot be combined with class activation maps")
+        if self.neighbours is not None:
+            raise ValueError("nearest neighbours cannot be combined with class activation maps")
         if getattr(self.model_loader.model, "class_activation_maps", None) is None:
             raise ValueError("class activation maps need a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
         paths = [Path(p) for p in image_paths]
