@@ -1117,6 +1117,36 @@ int lf_head_distill_bwd_f32(const float* feat, const float* w, const float* prob
                             const float* soft, float temperature, float alpha, float* dlogits, float* dfeat,
                             float* dw, float* db, int n, int f, int c, float inv_n, lf_stream_t stream);
 
+/* Class weights and the focal loss: the head (lf_head_fwd_f32 / lf_head_bwd_f32 below) with a weight per class,
+ * cw [c] (device memory; null = no weights), and the modulating factor (1 - p)^gamma.  Per sample, with
+ * z = feat w + b, p = softmax(z) and y = ytrue, which is soft (label smoothing and mixed targets arrive that way):
+ *   s    = sum_j cw_j y_j                                   cw == null: s = 1 exactly
+ *   m_j  = (1 - p_j)^gamma                                  gamma == 0: m_j = 1 exactly, also at p_j = 1
+ *                                                           (powf(0, 0) is taken as 1)
+ *   loss = s sum_j -y_j m_j log(clip(p_j, 1e-7, 1 - 1e-7))  (lf_head_fwd_f32's clip; m_j takes the unclipped p_j)
+ * Outputs: probs = p, loss [n], sw [n] = s (the sample's weight, for reporting; may be null).
+ * gamma is accepted only if it is 0 or lies in [1, 8]; a NaN, a negative gamma, one in (0, 1) and one above 8 are
+ * refused before any launch.  (x -> x^gamma is not Lipschitz at 0 for gamma < 1, and 1 - p loses all its relative
+ * accuracy as p -> 1: there is no honest rounding bound in (0, 1).)  The values of cw are the caller's to validate
+ * (finite, >= 0, not all zero).  gamma == 0 with cw == null is lf_head_fwd_f32's loss; maxima and sums are reduced
+ * across the 64 lanes of a wave, so it agrees within rounding, not bit for bit.  c <= 4096, n > 0, f > 0.
+ * Unlike Keras' class_weight, which weighs a sample by cw_label alone, the sample weight here is taken over the
+ * target as it arrives: with label smoothing ls it is (1 - ls) cw_label + ls mean(cw), and a mixed target weighs by
+ * its mixture.  The loss is divided by the batch size (inv_n below), not by the sum of the weights, as in Keras. */
+int lf_head_focal_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue, const float* cw,
+                          float gamma, float* probs, float* loss, float* sw, int n, int f, int c,
+                          lf_stream_t stream);
+/* The gradient of the mean of `loss` over 1 / inv_n samples, by the unclipped rule, as lf_head_bwd_f32's:
+ *   l_j = log(max(p_j, FLT_MIN))                            FLT_MIN = 1.17549435e-38
+ *   u_j = y_j (gamma (1 - p_j)^(gamma-1) p_j l_j - m_j)     gamma == 0: u_j = -y_j
+ *   dlogits_k = s (u_k - p_k sum_j u_j) inv_n
+ * (u_j is p_j d(loss / s)/dp_j, and the softmax Jacobian dp_j/dz_k = p_j ([j == k] - p_k) does the rest.)
+ * dfeat = dlogits w^T, dw = feat^T dlogits, db = sum_n dlogits, computed as lf_head_bwd_f32 computes them.  A sample
+ * with s == 0 (its classes all have weight 0) gets a dlogits row of exact zeros.  gamma as for the forward entry. */
+int lf_head_focal_bwd_f32(const float* feat, const float* w, const float* probs, const float* ytrue,
+                          const float* cw, float gamma, float* dlogits, float* dfeat, float* dw, float* db, int n,
+                          int f, int c, float inv_n, lf_stream_t stream);
+
 /* Mixup and CutMix: lf_input_stage_f32 (below) writing a blend of two model views per image, and the same blend of
  * the targets.  For a batch of n images of h x w, mix8[i] = {partner, w_out, w_in, y0, y1, x0, x1, t} (device, f32):
  *   A_i  = image i after its own aug4[i] (flip, rotation, contrast about its own mean, clamp) on the [0,1] image:

@@ -197,6 +197,8 @@ SIGNATURES = {
     "lf_head_bwd_f32": [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_float, P],
     "lf_head_distill_fwd_f32": [P, P, P, P, P, c_float, c_float, P, P, P, P, c_int, c_int, c_int, P],
     "lf_head_distill_bwd_f32": [P, P, P, P, P, c_float, c_float, P, P, P, P, c_int, c_int, c_int, c_float, P],
+    "lf_head_focal_fwd_f32": [P, P, P, P, P, c_float, P, P, P, c_int, c_int, c_int, P],
+    "lf_head_focal_bwd_f32": [P, P, P, P, P, c_float, P, P, P, P, c_int, c_int, c_int, c_float, P],
     "lf_mul_f32": [P, P, P, c_size_t, P],
     "lf_adamw_workspace": [c_int],
     "lf_adamw_step_f32": [P, P, P, P, P, P, P, c_int, C.c_longlong, c_float, c_float, c_float,

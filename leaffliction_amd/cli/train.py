@@ -17,6 +17,11 @@ the teacher running its inference path on every batch (bf16 unless --no-mixed-pr
 with probability P an image is blended with a partner from its batch, by Mixup (lambda ~ Beta(ALPHA, ALPHA)) or
 CutMix (a pasted box of area 1 - lambda), a fair coin deciding where both are on, and the step trains on the labels
 blended in the same ratio.  Not together with --teacher.
+`--class-weights {balanced,sqrt,FILE}` and `--focal-gamma G` (default 0; 0 or 1..8) make the step lean on the rare
+classes: the loss of a sample becomes s * sum_j -y_j (1 - p_j)^G log p_j with s = sum_j w_j y_j (class_weight_preset
+gives the w of the two presets from the counts of the unsharded training items; FILE is a JSON object from label to
+weight).  The loss is divided by the batch size, not by the sum of the weights, as Keras' class_weight does; unlike
+Keras the sample weight is taken over the smoothed target, (1 - ls) w_label + ls mean(w).  Not together with --teacher.
 `--calibrate` fits the temperature behind `predict --calibrated` once the model is saved: the saved variant's
 probabilities on the validation sequence (its inference path, batch by batch) go through predict/calibration.py and
 the result is written to calibration.json in --out-dir.  The training step and meta.json are untouched; with more than
@@ -79,6 +84,11 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="CutMix with a box of area 1 - lambda, lambda ~ Beta(ALPHA, ALPHA); 0 = off")
     p.add_argument("--mix-prob", type=float, default=1.0, metavar="P",
                    help="probability that an image is mixed at all (with --mixup / --cutmix)")
+    p.add_argument("--class-weights", default=None, metavar="{balanced,sqrt,FILE}",
+                   help="weigh the loss by class: N / (C n_c), its square root scaled to a mean sample weight of 1, "
+                        "or a JSON file {label: weight}")
+    p.add_argument("--focal-gamma", type=float, default=0.0, metavar="G",
+                   help="focal loss: every term of the loss is scaled by (1 - p)^G; 0 = off, else 1 <= G <= 8")
     p.add_argument("--calibrate", action="store_true",
                    help="after saving, fit the temperature on the validation split and write calibration.json")
     p.add_argument("--out-dir", type=Path, default=Path("artifacts/models"),
@@ -195,6 +205,71 @@ def mix_setting(args):
     return {"mixup": mixup, "cutmix": cutmix, "prob": prob}
 
 
+def class_weight_preset(mode: str, counts: List[int]) -> List[float]:
+    """The weights of `--class-weights balanced` and `sqrt` from the training counts n_c (all > 0), with C classes and
+    N = sum n_c.  balanced: w_c = N / (C n_c).  sqrt: w_c proportional to sqrt(N / (C n_c)), scaled so that
+    sum_c n_c w_c = N: the mean sample weight is 1, as it is for balanced."""
+    import math
+    if not counts or min(counts) <= 0:
+        raise ValueError(f"class weights need a positive count for every class, got {counts}")
+    total, c = float(sum(counts)), len(counts)
+    if mode == "balanced":
+        return [total / (c * n) for n in counts]
+    if mode == "sqrt":
+        r = [math.sqrt(total / (c * n)) for n in counts]
+        scale = total / sum(n * v for n, v in zip(counts, r))
+        return [v * scale for v in r]
+    raise ValueError(f"unknown class-weight preset {mode!r}")
+
+
+def class_weights_from_file(path: Path, label2idx: Dict[str, int]) -> List[float]:
+    """`--class-weights FILE`: a JSON object from label to weight, in the order of label2idx.  Every label must be
+    present and no other (LeafCNN.compile checks the values: finite, >= 0, not all zero)."""
+    import json
+    if not Path(path).exists():
+        raise FileNotFoundError(f"--class-weights: {path} is neither 'balanced', 'sqrt' nor a file")
+    data = json.loads(Path(path).read_text(encoding="utf-8"))
+    if not isinstance(data, dict):
+        raise ValueError(f"--class-weights {path}: a JSON object from label to weight expected")
+    missing, unknown = sorted(set(label2idx) - set(data)), sorted(set(data) - set(label2idx))
+    if missing or unknown:
+        raise ValueError(f"--class-weights {path}: missing labels {missing}, unknown labels {unknown}")
+    try:
+        weights = [float(data[label]) for label in sorted(label2idx, key=lambda k: label2idx[k])]
+    except (TypeError, ValueError):
+        raise ValueError(f"--class-weights {path}: every weight must be a number") from None
+    return weights
+
+
+def weighted_setting(args, train_items, label2idx: Dict[str, int]):
+    """The "weighted" entry of the training configuration from --class-weights / --focal-gamma and what meta.json's
+    `training` entry gains ({"class_weights": {"mode", "weights": label -> weight} | None, "focal_gamma"}); (None, None)
+    when neither flag is given.  The counts are taken over all training items, before any sharding, so every rank
+    gets the same weights.  Refused with ValueError: a gamma that is neither 0 nor in [1, 8], a bad FILE, and the
+    combination with --teacher (the distillation head has no weighted form)."""
+    from .. import nn
+    gamma = nn.focal_gamma("--focal-gamma", args.focal_gamma)
+    mode = args.class_weights
+    if mode is None and gamma == 0.0:
+        return None, None
+    if args.teacher is not None:
+        raise ValueError("--class-weights / --focal-gamma cannot be combined with --teacher")
+    labels = sorted(label2idx, key=lambda k: label2idx[k])
+    weights = recorded = None
+    if mode is not None:
+        if mode in ("balanced", "sqrt"):
+            counts = [0] * len(labels)
+            for it in train_items:
+                counts[label2idx[it.label]] += 1
+            weights = class_weight_preset(mode, counts)
+        else:
+            weights = class_weights_from_file(Path(mode), label2idx)
+        recorded = {"mode": mode, "weights": dict(zip(labels, weights))}
+        LOGGER.info("Class weights (%s): %s", mode, ", ".join(f"{k}: {v:.4g}" for k, v in recorded["weights"].items()))
+    LOGGER.info("Focal gamma: %.3g", gamma)
+    return {"class_weights": weights, "gamma": gamma}, {"class_weights": recorded, "focal_gamma": gamma}
+
+
 def create_data_sequences(train_items, val_items, label2idx, args, cfg, num_classes, dp):
     seq_workers = get_optimal_worker_count()
     common = dict(num_classes=num_classes, one_hot=cfg["label_smoothing"] > 0.0, workers=seq_workers,
@@ -304,6 +379,9 @@ def main(argv=None) -> None:
             cfg["mix"] = mix
             LOGGER.info("Mixing: mixup alpha %.3g, cutmix alpha %.3g, probability %.3g", mix["mixup"], mix["cutmix"],
                         mix["prob"])
+        weighted, weighted_meta = weighted_setting(args, train_items, label2idx)
+        if weighted is not None:
+            cfg["weighted"] = weighted
         teacher = distillation = None
         if args.teacher is not None:
             teacher, distillation = load_teacher(args, label2idx)
@@ -317,6 +395,8 @@ def main(argv=None) -> None:
             meta["training"]["distillation"] = distillation
         if mix is not None:
             meta["training"]["mix"] = mix
+        if weighted_meta is not None:
+            meta["training"].update(weighted_meta)
         callbacks, ema_cb = build_callbacks(cfg)
         if getattr(args, "target_val_acc", None):
             callbacks.append(StopOnValAcc(args.target_val_acc))

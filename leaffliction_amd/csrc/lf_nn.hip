@@ -960,6 +960,90 @@ __global__ __launch_bounds__(64) void head_distill_fwd_kernel(
     }
 }
 
+// Weighted head: class weights cw (null = none) and the focal modulating factor.
+//   p = softmax(z), s = sum_j cw_j y_j (1 without cw), m_j = (1 - p_j)^gamma (1 at gamma == 0),
+//   loss = s sum_j -y_j m_j log(clip(p_j))
+// One workgroup = one wave per sample, laid out as head_distill_fwd_kernel: lane l owns the classes l, l+64, ...,
+// writes their logits to LDS and is the only lane that reads them back; the maximum and the three sums cross the
+// lanes by butterfly.  p_j <= 1 holds for what this kernel computes (the denominator contains the numerator and
+// float sums of non-negative terms are monotone); the fmaxf keeps powf's base non-negative all the same.
+__global__ __launch_bounds__(64) void head_focal_fwd_kernel(
+    const float* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ b,
+    const float* __restrict__ ytrue, const float* __restrict__ cw, float gamma, float* __restrict__ probs,
+    float* __restrict__ loss, float* __restrict__ sw, int f, int c) {
+    extern __shared__ float sm[];  // [c] logits
+    const int n = blockIdx.x;
+    const size_t row = (size_t)n * c;
+    float mz = -INFINITY;
+    for (int j = threadIdx.x; j < c; j += 64) {
+        float acc = b[j];
+        for (int i = 0; i < f; ++i) acc = fmaf(feat[(size_t)n * f + i], w[(size_t)i * c + j], acc);
+        sm[j] = acc;
+        mz = fmaxf(mz, acc);
+    }
+    mz = wave_max_all(mz);
+    float den = 0.f;
+    for (int j = threadIdx.x; j < c; j += 64) den += expf(sm[j] - mz);
+    den = wave_sum_all(den);
+    float l = 0.f, s = 0.f;
+    for (int j = threadIdx.x; j < c; j += 64) {
+        const float pr = expf(sm[j] - mz) / den;
+        probs[row + j] = pr;
+        const float yv = ytrue[row + j];
+        // keras categorical_crossentropy: clip to [1e-7, 1-1e-7] then -sum y log p; the factor takes the unclipped p
+        const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
+        const float m = gamma == 0.f ? 1.f : powf(fmaxf(1.f - pr, 0.f), gamma);
+        l -= yv * m * logf(pc);
+        if (cw != nullptr) s = fmaf(cw[j], yv, s);
+    }
+    l = wave_sum_all(l);
+    s = cw != nullptr ? wave_sum_all(s) : 1.f;
+    if (threadIdx.x == 0) {
+        loss[n] = s * l;
+        if (sw != nullptr) sw[n] = s;
+    }
+}
+
+// The weighted head's backward, unclipped as head_bwd_kernel's:
+//   l_j = log(max(p_j, FLT_MIN)), q_j = max(1 - p_j, 0), r_j = q_j^(gamma-1)   (powf(0, 0) = 1)
+//   u_j = y_j (gamma r_j p_j l_j - r_j q_j)   (-y_j at gamma == 0),  dlogits_k = s (u_k - p_k sum_j u_j) inv_n
+// One wave per sample; lane l owns u of the classes l, l+64, ... in LDS until dlogits replaces it, and after the
+// barrier every lane reads the whole row for dfeat = dlogits W^T (as head_bwd_kernel); (dW, db) by outer_sum_kernel.
+__global__ __launch_bounds__(64) void head_focal_bwd_kernel(
+    const float* __restrict__ probs, const float* __restrict__ ytrue, const float* __restrict__ cw, float gamma,
+    const float* __restrict__ w, float* __restrict__ dlogits, float* __restrict__ dfeat, int f, int c,
+    float inv_n) {
+    extern __shared__ float sm[];  // [c] u, then dlogits
+    const int n = blockIdx.x;
+    const size_t row = (size_t)n * c;
+    float su = 0.f, s = 0.f;
+    for (int j = threadIdx.x; j < c; j += 64) {
+        const float pr = probs[row + j], yv = ytrue[row + j];
+        float u = -yv;
+        if (gamma != 0.f) {
+            const float q = fmaxf(1.f - pr, 0.f);
+            const float r = powf(q, gamma - 1.f);
+            u = yv * (gamma * r * pr * logf(fmaxf(pr, FLT_MIN)) - r * q);
+        }
+        sm[j] = u;
+        su += u;
+        if (cw != nullptr) s = fmaf(cw[j], yv, s);
+    }
+    su = wave_sum_all(su);
+    s = cw != nullptr ? wave_sum_all(s) : 1.f;
+    for (int j = threadIdx.x; j < c; j += 64) {
+        const float d = s * (sm[j] - probs[row + j] * su) * inv_n;
+        sm[j] = d;
+        dlogits[row + j] = d;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < f; i += 64) {
+        float acc = 0.f;
+        for (int j = 0; j < c; ++j) acc = fmaf(sm[j], w[(size_t)i * c + j], acc);
+        dfeat[(size_t)n * f + i] = acc;
+    }
+}
+
 // dlogits = (probs - ytrue) * inv_n, or with kDistill
 //   [(1-alpha)(probs - ytrue) + alpha T soft] * inv_n   (hard_w = 1-alpha, soft_w = alpha T);
 // dfeat = dlogits W^T; (dW, db) by outer_sum_kernel
@@ -1089,6 +1173,18 @@ inline bool distill_args_ok(float temperature, float alpha) {
     return temperature > 0.f && temperature <= FLT_MAX && alpha >= 0.f && alpha <= 1.f;
 }
 
+// gamma == 0, or 1 <= gamma <= 8 (NaN fails every comparison).  x -> x^gamma is not Lipschitz at 0 for gamma < 1
+// and 1 - p has no relative accuracy left as p -> 1, so (0, 1) has no rounding bound to offer.
+inline bool focal_gamma_ok(float gamma) { return gamma == 0.f || (gamma >= 1.f && gamma <= 8.f); }
+
+// What every head's backward ends with: dW[f][c] = sum_n feat[n][f] dlogits[n][c]; db[c] = sum_n dlogits[n][c]
+int head_weight_grads(const char* what, const float* feat, const float* dlogits, float* dw, float* db, int n, int f,
+                      int c, hipStream_t st) {
+    outer_sum_kernel<<<(unsigned)(((size_t)(f + 1) * c + 63) / 64), kBlock, 0, st>>>(feat, dlogits, dw, db,
+                                                                                   n, f, c);
+    return lf::check_launch(what);
+}
+
 // The backward pass of both heads: dlogits and dfeat per sample, then (dW, db) over the batch.
 template <bool kDistill>
 int head_bwd_launch(const char* what, const float* feat, const float* w, const float* probs, const float* ytrue,
@@ -1097,10 +1193,7 @@ int head_bwd_launch(const char* what, const float* feat, const float* w, const f
     hipStream_t st = lf::as_stream(stream);
     head_bwd_kernel<kDistill><<<n, 64, (size_t)c * sizeof(float), st>>>(probs, ytrue, soft, hard_w, soft_w, w,
                                                                        dlogits, dfeat, f, c, inv_n);
-    // dW[f][c] = sum_n feat[n][f] dlogits[n][c]; db[c] = sum_n dlogits[n][c]
-    outer_sum_kernel<<<(unsigned)(((size_t)(f + 1) * c + 63) / 64), kBlock, 0, st>>>(feat, dlogits, dw, db,
-                                                                                   n, f, c);
-    return lf::check_launch(what);
+    return head_weight_grads(what, feat, dlogits, dw, db, n, f, c, st);
 }
 
 // lf_input_stage_f32 (mix8 == nullptr) and lf_input_stage_mix_f32: the contrast means, then the stage's kernel
@@ -1544,6 +1637,31 @@ int lf_head_distill_bwd_f32(const float* feat, const float* w, const float* prob
                "alpha=%g (0..1)", (double)temperature, (double)alpha);
     return head_bwd_launch<true>("lf_head_distill_bwd", feat, w, probs, ytrue, soft, 1.f - alpha,
                                  alpha * temperature, dlogits, dfeat, dw, db, n, f, c, inv_n, stream);
+}
+
+int lf_head_focal_fwd_f32(const float* feat, const float* w, const float* b, const float* ytrue, const float* cw,
+                          float gamma, float* probs, float* loss, float* sw, int n, int f, int c,
+                          lf_stream_t stream) {
+    LF_REQUIRE(feat && w && b && ytrue && probs && loss, "lf_head_focal_fwd: null buffer");
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= kHeadMaxClasses, "lf_head_focal_fwd: bad dims n=%d f=%d c=%d", n, f,
+               c);
+    LF_REQUIRE(focal_gamma_ok(gamma), "lf_head_focal_fwd: bad gamma=%g (0, or 1..8)", (double)gamma);
+    head_focal_fwd_kernel<<<n, 64, (size_t)c * sizeof(float), lf::as_stream(stream)>>>(feat, w, b, ytrue, cw, gamma,
+                                                                                     probs, loss, sw, f, c);
+    return lf::check_launch("lf_head_focal_fwd");
+}
+
+int lf_head_focal_bwd_f32(const float* feat, const float* w, const float* probs, const float* ytrue,
+                          const float* cw, float gamma, float* dlogits, float* dfeat, float* dw, float* db, int n,
+                          int f, int c, float inv_n, lf_stream_t stream) {
+    LF_REQUIRE(feat && w && probs && ytrue && dlogits && dfeat && dw && db, "lf_head_focal_bwd: null buffer");
+    LF_REQUIRE(n > 0 && f > 0 && c > 0 && c <= kHeadMaxClasses, "lf_head_focal_bwd: bad dims n=%d f=%d c=%d", n, f,
+               c);
+    LF_REQUIRE(focal_gamma_ok(gamma), "lf_head_focal_bwd: bad gamma=%g (0, or 1..8)", (double)gamma);
+    hipStream_t st = lf::as_stream(stream);
+    head_focal_bwd_kernel<<<n, 64, (size_t)c * sizeof(float), st>>>(probs, ytrue, cw, gamma, w, dlogits, dfeat, f, c,
+                                                                  inv_n);
+    return head_weight_grads("lf_head_focal_bwd", feat, dlogits, dw, db, n, f, c, st);
 }
 
 int lf_mul_f32(const float* a, const float* b, float* out, size_t count, lf_stream_t stream) {

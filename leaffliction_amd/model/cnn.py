@@ -148,6 +148,8 @@ class LeafCNN:
     _mut = 0                            # see __init__ (class-level defaults: subclasses that skip it still step)
     last_kd: Optional[torch.Tensor] = None   # train_step with a teacher: the per-sample kd term
     last_targets: Optional[torch.Tensor] = None   # train_step with mixing on: the mixed targets the step trained on
+    last_sample_weights: Optional[torch.Tensor] = None   # train_step with a "weighted" loss: s of every sample
+    _cw_dev: Optional[torch.Tensor] = None   # the compiled class weights: one fixed device buffer [C]
     _infer_cache: Dict[str, Any] = {}
 
     def __init__(self, *, num_classes: int, img_size: int = 224, use_norm: bool = True,
@@ -604,7 +606,9 @@ class LeafCNN:
         In training mode the step runs in self.train_dtype (see set_training_dtype) and every tensor
         the backward pass needs is kept in self._saved.  teacher_probs (f32 [N,C], with y_true): the head is the
         distillation head at the compiled alpha / temperature, the loss the combined one, and the kd term alone
-        is left in _kd_buf(N)."""
+        is left in _kd_buf(N).  With a compiled "weighted" setting the training head is the weighted one
+        (lf_head_focal_*_f32): the loss carries the class weights and the focal factor, and the sample weights are
+        left in _sw_buf(N); inference and evaluation (training False) keep the plain head."""
         n, _c, h, w = x0.shape
         bf16 = training and self.train_dtype == "bf16"
         if bf16 and not (self.use_se and self._bf16_storage_ok(h, w)):
@@ -672,6 +676,11 @@ class LeafCNN:
             nn.head_distill_fwd(feat, P["dense.w"], P["dense.b"], y_true, teacher_probs, temperature, alpha, probs,
                                 soft, loss, self._kd_buf(n))
             sv.update({"soft": soft, "distill": (alpha, temperature)})
+        elif training and y_true is not None and self._weighted_setting() is not None:
+            cw, gamma = self._weighted_setting()
+            cw = self._cw_dev if cw is not None else None
+            nn.head_focal_fwd(feat, P["dense.w"], P["dense.b"], y_true, cw, gamma, probs, loss, self._sw_buf(n))
+            sv["weighted"] = (cw, gamma)
         else:
             nn.head_fwd(feat, P["dense.w"], P["dense.b"], y_true, probs, loss)
         sv.update({"feat": feat, "top_drop": top_drop, "probs": probs, "y_true": y_true,
@@ -719,6 +728,10 @@ class LeafCNN:
                 alpha, temperature = sv["distill"]
                 nn.head_distill_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], sv["soft"], temperature,
                                     alpha, dlogits, dfeat, G["dense.w"], G["dense.b"], inv_n)
+            elif sv.get("weighted") is not None:
+                cw, gamma = sv["weighted"]
+                nn.head_focal_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], cw, gamma, dlogits, dfeat,
+                                  G["dense.w"], G["dense.b"], inv_n)
             else:
                 nn.head_bwd(sv["feat"], P["dense.w"], sv["probs"], sv["y_true"], dlogits, dfeat,
                             G["dense.w"], G["dense.b"], inv_n)
@@ -890,6 +903,10 @@ class LeafCNN:
         With a compiled "mix" setting the step draws its Mixup / CutMix rows, mixes within the local batch in the input
         stage and trains on the mixed targets, which `last_targets` holds afterwards (None otherwise); a teacher
         and mixing together are refused.
+        With a compiled "weighted" setting the step minimises the class-weighted focal loss (lf_head_focal_*_f32) on
+        the targets it trains on, mixed ones included; the returned loss is that loss and `last_sample_weights` holds
+        every sample's weight s = sum_j cw_j y_j (None otherwise).  It is refused together with a teacher: the
+        distillation head has no weighted form.
         grad_sync(flat_g) is called between backward and the optimizer (data-parallel
         all-reduce); with global_n the local gradient is scaled by 1/global_n so that a SUM
         all-reduce yields the global-batch mean.  Returns (probs, per-sample loss) device
@@ -920,6 +937,10 @@ class LeafCNN:
             raise ValueError("train_step: Mixup / CutMix with a teacher is not supported (the teacher would have to "
                              "see the mixed image, which exists only inside this model's input stage)")
         self.last_targets = self._mixed_targets_buf(n, self.num_classes) if mixing else None
+        weighted = self._weighted_setting() is not None and n > 0
+        if weighted and extra:
+            raise ValueError("train_step: " + self._WEIGHTED_WITH_TEACHER)
+        self.last_sample_weights = self._sw_buf(n) if weighted else None
         if grad_overlap is not None:
             # two exchanges, the same two on every rank (a rank with an empty batch sends zeros in both)
             split = min(self.n_params, -(-self.grad_split() // 64) * 64)   # whole 256-byte lines per piece
@@ -960,7 +981,8 @@ class LeafCNN:
         this off.  teacher_probs (train_step) has a fixed buffer of its own, st["t"], and the distillation setting
         is part of the graph's key: the step with a teacher and the step without are two graphs.  The Mixup /
         CutMix rows are one more view of the staging buffer and the mix setting one more part of the key: a model
-        compiled without mixing replays the graph it always did."""
+        compiled without mixing replays the graph it always did.  The "weighted" setting (class weights and gamma) is
+        a part of the key in the same way; the weights themselves sit in one fixed device buffer."""
         if self._graphs_on and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8:
             return self._forward_backward_graph(x, y_true, between, teacher_probs)
         return self._forward_backward_eager(x, y_true, between, teacher_probs)
@@ -975,6 +997,8 @@ class LeafCNN:
         if self._mix_setting() is not None:
             key += (("mix",) + self._mix_setting(),)
             mix_hw = (int(x.shape[1]), int(x.shape[2]))
+        if self._weighted_setting() is not None:
+            key += (("weighted",) + self._weighted_setting(),)
         st = self._graphs.get(key)
         if st is None:
             st = self._graphs[key] = {"calls": 0, "graph": None}
@@ -1100,10 +1124,23 @@ class LeafCNN:
         are given a teacher's probabilities; and with "mix": {"mixup": a, "cutmix": b, "prob": p} (alphas >= 0 and
         finite, 0 <= p <= 1, default 1): every training step blends each image of its batch with a partner, by Mixup
         (lambda ~ Beta(a, a)) or CutMix (a box of area 1 - lambda, lambda ~ Beta(b, b)) with probability p, and
-        trains on the targets blended the same way (draw_mix_rows).  Mixing is off unless an alpha is positive."""
+        trains on the targets blended the same way (draw_mix_rows).  Mixing is off unless an alpha is positive.
+        "weighted": {"class_weights": [w_0, ..] | None, "gamma": g} (one finite weight >= 0 per class, not all zero;
+        g = 0 or 1 <= g <= 8): every training step minimises s * sum_j -y_j (1 - p_j)^g log p_j with the sample
+        weight s = sum_j w_j y_j taken over the target as the step sees it (smoothed, mixed), divided by the batch
+        size, not by the sum of the weights.  Off when the weights are None and g is 0; works together with "mix";
+        refused together with "distill"."""
         self._compiled = {"optimizer": optimizer or {}, "loss": loss or {}, "metrics": metrics or []}
         self._distill_setting()
         self._mix_setting()
+        weighted = self._weighted_setting()
+        if weighted is not None:
+            if self._distill_setting() is not None:
+                raise ValueError("compile: " + self._WEIGHTED_WITH_TEACHER)
+            if weighted[0] is not None:
+                if self._cw_dev is None:
+                    self._cw_dev = torch.empty(self.num_classes, dtype=torch.float32, device=self.device)
+                self._cw_dev.copy_(torch.tensor(weighted[0], dtype=torch.float32))
 
     def _distill_setting(self, required: bool = False) -> Optional[Tuple[float, float]]:
         """(alpha, temperature) of the compiled loss, None when it has no "distill"."""
@@ -1132,6 +1169,30 @@ class LeafCNN:
         if not 0.0 <= prob <= 1.0:
             raise ValueError(f"mix: prob must lie in [0, 1], got {prob}")
         return (mixup, cutmix, prob) if (mixup > 0 or cutmix > 0) else None
+
+    _WEIGHTED_WITH_TEACHER = ('a "weighted" loss (class weights / focal gamma) with a teacher is not supported: the '
+                              'distillation head has no weighted form')
+
+    def _weighted_setting(self) -> Optional[Tuple[Optional[Tuple[float, ...]], float]]:
+        """(class weights or None, gamma) of the compiled loss; None when it has no "weighted", or the weights are None
+        and gamma is 0."""
+        d = self._compiled.get("loss", {}).get("weighted")
+        if d is None:
+            return None
+        gamma = nn.focal_gamma("weighted", d.get("gamma", 0.0) or 0.0)
+        cw = d.get("class_weights")
+        if cw is None:
+            return (None, gamma) if gamma != 0.0 else None
+        cw = tuple(float(v) for v in cw)
+        if len(cw) != self.num_classes:
+            raise ValueError(f"weighted: {len(cw)} class weights for {self.num_classes} classes")
+        if not all(math.isfinite(v) and v >= 0.0 for v in cw) or not any(v > 0.0 for v in cw):
+            raise ValueError(f"weighted: class weights must be finite, >= 0 and not all zero, got {cw}")
+        return cw, gamma
+
+    def _sw_buf(self, n: int) -> torch.Tensor:
+        """The sample weights s of the last weighted step at batch n."""
+        return self._buf(n, "sw", (n,))
 
     def _mixed_targets_buf(self, n: int, c: int) -> torch.Tensor:
         """The mixed targets of the last mixing step at batch n."""
@@ -1174,12 +1235,18 @@ class LeafCNN:
 
         With a compiled "mix" setting (Mixup / CutMix) the training loss is the one against the mixed targets and the
         training accuracy counts a prediction as right when it is the argmax of the mixed target, the class with the
-        larger share of the image; validation is untouched.  A teacher together with mixing is refused."""
+        larger share of the image; validation is untouched.  A teacher together with mixing is refused.
+
+        With a compiled "weighted" setting (class weights / focal gamma) "loss" is the weighted loss: the mean over
+        the samples of s * sum_j -y_j (1 - p_j)^gamma log p_j, so it is not comparable with "val_loss", which stays
+        plain cross-entropy.  A teacher together with it is refused."""
         import logging
         import random as _random
         log = logging.getLogger(__name__)
         opt = self._compiled.get("optimizer", {})
         if teacher is not None:
+            if self._weighted_setting() is not None:
+                raise ValueError("fit: " + self._WEIGHTED_WITH_TEACHER)
             if self._mix_setting() is not None:
                 raise ValueError("fit: Mixup / CutMix with a teacher is not supported (the teacher would have to see "
                                  "the mixed image, which exists only inside this model's input stage)")

@@ -1287,6 +1287,34 @@ def head_distill_bwd(feat, w, probs, ytrue, soft, temperature: float, alpha: flo
               dw.data_ptr(), db.data_ptr(), n, f, c, float(inv_n), _stream())
 
 
+def focal_gamma(who: str, gamma) -> float:
+    """The focal exponent as the weighted head takes it: 0, or 1 <= gamma <= 8 (lf_head_focal_fwd_f32 says why)."""
+    gamma = float(gamma)
+    if not (gamma == 0.0 or 1.0 <= gamma <= 8.0):
+        raise ValueError(f"{who}: gamma must be 0 or lie in [1, 8], got {gamma}")
+    return gamma
+
+
+def head_focal_fwd(feat, w, b, ytrue, cw, gamma: float, probs, loss, sw=None):
+    """The weighted head (lf_head_focal_fwd_f32): class weights cw [C] (or None) and the focal factor
+    (1 - p)^gamma; writes probs, loss and (optionally) sw, the weight s of every sample."""
+    n, f, c = _head_distill_checks("head_focal_fwd", feat, w, {
+        "b": (b, "c"), "ytrue": (ytrue, "nc"), "cw": (cw, "c"), "probs": (probs, "nc"), "loss": (loss, "n"),
+        "sw": (sw, "n")})
+    _lib.call("lf_head_focal_fwd_f32", feat.data_ptr(), w.data_ptr(), b.data_ptr(), ytrue.data_ptr(), _ptr(cw),
+              focal_gamma("head_focal_fwd", gamma), probs.data_ptr(), loss.data_ptr(), _ptr(sw), n, f, c, _stream())
+    return probs
+
+
+def head_focal_bwd(feat, w, probs, ytrue, cw, gamma: float, dlogits, dfeat, dw, db, inv_n):
+    n, f, c = _head_distill_checks("head_focal_bwd", feat, w, {
+        "probs": (probs, "nc"), "ytrue": (ytrue, "nc"), "cw": (cw, "c"), "dlogits": (dlogits, "nc"),
+        "dfeat": (dfeat, "nf"), "dw": (dw, "fc"), "db": (db, "c")})
+    _lib.call("lf_head_focal_bwd_f32", feat.data_ptr(), w.data_ptr(), probs.data_ptr(), ytrue.data_ptr(), _ptr(cw),
+              focal_gamma("head_focal_bwd", gamma), dlogits.data_ptr(), dfeat.data_ptr(), dw.data_ptr(),
+              db.data_ptr(), n, f, c, float(inv_n), _stream())
+
+
 def mul(a, b, out):
     if a.shape != b.shape or out.shape != a.shape:
         raise ValueError("mul: shape mismatch")

@@ -49,7 +49,8 @@ def build_optimizer(cfg: Dict, base_lr) -> Dict[str, Any]:
 def build_loss(cfg: Dict) -> Dict[str, Any]:
     """CategoricalCrossentropy(label_smoothing) or sparse CCE (utils.py:30-35); a cfg that carries
     "distill": {"alpha", "temperature"} (train --teacher) hands it on to LeafCNN.compile, and so does one that
-    carries "mix": {"mixup", "cutmix", "prob"} (train --mixup / --cutmix)."""
+    carries "mix": {"mixup", "cutmix", "prob"} (train --mixup / --cutmix) or "weighted": {"class_weights", "gamma"}
+    (train --class-weights / --focal-gamma)."""
     ls = float(cfg.get("label_smoothing", 0.0) or 0.0)
     loss: Dict[str, Any] = {"name": "categorical_crossentropy" if ls > 0 else "sparse_categorical_crossentropy",
                             "label_smoothing": ls}
@@ -59,6 +60,10 @@ def build_loss(cfg: Dict) -> Dict[str, Any]:
     if cfg.get("mix") is not None:
         loss["mix"] = {"mixup": float(cfg["mix"]["mixup"]), "cutmix": float(cfg["mix"]["cutmix"]),
                        "prob": float(cfg["mix"]["prob"])}
+    if cfg.get("weighted") is not None:
+        cw = cfg["weighted"].get("class_weights")
+        loss["weighted"] = {"class_weights": None if cw is None else [float(v) for v in cw],
+                            "gamma": float(cfg["weighted"].get("gamma", 0.0))}
     return loss
 
 
