@@ -1167,6 +1167,39 @@ int lf_input_stage_mix_f32(const uint8_t* in, float* out, int n, int h, int w, c
                            lf_stream_t stream);
 int lf_mix_targets_f32(const float* y, const float* mix8, float* out, int n, int c, lf_stream_t stream);
 
+/* The online augmentation policy: one projective warp, one colour transform and one erase box per image, in place
+ * of lf_input_stage_f32's flip / rotation / contrast.  in u8 HWC [n,h,w,3] -> out f32 NCHW [n,3,h,w]; pol24 (device,
+ * f32 [n][24]) holds per image
+ *   {a,b,c,d,e,f,g,k}     floats 0..7: the inverse map, output -> source, a homography whose last entry is 1;
+ *   M (3x3, row-major), t floats 8..16 and 17..19: the colour transform;
+ *   {y0,y1,x0,x1}         floats 20..23: the erase box.
+ * mean3 / denom3 are host pointers, both set or both null, as for lf_pack_hwc_u8_to_nchw_f32.  No scratch: there is
+ * no mean pass, contrast pivots on a constant that t carries.  Output pixel (oy, ox):
+ *   erase   y0 <= oy < y1 and x0 <= ox < x1 (output coordinates): the value stored is exactly 0.0f, with
+ *           normalisation the dataset mean, and nothing is sampled.  A NaN edge, or y1 <= y0, or x1 <= x0, puts every
+ *           pixel outside.
+ *   warp    cx = (w-1)/2, cy = (h-1)/2, u = ox - cx, v = oy - cy, in fp32 in this order and without contraction:
+ *             den = max(g*u + k*v + 1, 1/16)
+ *             fx  = (a*u + b*v + c)/den + cx          fy = (d*u + e*v + f)/den + cy
+ *           (the division correctly rounded), fx and fy then clamped into [-2^20, 2^20] (a NaN is read as -2^20);
+ *           x0 = floor(fx), ax = fx - x0, y0 = floor(fy), ay = fy - y0, the taps x0, x0 + 1, y0, y0 + 1 reflected as
+ *           lf_tta_views_f32 reflects them, and b = top + (bot - top)*ay, top = v00 + (v01 - v00)*ax,
+ *           bot = v10 + (v11 - v10)*ax on the bytes as floats; p = b/255 per channel.  A mirror is a = -1: there is
+ *           no flip field.
+ *   colour  q_c = min(max(((M_c0*p_r + M_c1*p_g) + M_c2*p_b) + t_c, 0), 1), a NaN read as 0.
+ *   value   q_c, or (q_c - mean_c)/denom_c with mean3 set: the subtraction and the division each rounded on its own,
+ *           the arithmetic of lf_pack_hwc_u8_to_nchw_f32.
+ * Exact cases: the identity row ({1,0,0,0,1,0,0,0}, M = I, t = 0, an empty box) equals lf_pack_hwc_u8_to_nchw_f32 bit
+ * for bit; a pure mirror (a = -1), or an integer translation (c, f), with the identity M equals the pack of the
+ * mirrored or moved (reflected) image bit for bit.
+ * The rows are device data, so a bad one cannot be refused without a sync.  Whatever a row holds (NaN, infinities, a
+ * huge perspective term) nothing outside `in` is read and every value stored is finite and lies between the images of
+ * 0 and 1 under the normalisation; which value such a row gives is not specified.
+ * Refused before any launch: null buffers, n <= 0, n > 65535, h < 2, w < 2, h*w > 2^28, mean3 / denom3 not both set
+ * or both null, a mean that is not finite, a denom that is zero or not finite. */
+int lf_input_stage_policy_f32(const uint8_t* in, float* out, int n, int h, int w, const float* pol24,
+                              const float* mean3, const float* denom3, lf_stream_t stream);
+
 /* Test-time augmentation: v views of every image of a batch in one launch, and the v probability rows of every
  * image folded back into one.
  * lf_tta_views_f32: in u8 HWC [n,h,w,3] -> out f32 NCHW [n*v,3,h,w], image-major: row i*v + k is view k of image i.

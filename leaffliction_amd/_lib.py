@@ -154,6 +154,7 @@ SIGNATURES = {
     "lf_input_stage_f32": [P, P, c_int, c_int, c_int, P, P, P, P, P],
     "lf_input_stage_mix_f32": [P, P, c_int, c_int, c_int, P, P, P, P, P, P],
     "lf_mix_targets_f32": [P, P, P, c_int, c_int, P],
+    "lf_input_stage_policy_f32": [P, P, c_int, c_int, c_int, P, P, P, P],
     "lf_tta_views_f32": [P, P, c_int, c_int, c_int, P, c_int, P, P, P],
     "lf_tta_combine_f32": [P, P, c_int, P, P, P, c_int, c_int, P],
     "lf_calib_stats_workspace": [c_int, c_int, c_int],

@@ -22,6 +22,13 @@ classes: the loss of a sample becomes s * sum_j -y_j (1 - p_j)^G log p_j with s 
 gives the w of the two presets from the counts of the unsharded training items; FILE is a JSON object from label to
 weight).  The loss is divided by the batch size, not by the sum of the weights, as Keras' class_weight does; unlike
 Keras the sample weight is taken over the smoothed target, (1 - ls) w_label + ls mean(w).  Not together with --teacher.
+`--augment-policy {light,medium,strong}` (default: off) replaces the in-model flip / rotation / contrast by an
+augmentation policy drawn afresh for every image of every step (model.cnn.POLICY_PRESETS: mirror, turn, shear,
+perspective skew, crop, brightness, contrast, saturation, hue, random erasing; `strong` stands in for the offline
+Augmentation pass' ranges), applied by one fused input-stage kernel; not together with --mixup / --cutmix.
+`--balanced-sampling` (default: off) draws every training epoch so that all classes fill the same number of its slots
+(ManifestSequence(balanced=True)); validation is untouched.  Together the two train from the original, unbalanced
+folders without an offline balancing pass.
 `--calibrate` fits the temperature behind `predict --calibrated` once the model is saved: the saved variant's
 probabilities on the validation sequence (its inference path, batch by batch) go through predict/calibration.py and
 the result is written to calibration.json in --out-dir.  The training step and meta.json are untouched; with more than
@@ -89,6 +96,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "or a JSON file {label: weight}")
     p.add_argument("--focal-gamma", type=float, default=0.0, metavar="G",
                    help="focal loss: every term of the loss is scaled by (1 - p)^G; 0 = off, else 1 <= G <= 8")
+    p.add_argument("--augment-policy", choices=["light", "medium", "strong"], default=None,
+                   help="online augmentation policy in place of the in-model flip / rotation / contrast")
+    p.add_argument("--balanced-sampling", action="store_true",
+                   help="class-balanced sampling of the training items, every epoch anew")
     p.add_argument("--calibrate", action="store_true",
                    help="after saving, fit the temperature on the validation split and write calibration.json")
     p.add_argument("--out-dir", type=Path, default=Path("artifacts/models"),
@@ -205,6 +216,21 @@ def mix_setting(args):
     return {"mixup": mixup, "cutmix": cutmix, "prob": prob}
 
 
+def policy_setting(args):
+    """The "policy" entry of the training configuration (the preset's name) and what meta.json's `training` entry
+    gains ({"augment_policy": {"name", "ranges"}}) from --augment-policy; (None, None) when it is not given.  Refused
+    with ValueError together with --mixup / --cutmix: the mixing input stage samples flip / rotation / contrast
+    views, not policy rows."""
+    from ..model.cnn import resolve_policy
+    name = args.augment_policy
+    if name is None:
+        return None, None
+    if float(args.mixup) != 0.0 or float(args.cutmix) != 0.0:
+        raise ValueError("--augment-policy cannot be combined with --mixup / --cutmix")
+    ranges = {k: list(v) if isinstance(v, tuple) else v for k, v in resolve_policy(name).items()}
+    return name, {"augment_policy": {"name": name, "ranges": ranges}}
+
+
 def class_weight_preset(mode: str, counts: List[int]) -> List[float]:
     """The weights of `--class-weights balanced` and `sqrt` from the training counts n_c (all > 0), with C classes and
     N = sum n_c.  balanced: w_c = N / (C n_c).  sqrt: w_c proportional to sqrt(N / (C n_c)), scaled so that
@@ -275,7 +301,7 @@ def create_data_sequences(train_items, val_items, label2idx, args, cfg, num_clas
     common = dict(num_classes=num_classes, one_hot=cfg["label_smoothing"] > 0.0, workers=seq_workers,
                   rank=dp.rank, world=dp.world)
     train_seq = ManifestSequence(train_items, label2idx, args.img_size, args.batch_size, shuffle=True,
-                                 seed=args.seed, cache=cfg["cache"], **common)
+                                 seed=args.seed, cache=cfg["cache"], balanced=bool(args.balanced_sampling), **common)
     val_seq = ManifestSequence(val_items, label2idx, args.img_size, args.batch_size, shuffle=False,
                                seed=args.seed, cache=True, **common)
     return train_seq, val_seq
@@ -382,6 +408,12 @@ def main(argv=None) -> None:
         weighted, weighted_meta = weighted_setting(args, train_items, label2idx)
         if weighted is not None:
             cfg["weighted"] = weighted
+        policy, policy_meta = policy_setting(args)
+        if policy is not None:
+            cfg["policy"] = policy
+            LOGGER.info("Augmentation policy: %s %s", policy, policy_meta["augment_policy"]["ranges"])
+        if args.balanced_sampling:
+            LOGGER.info("Balanced sampling: every class fills the same number of slots of a training epoch")
         teacher = distillation = None
         if args.teacher is not None:
             teacher, distillation = load_teacher(args, label2idx)
@@ -397,6 +429,10 @@ def main(argv=None) -> None:
             meta["training"]["mix"] = mix
         if weighted_meta is not None:
             meta["training"].update(weighted_meta)
+        if policy_meta is not None:
+            meta["training"].update(policy_meta)
+        if args.balanced_sampling:
+            meta["training"]["balanced_sampling"] = True
         callbacks, ema_cb = build_callbacks(cfg)
         if getattr(args, "target_val_acc", None):
             callbacks.append(StopOnValAcc(args.target_val_acc))

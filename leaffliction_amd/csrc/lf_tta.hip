@@ -4,18 +4,21 @@
 //
 // Built without FMA contraction (Makefile, NO_CONTRACT): a view row with cos = 1, sin = 0, zoom = 1 and integer
 // shifts has integer source coordinates in exact arithmetic, every product and sum below is then exact in fp32, the
-// interpolation weights are 0, and what is stored is pack_value's arithmetic (lf_augment.hip) on the source byte:
+// interpolation weights are 0, and what is stored is pack_value's arithmetic (lf_sample.h) on the source byte:
 // lf_pack_hwc_u8_to_nchw_f32 of the moved image, bit for bit.
 #include <limits.h>
 #include <math.h>
 
 #include "lf_common.h"
+#include "lf_sample.h"
 #include "lf_wave.h"
 
 namespace {
 
 using lf::kHeadMaxClasses;
+using lf::pack_value;
 using lf::take_larger;
+using lf::taps;
 using lf::wave_argmax_all;
 
 constexpr int kBlock = 256;
@@ -28,36 +31,6 @@ struct ViewRows {
 struct ViewWeights {
     float w[kMaxViews];
 };
-
-// position of index i in its period of 2n (fill_mode="reflect", lf_nn.hip's reflect_idx: d c b a | a b c d | d c b a),
-// for any number of periods and negative i; most indices lie inside the first period and skip the division
-__device__ __forceinline__ int period_pos(int i, int period) {
-    if ((unsigned)i >= (unsigned)period) {
-        i %= period;
-        if (i < 0) i += period;
-    }
-    return i;
-}
-__device__ __forceinline__ int fold(int m, int n) { return m < n ? m : 2 * n - 1 - m; }
-
-// floor(f) and its neighbour, both reflected into [0, n); *frac = f - floor(f).  A coordinate beyond +-2^30 (a
-// zoom or shift of that size) is held there, so that the integer arithmetic stays defined; the indices are in range
-// whatever f is, a NaN included.
-__device__ __forceinline__ void taps(float f, int n, int* i0, int* i1, float* frac) {
-    const float f0 = floorf(f);
-    *frac = f - f0;
-    const int period = 2 * n;
-    const int m = period_pos((int)fminf(fmaxf(f0, -1073741824.f), 1073741824.f), period);
-    *i0 = fold(m, n);
-    *i1 = fold(m + 1 == period ? 0 : m + 1, n);
-}
-
-// pack_value of lf_augment.hip: every division and the subtraction round on their own
-template <bool NORM>
-__device__ __forceinline__ float pack_value(float byte, float mean, float denom) {
-    const float v = __fdiv_rn(byte, 255.0f);
-    return NORM ? __fdiv_rn(__fsub_rn(v, mean), denom) : v;
-}
 
 // One thread = one output pixel, for all v views of its image one after the other: grid = (pixel blocks, images), and
 // the blocks of one image are neighbours in one XCD's dispatch sequence (lf::xcd_block2), so the 3*h*w source bytes of
@@ -99,10 +72,7 @@ __global__ __launch_bounds__(kBlock) void tta_views_kernel(const uint8_t* __rest
         float* dst = out + ((size_t)blk.y * v + k) * 3 * hw + p;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float v00 = r0[xs[0] * 3 + c], v01 = r0[xs[1] * 3 + c];
-            const float v10 = r1[xs[0] * 3 + c], v11 = r1[xs[1] * 3 + c];
-            const float top = v00 + (v01 - v00) * ax, bot = v10 + (v11 - v10) * ax;
-            lf::stg<NT>(dst + c * hw, pack_value<NORM>(top + (bot - top) * ay, nm[c], nd[c]));
+            lf::stg<NT>(dst + c * hw, pack_value<NORM>(lf::bilerp_u8(r0, r1, xs, c, ax, ay), nm[c], nd[c]));
         }
     }
 }

@@ -17,7 +17,8 @@ NHWC host array instead).  For data-parallel training pass `rank`/`world`: every
 the same permutation and takes the rank-strided slice of each global batch.  With
 `cache=True` (and device batches) the resized uint8 dataset lives in HBM — 150 KB per 224x224
 image, so even 100 k images are 15 GB of the 288 GB — and a batch is one gather kernel; there
-is no per-step decode, host stack or PCIe upload.  Device batches of `POOL_MIN` files or more
+is no per-step decode, host stack or PCIe upload.  Beyond the reference, `balanced=True` makes every epoch
+class-balanced by sampling (see `_balanced_indexes`).  Device batches of `POOL_MIN` files or more
 (and the filling of that cache) go through `dataio/device_decode.py`: codec worker processes
 Huffman-decode the JPEGs, the GPU finishes the decoding and resizes — Pillow's pixels, bit for bit.
 """
@@ -42,7 +43,7 @@ class ManifestSequence:
                  workers: int = 1,
                  transform: Optional[Callable[[Path, ManifestItem, int],
                                               Tuple[np.ndarray, np.ndarray]]] = None,
-                 as_numpy: bool = False, rank: int = 0, world: int = 1, **kwargs) -> None:
+                 as_numpy: bool = False, rank: int = 0, world: int = 1, balanced: bool = False, **kwargs) -> None:
         if limit is not None:
             items = items[:limit]
         self.items = items
@@ -65,7 +66,19 @@ class ManifestSequence:
         self._cache_dev = None  # uint8 device tensor [N,S,S,3] (cache=True, device batches)
         self._decoder = None    # DeviceDecoder (device batches of POOL_MIN files or more)
         self._ahead: Dict[int, tuple] = {}   # batch index -> (decoder handle, item indexes) started by prefetch()
-        if self.shuffle:
+        self.balanced = bool(balanced)
+        if self.balanced:
+            if label2idx is None:
+                raise ValueError("balanced=True needs label2idx")
+            # per class, in label2idx's order: its item ids in a shuffled order, and how many of them are used up
+            self._class_queues: List[List[int]] = [[] for _ in label2idx]
+            for i, it in enumerate(items):
+                self._class_queues[label2idx[it.label]].append(i)
+            self._class_queues = [q for q in self._class_queues if q]
+            self._class_used = [len(q) for q in self._class_queues]   # every queue is shuffled before its first use
+            self._class_turn = 0
+            self.indexes = self._balanced_indexes()
+        elif self.shuffle:
             self.rng.shuffle(self.indexes)
         if self.cache:
             self._build_cache()
@@ -73,8 +86,35 @@ class ManifestSequence:
     def __len__(self) -> int:
         return math.ceil(len(self.items) / self.batch_size)
 
+    def _balanced_indexes(self) -> List[int]:
+        """One epoch of item ids, len(items) of them, in which every class fills the same number of slots, give or
+        take 1 (the classes that get the extra slot take turns from epoch to epoch).  The slots' classes are shuffled,
+        then every slot takes the next item of its class's queue: a class hands out its items in a shuffled order
+        and all of them before any again, its queue being reshuffled when it runs out and carried over from epoch to
+        epoch.  Everything comes from `self.rng`, so the order depends on the seed alone and every rank builds the
+        same list; `shuffle` plays no part."""
+        k, total = len(self._class_queues), len(self.items)
+        if k == 0:
+            return []
+        slots: List[int] = []
+        for j in range(k):
+            slots += [(self._class_turn + j) % k] * (total // k + (1 if j < total % k else 0))
+        self._class_turn = (self._class_turn + total % k) % k
+        self.rng.shuffle(slots)
+        out: List[int] = []
+        for c in slots:
+            queue = self._class_queues[c]
+            if self._class_used[c] == len(queue):
+                self.rng.shuffle(queue)
+                self._class_used[c] = 0
+            out.append(queue[self._class_used[c]])
+            self._class_used[c] += 1
+        return out
+
     def on_epoch_end(self) -> None:
-        if self.shuffle:
+        if self.balanced:
+            self.indexes = self._balanced_indexes()
+        elif self.shuffle:
             self.rng.shuffle(self.indexes)
         if self._ahead:       # started for the old order
             self._ahead.clear()

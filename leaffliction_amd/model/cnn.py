@@ -143,6 +143,180 @@ def draw_mix_rows(rng: np.random.RandomState, n: int, h: int, w: int, mixup: flo
     return rows
 
 
+# ---- the online augmentation policy (lf_input_stage_policy_f32): a dict of ranges, drawn afresh for every image of
+# every step.  mirror / vmirror: probabilities; rotate, hue: largest angle in degrees; shear: largest shear factor, on
+# a fair coin of axis; skew: (lo, hi) perspective tilt as a fraction of the side, towards one of the four sides; crop:
+# (lo, hi) side of the window, as a fraction, that is zoomed to the full image from a uniformly drawn place;
+# brightness: largest shift on the [0, 1] scale; contrast (about 0.5), saturation: (lo, hi) factors; erase_prob,
+# erase_area: (lo, hi) fraction of the image, erase_aspect: (lo, hi) of a log-uniform height / width ratio (in units
+# of the image's own).  `strong` stands in for the offline Augmentation pass (rotate +-30, shear 0.2, skew, crop); the
+# colour and erase magnitudes are this project's own.
+POLICY_OFF = {"mirror": 0.0, "vmirror": 0.0, "rotate": 0.0, "shear": 0.0, "skew": (0.0, 0.0), "crop": (1.0, 1.0),
+              "brightness": 0.0, "contrast": (1.0, 1.0), "saturation": (1.0, 1.0), "hue": 0.0,
+              "erase_prob": 0.0, "erase_area": (0.02, 0.2), "erase_aspect": (0.5, 2.0)}
+POLICY_PRESETS = {
+    "light": dict(POLICY_OFF, mirror=0.5, rotate=18.0, contrast=(0.9, 1.1)),
+    "medium": dict(POLICY_OFF, mirror=0.5, rotate=24.0, shear=0.1, skew=(0.02, 0.08), crop=(0.9, 1.0),
+                   brightness=0.1, contrast=(0.8, 1.2), saturation=(0.8, 1.2), hue=5.0,
+                   erase_prob=0.25, erase_area=(0.02, 0.1)),
+    "strong": dict(POLICY_OFF, mirror=0.5, vmirror=0.5, rotate=30.0, shear=0.2, skew=(0.05, 0.15), crop=(0.8, 0.95),
+                   brightness=0.2, contrast=(0.7, 1.3), saturation=(0.6, 1.4), hue=10.0,
+                   erase_prob=0.5, erase_area=(0.02, 0.2)),
+}
+POLICY_IDENTITY_ROW = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0,
+                       1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0,
+                       0.0, 0.0, 0.0, 0.0)   # a pol24 row that leaves an image alone: the plain pack
+POLICY_LUMA = (0.299, 0.587, 0.114)
+POLICY_DEN_RANGE = (0.5, 2.0)   # where draw_policy_rows keeps the projective denominator over the image corners
+
+
+def resolve_policy(policy) -> Dict[str, Any]:
+    """A preset's name, or a dict of ranges laid over POLICY_OFF -> the full dict of ranges, validated: numbers and
+    (lo, hi) pairs, all finite, probabilities in [0, 1], lo <= hi, factors and areas positive, crop at most 1, skew
+    below 1/2 (the corner denominators are 1 +- skew before the other parts)."""
+    if isinstance(policy, str):
+        if policy not in POLICY_PRESETS:
+            raise ValueError(f"policy: unknown preset {policy!r} (one of {sorted(POLICY_PRESETS)})")
+        policy = POLICY_PRESETS[policy]
+    if not isinstance(policy, dict):
+        raise ValueError(f"policy: a preset name or a dict of ranges expected, got {type(policy).__name__}")
+    unknown = sorted(set(policy) - set(POLICY_OFF))
+    if unknown:
+        raise ValueError(f"policy: unknown entries {unknown} (known: {sorted(POLICY_OFF)})")
+    out: Dict[str, Any] = {}
+    for key, default in POLICY_OFF.items():
+        v = policy.get(key, default)
+        if isinstance(default, tuple):
+            try:
+                lo, hi = (float(t) for t in v)
+            except (TypeError, ValueError):
+                raise ValueError(f"policy: {key} must be a (lo, hi) pair, got {v!r}") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+                raise ValueError(f"policy: {key} must be finite with lo <= hi, got {v!r}")
+            out[key] = (lo, hi)
+        else:
+            out[key] = float(v)
+            if not (math.isfinite(out[key]) and out[key] >= 0.0):
+                raise ValueError(f"policy: {key} must be finite and >= 0, got {v!r}")
+    for key in ("mirror", "vmirror", "erase_prob"):
+        if out[key] > 1.0:
+            raise ValueError(f"policy: {key} is a probability, got {out[key]}")
+    for key in ("crop", "contrast", "erase_area", "erase_aspect"):
+        if out[key][0] <= 0.0:
+            raise ValueError(f"policy: {key} must be positive, got {out[key]}")
+    if out["saturation"][0] < 0.0 or out["skew"][0] < 0.0:
+        raise ValueError("policy: saturation and skew must be >= 0")
+    if out["crop"][1] > 1.0 or out["erase_area"][1] > 1.0 or out["skew"][1] >= 0.5:
+        raise ValueError("policy: crop and erase_area are fractions of at most 1, skew one below 1/2")
+    return out
+
+
+def policy_colour(hue_deg, saturation, contrast, brightness):
+    """(M [..,3,3], t [..,3]) in float64 of the colour parts composed in this order: the hue turn about the grey axis,
+    the saturation s I + (1 - s) 1 L^T with L = POLICY_LUMA, the contrast about 0.5, the brightness shift (scalars, or
+    arrays of one shape).  Hue 0, saturation 1, contrast 1 and brightness 0 give exactly I and 0."""
+    th = np.radians(np.asarray(hue_deg, np.float64))[..., None, None]
+    s = np.asarray(saturation, np.float64)[..., None, None]
+    c = np.asarray(contrast, np.float64)
+    cross = np.array([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]])
+    hue = np.cos(th) * np.eye(3) + ((1.0 - np.cos(th)) / 3.0) * np.ones((3, 3)) + (np.sin(th) / math.sqrt(3.0)) * cross
+    sat = s * np.eye(3) + (1.0 - s) * np.outer(np.ones(3), np.array(POLICY_LUMA))
+    m = c[..., None, None] * (sat @ hue)
+    t = (0.5 * (1.0 - c) + np.asarray(brightness, np.float64))[..., None] * np.ones(3)
+    return m, t
+
+
+def policy_corner_dens(rows, h: int, w: int) -> np.ndarray:
+    """g u + k v + 1 of inverse maps {a..k} (rows [..,>=8]) at the four image corners (u = +-(w-1)/2,
+    v = +-(h-1)/2), float64 [..,4]."""
+    rows = np.asarray(rows, np.float64)
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    corners = np.array([[-cx, -cy], [-cx, cy], [cx, -cy], [cx, cy]])
+    return rows[..., 6:7] * corners[:, 0] + rows[..., 7:8] * corners[:, 1] + 1.0
+
+
+def policy_inverse_maps(h: int, w: int, mirror, vmirror, angle, shear_x, shear_y, skew_x, skew_y, crop, crop_u,
+                        crop_v) -> np.ndarray:
+    """The eight floats {a,b,c,d,e,f,g,k} of n images (every argument an array [n]), float64 [n,8]: the parts
+    composed as forward maps (source -> output, centred pixel coordinates) in the order mirror, turn (radians), shear,
+    skew, crop; inverted; scaled to a last entry of 1.  skew_x / skew_y: the tilt as a fraction of the side (the
+    forward denominator is 1 +- skew at the edges of that axis); crop: the window's side as a fraction, (crop_u,
+    crop_v) in [-1, 1] its place.  While the denominator of an image's f32 row over the four corners leaves
+    POLICY_DEN_RANGE (or its inverse has no positive last entry) its skew is halved; after 32 halvings it is dropped."""
+    n = len(angle)
+    cx, cy = max((w - 1) / 2.0, 0.5), max((h - 1) / 2.0, 0.5)
+    eye = np.broadcast_to(np.eye(3), (n, 3, 3))
+    flip, turn, shear, zoom = (eye.copy() for _ in range(4))
+    flip[:, 0, 0] = np.where(mirror, -1.0, 1.0)
+    flip[:, 1, 1] = np.where(vmirror, -1.0, 1.0)
+    turn[:, 0, 0] = turn[:, 1, 1] = np.cos(angle)
+    turn[:, 1, 0] = np.sin(angle)
+    turn[:, 0, 1] = -turn[:, 1, 0]
+    shear[:, 0, 1], shear[:, 1, 0] = shear_x, shear_y
+    zoom[:, 0, 0] = zoom[:, 1, 1] = 1.0 / crop
+    zoom[:, 0, 2] = -(crop_u * (1.0 - crop) * w / 2.0) / crop
+    zoom[:, 1, 2] = -(crop_v * (1.0 - crop) * h / 2.0) / crop
+    affine = shear @ turn @ flip
+    scale = np.ones(n)
+    out = np.empty((n, 8))
+    todo = np.arange(n)
+    for halving in range(33):
+        if halving == 32:
+            scale[todo] = 0.0       # an affine map: its last entry is 1 and its denominator too
+        skew = eye[todo].copy()
+        skew[:, 2, 0], skew[:, 2, 1] = scale[todo] * skew_x[todo] / cx, scale[todo] * skew_y[todo] / cy
+        inv = np.linalg.inv(zoom[todo] @ skew @ affine[todo])
+        last = inv[:, 2, 2]
+        ok = last > 0.0
+        rows = (inv / np.where(ok, last, 1.0)[:, None, None]).reshape(-1, 9)[:, :8]
+        dens = policy_corner_dens(rows.astype(np.float32), h, w)
+        ok &= (POLICY_DEN_RANGE[0] <= dens.min(axis=1)) & (dens.max(axis=1) <= POLICY_DEN_RANGE[1])
+        out[todo[ok]] = rows[ok]
+        todo = todo[~ok]
+        if todo.size == 0 or halving == 32:
+            break
+        scale[todo] *= 0.5
+    return out
+
+
+POLICY_DRAWS = 19   # uniforms per image, see draw_policy_rows
+
+
+def draw_policy_rows(rng: np.random.RandomState, n: int, h: int, w: int, policy) -> np.ndarray:
+    """The augmentation-policy rows of one step, f32 [n, 24] = {a,b,c,d,e,f,g,k, M (3x3), t (3), y0,y1,x0,x1} (the
+    rule is stated at lf_input_stage_policy_f32 in include/leafhip.h), from a policy (a preset's name or a dict of
+    ranges, resolve_policy).  Geometry: policy_inverse_maps; colour: policy_colour; the erase box has fractional
+    edges, its area drawn from erase_area and its aspect log-uniformly from erase_aspect, clipped to the image and
+    placed uniformly; no erase is the empty box {0,0,0,0}.  Everything is float64 until the final cast.
+    Taken from `rng`: one block of POLICY_DRAWS x n uniforms, whatever the policy holds, row j of it for: 0 mirror,
+    1 vertical mirror, 2 angle, 3 shear axis, 4 shear, 5 skew side, 6 skew size, 7 crop size, 8 / 9 crop place (x, y),
+    10 brightness, 11 contrast, 12 saturation, 13 hue, 14 erase at all, 15 erase area, 16 erase aspect, 17 / 18 erase
+    place (y, x).  So the count depends on n only."""
+    pol = resolve_policy(policy)
+    u = rng.uniform(size=(POLICY_DRAWS, n))
+    span = lambda r, t: r[0] + (r[1] - r[0]) * t          # noqa: E731
+    sym = lambda t: 2.0 * t - 1.0                         # noqa: E731
+    shear, on_x = pol["shear"] * sym(u[4]), u[3] < 0.5
+    skew = span(pol["skew"], u[6])
+    side = np.minimum((u[5] * 4.0).astype(np.int64), 3)   # +x, -x, +y, -y
+    geo = policy_inverse_maps(
+        h, w, mirror=u[0] < pol["mirror"], vmirror=u[1] < pol["vmirror"],
+        angle=math.radians(pol["rotate"]) * sym(u[2]),
+        shear_x=np.where(on_x, shear, 0.0), shear_y=np.where(on_x, 0.0, shear),
+        skew_x=np.choose(side, [skew, -skew, 0.0 * skew, 0.0 * skew]),
+        skew_y=np.choose(side, [0.0 * skew, 0.0 * skew, skew, -skew]),
+        crop=span(pol["crop"], u[7]), crop_u=sym(u[8]), crop_v=sym(u[9]))
+    m, t = policy_colour(pol["hue"] * sym(u[13]), span(pol["saturation"], u[12]), span(pol["contrast"], u[11]),
+                         pol["brightness"] * sym(u[10]))
+    area = span(pol["erase_area"], u[15])
+    aspect = np.exp(span(tuple(math.log(v) for v in pol["erase_aspect"]), u[16]))
+    on = (u[14] < pol["erase_prob"]).astype(np.float64)   # an image without erase: the empty box {0,0,0,0}
+    eh, ew = np.minimum(h * np.sqrt(area * aspect), h) * on, np.minimum(w * np.sqrt(area / aspect), w) * on
+    y0, x0 = u[17] * (h - eh) * on, u[18] * (w - ew) * on
+    box = np.stack([y0, y0 + eh, x0, x0 + ew], 1)
+    return np.concatenate([geo, m.reshape(n, 9), t, box], 1).astype(np.float32)
+
+
 class LeafCNN:
     name = "leaf_cnn"
     _mut = 0                            # see __init__ (class-level defaults: subclasses that skip it still step)
@@ -150,6 +324,7 @@ class LeafCNN:
     last_targets: Optional[torch.Tensor] = None   # train_step with mixing on: the mixed targets the step trained on
     last_sample_weights: Optional[torch.Tensor] = None   # train_step with a "weighted" loss: s of every sample
     _cw_dev: Optional[torch.Tensor] = None   # the compiled class weights: one fixed device buffer [C]
+    _policy: Optional[Tuple[Any, Dict[str, Any]]] = None   # the compiled "policy" entry and its resolved ranges
     _infer_cache: Dict[str, Any] = {}
 
     def __init__(self, *, num_classes: int, img_size: int = 224, use_norm: bool = True,
@@ -190,6 +365,7 @@ class LeafCNN:
         self.gen = torch.Generator(device="cpu").manual_seed(int(seed))
         self.np_rng = np.random.RandomState(int(seed) & 0x7FFFFFFF)
         self.mix_rng = np.random.RandomState(self._mix_seed(seed))
+        self.pol_rng = np.random.RandomState(self._policy_seed(seed))
         from ..utils.system_info import cap_torch_threads
         cap_torch_threads()   # the per-step host draws are small CPU tensor ops: see there
 
@@ -317,18 +493,25 @@ class LeafCNN:
         mixup, cutmix, prob = self._mix_setting()
         return draw_mix_rows(self.mix_rng, n, h, w, mixup, cutmix, prob)
 
-    def _step_random_views(self, n: int, augment: bool, mix: bool) -> Dict[str, Tuple[int, int]]:
+    def _host_policy(self, n: int, h: int, w: int) -> np.ndarray:
+        """This step's pol24 rows (draw_policy_rows at the compiled policy) from the policy generator."""
+        return draw_policy_rows(self.pol_rng, n, h, w, self._policy_setting())
+
+    def _step_random_views(self, n: int, augment: bool, mix: bool, pol: bool = False) -> Dict[str, Tuple[int, int]]:
         """name -> shape of the per-step random tensors, in their order in the staging buffer: "drop<i>" per stage,
-        "top", "aug", "mix" — each only when the model (or the step) has it."""
+        "top", "aug", "mix", "pol" — each only when the model (or the step) has it.  The policy rows stand in place
+        of the aug rows: a step with `pol` has no "aug"."""
         shapes: Dict[str, Tuple[int, int]] = {}
         if self.drop_block > 0:
             shapes.update({f"drop{i}": (n, f) for i, f in enumerate(self.widths)})
         if self.drop_top > 0:
             shapes["top"] = (n, self.widths[-1])
-        if augment:
+        if augment and not pol:
             shapes["aug"] = (n, 4)
         if mix:
             shapes["mix"] = (n, 8)
+        if pol:
+            shapes["pol"] = (n, 24)
         return shapes
 
     @staticmethod
@@ -339,25 +522,32 @@ class LeafCNN:
             off += a * b
         return out
 
-    def _fill_step_randoms(self, hv: Dict[str, torch.Tensor], n: int, mix_hw: Optional[Tuple[int, int]]) -> None:
+    def _fill_step_randoms(self, hv: Dict[str, torch.Tensor], n: int, mix_hw: Optional[Tuple[int, int]],
+                           pol_hw: Optional[Tuple[int, int]] = None) -> None:
         """This step's draws into the host views `hv` (_named_views of _step_random_views): dropout from `gen`,
-        augmentation from `np_rng`, the mix rows from `mix_rng`.  Needs no device."""
+        augmentation from `np_rng`, the mix rows from `mix_rng`, the policy rows from `pol_rng`.  Needs no device."""
         self._host_dropout(n, [v for k, v in hv.items() if k.startswith("drop") or k == "top"])
         if "aug" in hv:
             hv["aug"].copy_(torch.from_numpy(self._host_augmentation(n)))
         if "mix" in hv:
             hv["mix"].copy_(torch.from_numpy(self._host_mix(n, *mix_hw)))
+        if "pol" in hv:
+            hv["pol"].copy_(torch.from_numpy(self._host_policy(n, *pol_hw)))
 
-    def draw_step_randoms(self, n: int, augment: bool, mix_hw: Optional[Tuple[int, int]] = None):
+    def draw_step_randoms(self, n: int, augment: bool, mix_hw: Optional[Tuple[int, int]] = None,
+                          pol_hw: Optional[Tuple[int, int]] = None):
         """All per-step host draws (SpatialDropout2D / Dropout keep-scales, in-model
-        augmentation parameters, with mix_hw = (H, W) of the batch the Mixup / CutMix rows) through ONE pinned
+        augmentation parameters, with mix_hw = (H, W) of the batch the Mixup / CutMix rows, with pol_hw = (H, W) the
+        augmentation-policy rows in place of the augmentation parameters) through ONE pinned
         staging buffer and one asynchronous copy:
         pageable uploads would block the host until the stream drains, once per tensor.
-        Returns (drops, top_drop, aug4, mix8) as views of a persistent device buffer."""
-        shapes = self._step_random_views(n, augment, mix_hw is not None)
+        Returns (drops, top_drop, aug4, mix8, pol24) as views of a persistent device buffer."""
+        shapes = self._step_random_views(n, augment, mix_hw is not None, pol_hw is not None)
         if not shapes:
-            return None, None, None, None
+            return None, None, None, None, None
         skey = (n, augment) if mix_hw is None else (n, augment, "mix")
+        if pol_hw is not None:
+            skey += ("pol",)
         st = self._stage.get(skey)
         if st is None:
             total = sum(a * b for a, b in shapes.values())
@@ -370,12 +560,12 @@ class LeafCNN:
             ev.synchronize()  # the copy that last read this pinned slot has executed
         st["i"] = (st["i"] + 1) % len(st["ring"])
         st["used"] += 1
-        self._fill_step_randoms(self._named_views(host, shapes), n, mix_hw)
+        self._fill_step_randoms(self._named_views(host, shapes), n, mix_hw, pol_hw)
         st["dev"].copy_(host, non_blocking=True)
         ev.record()
         dv = self._named_views(st["dev"], shapes)
         drops = [dv[f"drop{i}"] for i in range(len(self.widths))] if self.drop_block > 0 else None
-        return drops, dv.get("top"), dv.get("aug"), dv.get("mix")
+        return drops, dv.get("top"), dv.get("aug"), dv.get("mix"), dv.get("pol")
 
     def _identity_aug(self, n: int) -> torch.Tensor:
         """aug4 rows that leave an image alone (no flip, angle 0, contrast 1), in a buffer that stays (the step's HIP
@@ -387,17 +577,27 @@ class LeafCNN:
         return t
 
     def _input(self, x, training: bool, aug4: Optional[torch.Tensor] = None,
-               mix8: Optional[torch.Tensor] = None) -> torch.Tensor:
+               mix8: Optional[torch.Tensor] = None, pol24: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Accepts uint8 [N,H,W,3] (host or device) or float32 [N,H,W,3] in [0,1] (the
         reference loader's format); returns normalised f32 NCHW on the device.  mix8 (f32 [N,8] on the device, with
         training): the Mixup / CutMix input stage, nn.input_stage_mix; a model without in-model augmentation mixes
-        the plain images (identity aug4 rows)."""
+        the plain images (identity aug4 rows).  pol24 (f32 [N,24] on the device, with training): the augmentation
+        policy's input stage, nn.input_stage_policy, in place of the flip / rotation / contrast stage, whether the
+        model was built with in-model augmentation or not; not together with mix8."""
         if isinstance(x, np.ndarray):
             x = torch.from_numpy(np.ascontiguousarray(x))
         x = x.to(self.device, non_blocking=True)
         n = x.shape[0]
         mean, denom = self._norm_consts()
         out = self._buf(n, "x0", (n, 3, x.shape[1], x.shape[2]))
+        if training and pol24 is not None:
+            if mix8 is not None:
+                raise ValueError(self._POLICY_WITH_MIX)
+            if x.dtype == torch.float32:
+                x = (x * 255.0).round().clamp_(0, 255).to(torch.uint8)
+            elif x.dtype != torch.uint8:
+                raise TypeError("model input must be uint8 or float32 [N,H,W,3]")
+            return nn.input_stage_policy(x.contiguous(), pol24, mean, denom, out=out)
         if training and mix8 is not None:
             if x.dtype == torch.float32:
                 x = (x * 255.0).round().clamp_(0, 255).to(torch.uint8)
@@ -907,6 +1107,8 @@ class LeafCNN:
         the targets it trains on, mixed ones included; the returned loss is that loss and `last_sample_weights` holds
         every sample's weight s = sum_j cw_j y_j (None otherwise).  It is refused together with a teacher: the
         distillation head has no weighted form.
+        With a compiled "policy" the step draws one augmentation-policy row per image and its input stage is
+        nn.input_stage_policy; allowed with a teacher, refused together with "mix".
         grad_sync(flat_g) is called between backward and the optimizer (data-parallel
         all-reduce); with global_n the local gradient is scaled by 1/global_n so that a SUM
         all-reduce yields the global-batch mean.  Returns (probs, per-sample loss) device
@@ -936,6 +1138,8 @@ class LeafCNN:
         if mixing and extra:
             raise ValueError("train_step: Mixup / CutMix with a teacher is not supported (the teacher would have to "
                              "see the mixed image, which exists only inside this model's input stage)")
+        if mixing and self._policy_setting() is not None:
+            raise ValueError("train_step: " + self._POLICY_WITH_MIX)
         self.last_targets = self._mixed_targets_buf(n, self.num_classes) if mixing else None
         weighted = self._weighted_setting() is not None and n > 0
         if weighted and extra:
@@ -982,7 +1186,9 @@ class LeafCNN:
         is part of the graph's key: the step with a teacher and the step without are two graphs.  The Mixup /
         CutMix rows are one more view of the staging buffer and the mix setting one more part of the key: a model
         compiled without mixing replays the graph it always did.  The "weighted" setting (class weights and gamma) is
-        a part of the key in the same way; the weights themselves sit in one fixed device buffer."""
+        a part of the key in the same way; the weights themselves sit in one fixed device buffer.  So is the
+        augmentation policy (its resolved ranges), whose rows are one more view of the staging buffer, in place of
+        the aug rows."""
         if self._graphs_on and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8:
             return self._forward_backward_graph(x, y_true, between, teacher_probs)
         return self._forward_backward_eager(x, y_true, between, teacher_probs)
@@ -999,6 +1205,10 @@ class LeafCNN:
             mix_hw = (int(x.shape[1]), int(x.shape[2]))
         if self._weighted_setting() is not None:
             key += (("weighted",) + self._weighted_setting(),)
+        pol_hw = None
+        if self._policy_setting() is not None:
+            key += (("policy",) + tuple(sorted(self._policy_setting().items())),)
+            pol_hw = (int(x.shape[1]), int(x.shape[2]))
         st = self._graphs.get(key)
         if st is None:
             st = self._graphs[key] = {"calls": 0, "graph": None}
@@ -1010,7 +1220,8 @@ class LeafCNN:
             st["graph"], st["calls"] = None, 2
         if st["graph"] is None and st["calls"] <= 2:
             return self._forward_backward_eager(x, y_true, between, teacher_probs)
-        drops, top, aug4, mix8 = self.draw_step_randoms(n, self.augment, mix_hw)  # fixed device views, fresh values
+        # fixed device views, fresh values
+        drops, top, aug4, mix8, pol24 = self.draw_step_randoms(n, self.augment, mix_hw, pol_hw)
         if st["graph"] is None:
             st["x"] = torch.empty_like(x)
             st["y"] = torch.empty_like(y_true)
@@ -1028,14 +1239,15 @@ class LeafCNN:
                 with torch.cuda.graph(g):
                     st["out"] = self._forward_backward_body(st["x"], st["y"], drops, top, aug4,
                                                             part=None if between is None else 0,
-                                                            teacher_probs=st["t"], mix8=mix8)
+                                                            teacher_probs=st["t"], mix8=mix8, pol24=pol24)
                 if g2 is not None:
                     with torch.cuda.graph(g2, pool=g.pool()):
                         self._forward_backward_body(st["x"], st["y"], drops, top, aug4, part=1)
             except Exception:
                 self._graphs_on = False   # capture is an optimisation: fall back to eager launches
                 torch.cuda.synchronize()
-                return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs, mix8)
+                return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs, mix8,
+                                                    pol24)
             st["graph"], st["graph2"] = g, g2
             st["ws_gen"] = nn.workspace_generation()
         else:
@@ -1051,28 +1263,32 @@ class LeafCNN:
 
     def _forward_backward_eager(self, x, y_true: torch.Tensor, between=None, teacher_probs=None):
         n = int(x.shape[0])
-        mix_hw = (int(x.shape[1]), int(x.shape[2])) if self._mix_setting() is not None else None
-        drops, top, aug4, mix8 = self.draw_step_randoms(n, self.augment, mix_hw)
-        return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs, mix8)
+        hw = (int(x.shape[1]), int(x.shape[2]))
+        mix_hw = hw if self._mix_setting() is not None else None
+        pol_hw = hw if self._policy_setting() is not None else None
+        drops, top, aug4, mix8, pol24 = self.draw_step_randoms(n, self.augment, mix_hw, pol_hw)
+        return self._forward_backward_split(x, y_true, drops, top, aug4, between, teacher_probs, mix8, pol24)
 
-    def _forward_backward_split(self, x, y_true, drops, top, aug4, between, teacher_probs=None, mix8=None):
+    def _forward_backward_split(self, x, y_true, drops, top, aug4, between, teacher_probs=None, mix8=None,
+                                pol24=None):
         if between is None:
-            return self._forward_backward_body(x, y_true, drops, top, aug4, teacher_probs=teacher_probs, mix8=mix8)
+            return self._forward_backward_body(x, y_true, drops, top, aug4, teacher_probs=teacher_probs, mix8=mix8,
+                                               pol24=pol24)
         out = self._forward_backward_body(x, y_true, drops, top, aug4, part=0, teacher_probs=teacher_probs,
-                                          mix8=mix8)
+                                          mix8=mix8, pol24=pol24)
         between()
         self._forward_backward_body(x, y_true, drops, top, aug4, part=1)
         return out
 
     def _forward_backward_body(self, x, y_true, drops, top, aug4, part: Optional[int] = None, teacher_probs=None,
-                               mix8=None):
+                               mix8=None, pol24=None):
         """part None: forward + the whole backward pass; 0: forward + backward part 0; 1: backward part 1.
         mix8: the step's Mixup / CutMix rows; the input stage blends the images and the head sees the targets blended
-        the same way (the buffer `last_targets` names)."""
+        the same way (the buffer `last_targets` names).  pol24: the step's augmentation-policy rows."""
         if part == 1:
             self.backward(1)
             return None
-        x0 = self._input(x, True, aug4, mix8)
+        x0 = self._input(x, True, aug4, mix8, pol24)
         if mix8 is not None:
             y_true = nn.mix_targets(y_true, mix8, out=self._mixed_targets_buf(*y_true.shape))
         if teacher_probs is None:
@@ -1101,6 +1317,13 @@ class LeafCNN:
         self.gen = torch.Generator(device="cpu").manual_seed(int(seed))
         self.np_rng = np.random.RandomState(int(seed) & 0x7FFFFFFF)
         self.mix_rng = np.random.RandomState(self._mix_seed(seed))
+        self.pol_rng = np.random.RandomState(self._policy_seed(seed))
+
+    @staticmethod
+    def _policy_seed(seed: int) -> int:
+        """The augmentation policy's draws have a generator of their own, as the Mixup / CutMix draws have (_mix_seed),
+        with another constant: the dropout stream is the same with the policy on and off."""
+        return (int(seed) ^ 0x504F4C59) & 0x7FFFFFFF
 
     @staticmethod
     def _mix_seed(seed: int) -> int:
@@ -1129,10 +1352,17 @@ class LeafCNN:
         g = 0 or 1 <= g <= 8): every training step minimises s * sum_j -y_j (1 - p_j)^g log p_j with the sample
         weight s = sum_j w_j y_j taken over the target as the step sees it (smoothed, mixed), divided by the batch
         size, not by the sum of the weights.  Off when the weights are None and g is 0; works together with "mix";
-        refused together with "distill"."""
+        refused together with "distill".
+        "policy": a preset's name ("light", "medium", "strong") or a dict of ranges (resolve_policy): every training
+        step draws one pol24 row per image (draw_policy_rows) and its input stage is nn.input_stage_policy in place
+        of the flip / rotation / contrast stage, for a model built with augment=False too.  Allowed with a teacher
+        (which keeps seeing the plain image); refused together with "mix"."""
         self._compiled = {"optimizer": optimizer or {}, "loss": loss or {}, "metrics": metrics or []}
+        self._policy = None
         self._distill_setting()
-        self._mix_setting()
+        mix, policy = self._mix_setting(), self._policy_setting()
+        if mix is not None and policy is not None:
+            raise ValueError("compile: " + self._POLICY_WITH_MIX)
         weighted = self._weighted_setting()
         if weighted is not None:
             if self._distill_setting() is not None:
@@ -1169,6 +1399,18 @@ class LeafCNN:
         if not 0.0 <= prob <= 1.0:
             raise ValueError(f"mix: prob must lie in [0, 1], got {prob}")
         return (mixup, cutmix, prob) if (mixup > 0 or cutmix > 0) else None
+
+    _POLICY_WITH_MIX = ('an augmentation "policy" together with "mix" (Mixup / CutMix) is not supported: the mixing '
+                        'input stage samples flip / rotation / contrast views, not policy rows')
+
+    def _policy_setting(self) -> Optional[Dict[str, Any]]:
+        """The resolved ranges (resolve_policy) of the compiled loss' "policy"; None when it has none."""
+        spec = self._compiled.get("loss", {}).get("policy")
+        if spec is None:
+            return None
+        if self._policy is None or self._policy[0] is not spec:
+            self._policy = (spec, resolve_policy(spec))
+        return self._policy[1]
 
     _WEIGHTED_WITH_TEACHER = ('a "weighted" loss (class weights / focal gamma) with a teacher is not supported: the '
                               'distillation head has no weighted form')

@@ -629,6 +629,29 @@ def input_stage_mix(x_u8: torch.Tensor, aug4: torch.Tensor, mix8: torch.Tensor, 
     return out
 
 
+def input_stage_policy(x_u8: torch.Tensor, pol24: torch.Tensor, mean=None, denom=None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The augmentation policy's input stage (lf_input_stage_policy_f32): u8 [N,H,W,3] -> f32 [N,3,H,W], every image
+    warped, recoloured and erased by its own row pol24 [N,24] = {a,b,c,d,e,f,g,k, M (3x3), t (3), y0,y1,x0,x1} (the
+    rule: include/leafhip.h), then normalised with mean / denom as pack_hwc_u8_to_nchw_f32 does it."""
+    if x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3 or not x_u8.is_contiguous() \
+            or not x_u8.is_cuda:
+        raise ValueError("input_stage_policy.x: a contiguous uint8 [N,H,W,3] tensor on the GPU expected")
+    n, h, w, _c = x_u8.shape
+    if (mean is None) != (denom is None):
+        raise ValueError("input_stage_policy: mean and denom go together")
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=_F32, device=x_u8.device)
+    _mix_checks("input_stage_policy", x_u8, {"pol": (pol24, (n, 24)), "out": (out, (n, 3, h, w))})
+    m = d = None
+    if mean is not None:
+        m = (_lib.c_float * 3)(*[float(v) for v in mean])
+        d = (_lib.c_float * 3)(*[float(v) for v in denom])
+    _lib.call("lf_input_stage_policy_f32", x_u8.data_ptr(), out.data_ptr(), n, h, w, pol24.data_ptr(), m, d,
+              _stream())
+    return out
+
+
 def mix_targets(y: torch.Tensor, mix8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Mixed targets out[i] = y[p] + t (y[i] - y[p]) with p, t from mix8 [N,8] (lf_mix_targets_f32), out of place."""
     if y.dim() != 2 or not y.is_cuda:

@@ -50,7 +50,8 @@ def build_loss(cfg: Dict) -> Dict[str, Any]:
     """CategoricalCrossentropy(label_smoothing) or sparse CCE (utils.py:30-35); a cfg that carries
     "distill": {"alpha", "temperature"} (train --teacher) hands it on to LeafCNN.compile, and so does one that
     carries "mix": {"mixup", "cutmix", "prob"} (train --mixup / --cutmix) or "weighted": {"class_weights", "gamma"}
-    (train --class-weights / --focal-gamma)."""
+    (train --class-weights / --focal-gamma) or "policy": a preset's name or a dict of ranges (train
+    --augment-policy)."""
     ls = float(cfg.get("label_smoothing", 0.0) or 0.0)
     loss: Dict[str, Any] = {"name": "categorical_crossentropy" if ls > 0 else "sparse_categorical_crossentropy",
                             "label_smoothing": ls}
@@ -64,6 +65,8 @@ def build_loss(cfg: Dict) -> Dict[str, Any]:
         cw = cfg["weighted"].get("class_weights")
         loss["weighted"] = {"class_weights": None if cw is None else [float(v) for v in cw],
                             "gamma": float(cfg["weighted"].get("gamma", 0.0))}
+    if cfg.get("policy") is not None:
+        loss["policy"] = cfg["policy"] if isinstance(cfg["policy"], str) else dict(cfg["policy"])
     return loss
 
 
