@@ -1268,6 +1268,50 @@ int lf_calib_stats(const float* probs, const int32_t* labels, int n, int c, cons
 int lf_calib_apply_f32(const float* probs, double beta, float* out, float* conf, int32_t* top, int n, int c,
                        lf_stream_t stream);
 
+/* ---- Conformal: prediction sets with guaranteed coverage (split conformal prediction) ---- */
+/* Inputs: probability rows p f32 [n][c], n > 0, 1 <= c <= 256; u f32 [n] in [0, 1], one value per row, or null: 1.0
+ * for every row.  Anything else (a null buffer, an unknown kind, lambda not finite or < 0, kreg < 0, stats without
+ * labels) returns -1 with a message before any launch.
+ *
+ * Order.  Within a row class k stands before class j iff p_k > p_j, or p_k == p_j and k < j: a total order on the
+ * f32 values; a NaN reads as 0.  r(j) is the number of classes before j (the rank; 0: the prediction, np.argmax).
+ * Cumulative mass.  m(j) is the float64 sum of the probabilities of the classes before j, added in rank order from
+ * 0.0: m at rank r + 1 = m at rank r + (double)p at rank r.  Every float64 operation is rounded on its own (no
+ * contraction), in exactly this order.
+ * Score of class j, in float64:
+ *   LF_CONFORMAL_LAC   1.0 - (double)p_j                              (u is not read)
+ *   LF_CONFORMAL_APS   m(j) + (double)u * (double)p_j                 (the product of two f32 is exact in f64)
+ *   LF_CONFORMAL_RAPS  the APS score + lambda * (double)max(0, r(j) + 1 - kreg), the penalty added last;
+ *                      lambda >= 0 finite, kreg >= 0.  lambda and kreg are not read by the other kinds.
+ * Set.  Class j is a member iff score(j) <= qhat[j] (false when either is a NaN; true for every j at +inf).  With
+ * force_top the class of rank 0 is always a member.  A marginal threshold is the same value c times.
+ * Threshold (on the host: predict/conformal.py).  From n calibration scores k = ceil((n + 1)(1 - alpha)), computed
+ * exactly (alpha is the fraction its decimal string names, 0 < alpha < 1); qhat is the k-th smallest score, +inf
+ * when k > n.  Marginal: one qhat from the scores of the rows' labels.  Class-conditional: qhat[j] from the rows whose
+ * label is j; a class with k_j > n_j gets +inf.
+ * Because the arithmetic and its order are fixed, the kernel equals a numpy float64 transcription of these lines in
+ * every bit (tests/conformal_ref.py), and `<=` stays exact when qhat is itself one of the scores.
+ *
+ * lf_conformal_scores: labels i32 [n] -> score f64 [n] = the score of the row's label, rank i32 [n] = r(label).  A
+ * row whose label lies outside [0, c) gets (NaN, -1).
+ * lf_conformal_sets: qhat f64 [c] on the device (8-byte aligned) -> member u8 [n][c] (1 or 0), size i32 [n] = the
+ * members of the row.  labels i32 [n] or null; with labels, stats i64 [4 + (c + 1) + 3 c] or null (8-byte aligned,
+ * cleared by the call), over the rows whose label lies in [0, c) -- the others count in `skipped` alone, their
+ * member and size are written all the same:
+ *   {rows, skipped, covered, size_sum}      covered: the label is a member; size_sum: the sum of size
+ *   size_hist[s], s = 0 .. c                rows with size s
+ *   per class k: {rows, covered, size_sum}  the same over the rows whose label is k
+ * One wave per row, the ranks and sums across the wave; a launch runs at most 8,192 waves, a wave then takes the
+ * rows w, w + waves, ...  No float goes through an atomic; the counters are added with integer ones. */
+#define LF_CONFORMAL_LAC 0
+#define LF_CONFORMAL_APS 1
+#define LF_CONFORMAL_RAPS 2
+int lf_conformal_scores(const float* probs, const int32_t* labels, const float* u, int n, int c, int kind,
+                        double lambda, int kreg, double* score, int32_t* rank, lf_stream_t stream);
+int lf_conformal_sets(const float* probs, const float* u, const double* qhat, int n, int c, int kind, double lambda,
+                      int kreg, int force_top, const int32_t* labels, uint8_t* member, int32_t* size,
+                      long long* stats, lf_stream_t stream);
+
 /* ---- Novelty score: Mahalanobis distance of the pooled features to the nearest class ---- */
 /* feat f32 [n][d] are rows of the network's pooled feature vector (GlobalAveragePooling's output).  Both calls: n > 0,
  * d a multiple of 16 with 16 <= d <= 256, 1 <= c <= 4096; anything else returns -1 with a message before any launch.

@@ -160,6 +160,8 @@ SIGNATURES = {
     "lf_calib_stats_workspace": [c_int, c_int, c_int],
     "lf_calib_stats": [P, P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_size_t, P],
     "lf_calib_apply_f32": [P, c_double, P, P, P, c_int, c_int, P],
+    "lf_conformal_scores": [P, P, P, c_int, c_int, c_int, c_double, c_int, P, P, P],
+    "lf_conformal_sets": [P, P, P, c_int, c_int, c_int, c_double, c_int, c_int, P, P, P, P, P],
     "lf_feat_moments": [P, P, c_int, c_int, c_int, P, P, P, P, P],
     "lf_maha_score_f32": [P, P, P, P, c_int, c_int, c_int, P, P, P, P],
     "lf_knn_query_tile": [],

@@ -63,19 +63,16 @@ def select_files(manifest: Path, split: str):
     return paths, names
 
 
-def calibrate(predictor, paths, names, bins: int = 15, manifest=None, split=None):
-    """Fit on the predictor's probabilities of `paths` (labels `names`) and write calibration.json beside its model;
-    returns what was written."""
+def labelled_rows(predictor, paths, names):
+    """(probs f32 [m,C], targets int32 [m]) of the files that could be read: the predictor's probability rows and the
+    index of each file's label name among the model's, -1 for a name the model does not know (the kernels skip such
+    a row).  One warning per file left out or unknown."""
     import numpy as np
-    import torch
-
-    from ..predict import calibration
-    labels = predictor.model_loader.labels
-    index = {name: j for j, name in enumerate(labels)}
+    index = {name: j for j, name in enumerate(predictor.model_loader.labels)}
     probs, kept = predictor.predict_probabilities(paths)
     for k in sorted(set(range(len(paths))) - set(kept)):
         logger.warning("Skipping %s: could not be read", paths[k])
-    targets = np.full(len(kept), -1, np.int32)   # -1: a label the model does not know; the kernel counts it as skipped
+    targets = np.full(len(kept), -1, np.int32)
     for j, k in enumerate(kept):
         if names[k] in index:
             targets[j] = index[names[k]]
@@ -83,6 +80,17 @@ def calibrate(predictor, paths, names, bins: int = 15, manifest=None, split=None
             logger.warning("Skipping %s: the model does not know the label %r", paths[k], names[k])
     if not (targets >= 0).any():
         raise ValueError("No image with a label the model knows could be read")
+    return probs, targets
+
+
+def calibrate(predictor, paths, names, bins: int = 15, manifest=None, split=None):
+    """Fit on the predictor's probabilities of `paths` (labels `names`) and write calibration.json beside its model;
+    returns what was written."""
+    import torch
+
+    from ..predict import calibration
+    labels = predictor.model_loader.labels
+    probs, targets = labelled_rows(predictor, paths, names)
     dev = torch.device("cuda", torch.cuda.current_device())
     return calibration.fit_and_save(predictor.learnings_dir, torch.from_numpy(probs).to(dev),
                                     torch.from_numpy(targets).to(dev), labels, bins=bins, manifest=manifest,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """`predict.py image_or_dir [-learnings DIR] [-out DIR] [-json P] [-batch] [--cam] [--montage] [--tta PRESET]
-[--calibrated] [--novelty] [--neighbours K] [--evaluate ...]`.
+[--calibrated] [--novelty] [--neighbours K] [--conformal [ALPHA]] [--evaluate ...]`.
 
 Flags, JSON schema (`batch_results` + `summary`), the sampled accuracy gate and the exit
 codes (1 on error, 2 when the gate is never reached) follow srcs/cli/predict.py:17-87,
@@ -26,6 +26,12 @@ gains `novelty_score` (squared Mahalanobis distance of the pooled features to th
 gains `neighbours` (the K pictures of `<learnings>/neighbours.npz` nearest in the model's feature space, as {file,
 label, sq_distance}, nearest first), `knn_label` (their vote), `knn_agreement` and `kth_sq_distance`; the index is
 built by cli.neighbours (exit status 1 without it); `summary` gains `neighbours`.  No prediction or probability changes.
+`--conformal [ALPHA]` (not in the reference; default 0.1), in every mode but --cam, also together with --calibrated,
+--tta, --novelty and --neighbours: every result gains `prediction_set` (the classes that cannot be ruled out, most
+probable first), `set_size` and `conformal_alpha`, from `<learnings>/conformal.json` and `conformal.npz` (fitted by
+cli.conformal; exit status 1 without them, and with a --tta or --calibrated setting other than the fitted one: the
+guarantee holds for the fitted pipeline alone); `summary` gains `conformal` = {alpha, score, mean_set_size,
+singletons, empty}, with --evaluate also the coverage on the evaluated files.  No prediction or probability changes.
 """
 from __future__ import annotations
 
@@ -76,6 +82,9 @@ def parse_args(argv=None):
     p.add_argument("--neighbours", type=int, default=None, metavar="K",
                    help="also name the K index pictures each picture most resembles "
                         "(<learnings>/neighbours.npz, built by cli.neighbours)")
+    p.add_argument("--conformal", nargs="?", const="0.1", default=None, metavar="ALPHA",
+                   help="also name the classes that cannot be ruled out at miscoverage ALPHA (default 0.1; "
+                        "<learnings>/conformal.json, fitted by cli.conformal)")
     return p.parse_args(argv)
 
 
@@ -102,6 +111,11 @@ def validate_inputs(args):
                              "point)")
         if args.cam:
             raise ValueError("--neighbours cannot be combined with --cam")
+    if args.conformal is not None:
+        from ..predict.conformal import alpha_fraction
+        alpha_fraction(args.conformal)
+        if args.cam:
+            raise ValueError("--conformal cannot be combined with --cam")
     if args.cam and not 0.0 <= args.cam_alpha <= 1.0:
         raise ValueError(f"--cam-alpha must lie in [0, 1], got {args.cam_alpha}")
     if not image_path.exists():
@@ -124,6 +138,9 @@ def validate_inputs(args):
     if args.neighbours is not None:
         from ..predict.neighbours import require_files
         require_files(learnings_dir)
+    if args.conformal is not None:
+        from ..predict.conformal import require_files as require_conformal
+        require_conformal(learnings_dir)
     if args.evaluate:
         if not args.batch_mode:
             raise ValueError("--evaluate requires --batch-mode")
@@ -178,13 +195,33 @@ def neighbours_summary(predictor, results):
             "agrees_with_prediction": agree / len(results) if results else None}
 
 
+CONFORMAL_KEYS = ("prediction_set", "set_size", "conformal_alpha")
+
+
+def conformal_summary(predictor, results, truths=None):
+    """`summary.conformal` of a predictor that reports prediction sets, None of any other.  truths (the results'
+    labels, where they are known): also the share of the sets that hold theirs."""
+    data = getattr(predictor, "conformal_data", None)
+    if data is None:
+        return None
+    n = len(results)
+    out = {"alpha": float(predictor.conformal), "score": data["score"],
+           "mean_set_size": sum(r["set_size"] for r in results) / n if n else None,
+           "singletons": sum(1 for r in results if r["set_size"] == 1) / n if n else None,
+           "empty": sum(1 for r in results if r["set_size"] == 0) / n if n else None}
+    if truths is not None:
+        out["coverage"] = sum(1 for r, t in zip(results, truths) if t in r["prediction_set"]) / n if n else None
+    return out
+
+
 def save_batch_results_json(results, processing_time, output_path, tta=None, calibration=None, novelty=None,
-                            neighbours=None):
+                            neighbours=None, conformal=None):
     """tta (the preset, when the predictions are test-time-augmented ones): `summary` also says so and gives the mean
     of the results' view agreement.  calibration (calibration_summary, when the confidences are calibrated ones):
     `summary.calibration`.  novelty (novelty_summary, when the results carry a novelty score): `summary.novelty`, and
     every entry of `batch_results` keeps its NOVELTY_KEYS.  neighbours (neighbours_summary): `summary.neighbours`, and
-    every entry keeps its NEIGHBOUR_KEYS."""
+    every entry keeps its NEIGHBOUR_KEYS.  conformal (conformal_summary): `summary.conformal`, and every entry keeps its
+    CONFORMAL_KEYS."""
     output_path = Path(output_path)
     if not output_path.is_absolute() and not str(output_path).startswith("artifacts/"):
         output_path = Path("artifacts/prediction_output") / output_path.name
@@ -193,7 +230,8 @@ def save_batch_results_json(results, processing_time, output_path, tta=None, cal
                                "confidence": r["confidence"],
                                "all_probabilities": r["all_probabilities"],
                                **({k: r[k] for k in NOVELTY_KEYS} if novelty is not None else {}),
-                               **({k: r[k] for k in NEIGHBOUR_KEYS} if neighbours is not None else {})}
+                               **({k: r[k] for k in NEIGHBOUR_KEYS} if neighbours is not None else {}),
+                               **({k: r[k] for k in CONFORMAL_KEYS} if conformal is not None else {})}
                               for r in results],
             "summary": create_batch_summary(results, processing_time)}
     if tta is not None:
@@ -206,6 +244,8 @@ def save_batch_results_json(results, processing_time, output_path, tta=None, cal
         data["summary"]["novelty"] = novelty
     if neighbours is not None:
         data["summary"]["neighbours"] = neighbours
+    if conformal is not None:
+        data["summary"]["conformal"] = conformal
     output_path.parent.mkdir(parents=True, exist_ok=True)
     with open(output_path, "w") as f:
         json.dump(data, f, indent=2)
@@ -329,7 +369,8 @@ def run_sampling_enforced_batch(predictor, image_dir: Path, manifest_path: Path,
                 saved = save_batch_results_json(results, proc, json_output, tta=getattr(predictor, "tta", None),
                                                 calibration=calibration_summary(predictor),
                                                 novelty=novelty_summary(predictor, results),
-                                                neighbours=neighbours_summary(predictor, results))
+                                                neighbours=neighbours_summary(predictor, results),
+                                                conformal=conformal_summary(predictor, results, truths=labels))
                 logger.info("Results saved to: %s", saved)
             try:
                 PredictionEvaluator(predictor).evaluate_predictions(
@@ -351,7 +392,7 @@ def main(argv=None) -> None:
         image_path, learnings_dir = validate_inputs(args)
         rk = init_from_env()   # replicas under torch.distributed.run; one process otherwise
         predictor = Predictor(learnings_dir, tta=args.tta, calibrated=args.calibrated, novelty=args.novelty,
-                              neighbours=args.neighbours)
+                              neighbours=args.neighbours, conformal=args.conformal)
         predictor.load()
         if args.batch_mode:
             if args.evaluate:
@@ -387,7 +428,8 @@ def main(argv=None) -> None:
             out = save_batch_results_json(results, proc, args.json_output, tta=args.tta,
                                           calibration=calibration_summary(predictor),
                                           novelty=novelty_summary(predictor, results),
-                                          neighbours=neighbours_summary(predictor, results))
+                                          neighbours=neighbours_summary(predictor, results),
+                                          conformal=conformal_summary(predictor, results))
             logger.info("Results saved to: %s", out)
             for k, v in create_batch_summary(results, proc).items():
                 logger.info("  %s: %s", k, v)
@@ -412,6 +454,9 @@ def main(argv=None) -> None:
                             f"{len(r['neighbours'])}; k-th squared distance {r['kth_sq_distance']:.4g})")
                 for nb in r["neighbours"]:
                     logger.info(f"    {nb['sq_distance']:.4g}  {nb['label']}  {nb['file']}")
+            if args.conformal is not None:
+                logger.info(f"Cannot be ruled out at alpha {r['conformal_alpha']:g}: "
+                            f"{', '.join(r['prediction_set']) or 'nothing (an empty set)'}")
             if args.tta:
                 logger.info(f"Views agreeing ({args.tta}): {r['view_agreement']:.0%}")
             for name, prob in sorted(r["all_probabilities"].items(), key=lambda x: -x[1])[:3]:

@@ -812,6 +812,88 @@ def calib_apply(probs: torch.Tensor, beta, out: Optional[torch.Tensor] = None
     return out, conf, top
 
 
+CONFORMAL_MAX_CLASSES = 256
+CONFORMAL_KINDS = ("lac", "aps", "raps")   # LF_CONFORMAL_LAC, _APS, _RAPS
+CONFORMAL_WAVES = 8192     # the most waves a conformal launch runs: beyond that many rows a wave takes several
+CONFORMAL_GLOBALS = ("rows", "skipped", "covered", "size_sum")
+
+
+def _conformal_args(who: str, probs: torch.Tensor, u, kind, lam, kreg) -> Tuple[int, int, int, float, int]:
+    """The checks both conformal wrappers make -> (n, c, kind number, lambda, kreg)."""
+    import math
+    _chk(probs, _F32, f"{who}.probs", 2)
+    n, c = probs.shape
+    if n == 0 or not 1 <= c <= CONFORMAL_MAX_CLASSES:
+        raise ValueError(f"{who}.probs: [N,C] with N > 0 and 1 <= C <= {CONFORMAL_MAX_CLASSES} expected, got "
+                         f"{tuple(probs.shape)}")
+    if u is not None:
+        _chk(u, _F32, f"{who}.u", 1)
+        if u.shape[0] != n or u.device != probs.device:
+            raise ValueError(f"{who}.u: expected [{n}] on {probs.device}, got {tuple(u.shape)} on {u.device}")
+    if kind not in CONFORMAL_KINDS:
+        raise ValueError(f"{who}: unknown score {kind!r}: one of {', '.join(CONFORMAL_KINDS)}")
+    lam, kreg = float(lam), int(kreg)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"{who}: lambda must be finite and >= 0, got {lam!r}")
+    if kreg < 0:
+        raise ValueError(f"{who}: kreg must be >= 0, got {kreg}")
+    return n, c, CONFORMAL_KINDS.index(kind), lam, kreg
+
+
+def _conformal_labels(who: str, labels: torch.Tensor, probs: torch.Tensor) -> None:
+    _chk(labels, torch.int32, f"{who}.labels", 1)
+    if labels.shape[0] != probs.shape[0] or labels.device != probs.device:
+        raise ValueError(f"{who}.labels: expected [{probs.shape[0]}] on {probs.device}, got {tuple(labels.shape)} on "
+                         f"{labels.device}")
+
+
+def conformal_scores(probs: torch.Tensor, labels: torch.Tensor, u: Optional[torch.Tensor] = None, kind: str = "aps",
+                     lam: float = 0.0, kreg: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The conformity score of every row's label (lf_conformal_scores; the rule: include/leafhip.h "Conformal"):
+    probs f32 [N,C], labels int32 [N] and u f32 [N] (None: 1.0 for every row) on the GPU -> (score f64 [N], rank
+    int32 [N] = the classes that stand before the label).  A label outside [0, C) gives (NaN, -1).  No sync."""
+    n, c, k, lam, kreg = _conformal_args("conformal_scores", probs, u, kind, lam, kreg)
+    _conformal_labels("conformal_scores", labels, probs)
+    score = torch.empty((n,), dtype=torch.float64, device=probs.device)
+    rank = torch.empty((n,), dtype=torch.int32, device=probs.device)
+    _lib.call("lf_conformal_scores", probs.data_ptr(), labels.data_ptr(), _ptr(u), n, c, k, _lib.c_double(lam), kreg,
+              score.data_ptr(), rank.data_ptr(), _stream())
+    return score, rank
+
+
+def conformal_sets(probs: torch.Tensor, qhat: torch.Tensor, u: Optional[torch.Tensor] = None, kind: str = "aps",
+                   lam: float = 0.0, kreg: int = 0, force_top: bool = True, labels: Optional[torch.Tensor] = None,
+                   stats: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[dict]]:
+    """The prediction sets at the thresholds qhat (lf_conformal_sets): probs f32 [N,C], qhat f64 [C] (one threshold
+    per class; a marginal one repeated), u f32 [N] or None and labels int32 [N] or None on the GPU -> (member uint8
+    [N,C], size int32 [N], stats).  With `stats` (needs labels; one device-to-host sync) the counters over the rows
+    whose label lies in [0, C) as host values: the ints rows, skipped, covered and size_sum, size_hist int64 [C+1],
+    and class_rows, class_covered, class_size_sum int64 [C]; None without."""
+    n, c, k, lam, kreg = _conformal_args("conformal_sets", probs, u, kind, lam, kreg)
+    _chk(qhat, torch.float64, "conformal_sets.qhat", 1)
+    if qhat.shape[0] != c or qhat.device != probs.device:
+        raise ValueError(f"conformal_sets.qhat: expected [{c}] on {probs.device}, got {tuple(qhat.shape)} on "
+                         f"{qhat.device}")
+    if labels is not None:
+        _conformal_labels("conformal_sets", labels, probs)
+    elif stats:
+        raise ValueError("conformal_sets: stats need labels")
+    member = torch.empty((n, c), dtype=torch.uint8, device=probs.device)
+    size = torch.empty((n,), dtype=torch.int32, device=probs.device)
+    g = len(CONFORMAL_GLOBALS)
+    counters = torch.empty((g + c + 1 + 3 * c,), dtype=torch.int64, device=probs.device) if stats else None
+    _lib.call("lf_conformal_sets", probs.data_ptr(), _ptr(u), qhat.data_ptr(), n, c, k, _lib.c_double(lam), kreg,
+              int(bool(force_top)), _ptr(labels), member.data_ptr(), size.data_ptr(), _ptr(counters), _stream())
+    if counters is None:
+        return member, size, None
+    h = counters.cpu().numpy()
+    per = h[g + c + 1:].reshape(c, 3)
+    out = {name: int(h[j]) for j, name in enumerate(CONFORMAL_GLOBALS)}
+    out.update(size_hist=h[g:g + c + 1].copy(), class_rows=per[:, 0].copy(), class_covered=per[:, 1].copy(),
+               class_size_sum=per[:, 2].copy())
+    return member, size, out
+
+
 NOVELTY_MAX_DIM = 256
 NOVELTY_DIM_STEP = 16
 NOVELTY_MAX_CLASSES = 4096

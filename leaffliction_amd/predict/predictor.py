@@ -28,6 +28,14 @@ TTA preset or with the heat maps of explain_batch.
 index DIR/neighbours.npz holds (on the device from load() on), and every result gains `neighbours` (K dicts {file,
 label, sq_distance}, nearest first), `knn_label`, `knn_agreement` and `kth_sq_distance`.  No prediction or probability
 changes.  The same combinations are refused as for novelty.
+
+`Predictor(dir, conformal=ALPHA)` (not in the reference) also says which classes cannot be ruled out
+(predict/conformal.py): the reported probability rows -- after the views' mean and the calibration, as DIR/conformal.json
+says they were fitted -- go through `nn.conformal_sets` at the thresholds the stored scores give for ALPHA, and every
+result gains `prediction_set` (labels, most probable first), `set_size` and `conformal_alpha`.  Over pictures
+exchangeable with the fitted split the set holds the true label with probability at least 1 - ALPHA.  A TTA preset or
+calibration setting other than the fitted one is refused; so are the heat maps of explain_batch.  No prediction or
+probability changes.
 """
 from __future__ import annotations
 
@@ -44,7 +52,8 @@ logger = get_logger(__name__)
 
 
 class Predictor:
-    def __init__(self, learnings_dir, tta=None, calibrated: bool = False, novelty: bool = False, neighbours=None):
+    def __init__(self, learnings_dir, tta=None, calibrated: bool = False, novelty: bool = False, neighbours=None,
+                 conformal=None):
         from .tta import PRESETS
         if tta is not None and tta not in PRESETS:
             raise ValueError(f"unknown TTA preset {tta!r}: one of {', '.join(PRESETS)}")
@@ -58,6 +67,9 @@ class Predictor:
             if tta is not None:
                 raise ValueError("nearest neighbours cannot be combined with a TTA preset (the features of several "
                                  "views are not one point)")
+        if conformal is not None:
+            from .conformal import alpha_fraction
+            alpha_fraction(conformal)
         self.learnings_dir = Path(learnings_dir)
         self.tta = tta
         self.calibrated = bool(calibrated)
@@ -68,6 +80,9 @@ class Predictor:
         self.neighbours = None if neighbours is None else int(neighbours)   # K, or None
         self.neighbours_data = None   # what neighbours.json and neighbours.npz hold, with neighbours=K after load()
         self._neighbours_dev = None   # the index's prepared features on the model's device
+        self.conformal = conformal    # alpha (a number or its decimal string), or None
+        self.conformal_data = None    # what conformal.json and conformal.npz hold, with conformal=ALPHA after load()
+        self._conformal_qhat = None   # the thresholds [C] for alpha, float64 host array
         self.model_loader = None
         self._initialized = False
         self._codec = None   # DeviceDecoder of the pooled batch path
@@ -87,8 +102,13 @@ class Predictor:
         if self.neighbours is not None:   # before the model: a missing file fails at once
             from . import neighbours
             neighbours.require_files(self.learnings_dir)
+        if self.conformal is not None:   # before the model: a missing file or another pipeline fails at once
+            from . import conformal
+            conformal.check_pipeline(conformal.load(self.learnings_dir), self.tta, self.calibrated)
         self.model_loader = ModelLoader(self.learnings_dir)
         self.model_loader.load()
+        if self.conformal is not None:
+            self._load_conformal()
         if self.novelty:
             self._load_novelty()
         if self.neighbours is not None:
@@ -137,6 +157,27 @@ class Predictor:
         self.neighbours_data = data
         self._neighbours_dev = torch.from_numpy(data["features"]).to(model.device)
 
+    def _load_conformal(self) -> None:
+        from . import conformal
+        labels = self.model_loader.labels
+        if len(labels) > conformal.MAX_CLASSES:
+            raise ValueError(f"conformal prediction takes 1..{conformal.MAX_CLASSES} classes, this model has "
+                             f"{len(labels)}")
+        data = conformal.load(self.learnings_dir, labels=labels)
+        self.conformal_data = data
+        self._conformal_qhat = conformal.thresholds(data["scores"], data["score_labels"], self.conformal,
+                                                    data["class_conditional"], len(labels))
+
+    def _conformal_rows(self, probs: np.ndarray) -> List[Dict[str, Any]]:
+        """The three conformal keys of every reported probability row [n,C] (host)."""
+        from . import conformal
+        labels = self.model_loader.labels
+        member, size, _stats = conformal.prediction_sets(probs, self._conformal_qhat,
+                                                         conformal.settings_of(self.conformal_data))
+        return [{"prediction_set": [labels[j] for j in row], "set_size": int(size[i]),
+                 "conformal_alpha": float(self.conformal)}
+                for i, row in enumerate(conformal.ordered_sets(probs, member))]
+
     def _neighbour_rows(self, g) -> List[Dict[str, Any]]:
         """The four neighbour keys of every row of the pooled features g [n,D] (device)."""
         from .. import nn
@@ -168,10 +209,11 @@ class Predictor:
                 out[k] = res[j]
         return out
 
-    def _result(self, path, original, probs, agreement=None, top=None, nov=None, nb=None) -> Dict[str, Any]:
+    def _result(self, path, original, probs, agreement=None, top=None, nov=None, nb=None,
+                cs=None) -> Dict[str, Any]:
         """top: the predicted class where it is not to be taken from `probs` (calibrated rows: two probabilities that
         differ may round to one float at a high temperature, and the prediction is the uncalibrated row's).  nov:
-        (novelty score, row of M nearest) of this picture.  nb: its four neighbour keys."""
+        (novelty score, row of M nearest) of this picture.  nb: its four neighbour keys.  cs: its three conformal keys."""
         labels = self.model_loader.labels
         top = int(np.argmax(probs)) if top is None else int(top)
         result = {"image_path": path, "top_prediction": labels[top], "confidence": float(probs[top]),
@@ -185,6 +227,8 @@ class Predictor:
                           nearest_class=labels[self.novelty_data["present"][int(nov[1])]])
         if nb is not None:
             result.update(nb)
+        if cs is not None:
+            result.update(cs)
         return result
 
     def _calibrate(self, probs):
@@ -198,7 +242,13 @@ class Predictor:
         images at a time; the view agreement [n] (agree / v) with a TTA preset set, None without one; and with
         calibrated=True the predictions [n] (the rows are then the calibrated ones), None without; and with
         novelty=True the pairs [n,2] (novelty score, nearest row of M) from the features of the same passes, None
-        without; and with neighbours=K the rows' neighbour keys (_neighbour_rows) from those features, None without."""
+        without; and with neighbours=K the rows' neighbour keys (_neighbour_rows) from those features, None without;
+        and with conformal=ALPHA the rows' conformal keys (_conformal_rows) from the returned rows, None without."""
+        rows, agreement, top, nov, nb = self._probability_rows(x, step)
+        return rows, agreement, top, nov, nb, None if self.conformal is None else self._conformal_rows(rows)
+
+    def _probability_rows(self, x, step: int):
+        """_predict_inputs without the conformal keys."""
         import torch
         model = self.model_loader.model
         agreement = nov = nb = None
@@ -236,12 +286,13 @@ class Predictor:
             return out, agreement, top, nov, nb
         return probs.cpu().numpy(), agreement, None, nov, nb
 
-    def _results(self, paths, kept, natives, probs, agreement, top, nov=None, nb=None) -> List[Dict[str, Any]]:
-        """One result per kept file: row j of probs (agreement, top, nov, nb: [n] or None) belongs to
+    def _results(self, paths, kept, natives, probs, agreement, top, nov=None, nb=None,
+                 cs=None) -> List[Dict[str, Any]]:
+        """One result per kept file: row j of probs (agreement, top, nov, nb, cs: [n] or None) belongs to
         paths[kept[j]]."""
         return [self._result(paths[k], natives[k], probs[j], None if agreement is None else agreement[j],
                              None if top is None else top[j], None if nov is None else nov[j],
-                             None if nb is None else nb[j])
+                             None if nb is None else nb[j], None if cs is None else cs[j])
                 for j, k in enumerate(kept)]
 
     def predict_single(self, image_path, use_transform: bool = False) -> Dict[str, Any]:
@@ -359,7 +410,7 @@ class Predictor:
         paths = [Path(p) for p in image_paths]
         rows, indices = [], []
         for kept, x, _natives, step in self._model_inputs(paths, keep_native=False):
-            rows.append(self._predict_inputs(x, step)[0])
+            rows.append(self._probability_rows(x, step)[0])
             indices += kept
         if not rows:
             return np.zeros((0, self.model_loader.num_classes), np.float32), []
@@ -418,6 +469,8 @@ class Predictor:
             raise ValueError("the novelty score cannot be combined with class activation maps")
         if self.neighbours is not None:
             raise ValueError("nearest neighbours cannot be combined with class activation maps")
+        if self.conformal is not None:
+            raise ValueError("prediction sets cannot be combined with class activation maps")
         if getattr(self.model_loader.model, "class_activation_maps", None) is None:
             raise ValueError("class activation maps need a leaf_cnn model (GlobalAveragePooling2D -> Dense head)")
         paths = [Path(p) for p in image_paths]
