@@ -493,6 +493,10 @@ int lf_jpeg_entropy_items_u8(const void* coef_base, const lf_jpeg_item* items, u
  *   whole MCUs -> coef (the layout above, still quantised; coef_cap in int16 elements) and qtab128 (the file's
  *   luminance and chrominance tables, 64 uint16 each, row-major).  Returns 0; 1 when the file is of a kind it
  *   does not cover (progressive, other samplings, grey, ragged size: decode with libjpeg); -1 when it is corrupt.
+ *   Only YCbCr files are taken (lf_jpeg_idct_rgb_u8 always converts): a file libjpeg reads as RGB — no JFIF APP0
+ *   and an Adobe APP14 with transform 0, or neither marker and the component ids 'R', 'G', 'B' — returns 1, from
+ *   this entry and from lf_jpeg_scan_prepare and the _ragged twins alike.  A Huffman table with an all-ones code
+ *   is corrupt (-1), as it is to libjpeg.
  * lf_jpeg_idct_rgb_u8 (GPU): dequantisation + jidctint islow IDCT + h2v2 fancy upsampling + YCbCr->RGB for N
  *   images of one size; image i's coefficients at coef + i*coef_stride bytes, its tables at qtab + i*qtab_stride. */
 int lf_jpeg_read_file(const uint8_t* data, size_t len, int16_t* coef, size_t coef_cap, uint16_t* qtab128,

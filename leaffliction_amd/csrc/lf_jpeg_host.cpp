@@ -297,9 +297,10 @@ static uint8_t* write_headers(uint8_t* p, int h, int w, int quality) {
 // Reading: markers + Huffman decoding of a baseline 4:2:0 file into the same coefficient layout the encoder
 // uses ([MCU][Y00 Y01 Y10 Y11 Cb Cr][64], zigzag order, still quantised) plus the file's two quantisation
 // tables; dequantisation, IDCT, upsampling and colour conversion are lf_jpeg_idct_rgb_u8's (GPU).
-// Everything this does not cover (progressive, other samplings, 12-bit, arithmetic coding; sizes that are not whole
-// MCUs for the plain entry points, widths under 5 for the _ragged ones) returns 1 and the caller decodes with libjpeg
-// as before.
+// Only YCbCr files are taken, by libjpeg's own rule for the colour space of a three-component file (JFIF APP0, Adobe
+// APP14 and its transform byte, component ids: is_ycbcr below).  Everything this does not cover (progressive, other
+// samplings, 12-bit, arithmetic coding, files stored as RGB; sizes that are not whole MCUs for the plain entry points,
+// widths under 5 for the _ragged ones) returns 1 and the caller decodes with libjpeg as before.
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -327,6 +328,8 @@ bool build_decoder(DHuff& t, const uint8_t* bits, const uint8_t* vals, int nvals
             }
         }
         t.maxcode[l] = bits[l - 1] ? code - 1 : -1;
+        // no code may be all ones (jdhuff.c jpeg_make_d_derived_tbl: JERR_BAD_HUFF_TABLE, Pillow's "broken data stream")
+        if (code >= (1 << l)) return false;
         code <<= 1;
     }
     t.maxcode[17] = 0x7fffffff;
@@ -477,10 +480,23 @@ struct Parsed {
     int comp_id[3] = {0, 0, 0}, comp_q[3] = {0, 0, 0};
     int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
     bool have_sof = false;
+    bool jfif = false, adobe = false;   // a JFIF APP0 / an Adobe APP14 was seen
+    int adobe_transform = 0;            // the Adobe marker's colour transform: 0 none (RGB), 1 YCbCr, 2 YCCK
     size_t scan = 0;   // offset of the first entropy-coded byte
 };
 
+// The colour space of a three-component file as libjpeg decides it (jdapimin.c default_decompress_parms): JFIF seen:
+// YCbCr; else Adobe seen: transform 0 is RGB, 1 is YCbCr (anything else: a warning, and YCbCr); else by the component
+// ids: 1, 2, 3 is YCbCr, 'R', 'G', 'B' is RGB, anything else YCbCr.
+bool is_ycbcr(const Parsed& P) {
+    if (P.jfif) return true;
+    if (P.adobe) return P.adobe_transform != 0;
+    return !(P.comp_id[0] == 'R' && P.comp_id[1] == 'G' && P.comp_id[2] == 'B');
+}
+
 // 0: `out.scan` is where the scan's bytes start; 1: a kind of file this path does not cover; -1: corrupt.
+// Only YCbCr files are taken: the GPU back end always converts YCbCr to RGB, so a file libjpeg reads as RGB (is_ycbcr)
+// is libjpeg's.
 // ragged: any height and any width from 5 up instead of whole MCUs only (the scan then holds ceil(h/16) * ceil(w/16)
 // MCUs, libjpeg's dummy blocks included; at chroma widths of 1 and 2 libjpeg-turbo's upsampler does something the GPU
 // back end does not restate, so those stay libjpeg's).
@@ -545,6 +561,13 @@ int parse_until_scan(const uint8_t* data, size_t len, Parsed& P, bool ragged) {
         } else if (m == 0xDD) {
             if (n < 2) return -1;
             P.restart = (int)be16(q);
+        } else if (m == 0xE0) {   // jdmarker.c examine_app0: the identifier and the 14 bytes of a JFIF header
+            if (n >= 14 && memcmp(q, "JFIF\0", 5) == 0) P.jfif = true;
+        } else if (m == 0xEE) {   // examine_app14: "Adobe", version, two flag words, the transform
+            if (n >= 12 && memcmp(q, "Adobe", 5) == 0) {
+                P.adobe = true;
+                P.adobe_transform = q[11];
+            }
         } else if (m == 0xDA) {
             if (!P.have_sof || n < 10 || q[0] != 3) return P.have_sof ? 1 : -1;
             for (int c = 0; c < 3; ++c) {
@@ -558,6 +581,7 @@ int parse_until_scan(const uint8_t* data, size_t len, Parsed& P, bool ragged) {
             if (q[7] != 0 || q[8] != 63) return 1;
             for (int k = 0; k < 64; ++k)
                 if (P.qt[P.comp_q[2]][k] != P.qt[P.comp_q[1]][k]) return 1;   // Cb and Cr with different tables
+            if (!is_ycbcr(P)) return 1;   // stored as RGB: no colour conversion, libjpeg's business
             P.scan = pos + seg;
             return 0;
         }
