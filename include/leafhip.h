@@ -1374,6 +1374,65 @@ size_t lf_knn_topk_workspace(int nq, int ng, int k, int segments);
 int lf_knn_topk_f32(const float* q, const float* g, int nq, int ng, int d, int k, const int32_t* exclude,
                     int segments, float* d2, int32_t* idx, void* ws, size_t ws_bytes, lf_stream_t stream);
 
+/* ---- Embedding map: exact (dense) t-SNE of feature rows, and the marks of its chart ---- */
+/* van der Maaten & Hinton's t-SNE without approximation and without random numbers: one feature matrix gives one map.
+ *
+ * Affinities (lf_tsne_perplexity_f32).  Row i of d2 f32 [n][n] (squared distances), the entry j = i left out BY INDEX
+ * (its value is never read into the rule), d_ij = (double)d2[i][j] - (double)min_{k != i} d2[i][k]:
+ *   p_{j|i} = exp(-beta_i d_ij) / S,  S = sum_{k != i} exp(-beta_i d_ik),  p_{i|i} = 0, stored as f32.
+ *   beta_i: bisection on the row's entropy H = ln S + beta sum(d e) / S against ln(perplexity).  beta = 1, lo = 0,
+ *   hi = inf.  One evaluation computes H at beta; it stops when |H - ln perplexity| <= 1e-5 or when it was the 100th.
+ *   Otherwise, H too large: lo = beta, and beta doubles while hi is inf, else moves to (lo + hi) / 2; H too small:
+ *   hi = beta and beta moves to (lo + hi) / 2.  The beta of the last evaluation is used and reported (beta f64 [n]),
+ *   with the number of evaluations (evals i32 [n]).  All of it in float64, exp included.
+ *   A row's sums: thread t of 256 adds its entries j = t, t + 256, ... in order, the 64 lanes of a wave fold by
+ *   __shfl_down 32, 16, ..., 1, the four waves add as ((w0 + w1) + w2) + w3.  One workgroup per row; the row is read
+ *   once into LDS, so p may be d2 itself (in place).
+ * Symmetric P (lf_tsne_symmetrize_f32).  P_ij = (p_{j|i} + p_{i|j}) / (float)(2n): one f32 addition, one correctly
+ *   rounded f32 division; in place, by 32 x 32 tiles, the workgroup of tile (a, b), a <= b, writing (b, a) as well
+ *   from LDS.  The result is exactly symmetric.
+ * Forces at a map y f32 [n][2] (lf_tsne_forces_f32), w_ij = 1 / (1 + |y_i - y_j|^2) for j != i (by index):
+ *   attr_i = sum_j P_ij w_ij (y_i - y_j)      f32 [n][2]
+ *   rep_i  = sum_j w_ij^2 (y_i - y_j)         f32 [n][2]
+ *   z_i    = sum_j w_ij                       f64 [n]
+ *   kl (f64 [n][2], or null: no logarithm is taken): a_i = sum_{j: P_ij > 0} P_ij ln P_ij, b_i = sum_{..} P_ij ln w_ij.
+ *   Per pair, all in f64 from the f32 operands: the differences (exact), d2 = fma(dy, dy, dx * dx),
+ *   w = 1 / (1 + d2); the terms fma(P * w, dx, .), fma(w * w, dx, .), w, fma(P, ln P, .) and fma(P, -log1p(d2), .)
+ *   (ln w, taken so that it keeps its digits where w is close to 1) add in f64.  attr and
+ *   rep are rounded to f32 once, when a row's sums are stored.
+ *   Order, a function of n alone: a wave owns row i; lane l adds its entries j = 256 t + 4 l + e (e = 0 .. 3 inside
+ *   t = 0, 1, ...) in ascending order, the lanes fold by __shfl_down 32, 16, ..., 1.  No atomics; the same call gives
+ *   the same bits.  P is streamed once, the y_j come from LDS in chunks of 4096 points, nothing of size n^2 is
+ *   written.
+ *   With Z = sum_i z_i: KL = sum_i a_i - sum_i b_i + ln Z * sum P.
+ * Step (lf_tsne_step_f32), one workgroup of 1024 threads.  Z = sum z_i (f64: thread t adds i = t, t + 1024, ... in
+ *   order, __shfl_down fold, the 16 waves from the left).  Per coordinate, in f64 from the f32 state:
+ *   grad = 4 (e attr - rep / Z);  gain <- (grad > 0) != (vel > 0) ? gain + 0.2f : gain * 0.8f, then max(gain, 0.01f),
+ *   both in f32;  vel <- (float)(mu vel - eta gain grad);  t = y + vel (f64);  y <- (float)(t - mean_c), mean_c the
+ *   f64 sum of the column's t (same order as Z) divided by n.  With kl (the forces' pieces) and kl_out f64 [1]:
+ *   kl_out[0] = sum a - sum b + ln Z * sum_p, sum_p the caller's f64 sum of P.
+ * Refused before any launch: null buffers, n outside 2..lf_tsne_max_points() = 16384 (symmetrize: 1..), a perplexity
+ * that is not finite or below 1, p / y not 16-byte aligned, kl without kl_out.
+ *
+ * lf_scatter_points_u8: m round marks into img u8 [h][w][3] in place, all integer.  xy i32 [m][2] = (x, y) pixel
+ * centres, colour i32 [m] an index into palette u8 [colours][3], radius 0..64, owner i32 [h][w] workspace (zeroed by
+ * the call).  Every pixel inside the picture with dx^2 + dy^2 <= radius^2 of mark k takes atomicMax(owner, k + 1)
+ * (an integer atomic: the outcome does not depend on the order, the mark with the highest index wins); then owned
+ * pixels get their mark's palette colour and all others stay.  A mark whose colour lies outside the palette takes no
+ * pixel.  Centres may lie anywhere (the sums are 64-bit); nothing is written outside the picture.  Refused before any
+ * launch: null buffers, m outside 1..2^20, radius outside 0..64, colours, h or w below 1, h * w above 2^28. */
+int lf_tsne_max_points(void);
+int lf_tsne_perplexity_f32(const float* d2, int n, double perplexity, float* p, double* beta, int32_t* evals,
+                           lf_stream_t stream);
+int lf_tsne_symmetrize_f32(float* p, int n, lf_stream_t stream);
+int lf_tsne_forces_f32(const float* p, const float* y, int n, float* attr, float* rep, double* z, double* kl,
+                       lf_stream_t stream);
+int lf_tsne_step_f32(float* y, float* vel, float* gain, const float* attr, const float* rep, const double* z, int n,
+                     double exaggeration, double eta, double momentum, const double* kl, double sum_p,
+                     double* kl_out, lf_stream_t stream);
+int lf_scatter_points_u8(const int32_t* xy, const int32_t* colour, int m, int radius, const uint8_t* palette,
+                         int colours, uint8_t* img, int h, int w, int32_t* owner, lf_stream_t stream);
+
 /* ---- Near-duplicate search: 128-bit difference hashes and their all-pairs Hamming search ---- */
 /* Integer and exact throughout; no float appears.
  *

@@ -169,6 +169,12 @@ SIGNATURES = {
     "lf_knn_segments": [c_int, c_int],
     "lf_knn_topk_workspace": [c_int, c_int, c_int, c_int],
     "lf_knn_topk_f32": [P, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P],
+    "lf_tsne_max_points": [],
+    "lf_tsne_perplexity_f32": [P, c_int, c_double, P, P, P, P],
+    "lf_tsne_symmetrize_f32": [P, c_int, P],
+    "lf_tsne_forces_f32": [P, P, c_int, P, P, P, P, P],
+    "lf_tsne_step_f32": [P, P, P, P, P, P, c_int, c_double, c_double, c_double, P, c_double, P, P],
+    "lf_scatter_points_u8": [P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P],
     "lf_dhash128_u8": [P, P, c_int, c_int, c_int, c_int, P],
     "lf_hamming_pairs_tile": [],
     "lf_hamming_pairs_rows": [],

@@ -54,16 +54,17 @@ def validate_inputs(args):
     return learnings_dir, manifest
 
 
-def build_index(predictor, paths, names, split=None):
+def build_index(predictor, paths, names, split=None, with_predicted: bool = False):
     """The index of the predictor's pooled features of `paths` (label names `names`): {"features" f32 [n,D] prepared,
     "labels" int32 [n], "files", "splits"} on the host, and the number of files skipped for a label the model does not
-    know.  One warning per unreadable file and per unknown label."""
+    know.  One warning per unreadable file and per unknown label.  with_predicted: the index also holds "predicted"
+    int32 [n], the class of each row's largest probability (cli.embedding colours its map by it)."""
     import numpy as np
 
     from ..predict import neighbours
     index = {name: j for j, name in enumerate(predictor.model_loader.labels)}
-    rows, own, files, seen, skipped = [], [], [], set(), 0
-    for kept, _probs, g in predictor.feature_chunks(paths):
+    rows, own, files, seen, skipped, predicted = [], [], [], set(), 0, []
+    for kept, probs, g in predictor.feature_chunks(paths):
         seen.update(kept)
         known = [j for j, k in enumerate(kept) if names[k] in index]
         for j, k in enumerate(kept):
@@ -72,14 +73,19 @@ def build_index(predictor, paths, names, split=None):
                 logger.warning("Skipping %s: the model does not know the label %r", paths[k], names[k])
         if known:
             rows.append(neighbours.prepare(g)[known].cpu().numpy())
+            if with_predicted:
+                predicted.append(probs.argmax(dim=1)[known].cpu().numpy())
             own += [index[names[kept[j]]] for j in known]
             files += [str(paths[kept[j]]) for j in known]
     for k in sorted(set(range(len(paths))) - seen):
         logger.warning("Skipping %s: could not be read", paths[k])
     if not rows:
         raise ValueError("No image of the split with a label the model knows could be read")
-    return {"features": np.ascontiguousarray(np.concatenate(rows), dtype=np.float32),
-            "labels": np.asarray(own, np.int32), "files": files, "splits": [str(split)] * len(files)}, skipped
+    index = {"features": np.ascontiguousarray(np.concatenate(rows), dtype=np.float32),
+             "labels": np.asarray(own, np.int32), "files": files, "splits": [str(split)] * len(files)}
+    if with_predicted:
+        index["predicted"] = np.concatenate(predicted).astype(np.int32)
+    return index, skipped
 
 
 def audit_index(index, label_names, k: int, device):

@@ -1031,6 +1031,116 @@ def knn_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, exclude: Opti
     return d2, idx
 
 
+TSNE_MAX_POINTS = 16384    # lf_tsne_max_points(): P is 1 GiB there
+
+
+def _tsne_tensor(who: str, t: torch.Tensor, dtype, shape, device=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.LeafHipError(f"{who}: expected a CUDA(HIP) tensor — there is no CPU path")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{who}: a contiguous {dtype} {list(shape)} tensor expected, got {t.dtype} {tuple(t.shape)}"
+                         f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{who}: expected on {device}, got {t.device}")
+    return t
+
+
+def _tsne_square(who: str, t: torch.Tensor, least: int) -> int:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.LeafHipError(f"{who}: expected a CUDA(HIP) tensor — there is no CPU path")
+    if t.dim() != 2 or t.shape[0] != t.shape[1] or not least <= t.shape[0] <= TSNE_MAX_POINTS:
+        raise ValueError(f"{who}: [n,n] with {least} <= n <= {TSNE_MAX_POINTS} expected, got {tuple(t.shape)}")
+    n = int(t.shape[0])
+    _tsne_tensor(who, t, _F32, (n, n))
+    if t.data_ptr() % 16:
+        raise ValueError(f"{who}: must start on a 16-byte boundary")
+    return n
+
+
+def tsne_perplexity(d2: torch.Tensor, perplexity: float, out: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The conditional affinity rows of t-SNE (lf_tsne_perplexity_f32; the rule: include/leafhip.h "Embedding map"):
+    d2 f32 [n,n] squared distances -> (p f32 [n,n] with p[i,i] = 0, beta f64 [n], evals int32 [n]).  out: where p
+    goes; None or d2 itself: in place, into d2.  No sync."""
+    n = _tsne_square("tsne_perplexity.d2", d2, 2)
+    perplexity = float(perplexity)
+    if not (perplexity >= 1.0 and perplexity < float("inf")):
+        raise ValueError(f"tsne_perplexity: perplexity={perplexity} (finite, >= 1)")
+    p = d2 if out is None else out
+    if p is not d2:
+        _tsne_tensor("tsne_perplexity.out", p, _F32, (n, n), d2.device)
+    beta = torch.empty((n,), dtype=torch.float64, device=d2.device)
+    evals = torch.empty((n,), dtype=torch.int32, device=d2.device)
+    _lib.call("lf_tsne_perplexity_f32", d2.data_ptr(), n, perplexity, p.data_ptr(), beta.data_ptr(), evals.data_ptr(),
+              _stream())
+    return p, beta, evals
+
+
+def tsne_symmetrize(p: torch.Tensor) -> torch.Tensor:
+    """P = (p + p^T) / 2n in f32, in place (lf_tsne_symmetrize_f32): p f32 [n,n].  Returns p.  No sync."""
+    n = _tsne_square("tsne_symmetrize.p", p, 1)
+    _lib.call("lf_tsne_symmetrize_f32", p.data_ptr(), n, _stream())
+    return p
+
+
+def tsne_forces(p: torch.Tensor, y: torch.Tensor, want_kl: bool = False, out: Optional[dict] = None) -> dict:
+    """The all-pairs sums of one t-SNE iteration (lf_tsne_forces_f32): P f32 [n,n] and the map y f32 [n,2] ->
+    {"attr" f32 [n,2], "rep" f32 [n,2], "z" f64 [n], "kl" f64 [n,2] (want_kl; else None)}.  out: such a dict to
+    write into (the loop reuses one).  P is read once; nothing of size n^2 is written.  No sync."""
+    n = _tsne_square("tsne_forces.p", p, 2)
+    dev = p.device
+    _tsne_tensor("tsne_forces.y", y, _F32, (n, 2), dev)
+    if y.data_ptr() % 16:
+        raise ValueError("tsne_forces.y: must start on a 16-byte boundary")
+    if out is None:
+        out = {"attr": torch.empty((n, 2), dtype=_F32, device=dev), "rep": torch.empty((n, 2), dtype=_F32, device=dev),
+               "z": torch.empty((n,), dtype=torch.float64, device=dev), "kl": None}
+    res = dict(out)
+    _tsne_tensor("tsne_forces.attr", res["attr"], _F32, (n, 2), dev)
+    _tsne_tensor("tsne_forces.rep", res["rep"], _F32, (n, 2), dev)
+    _tsne_tensor("tsne_forces.z", res["z"], torch.float64, (n,), dev)
+    if want_kl:
+        if res.get("kl") is None:
+            res["kl"] = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        _tsne_tensor("tsne_forces.kl", res["kl"], torch.float64, (n, 2), dev)
+    else:
+        res["kl"] = None
+    _lib.call("lf_tsne_forces_f32", p.data_ptr(), y.data_ptr(), n, res["attr"].data_ptr(), res["rep"].data_ptr(),
+              res["z"].data_ptr(), _ptr(res["kl"]), _stream())
+    return res
+
+
+def tsne_step(y: torch.Tensor, vel: torch.Tensor, gain: torch.Tensor, forces: dict, exaggeration: float, eta: float,
+              momentum: float, sum_p: Optional[float] = None, kl_out: Optional[torch.Tensor] = None
+              ) -> Optional[torch.Tensor]:
+    """One gradient step of t-SNE with gains, momentum and recentring, in place on y, vel, gain f32 [n,2]
+    (lf_tsne_step_f32), from tsne_forces' sums AT THIS y.  When the forces carry "kl" and sum_p (the float64 sum of
+    P) is given, the Kullback-Leibler divergence at the y the forces were taken at goes to kl_out f64 [1] (made when
+    None) and is returned, on the device.  One workgroup; no sync."""
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("tsne_step.y: a float32 [n,2] tensor expected")
+    n = int(y.shape[0])
+    if not 2 <= n <= TSNE_MAX_POINTS:
+        raise ValueError(f"tsne_step: n={n} (2..{TSNE_MAX_POINTS})")
+    _tsne_tensor("tsne_step.y", y, _F32, (n, 2))
+    dev = y.device
+    for name, t in (("vel", vel), ("gain", gain), ("attr", forces["attr"]), ("rep", forces["rep"])):
+        _tsne_tensor(f"tsne_step.{name}", t, _F32, (n, 2), dev)
+    _tsne_tensor("tsne_step.z", forces["z"], torch.float64, (n,), dev)
+    kl = forces.get("kl") if sum_p is not None else None
+    if kl is not None:
+        _tsne_tensor("tsne_step.kl", kl, torch.float64, (n, 2), dev)
+        if kl_out is None:
+            kl_out = torch.empty((1,), dtype=torch.float64, device=dev)
+        _tsne_tensor("tsne_step.kl_out", kl_out, torch.float64, (1,), dev)
+    else:
+        kl_out = None
+    _lib.call("lf_tsne_step_f32", y.data_ptr(), vel.data_ptr(), gain.data_ptr(), forces["attr"].data_ptr(),
+              forces["rep"].data_ptr(), forces["z"].data_ptr(), n, float(exaggeration), float(eta), float(momentum),
+              _ptr(kl), 0.0 if sum_p is None else float(sum_p), _ptr(kl_out), _stream())
+    return kl_out
+
+
 DHASH_VARIANTS = (1, 2, 4, 8)
 DHASH_MIN_SIDE, DHASH_MAX_SIDE = 9, 4096
 

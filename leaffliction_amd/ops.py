@@ -1373,6 +1373,42 @@ def draw_text_u8(img: torch.Tensor, texts) -> torch.Tensor:
     return img
 
 
+SCATTER_MAX_RADIUS = 64
+
+
+def scatter_points_u8(img: torch.Tensor, xy: torch.Tensor, colour: torch.Tensor, radius: int, palette: torch.Tensor,
+                      owner: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Round marks drawn in place into img [H,W,3] uint8 (lf_scatter_points_u8; the rule: include/leafhip.h): xy int32
+    [m,2] pixel centres (x, y), colour int32 [m] indices into palette uint8 [c,3], every pixel within `radius` of a
+    centre (dx^2 + dy^2 <= radius^2) taking the colour of the mark with the highest index that covers it.  Marks are
+    clipped to the picture; a colour index outside the palette paints nothing.  owner: int32 [H,W] workspace (made
+    when None).  Returns img.  No sync."""
+    _chk(img, _U8, "scatter_points.img", 3)
+    h, w, ch = img.shape
+    if ch != 3 or h == 0 or w == 0:
+        raise ValueError(f"scatter_points.img: expected [H,W,3] with H, W > 0, got {tuple(img.shape)}")
+    _chk(xy, _I32, "scatter_points.xy", 2)
+    _chk(colour, _I32, "scatter_points.colour", 1)
+    _chk(palette, _U8, "scatter_points.palette", 2)
+    m = int(xy.shape[0])
+    if m == 0 or xy.shape[1] != 2 or colour.shape[0] != m or palette.shape[1] != 3 or palette.shape[0] == 0:
+        raise ValueError(f"scatter_points: xy [m,2], colour [m] with m > 0 and palette [c,3] with c > 0 expected, got "
+                         f"{tuple(xy.shape)}, {tuple(colour.shape)}, {tuple(palette.shape)}")
+    radius = int(radius)
+    if not 0 <= radius <= SCATTER_MAX_RADIUS:
+        raise ValueError(f"scatter_points: radius={radius} (0..{SCATTER_MAX_RADIUS})")
+    if owner is None:
+        owner = torch.empty((h, w), dtype=_I32, device=img.device)
+    _chk(owner, _I32, "scatter_points.owner", 2)
+    if tuple(owner.shape) != (h, w):
+        raise ValueError(f"scatter_points.owner: expected [{h},{w}], got {tuple(owner.shape)}")
+    if any(t.device != img.device for t in (xy, colour, palette, owner)):
+        raise ValueError("scatter_points: all tensors must be on one device")
+    _lib.call("lf_scatter_points_u8", xy.data_ptr(), colour.data_ptr(), m, radius, palette.data_ptr(),
+              int(palette.shape[0]), img.data_ptr(), int(h), int(w), owner.data_ptr(), _stream())
+    return img
+
+
 @functools.lru_cache(maxsize=256)
 def canvas_axis_table(src: int, dst: int) -> np.ndarray:
     """lf_canvas_tiles_u8's table of one axis, int32 [dst, 2] = {first tap i, weight k of the second tap (of 2048)}:
